@@ -2,7 +2,7 @@
 """Bench of the hot path: bulk Aho-Corasick scan (BASELINE.json metric: input GB/s scanned,
 1k-keyword dictionary, bit-exact match set).
 
-  python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+  python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the scan over one rank's shard, text already resident in HBM, match records
@@ -14,15 +14,23 @@ left resident (unsorted) on the owning GPU.  Workloads (BASELINE.json `configs`,
   --config 5   uint32 symbols (vocabulary 32,768), 10,000 keywords, 2^30 tokens = 4 GiB per GPU
 
 Weak scaling: every rank owns its share of one stream, scanned with a warm-up halo >= lmax - 1
-symbols; no collective inside the timed region.  The gather of records to rank 0 (+ canonical
-order) is timed separately and reported as e2e.  `--gpus N` without a launcher (WORLD_SIZE unset)
+symbols; no collective inside the timed region.  `--gpus N` without a launcher (WORLD_SIZE unset)
 starts its N workers itself, as fresh child processes, before this process touches a GPU.
 Prints ONE JSON line on rank 0.
 
-The default line (config 2, one GPU) also carries, under "other_configs", a short run of configs 3
-and 5 at their full sizes after the headline's timed region (a few steps each, same measurement):
-the top-level metric / value / config / roofline / cpu_baseline are config 2's and are not touched
-by it.  `--no-other-configs` leaves them out.
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, config).  `--full` adds what takes
+runs or checks of its own: the record set checked against the oracle's known answer, `roofline`
+(HIP events around a sample of the timed launches), the e2e legs (scan + canonical order + gather
+of records to rank 0, through torch.distributed and through the C ABI, timed separately),
+`cpu_baseline`, and, on the default line (config 2, one GPU), "other_configs": a short run of
+configs 3 and 5 at their full sizes after the headline's timed region (a few steps each, same
+measurement; the top-level fields stay config 2's).  `--no-other-configs`, `--no-cpu-baseline`,
+`--no-multi-c-abi` leave those parts of a `--full` line out.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last step computed on rank 0 (see
+dump_outputs): the inputs are generated from fixed seeds, so two builds can be compared output
+for output.
 """
 import argparse
 import json
@@ -51,6 +59,10 @@ KERNELS = {1: "scan_dense_kernel", 2: "scan_csr_kernel", 3: "scan_sparse_kernel"
 FOLLOWERS = {1: "expand_items_once_kernel", 4: "expand_hits_kernel", 5: "close_holes_kernel"}
 VOCAB = 32768
 KNOWN_ANSWERS = os.path.join(ROOT, "tests", "golden", "known_answers.json")
+# --dump-outputs: at most this many records (3 float64 columns: 48 MB of the 64 MB a dump may take);
+# larger record sets are sampled by 4096-symbol block with this seed
+DUMP_MAX_RECORDS = 2_000_000
+DUMP_SEED = 2024
 
 
 def parse():
@@ -63,6 +75,10 @@ def parse():
     ap.add_argument("--mib", type=int, default=None, help="override the config's text MiB per GPU")
     ap.add_argument("--prewarm-ms", type=int, default=300,
                     help="untimed scans before the W warm-up steps until the device has been busy this long (clock ramp), 0 = none")
+    ap.add_argument("--full", action="store_true",
+                    help="also the known-answer check, roofline, e2e legs, CPU baseline and (default line) configs 3 and 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step (rank 0) as DIR/records.npy and DIR/count.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="default line only: leave out the short runs of configs 3 and 5")
     ap.add_argument("--cpu-sample-mib", type=int, default=None)
@@ -113,9 +129,10 @@ def known_answer(config, n_symbols_rank0):
     return best
 
 
-def measure(ctx, config, cfg, steps, warmup, prewarm_ms, as_configured, want_e2e=True):
-    """One workload on this rank's GPU: dictionary, plan, text, timed steps, record-set check.
-    Returns (result dict for rank 0's line, objects the CPU baseline needs)."""
+def measure(ctx, config, cfg, steps, warmup, prewarm_ms, as_configured, full, dump_dir=None):
+    """One workload on this rank's GPU: dictionary, plan, text, timed steps; with `full` also the
+    record-set check, roofline and e2e legs.  Returns (result dict for rank 0's line, objects the
+    CPU baseline needs)."""
     acm, torch, dist = ctx["acm"], ctx["torch"], ctx["dist"]
     rank, world, dev, rehearsal = ctx["rank"], ctx["world"], ctx["dev"], ctx["rehearsal"]
     sym = cfg["sym"]
@@ -169,32 +186,37 @@ def measure(ctx, config, cfg, steps, warmup, prewarm_ms, as_configured, want_e2e
             prewarm_steps += 8
     for _ in range(warmup):
         step()
-    # launches of the scan kernel per step (a 16 GiB step is 8 launches of 2^31 symbols): one untimed step with events
-    plan.timing(1)
-    step()
-    launches_per_step = max(plan.timing_read_all()[2], 1)
-    plan.timing(False)
-    # The kernel's duration is measured live, by HIP events on the launch stream inside the timed region --
-    # around a SAMPLE of its launches: the three events of a launch (start, end of the scan kernel, end of
-    # the kernel behind it) cost about 10 us on the stream (tools/exp_timing_overhead.py: a step of config
-    # 2 takes 282 us without them, 292 with), which is not the job's time.  About five launches are
-    # sampled, an odd period so that they fall on different launches of a step.
-    total_launches = launches_per_step * steps
-    timing_every = max(1, total_launches // (5 if total_launches >= 20 else 3 if total_launches >= 6 else 2))
-    if timing_every > 1 and timing_every % 2 == 0:
-        timing_every += 1
+    if full:
+        # launches of the scan kernel per step (a 16 GiB step is 8 launches of 2^31 symbols): one untimed step with events
+        plan.timing(1)
+        step()
+        launches_per_step = max(plan.timing_read_all()[2], 1)
+        plan.timing(False)
+        # The kernel's duration is measured live, by HIP events on the launch stream inside the timed region --
+        # around a SAMPLE of its launches: the three events of a launch (start, end of the scan kernel, end of
+        # the kernel behind it) cost about 10 us on the stream (tools/exp_timing_overhead.py: a step of config
+        # 2 takes 282 us without them, 292 with), which is not the job's time.  About five launches are
+        # sampled, an odd period so that they fall on different launches of a step.
+        total_launches = launches_per_step * steps
+        timing_every = max(1, total_launches // (5 if total_launches >= 20 else 3 if total_launches >= 6 else 2))
+        if timing_every > 1 and timing_every % 2 == 0:
+            timing_every += 1
     barrier()
-    plan.timing(timing_every)
+    if full:
+        plan.timing(timing_every)
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    kern_ms, all_ms, kern_launches = plan.timing_read_all()
-    plan.timing(False)
+    if full:
+        kern_ms, all_ms, kern_launches = plan.timing_read_all()
+        plan.timing(False)
     n_matches = int(count.item())
     assert n_matches == cap - 16, "scan and count-only pass disagree (%d != %d)" % (n_matches, cap - 16)
     plan.status()
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, records, n_matches, pos_base + n_scan)
 
     cdev = torch.device("cpu") if rehearsal else dev
     halo_max = halo
@@ -213,22 +235,23 @@ def measure(ctx, config, cfg, steps, warmup, prewarm_ms, as_configured, want_e2e
     total_bytes = float(n_own) * sym * world
     value = total_bytes * steps / elapsed / 1e9
 
-    # whole-set check of this rank's records (device side: count + order-independent digest)
-    full_count, full_digest = acm.synth.device_digest(records, n_matches)
-    assert full_count == n_matches
-    known = known_answer(config, n_own) if (as_configured and rank == 0) else None
-    checked = "count-only pass; CPU sample prefix (cpu_baseline)"
-    if known:
-        below, kc, kdg = known
-        got = (full_count, full_digest) if below == n_own else acm.synth.device_digest(records, n_matches, below=below)
-        assert got == (kc, kdg), "config %d: records with end_pos < %d differ from the oracle's known answer: %d / %#x, expected %d / %#x" % (
-            config, below, got[0], got[1], kc, kdg)
-        checked = "oracle (AC-75 variant, tests/golden/make_known_answers.py -> tests/golden/known_answers.json), %s: %d / %#018x" % (
-            "whole text" if below == n_own else "records ending in the first %d symbols" % below, kc, kdg)
+    if full:
+        # whole-set check of this rank's records (device side: count + order-independent digest)
+        full_count, full_digest = acm.synth.device_digest(records, n_matches)
+        assert full_count == n_matches
+        known = known_answer(config, n_own) if (as_configured and rank == 0) else None
+        checked = "count-only pass; CPU sample prefix (cpu_baseline)"
+        if known:
+            below, kc, kdg = known
+            got = (full_count, full_digest) if below == n_own else acm.synth.device_digest(records, n_matches, below=below)
+            assert got == (kc, kdg), "config %d: records with end_pos < %d differ from the oracle's known answer: %d / %#x, expected %d / %#x" % (
+                config, below, got[0], got[1], kc, kdg)
+            checked = "oracle (AC-75 variant, tests/golden/make_known_answers.py -> tests/golden/known_answers.json), %s: %d / %#018x" % (
+                "whole text" if below == n_own else "records ending in the first %d symbols" % below, kc, kdg)
 
     # ---- end-to-end leg: scan + canonical order + gather of records to rank 0 (separately timed)
     e2e_obj, gathered = None, None
-    if want_e2e:
+    if full:
         e2e_steps = max(1, min(steps, 5)) if n_matches < (1 << 24) else 1
 
         order_tmp = [None]
@@ -261,7 +284,7 @@ def measure(ctx, config, cfg, steps, warmup, prewarm_ms, as_configured, want_e2e
     # C caller of libac75_amd.so runs.  Rank 0 drives it over all N devices while the other ranks
     # wait at the barrier below; at N = 1 also with 8 shards on the one device.
     c_abi = None
-    if want_e2e and ctx.get("multi_c_abi", True) and not rehearsal:
+    if full and ctx.get("multi_c_abi", True) and not rehearsal:
         if rank == 0:
             try:
                 c_abi = c_abi_leg(ctx, m, kd, ko, sym, n_own, world, text, total_matches, records if world == 1 else None,
@@ -276,7 +299,7 @@ def measure(ctx, config, cfg, steps, warmup, prewarm_ms, as_configured, want_e2e
     # rank 0 by ncclSend / ncclRecv as 8-byte words) -- what a multi-process C caller runs.  At N = 1 by
     # default (librccl.so itself: communicator, ncclAllGather of the counts); at N > 1 only with
     # --rccl-c-abi: its send / receive path has run over the tests' loopback transport only.
-    if want_e2e and not rehearsal and e2e_obj is not None and (world == 1 or ctx.get("rccl_c_abi")) and not ctx.get("no_rccl_c_abi"):
+    if full and not rehearsal and e2e_obj is not None and (world == 1 or ctx.get("rccl_c_abi")) and not ctx.get("no_rccl_c_abi"):
         rccl = None
         try:
             uid = [acm.Comm.unique_id() if rank == 0 else None]
@@ -316,41 +339,9 @@ def measure(ctx, config, cfg, steps, warmup, prewarm_ms, as_configured, want_e2e
 
     res = None
     if rank == 0:
-        if gathered is not None:
-            assert gathered.shape[0] == total_matches, (gathered.shape[0], total_matches)
-            g = gathered.to(dev)
-            if g.shape[0] > 1:     # canonical order: end_pos ascending, at one end_pos the longer match first
-                ln = g[:, 1] & 0xFFFFFFFF
-                ok = (g[1:, 0] > g[:-1, 0]) | ((g[1:, 0] == g[:-1, 0]) & (ln[1:] < ln[:-1]))
-                assert bool(ok.all().item()), "gathered records not in canonical order"
-                del ln, ok
-            if world == 1:         # ... and the same record set as the unordered scan's (whose digest the oracle's known answer pins)
-                assert acm.synth.device_digest(g, g.shape[0]) == (full_count, full_digest), "ordered records differ from the scan's record set"
-            del g
-        # a step is one launch of the scan kernel per segment of 2^31 symbols (16 GiB: 8 launches)
-        kern_avg_ms = kern_ms / max(kern_launches, 1)
-        follow_avg_ms = (all_ms - kern_ms) / max(kern_launches, 1)
-        # SURVEY 8(d): sym bytes read per symbol + 16 bytes written per record -- of which the timed
-        # scan kernel moves the text and, per record, either the 16-byte record itself
-        # (records_direct) or the 8-byte item / hit it parks for the kernel behind it
-        direct = bool(info.get("records_direct"))
-        rec_bytes_scan = 16.0 if direct else 8.0
-        algo_bytes = (float(n_own) * sym + rec_bytes_scan * n_matches) / launches_per_step
-        achieved = algo_bytes / (kern_avg_ms * 1e-3) / 1e9 if kern_avg_ms > 0 else 0.0
         kname = KERNELS.get(info["kernel"], "kernel %d" % info["kernel"])
         if info["kernel"] == 5 and info.get("variant") == 2:
             kname = "scan_gram2_kernel"     # the 4-gram kernel with the lane-local sieve (dev_gram2.h)
-        # HBM bytes per launch of the scan kernel come from separate rocprofv3 --pmc passes of this
-        # command (tools/collect_profiles.sh -> profiles/traffic_config<c>.json): counters cannot
-        # be read in-process, so this is NOT from the run that prints this line and says so
-        traffic, traffic_src = None, None
-        tpath = os.path.join(ROOT, "profiles", "traffic_config%d.json" % config)
-        if os.path.exists(tpath) and as_configured:
-            with open(tpath) as f:
-                tj = json.load(f)
-            traffic = tj.get("hbm_bytes_per_launch")
-            traffic_src = "profiles/traffic_config%d.json: %s (separate rocprofv3 --pmc passes of this command, not this run)" % (
-                config, tj.get("source", "FETCH_SIZE x2 + WRITE_SIZE, gfx950 correction"))
         if info["kernel"] == 1:
             geometry = "%s<u%d,C=%d,S=%d> %d x %d threads; LDS: %d rows + %d hotfail entries of %d states, %d B" % (
                 kname, 8 * info["entry_bytes"], info["chunk_bytes"], info["streams"], info["grid_blocks"],
@@ -372,22 +363,55 @@ def measure(ctx, config, cfg, steps, warmup, prewarm_ms, as_configured, want_e2e
                 "matches_total": total_matches,
                 "parallelism": "text sharded x%d, %d-symbol halo (the largest any rank used), tables replicated" % (world, halo_max if world > 1 else 0),
                 "kernel": geometry, "dictionary_build_s": round(build_s, 3),
-                "record_set": {"count": full_count, "digest": "%#018x" % full_digest, "checked_against": checked},
             },
-            "roofline": {
-                "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "kernel": kname, "kernel_avg_ms": round(kern_avg_ms, 4), "kernel_launches": kern_launches,
-                "launches_per_step": launches_per_step,
-                "events": "HIP events on the launch stream around every %s launch of the timed region (%d of its %d launches)" % (
-                    "" if timing_every == 1 else "%d-th" % timing_every, kern_launches, launches_per_step * steps),
-                "algorithmic_bytes_per_launch": algo_bytes,
-                "algorithmic_bytes": "%d B per symbol read + %d B per record written by this kernel (%s)" % (
-                    sym, int(rec_bytes_scan), "the 16-byte records themselves" if direct else
-                    "8-byte items / hits parked for %s, which writes the 16-byte records" % FOLLOWERS.get(info["kernel"], "the kernel behind it")),
-                "behind_it": {"kernel": FOLLOWERS.get(info["kernel"]), "avg_ms": round(follow_avg_ms, 4),
-                              "what": "HIP events on the launch stream: end of the scan kernel -> end of the kernel it is followed by, averaged over the launches (of a scan's launches only the last one is followed by close_holes_kernel)"},
-            },
+        }
+    if rank == 0 and full:
+        if gathered is not None:
+            assert gathered.shape[0] == total_matches, (gathered.shape[0], total_matches)
+            g = gathered.to(dev)
+            if g.shape[0] > 1:     # canonical order: end_pos ascending, at one end_pos the longer match first
+                ln = g[:, 1] & 0xFFFFFFFF
+                ok = (g[1:, 0] > g[:-1, 0]) | ((g[1:, 0] == g[:-1, 0]) & (ln[1:] < ln[:-1]))
+                assert bool(ok.all().item()), "gathered records not in canonical order"
+                del ln, ok
+            if world == 1:         # ... and the same record set as the unordered scan's (whose digest the oracle's known answer pins)
+                assert acm.synth.device_digest(g, g.shape[0]) == (full_count, full_digest), "ordered records differ from the scan's record set"
+            del g
+        res["config"]["record_set"] = {"count": full_count, "digest": "%#018x" % full_digest, "checked_against": checked}
+        # a step is one launch of the scan kernel per segment of 2^31 symbols (16 GiB: 8 launches)
+        kern_avg_ms = kern_ms / max(kern_launches, 1)
+        follow_avg_ms = (all_ms - kern_ms) / max(kern_launches, 1)
+        # SURVEY 8(d): sym bytes read per symbol + 16 bytes written per record -- of which the timed
+        # scan kernel moves the text and, per record, either the 16-byte record itself
+        # (records_direct) or the 8-byte item / hit it parks for the kernel behind it
+        direct = bool(info.get("records_direct"))
+        rec_bytes_scan = 16.0 if direct else 8.0
+        algo_bytes = (float(n_own) * sym + rec_bytes_scan * n_matches) / launches_per_step
+        achieved = algo_bytes / (kern_avg_ms * 1e-3) / 1e9 if kern_avg_ms > 0 else 0.0
+        # HBM bytes per launch of the scan kernel come from separate rocprofv3 --pmc passes of this
+        # command (tools/collect_profiles.sh -> profiles/traffic_config<c>.json): counters cannot
+        # be read in-process, so this is NOT from the run that prints this line and says so
+        traffic, traffic_src = None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic_config%d.json" % config)
+        if os.path.exists(tpath) and as_configured:
+            with open(tpath) as f:
+                tj = json.load(f)
+            traffic = tj.get("hbm_bytes_per_launch")
+            traffic_src = "profiles/traffic_config%d.json: %s (separate rocprofv3 --pmc passes of this command, not this run)" % (
+                config, tj.get("source", "FETCH_SIZE x2 + WRITE_SIZE, gfx950 correction"))
+        res["roofline"] = {
+            "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+            "kernel": kname, "kernel_avg_ms": round(kern_avg_ms, 4), "kernel_launches": kern_launches,
+            "launches_per_step": launches_per_step,
+            "events": "HIP events on the launch stream around every %s launch of the timed region (%d of its %d launches)" % (
+                "" if timing_every == 1 else "%d-th" % timing_every, kern_launches, launches_per_step * steps),
+            "algorithmic_bytes_per_launch": algo_bytes,
+            "algorithmic_bytes": "%d B per symbol read + %d B per record written by this kernel (%s)" % (
+                sym, int(rec_bytes_scan), "the 16-byte records themselves" if direct else
+                "8-byte items / hits parked for %s, which writes the 16-byte records" % FOLLOWERS.get(info["kernel"], "the kernel behind it")),
+            "behind_it": {"kernel": FOLLOWERS.get(info["kernel"]), "avg_ms": round(follow_avg_ms, 4),
+                          "what": "HIP events on the launch stream: end of the scan kernel -> end of the kernel it is followed by, averaged over the launches (of a scan's launches only the last one is followed by close_holes_kernel)"},
         }
         if e2e_obj:
             res["e2e"] = e2e_obj
@@ -484,7 +508,7 @@ def main():
     ctx = dict(acm=acm, torch=torch, dist=dist, rank=rank, world=world, dev=dev, rehearsal=rehearsal, multi_c_abi=not args.no_multi_c_abi,
                rccl_c_abi=args.rccl_c_abi, no_rccl_c_abi=args.no_rccl_c_abi or args.no_multi_c_abi)
 
-    res, keep = measure(ctx, args.config, cfg, args.steps, args.warmup, args.prewarm_ms, as_configured)
+    res, keep = measure(ctx, args.config, cfg, args.steps, args.warmup, args.prewarm_ms, as_configured, args.full, args.dump_outputs)
     out = None
     if rank == 0:
         out = {
@@ -503,20 +527,21 @@ def main():
             "dtype": res["dtype"],
             "data": "synthetic" + (" (REHEARSAL: all ranks on one GPU over gloo; numbers meaningless)" if rehearsal else ""),
             "config": res["config"],
-            "roofline": res["roofline"],
-            "e2e": res["e2e"],
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["roofline"] = res["roofline"]
+            out["e2e"] = res["e2e"]
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n_sample = min((cfg["cpu_mib"] << 20) // keep["sym"], keep["n_own"])
             out["cpu_baseline"] = cpu_baseline(acm, keep["machine"], keep["kd"], keep["ko"], keep["gen"][:n_sample], keep["sym"],
                                                acm.synth.device_digest(keep["records"], keep["n_matches"], below=n_sample))
         # ---- the other single-GPU configs, briefly, under one extra key (the headline above is final)
-        if args.config == 2 and world == 1 and as_configured and not args.no_other_configs:
+        if args.full and args.config == 2 and world == 1 and as_configured and not args.no_other_configs:
             del keep
             torch.cuda.empty_cache()
             others = {}
             for c, (k_steps, k_warm) in ((3, (5, 1)), (5, (10, 2))):
-                r, k = measure(ctx, c, dict(CONFIGS[c]), k_steps, k_warm, 100, True, want_e2e=True)
+                r, k = measure(ctx, c, dict(CONFIGS[c]), k_steps, k_warm, 100, True, True)
                 others[str(c)] = {
                     "value": r["value"], "unit": "GB/s", "ms_per_step": r["ms_per_step"], "steps": k_steps, "warmup": k_warm,
                     "workload": r["config"]["workload"], "kernel": r["config"]["kernel"],
@@ -533,6 +558,27 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return out
+
+
+def dump_outputs(out_dir, records, n, n_symbols):
+    """The records of the last timed step, as a caller of Plan.scan receives them (the first n rows of
+    the int64 [cap, 2] buffer), written as out_dir/records.npy: float64 [k, 3] = (end_pos, length,
+    keyword_id), in canonical order (end_pos ascending, the longer match first, then keyword_id)
+    because the scan's own order varies from run to run; and out_dir/count.npy: float64 [1] = n.
+    Above DUMP_MAX_RECORDS only the records that end in a seeded random subset of the 4096-symbol
+    blocks of [0, n_symbols) are kept (at most DUMP_MAX_RECORDS of them, in that order)."""
+    import numpy as np
+    import torch
+    r = records[:n]
+    if n > DUMP_MAX_RECORDS:
+        keep = np.random.default_rng(DUMP_SEED).random(n_symbols // 4096 + 1) < 0.9 * DUMP_MAX_RECORDS / n
+        r = r[torch.from_numpy(keep).to(r.device)[r[:, 0] >> 12]]
+    a = r.cpu().numpy()
+    rec = np.stack([a[:, 0], a[:, 1] & 0xFFFFFFFF, (a[:, 1] >> 32) & 0xFFFFFFFF], axis=1).astype(np.float64)
+    rec = rec[np.lexsort((rec[:, 2], -rec[:, 1], rec[:, 0]))][:DUMP_MAX_RECORDS]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "records.npy"), rec)
+    np.save(os.path.join(out_dir, "count.npy"), np.array([n], dtype=np.float64))
 
 
 def cpu_baseline(acm, machine, kd, ko, dev_sample, sym, gpu_on_sample):

@@ -3,18 +3,19 @@
 #   tools/collect_profiles.sh <tag> [bench.py arguments, e.g. --config 3 --steps 3 --warmup 1]
 # Writes under gpurun_out/profile_<tag>/; copy what should be judged into profiles/.
 set -e
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 R=${1:-r03}
 shift || true
 ARGS="$@"
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profile_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $GRAFT_REPO_ROOT/bench.py $ARGS --no-cpu-baseline --no-other-configs --no-multi-c-abi > $OUT/bench_under_trace.json 2> $OUT/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py $ARGS --full --no-cpu-baseline --no-other-configs --no-multi-c-abi > $OUT/bench_under_trace.json 2> $OUT/trace.err
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS" \
            "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SMEM" \
            "FETCH_SIZE" "WRITE_SIZE GRBM_GUI_ACTIVE" "TCC_HIT_sum TCC_MISS_sum"; do
   name=$(echo $set | tr " " "_" | cut -c1-32)
-  rocprofv3 --pmc $set --output-format csv -d $OUT/pmc_$name -- python3 $GRAFT_REPO_ROOT/bench.py $ARGS --steps 3 --warmup 1 --prewarm-ms 0 --no-cpu-baseline --no-other-configs --no-multi-c-abi > /dev/null 2> $OUT/pmc_$name.err || echo "pmc $name failed"
+  rocprofv3 --pmc $set --output-format csv -d $OUT/pmc_$name -- python3 $ROOT/bench.py $ARGS --full --steps 3 --warmup 1 --prewarm-ms 0 --no-cpu-baseline --no-other-configs --no-multi-c-abi > /dev/null 2> $OUT/pmc_$name.err || echo "pmc $name failed"
   echo "pass $name done" >> $OUT/progress.txt
 done
 python3 - <<PY
