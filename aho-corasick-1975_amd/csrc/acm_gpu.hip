@@ -672,7 +672,8 @@ plan_create_flat_kw (const ACMFlat *flat, int device, uint32_t kw_base, ACMPlan 
                      (uint64_t)n * fi.width * entry_bytes <= (8ull << 30) && fi.lmax >= 1 && fi.lmax - 1 <= 16u * 255;
   const bool cont = dense && entry_bytes == 2; /* continuation mode, see scan_dense_kernel */
   const uint32_t rowbytes = fi.width * entry_bytes;
-  const uint32_t queue_bytes = (DENSE_THREADS / WAVE) * QCAP * 8;
+  /* (-DACM_DENSE_DIRECT_PARK: the dense kernel parks its items straight into HBM, no LDS queues) */
+  const uint32_t queue_bytes = DENSE_LDS_QUEUE ? (DENSE_THREADS / WAVE) * QCAP * 8 : 0;
 
   /* ---- LDS budget: rows of a breadth-first prefix [0, HD); continuation mode also keeps
    *      hotfail(s) (2 bytes) for every other state */

@@ -44,6 +44,21 @@ constexpr int DENSE_THREADS = 1024; /* one workgroup per CU, 16 waves */
 #endif
 /* a region must hold the items of two 16-step blocks beside a queue's worth: region_make_room */
 constexpr uint32_t DENSE_MIN_REGION_ITEMS = 2 * (16 * ACM_DENSE_S * WAVE + QCAP);
+/* continuation mode: straight-line run-over steps past a chunk before the lanes still inside a
+ * match park a walk item (IT_WALK) and stop; -DACM_DENSE_RUNOVER=n builds another count */
+#ifndef ACM_DENSE_RUNOVER
+#define ACM_DENSE_RUNOVER 4
+#endif
+constexpr uint32_t DENSE_RUNOVER = ACM_DENSE_RUNOVER;
+static_assert (DENSE_RUNOVER >= 1 && DENSE_RUNOVER <= 16, "the run-over steps read one 16-byte block past the chunk");
+/* dense kernel: items go through a 128-item LDS queue per wave to the wave's HBM region.
+ * -DACM_DENSE_DIRECT_PARK (experiment, slower: DESIGN.md 4.1) stores them straight from the slow
+ * side into the region and gives the queues' 16 KiB to rows */
+#ifdef ACM_DENSE_DIRECT_PARK
+constexpr bool DENSE_LDS_QUEUE = false;
+#else
+constexpr bool DENSE_LDS_QUEUE = true;
+#endif
 constexpr uint64_t SEGMENT = 1ull << 31; /* symbols per launch: positions inside a launch are 32-bit */
 /* tests shrink it with ACM_GPU_SEGMENT_LOG2 to cross segment seams on small inputs */
 
@@ -129,6 +144,9 @@ constexpr uint32_t IT_CONT = 1u << 15;  /* walk on from this (rowless) state: se
 constexpr uint32_t IT_K_SHIFT = 16;     /* 12 bits: run-over step k (symbols past the end of the lane's chunk) */
 constexpr uint32_t IT_RUN = 1u << 28;   /* queued during a chunk's run-over */
 constexpr uint32_t IT_OUT = 1u << 29;   /* report the outputs of the state itself at pos */
+/* with IT_RUN | IT_CONT: the lane stopped its run-over in this state (it has a row) after k steps;
+ * walk on from it with no hotfail bound (walk_continuation) */
+constexpr uint32_t IT_WALK = 1u << 30;
 
 #include "dev_emit.h"
 #include "dev_dense.h"

@@ -26,7 +26,7 @@ template <int S> struct Walk {
   uint32_t qn;     /* queue fill (wave-uniform) */
   uint32_t sticky; /* sticky mode, per lane: ~0 while one of its streams sits in a rowless state */
   Spill spill;
-  DIAG (unsigned long long d_slow_cycles = 0; unsigned long long d_slow_steps = 0;)
+  DIAG (unsigned long long d_slow_cycles = 0; unsigned long long d_slow_steps = 0; unsigned long long d_run_steps = 0;)
 };
 
 template <typename ENTRY>
@@ -46,6 +46,17 @@ struct StepAt {
   uint32_t pos0, k, live_from;
   int phase;
 };
+
+/* one item per lane with `hit`: through the wave's LDS queue, or (-DACM_DENSE_DIRECT_PARK)
+ * straight into the wave's HBM region */
+template <bool CONT, bool COUNT_ONLY, int S>
+__device__ __forceinline__ void
+dense_park (const EmitCtx &E, uint2 *queue, Walk<S> &w, bool hit, uint32_t pos, uint32_t word, uint32_t lane) {
+  if (DENSE_LDS_QUEUE)
+    queue_push<CONT, COUNT_ONLY, true> (E, queue, w.qn, hit, pos, word, lane, &w.spill);
+  else
+    region_push (&w.spill, hit, pos, word);
+}
 
 /* Slow side of one step: the whole wave comes here when some lane looked up an entry >= HD (next
  * state has outputs and/or no row in LDS), or -- sticky mode -- sits in a rowless state. */
@@ -84,10 +95,10 @@ dense_step_slow (const DenseK &K, const EmitCtx &E, uint32_t emit_from, uint32_t
       uint32_t word = ns[q] | (deep ? IT_CONT : 0u) | (out ? IT_OUT : 0u);
       if (at.phase == PH_RUN)
         word |= IT_RUN | (at.k << IT_K_SHIFT);
-      queue_push<CONT, COUNT_ONLY, true> (E, queue, w.qn, out | deep, pos, word, lane, &w.spill);
+      dense_park<CONT, COUNT_ONLY, S> (E, queue, w, out | deep, pos, word, lane);
     } else {
       const bool out = at.phase == PH_MAIN && (e[q] & FLAG) && window;
-      queue_push<CONT, COUNT_ONLY, true> (E, queue, w.qn, out, pos, ns[q], lane, &w.spill);
+      dense_park<CONT, COUNT_ONLY, S> (E, queue, w, out, pos, ns[q], lane);
       rowless |= ns[q] >= K.HD;
     }
   }
@@ -165,11 +176,39 @@ template <typename ENTRY, int S, bool COUNT_ONLY, int KN> struct BlockLoop<ENTRY
        const uint4 (&)[KN][S], uint32_t, uint32_t) {}
 };
 
+/* byte j (compile-time) of a 16-byte block */
+__device__ __forceinline__ uint32_t
+block_byte (const uint4 &v, uint32_t j) {
+  const uint32_t x = j < 4 ? v.x : (j < 8 ? v.y : (j < 12 ? v.z : v.w));
+  return (x >> (8 * (j & 3))) & 0xffu;
+}
+
+/* run-over step k (1 .. DENSE_RUNOVER) of continuation mode: byte k - 1 of the block after the
+ * chunk (ce0 = stream 0's chunk end), then step k + 1 -- all of them while k < lmax */
+template <typename ENTRY, int S, bool COUNT_ONLY, uint32_t k>
+__device__ __forceinline__ void
+dense_run_steps (const DenseK &K, const EmitCtx &E, uint32_t emit_from, uint32_t emit_end, const ENTRY *__restrict__ gdense,
+                 uint2 *queue, Walk<S> &w, const uint4 (&post)[S], uint32_t ce0, const uint32_t *__restrict__ dstart, uint32_t lane) {
+  if constexpr (k <= DENSE_RUNOVER) {
+    if (k < K.lmax) {
+      uint32_t b_[S];
+#pragma unroll
+      for (int q = 0; q < S; q++)
+        b_[q] = block_byte (post[q], k - 1);
+      const StepAt at = { ce0 + k - 1, k, dstart[k + 1], PH_RUN };
+      dense_step<ENTRY, S, COUNT_ONLY> (K, E, emit_from, emit_end, gdense, queue, w, b_, at, lane);
+      DIAG (w.d_run_steps++;)
+      dense_run_steps<ENTRY, S, COUNT_ONLY, k + 1> (K, E, emit_from, emit_end, gdense, queue, w, post, ce0, dstart, lane);
+    }
+  }
+}
+
 /* Tiles [range_begin, range_end) of 64*S*C bytes cover the whole segment, the last one possibly
  * ragged.  16-byte loads are clamped to the last block that holds a valid byte (an aligned
  * 16-byte block never straddles a page, so it cannot fault); what a lane walks beyond the end of
  * the segment is never reported (emit window [emit_from, n)).
- * LDS image: [HD rows][continuation mode: hotfail of every other state, 2 B each][16 queues]. */
+ * LDS image: [HD rows][continuation mode: hotfail of every other state, 2 B each][16 queues]
+ * [tile counter] (-DACM_DENSE_DIRECT_PARK: no queues). */
 template <typename ENTRY, int C, int S, bool COUNT_ONLY>
 __global__ __launch_bounds__ (DENSE_THREADS) void
 scan_dense_kernel (DenseK K, EmitCtx E, Launch A, const ENTRY *__restrict__ gdense, const uint4 *__restrict__ lds_image,
@@ -188,7 +227,7 @@ scan_dense_kernel (DenseK K, EmitCtx E, Launch A, const ENTRY *__restrict__ gden
   }
   /* tiles are handed out dynamically inside the workgroup (its waves do not run at the same
    * pace: a static split left the slowest wave of a block 11% behind the block's mean) */
-  uint32_t *next_tile = reinterpret_cast<uint32_t *> (smem + K.queue_off + (DENSE_THREADS / WAVE) * QCAP * 8);
+  uint32_t *next_tile = reinterpret_cast<uint32_t *> (smem + K.queue_off + (DENSE_LDS_QUEUE ? (DENSE_THREADS / WAVE) * QCAP * 8 : 0));
   if (threadIdx.x == 0)
     *next_tile = 0;
   __syncthreads ();
@@ -199,7 +238,7 @@ scan_dense_kernel (DenseK K, EmitCtx E, Launch A, const ENTRY *__restrict__ gden
   if (wib >= (DENSE_THREADS / WAVE) / 2)
     __builtin_amdgcn_s_setprio (1);
 #endif
-  uint2 *queue = reinterpret_cast<uint2 *> (smem + K.queue_off) + wib * QCAP;
+  uint2 *queue = DENSE_LDS_QUEUE ? reinterpret_cast<uint2 *> (smem + K.queue_off) + wib * QCAP : nullptr;
   const uint32_t waves_per_block = blockDim.x / WAVE;
   const uint32_t wave = blockIdx.x * waves_per_block + wib;
   const uint32_t emit_from = A.emit_from, emit_end = A.n;
@@ -331,40 +370,30 @@ scan_dense_kernel (DenseK K, EmitCtx E, Launch A, const ENTRY *__restrict__ gden
 #undef ACM_WALK_BLOCK
 #undef ACM_REFILL_BLOCK
     if (CONT) {
-      /* continuation mode, ownership by START position: run over into the following bytes until
-       * no lane's state is deeper than the number of bytes past its chunk (at most lmax - 1) */
-      bool done = false;
-      for (uint32_t b = 0; b < K.wub && !done; b++) {
-        if (b > 0) {
+      /* continuation mode, ownership by START position: run over into the following bytes,
+       * DENSE_RUNOVER straight-line steps at most (k < lmax: a state deeper than k after k steps
+       * needs a keyword longer than k + 1).  Then a lane-stream still deeper than the bytes past
+       * its chunk parks ONE walk item and stops: the expand kernel walks on from its state
+       * through the HBM rows (walk_continuation).  The wave no longer runs as long as its
+       * deepest lane-stream (a ballot, a done test and a depth_start load per step). */
+      region_make_room<CONT, COUNT_ONLY, S> (E, &w.spill);
+      dense_run_steps<ENTRY, S, COUNT_ONLY, 1> (K, E, emit_from, emit_end, gdense, queue, w, post, pos0 + C, dstart, lane);
+      if (K.lmax > DENSE_RUNOVER + 1) {
+        const uint32_t live_from = dstart[DENSE_RUNOVER + 1];
 #pragma unroll
-          for (int q = 0; q < S; q++)
-            post[q] = load_block (pos0, NB + b, q);
+        for (int q = 0; q < S; q++) {
+          const uint32_t pos = pos0 + q * K.stream_stride + C + DENSE_RUNOVER - 1;
+          const bool walk = w.s[q] >= live_from && pos + 1 < emit_end;
+          dense_park<CONT, COUNT_ONLY, S> (E, queue, w, walk, pos,
+                                           w.s[q] | IT_CONT | IT_RUN | IT_WALK | (DENSE_RUNOVER << IT_K_SHIFT), lane);
         }
-        region_make_room<CONT, COUNT_ONLY, S> (E, &w.spill);
-#define ACM_RUN_BYTE(COMP, SH, J)                                                                  \
-  if (!done) {                                                                                     \
-    const uint32_t k_ = 16 * b + (J) + 1;                                                          \
-    const uint32_t live_from_ = dstart[k_ + 1 <= K.lmax ? k_ + 1 : K.lmax + 1];                    \
-    uint32_t b_[S];                                                                                \
-    _Pragma ("unroll") for (int q = 0; q < S; q++) b_[q] = (post[q].COMP >> (SH)) & 0xffu;         \
-    const StepAt at_ = { pos0 + C + 16 * b + (J), k_, live_from_, PH_RUN };                        \
-    dense_step<ENTRY, S, COUNT_ONLY> (K, E, emit_from, emit_end, gdense, queue, w, b_, at_, lane); \
-    bool live_ = false;                                                                            \
-    _Pragma ("unroll") for (int q = 0; q < S; q++) live_ |= w.s[q] >= live_from_;                  \
-    done = k_ + 1 >= K.lmax || __ballot (live_) == 0;                                              \
-  }
-#define ACM_RUN_WORD(COMP, J)                                                                      \
-  ACM_RUN_BYTE (COMP, 0, (J) + 0) ACM_RUN_BYTE (COMP, 8, (J) + 1) ACM_RUN_BYTE (COMP, 16, (J) + 2) ACM_RUN_BYTE (COMP, 24, (J) + 3)
-        ACM_RUN_WORD (x, 0) ACM_RUN_WORD (y, 4) ACM_RUN_WORD (z, 8) ACM_RUN_WORD (w, 12)
-#undef ACM_RUN_WORD
-#undef ACM_RUN_BYTE
       }
 #pragma unroll
       for (int q = 0; q < S; q++)
         post[q] = load_block (npos0, NB, q);
     }
   }
-  if (w.qn) /* (at most 64 items: the last block's room covers them) */
+  if (DENSE_LDS_QUEUE && w.qn) /* (at most 64 items: the last block's room covers them) */
     queue_drain<CONT, COUNT_ONLY, true> (E, queue, w.qn, &w.spill, lane);
   if (lane == 0 && fill)
     fill[wave] = w.spill.fill;
@@ -377,6 +406,6 @@ scan_dense_kernel (DenseK K, EmitCtx E, Launch A, const ENTRY *__restrict__ gden
     o[3] = w.d_slow_steps;
     o[4] = w.d_slow_cycles;
     o[5] = d_text;
-    o[6] = d_tiles;
+    o[6] = d_tiles | (w.d_run_steps << 32); /* run-over steps in the high half */
   })
 }

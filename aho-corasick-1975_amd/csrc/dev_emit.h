@@ -81,6 +81,10 @@ struct ContResult {
  * through the HBM rows: j symbols later every output longer than j + dh -- and, past ce, longer
  * than the bytes past ce -- is such a match, and once the state is no deeper than that bound
  * nothing more can be missing.
+ * Walk item (IT_WALK, always with IT_RUN): the lane ended its run-over k symbols past ce in state
+ * st, still deeper than k.  The same walk from st with no hotfail term in the bound (dh = 0) finds
+ * what the unbounded run-over would have: outputs longer than the bytes past ce, until the state
+ * is no deeper than that.
  * One dependent load per symbol: the row entry carries the next state, its output flag and its
  * depth; the text byte of the following step is fetched alongside. */
 __device__ __forceinline__ uint32_t
@@ -94,7 +98,8 @@ walk_continuation (const EmitCtx &E, uint2 it, uint64_t o) {
   ContResult r = { 0, 0, 0, 0, make_uint4 (0, 0, 0, 0) };
   const uint32_t pos = it.x, st = it.y & IT_STATE;
   const uint32_t ce = item_chunk_end (E, it);
-  if (E.chain && st >= E.chain_base && pos + 9 <= E.n) {
+  const bool walk = (it.y & IT_WALK) != 0;
+  if (E.chain && !walk && st >= E.chain_base && pos + 9 <= E.n) {
     /* all that lies below st is one path of len symbols to a leaf t (chain record, acm_gpu.hip):
      * what the walk below would find is t's keyword len symbols on, or nothing */
     const uint4 c = E.chain[st - E.chain_base];
@@ -120,7 +125,8 @@ walk_continuation (const EmitCtx &E, uint2 it, uint64_t o) {
       return r;
     }
   }
-  const uint32_t dh = E.cont_dh[st];
+  /* a walk item (the run-over's end, st has a row): nothing is covered by a lane from here on */
+  const uint32_t dh = walk ? 0u : E.cont_dh[st];
   uint32_t s2 = st;
   uint32_t byte = pos + 1 < E.n ? E.text[pos + 1] : 0;
   for (uint32_t j = 1; pos + j < E.n; j++) {
@@ -255,6 +261,19 @@ queue_push (const EmitCtx &E, uint2 *queue, uint32_t &qn, bool hit, uint32_t pos
       queue_drain<CONT, COUNT_ONLY, PARK_ONLY> (E, queue, qn, sp, lane);
       qn = 0;
     }
+  }
+}
+
+/* Dense kernel: append one item per lane with `hit` straight to the wave's region, one plain
+ * 8-byte vector store per hitting lane at fill + its rank in the ballot; the fill stays
+ * wave-uniform (scalar registers).  region_make_room has made room for the whole block. */
+__device__ __forceinline__ void
+region_push (Spill *sp, bool hit, uint32_t pos, uint32_t word) {
+  const uint64_t m = __ballot (hit);
+  if (m) {
+    if (hit)
+      sp->region[sp->fill + rank_below (m)] = make_uint2 (pos, word);
+    sp->fill = uniform (sp->fill + (uint32_t)__popcll (m));
   }
 }
 

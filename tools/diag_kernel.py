@@ -22,13 +22,15 @@ def run(name, K, n, plant=True):
     L = acm.lib()
     L.acm_gpu_diag_read.argtypes = [C.c_void_p, C.c_uint]
     assert L.acm_gpu_diag_read(d.ctypes.data, waves) == 0
+    run_steps = (d[:, 6] >> np.uint64(32)).astype(np.float64)  # dense kernel: run-over steps in the high half
+    d[:, 6] &= np.uint64(0xFFFFFFFF)
     d = d.astype(np.float64)
     tot = d[:, 0]
     print("%-28s kernel cycles/wave: mean %.0f max %.0f | items parked/wave %.0f | slow steps %.0f, slow-side cyc %.0f (%.1f%%) = %.0f/step | "
-          "text wait %.0f cyc (%.1f%%), %.0f/tile, %d tiles" % (
+          "text wait %.0f cyc (%.1f%%), %.0f/tile, %d tiles | run-over steps %.3f/tile" % (
               name, tot.mean(), tot.max(), d[:, 2].mean(), d[:, 3].mean(), d[:, 4].mean(), 100 * d[:, 4].mean() / tot.mean(),
               d[:, 4].sum() / max(d[:, 3].sum(), 1), d[:, 5].mean(), 100 * d[:, 5].mean() / tot.mean(),
-              d[:, 5].sum() / max(d[:, 6].sum(), 1), d[:, 6].mean()), flush=True)
+              d[:, 5].sum() / max(d[:, 6].sum(), 1), d[:, 6].mean(), run_steps.sum() / max(d[:, 6].sum(), 1)), flush=True)
 
 
 if __name__ == "__main__":
