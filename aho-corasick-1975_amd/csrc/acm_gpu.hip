@@ -87,8 +87,12 @@ struct StartsMirror {
   }
 };
 
+/* the kernel family of a plan (ACMPlanInfo::kernel) */
+enum class PlanKind : uint32_t { Dense = 1, Csr = 2, Sparse = 3, Starts = 4, Gram = 5 };
+
 struct ACMPlan {
   int device = 0;
+  PlanKind kind = PlanKind::Csr;
   ACMFlatInfo finfo{};
   ACMPlanInfo info{};
   void *blob = nullptr; /* one device allocation holding every table */
@@ -100,21 +104,24 @@ struct ACMPlan {
   const uint16_t *d_cont_dh = nullptr;
   const uint4 *d_chain = nullptr; /* EmitCtx::chain */
   /* sparse kernel (2- and 4-byte symbols) */
-  SparseK SK{};
+  SparseK SK{};  /* Sparse and Starts plans (Starts: segments that are not 16-byte aligned) */
   StartsK TK{};
-  bool starts = false; /* start-parallel kernel instead of the sparse walk */
-  StartsMirror *mir = nullptr; /* starts plans: what acm_gpu_plan_update edits */
+  StartsMirror *mir = nullptr; /* Starts plans: what acm_gpu_plan_update edits */
   GramK GK{};
-  bool gram = false; /* 4-gram sieve kernel instead of the sticky dense walk */
-  bool gram_shorts = false, gram_wide = false;
-  bool gram2 = false; /* scan_gram2_kernel (dev_gram2.h) instead of scan_gram_kernel */
-  bool short_pass = false; /* narrow alphabets: the keywords of 1-3 symbols in a pass of their own (scan_short_kernel, dev_short.h) */
+  /* Gram plans, two forms by alphabet:
+   *   narrow (!hashed: up to 29 symbols + "other"): exact base-W 4-gram index, records written by the
+   *     scan kernel itself; gram2: scan_gram2_kernel (dev_gram2.h) instead of scan_gram_kernel (up to
+   *     26 symbols + "other"); short_pass: the keywords of 1-3 symbols in a pass of their own
+   *     (scan_short_kernel, dev_short.h), short_ids_lds: that pass has their ids in LDS;
+   *   hashed: hashed 4-byte windows, hits parked and expanded; inline_shorts: the keywords of 1-3
+   *     symbols in the kernel's own third queue.
+   * So gram2 and short_pass (with short_ids_lds) only with !hashed, inline_shorts only with hashed. */
+  bool hashed = false, gram2 = false, short_pass = false, short_ids_lds = false, inline_shorts = false;
   uint32_t short_lds_bytes = 0, short_lds_count_bytes = 0; /* scan_short_kernel: with records / count-only (the nibbles alone) */
-  bool short_ids_lds = false; /* scan_short_kernel: the keyword ids are in LDS (else read by rank from the image in HBM) */
   uint32_t short_blocks_per_cu = 1; /* scan_short_kernel, count-only: two blocks a CU when its LDS allows (8 waves a SIMD) */
   uint32_t gram_lds_bytes = 0;
   uint32_t class_sym_bytes = 0; /* comparator-class plans: the symbol size they were made for */
-  bool sparse = false, sparse_lut_lds = false, starts_lut_lds = false;
+  bool sparse_lut_lds = false, starts_lut_lds = false;
   uint32_t sparse_lds_bytes = 0, starts_lds_bytes = 0;
   /* dense kernel (breadth-first numbering too: the LDS rows are a breadth-first prefix) */
   DenseK K{};
@@ -595,696 +602,826 @@ fill_gram_tables (const ACMFlatView &fv, const ACMFlatInfo &fi, const GramImage 
   }
 }
 
-} // namespace
+/* ---- plan construction (acm_gpu_plan_create_flat, and the delta plans of acm_gpu_plan_update).
+ * One device allocation holds every table of a plan; its host image is built table by table: the
+ * CSR tables every plan has, then those of the kernel family the dictionary qualifies for. */
 
-namespace {
-int plan_create_flat_kw (const ACMFlat *flat, int device, uint32_t kw_base, ACMPlan **out);
-}
-
-extern "C" int
-acm_gpu_plan_create_flat (const ACMFlat *flat, int device, ACMPlan **out) {
-  return plan_create_flat_kw (flat, device, 0, out);
-}
-
-namespace {
-/* kw_base: added to every keyword id the plan reports (the delta plans of acm_gpu_plan_update) */
 int
-plan_create_flat_kw (const ACMFlat *flat, int device, uint32_t kw_base, ACMPlan **out) {
-  if (!flat || !out)
-    return ACM_GPU_E_ARG;
+env_int (const char *name, int absent) {
+  const char *e = getenv (name);
+  return e ? atoi (e) : absent;
+}
+
+/* the environment switches that shape a plan (experiments and tests), read once per plan */
+struct PlanSwitches {
+  int segment_log2 = env_int ("ACM_GPU_SEGMENT_LOG2", 0); /* launch segments of 2^12 .. 2^31 symbols */
+  int gram = env_int ("ACM_GPU_GRAM", 1); /* 0: never the 4-gram kernel; 2: whenever the dictionary qualifies; 3: hashed windows always */
+  bool bloom = env_int ("ACM_GPU_BLOOM", 1) != 0;          /* 0: no Bloom filters */
+  bool gram2 = env_int ("ACM_GPU_GRAM2", 1) != 0;          /* 0: scan_gram_kernel instead of scan_gram2_kernel */
+  bool peek8 = env_int ("ACM_GPU_PEEK8", 0) == 1;          /* 1: 8-byte peek entries whatever the size */
+  bool sparse_walk = getenv ("ACM_GPU_SPARSE") && strcmp (getenv ("ACM_GPU_SPARSE"), "walk") == 0; /* the sparse walk, not the start-parallel kernel */
+  bool short_blocks1 = env_int ("ACM_GPU_SHORT_BLOCKS", 0) == 1; /* 1: scan_short_kernel counts with one block a CU */
+  int grid_blocks = env_int ("ACM_GPU_GRID_BLOCKS", 0);    /* fewer workgroups than CUs */
+};
+
+/* asked once per device: the call takes a good part of a millisecond, and the delta plans of
+ * acm_gpu_plan_update are made at every dictionary change */
+int
+device_properties (int device, hipDeviceProp_t *prop) {
   int ndev = 0;
   if (hipGetDeviceCount (&ndev) != hipSuccess || ndev <= 0)
     return ACM_GPU_E_NODEVICE;
   if (device < 0 || device >= ndev)
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (device));
-  /* (asked once per device: the call takes a good part of a millisecond, and the delta plans of
-   * acm_gpu_plan_update are made at every dictionary change) */
   static std::mutex prop_mutex;
   static std::vector<std::pair<int, hipDeviceProp_t>> prop_cache;
-  hipDeviceProp_t prop;
-  {
-    std::lock_guard<std::mutex> g (prop_mutex);
-    bool have = false;
-    for (const auto &c : prop_cache)
-      if (c.first == device) {
-        prop = c.second;
-        have = true;
-      }
-    if (!have) {
-      HIP_TRY (hipGetDeviceProperties (&prop, device));
-      prop_cache.emplace_back (device, prop);
+  std::lock_guard<std::mutex> g (prop_mutex);
+  for (const auto &c : prop_cache)
+    if (c.first == device) {
+      *prop = c.second;
+      return ACM_GPU_OK;
     }
-  }
+  HIP_TRY (hipGetDeviceProperties (prop, device));
+  prop_cache.emplace_back (device, *prop);
+  return ACM_GPU_OK;
+}
 
+/* a plan in the making: the flat tables, the switches, and the host image of the plan's device
+ * allocation, grown table by table (256-byte aligned offsets) */
+struct PlanBuild {
+  const ACMFlat *flat;
   ACMFlatInfo fi;
   ACMFlatView fv;
-  acm_flat_info (flat, &fi);
-  acm_flat_view (flat, &fv);
-  if (fi.lmax >= (1u << 24))
-    return ACM_GPU_E_INELIGIBLE;
-  const bool interned = fi.sym_bytes == 8;
+  PlanSwitches sw;
+  uint32_t lds_cap; /* dynamic LDS a workgroup can have: 160 KiB on gfx950 */
+  uint32_t kw_base;
+  std::vector<unsigned char> host;
+
+  size_t
+  reserve (size_t bytes) {
+    size_t cur = host.size ();
+    const size_t at = blob_reserve (cur, bytes);
+    host.resize (cur, 0);
+    return at;
+  }
+  template <typename T>
+  T *
+  at (size_t off) {
+    return reinterpret_cast<T *> (host.data () + off);
+  }
+};
+
+/* CSR tables (every plan: the CSR kernel takes any text), output info, depth_start */
+struct CommonTables {
+  size_t o_row, o_sym, o_next, o_fail, o_cnbo, o_oinfo, o_dstart;
+};
+
+void
+build_common (PlanBuild &B, CommonTables &T) {
+  const ACMFlatInfo &fi = B.fi;
+  const ACMFlatView &fv = B.fv;
+  const uint32_t n = fi.n_states;
+  T.o_row = B.reserve (((size_t)n + 1) * 4);
+  T.o_sym = B.reserve ((size_t)(fi.n_edges ? fi.n_edges : 1) * 4);
+  T.o_next = B.reserve ((size_t)(fi.n_edges ? fi.n_edges : 1) * 4);
+  T.o_fail = B.reserve ((size_t)n * 4);
+  T.o_cnbo = B.reserve ((size_t)n * 4);
+  T.o_oinfo = B.reserve ((size_t)n * 16);
+  T.o_dstart = B.reserve (((size_t)fi.lmax + 2) * 4);
+  memcpy (B.at<uint32_t> (T.o_row), fv.row_ptr, ((size_t)n + 1) * 4);
+  memcpy (B.at<uint32_t> (T.o_sym), fv.edge_sym, (size_t)fi.n_edges * 4);
+  memcpy (B.at<uint32_t> (T.o_next), fv.edge_next, (size_t)fi.n_edges * 4);
+  memcpy (B.at<uint32_t> (T.o_fail), fv.fail, (size_t)n * 4);
+  memcpy (B.at<uint32_t> (T.o_cnbo), fv.nb_outputs, (size_t)n * 4);
+  uint32_t *oi = B.at<uint32_t> (T.o_oinfo);
+  for (uint32_t s = 0; s < n; s++) {
+    const uint32_t nb = fv.nb_outputs[s];
+    const uint32_t t0 = fv.term_kw[s] != NONE ? s : fv.out_link[s];
+    oi[4 * s + 0] = nb;
+    oi[4 * s + 1] = nb ? fv.out_link[t0] : 0;
+    oi[4 * s + 2] = nb ? fv.depth[t0] : 0;
+    oi[4 * s + 3] = nb ? fv.term_kw[t0] + B.kw_base : 0;
+  }
+  memcpy (B.at<uint32_t> (T.o_dstart), fv.depth_start, ((size_t)fi.lmax + 2) * 4);
+}
+
+void
+bind_common (ACMPlan *p, const PlanBuild &B, const CommonTables &T, unsigned char *b) {
+  auto u32p = [&] (size_t off) { return reinterpret_cast<const uint32_t *> (b + off); };
+  p->csr.row_ptr = u32p (T.o_row);
+  p->csr.edge_sym = u32p (T.o_sym);
+  p->csr.edge_next = u32p (T.o_next);
+  p->csr.fail = u32p (T.o_fail);
+  p->csr.nb_outputs = u32p (T.o_cnbo);
+  p->csr.lmax = B.fi.lmax;
+  p->d_oinfo = reinterpret_cast<const uint4 *> (b + T.o_oinfo);
+  p->d_dstart = u32p (T.o_dstart);
+}
+
+/* dense kernel (dev_dense.h), continuation or sticky mode: failure-resolved rows of every state;
+ * LDS holds the rows of a breadth-first prefix [0, HD), continuation mode also hotfail (s) (2 bytes)
+ * of every other state */
+struct DenseTables {
+  bool on = false, cont = false; /* cont: continuation mode (2-byte entries), see scan_dense_kernel */
+  uint32_t entry_bytes = 0, rowbytes = 0, queue_bytes = 0, HD = 0, rows_lds = 0, image_bytes = 0;
+  std::vector<uint16_t> hotfail;
+  size_t o_dense = 0, o_contdh = 0, o_wrows = 0, o_chain = 0, o_image = 0;
+};
+
+/* Chain records (EmitCtx::chain).  A continuation item says: walk on from rowless state s and
+ * report what is longer than j + depth (hotfail (s)) after j more symbols.  When f(s) has a
+ * row (hotfail (s) = f(s)), every failure transition out of the trie below s lands no deeper
+ * than that bound, so the walk can only ever report along the goto path; and when that path
+ * is a single chain of r <= 8 symbols to a leaf t with no keyword ending on the way, the
+ * whole walk is one comparison of the next r text bytes: 2 independent loads instead of 4-8
+ * dependent ones in expand_items_once_kernel. */
+void
+fill_chain_records (const ACMFlatView &fv, uint32_t n, const DenseTables &D, uint32_t *ch) {
+  for (uint32_t s0 = D.HD; s0 < n; s0++) {
+    uint32_t *r = ch + 4 * (size_t)(s0 - D.HD);
+    const uint32_t dh = fv.depth[D.hotfail[s0]];
+    if (fv.fail[s0] >= D.HD || dh >= 4000)
+      continue;
+    uint64_t syms = 0;
+    uint32_t len = 0, st = s0;
+    bool ok = true;
+    while (fv.row_ptr[st + 1] > fv.row_ptr[st]) { /* until a leaf */
+      if (fv.row_ptr[st + 1] - fv.row_ptr[st] != 1 || len == 8 || (st != s0 && fv.term_kw[st] != NONE)) {
+        ok = false;
+        break;
+      }
+      syms |= (uint64_t)(fv.edge_sym[fv.row_ptr[st]] & 0xFFu) << (8 * len);
+      st = fv.edge_next[fv.row_ptr[st]];
+      len++;
+    }
+    if (!ok)
+      continue;
+    r[0] = (len ? len : 15u) | (dh << 4);
+    r[1] = st;
+    r[2] = (uint32_t)syms;
+    r[3] = (uint32_t)(syms >> 32);
+  }
+}
+
+int
+build_dense (PlanBuild &B, DenseTables &D) {
+  const ACMFlatInfo &fi = B.fi;
+  const ACMFlatView &fv = B.fv;
+  const uint32_t n = fi.n_states;
+  /* failure-resolved rows for byte alphabets whenever the whole DFA fits comfortably in HBM */
+  D.entry_bytes = n <= 32768 ? 2 : 4;
+  D.on = fi.sym_bytes == 1 && fi.n_edges > 0 && (uint64_t)n * fi.width < (1ull << 31) &&
+         (uint64_t)n * fi.width * D.entry_bytes <= (8ull << 30) && fi.lmax >= 1 && fi.lmax - 1 <= 16u * 255;
+  D.cont = D.on && D.entry_bytes == 2;
+  D.rowbytes = fi.width * D.entry_bytes;
+  /* (-DACM_DENSE_DIRECT_PARK: the dense kernel parks its items straight into HBM, no LDS queues) */
+  D.queue_bytes = DENSE_LDS_QUEUE ? (DENSE_THREADS / WAVE) * QCAP * 8 : 0;
+  if (D.on) {
+    const uint32_t budget = B.lds_cap - D.queue_bytes - 512;
+    if (D.cont) {
+      /* HD * rowbytes + (n - HD) * 2 <= budget */
+      const uint64_t fixed = (uint64_t)n * 2;
+      D.HD = fixed >= budget ? 1 : (uint32_t)((budget - fixed) / (D.rowbytes - 2));
+    } else
+      D.HD = budget / D.rowbytes;
+    if (D.HD > n)
+      D.HD = n;
+    if (D.HD < 1)
+      D.HD = 1;
+  }
+  if (D.cont) {
+    D.hotfail.resize (n);
+    for (uint32_t s = 0; s < n; s++) /* f(s) < s: one pass in breadth-first order */
+      D.hotfail[s] = (uint16_t)(s < D.HD ? s : D.hotfail[fv.fail[s]]);
+  }
+  /* (the rows and the LDS image take 16 bytes of the blob in plans without rows too) */
+  D.o_dense = B.reserve ((D.on ? (size_t)n * D.rowbytes : 0) + 16);
+  D.o_contdh = B.reserve (D.cont ? (size_t)n * 2 : 0);
+  D.o_wrows = B.reserve (D.cont ? (size_t)n * fi.width * 4 : 0);
+  D.o_chain = B.reserve (D.cont ? (size_t)(n - D.HD) * 16 + 16 : 0);
+  D.rows_lds = D.on ? ((D.HD * D.rowbytes + 15) & ~15u) : 0;
+  D.image_bytes = D.on ? ((D.rows_lds + (D.cont ? (n - D.HD) * 2 : 0) + 15) & ~15u) : 0;
+  D.o_image = B.reserve (D.image_bytes + 16);
+  if (!D.on)
+    return ACM_GPU_OK;
+  int rc = acm_flat_dense_rows (B.flat, n, D.entry_bytes, B.at<unsigned char> (D.o_dense));
+  if (rc)
+    return rc;
+  /* LDS image: the first HD rows, then hotfail of the states [HD, n) */
+  memcpy (B.at<unsigned char> (D.o_image), B.at<unsigned char> (D.o_dense), (size_t)D.HD * D.rowbytes);
+  if (D.cont) {
+    const uint16_t *r16 = B.at<uint16_t> (D.o_dense);
+    uint32_t *wr = B.at<uint32_t> (D.o_wrows);
+    for (size_t i = 0; i < (size_t)n * fi.width; i++)
+      wr[i] = r16[i] | (fv.depth[r16[i] & 0x7FFFu] << 16);
+    uint16_t *cdh = B.at<uint16_t> (D.o_contdh);
+    for (uint32_t s = 0; s < n; s++)
+      cdh[s] = (uint16_t)fv.depth[D.hotfail[s]];
+    memcpy (B.at<unsigned char> (D.o_image + D.rows_lds), D.hotfail.data () + D.HD, (size_t)(n - D.HD) * 2);
+    fill_chain_records (fv, n, D, B.at<uint32_t> (D.o_chain));
+  }
+  return ACM_GPU_OK;
+}
+
+void
+bind_dense (ACMPlan *p, const PlanBuild &B, const DenseTables &D, unsigned char *b) {
+  const ACMFlatInfo &fi = B.fi;
+  p->entry_bytes = D.entry_bytes;
+  if (!D.on)
+    return;
+  p->kind = PlanKind::Dense;
+  p->d_dense = b + D.o_dense;
+  p->d_lds_image = b + D.o_image;
+  p->d_cont_dh = D.cont ? reinterpret_cast<const uint16_t *> (b + D.o_contdh) : nullptr;
+  p->d_chain = D.cont ? reinterpret_cast<const uint4 *> (b + D.o_chain) : nullptr;
+  p->d_wrows = D.cont ? reinterpret_cast<const uint32_t *> (b + D.o_wrows) : nullptr;
+  p->lds_image_bytes = D.image_bytes;
+  DenseK &K = p->K;
+  K.W = fi.width;
+  K.rowbytes = D.rowbytes;
+  K.lo = fi.alpha_lo;
+  K.span = fi.alpha_span;
+  K.HD = D.HD;
+  K.aux_off = D.rows_lds;
+  K.queue_off = D.image_bytes;
+  K.wub = fi.lmax > 1 ? (fi.lmax - 1 + 15) / 16 : 0;
+  K.lmax = fi.lmax;
+  K.stream_stride = WAVE * p->chunk;
+}
+
+/* 4-gram sieve kernel (dev_gram.h, dev_gram2.h, dev_short.h): sizes and places of its tables */
+struct GramTables {
+  bool on = false;     /* the tables are made (the plan takes the kernel if they fit LDS: bind_gram) */
+  bool hashed = false; /* wide alphabets: hashed 4-byte windows instead of the exact base-W index */
+  bool shorts = false; /* keywords of 1-3 symbols */
+  bool gram2 = false;
+  uint32_t n_depth4 = 0, bits_bytes = 0, tab2_words = 0, g2_off = 0;
+  GramK K{}; /* the kernel's sizes (bind_gram adds the pointers) */
+  size_t o_g4bits, o_g3rec, o_stab, o_shimg, o_g4rec, o_grec, o_gedge, o_g4gid, o_kw4, o_g4prefix, o_g4entry, o_g5peek, o_tab2, o_rows2, o_over2;
+};
+
+/* LDS of the waves' queues (hit queue, walk queues, short-keyword queue of hashed windows) */
+uint32_t
+gram_queue_bytes (const GramTables &G) {
+  return (SPARSE_THREADS / WAVE) * ((G.shorts && G.hashed ? QCAP : 0u) + GRAM_Q1 + GRAM_Q2 + (G.hashed ? HITS_STRIDE : 0u)) * 8;
+}
+
+/* narrow alphabets: what LDS has left after the bits and the queues goes to the two Bloom filters
+ * of the record gather (GramK::bloom5_bits): 8 to 16 bits per terminal 4-gram, the rest for the
+ * 5-grams; not worth it below 4 bits per 5-gram or for dictionaries of a few hundred keywords */
+void
+size_gram_bloom (const PlanBuild &B, GramTables &G) {
+  const ACMFlatView &fv = B.fv;
+  GramK &K = G.K;
+  if (!G.on || G.hashed || G.n_depth4 < 2048 || !B.sw.bloom)
+    return;
+  K.bloom_off = (K.g3_off + K.g3_bytes + 15) & ~15u;
+  const uint64_t used = (uint64_t)K.bloom_off + gram_queue_bytes (G) + WALK_CTX_BYTES + 64;
+  uint32_t n_term4 = 0, n_5 = 0;
+  for (uint32_t st = fv.depth_start[4]; st < fv.depth_start[5]; st++) {
+    n_term4 += fv.term_kw[st] != NONE ? 1u : 0u;
+    n_5 += fv.row_ptr[st + 1] - fv.row_ptr[st];
+  }
+  if (used >= B.lds_cap)
+    return;
+  const uint64_t free_bits = ((uint64_t)B.lds_cap - used) / 16 * 16 * 8;
+  uint64_t tb = (uint64_t)n_term4 * 12 + 1024;
+  if (tb > free_bits / 3)
+    tb = free_bits / 3;
+  tb = tb / 128 * 128;
+  const uint64_t fb = (free_bits - tb) / 128 * 128;
+  if (tb >= 1024 && fb >= (uint64_t)n_5 * 2 && fb < (1u << 24)) {
+    K.bloomT_bits = (uint32_t)tb;
+    K.bloom5_bits = (uint32_t)fb;
+  }
+}
+
+/* Which byte dictionaries get the 4-gram tables, and their sizes and places in the blob.  They are
+ * the dictionaries that the LDS scheme of the dense kernel does not serve well: every automaton of
+ * more than 32,768 states, and the smaller ones whose hot set outgrows LDS: the share of a uniform
+ * text's positions that land in a state without an LDS row is estimated as the sum over those
+ * states of span^-depth; above 0.1 % the continuation items swamp the dense kernel (measured on
+ * a-z, ms per GiB, dense against 4-gram: 1,100 keywords 0.06 % -> 0.38 / 0.41; 1,250 keywords
+ * 0.13 % -> 0.46 / 0.42; 1,500 keywords 0.26 % -> 0.58 / 0.43; 3,000 keywords -> 9.0 / 0.48). */
+int
+build_gram (PlanBuild &B, const DenseTables &D, GramTables &G) {
+  const ACMFlatInfo &fi = B.fi;
+  const ACMFlatView &fv = B.fv;
+  const uint32_t n = fi.n_states;
+  GramK &K = G.K;
+  double rowless_share = 0;
+  if (D.cont && fi.alpha_span > 1) {
+    for (uint32_t s = D.HD; s < n; s++)
+      rowless_share += pow ((double)fi.alpha_span, -(double)fv.depth[s]);
+  }
+  const bool narrow = fi.width <= 30 && fi.width == fi.alpha_span + 1 && B.sw.gram != 3;
+  bool any_short = false;
+  for (uint32_t k = 0; k < fi.n_keywords; k++)
+    any_short |= fv.depth[fv.kw_state[k]] < 4;
+  G.on = D.on && (D.entry_bytes == 4 || B.sw.gram >= 2 || rowless_share > 0.001) && B.sw.gram != 0 && fi.lmax >= 4 && n < 0x40000000u;
+  if (!G.on) {
+    B.reserve (0); /* (the blob ends on a 256-byte boundary, as it always did behind the 4-gram tables) */
+    return ACM_GPU_OK;
+  }
+  G.shorts = any_short; /* a nibble per 3-gram + their ids (narrow: a pass of their own, scan_short_kernel; hashed: the kernel's third queue) */
+  G.hashed = !narrow;
+  const bool hashed = G.hashed, narrow_shorts = G.shorts && !hashed;
+  const uint32_t gW = K.W = fi.width;
+  K.lo = fi.alpha_lo;
+  K.span = fi.alpha_span;
+  K.bloom_log2 = 19; /* hashed: 64 KB of Bloom bits */
+  G.n_depth4 = fv.depth_start[5] - fv.depth_start[4];
+  K.wtab_log2 = 4;
+  while (hashed && (1u << K.wtab_log2) < 2 * G.n_depth4 + 2)
+    K.wtab_log2++;
+  uint32_t n_short = 0; /* hashed windows: keywords of 1-3 symbols */
+  for (uint32_t k = 0; k < fi.n_keywords && hashed && G.shorts; k++)
+    if (fv.depth[fv.kw_state[k]] < 4) {
+      n_short++;
+      K.short_lens |= 1u << (fv.depth[fv.kw_state[k]] - 1);
+    }
+  K.stab_log2 = 4;
+  while ((1u << K.stab_log2) < 2 * n_short + 2)
+    K.stab_log2++;
+  K.W4 = hashed ? 1u << K.wtab_log2 : gW * gW * gW * gW; /* 8-byte records of the second stage */
+  K.g4words = hashed ? (1u << K.bloom_log2) / 32 : (K.W4 + 31) / 32;
+  const uint32_t W3 = !hashed ? gW * gW * gW : 0;
+  K.g3_off = (K.g4words * 4 + 15) & ~15u; /* nibble table right after the 4-gram bits */
+  K.g3_bytes = narrow_shorts ? ((W3 + 1) / 2 + 15) & ~15u : 0;
+  size_gram_bloom (B, G);
+  G.bits_bytes = K.bloom5_bits ? K.bloom_off + (K.bloomT_bits + K.bloom5_bits) / 8 : K.g3_off + K.g3_bytes;
+  /* scan_gram2_kernel (dev_gram2.h: lane-local sieve on two bits per 4-gram, no queue push per
+   * position, no Bloom filters): narrow alphabets whose table fits LDS beside the waves' areas --
+   * up to 26 symbols + "other".  ACM_GPU_GRAM2=0: scan_gram_kernel. */
+  G.tab2_words = !hashed ? (K.W4 + 15) / 16 : 0;
+  G.g2_off = (G.tab2_words * 4 + 15) & ~15u;
+  G.gram2 = !hashed && B.sw.gram2 && (uint64_t)G.g2_off + G2_LDS_FIXED <= B.lds_cap;
+  G.o_g4bits = B.reserve ((size_t)G.bits_bytes + 16);
+  G.o_g3rec = B.reserve (narrow_shorts ? (size_t)W3 * 16 : 0);
+  G.o_stab = B.reserve (hashed && G.shorts ? ((size_t)8 << K.stab_log2) : 0);
+  /* scan_short_kernel's LDS image: the nibbles, the number of set nibble bits in front of every 8
+   * 3-grams, the keyword ids in the order of those bits (a keyword of d symbols is the id of W^(3-d) 3-grams) */
+  uint32_t sh_ids = 0;
+  for (uint32_t st = 1; narrow_shorts && st < fv.depth_start[4]; st++)
+    if (fv.term_kw[st] != NONE)
+      sh_ids += fv.depth[st] == 1 ? gW * gW : (fv.depth[st] == 2 ? gW : 1u);
+  K.sh_nib_bytes = K.g3_bytes;
+  K.sh_base_bytes = narrow_shorts ? (((W3 + 7) / 8) * 4 + 15) & ~15u : 0;
+  K.sh_ids_bytes = (sh_ids * 4 + 15) & ~15u;
+  G.o_shimg = B.reserve (narrow_shorts ? (size_t)K.sh_nib_bytes + K.sh_base_bytes + K.sh_ids_bytes + 16 : 0);
+  G.o_g4rec = B.reserve ((size_t)K.W4 * 8);
+  G.o_grec = B.reserve ((size_t)n * 32);
+  G.o_gedge = B.reserve ((size_t)fi.n_edges * 8);
+  K.d4_begin = fv.depth_start[4];
+  K.d5_begin = fv.depth_start[5]; /* (lmax >= 4: depth_start has lmax + 2 entries) */
+  G.o_g4gid = B.reserve ((size_t)(K.d5_begin - K.d4_begin) * 4 + 16);
+  G.o_kw4 = B.reserve ((size_t)G.n_depth4 * 4 + 16);
+  G.o_g4prefix = B.reserve (!hashed ? (size_t)K.g4words * 4 + 16 : 0);
+  G.o_g4entry = B.reserve (!hashed ? (size_t)G.n_depth4 * 12 + 16 : 0);
+  const uint32_t n_depth5 = fi.lmax >= 5 ? fv.depth_start[6] - fv.depth_start[5] : 0;
+  /* peek entries of 4 bytes while a record index fits 23 bits (ACM_GPU_PEEK8=1: 8 bytes anyway -- tests) */
+  K.peek_packed = n < (1u << 23) && !B.sw.peek8 ? 1u : 0u;
+  K.d5_rel = K.peek_packed; /* (fewer than 2^23 states in all: a record index leaves bits 24-29 free too) */
+  K.kw_inline = (uint64_t)fi.n_keywords + B.kw_base <= HIT_KW_ID ? 1u : 0u;
+  K.queue_off = G.bits_bytes;
+  G.o_g5peek = B.reserve (!hashed ? (size_t)n_depth5 * (K.peek_packed ? 4 : 8) + 16 : 0);
+  G.o_tab2 = B.reserve (G.gram2 ? (size_t)G.g2_off + 16 : 0);
+  /* (the second stage's entries by row, with scan_gram2_kernel: classes are below 30, bits 30 and 31 are flags) */
+  G.o_rows2 = B.reserve (G.gram2 ? (size_t)G.tab2_words * 64 + 16 : 0);
+  G.o_over2 = B.reserve (G.gram2 ? (size_t)G.n_depth4 * 8 + 16 : 0);
+
+  /* the host image: fill_gram_tables, the keyword ids of the depth-4 states, scan_short_kernel's image */
+  GramImage I{ hashed, G.shorts, gW, K.bloom_log2, K.wtab_log2, K.stab_log2 };
+  I.bits = B.at<uint32_t> (G.o_g4bits);
+  I.g4 = B.at<uint32_t> (G.o_g4rec);
+  I.rec = B.at<uint32_t> (G.o_grec);
+  I.edge = B.at<uint32_t> (G.o_gedge);
+  I.g4gid = B.at<uint32_t> (G.o_g4gid);
+  I.nib = B.at<unsigned char> (G.o_g4bits + K.g3_off);
+  I.prefix = B.at<uint32_t> (G.o_g4prefix);
+  I.entry = B.at<uint32_t> (G.o_g4entry);
+  I.peek = hashed ? nullptr : B.at<uint32_t> (G.o_g5peek);
+  I.bloom = K.bloom5_bits ? B.at<uint32_t> (G.o_g4bits + K.bloom_off) : nullptr;
+  I.bloomT_bits = K.bloomT_bits;
+  I.bloom5_bits = K.bloom5_bits;
+  I.lo = fi.alpha_lo;
+  I.kw_base = B.kw_base;
+  I.kw_inline = K.kw_inline != 0;
+  I.peek_packed = K.peek_packed != 0;
+  I.g3 = B.at<uint32_t> (G.o_g3rec);
+  I.stab = B.at<uint32_t> (G.o_stab);
+  I.tab2 = G.gram2 ? B.at<uint32_t> (G.o_tab2) : nullptr;
+  I.rows2 = G.gram2 ? B.at<uint32_t> (G.o_rows2) : nullptr;
+  I.over2 = G.gram2 ? B.at<uint32_t> (G.o_over2) : nullptr;
+  fill_gram_tables (fv, fi, I);
+  for (uint32_t st = fv.depth_start[4]; st < fv.depth_start[5]; st++)
+    B.at<uint32_t> (G.o_kw4)[st - fv.depth_start[4]] = fv.term_kw[st] == NONE ? NONE : fv.term_kw[st] + B.kw_base;
+  if (!narrow_shorts)
+    return ACM_GPU_OK;
+  unsigned char *img = B.at<unsigned char> (G.o_shimg);
+  memcpy (img, I.nib, (W3 + 1) / 2);
+  uint32_t *base = reinterpret_cast<uint32_t *> (img + K.sh_nib_bytes), *ids = reinterpret_cast<uint32_t *> (img + K.sh_nib_bytes + K.sh_base_bytes);
+  uint32_t r = 0;
+  for (uint32_t i3 = 0; i3 < W3; i3++) {
+    if ((i3 & 7) == 0)
+      base[i3 >> 3] = r;
+    const uint32_t nb = (I.nib[i3 >> 1] >> ((i3 & 1) * 4)) & 7u;
+    for (uint32_t d = 0; d < 3; d++)
+      if ((nb >> d) & 1u)
+        ids[r++] = I.g3[4 * (size_t)i3 + d];
+  }
+  return r == sh_ids ? ACM_GPU_OK : ACM_GPU_E_ARG; /* (the two counts are of the same keywords) */
+}
+
+/* The plan takes the 4-gram kernel when its bits and queues fit LDS; else it stays a dense plan,
+ * with the 4-gram tables left unused in its blob. */
+void
+bind_gram (ACMPlan *p, const PlanBuild &B, const GramTables &G, unsigned char *b) {
+  if (!G.on || (uint64_t)G.bits_bytes + gram_queue_bytes (G) + WALK_CTX_BYTES > B.lds_cap)
+    return;
+  auto u32p = [&] (size_t off) { return reinterpret_cast<const uint32_t *> (b + off); };
+  p->kind = PlanKind::Gram;
+  p->hashed = G.hashed;
+  p->inline_shorts = G.shorts && G.hashed;
+  p->short_pass = G.shorts && !G.hashed;
+  p->gram2 = G.gram2;
+  p->d_kw4 = u32p (G.o_kw4);
+  GramK &K = p->GK;
+  K = G.K;
+  K.g4prefix = u32p (G.o_g4prefix);
+  K.g4entry = u32p (G.o_g4entry);
+  K.g5peek = u32p (G.o_g5peek);
+  K.g4rec = reinterpret_cast<const uint2 *> (b + G.o_g4rec);
+  K.g4bits = u32p (G.o_g4bits);
+  K.srec = reinterpret_cast<const uint4 *> (b + G.o_grec);
+  K.sedge = reinterpret_cast<const uint2 *> (b + G.o_gedge);
+  K.g4gid = u32p (G.o_g4gid);
+  K.g3rec = reinterpret_cast<const uint4 *> (b + G.o_g3rec);
+  K.wtab = reinterpret_cast<const uint2 *> (b + G.o_g4rec);
+  K.stab = reinterpret_cast<const uint2 *> (b + G.o_stab);
+  K.sh_img = u32p (G.o_shimg);
+  /* the ids in LDS too while they fit (29 K of them beside the tables and the waves' areas) */
+  p->short_ids_lds = (uint64_t)K.sh_nib_bytes + K.sh_base_bytes + K.sh_ids_bytes + SH_LDS_FIXED <= B.lds_cap;
+  p->short_lds_bytes = K.sh_nib_bytes + K.sh_base_bytes + (p->short_ids_lds ? K.sh_ids_bytes : 0u) + SH_LDS_FIXED;
+  p->short_lds_count_bytes = K.sh_nib_bytes + SH_LDS_FIXED;
+  p->short_blocks_per_cu = 2u * (K.sh_nib_bytes + SH_LDS_FIXED) <= 160u * 1024u ? 2u : 1u; /* (count-only: the nibbles alone) */
+  if (B.sw.short_blocks1)
+    p->short_blocks_per_cu = 1;
+  p->gram_lds_bytes = G.bits_bytes + gram_queue_bytes (G) + WALK_CTX_BYTES;
+  if (G.gram2) {
+    K.rows2 = reinterpret_cast<const uint2 *> (b + G.o_rows2);
+    K.over2 = reinterpret_cast<const uint2 *> (b + G.o_over2);
+    K.tab2 = u32p (G.o_tab2);
+    K.tab2_words = G.tab2_words;
+    K.g2_off = G.g2_off;
+    p->gram_lds_bytes = G.g2_off + G2_LDS_FIXED;
+  }
+}
+
+/* 2- and 4-byte symbols: the sparse walk's tables (state records, (symbol, next) edges, root table by
+ * symbol value) and, for fewer than 2^30 states, the same three for the start-parallel kernel (flags
+ * mean something else there) and its pair table.  A start-parallel plan keeps the sparse tables:
+ * a segment of text that is not 16-byte aligned takes the sparse walk. */
+struct SparseTables {
+  bool on = false, starts = false;
+  uint32_t lut_size = 0;
+  size_t o_srec, o_sedge, o_lut, o_trec, o_tedge, o_tlut, o_tpairs;
+};
+
+void
+build_sparse (PlanBuild &B, const DenseTables &D, SparseTables &S) {
+  const ACMFlatInfo &fi = B.fi;
+  const ACMFlatView &fv = B.fv;
+  const uint32_t n = fi.n_states;
+  S.on = !D.on && fi.sym_bytes >= 2 && fi.n_edges > 0 && n < 0x7FFFFFFFu;
+  if (!S.on)
+    return;
+  const uint32_t root_edges = fv.row_ptr[1];
+  const uint64_t top = root_edges ? (uint64_t)fv.edge_sym[root_edges - 1] + 1 : 0; /* rows are in ascending order */
+  S.lut_size = (uint32_t)(top < (1ull << 22) ? top : (1ull << 22));
+  S.lut_size = (S.lut_size + 3) & ~3u;
+  S.starts = n < 0x40000000u;
+  S.o_srec = B.reserve ((size_t)n * 32);
+  S.o_sedge = B.reserve ((size_t)fi.n_edges * 8);
+  S.o_lut = B.reserve ((size_t)S.lut_size * 4 + 16);
+  if (S.starts) {
+    S.o_trec = B.reserve ((size_t)n * 32);
+    S.o_tedge = B.reserve ((size_t)fi.n_edges * 8);
+    S.o_tlut = B.reserve ((size_t)S.lut_size * 4 + 16);
+    S.o_tpairs = B.reserve ((size_t)n * 8); /* by state id; filled for the root's children */
+  }
+  fill_sparse_tables (fv, fi, S.lut_size, B.at<uint32_t> (S.o_srec), B.at<uint32_t> (S.o_sedge), B.at<uint32_t> (S.o_lut));
+  if (S.starts)
+    fill_starts_tables (fv, fi, S.lut_size, B.at<uint32_t> (S.o_trec), B.at<uint32_t> (S.o_tedge), B.at<uint32_t> (S.o_tlut),
+                        B.at<uint32_t> (S.o_tpairs));
+}
+
+/* what acm_gpu_plan_update edits: the host copy of the start-parallel tables (nullptr when out of memory) */
+StartsMirror *
+make_starts_mirror (PlanBuild &B, const SparseTables &S, size_t o_oinfo, unsigned char *b) {
+  const ACMFlatInfo &fi = B.fi;
+  const ACMFlatView &fv = B.fv;
+  const uint32_t n = fi.n_states;
+  StartsMirror *M = new (std::nothrow) StartsMirror ();
+  if (!M)
+    return nullptr;
+  auto words = [&] (size_t off, size_t cnt) {
+    const uint32_t *w = B.at<uint32_t> (off);
+    return std::vector<uint32_t> (w, w + cnt);
+  };
+  M->tab[PT_REC] = words (S.o_trec, (size_t)n * 8);
+  M->tab[PT_EDGE] = words (S.o_tedge, (size_t)fi.n_edges * 2);
+  M->tab[PT_LUT] = words (S.o_tlut, S.lut_size);
+  M->tab[PT_PAIRS] = words (S.o_tpairs, (size_t)n * 2);
+  M->tab[PT_OINFO] = words (o_oinfo, (size_t)n * 4);
+  M->parent.assign (n, 0);
+  M->parent_sym.assign (n, 0);
+  M->depth.assign (fv.depth, fv.depth + n);
+  for (uint32_t st = 0; st < n; st++) {
+    M->tab[PT_REC][8 * (size_t)st] = st ? fv.row_ptr[st + 1] - fv.row_ptr[st] : M->tab[PT_REC][1]; /* row capacity = its size */
+    for (uint32_t e = fv.row_ptr[st]; e < fv.row_ptr[st + 1]; e++) {
+      M->parent[fv.edge_next[e]] = st;
+      M->parent_sym[fv.edge_next[e]] = fv.edge_sym[e];
+    }
+  }
+  M->dev[PT_REC] = reinterpret_cast<uint32_t *> (b + S.o_trec);
+  M->dev[PT_EDGE] = reinterpret_cast<uint32_t *> (b + S.o_tedge);
+  M->dev[PT_LUT] = reinterpret_cast<uint32_t *> (b + S.o_tlut);
+  M->dev[PT_PAIRS] = reinterpret_cast<uint32_t *> (b + S.o_tpairs);
+  M->dev[PT_OINFO] = reinterpret_cast<uint32_t *> (b + o_oinfo);
+  M->cap[PT_LUT] = S.lut_size;
+  M->n_states = n;
+  M->n_edges = fi.n_edges;
+  M->n_keywords = fi.n_keywords;
+  M->lmax = fi.lmax;
+  return M;
+}
+
+void
+bind_sparse (ACMPlan *p, PlanBuild &B, const SparseTables &S, size_t o_oinfo, unsigned char *b) {
+  const ACMFlatInfo &fi = B.fi;
+  if (!S.on)
+    return;
+  const uint32_t tps = 128 / fi.sym_bytes;
+  const uint32_t warm = fi.lmax > 1 ? fi.lmax - 1 : 0;
+  const uint32_t sparse_queue_bytes = (SPARSE_THREADS / WAVE) * QCAP * 8;
+  p->kind = S.starts && !B.sw.sparse_walk ? PlanKind::Starts : PlanKind::Sparse;
+  p->sparse_lut_lds = (uint64_t)S.lut_size * 4 + sparse_queue_bytes + 512 <= B.lds_cap;
+  p->SK.srec = reinterpret_cast<const uint4 *> (b + S.o_srec);
+  p->SK.sedge = reinterpret_cast<const uint2 *> (b + S.o_sedge);
+  p->SK.lut = reinterpret_cast<const uint32_t *> (b + S.o_lut);
+  p->SK.lut_size = S.lut_size;
+  p->SK.warm_subs = (warm + tps - 1) / tps;
+  p->SK.warm_skip = p->SK.warm_subs * tps - warm;
+  p->SK.queue_off = p->sparse_lut_lds ? S.lut_size * 4 : 0;
+  p->SK.R = 0; /* per launch */
+  p->sparse_lds_bytes = p->SK.queue_off + sparse_queue_bytes + 16;
+  if (!S.starts)
+    return;
+  p->TK.srec = reinterpret_cast<const uint4 *> (b + S.o_trec);
+  p->TK.sedge = reinterpret_cast<const uint2 *> (b + S.o_tedge);
+  p->TK.lut = reinterpret_cast<const uint32_t *> (b + S.o_tlut);
+  p->TK.pairs = reinterpret_cast<const uint2 *> (b + S.o_tpairs);
+  p->TK.lut_size = S.lut_size;
+  const uint32_t starts_queue_bytes = (SPARSE_THREADS / WAVE) * (QCAP + HITS_STRIDE) * 8;
+  p->starts_lut_lds = (uint64_t)S.lut_size * 4 + starts_queue_bytes + WALK_CTX_BYTES <= B.lds_cap;
+  p->TK.queue_off = p->starts_lut_lds ? S.lut_size * 4 : 0;
+  p->TK.R = 0;
+  p->starts_lds_bytes = p->TK.queue_off + starts_queue_bytes + WALK_CTX_BYTES;
+  if (p->kind == PlanKind::Starts)
+    p->mir = make_starts_mirror (B, S, o_oinfo, b);
+}
+
+/* ACMPlanInfo of a plan whose tables are made and bound */
+void
+fill_plan_info (ACMPlan *p, const DenseTables &D) {
+  ACMPlanInfo &I = p->info;
+  I.device = p->device;
+  I.kernel = (uint32_t)p->kind;
+  I.entry_bytes = D.on ? D.entry_bytes : 0;
+  I.width = p->finfo.width;
+  I.dense_rows = D.on ? p->finfo.n_states : 0;
+  I.lds_rows = D.HD;
+  I.lds_hotfail = D.cont ? p->finfo.n_states - D.HD : 0;
+  I.table_bytes = p->blob_bytes;
+  I.chunk_bytes = p->chunk;
+  I.streams = p->streams;
+  I.grid_blocks = (uint32_t)p->cu_count;
+  I.block_threads = SPARSE_THREADS;
+  switch (p->kind) {
+  case PlanKind::Dense:
+    I.lds_bytes = D.image_bytes + D.queue_bytes + 16 /* tile counter */;
+    I.block_threads = DENSE_THREADS;
+    break;
+  case PlanKind::Csr:
+    I.lds_bytes = QCAP * 8;
+    I.block_threads = WAVE;
+    I.grid_blocks = (uint32_t)p->cu_count * 16;
+    break;
+  case PlanKind::Sparse:
+  case PlanKind::Starts:
+    I.lds_bytes = p->kind == PlanKind::Starts ? p->starts_lds_bytes : p->sparse_lds_bytes;
+    I.streams = p->kind == PlanKind::Starts ? 1 : SPARSE_S;
+    I.chunk_bytes = 128;
+    break;
+  case PlanKind::Gram:
+    I.lds_bytes = p->gram_lds_bytes;
+    I.streams = 1;
+    I.chunk_bytes = 16;
+    break;
+  }
+}
+
+/* every table of the plan: host image, one device allocation, pointers */
+int
+build_tables (PlanBuild &B, ACMPlan *p) {
+  CommonTables T;
+  DenseTables D;
+  SparseTables S;
+  GramTables G;
+  build_common (B, T);
+  int rc = build_dense (B, D);
+  if (rc)
+    return rc;
+  build_sparse (B, D, S);
+  rc = build_gram (B, D, G); /* (last: the blob's size, table_bytes, is what it always was) */
+  if (rc)
+    return rc;
+  const size_t bytes = B.host.size ();
+  p->blob_bytes = bytes;
+  if (hipMalloc (&p->blob, bytes) != hipSuccess)
+    return ACM_GPU_E_NOMEM;
+  if (hipMemcpy (p->blob, B.host.data (), bytes, hipMemcpyHostToDevice) != hipSuccess)
+    return ACM_GPU_E_HIP;
+  const size_t ctl_bytes = 16 + 2 * POOL_CLASSES * POOL_CTR_STRIDE * sizeof (unsigned int);
+  if (hipMalloc (reinterpret_cast<void **> (&p->d_total), ctl_bytes) != hipSuccess || hipMemset (p->d_total, 0, ctl_bytes) != hipSuccess)
+    return ACM_GPU_E_NOMEM;
+  p->d_pool_ctr = reinterpret_cast<unsigned int *> (p->d_total + 2);
+  unsigned char *b = static_cast<unsigned char *> (p->blob);
+  bind_common (p, B, T, b);
+  bind_dense (p, B, D, b);
+  bind_gram (p, B, G, b);
+  bind_sparse (p, B, S, T.o_oinfo, b);
+  fill_plan_info (p, D);
+  return ACM_GPU_OK;
+}
+
+/* the dynamic LDS of the kernels the plan launches */
+int
+set_lds_attributes (const ACMPlan *p) {
+  const uint32_t sb = p->finfo.sym_bytes;
+  for (int co = 0; co < 2; co++) {
+    switch (p->kind) {
+    case PlanKind::Dense:
+      HIP_TRY (hipFuncSetAttribute (dense_kernel_ptr (p->entry_bytes, p->chunk, p->streams, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)p->info.lds_bytes));
+      break;
+    case PlanKind::Starts:
+      HIP_TRY (hipFuncSetAttribute (starts_kernel_ptr (sb, p->starts_lut_lds, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)p->starts_lds_bytes));
+      [[fallthrough]]; /* (the sparse walk takes the segments that are not 16-byte aligned) */
+    case PlanKind::Sparse:
+      HIP_TRY (hipFuncSetAttribute (sparse_kernel_ptr (sb, p->sparse_lut_lds, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)p->sparse_lds_bytes));
+      break;
+    case PlanKind::Gram:
+      HIP_TRY (hipFuncSetAttribute (gram_kernel_ptr (co != 0, p->inline_shorts, p->hashed, false, p->gram2), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)p->gram_lds_bytes));
+      if (p->short_pass)
+        HIP_TRY (hipFuncSetAttribute (short_kernel_ptr (co != 0, p->short_ids_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)(co ? p->short_lds_count_bytes : p->short_lds_bytes)));
+      break;
+    case PlanKind::Csr: break;
+    }
+  }
+  if (p->kind == PlanKind::Gram && !p->hashed)
+    HIP_TRY (hipFuncSetAttribute (gram_kernel_ptr (false, p->inline_shorts, false, true, p->gram2), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)p->gram_lds_bytes));
+  return ACM_GPU_OK;
+}
+
+/* 8-byte symbols: hash table {key, id} of the dictionary's symbols, through which the text is interned */
+int
+upload_intern_table (ACMPlan *p, const ACMFlatView &fv) {
+  uint32_t cap = 16;
+  while (cap < 2 * (fv.n_keys64 + 1))
+    cap <<= 1;
+  std::vector<uint32_t> tab ((size_t)cap * 4, 0);
+  auto mix = [] (uint64_t x) {
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+  };
+  for (uint32_t k = 0; k < fv.n_keys64; k++) {
+    const uint64_t key = fv.keys64[k];
+    uint32_t h = (uint32_t)mix (key) & (cap - 1);
+    while (tab[4 * (size_t)h + 2])
+      h = (h + 1) & (cap - 1);
+    tab[4 * (size_t)h] = (uint32_t)key;
+    tab[4 * (size_t)h + 1] = (uint32_t)(key >> 32);
+    tab[4 * (size_t)h + 2] = k + 1;
+  }
+  if (hipMalloc (reinterpret_cast<void **> (&p->d_intern), (size_t)cap * 16) != hipSuccess ||
+      hipMemcpy (p->d_intern, tab.data (), (size_t)cap * 16, hipMemcpyHostToDevice) != hipSuccess)
+    return ACM_GPU_E_NOMEM;
+  p->intern_mask = cap - 1;
+  return ACM_GPU_OK;
+}
+
+/* what maps a text to the symbols the kernels walk: the intern table of 8-byte symbols, the
+ * comparator classes of 4-byte symbols (cls32), the class LUT of 1- and 2-byte symbols */
+int
+build_text_side (ACMPlan *p, const PlanBuild &B, bool interned) {
+  const ACMFlatView &fv = B.fv;
   if (interned) {
-    if (!fv.keys64 && fi.n_edges)
+    int rc = upload_intern_table (p, fv);
+    if (rc)
+      return rc;
+  }
+  if (fv.keys32 || (B.fi.sym_bytes == 4 && fv.class_rep32)) {
+    p->cls32 = true;
+    for (uint32_t i = 0; i < fv.n_keys32; i++)
+      p->cls32_known[fv.keys32[i]] = fv.keys32_class[i];
+    p->cls32_reps.assign (fv.class_rep32, fv.class_rep32 + fv.n_classes);
+    if (hipMalloc (reinterpret_cast<void **> (&p->d_unknown), (size_t)(p->cls32_cap + 1) * 4) != hipSuccess)
+      return ACM_GPU_E_NOMEM;
+  }
+  if (fv.class_map) {
+    /* 65,536 entries either way: 2-byte symbols directly, bytes in pairs (see classmap_kernel) */
+    std::vector<uint16_t> lut (65536);
+    if (B.fi.sym_bytes == 1) {
+      for (uint32_t v = 0; v < 65536; v++)
+        lut[v] = (uint16_t)((fv.class_map[v >> 8] << 8) | (fv.class_map[v & 255] & 255));
+    } else
+      memcpy (lut.data (), fv.class_map, 65536 * 2);
+    if (hipMalloc (reinterpret_cast<void **> (&p->d_classlut), 65536 * 2) != hipSuccess ||
+        hipMemcpy (p->d_classlut, lut.data (), 65536 * 2, hipMemcpyHostToDevice) != hipSuccess)
+      return ACM_GPU_E_NOMEM;
+    HIP_TRY (hipFuncSetAttribute (reinterpret_cast<const void *> (&classmap_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * 2));
+  }
+  return ACM_GPU_OK;
+}
+
+/* kw_base: added to every keyword id the plan reports (the delta plans of acm_gpu_plan_update) */
+int
+plan_create (const ACMFlat *flat, int device, uint32_t kw_base, ACMPlan **out) {
+  if (!flat || !out)
+    return ACM_GPU_E_ARG;
+  hipDeviceProp_t prop;
+  int rc = device_properties (device, &prop);
+  if (rc)
+    return rc;
+  PlanBuild B{};
+  B.flat = flat;
+  acm_flat_info (flat, &B.fi);
+  acm_flat_view (flat, &B.fv);
+  B.lds_cap = (uint32_t)prop.maxSharedMemoryPerMultiProcessor >= 160 * 1024 ? 160 * 1024 : 64 * 1024;
+  B.kw_base = kw_base;
+  if (B.fi.lmax >= (1u << 24))
+    return ACM_GPU_E_INELIGIBLE;
+  const bool interned = B.fi.sym_bytes == 8;
+  if (interned) {
+    if (!B.fv.keys64 && B.fi.n_edges)
       return ACM_GPU_E_ARG;
-    fi.sym_bytes = 4; /* from here on: a machine over 4-byte ids */
+    B.fi.sym_bytes = 4; /* from here on: a machine over 4-byte ids */
   }
 
   ACMPlan *p = new (std::nothrow) ACMPlan ();
   if (!p)
     return ACM_GPU_E_NOMEM;
   p->device = device;
-  p->finfo = fi;
+  p->finfo = B.fi;
   p->kw_base = kw_base;
-  p->covered_keywords = fi.n_keywords;
-  p->text_sym_bytes = interned ? 8 : fi.sym_bytes;
+  p->covered_keywords = B.fi.n_keywords;
+  p->text_sym_bytes = interned ? 8 : B.fi.sym_bytes;
   p->cu_count = prop.multiProcessorCount;
-
-  if (const char *e = getenv ("ACM_GPU_SEGMENT_LOG2")) {
-    const int lg = atoi (e);
-    if (lg >= 12 && lg <= 31)
-      p->segment = 1ull << lg;
+  if (B.sw.segment_log2 >= 12 && B.sw.segment_log2 <= 31)
+    p->segment = 1ull << B.sw.segment_log2;
+  /* tests: fewer workgroups than CUs, so that one wave sees many tiles of a small text (the
+   * overflow path of the item regions fires hundreds of times per wave) */
+  if (B.sw.grid_blocks >= 1 && B.sw.grid_blocks < p->cu_count)
+    p->cu_count = B.sw.grid_blocks;
+  rc = build_tables (B, p);
+  if (!rc)
+    rc = set_lds_attributes (p);
+  if (!rc)
+    rc = build_text_side (p, B, interned);
+  if (rc) {
+    acm_gpu_plan_destroy (p); /* (takes a plan built part of the way) */
+    return rc;
   }
-  /* failure-resolved rows for byte alphabets whenever the whole DFA fits comfortably in HBM */
-  const uint32_t n = fi.n_states;
-  const uint32_t entry_bytes = n <= 32768 ? 2 : 4;
-  const bool dense = fi.sym_bytes == 1 && fi.n_edges > 0 && (uint64_t)n * fi.width < (1ull << 31) &&
-                     (uint64_t)n * fi.width * entry_bytes <= (8ull << 30) && fi.lmax >= 1 && fi.lmax - 1 <= 16u * 255;
-  const bool cont = dense && entry_bytes == 2; /* continuation mode, see scan_dense_kernel */
-  const uint32_t rowbytes = fi.width * entry_bytes;
-  /* (-DACM_DENSE_DIRECT_PARK: the dense kernel parks its items straight into HBM, no LDS queues) */
-  const uint32_t queue_bytes = DENSE_LDS_QUEUE ? (DENSE_THREADS / WAVE) * QCAP * 8 : 0;
-
-  /* ---- LDS budget: rows of a breadth-first prefix [0, HD); continuation mode also keeps
-   *      hotfail(s) (2 bytes) for every other state */
-  uint32_t HD = 0;
-  if (dense) {
-    const uint32_t lds_total = (uint32_t)prop.maxSharedMemoryPerMultiProcessor >= 160 * 1024 ? 160 * 1024 : 64 * 1024;
-    const uint32_t budget = lds_total - queue_bytes - 512;
-    if (cont) {
-      /* HD * rowbytes + (n - HD) * 2 <= budget */
-      const uint64_t fixed = (uint64_t)n * 2;
-      HD = fixed >= budget ? 1 : (uint32_t)((budget - fixed) / (rowbytes - 2));
-    } else
-      HD = budget / rowbytes;
-    if (HD > n)
-      HD = n;
-    if (HD < 1)
-      HD = 1;
-  }
-  std::vector<uint16_t> hotfail;
-  if (cont) {
-    hotfail.resize (n);
-    for (uint32_t s = 0; s < n; s++) /* f(s) < s: one pass in breadth-first order */
-      hotfail[s] = (uint16_t)(s < HD ? s : hotfail[fv.fail[s]]);
-  }
-
-  /* ---- device blob layout */
-  size_t cur = 0;
-  const size_t o_row = blob_reserve (cur, ((size_t)n + 1) * 4);
-  const size_t o_sym = blob_reserve (cur, (size_t)(fi.n_edges ? fi.n_edges : 1) * 4);
-  const size_t o_next = blob_reserve (cur, (size_t)(fi.n_edges ? fi.n_edges : 1) * 4);
-  const size_t o_fail = blob_reserve (cur, (size_t)n * 4);
-  const size_t o_cnbo = blob_reserve (cur, (size_t)n * 4);
-  const size_t o_oinfo = blob_reserve (cur, (size_t)n * 16);
-  const size_t dense_bytes = dense ? (size_t)n * rowbytes : 0;
-  const size_t o_dense = blob_reserve (cur, dense_bytes + 16);
-  const size_t o_contdh = blob_reserve (cur, cont ? (size_t)n * 2 : 0);
-  const size_t o_wrows = blob_reserve (cur, cont ? (size_t)n * fi.width * 4 : 0);
-  const size_t o_chain = blob_reserve (cur, cont ? (size_t)(n - HD) * 16 + 16 : 0);
-  const size_t o_dstart = blob_reserve (cur, ((size_t)fi.lmax + 2) * 4);
-  const uint32_t rows_lds = dense ? ((HD * rowbytes + 15) & ~15u) : 0;
-  const uint32_t image_bytes = dense ? ((rows_lds + (cont ? (n - HD) * 2 : 0) + 15) & ~15u) : 0;
-  const size_t o_image = blob_reserve (cur, image_bytes + 16);
-  /* sparse kernel tables: state records, (symbol, next) edges, root table by symbol value */
-  const bool sparse = !dense && fi.sym_bytes >= 2 && fi.n_edges > 0 && n < 0x7FFFFFFFu;
-  uint32_t lut_size = 0;
-  if (sparse) {
-    const uint32_t root_edges = fv.row_ptr[1];
-    const uint64_t top = root_edges ? (uint64_t)fv.edge_sym[root_edges - 1] + 1 : 0; /* rows are in ascending order */
-    lut_size = (uint32_t)(top < (1ull << 22) ? top : (1ull << 22));
-    lut_size = (lut_size + 3) & ~3u;
-  }
-  const size_t o_srec = blob_reserve (cur, sparse ? (size_t)n * 32 : 0);
-  const size_t o_sedge = blob_reserve (cur, sparse ? (size_t)fi.n_edges * 8 : 0);
-  const size_t o_lut = blob_reserve (cur, sparse ? (size_t)lut_size * 4 + 16 : 0);
-  /* the same three tables for the start-parallel kernel (flags mean something else there) */
-  const bool starts = sparse && n < 0x40000000u;
-  const size_t o_trec = blob_reserve (cur, starts ? (size_t)n * 32 : 0);
-  const size_t o_tedge = blob_reserve (cur, starts ? (size_t)fi.n_edges * 8 : 0);
-  const size_t o_tlut = blob_reserve (cur, starts ? (size_t)lut_size * 4 + 16 : 0);
-  const size_t o_tpairs = blob_reserve (cur, starts ? (size_t)n * 8 : 0); /* by state id; filled for the root's children */
-  /* 4-gram sieve kernel: byte dictionaries that the LDS scheme of the dense kernel does not serve
-   * well.  That is every automaton of more than 32,768 states, and the smaller ones whose hot set
-   * outgrows LDS: the share of a uniform text's positions that land in a state without an LDS row
-   * is estimated as the sum over those states of span^-depth; above 0.1 % the continuation items
-   * swamp the dense kernel (measured on a-z, ms per GiB, dense against 4-gram: 1,100 keywords
-   * 0.06 % -> 0.38 / 0.41; 1,250 keywords 0.13 % -> 0.46 / 0.42; 1,500 keywords 0.26 % -> 0.58 /
-   * 0.43; 3,000 keywords -> 9.0 / 0.48). */
-  const char *gram_env = getenv ("ACM_GPU_GRAM"); /* 0: never; 2: whenever the dictionary qualifies (experiments) */
-  const int gram_mode = gram_env ? atoi (gram_env) : 1;
-  double rowless_share = 0;
-  if (cont && fi.alpha_span > 1) {
-    for (uint32_t s = HD; s < n; s++)
-      rowless_share += pow ((double)fi.alpha_span, -(double)fv.depth[s]);
-  }
-  const bool gram_narrow = fi.width <= 30 && fi.width == fi.alpha_span + 1 && gram_mode != 3; /* 3: hashed windows always (experiments) */
-  bool any_short = false;
-  for (uint32_t k = 0; k < fi.n_keywords; k++)
-    any_short |= fv.depth[fv.kw_state[k]] < 4;
-  const bool gram_big = dense && (entry_bytes == 4 || gram_mode >= 2 || rowless_share > 0.001) && gram_mode != 0 &&
-                        fi.lmax >= 4 && n < 0x40000000u;
-  bool gram_shorts = gram_big && any_short; /* keywords of 1-3 symbols: a nibble per 3-gram + their ids (narrow alphabets: a pass of their own, scan_short_kernel; hashed windows: the kernel's third queue) */
-  /* wide alphabets: hashed 4-byte windows instead of the exact base-W index */
-  const bool gram_wide = gram_big && !gram_narrow;
-  bool gram = gram_big;
-  if (!gram)
-    gram_shorts = false;
-  const uint32_t gW = fi.width;
-  const uint32_t bloom_log2 = 19; /* wide: 64 KB of Bloom bits */
-  const uint32_t n_depth4 = gram ? fv.depth_start[5] - fv.depth_start[4] : 0;
-  uint32_t wtab_log2 = 4;
-  while (gram_wide && (1u << wtab_log2) < 2 * n_depth4 + 2)
-    wtab_log2++;
-  uint32_t n_short = 0, short_lens = 0; /* wide alphabets: keywords of 1-3 symbols */
-  for (uint32_t k = 0; k < fi.n_keywords && gram_wide && gram_shorts; k++)
-    if (fv.depth[fv.kw_state[k]] < 4) {
-      n_short++;
-      short_lens |= 1u << (fv.depth[fv.kw_state[k]] - 1);
-    }
-  uint32_t stab_log2 = 4;
-  while ((1u << stab_log2) < 2 * n_short + 2)
-    stab_log2++;
-  const uint32_t gW4 = !gram ? 0 : (gram_wide ? 1u << wtab_log2 : gW * gW * gW * gW); /* 8-byte records of the second stage */
-  const uint32_t g4words = gram ? (gram_wide ? (1u << bloom_log2) / 32 : (gW4 + 31) / 32) : 0;
-  const uint32_t gW3 = gram && !gram_wide ? gW * gW * gW : 0;
-  const uint32_t g3_off = (g4words * 4 + 15) & ~15u;                 /* nibble table right after the 4-gram bits */
-  const uint32_t g3_bytes = gram_shorts && !gram_wide ? ((gW3 + 1) / 2 + 15) & ~15u : 0;
-  /* narrow alphabets: what LDS has left after the bits and the queues goes to the two Bloom filters
-   * of the record gather (GramK::bloom5_bits): 8 to 16 bits per terminal 4-gram, the rest for the
-   * 5-grams; not worth it below 4 bits per 5-gram or for dictionaries of a few hundred keywords */
-  uint32_t bloom_off = 0, bloomT_bits = 0, bloom5_bits = 0;
-  const char *bloom_env = getenv ("ACM_GPU_BLOOM"); /* 0: no Bloom filters (experiments) */
-  if (gram && !gram_wide && n_depth4 >= 2048 && !(bloom_env && atoi (bloom_env) == 0)) {
-    const uint32_t lds_cap = (uint32_t)prop.maxSharedMemoryPerMultiProcessor >= 160 * 1024 ? 160 * 1024 : 64 * 1024;
-    const uint32_t gq_bytes = (SPARSE_THREADS / WAVE) * ((gram_shorts && gram_wide ? QCAP : 0u) + GRAM_Q1 + GRAM_Q2 + (gram_wide ? HITS_STRIDE : 0u)) * 8;
-    bloom_off = (g3_off + g3_bytes + 15) & ~15u;
-    const uint64_t used = (uint64_t)bloom_off + gq_bytes + WALK_CTX_BYTES + 64;
-    uint32_t n_term4 = 0, n_5 = 0;
-    for (uint32_t st = fv.depth_start[4]; st < fv.depth_start[5]; st++) {
-      n_term4 += fv.term_kw[st] != NONE ? 1u : 0u;
-      n_5 += fv.row_ptr[st + 1] - fv.row_ptr[st];
-    }
-    if (used < lds_cap) {
-      const uint64_t free_bits = ((uint64_t)lds_cap - used) / 16 * 16 * 8;
-      uint64_t tb = (uint64_t)n_term4 * 12 + 1024;
-      if (tb > free_bits / 3)
-        tb = free_bits / 3;
-      tb = tb / 128 * 128;
-      const uint64_t fb = (free_bits - tb) / 128 * 128;
-      if (tb >= 1024 && fb >= (uint64_t)n_5 * 2 && fb < (1u << 24)) {
-        bloomT_bits = (uint32_t)tb;
-        bloom5_bits = (uint32_t)fb;
-      }
-    }
-  }
-  const uint32_t bloom_bytes = bloom5_bits ? (bloomT_bits + bloom5_bits) / 8 : 0;
-  /* scan_gram2_kernel (dev_gram2.h: lane-local sieve on two bits per 4-gram, no queue push per
-   * position, no Bloom filters): narrow alphabets without keywords of 1-3 symbols whose table fits
-   * LDS beside the waves' areas -- up to 26 symbols + "other".  ACM_GPU_GRAM2=0: scan_gram_kernel. */
-  const uint32_t tab2_words = gram && !gram_wide ? (gW4 + 15) / 16 : 0;
-  const uint32_t g2_off = (tab2_words * 4 + 15) & ~15u;
-  const char *gram2_env = getenv ("ACM_GPU_GRAM2");
-  const bool gram2 = gram && !gram_wide && !(gram2_env && atoi (gram2_env) == 0) &&
-                     (uint64_t)g2_off + G2_LDS_FIXED <= ((uint32_t)prop.maxSharedMemoryPerMultiProcessor >= 160 * 1024 ? 160u * 1024 : 64u * 1024);
-  const size_t o_g4bits = blob_reserve (cur, gram ? (size_t)(bloom5_bits ? bloom_off + bloom_bytes : g3_off + g3_bytes) + 16 : 0);
-  const size_t o_g3rec = blob_reserve (cur, gram_shorts && !gram_wide ? (size_t)gW3 * 16 : 0);
-  const size_t o_stab = blob_reserve (cur, gram_wide && gram_shorts ? ((size_t)8 << stab_log2) : 0);
-  /* scan_short_kernel's LDS image: the nibbles, the number of set nibble bits in front of every 8
-   * 3-grams, the keyword ids in the order of those bits (a keyword of d symbols is the id of W^(3-d) 3-grams) */
-  uint32_t sh_ids = 0;
-  for (uint32_t st = 1; gram_shorts && !gram_wide && st < fv.depth_start[4 <= fi.lmax + 1 ? 4 : fi.lmax + 1]; st++)
-    if (fv.term_kw[st] != NONE)
-      sh_ids += fv.depth[st] == 1 ? gW * gW : (fv.depth[st] == 2 ? gW : 1u);
-  const uint32_t sh_nib_bytes = g3_bytes, sh_base_bytes = gram_shorts && !gram_wide ? (((gW3 + 7) / 8) * 4 + 15) & ~15u : 0;
-  const uint32_t sh_ids_bytes = (sh_ids * 4 + 15) & ~15u;
-  const size_t o_shimg = blob_reserve (cur, gram_shorts && !gram_wide ? (size_t)sh_nib_bytes + sh_base_bytes + sh_ids_bytes + 16 : 0);
-  const size_t o_g4rec = blob_reserve (cur, gram ? (size_t)gW4 * 8 : 0);
-  const size_t o_grec = blob_reserve (cur, gram ? (size_t)n * 32 : 0);
-  const size_t o_gedge = blob_reserve (cur, gram ? (size_t)fi.n_edges * 8 : 0);
-  const size_t o_g4gid = blob_reserve (cur, gram ? (size_t)(fv.depth_start[5 <= fi.lmax + 1 ? 5 : fi.lmax + 1] - fv.depth_start[4]) * 4 + 16 : 0);
-  const size_t o_kw4 = blob_reserve (cur, gram ? (size_t)n_depth4 * 4 + 16 : 0);
-  const size_t o_g4prefix = blob_reserve (cur, gram && !gram_wide ? (size_t)g4words * 4 + 16 : 0);
-  const size_t o_g4entry = blob_reserve (cur, gram && !gram_wide ? (size_t)n_depth4 * 12 + 16 : 0);
-  const uint32_t n_depth5 = gram && fi.lmax >= 5 ? fv.depth_start[6 <= fi.lmax + 1 ? 6 : fi.lmax + 1] - fv.depth_start[5] : 0;
-  /* peek entries of 4 bytes while a record index fits 23 bits (ACM_GPU_PEEK8=1: 8 bytes anyway -- tests) */
-  const bool peek_packed = n < (1u << 23) && !(getenv ("ACM_GPU_PEEK8") && atoi (getenv ("ACM_GPU_PEEK8")) == 1);
-  const size_t o_g5peek = blob_reserve (cur, gram && !gram_wide ? (size_t)n_depth5 * (peek_packed ? 4 : 8) + 16 : 0);
-  const size_t o_tab2 = blob_reserve (cur, gram2 ? (size_t)g2_off + 16 : 0);
-  const bool rows2 = gram2; /* (entry words: classes are below 30, bits 30 and 31 are flags) */
-  const size_t o_rows2 = blob_reserve (cur, rows2 ? (size_t)tab2_words * 64 + 16 : 0);
-  const size_t o_over2 = blob_reserve (cur, rows2 ? (size_t)n_depth4 * 8 + 16 : 0);
-  p->blob_bytes = cur;
-
-  std::vector<unsigned char> host (cur, 0);
-  memcpy (&host[o_row], fv.row_ptr, ((size_t)n + 1) * 4);
-  memcpy (&host[o_sym], fv.edge_sym, (size_t)fi.n_edges * 4);
-  memcpy (&host[o_next], fv.edge_next, (size_t)fi.n_edges * 4);
-  memcpy (&host[o_fail], fv.fail, (size_t)n * 4);
-  memcpy (&host[o_cnbo], fv.nb_outputs, (size_t)n * 4);
-  {
-    uint32_t *oi = reinterpret_cast<uint32_t *> (&host[o_oinfo]);
-    for (uint32_t s = 0; s < n; s++) {
-      const uint32_t nb = fv.nb_outputs[s];
-      const uint32_t t0 = fv.term_kw[s] != NONE ? s : fv.out_link[s];
-      oi[4 * s + 0] = nb;
-      oi[4 * s + 1] = nb ? fv.out_link[t0] : 0;
-      oi[4 * s + 2] = nb ? fv.depth[t0] : 0;
-      oi[4 * s + 3] = nb ? fv.term_kw[t0] + kw_base : 0;
-    }
-  }
-  memcpy (&host[o_dstart], fv.depth_start, ((size_t)fi.lmax + 2) * 4);
-  if (sparse)
-    fill_sparse_tables (fv, fi, lut_size, reinterpret_cast<uint32_t *> (&host[o_srec]), reinterpret_cast<uint32_t *> (&host[o_sedge]),
-                        reinterpret_cast<uint32_t *> (&host[o_lut]));
-  if (starts)
-    fill_starts_tables (fv, fi, lut_size, reinterpret_cast<uint32_t *> (&host[o_trec]), reinterpret_cast<uint32_t *> (&host[o_tedge]),
-                        reinterpret_cast<uint32_t *> (&host[o_tlut]), reinterpret_cast<uint32_t *> (&host[o_tpairs]));
-  if (gram) {
-    GramImage G{};
-    G.wide = gram_wide;
-    G.shorts = gram_shorts;
-    G.W = gW;
-    G.bloom_log2 = bloom_log2;
-    G.wtab_log2 = wtab_log2;
-    G.stab_log2 = stab_log2;
-    G.bits = reinterpret_cast<uint32_t *> (&host[o_g4bits]);
-    G.g4 = reinterpret_cast<uint32_t *> (&host[o_g4rec]);
-    G.rec = reinterpret_cast<uint32_t *> (&host[o_grec]);
-    G.edge = reinterpret_cast<uint32_t *> (&host[o_gedge]);
-    G.g4gid = reinterpret_cast<uint32_t *> (&host[o_g4gid]);
-    G.nib = &host[o_g4bits + g3_off];
-    G.g3 = reinterpret_cast<uint32_t *> (&host[o_g3rec]);
-    G.stab = reinterpret_cast<uint32_t *> (&host[o_stab]);
-    for (uint32_t st = fv.depth_start[4]; st < fv.depth_start[5]; st++)
-      reinterpret_cast<uint32_t *> (&host[o_kw4])[st - fv.depth_start[4]] = fv.term_kw[st] == NONE ? NONE : fv.term_kw[st] + kw_base;
-    G.prefix = reinterpret_cast<uint32_t *> (&host[o_g4prefix]);
-    G.entry = reinterpret_cast<uint32_t *> (&host[o_g4entry]);
-    G.peek = gram_wide ? nullptr : reinterpret_cast<uint32_t *> (&host[o_g5peek]);
-    G.bloom = bloom5_bits ? reinterpret_cast<uint32_t *> (&host[o_g4bits + bloom_off]) : nullptr;
-    G.bloomT_bits = bloomT_bits;
-    G.bloom5_bits = bloom5_bits;
-    G.lo = fi.alpha_lo;
-    G.kw_base = kw_base;
-    G.kw_inline = (uint64_t)fi.n_keywords + kw_base <= HIT_KW_ID;
-    G.peek_packed = peek_packed;
-    G.tab2 = gram2 ? reinterpret_cast<uint32_t *> (&host[o_tab2]) : nullptr;
-    G.rows2 = rows2 ? reinterpret_cast<uint32_t *> (&host[o_rows2]) : nullptr;
-    G.over2 = rows2 ? reinterpret_cast<uint32_t *> (&host[o_over2]) : nullptr;
-    fill_gram_tables (fv, fi, G);
-    if (gram_shorts && !gram_wide) {
-      unsigned char *img = &host[o_shimg];
-      memcpy (img, G.nib, (gW3 + 1) / 2);
-      uint32_t *base = reinterpret_cast<uint32_t *> (img + sh_nib_bytes), *ids = reinterpret_cast<uint32_t *> (img + sh_nib_bytes + sh_base_bytes);
-      uint32_t r = 0;
-      for (uint32_t i3 = 0; i3 < gW3; i3++) {
-        if ((i3 & 7) == 0)
-          base[i3 >> 3] = r;
-        const uint32_t nb = (G.nib[i3 >> 1] >> ((i3 & 1) * 4)) & 7u;
-        for (uint32_t d = 0; d < 3; d++)
-          if ((nb >> d) & 1u)
-            ids[r++] = G.g3[4 * (size_t)i3 + d];
-      }
-      if (r != sh_ids) { /* (the two counts are of the same keywords) */
-        delete p;
-        return ACM_GPU_E_ARG;
-      }
-    }
-  }
-  if (dense) {
-    int rc = acm_flat_dense_rows (flat, n, entry_bytes, &host[o_dense]);
-    if (rc) {
-      delete p;
-      return rc;
-    }
-    /* LDS image: the first HD rows, then hotfail of the states [HD, n) */
-    memcpy (&host[o_image], &host[o_dense], (size_t)HD * rowbytes);
-    if (cont) {
-      const uint16_t *r16 = reinterpret_cast<const uint16_t *> (&host[o_dense]);
-      uint32_t *wr = reinterpret_cast<uint32_t *> (&host[o_wrows]);
-      for (size_t i = 0; i < (size_t)n * fi.width; i++)
-        wr[i] = r16[i] | (fv.depth[r16[i] & 0x7FFFu] << 16);
-      uint16_t *cdh = reinterpret_cast<uint16_t *> (&host[o_contdh]);
-      for (uint32_t s = 0; s < n; s++)
-        cdh[s] = (uint16_t)fv.depth[hotfail[s]];
-      memcpy (&host[o_image + rows_lds], hotfail.data () + HD, (size_t)(n - HD) * 2);
-      /* Chain records (EmitCtx::chain).  A continuation item says: walk on from rowless state s and
-       * report what is longer than j + depth (hotfail (s)) after j more symbols.  When f(s) has a
-       * row (hotfail (s) = f(s)), every failure transition out of the trie below s lands no deeper
-       * than that bound, so the walk can only ever report along the goto path; and when that path
-       * is a single chain of r <= 8 symbols to a leaf t with no keyword ending on the way, the
-       * whole walk is one comparison of the next r text bytes: 2 independent loads instead of 4-8
-       * dependent ones in expand_items_once_kernel. */
-      uint32_t *ch = reinterpret_cast<uint32_t *> (&host[o_chain]);
-      for (uint32_t s0 = HD; s0 < n; s0++) {
-        uint32_t *r = ch + 4 * (size_t)(s0 - HD);
-        const uint32_t dh = fv.depth[hotfail[s0]];
-        if (fv.fail[s0] >= HD || dh >= 4000)
-          continue;
-        uint64_t syms = 0;
-        uint32_t len = 0, st = s0;
-        bool ok = true;
-        while (fv.row_ptr[st + 1] > fv.row_ptr[st]) { /* until a leaf */
-          if (fv.row_ptr[st + 1] - fv.row_ptr[st] != 1 || len == 8 || (st != s0 && fv.term_kw[st] != NONE)) {
-            ok = false;
-            break;
-          }
-          syms |= (uint64_t)(fv.edge_sym[fv.row_ptr[st]] & 0xFFu) << (8 * len);
-          st = fv.edge_next[fv.row_ptr[st]];
-          len++;
-        }
-        if (!ok)
-          continue;
-        r[0] = (len ? len : 15u) | (dh << 4);
-        r[1] = st;
-        r[2] = (uint32_t)syms;
-        r[3] = (uint32_t)(syms >> 32);
-      }
-    }
-  }
-  if (hipMalloc (&p->blob, cur) != hipSuccess) {
-    delete p;
-    return ACM_GPU_E_NOMEM;
-  }
-  if (hipMemcpy (p->blob, host.data (), cur, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree (p->blob);
-    delete p;
-    return ACM_GPU_E_HIP;
-  }
-  const size_t ctl_bytes = 16 + 2 * POOL_CLASSES * POOL_CTR_STRIDE * sizeof (unsigned int);
-  if (hipMalloc (reinterpret_cast<void **> (&p->d_total), ctl_bytes) != hipSuccess ||
-      hipMemset (p->d_total, 0, ctl_bytes) != hipSuccess) {
-    (void)hipFree (p->blob);
-    delete p;
-    return ACM_GPU_E_NOMEM;
-  }
-  p->d_pool_ctr = reinterpret_cast<unsigned int *> (p->d_total + 2);
-  unsigned char *b = static_cast<unsigned char *> (p->blob);
-  auto u32p = [&] (size_t off) { return reinterpret_cast<const uint32_t *> (b + off); };
-  p->csr.row_ptr = u32p (o_row);
-  p->csr.edge_sym = u32p (o_sym);
-  p->csr.edge_next = u32p (o_next);
-  p->csr.fail = u32p (o_fail);
-  p->csr.nb_outputs = u32p (o_cnbo);
-  p->csr.lmax = fi.lmax;
-  p->d_oinfo = reinterpret_cast<const uint4 *> (b + o_oinfo);
-  p->entry_bytes = entry_bytes;
-  if (dense) {
-    p->d_dense = b + o_dense;
-    p->d_lds_image = b + o_image;
-    p->d_cont_dh = cont ? reinterpret_cast<const uint16_t *> (b + o_contdh) : nullptr;
-    p->d_chain = cont ? reinterpret_cast<const uint4 *> (b + o_chain) : nullptr;
-    p->d_wrows = cont ? reinterpret_cast<const uint32_t *> (b + o_wrows) : nullptr;
-    p->lds_image_bytes = image_bytes;
-    DenseK &K = p->K;
-    K.W = fi.width;
-    K.rowbytes = rowbytes;
-    K.lo = fi.alpha_lo;
-    K.span = fi.alpha_span;
-    K.HD = HD;
-    K.aux_off = rows_lds;
-    K.queue_off = image_bytes;
-    K.wub = fi.lmax > 1 ? (fi.lmax - 1 + 15) / 16 : 0;
-    K.lmax = fi.lmax;
-    K.stream_stride = WAVE * p->chunk;
-  }
-  p->d_dstart = u32p (o_dstart);
-  if (gram) {
-    const uint32_t lds_total = (uint32_t)prop.maxSharedMemoryPerMultiProcessor >= 160 * 1024 ? 160 * 1024 : 64 * 1024;
-    const uint32_t gq = (SPARSE_THREADS / WAVE) * ((gram_shorts && gram_wide ? QCAP : 0u) + GRAM_Q1 + GRAM_Q2 + (gram_wide ? HITS_STRIDE : 0u)) * 8;
-    const uint32_t bits_bytes = bloom5_bits ? bloom_off + bloom_bytes : g3_off + g3_bytes;
-    if ((uint64_t)bits_bytes + gq + WALK_CTX_BYTES <= lds_total) {
-      p->d_kw4 = u32p (o_kw4);
-      p->GK.g4prefix = u32p (o_g4prefix);
-      p->GK.g4entry = u32p (o_g4entry);
-      p->GK.kw_inline = (uint64_t)fi.n_keywords + kw_base <= HIT_KW_ID ? 1u : 0u;
-      p->GK.g5peek = u32p (o_g5peek);
-      p->GK.peek_packed = peek_packed ? 1u : 0u;
-      p->GK.d5_begin = fv.depth_start[5 <= fi.lmax + 1 ? 5 : fi.lmax + 1];
-      p->GK.d5_rel = peek_packed ? 1u : 0u; /* (fewer than 2^23 states in all: a record index leaves bits 24-29 free too) */
-      p->GK.bloom_off = bloom_off;
-      p->GK.bloomT_bits = bloomT_bits;
-      p->GK.bloom5_bits = bloom5_bits;
-      p->gram = true;
-      p->GK.g4rec = reinterpret_cast<const uint2 *> (b + o_g4rec);
-      p->GK.g4bits = u32p (o_g4bits);
-      p->GK.srec = reinterpret_cast<const uint4 *> (b + o_grec);
-      p->GK.sedge = reinterpret_cast<const uint2 *> (b + o_gedge);
-      p->GK.g4gid = u32p (o_g4gid);
-      p->GK.d4_begin = fv.depth_start[4];
-      p->GK.g4words = g4words;
-      p->GK.g3rec = reinterpret_cast<const uint4 *> (b + o_g3rec);
-      p->GK.g3_off = g3_off;
-      p->GK.g3_bytes = g3_bytes;
-      p->GK.wtab = reinterpret_cast<const uint2 *> (b + o_g4rec);
-      p->GK.bloom_log2 = bloom_log2;
-      p->GK.wtab_log2 = wtab_log2;
-      p->GK.stab = reinterpret_cast<const uint2 *> (b + o_stab);
-      p->GK.stab_log2 = stab_log2;
-      p->GK.short_lens = short_lens;
-      p->gram_shorts = gram_shorts && gram_wide; /* (the kernel's own short-keyword path: hashed windows only) */
-      p->short_pass = gram_shorts && !gram_wide;
-      p->GK.sh_img = u32p (o_shimg);
-      p->GK.sh_nib_bytes = sh_nib_bytes;
-      p->GK.sh_base_bytes = sh_base_bytes;
-      p->GK.sh_ids_bytes = sh_ids_bytes;
-      /* the ids in LDS too while they fit (29 K of them beside the tables and the waves' areas) */
-      p->short_ids_lds = (uint64_t)sh_nib_bytes + sh_base_bytes + sh_ids_bytes + SH_LDS_FIXED <= lds_total;
-      p->short_lds_bytes = sh_nib_bytes + sh_base_bytes + (p->short_ids_lds ? sh_ids_bytes : 0u) + SH_LDS_FIXED;
-      p->short_lds_count_bytes = sh_nib_bytes + SH_LDS_FIXED;
-      p->short_blocks_per_cu = 2u * (sh_nib_bytes + SH_LDS_FIXED) <= 160u * 1024u ? 2u : 1u; /* (count-only: the nibbles alone) */
-      if (const char *e = getenv ("ACM_GPU_SHORT_BLOCKS"))
-        if (atoi (e) == 1)
-          p->short_blocks_per_cu = 1;
-      p->gram_wide = gram_wide;
-      p->GK.W = gW;
-      p->GK.lo = fi.alpha_lo;
-      p->GK.span = fi.alpha_span;
-      p->GK.W4 = gW4;
-      p->GK.queue_off = bits_bytes;
-      p->gram_lds_bytes = bits_bytes + gq + WALK_CTX_BYTES;
-      if (rows2) {
-        p->GK.rows2 = reinterpret_cast<const uint2 *> (b + o_rows2);
-        p->GK.over2 = reinterpret_cast<const uint2 *> (b + o_over2);
-      }
-      if (gram2) {
-        p->gram2 = true;
-        p->GK.tab2 = u32p (o_tab2);
-
-        p->GK.tab2_words = tab2_words;
-        p->GK.g2_off = g2_off;
-        p->gram_lds_bytes = g2_off + G2_LDS_FIXED;
-      }
-    }
-  }
-  if (sparse) {
-    const uint32_t tps = 128 / fi.sym_bytes;
-    const uint32_t warm = fi.lmax > 1 ? fi.lmax - 1 : 0;
-    const uint32_t sparse_queue_bytes = (SPARSE_THREADS / WAVE) * QCAP * 8;
-    const uint32_t lds_total = (uint32_t)prop.maxSharedMemoryPerMultiProcessor >= 160 * 1024 ? 160 * 1024 : 64 * 1024;
-    p->sparse = true;
-    p->sparse_lut_lds = (uint64_t)lut_size * 4 + sparse_queue_bytes + 512 <= lds_total;
-    p->SK.srec = reinterpret_cast<const uint4 *> (b + o_srec);
-    p->SK.sedge = reinterpret_cast<const uint2 *> (b + o_sedge);
-    p->SK.lut = u32p (o_lut);
-    p->SK.lut_size = lut_size;
-    p->SK.warm_subs = (warm + tps - 1) / tps;
-    p->SK.warm_skip = p->SK.warm_subs * tps - warm;
-    p->SK.queue_off = p->sparse_lut_lds ? lut_size * 4 : 0;
-    p->SK.R = 0; /* per launch */
-    p->sparse_lds_bytes = p->SK.queue_off + sparse_queue_bytes + 16;
-    const char *mode = getenv ("ACM_GPU_SPARSE");
-    p->starts = starts && !(mode && strcmp (mode, "walk") == 0);
-    if (starts) {
-      p->TK.srec = reinterpret_cast<const uint4 *> (b + o_trec);
-      p->TK.sedge = reinterpret_cast<const uint2 *> (b + o_tedge);
-      p->TK.lut = u32p (o_tlut);
-      p->TK.pairs = reinterpret_cast<const uint2 *> (b + o_tpairs);
-      p->TK.lut_size = lut_size;
-      const uint32_t starts_queue_bytes = (SPARSE_THREADS / WAVE) * (QCAP + HITS_STRIDE) * 8;
-      p->starts_lut_lds = (uint64_t)lut_size * 4 + starts_queue_bytes + WALK_CTX_BYTES <= lds_total;
-      p->TK.queue_off = p->starts_lut_lds ? lut_size * 4 : 0;
-      p->TK.R = 0;
-      p->starts_lds_bytes = p->TK.queue_off + starts_queue_bytes + WALK_CTX_BYTES;
-      if (p->starts) {
-        StartsMirror *M = new (std::nothrow) StartsMirror ();
-        if (M) {
-          auto words = [&] (size_t off, size_t cnt) {
-            const uint32_t *w = reinterpret_cast<const uint32_t *> (&host[off]);
-            return std::vector<uint32_t> (w, w + cnt);
-          };
-          M->tab[PT_REC] = words (o_trec, (size_t)n * 8);
-          M->tab[PT_EDGE] = words (o_tedge, (size_t)fi.n_edges * 2);
-          M->tab[PT_LUT] = words (o_tlut, lut_size);
-          M->tab[PT_PAIRS] = words (o_tpairs, (size_t)n * 2);
-          M->tab[PT_OINFO] = words (o_oinfo, (size_t)n * 4);
-          M->parent.assign (n, 0);
-          M->parent_sym.assign (n, 0);
-          M->depth.assign (fv.depth, fv.depth + n);
-          for (uint32_t st = 0; st < n; st++) {
-            M->tab[PT_REC][8 * (size_t)st] = st ? fv.row_ptr[st + 1] - fv.row_ptr[st] : M->tab[PT_REC][1]; /* row capacity = its size */
-            for (uint32_t e = fv.row_ptr[st]; e < fv.row_ptr[st + 1]; e++) {
-              M->parent[fv.edge_next[e]] = st;
-              M->parent_sym[fv.edge_next[e]] = fv.edge_sym[e];
-            }
-          }
-          M->dev[PT_REC] = reinterpret_cast<uint32_t *> (b + o_trec);
-          M->dev[PT_EDGE] = reinterpret_cast<uint32_t *> (b + o_tedge);
-          M->dev[PT_LUT] = reinterpret_cast<uint32_t *> (b + o_tlut);
-          M->dev[PT_PAIRS] = reinterpret_cast<uint32_t *> (b + o_tpairs);
-          M->dev[PT_OINFO] = reinterpret_cast<uint32_t *> (b + o_oinfo);
-          M->cap[PT_LUT] = lut_size;
-          M->n_states = n;
-          M->n_edges = fi.n_edges;
-          M->n_keywords = fi.n_keywords;
-          M->lmax = fi.lmax;
-          p->mir = M;
-        }
-      }
-    }
-  }
-
-  ACMPlanInfo &I = p->info;
-  I.device = device;
-  I.kernel = p->gram ? 5 : (dense ? 1 : (sparse ? (p->starts ? 4 : 3) : 2));
-  I.entry_bytes = dense ? entry_bytes : 0;
-  I.width = fi.width;
-  I.dense_rows = dense ? n : 0;
-  I.lds_rows = HD;
-  I.lds_hotfail = cont ? n - HD : 0;
-  I.lds_bytes = dense ? image_bytes + queue_bytes + 16 /* tile counter */ : QCAP * 8;
-  I.block_threads = dense ? DENSE_THREADS : WAVE;
-  I.grid_blocks = dense ? (uint32_t)p->cu_count : (uint32_t)p->cu_count * 16;
-  I.chunk_bytes = p->chunk;
-  I.streams = p->streams;
-  I.table_bytes = cur;
-
-/* a failure from here on must not leak the plan built so far */
-#define PLAN_TRY(expr)                                                                             \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) {                                                                        \
-      fprintf (stderr, "acm_gpu: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString (_e), __FILE__, \
-               __LINE__);                                                                          \
-      acm_gpu_plan_destroy (p);                                                                    \
-      return ACM_GPU_E_HIP;                                                                        \
-    }                                                                                              \
-  } while (0)
-  if (const char *e = getenv ("ACM_GPU_GRID_BLOCKS")) {
-    /* tests: fewer workgroups than CUs, so that one wave sees many tiles of a small text (the
-     * overflow path of the item regions fires hundreds of times per wave) */
-    const int g = atoi (e);
-    if (g >= 1 && g < p->cu_count)
-      p->cu_count = g;
-    I.grid_blocks = dense ? (uint32_t)p->cu_count : (uint32_t)p->cu_count * 16;
-  }
-  if (p->gram) {
-    I.lds_bytes = p->gram_lds_bytes;
-    I.block_threads = SPARSE_THREADS;
-    I.grid_blocks = (uint32_t)p->cu_count;
-    I.streams = 1;
-    I.chunk_bytes = 16;
-  }
-  if (sparse) {
-    I.lds_bytes = p->starts ? p->starts_lds_bytes : p->sparse_lds_bytes;
-    I.block_threads = SPARSE_THREADS;
-    I.grid_blocks = (uint32_t)p->cu_count;
-    I.streams = p->starts ? 1 : SPARSE_S;
-    I.chunk_bytes = 128;
-    for (int co = 0; co < 2; co++) {
-      PLAN_TRY (hipFuncSetAttribute (sparse_kernel_ptr (fi.sym_bytes, p->sparse_lut_lds, co != 0),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->sparse_lds_bytes));
-      if (p->starts)
-        PLAN_TRY (hipFuncSetAttribute (starts_kernel_ptr (fi.sym_bytes, p->starts_lut_lds, co != 0),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->starts_lds_bytes));
-    }
-  }
-  if (p->gram) {
-    for (int co = 0; co < 2; co++)
-      PLAN_TRY (hipFuncSetAttribute (gram_kernel_ptr (co != 0, p->gram_shorts, p->gram_wide, false, p->gram2), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)p->gram_lds_bytes));
-    if (!p->gram_wide)
-      PLAN_TRY (hipFuncSetAttribute (gram_kernel_ptr (false, p->gram_shorts, false, true, p->gram2), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)p->gram_lds_bytes));
-    if (p->short_pass)
-      for (int co = 0; co < 2; co++)
-        PLAN_TRY (hipFuncSetAttribute (short_kernel_ptr (co != 0, p->short_ids_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(co ? p->short_lds_count_bytes : p->short_lds_bytes)));
-  }
-  if (dense && !p->gram) {
-    for (int co = 0; co < 2; co++)
-      PLAN_TRY (hipFuncSetAttribute (dense_kernel_ptr (entry_bytes, p->chunk, p->streams, co != 0),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)I.lds_bytes));
-  }
-  if (interned) {
-    uint32_t cap = 16;
-    while (cap < 2 * (fv.n_keys64 + 1))
-      cap <<= 1;
-    std::vector<uint32_t> tab ((size_t)cap * 4, 0);
-    auto mix = [] (uint64_t x) {
-      x ^= x >> 30;
-      x *= 0xBF58476D1CE4E5B9ull;
-      x ^= x >> 27;
-      x *= 0x94D049BB133111EBull;
-      return x ^ (x >> 31);
-    };
-    for (uint32_t k = 0; k < fv.n_keys64; k++) {
-      const uint64_t key = fv.keys64[k];
-      uint32_t h = (uint32_t)mix (key) & (cap - 1);
-      while (tab[4 * (size_t)h + 2])
-        h = (h + 1) & (cap - 1);
-      tab[4 * (size_t)h] = (uint32_t)key;
-      tab[4 * (size_t)h + 1] = (uint32_t)(key >> 32);
-      tab[4 * (size_t)h + 2] = k + 1;
-    }
-    if (hipMalloc (reinterpret_cast<void **> (&p->d_intern), (size_t)cap * 16) != hipSuccess ||
-        hipMemcpy (p->d_intern, tab.data (), (size_t)cap * 16, hipMemcpyHostToDevice) != hipSuccess) {
-      acm_gpu_plan_destroy (p);
-      return ACM_GPU_E_NOMEM;
-    }
-    p->intern_mask = cap - 1;
-  }
-  if (fv.keys32 || (fi.sym_bytes == 4 && fv.class_rep32)) {
-    p->cls32 = true;
-    for (uint32_t i = 0; i < fv.n_keys32; i++)
-      p->cls32_known[fv.keys32[i]] = fv.keys32_class[i];
-    p->cls32_reps.assign (fv.class_rep32, fv.class_rep32 + fv.n_classes);
-    if (hipMalloc (reinterpret_cast<void **> (&p->d_unknown), (size_t)(p->cls32_cap + 1) * 4) != hipSuccess) {
-      acm_gpu_plan_destroy (p);
-      return ACM_GPU_E_NOMEM;
-    }
-  }
-  if (fv.class_map) {
-    /* 65,536 entries either way: 2-byte symbols directly, bytes in pairs (see classmap_kernel) */
-    std::vector<uint16_t> lut (65536);
-    if (fi.sym_bytes == 1) {
-      for (uint32_t v = 0; v < 65536; v++)
-        lut[v] = (uint16_t)((fv.class_map[v >> 8] << 8) | (fv.class_map[v & 255] & 255));
-    } else
-      memcpy (lut.data (), fv.class_map, 65536 * 2);
-    if (hipMalloc (reinterpret_cast<void **> (&p->d_classlut), 65536 * 2) != hipSuccess ||
-        hipMemcpy (p->d_classlut, lut.data (), 65536 * 2, hipMemcpyHostToDevice) != hipSuccess) {
-      acm_gpu_plan_destroy (p);
-      return ACM_GPU_E_NOMEM;
-    }
-    PLAN_TRY (hipFuncSetAttribute (reinterpret_cast<const void *> (&classmap_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 65536 * 2));
-  }
-#undef PLAN_TRY
   *out = p;
   return ACM_GPU_OK;
 }
 } // namespace
+
+extern "C" int
+acm_gpu_plan_create_flat (const ACMFlat *flat, int device, ACMPlan **out) {
+  return plan_create (flat, device, 0, out);
+}
 
 extern "C" int
 acm_gpu_plan_create (ACMachine *machine, int device, ACMPlan **out) {
@@ -1373,8 +1510,9 @@ acm_gpu_plan_info (const ACMPlan *plan, ACMPlanInfo *info) {
   *info = plan->info;
   info->delta_keywords = plan->delta ? plan->delta->finfo.n_keywords : 0;
   info->merges = plan->merges;
-  info->records_direct = ((plan->gram && !plan->gram_wide) || plan->info.kernel == 2) ? 1u : 0u;
-  info->variant = (plan->gram2 ? 2u : 0u) | (plan->short_pass ? 4u : 0u) | (plan->short_pass && !plan->short_ids_lds ? 8u : 0u);
+  const bool gram = plan->kind == PlanKind::Gram;
+  info->records_direct = ((gram && !plan->hashed) || plan->kind == PlanKind::Csr) ? 1u : 0u;
+  info->variant = gram ? (plan->gram2 ? 2u : 0u) | (plan->short_pass ? 4u : 0u) | (plan->short_pass && !plan->short_ids_lds ? 8u : 0u) : 0u;
 }
 
 extern "C" int
@@ -1586,6 +1724,20 @@ close_network_only () {
   return e && strcmp (e, "network") == 0 ? 1u : 0u;
 }
 
+/* the holes the `n_waves` waves of a pass left in their last chunks of records (the waves of the
+ * scan's widest launch: an earlier segment may have had more blocks than the last one; a short text
+ * has few -- every block of the kernel sorts all the descriptors it is given) */
+hipError_t
+launch_close_holes (ACMPlan *p, const EmitCtx &E, const RecHole *holes, uint32_t n_waves, hipStream_t st) {
+  uint32_t npow = 64;
+  while (npow < n_waves)
+    npow <<= 1;
+  const uint32_t blocks = n_waves / 16 > 0 ? n_waves / 16 : 1; /* 16 holes per block */
+  hipLaunchKernelGGL (close_holes_kernel, dim3 (blocks), dim3 (CLOSE_THREADS), npow * 16, st, E, holes, n_waves, npow,
+                      reinterpret_cast<unsigned int *> (p->d_total + 1), close_network_only ());
+  return hipGetLastError ();
+}
+
 template <bool COUNT_ONLY>
 int
 launch_gram (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t stop, bool first_segment, bool last_segment) {
@@ -1603,7 +1755,7 @@ launch_gram (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t 
   /* narrow alphabets: the kernel writes the records itself (no item buffer, no expansion; the holes
    * its waves leave in their last chunks are closed right behind it); hashed windows: hits parked
    * per wave and expanded as in the start-parallel kernel */
-  const bool direct = !p->gram_wide;
+  const bool direct = !p->hashed;
   void *items = (COUNT_ONLY || direct) ? nullptr : p->d_items;
   uint32_t *fill = (COUNT_ONLY || direct) ? nullptr : p->d_fill;
   void *holes = (!COUNT_ONLY && direct) ? p->d_holes : nullptr;
@@ -1621,7 +1773,7 @@ launch_gram (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t 
   if (dir)
     p->tiled_base += tiles;
   void *args[] = { &K, const_cast<EmitCtx *> (&E), &a, &a.text, &items, &p->region_items, &fill, &holes, &resume, &dir, &dir_base };
-  HIP_TRY (hipLaunchKernel (gram_kernel_ptr (COUNT_ONLY, p->gram_shorts, p->gram_wide, dir != nullptr, p->gram2), dim3 (grid), dim3 (SPARSE_THREADS), args,
+  HIP_TRY (hipLaunchKernel (gram_kernel_ptr (COUNT_ONLY, p->inline_shorts, p->hashed, dir != nullptr, p->gram2), dim3 (grid), dim3 (SPARSE_THREADS), args,
                             p->gram_lds_bytes, st));
   if (stop)
     HIP_TRY (hipEventRecord (stop, st));
@@ -1629,16 +1781,7 @@ launch_gram (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t 
     if (direct && dir) {
       /* (nothing: tile_gather_kernel reads the records where they lie) */
     } else if (direct && last_segment) {
-      /* (the waves of the scan's widest launch: an earlier segment may have had more blocks than this
-       * one; a short text has few -- every block of the kernel sorts all the descriptors it is given) */
-      const uint32_t n_waves = p->holes_waves[0];
-      uint32_t npow = 64;
-      while (npow < n_waves)
-        npow <<= 1;
-      const uint32_t blocks = n_waves / 16 > 0 ? n_waves / 16 : 1; /* 16 holes per block */
-      hipLaunchKernelGGL (close_holes_kernel, dim3 (blocks), dim3 (CLOSE_THREADS), npow * 16, st, E, static_cast<const RecHole *> (p->d_holes),
-                          n_waves, npow, reinterpret_cast<unsigned int *> (p->d_total + 1), close_network_only ());
-      HIP_TRY (hipGetLastError ());
+      HIP_TRY (launch_close_holes (p, E, static_cast<const RecHole *> (p->d_holes), p->holes_waves[0], st));
     } else if (!direct)
       launch_expand_hits (p, E, grid * wpb, st);
   }
@@ -1679,16 +1822,8 @@ launch_short (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t
                             COUNT_ONLY ? p->short_lds_count_bytes : p->short_lds_bytes, st));
   if (stop)
     HIP_TRY (hipEventRecord (stop, st));
-  if (!COUNT_ONLY && last_segment) {
-    const uint32_t n_waves = p->holes_waves[1];
-    uint32_t npow = 64;
-    while (npow < n_waves)
-      npow <<= 1;
-    const uint32_t blocks = n_waves / 16 > 0 ? n_waves / 16 : 1;
-    hipLaunchKernelGGL (close_holes_kernel, dim3 (blocks), dim3 (CLOSE_THREADS), npow * 16, st, E, holes, n_waves, npow,
-                        reinterpret_cast<unsigned int *> (p->d_total + 1), close_network_only ());
-    HIP_TRY (hipGetLastError ());
-  }
+  if (!COUNT_ONLY && last_segment)
+    HIP_TRY (launch_close_holes (p, E, holes, p->holes_waves[1], st));
   return ACM_GPU_OK;
 }
 
@@ -1813,14 +1948,8 @@ launch_dense (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t
   const uint32_t blocks_needed = (a.range_end + wpb - 1) / wpb;
   if (blocks_needed < grid)
     grid = blocks_needed;
-  /* the last 1/16 of the tiles is the dynamic pool (none for inputs of a few tiles per wave) */
-  const uint32_t pool = a.range_end >= grid * wpb * 8 ? a.range_end / 16 : 0;
-  a.static_end = a.range_end - pool;
-  a.pool_classes = grid < POOL_CLASSES ? grid : POOL_CLASSES;
-  a.pool_class_tiles = (pool + a.pool_classes - 1) / a.pool_classes;
-  a.pool_ctr = p->d_pool_ctr + (p->launch_seq & 1) * POOL_CLASSES * POOL_CTR_STRIDE;
-  a.pool_reset = p->d_pool_ctr + ((p->launch_seq & 1) ^ 1) * POOL_CLASSES * POOL_CTR_STRIDE;
-  p->launch_seq++;
+  static_assert (DENSE_THREADS == SPARSE_THREADS, "set_tile_pool counts blocks of SPARSE_THREADS");
+  set_tile_pool (p, a, grid * wpb);
   void *args[] = { &p->K, const_cast<EmitCtx *> (&E), &a, &p->d_dense, &p->d_lds_image, &p->lds_image_bytes, &a.text,
                    &p->d_items, &p->region_items, &p->d_fill, &p->d_dstart };
   HIP_TRY (hipLaunchKernel (dense_kernel_ptr (p->entry_bytes, p->chunk, p->streams, COUNT_ONLY), dim3 (grid), dim3 (DENSE_THREADS), args,
@@ -2223,7 +2352,7 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
   HIP_TRY (hipSetDevice (p->device));
   const uint32_t sb = p->finfo.sym_bytes;
   /* (a comparator-class plan walks its own aligned copy of the text) */
-  const bool use_dense = p->info.kernel == 1 && (p->d_classlut || (reinterpret_cast<uintptr_t> (d_text) & 15) == 0);
+  const bool use_dense = p->kind == PlanKind::Dense && (p->d_classlut || (reinterpret_cast<uintptr_t> (d_text) & 15) == 0);
   if (!accumulate && (n == 0 || p->finfo.n_edges == 0 || emit_from >= n || !use_dense))
     HIP_TRY (hipMemsetAsync (d_count, 0, sizeof (uint64_t), st));
   if (n == 0 || p->finfo.n_edges == 0 || emit_from >= n)
@@ -2257,7 +2386,7 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
     if (rc)
       return rc;
     d_text = p->d_remap;
-  } else if ((p->starts || p->gram) && (reinterpret_cast<uintptr_t> (d_text) & 15) != 0) {
+  } else if ((p->kind == PlanKind::Starts || p->kind == PlanKind::Gram) && (reinterpret_cast<uintptr_t> (d_text) & 15) != 0) {
     /* start-parallel / 4-gram plan, buffer not 16-byte aligned: scan an aligned copy (the CSR walk that
      * would take it as it is runs 20x slower, and knows nothing of incremental updates) */
     int rc = ensure_remap_buffer (p, (size_t)n * sb, st);
@@ -2266,11 +2395,12 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
     HIP_TRY (hipMemcpyAsync (p->d_remap, d_text, (size_t)n * sb, hipMemcpyDeviceToDevice, st));
     d_text = p->d_remap;
   }
-  const bool direct = p->gram && !p->gram_wide; /* records straight from the scan kernel: no item buffer */
-  if (use_dense || (!COUNT_ONLY && !direct && (p->gram || p->starts))) {
+  const bool gram = p->kind == PlanKind::Gram;
+  const bool direct = gram && !p->hashed; /* records straight from the scan kernel: no item buffer */
+  if (use_dense || (!COUNT_ONLY && !direct && (gram || p->kind == PlanKind::Starts))) {
     /* 4-gram plans over hashed windows see dense matches: room for one hit per 16 symbols, per 8
      * when the dictionary has keywords of 1-3 symbols; past that a wave reserves records 64 at a time */
-    int rc = ensure_item_buffer (p, n < p->segment ? n : p->segment, p->gram ? (p->gram_shorts ? 8 : 16) : 256,
+    int rc = ensure_item_buffer (p, n < p->segment ? n : p->segment, gram ? (p->inline_shorts ? 8 : 16) : 256,
                                  use_dense ? DENSE_MIN_REGION_ITEMS : 256);
     if (rc)
       return rc;
@@ -2308,38 +2438,51 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
   E.chunk_prev = tiled ? p->tiled_prev : nullptr;
   E.error = p->d_total ? reinterpret_cast<unsigned int *> (p->d_total) + 3 : nullptr;
 
-  /* segments of at most SEGMENT symbols; each restarts from the root `halo` symbols early
-   * (a multiple of 16 bytes so that the dense kernel keeps its alignment) */
-  const uint64_t halo = p->finfo.lmax > 1 ? (((uint64_t)p->finfo.lmax - 1 + 15) / 16) * 16 : 0;
+  /* segments of at most SEGMENT symbols; each restarts from the root `halo` symbols early (a
+   * multiple of 16 bytes so that the kernels keep their alignment); `launch` makes the launches of one */
   const uint64_t SEG = p->segment;
   const uint64_t first_seg = emit_from / SEG * SEG; /* earlier segments have nothing to report */
-  for (uint64_t seg = first_seg; seg < n; seg += SEG) {
-    const uint64_t seg_end = seg + SEG < n ? seg + SEG : n;
-    const uint64_t read_begin = seg > halo ? seg - halo : 0;
-    Launch a{};
-    a.text = static_cast<const unsigned char *> (d_text) + read_begin * sb;
-    a.n = (uint32_t)(seg_end - read_begin);
-    const uint64_t ef = emit_from > seg ? emit_from : seg;
-    a.emit_from = (uint32_t)(ef - read_begin);
-    E.pos_base = pos_base + read_begin;
-    E.text = a.text;
-    E.n = a.n;
-    E.emit_from = a.emit_from;
-    hipEvent_t stop, stop_all;
-    int rc = timing_begin (p, st, &stop, &stop_all);
-    if (rc)
-      return rc;
+  auto each_segment = [&] (uint64_t halo, auto launch) -> int {
+    for (uint64_t seg = first_seg; seg < n; seg += SEG) {
+      const uint64_t seg_end = seg + SEG < n ? seg + SEG : n;
+      const uint64_t read_begin = seg > halo ? seg - halo : 0;
+      Launch a{};
+      a.text = static_cast<const unsigned char *> (d_text) + read_begin * sb;
+      a.n = (uint32_t)(seg_end - read_begin);
+      const uint64_t ef = emit_from > seg ? emit_from : seg;
+      a.emit_from = (uint32_t)(ef - read_begin);
+      E.pos_base = pos_base + read_begin;
+      E.text = a.text;
+      E.n = a.n;
+      E.emit_from = a.emit_from;
+      hipEvent_t stop, stop_all;
+      int rc = timing_begin (p, st, &stop, &stop_all);
+      if (rc)
+        return rc;
+      rc = launch (a, stop, seg == first_seg, seg_end == n);
+      if (!rc && stop_all) /* behind the expansion / hole closing the launch functions enqueue after their scan kernel */
+        HIP_TRY (hipEventRecord (stop_all, st));
+      if (rc)
+        return rc;
+    }
+    return ACM_GPU_OK;
+  };
+  const uint64_t halo = p->finfo.lmax > 1 ? (((uint64_t)p->finfo.lmax - 1 + 15) / 16) * 16 : 0;
+  auto main_pass = [&] (Launch &a, hipEvent_t stop, bool first_segment, bool last_segment) -> int {
+    int rc = ACM_GPU_OK;
+    const bool aligned = (reinterpret_cast<uintptr_t> (a.text) & 15) == 0;
     if (use_dense)
-      rc = launch_dense<COUNT_ONLY> (p, E, a, st, stop, d_count, seg_end == n && !accumulate);
+      rc = launch_dense<COUNT_ONLY> (p, E, a, st, stop, d_count, last_segment && !accumulate);
     else {
       a.range_begin = 0;
       a.range_end = a.n;
-      if (p->gram)
-        rc = launch_gram<COUNT_ONLY> (p, E, a, st, stop, seg == first_seg, seg_end == n);
-      else if (p->starts && (reinterpret_cast<uintptr_t> (a.text) & 15) == 0)
+      if (gram)
+        rc = launch_gram<COUNT_ONLY> (p, E, a, st, stop, first_segment, last_segment);
+      else if (p->kind == PlanKind::Starts && aligned)
         rc = launch_starts<COUNT_ONLY> (p, E, a, st, stop);
       else {
-        if (p->sparse && (reinterpret_cast<uintptr_t> (a.text) & 15) == 0)
+        /* (the CSR walk takes any alignment: a Dense plan's unaligned text, a Starts plan's unaligned segment) */
+        if ((p->kind == PlanKind::Sparse || p->kind == PlanKind::Starts) && aligned)
           rc = launch_sparse<COUNT_ONLY> (p, E, a, st);
         else
           rc = launch_csr<COUNT_ONLY> (p, E, a, st);
@@ -2347,39 +2490,20 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
           HIP_TRY (hipEventRecord (stop, st));
       }
     }
-    if (!rc && stop_all) /* behind the expansion / hole closing the launch functions enqueue after their scan kernel */
-      HIP_TRY (hipEventRecord (stop_all, st));
-    if (rc) {
-      /* earlier segments may have left a partial running total and expand ticket behind */
-      if (use_dense && p->d_total)
-        (void)hipMemsetAsync (p->d_total, 0, 16, st);
-      return rc;
-    }
-  }
+    /* earlier segments may have left a partial running total and expand ticket behind */
+    if (rc && use_dense && p->d_total)
+      (void)hipMemsetAsync (p->d_total, 0, 16, st);
+    return rc;
+  };
+  int rc = each_segment (halo, main_pass);
   /* narrow alphabets: the keywords of 1-3 symbols, a pass of their own over the same segments
-   * (dev_short.h); their records follow the 4-gram pass' in the same buffer */
-  for (uint64_t seg = first_seg; p->gram && p->short_pass && !use_dense && seg < n; seg += SEG) {
-    const uint64_t seg_end = seg + SEG < n ? seg + SEG : n;
-    const uint64_t read_begin = seg > 16 ? seg - 16 : 0; /* (a halo of 2 symbols would do: 16 keeps the alignment) */
-    Launch a{};
-    a.text = static_cast<const unsigned char *> (d_text) + read_begin * sb;
-    a.n = (uint32_t)(seg_end - read_begin);
-    const uint64_t ef = emit_from > seg ? emit_from : seg;
-    a.emit_from = (uint32_t)(ef - read_begin);
-    E.pos_base = pos_base + read_begin;
-    E.text = a.text;
-    E.n = a.n;
-    E.emit_from = a.emit_from;
-    hipEvent_t stop, stop_all;
-    int rc = timing_begin (p, st, &stop, &stop_all);
-    if (!rc)
-      rc = launch_short<COUNT_ONLY> (p, E, a, st, stop, seg == first_seg, seg_end == n);
-    if (!rc && stop_all)
-      HIP_TRY (hipEventRecord (stop_all, st));
-    if (rc)
-      return rc;
-  }
-  return ACM_GPU_OK;
+   * (dev_short.h); their records follow the 4-gram pass' in the same buffer.  (A halo of 2 symbols
+   * would do: 16 keeps the alignment.) */
+  if (!rc && gram && p->short_pass)
+    rc = each_segment (16, [&] (Launch &a, hipEvent_t stop, bool first_segment, bool last_segment) {
+      return launch_short<COUNT_ONLY> (p, E, a, st, stop, first_segment, last_segment);
+    });
+  return rc;
 }
 
 /* a plan and, if it has one, its delta (acm_gpu_plan_update): both scans append to the same record
@@ -2820,7 +2944,7 @@ tiled_layout (const ACMPlan *p, uint64_t capacity, uint64_t n, uint64_t emit_fro
   const char *env = getenv ("ACM_GPU_ORDER"); /* radix / buckets: not this way (experiments, tests) */
   if (env && (strcmp (env, "radix") == 0 || strcmp (env, "buckets") == 0))
     return L;
-  if (!p->gram || p->gram_wide || p->short_pass || p->delta || p->finfo.lmax > WAVE * 16 || p->finfo.n_edges == 0)
+  if (p->kind != PlanKind::Gram || p->hashed || p->short_pass || p->delta || p->finfo.lmax > WAVE * 16 || p->finfo.n_edges == 0)
     return L; /* (a second pass' records do not lie tile by tile: the general order passes) */
   if (n == 0 || emit_from >= n || capacity == 0 || capacity >= (1ull << 31))
     return L;
@@ -3456,7 +3580,7 @@ acm_gpu_plan_update (ACMPlan *plan, ACMachine *machine) {
   const uint64_t gen = acm_internal_generation (machine);
   uint32_t sym_bytes = 0;
   const bool plain = acm_internal_symbol_bytes (machine, &sym_bytes) == ACM_GPU_OK;
-  if (plan->mir && plan->starts && plain && !plan->class_sym_bytes && sym_bytes == plan->finfo.sym_bytes) {
+  if (plan->kind == PlanKind::Starts && plan->mir && plain && !plan->class_sym_bytes && sym_bytes == plan->finfo.sym_bytes) {
     StartsMirror &M = *plan->mir;
     acm_internal_lock (machine);
     const uint32_t nk = (uint32_t)acm_nb_keywords (machine);
@@ -3564,7 +3688,7 @@ acm_gpu_plan_update (ACMPlan *plan, ACMachine *machine) {
     acm_release (tm);
     ACMPlan *fresh = nullptr;
     if (!rc) {
-      rc = plan_create_flat_kw (flat, plan->device, base_kw, &fresh);
+      rc = plan_create (flat, plan->device, base_kw, &fresh);
       acm_flat_release (flat);
     }
     if (rc)

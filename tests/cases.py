@@ -1,5 +1,8 @@
 """Shared dictionaries/texts for the parity tests (CPU table tests and GPU tests use the same
 cases so that a GPU failure can be bisected to the flattener or to the kernel)."""
+import json
+import os
+
 import numpy as np
 
 import aho_corasick_1975_amd as acm
@@ -22,6 +25,21 @@ def build_pair_packed(data, off, sym_size=1, variant=po.AC75):
     m.add_keywords_packed(data, off)
     o.add_keywords_packed(data, off)
     return m, o
+
+
+PLAN_SHAPES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plan_shapes.json")
+_plan_shapes = None
+
+
+def assert_plan_shape(key, plan):
+    """plan.describe() (every ACMPlanInfo field) equals what tests/golden/plan_shapes.json recorded
+    for the case `key`: which kernel family a dictionary gets and how its tables and LDS are laid out."""
+    global _plan_shapes
+    if _plan_shapes is None:
+        with open(PLAN_SHAPES) as f:
+            _plan_shapes = json.load(f)
+    assert key in _plan_shapes, key
+    assert plan.describe() == _plan_shapes[key], (key, plan.describe(), _plan_shapes[key])
 
 
 def rand_words(rng, n, lo, hi, minlen, maxlen, dtype=np.uint8):

@@ -8,7 +8,7 @@ import pytest
 
 import aho_corasick_1975_amd as acm
 from oracle import pyoracle as po
-from tests.cases import build_pair, build_pair_packed, small_cases
+from tests.cases import assert_plan_shape, build_pair, build_pair_packed, small_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -559,6 +559,7 @@ def test_small_grids_every_part_of_the_tile_pool_has_a_block(torch_cuda, monkeyp
         monkeypatch.setenv("ACM_GPU_GRID_BLOCKS", str(blocks))
         m, _ = build_pair(kws, sym)
         plan = m.plan(0)
+        assert_plan_shape("small_grids/%s/%d" % (kind, blocks), plan)
         assert plan.info.kernel == kernel and plan.info.grid_blocks in (blocks, blocks * 16), (kind, plan.describe())
         if kind.startswith("gram"):
             assert plan.info.variant == (2 if kind == "gram2" else 0)
@@ -610,6 +611,7 @@ def test_config2_full_size_properties(torch_cuda):
     m = acm.Machine(1)
     m.add_keywords_packed(kd, ko)
     plan = m.plan(0)
+    assert_plan_shape("config2", plan)
     n = 1 << 30
     text = acm.synth.device_text(n, kd, ko)
     whole = plan.scan_sorted(text)
@@ -645,6 +647,7 @@ def test_u32_config5_shape(torch_cuda, monkeypatch, mode):
     dev = acm.synth.device_text(n, kd, ko, sym_bytes=4)
     assert np.array_equal(dev.cpu().numpy().view(np.uint32), text)
     plan = m.plan(0)
+    assert_plan_shape("config5/" + mode, plan)
     assert plan.info.kernel == (3 if mode == "walk" else 4)   # root table in LDS either way
     want = o.scan(text)
     assert np.array_equal(plan.scan_sorted(dev), want)
@@ -668,6 +671,7 @@ def test_100k_dictionary_config3_shape(torch_cuda, monkeypatch, mode):
     n = 1 << 24
     text = acm.synth.text(n, kd, ko)
     plan = m.plan(0)
+    assert_plan_shape("config3/" + mode, plan)
     assert plan.info.kernel == (5 if mode == "gram" else 1)
     got = plan.scan_sorted(_dev(torch_cuda, text))
     cnt, dig = o.scan_mt(text, 8)
@@ -1206,6 +1210,7 @@ def test_interleaved_classes_and_u16_on_the_gpu(torch_cuda, kat):
         o.add_keyword(kw)
     text = rng.integers(0, 256, size=300001).astype(np.uint8)
     plan = m.plan_classes(0)
+    assert_plan_shape("classes/u8", plan)
     assert np.array_equal(plan.scan_sorted(_dev(torch_cuda, text)), o.scan(text))
     # 2-byte symbols, case-insensitive over UTF-16 units
     kws16 = [np.array([ord(c) for c in w], np.uint16) for w in ("Été", "STRASSE", "naïve", "Ωmega", "x")]
@@ -1216,6 +1221,7 @@ def test_interleaved_classes_and_u16_on_the_gpu(torch_cuda, kat):
         o16.add_keyword(kw)
     text16 = np.array([ord(c) for c in "l'été ÉTÉ Strasse straße NAÏVE ωMEGA ΩMEGa xX " * 999], np.uint16)
     plan16 = m16.plan_classes(0)
+    assert_plan_shape("classes/u16", plan16)
     want16 = o16.scan(text16)
     assert want16.size >= 999 * 8
     assert np.array_equal(plan16.scan_sorted(_dev(torch_cuda, text16)), want16)
@@ -1298,6 +1304,7 @@ def test_comparator_classes_text_of_two_million_distinct_symbols(torch_cuda, kat
         m.add_keyword(_u32(w))
         o.add_keyword(_u32(w))
     plan = m.plan_classes(0)
+    assert_plan_shape("classes/u32", plan)
     n = 1 << 21
     text = (0x10000 + np.arange(n, dtype=np.uint32) * 3).astype(np.uint32)      # 2 M distinct symbols, none of the dictionary's
     for at, w in ((5, "uSHErs"), (100000, "His"), (n - 4, "hers")):
@@ -1631,14 +1638,22 @@ def test_record_chunks_of_4096_slots(torch_cuda, monkeypatch, kind, seg_log2, cl
             assert np.array_equal(part, o_part)
 
 
-@pytest.mark.parametrize("kind,seed", [(k, s) for k in ("dense", "gramheads", "gram", "gramold", "gram26", "gram30", "gramsmall", "wide", "wideshort", "sticky", "short", "shortlds", "starts16", "starts32", "walk16", "walk32")
+# cases of _random_case under a plan-shaping switch: name -> (kind, switches).  (ACM_GPU_SHORT_BLOCKS=1
+# changes only the grid of scan_short_kernel's count-only launches, which ACMPlanInfo does not show:
+# its recorded shape is the plain `short` one, and what the case checks is the scans under the switch.)
+SWITCHED_CASES = {"gram30-nobloom": ("gram30", {"ACM_GPU_BLOOM": "0"}), "short-blocks1": ("short", {"ACM_GPU_SHORT_BLOCKS": "1"})}
+
+
+@pytest.mark.parametrize("kind,seed", [(k, s) for k in ("dense", "gramheads", "gram", "gramold", "gram26", "gram30", "gramsmall", "wide", "wideshort", "sticky", "short", "shortlds", "starts16", "starts32", "walk16", "walk32", *SWITCHED_CASES)
                                        for s in range(int(os.environ.get("ACM_SOAK_SEEDS", "3")))])   # ACM_SOAK_SEEDS=14: a soak run
 def test_randomized_dictionaries_and_shards(torch_cuda, monkeypatch, kind, seed):
     """Random dictionaries and texts through every kernel family; whole scans, count-only scans and
     random shards (emit_from, pos_base, odd offsets and lengths) against the oracle."""
     rng = np.random.default_rng(1000 * seed + sum(map(ord, kind)))
+    case = kind
+    kind, switches = SWITCHED_CASES.get(case, (kind, {}))
     kws, text, sym, env = _random_case(rng, kind)
-    for k, v in env.items():
+    for k, v in {**env, **switches}.items():
         monkeypatch.setenv(k, v)
     if seed == 2:   # launch segments of 8 Ki symbols instead of 2^31: every kernel family across many seams
         monkeypatch.setenv("ACM_GPU_SEGMENT_LOG2", "13")
@@ -1652,6 +1667,8 @@ def test_randomized_dictionaries_and_shards(torch_cuda, monkeypatch, kind, seed)
             text[at:at + w.size] = w
     m, o = build_pair(kws, sym)
     plan = m.plan(0)
+    if seed <= 2:   # (seeds of a soak run have no recorded shape)
+        assert_plan_shape("randomized/%s/%d" % (case, seed), plan)
     expect = {"dense": 1, "gramheads": 5, "gram": 5, "gramold": 5, "gram26": 5, "gram30": 5, "gramsmall": 5, "wide": 5, "wideshort": 5, "sticky": 1, "short": 5, "shortlds": 5, "starts16": 4, "starts32": 4, "walk16": 3, "walk32": 3}[kind]
     if kind in ("gram", "gramold", "gram26", "gram30", "wide", "wideshort", "sticky", "short", "shortlds"):
         assert plan.info.dense_rows > 32768, "the generator is meant to give more states than the LDS scheme takes"
@@ -1711,11 +1728,13 @@ def test_plan_of_an_empty_machine_and_its_first_keywords(torch_cuda, sym):
     text = (np.arange(5000) % 7 + 1).astype(dt)
     dev = _dev(torch_cuda, text)
     plan = m.plan(0)
+    assert_plan_shape("empty/%d/0" % sym, plan)
     assert plan.scan_sorted(dev).size == 0 and int(plan.count(dev).item()) == 0
-    for kw in ([3], [1, 2, 3], [7, 1], [2, 3, 4, 5, 6], [5]):
+    for i, kw in enumerate(([3], [1, 2, 3], [7, 1], [2, 3, 4, 5, 6], [5])):
         m.add_keyword(np.array(kw, dt))
         o.add_keyword(np.array(kw, dt))
         plan.update(m)
+        assert_plan_shape("empty/%d/%d" % (sym, i + 1), plan)
         want = o.scan(text)
         assert want.size > 0 and np.array_equal(plan.scan_sorted(dev), want)
 
@@ -1735,6 +1754,7 @@ def test_eight_byte_symbols_on_the_gpu(torch_cuda):
         at = int(rng.integers(0, text.size - w.size))
         text[at:at + w.size] = w
     plan = m.plan(0)
+    assert_plan_shape("u64", plan)
     assert plan.info.kernel == 4
     want = o.scan(text)
     assert want.size > 300
@@ -1759,4 +1779,5 @@ def test_eight_byte_symbols_on_the_gpu(torch_cuda):
         m.add_keyword(kw)
         o.add_keyword(kw)
     plan.update(m)
+    assert_plan_shape("u64/update", plan)
     assert np.array_equal(plan.scan_sorted(dev), o.scan(text))
