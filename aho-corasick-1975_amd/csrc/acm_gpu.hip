@@ -90,13 +90,42 @@ struct StartsMirror {
 /* the kernel family of a plan (ACMPlanInfo::kernel) */
 enum class PlanKind : uint32_t { Dense = 1, Csr = 2, Sparse = 3, Starts = 4, Gram = 5 };
 
+/* item buffer of the kernels that park items (dense, start-parallel, 4-gram over hashed windows):
+ * regions x region_items items of 8 B, one region per wave.  A plan owns one; its delta parks in
+ * the same one (ACMPlan::items). */
+struct ItemBuffer {
+  void *items = nullptr;
+  uint32_t *fill = nullptr; /* per region, zero between launches */
+  uint32_t regions = 0, region_items = 0;
+};
+
+/* what a scan of the plan writes on the device besides the caller's records: grown on demand, one
+ * scan at a time per plan (a delta has its own) */
+struct ScanScratch {
+  unsigned long long *d_total = nullptr; /* [0] running total of a scan, [1] low word = expand ticket; zero between scans */
+  unsigned int *d_pool_ctr = nullptr;    /* 2 x POOL_CLASSES tile-pool counters (same allocation), alternating per launch */
+  uint32_t launch_seq = 0;
+  /* the text the kernels walk when it is not the caller's: class ids, interned ids, an aligned copy */
+  void *d_remap = nullptr;
+  size_t remap_bytes = 0;
+  /* 4-gram kernel, narrow alphabets (records straight from the scan kernel): one hole descriptor
+   * per wave and the spill area, one chunk of records per wave (64 MB on 256 CUs) */
+  void *d_holes = nullptr, *d_spill = nullptr;
+  uint32_t spill_chunk = 0; /* slots per chunk the spill area was sized for */
+  uint32_t direct_regions = 0;
+};
+
 struct ACMPlan {
+  /* ---- tables and facts fixed when the plan is built (incremental updates of a Starts plan edit
+   * finfo, TK and d_oinfo: acm_gpu_plan_update, starts_flush) */
   int device = 0;
   PlanKind kind = PlanKind::Csr;
   ACMFlatInfo finfo{};
   ACMPlanInfo info{};
   void *blob = nullptr; /* one device allocation holding every table */
   size_t blob_bytes = 0;
+  int cu_count = 0;
+  uint64_t segment = SEGMENT;
   /* CSR kernel (breadth-first numbering) */
   CsrTables csr{};
   const uint4 *d_oinfo = nullptr;
@@ -131,23 +160,17 @@ struct ACMPlan {
   const uint32_t *d_dstart = nullptr;
   uint32_t lds_image_bytes = 0;
   uint32_t entry_bytes = 0, streams = ACM_DENSE_S, chunk = 64;
-  /* item buffer of the dense kernel: regions x region_items items of 8 B, one region per wave */
-  void *d_items = nullptr;
-  uint32_t *d_fill = nullptr;   /* per region, zero between launches */
-  unsigned long long *d_total = nullptr; /* [0] running total of a scan, [1] low word = expand ticket; zero between scans */
-  unsigned int *d_pool_ctr = nullptr;    /* 2 x POOL_CLASSES tile-pool counters (same allocation), alternating per launch */
-  uint32_t launch_seq = 0;
-  /* comparator-class plans: the text is mapped to class ids into d_remap before every scan */
+  /* comparator-class plans: the text is mapped to class ids into scratch.d_remap before every scan */
   uint16_t *d_classlut = nullptr;
   /* 8-byte symbols: hash table {key, id} of the dictionary's symbols; the text is interned to
-   * 4-byte ids into d_remap and finfo.sym_bytes is 4 (what the kernels walk) */
+   * 4-byte ids into scratch.d_remap and finfo.sym_bytes is 4 (what the kernels walk) */
   uint4 *d_intern = nullptr;
   uint32_t intern_mask = 0;
   uint32_t text_sym_bytes = 0; /* symbol size of the caller's text (== finfo.sym_bytes unless interned) */
   /* comparator classes of 4-byte symbols (ACMFlatView::keys32): every symbol classified so far ->
    * class, on the host and as the device's table {symbol, class + 1}; the text is mapped to class
-   * ids into d_remap before every scan and symbols met for the first time are classified on the
-   * host with the machine's comparator (cmp32; classify_text32) */
+   * ids into scratch.d_remap before every scan and symbols met for the first time are classified on
+   * the host with the machine's comparator (cmp32; classify_text32) -- so these grow with the texts */
   bool cls32 = false;
   std::unordered_map<uint32_t, uint32_t> cls32_known;
   std::vector<uint32_t> cls32_reps; /* one symbol per class, comparator order: class i + 1 */
@@ -162,22 +185,14 @@ struct ACMPlan {
    * map and the device table hold every one of them) */
   static constexpr uint32_t CLS32_CAP_MIN = 1u << 16, CLS32_CAP_MAX = 1u << 22, CLS32_KNOWN_MAX = 1u << 25;
   uint32_t cls32_cap = CLS32_CAP_MIN;
-  void *d_remap = nullptr;
-  size_t remap_bytes = 0;
-  uint32_t regions = 0, region_items = 0;
-  /* 4-gram kernel, narrow alphabets (records straight from the scan kernel): one hole descriptor
-   * per wave and the spill area, one chunk of records per wave (64 MB on 256 CUs) */
-  void *d_holes = nullptr, *d_spill = nullptr;
-  uint32_t spill_chunk = 0; /* slots per chunk the spill area was sized for */
-  uint32_t holes_waves[2] = { 0, 0 }; /* waves of the widest launch of the scan at hand (4-gram pass, short-keyword pass): the holes to close */
-  uint32_t direct_regions = 0;
-  /* a tiled scan in progress (acm_gpu_scan_ordered_device -> scan_tiled): the 4-gram kernel writes
-   * a TileEntry per tile from tiled_dir[tiled_base] on and links its chunks in tiled_prev */
-  void *tiled_dir = nullptr; /* TileEntry[] */
-  uint32_t *tiled_prev = nullptr;
-  uint32_t tiled_base = 0;
 
-  uint64_t segment = SEGMENT;
+  /* ---- what a scan writes */
+  ItemBuffer own_items;
+  ItemBuffer *shared_items = nullptr; /* delta plans: the buffer of the plan they belong to (scans of the two never overlap) */
+  ItemBuffer &items () { return shared_items ? *shared_items : own_items; }
+  ScanScratch scratch;
+
+  /* ---- update state (acm_gpu_plan_update; scan_plan counts delta_scanned and marks `retired`) */
   uint64_t generation = 0; /* for the machine-cached plan */
   /* Dictionary growth without a rebuild (acm_gpu_plan_update): the keywords a machine got after
    * this plan was made live in a small second plan, `delta`, scanned right after this one into the
@@ -189,14 +204,13 @@ struct ACMPlan {
   uint32_t covered_keywords = 0; /* keywords of the machine this plan and its delta report */
   uint32_t kw_base = 0;          /* added to the keyword ids of this plan's records (delta plans) */
   uint32_t merges = 0;           /* updates that rebuilt everything */
-  ACMPlan *items_owner = nullptr; /* delta plans: the plan whose item buffer they park in (scans of the two never overlap) */
   struct Retired {
     ACMPlan *plan;
     hipEvent_t done; /* nullptr until the first scan after the retirement has recorded it */
   };
   std::vector<Retired> retired;
-  int cu_count = 0;
-  /* timing */
+
+  /* ---- timing state (acm_gpu_plan_timing*, timing_begin) */
   bool timing = false;
   uint32_t timing_every = 1, timing_seq = 0; /* events around every timing_every-th launch (acm_gpu_plan_timing) */
   struct LaunchEvents {
@@ -244,79 +258,70 @@ blob_reserve (size_t &cursor, size_t bytes) {
   return at;
 }
 
-template <typename ENTRY, int C, int S, bool CO>
-const void *
-dense_fn () {
-  return reinterpret_cast<const void *> (&scan_dense_kernel<ENTRY, C, S, CO>);
-}
-
+/* ---- the kernel a plan launches, by the plan's own facts: set_lds_attributes and the launch
+ * functions ask the same function, so the attribute is set on what is launched */
+#define KERNEL_FN(...) reinterpret_cast<const void *> (&__VA_ARGS__)
 /* one geometry is built: 64-byte chunks, 2 streams per lane (the template takes others) */
 const void *
-dense_kernel_ptr (uint32_t entry_bytes, uint32_t chunk, uint32_t streams, bool count_only) {
-  (void)chunk;
-  (void)streams;
-  if (entry_bytes == 2)
-    return count_only ? dense_fn<uint16_t, 64, ACM_DENSE_S, true> () : dense_fn<uint16_t, 64, ACM_DENSE_S, false> ();
-  return count_only ? dense_fn<uint32_t, 64, ACM_DENSE_S, true> () : dense_fn<uint32_t, 64, ACM_DENSE_S, false> ();
+dense_kernel (const ACMPlan *p, bool count_only) {
+  if (p->entry_bytes == 2)
+    return count_only ? KERNEL_FN (scan_dense_kernel<uint16_t, 64, ACM_DENSE_S, true>) : KERNEL_FN (scan_dense_kernel<uint16_t, 64, ACM_DENSE_S, false>);
+  return count_only ? KERNEL_FN (scan_dense_kernel<uint32_t, 64, ACM_DENSE_S, true>) : KERNEL_FN (scan_dense_kernel<uint32_t, 64, ACM_DENSE_S, false>);
 }
 
 template <typename SYM>
 const void *
 sparse_fn (bool lut_lds, bool count_only) {
   if (lut_lds)
-    return count_only ? reinterpret_cast<const void *> (&scan_sparse_kernel<SYM, true, true>)
-                      : reinterpret_cast<const void *> (&scan_sparse_kernel<SYM, true, false>);
-  return count_only ? reinterpret_cast<const void *> (&scan_sparse_kernel<SYM, false, true>)
-                    : reinterpret_cast<const void *> (&scan_sparse_kernel<SYM, false, false>);
+    return count_only ? KERNEL_FN (scan_sparse_kernel<SYM, true, true>) : KERNEL_FN (scan_sparse_kernel<SYM, true, false>);
+  return count_only ? KERNEL_FN (scan_sparse_kernel<SYM, false, true>) : KERNEL_FN (scan_sparse_kernel<SYM, false, false>);
 }
 
 const void *
-sparse_kernel_ptr (uint32_t sym_bytes, bool lut_lds, bool count_only) {
-  return sym_bytes == 2 ? sparse_fn<uint16_t> (lut_lds, count_only) : sparse_fn<uint32_t> (lut_lds, count_only);
+sparse_kernel (const ACMPlan *p, bool count_only) {
+  return p->finfo.sym_bytes == 2 ? sparse_fn<uint16_t> (p->sparse_lut_lds, count_only) : sparse_fn<uint32_t> (p->sparse_lut_lds, count_only);
 }
 
 template <typename SYM>
 const void *
 starts_fn (bool lut_lds, bool count_only) {
   if (lut_lds)
-    return count_only ? reinterpret_cast<const void *> (&scan_starts_kernel<SYM, true, true>)
-                      : reinterpret_cast<const void *> (&scan_starts_kernel<SYM, true, false>);
-  return count_only ? reinterpret_cast<const void *> (&scan_starts_kernel<SYM, false, true>)
-                    : reinterpret_cast<const void *> (&scan_starts_kernel<SYM, false, false>);
+    return count_only ? KERNEL_FN (scan_starts_kernel<SYM, true, true>) : KERNEL_FN (scan_starts_kernel<SYM, true, false>);
+  return count_only ? KERNEL_FN (scan_starts_kernel<SYM, false, true>) : KERNEL_FN (scan_starts_kernel<SYM, false, false>);
 }
 
 const void *
-short_kernel_ptr (bool count_only, bool ids_lds) {
+short_kernel (const ACMPlan *p, bool count_only) {
   if (count_only)
-    return reinterpret_cast<const void *> (&scan_short_kernel<true, true>);
-  return ids_lds ? reinterpret_cast<const void *> (&scan_short_kernel<false, true>) : reinterpret_cast<const void *> (&scan_short_kernel<false, false>);
+    return KERNEL_FN (scan_short_kernel<true, true>);
+  return p->short_ids_lds ? KERNEL_FN (scan_short_kernel<false, true>) : KERNEL_FN (scan_short_kernel<false, false>);
 }
 
+/* tiled: a tiled scan (narrow alphabets, record mode) */
 const void *
-gram_kernel_ptr (bool count_only, bool shorts, bool wide, bool tiled = false, bool gram2 = false) {
-  if (gram2) {
+gram_kernel (const ACMPlan *p, bool count_only, bool tiled) {
+  const bool wide = p->hashed, shorts = p->inline_shorts;
+  if (p->gram2) {
     if (tiled)
-      return reinterpret_cast<const void *> (&scan_gram2_kernel<false, true>);
-    return count_only ? reinterpret_cast<const void *> (&scan_gram2_kernel<true, false>) : reinterpret_cast<const void *> (&scan_gram2_kernel<false, false>);
+      return KERNEL_FN (scan_gram2_kernel<false, true>);
+    return count_only ? KERNEL_FN (scan_gram2_kernel<true, false>) : KERNEL_FN (scan_gram2_kernel<false, false>);
   }
   /* (keywords of 1-3 symbols inside the kernel: hashed windows only -- narrow alphabets give them a
    * pass of their own, scan_short_kernel; the instantiations that did both spilled 140 to 320 vector registers) */
   if (tiled) /* (narrow alphabets, record mode) */
-    return reinterpret_cast<const void *> (&scan_gram_kernel<false, false, false, true>);
+    return KERNEL_FN (scan_gram_kernel<false, false, false, true>);
   if (wide && shorts)
-    return count_only ? reinterpret_cast<const void *> (&scan_gram_kernel<true, true, true, false>)
-                      : reinterpret_cast<const void *> (&scan_gram_kernel<false, true, true, false>);
+    return count_only ? KERNEL_FN (scan_gram_kernel<true, true, true, false>) : KERNEL_FN (scan_gram_kernel<false, true, true, false>);
   if (wide)
-    return count_only ? reinterpret_cast<const void *> (&scan_gram_kernel<true, false, true, false>)
-                      : reinterpret_cast<const void *> (&scan_gram_kernel<false, false, true, false>);
-  return count_only ? reinterpret_cast<const void *> (&scan_gram_kernel<true, false, false, false>)
-                    : reinterpret_cast<const void *> (&scan_gram_kernel<false, false, false, false>);
+    return count_only ? KERNEL_FN (scan_gram_kernel<true, false, true, false>) : KERNEL_FN (scan_gram_kernel<false, false, true, false>);
+  return count_only ? KERNEL_FN (scan_gram_kernel<true, false, false, false>) : KERNEL_FN (scan_gram_kernel<false, false, false, false>);
 }
 
 const void *
-starts_kernel_ptr (uint32_t sym_bytes, bool lut_lds, bool count_only) {
-  return sym_bytes == 2 ? starts_fn<uint16_t> (lut_lds, count_only) : starts_fn<uint32_t> (lut_lds, count_only);
+starts_kernel (const ACMPlan *p, bool count_only) {
+  return p->finfo.sym_bytes == 2 ? starts_fn<uint16_t> (p->starts_lut_lds, count_only) : starts_fn<uint32_t> (p->starts_lut_lds, count_only);
 }
+#undef KERNEL_FN
 
 void
 drop_cached_plan (void *p) {
@@ -1255,9 +1260,9 @@ build_tables (PlanBuild &B, ACMPlan *p) {
   if (hipMemcpy (p->blob, B.host.data (), bytes, hipMemcpyHostToDevice) != hipSuccess)
     return ACM_GPU_E_HIP;
   const size_t ctl_bytes = 16 + 2 * POOL_CLASSES * POOL_CTR_STRIDE * sizeof (unsigned int);
-  if (hipMalloc (reinterpret_cast<void **> (&p->d_total), ctl_bytes) != hipSuccess || hipMemset (p->d_total, 0, ctl_bytes) != hipSuccess)
+  if (hipMalloc (reinterpret_cast<void **> (&p->scratch.d_total), ctl_bytes) != hipSuccess || hipMemset (p->scratch.d_total, 0, ctl_bytes) != hipSuccess)
     return ACM_GPU_E_NOMEM;
-  p->d_pool_ctr = reinterpret_cast<unsigned int *> (p->d_total + 2);
+  p->scratch.d_pool_ctr = reinterpret_cast<unsigned int *> (p->scratch.d_total + 2);
   unsigned char *b = static_cast<unsigned char *> (p->blob);
   bind_common (p, B, T, b);
   bind_dense (p, B, D, b);
@@ -1270,33 +1275,32 @@ build_tables (PlanBuild &B, ACMPlan *p) {
 /* the dynamic LDS of the kernels the plan launches */
 int
 set_lds_attributes (const ACMPlan *p) {
-  const uint32_t sb = p->finfo.sym_bytes;
   for (int co = 0; co < 2; co++) {
     switch (p->kind) {
     case PlanKind::Dense:
-      HIP_TRY (hipFuncSetAttribute (dense_kernel_ptr (p->entry_bytes, p->chunk, p->streams, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
+      HIP_TRY (hipFuncSetAttribute (dense_kernel (p, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)p->info.lds_bytes));
       break;
     case PlanKind::Starts:
-      HIP_TRY (hipFuncSetAttribute (starts_kernel_ptr (sb, p->starts_lut_lds, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
+      HIP_TRY (hipFuncSetAttribute (starts_kernel (p, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)p->starts_lds_bytes));
       [[fallthrough]]; /* (the sparse walk takes the segments that are not 16-byte aligned) */
     case PlanKind::Sparse:
-      HIP_TRY (hipFuncSetAttribute (sparse_kernel_ptr (sb, p->sparse_lut_lds, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
+      HIP_TRY (hipFuncSetAttribute (sparse_kernel (p, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)p->sparse_lds_bytes));
       break;
     case PlanKind::Gram:
-      HIP_TRY (hipFuncSetAttribute (gram_kernel_ptr (co != 0, p->inline_shorts, p->hashed, false, p->gram2), hipFuncAttributeMaxDynamicSharedMemorySize,
+      HIP_TRY (hipFuncSetAttribute (gram_kernel (p, co != 0, false), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)p->gram_lds_bytes));
       if (p->short_pass)
-        HIP_TRY (hipFuncSetAttribute (short_kernel_ptr (co != 0, p->short_ids_lds), hipFuncAttributeMaxDynamicSharedMemorySize,
+        HIP_TRY (hipFuncSetAttribute (short_kernel (p, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)(co ? p->short_lds_count_bytes : p->short_lds_bytes)));
       break;
     case PlanKind::Csr: break;
     }
   }
   if (p->kind == PlanKind::Gram && !p->hashed)
-    HIP_TRY (hipFuncSetAttribute (gram_kernel_ptr (false, p->inline_shorts, false, true, p->gram2), hipFuncAttributeMaxDynamicSharedMemorySize,
+    HIP_TRY (hipFuncSetAttribute (gram_kernel (p, false, true), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)p->gram_lds_bytes));
   return ACM_GPU_OK;
 }
@@ -1471,18 +1475,12 @@ acm_gpu_plan_destroy (ACMPlan *plan) {
     (void)hipEventDestroy (ev.scan_done);
     (void)hipEventDestroy (ev.all_done);
   }
-  if (plan->blob)
-    (void)hipFree (plan->blob);
-  if (plan->d_items && !plan->items_owner)
-    (void)hipFree (plan->d_items);
-  if (plan->d_fill && !plan->items_owner)
-    (void)hipFree (plan->d_fill);
-  if (plan->d_holes)
-    (void)hipFree (plan->d_holes);
-  if (plan->d_spill)
-    (void)hipFree (plan->d_spill);
-  if (plan->d_total)
-    (void)hipFree (plan->d_total);
+  /* the device allocations of the plan's own (a delta's item buffer is its owner's) */
+  void *const owned[] = { plan->blob, plan->own_items.items, plan->own_items.fill, plan->scratch.d_holes, plan->scratch.d_spill, plan->scratch.d_total,
+                          plan->scratch.d_remap, plan->d_intern, plan->d_cls32, plan->d_unknown, plan->d_classlut };
+  for (void *d : owned)
+    if (d)
+      (void)hipFree (d);
   if (plan->mir) {
     if (plan->mir->own)
       for (int t = 0; t < 5; t++)
@@ -1492,16 +1490,6 @@ acm_gpu_plan_destroy (ACMPlan *plan) {
       (void)hipFree (plan->mir->d_patches);
     delete plan->mir;
   }
-  if (plan->d_intern)
-    (void)hipFree (plan->d_intern);
-  if (plan->d_cls32)
-    (void)hipFree (plan->d_cls32);
-  if (plan->d_unknown)
-    (void)hipFree (plan->d_unknown);
-  if (plan->d_classlut)
-    (void)hipFree (plan->d_classlut);
-  if (plan->d_remap)
-    (void)hipFree (plan->d_remap);
   delete plan;
 }
 
@@ -1521,10 +1509,10 @@ acm_gpu_plan_status (ACMPlan *plan) {
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
   HIP_TRY (hipDeviceSynchronize ());
-  if (!plan->d_total)
+  if (!plan->scratch.d_total)
     return ACM_GPU_OK;
   unsigned int words[4] = { 0, 0, 0, 0 };
-  HIP_TRY (hipMemcpy (words, plan->d_total, sizeof words, hipMemcpyDeviceToHost));
+  HIP_TRY (hipMemcpy (words, plan->scratch.d_total, sizeof words, hipMemcpyDeviceToHost));
   if (words[3])
     return ACM_GPU_E_INTERNAL;
   return plan->delta ? acm_gpu_plan_status (plan->delta) : ACM_GPU_OK;
@@ -1624,7 +1612,7 @@ launch_sparse (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st) {
   if ((tiles + wpb - 1) / wpb < grid)
     grid = (tiles + wpb - 1) / wpb;
   void *args[] = { &K, const_cast<EmitCtx *> (&E), &a, &a.text };
-  HIP_TRY (hipLaunchKernel (sparse_kernel_ptr (p->finfo.sym_bytes, p->sparse_lut_lds, COUNT_ONLY), dim3 (grid),
+  HIP_TRY (hipLaunchKernel (sparse_kernel (p, COUNT_ONLY), dim3 (grid),
                             dim3 (SPARSE_THREADS), args, p->sparse_lds_bytes, st));
   return ACM_GPU_OK;
 }
@@ -1639,81 +1627,91 @@ set_tile_pool (ACMPlan *p, Launch &a, uint32_t waves) {
   const uint32_t blocks = waves / (SPARSE_THREADS / WAVE) > 0 ? waves / (SPARSE_THREADS / WAVE) : 1;
   a.pool_classes = blocks < POOL_CLASSES ? blocks : POOL_CLASSES; /* (grids of fewer blocks than parts: every part must have a block) */
   a.pool_class_tiles = (pool + a.pool_classes - 1) / a.pool_classes;
-  a.pool_ctr = p->d_pool_ctr + (p->launch_seq & 1) * POOL_CLASSES * POOL_CTR_STRIDE;
-  a.pool_reset = p->d_pool_ctr + ((p->launch_seq & 1) ^ 1) * POOL_CLASSES * POOL_CTR_STRIDE;
-  p->launch_seq++;
+  a.pool_ctr = p->scratch.d_pool_ctr + (p->scratch.launch_seq & 1) * POOL_CLASSES * POOL_CTR_STRIDE;
+  a.pool_reset = p->scratch.d_pool_ctr + ((p->scratch.launch_seq & 1) ^ 1) * POOL_CLASSES * POOL_CTR_STRIDE;
+  p->scratch.launch_seq++;
 }
 
 /* records of the hits parked by `regions_used` waves of the start-parallel / 4-gram kernels */
 void
 launch_expand_hits (ACMPlan *p, const EmitCtx &E, uint32_t regions_used, hipStream_t st) {
   /* 1024 threads per 16 regions (config 3, 4 GiB: 1.10 ms; 8, 4, 2 regions or smaller blocks: 1.25-1.33) */
+  const ItemBuffer &I = p->items ();
   hipLaunchKernelGGL ((expand_hits_kernel<1024, 16>), dim3 ((regions_used + 15) / 16), dim3 (1024), 0, st, E,
-                      static_cast<const uint2 *> (p->d_items), p->region_items, p->d_fill, regions_used);
+                      static_cast<const uint2 *> (I.items), I.region_items, I.fill, regions_used);
+}
+
+/* The tiles of one launch of a start-parallel kernel (scan_starts, scan_gram / gram2, scan_short)
+ * over a segment of n symbols: tile t is the groups [t * R, (t + 1) * R) of `group` symbols each,
+ * the launch takes the tiles [begin, end) with `grid` blocks.
+ *   back    a match that ends at emit_from or later starts no earlier than emit_from - back: the
+ *           groups in front of that one are skipped
+ *   blocks  the blocks of a full grid: R = groups to scan / (16 tiles for each of their waves),
+ *           within 4 .. 64 (4 to 64 KiB of text a tile); fewer blocks than that when there are few tiles
+ *   round4  R a multiple of 4 (kernels that take a tile's groups four at a time)
+ *   fixed_R not 0: R whatever the text (experiments) */
+struct TileGeometry {
+  uint32_t R, begin, end, grid;
+};
+constexpr uint32_t TILE_R_MIN = 4, TILE_R_MAX = 64;
+TileGeometry
+tile_geometry (uint32_t n, uint32_t emit_from, uint32_t group, uint32_t back, uint32_t blocks, bool round4, uint32_t fixed_R = 0) {
+  const uint32_t wpb = SPARSE_THREADS / WAVE;
+  const uint32_t ngroups = (uint32_t)(((uint64_t)n + group - 1) / group);
+  const uint32_t first_group = (emit_from > back ? emit_from - back : 0) / group;
+  uint64_t R = (ngroups - first_group) / ((uint64_t)blocks * wpb * 16);
+  if (round4)
+    R &= ~3ull;
+  R = R < TILE_R_MIN ? TILE_R_MIN : (R > TILE_R_MAX ? TILE_R_MAX : R);
+  if (fixed_R)
+    R = fixed_R;
+  TileGeometry T;
+  T.R = (uint32_t)R;
+  T.begin = first_group / T.R;
+  T.end = (uint32_t)((ngroups + R - 1) / R);
+  const uint32_t tiles = T.end - T.begin;
+  T.grid = (tiles + wpb - 1) / wpb < blocks ? (tiles + wpb - 1) / wpb : blocks;
+  return T;
+}
+
+/* a match that ends at emit_from or later starts no earlier than emit_from - (lmax - 1) */
+uint32_t
+lookback (const ACMPlan *p) {
+  return p->finfo.lmax > 1 ? p->finfo.lmax - 1 : 0;
 }
 
 template <bool COUNT_ONLY>
 int
 launch_starts (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t stop) {
-  const uint32_t group = WAVE * (16 / p->finfo.sym_bytes); /* symbols per 1 KiB group */
-  const uint32_t ngroups = (uint32_t)(((uint64_t)a.n + group - 1) / group);
-  uint32_t grid = p->info.grid_blocks;
   const uint32_t wpb = SPARSE_THREADS / WAVE;
-  /* a match that ends at emit_from or later starts no earlier than emit_from - (lmax - 1) */
-  const uint32_t back = p->finfo.lmax > 1 ? p->finfo.lmax - 1 : 0;
-  const uint32_t first_group = (a.emit_from > back ? a.emit_from - back : 0) / group;
-  /* groups per tile: about sixteen tiles per wave, 4 to 64 KiB each, a multiple of 4 */
-  uint64_t R = (ngroups - first_group) / ((uint64_t)grid * wpb * 16) & ~3ull;
-  if (R < 4)
-    R = 4;
-  if (R > 64)
-    R = 64;
+  /* groups of 1 KiB; about sixteen tiles per wave, 4 to 64 KiB each, a multiple of 4 */
+  const TileGeometry T = tile_geometry (a.n, a.emit_from, WAVE * (16 / p->finfo.sym_bytes), lookback (p), p->info.grid_blocks, true);
   StartsK K = p->TK;
-  K.R = (uint32_t)R;
-  a.range_begin = first_group / (uint32_t)R;
-  a.range_end = (uint32_t)((ngroups + R - 1) / R);
-  const uint32_t tiles = a.range_end - a.range_begin;
-  if ((tiles + wpb - 1) / wpb < grid)
-    grid = (tiles + wpb - 1) / wpb;
-  set_tile_pool (p, a, grid * wpb);
-  void *items = COUNT_ONLY ? nullptr : p->d_items;
-  uint32_t *fill = COUNT_ONLY ? nullptr : p->d_fill;
-  void *args[] = { &K, const_cast<EmitCtx *> (&E), &a, &a.text, &items, &p->region_items, &fill };
-  HIP_TRY (hipLaunchKernel (starts_kernel_ptr (p->finfo.sym_bytes, p->starts_lut_lds, COUNT_ONLY), dim3 (grid),
-                            dim3 (SPARSE_THREADS), args, p->starts_lds_bytes, st));
+  K.R = T.R;
+  a.range_begin = T.begin;
+  a.range_end = T.end;
+  set_tile_pool (p, a, T.grid * wpb);
+  ItemBuffer &I = p->items ();
+  void *items = COUNT_ONLY ? nullptr : I.items;
+  uint32_t *fill = COUNT_ONLY ? nullptr : I.fill;
+  void *args[] = { &K, const_cast<EmitCtx *> (&E), &a, &a.text, &items, &I.region_items, &fill };
+  HIP_TRY (hipLaunchKernel (starts_kernel (p, COUNT_ONLY), dim3 (T.grid), dim3 (SPARSE_THREADS), args, p->starts_lds_bytes, st));
   if (stop) /* the timing brackets the scan kernel alone, as for the dense kernel */
     HIP_TRY (hipEventRecord (stop, st));
   if (!COUNT_ONLY)
-    launch_expand_hits (p, E, grid * wpb, st);
+    launch_expand_hits (p, E, T.grid * wpb, st);
   return ACM_GPU_OK;
 }
 
-/* the tiles of one launch of the 4-gram kernel over a segment of n symbols: R groups of 1,024
- * symbols each, tiles [begin, end) */
-struct GramTiling {
-  uint32_t R, begin, end;
-};
-constexpr uint32_t GRAM_R_MIN = 4; /* groups per tile, at least (tiled_layout's bound counts on it) */
-GramTiling
+/* the tiles of one launch of the 4-gram kernel over a segment of n symbols: groups of 1,024
+ * symbols, one block a CU, R as it comes (any number of groups; tiled_layout's bound counts on
+ * GRAM_R_MIN) */
+constexpr uint32_t GRAM_R_MIN = TILE_R_MIN;
+TileGeometry
 gram_tiling (const ACMPlan *p, uint32_t n, uint32_t emit_from) {
-  const uint32_t group = WAVE * 16;
-  const uint32_t ngroups = (uint32_t)(((uint64_t)n + group - 1) / group);
-  const uint32_t wpb = SPARSE_THREADS / WAVE;
-  const uint32_t back = p->finfo.lmax > 1 ? p->finfo.lmax - 1 : 0;
-  const uint32_t first_group = (emit_from > back ? emit_from - back : 0) / group;
-  uint64_t R = (ngroups - first_group) / ((uint64_t)p->cu_count * wpb * 16);
-  if (R < GRAM_R_MIN)
-    R = GRAM_R_MIN;
-  if (R > 64)
-    R = 64;
   static const int r_env = getenv ("ACM_GPU_GRAM_R") ? atoi (getenv ("ACM_GPU_GRAM_R")) : 0; /* experiments: groups per tile (a multiple of 4, up to 64) */
-  if (r_env >= 4 && r_env <= 64 && r_env % 4 == 0)
-    R = (uint64_t)r_env;
-  GramTiling t;
-  t.R = (uint32_t)R;
-  t.begin = first_group / (uint32_t)R;
-  t.end = (uint32_t)((ngroups + R - 1) / R);
-  return t;
+  const uint32_t fixed_R = (r_env >= 4 && r_env <= 64 && r_env % 4 == 0) ? (uint32_t)r_env : 0;
+  return tile_geometry (n, emit_from, WAVE * 16, lookback (p), (uint32_t)p->cu_count, false, fixed_R);
 }
 
 /* ACM_GPU_CLOSE_SORT=network: close_holes_kernel sorts its descriptors with the bitonic network whatever
@@ -1734,54 +1732,62 @@ launch_close_holes (ACMPlan *p, const EmitCtx &E, const RecHole *holes, uint32_t
     npow <<= 1;
   const uint32_t blocks = n_waves / 16 > 0 ? n_waves / 16 : 1; /* 16 holes per block */
   hipLaunchKernelGGL (close_holes_kernel, dim3 (blocks), dim3 (CLOSE_THREADS), npow * 16, st, E, holes, n_waves, npow,
-                      reinterpret_cast<unsigned int *> (p->d_total + 1), close_network_only ());
+                      reinterpret_cast<unsigned int *> (p->scratch.d_total + 1), close_network_only ());
   return hipGetLastError ();
 }
 
+/* a tiled scan in progress (acm_gpu_scan_ordered_device -> scan_tiled): the 4-gram kernel writes a
+ * TileEntry per tile from dir[base] on and links its chunks in chunk_prev */
+struct TiledScan {
+  TileEntry *dir;
+  uint32_t *chunk_prev;
+  uint32_t base; /* tiles of the launches so far */
+};
+
+/* holes_waves: waves of the widest launch of the scan at hand so far -- the holes to close behind its
+ * last segment; tiled: the scan is a tiled one (narrow alphabets, record mode) */
 template <bool COUNT_ONLY>
 int
-launch_gram (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t stop, bool first_segment, bool last_segment) {
-  uint32_t grid = (uint32_t)p->cu_count;
+launch_gram (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t stop, bool first_segment, bool last_segment,
+             uint32_t &holes_waves, TiledScan *tiled) {
   const uint32_t wpb = SPARSE_THREADS / WAVE;
-  const GramTiling T = gram_tiling (p, a.n, a.emit_from);
+  const TileGeometry T = gram_tiling (p, a.n, a.emit_from);
+  const uint32_t grid = T.grid, tiles = T.end - T.begin;
   GramK K = p->GK;
   K.R = T.R;
   a.range_begin = T.begin;
   a.range_end = T.end;
-  const uint32_t tiles = a.range_end - a.range_begin;
-  if ((tiles + wpb - 1) / wpb < grid)
-    grid = (tiles + wpb - 1) / wpb;
   set_tile_pool (p, a, grid * wpb);
   /* narrow alphabets: the kernel writes the records itself (no item buffer, no expansion; the holes
    * its waves leave in their last chunks are closed right behind it); hashed windows: hits parked
    * per wave and expanded as in the start-parallel kernel */
   const bool direct = !p->hashed;
-  void *items = (COUNT_ONLY || direct) ? nullptr : p->d_items;
-  uint32_t *fill = (COUNT_ONLY || direct) ? nullptr : p->d_fill;
-  void *holes = (!COUNT_ONLY && direct) ? p->d_holes : nullptr;
+  ItemBuffer &I = p->items ();
+  void *items = (COUNT_ONLY || direct) ? nullptr : I.items;
+  uint32_t *fill = (COUNT_ONLY || direct) ? nullptr : I.fill;
+  void *holes = (!COUNT_ONLY && direct) ? p->scratch.d_holes : nullptr;
   /* the segments of one scan share the waves' chunks of records: a wave picks up in segment k + 1
    * the chunk it was filling at the end of segment k (its hole descriptor says where), and the
    * holes are closed once, behind the last segment */
   uint32_t resume = first_segment ? 0u : 1u;
   if (holes && first_segment)
-    HIP_TRY (hipMemsetAsync (holes, 0, (size_t)p->direct_regions * sizeof (RecHole), st));
-  if (first_segment || grid * wpb > p->holes_waves[0])
-    p->holes_waves[0] = grid * wpb;
+    HIP_TRY (hipMemsetAsync (holes, 0, (size_t)p->scratch.direct_regions * sizeof (RecHole), st));
+  if (first_segment || grid * wpb > holes_waves)
+    holes_waves = grid * wpb;
   /* a tiled scan: a directory entry per tile, the chunks linked, the holes left alone (dev_tiles.h) */
-  TileEntry *dir = (!COUNT_ONLY && direct) ? static_cast<TileEntry *> (p->tiled_dir) : nullptr;
-  uint32_t dir_base = p->tiled_base;
-  if (dir)
-    p->tiled_base += tiles;
-  void *args[] = { &K, const_cast<EmitCtx *> (&E), &a, &a.text, &items, &p->region_items, &fill, &holes, &resume, &dir, &dir_base };
-  HIP_TRY (hipLaunchKernel (gram_kernel_ptr (COUNT_ONLY, p->inline_shorts, p->hashed, dir != nullptr, p->gram2), dim3 (grid), dim3 (SPARSE_THREADS), args,
-                            p->gram_lds_bytes, st));
+  TileEntry *dir = tiled ? tiled->dir : nullptr;
+  uint32_t dir_base = tiled ? tiled->base : 0;
+  if (tiled)
+    tiled->base += tiles;
+  void *args[] = { &K, const_cast<EmitCtx *> (&E), &a, &a.text, &items, &I.region_items, &fill, &holes, &resume, &dir, &dir_base };
+  HIP_TRY (hipLaunchKernel (gram_kernel (p, COUNT_ONLY, tiled != nullptr), dim3 (grid), dim3 (SPARSE_THREADS), args, p->gram_lds_bytes, st));
   if (stop)
     HIP_TRY (hipEventRecord (stop, st));
   if (!COUNT_ONLY) {
-    if (direct && dir) {
+    if (direct && tiled) {
       /* (nothing: tile_gather_kernel reads the records where they lie) */
     } else if (direct && last_segment) {
-      HIP_TRY (launch_close_holes (p, E, static_cast<const RecHole *> (p->d_holes), p->holes_waves[0], st));
+      HIP_TRY (launch_close_holes (p, E, static_cast<const RecHole *> (p->scratch.d_holes), holes_waves, st));
     } else if (!direct)
       launch_expand_hits (p, E, grid * wpb, st);
   }
@@ -1792,38 +1798,33 @@ launch_gram (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t 
  * segment (dev_short.h), into the same record buffer; its waves' holes have descriptors of their own */
 template <bool COUNT_ONLY>
 int
-launch_short (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t stop, bool first_segment, bool last_segment) {
-  /* (count-only: 61 registers, two blocks a CU while LDS allows; with records one) */
-  uint32_t grid = (uint32_t)p->cu_count * (COUNT_ONLY ? p->short_blocks_per_cu : 1u);
+launch_short (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t stop, bool first_segment, bool last_segment,
+              uint32_t &holes_waves) {
   const uint32_t wpb = SPARSE_THREADS / WAVE;
-  const uint32_t short_regions = p->direct_regions;
-  /* a match of 1-3 symbols that ends at emit_from or later starts no earlier than emit_from - 2 */
-  const uint32_t group = WAVE * 16;
-  const uint32_t ngroups = (uint32_t)(((uint64_t)a.n + group - 1) / group);
-  const uint32_t first_group = (a.emit_from > 2 ? a.emit_from - 2 : 0) / group;
-  uint64_t R = (ngroups - first_group) / ((uint64_t)grid * wpb * 16);
-  R = R < 4 ? 4 : (R > 64 ? 64 : R & ~3ull); /* (a multiple of 4: the kernel takes a tile's groups four at a time) */
+  const uint32_t short_regions = p->scratch.direct_regions;
+  /* (count-only: 61 registers, two blocks a CU while LDS allows; with records one.)  A match of 1-3
+   * symbols that ends at emit_from or later starts no earlier than emit_from - 2; R a multiple of
+   * 4: the kernel takes a tile's groups four at a time */
+  const TileGeometry T = tile_geometry (a.n, a.emit_from, WAVE * 16, 2, (uint32_t)p->cu_count * (COUNT_ONLY ? p->short_blocks_per_cu : 1u), true);
+  const uint32_t grid = T.grid;
   GramK K = p->GK;
-  K.R = (uint32_t)R;
-  a.range_begin = first_group / (uint32_t)R;
-  a.range_end = (uint32_t)((ngroups + R - 1) / R);
-  const uint32_t tiles = a.range_end - a.range_begin;
-  if ((tiles + wpb - 1) / wpb < grid)
-    grid = (tiles + wpb - 1) / wpb;
+  K.R = T.R;
+  a.range_begin = T.begin;
+  a.range_end = T.end;
   set_tile_pool (p, a, grid * wpb);
-  RecHole *holes = COUNT_ONLY ? nullptr : static_cast<RecHole *> (p->d_holes) + p->direct_regions;
+  RecHole *holes = COUNT_ONLY ? nullptr : static_cast<RecHole *> (p->scratch.d_holes) + p->scratch.direct_regions;
   uint32_t resume = first_segment ? 0u : 1u;
   if (holes && first_segment)
     HIP_TRY (hipMemsetAsync (holes, 0, (size_t)short_regions * sizeof (RecHole), st));
-  if (first_segment || grid * wpb > p->holes_waves[1])
-    p->holes_waves[1] = grid * wpb;
+  if (first_segment || grid * wpb > holes_waves)
+    holes_waves = grid * wpb;
   void *args[] = { &K, const_cast<EmitCtx *> (&E), &a, &a.text, &holes, &resume };
-  HIP_TRY (hipLaunchKernel (short_kernel_ptr (COUNT_ONLY, p->short_ids_lds), dim3 (grid), dim3 (SPARSE_THREADS), args,
+  HIP_TRY (hipLaunchKernel (short_kernel (p, COUNT_ONLY), dim3 (grid), dim3 (SPARSE_THREADS), args,
                             COUNT_ONLY ? p->short_lds_count_bytes : p->short_lds_bytes, st));
   if (stop)
     HIP_TRY (hipEventRecord (stop, st));
   if (!COUNT_ONLY && last_segment)
-    HIP_TRY (launch_close_holes (p, E, holes, p->holes_waves[1], st));
+    HIP_TRY (launch_close_holes (p, E, holes, holes_waves, st));
   return ACM_GPU_OK;
 }
 
@@ -1863,76 +1864,73 @@ ensure_item_buffer (ACMPlan *user, uint64_t n, uint32_t symbols_per_item = 256, 
   /* a delta plan parks in the buffer of the plan it belongs to: their scans run one after the
    * other on one stream, and a fresh 140 MB buffer (with the waits it takes to set one up) for
    * every delta made every dictionary change cost more than the delta itself */
-  ACMPlan *p = user->items_owner ? user->items_owner : user;
+  ItemBuffer *buf = &user->items ();
   /* one region per wave of the kernels that park items (dense, 4-gram, start-parallel: one block of
    * 16 waves per CU) -- of the plan that SCANS, not of the buffer's owner: an owner of the CSR kind
    * (a plan made from an empty machine) has cu_count * 16 single-wave blocks, which sized the
    * buffer of a dense delta at 65,536 regions x 4,352 items = 2.3 GB */
   uint32_t regions = (uint32_t)user->cu_count * (DENSE_THREADS / WAVE);
-  if (p->d_items && p->regions > regions)
-    regions = p->regions; /* (shared by a plan and its delta: never shrink what the other one uses) */
+  if (buf->items && buf->regions > regions)
+    regions = buf->regions; /* (shared by a plan and its delta: never shrink what the other one uses) */
   uint64_t per = (n / symbols_per_item + regions - 1) / regions;
   per = (per + 63) / 64 * 64;
   if (per < min_items)
     per = min_items;
   if (per > (1u << 20))
     per = 1u << 20;
-  if (!(p->d_items && p->regions == regions && p->region_items >= per)) {
-    if (p->d_items || p->d_fill)
+  if (!(buf->items && buf->regions == regions && buf->region_items >= per)) {
+    if (buf->items || buf->fill)
       HIP_TRY (hipDeviceSynchronize ()); /* earlier scans (pieces of a stream) may still be parking items */
-    if (p->d_items)
-      HIP_TRY (hipFree (p->d_items));
-    if (p->d_fill)
-      HIP_TRY (hipFree (p->d_fill));
-    p->d_items = nullptr;
-    p->d_fill = nullptr;
-    if (hipMalloc (&p->d_items, (size_t)regions * per * 8) != hipSuccess)
+    if (buf->items)
+      HIP_TRY (hipFree (buf->items));
+    if (buf->fill)
+      HIP_TRY (hipFree (buf->fill));
+    buf->items = nullptr;
+    buf->fill = nullptr;
+    if (hipMalloc (&buf->items, (size_t)regions * per * 8) != hipSuccess)
       return ACM_GPU_E_NOMEM;
-    if (hipMalloc (reinterpret_cast<void **> (&p->d_fill), (size_t)regions * 4) != hipSuccess)
+    if (hipMalloc (reinterpret_cast<void **> (&buf->fill), (size_t)regions * 4) != hipSuccess)
       return ACM_GPU_E_NOMEM;
-    HIP_TRY (hipMemset (p->d_fill, 0, (size_t)regions * 4));
+    HIP_TRY (hipMemset (buf->fill, 0, (size_t)regions * 4));
     /* the memset runs on the null stream; the scans may run on streams that do not wait for it */
     HIP_TRY (hipDeviceSynchronize ());
-    p->regions = regions;
-    p->region_items = (uint32_t)per;
+    buf->regions = regions;
+    buf->region_items = (uint32_t)per;
   }
-  user->d_items = p->d_items;
-  user->d_fill = p->d_fill;
-  user->regions = p->regions;
-  user->region_items = p->region_items;
+  return ACM_GPU_OK;
+}
+
+/* hole descriptors and spill area of a plan whose scan kernel writes the records itself */
+int
+ensure_direct_buffers (ACMPlan *p, uint32_t rec_chunk) {
+  const uint32_t regions = (uint32_t)p->cu_count * (SPARSE_THREADS / WAVE);
+  if (p->scratch.d_holes && p->scratch.d_spill && p->scratch.direct_regions >= regions && p->scratch.spill_chunk >= rec_chunk)
+    return ACM_GPU_OK;
+  if (p->scratch.d_holes || p->scratch.d_spill)
+    HIP_TRY (hipDeviceSynchronize ());
+  if (p->scratch.d_holes)
+    HIP_TRY (hipFree (p->scratch.d_holes));
+  if (p->scratch.d_spill)
+    HIP_TRY (hipFree (p->scratch.d_spill));
+  p->scratch.d_holes = p->scratch.d_spill = nullptr;
+  if (hipMalloc (&p->scratch.d_holes, (size_t)regions * 2 * sizeof (RecHole)) != hipSuccess || /* (the 4-gram pass's and the short-keyword pass's) */
+      hipMalloc (&p->scratch.d_spill, (size_t)regions * rec_chunk * 16) != hipSuccess) /* (one chunk per wave: 64 MB, 256 MB with big chunks) */
+    return ACM_GPU_E_NOMEM;
+  p->scratch.direct_regions = regions;
+  p->scratch.spill_chunk = rec_chunk;
   return ACM_GPU_OK;
 }
 
 /* expand_items_once_kernel: 1024 threads per 16 regions (one block per CU on config 2), the items
  * of 4 rounds in registers, one atomic per block (measured against one atomic per round of 1,024
  * items, smaller blocks and fewer rounds: DESIGN.md 4.2) */
-/* hole descriptors and spill area of a plan whose scan kernel writes the records itself */
-int
-ensure_direct_buffers (ACMPlan *p, uint32_t rec_chunk) {
-  const uint32_t regions = (uint32_t)p->cu_count * (SPARSE_THREADS / WAVE);
-  if (p->d_holes && p->d_spill && p->direct_regions >= regions && p->spill_chunk >= rec_chunk)
-    return ACM_GPU_OK;
-  if (p->d_holes || p->d_spill)
-    HIP_TRY (hipDeviceSynchronize ());
-  if (p->d_holes)
-    HIP_TRY (hipFree (p->d_holes));
-  if (p->d_spill)
-    HIP_TRY (hipFree (p->d_spill));
-  p->d_holes = p->d_spill = nullptr;
-  if (hipMalloc (&p->d_holes, (size_t)regions * 2 * sizeof (RecHole)) != hipSuccess || /* (the 4-gram pass's and the short-keyword pass's) */
-      hipMalloc (&p->d_spill, (size_t)regions * rec_chunk * 16) != hipSuccess) /* (one chunk per wave: 64 MB, 256 MB with big chunks) */
-    return ACM_GPU_E_NOMEM;
-  p->direct_regions = regions;
-  p->spill_chunk = rec_chunk;
-  return ACM_GPU_OK;
-}
-
 template <bool CONT, bool COUNT_ONLY>
 void
 launch_expand_cfg (ACMPlan *p, const EmitCtx &E, uint32_t regions_used, const ExpandTail &tail, hipStream_t st) {
   const dim3 g ((regions_used + 15) / 16);
+  const ItemBuffer &I = p->items ();
   hipLaunchKernelGGL ((expand_items_once_kernel<CONT, COUNT_ONLY, 1024, 16, 4>), g, dim3 (1024), 0, st, E,
-                      static_cast<const uint2 *> (p->d_items), p->region_items, p->d_fill, tail);
+                      static_cast<const uint2 *> (I.items), I.region_items, I.fill, tail);
 }
 
 /* scan kernel, then the expansion of what it parked; the caller's counter is written by the
@@ -1950,15 +1948,15 @@ launch_dense (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t
     grid = blocks_needed;
   static_assert (DENSE_THREADS == SPARSE_THREADS, "set_tile_pool counts blocks of SPARSE_THREADS");
   set_tile_pool (p, a, grid * wpb);
+  ItemBuffer &I = p->items ();
   void *args[] = { &p->K, const_cast<EmitCtx *> (&E), &a, &p->d_dense, &p->d_lds_image, &p->lds_image_bytes, &a.text,
-                   &p->d_items, &p->region_items, &p->d_fill, &p->d_dstart };
-  HIP_TRY (hipLaunchKernel (dense_kernel_ptr (p->entry_bytes, p->chunk, p->streams, COUNT_ONLY), dim3 (grid), dim3 (DENSE_THREADS), args,
-                            p->info.lds_bytes, st));
+                   &I.items, &I.region_items, &I.fill, &p->d_dstart };
+  HIP_TRY (hipLaunchKernel (dense_kernel (p, COUNT_ONLY), dim3 (grid), dim3 (DENSE_THREADS), args, p->info.lds_bytes, st));
   if (stop)
     HIP_TRY (hipEventRecord (stop, st));
   ExpandTail tail;
   tail.user_count = reinterpret_cast<unsigned long long *> (d_count);
-  tail.ticket = reinterpret_cast<unsigned int *> (p->d_total + 1);
+  tail.ticket = reinterpret_cast<unsigned int *> (p->scratch.d_total + 1);
   tail.last_segment = last_segment ? 1 : 0;
   if (p->entry_bytes == 2)
     launch_expand_cfg<true, COUNT_ONLY> (p, E, grid * wpb, tail, st);
@@ -2185,17 +2183,17 @@ mirror_insert (StartsMirror &M, const uint32_t *symbols, uint32_t len, uint32_t 
 /* maps n symbols of d_text to class ids into the plan's own buffer (grown as needed) */
 int
 ensure_remap_buffer (ACMPlan *p, size_t bytes, hipStream_t st) {
-  if (p->remap_bytes < bytes + 16) {
-    if (p->d_remap) {
+  if (p->scratch.remap_bytes < bytes + 16) {
+    if (p->scratch.d_remap) {
       HIP_TRY (hipStreamSynchronize (st)); /* an earlier scan may still read the old buffer */
-      HIP_TRY (hipFree (p->d_remap));
-      p->d_remap = nullptr;
-      p->remap_bytes = 0;
+      HIP_TRY (hipFree (p->scratch.d_remap));
+      p->scratch.d_remap = nullptr;
+      p->scratch.remap_bytes = 0;
     }
     const size_t want = bytes + bytes / 8 + 4096;
-    if (hipMalloc (&p->d_remap, want) != hipSuccess)
+    if (hipMalloc (&p->scratch.d_remap, want) != hipSuccess)
       return ACM_GPU_E_NOMEM;
-    p->remap_bytes = want;
+    p->scratch.remap_bytes = want;
   }
   return ACM_GPU_OK;
 }
@@ -2213,7 +2211,7 @@ classmap_text (ACMPlan *p, const void *d_text, uint64_t n, hipStream_t st) {
     const uint64_t want_blocks = (blocks16 + 1023) / 1024;
     const uint32_t grid = (uint32_t)(want_blocks < (uint64_t)p->cu_count ? want_blocks : (uint64_t)p->cu_count);
     hipLaunchKernelGGL (classmap_kernel, dim3 (grid), dim3 (1024), 65536 * 2, st, static_cast<const uint4 *> (d_text),
-                        static_cast<uint4 *> (p->d_remap), blocks16, p->d_classlut);
+                        static_cast<uint4 *> (p->scratch.d_remap), blocks16, p->d_classlut);
   }
   const uint64_t done = blocks16 * 16 / sb;
   if (done < n) {
@@ -2221,10 +2219,10 @@ classmap_text (ACMPlan *p, const void *d_text, uint64_t n, hipStream_t st) {
     const uint32_t grid = (uint32_t)((left + 255) / 256 < 4096 ? (left + 255) / 256 : 4096);
     if (sb == 1)
       hipLaunchKernelGGL ((classmap_tail_kernel<uint8_t>), dim3 (grid), dim3 (256), 0, st, static_cast<const uint8_t *> (d_text),
-                          static_cast<uint8_t *> (p->d_remap), done, n, p->d_classlut);
+                          static_cast<uint8_t *> (p->scratch.d_remap), done, n, p->d_classlut);
     else
       hipLaunchKernelGGL ((classmap_tail_kernel<uint16_t>), dim3 (grid), dim3 (256), 0, st, static_cast<const uint16_t *> (d_text),
-                          static_cast<uint16_t *> (p->d_remap), done, n, p->d_classlut);
+                          static_cast<uint16_t *> (p->scratch.d_remap), done, n, p->d_classlut);
   }
   HIP_TRY (hipGetLastError ());
   return ACM_GPU_OK;
@@ -2306,7 +2304,7 @@ classify_text32 (ACMPlan *p, const void *d_text, uint64_t n, hipStream_t st) {
   for (uint32_t round = 0; round < ACMPlan::CLS32_KNOWN_MAX / ACMPlan::CLS32_CAP_MIN + 64; round++) {
     HIP_TRY (hipMemsetAsync (p->d_unknown, 0, 4, st));
     hipLaunchKernelGGL (classify32_kernel, dim3 (grid), dim3 (256), 0, st, static_cast<const uint32_t *> (d_text),
-                        static_cast<uint32_t *> (p->d_remap), n, p->d_cls32, p->cls32_slots - 1, p->d_unknown + 1, p->d_unknown,
+                        static_cast<uint32_t *> (p->scratch.d_remap), n, p->d_cls32, p->cls32_slots - 1, p->d_unknown + 1, p->d_unknown,
                         p->cls32_cap);
     HIP_TRY (hipGetLastError ());
     uint32_t cnt = 0;
@@ -2341,10 +2339,117 @@ classify_text32 (ACMPlan *p, const void *d_text, uint64_t n, hipStream_t st) {
   return ACM_GPU_E_INTERNAL;
 }
 
+/* The text the kernels walk: the caller's, or the plan's own copy of it in scratch.d_remap (*text is
+ * redirected): interned ids, class ids, an aligned copy. */
+int
+prepare_text (ACMPlan *p, const void **text, uint64_t n, hipStream_t st) {
+  const void *d_text = *text;
+  const uint32_t sb = p->finfo.sym_bytes;
+  if (p->d_intern) {
+    /* 8-byte symbols: the kernels walk the 4-byte ids of the text */
+    if (reinterpret_cast<uintptr_t> (d_text) & 7)
+      return ACM_GPU_E_ARG;
+    int rc = ensure_remap_buffer (p, (size_t)n * 4, st);
+    if (rc)
+      return rc;
+    const uint64_t want_blocks = (n + 255) / 256;
+    const uint32_t grid = (uint32_t)(want_blocks < (uint64_t)p->cu_count * 32 ? want_blocks : (uint64_t)p->cu_count * 32);
+    hipLaunchKernelGGL (intern_kernel, dim3 (grid), dim3 (256), 0, st, static_cast<const uint64_t *> (d_text),
+                        static_cast<uint32_t *> (p->scratch.d_remap), n, p->d_intern, p->intern_mask);
+    HIP_TRY (hipGetLastError ());
+    *text = p->scratch.d_remap;
+  } else if (p->cls32) {
+    int rc = classify_text32 (p, d_text, n, st);
+    if (rc)
+      return rc;
+    *text = p->scratch.d_remap;
+  } else if (p->d_classlut) {
+    /* comparator-class plan: walk the class ids of the text (our own, aligned, copy) */
+    int rc = classmap_text (p, d_text, n, st);
+    if (rc)
+      return rc;
+    *text = p->scratch.d_remap;
+  } else if ((p->kind == PlanKind::Starts || p->kind == PlanKind::Gram) && (reinterpret_cast<uintptr_t> (d_text) & 15) != 0) {
+    /* start-parallel / 4-gram plan, buffer not 16-byte aligned: scan an aligned copy (the CSR walk that
+     * would take it as it is runs 20x slower, and knows nothing of incremental updates) */
+    int rc = ensure_remap_buffer (p, (size_t)n * sb, st);
+    if (rc)
+      return rc;
+    HIP_TRY (hipMemcpyAsync (p->scratch.d_remap, d_text, (size_t)n * sb, hipMemcpyDeviceToDevice, st));
+    *text = p->scratch.d_remap;
+  }
+  return ACM_GPU_OK;
+}
+
+/* every segment of a scan restarts from the root `halo` symbols early: the longest keyword less
+ * one, rounded up to a multiple of 16 bytes so that the kernels keep their alignment */
+uint64_t
+scan_halo (uint32_t lmax) {
+  return lmax > 1 ? (((uint64_t)lmax - 1 + 15) / 16) * 16 : 0;
+}
+
+/* One launch's share of a scan of n symbols that reports from emit_from on: the symbols
+ * [read_begin, read_begin + n) of the text, matches that end at emit_from (relative to read_begin)
+ * or later.  Segments are at most ACMPlan::segment symbols plus the halo in front. */
+struct Segment {
+  uint64_t read_begin;
+  uint32_t n, emit_from;
+  bool first, last;
+};
+
+/* f (const Segment &) for every segment of the scan, until one fails */
+template <typename F>
+int
+for_each_segment (const ACMPlan *p, uint64_t n, uint64_t emit_from, uint64_t halo, F f) {
+  const uint64_t SEG = p->segment;
+  const uint64_t first_seg = emit_from / SEG * SEG; /* earlier segments have nothing to report */
+  for (uint64_t seg = first_seg; seg < n; seg += SEG) {
+    const uint64_t seg_end = seg + SEG < n ? seg + SEG : n;
+    const uint64_t read_begin = seg > halo ? seg - halo : 0;
+    const uint64_t ef = emit_from > seg ? emit_from : seg;
+    const Segment S = { read_begin, (uint32_t)(seg_end - read_begin), (uint32_t)(ef - read_begin), seg == first_seg, seg_end == n };
+    const int rc = f (S);
+    if (rc)
+      return rc;
+  }
+  return ACM_GPU_OK;
+}
+
+/* what the launches of one scan have in common; the segment (text, n, emit_from, pos_base) is set
+ * per launch.  spill: records past `capacity` go to the plan's spill area (scans whose kernel writes
+ * the records itself); chunk_prev: the chunk links of a tiled scan. */
+EmitCtx
+make_emit_ctx (const ACMPlan *p, ACMRecord *records, uint64_t capacity, unsigned long long *count, uint32_t rec_chunk, bool spill,
+               uint32_t *chunk_prev) {
+  EmitCtx E{};
+  E.oinfo = p->d_oinfo;
+  E.records = records;
+  E.count = count;
+  E.capacity = capacity;
+  E.wrows = p->d_wrows;
+  E.cont_dh = p->d_cont_dh;
+  E.W = p->K.W;
+  E.lo = p->K.lo;
+  E.span = p->K.span;
+  E.chunk = p->chunk;
+  E.n_states = p->finfo.n_states;
+  E.kw4 = p->d_kw4;
+  E.chain = p->d_chain;
+  E.chain_base = p->K.HD;
+  E.spill = static_cast<uint4 *> (p->scratch.d_spill);
+  E.spill_slots = spill ? (uint64_t)p->scratch.direct_regions * rec_chunk : 0;
+  E.rec_chunk = rec_chunk;
+  E.chunk_prev = chunk_prev;
+  E.error = p->scratch.d_total ? reinterpret_cast<unsigned int *> (p->scratch.d_total) + 3 : nullptr;
+  return E;
+}
+
+/* tiled_scan: the scan is one of scan_tiled's (a Gram plan over a narrow alphabet, with records) */
 template <bool COUNT_ONLY>
 int
 scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint64_t pos_base, ACMRecord *d_records,
-           uint64_t capacity, uint64_t *d_count, hipStream_t st, bool accumulate = false, unsigned long long *shared_total = nullptr) {
+           uint64_t capacity, uint64_t *d_count, hipStream_t st, bool accumulate = false, unsigned long long *shared_total = nullptr,
+           TiledScan *tiled_scan = nullptr) {
   /* shared_total (with accumulate): the running total of ANOTHER plan to add to -- a delta plan
    * appends its records to those of the plan it belongs to */
   /* accumulate (streaming): records are appended after those of earlier calls -- the plan's
@@ -2362,96 +2467,49 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
     if (rc)
       return rc;
   }
-  if (p->d_intern) {
-    /* 8-byte symbols: the kernels walk the 4-byte ids of the text */
-    if (reinterpret_cast<uintptr_t> (d_text) & 7)
-      return ACM_GPU_E_ARG;
-    int rc = ensure_remap_buffer (p, (size_t)n * 4, st);
-    if (rc)
-      return rc;
-    const uint64_t want_blocks = (n + 255) / 256;
-    const uint32_t grid = (uint32_t)(want_blocks < (uint64_t)p->cu_count * 32 ? want_blocks : (uint64_t)p->cu_count * 32);
-    hipLaunchKernelGGL (intern_kernel, dim3 (grid), dim3 (256), 0, st, static_cast<const uint64_t *> (d_text),
-                        static_cast<uint32_t *> (p->d_remap), n, p->d_intern, p->intern_mask);
-    HIP_TRY (hipGetLastError ());
-    d_text = p->d_remap;
-  } else if (p->cls32) {
-    int rc = classify_text32 (p, d_text, n, st);
-    if (rc)
-      return rc;
-    d_text = p->d_remap;
-  } else if (p->d_classlut) {
-    /* comparator-class plan: walk the class ids of the text (our own, aligned, copy) */
-    int rc = classmap_text (p, d_text, n, st);
-    if (rc)
-      return rc;
-    d_text = p->d_remap;
-  } else if ((p->kind == PlanKind::Starts || p->kind == PlanKind::Gram) && (reinterpret_cast<uintptr_t> (d_text) & 15) != 0) {
-    /* start-parallel / 4-gram plan, buffer not 16-byte aligned: scan an aligned copy (the CSR walk that
-     * would take it as it is runs 20x slower, and knows nothing of incremental updates) */
-    int rc = ensure_remap_buffer (p, (size_t)n * sb, st);
-    if (rc)
-      return rc;
-    HIP_TRY (hipMemcpyAsync (p->d_remap, d_text, (size_t)n * sb, hipMemcpyDeviceToDevice, st));
-    d_text = p->d_remap;
-  }
+  int rc = prepare_text (p, &d_text, n, st);
+  if (rc)
+    return rc;
+
+  /* what kind of scan this is */
   const bool gram = p->kind == PlanKind::Gram;
   const bool direct = gram && !p->hashed; /* records straight from the scan kernel: no item buffer */
-  if (use_dense || (!COUNT_ONLY && !direct && (gram || p->kind == PlanKind::Starts))) {
-    /* 4-gram plans over hashed windows see dense matches: room for one hit per 16 symbols, per 8
-     * when the dictionary has keywords of 1-3 symbols; past that a wave reserves records 64 at a time */
-    int rc = ensure_item_buffer (p, n < p->segment ? n : p->segment, gram ? (p->inline_shorts ? 8 : 16) : 256,
-                                 use_dense ? DENSE_MIN_REGION_ITEMS : 256);
-    if (rc)
-      return rc;
-  }
-  const bool tiled = !COUNT_ONLY && direct && p->tiled_dir != nullptr;
+  const bool tiled = !COUNT_ONLY && direct && tiled_scan != nullptr;
   /* slots per chunk of records (EmitCtx::rec_chunk): big chunks for long texts, when no directory
    * of tiles counts in chunks (ACM_GPU_REC_CHUNK=1024 / 4096: one or the other anyway -- tests) */
   uint32_t rec_chunk = (!tiled && n >= (64ull << 20)) ? REC_CHUNK_BIG : REC_CHUNK;
   if (const char *e = getenv ("ACM_GPU_REC_CHUNK"))
     if (!tiled && (atoi (e) == (int)REC_CHUNK || atoi (e) == (int)REC_CHUNK_BIG))
       rec_chunk = (uint32_t)atoi (e);
-  if (!COUNT_ONLY && direct) {
-    int rc = ensure_direct_buffers (p, rec_chunk);
+
+  if (use_dense || (!COUNT_ONLY && !direct && (gram || p->kind == PlanKind::Starts))) {
+    /* 4-gram plans over hashed windows see dense matches: room for one hit per 16 symbols, per 8
+     * when the dictionary has keywords of 1-3 symbols; past that a wave reserves records 64 at a time */
+    rc = ensure_item_buffer (p, n < p->segment ? n : p->segment, gram ? (p->inline_shorts ? 8 : 16) : 256,
+                             use_dense ? DENSE_MIN_REGION_ITEMS : 256);
     if (rc)
       return rc;
   }
-  EmitCtx E{};
-  E.oinfo = p->d_oinfo;
-  E.records = d_records;
-  E.count = shared_total ? shared_total : ((use_dense || accumulate || tiled) ? p->d_total : reinterpret_cast<unsigned long long *> (d_count));
-  E.capacity = COUNT_ONLY ? 0 : capacity;
-  E.wrows = p->d_wrows;
-  E.cont_dh = p->d_cont_dh;
-  E.W = p->K.W;
-  E.lo = p->K.lo;
-  E.span = p->K.span;
-  E.chunk = p->chunk;
-  E.n_states = p->finfo.n_states;
-  E.kw4 = p->d_kw4;
-  E.chain = p->d_chain;
-  E.chain_base = p->K.HD;
-  E.spill = static_cast<uint4 *> (p->d_spill);
-  E.spill_slots = (!COUNT_ONLY && direct && !tiled) ? (uint64_t)p->direct_regions * rec_chunk : 0;
-  E.rec_chunk = rec_chunk;
-  E.chunk_prev = tiled ? p->tiled_prev : nullptr;
-  E.error = p->d_total ? reinterpret_cast<unsigned int *> (p->d_total) + 3 : nullptr;
+  if (!COUNT_ONLY && direct) {
+    rc = ensure_direct_buffers (p, rec_chunk);
+    if (rc)
+      return rc;
+  }
 
-  /* segments of at most SEGMENT symbols; each restarts from the root `halo` symbols early (a
-   * multiple of 16 bytes so that the kernels keep their alignment); `launch` makes the launches of one */
-  const uint64_t SEG = p->segment;
-  const uint64_t first_seg = emit_from / SEG * SEG; /* earlier segments have nothing to report */
-  auto each_segment = [&] (uint64_t halo, auto launch) -> int {
-    for (uint64_t seg = first_seg; seg < n; seg += SEG) {
-      const uint64_t seg_end = seg + SEG < n ? seg + SEG : n;
-      const uint64_t read_begin = seg > halo ? seg - halo : 0;
+  unsigned long long *const count =
+    shared_total ? shared_total : ((use_dense || accumulate || tiled) ? p->scratch.d_total : reinterpret_cast<unsigned long long *> (d_count));
+  EmitCtx E = make_emit_ctx (p, d_records, COUNT_ONLY ? 0 : capacity, count, rec_chunk, !COUNT_ONLY && direct && !tiled,
+                             tiled ? tiled_scan->chunk_prev : nullptr);
+  uint32_t holes_waves[2] = { 0, 0 }; /* widest launch so far of the 4-gram pass, of the short-keyword pass */
+
+  /* one pass over the segments of the text; `launch` makes the launches of one */
+  auto pass = [&] (uint64_t halo, auto launch) -> int {
+    return for_each_segment (p, n, emit_from, halo, [&] (const Segment &S) -> int {
       Launch a{};
-      a.text = static_cast<const unsigned char *> (d_text) + read_begin * sb;
-      a.n = (uint32_t)(seg_end - read_begin);
-      const uint64_t ef = emit_from > seg ? emit_from : seg;
-      a.emit_from = (uint32_t)(ef - read_begin);
-      E.pos_base = pos_base + read_begin;
+      a.text = static_cast<const unsigned char *> (d_text) + S.read_begin * sb;
+      a.n = S.n;
+      a.emit_from = S.emit_from;
+      E.pos_base = pos_base + S.read_begin;
       E.text = a.text;
       E.n = a.n;
       E.emit_from = a.emit_from;
@@ -2459,15 +2517,12 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
       int rc = timing_begin (p, st, &stop, &stop_all);
       if (rc)
         return rc;
-      rc = launch (a, stop, seg == first_seg, seg_end == n);
+      rc = launch (a, stop, S.first, S.last);
       if (!rc && stop_all) /* behind the expansion / hole closing the launch functions enqueue after their scan kernel */
         HIP_TRY (hipEventRecord (stop_all, st));
-      if (rc)
-        return rc;
-    }
-    return ACM_GPU_OK;
+      return rc;
+    });
   };
-  const uint64_t halo = p->finfo.lmax > 1 ? (((uint64_t)p->finfo.lmax - 1 + 15) / 16) * 16 : 0;
   auto main_pass = [&] (Launch &a, hipEvent_t stop, bool first_segment, bool last_segment) -> int {
     int rc = ACM_GPU_OK;
     const bool aligned = (reinterpret_cast<uintptr_t> (a.text) & 15) == 0;
@@ -2477,7 +2532,7 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
       a.range_begin = 0;
       a.range_end = a.n;
       if (gram)
-        rc = launch_gram<COUNT_ONLY> (p, E, a, st, stop, first_segment, last_segment);
+        rc = launch_gram<COUNT_ONLY> (p, E, a, st, stop, first_segment, last_segment, holes_waves[0], tiled ? tiled_scan : nullptr);
       else if (p->kind == PlanKind::Starts && aligned)
         rc = launch_starts<COUNT_ONLY> (p, E, a, st, stop);
       else {
@@ -2491,17 +2546,17 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
       }
     }
     /* earlier segments may have left a partial running total and expand ticket behind */
-    if (rc && use_dense && p->d_total)
-      (void)hipMemsetAsync (p->d_total, 0, 16, st);
+    if (rc && use_dense && p->scratch.d_total)
+      (void)hipMemsetAsync (p->scratch.d_total, 0, 16, st);
     return rc;
   };
-  int rc = each_segment (halo, main_pass);
+  rc = pass (scan_halo (p->finfo.lmax), main_pass);
   /* narrow alphabets: the keywords of 1-3 symbols, a pass of their own over the same segments
    * (dev_short.h); their records follow the 4-gram pass' in the same buffer.  (A halo of 2 symbols
    * would do: 16 keeps the alignment.) */
   if (!rc && gram && p->short_pass)
-    rc = each_segment (16, [&] (Launch &a, hipEvent_t stop, bool first_segment, bool last_segment) {
-      return launch_short<COUNT_ONLY> (p, E, a, st, stop, first_segment, last_segment);
+    rc = pass (16, [&] (Launch &a, hipEvent_t stop, bool first_segment, bool last_segment) {
+      return launch_short<COUNT_ONLY> (p, E, a, st, stop, first_segment, last_segment, holes_waves[1]);
     });
   return rc;
 }
@@ -2525,10 +2580,10 @@ scan_plan (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
     return scan_impl<COUNT_ONLY> (p, d_text, n, emit_from, pos_base, d_records, capacity, d_count, st, accumulate);
   int rc = scan_impl<COUNT_ONLY> (p, d_text, n, emit_from, pos_base, d_records, capacity, d_count, st, true);
   if (!rc)
-    rc = scan_impl<COUNT_ONLY> (p->delta, d_text, n, emit_from, pos_base, d_records, capacity, d_count, st, true, p->d_total);
+    rc = scan_impl<COUNT_ONLY> (p->delta, d_text, n, emit_from, pos_base, d_records, capacity, d_count, st, true, p->scratch.d_total);
   p->delta_scanned += n; /* what acm_gpu_plan_update weighs against the cost of one plan of everything */
   if (!accumulate) { /* (also after a failure: the total must not leak into the next scan) */
-    hipLaunchKernelGGL (finish_count_kernel, dim3 (1), dim3 (64), 0, st, p->d_total, reinterpret_cast<unsigned long long *> (d_count));
+    hipLaunchKernelGGL (finish_count_kernel, dim3 (1), dim3 (64), 0, st, p->scratch.d_total, reinterpret_cast<unsigned long long *> (d_count));
     HIP_TRY (hipGetLastError ());
   }
   return rc;
@@ -2572,7 +2627,6 @@ struct ACMStream {
   uint64_t pieces = 0;
   uint64_t prev_valid = 0; /* context + piece symbols held, contiguously, by the previous slot */
   uint64_t last_piece = 0; /* length of the previous piece */
-  uint64_t prev_piece_len () const { return last_piece; }
 };
 
 extern "C" int
@@ -2585,7 +2639,7 @@ acm_gpu_stream_open (ACMPlan *plan, uint64_t max_piece_symbols, uint64_t record_
     return ACM_GPU_E_NOMEM;
   s->plan = plan;
   s->sb = plan->text_sym_bytes; /* of the caller's text (8-byte symbols are interned inside the scan) */
-  s->halo = plan->finfo.lmax > 1 ? (((uint64_t)plan->finfo.lmax - 1 + 15) / 16) * 16 : 0;
+  s->halo = scan_halo (plan->finfo.lmax);
   s->max_piece = (max_piece_symbols + 15) / 16 * 16;
   s->capacity = record_capacity;
   const size_t slot_bytes = (size_t)(s->halo + s->max_piece) * s->sb + 16;
@@ -2602,7 +2656,7 @@ acm_gpu_stream_open (ACMPlan *plan, uint64_t max_piece_symbols, uint64_t record_
    * the plan (on whatever stream) must have drained, and the memset (null stream) must have landed
    * before the stream's own non-blocking streams touch the total: without the waits a warm
    * process lost the first piece's count now and then */
-  ok = ok && hipDeviceSynchronize () == hipSuccess && hipMemset (plan->d_total, 0, 8) == hipSuccess &&
+  ok = ok && hipDeviceSynchronize () == hipSuccess && hipMemset (plan->scratch.d_total, 0, 8) == hipSuccess &&
        hipDeviceSynchronize () == hipSuccess;
   if (!ok) {
     acm_gpu_stream_close (s);
@@ -2642,7 +2696,7 @@ acm_gpu_stream_feed (ACMStream *s, const void *text, uint64_t n_symbols) {
     const uint64_t ctx = s->prev_valid < s->halo ? s->prev_valid : s->halo;
     HIP_TRY (hipStreamWaitEvent (s->compute, s->copied[cur], 0));
     if (ctx) {
-      const unsigned char *tail = s->slot[prev] + (s->halo + s->prev_piece_len () - ctx) * s->sb;
+      const unsigned char *tail = s->slot[prev] + (s->halo + s->last_piece - ctx) * s->sb;
       HIP_TRY (hipMemcpyAsync (piece_at - ctx * s->sb, tail, (size_t)ctx * s->sb, hipMemcpyDeviceToDevice, s->compute));
     }
     HIP_TRY (hipEventRecord (s->tail_read[prev], s->compute));
@@ -2673,7 +2727,7 @@ acm_gpu_stream_finish (ACMStream *s, ACMRecord *records, uint64_t capacity, uint
   HIP_TRY (hipStreamSynchronize (s->copy));
   HIP_TRY (hipStreamSynchronize (s->compute));
   unsigned long long total = 0;
-  HIP_TRY (hipMemcpy (&total, p->d_total, 8, hipMemcpyDeviceToHost));
+  HIP_TRY (hipMemcpy (&total, p->scratch.d_total, 8, hipMemcpyDeviceToHost));
   *n_found = total;
   if (total > s->capacity || total > capacity)
     return ACM_GPU_E_OVERFLOW;
@@ -2703,7 +2757,7 @@ acm_gpu_stream_close (ACMStream *s) {
     (void)hipStreamSynchronize (s->copy);
   if (s->compute)
     (void)hipStreamSynchronize (s->compute);
-  (void)hipMemset (s->plan->d_total, 0, 8); /* hand the plan back with a clean running total */
+  (void)hipMemset (s->plan->scratch.d_total, 0, 8); /* hand the plan back with a clean running total */
   (void)hipDeviceSynchronize ();
   for (int i = 0; i < 2; i++) {
     if (s->slot[i]) (void)hipFree (s->slot[i]);
@@ -2878,7 +2932,7 @@ order_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, const unsigned l
   K.wlog = L.wlog;
   K.n_buckets = L.n_buckets;
   K.len_bits = L.len_bits;
-  K.error = plan->d_total ? reinterpret_cast<unsigned int *> (plan->d_total) + 3 : nullptr;
+  K.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
   K.n_dev = n_dev;
   K.span = span;
   K.mode = n_dev ? 2u : (L.sparse ? 1u : 0u);
@@ -2932,7 +2986,7 @@ struct TiledPlan {
   size_t o_raw = 0, o_prev = 0, o_dir = 0, o_size = 0, o_begin = 0, o_crowded = 0, o_over = 0, o_cub = 0, cub_bytes = 0, total = 0;
 };
 
-/* the tiles of all the launches scan_impl makes for this text (the same walk over the segments).
+/* the tiles of all the launches scan_impl makes for this text.
  * bound: an upper bound of the layout over every emit_from (acm_gpu_scan_ordered_tmp_bytes): the
  * tiles are counted at the smallest R gram_tiling ever picks.  (Round 3 sized the scratch with
  * emit_from = 0 "for the most tiles" -- but R = clamp (groups behind emit_from / (16 per wave), 4,
@@ -2948,23 +3002,19 @@ tiled_layout (const ACMPlan *p, uint64_t capacity, uint64_t n, uint64_t emit_fro
     return L; /* (a second pass' records do not lie tile by tile: the general order passes) */
   if (n == 0 || emit_from >= n || capacity == 0 || capacity >= (1ull << 31))
     return L;
-  const uint64_t halo = p->finfo.lmax > 1 ? (((uint64_t)p->finfo.lmax - 1 + 15) / 16) * 16 : 0;
-  const uint64_t SEG = p->segment;
   uint64_t tiles = 0;
-  for (uint64_t seg = emit_from / SEG * SEG; seg < n; seg += SEG) {
-    const uint64_t seg_end = seg + SEG < n ? seg + SEG : n;
-    const uint64_t read_begin = seg > halo ? seg - halo : 0;
-    const uint64_t ef = emit_from > seg ? emit_from : seg;
-    GramTiling T = gram_tiling (p, (uint32_t)(seg_end - read_begin), (uint32_t)(ef - read_begin));
+  (void)for_each_segment (p, n, emit_from, scan_halo (p->finfo.lmax), [&] (const Segment &S) {
+    TileGeometry T = gram_tiling (p, S.n, S.emit_from);
     if (bound) { /* every group of the segment, GRAM_R_MIN groups per tile */
-      const uint32_t ngroups = (uint32_t)((seg_end - read_begin + WAVE * 16 - 1) / (WAVE * 16));
+      const uint32_t ngroups = (uint32_t)(((uint64_t)S.n + WAVE * 16 - 1) / (WAVE * 16));
       T.begin = 0;
       T.end = (ngroups + GRAM_R_MIN - 1) / GRAM_R_MIN;
     }
     tiles += T.end - T.begin;
     if (T.R * (WAVE * 16) / (1u << TILE_BUCKET_LOG2) + 1 > L.nsub)
       L.nsub = T.R * (WAVE * 16) / (1u << TILE_BUCKET_LOG2) + 1;
-  }
+    return ACM_GPU_OK;
+  });
   if (tiles == 0 || tiles >= (1ull << 30))
     return L;
   L.n_tiles = (uint32_t)tiles;
@@ -2994,16 +3044,11 @@ scan_tiled (ACMPlan *plan, const TiledPlan &L, const void *d_text, uint64_t n_sy
             uint64_t capacity, uint64_t *d_count, void *d_tmp, hipStream_t st) {
   HIP_TRY (hipSetDevice (plan->device));
   unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  plan->tiled_dir = t + L.o_dir;
-  plan->tiled_prev = reinterpret_cast<uint32_t *> (t + L.o_prev);
-  plan->tiled_base = 0;
-  int rc = scan_impl<false> (plan, d_text, n_symbols, emit_from, pos_base, reinterpret_cast<ACMRecord *> (t + L.o_raw), L.raw_slots, d_count, st);
-  const uint32_t written = plan->tiled_base;
-  plan->tiled_dir = nullptr;
-  plan->tiled_prev = nullptr;
-  plan->tiled_base = 0;
-  if (rc || written != L.n_tiles) {
-    (void)hipMemsetAsync (plan->d_total, 0, 8, st); /* (the scan's running total must not leak into the next one) */
+  TiledScan tiled = { reinterpret_cast<TileEntry *> (t + L.o_dir), reinterpret_cast<uint32_t *> (t + L.o_prev), 0 };
+  int rc = scan_impl<false> (plan, d_text, n_symbols, emit_from, pos_base, reinterpret_cast<ACMRecord *> (t + L.o_raw), L.raw_slots, d_count, st,
+                             false, nullptr, &tiled);
+  if (rc || tiled.base != L.n_tiles) { /* (the directory was sized by tiled_layout, filled by launch_gram) */
+    (void)hipMemsetAsync (plan->scratch.d_total, 0, 8, st); /* (the scan's running total must not leak into the next one) */
     return rc ? rc : ACM_GPU_E_INTERNAL;
   }
   TileK K{};
@@ -3016,14 +3061,14 @@ scan_tiled (ACMPlan *plan, const TiledPlan &L, const void *d_text, uint64_t n_sy
   K.out = d_records;
   K.capacity = capacity;
   K.d_count = reinterpret_cast<unsigned long long *> (d_count);
-  K.reserved = plan->d_total;
+  K.reserved = plan->scratch.d_total;
   K.len_bits = L.len_bits;
   K.nsub = L.nsub;
   K.crowded = reinterpret_cast<uint32_t *> (t + L.o_crowded);
   K.raw_slots = L.raw_slots;
   K.over_total = reinterpret_cast<unsigned long long *> (t + L.o_over);
   HIP_TRY (hipMemsetAsync (K.over_total, 0, 8, st));
-  K.error = reinterpret_cast<unsigned int *> (plan->d_total) + 3;
+  K.error = reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3;
   const uint32_t sblocks = (L.n_tiles + 1 + 3) / 4;
   hipLaunchKernelGGL (tile_size_kernel, dim3 (sblocks < (uint32_t)plan->cu_count * 16 ? sblocks : (uint32_t)plan->cu_count * 16), dim3 (256), 0, st, K);
   HIP_TRY (hipGetLastError ());
@@ -3697,7 +3742,7 @@ acm_gpu_plan_update (ACMPlan *plan, ACMachine *machine) {
     fresh->cmp32 = plan->cmp32;
     fresh->cmp32_arg = plan->cmp32_arg;
     fresh->segment = plan->segment;
-    fresh->items_owner = plan;
+    fresh->shared_items = &plan->items ();
     if (plan->delta)
       plan->retired.push_back (ACMPlan::Retired{ plan->delta, nullptr });
     plan->delta = fresh;
