@@ -83,6 +83,7 @@ EXPORTS = [
     "acm_gpu_multi_scan_device", "acm_set_symbol_bytes", "acm_scan_path", "acm_gpu_wire_bits", "acm_gpu_pack_records_device",
     "acm_gpu_unpack_records_device", "acm_gpu_comm_unique_id", "acm_gpu_comm_init_rank", "acm_gpu_comm_free", "acm_gpu_comm_create",
     "acm_gpu_comm_destroy", "acm_gpu_comm_gather_records",
+    "acm_gpu_scan_batch_tmp_bytes", "acm_gpu_scan_batch_device", "acm_gpu_scan_batch_host", "acm_scan_batch",
 ]
 
 
@@ -230,6 +231,14 @@ def lib():
     L.acm_gpu_comm_gather_records.argtypes = [vp, vp, vp, u64, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(u64), vp]
     L.acm_gpu_plan_timing_read_all.restype = i32
     L.acm_gpu_plan_timing_read_all.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]
+    L.acm_gpu_scan_batch_tmp_bytes.restype = sz
+    L.acm_gpu_scan_batch_tmp_bytes.argtypes = [vp, u64, u64, u64]
+    L.acm_gpu_scan_batch_device.restype = i32
+    L.acm_gpu_scan_batch_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_batch_host.restype = i32
+    L.acm_gpu_scan_batch_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_scan_batch.restype = i32
+    L.acm_scan_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
     L.acm_gpu_synth_text.restype = i32
     L.acm_gpu_synth_text.argtypes = [i32, vp, u64, u64, u32, u32, vp, vp, u32, vp]
     _lib = L
@@ -492,6 +501,38 @@ class Machine:
             _check(rc, "acm_scan")
             return out[:n.value]
 
+    def scan_batch(self, texts, capacity=None):
+        """acm_scan_batch(): a list of texts (bytes or arrays of symbols), each scanned from the root
+        on its own in ONE call.  Returns a list with one record array per text, end_pos relative to
+        the text's own first symbol -- what scan_host() gives for each of them alone."""
+        def symbols(t):
+            if self.sym_size in _SYM_DTYPE:
+                return self._symbols(t)
+            return np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t)
+        parts = [symbols(t) for t in texts]
+        offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            np.cumsum([p.size * p.itemsize // self.sym_size for p in parts], out=offsets[1:])
+        packed = (np.concatenate([p.reshape(-1).view(np.uint8) for p in parts]) if parts else np.zeros(0, np.uint8))
+        n_sym = int(offsets[-1])
+        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
+        while True:
+            out = np.zeros(cap, dtype=RECORD_DTYPE)
+            first = np.zeros(len(parts) + 1, dtype=np.uint64)
+            n = C.c_uint64(0)
+            rc = self.L.acm_scan_batch(self.handle, packed.ctypes.data, offsets.ctypes.data, len(parts), out.ctypes.data, None,
+                                       first.ctypes.data, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and capacity is None:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_scan_batch")
+            res = []
+            for t in range(len(parts)):
+                r = out[int(first[t]):int(first[t + 1])].copy()
+                r["end_pos"] -= offsets[t]
+                res.append(r)
+            return res
+
 
 class Plan:
     """Device-resident flattened automaton (ACMPlan).  Scans take torch CUDA tensors (device
@@ -632,6 +673,60 @@ class Plan:
                 continue
             _check(rc, "acm_gpu_scan_host")
             return out[:n.value]
+
+    def scan_batch(self, text, offsets, capacity=None):
+        """acm_gpu_scan_batch_device(): `text` is a device tensor holding the texts of a batch side
+        by side, `offsets` an int64 device tensor of n_texts + 1 entries (text t = symbols
+        [offsets[t], offsets[t + 1])).  Every text is scanned from the root on its own.  Returns
+        numpy arrays (records, text_id, first): the records in canonical order with end_pos = the
+        index in `text`, the text of each, and first[t] .. first[t + 1] = the records of text t.
+        capacity must hold the matches of the whole buffer: by default Plan.count() says how many
+        there are, and an overflow is repeated once with the size the call reports."""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        cap = int(capacity) if capacity is not None else max(int(self.count(text).item()), 1)
+        for attempt in (0, 1):
+            records = torch.empty((cap, 2), dtype=torch.int64, device=text.device)
+            text_id = torch.empty(cap, dtype=torch.int32, device=text.device)
+            first = torch.zeros(n_texts + 1, dtype=torch.int64, device=text.device)
+            count = torch.zeros(1, dtype=torch.int64, device=text.device)
+            tb = lib().acm_gpu_scan_batch_tmp_bytes(self.h, cap, n_symbols, n_texts)
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+            _check(lib().acm_gpu_scan_batch_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, records.data_ptr(),
+                                                   text_id.data_ptr(), first.data_ptr(), cap, count.data_ptr(), tmp.data_ptr(), tmp.numel(),
+                                                   self._stream()), "acm_gpu_scan_batch_device")
+            n = int(count.item())
+            if n <= cap:
+                break
+            if attempt == 1:
+                raise ACMError(ACM_GPU_E_OVERFLOW, "acm_gpu_scan_batch_device: %d records" % n)
+            cap = n
+        self.status()
+        return (np.frombuffer(records[:n].cpu().numpy().tobytes(), dtype=RECORD_DTYPE).copy(),
+                text_id[:n].cpu().numpy().view(np.uint32).copy(), first.cpu().numpy().view(np.uint64).copy())
+
+    def scan_batch_host(self, text, offsets, capacity=None):
+        """acm_gpu_scan_batch_host(): the same from host arrays, through the C ABI only (no torch)."""
+        t = np.ascontiguousarray(text)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        n_texts = off.size - 1
+        cap = int(capacity) if capacity is not None else max(1024, t.size * t.itemsize // self.sym_size // 64)
+        for attempt in (0, 1):
+            out = np.zeros(cap, dtype=RECORD_DTYPE)
+            tid = np.zeros(cap, dtype=np.uint32)
+            first = np.zeros(n_texts + 1, dtype=np.uint64)
+            n = C.c_uint64(0)
+            rc = lib().acm_gpu_scan_batch_host(self.h, t.ctypes.data, off.ctypes.data, n_texts, out.ctypes.data, tid.ctypes.data,
+                                               first.ctypes.data, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_gpu_scan_batch_host")
+            return out[:n.value], tid[:n.value], first
 
     def stream(self, max_piece_symbols, record_capacity):
         return Stream(self, max_piece_symbols, record_capacity)

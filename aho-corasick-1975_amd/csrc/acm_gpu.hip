@@ -3186,6 +3186,183 @@ acm_gpu_scan_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t
 #undef HOST_TRY
 }
 
+/* ------------------------------------------------------------------ batch scans (include/acm_gpu.h, dev_batch.h)
+ * The ordered scan of the concatenation into the caller's scratch, then the pass over its records:
+ * those that lie inside one text go to d_records, with their text beside them. */
+namespace {
+struct BatchLayout {
+  uint64_t n_blocks = 0, n_tiles = 0;
+  size_t o_ctl = 0, o_index = 0, o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, o_rec = 0, o_ord = 0, ord_bytes = 0, total = 0;
+};
+BatchLayout
+batch_layout (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols) {
+  BatchLayout L;
+  L.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
+  L.n_tiles = (capacity + BATCH_TILE - 1) / BATCH_TILE;
+  size_t cub = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, cub, static_cast<uint32_t *> (nullptr), static_cast<uint32_t *> (nullptr), (int)(L.n_tiles + 1), nullptr);
+  L.cub_bytes = cub;
+  L.ord_bytes = acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols);
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (BatchCtl));
+  L.o_index = blob_reserve (cur, L.n_blocks * 4);
+  L.o_count = blob_reserve (cur, (L.n_tiles + 1) * 4);
+  L.o_begin = blob_reserve (cur, (L.n_tiles + 1) * 4);
+  L.o_cub = blob_reserve (cur, cub + 16);
+  L.o_rec = blob_reserve (cur, (capacity ? capacity : 1) * sizeof (ACMRecord));
+  L.o_ord = blob_reserve (cur, L.ord_bytes);
+  L.total = cur + 256;
+  return L;
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_scan_batch_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  (void)n_texts; /* (nothing here is sized by the number of texts: the index goes by blocks of positions) */
+  if (!plan || capacity >= (1ull << 31))
+    return 0;
+  return batch_layout (plan, capacity, n_symbols).total;
+}
+
+extern "C" int
+acm_gpu_scan_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts,
+                           ACMRecord *d_records, uint32_t *d_text_id, uint64_t *d_first, uint64_t capacity, uint64_t *d_count, void *d_tmp,
+                           size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || n_texts >= (1ull << 32) || capacity >= (1ull << 31) || (n_symbols && !d_text) || (capacity && !d_records))
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0) { /* no text, no symbol, no record */
+    if (n_symbols)
+      return ACM_GPU_E_ARG;
+    HIP_TRY (hipSetDevice (plan->device));
+    HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
+    if (d_first)
+      HIP_TRY (hipMemsetAsync (d_first, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  const BatchLayout L = batch_layout (plan, capacity, n_symbols);
+  if (!d_offsets || !d_tmp || tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  ACMRecord *ordered = reinterpret_cast<ACMRecord *> (t + L.o_rec);
+  int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, 0, ordered, capacity, d_count, t + L.o_ord, L.ord_bytes, stream);
+  if (rc)
+    return rc;
+  BatchK K{};
+  K.in = ordered;
+  K.capacity = capacity;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_count);
+  K.offsets = d_offsets;
+  K.n_texts = n_texts;
+  K.n_symbols = n_symbols;
+  K.index = reinterpret_cast<uint32_t *> (t + L.o_index);
+  K.n_blocks = L.n_blocks;
+  K.tile_count = reinterpret_cast<uint32_t *> (t + L.o_count);
+  K.tile_begin = reinterpret_cast<const uint32_t *> (t + L.o_begin);
+  K.n_tiles = L.n_tiles;
+  K.out = d_records;
+  K.text_id = d_text_id;
+  K.first = d_first;
+  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
+  K.ctl = reinterpret_cast<BatchCtl *> (t + L.o_ctl);
+  K.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+  /* grid-stride kernels: never more blocks than keep the chip busy.  The two kernels that also walk
+   * offsets[] are sized by the positions; a batch of many texts over few symbols (mostly empty texts)
+   * gets the full capped grid instead -- one size, whatever the number of texts */
+  const uint64_t most = (uint64_t)plan->cu_count * 8;
+  auto capped = [&] (uint64_t blocks) { return dim3 ((uint32_t)(blocks < 1 ? 1 : blocks < most ? blocks : most)); };
+  const uint64_t many_texts = n_texts >= (1ull << 16) ? most : 1;
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (BatchCtl), st));
+  /* (the index goes by the positions, the check of offsets[] by a grid-stride loop of the same launch) */
+  hipLaunchKernelGGL (batch_index_kernel, capped (std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  hipLaunchKernelGGL (batch_filter_kernel<false>, capped (L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  size_t cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.tile_count, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(L.n_tiles + 1), st));
+  hipLaunchKernelGGL (batch_filter_kernel<true>, capped (L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  hipLaunchKernelGGL (batch_first_kernel, capped (std::max (L.n_blocks / 4 + 1, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  return ACM_GPU_OK;
+}
+
+namespace {
+/* offsets[0 .. n_texts] of a batch on the host: first 0, non-decreasing (the last is the number of symbols) */
+bool
+batch_offsets_ok (const uint64_t *offsets, uint64_t n_texts) {
+  if (!offsets || offsets[0] != 0)
+    return false;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (offsets[t] > offsets[t + 1])
+      return false;
+  return true;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_scan_batch_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, ACMRecord *records, uint32_t *text_id,
+                         uint64_t *first, uint64_t capacity, uint64_t *n_found) {
+  if (!plan || !n_found || n_texts >= (1ull << 32) || capacity >= (1ull << 31) || (capacity && !records) || !batch_offsets_ok (offsets, n_texts))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_symbols = offsets[n_texts];
+  if (n_symbols && !text)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, tmp_bytes = acm_gpu_scan_batch_tmp_bytes (plan, capacity, n_symbols, n_texts);
+  void *d_text = nullptr, *d_off = nullptr, *d_rec = nullptr, *d_tid = nullptr, *d_first = nullptr, *d_tmp = nullptr, *d_count = nullptr;
+  uint64_t found = 0;
+  auto cleanup = [&] () {
+    for (void *p : { d_text, d_off, d_rec, d_tid, d_first, d_tmp, d_count })
+      if (p)
+        (void)hipFree (p);
+  };
+#define HOST_TRY(expr)                                                                             \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess) {                                                                        \
+      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
+      cleanup ();                                                                                  \
+      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
+    }                                                                                              \
+  } while (0)
+  HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
+  HOST_TRY (hipMalloc (&d_off, (n_texts + 1) * 8));
+  HOST_TRY (hipMalloc (&d_count, 8));
+  HOST_TRY (hipMalloc (&d_rec, capacity ? capacity * 16 : 16));
+  HOST_TRY (hipMalloc (&d_tid, capacity ? capacity * 4 : 16));
+  HOST_TRY (hipMalloc (&d_first, (n_texts + 1) * 8));
+  HOST_TRY (hipMalloc (&d_tmp, tmp_bytes));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+  const int rc = acm_gpu_scan_batch_device (plan, d_text, n_symbols, static_cast<const uint64_t *> (d_off), n_texts, static_cast<ACMRecord *> (d_rec),
+                                            static_cast<uint32_t *> (d_tid), static_cast<uint64_t *> (d_first), capacity,
+                                            static_cast<uint64_t *> (d_count), d_tmp, tmp_bytes, nullptr);
+  if (rc) {
+    (void)hipDeviceSynchronize ();
+    cleanup ();
+    return rc;
+  }
+  HOST_TRY (hipMemcpy (&found, d_count, 8, hipMemcpyDeviceToHost));
+  *n_found = found;
+  if (found > capacity) {
+    cleanup ();
+    return ACM_GPU_E_OVERFLOW;
+  }
+  if (found)
+    HOST_TRY (hipMemcpy (records, d_rec, found * 16, hipMemcpyDeviceToHost));
+  if (found && text_id)
+    HOST_TRY (hipMemcpy (text_id, d_tid, found * 4, hipMemcpyDeviceToHost));
+  if (first)
+    HOST_TRY (hipMemcpy (first, d_first, (n_texts + 1) * 8, hipMemcpyDeviceToHost));
+  HOST_TRY (hipDeviceSynchronize ());
+  cleanup ();
+  return ACM_GPU_OK;
+#undef HOST_TRY
+}
+
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
 extern "C" int
 acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint32_t *len_bits, uint32_t *kw_bits) {
@@ -3782,41 +3959,44 @@ struct PlanDropperInit {
 /* The reference lets many threads work on one shared machine (README.md:364); the cached plan and
  * its scratch buffers serve one scan at a time, so concurrent acm_scan calls on one machine queue
  * up on the machine's plan lock (threads that want to scan in parallel make a plan each). */
-extern "C" int
-acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
-  if (!machine || !n_found)
-    return ACM_GPU_E_ARG;
-  /* which path (include/acm_gpu.h): ACM_CMP_DEFAULT over 1/2/4/8 bytes -> GPU; another comparator
-   * with its symbol size declared -> GPU over its classes (1/2/4 bytes) or the caller loop on the host */
+namespace {
+/* what acm_scan and acm_scan_batch run on a machine (include/acm_gpu.h) */
+struct ScanRoute {
+  int path = ACM_SCAN_PATH_NONE; /* ACM_SCAN_PATH_* */
+  uint32_t said = 0;             /* the declared symbol size (the host loop's stride) */
+  ACMPlan *plan = nullptr;       /* the machine's cached plan, up to date (GPU paths, from route_plan) */
+};
+
+/* which path: ACM_CMP_DEFAULT over 1/2/4/8 bytes -> GPU; another comparator with its symbol size
+ * declared -> GPU over its classes (1/2/4 bytes) or the caller loop on the host */
+int
+scan_route (ACMachine *machine, ScanRoute *R) {
   uint32_t own_bytes = 0;
   const bool plain = acm_internal_symbol_bytes (machine, &own_bytes) == ACM_GPU_OK;
   uint32_t said = acm_internal_declared_symbol_bytes (machine);
-  if (!plain && said == 0) {
-    /* (ACM_CMP_DEFAULT over symbols of another size says the size itself: memcmp's length) */
-    CMP_TYPE cmp = nullptr;
-    void *cmp_arg = nullptr;
-    acm_internal_comparator (machine, &cmp, &cmp_arg);
-    if (cmp == ACM_CMP_DEFAULT && cmp_arg && *static_cast<const size_t *> (cmp_arg) > 0 && *static_cast<const size_t *> (cmp_arg) <= 4096)
-      said = (uint32_t)*static_cast<const size_t *> (cmp_arg);
-  }
+  CMP_TYPE cmp = nullptr;
+  void *cmp_arg = nullptr;
+  acm_internal_comparator (machine, &cmp, &cmp_arg);
+  /* (ACM_CMP_DEFAULT over symbols of another size says the size itself: memcmp's length) */
+  if (!plain && said == 0 && cmp == ACM_CMP_DEFAULT && cmp_arg && *static_cast<const size_t *> (cmp_arg) > 0 &&
+      *static_cast<const size_t *> (cmp_arg) <= 4096)
+    said = (uint32_t)*static_cast<const size_t *> (cmp_arg);
   if (!plain && said == 0)
     return ACM_GPU_E_INELIGIBLE;
-  bool classes = !plain && (said == 1 || said == 2 || said == 4);
-  {
-    CMP_TYPE cmp = nullptr;
-    void *cmp_arg = nullptr;
-    acm_internal_comparator (machine, &cmp, &cmp_arg);
-    if (cmp == ACM_CMP_DEFAULT)
-      classes = false; /* (memcmp over 3, 5, ... bytes: no classes to enumerate, the loop itself) */
-  }
-  acm_internal_plan_lock (machine);
+  /* (memcmp over 3, 5, ... bytes: no classes to enumerate, the loop itself) */
+  const bool classes = !plain && (said == 1 || said == 2 || said == 4) && cmp != ACM_CMP_DEFAULT;
+  R->said = said;
+  R->path = plain ? ACM_SCAN_PATH_GPU : classes ? ACM_SCAN_PATH_GPU_CLASSES : ACM_SCAN_PATH_CPU_LOOP;
+  return ACM_GPU_OK;
+}
+
+/* the GPU paths, with the machine's plan lock held: the cached plan, made or brought up to date.
+ * A comparator that is no consistent order over all symbol values (acm_flatten_classes refuses it)
+ * cannot be taken by the GPU by its nature: the route becomes the loop itself. */
+int
+route_plan (ACMachine *machine, ScanRoute *R) {
+  const bool classes = R->path == ACM_SCAN_PATH_GPU_CLASSES;
   int rc = ACM_GPU_OK;
-  if (!plain && !classes) {
-    rc = acm_internal_cpu_scan (machine, text, n_symbols, said, records, capacity, n_found);
-    acm_internal_set_scan_path (machine, ACM_SCAN_PATH_CPU_LOOP);
-    acm_internal_plan_unlock (machine);
-    return rc;
-  }
   void **slot = acm_internal_plan_slot (machine);
   ACMPlan *plan = static_cast<ACMPlan *> (*slot);
   if (plan && (plan->generation != acm_internal_generation (machine) ||
@@ -3829,23 +4009,60 @@ acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *r
     /* keywords inserted while the tables are being made are picked up by the next call: the
      * generation is read first */
     const uint64_t gen = acm_internal_generation (machine);
-    rc = classes ? acm_gpu_plan_create_classes (machine, said, device, &plan) : acm_gpu_plan_create (machine, device, &plan);
+    rc = classes ? acm_gpu_plan_create_classes (machine, R->said, device, &plan) : acm_gpu_plan_create (machine, device, &plan);
     if (!rc) {
       plan->generation = gen;
       *slot = plan;
     }
   }
   if (rc == ACM_GPU_E_INELIGIBLE && classes) {
-    /* the comparator is no consistent order over all symbol values (acm_flatten_classes): the GPU
-     * cannot take this machine by its nature -- the loop itself */
-    rc = acm_internal_cpu_scan (machine, text, n_symbols, said, records, capacity, n_found);
-    acm_internal_set_scan_path (machine, ACM_SCAN_PATH_CPU_LOOP);
-    acm_internal_plan_unlock (machine);
-    return rc;
+    R->path = ACM_SCAN_PATH_CPU_LOOP;
+    return ACM_GPU_OK;
   }
+  R->plan = plan;
+  return rc;
+}
+} // namespace
+
+extern "C" int
+acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
+  if (!machine || !n_found)
+    return ACM_GPU_E_ARG;
+  ScanRoute R;
+  int rc = scan_route (machine, &R);
+  if (rc)
+    return rc;
+  acm_internal_plan_lock (machine);
+  if (R.path != ACM_SCAN_PATH_CPU_LOOP)
+    rc = route_plan (machine, &R);
   if (!rc) {
-    rc = acm_gpu_scan_host (plan, text, n_symbols, 0, 0, records, capacity, n_found);
-    acm_internal_set_scan_path (machine, classes ? ACM_SCAN_PATH_GPU_CLASSES : ACM_SCAN_PATH_GPU);
+    rc = R.path == ACM_SCAN_PATH_CPU_LOOP ? acm_internal_cpu_scan (machine, text, n_symbols, R.said, records, capacity, n_found)
+                                          : acm_gpu_scan_host (R.plan, text, n_symbols, 0, 0, records, capacity, n_found);
+    acm_internal_set_scan_path (machine, R.path);
+  }
+  acm_internal_plan_unlock (machine);
+  return rc;
+}
+
+/* the same on a batch of texts (include/acm_gpu.h): same route, same cached plan, same lock */
+extern "C" int
+acm_scan_batch (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, ACMRecord *records, uint32_t *text_id,
+                uint64_t *first, uint64_t capacity, uint64_t *n_found) {
+  if (!machine || !n_found || n_texts >= (1ull << 32) || (capacity && !records) || !batch_offsets_ok (offsets, n_texts) ||
+      (offsets[n_texts] && !text))
+    return ACM_GPU_E_ARG;
+  ScanRoute R;
+  int rc = scan_route (machine, &R);
+  if (rc)
+    return rc;
+  acm_internal_plan_lock (machine);
+  if (R.path != ACM_SCAN_PATH_CPU_LOOP)
+    rc = route_plan (machine, &R);
+  if (!rc) {
+    rc = R.path == ACM_SCAN_PATH_CPU_LOOP
+           ? acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, R.said, records, text_id, first, capacity, n_found)
+           : acm_gpu_scan_batch_host (R.plan, text, offsets, n_texts, records, text_id, first, capacity, n_found);
+    acm_internal_set_scan_path (machine, R.path);
   }
   acm_internal_plan_unlock (machine);
   return rc;

@@ -691,6 +691,33 @@ acm_print (ACMachine *machine, FILE *stream, PRINT_TYPE printer) {
   fprintf (stream, "\n");
 }
 
+/* the caller loop over symbols [begin, end) of `text`, from the root; appends behind the `found`
+ * records there are and returns the new total (text_id, when given, takes `id` beside every record) */
+static uint64_t
+cpu_loop (const ACMachine *m, const void *text, uint64_t begin, uint64_t end, uint32_t sym_bytes, ACMRecord *records, uint32_t *text_id, uint32_t id,
+          uint64_t capacity, uint64_t found) {
+  const unsigned char *t = text;
+  const struct _ac_state *s = m->root;
+  for (uint64_t i = begin; i < end; i++) {
+    s = automaton_step (s, t + i * sym_bytes);
+    uint32_t nb = LOAD (&s->nb_outputs);
+    for (const struct _ac_state *o = s; nb; o = LOAD (&o->fail)) { /* nearest (= longest) terminal state first */
+      if (!LOAD (&o->terminal))
+        continue;
+      if (found < capacity) {
+        records[found].end_pos = i;
+        records[found].length = o->depth;
+        records[found].keyword_id = o->rank;
+        if (text_id)
+          text_id[found] = id;
+      }
+      found++;
+      nb--;
+    }
+  }
+  return found;
+}
+
 /* The reference's caller loop (examples/test.c:17-23; acm_match aho_corasick.c:434-448, acm_get_match
  * :451-482) over a buffer of fixed-size symbols, with THIS library's own automaton step and failure
  * chain -- what acm_scan runs for a machine the GPU path cannot take (a comparator of its own over
@@ -704,24 +731,29 @@ acm_internal_cpu_scan (ACMachine *m, const void *text, uint64_t n_symbols, uint3
 #ifdef ACM_NMEYER_85
   acm_internal_refresh (m);
 #endif
-  const unsigned char *t = text;
-  const struct _ac_state *s = m->root;
+  *n_found = cpu_loop (m, text, 0, n_symbols, sym_bytes, records, NULL, 0, capacity, 0);
+  return *n_found > capacity ? ACM_GPU_E_OVERFLOW : ACM_GPU_OK;
+}
+
+/* The same loop over a batch (acm_scan_batch, include/acm_gpu.h): from the root at every offset,
+ * end_pos = the index in the whole buffer; text_id and first may be NULL.  offsets[] has been
+ * checked by the caller. */
+int
+acm_internal_cpu_scan_batch (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, ACMRecord *records,
+                             uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found) {
+  if (!m || !n_found || !offsets || (offsets[n_texts] && !text) || (capacity && !records) || !sym_bytes)
+    return ACM_GPU_E_ARG;
+#ifdef ACM_NMEYER_85
+  acm_internal_refresh (m);
+#endif
   uint64_t found = 0;
-  for (uint64_t i = 0; i < n_symbols; i++) {
-    s = automaton_step (s, t + i * sym_bytes);
-    uint32_t nb = LOAD (&s->nb_outputs);
-    for (const struct _ac_state *o = s; nb; o = LOAD (&o->fail)) { /* nearest (= longest) terminal state first */
-      if (!LOAD (&o->terminal))
-        continue;
-      if (found < capacity) {
-        records[found].end_pos = i;
-        records[found].length = o->depth;
-        records[found].keyword_id = o->rank;
-      }
-      found++;
-      nb--;
-    }
+  for (uint64_t t = 0; t < n_texts; t++) {
+    if (first)
+      first[t] = found;
+    found = cpu_loop (m, text, offsets[t], offsets[t + 1], sym_bytes, records, text_id, (uint32_t)t, capacity, found);
   }
+  if (first)
+    first[n_texts] = found;
   *n_found = found;
   return found > capacity ? ACM_GPU_E_OVERFLOW : ACM_GPU_OK;
 }

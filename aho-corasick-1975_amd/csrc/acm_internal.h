@@ -55,6 +55,9 @@ void acm_internal_comparator (const ACMachine *m, CMP_TYPE *cmp, void **cmp_arg)
 uint32_t acm_internal_declared_symbol_bytes (const ACMachine *m);
 int acm_internal_cpu_scan (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records, uint64_t capacity,
                            uint64_t *n_found);
+/* the same loop from the root on every text of a batch (acm_scan_batch); offsets[] already checked */
+int acm_internal_cpu_scan_batch (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, ACMRecord *records,
+                                 uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

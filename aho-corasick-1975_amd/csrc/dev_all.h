@@ -159,5 +159,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_misc.h"
 #include "dev_order.h"
 #include "dev_tiles.h"
+#include "dev_batch.h"
 
 } // namespace

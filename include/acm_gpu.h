@@ -304,6 +304,59 @@ int acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecor
 int acm_set_symbol_bytes (ACMachine *machine, uint32_t sym_bytes);
 int acm_scan_path (const ACMachine *machine);
 
+/* ------------------------------------------------------------------ batch scan: many texts in one call
+ * The reference's callers mostly do not have one text: they run the loop above word by word and
+ * line by line (log lines, packets, table cells), each from acm_initiate on its own.  A batch is
+ * n_texts such texts packed into one buffer: text t is the symbols [offsets[t], offsets[t + 1]),
+ * with offsets[0 .. n_texts] non-decreasing, offsets[0] = 0 and offsets[n_texts] = n_symbols (empty
+ * texts are allowed).
+ *
+ * The result is DEFINED as the caller loop run from acm_initiate(machine) on every text separately,
+ * t = 0, 1, ..., the results concatenated; a record of text t carries end_pos = offsets[t] + i, the
+ * index in the whole buffer.  Positions are therefore unique and the order is the plain canonical
+ * one (end_pos ascending, length descending).  Beside the records:
+ *     text_id[r]            the text of record r;
+ *     first[0 .. n_texts]   records [first[t], first[t + 1]) are those of text t, first[n_texts] is
+ *                           the number of records; end_pos - offsets[text_id] is the position
+ *                           inside the text.
+ * (Scanning the concatenation with acm_gpu_scan_* instead would also report the matches that begin
+ * in one text and end in the next.  The automaton reports every occurrence of every keyword, so
+ * the batch's records are exactly the concatenation's that lie inside one text: the ordered scan of
+ * the buffer -- whatever kernel the plan has -- and one pass over its RECORDS, dev_batch.h.)
+ *
+ * acm_gpu_scan_batch_device: acm_gpu_scan_ordered_device (emit_from = 0, pos_base = 0) and that pass
+ * behind it on `stream`; asynchronous to exactly the extent that call is.  CAPACITY: `capacity`
+ * must hold the matches of the CONCATENATION (they are found first, in d_tmp).  *d_count <=
+ * capacity afterwards: it is the exact number of the batch's records, and d_records, d_text_id and
+ * d_first are complete.  *d_count > capacity: it is the concatenation's count -- a capacity that is
+ * guaranteed to suffice -- and the three outputs are unspecified; nothing is dropped silently.
+ * n_texts = 0 requires n_symbols = 0 and gives no record; n_texts >= 2^32 is ACM_GPU_E_ARG, and so is
+ * capacity >= 2^31 (the tiles' counts and their prefix sum are 32-bit, as the bucket order's are).
+ * d_offsets that break the contract above leave *d_count = 0 and make acm_gpu_plan_status report
+ * ACM_GPU_E_INTERNAL (as a record out of range does in acm_gpu_order_records_device); nothing is
+ * read or written out of bounds.  d_tmp must hold acm_gpu_scan_batch_tmp_bytes(plan, capacity,
+ * n_symbols, n_texts) bytes (about 32 bytes per record of capacity, 4 bytes per 4,096 symbols).
+ * acm_gpu_scan_batch_host: the same from host memory, blocking; offsets[] is checked on the host
+ * (ACM_GPU_E_ARG); on ACM_GPU_E_OVERFLOW *n_found holds a capacity that suffices.
+ * acm_scan_batch: the call on the machine itself, total over machines exactly as acm_scan is (same
+ * paths, same cached plan, acm_scan_path says which ran): the GPU paths run
+ * acm_gpu_scan_batch_host, ACM_SCAN_PATH_CPU_LOOP runs the loop on the host from the root at every
+ * offset.  A missing device stays an error, never a fallback.
+ * text_id and first may be NULL wherever they appear. */
+size_t acm_gpu_scan_batch_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols,
+                               const uint64_t *d_offsets, uint64_t n_texts,
+                               ACMRecord *d_records, uint32_t *d_text_id /* may be NULL */,
+                               uint64_t *d_first /* n_texts + 1, may be NULL */,
+                               uint64_t capacity, uint64_t *d_count,
+                               void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_batch_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts,
+                             ACMRecord *records, uint32_t *text_id, uint64_t *first,
+                             uint64_t capacity, uint64_t *n_found);          /* blocking */
+int acm_scan_batch (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts,
+                    ACMRecord *records, uint32_t *text_id, uint64_t *first,
+                    uint64_t capacity, uint64_t *n_found);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
