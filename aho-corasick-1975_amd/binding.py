@@ -84,6 +84,8 @@ EXPORTS = [
     "acm_gpu_unpack_records_device", "acm_gpu_comm_unique_id", "acm_gpu_comm_init_rank", "acm_gpu_comm_free", "acm_gpu_comm_create",
     "acm_gpu_comm_destroy", "acm_gpu_comm_gather_records",
     "acm_gpu_scan_batch_tmp_bytes", "acm_gpu_scan_batch_device", "acm_gpu_scan_batch_host", "acm_scan_batch",
+    "acm_gpu_flows_create", "acm_gpu_flows_destroy", "acm_gpu_flows_reset", "acm_gpu_scan_flows_tmp_bytes", "acm_gpu_scan_flows_device",
+    "acm_gpu_scan_flows_host", "acm_scan_from",
 ]
 
 
@@ -239,6 +241,20 @@ def lib():
     L.acm_gpu_scan_batch_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
     L.acm_scan_batch.restype = i32
     L.acm_scan_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_flows_create.restype = i32
+    L.acm_gpu_flows_create.argtypes = [vp, u64, C.POINTER(vp)]
+    L.acm_gpu_flows_destroy.restype = None
+    L.acm_gpu_flows_destroy.argtypes = [vp]
+    L.acm_gpu_flows_reset.restype = i32
+    L.acm_gpu_flows_reset.argtypes = [vp, vp, u64, vp]
+    L.acm_gpu_scan_flows_tmp_bytes.restype = sz
+    L.acm_gpu_scan_flows_tmp_bytes.argtypes = [vp, vp, u64, u64, u64]
+    L.acm_gpu_scan_flows_device.restype = i32
+    L.acm_gpu_scan_flows_device.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_flows_host.restype = i32
+    L.acm_gpu_scan_flows_host.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_scan_from.restype = i32
+    L.acm_scan_from.argtypes = [vp, C.POINTER(vp), vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_gpu_synth_text.restype = i32
     L.acm_gpu_synth_text.argtypes = [i32, vp, u64, u64, u32, u32, vp, vp, u32, vp]
     _lib = L
@@ -501,6 +517,29 @@ class Machine:
             _check(rc, "acm_scan")
             return out[:n.value]
 
+    def root(self):
+        """The cursor of a scan that has seen nothing yet (acm_initiate): what scan_from() and the
+        per-symbol acm_match start from."""
+        return C.c_void_p(self.L.acm_initiate(self.handle))
+
+    def scan_from(self, cursor, text, capacity=None):
+        """acm_scan_from(): scan_host() continued from `cursor` (root(), or what an earlier scan_from
+        or acm_match left).  Returns (records, cursor afterwards): end_pos is the index in `text`, a
+        keyword cut by the boundary between two texts is found.  `cursor` itself is not changed."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        cap = int(capacity) if capacity is not None else max(1024, t.size // 64)
+        while True:
+            out = np.zeros(cap, dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            cur = C.c_void_p(cursor.value)
+            rc = self.L.acm_scan_from(self.handle, C.byref(cur), t.ctypes.data, t.size * t.itemsize // self.sym_size, out.ctypes.data, cap,
+                                      C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and capacity is None:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_scan_from")
+            return out[:n.value], cur
+
     def scan_batch(self, texts, capacity=None):
         """acm_scan_batch(): a list of texts (bytes or arrays of symbols), each scanned from the root
         on its own in ONE call.  Returns a list with one record array per text, end_pos relative to
@@ -731,6 +770,11 @@ class Plan:
     def stream(self, max_piece_symbols, record_capacity):
         return Stream(self, max_piece_symbols, record_capacity)
 
+    def flows(self, n_flows):
+        """acm_gpu_flows_create(): the state of n_flows flows (connections, files, log sources) on the
+        device, all at the root; Flows.scan() is a batch scan whose texts continue them."""
+        return Flows(self, n_flows)
+
     def wire(self, span, pos_lo):
         """(pos_lo, pos_bits, len_bits) for the 8-byte wire form of the records of a scan of `span` symbols
         with pos_base = pos_lo (acm_gpu_wire_bits), or None when the fields do not fit 64 bits."""
@@ -878,6 +922,95 @@ class Comm:
         if self.nccl:
             lib().acm_gpu_comm_free(self.nccl)
             self.nccl = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Flows:
+    """acm_gpu_flows_* / acm_gpu_scan_flows_*: a batch scan whose text t continues flow flow[t] -- a
+    keyword cut by the boundary between two pieces of a flow is found, with end_pos in the piece it
+    ends in.  Results as Plan.scan_batch gives them: numpy arrays (records, text_id, first)."""
+
+    def __init__(self, plan, n_flows):
+        self.plan = plan
+        self.n_flows = int(n_flows)
+        h = C.c_void_p()
+        _check(lib().acm_gpu_flows_create(plan.h, self.n_flows, C.byref(h)), "acm_gpu_flows_create")
+        self.h = h
+
+    def scan(self, text, offsets, flow=None, capacity=None):
+        """acm_gpu_scan_flows_device(): `text` and `offsets` (int64) as in Plan.scan_batch, `flow` an
+        int32 device tensor of n_texts flow ids (None: text t is flow t).  An overflow is repeated
+        once with the size the call reports (the flows have not moved)."""
+        import torch
+        p = self.plan
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        assert flow is None or (flow.is_cuda and flow.is_contiguous() and flow.dtype == torch.int32 and flow.numel() == offsets.numel() - 1)
+        n_symbols = text.numel() * text.element_size() // p.sym_size
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        cap = int(capacity) if capacity is not None else max(1024, n_symbols // 64)
+        for attempt in (0, 1):
+            records = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=text.device)
+            text_id = torch.empty(max(cap, 1), dtype=torch.int32, device=text.device)
+            first = torch.zeros(n_texts + 1, dtype=torch.int64, device=text.device)
+            count = torch.zeros(1, dtype=torch.int64, device=text.device)
+            tb = lib().acm_gpu_scan_flows_tmp_bytes(p.h, self.h, cap, n_symbols, n_texts)
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+            _check(lib().acm_gpu_scan_flows_device(p.h, self.h, text.data_ptr(), n_symbols, offsets.data_ptr(),
+                                                   flow.data_ptr() if flow is not None else None, n_texts, records.data_ptr(), text_id.data_ptr(),
+                                                   first.data_ptr(), cap, count.data_ptr(), tmp.data_ptr(), tmp.numel(), p._stream()),
+                   "acm_gpu_scan_flows_device")
+            n = int(count.item())
+            if n <= cap:
+                break
+            if attempt == 1:
+                raise ACMError(ACM_GPU_E_OVERFLOW, "acm_gpu_scan_flows_device: %d records" % n)
+            cap = n
+        p.status()
+        return (np.frombuffer(records[:n].cpu().numpy().tobytes(), dtype=RECORD_DTYPE).copy(),
+                text_id[:n].cpu().numpy().view(np.uint32).copy(), first.cpu().numpy().view(np.uint64).copy())
+
+    def scan_host(self, text, offsets, flow=None, capacity=None):
+        """acm_gpu_scan_flows_host(): the same from host arrays, through the C ABI only (no torch)."""
+        p = self.plan
+        t = np.ascontiguousarray(text)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        n_texts = off.size - 1
+        fl = None if flow is None else np.ascontiguousarray(flow, dtype=np.uint32)
+        assert fl is None or fl.size == n_texts
+        n_sym = t.size * t.itemsize // p.sym_size
+        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
+        for attempt in (0, 1):
+            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
+            tid = np.zeros(max(cap, 1), dtype=np.uint32)
+            first = np.zeros(n_texts + 1, dtype=np.uint64)
+            n = C.c_uint64(0)
+            rc = lib().acm_gpu_scan_flows_host(p.h, self.h, t.ctypes.data, n_sym, off.ctypes.data, fl.ctypes.data if fl is not None else None,
+                                               n_texts, out.ctypes.data, tid.ctypes.data, first.ctypes.data, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_gpu_scan_flows_host")
+            return out[:n.value], tid[:n.value], first
+
+    def reset(self, ids=None):
+        """acm_gpu_flows_reset(): the flows `ids` (an int32 device tensor; None: all) back to the root."""
+        if ids is not None:
+            import torch
+            assert ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int32
+        _check(lib().acm_gpu_flows_reset(self.h, ids.data_ptr() if ids is not None else None, ids.numel() if ids is not None else 0,
+                                         self.plan._stream() if ids is not None else None), "acm_gpu_flows_reset")
+
+    def close(self):
+        if self.h:
+            lib().acm_gpu_flows_destroy(self.h)
+            self.h = None
 
     def __del__(self):
         try:

@@ -3127,13 +3127,17 @@ acm_gpu_scan_ordered_device (ACMPlan *plan, const void *d_text, uint64_t n_symbo
 }
 
 /* ------------------------------------------------------------------ host-buffer convenience */
-extern "C" int
-acm_gpu_scan_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t emit_from, uint64_t pos_base,
-                   ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
-  if (!plan || !n_found || (n_symbols && !text) || (capacity && !records))
+namespace {
+/* acm_gpu_scan_host over `prefix` (n_prefix symbols, may be none) followed by `text`: the two are
+ * uploaded side by side, so that acm_scan_from need not copy its text on the host */
+int
+scan_host_prefixed (ACMPlan *plan, const void *prefix, uint64_t n_prefix, const void *text, uint64_t n_text, uint64_t emit_from, uint64_t pos_base,
+                    ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
+  if (!plan || !n_found || (n_text && !text) || (n_prefix && !prefix) || (capacity && !records))
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
+  const uint64_t n_symbols = n_prefix + n_text;
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, pbytes = (size_t)n_prefix * plan->text_sym_bytes;
   void *d_text = nullptr, *d_rec = nullptr, *d_tmp = nullptr;
   uint64_t *d_count = nullptr;
   int rc = ACM_GPU_OK;
@@ -3156,8 +3160,10 @@ acm_gpu_scan_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t
   HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
   HOST_TRY (hipMalloc (reinterpret_cast<void **> (&d_count), 8));
   HOST_TRY (hipMalloc (&d_rec, capacity ? capacity * 16 : 16));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  if (pbytes)
+    HOST_TRY (hipMemcpy (d_text, prefix, pbytes, hipMemcpyHostToDevice));
+  if (tbytes > pbytes)
+    HOST_TRY (hipMemcpy (static_cast<unsigned char *> (d_text) + pbytes, text, tbytes - pbytes, hipMemcpyHostToDevice));
   rc = acm_gpu_scan_device (plan, d_text, n_symbols, emit_from, pos_base, static_cast<ACMRecord *> (d_rec), capacity, d_count, nullptr);
   if (rc) {
     cleanup ();
@@ -3184,6 +3190,13 @@ acm_gpu_scan_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t
   cleanup ();
   return ACM_GPU_OK;
 #undef HOST_TRY
+}
+} // namespace
+
+extern "C" int
+acm_gpu_scan_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t emit_from, uint64_t pos_base,
+                   ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
+  return scan_host_prefixed (plan, nullptr, 0, text, n_symbols, emit_from, pos_base, records, capacity, n_found);
 }
 
 /* ------------------------------------------------------------------ batch scans (include/acm_gpu.h, dev_batch.h)
@@ -3224,10 +3237,21 @@ acm_gpu_scan_batch_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n
   return batch_layout (plan, capacity, n_symbols).total;
 }
 
-extern "C" int
-acm_gpu_scan_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts,
-                           ACMRecord *d_records, uint32_t *d_text_id, uint64_t *d_first, uint64_t capacity, uint64_t *d_count, void *d_tmp,
-                           size_t tmp_bytes, void *stream) {
+namespace {
+/* flow scans (dev_flows.h): the batch is an expanded buffer whose texts begin with carried symbols */
+struct BatchHeads {
+  const uint32_t *head;        /* [n_texts] carried symbols in front of every text */
+  const uint64_t *base;        /* [n_real + 1] the texts' offsets in the caller's buffer */
+  uint64_t n_real;             /* texts that report (the rest is fill) */
+  const unsigned int *pre_bad; /* the caller's own checks have failed */
+};
+
+/* acm_gpu_scan_batch_device; HEADS: what the flow scan runs behind its gather pass */
+template <bool HEADS>
+int
+batch_scan (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_records,
+            uint32_t *d_text_id, uint64_t *d_first, uint64_t capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream,
+            const BatchHeads *heads) {
   if (!plan || !d_count || n_texts >= (1ull << 32) || capacity >= (1ull << 31) || (n_symbols && !d_text) || (capacity && !d_records))
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
@@ -3267,6 +3291,12 @@ acm_gpu_scan_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols
   K.d_count = reinterpret_cast<unsigned long long *> (d_count);
   K.ctl = reinterpret_cast<BatchCtl *> (t + L.o_ctl);
   K.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+  if (HEADS) {
+    K.head = heads->head;
+    K.base = heads->base;
+    K.n_real = heads->n_real;
+    K.pre_bad = heads->pre_bad;
+  }
   /* grid-stride kernels: never more blocks than keep the chip busy.  The two kernels that also walk
    * offsets[] are sized by the positions; a batch of many texts over few symbols (mostly empty texts)
    * gets the full capped grid instead -- one size, whatever the number of texts */
@@ -3275,17 +3305,26 @@ acm_gpu_scan_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols
   const uint64_t many_texts = n_texts >= (1ull << 16) ? most : 1;
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (BatchCtl), st));
   /* (the index goes by the positions, the check of offsets[] by a grid-stride loop of the same launch) */
-  hipLaunchKernelGGL (batch_index_kernel, capped (std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
+  hipLaunchKernelGGL (batch_index_kernel<HEADS>, capped (std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (batch_filter_kernel<false>, capped (L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
+  hipLaunchKernelGGL ((batch_filter_kernel<false, HEADS>), capped (L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
   size_t cub = L.cub_bytes;
   HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.tile_count, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(L.n_tiles + 1), st));
-  hipLaunchKernelGGL (batch_filter_kernel<true>, capped (L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
+  hipLaunchKernelGGL ((batch_filter_kernel<true, HEADS>), capped (L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (batch_first_kernel, capped (std::max (L.n_blocks / 4 + 1, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
+  hipLaunchKernelGGL (batch_first_kernel<HEADS>, capped (std::max (L.n_blocks / 4 + 1, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
   return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_scan_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts,
+                           ACMRecord *d_records, uint32_t *d_text_id, uint64_t *d_first, uint64_t capacity, uint64_t *d_count, void *d_tmp,
+                           size_t tmp_bytes, void *stream) {
+  return batch_scan<false> (plan, d_text, n_symbols, d_offsets, n_texts, d_records, d_text_id, d_first, capacity, d_count, d_tmp, tmp_bytes, stream,
+                            nullptr);
 }
 
 namespace {
@@ -3338,6 +3377,289 @@ acm_gpu_scan_batch_host (ACMPlan *plan, const void *text, const uint64_t *offset
     HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
   HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
   const int rc = acm_gpu_scan_batch_device (plan, d_text, n_symbols, static_cast<const uint64_t *> (d_off), n_texts, static_cast<ACMRecord *> (d_rec),
+                                            static_cast<uint32_t *> (d_tid), static_cast<uint64_t *> (d_first), capacity,
+                                            static_cast<uint64_t *> (d_count), d_tmp, tmp_bytes, nullptr);
+  if (rc) {
+    (void)hipDeviceSynchronize ();
+    cleanup ();
+    return rc;
+  }
+  HOST_TRY (hipMemcpy (&found, d_count, 8, hipMemcpyDeviceToHost));
+  *n_found = found;
+  if (found > capacity) {
+    cleanup ();
+    return ACM_GPU_E_OVERFLOW;
+  }
+  if (found)
+    HOST_TRY (hipMemcpy (records, d_rec, found * 16, hipMemcpyDeviceToHost));
+  if (found && text_id)
+    HOST_TRY (hipMemcpy (text_id, d_tid, found * 4, hipMemcpyDeviceToHost));
+  if (first)
+    HOST_TRY (hipMemcpy (first, d_first, (n_texts + 1) * 8, hipMemcpyDeviceToHost));
+  HOST_TRY (hipDeviceSynchronize ());
+  cleanup ();
+  return ACM_GPU_OK;
+#undef HOST_TRY
+}
+
+/* ------------------------------------------------------------------ flow scans (include/acm_gpu.h, dev_flows.h)
+ * Per-flow state on the device and the passes around the batch scan that use it. */
+struct ACMFlows {
+  ACMPlan *plan = nullptr;
+  int device = 0;
+  uint64_t n_flows = 0;
+  uint32_t sb = 1;           /* bytes per symbol of the caller's text */
+  uint32_t slot_symbols = 0; /* a slot holds this many: lmax - 1 at creation, rounded up to whole 16 bytes */
+  uint32_t slot_bytes = 16;
+  unsigned char *d_carry = nullptr; /* [n_flows] slots */
+  uint32_t *d_len = nullptr;        /* [n_flows] symbols each slot holds */
+  uint32_t *d_claim = nullptr;      /* [n_flows] sequence number of the last call the flow took part in */
+  uint32_t seq = 0;
+};
+
+namespace {
+/* symbols of a full carry: the longest keyword of the plan and of its delta, less one */
+uint32_t
+flows_keep (const ACMPlan *p) {
+  const uint32_t own = p->finfo.lmax, more = p->delta ? p->delta->finfo.lmax : 0;
+  const uint32_t lmax = own > more ? own : more;
+  return lmax > 1 ? lmax - 1 : 0;
+}
+
+struct HeadTo64 {
+  __host__ __device__ uint64_t operator() (uint32_t v) const { return v; }
+};
+using HeadIterator = hipcub::TransformInputIterator<uint64_t, HeadTo64, const uint32_t *>;
+
+struct FlowsLayout {
+  uint64_t n_expanded = 0;
+  size_t o_ctl = 0, o_head = 0, o_sum = 0, o_xoff = 0, o_cub = 0, cub_bytes = 0, o_text = 0, o_batch = 0, batch_bytes = 0, total = 0;
+};
+FlowsLayout
+flows_layout (const ACMPlan *plan, const ACMFlows *flows, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  FlowsLayout L;
+  L.n_expanded = n_symbols + n_texts * flows_keep (plan); /* every text behind a full carry: the worst case */
+  size_t cub = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, cub, HeadIterator (static_cast<const uint32_t *> (nullptr), HeadTo64 ()), static_cast<uint64_t *> (nullptr), (int)(n_texts + 1), nullptr);
+  L.cub_bytes = cub;
+  L.batch_bytes = batch_layout (plan, capacity, L.n_expanded).total;
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (FlowsCtl));
+  L.o_head = blob_reserve (cur, (n_texts + 1) * 4);
+  L.o_sum = blob_reserve (cur, (n_texts + 1) * 8);
+  L.o_xoff = blob_reserve (cur, (n_texts + 2) * 8);
+  L.o_cub = blob_reserve (cur, cub + 16);
+  L.o_text = blob_reserve (cur, L.n_expanded * flows->sb + 256);
+  L.o_batch = blob_reserve (cur, L.batch_bytes);
+  L.total = cur + 256;
+  return L;
+}
+
+uint32_t
+log2_ceil_capped (uint64_t x, uint32_t most) {
+  uint32_t l = 0;
+  while (l < most && (1ull << l) < x)
+    l++;
+  return l;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_flows_create (ACMPlan *plan, uint64_t n_flows, ACMFlows **out) {
+  if (!plan || !out || n_flows == 0 || n_flows >= (1ull << 32))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  ACMFlows *f = new (std::nothrow) ACMFlows ();
+  if (!f)
+    return ACM_GPU_E_NOMEM;
+  f->plan = plan;
+  f->device = plan->device;
+  f->n_flows = n_flows;
+  f->sb = plan->text_sym_bytes;
+  f->slot_bytes = (uint32_t)(((size_t)flows_keep (plan) * f->sb + 15) / 16 * 16);
+  if (f->slot_bytes == 0)
+    f->slot_bytes = 16;
+  f->slot_symbols = f->slot_bytes / f->sb;
+  const bool ok = hipMalloc (reinterpret_cast<void **> (&f->d_carry), (size_t)n_flows * f->slot_bytes) == hipSuccess &&
+                  hipMalloc (reinterpret_cast<void **> (&f->d_len), (size_t)n_flows * 4) == hipSuccess &&
+                  hipMalloc (reinterpret_cast<void **> (&f->d_claim), (size_t)n_flows * 4) == hipSuccess &&
+                  hipMemset (f->d_len, 0, (size_t)n_flows * 4) == hipSuccess && hipMemset (f->d_claim, 0, (size_t)n_flows * 4) == hipSuccess &&
+                  hipDeviceSynchronize () == hipSuccess;
+  if (!ok) {
+    acm_gpu_flows_destroy (f);
+    return ACM_GPU_E_NOMEM;
+  }
+  *out = f;
+  return ACM_GPU_OK;
+}
+
+extern "C" void
+acm_gpu_flows_destroy (ACMFlows *f) {
+  if (!f)
+    return;
+  (void)hipSetDevice (f->device);
+  for (void *d : { static_cast<void *> (f->d_carry), static_cast<void *> (f->d_len), static_cast<void *> (f->d_claim) })
+    if (d)
+      (void)hipFree (d);
+  delete f;
+}
+
+extern "C" int
+acm_gpu_flows_reset (ACMFlows *f, const uint32_t *d_flow_ids, uint64_t n, void *stream) {
+  if (!f)
+    return ACM_GPU_E_ARG;
+  const uint64_t items = d_flow_ids ? n : f->n_flows;
+  if (items == 0)
+    return ACM_GPU_OK;
+  ACMPlan *plan = f->plan;
+  HIP_TRY (hipSetDevice (plan->device));
+  const uint64_t most = (uint64_t)plan->cu_count * 8, want = (items + FLOWS_THREADS - 1) / FLOWS_THREADS;
+  unsigned int *error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+  hipLaunchKernelGGL (flows_reset_kernel, dim3 ((uint32_t)(want < most ? want : most)), dim3 (FLOWS_THREADS), 0, static_cast<hipStream_t> (stream),
+                      f->d_len, f->n_flows, d_flow_ids, n, error);
+  HIP_TRY (hipGetLastError ());
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_scan_flows_tmp_bytes (const ACMPlan *plan, const ACMFlows *flows, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!plan || !flows || flows->plan != plan || capacity >= (1ull << 31) || n_texts >= (1ull << 31))
+    return 0;
+  return flows_layout (plan, flows, capacity, n_symbols, n_texts).total;
+}
+
+extern "C" int
+acm_gpu_scan_flows_device (ACMPlan *plan, ACMFlows *flows, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, const uint32_t *d_flow,
+                           uint64_t n_texts, ACMRecord *d_records, uint32_t *d_text_id, uint64_t *d_first, uint64_t capacity, uint64_t *d_count,
+                           void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !flows || flows->plan != plan || !d_count || n_texts >= (1ull << 31) || capacity >= (1ull << 31) || (n_symbols && !d_text) ||
+      (capacity && !d_records))
+    return ACM_GPU_E_ARG;
+  const uint32_t keep = flows_keep (plan);
+  if (keep > flows->slot_symbols) /* an update has brought a keyword longer than the slots were made for: never a short carry */
+    return ACM_GPU_E_ARG;
+  if (!d_flow && n_texts > flows->n_flows)
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0) { /* no text, no symbol, no record */
+    if (n_symbols)
+      return ACM_GPU_E_ARG;
+    HIP_TRY (hipSetDevice (plan->device));
+    HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
+    if (d_first)
+      HIP_TRY (hipMemsetAsync (d_first, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  const FlowsLayout L = flows_layout (plan, flows, capacity, n_symbols, n_texts);
+  if (!d_offsets || !d_tmp || tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  if (++flows->seq == 0) { /* the sequence numbers have gone round: no claim of an old call may look like a new one */
+    HIP_TRY (hipMemsetAsync (flows->d_claim, 0, (size_t)flows->n_flows * 4, st));
+    flows->seq = 1;
+  }
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  FlowsK F{};
+  F.text = static_cast<const unsigned char *> (d_text);
+  F.offsets = d_offsets;
+  F.flow = d_flow;
+  F.n_texts = n_texts;
+  F.n_symbols = n_symbols;
+  F.n_flows = flows->n_flows;
+  F.sb = flows->sb;
+  F.keep = keep;
+  F.slot_bytes = flows->slot_bytes;
+  F.carry = flows->d_carry;
+  F.carry_len = flows->d_len;
+  F.claim = flows->d_claim;
+  F.seq = flows->seq;
+  F.head = reinterpret_cast<uint32_t *> (t + L.o_head);
+  F.head_sum = reinterpret_cast<const uint64_t *> (t + L.o_sum);
+  F.xoff = reinterpret_cast<uint64_t *> (t + L.o_xoff);
+  F.expanded = t + L.o_text;
+  F.n_expanded = L.n_expanded;
+  F.ctl = reinterpret_cast<FlowsCtl *> (t + L.o_ctl);
+  F.batch = reinterpret_cast<const BatchCtl *> (t + L.o_batch + batch_layout (plan, capacity, L.n_expanded).o_ctl);
+  F.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+  /* grid-stride kernels with capped grids: one launch size whatever the number of texts and flows */
+  const uint64_t most = (uint64_t)plan->cu_count * 8;
+  auto capped = [&] (uint64_t blocks) { return dim3 ((uint32_t)(blocks < 1 ? 1 : blocks < most ? blocks : most)); };
+  const uint64_t per_text = (n_texts + 2 + FLOWS_THREADS - 1) / FLOWS_THREADS;
+  HIP_TRY (hipMemsetAsync (F.ctl, 0, sizeof (FlowsCtl), st));
+  hipLaunchKernelGGL (flows_check_kernel, capped (per_text), dim3 (FLOWS_THREADS), 0, st, F);
+  HIP_TRY (hipGetLastError ());
+  hipLaunchKernelGGL (flows_head_kernel, capped (per_text), dim3 (FLOWS_THREADS), 0, st, F);
+  HIP_TRY (hipGetLastError ());
+  size_t cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, HeadIterator (F.head, HeadTo64 ()), reinterpret_cast<uint64_t *> (t + L.o_sum),
+                                             (int)(n_texts + 1), st));
+  hipLaunchKernelGGL (flows_xoff_kernel, capped (per_text), dim3 (FLOWS_THREADS), 0, st, F);
+  HIP_TRY (hipGetLastError ());
+  /* the gather: lanes per text by the mean length of a text, 16 bytes a lane and step */
+  F.group_log2 = log2_ceil_capped ((n_symbols * F.sb / n_texts + 15) / 16, 6);
+  const uint64_t gather_blocks = std::max (((n_texts << F.group_log2) + FLOWS_THREADS - 1) / FLOWS_THREADS, n_texts * keep * F.sb / 16 / FLOWS_THREADS + 1);
+  hipLaunchKernelGGL (flows_gather_kernel, capped (gather_blocks), dim3 (FLOWS_THREADS), 0, st, F);
+  HIP_TRY (hipGetLastError ());
+  BatchHeads H{ F.head, d_offsets, n_texts, &F.ctl->bad };
+  const int rc = batch_scan<true> (plan, F.expanded, L.n_expanded, F.xoff, n_texts + 1, d_records, d_text_id, d_first, capacity, d_count, t + L.o_batch,
+                                   L.batch_bytes, stream, &H);
+  if (rc)
+    return rc;
+  F.group_log2 = log2_ceil_capped (flows->slot_bytes / 16, 6);
+  hipLaunchKernelGGL (flows_carry_kernel, capped (((n_texts << F.group_log2) + FLOWS_THREADS - 1) / FLOWS_THREADS), dim3 (FLOWS_THREADS), 0, st, F);
+  HIP_TRY (hipGetLastError ());
+  return ACM_GPU_OK;
+}
+
+extern "C" int
+acm_gpu_scan_flows_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint64_t n_symbols, const uint64_t *offsets, const uint32_t *flow,
+                         uint64_t n_texts, ACMRecord *records, uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found) {
+  if (!plan || !flows || flows->plan != plan || !n_found || n_texts >= (1ull << 31) || capacity >= (1ull << 31) || (capacity && !records) ||
+      !batch_offsets_ok (offsets, n_texts) || offsets[n_texts] != n_symbols || (n_symbols && !text))
+    return ACM_GPU_E_ARG;
+  /* the flow ids, checked here as the device checks them: below n_flows, none twice */
+  if (!flow && n_texts > flows->n_flows)
+    return ACM_GPU_E_ARG;
+  if (flow) {
+    std::vector<uint32_t> ids (flow, flow + n_texts);
+    std::sort (ids.begin (), ids.end ());
+    if ((n_texts && ids.back () >= flows->n_flows) || std::adjacent_find (ids.begin (), ids.end ()) != ids.end ())
+      return ACM_GPU_E_ARG;
+  }
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, tmp_bytes = acm_gpu_scan_flows_tmp_bytes (plan, flows, capacity, n_symbols, n_texts);
+  void *d_text = nullptr, *d_off = nullptr, *d_flow = nullptr, *d_rec = nullptr, *d_tid = nullptr, *d_first = nullptr, *d_tmp = nullptr,
+       *d_count = nullptr;
+  uint64_t found = 0;
+  auto cleanup = [&] () {
+    for (void *p : { d_text, d_off, d_flow, d_rec, d_tid, d_first, d_tmp, d_count })
+      if (p)
+        (void)hipFree (p);
+  };
+#define HOST_TRY(expr)                                                                             \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess) {                                                                        \
+      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
+      cleanup ();                                                                                  \
+      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
+    }                                                                                              \
+  } while (0)
+  HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
+  HOST_TRY (hipMalloc (&d_off, (n_texts + 1) * 8));
+  HOST_TRY (hipMalloc (&d_flow, n_texts ? n_texts * 4 : 16));
+  HOST_TRY (hipMalloc (&d_count, 8));
+  HOST_TRY (hipMalloc (&d_rec, capacity ? capacity * 16 : 16));
+  HOST_TRY (hipMalloc (&d_tid, capacity ? capacity * 4 : 16));
+  HOST_TRY (hipMalloc (&d_first, (n_texts + 1) * 8));
+  HOST_TRY (hipMalloc (&d_tmp, tmp_bytes ? tmp_bytes : 16));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+  if (flow && n_texts)
+    HOST_TRY (hipMemcpy (d_flow, flow, n_texts * 4, hipMemcpyHostToDevice));
+  const int rc = acm_gpu_scan_flows_device (plan, flows, d_text, n_symbols, static_cast<const uint64_t *> (d_off),
+                                            flow ? static_cast<const uint32_t *> (d_flow) : nullptr, n_texts, static_cast<ACMRecord *> (d_rec),
                                             static_cast<uint32_t *> (d_tid), static_cast<uint64_t *> (d_first), capacity,
                                             static_cast<uint64_t *> (d_count), d_tmp, tmp_bytes, nullptr);
   if (rc) {
@@ -4064,6 +4386,49 @@ acm_scan_batch (ACMachine *machine, const void *text, const uint64_t *offsets, u
            : acm_gpu_scan_batch_host (R.plan, text, offsets, n_texts, records, text_id, first, capacity, n_found);
     acm_internal_set_scan_path (machine, R.path);
   }
+  acm_internal_plan_unlock (machine);
+  return rc;
+}
+
+/* acm_scan continued from a cursor (include/acm_gpu.h): the reference's own `const ACState *`, in
+ * and out.  GPU paths: the cursor's spelling (its parent links, as acm_get_match walks them) goes
+ * in front of the text with the emit boundary behind it; the cursor afterwards is a walk with the
+ * product's own acm_match from the root over the last lmax symbols of spelling + text (lmax, not
+ * lmax - 1: the cursor may sit on a state of full depth). */
+extern "C" int
+acm_scan_from (ACMachine *machine, const ACState **cursor, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity,
+               uint64_t *n_found) {
+  if (!machine || !cursor || !*cursor || (*cursor)->machine != machine || !n_found || (n_symbols && !text) || (capacity && !records))
+    return ACM_GPU_E_ARG;
+  ScanRoute R;
+  int rc = scan_route (machine, &R);
+  if (rc)
+    return rc;
+  acm_internal_plan_lock (machine);
+  if (R.path != ACM_SCAN_PATH_CPU_LOOP)
+    rc = route_plan (machine, &R);
+  if (!rc && R.path == ACM_SCAN_PATH_CPU_LOOP)
+    rc = acm_internal_cpu_scan_from (machine, cursor, text, n_symbols, R.said, records, capacity, n_found);
+  else if (!rc) {
+    const uint32_t sb = R.plan->text_sym_bytes;
+    const uint64_t depth = (*cursor)->depth;
+    std::vector<unsigned char> spelling ((size_t)depth * sb);
+    uint64_t k = depth;
+    for (const ACState *s = *cursor; s->parent; s = s->parent)
+      memcpy (spelling.data () + (size_t)--k * sb, s->letter, sb);
+    rc = scan_host_prefixed (R.plan, spelling.data (), depth, text, n_symbols, depth, 0, records, capacity, n_found);
+    if (!rc) {
+      for (uint64_t r = 0; r < *n_found; r++)
+        records[r].end_pos -= depth;
+      const uint64_t all = depth + n_symbols, lmax = (uint64_t)flows_keep (R.plan) + 1;
+      const ACState *s = acm_internal_root (machine);
+      for (uint64_t i = all > lmax ? all - lmax : 0; i < all; i++)
+        (void)acm_match (&s, i < depth ? spelling.data () + (size_t)i * sb : static_cast<const unsigned char *> (text) + (size_t)(i - depth) * sb);
+      *cursor = s;
+    }
+  }
+  if (!rc || rc == ACM_GPU_E_OVERFLOW)
+    acm_internal_set_scan_path (machine, R.path);
   acm_internal_plan_unlock (machine);
   return rc;
 }

@@ -691,13 +691,14 @@ acm_print (ACMachine *machine, FILE *stream, PRINT_TYPE printer) {
   fprintf (stream, "\n");
 }
 
-/* the caller loop over symbols [begin, end) of `text`, from the root; appends behind the `found`
- * records there are and returns the new total (text_id, when given, takes `id` beside every record) */
+/* the caller loop over symbols [begin, end) of `text`, from *state (NULL: from the root); appends
+ * behind the `found` records there are and returns the new total (text_id, when given, takes `id`
+ * beside every record); *state becomes the state the loop ends in */
 static uint64_t
-cpu_loop (const ACMachine *m, const void *text, uint64_t begin, uint64_t end, uint32_t sym_bytes, ACMRecord *records, uint32_t *text_id, uint32_t id,
-          uint64_t capacity, uint64_t found) {
+cpu_loop_from (const ACMachine *m, const struct _ac_state **state, const void *text, uint64_t begin, uint64_t end, uint32_t sym_bytes,
+               ACMRecord *records, uint32_t *text_id, uint32_t id, uint64_t capacity, uint64_t found) {
   const unsigned char *t = text;
-  const struct _ac_state *s = m->root;
+  const struct _ac_state *s = state && *state ? *state : m->root;
   for (uint64_t i = begin; i < end; i++) {
     s = automaton_step (s, t + i * sym_bytes);
     uint32_t nb = LOAD (&s->nb_outputs);
@@ -715,7 +716,15 @@ cpu_loop (const ACMachine *m, const void *text, uint64_t begin, uint64_t end, ui
       nb--;
     }
   }
+  if (state)
+    *state = s;
   return found;
+}
+
+static uint64_t
+cpu_loop (const ACMachine *m, const void *text, uint64_t begin, uint64_t end, uint32_t sym_bytes, ACMRecord *records, uint32_t *text_id, uint32_t id,
+          uint64_t capacity, uint64_t found) {
+  return cpu_loop_from (m, NULL, text, begin, end, sym_bytes, records, text_id, id, capacity, found);
 }
 
 /* The reference's caller loop (examples/test.c:17-23; acm_match aho_corasick.c:434-448, acm_get_match
@@ -756,4 +765,22 @@ acm_internal_cpu_scan_batch (ACMachine *m, const void *text, const uint64_t *off
     first[n_texts] = found;
   *n_found = found;
   return found > capacity ? ACM_GPU_E_OVERFLOW : ACM_GPU_OK;
+}
+
+/* The same loop continued from *cursor (acm_scan_from, include/acm_gpu.h): end_pos = the index in
+ * `text`; *cursor becomes the state the loop ends in, and stays as it is when the records do not fit. */
+int
+acm_internal_cpu_scan_from (ACMachine *m, const ACState **cursor, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records,
+                            uint64_t capacity, uint64_t *n_found) {
+  if (!m || !cursor || !*cursor || !n_found || (n_symbols && !text) || (capacity && !records) || !sym_bytes)
+    return ACM_GPU_E_ARG;
+#ifdef ACM_NMEYER_85
+  acm_internal_refresh (m);
+#endif
+  const struct _ac_state *s = *cursor;
+  *n_found = cpu_loop_from (m, &s, text, 0, n_symbols, sym_bytes, records, NULL, 0, capacity, 0);
+  if (*n_found > capacity)
+    return ACM_GPU_E_OVERFLOW;
+  *cursor = s;
+  return ACM_GPU_OK;
 }

@@ -58,6 +58,9 @@ int acm_internal_cpu_scan (ACMachine *m, const void *text, uint64_t n_symbols, u
 /* the same loop from the root on every text of a batch (acm_scan_batch); offsets[] already checked */
 int acm_internal_cpu_scan_batch (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, ACMRecord *records,
                                  uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found);
+/* the same loop continued from *cursor (acm_scan_from); *cursor is unchanged unless the call returns ACM_GPU_OK */
+int acm_internal_cpu_scan_from (ACMachine *m, const ACState **cursor, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records,
+                                uint64_t capacity, uint64_t *n_found);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

@@ -160,5 +160,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_order.h"
 #include "dev_tiles.h"
 #include "dev_batch.h"
+#include "dev_flows.h"
 
 } // namespace

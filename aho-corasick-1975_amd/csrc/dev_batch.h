@@ -55,6 +55,15 @@ struct BatchK {
   unsigned long long *d_count;
   BatchCtl *ctl;
   unsigned int *error;             /* the plan's device-side flag (acm_gpu_plan_status) */
+  /* HEADS instantiations only (flow scans, dev_flows.h): `offsets` are those of an expanded buffer
+   * whose text t begins with head[t] symbols carried over from earlier calls.  A record is kept iff
+   * it also ends at or behind offsets[t] + head[t]; its end_pos is rebased to base[t], the text's
+   * offset in the caller's buffer.  Only the first n_real texts report (what follows is fill), and
+   * *pre_bad says that the caller's own checks have failed already. */
+  const uint32_t *head;
+  const uint64_t *base;            /* [n_real + 1] */
+  uint64_t n_real;
+  const unsigned int *pre_bad;
 };
 
 /* largest t in [lo, hi] with offsets[t] <= pos; offsets[lo] <= pos is the caller's */
@@ -70,12 +79,13 @@ batch_text_of (const uint64_t *__restrict__ offsets, uint64_t lo, uint64_t hi, u
   return lo;
 }
 
+template <bool HEADS>
 __global__ __launch_bounds__ (BATCH_THREADS) void
 batch_index_kernel (BatchK K) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, me = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   bool bad = false;
   if (me == 0)
-    bad = K.offsets[0] != 0 || K.offsets[K.n_texts] != K.n_symbols;
+    bad = K.offsets[0] != 0 || K.offsets[K.n_texts] != K.n_symbols || (HEADS && *K.pre_bad);
   for (uint64_t t = me; t < K.n_texts; t += stride)
     bad = bad || K.offsets[t] > K.offsets[t + 1];
   if (bad) {
@@ -96,7 +106,7 @@ batch_n (const BatchK &K) {
   return c > K.capacity ? 0 : c;
 }
 
-template <bool WRITE>
+template <bool WRITE, bool HEADS>
 __global__ __launch_bounds__ (BATCH_THREADS) void
 batch_filter_kernel (BatchK K) {
   __shared__ uint32_t kept[BATCH_PER * BATCH_WAVES];
@@ -135,6 +145,13 @@ batch_filter_kernel (BatchK K) {
           const uint64_t t = batch_text_of (K.offsets, lo, hi, pos);
           tid[q] = (uint32_t)t;
           keep[q] = pos + 1 >= K.offsets[t] + rec[q].z; /* the match begins inside its text */
+          if (HEADS) {
+            const uint64_t body = K.offsets[t] + (t < K.n_real ? K.head[t] : 0); /* (read in bounds also when nothing is kept) */
+            keep[q] = keep[q] && t < K.n_real && pos >= body;
+            const uint64_t at = pos - body + (t < K.n_real ? K.base[t] : 0);
+            rec[q].x = (uint32_t)at;
+            rec[q].y = (uint32_t)(at >> 32);
+          }
         }
       }
       const uint64_t m = __ballot (keep[q]);
@@ -172,17 +189,19 @@ batch_filter_kernel (BatchK K) {
   }
 }
 
+template <bool HEADS>
 __global__ __launch_bounds__ (BATCH_THREADS) void
 batch_first_kernel (BatchK K) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, me = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool overflow = K.ctl->overflow != 0;
   const uint64_t n = K.ctl->bad || overflow ? 0 : K.tile_begin[K.n_tiles];
-  if (me == 0 && !overflow)
+  if (me == 0 && (!overflow || (HEADS && K.ctl->bad))) /* (a bad flow call has scanned fill: whatever that found, nothing is reported) */
     *K.d_count = n;
   if (!K.first)
     return;
-  for (uint64_t t = me; t <= K.n_texts; t += stride) {
-    const uint64_t off = K.offsets[t];
+  const uint64_t n_texts = HEADS ? K.n_real : K.n_texts;
+  for (uint64_t t = me; t <= n_texts; t += stride) {
+    const uint64_t off = HEADS ? (K.ctl->bad ? 0 : K.base[t]) : K.offsets[t];
     uint64_t lo = 0, hi = n; /* the first kept record that ends at or behind offsets[t] */
     while (lo < hi) {
       const uint64_t mid = lo + (hi - lo) / 2;
@@ -191,6 +210,6 @@ batch_first_kernel (BatchK K) {
       else
         hi = mid;
     }
-    K.first[t] = t == K.n_texts ? n : lo;
+    K.first[t] = t == n_texts ? n : lo;
   }
 }

@@ -357,6 +357,64 @@ int acm_scan_batch (ACMachine *machine, const void *text, const uint64_t *offset
                     ACMRecord *records, uint32_t *text_id, uint64_t *first,
                     uint64_t capacity, uint64_t *n_found);
 
+/* ------------------------------------------------------------------ flow scans: batch texts that continue earlier ones
+ * The reference's scan state is the caller's cursor: one `const ACState *` per connection, file or
+ * log source, fed a piece whenever one arrives, and a keyword cut by a piece boundary is still found
+ * (aho_corasick.h:47-48,70).  An ACMFlows holds that state for n_flows flows on the plan's device:
+ * per flow its CARRY, the last min (lmax - 1, symbols seen so far) symbols in the caller's symbol
+ * size, and the carry's length -- a spelling, not a state id, so it is valid for every plan kind,
+ * for class and interned plans and for a plan with a delta (lmax is the larger of the two).
+ *
+ * acm_gpu_flows_create: all flows at the root.  The slot width is fixed here (lmax - 1 symbols,
+ * rounded up to whole 16 bytes); when a later acm_gpu_plan_update brings a keyword the slots cannot
+ * serve, the next flow scan returns ACM_GPU_E_ARG -- it never scans with a short carry.
+ * acm_gpu_flows_reset: the flows d_flow_ids[0 .. n) (device memory; NULL: all of them) back to the
+ * root, on `stream`.  Destroy the flows before their plan.
+ *
+ * A flow scan is a batch scan (above: same buffer, offsets[] contract, text_id, first, d_count and
+ * capacity rule) whose text t continues flow f = d_flow[t] (d_flow NULL: text t is flow t, n_texts
+ * <= n_flows).  DEFINITION: let H_f be everything flow f was fed since its creation or reset; text
+ * t yields the records of the caller loop run from the root over H_f followed by text t that END
+ * INSIDE text t, with end_pos = offsets[t] + the index inside text t -- so `length` may exceed the
+ * position inside the text.  Plain canonical order.  Afterwards H_f has grown by text t.  Empty
+ * texts leave their flow as it is, flows that do not appear are untouched.
+ * Every flow id must be below n_flows and no flow may appear twice in one call.  On the device a
+ * violation is handled as bad offsets are: *d_count = 0, acm_gpu_plan_status reports
+ * ACM_GPU_E_INTERNAL, nothing is read or written out of bounds and NO carry changes; the host entry
+ * checks the same on the host (ACM_GPU_E_ARG).
+ * CAPACITY must hold the matches of the scanned buffer, which is the texts with their carries in
+ * front (dev_flows.h).  *d_count > capacity: it is a capacity that suffices, the outputs are
+ * unspecified and no carry has changed: the same call is simply repeated with room.
+ * d_tmp must hold acm_gpu_scan_flows_tmp_bytes (...) bytes: the batch scan's scratch for the WORST
+ * CASE of n_symbols + n_texts * (lmax - 1) symbols plus that many symbols (the texts are copied
+ * behind their carries once) and 20 bytes per text.  n_texts and capacity must be below 2^31.
+ * acm_gpu_scan_flows_device is nothing but launches on `stream`; one call at a time per ACMFlows
+ * and per plan.  acm_gpu_scan_flows_host: the same from host memory, blocking (offsets[n_texts] must
+ * equal n_symbols); ACM_GPU_E_OVERFLOW leaves a capacity that suffices in *n_found. */
+typedef struct ACMFlows ACMFlows;
+int acm_gpu_flows_create (ACMPlan *plan, uint64_t n_flows, ACMFlows **out);
+void acm_gpu_flows_destroy (ACMFlows *flows);
+int acm_gpu_flows_reset (ACMFlows *flows, const uint32_t *d_flow_ids /* NULL: all */, uint64_t n, void *stream);
+size_t acm_gpu_scan_flows_tmp_bytes (const ACMPlan *plan, const ACMFlows *flows, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_flows_device (ACMPlan *plan, ACMFlows *flows, const void *d_text, uint64_t n_symbols,
+                               const uint64_t *d_offsets, const uint32_t *d_flow /* [n_texts], NULL: text t is flow t */,
+                               uint64_t n_texts, ACMRecord *d_records, uint32_t *d_text_id /* may be NULL */,
+                               uint64_t *d_first /* n_texts + 1, may be NULL */, uint64_t capacity, uint64_t *d_count,
+                               void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_flows_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint64_t n_symbols,
+                             const uint64_t *offsets, const uint32_t *flow /* NULL: text t is flow t */, uint64_t n_texts,
+                             ACMRecord *records, uint32_t *text_id, uint64_t *first,
+                             uint64_t capacity, uint64_t *n_found);          /* blocking */
+
+/* The cursor on the machine: acm_scan continued from *cursor, the reference's own `const ACState *`
+ * (acm_initiate gives the root's).  Returns the records of the caller loop continued from *cursor
+ * over text[0 .. n_symbols), end_pos = the index in `text` (so `length` may exceed end_pos + 1);
+ * *cursor afterwards is exactly the state the per-symbol loop would hold, usable with acm_match and
+ * acm_get_match at once -- bulk and per-symbol feeding mix freely.  Same three paths as acm_scan
+ * (acm_scan_path says which ran).  On any error, ACM_GPU_E_OVERFLOW included, *cursor is unchanged. */
+int acm_scan_from (ACMachine *machine, const ACState **cursor, const void *text, uint64_t n_symbols,
+                   ACMRecord *records, uint64_t capacity, uint64_t *n_found);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
