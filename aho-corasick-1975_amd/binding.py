@@ -86,6 +86,7 @@ EXPORTS = [
     "acm_gpu_scan_batch_tmp_bytes", "acm_gpu_scan_batch_device", "acm_gpu_scan_batch_host", "acm_scan_batch",
     "acm_gpu_flows_create", "acm_gpu_flows_destroy", "acm_gpu_flows_reset", "acm_gpu_scan_flows_tmp_bytes", "acm_gpu_scan_flows_device",
     "acm_gpu_scan_flows_host", "acm_scan_from",
+    "acm_gpu_tally_tmp_bytes", "acm_gpu_tally_device", "acm_gpu_tally_form", "acm_gpu_tally_keywords", "acm_gpu_tally_host", "acm_tally",
 ]
 
 
@@ -241,6 +242,18 @@ def lib():
     L.acm_gpu_scan_batch_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
     L.acm_scan_batch.restype = i32
     L.acm_scan_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_tally_tmp_bytes.restype = sz
+    L.acm_gpu_tally_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_tally_device.restype = i32
+    L.acm_gpu_tally_device.argtypes = [vp, vp, u64, u64, vp, u64, u64, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_tally_form.restype = i32
+    L.acm_gpu_tally_form.argtypes = [vp]
+    L.acm_gpu_tally_keywords.restype = u64
+    L.acm_gpu_tally_keywords.argtypes = [vp]
+    L.acm_gpu_tally_host.restype = i32
+    L.acm_gpu_tally_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_tally.restype = i32
+    L.acm_tally.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_gpu_flows_create.restype = i32
     L.acm_gpu_flows_create.argtypes = [vp, u64, C.POINTER(vp)]
     L.acm_gpu_flows_destroy.restype = None
@@ -572,6 +585,19 @@ class Machine:
                 res.append(r)
             return res
 
+    def tally(self, text, tally=None):
+        """acm_tally(): how often every keyword occurs in `text`.  Returns (np.uint64 array with one
+        counter per keyword, number of matches).  `tally` (an earlier call's array, at least
+        nb_keywords entries) is ADDED TO in place; keyword(k) gives the spelling of counter k."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        if tally is None:
+            tally = np.zeros(self.nb_keywords, dtype=np.uint64)
+        assert tally.dtype == np.uint64 and tally.flags.c_contiguous
+        total = C.c_uint64(0)
+        _check(self.L.acm_tally(self.handle, t.ctypes.data, t.size * t.itemsize // self.sym_size, tally.ctypes.data, tally.size,
+                                C.byref(total)), "acm_tally")
+        return tally, int(total.value)
+
 
 class Plan:
     """Device-resident flattened automaton (ACMPlan).  Scans take torch CUDA tensors (device
@@ -766,6 +792,51 @@ class Plan:
                 continue
             _check(rc, "acm_gpu_scan_batch_host")
             return out[:n.value], tid[:n.value], first
+
+    @property
+    def tally_form(self):
+        """acm_gpu_tally_form(): 1 = the plan's tally kernel counts in LDS, 2 = with global atomics."""
+        return int(lib().acm_gpu_tally_form(self.h))
+
+    @property
+    def tally_keywords(self):
+        """acm_gpu_tally_keywords(): the counters a tally of this plan needs."""
+        return int(lib().acm_gpu_tally_keywords(self.h))
+
+    def tally(self, text, n_symbols=None, emit_from=0, tally=None, window=None, capacity=None):
+        """acm_gpu_tally_device(): per-keyword match counts of a device tensor; no record leaves the
+        device.  `tally` (an int64 device tensor with at least tally_keywords entries; None: a zeroed
+        one) is ADDED TO.  `window` (symbols, a multiple of 16) and `capacity` (records per window)
+        default to 16 Mi symbols and 1 Mi records.  Returns (tally, total, need): need > capacity says
+        that a window overflowed -- tally is untouched and total is 0 then, and a capacity of `need`
+        suffices for the same window.  Synchronises to read total and need."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        window = int(window) if window is not None else 1 << 24
+        capacity = int(capacity) if capacity is not None else 1 << 20
+        if tally is None:
+            tally = torch.zeros(max(self.tally_keywords, 1), dtype=torch.int64, device=text.device)
+        assert tally.is_cuda and tally.is_contiguous() and tally.dtype == torch.int64
+        out = torch.zeros(2, dtype=torch.int64, device=text.device)
+        tb = lib().acm_gpu_tally_tmp_bytes(self.h, window, capacity)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        _check(lib().acm_gpu_tally_device(self.h, text.data_ptr(), n_symbols, emit_from, tally.data_ptr(), tally.numel(), window, capacity,
+                                          out.data_ptr(), out.data_ptr() + 8, tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_tally_device")
+        total, need = (int(x) for x in out.cpu())
+        return tally, total, need
+
+    def tally_host(self, text):
+        """acm_gpu_tally_host(): numpy in, (np.uint64 counters, total) out, through the C ABI only (no
+        torch).  The call sizes its windows itself and never overflows."""
+        t = np.ascontiguousarray(text)
+        tally = np.zeros(max(self.tally_keywords, 1), dtype=np.uint64)
+        total = C.c_uint64(0)
+        _check(lib().acm_gpu_tally_host(self.h, t.ctypes.data, t.size * t.itemsize // self.sym_size, tally.ctypes.data, tally.size,
+                                        C.byref(total)), "acm_gpu_tally_host")
+        return tally, int(total.value)
 
     def stream(self, max_piece_symbols, record_capacity):
         return Stream(self, max_piece_symbols, record_capacity)

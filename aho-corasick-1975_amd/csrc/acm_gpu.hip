@@ -3685,6 +3685,199 @@ acm_gpu_scan_flows_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint6
 #undef HOST_TRY
 }
 
+/* ------------------------------------------------------------------ per-keyword tallies (include/acm_gpu.h, dev_tally.h)
+ * The record scan of the text, window by window into the caller's scratch, and a histogram pass
+ * over every window's records; the caller's counters take the sums at the end, all or nothing. */
+namespace {
+struct TallyLayout {
+  size_t o_ctl = 0, o_hist = 0, o_count = 0, o_rec = 0, total = 0;
+};
+TallyLayout
+tally_layout (const ACMPlan *plan, uint64_t capacity) {
+  TallyLayout L;
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (TallyCtl));
+  L.o_hist = blob_reserve (cur, ((size_t)plan->covered_keywords + 1) * 8);
+  L.o_count = blob_reserve (cur, 8);
+  L.o_rec = blob_reserve (cur, (size_t)capacity * sizeof (ACMRecord));
+  L.total = cur + 256;
+  return L;
+}
+
+/* ACM_GPU_TALLY=global: every plan takes the form of the big dictionaries (experiments, tests) */
+bool
+tally_lds_form (const ACMPlan *plan) {
+  const bool global = getenv ("ACM_GPU_TALLY") && strcmp (getenv ("ACM_GPU_TALLY"), "global") == 0;
+  return !global && plan->covered_keywords <= TALLY_LDS_KEYWORDS;
+}
+
+/* M of the capacity bound: most records one position can have, the plan's and its delta's.  A
+ * start-parallel plan that is edited in place does not keep finfo.max_outputs up to date: the
+ * keywords that end at one position have different lengths, so lmax bounds their number. */
+uint64_t
+tally_max_outputs (const ACMPlan *plan) {
+  uint64_t m = 0;
+  for (const ACMPlan *p : { plan, static_cast<const ACMPlan *> (plan->delta) })
+    if (p)
+      m += p->mir ? std::min (p->finfo.lmax, p->finfo.n_keywords) : p->finfo.max_outputs;
+  return m ? m : 1;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_tally_form (const ACMPlan *plan) {
+  if (!plan)
+    return ACM_GPU_E_ARG;
+  return tally_lds_form (plan) ? ACM_GPU_TALLY_FORM_LDS : ACM_GPU_TALLY_FORM_GLOBAL;
+}
+
+extern "C" uint64_t
+acm_gpu_tally_keywords (const ACMPlan *plan) {
+  return plan ? plan->covered_keywords : 0;
+}
+
+extern "C" size_t
+acm_gpu_tally_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t capacity) {
+  (void)window_symbols; /* (what a window's scan needs beside its records belongs to the plan) */
+  if (!plan || capacity == 0 || capacity >= (1ull << 31))
+    return 0;
+  return tally_layout (plan, capacity).total;
+}
+
+extern "C" int
+acm_gpu_tally_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t emit_from, uint64_t *d_tally, uint64_t n_keywords,
+                      uint64_t window_symbols, uint64_t capacity, uint64_t *d_total, uint64_t *d_need, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_tally || !d_total || !d_need || !d_tmp || (n_symbols && !d_text) || window_symbols == 0 || window_symbols % 16 ||
+      capacity == 0 || capacity >= (1ull << 31) || n_keywords < plan->covered_keywords)
+    return ACM_GPU_E_ARG;
+  const TallyLayout L = tally_layout (plan, capacity);
+  if (tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  uint64_t *d_count = reinterpret_cast<uint64_t *> (t + L.o_count);
+  ACMRecord *rec = reinterpret_cast<ACMRecord *> (t + L.o_rec);
+  HIP_TRY (hipMemsetAsync (t, 0, L.o_rec, st)); /* control words, histogram, count */
+  HIP_TRY (hipMemsetAsync (d_total, 0, 8, st));
+
+  /* window w owns the matches that end in it and starts from the root lmax - 1 symbols early,
+   * rounded down to a 16-byte boundary of the text (acm_gpu_multi_shard_bounds' rule: the kernels
+   * keep their alignment) */
+  const uint32_t sb = plan->text_sym_bytes;
+  const uint64_t per16 = 16 / sb ? 16 / sb : 1, warm = flows_keep (plan);
+  for (uint64_t wb = emit_from / window_symbols * window_symbols; wb < n_symbols; wb += window_symbols) {
+    const uint64_t we = n_symbols - wb > window_symbols ? wb + window_symbols : n_symbols;
+    const uint64_t ef = emit_from > wb ? emit_from : wb;
+    const uint64_t rb = (wb > warm ? wb - warm : 0) / per16 * per16;
+    int rc = scan_plan<false> (plan, static_cast<const unsigned char *> (d_text) + rb * sb, we - rb, ef - rb, 0, rec, capacity, d_count, st);
+    if (rc)
+      return rc;
+    TallyK K{};
+    K.rec = rec;
+    K.capacity = capacity;
+    K.n_dev = reinterpret_cast<const unsigned long long *> (d_count);
+    K.hist = reinterpret_cast<unsigned long long *> (t + L.o_hist);
+    K.n_keywords = plan->covered_keywords;
+    K.ctl = reinterpret_cast<TallyCtl *> (t + L.o_ctl);
+    K.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+    /* grid-stride, two blocks per CU (what the LDS form's counters allow), whatever the scan found */
+    const dim3 grid ((uint32_t)plan->cu_count * 2);
+    if (tally_lds_form (plan))
+      hipLaunchKernelGGL (tally_records_kernel<true>, grid, dim3 (TALLY_THREADS), (size_t)K.n_keywords * 4, st, K);
+    else
+      hipLaunchKernelGGL (tally_records_kernel<false>, grid, dim3 (TALLY_THREADS), 0, st, K);
+    HIP_TRY (hipGetLastError ());
+  }
+  TallyK K{};
+  K.capacity = capacity;
+  K.hist = reinterpret_cast<unsigned long long *> (t + L.o_hist);
+  K.n_keywords = plan->covered_keywords;
+  K.ctl = reinterpret_cast<TallyCtl *> (t + L.o_ctl);
+  K.d_tally = reinterpret_cast<unsigned long long *> (d_tally);
+  K.d_total = reinterpret_cast<unsigned long long *> (d_total);
+  K.d_need = reinterpret_cast<unsigned long long *> (d_need);
+  const uint64_t blocks = ((uint64_t)K.n_keywords + TALLY_THREADS - 1) / TALLY_THREADS, most = (uint64_t)plan->cu_count * 8;
+  hipLaunchKernelGGL (tally_finish_kernel, dim3 ((uint32_t)(blocks < 1 ? 1 : blocks < most ? blocks : most)), dim3 (TALLY_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  return ACM_GPU_OK;
+}
+
+extern "C" int
+acm_gpu_tally_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t *tally, uint64_t n_keywords, uint64_t *total) {
+  if (!plan || !tally || (n_symbols && !text) || n_keywords < plan->covered_keywords)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  /* defaults: windows of 32 Mi symbols, room for 2 Mi records (32 MiB) -- one match per 16 symbols;
+   * ACM_GPU_TALLY_CAPACITY=<records> sets another room (tests of the second attempt) */
+  uint64_t window = 1ull << 25, capacity = 1ull << 21;
+  if (const char *e = getenv ("ACM_GPU_TALLY_CAPACITY"))
+    if (atoll (e) > 0 && (uint64_t)atoll (e) < (1ull << 31))
+      capacity = (uint64_t)atoll (e);
+  /* (a short text cannot have more than n x M records) */
+  if (n_symbols < (1ull << 31) / tally_max_outputs (plan) && n_symbols * tally_max_outputs (plan) < capacity)
+    capacity = n_symbols ? n_symbols * tally_max_outputs (plan) : 1;
+  const uint32_t kw = plan->covered_keywords;
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
+  void *d_text = nullptr, *d_tally = nullptr, *d_out = nullptr, *d_tmp = nullptr;
+  auto cleanup = [&] () {
+    for (void *p : { d_text, d_tally, d_out, d_tmp })
+      if (p)
+        (void)hipFree (p);
+  };
+#define HOST_TRY(expr)                                                                             \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess) {                                                                        \
+      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
+      cleanup ();                                                                                  \
+      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
+    }                                                                                              \
+  } while (0)
+  HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
+  HOST_TRY (hipMalloc (&d_tally, ((size_t)kw + 1) * 8));
+  HOST_TRY (hipMalloc (&d_out, 16)); /* total, need */
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  HOST_TRY (hipMemset (d_tally, 0, ((size_t)kw + 1) * 8));
+  uint64_t out[2] = { 0, 0 };
+  for (int attempt = 0; attempt < 2; attempt++) {
+    const size_t tmp_bytes = acm_gpu_tally_tmp_bytes (plan, window, capacity);
+    HOST_TRY (hipMalloc (&d_tmp, tmp_bytes));
+    const int rc = acm_gpu_tally_device (plan, d_text, n_symbols, 0, static_cast<uint64_t *> (d_tally), kw, window, capacity,
+                                         static_cast<uint64_t *> (d_out), static_cast<uint64_t *> (d_out) + 1, d_tmp, tmp_bytes, nullptr);
+    if (rc) {
+      (void)hipDeviceSynchronize ();
+      cleanup ();
+      return rc;
+    }
+    HOST_TRY (hipMemcpy (out, d_out, 16, hipMemcpyDeviceToHost));
+    HOST_TRY (hipFree (d_tmp));
+    d_tmp = nullptr;
+    if (out[1] <= capacity)
+      break;
+    if (attempt == 1) { /* (W x M records cannot be exceeded: never expected) */
+      cleanup ();
+      return ACM_GPU_E_INTERNAL;
+    }
+    /* a window of W symbols has at most W x M records: the second attempt cannot overflow */
+    const uint64_t m = tally_max_outputs (plan);
+    if (capacity / m < 16)
+      capacity = 16 * m;
+    window = capacity / m / 16 * 16;
+  }
+  std::vector<uint64_t> add ((size_t)kw + 1);
+  HOST_TRY (hipMemcpy (add.data (), d_tally, (size_t)kw * 8, hipMemcpyDeviceToHost));
+  HOST_TRY (hipDeviceSynchronize ());
+  cleanup ();
+  for (uint32_t k = 0; k < kw; k++)
+    tally[k] += add[k];
+  if (total)
+    *total = out[0];
+  return ACM_GPU_OK;
+#undef HOST_TRY
+}
+
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
 extern "C" int
 acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint32_t *len_bits, uint32_t *kw_bits) {
@@ -4385,6 +4578,28 @@ acm_scan_batch (ACMachine *machine, const void *text, const uint64_t *offsets, u
            ? acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, R.said, records, text_id, first, capacity, n_found)
            : acm_gpu_scan_batch_host (R.plan, text, offsets, n_texts, records, text_id, first, capacity, n_found);
     acm_internal_set_scan_path (machine, R.path);
+  }
+  acm_internal_plan_unlock (machine);
+  return rc;
+}
+
+/* the per-keyword tally (include/acm_gpu.h): same route, same cached plan, same lock */
+extern "C" int
+acm_tally (ACMachine *machine, const void *text, uint64_t n_symbols, uint64_t *tally, uint64_t n_keywords, uint64_t *total) {
+  if (!machine || !tally || (n_symbols && !text))
+    return ACM_GPU_E_ARG;
+  ScanRoute R;
+  int rc = scan_route (machine, &R);
+  if (rc)
+    return rc;
+  acm_internal_plan_lock (machine);
+  if (R.path != ACM_SCAN_PATH_CPU_LOOP)
+    rc = route_plan (machine, &R);
+  if (!rc) {
+    rc = R.path == ACM_SCAN_PATH_CPU_LOOP ? acm_internal_cpu_tally (machine, text, n_symbols, R.said, tally, n_keywords, total)
+                                          : acm_gpu_tally_host (R.plan, text, n_symbols, tally, n_keywords, total);
+    if (!rc)
+      acm_internal_set_scan_path (machine, R.path);
   }
   acm_internal_plan_unlock (machine);
   return rc;

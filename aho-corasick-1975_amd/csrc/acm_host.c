@@ -784,3 +784,32 @@ acm_internal_cpu_scan_from (ACMachine *m, const ACState **cursor, const void *te
   *cursor = s;
   return ACM_GPU_OK;
 }
+
+/* The same loop for acm_tally (include/acm_gpu.h): what the reference's second example does with its
+ * matches (examples/aho_corasick_generic_test.c:168-210, `(*(size_t *) m3.value)++`), per keyword id. */
+int
+acm_internal_cpu_tally (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t *tally, uint64_t n_keywords,
+                        uint64_t *total) {
+  if (!m || !tally || (n_symbols && !text) || !sym_bytes || n_keywords < acm_nb_keywords (m))
+    return ACM_GPU_E_ARG;
+#ifdef ACM_NMEYER_85
+  acm_internal_refresh (m);
+#endif
+  const unsigned char *t = text;
+  const struct _ac_state *s = m->root;
+  uint64_t found = 0;
+  for (uint64_t i = 0; i < n_symbols; i++) {
+    s = automaton_step (s, t + i * sym_bytes);
+    uint32_t nb = LOAD (&s->nb_outputs);
+    for (const struct _ac_state *o = s; nb; o = LOAD (&o->fail)) {
+      if (!LOAD (&o->terminal))
+        continue;
+      if (o->rank < n_keywords) /* (a keyword inserted by another thread since the check above is not counted) */
+        tally[o->rank]++, found++;
+      nb--;
+    }
+  }
+  if (total)
+    *total = found;
+  return ACM_GPU_OK;
+}

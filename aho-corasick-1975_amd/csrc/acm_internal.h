@@ -61,6 +61,10 @@ int acm_internal_cpu_scan_batch (ACMachine *m, const void *text, const uint64_t 
 /* the same loop continued from *cursor (acm_scan_from); *cursor is unchanged unless the call returns ACM_GPU_OK */
 int acm_internal_cpu_scan_from (ACMachine *m, const ACState **cursor, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records,
                                 uint64_t capacity, uint64_t *n_found);
+/* the same loop, counting per keyword instead of recording (acm_tally): tally[keyword_id] += 1 per match, *total (may be
+ * NULL) = their number; ACM_GPU_E_ARG, with nothing counted, when n_keywords is below the machine's number of keywords */
+int acm_internal_cpu_tally (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t *tally, uint64_t n_keywords,
+                            uint64_t *total);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

@@ -161,5 +161,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_tiles.h"
 #include "dev_batch.h"
 #include "dev_flows.h"
+#include "dev_tally.h"
 
 } // namespace

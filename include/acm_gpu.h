@@ -415,6 +415,70 @@ int acm_gpu_scan_flows_host (ACMPlan *plan, ACMFlows *flows, const void *text, u
 int acm_scan_from (ACMachine *machine, const ACState **cursor, const void *text, uint64_t n_symbols,
                    ACMRecord *records, uint64_t capacity, uint64_t *n_found);
 
+/* ------------------------------------------------------------------ per-keyword tallies
+ * What the reference's callers do with their matches above all: count how often every keyword occurs
+ * (examples/aho_corasick_generic_test.c:168-210 runs `(*(size_t *) m3.value)++` for every match; the
+ * README's timings are for "find (and count occurencies of) those keywords").  The answer is one
+ * counter per keyword; no record leaves the device and no record capacity for the whole text has to
+ * be guessed.
+ *
+ * DEFINITION: tally[k] grows by the number of records of the caller loop over text[0 .. n_symbols)
+ * with keyword_id == k and end_pos >= emit_from; `total` is their number -- what acm_gpu_count_device
+ * reports, and the sum of the increments.  The counters are ADDED TO, never cleared: a caller zeroes
+ * them once and then feeds many texts (as the reference's `value`s keep counting).
+ *
+ * acm_gpu_tally_device: the text is cut into windows of window_symbols symbols (a multiple of 16,
+ * greater than 0).  Window w owns the matches that END in it; its scan starts from the root lmax - 1
+ * symbols earlier (lmax: the larger of the plan's and its delta's), rounded down to a 16-byte
+ * boundary of the text -- acm_gpu_multi_shard_bounds' rule.  Windows that lie wholly in front of
+ * emit_from are skipped.  Every window is scanned as acm_gpu_scan_device scans (any plan kind, a
+ * pending delta included) into `capacity` records inside d_tmp and tallied there (dev_tally.h).
+ * CAPACITY is per WINDOW, greater than 0 and below 2^31.  A window of W symbols has at most W x M
+ * records, M = the sum of the plan's and its delta's ACMFlatInfo::max_outputs: capacity >=
+ * window_symbols x M cannot overflow.  Outputs, all device memory, valid when `stream` has passed:
+ *     no window found more than `capacity` records:  d_tally[k] += the increments, *d_total = their
+ *         sum, *d_need = the largest record count of a window (<= capacity);
+ *     some window did:  d_tally is left EXACTLY as it was (all or nothing: the counters accumulate
+ *         over calls, an overflowing call must not leave half a text in them), *d_total = 0,
+ *         *d_need = the largest record count of a window (> capacity): a capacity that suffices for
+ *         this window size.
+ * n_keywords = the entries of d_tally, at least the number of keywords the plan and its delta report
+ * (acm_gpu_tally_keywords: acm_nb_keywords of the machine when the plan was made or last updated),
+ * else ACM_GPU_E_ARG.
+ * d_tmp must hold acm_gpu_tally_tmp_bytes (plan, window_symbols, capacity) bytes (16 per record of
+ * capacity, 8 per keyword).  The call only queues work on `stream`; one scan at a time per plan as
+ * ever, and not while a stream (acm_gpu_stream_*) is open on it.  A keyword id in a record that is
+ * no keyword of the plan (never expected) is not counted and makes acm_gpu_plan_status report
+ * ACM_GPU_E_INTERNAL.
+ * acm_gpu_tally_form: which of dev_tally.h's two kernel forms the plan's tallies take -- counters in
+ * LDS for dictionaries of up to 16,384 keywords, global atomics beyond that or when the environment
+ * says ACM_GPU_TALLY=global.
+ * acm_gpu_tally_host: the same from host memory, blocking, emit_from = 0.  It picks the window and
+ * the capacity itself: windows of 32 Mi symbols and room for 2 Mi records (32 MiB; less for a text
+ * that cannot have that many; ACM_GPU_TALLY_CAPACITY=<records> in the environment sets another room).
+ * It never returns ACM_GPU_E_OVERFLOW: when a window held more, the call is repeated once with
+ * window_symbols = capacity / M rounded down to a multiple of 16 (the capacity grown to 16 x M when
+ * that would be 0), which cannot overflow by the bound above.  `total` may be NULL.
+ * acm_tally: the call on the machine itself, total over machines exactly as acm_scan is (same three
+ * paths, same cached plan and acm_gpu_plan_update, acm_scan_path says which ran): the GPU paths run
+ * acm_gpu_tally_host, ACM_SCAN_PATH_CPU_LOOP runs the caller loop on the host and increments the
+ * counters there.  A missing device stays an error, never a fallback.  acm_get_keyword turns an
+ * index of `tally` back into the keyword's spelling and value. */
+#define ACM_GPU_TALLY_FORM_LDS 1
+#define ACM_GPU_TALLY_FORM_GLOBAL 2
+size_t acm_gpu_tally_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t capacity);
+int acm_gpu_tally_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t emit_from,
+                          uint64_t *d_tally, uint64_t n_keywords,
+                          uint64_t window_symbols, uint64_t capacity,
+                          uint64_t *d_total, uint64_t *d_need,
+                          void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_tally_form (const ACMPlan *plan);
+uint64_t acm_gpu_tally_keywords (const ACMPlan *plan);
+int acm_gpu_tally_host (ACMPlan *plan, const void *text, uint64_t n_symbols,
+                        uint64_t *tally, uint64_t n_keywords, uint64_t *total);   /* blocking */
+int acm_tally (ACMachine *machine, const void *text, uint64_t n_symbols,
+               uint64_t *tally, uint64_t n_keywords, uint64_t *total);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
