@@ -87,6 +87,8 @@ EXPORTS = [
     "acm_gpu_flows_create", "acm_gpu_flows_destroy", "acm_gpu_flows_reset", "acm_gpu_scan_flows_tmp_bytes", "acm_gpu_scan_flows_device",
     "acm_gpu_scan_flows_host", "acm_scan_from",
     "acm_gpu_tally_tmp_bytes", "acm_gpu_tally_device", "acm_gpu_tally_form", "acm_gpu_tally_keywords", "acm_gpu_tally_host", "acm_tally",
+    "acm_select_records", "acm_gpu_select_tmp_bytes", "acm_gpu_select_records_device", "acm_gpu_select_form",
+    "acm_gpu_scan_select_tmp_bytes", "acm_gpu_scan_select_device", "acm_gpu_scan_select_host", "acm_select",
 ]
 
 
@@ -254,6 +256,22 @@ def lib():
     L.acm_gpu_tally_host.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_tally.restype = i32
     L.acm_tally.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_select_records.restype = u64
+    L.acm_select_records.argtypes = [vp, u64]
+    L.acm_gpu_select_tmp_bytes.restype = sz
+    L.acm_gpu_select_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_select_records_device.restype = i32
+    L.acm_gpu_select_records_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_select_form.restype = i32
+    L.acm_gpu_select_form.argtypes = [vp]
+    L.acm_gpu_scan_select_tmp_bytes.restype = sz
+    L.acm_gpu_scan_select_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_scan_select_device.restype = i32
+    L.acm_gpu_scan_select_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_select_host.restype = i32
+    L.acm_gpu_scan_select_host.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
+    L.acm_select.restype = i32
+    L.acm_select.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_gpu_flows_create.restype = i32
     L.acm_gpu_flows_create.argtypes = [vp, u64, C.POINTER(vp)]
     L.acm_gpu_flows_destroy.restype = None
@@ -280,6 +298,14 @@ def _check(rc, what):
 
 
 _SYM_DTYPE = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
+
+
+def select_records(array):
+    """acm_select_records(): the leftmost-longest non-overlapping records of `array` (RECORD_DTYPE, in
+    canonical order), by the sequential pass on the host.  Returns a new array; `array` is not changed."""
+    a = np.array(array, dtype=RECORD_DTYPE, copy=True).reshape(-1)
+    n = lib().acm_select_records(a.ctypes.data if a.size else None, a.size)
+    return a[:n]
 
 
 class FlatTables:
@@ -598,6 +624,23 @@ class Machine:
                                 C.byref(total)), "acm_tally")
         return tally, int(total.value)
 
+    def select(self, text, capacity=None):
+        """acm_select(): the leftmost-longest non-overlapping matches of `text` in canonical order --
+        the one tiling a replacer, a redactor or a tokeniser acts on.  `capacity` must hold ALL
+        matches (they are found first); by default an overflow is repeated once with the size the
+        call reports."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        cap = int(capacity) if capacity is not None else max(1024, t.size // 64)
+        for attempt in (0, 1):
+            out = np.zeros(cap, dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            rc = self.L.acm_select(self.handle, t.ctypes.data, t.size * t.itemsize // self.sym_size, out.ctypes.data, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_select")
+            return out[:n.value]
+
 
 class Plan:
     """Device-resident flattened automaton (ACMPlan).  Scans take torch CUDA tensors (device
@@ -837,6 +880,68 @@ class Plan:
         _check(lib().acm_gpu_tally_host(self.h, t.ctypes.data, t.size * t.itemsize // self.sym_size, tally.ctypes.data, tally.size,
                                         C.byref(total)), "acm_gpu_tally_host")
         return tally, int(total.value)
+
+    @property
+    def select_form(self):
+        """acm_gpu_select_form(): 1 = the plan's selections go by tiles of candidates in LDS, 2 = by the
+        walk through global memory (a keyword longer than a tile, or ACM_GPU_SELECT=walk)."""
+        return int(lib().acm_gpu_select_form(self.h))
+
+    def select_records(self, records, n, pos_lo, span, out=None):
+        """acm_gpu_select_records_device(): SELECT of the first n records of `records` (an int64
+        [capacity, 2] device tensor in canonical order, every start and end in [pos_lo, pos_lo +
+        span)) into `out` (None: a new tensor; may be `records` itself).  Returns (out, count): the
+        selected records are out[:count].  Synchronises to read the count."""
+        import torch
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64
+        n = int(n)
+        if out is None:
+            out = torch.empty((max(n, 1), 2), dtype=torch.int64, device=records.device)
+        assert out.is_cuda and out.is_contiguous() and out.shape[0] >= n and records.shape[0] >= n
+        count = torch.zeros(1, dtype=torch.int64, device=records.device)
+        tb = lib().acm_gpu_select_tmp_bytes(self.h, n, span)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
+        _check(lib().acm_gpu_select_records_device(self.h, records.data_ptr(), n, None, pos_lo, span, out.data_ptr(), count.data_ptr(),
+                                                   tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_select_records_device")
+        return out, int(count.item())
+
+    def scan_select(self, text, n_symbols=None, pos_base=0, capacity=None, records=None, count=None, tmp=None):
+        """acm_gpu_scan_select_device(): the ordered scan of a device tensor and the leftmost-longest
+        selection of its records, queued on the current stream.  Returns (records, count, tmp):
+        records[:count] is the selection when count <= capacity; a greater count is the number of ALL
+        matches, the capacity the call needs."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        if records is None:
+            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+            records = torch.empty((cap, 2), dtype=torch.int64, device=text.device)
+        if count is None:
+            count = torch.zeros(1, dtype=torch.int64, device=text.device)
+        tb = lib().acm_gpu_scan_select_tmp_bytes(self.h, records.shape[0], n_symbols)
+        if tmp is None or tmp.numel() < tb:
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        _check(lib().acm_gpu_scan_select_device(self.h, text.data_ptr(), n_symbols, pos_base, records.data_ptr(), records.shape[0],
+                                                count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_scan_select_device")
+        return records, count, tmp
+
+    def scan_select_host(self, text, pos_base=0, capacity=None):
+        """acm_gpu_scan_select_host(): numpy in, the selected records out, through the C ABI only (no
+        torch); an overflow is repeated once with the size the call reports."""
+        t = np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
+        for attempt in (0, 1):
+            out = np.zeros(cap, dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            rc = lib().acm_gpu_scan_select_host(self.h, t.ctypes.data, n_sym, pos_base, out.ctypes.data, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_gpu_scan_select_host")
+            return out[:n.value]
 
     def stream(self, max_piece_symbols, record_capacity):
         return Stream(self, max_piece_symbols, record_capacity)

@@ -3878,6 +3878,232 @@ acm_gpu_tally_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_
 #undef HOST_TRY
 }
 
+/* ------------------------------------------------------------------ leftmost-longest selection (include/acm_gpu.h, dev_select.h)
+ * The passes over a record set in canonical order; acm_gpu_scan_select_device runs them behind the
+ * ordered scan. */
+namespace {
+struct SelectLayout {
+  uint64_t n_chunks = 0;
+  size_t o_ctl = 0, o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, o_map = 0, o_entry = 0, o_base = 0, o_keyed = 0, o_work = 0, work_bytes = 0,
+         total = 0;
+};
+/* nothing here depends on the environment: the maps and the tiles' words are sized for every T */
+SelectLayout
+select_layout (const ACMPlan *plan, uint64_t capacity, uint64_t span) {
+  SelectLayout L;
+  L.n_chunks = (capacity + SELECT_CHUNK - 1) / SELECT_CHUNK;
+  size_t cub = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, cub, static_cast<uint32_t *> (nullptr), static_cast<uint32_t *> (nullptr), (int)(L.n_chunks + 1), nullptr);
+  L.cub_bytes = cub;
+  /* the order pass's scratch; the candidates take its place when the order is made */
+  L.work_bytes = std::max (acm_gpu_order_tmp_bytes (plan, capacity, span), (size_t)capacity * sizeof (ACMRecord) + 256);
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (SelectCtl));
+  L.o_count = blob_reserve (cur, (L.n_chunks + 1) * 4);
+  L.o_begin = blob_reserve (cur, (L.n_chunks + 1) * 4);
+  L.o_cub = blob_reserve (cur, cub + 16);
+  L.o_map = blob_reserve (cur, ((size_t)capacity + SELECT_TILE_MAX) * 4); /* tiles x E <= capacity + T words */
+  L.o_entry = blob_reserve (cur, ((size_t)capacity / SELECT_TILE_MIN + 1) * 4);
+  L.o_base = blob_reserve (cur, ((size_t)capacity / SELECT_TILE_MIN + 1) * 4);
+  L.o_keyed = blob_reserve (cur, (size_t)(capacity ? capacity : 1) * sizeof (ACMRecord));
+  L.o_work = blob_reserve (cur, L.work_bytes);
+  L.total = cur + 256;
+  return L;
+}
+
+uint32_t
+select_lmax (const ACMPlan *plan) {
+  return flows_keep (plan) + 1;
+}
+
+/* ACM_GPU_SELECT_TILE=<candidates>: T (tests; read at every call) */
+uint32_t
+select_tile (void) {
+  const int t = env_int ("ACM_GPU_SELECT_TILE", (int)SELECT_TILE_DEFAULT);
+  return t >= (int)SELECT_TILE_MIN && t <= (int)SELECT_TILE_MAX ? (uint32_t)t : SELECT_TILE_DEFAULT;
+}
+
+/* ACM_GPU_SELECT=walk: every plan takes the general form (experiments, tests) */
+bool
+select_tiled_form (const ACMPlan *plan) {
+  const bool walk = getenv ("ACM_GPU_SELECT") && strcmp (getenv ("ACM_GPU_SELECT"), "walk") == 0;
+  return !walk && select_lmax (plan) <= select_tile ();
+}
+} // namespace
+
+extern "C" int
+acm_gpu_select_form (const ACMPlan *plan) {
+  if (!plan)
+    return ACM_GPU_E_ARG;
+  return select_tiled_form (plan) ? ACM_GPU_SELECT_FORM_TILED : ACM_GPU_SELECT_FORM_WALK;
+}
+
+extern "C" size_t
+acm_gpu_select_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t span) {
+  if (!plan || capacity >= (1ull << 31))
+    return 0;
+  return select_layout (plan, capacity, span).total;
+}
+
+extern "C" int
+acm_gpu_select_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, uint64_t pos_lo, uint64_t span,
+                               ACMRecord *d_out, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || n >= (1ull << 31) || (n && (!d_records || !d_out || !d_tmp || span == 0)))
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n == 0) { /* no room, no record: a count that came in stays (it says what room the records need) */
+    HIP_TRY (hipSetDevice (plan->device));
+    if (!d_n)
+      HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
+    else if (d_n != d_count)
+      HIP_TRY (hipMemcpyAsync (d_count, d_n, 8, hipMemcpyDeviceToDevice, st));
+    return ACM_GPU_OK;
+  }
+  const SelectLayout L = select_layout (plan, n, span);
+  if (tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  SelectK K{};
+  K.in = d_records;
+  K.capacity = n;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.pos_lo = pos_lo;
+  K.span = span;
+  K.lmax = select_lmax (plan);
+  K.T = select_tile ();
+  K.E = K.lmax < K.T ? K.lmax : K.T;
+  K.keyed = reinterpret_cast<ACMRecord *> (t + L.o_keyed);
+  K.chunk_count = reinterpret_cast<uint32_t *> (t + L.o_count);
+  K.chunk_begin = reinterpret_cast<const uint32_t *> (t + L.o_begin);
+  K.n_chunks = L.n_chunks;
+  K.cand = reinterpret_cast<ACMRecord *> (t + L.o_work);
+  K.map = reinterpret_cast<uint32_t *> (t + L.o_map);
+  K.tile_entry = reinterpret_cast<uint32_t *> (t + L.o_entry);
+  K.tile_base = reinterpret_cast<uint32_t *> (t + L.o_base);
+  K.max_tiles = (n + K.T - 1) / K.T;
+  K.out = d_out;
+  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
+  K.ctl = reinterpret_cast<SelectCtl *> (t + L.o_ctl);
+  K.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+  const uint64_t most = (uint64_t)plan->cu_count * 8;
+  auto capped = [&] (uint64_t blocks) { return dim3 ((uint32_t)(blocks < 1 ? 1 : blocks < most ? blocks : most)); };
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (SelectCtl), st));
+  /* a. keys, the records that break the contract out, the order by (start, length descending) */
+  hipLaunchKernelGGL (select_key_kernel, capped ((n + SELECT_THREADS - 1) / SELECT_THREADS), dim3 (SELECT_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  hipLaunchKernelGGL (select_drop_kernel, dim3 (1), dim3 (SELECT_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  if (order_by_buckets (plan, order_layout (plan, n, span))) {
+    const int rc = order_records (plan, K.keyed, n, &K.ctl->n, pos_lo, span, t + L.o_work, L.work_bytes, stream);
+    if (rc)
+      return rc;
+  } else {
+    /* record sets the bucket passes do not take (positions past 2^40; ACM_GPU_ORDER=radix): the count
+     * comes to the host for the radix sort, as in acm_gpu_scan_ordered_device */
+    uint64_t kept = 0;
+    HIP_TRY (hipMemcpyAsync (&kept, &K.ctl->n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY (hipStreamSynchronize (st));
+    if (kept > 1) {
+      const int rc = order_records (plan, K.keyed, kept, nullptr, pos_lo, span, t + L.o_work, L.work_bytes, stream);
+      if (rc)
+        return rc;
+    }
+  }
+  /* b. the candidates */
+  hipLaunchKernelGGL (select_cand_kernel<false>, capped (L.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  size_t cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.chunk_count, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(L.n_chunks + 1), st));
+  hipLaunchKernelGGL (select_cand_kernel<true>, capped (L.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  if (!select_tiled_form (plan)) { /* f. */
+    hipLaunchKernelGGL (select_walk_kernel, dim3 (1), dim3 (WAVE), 0, st, K);
+    HIP_TRY (hipGetLastError ());
+    return ACM_GPU_OK;
+  }
+  /* c. d. e. */
+  const size_t lds = select_tile_lds (K.T);
+  hipLaunchKernelGGL (select_tile_kernel<false>, capped (K.max_tiles), dim3 (SELECT_THREADS), lds, st, K);
+  HIP_TRY (hipGetLastError ());
+  hipLaunchKernelGGL (select_resolve_kernel, dim3 (1), dim3 (SELECT_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  hipLaunchKernelGGL (select_tile_kernel<true>, capped (K.max_tiles), dim3 (SELECT_THREADS), lds, st, K);
+  HIP_TRY (hipGetLastError ());
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_scan_select_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols) {
+  if (!plan || capacity >= (1ull << 31))
+    return 0;
+  /* (the scan's scratch is free again when the selection begins: it reads d_records) */
+  return std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_select_tmp_bytes (plan, capacity, n_symbols));
+}
+
+extern "C" int
+acm_gpu_scan_select_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, ACMRecord *d_records, uint64_t capacity,
+                            uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || capacity >= (1ull << 31) || (n_symbols && !d_text) || (capacity && (!d_records || !d_tmp)))
+    return ACM_GPU_E_ARG;
+  if (capacity && tmp_bytes < acm_gpu_scan_select_tmp_bytes (plan, capacity, n_symbols))
+    return ACM_GPU_E_ARG;
+  int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, d_records, capacity, d_count, d_tmp, tmp_bytes, stream);
+  if (rc || capacity == 0 || n_symbols == 0) /* (no room: *d_count says what the records need; no text: 0) */
+    return rc;
+  return acm_gpu_select_records_device (plan, d_records, capacity, d_count, pos_base, n_symbols, d_records, d_count, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_select_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, ACMRecord *records, uint64_t capacity,
+                          uint64_t *n_found) {
+  if (!plan || !n_found || capacity >= (1ull << 31) || (n_symbols && !text) || (capacity && !records))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, tmp_bytes = acm_gpu_scan_select_tmp_bytes (plan, capacity, n_symbols);
+  void *d_text = nullptr, *d_rec = nullptr, *d_tmp = nullptr, *d_count = nullptr;
+  uint64_t found = 0;
+  auto cleanup = [&] () {
+    for (void *p : { d_text, d_rec, d_tmp, d_count })
+      if (p)
+        (void)hipFree (p);
+  };
+#define HOST_TRY(expr)                                                                             \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess) {                                                                        \
+      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
+      cleanup ();                                                                                  \
+      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
+    }                                                                                              \
+  } while (0)
+  HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
+  HOST_TRY (hipMalloc (&d_count, 8));
+  HOST_TRY (hipMalloc (&d_rec, capacity ? capacity * 16 : 16));
+  HOST_TRY (hipMalloc (&d_tmp, tmp_bytes ? tmp_bytes : 16));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  const int rc = acm_gpu_scan_select_device (plan, d_text, n_symbols, pos_base, static_cast<ACMRecord *> (d_rec), capacity,
+                                             static_cast<uint64_t *> (d_count), d_tmp, tmp_bytes, nullptr);
+  if (rc) {
+    (void)hipDeviceSynchronize ();
+    cleanup ();
+    return rc;
+  }
+  HOST_TRY (hipMemcpy (&found, d_count, 8, hipMemcpyDeviceToHost));
+  *n_found = found;
+  if (found > capacity) {
+    cleanup ();
+    return ACM_GPU_E_OVERFLOW;
+  }
+  if (found)
+    HOST_TRY (hipMemcpy (records, d_rec, found * 16, hipMemcpyDeviceToHost));
+  HOST_TRY (hipDeviceSynchronize ());
+  cleanup ();
+  return ACM_GPU_OK;
+#undef HOST_TRY
+}
+
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
 extern "C" int
 acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint32_t *len_bits, uint32_t *kw_bits) {
@@ -4599,6 +4825,32 @@ acm_tally (ACMachine *machine, const void *text, uint64_t n_symbols, uint64_t *t
     rc = R.path == ACM_SCAN_PATH_CPU_LOOP ? acm_internal_cpu_tally (machine, text, n_symbols, R.said, tally, n_keywords, total)
                                           : acm_gpu_tally_host (R.plan, text, n_symbols, tally, n_keywords, total);
     if (!rc)
+      acm_internal_set_scan_path (machine, R.path);
+  }
+  acm_internal_plan_unlock (machine);
+  return rc;
+}
+
+/* the leftmost-longest selection (include/acm_gpu.h): same route, same cached plan, same lock */
+extern "C" int
+acm_select (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
+  if (!machine || !n_found || (n_symbols && !text) || (capacity && !records))
+    return ACM_GPU_E_ARG;
+  ScanRoute R;
+  int rc = scan_route (machine, &R);
+  if (rc)
+    return rc;
+  acm_internal_plan_lock (machine);
+  if (R.path != ACM_SCAN_PATH_CPU_LOOP)
+    rc = route_plan (machine, &R);
+  if (!rc) {
+    if (R.path == ACM_SCAN_PATH_CPU_LOOP) {
+      rc = acm_internal_cpu_scan (machine, text, n_symbols, R.said, records, capacity, n_found);
+      if (!rc)
+        *n_found = acm_select_records (records, *n_found);
+    } else
+      rc = acm_gpu_scan_select_host (R.plan, text, n_symbols, 0, records, capacity, n_found);
+    if (!rc || rc == ACM_GPU_E_OVERFLOW)
       acm_internal_set_scan_path (machine, R.path);
   }
   acm_internal_plan_unlock (machine);

@@ -813,3 +813,47 @@ acm_internal_cpu_tally (ACMachine *m, const void *text, uint64_t n_symbols, uint
     *total = found;
   return ACM_GPU_OK;
 }
+
+/* SELECT of records in canonical order (include/acm_gpu.h), in place in the front of the array: the
+ * plain sequential greedy pass.  The order is by end and the rule goes by start, so a round looks
+ * at a window: from the first record that ends at or behind p up to the first that ends lmax or
+ * more behind the best start so far (lmax = the longest record of the set) -- that one and every
+ * later one starts behind it.  Everything up to the record taken ends in front of the new p: the
+ * output never overwrites a record that is still to be read.  Starts are signed, so that a record
+ * whose length exceeds end_pos + 1 (acm_scan_from's, a flow's) keeps its place in front. */
+uint64_t
+acm_select_records (ACMRecord *records, uint64_t n) {
+  if (!records)
+    return 0;
+  uint32_t lmax = 0;
+  for (uint64_t j = 0; j < n; j++)
+    if (records[j].length > lmax)
+      lmax = records[j].length;
+  uint64_t out = 0, i = 0;
+  int64_t p = INT64_MIN;
+  while (i < n) {
+    uint64_t best = n;
+    int64_t bstart = 0;
+    for (uint64_t j = i; j < n; j++) {
+      const ACMRecord *r = &records[j];
+      if (best != n && (int64_t)r->end_pos - bstart >= (int64_t)lmax)
+        break;
+      const int64_t start = (int64_t)r->end_pos + 1 - (int64_t)r->length;
+      if (start < p)
+        continue;
+      const ACMRecord *b = best != n ? &records[best] : NULL;
+      if (!b || start < bstart || (start == bstart && (r->length > b->length || (r->length == b->length && r->keyword_id < b->keyword_id)))) {
+        best = j;
+        bstart = start;
+      }
+    }
+    if (best == n)
+      break;
+    const ACMRecord take = records[best];
+    records[out++] = take;
+    p = (int64_t)take.end_pos + 1;
+    while (i < n && (int64_t)records[i].end_pos < p)
+      i++;
+  }
+  return out;
+}

@@ -162,5 +162,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_batch.h"
 #include "dev_flows.h"
 #include "dev_tally.h"
+#include "dev_select.h"
 
 } // namespace

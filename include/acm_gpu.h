@@ -479,6 +479,80 @@ int acm_gpu_tally_host (ACMPlan *plan, const void *text, uint64_t n_symbols,
 int acm_tally (ACMachine *machine, const void *text, uint64_t n_symbols,
                uint64_t *tally, uint64_t n_keywords, uint64_t *total);
 
+/* ------------------------------------------------------------------ leftmost-longest non-overlapping matches
+ * Search-and-replace, redaction, tokenising against a vocabulary and highlighting need ONE tiling of
+ * the text, not every occurrence: the non-overlapping matches, taken leftmost first and longest at a
+ * tie.  On `ushers` with {he, she, his, hers} the caller loop reports she, he and hers; a replacer
+ * acts on `she` alone.
+ *
+ * DEFINITION.  Let R be a record set; a record's start is end_pos + 1 - length.  SELECT (R):
+ *     1. set p to the smallest position;
+ *     2. among the records with start >= p take those with the smallest start;
+ *     3. of those take the one with the greatest length (two of equal start and length are not
+ *        expected -- no scan gives them; the host helper then takes the smaller keyword_id);
+ *     4. emit the record;
+ *     5. set p to its end_pos + 1;
+ *     6. repeat from 2 until no record has start >= p.
+ * The output is in canonical order: starts and ends both ascend, no two emitted records share a
+ * symbol.  The batch scan's records never cross a text boundary, so SELECT of a batch's records is
+ * the concatenation of SELECT of every text's records.
+ *
+ * acm_select_records: SELECT of records[0 .. n), which are in canonical order, in place in the front
+ * of the array; returns the selected count.  The plain sequential pass on the host, no device.
+ * Starts are taken as signed numbers (a record of acm_scan_from may begin in front of its text).
+ *
+ * acm_gpu_select_records_device: the same on the device (dev_select.h).  d_records is in canonical
+ * order; d_n (device, may be NULL) holds the record count and n_or_capacity the room of d_records
+ * and d_out -- with d_n NULL n_or_capacity is the count itself.  Every position, the starts
+ * included, lies in [pos_lo, pos_lo + span), and no length exceeds the plan's lmax (the larger of
+ * the plan's and its delta's).  d_out may be d_records, d_count may be d_n.  *d_count (device)
+ * receives the selected count; when *d_n exceeds n_or_capacity (a scan that overflowed) nothing is
+ * selected and *d_count = *d_n.  The call only queues launches on `stream`, with no host round trip
+ * (except for record sets the bucket order does not take -- a span of 2^40 positions or more --
+ * where the count comes to the host once, as in acm_gpu_scan_ordered_device).  A record that breaks
+ * the contract -- a start below pos_lo (a flow's record that reaches back into its carry, hand-made
+ * input), a position outside the range, a length of 0 or beyond lmax -- is DROPPED, nothing is read
+ * or written out of bounds and acm_gpu_plan_status reports ACM_GPU_E_INTERNAL, as for a record out
+ * of range in acm_gpu_order_records_device.  n_or_capacity must be below 2^31 (ACM_GPU_E_ARG).
+ * d_tmp must hold acm_gpu_select_tmp_bytes (plan, n_or_capacity, span) bytes (about 40 bytes per
+ * record of capacity).
+ * acm_gpu_select_form: which of dev_select.h's two forms the plan's selections take -- tiles of T
+ * candidates in LDS (T = 1,024; ACM_GPU_SELECT_TILE=<8 .. 2048> in the environment sets another,
+ * read at every call) when lmax <= T, else, or when the environment says ACM_GPU_SELECT=walk, one
+ * lane that walks the chain through global memory: slow and correct, so that no plan is refused.
+ *
+ * acm_gpu_scan_select_device: acm_gpu_scan_ordered_device with emit_from = 0 and the pass above
+ * behind it on `stream`.  The selection of a shard is not the shard of the selection: there is no
+ * emit_from, and multi-GPU selection is out of scope (select on one device, or gather the records
+ * with acm_gpu_multi_* and select them there).  CAPACITY is the batch scan's rule: `capacity` must
+ * hold ALL matches, they are found first.  *d_count <= capacity afterwards: it is the exact selected
+ * count and d_records is complete.  *d_count > capacity: it is the scan's count -- a capacity that
+ * suffices -- and the records are unspecified.  d_tmp must hold acm_gpu_scan_select_tmp_bytes (plan,
+ * capacity, n_symbols) bytes.
+ * acm_gpu_scan_select_host: the same from host memory, blocking; on ACM_GPU_E_OVERFLOW *n_found holds
+ * a capacity that suffices.
+ * acm_select: the call on the machine itself, total over machines exactly as acm_scan is (same three
+ * paths, same cached plan and acm_gpu_plan_update, acm_scan_path says which ran): the GPU paths run
+ * acm_gpu_scan_select_host, ACM_SCAN_PATH_CPU_LOOP runs the caller loop on the host and then
+ * acm_select_records.  A missing device stays an error, never a fallback. */
+#define ACM_GPU_SELECT_FORM_TILED 1
+#define ACM_GPU_SELECT_FORM_WALK 2
+uint64_t acm_select_records (ACMRecord *records, uint64_t n);
+size_t acm_gpu_select_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t span);
+int acm_gpu_select_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64_t n_or_capacity,
+                                   const uint64_t *d_n /* device count, may be NULL: n is the count */,
+                                   uint64_t pos_lo, uint64_t span, ACMRecord *d_out, uint64_t *d_count,
+                                   void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_select_form (const ACMPlan *plan);
+size_t acm_gpu_scan_select_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols);
+int acm_gpu_scan_select_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                ACMRecord *d_records, uint64_t capacity, uint64_t *d_count,
+                                void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_select_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base,
+                              ACMRecord *records, uint64_t capacity, uint64_t *n_found);   /* blocking */
+int acm_select (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records,
+                uint64_t capacity, uint64_t *n_found);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
