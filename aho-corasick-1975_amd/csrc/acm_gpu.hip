@@ -50,6 +50,17 @@
     }                                                                                              \
   } while (0)
 
+/* the host-buffer conveniences: out of memory is told apart; their device buffers belong to a
+ * DeviceTemps, so nothing is freed here */
+#define HOST_TRY(expr)                                                                             \
+  do {                                                                                             \
+    hipError_t _e = (expr);                                                                        \
+    if (_e != hipSuccess) {                                                                        \
+      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
+      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
+    }                                                                                              \
+  } while (0)
+
 #include "dev_all.h"
 
 /* ====================================================================== host side */
@@ -257,6 +268,78 @@ blob_reserve (size_t &cursor, size_t bytes) {
   cursor += bytes;
   return at;
 }
+
+int
+env_int (const char *name, int absent) {
+  const char *e = getenv (name);
+  return e ? atoi (e) : absent;
+}
+
+/* the plan's error flag (acm_gpu_plan_status reads it), nullptr while the plan has no scratch */
+unsigned int *
+error_word (const ACMPlan *plan) {
+  return plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+}
+
+/* grid of a grid-stride kernel: `blocks`, at least one, never more than per_cu a CU */
+dim3
+capped_grid (const ACMPlan *plan, uint64_t blocks, uint32_t per_cu = 8) {
+  const uint64_t most = (uint64_t)plan->cu_count * per_cu;
+  return dim3 ((uint32_t)(blocks < 1 ? 1 : blocks < most ? blocks : most));
+}
+
+/* scratch of hipcub's exclusive sum over n 32-bit counts */
+size_t
+exclusive_sum_bytes (uint64_t n) {
+  size_t bytes = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, bytes, static_cast<uint32_t *> (nullptr), static_cast<uint32_t *> (nullptr), (int)n, nullptr);
+  return bytes;
+}
+
+/* the longest keyword of the plan and of its delta.  acm_gpu_plan_update keeps plan->finfo.lmax at
+ * the maximum of both ("halos and sort keys go by the longest keyword of both"), so this equals
+ * plan->finfo.lmax; the form says what is meant */
+uint32_t
+plan_lmax (const ACMPlan *plan) {
+  const uint32_t own = plan->finfo.lmax, more = plan->delta ? plan->delta->finfo.lmax : 0;
+  return own > more ? own : more;
+}
+
+/* bits of a sort key's length field: every length in [0, lmax] */
+uint32_t
+len_bits_of (uint32_t lmax) {
+  uint32_t bits = 1;
+  while ((1u << bits) <= lmax)
+    bits++;
+  return bits;
+}
+
+/* temporary device memory of one call: blocks of at least 16 bytes, freed when the call returns */
+struct DeviceTemps {
+  std::vector<void *> blocks;
+  DeviceTemps () = default;
+  DeviceTemps (const DeviceTemps &) = delete;
+  DeviceTemps &operator= (const DeviceTemps &) = delete;
+  ~DeviceTemps () {
+    for (void *b : blocks)
+      (void)hipFree (b);
+  }
+  template <typename T>
+  hipError_t
+  get (T **out, size_t bytes) {
+    void *b = nullptr;
+    const hipError_t e = hipMalloc (&b, bytes < 16 ? 16 : bytes);
+    if (e == hipSuccess)
+      blocks.push_back (b);
+    *out = static_cast<T *> (b);
+    return e;
+  }
+  hipError_t
+  release (void *b) { /* one block before the others */
+    blocks.erase (std::remove (blocks.begin (), blocks.end (), b), blocks.end ());
+    return hipFree (b);
+  }
+};
 
 /* ---- the kernel a plan launches, by the plan's own facts: set_lds_attributes and the launch
  * functions ask the same function, so the attribute is set on what is launched */
@@ -610,12 +693,6 @@ fill_gram_tables (const ACMFlatView &fv, const ACMFlatInfo &fi, const GramImage 
 /* ---- plan construction (acm_gpu_plan_create_flat, and the delta plans of acm_gpu_plan_update).
  * One device allocation holds every table of a plan; its host image is built table by table: the
  * CSR tables every plan has, then those of the kernel family the dictionary qualifies for. */
-
-int
-env_int (const char *name, int absent) {
-  const char *e = getenv (name);
-  return e ? atoi (e) : absent;
-}
 
 /* the environment switches that shape a plan (experiments and tests), read once per plan */
 struct PlanSwitches {
@@ -2440,7 +2517,7 @@ make_emit_ctx (const ACMPlan *p, ACMRecord *records, uint64_t capacity, unsigned
   E.spill_slots = spill ? (uint64_t)p->scratch.direct_regions * rec_chunk : 0;
   E.rec_chunk = rec_chunk;
   E.chunk_prev = chunk_prev;
-  E.error = p->scratch.d_total ? reinterpret_cast<unsigned int *> (p->scratch.d_total) + 3 : nullptr;
+  E.error = error_word (p);
   return E;
 }
 
@@ -2733,13 +2810,13 @@ acm_gpu_stream_finish (ACMStream *s, ACMRecord *records, uint64_t capacity, uint
     return ACM_GPU_E_OVERFLOW;
   if (total > 1) {
     const size_t tb = acm_gpu_order_tmp_bytes (p, total, s->position);
+    DeviceTemps temps;
     void *tmp = nullptr;
-    if (hipMalloc (&tmp, tb) != hipSuccess)
+    if (temps.get (&tmp, tb) != hipSuccess)
       return ACM_GPU_E_NOMEM;
     int rc = acm_gpu_order_records_device (p, s->d_records, total, 0, s->position, tmp, tb, s->compute);
     if (!rc && hipStreamSynchronize (s->compute) != hipSuccess)
       rc = ACM_GPU_E_HIP;
-    (void)hipFree (tmp);
     if (rc)
       return rc;
   }
@@ -2822,9 +2899,7 @@ radix_sort_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, void *d_tmp
   Rec16 *v1 = reinterpret_cast<Rec16 *> (t + 2 * align256 (n * 8));
   void *cub_tmp = t + 2 * align256 (n * 8) + align256 (n * 16);
   size_t cub_bytes = cub_sort_bytes (n);
-  uint32_t len_bits = 1;
-  while ((1u << len_bits) <= plan->finfo.lmax)
-    len_bits++;
+  const uint32_t len_bits = len_bits_of (plan_lmax (plan));
   /* key = end_pos in the high bits, (max - length) below: 64 - len_bits bits remain for positions */
   hipLaunchKernelGGL (make_keys_kernel, dim3 ((uint32_t)((n + 255) / 256)), dim3 (256), 0, st, d_records, n, len_bits, pos_lo, k0);
   HIP_TRY (hipGetLastError ());
@@ -2850,12 +2925,10 @@ order_layout (const ACMPlan *plan, uint64_t n, uint64_t span) {
   OrderPlan L;
   if (n == 0 || span == 0 || n >= (1ull << 31))
     return L;
-  uint32_t span_bits = 1, len_bits = 1;
+  uint32_t span_bits = 1;
   while ((1ull << span_bits) < span && span_bits < 63)
     span_bits++;
-  const uint32_t lmax = plan->finfo.lmax > (plan->delta ? plan->delta->finfo.lmax : 0) ? plan->finfo.lmax : (plan->delta ? plan->delta->finfo.lmax : 0);
-  while ((1u << len_bits) <= lmax)
-    len_bits++;
+  const uint32_t len_bits = len_bits_of (plan_lmax (plan));
   L.len_bits = len_bits;
   L.key_bits = span_bits + len_bits < 64 ? (int)(span_bits + len_bits) : 64;
   /* buckets of ORDER_POSITIONS positions (fewer when the whole range is shorter): whatever a
@@ -2869,8 +2942,7 @@ order_layout (const ACMPlan *plan, uint64_t n, uint64_t span) {
     return L;
   L.wlog = wlog;
   L.n_buckets = (uint32_t)nb;
-  size_t cub = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, cub, static_cast<uint32_t *> (nullptr), static_cast<uint32_t *> (nullptr), (int)(nb + 1), nullptr);
+  const size_t cub = exclusive_sum_bytes (nb + 1);
   L.cub_bytes = cub;
   size_t cur = 0;
   L.o_hist = blob_reserve (cur, (nb + 1) * 4 + (nb + 2) * 4); /* counts, then (o_cur, right behind them) a zero word and the sums */
@@ -2932,7 +3004,7 @@ order_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, const unsigned l
   K.wlog = L.wlog;
   K.n_buckets = L.n_buckets;
   K.len_bits = L.len_bits;
-  K.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+  K.error = error_word (plan);
   K.n_dev = n_dev;
   K.span = span;
   K.mode = n_dev ? 2u : (L.sparse ? 1u : 0u);
@@ -2941,25 +3013,25 @@ order_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, const unsigned l
    * is where bucket b ENDS, so that P = cur reads P[b] = begin, P[b + 1] = end for pass C (no copy
    * of the sums is kept) */
   const uint64_t pieces = (n + ORDER_PIECE - 1) / ORDER_PIECE, pblocks = (pieces + ORDER_THREADS / WAVE - 1) / (ORDER_THREADS / WAVE);
-  const uint32_t grid = (uint32_t)(pblocks < (uint64_t)plan->cu_count * 8 ? pblocks : (uint64_t)plan->cu_count * 8);
+  const dim3 grid = capped_grid (plan, pblocks);
   HIP_TRY (hipMemsetAsync (hist, 0, order_zero_bytes (L), st)); /* (the counts and cur[0], which lies right behind them) */
-  hipLaunchKernelGGL (order_bucket_kernel<false>, dim3 (grid), dim3 (ORDER_THREADS), 0, st, K, hist, static_cast<ACMRecord *> (nullptr));
+  hipLaunchKernelGGL (order_bucket_kernel<false>, grid, dim3 (ORDER_THREADS), 0, st, K, hist, static_cast<ACMRecord *> (nullptr));
   HIP_TRY (hipGetLastError ());
   size_t cub = L.cub_bytes;
   HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, hist, cur + 1, (int)(L.n_buckets + 1), st));
-  hipLaunchKernelGGL (order_bucket_kernel<true>, dim3 (grid), dim3 (ORDER_THREADS), 0, st, K, cur + 1, bucketed);
+  hipLaunchKernelGGL (order_bucket_kernel<true>, grid, dim3 (ORDER_THREADS), 0, st, K, cur + 1, bucketed);
   HIP_TRY (hipGetLastError ());
   /* pass C: buckets (dense record sets) or windows of buckets (sparse ones) of up to 256 records by
-   * a wave each, crowded buckets by a block each (each role skips the others' buckets) */
+   * a wave each, crowded buckets by a block each (each role skips the others' buckets); a role
+   * that does not run keeps a grid of zero */
   uint32_t wgrid = 0, sgrid = 0;
   if (n_dev || L.sparse) { /* (with the count on the device both are there: the one whose kind of set it is not returns at once) */
     const uint64_t windows = (n + ORDER_WINDOW - 1) / ORDER_WINDOW, wblocks = (windows + 3) / 4;
-    wgrid = (uint32_t)(wblocks < (uint64_t)plan->cu_count * 16 ? wblocks : (uint64_t)plan->cu_count * 16);
+    wgrid = capped_grid (plan, wblocks, 16).x;
   }
   if (n_dev || !L.sparse)
-    sgrid = (uint32_t)((L.n_buckets + 3) / 4 < (uint32_t)plan->cu_count * 16 ? (L.n_buckets + 3) / 4 : (uint32_t)plan->cu_count * 16);
-  const uint32_t cblocks = (L.n_buckets + ORDER_COUNT_THREADS - 1) / ORDER_COUNT_THREADS;
-  const uint32_t cgrid = cblocks < (uint32_t)plan->cu_count * 8 ? cblocks : (uint32_t)plan->cu_count * 8;
+    sgrid = capped_grid (plan, (L.n_buckets + 3) / 4, 16).x;
+  const uint32_t cgrid = capped_grid (plan, (L.n_buckets + ORDER_COUNT_THREADS - 1) / ORDER_COUNT_THREADS).x;
   hipLaunchKernelGGL (order_finish_kernel, dim3 (wgrid + sgrid + cgrid), dim3 (256), 0, st, K, cur, bucketed, d_records, wgrid, sgrid);
   HIP_TRY (hipGetLastError ());
   return ACM_GPU_OK;
@@ -2998,7 +3070,7 @@ tiled_layout (const ACMPlan *p, uint64_t capacity, uint64_t n, uint64_t emit_fro
   const char *env = getenv ("ACM_GPU_ORDER"); /* radix / buckets: not this way (experiments, tests) */
   if (env && (strcmp (env, "radix") == 0 || strcmp (env, "buckets") == 0))
     return L;
-  if (p->kind != PlanKind::Gram || p->hashed || p->short_pass || p->delta || p->finfo.lmax > WAVE * 16 || p->finfo.n_edges == 0)
+  if (p->kind != PlanKind::Gram || p->hashed || p->short_pass || p->delta || plan_lmax (p) > WAVE * 16 || p->finfo.n_edges == 0)
     return L; /* (a second pass' records do not lie tile by tile: the general order passes) */
   if (n == 0 || emit_from >= n || capacity == 0 || capacity >= (1ull << 31))
     return L;
@@ -3020,10 +3092,8 @@ tiled_layout (const ACMPlan *p, uint64_t capacity, uint64_t n, uint64_t emit_fro
   L.n_tiles = (uint32_t)tiles;
   /* whole chunks: the records and what every wave may leave unused of its last chunk */
   L.raw_slots = (capacity + REC_CHUNK - 1) / REC_CHUNK * REC_CHUNK + ((uint64_t)p->cu_count * (SPARSE_THREADS / WAVE) + 1) * REC_CHUNK;
-  while ((1u << L.len_bits) <= p->finfo.lmax)
-    L.len_bits++;
-  size_t cub = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, cub, static_cast<uint32_t *> (nullptr), static_cast<uint32_t *> (nullptr), (int)(L.n_tiles + 1), nullptr);
+  L.len_bits = len_bits_of (plan_lmax (p));
+  const size_t cub = exclusive_sum_bytes ((uint64_t)L.n_tiles + 1);
   L.cub_bytes = cub;
   size_t cur = 0;
   L.o_raw = blob_reserve (cur, L.raw_slots * sizeof (ACMRecord));
@@ -3068,18 +3138,15 @@ scan_tiled (ACMPlan *plan, const TiledPlan &L, const void *d_text, uint64_t n_sy
   K.raw_slots = L.raw_slots;
   K.over_total = reinterpret_cast<unsigned long long *> (t + L.o_over);
   HIP_TRY (hipMemsetAsync (K.over_total, 0, 8, st));
-  K.error = reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3;
-  const uint32_t sblocks = (L.n_tiles + 1 + 3) / 4;
-  hipLaunchKernelGGL (tile_size_kernel, dim3 (sblocks < (uint32_t)plan->cu_count * 16 ? sblocks : (uint32_t)plan->cu_count * 16), dim3 (256), 0, st, K);
+  K.error = error_word (plan);
+  hipLaunchKernelGGL (tile_size_kernel, capped_grid (plan, (L.n_tiles + 1 + 3) / 4, 16), dim3 (256), 0, st, K);
   HIP_TRY (hipGetLastError ());
   size_t cub = L.cub_bytes;
   HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.size, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(L.n_tiles + 1), st));
-  const uint32_t gblocks = L.n_tiles < (uint32_t)plan->cu_count * 16 ? L.n_tiles : (uint32_t)plan->cu_count * 16;
-  hipLaunchKernelGGL (tile_gather_kernel, dim3 (gblocks), dim3 (TILE_THREADS), tile_lds_bytes (L.nsub), st, K);
+  hipLaunchKernelGGL (tile_gather_kernel, capped_grid (plan, L.n_tiles, 16), dim3 (TILE_THREADS), tile_lds_bytes (L.nsub), st, K);
   HIP_TRY (hipGetLastError ());
   /* the tiles it found crowded (dense matches; none on ordinary texts: the kernel returns at once) */
-  const uint32_t cblocks = L.n_tiles < (uint32_t)plan->cu_count * 4 ? L.n_tiles : (uint32_t)plan->cu_count * 4;
-  hipLaunchKernelGGL (tile_crowded_kernel, dim3 (cblocks), dim3 (TILE_THREADS), tile_lds_bytes (L.nsub), st, K);
+  hipLaunchKernelGGL (tile_crowded_kernel, capped_grid (plan, L.n_tiles, 4), dim3 (TILE_THREADS), tile_lds_bytes (L.nsub), st, K);
   HIP_TRY (hipGetLastError ());
   return ACM_GPU_OK;
 }
@@ -3128,6 +3195,51 @@ acm_gpu_scan_ordered_device (ACMPlan *plan, const void *d_text, uint64_t n_symbo
 
 /* ------------------------------------------------------------------ host-buffer convenience */
 namespace {
+/* what a batch brings down beside its records */
+struct BatchDownload {
+  uint32_t *text_id;
+  const uint32_t *d_text_id;
+  uint64_t *first;
+  const uint64_t *d_first;
+  uint64_t n_texts;
+};
+
+/* the end of a host convenience, behind its device call (which gave rc): the count, *n_found,
+ * ACM_GPU_E_OVERFLOW when the records had no room, else `order (found)` and the records (with a
+ * batch's text ids and first[]), then the wait for the device.  After a failed device call the
+ * device is waited for too, once, before the caller's buffers go away. */
+template <typename Order>
+int
+download_records (int rc, const uint64_t *d_count, const ACMRecord *d_rec, ACMRecord *records, uint64_t capacity, uint64_t *n_found,
+                  const BatchDownload *batch, Order order) {
+  uint64_t found = 0;
+  if (!rc) {
+    HOST_TRY (hipMemcpy (&found, d_count, 8, hipMemcpyDeviceToHost));
+    *n_found = found;
+    if (found > capacity)
+      return ACM_GPU_E_OVERFLOW;
+    rc = order (found);
+  }
+  if (rc) {
+    (void)hipDeviceSynchronize ();
+    return rc;
+  }
+  if (found)
+    HOST_TRY (hipMemcpy (records, d_rec, found * 16, hipMemcpyDeviceToHost));
+  if (batch && found && batch->text_id)
+    HOST_TRY (hipMemcpy (batch->text_id, batch->d_text_id, found * 4, hipMemcpyDeviceToHost));
+  if (batch && batch->first)
+    HOST_TRY (hipMemcpy (batch->first, batch->d_first, (batch->n_texts + 1) * 8, hipMemcpyDeviceToHost));
+  HOST_TRY (hipDeviceSynchronize ());
+  return ACM_GPU_OK;
+}
+
+int
+download_records (int rc, const uint64_t *d_count, const ACMRecord *d_rec, ACMRecord *records, uint64_t capacity, uint64_t *n_found,
+                  const BatchDownload *batch = nullptr) {
+  return download_records (rc, d_count, d_rec, records, capacity, n_found, batch, [] (uint64_t) { return (int)ACM_GPU_OK; });
+}
+
 /* acm_gpu_scan_host over `prefix` (n_prefix symbols, may be none) followed by `text`: the two are
  * uploaded side by side, so that acm_scan_from need not copy its text on the host */
 int
@@ -3138,58 +3250,26 @@ scan_host_prefixed (ACMPlan *plan, const void *prefix, uint64_t n_prefix, const 
   HIP_TRY (hipSetDevice (plan->device));
   const uint64_t n_symbols = n_prefix + n_text;
   const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, pbytes = (size_t)n_prefix * plan->text_sym_bytes;
-  void *d_text = nullptr, *d_rec = nullptr, *d_tmp = nullptr;
+  DeviceTemps temps;
+  unsigned char *d_text = nullptr;
   uint64_t *d_count = nullptr;
-  int rc = ACM_GPU_OK;
-  uint64_t found = 0;
-  auto cleanup = [&] () {
-    if (d_text) (void)hipFree (d_text);
-    if (d_rec) (void)hipFree (d_rec);
-    if (d_tmp) (void)hipFree (d_tmp);
-    if (d_count) (void)hipFree (d_count);
-  };
-#define HOST_TRY(expr)                                                                             \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) {                                                                        \
-      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
-      cleanup ();                                                                                  \
-      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
-    }                                                                                              \
-  } while (0)
-  HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
-  HOST_TRY (hipMalloc (reinterpret_cast<void **> (&d_count), 8));
-  HOST_TRY (hipMalloc (&d_rec, capacity ? capacity * 16 : 16));
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_count, 8));
+  HOST_TRY (temps.get (&d_rec, capacity * 16));
   if (pbytes)
     HOST_TRY (hipMemcpy (d_text, prefix, pbytes, hipMemcpyHostToDevice));
   if (tbytes > pbytes)
-    HOST_TRY (hipMemcpy (static_cast<unsigned char *> (d_text) + pbytes, text, tbytes - pbytes, hipMemcpyHostToDevice));
-  rc = acm_gpu_scan_device (plan, d_text, n_symbols, emit_from, pos_base, static_cast<ACMRecord *> (d_rec), capacity, d_count, nullptr);
-  if (rc) {
-    cleanup ();
-    return rc;
-  }
-  HOST_TRY (hipMemcpy (&found, d_count, 8, hipMemcpyDeviceToHost));
-  *n_found = found;
-  if (found > capacity) {
-    cleanup ();
-    return ACM_GPU_E_OVERFLOW;
-  }
-  if (found > 1) {
-    size_t tb = acm_gpu_order_tmp_bytes (plan, found, n_symbols);
-    HOST_TRY (hipMalloc (&d_tmp, tb));
-    rc = acm_gpu_order_records_device (plan, static_cast<ACMRecord *> (d_rec), found, pos_base, n_symbols, d_tmp, tb, nullptr);
-    if (rc) {
-      cleanup ();
-      return rc;
-    }
-  }
-  if (found)
-    HOST_TRY (hipMemcpy (records, d_rec, found * 16, hipMemcpyDeviceToHost));
-  HOST_TRY (hipDeviceSynchronize ());
-  cleanup ();
-  return ACM_GPU_OK;
-#undef HOST_TRY
+    HOST_TRY (hipMemcpy (d_text + pbytes, text, tbytes - pbytes, hipMemcpyHostToDevice));
+  const int rc = acm_gpu_scan_device (plan, d_text, n_symbols, emit_from, pos_base, d_rec, capacity, d_count, nullptr);
+  return download_records (rc, d_count, d_rec, records, capacity, n_found, nullptr, [&] (uint64_t found) -> int {
+    if (found <= 1)
+      return ACM_GPU_OK;
+    const size_t tb = acm_gpu_order_tmp_bytes (plan, found, n_symbols);
+    void *d_tmp = nullptr;
+    HOST_TRY (temps.get (&d_tmp, tb));
+    return acm_gpu_order_records_device (plan, d_rec, found, pos_base, n_symbols, d_tmp, tb, nullptr);
+  });
 }
 } // namespace
 
@@ -3212,8 +3292,7 @@ batch_layout (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols) {
   BatchLayout L;
   L.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
   L.n_tiles = (capacity + BATCH_TILE - 1) / BATCH_TILE;
-  size_t cub = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, cub, static_cast<uint32_t *> (nullptr), static_cast<uint32_t *> (nullptr), (int)(L.n_tiles + 1), nullptr);
+  const size_t cub = exclusive_sum_bytes (L.n_tiles + 1);
   L.cub_bytes = cub;
   L.ord_bytes = acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols);
   size_t cur = 0;
@@ -3246,6 +3325,18 @@ struct BatchHeads {
   const unsigned int *pre_bad; /* the caller's own checks have failed */
 };
 
+/* a batch of no texts: no symbol, no record */
+int
+empty_batch (ACMPlan *plan, uint64_t n_symbols, uint64_t *d_first, uint64_t *d_count, hipStream_t st) {
+  if (n_symbols)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
+  if (d_first)
+    HIP_TRY (hipMemsetAsync (d_first, 0, 8, st));
+  return ACM_GPU_OK;
+}
+
 /* acm_gpu_scan_batch_device; HEADS: what the flow scan runs behind its gather pass */
 template <bool HEADS>
 int
@@ -3255,15 +3346,8 @@ batch_scan (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_
   if (!plan || !d_count || n_texts >= (1ull << 32) || capacity >= (1ull << 31) || (n_symbols && !d_text) || (capacity && !d_records))
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
-  if (n_texts == 0) { /* no text, no symbol, no record */
-    if (n_symbols)
-      return ACM_GPU_E_ARG;
-    HIP_TRY (hipSetDevice (plan->device));
-    HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
-    if (d_first)
-      HIP_TRY (hipMemsetAsync (d_first, 0, 8, st));
-    return ACM_GPU_OK;
-  }
+  if (n_texts == 0)
+    return empty_batch (plan, n_symbols, d_first, d_count, st);
   const BatchLayout L = batch_layout (plan, capacity, n_symbols);
   if (!d_offsets || !d_tmp || tmp_bytes < L.total)
     return ACM_GPU_E_ARG;
@@ -3290,7 +3374,7 @@ batch_scan (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_
   K.first = d_first;
   K.d_count = reinterpret_cast<unsigned long long *> (d_count);
   K.ctl = reinterpret_cast<BatchCtl *> (t + L.o_ctl);
-  K.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+  K.error = error_word (plan);
   if (HEADS) {
     K.head = heads->head;
     K.base = heads->base;
@@ -3300,20 +3384,18 @@ batch_scan (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_
   /* grid-stride kernels: never more blocks than keep the chip busy.  The two kernels that also walk
    * offsets[] are sized by the positions; a batch of many texts over few symbols (mostly empty texts)
    * gets the full capped grid instead -- one size, whatever the number of texts */
-  const uint64_t most = (uint64_t)plan->cu_count * 8;
-  auto capped = [&] (uint64_t blocks) { return dim3 ((uint32_t)(blocks < 1 ? 1 : blocks < most ? blocks : most)); };
-  const uint64_t many_texts = n_texts >= (1ull << 16) ? most : 1;
+  const uint64_t many_texts = n_texts >= (1ull << 16) ? (uint64_t)plan->cu_count * 8 : 1;
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (BatchCtl), st));
   /* (the index goes by the positions, the check of offsets[] by a grid-stride loop of the same launch) */
-  hipLaunchKernelGGL (batch_index_kernel<HEADS>, capped (std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
+  hipLaunchKernelGGL (batch_index_kernel<HEADS>, capped_grid (plan, std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL ((batch_filter_kernel<false, HEADS>), capped (L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
+  hipLaunchKernelGGL ((batch_filter_kernel<false, HEADS>), capped_grid (plan, L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
   size_t cub = L.cub_bytes;
   HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.tile_count, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(L.n_tiles + 1), st));
-  hipLaunchKernelGGL ((batch_filter_kernel<true, HEADS>), capped (L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
+  hipLaunchKernelGGL ((batch_filter_kernel<true, HEADS>), capped_grid (plan, L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (batch_first_kernel<HEADS>, capped (std::max (L.n_blocks / 4 + 1, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
+  hipLaunchKernelGGL (batch_first_kernel<HEADS>, capped_grid (plan, std::max (L.n_blocks / 4 + 1, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
   return ACM_GPU_OK;
 }
@@ -3338,6 +3420,42 @@ batch_offsets_ok (const uint64_t *offsets, uint64_t n_texts) {
       return false;
   return true;
 }
+
+/* acm_gpu_scan_batch_host and, with `flows` (and maybe the texts' flow ids), acm_gpu_scan_flows_host
+ * behind their argument checks: everything up, the device call, everything down */
+int
+batch_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint64_t n_symbols, const uint64_t *offsets, const uint32_t *flow, uint64_t n_texts,
+            ACMRecord *records, uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found) {
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
+  const size_t tmp_bytes = flows ? acm_gpu_scan_flows_tmp_bytes (plan, flows, capacity, n_symbols, n_texts)
+                                 : acm_gpu_scan_batch_tmp_bytes (plan, capacity, n_symbols, n_texts);
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_off = nullptr, *d_count = nullptr, *d_first = nullptr;
+  uint32_t *d_flow = nullptr, *d_tid = nullptr;
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
+  if (flows)
+    HOST_TRY (temps.get (&d_flow, n_texts * 4));
+  HOST_TRY (temps.get (&d_count, 8));
+  HOST_TRY (temps.get (&d_rec, capacity * 16));
+  HOST_TRY (temps.get (&d_tid, capacity * 4));
+  HOST_TRY (temps.get (&d_first, (n_texts + 1) * 8));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+  if (flow && n_texts)
+    HOST_TRY (hipMemcpy (d_flow, flow, n_texts * 4, hipMemcpyHostToDevice));
+  const int rc = flows ? acm_gpu_scan_flows_device (plan, flows, d_text, n_symbols, d_off, flow ? d_flow : nullptr, n_texts, d_rec, d_tid, d_first, capacity,
+                                                    d_count, d_tmp, tmp_bytes, nullptr)
+                       : acm_gpu_scan_batch_device (plan, d_text, n_symbols, d_off, n_texts, d_rec, d_tid, d_first, capacity, d_count, d_tmp, tmp_bytes,
+                                                    nullptr);
+  const BatchDownload down = { text_id, d_tid, first, d_first, n_texts };
+  return download_records (rc, d_count, d_rec, records, capacity, n_found, &down);
+}
 } // namespace
 
 extern "C" int
@@ -3348,58 +3466,7 @@ acm_gpu_scan_batch_host (ACMPlan *plan, const void *text, const uint64_t *offset
   const uint64_t n_symbols = offsets[n_texts];
   if (n_symbols && !text)
     return ACM_GPU_E_ARG;
-  HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, tmp_bytes = acm_gpu_scan_batch_tmp_bytes (plan, capacity, n_symbols, n_texts);
-  void *d_text = nullptr, *d_off = nullptr, *d_rec = nullptr, *d_tid = nullptr, *d_first = nullptr, *d_tmp = nullptr, *d_count = nullptr;
-  uint64_t found = 0;
-  auto cleanup = [&] () {
-    for (void *p : { d_text, d_off, d_rec, d_tid, d_first, d_tmp, d_count })
-      if (p)
-        (void)hipFree (p);
-  };
-#define HOST_TRY(expr)                                                                             \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) {                                                                        \
-      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
-      cleanup ();                                                                                  \
-      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
-    }                                                                                              \
-  } while (0)
-  HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
-  HOST_TRY (hipMalloc (&d_off, (n_texts + 1) * 8));
-  HOST_TRY (hipMalloc (&d_count, 8));
-  HOST_TRY (hipMalloc (&d_rec, capacity ? capacity * 16 : 16));
-  HOST_TRY (hipMalloc (&d_tid, capacity ? capacity * 4 : 16));
-  HOST_TRY (hipMalloc (&d_first, (n_texts + 1) * 8));
-  HOST_TRY (hipMalloc (&d_tmp, tmp_bytes));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
-  const int rc = acm_gpu_scan_batch_device (plan, d_text, n_symbols, static_cast<const uint64_t *> (d_off), n_texts, static_cast<ACMRecord *> (d_rec),
-                                            static_cast<uint32_t *> (d_tid), static_cast<uint64_t *> (d_first), capacity,
-                                            static_cast<uint64_t *> (d_count), d_tmp, tmp_bytes, nullptr);
-  if (rc) {
-    (void)hipDeviceSynchronize ();
-    cleanup ();
-    return rc;
-  }
-  HOST_TRY (hipMemcpy (&found, d_count, 8, hipMemcpyDeviceToHost));
-  *n_found = found;
-  if (found > capacity) {
-    cleanup ();
-    return ACM_GPU_E_OVERFLOW;
-  }
-  if (found)
-    HOST_TRY (hipMemcpy (records, d_rec, found * 16, hipMemcpyDeviceToHost));
-  if (found && text_id)
-    HOST_TRY (hipMemcpy (text_id, d_tid, found * 4, hipMemcpyDeviceToHost));
-  if (first)
-    HOST_TRY (hipMemcpy (first, d_first, (n_texts + 1) * 8, hipMemcpyDeviceToHost));
-  HOST_TRY (hipDeviceSynchronize ());
-  cleanup ();
-  return ACM_GPU_OK;
-#undef HOST_TRY
+  return batch_host (plan, nullptr, text, n_symbols, offsets, nullptr, n_texts, records, text_id, first, capacity, n_found);
 }
 
 /* ------------------------------------------------------------------ flow scans (include/acm_gpu.h, dev_flows.h)
@@ -3421,8 +3488,7 @@ namespace {
 /* symbols of a full carry: the longest keyword of the plan and of its delta, less one */
 uint32_t
 flows_keep (const ACMPlan *p) {
-  const uint32_t own = p->finfo.lmax, more = p->delta ? p->delta->finfo.lmax : 0;
-  const uint32_t lmax = own > more ? own : more;
+  const uint32_t lmax = plan_lmax (p);
   return lmax > 1 ? lmax - 1 : 0;
 }
 
@@ -3513,10 +3579,8 @@ acm_gpu_flows_reset (ACMFlows *f, const uint32_t *d_flow_ids, uint64_t n, void *
     return ACM_GPU_OK;
   ACMPlan *plan = f->plan;
   HIP_TRY (hipSetDevice (plan->device));
-  const uint64_t most = (uint64_t)plan->cu_count * 8, want = (items + FLOWS_THREADS - 1) / FLOWS_THREADS;
-  unsigned int *error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
-  hipLaunchKernelGGL (flows_reset_kernel, dim3 ((uint32_t)(want < most ? want : most)), dim3 (FLOWS_THREADS), 0, static_cast<hipStream_t> (stream),
-                      f->d_len, f->n_flows, d_flow_ids, n, error);
+  hipLaunchKernelGGL (flows_reset_kernel, capped_grid (plan, (items + FLOWS_THREADS - 1) / FLOWS_THREADS), dim3 (FLOWS_THREADS), 0,
+                      static_cast<hipStream_t> (stream), f->d_len, f->n_flows, d_flow_ids, n, error_word (plan));
   HIP_TRY (hipGetLastError ());
   return ACM_GPU_OK;
 }
@@ -3541,15 +3605,8 @@ acm_gpu_scan_flows_device (ACMPlan *plan, ACMFlows *flows, const void *d_text, u
   if (!d_flow && n_texts > flows->n_flows)
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
-  if (n_texts == 0) { /* no text, no symbol, no record */
-    if (n_symbols)
-      return ACM_GPU_E_ARG;
-    HIP_TRY (hipSetDevice (plan->device));
-    HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
-    if (d_first)
-      HIP_TRY (hipMemsetAsync (d_first, 0, 8, st));
-    return ACM_GPU_OK;
-  }
+  if (n_texts == 0)
+    return empty_batch (plan, n_symbols, d_first, d_count, st);
   const FlowsLayout L = flows_layout (plan, flows, capacity, n_symbols, n_texts);
   if (!d_offsets || !d_tmp || tmp_bytes < L.total)
     return ACM_GPU_E_ARG;
@@ -3580,25 +3637,23 @@ acm_gpu_scan_flows_device (ACMPlan *plan, ACMFlows *flows, const void *d_text, u
   F.n_expanded = L.n_expanded;
   F.ctl = reinterpret_cast<FlowsCtl *> (t + L.o_ctl);
   F.batch = reinterpret_cast<const BatchCtl *> (t + L.o_batch + batch_layout (plan, capacity, L.n_expanded).o_ctl);
-  F.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+  F.error = error_word (plan);
   /* grid-stride kernels with capped grids: one launch size whatever the number of texts and flows */
-  const uint64_t most = (uint64_t)plan->cu_count * 8;
-  auto capped = [&] (uint64_t blocks) { return dim3 ((uint32_t)(blocks < 1 ? 1 : blocks < most ? blocks : most)); };
   const uint64_t per_text = (n_texts + 2 + FLOWS_THREADS - 1) / FLOWS_THREADS;
   HIP_TRY (hipMemsetAsync (F.ctl, 0, sizeof (FlowsCtl), st));
-  hipLaunchKernelGGL (flows_check_kernel, capped (per_text), dim3 (FLOWS_THREADS), 0, st, F);
+  hipLaunchKernelGGL (flows_check_kernel, capped_grid (plan, per_text), dim3 (FLOWS_THREADS), 0, st, F);
   HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (flows_head_kernel, capped (per_text), dim3 (FLOWS_THREADS), 0, st, F);
+  hipLaunchKernelGGL (flows_head_kernel, capped_grid (plan, per_text), dim3 (FLOWS_THREADS), 0, st, F);
   HIP_TRY (hipGetLastError ());
   size_t cub = L.cub_bytes;
   HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, HeadIterator (F.head, HeadTo64 ()), reinterpret_cast<uint64_t *> (t + L.o_sum),
                                              (int)(n_texts + 1), st));
-  hipLaunchKernelGGL (flows_xoff_kernel, capped (per_text), dim3 (FLOWS_THREADS), 0, st, F);
+  hipLaunchKernelGGL (flows_xoff_kernel, capped_grid (plan, per_text), dim3 (FLOWS_THREADS), 0, st, F);
   HIP_TRY (hipGetLastError ());
   /* the gather: lanes per text by the mean length of a text, 16 bytes a lane and step */
   F.group_log2 = log2_ceil_capped ((n_symbols * F.sb / n_texts + 15) / 16, 6);
   const uint64_t gather_blocks = std::max (((n_texts << F.group_log2) + FLOWS_THREADS - 1) / FLOWS_THREADS, n_texts * keep * F.sb / 16 / FLOWS_THREADS + 1);
-  hipLaunchKernelGGL (flows_gather_kernel, capped (gather_blocks), dim3 (FLOWS_THREADS), 0, st, F);
+  hipLaunchKernelGGL (flows_gather_kernel, capped_grid (plan, gather_blocks), dim3 (FLOWS_THREADS), 0, st, F);
   HIP_TRY (hipGetLastError ());
   BatchHeads H{ F.head, d_offsets, n_texts, &F.ctl->bad };
   const int rc = batch_scan<true> (plan, F.expanded, L.n_expanded, F.xoff, n_texts + 1, d_records, d_text_id, d_first, capacity, d_count, t + L.o_batch,
@@ -3606,7 +3661,7 @@ acm_gpu_scan_flows_device (ACMPlan *plan, ACMFlows *flows, const void *d_text, u
   if (rc)
     return rc;
   F.group_log2 = log2_ceil_capped (flows->slot_bytes / 16, 6);
-  hipLaunchKernelGGL (flows_carry_kernel, capped (((n_texts << F.group_log2) + FLOWS_THREADS - 1) / FLOWS_THREADS), dim3 (FLOWS_THREADS), 0, st, F);
+  hipLaunchKernelGGL (flows_carry_kernel, capped_grid (plan, ((n_texts << F.group_log2) + FLOWS_THREADS - 1) / FLOWS_THREADS), dim3 (FLOWS_THREADS), 0, st, F);
   HIP_TRY (hipGetLastError ());
   return ACM_GPU_OK;
 }
@@ -3626,63 +3681,7 @@ acm_gpu_scan_flows_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint6
     if ((n_texts && ids.back () >= flows->n_flows) || std::adjacent_find (ids.begin (), ids.end ()) != ids.end ())
       return ACM_GPU_E_ARG;
   }
-  HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, tmp_bytes = acm_gpu_scan_flows_tmp_bytes (plan, flows, capacity, n_symbols, n_texts);
-  void *d_text = nullptr, *d_off = nullptr, *d_flow = nullptr, *d_rec = nullptr, *d_tid = nullptr, *d_first = nullptr, *d_tmp = nullptr,
-       *d_count = nullptr;
-  uint64_t found = 0;
-  auto cleanup = [&] () {
-    for (void *p : { d_text, d_off, d_flow, d_rec, d_tid, d_first, d_tmp, d_count })
-      if (p)
-        (void)hipFree (p);
-  };
-#define HOST_TRY(expr)                                                                             \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) {                                                                        \
-      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
-      cleanup ();                                                                                  \
-      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
-    }                                                                                              \
-  } while (0)
-  HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
-  HOST_TRY (hipMalloc (&d_off, (n_texts + 1) * 8));
-  HOST_TRY (hipMalloc (&d_flow, n_texts ? n_texts * 4 : 16));
-  HOST_TRY (hipMalloc (&d_count, 8));
-  HOST_TRY (hipMalloc (&d_rec, capacity ? capacity * 16 : 16));
-  HOST_TRY (hipMalloc (&d_tid, capacity ? capacity * 4 : 16));
-  HOST_TRY (hipMalloc (&d_first, (n_texts + 1) * 8));
-  HOST_TRY (hipMalloc (&d_tmp, tmp_bytes ? tmp_bytes : 16));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
-  if (flow && n_texts)
-    HOST_TRY (hipMemcpy (d_flow, flow, n_texts * 4, hipMemcpyHostToDevice));
-  const int rc = acm_gpu_scan_flows_device (plan, flows, d_text, n_symbols, static_cast<const uint64_t *> (d_off),
-                                            flow ? static_cast<const uint32_t *> (d_flow) : nullptr, n_texts, static_cast<ACMRecord *> (d_rec),
-                                            static_cast<uint32_t *> (d_tid), static_cast<uint64_t *> (d_first), capacity,
-                                            static_cast<uint64_t *> (d_count), d_tmp, tmp_bytes, nullptr);
-  if (rc) {
-    (void)hipDeviceSynchronize ();
-    cleanup ();
-    return rc;
-  }
-  HOST_TRY (hipMemcpy (&found, d_count, 8, hipMemcpyDeviceToHost));
-  *n_found = found;
-  if (found > capacity) {
-    cleanup ();
-    return ACM_GPU_E_OVERFLOW;
-  }
-  if (found)
-    HOST_TRY (hipMemcpy (records, d_rec, found * 16, hipMemcpyDeviceToHost));
-  if (found && text_id)
-    HOST_TRY (hipMemcpy (text_id, d_tid, found * 4, hipMemcpyDeviceToHost));
-  if (first)
-    HOST_TRY (hipMemcpy (first, d_first, (n_texts + 1) * 8, hipMemcpyDeviceToHost));
-  HOST_TRY (hipDeviceSynchronize ());
-  cleanup ();
-  return ACM_GPU_OK;
-#undef HOST_TRY
+  return batch_host (plan, flows, text, n_symbols, offsets, flow, n_texts, records, text_id, first, capacity, n_found);
 }
 
 /* ------------------------------------------------------------------ per-keyword tallies (include/acm_gpu.h, dev_tally.h)
@@ -3780,7 +3779,7 @@ acm_gpu_tally_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uin
     K.hist = reinterpret_cast<unsigned long long *> (t + L.o_hist);
     K.n_keywords = plan->covered_keywords;
     K.ctl = reinterpret_cast<TallyCtl *> (t + L.o_ctl);
-    K.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
+    K.error = error_word (plan);
     /* grid-stride, two blocks per CU (what the LDS form's counters allow), whatever the scan found */
     const dim3 grid ((uint32_t)plan->cu_count * 2);
     if (tally_lds_form (plan))
@@ -3797,8 +3796,7 @@ acm_gpu_tally_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uin
   K.d_tally = reinterpret_cast<unsigned long long *> (d_tally);
   K.d_total = reinterpret_cast<unsigned long long *> (d_total);
   K.d_need = reinterpret_cast<unsigned long long *> (d_need);
-  const uint64_t blocks = ((uint64_t)K.n_keywords + TALLY_THREADS - 1) / TALLY_THREADS, most = (uint64_t)plan->cu_count * 8;
-  hipLaunchKernelGGL (tally_finish_kernel, dim3 ((uint32_t)(blocks < 1 ? 1 : blocks < most ? blocks : most)), dim3 (TALLY_THREADS), 0, st, K);
+  hipLaunchKernelGGL (tally_finish_kernel, capped_grid (plan, ((uint64_t)K.n_keywords + TALLY_THREADS - 1) / TALLY_THREADS), dim3 (TALLY_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
   return ACM_GPU_OK;
 }
@@ -3819,47 +3817,30 @@ acm_gpu_tally_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_
     capacity = n_symbols ? n_symbols * tally_max_outputs (plan) : 1;
   const uint32_t kw = plan->covered_keywords;
   const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
-  void *d_text = nullptr, *d_tally = nullptr, *d_out = nullptr, *d_tmp = nullptr;
-  auto cleanup = [&] () {
-    for (void *p : { d_text, d_tally, d_out, d_tmp })
-      if (p)
-        (void)hipFree (p);
-  };
-#define HOST_TRY(expr)                                                                             \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) {                                                                        \
-      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
-      cleanup ();                                                                                  \
-      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
-    }                                                                                              \
-  } while (0)
-  HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
-  HOST_TRY (hipMalloc (&d_tally, ((size_t)kw + 1) * 8));
-  HOST_TRY (hipMalloc (&d_out, 16)); /* total, need */
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_tally = nullptr, *d_out = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_tally, ((size_t)kw + 1) * 8));
+  HOST_TRY (temps.get (&d_out, 16)); /* total, need */
   if (tbytes)
     HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
   HOST_TRY (hipMemset (d_tally, 0, ((size_t)kw + 1) * 8));
   uint64_t out[2] = { 0, 0 };
   for (int attempt = 0; attempt < 2; attempt++) {
     const size_t tmp_bytes = acm_gpu_tally_tmp_bytes (plan, window, capacity);
-    HOST_TRY (hipMalloc (&d_tmp, tmp_bytes));
-    const int rc = acm_gpu_tally_device (plan, d_text, n_symbols, 0, static_cast<uint64_t *> (d_tally), kw, window, capacity,
-                                         static_cast<uint64_t *> (d_out), static_cast<uint64_t *> (d_out) + 1, d_tmp, tmp_bytes, nullptr);
+    HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+    const int rc = acm_gpu_tally_device (plan, d_text, n_symbols, 0, d_tally, kw, window, capacity, d_out, d_out + 1, d_tmp, tmp_bytes, nullptr);
     if (rc) {
       (void)hipDeviceSynchronize ();
-      cleanup ();
       return rc;
     }
     HOST_TRY (hipMemcpy (out, d_out, 16, hipMemcpyDeviceToHost));
-    HOST_TRY (hipFree (d_tmp));
-    d_tmp = nullptr;
+    HOST_TRY (temps.release (d_tmp)); /* (the second attempt's is another size) */
     if (out[1] <= capacity)
       break;
-    if (attempt == 1) { /* (W x M records cannot be exceeded: never expected) */
-      cleanup ();
+    if (attempt == 1) /* (W x M records cannot be exceeded: never expected) */
       return ACM_GPU_E_INTERNAL;
-    }
     /* a window of W symbols has at most W x M records: the second attempt cannot overflow */
     const uint64_t m = tally_max_outputs (plan);
     if (capacity / m < 16)
@@ -3869,13 +3850,11 @@ acm_gpu_tally_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_
   std::vector<uint64_t> add ((size_t)kw + 1);
   HOST_TRY (hipMemcpy (add.data (), d_tally, (size_t)kw * 8, hipMemcpyDeviceToHost));
   HOST_TRY (hipDeviceSynchronize ());
-  cleanup ();
   for (uint32_t k = 0; k < kw; k++)
     tally[k] += add[k];
   if (total)
     *total = out[0];
   return ACM_GPU_OK;
-#undef HOST_TRY
 }
 
 /* ------------------------------------------------------------------ leftmost-longest selection (include/acm_gpu.h, dev_select.h)
@@ -3892,8 +3871,7 @@ SelectLayout
 select_layout (const ACMPlan *plan, uint64_t capacity, uint64_t span) {
   SelectLayout L;
   L.n_chunks = (capacity + SELECT_CHUNK - 1) / SELECT_CHUNK;
-  size_t cub = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, cub, static_cast<uint32_t *> (nullptr), static_cast<uint32_t *> (nullptr), (int)(L.n_chunks + 1), nullptr);
+  const size_t cub = exclusive_sum_bytes (L.n_chunks + 1);
   L.cub_bytes = cub;
   /* the order pass's scratch; the candidates take its place when the order is made */
   L.work_bytes = std::max (acm_gpu_order_tmp_bytes (plan, capacity, span), (size_t)capacity * sizeof (ACMRecord) + 256);
@@ -3911,11 +3889,6 @@ select_layout (const ACMPlan *plan, uint64_t capacity, uint64_t span) {
   return L;
 }
 
-uint32_t
-select_lmax (const ACMPlan *plan) {
-  return flows_keep (plan) + 1;
-}
-
 /* ACM_GPU_SELECT_TILE=<candidates>: T (tests; read at every call) */
 uint32_t
 select_tile (void) {
@@ -3927,7 +3900,7 @@ select_tile (void) {
 bool
 select_tiled_form (const ACMPlan *plan) {
   const bool walk = getenv ("ACM_GPU_SELECT") && strcmp (getenv ("ACM_GPU_SELECT"), "walk") == 0;
-  return !walk && select_lmax (plan) <= select_tile ();
+  return !walk && plan_lmax (plan) <= select_tile ();
 }
 } // namespace
 
@@ -3970,7 +3943,7 @@ acm_gpu_select_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64
   K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
   K.pos_lo = pos_lo;
   K.span = span;
-  K.lmax = select_lmax (plan);
+  K.lmax = plan_lmax (plan);
   K.T = select_tile ();
   K.E = K.lmax < K.T ? K.lmax : K.T;
   K.keyed = reinterpret_cast<ACMRecord *> (t + L.o_keyed);
@@ -3985,12 +3958,10 @@ acm_gpu_select_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64
   K.out = d_out;
   K.d_count = reinterpret_cast<unsigned long long *> (d_count);
   K.ctl = reinterpret_cast<SelectCtl *> (t + L.o_ctl);
-  K.error = plan->scratch.d_total ? reinterpret_cast<unsigned int *> (plan->scratch.d_total) + 3 : nullptr;
-  const uint64_t most = (uint64_t)plan->cu_count * 8;
-  auto capped = [&] (uint64_t blocks) { return dim3 ((uint32_t)(blocks < 1 ? 1 : blocks < most ? blocks : most)); };
+  K.error = error_word (plan);
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (SelectCtl), st));
   /* a. keys, the records that break the contract out, the order by (start, length descending) */
-  hipLaunchKernelGGL (select_key_kernel, capped ((n + SELECT_THREADS - 1) / SELECT_THREADS), dim3 (SELECT_THREADS), 0, st, K);
+  hipLaunchKernelGGL (select_key_kernel, capped_grid (plan, (n + SELECT_THREADS - 1) / SELECT_THREADS), dim3 (SELECT_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
   hipLaunchKernelGGL (select_drop_kernel, dim3 (1), dim3 (SELECT_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
@@ -4011,11 +3982,11 @@ acm_gpu_select_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64
     }
   }
   /* b. the candidates */
-  hipLaunchKernelGGL (select_cand_kernel<false>, capped (L.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K);
+  hipLaunchKernelGGL (select_cand_kernel<false>, capped_grid (plan, L.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
   size_t cub = L.cub_bytes;
   HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.chunk_count, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(L.n_chunks + 1), st));
-  hipLaunchKernelGGL (select_cand_kernel<true>, capped (L.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K);
+  hipLaunchKernelGGL (select_cand_kernel<true>, capped_grid (plan, L.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
   if (!select_tiled_form (plan)) { /* f. */
     hipLaunchKernelGGL (select_walk_kernel, dim3 (1), dim3 (WAVE), 0, st, K);
@@ -4024,11 +3995,11 @@ acm_gpu_select_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64
   }
   /* c. d. e. */
   const size_t lds = select_tile_lds (K.T);
-  hipLaunchKernelGGL (select_tile_kernel<false>, capped (K.max_tiles), dim3 (SELECT_THREADS), lds, st, K);
+  hipLaunchKernelGGL (select_tile_kernel<false>, capped_grid (plan, K.max_tiles), dim3 (SELECT_THREADS), lds, st, K);
   HIP_TRY (hipGetLastError ());
   hipLaunchKernelGGL (select_resolve_kernel, dim3 (1), dim3 (SELECT_THREADS), 0, st, K);
   HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (select_tile_kernel<true>, capped (K.max_tiles), dim3 (SELECT_THREADS), lds, st, K);
+  hipLaunchKernelGGL (select_tile_kernel<true>, capped_grid (plan, K.max_tiles), dim3 (SELECT_THREADS), lds, st, K);
   HIP_TRY (hipGetLastError ());
   return ACM_GPU_OK;
 }
@@ -4061,47 +4032,18 @@ acm_gpu_scan_select_host (ACMPlan *plan, const void *text, uint64_t n_symbols, u
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
   const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, tmp_bytes = acm_gpu_scan_select_tmp_bytes (plan, capacity, n_symbols);
-  void *d_text = nullptr, *d_rec = nullptr, *d_tmp = nullptr, *d_count = nullptr;
-  uint64_t found = 0;
-  auto cleanup = [&] () {
-    for (void *p : { d_text, d_rec, d_tmp, d_count })
-      if (p)
-        (void)hipFree (p);
-  };
-#define HOST_TRY(expr)                                                                             \
-  do {                                                                                             \
-    hipError_t _e = (expr);                                                                        \
-    if (_e != hipSuccess) {                                                                        \
-      fprintf (stderr, "acm_gpu: %s failed: %s\n", #expr, hipGetErrorString (_e));                  \
-      cleanup ();                                                                                  \
-      return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
-    }                                                                                              \
-  } while (0)
-  HOST_TRY (hipMalloc (&d_text, tbytes ? tbytes : 16));
-  HOST_TRY (hipMalloc (&d_count, 8));
-  HOST_TRY (hipMalloc (&d_rec, capacity ? capacity * 16 : 16));
-  HOST_TRY (hipMalloc (&d_tmp, tmp_bytes ? tmp_bytes : 16));
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_count = nullptr;
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_count, 8));
+  HOST_TRY (temps.get (&d_rec, capacity * 16));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
   if (tbytes)
     HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  const int rc = acm_gpu_scan_select_device (plan, d_text, n_symbols, pos_base, static_cast<ACMRecord *> (d_rec), capacity,
-                                             static_cast<uint64_t *> (d_count), d_tmp, tmp_bytes, nullptr);
-  if (rc) {
-    (void)hipDeviceSynchronize ();
-    cleanup ();
-    return rc;
-  }
-  HOST_TRY (hipMemcpy (&found, d_count, 8, hipMemcpyDeviceToHost));
-  *n_found = found;
-  if (found > capacity) {
-    cleanup ();
-    return ACM_GPU_E_OVERFLOW;
-  }
-  if (found)
-    HOST_TRY (hipMemcpy (records, d_rec, found * 16, hipMemcpyDeviceToHost));
-  HOST_TRY (hipDeviceSynchronize ());
-  cleanup ();
-  return ACM_GPU_OK;
-#undef HOST_TRY
+  const int rc = acm_gpu_scan_select_device (plan, d_text, n_symbols, pos_base, d_rec, capacity, d_count, d_tmp, tmp_bytes, nullptr);
+  return download_records (rc, d_count, d_rec, records, capacity, n_found);
 }
 
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
@@ -4117,7 +4059,7 @@ acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint3
   };
   const uint64_t kw_max = (uint64_t)plan->covered_keywords + plan->finfo.n_keywords + plan->kw_base; /* (an upper bound: a delta's ids follow the plan's) */
   *pos_bits = bits (span ? span - 1 : 0);
-  *len_bits = bits (plan->finfo.lmax);
+  *len_bits = bits (plan_lmax (plan));
   *kw_bits = bits (kw_max);
   return *pos_bits + *len_bits + *kw_bits <= 64 ? ACM_GPU_OK : ACM_GPU_E_INELIGIBLE;
 }
@@ -4304,6 +4246,36 @@ acm_gpu_multi_shard_bounds (const ACMMulti *mu, uint64_t n, int shard, uint64_t 
 }
 
 namespace {
+/* waits for the stream of every device in use: all of them, whatever fails; the first failure */
+hipError_t
+drain (ACMMulti *mu) {
+  hipError_t first = hipSuccess;
+  for (size_t i = 0; i < mu->distinct.size (); i++) {
+    hipError_t e = hipSetDevice (mu->distinct[i]);
+    if (e == hipSuccess)
+      e = hipStreamSynchronize (mu->stream[i]);
+    if (first == hipSuccess)
+      first = e;
+  }
+  return first;
+}
+
+/* a device buffer kept from call to call, of at least `want` units (grow-only; *cap counts units) */
+template <typename T, typename N>
+hipError_t
+grow_to (T **buf, N *cap, N want, size_t unit_bytes) {
+  if (*cap >= want)
+    return hipSuccess;
+  if (*buf)
+    (void)hipFree (*buf);
+  *buf = nullptr;
+  *cap = 0;
+  const hipError_t e = hipMalloc (reinterpret_cast<void **> (buf), want * unit_bytes);
+  if (e == hipSuccess)
+    *cap = want;
+  return e;
+}
+
 /* shards scanned, ordered and gathered: d_text[r] on dev[r] holds [read_begin_r, own_end_r) */
 int
 multi_scan (ACMMulti *mu, const void *const *d_text, uint64_t n, ACMRecord *d_out, uint64_t capacity, uint64_t *n_found) {
@@ -4319,10 +4291,7 @@ multi_scan (ACMMulti *mu, const void *const *d_text, uint64_t n, ACMRecord *d_ou
     hipError_t _e = (expr);                                                                        \
     if (_e != hipSuccess) {                                                                        \
       fprintf (stderr, "acm_gpu: %s failed: %s (%s:%d)\n", #expr, hipGetErrorString (_e), __FILE__, __LINE__); \
-      for (size_t i_ = 0; i_ < mu->distinct.size (); i_++) {                                       \
-        (void)hipSetDevice (mu->distinct[i_]);                                                     \
-        (void)hipStreamSynchronize (mu->stream[i_]);                                               \
-      }                                                                                            \
+      (void)drain (mu);                                                                            \
       return _e == hipErrorOutOfMemory ? ACM_GPU_E_NOMEM : ACM_GPU_E_HIP;                          \
     }                                                                                              \
   } while (0)
@@ -4332,25 +4301,11 @@ multi_scan (ACMMulti *mu, const void *const *d_text, uint64_t n, ACMRecord *d_ou
     const Shard &s = sh[r];
     if (!B.cnt && hipMalloc (reinterpret_cast<void **> (&B.cnt), 8) != hipSuccess)
       return ACM_GPU_E_NOMEM;
-    if (B.rec_cap < want) {
-      if (B.rec)
-        (void)hipFree (B.rec);
-      B.rec = nullptr;
-      B.rec_cap = 0;
-      if (hipMalloc (reinterpret_cast<void **> (&B.rec), want * sizeof (ACMRecord)) != hipSuccess)
-        return ACM_GPU_E_NOMEM;
-      B.rec_cap = want;
-    }
+    if (grow_to (&B.rec, &B.rec_cap, want, sizeof (ACMRecord)) != hipSuccess)
+      return ACM_GPU_E_NOMEM;
     const size_t tb = s.e > s.b ? acm_gpu_scan_ordered_tmp_bytes (mu->plan[s.slot], B.rec_cap, s.e - s.rb) : 0;
-    if (B.tmp_cap < tb) {
-      if (B.tmp)
-        (void)hipFree (B.tmp);
-      B.tmp = nullptr;
-      B.tmp_cap = 0;
-      if (hipMalloc (&B.tmp, tb) != hipSuccess)
-        return ACM_GPU_E_NOMEM;
-      B.tmp_cap = tb;
-    }
+    if (grow_to (&B.tmp, &B.tmp_cap, tb, 1) != hipSuccess)
+      return ACM_GPU_E_NOMEM;
     return ACM_GPU_OK;
   };
   /* first pass: every shard into a record buffer sized by what the call before found on a text of
@@ -4377,10 +4332,7 @@ multi_scan (ACMMulti *mu, const void *const *d_text, uint64_t n, ACMRecord *d_ou
       }
       rc = ensure (r, want);
       if (rc) {
-        for (size_t i = 0; i < mu->distinct.size (); i++) {
-          (void)hipSetDevice (mu->distinct[i]);
-          (void)hipStreamSynchronize (mu->stream[i]);
-        }
+        (void)drain (mu);
         return rc;
       }
       /* (shards of one device share its stream: their scans run one after the other.)  Scan and
@@ -4389,10 +4341,7 @@ multi_scan (ACMMulti *mu, const void *const *d_text, uint64_t n, ACMRecord *d_ou
       if (s.e > s.b) {
         rc = acm_gpu_scan_ordered_device (mu->plan[s.slot], d_text[r], s.e - s.rb, s.b - s.rb, s.rb, B.rec, B.rec_cap, B.cnt, B.tmp, B.tmp_cap, mu->stream[s.slot]);
         if (rc) {
-          for (size_t i = 0; i < mu->distinct.size (); i++) {
-            (void)hipSetDevice (mu->distinct[i]);
-            (void)hipStreamSynchronize (mu->stream[i]);
-          }
+          (void)drain (mu);
           return rc;
         }
       } else
@@ -4401,10 +4350,7 @@ multi_scan (ACMMulti *mu, const void *const *d_text, uint64_t n, ACMRecord *d_ou
     }
     if (!any)
       break;
-    for (size_t i = 0; i < mu->distinct.size (); i++) {
-      MULTI_TRY (hipSetDevice (mu->distinct[i]));
-      MULTI_TRY (hipStreamSynchronize (mu->stream[i]));
-    }
+    MULTI_TRY (drain (mu));
   }
   uint64_t total = 0;
   for (size_t r = 0; r < R; r++) {
@@ -4426,12 +4372,7 @@ multi_scan (ACMMulti *mu, const void *const *d_text, uint64_t n, ACMRecord *d_ou
       remote += mu->h_found[r];
   if (remote > mu->stage0_cap && !wire_off) {
     MULTI_TRY (hipSetDevice (mu->dev[0]));
-    if (mu->stage0)
-      MULTI_TRY (hipFree (mu->stage0));
-    mu->stage0 = nullptr;
-    mu->stage0_cap = 0;
-    MULTI_TRY (hipMalloc (reinterpret_cast<void **> (&mu->stage0), remote * 8));
-    mu->stage0_cap = remote;
+    MULTI_TRY (grow_to (&mu->stage0, &mu->stage0_cap, remote, 8));
   }
   if (mu->arrived.size () < R)
     mu->arrived.resize (R, nullptr);
@@ -4458,10 +4399,7 @@ multi_scan (ACMMulti *mu, const void *const *d_text, uint64_t n, ACMRecord *d_ou
           rc = acm_gpu_unpack_records_device (mu->stage0 + soff, found, s.rb, pb, lb, d_out + off, mu->stream[0]);
         }
         if (rc) {
-          for (size_t i = 0; i < mu->distinct.size (); i++) {
-            (void)hipSetDevice (mu->distinct[i]);
-            (void)hipStreamSynchronize (mu->stream[i]);
-          }
+          (void)drain (mu);
           return rc;
         }
         soff += found;
@@ -4470,10 +4408,7 @@ multi_scan (ACMMulti *mu, const void *const *d_text, uint64_t n, ACMRecord *d_ou
     }
     off += found;
   }
-  for (size_t i = 0; i < mu->distinct.size (); i++) {
-    MULTI_TRY (hipSetDevice (mu->distinct[i]));
-    MULTI_TRY (hipStreamSynchronize (mu->stream[i]));
-  }
+  MULTI_TRY (drain (mu));
   for (size_t i = 0; i < mu->distinct.size () && !rc; i++)
     rc = acm_gpu_plan_status (mu->plan[i]);
   return rc;
@@ -4765,10 +4700,18 @@ route_plan (ACMachine *machine, ScanRoute *R) {
 }
 } // namespace
 
-extern "C" int
-acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
-  if (!machine || !n_found)
-    return ACM_GPU_E_ARG;
+namespace {
+/* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
+ * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally only a scan that
+ * succeeded, acm_select and acm_scan_from also one that found more records than there was room for. */
+enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
+
+/* what every machine-level call does around its scan: the route, the machine's plan lock, the
+ * cached plan (GPU paths), then host_loop (declared symbol size) or on_gpu (plan), the path for
+ * acm_scan_path, the unlock */
+template <typename HostLoop, typename OnGpu>
+int
+routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on_gpu) {
   ScanRoute R;
   int rc = scan_route (machine, &R);
   if (rc)
@@ -4777,84 +4720,62 @@ acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *r
   if (R.path != ACM_SCAN_PATH_CPU_LOOP)
     rc = route_plan (machine, &R);
   if (!rc) {
-    rc = R.path == ACM_SCAN_PATH_CPU_LOOP ? acm_internal_cpu_scan (machine, text, n_symbols, R.said, records, capacity, n_found)
-                                          : acm_gpu_scan_host (R.plan, text, n_symbols, 0, 0, records, capacity, n_found);
-    acm_internal_set_scan_path (machine, R.path);
+    rc = R.path == ACM_SCAN_PATH_CPU_LOOP ? host_loop (R.said) : on_gpu (R.plan);
+    if (record == RecordPath::Always || !rc || (record == RecordPath::OnSuccessOrOverflow && rc == ACM_GPU_E_OVERFLOW))
+      acm_internal_set_scan_path (machine, R.path);
   }
   acm_internal_plan_unlock (machine);
   return rc;
 }
+} // namespace
 
-/* the same on a batch of texts (include/acm_gpu.h): same route, same cached plan, same lock */
+/* The five calls below run on the same route, the same cached plan, under the same lock. */
+extern "C" int
+acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
+  if (!machine || !n_found)
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::Always, [&] (uint32_t said) { return acm_internal_cpu_scan (machine, text, n_symbols, said, records, capacity, n_found); },
+    [&] (ACMPlan *plan) { return acm_gpu_scan_host (plan, text, n_symbols, 0, 0, records, capacity, n_found); });
+}
+
+/* the same on a batch of texts (include/acm_gpu.h) */
 extern "C" int
 acm_scan_batch (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, ACMRecord *records, uint32_t *text_id,
                 uint64_t *first, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found || n_texts >= (1ull << 32) || (capacity && !records) || !batch_offsets_ok (offsets, n_texts) ||
       (offsets[n_texts] && !text))
     return ACM_GPU_E_ARG;
-  ScanRoute R;
-  int rc = scan_route (machine, &R);
-  if (rc)
-    return rc;
-  acm_internal_plan_lock (machine);
-  if (R.path != ACM_SCAN_PATH_CPU_LOOP)
-    rc = route_plan (machine, &R);
-  if (!rc) {
-    rc = R.path == ACM_SCAN_PATH_CPU_LOOP
-           ? acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, R.said, records, text_id, first, capacity, n_found)
-           : acm_gpu_scan_batch_host (R.plan, text, offsets, n_texts, records, text_id, first, capacity, n_found);
-    acm_internal_set_scan_path (machine, R.path);
-  }
-  acm_internal_plan_unlock (machine);
-  return rc;
+  return routed_scan (
+    machine, RecordPath::Always,
+    [&] (uint32_t said) { return acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, said, records, text_id, first, capacity, n_found); },
+    [&] (ACMPlan *plan) { return acm_gpu_scan_batch_host (plan, text, offsets, n_texts, records, text_id, first, capacity, n_found); });
 }
 
-/* the per-keyword tally (include/acm_gpu.h): same route, same cached plan, same lock */
+/* the per-keyword tally (include/acm_gpu.h) */
 extern "C" int
 acm_tally (ACMachine *machine, const void *text, uint64_t n_symbols, uint64_t *tally, uint64_t n_keywords, uint64_t *total) {
   if (!machine || !tally || (n_symbols && !text))
     return ACM_GPU_E_ARG;
-  ScanRoute R;
-  int rc = scan_route (machine, &R);
-  if (rc)
-    return rc;
-  acm_internal_plan_lock (machine);
-  if (R.path != ACM_SCAN_PATH_CPU_LOOP)
-    rc = route_plan (machine, &R);
-  if (!rc) {
-    rc = R.path == ACM_SCAN_PATH_CPU_LOOP ? acm_internal_cpu_tally (machine, text, n_symbols, R.said, tally, n_keywords, total)
-                                          : acm_gpu_tally_host (R.plan, text, n_symbols, tally, n_keywords, total);
-    if (!rc)
-      acm_internal_set_scan_path (machine, R.path);
-  }
-  acm_internal_plan_unlock (machine);
-  return rc;
+  return routed_scan (
+    machine, RecordPath::OnSuccess, [&] (uint32_t said) { return acm_internal_cpu_tally (machine, text, n_symbols, said, tally, n_keywords, total); },
+    [&] (ACMPlan *plan) { return acm_gpu_tally_host (plan, text, n_symbols, tally, n_keywords, total); });
 }
 
-/* the leftmost-longest selection (include/acm_gpu.h): same route, same cached plan, same lock */
+/* the leftmost-longest selection (include/acm_gpu.h) */
 extern "C" int
 acm_select (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found || (n_symbols && !text) || (capacity && !records))
     return ACM_GPU_E_ARG;
-  ScanRoute R;
-  int rc = scan_route (machine, &R);
-  if (rc)
-    return rc;
-  acm_internal_plan_lock (machine);
-  if (R.path != ACM_SCAN_PATH_CPU_LOOP)
-    rc = route_plan (machine, &R);
-  if (!rc) {
-    if (R.path == ACM_SCAN_PATH_CPU_LOOP) {
-      rc = acm_internal_cpu_scan (machine, text, n_symbols, R.said, records, capacity, n_found);
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      const int rc = acm_internal_cpu_scan (machine, text, n_symbols, said, records, capacity, n_found);
       if (!rc)
         *n_found = acm_select_records (records, *n_found);
-    } else
-      rc = acm_gpu_scan_select_host (R.plan, text, n_symbols, 0, records, capacity, n_found);
-    if (!rc || rc == ACM_GPU_E_OVERFLOW)
-      acm_internal_set_scan_path (machine, R.path);
-  }
-  acm_internal_plan_unlock (machine);
-  return rc;
+      return rc;
+    },
+    [&] (ACMPlan *plan) { return acm_gpu_scan_select_host (plan, text, n_symbols, 0, records, capacity, n_found); });
 }
 
 /* acm_scan continued from a cursor (include/acm_gpu.h): the reference's own `const ACState *`, in
@@ -4867,37 +4788,28 @@ acm_scan_from (ACMachine *machine, const ACState **cursor, const void *text, uin
                uint64_t *n_found) {
   if (!machine || !cursor || !*cursor || (*cursor)->machine != machine || !n_found || (n_symbols && !text) || (capacity && !records))
     return ACM_GPU_E_ARG;
-  ScanRoute R;
-  int rc = scan_route (machine, &R);
-  if (rc)
-    return rc;
-  acm_internal_plan_lock (machine);
-  if (R.path != ACM_SCAN_PATH_CPU_LOOP)
-    rc = route_plan (machine, &R);
-  if (!rc && R.path == ACM_SCAN_PATH_CPU_LOOP)
-    rc = acm_internal_cpu_scan_from (machine, cursor, text, n_symbols, R.said, records, capacity, n_found);
-  else if (!rc) {
-    const uint32_t sb = R.plan->text_sym_bytes;
-    const uint64_t depth = (*cursor)->depth;
-    std::vector<unsigned char> spelling ((size_t)depth * sb);
-    uint64_t k = depth;
-    for (const ACState *s = *cursor; s->parent; s = s->parent)
-      memcpy (spelling.data () + (size_t)--k * sb, s->letter, sb);
-    rc = scan_host_prefixed (R.plan, spelling.data (), depth, text, n_symbols, depth, 0, records, capacity, n_found);
-    if (!rc) {
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) { return acm_internal_cpu_scan_from (machine, cursor, text, n_symbols, said, records, capacity, n_found); },
+    [&] (ACMPlan *plan) {
+      const uint32_t sb = plan->text_sym_bytes;
+      const uint64_t depth = (*cursor)->depth;
+      std::vector<unsigned char> spelling ((size_t)depth * sb);
+      uint64_t k = depth;
+      for (const ACState *s = *cursor; s->parent; s = s->parent)
+        memcpy (spelling.data () + (size_t)--k * sb, s->letter, sb);
+      const int rc = scan_host_prefixed (plan, spelling.data (), depth, text, n_symbols, depth, 0, records, capacity, n_found);
+      if (rc)
+        return rc;
       for (uint64_t r = 0; r < *n_found; r++)
         records[r].end_pos -= depth;
-      const uint64_t all = depth + n_symbols, lmax = (uint64_t)flows_keep (R.plan) + 1;
+      const uint64_t all = depth + n_symbols, lmax = plan_lmax (plan);
       const ACState *s = acm_internal_root (machine);
       for (uint64_t i = all > lmax ? all - lmax : 0; i < all; i++)
         (void)acm_match (&s, i < depth ? spelling.data () + (size_t)i * sb : static_cast<const unsigned char *> (text) + (size_t)(i - depth) * sb);
       *cursor = s;
-    }
-  }
-  if (!rc || rc == ACM_GPU_E_OVERFLOW)
-    acm_internal_set_scan_path (machine, R.path);
-  acm_internal_plan_unlock (machine);
-  return rc;
+      return rc;
+    });
 }
 
 #ifdef ACM_DIAG
