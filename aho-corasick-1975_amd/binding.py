@@ -89,6 +89,8 @@ EXPORTS = [
     "acm_gpu_tally_tmp_bytes", "acm_gpu_tally_device", "acm_gpu_tally_form", "acm_gpu_tally_keywords", "acm_gpu_tally_host", "acm_tally",
     "acm_select_records", "acm_gpu_select_tmp_bytes", "acm_gpu_select_records_device", "acm_gpu_select_form",
     "acm_gpu_scan_select_tmp_bytes", "acm_gpu_scan_select_device", "acm_gpu_scan_select_host", "acm_select",
+    "acm_replace_records", "acm_gpu_replace_tmp_bytes", "acm_gpu_replace_records_device", "acm_gpu_scan_replace_tmp_bytes",
+    "acm_gpu_scan_replace_device", "acm_gpu_scan_replace_host", "acm_replace",
 ]
 
 
@@ -272,6 +274,20 @@ def lib():
     L.acm_gpu_scan_select_host.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
     L.acm_select.restype = i32
     L.acm_select.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_replace_records.restype = i32
+    L.acm_replace_records.argtypes = [vp, u64, u32, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_replace_tmp_bytes.restype = sz
+    L.acm_gpu_replace_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_replace_records_device.restype = i32
+    L.acm_gpu_replace_records_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, vp, u64, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_replace_tmp_bytes.restype = sz
+    L.acm_gpu_scan_replace_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_scan_replace_device.restype = i32
+    L.acm_gpu_scan_replace_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, vp, u64, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_replace_host.restype = i32
+    L.acm_gpu_scan_replace_host.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_replace.restype = i32
+    L.acm_replace.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.acm_gpu_flows_create.restype = i32
     L.acm_gpu_flows_create.argtypes = [vp, u64, C.POINTER(vp)]
     L.acm_gpu_flows_destroy.restype = None
@@ -306,6 +322,59 @@ def select_records(array):
     a = np.array(array, dtype=RECORD_DTYPE, copy=True).reshape(-1)
     n = lib().acm_select_records(a.ctypes.data if a.size else None, a.size)
     return a[:n]
+
+
+def replacement_table(replacements, sym_size, fill=None):
+    """(repl_data, repl_off, n_keywords) of the replace calls.  `replacements`: one entry per keyword, in
+    keyword_id order, each `bytes` (one symbol per byte, as Machine.add_keyword takes them; raw bytes
+    for a symbol size numpy has no type for) or an array of symbols, possibly empty.  `fill`: ONE
+    symbol instead (mask mode): repl_off is None then."""
+    dtype = _SYM_DTYPE.get(sym_size, np.uint8)
+    per = sym_size // np.dtype(dtype).itemsize                      # array entries per symbol
+    assert (replacements is None) != (fill is None), "either replacements or fill"
+
+    def symbols(x):
+        if isinstance(x, (bytes, bytearray)):
+            x = np.frombuffer(bytes(x), dtype=np.uint8)
+        a = np.ascontiguousarray(x, dtype=dtype).reshape(-1)
+        assert a.size % per == 0
+        return a
+    if fill is not None:
+        one = symbols(fill) if isinstance(fill, (bytes, bytearray, np.ndarray, list, tuple)) else np.array([fill], dtype=dtype)
+        assert one.size == per, "fill is one symbol"
+        return one, None, 0
+    parts = [symbols(r) for r in replacements]
+    off = np.zeros(len(parts) + 1, np.uint64)
+    if parts:
+        np.cumsum([p.size // per for p in parts], out=off[1:])
+    data = np.concatenate(parts + [np.zeros(per, dtype)])           # (never empty: the calls want an address)
+    return data, off, len(parts)
+
+
+def replace_records(text, records, replacements=None, fill=None, pos_base=0, sym_size=None, out_capacity=None):
+    """acm_replace_records(): `text` (an array of symbols; with sym_size, raw bytes of symbols of that
+    size) with every record of `records` (a selection: RECORD_DTYPE, canonical order, no two sharing a
+    symbol) replaced by its keyword's entry of `replacements`, or masked with `fill`; the sequential
+    pass on the host.  Returns the new array.  out_capacity (symbols; None: what the output needs)."""
+    t = np.ascontiguousarray(text)
+    sb = int(sym_size) if sym_size is not None else t.itemsize
+    n_sym = t.size * t.itemsize // sb
+    rec = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
+    data, off, nk = replacement_table(replacements, sb, fill)
+    need = C.c_uint64(0)
+
+    def call(out, cap):
+        return lib().acm_replace_records(t.ctypes.data if t.size else None, n_sym, sb, pos_base, rec.ctypes.data if rec.size else None, rec.size,
+                                         data.ctypes.data, off.ctypes.data if off is not None else None, nk,
+                                         out.ctypes.data if out is not None else None, cap, C.byref(need))
+    if out_capacity is None:
+        rc = call(None, 0)
+        if rc not in (ACM_GPU_OK, ACM_GPU_E_OVERFLOW):
+            _check(rc, "acm_replace_records")
+        out_capacity = int(need.value)
+    out = np.zeros(max(int(out_capacity) * sb // t.itemsize, 1), dtype=t.dtype)
+    _check(call(out, int(out_capacity)), "acm_replace_records")
+    return out[:int(need.value) * sb // t.itemsize]
 
 
 class FlatTables:
@@ -642,6 +711,40 @@ class Machine:
             return out[:n.value]
 
 
+    def replace(self, text, replacements=None, fill=None, out_capacity=None):
+        """acm_replace(): `text` with its leftmost-longest non-overlapping matches (select()) replaced:
+        by `replacements`, a list with one entry per keyword in keyword_id order (`bytes` or arrays
+        of symbols, an empty one deletes the match), or every symbol of every match by the ONE symbol
+        `fill`.  Returns (the new text as an array of the machine's symbols, the number of matches
+        replaced).  out_capacity (symbols): by default an output overflow is repeated once with the
+        size the call reports."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        data, off, nk = replacement_table(replacements, self.sym_size, fill)
+        cap = int(out_capacity) if out_capacity is not None else n_sym + 1024
+        for attempt in (0, 1):
+            out = np.zeros(max(cap * self.sym_size // t.itemsize, 1), dtype=t.dtype)
+            need, m = C.c_uint64(0), C.c_uint64(0)
+            rc = self.L.acm_replace(self.handle, t.ctypes.data if t.size else None, n_sym, data.ctypes.data,
+                                    off.ctypes.data if off is not None else None, nk, out.ctypes.data, cap, C.byref(need), C.byref(m))
+            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
+                cap = int(need.value)
+                continue
+            _check(rc, "acm_replace")
+            return out[:int(need.value) * self.sym_size // t.itemsize], int(m.value)
+
+
+class Replaced:
+    """What Plan.replace_records() and Plan.scan_replace() leave on the device: `out` (a uint8 tensor,
+    the first out_symbols symbols are the new text when out_symbols <= out_capacity), out_symbols and
+    count (Python ints, read after a synchronise), records (the selection: int64 [capacity, 2]),
+    out_start (an int64 tensor, one entry per record, or None)."""
+
+    def __init__(self, out, out_symbols, out_capacity, records, count, out_start):
+        self.out, self.out_symbols, self.out_capacity = out, out_symbols, out_capacity
+        self.records, self.count, self.out_start = records, count, out_start
+
+
 class Plan:
     """Device-resident flattened automaton (ACMPlan).  Scans take torch CUDA tensors (device
     memory and streams are torch's; the kernels are this library's)."""
@@ -942,6 +1045,94 @@ class Plan:
                 continue
             _check(rc, "acm_gpu_scan_select_host")
             return out[:n.value]
+
+    def _replace_inputs(self, text, n_symbols, replacements, fill, out, out_capacity, most_records):
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        data, off, nk = replacement_table(replacements, self.sym_size, fill)
+        d_data = torch.from_numpy(data.view(np.uint8).copy()).to(text.device)
+        d_off = torch.from_numpy(off.view(np.int64).copy()).to(text.device) if off is not None else None
+        if out_capacity is None:
+            if out is not None:
+                out_capacity = out.numel() * out.element_size() // self.sym_size
+            else:                                                   # every record grows the text by less than the longest replacement
+                longest = int(np.diff(off.astype(np.int64)).max()) if off is not None and nk else 1
+                out_capacity = n_symbols + most_records * max(longest - 1, 0)
+        if out is None:
+            out = torch.empty(max(out_capacity * self.sym_size, 16), dtype=torch.uint8, device=text.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= out_capacity * self.sym_size
+        return n_symbols, d_data, d_off, nk, out, int(out_capacity)
+
+    def replace_records(self, text, records, n, replacements=None, fill=None, pos_base=0, n_symbols=None, out=None, out_capacity=None,
+                        out_start=False, count=None):
+        """acm_gpu_replace_records_device(): `text` (a device tensor) with the selection records[:n] (an
+        int64 [capacity, 2] device tensor: canonical order, no two records sharing a symbol) replaced
+        by `replacements` (one entry per keyword, see replacement_table) or masked with `fill`, into
+        `out` (None: a new uint8 tensor; it must not overlap `text`).  `count` (a device int64 tensor)
+        gives the number of records on the device: n is the room of `records` then.  Returns a
+        Replaced; synchronises to read out_symbols."""
+        import torch
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
+        n = int(n)
+        n_symbols, d_data, d_off, nk, out, out_capacity = self._replace_inputs(text, n_symbols, replacements, fill, out, out_capacity, n)
+        res = torch.zeros(1, dtype=torch.int64, device=text.device)
+        starts = torch.zeros(max(n, 1), dtype=torch.int64, device=text.device) if out_start else None
+        tb = lib().acm_gpu_replace_tmp_bytes(self.h, n, n_symbols)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        _check(lib().acm_gpu_replace_records_device(self.h, text.data_ptr(), n_symbols, pos_base, records.data_ptr(), n,
+                                                    count.data_ptr() if count is not None else None, d_data.data_ptr(),
+                                                    d_off.data_ptr() if d_off is not None else None, nk, out.data_ptr(), out_capacity,
+                                                    res.data_ptr(), starts.data_ptr() if out_start else None, tmp.data_ptr(), tmp.numel(),
+                                                    self._stream()), "acm_gpu_replace_records_device")
+        return Replaced(out, int(res.item()), out_capacity, records, int(count.item()) if count is not None else n, starts)
+
+    def scan_replace(self, text, replacements=None, fill=None, n_symbols=None, pos_base=0, capacity=None, records=None, out=None,
+                     out_capacity=None, out_start=False):
+        """acm_gpu_scan_replace_device(): the ordered scan of a device tensor, the leftmost-longest
+        selection of its records and the replacement, queued on the current stream.  `capacity` must
+        hold ALL matches.  Returns a Replaced: count > capacity is the number of ALL matches (nothing
+        was replaced, out_symbols is 0); out_symbols > out_capacity is the room the output needs.
+        Synchronises to read the two."""
+        import torch
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        if records is None:
+            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+            records = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=text.device)
+        else:
+            cap = records.shape[0] if capacity is None else int(capacity)
+        n_symbols, d_data, d_off, nk, out, out_capacity = self._replace_inputs(text, n_symbols, replacements, fill, out, out_capacity, cap)
+        res = torch.zeros(2, dtype=torch.int64, device=text.device)
+        starts = torch.zeros(max(cap, 1), dtype=torch.int64, device=text.device) if out_start else None
+        tb = lib().acm_gpu_scan_replace_tmp_bytes(self.h, cap, n_symbols)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        _check(lib().acm_gpu_scan_replace_device(self.h, text.data_ptr(), n_symbols, pos_base, records.data_ptr(), cap, res.data_ptr(),
+                                                 d_data.data_ptr(), d_off.data_ptr() if d_off is not None else None, nk, out.data_ptr(),
+                                                 out_capacity, res.data_ptr() + 8, starts.data_ptr() if out_start else None, tmp.data_ptr(),
+                                                 tmp.numel(), self._stream()), "acm_gpu_scan_replace_device")
+        count, out_symbols = (int(x) for x in res.cpu())
+        return Replaced(out, out_symbols, out_capacity, records, count, starts)
+
+    def scan_replace_host(self, text, replacements=None, fill=None, out_capacity=None):
+        """acm_gpu_scan_replace_host(): numpy in, (the new text, the number of matches replaced) out,
+        through the C ABI only (no torch).  No record capacity: the call counts the matches first.  An
+        output overflow is repeated once with the size the call reports when out_capacity is None."""
+        t = np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        data, off, nk = replacement_table(replacements, self.sym_size, fill)
+        cap = int(out_capacity) if out_capacity is not None else n_sym + 1024
+        for attempt in (0, 1):
+            out = np.zeros(max(cap * self.sym_size // t.itemsize, 1), dtype=t.dtype)
+            need, m = C.c_uint64(0), C.c_uint64(0)
+            rc = lib().acm_gpu_scan_replace_host(self.h, t.ctypes.data if t.size else None, n_sym, data.ctypes.data,
+                                                 off.ctypes.data if off is not None else None, nk, out.ctypes.data, cap, C.byref(need), C.byref(m))
+            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
+                cap = int(need.value)
+                continue
+            _check(rc, "acm_gpu_scan_replace_host")
+            return out[:int(need.value) * self.sym_size // t.itemsize], int(m.value)
 
     def stream(self, max_piece_symbols, record_capacity):
         return Stream(self, max_piece_symbols, record_capacity)

@@ -296,6 +296,14 @@ exclusive_sum_bytes (uint64_t n) {
   return bytes;
 }
 
+/* the same over n signed 64-bit sums */
+size_t
+exclusive_sum_bytes64 (uint64_t n) {
+  size_t bytes = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, bytes, static_cast<long long *> (nullptr), static_cast<long long *> (nullptr), (int)n, nullptr);
+  return bytes;
+}
+
 /* the longest keyword of the plan and of its delta.  acm_gpu_plan_update keeps plan->finfo.lmax at
  * the maximum of both ("halos and sort keys go by the longest keyword of both"), so this equals
  * plan->finfo.lmax; the form says what is meant */
@@ -4046,6 +4054,228 @@ acm_gpu_scan_select_host (ACMPlan *plan, const void *text, uint64_t n_symbols, u
   return download_records (rc, d_count, d_rec, records, capacity, n_found);
 }
 
+/* ------------------------------------------------------------------ search-and-replace (include/acm_gpu.h, dev_replace.h)
+ * The passes behind a selection: validate and measure, the prefix over the chunks and the records'
+ * places in the output, the output itself. */
+namespace {
+struct ReplaceLayout {
+  uint64_t n_chunks = 0;
+  size_t o_ctl = 0, o_sum = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, o_start = 0, total = 0;
+};
+ReplaceLayout
+replace_layout (uint64_t capacity) {
+  ReplaceLayout L;
+  L.n_chunks = (capacity + REPLACE_CHUNK - 1) / REPLACE_CHUNK;
+  L.cub_bytes = exclusive_sum_bytes64 (L.n_chunks + 1);
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (ReplaceCtl));
+  L.o_sum = blob_reserve (cur, (L.n_chunks + 1) * 8);
+  L.o_begin = blob_reserve (cur, (L.n_chunks + 1) * 8);
+  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
+  L.o_start = blob_reserve (cur, (size_t)(capacity ? capacity : 1) * 8);
+  L.total = cur + 256;
+  return L;
+}
+
+/* ACM_GPU_REPLACE_TILE=<bytes of output>: pass c's tile, a multiple of 16 (tests; read at every call) */
+uint32_t
+replace_tile (void) {
+  const int t = env_int ("ACM_GPU_REPLACE_TILE", (int)REPLACE_TILE_DEFAULT);
+  return t >= (int)REPLACE_TILE_MIN && t <= (int)REPLACE_TILE_MAX && t % 16 == 0 ? (uint32_t)t : REPLACE_TILE_DEFAULT;
+}
+
+/* table mode: the table has an entry for every keyword the plan can report */
+bool
+replace_table_covers (const ACMPlan *plan, const uint64_t *repl_off, uint64_t n_keywords) {
+  return !repl_off || n_keywords >= plan->covered_keywords;
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_replace_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_symbols) {
+  (void)n_symbols; /* (the passes keep nothing per symbol) */
+  if (!plan || n_or_capacity >= (1ull << 31))
+    return 0;
+  return replace_layout (n_or_capacity).total;
+}
+
+namespace {
+/* the passes, with the layout of their scratch (made once per call) */
+int
+replace_records (ACMPlan *plan, const ReplaceLayout &L, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const ACMRecord *d_sel, uint64_t n,
+                 const uint64_t *d_n, const void *d_repl_data, const uint64_t *d_repl_off, uint64_t n_keywords, void *d_out, uint64_t out_capacity,
+                 uint64_t *d_out_symbols, int64_t *d_out_start, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_out_symbols || !d_tmp || n >= (1ull << 31) || (n_symbols && !d_text) || (out_capacity && !d_out) || (n && !d_sel) ||
+      (!d_repl_off && !d_repl_data) || n_keywords >= (1ull << 32))
+    return ACM_GPU_E_ARG;
+  const uint32_t sb = plan->text_sym_bytes;
+  const uintptr_t t0 = reinterpret_cast<uintptr_t> (d_text), o0 = reinterpret_cast<uintptr_t> (d_out);
+  if (t0 % sb || o0 % sb || reinterpret_cast<uintptr_t> (d_repl_data) % sb || n_symbols >= (1ull << 56) / sb || out_capacity >= (1ull << 56) / sb)
+    return ACM_GPU_E_ARG;
+  if (n_symbols && out_capacity && t0 < o0 + out_capacity * sb && o0 < t0 + n_symbols * sb) /* the output is built from the text beside it */
+    return ACM_GPU_E_ARG;
+  if (tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  ReplaceK K{};
+  K.sel = d_sel;
+  K.capacity = n;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.text = static_cast<const unsigned char *> (d_text);
+  K.n_symbols = n_symbols;
+  K.pos_base = pos_base;
+  K.sb = sb;
+  K.tile_words = replace_tile () / 16;
+  K.repl = static_cast<const unsigned char *> (d_repl_data);
+  K.repl_off = reinterpret_cast<const unsigned long long *> (d_repl_off);
+  K.n_keywords = n_keywords;
+  K.chunk_sum = reinterpret_cast<long long *> (t + L.o_sum);
+  K.chunk_begin = reinterpret_cast<const long long *> (t + L.o_begin);
+  K.n_chunks = L.n_chunks;
+  K.out_start = reinterpret_cast<long long *> (t + L.o_start);
+  K.d_out_start = reinterpret_cast<long long *> (d_out_start);
+  K.out = static_cast<unsigned char *> (d_out);
+  K.out_capacity = out_capacity;
+  K.d_out_symbols = reinterpret_cast<unsigned long long *> (d_out_symbols);
+  K.ctl = reinterpret_cast<ReplaceCtl *> (t + L.o_ctl);
+  K.error = error_word (plan);
+  const bool mask = d_repl_off == nullptr;
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (ReplaceCtl), st));
+  /* a. */
+  const dim3 chunks_grid = capped_grid (plan, std::max (L.n_chunks + 1, mask ? (uint64_t)0 : (n_keywords + REPLACE_THREADS - 1) / REPLACE_THREADS));
+  if (mask)
+    hipLaunchKernelGGL (replace_measure_kernel<true>, chunks_grid, dim3 (REPLACE_THREADS), 0, st, K);
+  else
+    hipLaunchKernelGGL (replace_measure_kernel<false>, chunks_grid, dim3 (REPLACE_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  /* b. */
+  size_t cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.chunk_sum, reinterpret_cast<long long *> (t + L.o_begin), (int)(L.n_chunks + 1), st));
+  if (mask)
+    hipLaunchKernelGGL (replace_starts_kernel<true>, capped_grid (plan, L.n_chunks), dim3 (REPLACE_THREADS), 0, st, K);
+  else
+    hipLaunchKernelGGL (replace_starts_kernel<false>, capped_grid (plan, L.n_chunks), dim3 (REPLACE_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  /* c. the grid by the room of the output, not by what the passes found */
+  const uint64_t tiles = (out_capacity * sb + 15 + 16) / ((uint64_t)K.tile_words * 16) + 1;
+  if (mask)
+    hipLaunchKernelGGL (replace_build_kernel<true>, capped_grid (plan, tiles), dim3 (REPLACE_THREADS), 0, st, K);
+  else
+    hipLaunchKernelGGL (replace_build_kernel<false>, capped_grid (plan, tiles), dim3 (REPLACE_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  return ACM_GPU_OK;
+}
+
+} // namespace
+
+extern "C" int
+acm_gpu_replace_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const ACMRecord *d_sel,
+                                uint64_t n, const uint64_t *d_n, const void *d_repl_data, const uint64_t *d_repl_off, uint64_t n_keywords,
+                                void *d_out, uint64_t out_capacity, uint64_t *d_out_symbols, int64_t *d_out_start, void *d_tmp, size_t tmp_bytes,
+                                void *stream) {
+  if (!plan || n >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  return replace_records (plan, replace_layout (n), d_text, n_symbols, pos_base, d_sel, n, d_n, d_repl_data, d_repl_off, n_keywords, d_out,
+                          out_capacity, d_out_symbols, d_out_start, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" size_t
+acm_gpu_scan_replace_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols) {
+  if (!plan || capacity >= (1ull << 31))
+    return 0;
+  /* (the selection has ended when the replace passes begin: they read d_records) */
+  return std::max (acm_gpu_scan_select_tmp_bytes (plan, capacity, n_symbols), acm_gpu_replace_tmp_bytes (plan, capacity, n_symbols));
+}
+
+extern "C" int
+acm_gpu_scan_replace_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, ACMRecord *d_records, uint64_t capacity,
+                             uint64_t *d_count, const void *d_repl_data, const uint64_t *d_repl_off, uint64_t n_keywords, void *d_out,
+                             uint64_t out_capacity, uint64_t *d_out_symbols, int64_t *d_out_start, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || !d_out_symbols || !d_tmp || capacity >= (1ull << 31) || (n_symbols && !d_text) || (capacity && !d_records) ||
+      (out_capacity && !d_out) || (!d_repl_off && !d_repl_data) || !replace_table_covers (plan, d_repl_off, n_keywords))
+    return ACM_GPU_E_ARG;
+  const ReplaceLayout L = replace_layout (capacity);
+  if (tmp_bytes < std::max (acm_gpu_scan_select_tmp_bytes (plan, capacity, n_symbols), L.total))
+    return ACM_GPU_E_ARG;
+  const int rc = acm_gpu_scan_select_device (plan, d_text, n_symbols, pos_base, d_records, capacity, d_count, d_tmp, tmp_bytes, stream);
+  if (rc)
+    return rc;
+  return replace_records (plan, L, d_text, n_symbols, pos_base, d_records, capacity, d_count, d_repl_data, d_repl_off, n_keywords, d_out, out_capacity,
+                          d_out_symbols, d_out_start, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_replace_host (ACMPlan *plan, const void *text, uint64_t n_symbols, const void *repl_data, const uint64_t *repl_off, uint64_t n_keywords,
+                           void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_replaced) {
+  if (!plan || !out_symbols || (n_symbols && !text) || (out_capacity && !out) || (!repl_off && !repl_data) ||
+      !replace_table_covers (plan, repl_off, n_keywords) || n_keywords >= (1ull << 32))
+    return ACM_GPU_E_ARG;
+  const uint32_t sb = plan->text_sym_bytes;
+  if (repl_off) {
+    if (repl_off[0] != 0)
+      return ACM_GPU_E_ARG;
+    for (uint64_t k = 0; k < n_keywords; k++)
+      if (repl_off[k] > repl_off[k + 1])
+        return ACM_GPU_E_ARG;
+    if (repl_off[n_keywords] && !repl_data)
+      return ACM_GPU_E_ARG;
+  }
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * sb, obytes = (size_t)out_capacity * sb;
+  const size_t rbytes = (size_t)(repl_off ? repl_off[n_keywords] : 1) * sb;
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr, *d_repl = nullptr, *d_out = nullptr;
+  uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the count, the output's symbols */
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_res, 16));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  /* the record room is the exact number of matches: the caller gives none and sees no record overflow */
+  uint64_t matches = 0;
+  int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_res, nullptr);
+  if (rc) {
+    (void)hipDeviceSynchronize ();
+    return rc;
+  }
+  HOST_TRY (hipMemcpy (&matches, d_res, 8, hipMemcpyDeviceToHost));
+  if (matches >= (1ull << 31)) /* (acm_gpu_scan_select_device's limit) */
+    return ACM_GPU_E_ARG;
+  const size_t tmp_bytes = acm_gpu_scan_replace_tmp_bytes (plan, matches, n_symbols);
+  HOST_TRY (temps.get (&d_rec, matches * 16));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  HOST_TRY (temps.get (&d_repl, rbytes));
+  HOST_TRY (temps.get (&d_out, obytes));
+  if (rbytes && repl_data)
+    HOST_TRY (hipMemcpy (d_repl, repl_data, rbytes, hipMemcpyHostToDevice));
+  if (repl_off) {
+    HOST_TRY (temps.get (&d_off, (n_keywords + 1) * 8));
+    HOST_TRY (hipMemcpy (d_off, repl_off, (n_keywords + 1) * 8, hipMemcpyHostToDevice));
+  }
+  rc = acm_gpu_scan_replace_device (plan, d_text, n_symbols, 0, d_rec, matches, d_res, d_repl, d_off, n_keywords, d_out, out_capacity, d_res + 1,
+                                    nullptr, d_tmp, tmp_bytes, nullptr);
+  if (!rc)
+    rc = acm_gpu_plan_status (plan); /* (waits for the device) */
+  if (rc) {
+    (void)hipDeviceSynchronize ();
+    return rc;
+  }
+  uint64_t res[2] = { 0, 0 };
+  HOST_TRY (hipMemcpy (res, d_res, 16, hipMemcpyDeviceToHost));
+  if (res[0] > matches) /* (the scan found more than the count said: never expected) */
+    return ACM_GPU_E_INTERNAL;
+  *out_symbols = res[1];
+  if (n_replaced)
+    *n_replaced = res[0];
+  if (res[1] > out_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (res[1])
+    HOST_TRY (hipMemcpy (out, d_out, (size_t)res[1] * sb, hipMemcpyDeviceToHost));
+  return ACM_GPU_OK;
+}
+
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
 extern "C" int
 acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint32_t *len_bits, uint32_t *kw_bits) {
@@ -4703,7 +4933,8 @@ route_plan (ACMachine *machine, ScanRoute *R) {
 namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally only a scan that
- * succeeded, acm_select and acm_scan_from also one that found more records than there was room for. */
+ * succeeded, acm_select and acm_scan_from also one that found more records than there was room for,
+ * acm_replace also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -4729,7 +4960,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The five calls below run on the same route, the same cached plan, under the same lock. */
+/* The six calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -4776,6 +5007,46 @@ acm_select (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord 
       return rc;
     },
     [&] (ACMPlan *plan) { return acm_gpu_scan_select_host (plan, text, n_symbols, 0, records, capacity, n_found); });
+}
+
+/* search-and-replace (include/acm_gpu.h) */
+extern "C" int
+acm_replace (ACMachine *machine, const void *text, uint64_t n_symbols, const void *repl_data, const uint64_t *repl_off, uint64_t n_keywords, void *out,
+             uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_replaced) {
+  if (!machine || !out_symbols || (n_symbols && !text) || (out_capacity && !out) || (!repl_off && !repl_data))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      /* the caller loop into a record room the call grows itself, the selection, the sequential pass.
+       * The table covers every keyword of the machine, as on the GPU paths. */
+      if (repl_off && n_keywords < acm_nb_keywords (machine))
+        return (int)ACM_GPU_E_ARG;
+      uint64_t room = std::max<uint64_t> (1024, n_symbols / 64), found = 0;
+      ACMRecord *records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
+      if (!records)
+        return (int)ACM_GPU_E_NOMEM;
+      int rc = acm_internal_cpu_scan (machine, text, n_symbols, said, records, room, &found);
+      if (rc == ACM_GPU_E_OVERFLOW) {
+        free (records);
+        room = found;
+        records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
+        if (!records)
+          return (int)ACM_GPU_E_NOMEM;
+        rc = acm_internal_cpu_scan (machine, text, n_symbols, said, records, room, &found);
+        if (rc == ACM_GPU_E_OVERFLOW) /* (keywords inserted between the two scans) */
+          rc = ACM_GPU_E_INTERNAL;
+      }
+      if (!rc) {
+        found = acm_select_records (records, found);
+        if (n_replaced)
+          *n_replaced = found;
+        rc = acm_replace_records (text, n_symbols, said, 0, records, found, repl_data, repl_off, n_keywords, out, out_capacity, out_symbols);
+      }
+      free (records);
+      return rc;
+    },
+    [&] (ACMPlan *plan) { return acm_gpu_scan_replace_host (plan, text, n_symbols, repl_data, repl_off, n_keywords, out, out_capacity, out_symbols, n_replaced); });
 }
 
 /* acm_scan continued from a cursor (include/acm_gpu.h): the reference's own `const ACState *`, in

@@ -857,3 +857,58 @@ acm_select_records (ACMRecord *records, uint64_t n) {
   }
   return out;
 }
+
+/* REPLACE of a text under a selection (include/acm_gpu.h): the plain sequential pass.  The records
+ * are checked and the output measured first, so that nothing is written when it has no room. */
+int
+acm_replace_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t pos_base, const ACMRecord *records, uint64_t n,
+                     const void *repl_data, const uint64_t *repl_off, uint64_t n_keywords, void *out, uint64_t out_capacity,
+                     uint64_t *out_symbols) {
+  if (!out_symbols || !sym_bytes || (n_symbols && !text) || (n && !records) || (out_capacity && !out) || (!repl_off && !repl_data))
+    return ACM_GPU_E_ARG;
+  uint64_t next = 0, need = n_symbols; /* the first symbol no record has taken yet (relative to the text) */
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+      return ACM_GPU_E_ARG;
+    const uint64_t start = r->end_pos - pos_base + 1 - r->length;
+    if (start < next)
+      return ACM_GPU_E_ARG;
+    next = start + r->length;
+    if (repl_off) {
+      if (r->keyword_id >= n_keywords || repl_off[r->keyword_id] > repl_off[(uint64_t)r->keyword_id + 1] ||
+          (repl_off[(uint64_t)r->keyword_id + 1] && !repl_data))
+        return ACM_GPU_E_ARG;
+      need = need - r->length + (repl_off[(uint64_t)r->keyword_id + 1] - repl_off[r->keyword_id]);
+    }
+  }
+  *out_symbols = need;
+  if (need > out_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  const unsigned char *t = text, *rd = repl_data;
+  unsigned char *o = out;
+  const size_t sb = sym_bytes;
+  uint64_t at = 0; /* symbols of the output so far */
+  next = 0;
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    const uint64_t start = r->end_pos - pos_base + 1 - r->length;
+    if (start > next)
+      memcpy (o + at * sb, t + next * sb, (start - next) * sb);
+    at += start - next;
+    if (repl_off) {
+      const uint64_t rb = repl_off[r->keyword_id], rl = repl_off[(uint64_t)r->keyword_id + 1] - rb;
+      if (rl)
+        memcpy (o + at * sb, rd + rb * sb, rl * sb);
+      at += rl;
+    } else {
+      for (uint64_t k = 0; k < r->length; k++)
+        memcpy (o + (at + k) * sb, rd, sb);
+      at += r->length;
+    }
+    next = start + r->length;
+  }
+  if (n_symbols > next)
+    memcpy (o + at * sb, t + next * sb, (n_symbols - next) * sb);
+  return ACM_GPU_OK;
+}

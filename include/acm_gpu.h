@@ -553,6 +553,105 @@ int acm_gpu_scan_select_host (ACMPlan *plan, const void *text, uint64_t n_symbol
 int acm_select (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records,
                 uint64_t capacity, uint64_t *n_found);
 
+/* ------------------------------------------------------------------ search-and-replace
+ * What a replacer or a redactor does with the selection above: the text with every selected match
+ * replaced by its keyword's replacement (or masked), built where the text is -- no record and no
+ * byte of the text goes through the host when the pipeline stays on the device.
+ *
+ * DEFINITION.  Let S = r_0 ... r_{m-1} be a selection: records in canonical order, no two sharing a
+ * symbol, every start s_j = end_pos_j + 1 - length_j - pos_base and every end e_j = end_pos_j -
+ * pos_base in [0, n_symbols).  Let repl_data, repl_off[0 .. n_keywords] be a replacement table: its
+ * symbols have the CALLER's symbol size, the one d_text has (also for class plans and for plans that
+ * intern 8-byte symbols); repl_off never decreases and repl_off[0] = 0; the replacement R (k) of
+ * keyword k is the symbols [repl_off[k], repl_off[k + 1]) of repl_data and may be empty (deletion).
+ * REPLACE (text, S, table) is
+ *     text[0 .. s_0)  R (kw_0)  text[e_0 + 1 .. s_1)  R (kw_1)  ...  R (kw_{m-1})  text[e_{m-1} + 1 .. n_symbols)
+ * The stretches between the matches are the caller's original symbols, bit for bit -- never the
+ * class-mapped or interned copy a plan keeps for its scan.
+ * MASK mode: repl_off == NULL, and repl_data points at ONE symbol.  Every symbol of every selected
+ * match becomes that symbol; the output has n_symbols symbols.
+ * Beside the output: out_symbols, its length; n_replaced = m; and out_start[j] (optional), the index
+ * in the output at which replacement j begins -- with r_j the offset map a highlighter or a later pass
+ * needs:  out_start[j] = s_j + the sum over i < j of (|R (kw_i)| - length_i), in signed 64-bit
+ * arithmetic.
+ *
+ * acm_replace_records: the plain sequential pass on the host, no device; any sym_bytes > 0.  `n` is
+ * the number of records.  ACM_GPU_E_OVERFLOW with *out_symbols = the length needed when out_capacity
+ * (symbols) is too small: nothing is written then.  ACM_GPU_E_ARG for records that are no tiling of
+ * [pos_base, pos_base + n_symbols) (out of range, overlapping, out of order) and, in table mode, for
+ * a keyword id >= n_keywords or a keyword whose repl_off decreases.
+ *
+ * acm_gpu_replace_records_device: the same on the device (dev_replace.h) for ANY selection resident
+ * there -- acm_gpu_scan_select_device's, acm_gpu_select_records_device's, a batch scan's records
+ * after selection (they never cross a text).  Arguments in this order: the text (d_text, n_symbols,
+ * pos_base), the selection (d_sel, n_or_capacity, d_n: exactly as in acm_gpu_select_records_device --
+ * with d_n NULL n_or_capacity is the count itself, else *d_n is the count and n_or_capacity the room;
+ * below 2^31), the table (d_repl_data, d_repl_off -- NULL for mask mode --, n_keywords), the output
+ * (d_out, out_capacity in symbols, d_out_symbols: device, 8 bytes; d_out_start: device, an int64_t
+ * per record of n_or_capacity, may be NULL), the scratch (d_tmp of acm_gpu_replace_tmp_bytes (plan,
+ * n_or_capacity, n_symbols) bytes: about 8 per record) and the stream.  The call only queues
+ * launches on `stream`, with no host round trip.  d_out must not overlap d_text (ACM_GPU_E_ARG); both
+ * may have ANY byte alignment that is a multiple of the symbol size (the copy loads whole aligned
+ * 16-byte words of its sources: up to 15 bytes in front of and behind a stretch it copies are read,
+ * never beyond the aligned word that holds a byte of the stretch).  *d_out_symbols > out_capacity
+ * afterwards: it is the capacity needed, d_out is unspecified and nothing was written outside
+ * d_out[0 .. out_capacity).  *d_n > n_or_capacity (a scan that overflowed): *d_out_symbols = 0 and
+ * d_out is untouched.  A contract violation -- a record out of range, two records that overlap or
+ * are out of order, in table mode a keyword id >= n_keywords or a repl_off that decreases -- is
+ * handled as bad offsets and bad records are elsewhere: a validation pass sees every record and the
+ * whole table before any address is formed from them, acm_gpu_plan_status reports
+ * ACM_GPU_E_INTERNAL, *d_out_symbols = 0, d_out is untouched and nothing is read or written out of
+ * bounds.  The output is built in tiles of 16,384 bytes (ACM_GPU_REPLACE_TILE=<bytes> in the
+ * environment sets another: a multiple of 16 from 256 to 1 Mi, read at every call).
+ *
+ * acm_gpu_scan_replace_device: acm_gpu_scan_select_device with the passes above behind it on
+ * `stream`; the selected records stay in d_records[0 .. *d_count).  The record capacity rule is
+ * select's: `capacity` must hold ALL matches.  *d_count > capacity afterwards: it is the scan's
+ * count, *d_out_symbols = 0 and d_out is untouched.  In table mode n_keywords must be at least
+ * acm_gpu_tally_keywords (plan), else ACM_GPU_E_ARG.  d_tmp (never NULL) must hold
+ * acm_gpu_scan_replace_tmp_bytes (plan, capacity, n_symbols) bytes: the scan's and the selection's
+ * scratch is reused, the selection has ended when the replace passes begin.
+ * acm_gpu_scan_replace_host: the same from host memory, blocking.  The caller gives NO record
+ * capacity: the call counts the matches first (acm_gpu_count_device) and sizes the record room by
+ * that; it never reports a record overflow, ACM_GPU_E_OVERFLOW means only "out_capacity is too
+ * small, *out_symbols suffices" (n_replaced is valid then, `out` is not).  A text with 2^31 matches
+ * or more is ACM_GPU_E_ARG (acm_gpu_scan_select_device's limit: replace such a text in pieces).
+ * In table mode n_keywords below acm_gpu_tally_keywords (plan), or a repl_off that decreases or
+ * does not begin with 0, is ACM_GPU_E_ARG.  n_replaced may be NULL.
+ * acm_replace: the call on the machine itself, total over machines exactly as acm_scan is (same three
+ * paths, same cached plan and acm_gpu_plan_update, acm_scan_path says which ran -- recorded on
+ * success and on an output overflow): the GPU paths run acm_gpu_scan_replace_host,
+ * ACM_SCAN_PATH_CPU_LOOP runs the caller loop on the host into a record room the call grows itself,
+ * then acm_select_records, then acm_replace_records.  On every path a table with n_keywords below
+ * the machine's number of keywords is ACM_GPU_E_ARG, whether a keyword without an entry matched or
+ * not; a record room that cannot be allocated is ACM_GPU_E_NOMEM.  A missing device stays an error,
+ * never a fallback. */
+int acm_replace_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t pos_base,
+                         const ACMRecord *records, uint64_t n,
+                         const void *repl_data, const uint64_t *repl_off, uint64_t n_keywords,
+                         void *out, uint64_t out_capacity, uint64_t *out_symbols);
+size_t acm_gpu_replace_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_symbols);
+int acm_gpu_replace_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                    const ACMRecord *d_sel, uint64_t n_or_capacity,
+                                    const uint64_t *d_n /* device count, may be NULL: n is the count */,
+                                    const void *d_repl_data, const uint64_t *d_repl_off /* NULL: mask mode */,
+                                    uint64_t n_keywords, void *d_out, uint64_t out_capacity,
+                                    uint64_t *d_out_symbols, int64_t *d_out_start /* may be NULL */,
+                                    void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_scan_replace_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols);
+int acm_gpu_scan_replace_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                 ACMRecord *d_records, uint64_t capacity, uint64_t *d_count,
+                                 const void *d_repl_data, const uint64_t *d_repl_off, uint64_t n_keywords,
+                                 void *d_out, uint64_t out_capacity, uint64_t *d_out_symbols,
+                                 int64_t *d_out_start, void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_replace_host (ACMPlan *plan, const void *text, uint64_t n_symbols,
+                               const void *repl_data, const uint64_t *repl_off, uint64_t n_keywords,
+                               void *out, uint64_t out_capacity, uint64_t *out_symbols,
+                               uint64_t *n_replaced);   /* blocking */
+int acm_replace (ACMachine *machine, const void *text, uint64_t n_symbols,
+                 const void *repl_data, const uint64_t *repl_off, uint64_t n_keywords,
+                 void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_replaced);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
