@@ -10,6 +10,7 @@ There is no CPU scan path here: the bulk scan raises if the library or a GPU is 
 from .binding import (  # noqa: F401
     ACMError, Machine, Plan, Stream, MultiScan, Comm, FlatTables, RECORD_DTYPE, build_native, lib, library_path,
     select_records, replace_records, replacement_table, Replaced,
+    grep_gather, Grepped,
 )
 from . import synth  # noqa: F401
 from . import sharded  # noqa: F401

@@ -16,6 +16,7 @@ ACM_GPU_E_NODEVICE = -2
 ACM_GPU_E_HIP = -3
 ACM_GPU_E_OVERFLOW = -4
 ACM_GPU_E_ARG = -5
+ACM_GREP_MATCHING, ACM_GREP_INVERT = 0, 1
 
 
 class ACMError(RuntimeError):
@@ -91,6 +92,7 @@ EXPORTS = [
     "acm_gpu_scan_select_tmp_bytes", "acm_gpu_scan_select_device", "acm_gpu_scan_select_host", "acm_select",
     "acm_replace_records", "acm_gpu_replace_tmp_bytes", "acm_gpu_replace_records_device", "acm_gpu_scan_replace_tmp_bytes",
     "acm_gpu_scan_replace_device", "acm_gpu_scan_replace_host", "acm_replace",
+    "acm_grep_gather", "acm_gpu_grep_tmp_bytes", "acm_gpu_grep_device", "acm_gpu_grep_host", "acm_grep",
 ]
 
 
@@ -288,6 +290,16 @@ def lib():
     L.acm_gpu_scan_replace_host.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.acm_replace.restype = i32
     L.acm_replace.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_grep_gather.restype = i32
+    L.acm_grep_gather.argtypes = [vp, u32, vp, u64, vp, u32, vp, C.POINTER(u64), vp, u64, vp, C.POINTER(u64)]
+    L.acm_gpu_grep_tmp_bytes.restype = sz
+    L.acm_gpu_grep_tmp_bytes.argtypes = [vp, u64, u64, u64, u64]
+    L.acm_gpu_grep_device.restype = i32
+    L.acm_gpu_grep_device.argtypes = [vp, vp, u64, vp, u64, u32, u64, u64, vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_grep_host.restype = i32
+    L.acm_gpu_grep_host.argtypes = [vp, vp, vp, u64, u32, vp, vp, C.POINTER(u64), C.POINTER(u64), vp, u64, vp, C.POINTER(u64)]
+    L.acm_grep.restype = i32
+    L.acm_grep.argtypes = [vp, vp, vp, u64, u32, vp, vp, C.POINTER(u64), C.POINTER(u64), vp, u64, vp, C.POINTER(u64)]
     L.acm_gpu_flows_create.restype = i32
     L.acm_gpu_flows_create.argtypes = [vp, u64, C.POINTER(vp)]
     L.acm_gpu_flows_destroy.restype = None
@@ -375,6 +387,76 @@ def replace_records(text, records, replacements=None, fill=None, pos_base=0, sym
     out = np.zeros(max(int(out_capacity) * sb // t.itemsize, 1), dtype=t.dtype)
     _check(call(out, int(out_capacity)), "acm_replace_records")
     return out[:int(need.value) * sb // t.itemsize]
+
+
+class Grepped:
+    """What the grep calls return.  hits (one counter per text), kept (the ids of the kept texts,
+    ascending), out_offsets (n_kept + 1 offsets into `out`) and `out` (the kept texts, packed; None
+    without a gather): int64 / int32 / uint8 device tensors from Plan.grep() -- kept, out_offsets and
+    out have room for every text, their first n_kept (+ 1) entries and out_symbols symbols count --,
+    numpy arrays cut to size from the host calls.  n_kept, total, need and out_symbols are Python
+    ints (Plan.grep() synchronises to read them): need > capacity says that a window overflowed
+    (n_kept = total = out_symbols = 0 then), out_symbols > out_capacity is the room the output needs."""
+
+    def __init__(self, hits, kept, n_kept, total, need, out, out_offsets, out_symbols, out_capacity=None):
+        self.hits, self.kept, self.n_kept, self.total, self.need = hits, kept, n_kept, total, need
+        self.out, self.out_offsets, self.out_symbols, self.out_capacity = out, out_offsets, out_symbols, out_capacity
+
+
+def _grep_host_call(fn, what, handle, t, sym_size, off, invert, gather, out_capacity):
+    """acm_gpu_grep_host / acm_grep: numpy in, a Grepped of numpy arrays out.  An output overflow is
+    repeated once with the size the call reports when out_capacity is None."""
+    n_texts = off.size - 1
+    n_sym = int(off[-1])
+    assert t.size * t.itemsize == n_sym * sym_size, "the last offset is the number of symbols"
+    hits = np.zeros(n_texts, np.uint64)
+    kept = np.zeros(n_texts, np.uint32)
+    out_off = np.zeros(n_texts + 1, np.uint64)
+    cap = int(out_capacity) if out_capacity is not None else n_sym
+    for attempt in (0, 1):
+        out = np.zeros(max(cap * sym_size // t.itemsize, 1), dtype=t.dtype) if gather else None
+        nk, total, need = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, ACM_GREP_INVERT if invert else ACM_GREP_MATCHING,
+                hits.ctypes.data, kept.ctypes.data, C.byref(nk), C.byref(total), out.ctypes.data if gather else None, cap if gather else 0,
+                out_off.ctypes.data, C.byref(need))
+        if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
+            cap = int(need.value)
+            continue
+        _check(rc, what)
+        k, sym = int(nk.value), int(need.value)
+        return Grepped(hits, kept[:k], k, int(total.value), None, out[:sym * sym_size // t.itemsize] if gather else None, out_off[:k + 1], sym, cap)
+
+
+def grep_gather(text, offsets, hits, invert=False, sym_size=None, gather=True, out_capacity=None):
+    """acm_grep_gather(): the kept texts of a batch under given hit counts, by the sequential pass on
+    the host.  `text` (an array of symbols; with sym_size, raw bytes of symbols of that size) holds
+    the texts side by side, text t = symbols [offsets[t], offsets[t + 1]).  Returns a Grepped of numpy
+    arrays (hits is the argument itself; total is its sum, need None).  out_capacity (symbols; None:
+    what the output needs)."""
+    t = np.ascontiguousarray(text)
+    sb = int(sym_size) if sym_size is not None else t.itemsize
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    h = np.ascontiguousarray(hits, dtype=np.uint64)
+    n_texts = off.size - 1
+    assert n_texts >= 0 and h.size == n_texts
+    kept = np.zeros(max(n_texts, 1), np.uint32)
+    out_off = np.zeros(n_texts + 1, np.uint64)
+    nk, sym = C.c_uint64(0), C.c_uint64(0)
+    flags = ACM_GREP_INVERT if invert else ACM_GREP_MATCHING
+
+    def call(out, cap):
+        return lib().acm_grep_gather(t.ctypes.data if t.size else None, sb, off.ctypes.data, n_texts, h.ctypes.data if h.size else None, flags,
+                                     kept.ctypes.data, C.byref(nk), out.ctypes.data if out is not None else None, cap, out_off.ctypes.data,
+                                     C.byref(sym))
+    out = None
+    if gather:
+        if out_capacity is None:
+            _check(call(None, 0), "acm_grep_gather")
+            out_capacity = int(sym.value)
+        out = np.zeros(max(int(out_capacity) * sb // t.itemsize, 1), dtype=t.dtype)
+    _check(call(out, int(out_capacity) if gather else 0), "acm_grep_gather")
+    k, n = int(nk.value), int(sym.value)
+    return Grepped(h, kept[:k], k, int(h.sum()), None, out[:n * sb // t.itemsize] if gather else None, out_off[:k + 1], n, out_capacity)
 
 
 class FlatTables:
@@ -734,6 +816,24 @@ class Machine:
             return out[:int(need.value) * self.sym_size // t.itemsize], int(m.value)
 
 
+    def grep(self, texts, invert=False, gather=True):
+        """acm_grep(): `grep -F -f` over a list of texts (bytes or arrays of symbols), each scanned from
+        the root on its own in ONE call.  Returns a Grepped of numpy arrays: hits per text, the ids of
+        the texts with a match (invert: of those without one) and, with gather, those texts packed in
+        `out` with their offsets."""
+        def symbols(t):
+            if self.sym_size in _SYM_DTYPE:
+                return self._symbols(t)
+            return np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t)
+        parts = [symbols(t).reshape(-1) for t in texts]
+        offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            np.cumsum([p.size * p.itemsize // self.sym_size for p in parts], out=offsets[1:])
+        dtype = _SYM_DTYPE.get(self.sym_size, np.uint8)
+        packed = np.concatenate([p.view(dtype) for p in parts]) if parts else np.zeros(0, dtype)
+        return _grep_host_call(self.L.acm_grep, "acm_grep", self.handle, packed, self.sym_size, offsets, invert, gather, None)
+
+
 class Replaced:
     """What Plan.replace_records() and Plan.scan_replace() leave on the device: `out` (a uint8 tensor,
     the first out_symbols symbols are the new text when out_symbols <= out_capacity), out_symbols and
@@ -983,6 +1083,54 @@ class Plan:
         _check(lib().acm_gpu_tally_host(self.h, t.ctypes.data, t.size * t.itemsize // self.sym_size, tally.ctypes.data, tally.size,
                                         C.byref(total)), "acm_gpu_tally_host")
         return tally, int(total.value)
+
+    def grep(self, text, offsets, invert=False, window=None, capacity=None, gather=True, out=None, out_capacity=None):
+        """acm_gpu_grep_device(): `grep -F -f` over a batch on the device.  `text` is a device tensor
+        holding the texts side by side, `offsets` an int64 device tensor of n_texts + 1 entries.  No
+        record leaves the device.  `window` (symbols, a multiple of 16) and `capacity` (records per
+        window) default to 16 Mi symbols and 1 Mi records.  With gather the kept texts are packed into
+        `out` (None: a new uint8 tensor with room for out_capacity symbols, by default for the whole
+        buffer; it must not overlap `text`).  Returns a Grepped of device tensors; synchronises to
+        read its four numbers."""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        window = int(window) if window is not None else 1 << 24
+        capacity = int(capacity) if capacity is not None else 1 << 20
+        dev = text.device
+        hits = torch.zeros(max(n_texts, 1), dtype=torch.int64, device=dev)
+        kept = torch.zeros(max(n_texts, 1), dtype=torch.int32, device=dev)
+        out_off = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
+        res = torch.zeros(4, dtype=torch.int64, device=dev)                      # n_kept, total, need, out_symbols
+        if gather:
+            if out_capacity is None:
+                out_capacity = out.numel() * out.element_size() // self.sym_size if out is not None else n_symbols
+            if out is None:
+                out = torch.empty(max(int(out_capacity) * self.sym_size, 16), dtype=torch.uint8, device=dev)
+            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= int(out_capacity) * self.sym_size
+        else:
+            out, out_capacity = None, 0
+        tb = lib().acm_gpu_grep_tmp_bytes(self.h, window, capacity, n_symbols, n_texts)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        _check(lib().acm_gpu_grep_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts,
+                                         ACM_GREP_INVERT if invert else ACM_GREP_MATCHING, window, capacity, hits.data_ptr(), kept.data_ptr(),
+                                         res.data_ptr(), res.data_ptr() + 8, res.data_ptr() + 16, out.data_ptr() if gather else None,
+                                         int(out_capacity), out_off.data_ptr(), res.data_ptr() + 24 if gather else None, tmp.data_ptr(),
+                                         tmp.numel(), self._stream()), "acm_gpu_grep_device")
+        n_kept, total, need, out_symbols = (int(x) for x in res.cpu())
+        if not gather:
+            out_symbols = int(out_off[n_kept].item()) if need <= capacity else 0
+        return Grepped(hits[:n_texts], kept, n_kept, total, need, out, out_off, out_symbols, int(out_capacity))
+
+    def grep_host(self, text, offsets, invert=False, gather=True, out_capacity=None):
+        """acm_gpu_grep_host(): the same from host arrays, through the C ABI only (no torch).  The call
+        sizes its windows itself and never reports a record overflow.  Returns a Grepped of numpy arrays."""
+        t = np.ascontiguousarray(text)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        return _grep_host_call(lib().acm_gpu_grep_host, "acm_gpu_grep_host", self.h, t, self.sym_size, off, invert, gather, out_capacity)
 
     @property
     def select_form(self):

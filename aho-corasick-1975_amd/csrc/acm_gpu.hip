@@ -3718,6 +3718,30 @@ tally_lds_form (const ACMPlan *plan) {
   return !global && plan->covered_keywords <= TALLY_LDS_KEYWORDS;
 }
 
+/* the window walk of acm_gpu_tally_device and acm_gpu_grep_device: window w owns the matches that
+ * end in it and starts from the root lmax - 1 symbols early, rounded down to a 16-byte boundary of
+ * the text (acm_gpu_multi_shard_bounds' rule: the kernels keep their alignment).  Every window is
+ * scanned into `rec`, its count into d_count; behind (read begin) queues what the caller does with
+ * the records, whose positions are relative to the window's read begin. */
+template <typename Behind>
+int
+scan_windows (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t emit_from, uint64_t window_symbols, ACMRecord *rec, uint64_t capacity,
+              uint64_t *d_count, hipStream_t st, Behind behind) {
+  const uint32_t sb = plan->text_sym_bytes;
+  const uint64_t per16 = 16 / sb ? 16 / sb : 1, warm = flows_keep (plan);
+  for (uint64_t wb = emit_from / window_symbols * window_symbols; wb < n_symbols; wb += window_symbols) {
+    const uint64_t we = n_symbols - wb > window_symbols ? wb + window_symbols : n_symbols;
+    const uint64_t ef = emit_from > wb ? emit_from : wb;
+    const uint64_t rb = (wb > warm ? wb - warm : 0) / per16 * per16;
+    int rc = scan_plan<false> (plan, static_cast<const unsigned char *> (d_text) + rb * sb, we - rb, ef - rb, 0, rec, capacity, d_count, st);
+    if (!rc)
+      rc = behind (rb);
+    if (rc)
+      return rc;
+  }
+  return ACM_GPU_OK;
+}
+
 /* M of the capacity bound: most records one position can have, the plan's and its delta's.  A
  * start-parallel plan that is edited in place does not keep finfo.max_outputs up to date: the
  * keywords that end at one position have different lengths, so lmax bounds their number. */
@@ -3768,18 +3792,7 @@ acm_gpu_tally_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uin
   HIP_TRY (hipMemsetAsync (t, 0, L.o_rec, st)); /* control words, histogram, count */
   HIP_TRY (hipMemsetAsync (d_total, 0, 8, st));
 
-  /* window w owns the matches that end in it and starts from the root lmax - 1 symbols early,
-   * rounded down to a 16-byte boundary of the text (acm_gpu_multi_shard_bounds' rule: the kernels
-   * keep their alignment) */
-  const uint32_t sb = plan->text_sym_bytes;
-  const uint64_t per16 = 16 / sb ? 16 / sb : 1, warm = flows_keep (plan);
-  for (uint64_t wb = emit_from / window_symbols * window_symbols; wb < n_symbols; wb += window_symbols) {
-    const uint64_t we = n_symbols - wb > window_symbols ? wb + window_symbols : n_symbols;
-    const uint64_t ef = emit_from > wb ? emit_from : wb;
-    const uint64_t rb = (wb > warm ? wb - warm : 0) / per16 * per16;
-    int rc = scan_plan<false> (plan, static_cast<const unsigned char *> (d_text) + rb * sb, we - rb, ef - rb, 0, rec, capacity, d_count, st);
-    if (rc)
-      return rc;
+  const int rc = scan_windows (plan, d_text, n_symbols, emit_from, window_symbols, rec, capacity, d_count, st, [&] (uint64_t) -> int {
     TallyK K{};
     K.rec = rec;
     K.capacity = capacity;
@@ -3795,7 +3808,10 @@ acm_gpu_tally_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uin
     else
       hipLaunchKernelGGL (tally_records_kernel<false>, grid, dim3 (TALLY_THREADS), 0, st, K);
     HIP_TRY (hipGetLastError ());
-  }
+    return ACM_GPU_OK;
+  });
+  if (rc)
+    return rc;
   TallyK K{};
   K.capacity = capacity;
   K.hist = reinterpret_cast<unsigned long long *> (t + L.o_hist);
@@ -3862,6 +3878,244 @@ acm_gpu_tally_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_
     tally[k] += add[k];
   if (total)
     *total = out[0];
+  return ACM_GPU_OK;
+}
+
+/* ------------------------------------------------------------------ grep over a batch (include/acm_gpu.h, dev_grep.h)
+ * The record scan of the buffer, window by window into the caller's scratch, a pass over every
+ * window's records that counts them per text, then the kept texts' ids, their offsets in the
+ * output and the output itself. */
+namespace {
+struct GrepLayout {
+  uint64_t n_blocks = 0, n_tiles = 0;
+  size_t o_ctl = 0, o_count = 0, o_hits = 0, zero_bytes = 0, o_index = 0, o_tkept = 0, o_tkept_begin = 0, o_tsym = 0, o_tsym_begin = 0, o_cub = 0,
+         cub_bytes = 0, o_kept = 0, o_kept_off = 0, o_rec = 0, total = 0;
+};
+GrepLayout
+grep_layout (uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  GrepLayout L;
+  L.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
+  L.n_tiles = (n_texts + GREP_TILE - 1) / GREP_TILE;
+  L.cub_bytes = std::max (exclusive_sum_bytes (L.n_tiles + 1), exclusive_sum_bytes64 (L.n_tiles + 1));
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (GrepCtl));
+  L.o_count = blob_reserve (cur, 8);
+  L.o_hits = blob_reserve (cur, (n_texts + 1) * 8);
+  L.zero_bytes = cur; /* control words, count, hit counters: cleared in front of every call */
+  L.o_index = blob_reserve (cur, L.n_blocks * 4);
+  L.o_tkept = blob_reserve (cur, (L.n_tiles + 1) * 4);
+  L.o_tkept_begin = blob_reserve (cur, (L.n_tiles + 1) * 4);
+  L.o_tsym = blob_reserve (cur, (L.n_tiles + 1) * 8);
+  L.o_tsym_begin = blob_reserve (cur, (L.n_tiles + 1) * 8);
+  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
+  L.o_kept = blob_reserve (cur, (n_texts + 1) * 4);
+  L.o_kept_off = blob_reserve (cur, (n_texts + 2) * 8);
+  L.o_rec = blob_reserve (cur, (size_t)capacity * sizeof (ACMRecord));
+  L.total = cur + 256;
+  return L;
+}
+
+/* ACM_GPU_GREP_TILE=<bytes of output>: the gather's tile, a multiple of 16 (tests; read at every call) */
+uint32_t
+grep_out_tile (void) {
+  const int t = env_int ("ACM_GPU_GREP_TILE", (int)GREP_OUT_TILE_DEFAULT);
+  return t >= (int)GREP_OUT_TILE_MIN && t <= (int)GREP_OUT_TILE_MAX && t % 16 == 0 ? (uint32_t)t : GREP_OUT_TILE_DEFAULT;
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_grep_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  (void)window_symbols; /* (what a window's scan needs beside its records belongs to the plan) */
+  if (!plan || capacity == 0 || capacity >= (1ull << 31) || n_texts >= (1ull << 31))
+    return 0;
+  return grep_layout (capacity, n_symbols, n_texts).total;
+}
+
+extern "C" int
+acm_gpu_grep_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint32_t flags,
+                     uint64_t window_symbols, uint64_t capacity, uint64_t *d_hits, uint32_t *d_kept, uint64_t *d_n_kept, uint64_t *d_total,
+                     uint64_t *d_need, void *d_out, uint64_t out_capacity, uint64_t *d_out_offsets, uint64_t *d_out_symbols, void *d_tmp,
+                     size_t tmp_bytes, void *stream) {
+  if (!plan || !d_n_kept || !d_total || !d_need || (n_symbols && !d_text) || window_symbols == 0 || window_symbols % 16 || capacity == 0 ||
+      capacity >= (1ull << 31) || n_texts >= (1ull << 31) || flags > ACM_GREP_INVERT || (d_out != nullptr) != (d_out_symbols != nullptr))
+    return ACM_GPU_E_ARG;
+  const uint32_t sb = plan->text_sym_bytes;
+  const uintptr_t t0 = reinterpret_cast<uintptr_t> (d_text), o0 = reinterpret_cast<uintptr_t> (d_out);
+  if (t0 % sb || o0 % sb || n_symbols >= (1ull << 56) / sb || out_capacity >= (1ull << 56) / sb)
+    return ACM_GPU_E_ARG;
+  if (d_out && n_symbols && out_capacity && t0 < o0 + out_capacity * sb && o0 < t0 + n_symbols * sb) /* the output is built from the text beside it */
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0) { /* a batch of no texts: no symbol, nothing kept */
+    if (n_symbols)
+      return ACM_GPU_E_ARG;
+    HIP_TRY (hipSetDevice (plan->device));
+    for (uint64_t *d : { d_n_kept, d_total, d_need, d_out_symbols, d_out_offsets })
+      if (d)
+        HIP_TRY (hipMemsetAsync (d, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  const GrepLayout L = grep_layout (capacity, n_symbols, n_texts);
+  if (!d_offsets || !d_tmp || tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  uint64_t *d_count = reinterpret_cast<uint64_t *> (t + L.o_count);
+  ACMRecord *rec = reinterpret_cast<ACMRecord *> (t + L.o_rec);
+  GrepK K{};
+  K.rec = rec;
+  K.capacity = capacity;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_count);
+  K.offsets = d_offsets;
+  K.n_texts = n_texts;
+  K.n_symbols = n_symbols;
+  K.index = reinterpret_cast<const uint32_t *> (t + L.o_index);
+  K.hits = reinterpret_cast<unsigned long long *> (t + L.o_hits);
+  K.flags = flags;
+  K.tile_kept = reinterpret_cast<uint32_t *> (t + L.o_tkept);
+  K.tile_kept_begin = reinterpret_cast<const uint32_t *> (t + L.o_tkept_begin);
+  K.tile_sym = reinterpret_cast<unsigned long long *> (t + L.o_tsym);
+  K.tile_sym_begin = reinterpret_cast<const unsigned long long *> (t + L.o_tsym_begin);
+  K.n_tiles = L.n_tiles;
+  K.kept = reinterpret_cast<uint32_t *> (t + L.o_kept);
+  K.kept_off = reinterpret_cast<unsigned long long *> (t + L.o_kept_off);
+  K.d_hits = reinterpret_cast<unsigned long long *> (d_hits);
+  K.d_kept = d_kept;
+  K.d_out_offsets = reinterpret_cast<unsigned long long *> (d_out_offsets);
+  K.d_n_kept = reinterpret_cast<unsigned long long *> (d_n_kept);
+  K.d_total = reinterpret_cast<unsigned long long *> (d_total);
+  K.d_need = reinterpret_cast<unsigned long long *> (d_need);
+  K.d_out_symbols = reinterpret_cast<unsigned long long *> (d_out_symbols);
+  K.text = static_cast<const unsigned char *> (d_text);
+  K.out = static_cast<unsigned char *> (d_out);
+  K.out_capacity = out_capacity;
+  K.sb = sb;
+  K.tile_words = grep_out_tile () / 16;
+  K.ctl = reinterpret_cast<GrepCtl *> (t + L.o_ctl);
+  K.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (t, 0, L.zero_bytes, st));
+  /* 1. the index and the check of offsets[], by batch_index_kernel's own launch rule */
+  BatchK B{};
+  B.offsets = d_offsets;
+  B.n_texts = n_texts;
+  B.n_symbols = n_symbols;
+  B.index = reinterpret_cast<uint32_t *> (t + L.o_index);
+  B.n_blocks = L.n_blocks;
+  B.ctl = &K.ctl->batch;
+  B.error = K.error;
+  const uint64_t many_texts = n_texts >= (1ull << 16) ? (uint64_t)plan->cu_count * 8 : 1;
+  hipLaunchKernelGGL (batch_index_kernel<false>, capped_grid (plan, std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, B);
+  HIP_TRY (hipGetLastError ());
+  /* 2. every window's records, counted per text: the grid by the room, whatever the scan found */
+  const dim3 hits_grid = capped_grid (plan, (capacity + GREP_THREADS - 1) / GREP_THREADS);
+  const int rc = scan_windows (plan, d_text, n_symbols, 0, window_symbols, rec, capacity, d_count, st, [&] (uint64_t read_begin) -> int {
+    K.read_begin = read_begin;
+    hipLaunchKernelGGL (grep_hits_kernel, hits_grid, dim3 (GREP_THREADS), 0, st, K);
+    HIP_TRY (hipGetLastError ());
+    return ACM_GPU_OK;
+  });
+  if (rc)
+    return rc;
+  /* 3. */
+  const dim3 tiles_grid = capped_grid (plan, L.n_tiles + 1);
+  hipLaunchKernelGGL (grep_flag_kernel<false>, tiles_grid, dim3 (GREP_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  size_t cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.tile_kept, reinterpret_cast<uint32_t *> (t + L.o_tkept_begin), (int)(L.n_tiles + 1), st));
+  cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_tsym),
+                                             reinterpret_cast<long long *> (t + L.o_tsym_begin), (int)(L.n_tiles + 1), st));
+  hipLaunchKernelGGL (grep_flag_kernel<true>, tiles_grid, dim3 (GREP_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  /* 4. the grid by the room of the output, not by what the passes found */
+  if (d_out) {
+    const uint64_t tiles = (out_capacity * sb + 15 + 16) / ((uint64_t)K.tile_words * 16) + 1;
+    hipLaunchKernelGGL (grep_gather_kernel, capped_grid (plan, tiles), dim3 (GREP_THREADS), 0, st, K);
+    HIP_TRY (hipGetLastError ());
+  }
+  return ACM_GPU_OK;
+}
+
+extern "C" int
+acm_gpu_grep_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t flags, uint64_t *hits, uint32_t *kept,
+                   uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols) {
+  if (!plan || !n_kept || n_texts >= (1ull << 31) || flags > ACM_GREP_INVERT || !batch_offsets_ok (offsets, n_texts))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_symbols = offsets[n_texts];
+  if (n_symbols && !text)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  /* the window and the record room as acm_gpu_tally_host picks them, ACM_GPU_TALLY_CAPACITY included */
+  uint64_t window = 1ull << 25, capacity = 1ull << 21;
+  if (const char *e = getenv ("ACM_GPU_TALLY_CAPACITY"))
+    if (atoll (e) > 0 && (uint64_t)atoll (e) < (1ull << 31))
+      capacity = (uint64_t)atoll (e);
+  if (n_symbols < (1ull << 31) / tally_max_outputs (plan) && n_symbols * tally_max_outputs (plan) < capacity)
+    capacity = n_symbols ? n_symbols * tally_max_outputs (plan) : 1;
+  const uint32_t sb = plan->text_sym_bytes;
+  const size_t tbytes = (size_t)n_symbols * sb;
+  if (!out)
+    out_capacity = 0;
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr, *d_out = nullptr;
+  uint64_t *d_off = nullptr, *d_hits = nullptr, *d_out_off = nullptr, *d_res = nullptr; /* d_res: n_kept, total, need, out_symbols */
+  uint32_t *d_kept = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
+  HOST_TRY (temps.get (&d_hits, n_texts * 8));
+  HOST_TRY (temps.get (&d_kept, n_texts * 4));
+  HOST_TRY (temps.get (&d_out_off, (n_texts + 1) * 8));
+  HOST_TRY (temps.get (&d_res, 32));
+  if (out)
+    HOST_TRY (temps.get (&d_out, (size_t)out_capacity * sb));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+  uint64_t res[4] = { 0, 0, 0, 0 };
+  for (int attempt = 0; attempt < 2; attempt++) {
+    const size_t tmp_bytes = acm_gpu_grep_tmp_bytes (plan, window, capacity, n_symbols, n_texts);
+    HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+    int rc = acm_gpu_grep_device (plan, d_text, n_symbols, d_off, n_texts, flags, window, capacity, d_hits, d_kept, d_res, d_res + 1, d_res + 2, d_out,
+                                  out_capacity, d_out_off, out ? d_res + 3 : nullptr, d_tmp, tmp_bytes, nullptr);
+    if (!rc)
+      rc = acm_gpu_plan_status (plan); /* (waits for the device) */
+    if (rc) {
+      (void)hipDeviceSynchronize ();
+      return rc;
+    }
+    HOST_TRY (hipMemcpy (res, d_res, 32, hipMemcpyDeviceToHost));
+    HOST_TRY (temps.release (d_tmp)); /* (the second attempt's is another size) */
+    if (res[2] <= capacity)
+      break;
+    if (attempt == 1) /* (W x M records cannot be exceeded: never expected) */
+      return ACM_GPU_E_INTERNAL;
+    /* a window of W symbols has at most W x M records: the second attempt cannot overflow */
+    const uint64_t m = tally_max_outputs (plan);
+    if (capacity / m < 16)
+      capacity = 16 * m;
+    window = capacity / m / 16 * 16;
+  }
+  if (res[0] > n_texts)
+    return ACM_GPU_E_INTERNAL;
+  *n_kept = res[0];
+  if (total)
+    *total = res[1];
+  if (hits && n_texts)
+    HOST_TRY (hipMemcpy (hits, d_hits, n_texts * 8, hipMemcpyDeviceToHost));
+  if (kept && res[0])
+    HOST_TRY (hipMemcpy (kept, d_kept, res[0] * 4, hipMemcpyDeviceToHost));
+  uint64_t symbols = 0; /* (also without an output buffer: the last offset) */
+  HOST_TRY (hipMemcpy (&symbols, d_out_off + res[0], 8, hipMemcpyDeviceToHost));
+  if (out_offsets)
+    HOST_TRY (hipMemcpy (out_offsets, d_out_off, (res[0] + 1) * 8, hipMemcpyDeviceToHost));
+  if (out_symbols)
+    *out_symbols = symbols;
+  if (!out)
+    return ACM_GPU_OK;
+  if (symbols > out_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (symbols)
+    HOST_TRY (hipMemcpy (out, d_out, (size_t)symbols * sb, hipMemcpyDeviceToHost));
   return ACM_GPU_OK;
 }
 
@@ -4934,7 +5188,7 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally only a scan that
  * succeeded, acm_select and acm_scan_from also one that found more records than there was room for,
- * acm_replace also one whose output had no room. */
+ * acm_replace and acm_grep also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -4960,7 +5214,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The six calls below run on the same route, the same cached plan, under the same lock. */
+/* The seven calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -5047,6 +5301,38 @@ acm_replace (ACMachine *machine, const void *text, uint64_t n_symbols, const voi
       return rc;
     },
     [&] (ACMPlan *plan) { return acm_gpu_scan_replace_host (plan, text, n_symbols, repl_data, repl_off, n_keywords, out, out_capacity, out_symbols, n_replaced); });
+}
+
+/* grep over a batch (include/acm_gpu.h) */
+extern "C" int
+acm_grep (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t flags, uint64_t *hits, uint32_t *kept,
+          uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols) {
+  if (!machine || !n_kept || n_texts >= (1ull << 31) || flags > ACM_GREP_INVERT || !batch_offsets_ok (offsets, n_texts) ||
+      (offsets[n_texts] && !text))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      /* the caller loop from the root at every offset, counting; then the sequential gather */
+      std::vector<uint64_t> own;
+      uint64_t *h = hits;
+      if (!h) {
+        own.resize (n_texts + 1);
+        h = own.data ();
+      }
+      int rc = acm_internal_cpu_grep_hits (machine, text, offsets, n_texts, said, h);
+      if (rc)
+        return rc;
+      if (total) {
+        *total = 0;
+        for (uint64_t t = 0; t < n_texts; t++)
+          *total += h[t];
+      }
+      return acm_grep_gather (text, said, offsets, n_texts, h, flags, kept, n_kept, out, out ? out_capacity : 0, out_offsets, out_symbols);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_grep_host (plan, text, offsets, n_texts, flags, hits, kept, n_kept, total, out, out_capacity, out_offsets, out_symbols);
+    });
 }
 
 /* acm_scan continued from a cursor (include/acm_gpu.h): the reference's own `const ACState *`, in

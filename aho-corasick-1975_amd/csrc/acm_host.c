@@ -814,6 +814,68 @@ acm_internal_cpu_tally (ACMachine *m, const void *text, uint64_t n_symbols, uint
   return ACM_GPU_OK;
 }
 
+/* The same loop for acm_grep (include/acm_gpu.h): from the root at every offset, counting the matches
+ * of every text -- the reference's word-by-word use (examples/aho_corasick_generic_test.c:168-210
+ * restarts from acm_initiate for every word it reads).  offsets[] has been checked by the caller. */
+int
+acm_internal_cpu_grep_hits (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint64_t *hits) {
+  if (!m || !offsets || (n_texts && !hits) || (offsets[n_texts] && !text) || !sym_bytes)
+    return ACM_GPU_E_ARG;
+#ifdef ACM_NMEYER_85
+  acm_internal_refresh (m);
+#endif
+  for (uint64_t t = 0; t < n_texts; t++)
+    hits[t] = cpu_loop (m, text, offsets[t], offsets[t + 1], sym_bytes, NULL, NULL, 0, 0, 0);
+  return ACM_GPU_OK;
+}
+
+/* KEPT and GATHER of a batch under its hit counts (include/acm_gpu.h): the plain sequential pass.
+ * The output is measured first, so that nothing is written to it when it has no room. */
+int
+acm_grep_gather (const void *text, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts, const uint64_t *hits, uint32_t flags,
+                 uint32_t *kept, uint64_t *n_kept, void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols) {
+  if (!sym_bytes || !n_kept || !offsets || offsets[0] != 0 || (n_texts && !hits) || n_texts >= (1ull << 31) || flags > ACM_GREP_INVERT)
+    return ACM_GPU_E_ARG;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (offsets[t] > offsets[t + 1])
+      return ACM_GPU_E_ARG;
+  if (out && offsets[n_texts] && !text)
+    return ACM_GPU_E_ARG;
+  const int invert = flags == ACM_GREP_INVERT;
+  uint64_t k = 0, symbols = 0;
+  for (uint64_t t = 0; t < n_texts; t++) {
+    if ((hits[t] > 0) == invert)
+      continue;
+    if (kept)
+      kept[k] = (uint32_t)t;
+    if (out_offsets)
+      out_offsets[k] = symbols;
+    symbols += offsets[t + 1] - offsets[t];
+    k++;
+  }
+  if (out_offsets)
+    out_offsets[k] = symbols;
+  *n_kept = k;
+  if (out_symbols)
+    *out_symbols = symbols;
+  if (!out)
+    return ACM_GPU_OK;
+  if (symbols > out_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  const unsigned char *src = text;
+  unsigned char *o = out;
+  const size_t sb = sym_bytes;
+  uint64_t at = 0;
+  for (uint64_t t = 0; t < n_texts; t++) {
+    const uint64_t len = offsets[t + 1] - offsets[t];
+    if ((hits[t] > 0) == invert || !len)
+      continue;
+    memcpy (o + at * sb, src + offsets[t] * sb, len * sb);
+    at += len;
+  }
+  return ACM_GPU_OK;
+}
+
 /* SELECT of records in canonical order (include/acm_gpu.h), in place in the front of the array: the
  * plain sequential greedy pass.  The order is by end and the rule goes by start, so a round looks
  * at a window: from the first record that ends at or behind p up to the first that ends lmax or

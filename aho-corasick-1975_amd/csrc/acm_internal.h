@@ -65,6 +65,9 @@ int acm_internal_cpu_scan_from (ACMachine *m, const ACState **cursor, const void
  * NULL) = their number; ACM_GPU_E_ARG, with nothing counted, when n_keywords is below the machine's number of keywords */
 int acm_internal_cpu_tally (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t *tally, uint64_t n_keywords,
                             uint64_t *total);
+/* the same loop from the root on every text of a batch, counting per text instead of recording (acm_grep): hits[t] = the
+ * number of matches of text t; offsets[] already checked */
+int acm_internal_cpu_grep_hits (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint64_t *hits);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

@@ -164,5 +164,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_tally.h"
 #include "dev_select.h"
 #include "dev_replace.h"
+#include "dev_grep.h"
 
 } // namespace

@@ -652,6 +652,102 @@ int acm_replace (ACMachine *machine, const void *text, uint64_t n_symbols,
                  const void *repl_data, const uint64_t *repl_off, uint64_t n_keywords,
                  void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_replaced);
 
+/* ------------------------------------------------------------------ grep over a batch
+ * The reference's callers mostly hold many small texts -- log lines, packets, cells, the words of
+ * examples/aho_corasick_generic_test.c:168-210, which restarts at the root for every word it reads,
+ * the README's per-word loop -- and ask a dictionary what `grep -F -f` answers: which of my texts
+ * contain a keyword, how many matches each has, and the matching (or the non-matching) texts
+ * themselves, so that the next stage sees only those.  No record leaves the device and no record
+ * capacity for the whole buffer has to be guessed: this is the batch counterpart of the tally.
+ *
+ * DEFINITION.  A batch is as in the batch scan: n_texts texts packed in one buffer, the same
+ * offsets[0 .. n_texts] contract, empty texts allowed.  hits[t] is the number of records of text t
+ * in acm_scan_batch's result, first[t + 1] - first[t]: the caller loop run from the root on every
+ * text alone; a match that begins in an earlier text does not count.  KEPT is the ascending list of
+ * the texts t with hits[t] > 0 when flags == ACM_GREP_MATCHING (0); with ACM_GREP_INVERT (1) it is
+ * the texts with hits[t] == 0 (an empty text is never a hit, so INVERT keeps it).
+ * kept[0 .. n_kept) holds their ids.  `total` is the sum of all hits[t], whatever the flags.
+ * GATHER (optional: an output buffer is given): `out` is the symbols of the kept texts in order,
+ * packed; out_offsets[0 .. n_kept] holds their offsets in `out`, out_offsets[0] = 0, and
+ * out_symbols = out_offsets[n_kept].  The symbols are the caller's originals, bit for bit, in the
+ * caller's symbol size -- never the class-mapped or interned copy a plan keeps for its scan
+ * (acm_replace's rule).  kept/out_offsets/out are what the next acm_gpu_scan_batch_device,
+ * acm_gpu_scan_replace_device or a tokeniser consumes directly on the device.
+ *
+ * acm_grep_gather: KEPT and GATHER from given hit counts, the plain sequential pass on the host, no
+ * device; any sym_bytes > 0.  kept, out, out_offsets and out_symbols may be NULL (out NULL: nothing
+ * is gathered, *out_symbols still says what it would take).  ACM_GPU_E_OVERFLOW with *out_symbols =
+ * the length needed, and nothing written to `out`, when out_capacity (symbols) is too small: kept,
+ * n_kept and out_offsets are written all the same.  ACM_GPU_E_ARG for offsets that do not begin with
+ * 0 or that decrease, for flags above 1 and for n_texts >= 2^31.
+ *
+ * acm_gpu_grep_device: the same on the device (dev_grep.h), hits included.  Windows and record
+ * capacity are acm_gpu_tally_device's: the buffer is cut into windows of window_symbols symbols (a
+ * multiple of 16, greater than 0); every window starts from the root lmax - 1 symbols early, rounded
+ * down to a 16-byte boundary of the text, and is scanned as acm_gpu_scan_device scans (any plan
+ * kind, a pending delta included) into `capacity` records inside d_tmp; CAPACITY is per WINDOW,
+ * greater than 0 and below 2^31, and capacity >= window_symbols x M (M as in the tally section)
+ * cannot overflow.  There is no emit_from.  Outputs, all device memory, SET (not added to), valid
+ * when `stream` has passed: d_hits (n_texts entries) and d_kept (room for n_texts ids) may be NULL,
+ * d_out_offsets (room for n_texts + 1) may be NULL; *d_need = the largest record count of a window.
+ *     some window found more than `capacity`:  *d_n_kept = *d_total = 0, *d_out_symbols = 0 when
+ *         d_out is given, *d_need > capacity is a capacity that suffices for this window size;
+ *         every other output is unspecified; nothing is written outside the buffers.
+ * d_out NULL: no gather, and d_out_symbols must be NULL too (ACM_GPU_E_ARG when exactly one of the
+ * two is NULL).  Gather overflow: *d_out_symbols > out_capacity afterwards is the capacity needed;
+ * d_out is unspecified, nothing was written outside d_out[0 .. out_capacity), and d_hits, d_kept,
+ * d_n_kept, d_total and d_out_offsets are complete and valid.  d_out must not overlap d_text
+ * (ACM_GPU_E_ARG); both may have ANY byte alignment that is a multiple of the symbol size (the copy
+ * loads whole aligned 16-byte words of the text: up to 15 bytes in front of and behind a text it
+ * copies are read, never beyond the aligned word that holds a byte of that text) --
+ * acm_gpu_replace_records_device's rule.  The output is built in tiles of 16,384 bytes
+ * (ACM_GPU_GREP_TILE=<bytes> in the environment sets another: a multiple of 16 from 256 to 1 Mi,
+ * read at every call).
+ * n_texts >= 2^31 is ACM_GPU_E_ARG.  n_texts = 0 requires n_symbols = 0 and gives n_kept = 0.
+ * d_offsets that break the contract (first not 0, last not n_symbols, decreasing) are handled as the
+ * batch scan handles them: all counts are 0, no other output is written, acm_gpu_plan_status
+ * reports ACM_GPU_E_INTERNAL, nothing is read or written out of bounds and no address is formed
+ * from an offset before the check has seen it.  d_tmp must hold acm_gpu_grep_tmp_bytes (plan,
+ * window_symbols, capacity, n_symbols, n_texts) bytes: 16 per record of capacity, 20 per text, 4 per
+ * 4,096 symbols, 24 per 1,024 texts (0 for a capacity or an n_texts the call would refuse).  The
+ * call only queues launches on `stream`, with no host round trip; one scan at a time per plan as
+ * ever, and not while a stream (acm_gpu_stream_*) is open on it.
+ * acm_gpu_grep_host: the same from host memory, blocking.  It picks the window and the capacity
+ * exactly as acm_gpu_tally_host does (ACM_GPU_TALLY_CAPACITY included, repeated once with
+ * window_symbols = capacity / M) and never reports a record overflow: ACM_GPU_E_OVERFLOW means only
+ * "out_capacity is too small, *out_symbols suffices" -- hits, kept, n_kept, total and out_offsets
+ * are valid then.  offsets[] is checked on the host (ACM_GPU_E_ARG; the last offset is the number of
+ * symbols).  Every output pointer except n_kept may be NULL; out NULL: no gather, *out_symbols still
+ * says what it would take.
+ * acm_grep: the call on the machine itself, total over machines exactly as acm_tally is (same three
+ * paths, same cached plan and acm_gpu_plan_update, acm_scan_path says which ran -- recorded on
+ * success and on an output overflow): the GPU paths run acm_gpu_grep_host, ACM_SCAN_PATH_CPU_LOOP
+ * runs the caller loop on the host from the root at every offset, counting the hits of every text,
+ * then acm_grep_gather.  A missing device stays an error, never a fallback. */
+#define ACM_GREP_MATCHING 0
+#define ACM_GREP_INVERT 1
+int acm_grep_gather (const void *text, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                     const uint64_t *hits, uint32_t flags, uint32_t *kept, uint64_t *n_kept,
+                     void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols);
+size_t acm_gpu_grep_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t capacity,
+                               uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_grep_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols,
+                         const uint64_t *d_offsets, uint64_t n_texts, uint32_t flags,
+                         uint64_t window_symbols, uint64_t capacity,
+                         uint64_t *d_hits /* n_texts, may be NULL */, uint32_t *d_kept /* n_texts, may be NULL */,
+                         uint64_t *d_n_kept, uint64_t *d_total, uint64_t *d_need,
+                         void *d_out /* may be NULL: no gather */, uint64_t out_capacity,
+                         uint64_t *d_out_offsets /* n_texts + 1, may be NULL */,
+                         uint64_t *d_out_symbols /* NULL iff d_out is */,
+                         void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_grep_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts,
+                       uint32_t flags, uint64_t *hits, uint32_t *kept, uint64_t *n_kept, uint64_t *total,
+                       void *out, uint64_t out_capacity, uint64_t *out_offsets,
+                       uint64_t *out_symbols);   /* blocking */
+int acm_grep (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts,
+              uint32_t flags, uint64_t *hits, uint32_t *kept, uint64_t *n_kept, uint64_t *total,
+              void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
