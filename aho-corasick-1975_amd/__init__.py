@@ -11,6 +11,7 @@ from .binding import (  # noqa: F401
     ACMError, Machine, Plan, Stream, MultiScan, Comm, FlatTables, RECORD_DTYPE, build_native, lib, library_path,
     select_records, replace_records, replacement_table, Replaced,
     grep_gather, Grepped,
+    tally_batch_records, TalliedBatch,
 )
 from . import synth  # noqa: F401
 from . import sharded  # noqa: F401

@@ -93,6 +93,7 @@ EXPORTS = [
     "acm_replace_records", "acm_gpu_replace_tmp_bytes", "acm_gpu_replace_records_device", "acm_gpu_scan_replace_tmp_bytes",
     "acm_gpu_scan_replace_device", "acm_gpu_scan_replace_host", "acm_replace",
     "acm_grep_gather", "acm_gpu_grep_tmp_bytes", "acm_gpu_grep_device", "acm_gpu_grep_host", "acm_grep",
+    "acm_tally_batch_records", "acm_gpu_tally_batch_tmp_bytes", "acm_gpu_tally_batch_device", "acm_gpu_tally_batch_host", "acm_tally_batch",
 ]
 
 
@@ -300,6 +301,16 @@ def lib():
     L.acm_gpu_grep_host.argtypes = [vp, vp, vp, u64, u32, vp, vp, C.POINTER(u64), C.POINTER(u64), vp, u64, vp, C.POINTER(u64)]
     L.acm_grep.restype = i32
     L.acm_grep.argtypes = [vp, vp, vp, u64, u32, vp, vp, C.POINTER(u64), C.POINTER(u64), vp, u64, vp, C.POINTER(u64)]
+    L.acm_tally_batch_records.restype = i32
+    L.acm_tally_batch_records.argtypes = [vp, vp, u64, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_tally_batch_tmp_bytes.restype = sz
+    L.acm_gpu_tally_batch_tmp_bytes.argtypes = [vp, u64, u64, u64, u64, u64]
+    L.acm_gpu_tally_batch_device.restype = i32
+    L.acm_gpu_tally_batch_device.argtypes = [vp, vp, u64, vp, u64, u64, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.acm_gpu_tally_batch_host.restype = i32
+    L.acm_gpu_tally_batch_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_tally_batch.restype = i32
+    L.acm_tally_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.acm_gpu_flows_create.restype = i32
     L.acm_gpu_flows_create.argtypes = [vp, u64, C.POINTER(vp)]
     L.acm_gpu_flows_destroy.restype = None
@@ -457,6 +468,71 @@ def grep_gather(text, offsets, hits, invert=False, sym_size=None, gather=True, o
     _check(call(out, int(out_capacity) if gather else 0), "acm_grep_gather")
     k, n = int(nk.value), int(sym.value)
     return Grepped(h, kept[:k], k, int(h.sum()), None, out[:n * sb // t.itemsize] if gather else None, out_off[:k + 1], n, out_capacity)
+
+
+class TalliedBatch:
+    """What the tally_batch calls return: the text x keyword count matrix of a batch in CSR form.
+    row_ptr (n_texts + 1 entries), col (keyword ids, ascending within a row) and val (counts): int64 /
+    int32 / int64 device tensors from Plan.tally_batch() -- col and val have room for pair_capacity
+    entries, their first nnz count --, uint64 / uint32 / uint64 numpy arrays cut to size from the host
+    calls.  nnz, total, need and need_pairs are Python ints (Plan.tally_batch() synchronises to read
+    them; the host calls leave need and need_pairs None): need > capacity says that a window
+    overflowed, need_pairs > pair_capacity that the pairs did -- nnz = total = 0 then, and a repeat
+    with that value has room."""
+
+    def __init__(self, row_ptr, col, val, nnz, total, need=None, need_pairs=None):
+        self.row_ptr, self.col, self.val, self.nnz, self.total, self.need, self.need_pairs = row_ptr, col, val, nnz, total, need, need_pairs
+
+    def to_sparse_csr(self, n_keywords):
+        """The matrix as a torch.sparse_csr_tensor of n_texts x n_keywords int64 counts, built on the
+        arrays where they are: nothing is copied when they are device tensors."""
+        import torch
+
+        def tensor(a, dtype):
+            return a.view(dtype) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).view(dtype)
+        return torch.sparse_csr_tensor(tensor(self.row_ptr, torch.int64), tensor(self.col, torch.int32)[:self.nnz],
+                                       tensor(self.val, torch.int64)[:self.nnz], size=(self.row_ptr.shape[0] - 1, int(n_keywords)))
+
+
+def _tally_batch_host_call(fn, what, handle, t, sym_size, off):
+    """acm_gpu_tally_batch_host / acm_tally_batch: numpy in, a TalliedBatch of numpy arrays out.  An
+    output overflow is repeated once with the size the call reports."""
+    n_texts = off.size - 1
+    n_sym = int(off[-1])
+    assert t.size * t.itemsize == n_sym * sym_size, "the last offset is the number of symbols"
+    row_ptr = np.zeros(n_texts + 1, np.uint64)
+    cap = max(1024, n_sym // 16)
+    for attempt in (0, 1):
+        col, val = np.zeros(cap, np.uint32), np.zeros(cap, np.uint64)
+        nnz, total = C.c_uint64(0), C.c_uint64(0)
+        rc = fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data, cap,
+                C.byref(nnz), C.byref(total))
+        if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
+            cap = int(nnz.value)
+            continue
+        _check(rc, what)
+        k = int(nnz.value)
+        return TalliedBatch(row_ptr, col[:k], val[:k], k, int(total.value))
+
+
+def tally_batch_records(records, first, n_keywords):
+    """acm_tally_batch_records(): the text x keyword count matrix of a batch scan's records (a
+    RECORD_DTYPE array) and first[] (n_texts + 1 entries), by the sequential pass on the host.
+    Returns a TalliedBatch of numpy arrays."""
+    rec = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
+    f = np.ascontiguousarray(first, dtype=np.uint64)
+    assert f.size >= 1, "first has n_texts + 1 entries"
+    n_texts = f.size - 1
+    row_ptr = np.zeros(n_texts + 1, np.uint64)
+    nnz = C.c_uint64(0)
+    data = rec.ctypes.data if rec.size else None
+    _check(lib().acm_tally_batch_records(data, f.ctypes.data, n_texts, int(n_keywords), row_ptr.ctypes.data, None, None, 0, C.byref(nnz)),
+           "acm_tally_batch_records")
+    k = int(nnz.value)
+    col, val = np.zeros(max(k, 1), np.uint32), np.zeros(max(k, 1), np.uint64)
+    _check(lib().acm_tally_batch_records(data, f.ctypes.data, n_texts, int(n_keywords), row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data, k,
+                                         C.byref(nnz)), "acm_tally_batch_records")
+    return TalliedBatch(row_ptr, col[:k], val[:k], k, int(val[:k].sum()))
 
 
 class FlatTables:
@@ -833,6 +909,22 @@ class Machine:
         packed = np.concatenate([p.view(dtype) for p in parts]) if parts else np.zeros(0, dtype)
         return _grep_host_call(self.L.acm_grep, "acm_grep", self.handle, packed, self.sym_size, offsets, invert, gather, None)
 
+    def tally_batch(self, texts):
+        """acm_tally_batch(): which keywords occur how often in which text of a list of texts (bytes or
+        arrays of symbols), each scanned from the root on its own in ONE call.  Returns a TalliedBatch
+        of numpy arrays: the text x keyword count matrix in CSR form."""
+        def symbols(t):
+            if self.sym_size in _SYM_DTYPE:
+                return self._symbols(t)
+            return np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t)
+        parts = [symbols(t).reshape(-1) for t in texts]
+        offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            np.cumsum([p.size * p.itemsize // self.sym_size for p in parts], out=offsets[1:])
+        dtype = _SYM_DTYPE.get(self.sym_size, np.uint8)
+        packed = np.concatenate([p.view(dtype) for p in parts]) if parts else np.zeros(0, dtype)
+        return _tally_batch_host_call(self.L.acm_tally_batch, "acm_tally_batch", self.handle, packed, self.sym_size, offsets)
+
 
 class Replaced:
     """What Plan.replace_records() and Plan.scan_replace() leave on the device: `out` (a uint8 tensor,
@@ -1131,6 +1223,43 @@ class Plan:
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         assert off.size >= 1, "offsets has n_texts + 1 entries"
         return _grep_host_call(lib().acm_gpu_grep_host, "acm_gpu_grep_host", self.h, t, self.sym_size, off, invert, gather, out_capacity)
+
+    def tally_batch(self, text, offsets, window=None, capacity=None, pair_capacity=None):
+        """acm_gpu_tally_batch_device(): the text x keyword count matrix of a batch on the device, in
+        CSR form.  `text` is a device tensor holding the texts side by side, `offsets` an int64 device
+        tensor of n_texts + 1 entries.  No record leaves the device.  `window` (symbols, a multiple of
+        16) and `capacity` (records per window) default to 16 Mi symbols and 1 Mi records,
+        `pair_capacity` (the room of col and val) to `capacity`.  Returns a TalliedBatch of device
+        tensors; synchronises to read its four numbers."""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        window = int(window) if window is not None else 1 << 24
+        capacity = int(capacity) if capacity is not None else 1 << 20
+        pair_capacity = int(pair_capacity) if pair_capacity is not None else capacity
+        dev = text.device
+        row_ptr = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
+        col = torch.zeros(max(pair_capacity, 1), dtype=torch.int32, device=dev)
+        val = torch.zeros(max(pair_capacity, 1), dtype=torch.int64, device=dev)
+        res = torch.zeros(4, dtype=torch.int64, device=dev)                      # nnz, total, need, need_pairs
+        tb = lib().acm_gpu_tally_batch_tmp_bytes(self.h, window, capacity, pair_capacity, n_symbols, n_texts)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        _check(lib().acm_gpu_tally_batch_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity,
+                                                row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), res.data_ptr(), res.data_ptr() + 8,
+                                                res.data_ptr() + 16, res.data_ptr() + 24, tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_tally_batch_device")
+        nnz, total, need, need_pairs = (int(x) for x in res.cpu())
+        return TalliedBatch(row_ptr, col, val, nnz, total, need, need_pairs)
+
+    def tally_batch_host(self, text, offsets):
+        """acm_gpu_tally_batch_host(): the same from host arrays, through the C ABI only (no torch).
+        The call sizes its windows and its pair room itself.  Returns a TalliedBatch of numpy arrays."""
+        t = np.ascontiguousarray(text)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        return _tally_batch_host_call(lib().acm_gpu_tally_batch_host, "acm_gpu_tally_batch_host", self.h, t, self.sym_size, off)
 
     @property
     def select_form(self):

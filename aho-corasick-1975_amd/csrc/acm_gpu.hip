@@ -4119,6 +4119,270 @@ acm_gpu_grep_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uin
   return ACM_GPU_OK;
 }
 
+/* ------------------------------------------------------------------ per-text keyword counts of a batch (include/acm_gpu.h, dev_tally_batch.h)
+ * grep's window walk, every window's records reduced to partial (text, keyword) pairs, then the
+ * pairs bucketed by text, merged per row and compacted into the caller's CSR arrays. */
+namespace {
+struct TallyBatchLayout {
+  uint64_t n_blocks = 0, n_keywords = 0;
+  size_t o_ctl = 0, o_count = 0, o_hist = 0, o_row_nnz = 0, zero_bytes = 0, o_index = 0, o_begin = 0, o_row_ptr = 0, o_wide = 0, o_cub = 0, cub_bytes = 0,
+         o_pkey = 0, o_pcnt = 0, o_bkw = 0, o_btext = 0, o_bval = 0, o_whist = 0, o_rec = 0, total = 0;
+};
+TallyBatchLayout
+tally_batch_layout (const ACMPlan *plan, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts) {
+  TallyBatchLayout L;
+  L.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
+  L.n_keywords = (uint64_t)plan->covered_keywords + 1;
+  L.cub_bytes = std::max (exclusive_sum_bytes (n_texts + 1), exclusive_sum_bytes64 (n_texts + 1));
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (TbCtl));
+  L.o_count = blob_reserve (cur, 8);
+  L.o_hist = blob_reserve (cur, (n_texts + 1) * 4);
+  L.o_row_nnz = blob_reserve (cur, (n_texts + 1) * 8);
+  L.zero_bytes = cur; /* control words, count, pairs per text, row lengths: cleared in front of every call */
+  L.o_index = blob_reserve (cur, L.n_blocks * 4);
+  L.o_begin = blob_reserve (cur, (n_texts + 1) * 4);
+  L.o_row_ptr = blob_reserve (cur, (n_texts + 1) * 8);
+  L.o_wide = blob_reserve (cur, (n_texts + 1) * 4);
+  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
+  L.o_pkey = blob_reserve (cur, (size_t)pair_capacity * 8);
+  L.o_pcnt = blob_reserve (cur, (size_t)pair_capacity * 4);
+  L.o_bkw = blob_reserve (cur, (size_t)pair_capacity * 4);
+  L.o_btext = blob_reserve (cur, (size_t)pair_capacity * 4);
+  L.o_bval = blob_reserve (cur, (size_t)pair_capacity * 8);
+  L.o_whist = blob_reserve (cur, (size_t)TB_WIDE_BLOCKS * L.n_keywords * 8);
+  L.o_rec = blob_reserve (cur, (size_t)capacity * sizeof (ACMRecord));
+  L.total = cur + 256;
+  return L;
+}
+
+/* ACM_GPU_TALLY_BATCH_SLOTS=<a power of two from 8 to 4,096>: the slots of a block's LDS table;
+ * ACM_GPU_TALLY_BATCH_ROW=<1 to 2,048>: R, the entries of the widest row merged in LDS (tests,
+ * experiments; read at every call) */
+uint32_t
+tally_batch_slots (void) {
+  const int s = env_int ("ACM_GPU_TALLY_BATCH_SLOTS", (int)TB_SLOTS_DEFAULT);
+  return s >= (int)TB_SLOTS_MIN && s <= (int)TB_SLOTS_MAX && (s & (s - 1)) == 0 ? (uint32_t)s : TB_SLOTS_DEFAULT;
+}
+uint32_t
+tally_batch_row (void) {
+  const int r = env_int ("ACM_GPU_TALLY_BATCH_ROW", (int)TB_ROW_DEFAULT);
+  return r >= 1 && r <= (int)TB_ROW_MAX ? (uint32_t)r : TB_ROW_DEFAULT;
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_tally_batch_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols,
+                               uint64_t n_texts) {
+  (void)window_symbols; /* (what a window's scan needs beside its records belongs to the plan) */
+  if (!plan || capacity == 0 || capacity >= (1ull << 31) || pair_capacity == 0 || pair_capacity >= (1ull << 31) || n_texts >= (1ull << 31))
+    return 0;
+  return tally_batch_layout (plan, capacity, pair_capacity, n_symbols, n_texts).total;
+}
+
+extern "C" int
+acm_gpu_tally_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint64_t window_symbols,
+                            uint64_t capacity, uint64_t pair_capacity, uint64_t *d_row_ptr, uint32_t *d_col, uint64_t *d_val, uint64_t *d_nnz,
+                            uint64_t *d_total, uint64_t *d_need, uint64_t *d_need_pairs, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_row_ptr || !d_col || !d_val || !d_nnz || !d_total || !d_need || !d_need_pairs || (n_symbols && !d_text) || window_symbols == 0 ||
+      window_symbols % 16 || capacity == 0 || capacity >= (1ull << 31) || pair_capacity == 0 || pair_capacity >= (1ull << 31) ||
+      n_texts >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  const uint32_t sb = plan->text_sym_bytes;
+  if (reinterpret_cast<uintptr_t> (d_text) % sb || n_symbols >= (1ull << 56) / sb)
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0) { /* a batch of no texts: no symbol, an empty matrix */
+    if (n_symbols)
+      return ACM_GPU_E_ARG;
+    HIP_TRY (hipSetDevice (plan->device));
+    for (uint64_t *d : { d_row_ptr, d_nnz, d_total, d_need, d_need_pairs })
+      HIP_TRY (hipMemsetAsync (d, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  const TallyBatchLayout L = tally_batch_layout (plan, capacity, pair_capacity, n_symbols, n_texts);
+  if (!d_offsets || !d_tmp || tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  uint64_t *d_count = reinterpret_cast<uint64_t *> (t + L.o_count);
+  ACMRecord *rec = reinterpret_cast<ACMRecord *> (t + L.o_rec);
+  TbK K{};
+  K.rec = rec;
+  K.capacity = capacity;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_count);
+  K.offsets = d_offsets;
+  K.n_texts = n_texts;
+  K.n_symbols = n_symbols;
+  K.index = reinterpret_cast<const uint32_t *> (t + L.o_index);
+  K.n_keywords = plan->covered_keywords;
+  K.slots = tally_batch_slots ();
+  K.shift = 64;
+  for (uint32_t s = K.slots; s > 1; s >>= 1)
+    K.shift--;
+  K.pair_capacity = pair_capacity;
+  K.pkey = reinterpret_cast<unsigned long long *> (t + L.o_pkey);
+  K.pcnt = reinterpret_cast<uint32_t *> (t + L.o_pcnt);
+  K.hist = reinterpret_cast<uint32_t *> (t + L.o_hist);
+  K.begin = reinterpret_cast<const uint32_t *> (t + L.o_begin);
+  K.bkw = reinterpret_cast<uint32_t *> (t + L.o_bkw);
+  K.btext = reinterpret_cast<uint32_t *> (t + L.o_btext);
+  K.bval = reinterpret_cast<unsigned long long *> (t + L.o_bval);
+  K.row = tally_batch_row ();
+  K.row_p2 = 1;
+  while (K.row_p2 < K.row)
+    K.row_p2 <<= 1;
+  K.mcol = K.pcnt; /* (the partial pairs are dead behind the scatter) */
+  K.mval = K.pkey;
+  K.row_nnz = reinterpret_cast<unsigned long long *> (t + L.o_row_nnz);
+  K.wide = reinterpret_cast<uint32_t *> (t + L.o_wide);
+  K.whist = reinterpret_cast<unsigned long long *> (t + L.o_whist);
+  K.row_ptr = reinterpret_cast<const unsigned long long *> (t + L.o_row_ptr);
+  K.d_row_ptr = reinterpret_cast<unsigned long long *> (d_row_ptr);
+  K.d_col = d_col;
+  K.d_val = reinterpret_cast<unsigned long long *> (d_val);
+  K.d_nnz = reinterpret_cast<unsigned long long *> (d_nnz);
+  K.d_total = reinterpret_cast<unsigned long long *> (d_total);
+  K.d_need = reinterpret_cast<unsigned long long *> (d_need);
+  K.d_need_pairs = reinterpret_cast<unsigned long long *> (d_need_pairs);
+  K.ctl = reinterpret_cast<TbCtl *> (t + L.o_ctl);
+  K.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (t, 0, L.zero_bytes, st));
+  /* 1. the index and the check of offsets[], as acm_gpu_grep_device launches it */
+  BatchK B{};
+  B.offsets = d_offsets;
+  B.n_texts = n_texts;
+  B.n_symbols = n_symbols;
+  B.index = reinterpret_cast<uint32_t *> (t + L.o_index);
+  B.n_blocks = L.n_blocks;
+  B.ctl = &K.ctl->batch;
+  B.error = K.error;
+  const uint64_t many_texts = n_texts >= (1ull << 16) ? (uint64_t)plan->cu_count * 8 : 1;
+  hipLaunchKernelGGL (batch_index_kernel<false>, capped_grid (plan, std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, B);
+  HIP_TRY (hipGetLastError ());
+  /* 2. every window's records to partial pairs: the grid by the room, two blocks per CU at the most */
+  const dim3 pairs_grid = capped_grid (plan, (capacity + TB_THREADS - 1) / TB_THREADS, 2);
+  const size_t table_bytes = (size_t)K.slots * 12;
+  const int rc = scan_windows (plan, d_text, n_symbols, 0, window_symbols, rec, capacity, d_count, st, [&] (uint64_t read_begin) -> int {
+    K.read_begin = read_begin;
+    hipLaunchKernelGGL (tb_pairs_kernel, pairs_grid, dim3 (TB_THREADS), table_bytes, st, K);
+    HIP_TRY (hipGetLastError ());
+    return ACM_GPU_OK;
+  });
+  if (rc)
+    return rc;
+  /* 3. the grids by the room of the pairs */
+  const dim3 pair_grid = capped_grid (plan, (pair_capacity + TB_THREADS - 1) / TB_THREADS);
+  hipLaunchKernelGGL (tb_hist_kernel, pair_grid, dim3 (TB_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  size_t cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.hist, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(n_texts + 1), st));
+  hipLaunchKernelGGL (tb_scatter_kernel, pair_grid, dim3 (TB_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  /* 4. */
+  hipLaunchKernelGGL (tb_merge_kernel, capped_grid (plan, (n_texts + TB_TILE - 1) / TB_TILE), dim3 (TB_THREADS), (size_t)K.row_p2 * 16 + ((size_t)K.row_p2 + 1) * 4,
+                      st, K);
+  HIP_TRY (hipGetLastError ());
+  hipLaunchKernelGGL (tb_wide_kernel, dim3 (TB_WIDE_BLOCKS), dim3 (TB_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  /* 5. */
+  cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_row_nnz),
+                                             reinterpret_cast<long long *> (t + L.o_row_ptr), (int)(n_texts + 1), st));
+  hipLaunchKernelGGL (tb_finish_kernel, capped_grid (plan, (std::max (pair_capacity, n_texts + 1) + TB_THREADS - 1) / TB_THREADS), dim3 (TB_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  return ACM_GPU_OK;
+}
+
+extern "C" int
+acm_gpu_tally_batch_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint64_t *row_ptr, uint32_t *col, uint64_t *val,
+                          uint64_t nnz_capacity, uint64_t *nnz, uint64_t *total) {
+  if (!plan || !row_ptr || !nnz || n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_symbols = offsets[n_texts];
+  if (n_symbols && !text)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  /* the window and the record room as acm_gpu_tally_host picks them, ACM_GPU_TALLY_CAPACITY included;
+   * the pair room: as many as records of a window, no more than the buffer can have */
+  uint64_t window = 1ull << 25, capacity = 1ull << 21;
+  if (const char *e = getenv ("ACM_GPU_TALLY_CAPACITY"))
+    if (atoll (e) > 0 && (uint64_t)atoll (e) < (1ull << 31))
+      capacity = (uint64_t)atoll (e);
+  uint64_t pair_capacity = std::max<uint64_t> (capacity, 1ull << 16);
+  const uint64_t most = n_symbols < (1ull << 31) / tally_max_outputs (plan) ? n_symbols * tally_max_outputs (plan) : 1ull << 31;
+  if (most < capacity)
+    capacity = most ? most : 1;
+  if (most < pair_capacity)
+    pair_capacity = most ? most : 1;
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_off = nullptr, *d_row_ptr = nullptr, *d_val = nullptr, *d_res = nullptr; /* d_res: nnz, total, need, need_pairs */
+  uint32_t *d_col = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
+  HOST_TRY (temps.get (&d_row_ptr, (n_texts + 1) * 8));
+  HOST_TRY (temps.get (&d_res, 32));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+  uint64_t res[4] = { 0, 0, 0, 0 };
+  bool again_records = false, again_pairs = false;
+  for (;;) {
+    const size_t tmp_bytes = acm_gpu_tally_batch_tmp_bytes (plan, window, capacity, pair_capacity, n_symbols, n_texts);
+    HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+    HOST_TRY (temps.get (&d_col, (size_t)pair_capacity * 4));
+    HOST_TRY (temps.get (&d_val, (size_t)pair_capacity * 8));
+    int rc = acm_gpu_tally_batch_device (plan, d_text, n_symbols, d_off, n_texts, window, capacity, pair_capacity, d_row_ptr, d_col, d_val, d_res,
+                                         d_res + 1, d_res + 2, d_res + 3, d_tmp, tmp_bytes, nullptr);
+    if (!rc)
+      rc = acm_gpu_plan_status (plan); /* (waits for the device) */
+    if (rc) {
+      (void)hipDeviceSynchronize ();
+      return rc;
+    }
+    HOST_TRY (hipMemcpy (res, d_res, 32, hipMemcpyDeviceToHost));
+    if (res[2] <= capacity && res[3] <= pair_capacity)
+      break;
+    HOST_TRY (temps.release (d_tmp)); /* (the next attempt's are other sizes) */
+    HOST_TRY (temps.release (d_col));
+    HOST_TRY (temps.release (d_val));
+    if (res[2] > capacity) {
+      if (again_records) /* (W x M records cannot be exceeded: never expected) */
+        return ACM_GPU_E_INTERNAL;
+      again_records = true;
+      /* a window of W symbols has at most W x M records: the second attempt cannot overflow */
+      const uint64_t m = tally_max_outputs (plan);
+      if (capacity / m < 16)
+        capacity = 16 * m;
+      window = capacity / m / 16 * 16;
+    } else {
+      if (again_pairs) /* (the kept records cannot be exceeded: never expected) */
+        return ACM_GPU_E_INTERNAL;
+      if (res[3] >= (1ull << 31)) /* more partial pairs than one call holds */
+        return ACM_GPU_E_NOMEM;
+      again_pairs = true;
+      pair_capacity = res[3];
+    }
+  }
+  if (res[0] > pair_capacity)
+    return ACM_GPU_E_INTERNAL;
+  HOST_TRY (hipMemcpy (row_ptr, d_row_ptr, (n_texts + 1) * 8, hipMemcpyDeviceToHost));
+  *nnz = res[0];
+  if (total)
+    *total = res[1];
+  if (!col || !val) /* the call only counts */
+    return ACM_GPU_OK;
+  if (res[0] > nnz_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (res[0]) {
+    HOST_TRY (hipMemcpy (col, d_col, res[0] * 4, hipMemcpyDeviceToHost));
+    HOST_TRY (hipMemcpy (val, d_val, res[0] * 8, hipMemcpyDeviceToHost));
+  }
+  return ACM_GPU_OK;
+}
+
 /* ------------------------------------------------------------------ leftmost-longest selection (include/acm_gpu.h, dev_select.h)
  * The passes over a record set in canonical order; acm_gpu_scan_select_device runs them behind the
  * ordered scan. */
@@ -5188,7 +5452,7 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally only a scan that
  * succeeded, acm_select and acm_scan_from also one that found more records than there was room for,
- * acm_replace and acm_grep also one whose output had no room. */
+ * acm_replace, acm_grep and acm_tally_batch also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -5214,7 +5478,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The seven calls below run on the same route, the same cached plan, under the same lock. */
+/* The eight calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -5333,6 +5597,44 @@ acm_grep (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_
     [&] (ACMPlan *plan) {
       return acm_gpu_grep_host (plan, text, offsets, n_texts, flags, hits, kept, n_kept, total, out, out_capacity, out_offsets, out_symbols);
     });
+}
+
+/* per-text keyword counts of a batch (include/acm_gpu.h) */
+extern "C" int
+acm_tally_batch (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, uint64_t *row_ptr, uint32_t *col, uint64_t *val,
+                 uint64_t nnz_capacity, uint64_t *nnz, uint64_t *total) {
+  if (!machine || !row_ptr || !nnz || n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts) || (offsets[n_texts] && !text))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      /* the caller loop from the root at every offset into a record room the call grows itself, then the sequential pass */
+      const uint64_t n_symbols = offsets[n_texts];
+      uint64_t room = std::max<uint64_t> (1024, n_symbols / 64), found = 0;
+      std::vector<uint64_t> first (n_texts + 1);
+      ACMRecord *records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
+      if (!records)
+        return (int)ACM_GPU_E_NOMEM;
+      int rc = acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, said, records, nullptr, first.data (), room, &found);
+      if (rc == ACM_GPU_E_OVERFLOW) {
+        free (records);
+        room = found;
+        records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
+        if (!records)
+          return (int)ACM_GPU_E_NOMEM;
+        rc = acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, said, records, nullptr, first.data (), room, &found);
+        if (rc == ACM_GPU_E_OVERFLOW) /* (keywords inserted between the two scans) */
+          rc = ACM_GPU_E_INTERNAL;
+      }
+      if (!rc) {
+        if (total)
+          *total = found;
+        rc = acm_tally_batch_records (records, first.data (), n_texts, acm_nb_keywords (machine), row_ptr, col, val, nnz_capacity, nnz);
+      }
+      free (records);
+      return rc;
+    },
+    [&] (ACMPlan *plan) { return acm_gpu_tally_batch_host (plan, text, offsets, n_texts, row_ptr, col, val, nnz_capacity, nnz, total); });
 }
 
 /* acm_scan continued from a cursor (include/acm_gpu.h): the reference's own `const ACState *`, in

@@ -876,6 +876,74 @@ acm_grep_gather (const void *text, uint32_t sym_bytes, const uint64_t *offsets, 
   return ACM_GPU_OK;
 }
 
+static int
+cmp_u32 (const void *a, const void *b) {
+  const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b;
+  return x < y ? -1 : x > y;
+}
+
+/* The text x keyword count matrix of a batch's records in CSR form (include/acm_gpu.h): the plain
+ * sequential pass.  seen[k] = t + 1 while row t has met keyword k: the first walk counts every row's
+ * distinct keywords, so that nothing is written to col and val when they have no room; the second
+ * collects a row's keywords where they go, sorts them and reads their counters back (and clears
+ * them). */
+int
+acm_tally_batch_records (const ACMRecord *records, const uint64_t *first, uint64_t n_texts, uint64_t n_keywords, uint64_t *row_ptr, uint32_t *col,
+                         uint64_t *val, uint64_t nnz_capacity, uint64_t *nnz) {
+  if (!first || first[0] != 0 || !row_ptr || !nnz || n_texts >= (1ull << 31) || n_keywords >= (1ull << 32))
+    return ACM_GPU_E_ARG;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (first[t] > first[t + 1])
+      return ACM_GPU_E_ARG;
+  const uint64_t n = first[n_texts];
+  if (n && !records)
+    return ACM_GPU_E_ARG;
+  for (uint64_t r = 0; r < n; r++)
+    if (records[r].keyword_id >= n_keywords)
+      return ACM_GPU_E_ARG;
+  uint32_t *seen = calloc (n_keywords ? n_keywords : 1, sizeof (uint32_t));
+  uint64_t *count = calloc (n_keywords ? n_keywords : 1, sizeof (uint64_t));
+  if (!seen || !count) {
+    free (seen);
+    free (count);
+    return ACM_GPU_E_NOMEM;
+  }
+  uint64_t all = 0;
+  for (uint64_t t = 0; t < n_texts; t++) {
+    row_ptr[t] = all;
+    for (uint64_t r = first[t]; r < first[t + 1]; r++) {
+      const uint32_t k = records[r].keyword_id;
+      if (seen[k] != (uint32_t)t + 1) {
+        seen[k] = (uint32_t)t + 1;
+        all++;
+      }
+    }
+  }
+  row_ptr[n_texts] = all;
+  *nnz = all;
+  int rc = ACM_GPU_OK;
+  if (col && val && all > nnz_capacity)
+    rc = ACM_GPU_E_OVERFLOW;
+  else if (col && val)
+    for (uint64_t t = 0; t < n_texts; t++) {
+      uint32_t *c = col + row_ptr[t];
+      uint64_t m = 0;
+      for (uint64_t r = first[t]; r < first[t + 1]; r++) {
+        const uint32_t k = records[r].keyword_id;
+        if (count[k]++ == 0)
+          c[m++] = k;
+      }
+      qsort (c, m, sizeof (uint32_t), cmp_u32);
+      for (uint64_t j = 0; j < m; j++) {
+        val[row_ptr[t] + j] = count[c[j]];
+        count[c[j]] = 0;
+      }
+    }
+  free (seen);
+  free (count);
+  return rc;
+}
+
 /* SELECT of records in canonical order (include/acm_gpu.h), in place in the front of the array: the
  * plain sequential greedy pass.  The order is by end and the rule goes by start, so a round looks
  * at a window: from the first record that ends at or behind p up to the first that ends lmax or

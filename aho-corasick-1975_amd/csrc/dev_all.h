@@ -165,5 +165,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_select.h"
 #include "dev_replace.h"
 #include "dev_grep.h"
+#include "dev_tally_batch.h"
 
 } // namespace

@@ -93,6 +93,31 @@ grep_stopped (const GrepK &K) {
   return K.ctl->batch.bad != 0 || K.ctl->need > K.capacity;
 }
 
+/* the text of record r of a window read from symbol read_begin on, and whether the record counts:
+ * its position through the index (batch_text_of between the index entries of its block and the
+ * next), kept iff the match begins inside that text (batch_filter_kernel's test).  A position
+ * outside the buffer (never expected) sets `wrong` and does not count.  Shared with
+ * dev_tally_batch.h. */
+__device__ __forceinline__ bool
+grep_record_text (const uint4 r, uint64_t read_begin, const uint64_t *offsets, uint64_t n_texts, uint64_t n_symbols, const uint32_t *index,
+                  uint32_t &t, bool &wrong) {
+  const uint64_t rel = ((uint64_t)r.y << 32) | r.x;
+  const uint64_t pos = rel + read_begin;
+  if (rel >= n_symbols || pos >= n_symbols) { /* not a position of the buffer: reported, not counted */
+    wrong = true;
+    return false;
+  }
+  const uint64_t b = pos >> BATCH_BLOCK_LOG2;
+  uint64_t lo = index[b], hi = index[b + 1];
+  if (hi > n_texts - 1)
+    hi = n_texts - 1;
+  if (lo > hi)
+    lo = hi;
+  const uint64_t tt = batch_text_of (offsets, lo, hi, pos);
+  t = (uint32_t)tt;
+  return pos + 1 >= offsets[tt] + r.z; /* the match begins inside its text */
+}
+
 /* pass 2 */
 __global__ __launch_bounds__ (GREP_THREADS) void
 grep_hits_kernel (GrepK K) {
@@ -112,24 +137,8 @@ grep_hits_kernel (GrepK K) {
     const uint64_t i = base + lane;
     bool keep = false;
     uint32_t t = 0;
-    if (i < n) {
-      const uint4 r = *reinterpret_cast<const uint4 *> (&K.rec[i]);
-      const uint64_t rel = ((uint64_t)r.y << 32) | r.x;
-      const uint64_t pos = rel + K.read_begin;
-      if (rel >= K.n_symbols || pos >= K.n_symbols) { /* not a position of the buffer (never expected): reported, not counted */
-        wrong = true;
-      } else {
-        const uint64_t b = pos >> BATCH_BLOCK_LOG2;
-        uint64_t lo = K.index[b], hi = K.index[b + 1];
-        if (hi > K.n_texts - 1)
-          hi = K.n_texts - 1;
-        if (lo > hi)
-          lo = hi;
-        const uint64_t tt = batch_text_of (K.offsets, lo, hi, pos);
-        t = (uint32_t)tt;
-        keep = pos + 1 >= K.offsets[tt] + r.z; /* the match begins inside its text */
-      }
-    }
+    if (i < n)
+      keep = grep_record_text (*reinterpret_cast<const uint4 *> (&K.rec[i]), K.read_begin, K.offsets, K.n_texts, K.n_symbols, K.index, t, wrong);
     const unsigned long long m = __ballot (keep);
     if (m == 0)
       continue;

@@ -748,6 +748,89 @@ int acm_grep (ACMachine *machine, const void *text, const uint64_t *offsets, uin
               uint32_t flags, uint64_t *hits, uint32_t *kept, uint64_t *n_kept, uint64_t *total,
               void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols);
 
+/* ------------------------------------------------------------------ per-text keyword counts of a batch
+ * The tally says how often every keyword occurs in a buffer, grep how many matches every text of a
+ * batch has.  This is their product: which keywords fired in which text, and how often -- the rule
+ * set per packet of an IDS, the labels per log line, the bag-of-keywords row per document -- as a
+ * text x keyword count matrix in CSR form, which is what a sparse-matrix consumer (torch's
+ * sparse_csr_tensor among them) reads as it is.  No record leaves the device and no record capacity
+ * for the whole buffer has to be guessed.
+ *
+ * DEFINITION.  A batch is as in the batch scan: n_texts texts packed in one buffer, the same
+ * offsets[0 .. n_texts] contract, empty texts allowed.  C[t][k] is the number of records of text t
+ * in acm_scan_batch's result whose keyword_id is k: the caller loop run from the root on every text
+ * alone; a match that begins in an earlier text does not count.  The result is C in CSR form:
+ * row_ptr[0 .. n_texts] (uint64_t, row_ptr[0] = 0), row t is the entries [row_ptr[t], row_ptr[t + 1])
+ * of col[] (uint32_t keyword ids, strictly ascending within a row) and val[] (uint64_t counts, all
+ * > 0); nnz = row_ptr[n_texts]; `total` is the sum of all val and equals grep's `total`.  Outputs
+ * are SET, not added to.
+ *
+ * acm_tally_batch_records: C of a batch scan's records (any order within a text) and first[], the
+ * plain sequential pass on the host, no device.  ACM_GPU_E_OVERFLOW with *nnz = the entries needed
+ * when nnz_capacity is too small: col and val are untouched then, row_ptr is written all the same.
+ * col and val may be NULL: the call only counts (row_ptr and *nnz) and returns ACM_GPU_OK.
+ * ACM_GPU_E_ARG for a first[] that decreases or does not begin with 0, for a keyword_id >=
+ * n_keywords and for n_texts >= 2^31.
+ *
+ * acm_gpu_tally_batch_device: the same on the device (dev_tally_batch.h).  Windows and the record
+ * `capacity` per window are exactly acm_gpu_grep_device's (the same rules and the same *d_need, any
+ * plan kind, a pending delta included, not while a stream is open).  The records of every window are
+ * reduced to PARTIAL pairs (text, keyword, count) -- one block's share of a pair; a pair may have
+ * several --, which are bucketed by text and merged.  pair_capacity (greater than 0, below 2^31) is
+ * the room of d_col and d_val and also of the scratch area of the partial pairs, which are never
+ * fewer than nnz and never more than the kept records (the records that count: `total`).  Outputs,
+ * all device memory, valid when `stream` has passed; d_row_ptr has n_texts + 1 entries.
+ *     no overflow:  every output is complete, *d_need <= capacity, and *d_need_pairs <= pair_capacity
+ *         is the number of partial pairs this run made.
+ *     some window found more than `capacity`:  *d_nnz = *d_total = 0, *d_need > capacity is a
+ *         capacity that suffices for this window size; every other output is unspecified.
+ *     more partial pairs than pair_capacity:  *d_nnz = *d_total = 0, *d_need_pairs > pair_capacity
+ *         is the number of kept records of the call: a capacity that always suffices and that does
+ *         not depend on the order in which the scan left its records (the number of partial pairs
+ *         does); d_row_ptr, d_col and d_val are not written.
+ * Nothing is ever written outside the buffers.  d_offsets that break the contract are handled as
+ * grep handles them: *d_nnz = *d_total = *d_need_pairs = 0, d_row_ptr, d_col and d_val are not
+ * written, acm_gpu_plan_status reports ACM_GPU_E_INTERNAL, and no address is formed from an offset
+ * before the check has seen it.  A keyword_id that is no keyword of the plan (never expected) is not
+ * counted and raises the same flag.  n_texts >= 2^31 is ACM_GPU_E_ARG; n_texts = 0 requires
+ * n_symbols = 0 and gives row_ptr[0] = 0, nnz = 0.  d_tmp must hold acm_gpu_tally_batch_tmp_bytes
+ * (plan, window_symbols, capacity, pair_capacity, n_symbols, n_texts) bytes: 16 per record of
+ * capacity, 28 per pair of pair_capacity, 28 per text, 4 per 4,096 symbols, 64 per keyword (0 for
+ * arguments the call would refuse).  A row of more than 2,048 partial pairs is merged by a slow
+ * form that is always correct.  In the environment, read at every call (tests, experiments):
+ * ACM_GPU_TALLY_BATCH_SLOTS=<a power of two from 8 to 4,096> is the size of a block's table of
+ * pairs, ACM_GPU_TALLY_BATCH_ROW=<1 to 2,048> the widest row of the fast form.  The call only
+ * queues launches on `stream`, with no host round trip.
+ * acm_gpu_tally_batch_host: the same from host memory, blocking.  It picks the window and the record
+ * capacity exactly as acm_gpu_tally_host does (ACM_GPU_TALLY_CAPACITY included, repeated once with
+ * window_symbols = capacity / M), picks a pair room by itself and repeats once with *d_need_pairs
+ * when that was too small.  ACM_GPU_E_OVERFLOW means only "nnz_capacity is too small, *nnz
+ * suffices": row_ptr, total and nnz are valid then, col and val untouched.  col and val may be
+ * NULL: the call only counts.  offsets[] is checked on the host (ACM_GPU_E_ARG).
+ * acm_tally_batch: the call on the machine itself, total over machines exactly as acm_grep is (same
+ * three paths, same cached plan and acm_gpu_plan_update, acm_scan_path says which ran -- recorded on
+ * success and on an output overflow): the GPU paths run acm_gpu_tally_batch_host,
+ * ACM_SCAN_PATH_CPU_LOOP runs the caller loop on the host from the root at every offset into a
+ * record room the call grows itself, then acm_tally_batch_records.  A missing device stays an
+ * error, never a fallback. */
+int acm_tally_batch_records (const ACMRecord *records, const uint64_t *first, uint64_t n_texts,
+                             uint64_t n_keywords, uint64_t *row_ptr, uint32_t *col, uint64_t *val,
+                             uint64_t nnz_capacity, uint64_t *nnz);
+size_t acm_gpu_tally_batch_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t capacity,
+                                      uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_tally_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols,
+                                const uint64_t *d_offsets, uint64_t n_texts,
+                                uint64_t window_symbols, uint64_t capacity, uint64_t pair_capacity,
+                                uint64_t *d_row_ptr /* n_texts + 1 */, uint32_t *d_col, uint64_t *d_val,
+                                uint64_t *d_nnz, uint64_t *d_total, uint64_t *d_need, uint64_t *d_need_pairs,
+                                void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_tally_batch_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts,
+                              uint64_t *row_ptr, uint32_t *col, uint64_t *val, uint64_t nnz_capacity,
+                              uint64_t *nnz, uint64_t *total);   /* blocking */
+int acm_tally_batch (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts,
+                     uint64_t *row_ptr, uint32_t *col, uint64_t *val, uint64_t nnz_capacity,
+                     uint64_t *nnz, uint64_t *total);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
