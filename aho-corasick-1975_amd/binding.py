@@ -17,6 +17,7 @@ ACM_GPU_E_HIP = -3
 ACM_GPU_E_OVERFLOW = -4
 ACM_GPU_E_ARG = -5
 ACM_GREP_MATCHING, ACM_GREP_INVERT = 0, 1
+ACM_SPLIT_EVERY, ACM_SPLIT_RUNS = 0, 1
 
 
 class ACMError(RuntimeError):
@@ -93,6 +94,7 @@ EXPORTS = [
     "acm_replace_records", "acm_gpu_replace_tmp_bytes", "acm_gpu_replace_records_device", "acm_gpu_scan_replace_tmp_bytes",
     "acm_gpu_scan_replace_device", "acm_gpu_scan_replace_host", "acm_replace",
     "acm_grep_gather", "acm_gpu_grep_tmp_bytes", "acm_gpu_grep_device", "acm_gpu_grep_host", "acm_grep",
+    "acm_split_offsets", "acm_gpu_split_tmp_bytes", "acm_gpu_split_device", "acm_gpu_split_host", "acm_gpu_grep_lines_host", "acm_grep_lines",
     "acm_tally_batch_records", "acm_gpu_tally_batch_tmp_bytes", "acm_gpu_tally_batch_device", "acm_gpu_tally_batch_host", "acm_tally_batch",
 ]
 
@@ -311,6 +313,17 @@ def lib():
     L.acm_gpu_tally_batch_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.acm_tally_batch.restype = i32
     L.acm_tally_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_split_offsets.restype = i32
+    L.acm_split_offsets.argtypes = [vp, u64, u32, vp, u32, u32, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_split_tmp_bytes.restype = sz
+    L.acm_gpu_split_tmp_bytes.argtypes = [vp, u64]
+    L.acm_gpu_split_device.restype = i32
+    L.acm_gpu_split_device.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_split_host.restype = i32
+    L.acm_gpu_split_host.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, C.POINTER(u64)]
+    for fn in (L.acm_gpu_grep_lines_host, L.acm_grep_lines):
+        fn.restype = i32
+        fn.argtypes = [vp, vp, u64, vp, u32, u32, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, u64, C.POINTER(u64), u64, vp, vp, vp, vp]
     L.acm_gpu_flows_create.restype = i32
     L.acm_gpu_flows_create.argtypes = [vp, u64, C.POINTER(vp)]
     L.acm_gpu_flows_destroy.restype = None
@@ -409,9 +422,10 @@ class Grepped:
     ints (Plan.grep() synchronises to read them): need > capacity says that a window overflowed
     (n_kept = total = out_symbols = 0 then), out_symbols > out_capacity is the room the output needs."""
 
-    def __init__(self, hits, kept, n_kept, total, need, out, out_offsets, out_symbols, out_capacity=None):
+    def __init__(self, hits, kept, n_kept, total, need, out, out_offsets, out_symbols, out_capacity=None, offsets=None, n_texts=None):
         self.hits, self.kept, self.n_kept, self.total, self.need = hits, kept, n_kept, total, need
         self.out, self.out_offsets, self.out_symbols, self.out_capacity = out, out_offsets, out_symbols, out_capacity
+        self.offsets, self.n_texts = offsets, n_texts      # the grep_lines calls: the n_texts + 1 offsets the buffer was cut at
 
 
 def _grep_host_call(fn, what, handle, t, sym_size, off, invert, gather, out_capacity):
@@ -533,6 +547,62 @@ def tally_batch_records(records, first, n_keywords):
     _check(lib().acm_tally_batch_records(data, f.ctypes.data, n_texts, int(n_keywords), row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data, k,
                                          C.byref(nnz)), "acm_tally_batch_records")
     return TalliedBatch(row_ptr, col[:k], val[:k], k, int(val[:k].sum()))
+
+
+def _delims(delims, sym_size, raw=False):
+    """delimiters as a contiguous array of whole symbols: bytes are one symbol per byte, widened to the
+    symbol size (b"\\n" is the symbol 10), unless `raw` (symbols without a numpy type: the bytes as they are)"""
+    if raw or sym_size not in _SYM_DTYPE:
+        d = np.frombuffer(bytes(delims), dtype=np.uint8) if isinstance(delims, (bytes, bytearray)) else np.ascontiguousarray(delims).reshape(-1).view(np.uint8)
+        assert d.size % sym_size == 0
+        return d, d.size // sym_size
+    if isinstance(delims, (bytes, bytearray)):
+        delims = np.frombuffer(bytes(delims), dtype=np.uint8)
+    d = np.ascontiguousarray(np.asarray(delims).reshape(-1), dtype=_SYM_DTYPE[sym_size])
+    return d, d.size
+
+
+def split_offsets(text, delims=b"\n", runs=False, sym_size=None):
+    """acm_split_offsets(): the offsets of the texts a buffer holds between its delimiter symbols, by
+    the sequential pass on the host -- lines (a cut behind every delimiter) or, with runs, words (a cut
+    behind every run of delimiters); an unterminated last text counts.  `text` is an array of symbols;
+    with sym_size, raw bytes of symbols of that size, and `delims` raw bytes too.  Returns the
+    n_texts + 1 offsets as a numpy uint64 array."""
+    t = np.ascontiguousarray(text)
+    sb = int(sym_size) if sym_size is not None else t.itemsize
+    d, nd = _delims(delims, sb, raw=sym_size is not None)
+    n_sym = t.size * t.itemsize // sb
+    flags = ACM_SPLIT_RUNS if runs else ACM_SPLIT_EVERY
+    n = C.c_uint64(0)
+    _check(lib().acm_split_offsets(t.ctypes.data if t.size else None, n_sym, sb, d.ctypes.data, nd, flags, None, 0, C.byref(n)), "acm_split_offsets")
+    off = np.zeros(int(n.value) + 1, np.uint64)
+    _check(lib().acm_split_offsets(t.ctypes.data if t.size else None, n_sym, sb, d.ctypes.data, nd, flags, off.ctypes.data, int(n.value), C.byref(n)),
+           "acm_split_offsets")
+    return off
+
+
+def _grep_lines_host_call(fn, what, handle, t, sym_size, d, nd, runs, invert, gather):
+    """acm_gpu_grep_lines_host / acm_grep_lines: numpy in, a Grepped of numpy arrays out.  A first call
+    with no room for a text learns n_texts (it ends behind the split's count), the second has room."""
+    n_sym = t.size * t.itemsize // sym_size
+    sflags, gflags = ACM_SPLIT_RUNS if runs else ACM_SPLIT_EVERY, ACM_GREP_INVERT if invert else ACM_GREP_MATCHING
+    nt, nk, total, sym = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    tp = t.ctypes.data if t.size else None
+    one = np.zeros(1, np.uint64)
+    rc = fn(handle, tp, n_sym, d.ctypes.data, nd, sflags, gflags, C.byref(nt), C.byref(nk), C.byref(total), None, 0, C.byref(sym), 0,
+            one.ctypes.data, None, None, None)
+    if rc != ACM_GPU_E_OVERFLOW:
+        _check(rc, what)
+    n = int(nt.value)
+    off, out_off = np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+    hits, kept = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32)
+    out = np.zeros(max(n_sym * sym_size // t.itemsize, 1), dtype=t.dtype) if gather else None       # the kept texts never need more than all
+    _check(fn(handle, tp, n_sym, d.ctypes.data, nd, sflags, gflags, C.byref(nt), C.byref(nk), C.byref(total), out.ctypes.data if gather else None,
+              n_sym if gather else 0, C.byref(sym), n, off.ctypes.data, hits.ctypes.data, kept.ctypes.data, out_off.ctypes.data), what)
+    assert int(nt.value) == n
+    k, s = int(nk.value), int(sym.value)
+    return Grepped(hits[:n], kept[:k], k, int(total.value), None, out[:s * sym_size // t.itemsize] if gather else None, out_off[:k + 1], s, n_sym,
+                   offsets=off, n_texts=n)
 
 
 class FlatTables:
@@ -909,6 +979,18 @@ class Machine:
         packed = np.concatenate([p.view(dtype) for p in parts]) if parts else np.zeros(0, dtype)
         return _grep_host_call(self.L.acm_grep, "acm_grep", self.handle, packed, self.sym_size, offsets, invert, gather, None)
 
+    def grep_lines(self, buffer, delims=b"\n", runs=False, invert=False, gather=True):
+        """acm_grep_lines(): `grep -F -f keywords file` on a raw buffer (bytes or an array of symbols):
+        cut into texts at the delimiter symbols -- lines, or with runs words --, each text scanned from
+        the root on its own, all in ONE call.  Returns a Grepped of numpy arrays that also carries the
+        `offsets` the buffer was cut at and `n_texts`; a kept line keeps its delimiter."""
+        if self.sym_size in _SYM_DTYPE:
+            t = self._symbols(buffer).reshape(-1)
+        else:
+            t = np.frombuffer(bytes(buffer), dtype=np.uint8) if isinstance(buffer, (bytes, bytearray)) else np.ascontiguousarray(buffer).reshape(-1)
+        d, nd = _delims(delims, self.sym_size)
+        return _grep_lines_host_call(self.L.acm_grep_lines, "acm_grep_lines", self.handle, t, self.sym_size, d, nd, runs, invert, gather)
+
     def tally_batch(self, texts):
         """acm_tally_batch(): which keywords occur how often in which text of a list of texts (bytes or
         arrays of symbols), each scanned from the root on its own in ONE call.  Returns a TalliedBatch
@@ -1223,6 +1305,67 @@ class Plan:
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         assert off.size >= 1, "offsets has n_texts + 1 entries"
         return _grep_host_call(lib().acm_gpu_grep_host, "acm_gpu_grep_host", self.h, t, self.sym_size, off, invert, gather, out_capacity)
+
+    def split(self, text, delims=b"\n", runs=False, capacity=None):
+        """acm_gpu_split_device(): the offsets of the texts a device buffer holds between its delimiter
+        symbols -- lines, or with runs words (a text is a word and the run of delimiters behind it); an
+        unterminated last text counts.  `text` is a device tensor of symbols, `delims` up to 16 symbols
+        (bytes: one symbol per byte).  Returns the int64 device tensor offsets[: n_texts + 1], which
+        Plan.grep, Plan.scan_batch, Plan.tally_batch and Flows take as it is.  Without `capacity` the
+        texts are counted first (one synchronise) and the tensor is sized by the count; with it the
+        call raises ACM_GPU_E_OVERFLOW, the count needed in its `need`, when there are more texts."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        n_symbols = text.numel() * text.element_size() // self.sym_size
+        d, nd = _delims(delims, self.sym_size)
+        flags = ACM_SPLIT_RUNS if runs else ACM_SPLIT_EVERY
+        dev = text.device
+        tmp = torch.empty(max(lib().acm_gpu_split_tmp_bytes(self.h, n_symbols), 16), dtype=torch.uint8, device=dev)
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+
+        def call(off, cap):
+            _check(lib().acm_gpu_split_device(self.h, text.data_ptr(), n_symbols, d.ctypes.data, nd, flags, off.data_ptr() if off is not None else None,
+                                              cap, count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_split_device")
+        if capacity is None:
+            call(None, 0)
+            capacity = int(count.item())
+        off = torch.zeros(int(capacity) + 1, dtype=torch.int64, device=dev)
+        call(off, int(capacity))
+        n = int(count.item())
+        if n > int(capacity):
+            e = ACMError(ACM_GPU_E_OVERFLOW, "acm_gpu_split_device: %d texts, room for %d" % (n, int(capacity)))
+            e.need = n
+            raise e
+        return off[:n + 1]
+
+    def split_host(self, text, delims=b"\n", runs=False, capacity=None):
+        """acm_gpu_split_host(): the same from a host array, through the C ABI only (no torch).  Returns
+        the n_texts + 1 offsets as a numpy uint64 array; with `capacity`, raises on more texts as split()."""
+        t = np.ascontiguousarray(text)
+        n_symbols = t.size * t.itemsize // self.sym_size
+        d, nd = _delims(delims, self.sym_size)
+        flags = ACM_SPLIT_RUNS if runs else ACM_SPLIT_EVERY
+        n = C.c_uint64(0)
+        tp = t.ctypes.data if t.size else None
+        if capacity is None:
+            _check(lib().acm_gpu_split_host(self.h, tp, n_symbols, d.ctypes.data, nd, flags, None, 0, C.byref(n)), "acm_gpu_split_host")
+            capacity = int(n.value)
+        off = np.zeros(int(capacity) + 1, np.uint64)
+        rc = lib().acm_gpu_split_host(self.h, tp, n_symbols, d.ctypes.data, nd, flags, off.ctypes.data, int(capacity), C.byref(n))
+        if rc == ACM_GPU_E_OVERFLOW:
+            e = ACMError(rc, "acm_gpu_split_host: %d texts, room for %d" % (n.value, int(capacity)))
+            e.need = int(n.value)
+            raise e
+        _check(rc, "acm_gpu_split_host")
+        return off[:int(n.value) + 1]
+
+    def grep_lines_host(self, text, delims=b"\n", runs=False, invert=False, gather=True):
+        """acm_gpu_grep_lines_host(): `grep -F -f` on a raw buffer in host memory: uploaded once, cut
+        into texts on the device, then grep as grep_host() runs it.  Returns a Grepped of numpy arrays
+        that also carries `offsets` and `n_texts`."""
+        t = np.ascontiguousarray(text).reshape(-1)
+        d, nd = _delims(delims, self.sym_size)
+        return _grep_lines_host_call(lib().acm_gpu_grep_lines_host, "acm_gpu_grep_lines_host", self.h, t, self.sym_size, d, nd, runs, invert, gather)
 
     def tally_batch(self, text, offsets, window=None, capacity=None, pair_capacity=None):
         """acm_gpu_tally_batch_device(): the text x keyword count matrix of a batch on the device, in

@@ -4036,15 +4036,14 @@ acm_gpu_grep_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, cons
   return ACM_GPU_OK;
 }
 
-extern "C" int
-acm_gpu_grep_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t flags, uint64_t *hits, uint32_t *kept,
-                   uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols) {
-  if (!plan || !n_kept || n_texts >= (1ull << 31) || flags > ACM_GREP_INVERT || !batch_offsets_ok (offsets, n_texts))
-    return ACM_GPU_E_ARG;
-  const uint64_t n_symbols = offsets[n_texts];
-  if (n_symbols && !text)
-    return ACM_GPU_E_ARG;
-  HIP_TRY (hipSetDevice (plan->device));
+namespace {
+/* what acm_gpu_grep_host and acm_gpu_grep_lines_host do once the text and its offsets are on the
+ * device (blocks of `temps`, which also owns what this makes): the window and capacity choice, the
+ * one repeat, the downloads.  Arguments as acm_gpu_grep_host's, checked by the caller. */
+int
+grep_resident (ACMPlan *plan, DeviceTemps &temps, const void *d_text, uint64_t n_symbols, const uint64_t *d_off, uint64_t n_texts, uint32_t flags,
+               uint64_t *hits, uint32_t *kept, uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets,
+               uint64_t *out_symbols) {
   /* the window and the record room as acm_gpu_tally_host picks them, ACM_GPU_TALLY_CAPACITY included */
   uint64_t window = 1ull << 25, capacity = 1ull << 21;
   if (const char *e = getenv ("ACM_GPU_TALLY_CAPACITY"))
@@ -4053,24 +4052,17 @@ acm_gpu_grep_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uin
   if (n_symbols < (1ull << 31) / tally_max_outputs (plan) && n_symbols * tally_max_outputs (plan) < capacity)
     capacity = n_symbols ? n_symbols * tally_max_outputs (plan) : 1;
   const uint32_t sb = plan->text_sym_bytes;
-  const size_t tbytes = (size_t)n_symbols * sb;
   if (!out)
     out_capacity = 0;
-  DeviceTemps temps;
-  void *d_text = nullptr, *d_tmp = nullptr, *d_out = nullptr;
-  uint64_t *d_off = nullptr, *d_hits = nullptr, *d_out_off = nullptr, *d_res = nullptr; /* d_res: n_kept, total, need, out_symbols */
+  void *d_tmp = nullptr, *d_out = nullptr;
+  uint64_t *d_hits = nullptr, *d_out_off = nullptr, *d_res = nullptr; /* d_res: n_kept, total, need, out_symbols */
   uint32_t *d_kept = nullptr;
-  HOST_TRY (temps.get (&d_text, tbytes));
-  HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
   HOST_TRY (temps.get (&d_hits, n_texts * 8));
   HOST_TRY (temps.get (&d_kept, n_texts * 4));
   HOST_TRY (temps.get (&d_out_off, (n_texts + 1) * 8));
   HOST_TRY (temps.get (&d_res, 32));
   if (out)
     HOST_TRY (temps.get (&d_out, (size_t)out_capacity * sb));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
   uint64_t res[4] = { 0, 0, 0, 0 };
   for (int attempt = 0; attempt < 2; attempt++) {
     const size_t tmp_bytes = acm_gpu_grep_tmp_bytes (plan, window, capacity, n_symbols, n_texts);
@@ -4117,6 +4109,223 @@ acm_gpu_grep_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uin
   if (symbols)
     HOST_TRY (hipMemcpy (out, d_out, (size_t)symbols * sb, hipMemcpyDeviceToHost));
   return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_grep_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t flags, uint64_t *hits, uint32_t *kept,
+                   uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols) {
+  if (!plan || !n_kept || n_texts >= (1ull << 31) || flags > ACM_GREP_INVERT || !batch_offsets_ok (offsets, n_texts))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_symbols = offsets[n_texts];
+  if (n_symbols && !text)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
+  DeviceTemps temps;
+  void *d_text = nullptr;
+  uint64_t *d_off = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+  return grep_resident (plan, temps, d_text, n_symbols, d_off, n_texts, flags, hits, kept, n_kept, total, out, out_capacity, out_offsets, out_symbols);
+}
+
+/* ------------------------------------------------------------------ a buffer cut into texts (include/acm_gpu.h, dev_split.h)
+ * Count per tile, prefix sum over the tiles, write.  The plan gives its device, its caller symbol
+ * size and its grid cap, nothing else. */
+namespace {
+struct SplitLayout {
+  uint32_t tile_words = 0;
+  uint64_t n_words = 0, n_tiles = 0;
+  size_t o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, total = 0;
+};
+
+/* ACM_GPU_SPLIT_TILE=<bytes of text>: the passes' tile, a multiple of 16 (tests; read at every call) */
+uint32_t
+split_tile (void) {
+  const int t = env_int ("ACM_GPU_SPLIT_TILE", (int)SPLIT_TILE_DEFAULT);
+  return t >= (int)SPLIT_TILE_MIN && t <= (int)SPLIT_TILE_MAX && t % 16 == 0 ? (uint32_t)t : SPLIT_TILE_DEFAULT;
+}
+
+/* the scratch is laid out for the most words a text of this size can touch (15 bytes off the grid);
+ * n_words and n_tiles are those of the text's own address mod 16, `mis` */
+SplitLayout
+split_layout (uint64_t n_symbols, uint32_t sb, uint32_t mis) {
+  SplitLayout L;
+  L.tile_words = split_tile () / 16;
+  L.n_words = (n_symbols * sb + mis + 15) / 16;
+  L.n_tiles = (L.n_words + L.tile_words - 1) / L.tile_words;
+  const uint64_t most_tiles = ((n_symbols * sb + 30) / 16 + L.tile_words - 1) / L.tile_words;
+  L.cub_bytes = exclusive_sum_bytes64 (most_tiles + 1);
+  size_t cur = 0;
+  L.o_count = blob_reserve (cur, (most_tiles + 1) * 8);
+  L.o_begin = blob_reserve (cur, (most_tiles + 1) * 8);
+  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
+  L.total = cur + 256;
+  return L;
+}
+
+bool
+split_size_ok (const ACMPlan *plan, uint64_t n_symbols) {
+  return n_symbols < (1ull << 56) / plan->text_sym_bytes && (n_symbols * plan->text_sym_bytes + 30) / 16 / (SPLIT_TILE_MIN / 16) + 2 < (1ull << 31);
+}
+
+template <int SB>
+void
+split_launch (const ACMPlan *plan, const SplitLayout &L, const SplitK &K, unsigned char *t, hipStream_t st, hipError_t *err) {
+  hipLaunchKernelGGL (split_count_kernel<SB>, capped_grid (plan, L.n_tiles + 1), dim3 (SPLIT_THREADS), 0, st, K);
+  if ((*err = hipGetLastError ()) != hipSuccess)
+    return;
+  size_t cub = L.cub_bytes;
+  *err = hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_count), reinterpret_cast<long long *> (t + L.o_begin),
+                                           (int)(L.n_tiles + 1), st);
+  if (*err != hipSuccess)
+    return;
+  hipLaunchKernelGGL (split_write_kernel<SB>, K.offsets ? capped_grid (plan, L.n_tiles) : dim3 (1), dim3 (SPLIT_THREADS), 0, st, K);
+  *err = hipGetLastError ();
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_split_tmp_bytes (const ACMPlan *plan, uint64_t n_symbols) {
+  if (!plan || !split_size_ok (plan, n_symbols))
+    return 0;
+  return split_layout (n_symbols, plan->text_sym_bytes, 15).total;
+}
+
+extern "C" int
+acm_gpu_split_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const void *delims, uint32_t n_delims, uint32_t flags, uint64_t *d_offsets,
+                      uint64_t capacity, uint64_t *d_n_texts, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_n_texts || !delims || n_delims == 0 || n_delims > ACM_SPLIT_MAX_DELIMS || flags > ACM_SPLIT_RUNS || (n_symbols && !d_text) ||
+      (d_offsets && capacity >= (1ull << 31)) || !split_size_ok (plan, n_symbols))
+    return ACM_GPU_E_ARG;
+  const uint32_t sb = plan->text_sym_bytes;
+  const uintptr_t t0 = reinterpret_cast<uintptr_t> (d_text);
+  if (t0 % sb)
+    return ACM_GPU_E_ARG;
+  const SplitLayout L = split_layout (n_symbols, sb, (uint32_t)(t0 & 15));
+  if (n_symbols && (!d_tmp || tmp_bytes < L.total))
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  HIP_TRY (hipSetDevice (plan->device));
+  if (n_symbols == 0) { /* no symbol: no text, offsets = [0] */
+    HIP_TRY (hipMemsetAsync (d_n_texts, 0, 8, st));
+    if (d_offsets)
+      HIP_TRY (hipMemsetAsync (d_offsets, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  SplitK K{};
+  K.text = static_cast<const unsigned char *> (d_text);
+  K.n_symbols = n_symbols;
+  for (uint32_t j = 0; j < n_delims; j++) { /* the caller's symbols, bit for bit; below 4 bytes repeated over 32 bits */
+    unsigned long long v = 0;
+    memcpy (&v, static_cast<const unsigned char *> (delims) + (size_t)j * sb, sb);
+    K.delim[j] = sb == 1 ? v * 0x01010101ull : sb == 2 ? v * 0x00010001ull : v;
+  }
+  K.n_delims = n_delims;
+  K.runs = flags == ACM_SPLIT_RUNS;
+  K.tile_words = L.tile_words;
+  K.n_words = L.n_words;
+  K.n_tiles = L.n_tiles;
+  K.tile_count = reinterpret_cast<unsigned long long *> (t + L.o_count);
+  K.tile_begin = reinterpret_cast<const unsigned long long *> (t + L.o_begin);
+  K.offsets = reinterpret_cast<unsigned long long *> (d_offsets);
+  K.capacity = capacity;
+  K.d_n_texts = reinterpret_cast<unsigned long long *> (d_n_texts);
+  hipError_t err = hipSuccess;
+  switch (sb) {
+  case 1: split_launch<1> (plan, L, K, t, st, &err); break;
+  case 2: split_launch<2> (plan, L, K, t, st, &err); break;
+  case 4: split_launch<4> (plan, L, K, t, st, &err); break;
+  case 8: split_launch<8> (plan, L, K, t, st, &err); break;
+  default: return ACM_GPU_E_ARG;
+  }
+  HIP_TRY (err);
+  return ACM_GPU_OK;
+}
+
+namespace {
+/* the count run of a text on the device and its one round trip: *n_texts */
+int
+split_count_resident (ACMPlan *plan, DeviceTemps &temps, const void *d_text, uint64_t n_symbols, const void *delims, uint32_t n_delims, uint32_t flags,
+                      void **d_tmp, size_t *tmp_bytes, uint64_t **d_n, uint64_t *n_texts) {
+  *tmp_bytes = acm_gpu_split_tmp_bytes (plan, n_symbols);
+  HOST_TRY (temps.get (d_tmp, *tmp_bytes));
+  HOST_TRY (temps.get (d_n, 8));
+  const int rc = acm_gpu_split_device (plan, d_text, n_symbols, delims, n_delims, flags, nullptr, 0, *d_n, *d_tmp, *tmp_bytes, nullptr);
+  if (rc)
+    return rc;
+  HOST_TRY (hipMemcpy (n_texts, *d_n, 8, hipMemcpyDeviceToHost));
+  return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_split_host (ACMPlan *plan, const void *text, uint64_t n_symbols, const void *delims, uint32_t n_delims, uint32_t flags, uint64_t *offsets,
+                    uint64_t capacity, uint64_t *n_texts) {
+  if (!plan || !n_texts || !delims || n_delims == 0 || n_delims > ACM_SPLIT_MAX_DELIMS || flags > ACM_SPLIT_RUNS || (n_symbols && !text) ||
+      !split_size_ok (plan, n_symbols))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_n = nullptr, *d_off = nullptr;
+  size_t tmp_bytes = 0;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  int rc = split_count_resident (plan, temps, d_text, n_symbols, delims, n_delims, flags, &d_tmp, &tmp_bytes, &d_n, n_texts);
+  if (rc || !offsets)
+    return rc;
+  if (*n_texts > capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (*n_texts >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  HOST_TRY (temps.get (&d_off, (*n_texts + 1) * 8));
+  rc = acm_gpu_split_device (plan, d_text, n_symbols, delims, n_delims, flags, d_off, *n_texts, d_n, d_tmp, tmp_bytes, nullptr);
+  if (rc)
+    return rc;
+  HOST_TRY (hipMemcpy (offsets, d_off, (*n_texts + 1) * 8, hipMemcpyDeviceToHost));
+  return ACM_GPU_OK;
+}
+
+extern "C" int
+acm_gpu_grep_lines_host (ACMPlan *plan, const void *text, uint64_t n_symbols, const void *delims, uint32_t n_delims, uint32_t split_flags,
+                         uint32_t grep_flags, uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity,
+                         uint64_t *out_symbols, uint64_t texts_capacity, uint64_t *offsets, uint64_t *hits, uint32_t *kept, uint64_t *out_offsets) {
+  if (!plan || !n_texts || !n_kept || !delims || n_delims == 0 || n_delims > ACM_SPLIT_MAX_DELIMS || split_flags > ACM_SPLIT_RUNS ||
+      grep_flags > ACM_GREP_INVERT || (n_symbols && !text) || !split_size_ok (plan, n_symbols))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_n = nullptr, *d_off = nullptr;
+  size_t tmp_bytes = 0;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  int rc = split_count_resident (plan, temps, d_text, n_symbols, delims, n_delims, split_flags, &d_tmp, &tmp_bytes, &d_n, n_texts);
+  if (rc)
+    return rc;
+  const uint64_t n = *n_texts;
+  if ((offsets || hits || kept || out_offsets) && n > texts_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (n >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  HOST_TRY (temps.get (&d_off, (n + 1) * 8));
+  rc = acm_gpu_split_device (plan, d_text, n_symbols, delims, n_delims, split_flags, d_off, n, d_n, d_tmp, tmp_bytes, nullptr);
+  if (rc)
+    return rc;
+  if (offsets) /* (the default stream: behind the split) */
+    HOST_TRY (hipMemcpy (offsets, d_off, (n + 1) * 8, hipMemcpyDeviceToHost));
+  HOST_TRY (temps.release (d_tmp));
+  return grep_resident (plan, temps, d_text, n_symbols, d_off, n, grep_flags, hits, kept, n_kept, total, out, out_capacity, out_offsets, out_symbols);
 }
 
 /* ------------------------------------------------------------------ per-text keyword counts of a batch (include/acm_gpu.h, dev_tally_batch.h)
@@ -5452,7 +5661,7 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally only a scan that
  * succeeded, acm_select and acm_scan_from also one that found more records than there was room for,
- * acm_replace, acm_grep and acm_tally_batch also one whose output had no room. */
+ * acm_replace, acm_grep, acm_grep_lines and acm_tally_batch also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -5478,7 +5687,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The eight calls below run on the same route, the same cached plan, under the same lock. */
+/* The nine calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -5596,6 +5805,26 @@ acm_grep (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_
     },
     [&] (ACMPlan *plan) {
       return acm_gpu_grep_host (plan, text, offsets, n_texts, flags, hits, kept, n_kept, total, out, out_capacity, out_offsets, out_symbols);
+    });
+}
+
+/* grep over a raw buffer, split at delimiters first (include/acm_gpu.h) */
+extern "C" int
+acm_grep_lines (ACMachine *machine, const void *text, uint64_t n_symbols, const void *delims, uint32_t n_delims, uint32_t split_flags, uint32_t grep_flags,
+                uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t texts_capacity,
+                uint64_t *offsets, uint64_t *hits, uint32_t *kept, uint64_t *out_offsets) {
+  if (!machine || !n_texts || !n_kept || !delims || n_delims == 0 || n_delims > ACM_SPLIT_MAX_DELIMS || split_flags > ACM_SPLIT_RUNS ||
+      grep_flags > ACM_GREP_INVERT || (n_symbols && !text))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      return acm_internal_cpu_grep_lines (machine, text, n_symbols, said, delims, n_delims, split_flags, grep_flags, n_texts, n_kept, total, out,
+                                          out_capacity, out_symbols, texts_capacity, offsets, hits, kept, out_offsets);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_grep_lines_host (plan, text, n_symbols, delims, n_delims, split_flags, grep_flags, n_texts, n_kept, total, out, out_capacity,
+                                      out_symbols, texts_capacity, offsets, hits, kept, out_offsets);
     });
 }
 

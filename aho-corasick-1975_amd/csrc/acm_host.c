@@ -876,6 +876,87 @@ acm_grep_gather (const void *text, uint32_t sym_bytes, const uint64_t *offsets, 
   return ACM_GPU_OK;
 }
 
+/* SPLIT of a buffer at delimiter symbols (include/acm_gpu.h): the plain sequential pass.  The cuts
+ * are counted first, so that nothing is written to offsets[] when it has no room. */
+static int
+split_is_delim (const unsigned char *sym, size_t sb, const unsigned char *delims, uint32_t n_delims) {
+  for (uint32_t d = 0; d < n_delims; d++)
+    if (memcmp (sym, delims + d * sb, sb) == 0)
+      return 1;
+  return 0;
+}
+
+int
+acm_split_offsets (const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *delims, uint32_t n_delims, uint32_t flags, uint64_t *offsets,
+                   uint64_t capacity, uint64_t *n_texts) {
+  if (!sym_bytes || !n_texts || !delims || n_delims == 0 || n_delims > ACM_SPLIT_MAX_DELIMS || flags > ACM_SPLIT_RUNS || (n_symbols && !text))
+    return ACM_GPU_E_ARG;
+  const unsigned char *t = text;
+  const size_t sb = sym_bytes;
+  const int runs = flags == ACM_SPLIT_RUNS;
+  for (int write = 0; write < 2; write++) {
+    uint64_t k = 0;
+    int here = n_symbols ? split_is_delim (t, sb, delims, n_delims) : 0;
+    if (write)
+      offsets[0] = 0;
+    for (uint64_t i = 0; i < n_symbols; i++) {
+      const int next = i + 1 < n_symbols ? split_is_delim (t + (i + 1) * sb, sb, delims, n_delims) : 0;
+      if (i + 1 == n_symbols || (here && !(runs && next))) {
+        k++;
+        if (write)
+          offsets[k] = i + 1;
+      }
+      here = next;
+    }
+    *n_texts = k;
+    if (!offsets)
+      break;
+    if (k > capacity)
+      return ACM_GPU_E_OVERFLOW;
+  }
+  return ACM_GPU_OK;
+}
+
+/* acm_grep_lines on the host (include/acm_gpu.h): the split, the caller loop from the root on every
+ * text, counting, then the sequential gather -- what ACM_SCAN_PATH_CPU_LOOP runs. */
+int
+acm_internal_cpu_grep_lines (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *delims, uint32_t n_delims,
+                             uint32_t split_flags, uint32_t grep_flags, uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out,
+                             uint64_t out_capacity, uint64_t *out_symbols, uint64_t texts_capacity, uint64_t *offsets, uint64_t *hits, uint32_t *kept,
+                             uint64_t *out_offsets) {
+  if (!m || !n_texts || !n_kept || grep_flags > ACM_GREP_INVERT)
+    return ACM_GPU_E_ARG;
+  uint64_t n = 0;
+  int rc = acm_split_offsets (text, n_symbols, sym_bytes, delims, n_delims, split_flags, NULL, 0, &n);
+  if (rc)
+    return rc;
+  *n_texts = n;
+  if ((offsets || hits || kept || out_offsets) && n > texts_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (n >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  uint64_t *own_off = offsets ? NULL : malloc ((n + 1) * sizeof (uint64_t));
+  uint64_t *own_hits = hits ? NULL : malloc ((n + 1) * sizeof (uint64_t));
+  uint64_t *off = offsets ? offsets : own_off, *h = hits ? hits : own_hits;
+  if (!off || !h)
+    rc = ACM_GPU_E_NOMEM;
+  if (!rc)
+    rc = acm_split_offsets (text, n_symbols, sym_bytes, delims, n_delims, split_flags, off, n, &n);
+  if (!rc)
+    rc = acm_internal_cpu_grep_hits (m, text, off, n, sym_bytes, h);
+  if (!rc) {
+    if (total) {
+      *total = 0;
+      for (uint64_t t = 0; t < n; t++)
+        *total += h[t];
+    }
+    rc = acm_grep_gather (text, sym_bytes, off, n, h, grep_flags, kept, n_kept, out, out ? out_capacity : 0, out_offsets, out_symbols);
+  }
+  free (own_off);
+  free (own_hits);
+  return rc;
+}
+
 static int
 cmp_u32 (const void *a, const void *b) {
   const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b;

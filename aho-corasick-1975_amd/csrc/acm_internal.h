@@ -68,6 +68,11 @@ int acm_internal_cpu_tally (ACMachine *m, const void *text, uint64_t n_symbols, 
 /* the same loop from the root on every text of a batch, counting per text instead of recording (acm_grep): hits[t] = the
  * number of matches of text t; offsets[] already checked */
 int acm_internal_cpu_grep_hits (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint64_t *hits);
+/* acm_grep_lines' host path: acm_split_offsets, the loop above, acm_grep_gather (arguments as acm_grep_lines') */
+int acm_internal_cpu_grep_lines (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *delims, uint32_t n_delims,
+                                 uint32_t split_flags, uint32_t grep_flags, uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out,
+                                 uint64_t out_capacity, uint64_t *out_symbols, uint64_t texts_capacity, uint64_t *offsets, uint64_t *hits,
+                                 uint32_t *kept, uint64_t *out_offsets);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

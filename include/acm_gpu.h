@@ -831,6 +831,102 @@ int acm_tally_batch (ACMachine *machine, const void *text, const uint64_t *offse
                      uint64_t *row_ptr, uint32_t *col, uint64_t *val, uint64_t nnz_capacity,
                      uint64_t *nnz, uint64_t *total);
 
+/* ------------------------------------------------------------------ a buffer cut into texts: the batch calls' front end
+ * Every batch call above takes offsets[] as given.  A caller with a file or a capture holds ONE
+ * buffer with delimiters in it -- log lines, cells, the words that
+ * examples/aho_corasick_generic_test.c:168-210 reads one by one -- and these calls make the offsets
+ * from it, on the device, so that the text never has to visit the host for it.
+ *
+ * DEFINITION.  SPLIT (text[0 .. n), delims[0 .. d), flags); all symbols have the caller's symbol
+ * size; 1 <= d <= 16 (ACM_SPLIT_MAX_DELIMS).
+ *   is_delim (i): text[i] equals one of delims[] BIT FOR BIT, in the caller's symbols -- never in the
+ *     class-mapped or interned copy a plan keeps for its scan (acm_replace's rule): under a
+ *     case-folding comparator and the delimiter "x", "X" is no delimiter.
+ *   ACM_SPLIT_EVERY (0): there is a cut behind every i with is_delim (i).  These are lines:
+ *     "a\n\nb" is the three texts "a\n", "\n", "b".
+ *   ACM_SPLIT_RUNS (1): there is a cut behind i when is_delim (i) and (i + 1 == n or not
+ *     is_delim (i + 1)).  These are words: a text is a word with the whole run of delimiters that
+ *     follows it; a run at the very front of the buffer is a text of its own.
+ *   In both modes there is a cut behind n - 1 when n > 0: an unterminated last line is a text.
+ *   offsets = [0] ++ [i + 1 for every cut, ascending]; n_texts = the number of cuts; n = 0 gives
+ *   n_texts = 0 and offsets = [0].
+ * Offsets ascend strictly, offsets[0] = 0 and offsets[n_texts] = n: exactly the batch contract (no
+ * text is empty), so the result feeds every acm_gpu_*_batch / flows / grep / tally_batch call as it
+ * is.  The delimiter is the LAST symbol(s) of the text it ends: the gathered output of a grep
+ * reproduces the kept lines with their newlines, as `grep` prints them.  A keyword that contains a
+ * delimiter can therefore match only at the end of a text (under RUNS, and for a keyword of
+ * several delimiters, only in the run that ends one).
+ *
+ * acm_split_offsets: the plain sequential pass on the host, no device; any sym_bytes > 0 (memcmp).
+ * offsets (room for capacity + 1) may be NULL: the call only counts and ignores capacity.
+ * ACM_GPU_E_OVERFLOW with *n_texts = the count needed, and nothing written to offsets, when
+ * capacity is too small.  ACM_GPU_E_ARG for n_delims of 0 or above 16 and for flags above 1.
+ *
+ * acm_gpu_split_device: the same on the device (dev_split.h).  The symbol size is the plan's caller
+ * symbol size (1, 2, 4 or 8); the plan is used for nothing but its device, that size and its grid
+ * cap, so a plan with a pending delta, a class plan and an interned 8-byte plan behave alike, and no
+ * contract can be broken by data: acm_gpu_plan_status is not involved.  `delims` is HOST memory,
+ * n_delims symbols; they travel as kernel arguments, nothing is copied and delims may be freed on
+ * return.  Outputs, device memory, valid when `stream` has passed: *d_n_texts is always the exact
+ * count; d_offsets[0 .. *d_n_texts] when *d_n_texts <= capacity.  *d_n_texts > capacity: it is the
+ * capacity needed, d_offsets[0 .. capacity] is unspecified and nothing was written outside it.
+ * d_offsets NULL: the call only counts and ignores capacity.  ACM_GPU_E_ARG: capacity >= 2^31 with
+ * d_offsets given (the batch calls refuse such an n_texts anyway), n_delims of 0 or above 16, flags
+ * above 1, a d_text that is no multiple of the symbol size, a tmp_bytes that is too small.  d_text
+ * may have ANY alignment that is a multiple of the symbol size: the kernels load whole aligned
+ * 16-byte words (replace's and grep's rule: up to 15 bytes in front of and behind the buffer are
+ * read, never beyond the aligned word that holds a byte of it), and a symbol outside [0, n) never
+ * counts, whatever its value.  Two passes over tiles of 16,384 bytes of the text
+ * (ACM_GPU_SPLIT_TILE=<bytes> in the environment sets another: a multiple of 16 from 256 to 1 Mi,
+ * read at every call) with a prefix sum over the tiles' counts between them.  d_tmp must hold
+ * acm_gpu_split_tmp_bytes (plan, n_symbols) bytes -- 16 per tile, for the tile size in force -- (0
+ * for a buffer the call would refuse).  The call only queues launches on `stream`, with no host
+ * round trip.
+ * acm_gpu_split_host: the same from host memory, blocking.  ACM_GPU_E_OVERFLOW with *n_texts = the
+ * count needed when capacity is too small.
+ *
+ * acm_gpu_grep_lines_host: `grep -F -f keywords file` on a raw buffer in host memory, blocking.  The
+ * text is uploaded once and split on the device -- a count run, ONE host round trip for n_texts,
+ * which sizes the per-text buffers, then the run that writes the offsets --, then grep runs exactly
+ * as acm_gpu_grep_host runs it (same window and capacity choice, ACM_GPU_TALLY_CAPACITY, the one
+ * repeat).  *n_texts and *n_kept are required.  offsets (texts_capacity + 1 entries), hits, kept
+ * (texts_capacity each) and out_offsets (texts_capacity + 1) are optional.  ACM_GPU_E_OVERFLOW has
+ * two meanings, told apart by the caller: *n_texts > texts_capacity while a per-text array was
+ * asked for -- only *n_texts is valid, nothing else was written --; otherwise *out_symbols >
+ * out_capacity -- everything but `out` is valid, as in acm_gpu_grep_host.  With all four per-text
+ * pointers NULL there is no first kind.  A buffer of 2^31 texts or more is ACM_GPU_E_ARG
+ * (*n_texts says how many).
+ * acm_grep_lines: the call on the machine itself, total over machines exactly as acm_grep is (same
+ * three paths, acm_scan_path recorded on success and on either overflow): the GPU paths run
+ * acm_gpu_grep_lines_host, ACM_SCAN_PATH_CPU_LOOP runs acm_split_offsets with the declared symbol
+ * size, then the host loop acm_grep uses, then acm_grep_gather.  A missing device stays an error. */
+#define ACM_SPLIT_EVERY 0
+#define ACM_SPLIT_RUNS 1
+#define ACM_SPLIT_MAX_DELIMS 16
+int acm_split_offsets (const void *text, uint64_t n_symbols, uint32_t sym_bytes,
+                       const void *delims, uint32_t n_delims, uint32_t flags,
+                       uint64_t *offsets /* capacity + 1, may be NULL: count only */, uint64_t capacity,
+                       uint64_t *n_texts);
+size_t acm_gpu_split_tmp_bytes (const ACMPlan *plan, uint64_t n_symbols);
+int acm_gpu_split_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols,
+                          const void *delims /* HOST memory, n_delims symbols */, uint32_t n_delims, uint32_t flags,
+                          uint64_t *d_offsets /* capacity + 1, may be NULL: count only */, uint64_t capacity,
+                          uint64_t *d_n_texts, void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_split_host (ACMPlan *plan, const void *text, uint64_t n_symbols, const void *delims, uint32_t n_delims,
+                        uint32_t flags, uint64_t *offsets, uint64_t capacity, uint64_t *n_texts);   /* blocking */
+int acm_gpu_grep_lines_host (ACMPlan *plan, const void *text, uint64_t n_symbols,
+                             const void *delims, uint32_t n_delims, uint32_t split_flags, uint32_t grep_flags,
+                             uint64_t *n_texts, uint64_t *n_kept, uint64_t *total,
+                             void *out, uint64_t out_capacity, uint64_t *out_symbols,
+                             uint64_t texts_capacity, uint64_t *offsets, uint64_t *hits, uint32_t *kept,
+                             uint64_t *out_offsets);   /* blocking */
+int acm_grep_lines (ACMachine *machine, const void *text, uint64_t n_symbols,
+                    const void *delims, uint32_t n_delims, uint32_t split_flags, uint32_t grep_flags,
+                    uint64_t *n_texts, uint64_t *n_kept, uint64_t *total,
+                    void *out, uint64_t out_capacity, uint64_t *out_symbols,
+                    uint64_t texts_capacity, uint64_t *offsets, uint64_t *hits, uint32_t *kept,
+                    uint64_t *out_offsets);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
