@@ -10,6 +10,7 @@ There is no CPU scan path here: the bulk scan raises if the library or a GPU is 
 from .binding import (  # noqa: F401
     ACMError, Machine, Plan, Stream, MultiScan, Comm, FlatTables, RECORD_DTYPE, build_native, lib, library_path,
     select_records, replace_records, replacement_table, Replaced,
+    tokens_records, Tokens, TOKENS_GAP_SYMBOL, TOKENS_GAP_RUN, TOKENS_GAP_DROP,
     grep_gather, Grepped, split_offsets,
     tally_batch_records, TalliedBatch,
 )

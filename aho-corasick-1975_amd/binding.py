@@ -93,6 +93,8 @@ EXPORTS = [
     "acm_gpu_scan_select_tmp_bytes", "acm_gpu_scan_select_device", "acm_gpu_scan_select_host", "acm_select",
     "acm_replace_records", "acm_gpu_replace_tmp_bytes", "acm_gpu_replace_records_device", "acm_gpu_scan_replace_tmp_bytes",
     "acm_gpu_scan_replace_device", "acm_gpu_scan_replace_host", "acm_replace",
+    "acm_tokens_records", "acm_gpu_tokens_tmp_bytes", "acm_gpu_tokens_records_device", "acm_gpu_scan_tokens_tmp_bytes",
+    "acm_gpu_scan_tokens_device", "acm_gpu_scan_tokens_host", "acm_tokenize",
     "acm_grep_gather", "acm_gpu_grep_tmp_bytes", "acm_gpu_grep_device", "acm_gpu_grep_host", "acm_grep",
     "acm_split_offsets", "acm_gpu_split_tmp_bytes", "acm_gpu_split_device", "acm_gpu_split_host", "acm_gpu_grep_lines_host", "acm_grep_lines",
     "acm_tally_batch_records", "acm_gpu_tally_batch_tmp_bytes", "acm_gpu_tally_batch_device", "acm_gpu_tally_batch_host", "acm_tally_batch",
@@ -293,6 +295,20 @@ def lib():
     L.acm_gpu_scan_replace_host.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.acm_replace.restype = i32
     L.acm_replace.argtypes = [vp, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_tokens_records.restype = i32
+    L.acm_tokens_records.argtypes = [vp, u64, u32, u64, vp, u64, vp, u64, vp, u64, u32, u32, vp, vp, vp, u64, C.POINTER(u64), vp]
+    L.acm_gpu_tokens_tmp_bytes.restype = sz
+    L.acm_gpu_tokens_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_tokens_records_device.restype = i32
+    L.acm_gpu_tokens_records_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, u64, u32, u32, vp, vp, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_tokens_tmp_bytes.restype = sz
+    L.acm_gpu_scan_tokens_tmp_bytes.argtypes = [vp, u64, u64, u64]
+    L.acm_gpu_scan_tokens_device.restype = i32
+    L.acm_gpu_scan_tokens_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, u64, vp, vp, u64, u32, u32, vp, vp, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_tokens_host.restype = i32
+    L.acm_gpu_scan_tokens_host.argtypes = [vp, vp, u64, vp, u64, vp, u64, u32, u32, vp, vp, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]
+    L.acm_tokenize.restype = i32
+    L.acm_tokenize.argtypes = [vp, vp, u64, vp, u64, vp, u64, u32, u32, vp, vp, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]
     L.acm_grep_gather.restype = i32
     L.acm_grep_gather.argtypes = [vp, u32, vp, u64, vp, u32, vp, C.POINTER(u64), vp, u64, vp, C.POINTER(u64)]
     L.acm_gpu_grep_tmp_bytes.restype = sz
@@ -411,6 +427,100 @@ def replace_records(text, records, replacements=None, fill=None, pos_base=0, sym
     out = np.zeros(max(int(out_capacity) * sb // t.itemsize, 1), dtype=t.dtype)
     _check(call(out, int(out_capacity)), "acm_replace_records")
     return out[:int(need.value) * sb // t.itemsize]
+
+
+TOKENS_GAP_SYMBOL, TOKENS_GAP_RUN, TOKENS_GAP_DROP = 0, 1, 2
+_TOKEN_MODES = {"symbol": TOKENS_GAP_SYMBOL, "run": TOKENS_GAP_RUN, "drop": TOKENS_GAP_DROP}
+
+
+def _token_mode(mode):
+    return _TOKEN_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+class Tokens:
+    """What the tokenising calls return.  ids (one vocabulary id per token), start (where every token
+    begins, in the records' coordinate), length (its symbols) and first (n_texts + 1 row pointers:
+    tokens [first[t], first[t + 1]) are those of text t; None when the buffer was one text): int32 /
+    int64 / int32 / int64 device tensors with room for token_capacity entries from Plan.tokens_records()
+    and Plan.scan_tokens() -- the first n_tokens count --, uint32 / uint64 / uint32 / uint64 numpy arrays
+    cut to size from the host calls.  n_tokens and count are Python ints (the device calls synchronise to
+    read them): n_tokens > token_capacity is the room the tokens need (ids, start and length are
+    unspecified then, first is valid), count > the record capacity the room the records need (n_tokens
+    is 0 then).  records is the selection (int64 [capacity, 2], device calls only), count its size."""
+
+    def __init__(self, ids, start, length, first, n_tokens, records=None, count=None, token_capacity=None):
+        self.ids, self.start, self.length, self.first, self.n_tokens = ids, start, length, first, n_tokens
+        self.records, self.count, self.token_capacity = records, count, token_capacity
+
+    def padded(self, pad_id):
+        """The ragged rows as one n_texts x max_len int64 tensor on the device the ids are on (numpy
+        arrays go to the current device first), short rows filled with pad_id; built by torch from ids
+        and first."""
+        import torch
+        assert self.first is not None, "padded() is for a batch"
+
+        def tensor(a, dtype):
+            if isinstance(a, torch.Tensor):
+                return a
+            return torch.from_numpy(np.ascontiguousarray(a).view(dtype)).cuda()
+        ids = tensor(self.ids, np.int32)[:self.n_tokens].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        first = tensor(self.first, np.int64).view(torch.int64)
+        lens = first[1:] - first[:-1]
+        n_texts = lens.numel()
+        width = int(lens.max().item()) if n_texts else 0
+        out = torch.full((n_texts, width), int(pad_id), dtype=torch.int64, device=ids.device)
+        if self.n_tokens:
+            row = torch.repeat_interleave(torch.arange(n_texts, device=ids.device), lens)
+            col = torch.arange(self.n_tokens, device=ids.device) - first[row]
+            out[row, col] = ids
+        return out
+
+
+def _tok_of(tok_of):
+    if tok_of is None:
+        return None, 0
+    a = np.ascontiguousarray(tok_of, dtype=np.uint32).reshape(-1)
+    return (a if a.size else np.zeros(1, np.uint32)), int(np.asarray(tok_of).size)
+
+
+def _tokens_host_call(call, what, n_texts, offsets_given, token_capacity):
+    """the two-call pattern of the host entries: count (tok_id NULL), then fill.  call (ids, start,
+    length, capacity, n_tokens, first, n_selected) -> rc"""
+    first = np.zeros(n_texts + 1, np.uint64) if offsets_given else None
+    need, m = C.c_uint64(0), C.c_uint64(0)
+    if token_capacity is None:
+        _check(call(None, None, None, 0, need, first, m), what)
+        token_capacity = int(need.value)
+    cap = int(token_capacity)
+    ids, start, length = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint32)
+    _check(call(ids, start, length, cap, need, first, m), what)
+    k = int(need.value)
+    return Tokens(ids[:k], start[:k], length[:k], first, k, None, int(m.value), cap)
+
+
+def tokens_records(text, records, offsets=None, mode="run", gap_base=0, tok_of=None, pos_base=0, sym_size=None, token_capacity=None):
+    """acm_tokens_records(): the token stream of `text` (an array of symbols; with sym_size, raw bytes
+    of symbols of that size; may be None in "run" and "drop" mode when sym_size and n_symbols =
+    offsets[-1] say enough) under the selection `records` (RECORD_DTYPE, canonical order, no two
+    sharing a symbol), by the sequential pass on the host.  `offsets` (n_texts + 1 entries) makes the
+    buffer a batch.  Returns a Tokens of numpy arrays."""
+    t = np.ascontiguousarray(text)
+    sb = int(sym_size) if sym_size is not None else t.itemsize
+    n_sym = t.size * t.itemsize // sb
+    rec = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
+    off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+    n_texts = off.size - 1 if off is not None else 0
+    table, nk = _tok_of(tok_of)
+    md = _token_mode(mode)
+
+    def call(ids, start, length, cap, need, first, m):
+        m.value = rec.size
+        return lib().acm_tokens_records(t.ctypes.data if t.size else None, n_sym, sb, pos_base, rec.ctypes.data if rec.size else None, rec.size,
+                                        off.ctypes.data if off is not None else None, n_texts, table.ctypes.data if table is not None else None, nk,
+                                        int(gap_base), md, ids.ctypes.data if ids is not None else None,
+                                        start.ctypes.data if start is not None else None, length.ctypes.data if length is not None else None, cap,
+                                        C.byref(need), first.ctypes.data if first is not None else None)
+    return _tokens_host_call(call, "acm_tokens_records", n_texts, off is not None, token_capacity)
 
 
 class Grepped:
@@ -961,6 +1071,40 @@ class Machine:
             _check(rc, "acm_replace")
             return out[:int(need.value) * self.sym_size // t.itemsize], int(m.value)
 
+
+    def tokenize(self, texts_or_text, mode="run", gap_base=0, tok_of=None, token_capacity=None):
+        """acm_tokenize(): the MaxMatch (greedy longest-match) tokens of one text (bytes or an array of
+        symbols) or of a list of texts, each scanned from the root on its own, in ONE call: one token
+        per selected match (id = tok_of[keyword_id], or the keyword id), and for the symbols no keyword
+        covers by `mode` one token each ("symbol": gap_base + the symbol's value, 1- and 2-byte
+        symbols), one token per run ("run": gap_base) or none ("drop").  Returns a Tokens of numpy
+        arrays; `first` holds the row pointers of a list.  The call counts first and then fills."""
+        def symbols(t):
+            if self.sym_size in _SYM_DTYPE:
+                return self._symbols(t)
+            return np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t)
+        dtype = _SYM_DTYPE.get(self.sym_size, np.uint8)
+        off = None
+        if isinstance(texts_or_text, (list, tuple)):
+            parts = [symbols(t).reshape(-1) for t in texts_or_text]
+            off = np.zeros(len(parts) + 1, dtype=np.uint64)
+            if parts:
+                np.cumsum([p.size * p.itemsize // self.sym_size for p in parts], out=off[1:])
+            packed = np.concatenate([p.view(dtype) for p in parts]) if parts else np.zeros(0, dtype)
+        else:
+            packed = symbols(texts_or_text).reshape(-1)
+        n_sym = packed.size * packed.itemsize // self.sym_size
+        n_texts = off.size - 1 if off is not None else 0
+        table, nk = _tok_of(tok_of)
+        md = _token_mode(mode)
+
+        def call(ids, start, length, cap, need, first, m):
+            return self.L.acm_tokenize(self.handle, packed.ctypes.data if packed.size else None, n_sym, off.ctypes.data if off is not None else None,
+                                       n_texts, table.ctypes.data if table is not None else None, nk, int(gap_base), md,
+                                       ids.ctypes.data if ids is not None else None, start.ctypes.data if start is not None else None,
+                                       length.ctypes.data if length is not None else None, cap, C.byref(need),
+                                       first.ctypes.data if first is not None else None, C.byref(m))
+        return _tokens_host_call(call, "acm_tokenize", n_texts, off is not None, token_capacity)
 
     def grep(self, texts, invert=False, gather=True):
         """acm_grep(): `grep -F -f` over a list of texts (bytes or arrays of symbols), each scanned from
@@ -1553,6 +1697,111 @@ class Plan:
                 continue
             _check(rc, "acm_gpu_scan_replace_host")
             return out[:int(need.value) * self.sym_size // t.itemsize], int(m.value)
+
+    def _token_outputs(self, dev, token_capacity, n_texts, count_only):
+        import torch
+        cap = int(token_capacity)
+        if count_only:
+            ids = start = length = None
+        else:
+            ids = torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
+            start = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
+            length = torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
+        first = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev) if n_texts is not None else None
+        return cap, ids, start, length, first
+
+    def tokens_records(self, text, records, n, offsets=None, mode="run", gap_base=0, tok_of=None, pos_base=0, n_symbols=None, token_capacity=None,
+                       count=None, count_only=False):
+        """acm_gpu_tokens_records_device(): the token stream of `text` (a device tensor; may be None in
+        "run" and "drop" mode with n_symbols given) under the selection records[:n] (an int64
+        [capacity, 2] device tensor: canonical order, no two records sharing a symbol).  `offsets` (an
+        int64 device tensor of n_texts + 1 entries) makes the buffer a batch; `count` (a device int64
+        tensor) gives the number of records on the device, n is the room of `records` then.
+        token_capacity: by default n_symbols, which always suffices.  Returns a Tokens of device
+        tensors; synchronises to read n_tokens."""
+        import torch
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
+        n = int(n)
+        dev = records.device
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_texts = None
+        if offsets is not None:
+            assert offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+            n_texts = offsets.numel() - 1
+        table, nk = _tok_of(tok_of)
+        d_of = torch.from_numpy(table.view(np.int32).copy()).to(dev) if table is not None else None
+        cap, ids, start, length, first = self._token_outputs(dev, n_symbols if token_capacity is None else token_capacity, n_texts, count_only)
+        res = torch.zeros(1, dtype=torch.int64, device=dev)
+        tb = lib().acm_gpu_tokens_tmp_bytes(self.h, n, n_symbols)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        _check(lib().acm_gpu_tokens_records_device(self.h, text.data_ptr() if text is not None else None, n_symbols, pos_base, records.data_ptr(), n,
+                                                   count.data_ptr() if count is not None else None,
+                                                   offsets.data_ptr() if offsets is not None else None, n_texts or 0,
+                                                   d_of.data_ptr() if d_of is not None else None, nk, int(gap_base), _token_mode(mode),
+                                                   ids.data_ptr() if ids is not None else None, start.data_ptr() if start is not None else None,
+                                                   length.data_ptr() if length is not None else None, cap, res.data_ptr(),
+                                                   first.data_ptr() if first is not None else None, tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_tokens_records_device")
+        return Tokens(ids, start, length, first, int(res.item()), records, int(count.item()) if count is not None else n, cap)
+
+    def scan_tokens(self, text, offsets=None, mode="run", gap_base=0, tok_of=None, n_symbols=None, pos_base=0, capacity=None, records=None,
+                    token_capacity=None, count_only=False):
+        """acm_gpu_scan_tokens_device(): the ordered scan of a device tensor (with `offsets`, an int64
+        device tensor of n_texts + 1 entries: the batch scan, every text from the root on its own), the
+        leftmost-longest selection of its records and the token passes, queued on the current stream.
+        `capacity` must hold ALL matches of the buffer.  token_capacity: by default n_symbols, which
+        always suffices.  Returns a Tokens of device tensors: count > capacity is a record room that
+        suffices (n_tokens is 0 then); n_tokens > token_capacity is the room the tokens need.
+        Synchronises to read the two."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        dev = text.device
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        if records is None:
+            cap_r = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+            records = torch.empty((max(cap_r, 1), 2), dtype=torch.int64, device=dev)
+        else:
+            cap_r = records.shape[0] if capacity is None else int(capacity)
+        n_texts = None
+        if offsets is not None:
+            assert offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+            n_texts = offsets.numel() - 1
+        table, nk = _tok_of(tok_of)
+        d_of = torch.from_numpy(table.view(np.int32).copy()).to(dev) if table is not None else None
+        cap, ids, start, length, first = self._token_outputs(dev, n_symbols if token_capacity is None else token_capacity, n_texts, count_only)
+        res = torch.zeros(2, dtype=torch.int64, device=dev)
+        tb = lib().acm_gpu_scan_tokens_tmp_bytes(self.h, cap_r, n_symbols, n_texts or 0)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        _check(lib().acm_gpu_scan_tokens_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
+                                                n_texts or 0, records.data_ptr(), cap_r, res.data_ptr(),
+                                                d_of.data_ptr() if d_of is not None else None, nk, int(gap_base), _token_mode(mode),
+                                                ids.data_ptr() if ids is not None else None, start.data_ptr() if start is not None else None,
+                                                length.data_ptr() if length is not None else None, cap, res.data_ptr() + 8,
+                                                first.data_ptr() if first is not None else None, tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_scan_tokens_device")
+        count, n_tokens = (int(x) for x in res.cpu())
+        return Tokens(ids, start, length, first, n_tokens, records, count, cap)
+
+    def scan_tokens_host(self, text, offsets=None, mode="run", gap_base=0, tok_of=None, token_capacity=None):
+        """acm_gpu_scan_tokens_host(): numpy in, a Tokens of numpy arrays out, through the C ABI only (no
+        torch).  No record capacity: the call counts the matches first.  token_capacity None: the call
+        is made twice, count and then fill."""
+        t = np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        n_texts = off.size - 1 if off is not None else 0
+        table, nk = _tok_of(tok_of)
+        md = _token_mode(mode)
+
+        def call(ids, start, length, cap, need, first, m):
+            return lib().acm_gpu_scan_tokens_host(self.h, t.ctypes.data if t.size else None, n_sym, off.ctypes.data if off is not None else None,
+                                                  n_texts, table.ctypes.data if table is not None else None, nk, int(gap_base), md,
+                                                  ids.ctypes.data if ids is not None else None, start.ctypes.data if start is not None else None,
+                                                  length.ctypes.data if length is not None else None, cap, C.byref(need),
+                                                  first.ctypes.data if first is not None else None, C.byref(m))
+        return _tokens_host_call(call, "acm_gpu_scan_tokens_host", n_texts, off is not None, token_capacity)
 
     def stream(self, max_piece_symbols, record_capacity):
         return Stream(self, max_piece_symbols, record_capacity)

@@ -5003,6 +5003,255 @@ acm_gpu_scan_replace_host (ACMPlan *plan, const void *text, uint64_t n_symbols, 
   return ACM_GPU_OK;
 }
 
+/* ------------------------------------------------------------------ tokenising (include/acm_gpu.h, dev_tokens.h)
+ * The passes behind a selection: validate, count the token starts per tile of the text, the prefix
+ * over the tiles, the tokens themselves. */
+namespace {
+/* ACM_GPU_TOKENS_TILE=<symbols>: the tile of the passes, a multiple of 64 (tests; read at every call) */
+uint32_t
+tokens_tile (void) {
+  const int t = env_int ("ACM_GPU_TOKENS_TILE", (int)TOKENS_TILE_DEFAULT);
+  return t >= (int)TOKENS_TILE_MIN && t <= (int)TOKENS_TILE_MAX && t % 64 == 0 ? (uint32_t)t : TOKENS_TILE_DEFAULT;
+}
+
+struct TokensLayout {
+  uint32_t tile = 0;
+  uint64_t n_tiles = 0;
+  size_t o_ctl = 0, o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, total = 0;
+};
+TokensLayout
+tokens_layout (uint64_t n_symbols) {
+  TokensLayout L;
+  L.tile = tokens_tile ();
+  L.n_tiles = (n_symbols + L.tile - 1) / L.tile;
+  if (L.n_tiles + 1 >= (1ull << 31)) /* (the prefix sum counts its entries in an int: no layout) */
+    return L;
+  L.cub_bytes = exclusive_sum_bytes64 (L.n_tiles + 1);
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (TokensCtl));
+  L.o_count = blob_reserve (cur, (L.n_tiles + 1) * 8);
+  L.o_begin = blob_reserve (cur, (L.n_tiles + 1) * 8);
+  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
+  L.total = cur + 256;
+  return L;
+}
+
+/* a table keyword -> vocabulary id has an entry for every keyword the plan can report */
+bool
+tokens_table_covers (const ACMPlan *plan, const uint32_t *tok_of, uint64_t n_keywords) {
+  return !tok_of || n_keywords >= plan->covered_keywords;
+}
+
+/* what every entry checks of the mode: SYMBOL reads the text as numbers of 1 or 2 bytes */
+bool
+tokens_mode_ok (uint32_t sym_bytes, uint32_t gap_base, uint32_t mode) {
+  if (mode > ACM_TOKENS_GAP_DROP)
+    return false;
+  return mode != ACM_TOKENS_GAP_SYMBOL || (sym_bytes <= 2 && (uint64_t)gap_base <= (1ull << 32) - (1ull << (8 * sym_bytes)));
+}
+
+/* the passes, with the layout of their scratch (made once per call) */
+int
+tokens_records (ACMPlan *plan, const TokensLayout &L, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const ACMRecord *d_sel, uint64_t n,
+                const uint64_t *d_n, const uint64_t *d_offsets, uint64_t n_texts, const uint32_t *d_tok_of, uint64_t n_keywords, uint32_t gap_base,
+                uint32_t mode, uint32_t *d_tok_id, uint64_t *d_tok_start, uint32_t *d_tok_len, uint64_t token_capacity, uint64_t *d_n_tokens,
+                uint64_t *d_tok_first, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_n_tokens || !d_tmp || n >= (1ull << 31) || (n && !d_sel) || (!d_offsets && d_tok_first) || (d_offsets && n_texts >= (1ull << 31)) ||
+      n_keywords >= (1ull << 32) || n_symbols >= (1ull << 56))
+    return ACM_GPU_E_ARG;
+  const uint32_t sb = plan->text_sym_bytes;
+  if (!tokens_mode_ok (sb, gap_base, mode))
+    return ACM_GPU_E_ARG;
+  if (mode == ACM_TOKENS_GAP_SYMBOL && ((n_symbols && !d_text) || reinterpret_cast<uintptr_t> (d_text) % sb))
+    return ACM_GPU_E_ARG;
+  if (L.total == 0 || tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  TokensK K{};
+  K.sel = d_sel;
+  K.capacity = n;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.text = static_cast<const unsigned char *> (d_text);
+  K.n_symbols = n_symbols;
+  K.pos_base = pos_base;
+  K.sb = sb;
+  K.mode = mode;
+  K.gap_base = gap_base;
+  K.tile = L.tile;
+  K.offsets = reinterpret_cast<const unsigned long long *> (d_offsets);
+  K.n_texts = d_offsets ? n_texts : 0;
+  K.tok_of = d_tok_of;
+  K.n_keywords = n_keywords;
+  K.tile_count = reinterpret_cast<long long *> (t + L.o_count);
+  K.tile_begin = reinterpret_cast<const long long *> (t + L.o_begin);
+  K.n_tiles = L.n_tiles;
+  K.tok_id = d_tok_id;
+  K.tok_start = reinterpret_cast<unsigned long long *> (d_tok_start);
+  K.tok_len = d_tok_len;
+  K.token_capacity = d_tok_id ? token_capacity : 0;
+  K.d_n_tokens = reinterpret_cast<unsigned long long *> (d_n_tokens);
+  K.tok_first = reinterpret_cast<unsigned long long *> (d_tok_first);
+  K.ctl = reinterpret_cast<TokensCtl *> (t + L.o_ctl);
+  K.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (TokensCtl), st));
+  /* a. the grid by the rooms the caller names */
+  const uint64_t check_blocks = std::max ((n + TOKENS_THREADS - 1) / TOKENS_THREADS, d_offsets ? (n_texts + TOKENS_THREADS) / TOKENS_THREADS : (uint64_t)0);
+  hipLaunchKernelGGL (tokens_check_kernel, capped_grid (plan, check_blocks), dim3 (TOKENS_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  /* b. c. d. the grid by the tiles of the text */
+  hipLaunchKernelGGL (tokens_tile_kernel<false>, capped_grid (plan, L.n_tiles + 1), dim3 (TOKENS_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  size_t cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.tile_count, reinterpret_cast<long long *> (t + L.o_begin), (int)(L.n_tiles + 1), st));
+  hipLaunchKernelGGL (tokens_tile_kernel<true>, capped_grid (plan, std::max (L.n_tiles, d_offsets ? (n_texts + TOKENS_THREADS) / TOKENS_THREADS / 64 : (uint64_t)0)),
+                      dim3 (TOKENS_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_tokens_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_symbols) {
+  if (!plan || n_or_capacity >= (1ull << 31))
+    return 0;
+  return tokens_layout (n_symbols).total; /* (the passes keep nothing per record) */
+}
+
+extern "C" int
+acm_gpu_tokens_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const ACMRecord *d_sel, uint64_t n,
+                               const uint64_t *d_n, const uint64_t *d_offsets, uint64_t n_texts, const uint32_t *d_tok_of, uint64_t n_keywords,
+                               uint32_t gap_base, uint32_t mode, uint32_t *d_tok_id, uint64_t *d_tok_start, uint32_t *d_tok_len,
+                               uint64_t token_capacity, uint64_t *d_n_tokens, uint64_t *d_tok_first, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || n_symbols >= (1ull << 56))
+    return ACM_GPU_E_ARG;
+  return tokens_records (plan, tokens_layout (n_symbols), d_text, n_symbols, pos_base, d_sel, n, d_n, d_offsets, n_texts, d_tok_of, n_keywords, gap_base,
+                         mode, d_tok_id, d_tok_start, d_tok_len, token_capacity, d_n_tokens, d_tok_first, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" size_t
+acm_gpu_scan_tokens_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!plan || capacity >= (1ull << 31))
+    return 0;
+  /* (one room for both forms of the call: the scans and the selection have ended when the token passes begin) */
+  const size_t scans = std::max (acm_gpu_scan_select_tmp_bytes (plan, capacity, n_symbols),
+                                 std::max (acm_gpu_scan_batch_tmp_bytes (plan, capacity, n_symbols, n_texts), acm_gpu_select_tmp_bytes (plan, capacity, n_symbols)));
+  return std::max (scans, acm_gpu_tokens_tmp_bytes (plan, capacity, n_symbols));
+}
+
+extern "C" int
+acm_gpu_scan_tokens_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts,
+                            ACMRecord *d_records, uint64_t capacity, uint64_t *d_count, const uint32_t *d_tok_of, uint64_t n_keywords, uint32_t gap_base,
+                            uint32_t mode, uint32_t *d_tok_id, uint64_t *d_tok_start, uint32_t *d_tok_len, uint64_t token_capacity,
+                            uint64_t *d_n_tokens, uint64_t *d_tok_first, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || !d_n_tokens || !d_tmp || capacity >= (1ull << 31) || n_symbols >= (1ull << 56) || (n_symbols && !d_text) ||
+      (capacity && !d_records) || (!d_offsets && d_tok_first) || (d_offsets && (pos_base || n_texts >= (1ull << 31))) ||
+      !tokens_mode_ok (plan->text_sym_bytes, gap_base, mode) || !tokens_table_covers (plan, d_tok_of, n_keywords))
+    return ACM_GPU_E_ARG;
+  const TokensLayout L = tokens_layout (n_symbols);
+  if (tmp_bytes < acm_gpu_scan_tokens_tmp_bytes (plan, capacity, n_symbols, n_texts))
+    return ACM_GPU_E_ARG;
+  int rc;
+  if (!d_offsets)
+    rc = acm_gpu_scan_select_device (plan, d_text, n_symbols, pos_base, d_records, capacity, d_count, d_tmp, tmp_bytes, stream);
+  else {
+    rc = acm_gpu_scan_batch_device (plan, d_text, n_symbols, d_offsets, n_texts, d_records, nullptr, nullptr, capacity, d_count, d_tmp, tmp_bytes, stream);
+    if (!rc && capacity && n_symbols) /* (no room: *d_count says what the records need; no text: 0) */
+      rc = acm_gpu_select_records_device (plan, d_records, capacity, d_count, 0, n_symbols, d_records, d_count, d_tmp, tmp_bytes, stream);
+  }
+  if (rc)
+    return rc;
+  return tokens_records (plan, L, d_text, n_symbols, pos_base, d_records, capacity, d_count, d_offsets, n_texts, d_tok_of, n_keywords, gap_base, mode,
+                         d_tok_id, d_tok_start, d_tok_len, token_capacity, d_n_tokens, d_tok_first, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_tokens_host (ACMPlan *plan, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const uint32_t *tok_of,
+                          uint64_t n_keywords, uint32_t gap_base, uint32_t mode, uint32_t *tok_id, uint64_t *tok_start, uint32_t *tok_len,
+                          uint64_t token_capacity, uint64_t *n_tokens, uint64_t *tok_first, uint64_t *n_selected) {
+  if (!plan || !n_tokens || (n_symbols && !text) || (!offsets && tok_first) || n_keywords >= (1ull << 32) ||
+      !tokens_mode_ok (plan->text_sym_bytes, gap_base, mode) || !tokens_table_covers (plan, tok_of, n_keywords))
+    return ACM_GPU_E_ARG;
+  if (offsets && (n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts) || offsets[n_texts] != n_symbols))
+    return ACM_GPU_E_ARG;
+  const uint32_t sb = plan->text_sym_bytes;
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * sb;
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_res = nullptr, *d_off = nullptr, *d_first = nullptr, *d_start = nullptr; /* d_res: the count, the tokens */
+  uint32_t *d_of = nullptr, *d_id = nullptr, *d_len = nullptr;
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_res, 16));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  /* the record room is the number of matches of the buffer: the caller gives none and sees no record overflow */
+  uint64_t matches = 0;
+  int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_res, nullptr);
+  if (rc) {
+    (void)hipDeviceSynchronize ();
+    return rc;
+  }
+  HOST_TRY (hipMemcpy (&matches, d_res, 8, hipMemcpyDeviceToHost));
+  if (matches >= (1ull << 31)) /* (acm_gpu_scan_select_device's limit) */
+    return ACM_GPU_E_ARG;
+  if (offsets && matches == 0) /* (the batch scan is given room for a record) */
+    matches = 1;
+  const uint64_t room = tok_id ? token_capacity : 0;
+  const size_t tmp_bytes = acm_gpu_scan_tokens_tmp_bytes (plan, matches, n_symbols, n_texts);
+  HOST_TRY (temps.get (&d_rec, matches * 16));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  if (tok_id) {
+    HOST_TRY (temps.get (&d_id, room * 4));
+    if (tok_start)
+      HOST_TRY (temps.get (&d_start, room * 8));
+    if (tok_len)
+      HOST_TRY (temps.get (&d_len, room * 4));
+  }
+  if (tok_of) {
+    HOST_TRY (temps.get (&d_of, n_keywords * 4));
+    if (n_keywords)
+      HOST_TRY (hipMemcpy (d_of, tok_of, n_keywords * 4, hipMemcpyHostToDevice));
+  }
+  if (offsets) {
+    HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
+    HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+    if (tok_first)
+      HOST_TRY (temps.get (&d_first, (n_texts + 1) * 8));
+  }
+  rc = acm_gpu_scan_tokens_device (plan, d_text, n_symbols, 0, d_off, n_texts, d_rec, matches, d_res, tok_of ? d_of : nullptr, n_keywords, gap_base, mode,
+                                   tok_id ? d_id : nullptr, d_start, d_len, room, d_res + 1, d_first, d_tmp, tmp_bytes, nullptr);
+  if (!rc)
+    rc = acm_gpu_plan_status (plan); /* (waits for the device) */
+  if (rc) {
+    (void)hipDeviceSynchronize ();
+    return rc;
+  }
+  uint64_t res[2] = { 0, 0 };
+  HOST_TRY (hipMemcpy (res, d_res, 16, hipMemcpyDeviceToHost));
+  if (res[0] > matches) /* (the scan found more than the count said: never expected) */
+    return ACM_GPU_E_INTERNAL;
+  *n_tokens = res[1];
+  if (n_selected)
+    *n_selected = res[0];
+  if (tok_first)
+    HOST_TRY (hipMemcpy (tok_first, d_first, (n_texts + 1) * 8, hipMemcpyDeviceToHost));
+  if (!tok_id)
+    return ACM_GPU_OK;
+  if (res[1] > token_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (res[1]) {
+    HOST_TRY (hipMemcpy (tok_id, d_id, (size_t)res[1] * 4, hipMemcpyDeviceToHost));
+    if (tok_start)
+      HOST_TRY (hipMemcpy (tok_start, d_start, (size_t)res[1] * 8, hipMemcpyDeviceToHost));
+    if (tok_len)
+      HOST_TRY (hipMemcpy (tok_len, d_len, (size_t)res[1] * 4, hipMemcpyDeviceToHost));
+  }
+  return ACM_GPU_OK;
+}
+
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
 extern "C" int
 acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint32_t *len_bits, uint32_t *kw_bits) {
@@ -5661,7 +5910,7 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally only a scan that
  * succeeded, acm_select and acm_scan_from also one that found more records than there was room for,
- * acm_replace, acm_grep, acm_grep_lines and acm_tally_batch also one whose output had no room. */
+ * acm_replace, acm_tokenize, acm_grep, acm_grep_lines and acm_tally_batch also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -5687,7 +5936,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The nine calls below run on the same route, the same cached plan, under the same lock. */
+/* The ten calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -5774,6 +6023,57 @@ acm_replace (ACMachine *machine, const void *text, uint64_t n_symbols, const voi
       return rc;
     },
     [&] (ACMPlan *plan) { return acm_gpu_scan_replace_host (plan, text, n_symbols, repl_data, repl_off, n_keywords, out, out_capacity, out_symbols, n_replaced); });
+}
+
+/* tokenising (include/acm_gpu.h) */
+extern "C" int
+acm_tokenize (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const uint32_t *tok_of,
+              uint64_t n_keywords, uint32_t gap_base, uint32_t mode, uint32_t *tok_id, uint64_t *tok_start, uint32_t *tok_len, uint64_t token_capacity,
+              uint64_t *n_tokens, uint64_t *tok_first, uint64_t *n_selected) {
+  if (!machine || !n_tokens || (n_symbols && !text) || (!offsets && tok_first) || mode > ACM_TOKENS_GAP_DROP)
+    return ACM_GPU_E_ARG;
+  if (offsets && (n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts) || offsets[n_texts] != n_symbols))
+    return ACM_GPU_E_ARG;
+  if (tok_of && n_keywords < acm_nb_keywords (machine)) /* the table covers every keyword of the machine, on every path */
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      /* the caller loop from the root at every offset into a record room the call grows itself, the
+       * selection (a batch's records never cross a text: one selection serves all texts), the sequential pass */
+      auto scan = [&] (ACMRecord *records, uint64_t room, uint64_t *found) {
+        return offsets ? acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, said, records, nullptr, nullptr, room, found)
+                       : acm_internal_cpu_scan (machine, text, n_symbols, said, records, room, found);
+      };
+      uint64_t room = std::max<uint64_t> (1024, n_symbols / 64), found = 0;
+      ACMRecord *records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
+      if (!records)
+        return (int)ACM_GPU_E_NOMEM;
+      int rc = scan (records, room, &found);
+      if (rc == ACM_GPU_E_OVERFLOW) {
+        free (records);
+        room = found;
+        records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
+        if (!records)
+          return (int)ACM_GPU_E_NOMEM;
+        rc = scan (records, room, &found);
+        if (rc == ACM_GPU_E_OVERFLOW) /* (keywords inserted between the two scans) */
+          rc = ACM_GPU_E_INTERNAL;
+      }
+      if (!rc) {
+        found = acm_select_records (records, found);
+        if (n_selected)
+          *n_selected = found;
+        rc = acm_tokens_records (text, n_symbols, said, 0, records, found, offsets, n_texts, tok_of, n_keywords, gap_base, mode, tok_id, tok_start,
+                                 tok_len, token_capacity, n_tokens, tok_first);
+      }
+      free (records);
+      return rc;
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_scan_tokens_host (plan, text, n_symbols, offsets, n_texts, tok_of, n_keywords, gap_base, mode, tok_id, tok_start, tok_len,
+                                       token_capacity, n_tokens, tok_first, n_selected);
+    });
 }
 
 /* grep over a batch (include/acm_gpu.h) */

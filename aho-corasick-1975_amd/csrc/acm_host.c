@@ -1123,3 +1123,106 @@ acm_replace_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, u
     memcpy (o + at * sb, t + next * sb, (n_symbols - next) * sb);
   return ACM_GPU_OK;
 }
+
+/* TOKENS of a text under a selection (include/acm_gpu.h): the plain sequential pass.  One walk does
+ * both jobs: with `write` it fills the three token arrays, without it only counts; tok_first[] is
+ * written either way.  The caller has checked the records and the offsets. */
+static uint64_t
+tokens_walk (const unsigned char *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t pos_base, const ACMRecord *records, uint64_t n,
+             const uint64_t *offsets, uint64_t n_texts, const uint32_t *tok_of, uint32_t gap_base, uint32_t mode, int write, uint32_t *tok_id,
+             uint64_t *tok_start, uint32_t *tok_len, uint64_t *tok_first) {
+  uint64_t count = 0, next = 0;
+  uint64_t t = 0; /* the first text whose tok_first is still to come */
+  uint64_t u = 0; /* the first offset behind the gap symbol in hand (RUN) */
+  for (uint64_t j = 0; j <= n; j++) {
+    const uint64_t start = j < n ? records[j].end_pos - pos_base + 1 - records[j].length : n_symbols;
+    uint64_t i = next; /* the gap [next, start) */
+    while (i < start && mode != ACM_TOKENS_GAP_DROP) {
+      uint64_t end = i + 1;
+      if (mode == ACM_TOKENS_GAP_RUN) {
+        end = start;
+        if (offsets) {
+          while (u <= n_texts && offsets[u] <= i)
+            u++;
+          if (u <= n_texts && offsets[u] < end)
+            end = offsets[u];
+        }
+      }
+      while (tok_first && t <= n_texts && offsets[t] <= i)
+        tok_first[t++] = count;
+      if (write) {
+        uint32_t id = gap_base;
+        if (mode == ACM_TOKENS_GAP_SYMBOL)
+          id += sym_bytes == 1 ? text[i] : (uint32_t)text[2 * i] | ((uint32_t)text[2 * i + 1] << 8);
+        tok_id[count] = id;
+        if (tok_start)
+          tok_start[count] = i + pos_base;
+        if (tok_len)
+          tok_len[count] = end - i > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(end - i);
+      }
+      count++;
+      i = end;
+    }
+    if (j == n)
+      break;
+    while (tok_first && t <= n_texts && offsets[t] <= start)
+      tok_first[t++] = count;
+    if (write) {
+      tok_id[count] = tok_of ? tok_of[records[j].keyword_id] : records[j].keyword_id;
+      if (tok_start)
+        tok_start[count] = start + pos_base;
+      if (tok_len)
+        tok_len[count] = records[j].length;
+    }
+    count++;
+    next = start + records[j].length;
+  }
+  while (tok_first && t <= n_texts)
+    tok_first[t++] = count;
+  return count;
+}
+
+int
+acm_tokens_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t pos_base, const ACMRecord *records, uint64_t n,
+                    const uint64_t *offsets, uint64_t n_texts, const uint32_t *tok_of, uint64_t n_keywords, uint32_t gap_base, uint32_t mode,
+                    uint32_t *tok_id, uint64_t *tok_start, uint32_t *tok_len, uint64_t token_capacity, uint64_t *n_tokens, uint64_t *tok_first) {
+  if (!n_tokens || !sym_bytes || (n && !records) || mode > ACM_TOKENS_GAP_DROP || (!offsets && tok_first) || (offsets && n_texts >= (1ull << 31)))
+    return ACM_GPU_E_ARG;
+  if (mode == ACM_TOKENS_GAP_SYMBOL) {
+    if (sym_bytes > 2 || (uint64_t)gap_base > (1ull << 32) - (1ull << (8 * sym_bytes)) || (n_symbols && !text))
+      return ACM_GPU_E_ARG;
+  }
+  if (offsets) {
+    if (offsets[0] != 0 || offsets[n_texts] != n_symbols)
+      return ACM_GPU_E_ARG;
+    for (uint64_t t = 0; t < n_texts; t++)
+      if (offsets[t] > offsets[t + 1])
+        return ACM_GPU_E_ARG;
+  }
+  uint64_t next = 0, u = 0; /* the first symbol no record has taken yet; the first offset behind the record's start */
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+      return ACM_GPU_E_ARG;
+    const uint64_t start = r->end_pos - pos_base + 1 - r->length;
+    if (start < next)
+      return ACM_GPU_E_ARG;
+    next = start + r->length;
+    if (tok_of && r->keyword_id >= n_keywords)
+      return ACM_GPU_E_ARG;
+    if (offsets) { /* a record lies inside one text */
+      while (u <= n_texts && offsets[u] <= start)
+        u++;
+      if (u <= n_texts && offsets[u] < next)
+        return ACM_GPU_E_ARG;
+    }
+  }
+  const unsigned char *t = text;
+  *n_tokens = tokens_walk (t, n_symbols, sym_bytes, pos_base, records, n, offsets, n_texts, tok_of, gap_base, mode, 0, NULL, NULL, NULL, tok_first);
+  if (!tok_id)
+    return ACM_GPU_OK;
+  if (*n_tokens > token_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  (void)tokens_walk (t, n_symbols, sym_bytes, pos_base, records, n, offsets, n_texts, tok_of, gap_base, mode, 1, tok_id, tok_start, tok_len, NULL);
+  return ACM_GPU_OK;
+}

@@ -164,6 +164,7 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_tally.h"
 #include "dev_select.h"
 #include "dev_replace.h"
+#include "dev_tokens.h"
 #include "dev_grep.h"
 #include "dev_tally_batch.h"
 #include "dev_split.h"

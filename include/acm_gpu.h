@@ -652,6 +652,141 @@ int acm_replace (ACMachine *machine, const void *text, uint64_t n_symbols,
                  const void *repl_data, const uint64_t *repl_off, uint64_t n_keywords,
                  void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_replaced);
 
+/* ------------------------------------------------------------------ tokenising against a vocabulary
+ * What a model-side consumer does with the selection: the MaxMatch (greedy longest-match) tokeniser
+ * over the dictionary.  A sequence of token ids that covers the text -- one id per selected match and
+ * something defined for the symbols no keyword covers --, where every token lies, and for a batch a
+ * row pointer per text: a ragged tensor, made where the text is.
+ *
+ * DEFINITION.  Inputs: text[0 .. n_symbols) in the caller's symbols; a selection S exactly as REPLACE
+ * takes it (records in canonical order, no two sharing a symbol, every start s_j = end_pos_j + 1 -
+ * length_j - pos_base and every end e_j = end_pos_j - pos_base in [0, n_symbols)); optionally a batch,
+ * offsets[0 .. n_texts] under the batch contract (offsets[n_texts] = n_symbols, empty texts allowed;
+ * offsets == NULL: the buffer is one text, n_texts is ignored) -- no record crosses a text boundary;
+ * optionally tok_of[0 .. n_keywords), the vocabulary id of every keyword (NULL: the token of keyword
+ * k is k); gap_base; and a mode.
+ * Symbol i is COVERED when some r_j has s_j <= i <= e_j, else UNCOVERED.  The token stream, left to
+ * right, has one token per unit:
+ *     every selected match: id = tok_of[kw_j] (kw_j without a table), start s_j, length length_j;
+ *     ACM_TOKENS_GAP_SYMBOL (0): every uncovered symbol i is a unit of its own, id = gap_base + the
+ *         value of text[i] (byte fallback), start i, length 1.  The value is the little-endian read
+ *         of the CALLER's symbol, bit for bit, never the class-mapped or interned copy a plan keeps
+ *         (acm_replace's rule): under a case-folding comparator an uncovered `U` is gap_base + 'U'.
+ *         Only for symbols of 1 or 2 bytes, with gap_base <= 2^32 - 2^(8 x sym_bytes); anything else
+ *         is ACM_GPU_E_ARG;
+ *     ACM_TOKENS_GAP_RUN (1): every maximal run of uncovered symbols that lies inside ONE text is one
+ *         unit, id = gap_base (the "unknown" id), start = the run's first symbol, length = the run's
+ *         length (a run of 2^32 symbols or more reports 2^32 - 1); a run that meets a text boundary
+ *         is cut there;
+ *     ACM_TOKENS_GAP_DROP (2): uncovered symbols give no token.
+ * Outputs: tok_id[] (uint32_t); tok_start[] (uint64_t, in the records' coordinate: buffer index +
+ * pos_base; optional); tok_len[] (uint32_t; optional); n_tokens; for a batch tok_first[0 .. n_texts]
+ * (uint64_t; optional): tokens [tok_first[t], tok_first[t + 1]) are those of text t, tok_first[0] = 0,
+ * tok_first[n_texts] = n_tokens, an empty text has an empty range.  Starts ascend strictly; in SYMBOL
+ * and RUN mode the tokens tile the buffer: the sum of tok_len is n_symbols.
+ * `ushers` with he=0, she=1, his=2, hers=3 (SELECT gives `she`, symbols 1 to 3), gb = gap_base:
+ *     SYMBOL  ids [gb+'u', 1, gb+'r', gb+'s']  starts [0, 1, 4, 5]  lengths [1, 3, 1, 1]
+ *     RUN     ids [gb, 1, gb]                  starts [0, 1, 4]     lengths [1, 3, 2]
+ *     DROP    ids [1]                          starts [1]           lengths [3]
+ * The same symbols as the batch `us` | `hers` (offsets 0, 2, 6): SELECT keeps `hers`; RUN gives ids
+ * [gb, 3], starts [0, 2], lengths [2, 4], tok_first [0, 1, 2].  `abcd` without a match as the batch
+ * `ab` | `cd`: RUN gives two tokens [gb, gb] at 0 and 2; as one text it gives one.
+ *
+ * acm_tokens_records: the plain sequential pass on the host, no device; any sym_bytes > 0 in RUN and
+ * DROP mode (the text is not read there and may be NULL).  `n` is the number of records.  tok_id,
+ * tok_start, tok_len and tok_first may each be NULL; tok_id == NULL: the call only counts and ignores
+ * token_capacity; tok_first without offsets is ACM_GPU_E_ARG.  ACM_GPU_E_OVERFLOW when token_capacity
+ * is too small: *n_tokens = the count needed, nothing is written to the three token arrays, tok_first
+ * is written all the same.  ACM_GPU_E_ARG for records that are no tiling (REPLACE's rule), a record
+ * that crosses a text boundary, a keyword_id >= n_keywords when tok_of is given, offsets that break
+ * the batch contract, a mode above 2, the SYMBOL-mode limits above and n_texts >= 2^31.
+ *
+ * acm_gpu_tokens_records_device: the same on the device (dev_tokens.h) for ANY selection resident
+ * there.  Arguments in this order: the text (d_text, n_symbols, pos_base), the selection (d_sel,
+ * n_or_capacity below 2^31, d_n: exactly acm_gpu_replace_records_device's), the batch (d_offsets --
+ * NULL: one text, d_tok_first must then be NULL too --, n_texts below 2^31), the vocabulary (d_tok_of
+ * or NULL, n_keywords, gap_base, mode), the outputs (d_tok_id, d_tok_start, d_tok_len, token_capacity,
+ * d_n_tokens: device, 8 bytes; d_tok_first), the scratch and the stream.  The call only queues
+ * launches on `stream`, with no host round trip; the launch geometry goes by n_symbols and the rooms
+ * the caller names, never by a count on the device.  Every output element is written once, by one
+ * lane, with no atomics on outputs.  *d_n_tokens is always the exact count for valid input.
+ * *d_n_tokens > token_capacity: it is the capacity needed, the three token arrays are unspecified,
+ * nothing was written outside [0 .. token_capacity), d_tok_first is complete and valid.  d_tok_id ==
+ * NULL: count only (d_tok_first is still written).  *d_n > n_or_capacity (a scan that overflowed):
+ * *d_n_tokens = 0 and nothing else is written.  In RUN and DROP mode the passes never read the text
+ * and d_text may be NULL; in SYMBOL mode d_text may have any alignment that is a multiple of the
+ * symbol size (the passes read only symbols of the buffer itself).  A contract violation -- a record
+ * out of range, two records that overlap or are out of order, a record that crosses a text boundary,
+ * a keyword_id >= n_keywords with d_tok_of given, offsets that decrease, do not begin with 0 or do not
+ * end with n_symbols -- is handled as replace and grep handle theirs: a validation pass sees every
+ * record, the offsets and the ids before any address is formed from them, acm_gpu_plan_status reports
+ * ACM_GPU_E_INTERNAL, *d_n_tokens = 0, no other output is written and nothing is read or written out
+ * of bounds.  The work is done in tiles of 8,192 symbols (ACM_GPU_TOKENS_TILE=<symbols> in the
+ * environment sets another: a multiple of 64 from 64 to 16,384, read at every call -- by
+ * acm_gpu_tokens_tmp_bytes too, whose answer is 16 bytes per tile: size the scratch under the setting
+ * the call will see).
+ *
+ * acm_gpu_scan_tokens_device: with d_offsets == NULL acm_gpu_scan_select_device, with offsets (pos_base
+ * must be 0 then) acm_gpu_scan_batch_device and acm_gpu_select_records_device over [0, n_symbols) -- a
+ * batch's records never cross a text, so one selection serves all texts --, then the passes above,
+ * all on `stream`; the selected records stay in d_records[0 .. *d_count).  The record capacity rule
+ * is select's and the batch scan's: `capacity` must hold ALL matches of the buffer.  *d_count >
+ * capacity afterwards: it is a capacity that suffices, and *d_n_tokens = 0.  With d_tok_of, n_keywords
+ * must be at least acm_gpu_tally_keywords (plan), else ACM_GPU_E_ARG.  d_tmp (never NULL) must hold
+ * acm_gpu_scan_tokens_tmp_bytes (plan, capacity, n_symbols, n_texts) bytes: the scans' and the
+ * selection's scratch is reused, they have ended when the token passes begin.
+ * acm_gpu_scan_tokens_host: the same from host memory, blocking.  The caller gives NO record capacity:
+ * the call counts the matches first, as acm_gpu_scan_replace_host does.  ACM_GPU_E_OVERFLOW means only
+ * "token_capacity is too small, *n_tokens suffices"; tok_first is valid then.  Offsets are checked on
+ * the host (ACM_GPU_E_ARG).  tok_id == NULL counts: the two-call pattern is count, then fill.
+ * n_selected (may be NULL) receives the number of selected matches.
+ * acm_tokenize: the call on the machine itself, total over machines exactly as acm_replace is (same
+ * three paths, same cached plan and acm_gpu_plan_update, acm_scan_path says which ran -- recorded on
+ * success and on a token overflow): the GPU paths run acm_gpu_scan_tokens_host,
+ * ACM_SCAN_PATH_CPU_LOOP runs the caller loop from the root at every offset into a record room the
+ * call grows itself, then acm_select_records, then acm_tokens_records with the declared symbol size.
+ * A tok_of with n_keywords below the machine's number of keywords is ACM_GPU_E_ARG on every path.  A
+ * missing device stays an error, never a fallback. */
+#define ACM_TOKENS_GAP_SYMBOL 0
+#define ACM_TOKENS_GAP_RUN 1
+#define ACM_TOKENS_GAP_DROP 2
+int acm_tokens_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t pos_base,
+                        const ACMRecord *records, uint64_t n,
+                        const uint64_t *offsets /* NULL: one text */, uint64_t n_texts,
+                        const uint32_t *tok_of /* NULL: the keyword ids */, uint64_t n_keywords,
+                        uint32_t gap_base, uint32_t mode,
+                        uint32_t *tok_id, uint64_t *tok_start, uint32_t *tok_len, uint64_t token_capacity,
+                        uint64_t *n_tokens, uint64_t *tok_first);
+size_t acm_gpu_tokens_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_symbols);
+int acm_gpu_tokens_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                   const ACMRecord *d_sel, uint64_t n_or_capacity,
+                                   const uint64_t *d_n /* device count, may be NULL: n is the count */,
+                                   const uint64_t *d_offsets /* NULL: one text */, uint64_t n_texts,
+                                   const uint32_t *d_tok_of /* NULL: the keyword ids */, uint64_t n_keywords,
+                                   uint32_t gap_base, uint32_t mode,
+                                   uint32_t *d_tok_id, uint64_t *d_tok_start, uint32_t *d_tok_len,
+                                   uint64_t token_capacity, uint64_t *d_n_tokens, uint64_t *d_tok_first,
+                                   void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_scan_tokens_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_tokens_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                const uint64_t *d_offsets /* NULL: one text */, uint64_t n_texts,
+                                ACMRecord *d_records, uint64_t capacity, uint64_t *d_count,
+                                const uint32_t *d_tok_of, uint64_t n_keywords, uint32_t gap_base, uint32_t mode,
+                                uint32_t *d_tok_id, uint64_t *d_tok_start, uint32_t *d_tok_len,
+                                uint64_t token_capacity, uint64_t *d_n_tokens, uint64_t *d_tok_first,
+                                void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_tokens_host (ACMPlan *plan, const void *text, uint64_t n_symbols,
+                              const uint64_t *offsets /* NULL: one text */, uint64_t n_texts,
+                              const uint32_t *tok_of, uint64_t n_keywords, uint32_t gap_base, uint32_t mode,
+                              uint32_t *tok_id, uint64_t *tok_start, uint32_t *tok_len,
+                              uint64_t token_capacity, uint64_t *n_tokens, uint64_t *tok_first,
+                              uint64_t *n_selected);   /* blocking */
+int acm_tokenize (ACMachine *machine, const void *text, uint64_t n_symbols,
+                  const uint64_t *offsets /* NULL: one text */, uint64_t n_texts,
+                  const uint32_t *tok_of, uint64_t n_keywords, uint32_t gap_base, uint32_t mode,
+                  uint32_t *tok_id, uint64_t *tok_start, uint32_t *tok_len,
+                  uint64_t token_capacity, uint64_t *n_tokens, uint64_t *tok_first, uint64_t *n_selected);
+
 /* ------------------------------------------------------------------ grep over a batch
  * The reference's callers mostly hold many small texts -- log lines, packets, cells, the words of
  * examples/aho_corasick_generic_test.c:168-210, which restarts at the root for every word it reads,
