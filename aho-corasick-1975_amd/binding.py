@@ -18,6 +18,9 @@ ACM_GPU_E_OVERFLOW = -4
 ACM_GPU_E_ARG = -5
 ACM_GREP_MATCHING, ACM_GREP_INVERT = 0, 1
 ACM_SPLIT_EVERY, ACM_SPLIT_RUNS = 0, 1
+ACM_WORDS_LEFT, ACM_WORDS_RIGHT, ACM_WORDS_BOTH = 1, 2, 3
+# the usual ASCII word set as inclusive (lo, hi) ranges: 0-9, A-Z, _, a-z (UTF-8 byte text adds (0x80, 0xFF))
+ASCII_WORD = ((0x30, 0x39), (0x41, 0x5A), (0x5F, 0x5F), (0x61, 0x7A))
 
 
 class ACMError(RuntimeError):
@@ -98,6 +101,8 @@ EXPORTS = [
     "acm_grep_gather", "acm_gpu_grep_tmp_bytes", "acm_gpu_grep_device", "acm_gpu_grep_host", "acm_grep",
     "acm_split_offsets", "acm_gpu_split_tmp_bytes", "acm_gpu_split_device", "acm_gpu_split_host", "acm_gpu_grep_lines_host", "acm_grep_lines",
     "acm_tally_batch_records", "acm_gpu_tally_batch_tmp_bytes", "acm_gpu_tally_batch_device", "acm_gpu_tally_batch_host", "acm_tally_batch",
+    "acm_words_records", "acm_gpu_words_tmp_bytes", "acm_gpu_words_records_device", "acm_gpu_scan_words_tmp_bytes", "acm_gpu_scan_words_device",
+    "acm_gpu_scan_words_host", "acm_scan_words",
 ]
 
 
@@ -340,6 +345,20 @@ def lib():
     for fn in (L.acm_gpu_grep_lines_host, L.acm_grep_lines):
         fn.restype = i32
         fn.argtypes = [vp, vp, u64, vp, u32, u32, u32, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, u64, C.POINTER(u64), u64, vp, vp, vp, vp]
+    L.acm_words_records.restype = i32
+    L.acm_words_records.argtypes = [vp, u64, u32, u64, vp, u64, vp, u32, u32, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_words_tmp_bytes.restype = sz
+    L.acm_gpu_words_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_words_records_device.restype = i32
+    L.acm_gpu_words_records_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, u32, u32, vp, u64, vp, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_words_tmp_bytes.restype = sz
+    L.acm_gpu_scan_words_tmp_bytes.argtypes = [vp, u64, u64, u64]
+    L.acm_gpu_scan_words_device.restype = i32
+    L.acm_gpu_scan_words_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, u32, u32, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_words_host.restype = i32
+    L.acm_gpu_scan_words_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, u32, u32, vp, u64, C.POINTER(u64)]
+    L.acm_scan_words.restype = i32
+    L.acm_scan_words.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, C.POINTER(u64)]
     L.acm_gpu_flows_create.restype = i32
     L.acm_gpu_flows_create.argtypes = [vp, u64, C.POINTER(vp)]
     L.acm_gpu_flows_destroy.restype = None
@@ -689,6 +708,38 @@ def split_offsets(text, delims=b"\n", runs=False, sym_size=None):
     _check(lib().acm_split_offsets(t.ctypes.data if t.size else None, n_sym, sb, d.ctypes.data, nd, flags, off.ctypes.data, int(n.value), C.byref(n)),
            "acm_split_offsets")
     return off
+
+
+def _word_ranges(ranges, sym_size):
+    """a word set -- inclusive (lo, hi) pairs of symbol values -- as the contiguous 2 * n_ranges symbols the C calls take"""
+    r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2), dtype=_SYM_DTYPE[sym_size]).reshape(-1)
+    return r, r.size // 2
+
+
+_WORD_FLAGS = {"left": ACM_WORDS_LEFT, "right": ACM_WORDS_RIGHT, "both": ACM_WORDS_BOTH}
+
+
+def _word_flags(flags):
+    return _WORD_FLAGS[flags] if isinstance(flags, str) else int(flags)
+
+
+def words_records(text, records, offsets=None, ranges=ASCII_WORD, flags="both", pos_base=0, sym_size=None):
+    """acm_words_records(): the whole-word records of `records` (RECORD_DTYPE, any order) over `text`
+    (an array of symbols; with sym_size, raw bytes of symbols of that size), by the sequential pass on
+    the host: a record is kept when the symbol in front of it ("left"), behind it ("right") or both
+    ("both": grep -w) is no word symbol or lies outside the record's text.  `ranges` is the word set,
+    inclusive (lo, hi) pairs; `offsets` (n_texts + 1 entries) cuts the buffer into texts.  Returns a
+    new array in the order of the input; `records` is not changed."""
+    t = np.ascontiguousarray(text)
+    sb = int(sym_size) if sym_size is not None else t.itemsize
+    r, nr = _word_ranges(ranges, sb)
+    a = np.array(records, dtype=RECORD_DTYPE, copy=True).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+    n = C.c_uint64(0)
+    _check(lib().acm_words_records(t.ctypes.data if t.size else None, t.size * t.itemsize // sb, sb, int(pos_base),
+                                   off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, r.ctypes.data, nr,
+                                   _word_flags(flags), a.ctypes.data if a.size else None, a.size, C.byref(n)), "acm_words_records")
+    return a[:n.value]
 
 
 def _grep_lines_host_call(fn, what, handle, t, sym_size, d, nd, runs, invert, gather):
@@ -1048,6 +1099,24 @@ class Machine:
             _check(rc, "acm_select")
             return out[:n.value]
 
+
+    def scan_words(self, text, ranges=ASCII_WORD, flags="both", capacity=None):
+        """acm_scan_words(): the whole-word matches of `text` in canonical order (see words_records).
+        `capacity` must hold ALL matches (they are found first); by default an overflow is repeated
+        once with the size the call reports."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        r, nr = _word_ranges(ranges, self.sym_size)
+        cap = int(capacity) if capacity is not None else max(1024, t.size // 64)
+        for attempt in (0, 1):
+            out = np.zeros(cap, dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            rc = self.L.acm_scan_words(self.handle, t.ctypes.data, t.size * t.itemsize // self.sym_size, r.ctypes.data, nr, _word_flags(flags),
+                                       out.ctypes.data, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_scan_words")
+            return out[:n.value]
 
     def replace(self, text, replacements=None, fill=None, out_capacity=None):
         """acm_replace(): `text` with its leftmost-longest non-overlapping matches (select()) replaced:
@@ -1608,6 +1677,81 @@ class Plan:
                 cap = int(n.value)
                 continue
             _check(rc, "acm_gpu_scan_select_host")
+            return out[:n.value]
+
+    def words_records(self, text, records, n, offsets=None, ranges=ASCII_WORD, flags="both", pos_base=0, n_symbols=None, out=None, count=None,
+                      out_count=None):
+        """acm_gpu_words_records_device(): the whole-word records (see words_records) of records[:n] (an
+        int64 [capacity, 2] device tensor, any order) over `text` (a device tensor), into `out` (None:
+        a new tensor; it must not overlap `records`), queued on the current stream.  `count` (a device
+        int64 tensor) gives the number of records on the device: n is the room of `records` and `out`
+        then.  `offsets` is a device int64 tensor of n_texts + 1 entries.  Returns (out, out_count):
+        out_count (None: a new device tensor; may be `count`) holds the number of kept records, or
+        `count`'s value when that exceeds n.  Nothing is synchronised."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
+        n = int(n)
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        if out is None:
+            out = torch.empty((max(n, 1), 2), dtype=torch.int64, device=records.device)
+        assert out.is_cuda and out.is_contiguous() and out.shape[0] >= n
+        if out_count is None:
+            out_count = torch.zeros(1, dtype=torch.int64, device=records.device)
+        r, nr = _word_ranges(ranges, self.sym_size)
+        n_texts = offsets.numel() - 1 if offsets is not None else 0
+        tb = lib().acm_gpu_words_tmp_bytes(self.h, n, n_texts)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
+        _check(lib().acm_gpu_words_records_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
+                                                  n_texts, r.ctypes.data, nr, _word_flags(flags), records.data_ptr(), n,
+                                                  count.data_ptr() if count is not None else None, out.data_ptr(), out_count.data_ptr(),
+                                                  tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_words_records_device")
+        return out, out_count
+
+    def scan_words(self, text, offsets=None, ranges=ASCII_WORD, flags="both", n_symbols=None, pos_base=0, capacity=None, records=None, count=None,
+                   tmp=None):
+        """acm_gpu_scan_words_device(): the ordered scan of a device tensor and the whole-word filter of
+        its records, queued on the current stream.  Returns (records, count, tmp): records[:count] are
+        the whole-word matches in canonical order when count <= capacity; a greater count is the
+        number of ALL matches, the capacity the call needs."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        if records is None:
+            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+            records = torch.empty((cap, 2), dtype=torch.int64, device=text.device)
+        if count is None:
+            count = torch.zeros(1, dtype=torch.int64, device=text.device)
+        r, nr = _word_ranges(ranges, self.sym_size)
+        n_texts = offsets.numel() - 1 if offsets is not None else 0
+        tb = lib().acm_gpu_scan_words_tmp_bytes(self.h, records.shape[0], n_symbols, n_texts)
+        if tmp is None or tmp.numel() < tb:
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        _check(lib().acm_gpu_scan_words_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
+                                               n_texts, r.ctypes.data, nr, _word_flags(flags), records.data_ptr(), records.shape[0],
+                                               count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_scan_words_device")
+        return records, count, tmp
+
+    def scan_words_host(self, text, offsets=None, ranges=ASCII_WORD, flags="both", pos_base=0, capacity=None):
+        """acm_gpu_scan_words_host(): numpy in, the whole-word records out, through the C ABI only (no
+        torch); an overflow is repeated once with the size the call reports."""
+        t = np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        r, nr = _word_ranges(ranges, self.sym_size)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
+        for attempt in (0, 1):
+            out = np.zeros(cap, dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            rc = lib().acm_gpu_scan_words_host(self.h, t.ctypes.data if t.size else None, n_sym, pos_base, off.ctypes.data if off is not None else None,
+                                               off.size - 1 if off is not None else 0, r.ctypes.data, nr, _word_flags(flags), out.ctypes.data, cap,
+                                               C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_gpu_scan_words_host")
             return out[:n.value]
 
     def _replace_inputs(self, text, n_symbols, replacements, fill, out, out_capacity, most_records):

@@ -5252,6 +5252,218 @@ acm_gpu_scan_tokens_host (ACMPlan *plan, const void *text, uint64_t n_symbols, c
   return ACM_GPU_OK;
 }
 
+/* ------------------------------------------------------------------ whole-word matches (include/acm_gpu.h, dev_words.h)
+ * One stable compaction of a record set under the symbols next to each match: the check of
+ * offsets[], the mark pass, the prefix over the tiles, the write pass. */
+namespace {
+struct WordsLayout {
+  uint32_t tile = 0;
+  uint64_t n_tiles = 0;
+  size_t o_ctl = 0, o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, o_mask = 0, total = 0;
+};
+
+/* ACM_GPU_WORDS_TILE=<records>: the passes' tile, a multiple of 64 (tests; read at every call) */
+uint32_t
+words_tile (void) {
+  const int t = env_int ("ACM_GPU_WORDS_TILE", (int)WORDS_TILE_DEFAULT);
+  return t >= (int)WORDS_TILE_MIN && t <= (int)WORDS_TILE_MAX && t % (int)WAVE == 0 ? (uint32_t)t : WORDS_TILE_DEFAULT;
+}
+
+WordsLayout
+words_layout (uint64_t capacity) {
+  WordsLayout L;
+  L.tile = words_tile ();
+  L.n_tiles = (capacity + L.tile - 1) / L.tile;
+  L.cub_bytes = exclusive_sum_bytes64 (L.n_tiles + 1);
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (WordsCtl));
+  L.o_count = blob_reserve (cur, (L.n_tiles + 1) * 8);
+  L.o_begin = blob_reserve (cur, (L.n_tiles + 1) * 8);
+  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
+  L.o_mask = blob_reserve (cur, ((size_t)capacity + WAVE - 1) / WAVE * 8);
+  L.total = cur + 256;
+  return L;
+}
+
+/* the word set of a call into the kernels' arguments: the caller's symbols as unsigned integers */
+bool
+words_ranges (WordsK &K, uint32_t sb, const void *ranges, uint32_t n_ranges, uint32_t flags) {
+  if (!acm_internal_words_args_ok (sb, ranges, n_ranges, flags))
+    return false;
+  for (uint32_t j = 0; j < n_ranges; j++) {
+    unsigned long long lo = 0, hi = 0;
+    memcpy (&lo, static_cast<const unsigned char *> (ranges) + (size_t)(2 * j) * sb, sb);
+    memcpy (&hi, static_cast<const unsigned char *> (ranges) + (size_t)(2 * j + 1) * sb, sb);
+    K.lo[j] = lo;
+    K.hi[j] = hi;
+  }
+  K.n_ranges = n_ranges;
+  K.flags = flags;
+  return true;
+}
+
+template <int SB>
+void
+words_launch (const ACMPlan *plan, const WordsLayout &L, const WordsK &K, unsigned char *t, hipStream_t st, hipError_t *err) {
+  hipLaunchKernelGGL (words_mark_kernel<SB>, capped_grid (plan, L.n_tiles + 1), dim3 (WORDS_THREADS), 0, st, K);
+  if ((*err = hipGetLastError ()) != hipSuccess)
+    return;
+  size_t cub = L.cub_bytes;
+  *err = hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_count), reinterpret_cast<long long *> (t + L.o_begin),
+                                           (int)(L.n_tiles + 1), st);
+  if (*err != hipSuccess)
+    return;
+  hipLaunchKernelGGL (words_write_kernel, capped_grid (plan, L.n_tiles), dim3 (WORDS_THREADS), 0, st, K);
+  *err = hipGetLastError ();
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_words_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_texts) {
+  (void)n_texts; /* (nothing here is sized by the number of texts: a record's text is a bisection of offsets[]) */
+  if (!plan || n_or_capacity >= (1ull << 31))
+    return 0;
+  return words_layout (n_or_capacity).total;
+}
+
+extern "C" int
+acm_gpu_words_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts,
+                              const void *ranges, uint32_t n_ranges, uint32_t flags, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n,
+                              ACMRecord *d_out, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || n >= (1ull << 31) || n_symbols >= (1ull << 56) || (n_symbols && !d_text) || (n && (!d_records || !d_out || !d_tmp)) ||
+      (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+    return ACM_GPU_E_ARG;
+  const uint32_t sb = plan->text_sym_bytes;
+  WordsK K{};
+  if (!words_ranges (K, sb, ranges, n_ranges, flags) || reinterpret_cast<uintptr_t> (d_text) % sb)
+    return ACM_GPU_E_ARG;
+  if (n) { /* (the output is written while the input is still read) */
+    const uintptr_t a = reinterpret_cast<uintptr_t> (d_records), b = reinterpret_cast<uintptr_t> (d_out);
+    if (a < b + n * sizeof (ACMRecord) && b < a + n * sizeof (ACMRecord))
+      return ACM_GPU_E_ARG;
+  }
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n == 0) { /* no room, no record: a count that came in stays (it says what room the records need) */
+    HIP_TRY (hipSetDevice (plan->device));
+    if (!d_n)
+      HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
+    else if (d_n != d_count)
+      HIP_TRY (hipMemcpyAsync (d_count, d_n, 8, hipMemcpyDeviceToDevice, st));
+    return ACM_GPU_OK;
+  }
+  const WordsLayout L = words_layout (n);
+  if (tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  K.text = static_cast<const unsigned char *> (d_text);
+  K.n_symbols = n_symbols;
+  K.pos_base = pos_base;
+  K.offsets = n_texts ? d_offsets : nullptr; /* (no text: no symbol, every record breaks the contract) */
+  K.n_texts = n_texts;
+  K.in = d_records;
+  K.capacity = n;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.tile = L.tile;
+  K.n_tiles = L.n_tiles;
+  K.mask = reinterpret_cast<unsigned long long *> (t + L.o_mask);
+  K.tile_count = reinterpret_cast<unsigned long long *> (t + L.o_count);
+  K.tile_begin = reinterpret_cast<const unsigned long long *> (t + L.o_begin);
+  K.out = d_out;
+  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
+  K.ctl = reinterpret_cast<WordsCtl *> (t + L.o_ctl);
+  K.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (WordsCtl), st));
+  if (K.offsets) { /* one size, whatever the number of texts */
+    hipLaunchKernelGGL (words_check_kernel, capped_grid (plan, (n_texts + WORDS_THREADS - 1) / WORDS_THREADS), dim3 (WORDS_THREADS), 0, st, K);
+    HIP_TRY (hipGetLastError ());
+  }
+  hipError_t err = hipSuccess;
+  switch (sb) {
+  case 1: words_launch<1> (plan, L, K, t, st, &err); break;
+  case 2: words_launch<2> (plan, L, K, t, st, &err); break;
+  case 4: words_launch<4> (plan, L, K, t, st, &err); break;
+  case 8: words_launch<8> (plan, L, K, t, st, &err); break;
+  default: return ACM_GPU_E_ARG;
+  }
+  HIP_TRY (err);
+  return ACM_GPU_OK;
+}
+
+namespace {
+/* the fused call's scratch: the ordered scan's records, then the room the scan and the filter share
+ * (the scan has ended when the filter begins) */
+struct ScanWordsLayout {
+  size_t o_rec = 0, o_work = 0, work_bytes = 0, total = 0;
+};
+ScanWordsLayout
+scan_words_layout (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  ScanWordsLayout L;
+  L.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_words_tmp_bytes (plan, capacity, n_texts));
+  size_t cur = 0;
+  L.o_rec = blob_reserve (cur, (size_t)(capacity ? capacity : 1) * sizeof (ACMRecord));
+  L.o_work = blob_reserve (cur, L.work_bytes);
+  L.total = cur + 256;
+  return L;
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_scan_words_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!plan || capacity >= (1ull << 31))
+    return 0;
+  return scan_words_layout (plan, capacity, n_symbols, n_texts).total;
+}
+
+extern "C" int
+acm_gpu_scan_words_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts,
+                           const void *ranges, uint32_t n_ranges, uint32_t flags, ACMRecord *d_records, uint64_t capacity, uint64_t *d_count,
+                           void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || capacity >= (1ull << 31) || (n_symbols && !d_text) || (capacity && (!d_records || !d_tmp)) ||
+      !acm_internal_words_args_ok (plan->text_sym_bytes, ranges, n_ranges, flags))
+    return ACM_GPU_E_ARG;
+  const ScanWordsLayout L = scan_words_layout (plan, capacity, n_symbols, n_texts);
+  if (capacity && tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  ACMRecord *found = capacity ? reinterpret_cast<ACMRecord *> (t + L.o_rec) : nullptr;
+  const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, found, capacity, d_count, capacity ? t + L.o_work : nullptr,
+                                              L.work_bytes, stream);
+  if (rc || capacity == 0) /* (no room: *d_count says what the records need) */
+    return rc;
+  return acm_gpu_words_records_device (plan, d_text, n_symbols, pos_base, d_offsets, n_texts, ranges, n_ranges, flags, found, capacity, d_count,
+                                       d_records, d_count, t + L.o_work, L.work_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_words_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                         const void *ranges, uint32_t n_ranges, uint32_t flags, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
+  if (!plan || !n_found || capacity >= (1ull << 31) || (n_symbols && !text) || (capacity && !records) ||
+      !acm_internal_words_args_ok (plan->text_sym_bytes, ranges, n_ranges, flags))
+    return ACM_GPU_E_ARG;
+  if (offsets && (n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts) || offsets[n_texts] != n_symbols))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, tmp_bytes = acm_gpu_scan_words_tmp_bytes (plan, capacity, n_symbols, n_texts);
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_count = nullptr, *d_off = nullptr;
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (temps.get (&d_count, 8));
+  HOST_TRY (temps.get (&d_rec, capacity * 16));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  if (tbytes)
+    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  if (offsets) {
+    HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
+    HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+  }
+  const int rc = acm_gpu_scan_words_device (plan, d_text, n_symbols, pos_base, d_off, n_texts, ranges, n_ranges, flags, d_rec, capacity, d_count, d_tmp,
+                                            tmp_bytes, nullptr);
+  return download_records (rc, d_count, d_rec, records, capacity, n_found);
+}
+
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
 extern "C" int
 acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint32_t *len_bits, uint32_t *kw_bits) {
@@ -5909,7 +6121,7 @@ route_plan (ACMachine *machine, ScanRoute *R) {
 namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally only a scan that
- * succeeded, acm_select and acm_scan_from also one that found more records than there was room for,
+ * succeeded, acm_select, acm_scan_words and acm_scan_from also one that found more records than there was room for,
  * acm_replace, acm_tokenize, acm_grep, acm_grep_lines and acm_tally_batch also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
@@ -5936,7 +6148,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The ten calls below run on the same route, the same cached plan, under the same lock. */
+/* The eleven calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -5983,6 +6195,18 @@ acm_select (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord 
       return rc;
     },
     [&] (ACMPlan *plan) { return acm_gpu_scan_select_host (plan, text, n_symbols, 0, records, capacity, n_found); });
+}
+
+/* whole-word matches of one text (include/acm_gpu.h) */
+extern "C" int
+acm_scan_words (ACMachine *machine, const void *text, uint64_t n_symbols, const void *ranges, uint32_t n_ranges, uint32_t flags, ACMRecord *records,
+                uint64_t capacity, uint64_t *n_found) {
+  if (!machine || !n_found || (n_symbols && !text) || (capacity && !records))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) { return acm_internal_cpu_scan_words (machine, text, n_symbols, said, ranges, n_ranges, flags, records, capacity, n_found); },
+    [&] (ACMPlan *plan) { return acm_gpu_scan_words_host (plan, text, n_symbols, 0, nullptr, 0, ranges, n_ranges, flags, records, capacity, n_found); });
 }
 
 /* search-and-replace (include/acm_gpu.h) */

@@ -1069,6 +1069,96 @@ acm_select_records (ACMRecord *records, uint64_t n) {
   return out;
 }
 
+/* WORDS of a record set (include/acm_gpu.h): the plain sequential pass, in place in the front of the
+ * array.  Symbols are unsigned little-endian integers of sym_bytes bytes.  Everything is checked
+ * first, so that nothing is modified when the call fails. */
+static uint64_t
+words_symbol (const unsigned char *text, uint64_t i, uint32_t sb) {
+  uint64_t v = 0;
+  for (uint32_t k = 0; k < sb; k++)
+    v |= (uint64_t)text[i * sb + k] << (8 * k);
+  return v;
+}
+
+static int
+words_is_word (uint64_t x, const unsigned char *ranges, uint32_t n_ranges, uint32_t sb) {
+  for (uint32_t j = 0; j < n_ranges; j++)
+    if (x >= words_symbol (ranges, 2 * (uint64_t)j, sb) && x <= words_symbol (ranges, 2 * (uint64_t)j + 1, sb))
+      return 1;
+  return 0;
+}
+
+int
+acm_internal_words_args_ok (uint32_t sym_bytes, const void *ranges, uint32_t n_ranges, uint32_t flags) {
+  if ((sym_bytes != 1 && sym_bytes != 2 && sym_bytes != 4 && sym_bytes != 8) || !ranges || n_ranges == 0 || n_ranges > ACM_WORDS_MAX_RANGES ||
+      flags == 0 || flags > ACM_WORDS_BOTH)
+    return 0;
+  for (uint32_t j = 0; j < n_ranges; j++)
+    if (words_symbol (ranges, 2 * (uint64_t)j, sym_bytes) > words_symbol (ranges, 2 * (uint64_t)j + 1, sym_bytes))
+      return 0;
+  return 1;
+}
+
+int
+acm_words_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                   const void *ranges, uint32_t n_ranges, uint32_t flags, ACMRecord *records, uint64_t n, uint64_t *n_kept) {
+  if (!n_kept || (n_symbols && !text) || (n && !records) || !acm_internal_words_args_ok (sym_bytes, ranges, n_ranges, flags))
+    return ACM_GPU_E_ARG;
+  if (offsets) {
+    if (offsets[0] != 0 || offsets[n_texts] != n_symbols)
+      return ACM_GPU_E_ARG;
+    for (uint64_t t = 0; t < n_texts; t++)
+      if (offsets[t] > offsets[t + 1])
+        return ACM_GPU_E_ARG;
+  }
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+      return ACM_GPU_E_ARG;
+  }
+  const unsigned char *t = text;
+  uint64_t kept = 0;
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord r = records[j];
+    const uint64_t e = r.end_pos - pos_base, s = e + 1 - r.length;
+    uint64_t t_lo = 0, t_hi = n_symbols; /* the record's text: [t_lo, t_hi) */
+    if (offsets) {                       /* (n_texts > 0: a record lies in [0, n_symbols) = [0, offsets[n_texts])) */
+      uint64_t lo = 0, hi = n_texts - 1; /* the largest text with offsets[text] <= s */
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (offsets[mid] <= s)
+          lo = mid;
+        else
+          hi = mid - 1;
+      }
+      t_lo = offsets[lo];
+      t_hi = offsets[lo + 1];
+      if (e >= t_hi) /* the match spans a cut: no match of any text */
+        continue;
+    }
+    if ((flags & ACM_WORDS_LEFT) && s > t_lo && words_is_word (words_symbol (t, s - 1, sym_bytes), ranges, n_ranges, sym_bytes))
+      continue;
+    if ((flags & ACM_WORDS_RIGHT) && e + 1 < t_hi && words_is_word (words_symbol (t, e + 1, sym_bytes), ranges, n_ranges, sym_bytes))
+      continue;
+    records[kept++] = r;
+  }
+  *n_kept = kept;
+  return ACM_GPU_OK;
+}
+
+/* acm_scan_words on the host (include/acm_gpu.h): the caller loop, then the sequential pass over
+ * what it found -- what ACM_SCAN_PATH_CPU_LOOP runs.  The arguments are checked before the scan. */
+int
+acm_internal_cpu_scan_words (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *ranges, uint32_t n_ranges,
+                             uint32_t flags, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
+  if (!m || !n_found || !acm_internal_words_args_ok (sym_bytes, ranges, n_ranges, flags))
+    return ACM_GPU_E_ARG;
+  const int rc = acm_internal_cpu_scan (m, text, n_symbols, sym_bytes, records, capacity, n_found);
+  if (rc)
+    return rc;
+  return acm_words_records (text, n_symbols, sym_bytes, 0, NULL, 0, ranges, n_ranges, flags, records, *n_found, n_found);
+}
+
 /* REPLACE of a text under a selection (include/acm_gpu.h): the plain sequential pass.  The records
  * are checked and the output measured first, so that nothing is written when it has no room. */
 int

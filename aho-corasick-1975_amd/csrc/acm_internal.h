@@ -73,6 +73,11 @@ int acm_internal_cpu_grep_lines (ACMachine *m, const void *text, uint64_t n_symb
                                  uint32_t split_flags, uint32_t grep_flags, uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out,
                                  uint64_t out_capacity, uint64_t *out_symbols, uint64_t texts_capacity, uint64_t *offsets, uint64_t *hits,
                                  uint32_t *kept, uint64_t *out_offsets);
+/* WORDS' arguments (include/acm_gpu.h): a symbol size of 1, 2, 4 or 8, 1 .. ACM_WORDS_MAX_RANGES ranges with lo <= hi, flags 1 .. 3 */
+int acm_internal_words_args_ok (uint32_t sym_bytes, const void *ranges, uint32_t n_ranges, uint32_t flags);
+/* acm_scan_words' host path: the caller loop, then acm_words_records over its records (arguments as acm_scan_words') */
+int acm_internal_cpu_scan_words (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *ranges, uint32_t n_ranges,
+                                 uint32_t flags, ACMRecord *records, uint64_t capacity, uint64_t *n_found);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

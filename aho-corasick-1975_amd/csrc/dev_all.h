@@ -168,5 +168,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_grep.h"
 #include "dev_tally_batch.h"
 #include "dev_split.h"
+#include "dev_words.h"
 
 } // namespace

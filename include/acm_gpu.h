@@ -1062,6 +1062,107 @@ int acm_grep_lines (ACMachine *machine, const void *text, uint64_t n_symbols,
                     uint64_t texts_capacity, uint64_t *offsets, uint64_t *hits, uint32_t *kept,
                     uint64_t *out_offsets);
 
+/* ------------------------------------------------------------------ whole-word matches
+ * Every consumer above acts on the raw match set: with {he, she, his, hers} a replacer built on
+ * acm_replace rewrites the "he" inside "the", "other" and "where".  `grep -w` and keyword
+ * extraction exist to prevent that.  WORDS is the record filter that looks at the two symbols next
+ * to a match.  It runs in front of SELECT -- the leftmost-longest tiling is taken among the
+ * whole-word matches -- and has acm_gpu_select_records_device's calling shape, so it composes with
+ * the select, replace and tokens passes with no change to any of them.
+ *
+ * DEFINITION.  The word set is ranges[0 .. 2 * n_ranges) in the caller's symbol size: pair j is the
+ * inclusive range [lo_j, hi_j], symbols compared as unsigned little-endian integers of sym_bytes
+ * bytes; 1 <= n_ranges <= 16 (ACM_WORDS_MAX_RANGES); a pair with lo > hi is ACM_GPU_E_ARG.
+ * is_word (x) holds when x lies in some range.  It is tested on the caller's ORIGINAL symbols, bit
+ * for bit -- never on the class-mapped or interned copy a plan keeps for its scan (acm_replace's
+ * rule): under a case-folding comparator and the range a-z, "A" is no word symbol.  The usual ASCII
+ * set is the four ranges  0-9, A-Z, _, a-z  = { '0','9', 'A','Z', '_','_', 'a','z' }; callers with
+ * UTF-8 byte text add [0x80, 0xFF].
+ * Texts: offsets[0 .. n_texts] follows the batch contract (first 0, last n_symbols, never
+ * decreasing, empty texts allowed); offsets == NULL means that the buffer is one text.
+ * WORDS (R, text, offsets, ranges, flags).  For a record r let s = end_pos + 1 - length - pos_base,
+ * e = end_pos - pos_base and t the text with offsets[t] <= s < offsets[t + 1].  Then
+ *   left_ok (r):  s == offsets[t] or not is_word (text[s - 1]);
+ *   right_ok (r): e + 1 == offsets[t + 1] or not is_word (text[e + 1]);
+ *   ACM_WORDS_LEFT (1) keeps r when left_ok holds (matches that begin a word), ACM_WORDS_RIGHT (2)
+ *   when right_ok holds (matches that end a word), ACM_WORDS_BOTH (3) when both hold: `grep -w`'s
+ *   test.  flags of 0 or above 3 is ACM_GPU_E_ARG.
+ * The match's own symbols are not looked at: a keyword "e.g." or "New York" is whole-word when its
+ * neighbours are no word symbols.  A symbol outside its text never counts, whatever its value: the
+ * one in front of offsets[t], the one behind offsets[t + 1] - 1, anything outside [0, n_symbols);
+ * such a symbol is never loaded.  With offsets given, a record with e >= offsets[t + 1] (a match
+ * that spans a cut) is dropped silently, so WORDS of the ordered scan of the packed buffer equals
+ * WORDS of acm_scan_batch's records.  The output is the kept records in the order of the input
+ * (stable); the input order is arbitrary, so the filter also runs on acm_gpu_scan_device's
+ * unordered records, in front of an order pass that then has less to do.
+ *
+ * acm_words_records: the plain sequential pass on the host, no device, in place in the front of
+ * the array; sym_bytes 1, 2, 4 or 8 (another size is ACM_GPU_E_ARG).  Offsets that break the batch
+ * contract, a record outside [pos_base, pos_base + n_symbols) (its end or its start) or of length
+ * 0: ACM_GPU_E_ARG, nothing modified.
+ *
+ * acm_gpu_words_records_device: the same on the device (dev_words.h), acm_gpu_select_records_device's
+ * shape: d_n NULL -- n_or_capacity is the number of records; d_n given -- *d_n is, and n_or_capacity
+ * the room of d_records and d_out (below 2^31).  *d_n > n_or_capacity (a scan that overflowed):
+ * nothing is kept and *d_count = *d_n.  The call only queues launches on `stream`, with no host
+ * round trip.  The plan is used for its device, its caller symbol size and its grid cap only: class
+ * plans, interned 8-byte plans and plans with a pending delta behave alike.  `ranges` is HOST
+ * memory, 2 * n_ranges symbols; they travel as kernel arguments and may be freed on return.
+ * d_count may be d_n; d_out must not overlap d_records (ACM_GPU_E_ARG).  d_text may have any
+ * alignment that is a multiple of the symbol size (the neighbours are loaded as single naturally
+ * aligned symbols).  Two passes over tiles of 4,096 records (ACM_GPU_WORDS_TILE=<records> in the
+ * environment sets another: a multiple of 64 from 64 to 1 Mi, read at every call) with a prefix sum
+ * over the tiles' counts between them; d_tmp must hold acm_gpu_words_tmp_bytes (plan,
+ * n_or_capacity, n_texts) bytes (0 for a call that would be refused).  A record that breaks the
+ * contract (a position outside [pos_base, pos_base + n_symbols), a start below pos_base, a length
+ * of 0) is dropped, nothing is read or written out of bounds and acm_gpu_plan_status reports
+ * ACM_GPU_E_INTERNAL (select's rule).  d_offsets that break the batch contract are handled as the
+ * batch scan handles them: *d_count = 0, no other output, status ACM_GPU_E_INTERNAL; no address is
+ * formed from an offset before the check has seen it.
+ *
+ * acm_gpu_scan_words_device: the filter applied to acm_gpu_scan_ordered_device's records with
+ * emit_from = 0, in canonical order.  capacity must hold ALL matches (select's rule): *d_count <=
+ * capacity -- the count is exact and the records are complete; *d_count > capacity -- it is the
+ * scan's count and the records are unspecified.
+ * acm_gpu_scan_words_host: the same from host memory, blocking.  ACM_GPU_E_OVERFLOW with *n_found
+ * = a capacity that suffices.  Offsets that break the batch contract are ACM_GPU_E_ARG.
+ * acm_scan_words: the call on the machine itself, for one text, total over machines exactly as
+ * acm_select is (same three paths, same cached plan, acm_scan_path recorded on success and on
+ * overflow): ACM_SCAN_PATH_CPU_LOOP runs the caller loop and then acm_words_records.  Batch callers
+ * filter acm_scan_batch's records with acm_words_records or the device call.  A missing device
+ * stays an error.
+ *
+ * Out of scope: whole-word flags inside acm_grep, acm_tally, acm_tally_batch and acm_tokenize (their
+ * signatures do not change); several GPUs, streams and flows; Unicode property tables beyond 16
+ * ranges. */
+#define ACM_WORDS_LEFT 1
+#define ACM_WORDS_RIGHT 2
+#define ACM_WORDS_BOTH 3
+#define ACM_WORDS_MAX_RANGES 16
+int acm_words_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t pos_base,
+                       const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                       const void *ranges, uint32_t n_ranges, uint32_t flags,
+                       ACMRecord *records, uint64_t n, uint64_t *n_kept);   /* in place, front of the array */
+size_t acm_gpu_words_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_texts);
+int acm_gpu_words_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                  const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                  const void *ranges /* HOST memory, 2 * n_ranges symbols */, uint32_t n_ranges, uint32_t flags,
+                                  const ACMRecord *d_records, uint64_t n_or_capacity, const uint64_t *d_n /* may be NULL */,
+                                  ACMRecord *d_out, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_scan_words_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_words_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                               const uint64_t *d_offsets, uint64_t n_texts,
+                               const void *ranges, uint32_t n_ranges, uint32_t flags,
+                               ACMRecord *d_records, uint64_t capacity, uint64_t *d_count,
+                               void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_words_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base,
+                             const uint64_t *offsets, uint64_t n_texts,
+                             const void *ranges, uint32_t n_ranges, uint32_t flags,
+                             ACMRecord *records, uint64_t capacity, uint64_t *n_found);   /* blocking */
+int acm_scan_words (ACMachine *machine, const void *text, uint64_t n_symbols,
+                    const void *ranges, uint32_t n_ranges, uint32_t flags,
+                    ACMRecord *records, uint64_t capacity, uint64_t *n_found);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
