@@ -3248,6 +3248,72 @@ download_records (int rc, const uint64_t *d_count, const ACMRecord *d_rec, ACMRe
   return download_records (rc, d_count, d_rec, records, capacity, n_found, batch, [] (uint64_t) { return (int)ACM_GPU_OK; });
 }
 
+/* ---- the steps the host conveniences share, one copy of each.
+ * The text of a call on the device, in a block of `temps` */
+hipError_t
+upload_text (DeviceTemps &temps, const ACMPlan *plan, const void *text, uint64_t n_symbols, void **d_text) {
+  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
+  const hipError_t e = temps.get (d_text, tbytes);
+  return e != hipSuccess || !tbytes ? e : hipMemcpy (*d_text, text, tbytes, hipMemcpyHostToDevice);
+}
+
+/* the same for offsets[0 .. n_texts] of a batch */
+hipError_t
+upload_offsets (DeviceTemps &temps, const uint64_t *offsets, uint64_t n_texts, uint64_t **d_off) {
+  const hipError_t e = temps.get (d_off, (n_texts + 1) * 8);
+  return e != hipSuccess ? e : hipMemcpy (*d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice);
+}
+
+/* behind a device call that gave rc: with check_status the plan's error word is read after a call that succeeded (which
+ * waits for the device); after a failure the device is waited for, once, before the caller's buffers go away */
+int
+settle (ACMPlan *plan, int rc, bool check_status) {
+  if (!rc && check_status)
+    rc = acm_gpu_plan_status (plan);
+  if (rc)
+    (void)hipDeviceSynchronize ();
+  return rc;
+}
+
+/* the record room of the calls whose caller gives none and sees no record overflow (replace, tokens): the exact number
+ * of matches, counted first into d_count and brought down in one round trip (below acm_gpu_scan_select_device's limit) */
+int
+count_first (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t *d_count, uint64_t *matches) {
+  if (const int rc = settle (plan, acm_gpu_count_device (plan, d_text, n_symbols, 0, d_count, nullptr), false))
+    return rc;
+  HOST_TRY (hipMemcpy (matches, d_count, 8, hipMemcpyDeviceToHost));
+  return *matches >= (1ull << 31) ? ACM_GPU_E_ARG : ACM_GPU_OK;
+}
+
+/* offsets[0 .. n_texts] of a batch on the host: first 0, non-decreasing (the last is the number of symbols) */
+bool
+batch_offsets_ok (const uint64_t *offsets, uint64_t n_texts) {
+  if (!offsets || offsets[0] != 0)
+    return false;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (offsets[t] > offsets[t + 1])
+      return false;
+  return true;
+}
+
+/* a batch's arguments: fewer than `limit` texts, offsets[] as above, a text where there are symbols */
+bool
+batch_args_ok (const void *text, const uint64_t *offsets, uint64_t n_texts, uint64_t limit) {
+  return n_texts < limit && batch_offsets_ok (offsets, n_texts) && (!offsets[n_texts] || text);
+}
+
+/* where offsets[] may be NULL (one text) and the number of symbols is given beside it: fewer than 2^31 texts, which end there */
+bool
+optional_offsets_ok (const uint64_t *offsets, uint64_t n_texts, uint64_t n_symbols) {
+  return !offsets || (n_texts < (1ull << 31) && batch_offsets_ok (offsets, n_texts) && offsets[n_texts] == n_symbols);
+}
+
+/* SPLIT's delimiters and flags */
+bool
+split_args_ok (const void *delims, uint32_t n_delims, uint32_t flags) {
+  return delims && n_delims != 0 && n_delims <= ACM_SPLIT_MAX_DELIMS && flags <= ACM_SPLIT_RUNS;
+}
+
 /* acm_gpu_scan_host over `prefix` (n_prefix symbols, may be none) followed by `text`: the two are
  * uploaded side by side, so that acm_scan_from need not copy its text on the host */
 int
@@ -3418,24 +3484,12 @@ acm_gpu_scan_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols
 }
 
 namespace {
-/* offsets[0 .. n_texts] of a batch on the host: first 0, non-decreasing (the last is the number of symbols) */
-bool
-batch_offsets_ok (const uint64_t *offsets, uint64_t n_texts) {
-  if (!offsets || offsets[0] != 0)
-    return false;
-  for (uint64_t t = 0; t < n_texts; t++)
-    if (offsets[t] > offsets[t + 1])
-      return false;
-  return true;
-}
-
 /* acm_gpu_scan_batch_host and, with `flows` (and maybe the texts' flow ids), acm_gpu_scan_flows_host
  * behind their argument checks: everything up, the device call, everything down */
 int
 batch_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint64_t n_symbols, const uint64_t *offsets, const uint32_t *flow, uint64_t n_texts,
             ACMRecord *records, uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found) {
   HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
   const size_t tmp_bytes = flows ? acm_gpu_scan_flows_tmp_bytes (plan, flows, capacity, n_symbols, n_texts)
                                  : acm_gpu_scan_batch_tmp_bytes (plan, capacity, n_symbols, n_texts);
   DeviceTemps temps;
@@ -3443,8 +3497,8 @@ batch_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint64_t n_symbols
   uint64_t *d_off = nullptr, *d_count = nullptr, *d_first = nullptr;
   uint32_t *d_flow = nullptr, *d_tid = nullptr;
   ACMRecord *d_rec = nullptr;
-  HOST_TRY (temps.get (&d_text, tbytes));
-  HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
   if (flows)
     HOST_TRY (temps.get (&d_flow, n_texts * 4));
   HOST_TRY (temps.get (&d_count, 8));
@@ -3452,9 +3506,6 @@ batch_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint64_t n_symbols
   HOST_TRY (temps.get (&d_tid, capacity * 4));
   HOST_TRY (temps.get (&d_first, (n_texts + 1) * 8));
   HOST_TRY (temps.get (&d_tmp, tmp_bytes));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
   if (flow && n_texts)
     HOST_TRY (hipMemcpy (d_flow, flow, n_texts * 4, hipMemcpyHostToDevice));
   const int rc = flows ? acm_gpu_scan_flows_device (plan, flows, d_text, n_symbols, d_off, flow ? d_flow : nullptr, n_texts, d_rec, d_tid, d_first, capacity,
@@ -3469,12 +3520,9 @@ batch_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint64_t n_symbols
 extern "C" int
 acm_gpu_scan_batch_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, ACMRecord *records, uint32_t *text_id,
                          uint64_t *first, uint64_t capacity, uint64_t *n_found) {
-  if (!plan || !n_found || n_texts >= (1ull << 32) || capacity >= (1ull << 31) || (capacity && !records) || !batch_offsets_ok (offsets, n_texts))
+  if (!plan || !n_found || capacity >= (1ull << 31) || (capacity && !records) || !batch_args_ok (text, offsets, n_texts, 1ull << 32))
     return ACM_GPU_E_ARG;
-  const uint64_t n_symbols = offsets[n_texts];
-  if (n_symbols && !text)
-    return ACM_GPU_E_ARG;
-  return batch_host (plan, nullptr, text, n_symbols, offsets, nullptr, n_texts, records, text_id, first, capacity, n_found);
+  return batch_host (plan, nullptr, text, offsets[n_texts], offsets, nullptr, n_texts, records, text_id, first, capacity, n_found);
 }
 
 /* ------------------------------------------------------------------ flow scans (include/acm_gpu.h, dev_flows.h)
@@ -3677,8 +3725,8 @@ acm_gpu_scan_flows_device (ACMPlan *plan, ACMFlows *flows, const void *d_text, u
 extern "C" int
 acm_gpu_scan_flows_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint64_t n_symbols, const uint64_t *offsets, const uint32_t *flow,
                          uint64_t n_texts, ACMRecord *records, uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found) {
-  if (!plan || !flows || flows->plan != plan || !n_found || n_texts >= (1ull << 31) || capacity >= (1ull << 31) || (capacity && !records) ||
-      !batch_offsets_ok (offsets, n_texts) || offsets[n_texts] != n_symbols || (n_symbols && !text))
+  if (!plan || !flows || flows->plan != plan || !n_found || capacity >= (1ull << 31) || (capacity && !records) ||
+      !batch_args_ok (text, offsets, n_texts, 1ull << 31) || offsets[n_texts] != n_symbols)
     return ACM_GPU_E_ARG;
   /* the flow ids, checked here as the device checks them: below n_flows, none twice */
   if (!flow && n_texts > flows->n_flows)
@@ -3752,6 +3800,43 @@ tally_max_outputs (const ACMPlan *plan) {
     if (p)
       m += p->mir ? std::min (p->finfo.lmax, p->finfo.n_keywords) : p->finfo.max_outputs;
   return m ? m : 1;
+}
+
+/* the window and the record room of the windowed host calls (tally, grep, tally_batch): windows of
+ * 32 Mi symbols, room for 2 Mi records (32 MiB) -- one match per 16 symbols; the environment can
+ * set another room, in records (tests of the second attempt) */
+struct RecordRoom {
+  uint64_t window, capacity;
+  bool shrunk;
+};
+
+RecordRoom
+tally_room (const ACMPlan *plan, uint64_t n_symbols) {
+  RecordRoom R = { 1ull << 25, 1ull << 21, false };
+  if (const char *e = getenv ("ACM_GPU_TALLY_CAPACITY")) {
+    const long long said = atoll (e);
+    if (said > 0 && (uint64_t)said < (1ull << 31))
+      R.capacity = (uint64_t)said;
+  }
+  /* (a short text cannot have more than n x M records) */
+  const uint64_t m = tally_max_outputs (plan);
+  if (n_symbols < (1ull << 31) / m && n_symbols * m < R.capacity)
+    R.capacity = n_symbols ? n_symbols * m : 1;
+  return R;
+}
+
+/* the second attempt, behind a window that had more records than the room: a window of W symbols
+ * has at most W x M records, so this one cannot overflow.  false: it did all the same (never expected) */
+bool
+tally_room_shrink (const ACMPlan *plan, RecordRoom *R) {
+  if (R->shrunk)
+    return false;
+  R->shrunk = true;
+  const uint64_t m = tally_max_outputs (plan);
+  if (R->capacity / m < 16)
+    R->capacity = 16 * m;
+  R->window = R->capacity / m / 16 * 16;
+  return true;
 }
 } // namespace
 
@@ -3830,46 +3915,29 @@ acm_gpu_tally_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_
   if (!plan || !tally || (n_symbols && !text) || n_keywords < plan->covered_keywords)
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  /* defaults: windows of 32 Mi symbols, room for 2 Mi records (32 MiB) -- one match per 16 symbols;
-   * ACM_GPU_TALLY_CAPACITY=<records> sets another room (tests of the second attempt) */
-  uint64_t window = 1ull << 25, capacity = 1ull << 21;
-  if (const char *e = getenv ("ACM_GPU_TALLY_CAPACITY"))
-    if (atoll (e) > 0 && (uint64_t)atoll (e) < (1ull << 31))
-      capacity = (uint64_t)atoll (e);
-  /* (a short text cannot have more than n x M records) */
-  if (n_symbols < (1ull << 31) / tally_max_outputs (plan) && n_symbols * tally_max_outputs (plan) < capacity)
-    capacity = n_symbols ? n_symbols * tally_max_outputs (plan) : 1;
+  RecordRoom room = tally_room (plan, n_symbols);
   const uint32_t kw = plan->covered_keywords;
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
   DeviceTemps temps;
   void *d_text = nullptr, *d_tmp = nullptr;
   uint64_t *d_tally = nullptr, *d_out = nullptr;
-  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
   HOST_TRY (temps.get (&d_tally, ((size_t)kw + 1) * 8));
   HOST_TRY (temps.get (&d_out, 16)); /* total, need */
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
   HOST_TRY (hipMemset (d_tally, 0, ((size_t)kw + 1) * 8));
   uint64_t out[2] = { 0, 0 };
-  for (int attempt = 0; attempt < 2; attempt++) {
-    const size_t tmp_bytes = acm_gpu_tally_tmp_bytes (plan, window, capacity);
+  for (;;) {
+    const size_t tmp_bytes = acm_gpu_tally_tmp_bytes (plan, room.window, room.capacity);
     HOST_TRY (temps.get (&d_tmp, tmp_bytes));
-    const int rc = acm_gpu_tally_device (plan, d_text, n_symbols, 0, d_tally, kw, window, capacity, d_out, d_out + 1, d_tmp, tmp_bytes, nullptr);
-    if (rc) {
-      (void)hipDeviceSynchronize ();
+    /* (the one windowed call that does not read the plan's error word) */
+    if (const int rc = settle (plan, acm_gpu_tally_device (plan, d_text, n_symbols, 0, d_tally, kw, room.window, room.capacity, d_out, d_out + 1, d_tmp,
+                                                           tmp_bytes, nullptr), false))
       return rc;
-    }
     HOST_TRY (hipMemcpy (out, d_out, 16, hipMemcpyDeviceToHost));
     HOST_TRY (temps.release (d_tmp)); /* (the second attempt's is another size) */
-    if (out[1] <= capacity)
+    if (out[1] <= room.capacity)
       break;
-    if (attempt == 1) /* (W x M records cannot be exceeded: never expected) */
+    if (!tally_room_shrink (plan, &room))
       return ACM_GPU_E_INTERNAL;
-    /* a window of W symbols has at most W x M records: the second attempt cannot overflow */
-    const uint64_t m = tally_max_outputs (plan);
-    if (capacity / m < 16)
-      capacity = 16 * m;
-    window = capacity / m / 16 * 16;
   }
   std::vector<uint64_t> add ((size_t)kw + 1);
   HOST_TRY (hipMemcpy (add.data (), d_tally, (size_t)kw * 8, hipMemcpyDeviceToHost));
@@ -4038,19 +4106,13 @@ acm_gpu_grep_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, cons
 
 namespace {
 /* what acm_gpu_grep_host and acm_gpu_grep_lines_host do once the text and its offsets are on the
- * device (blocks of `temps`, which also owns what this makes): the window and capacity choice, the
- * one repeat, the downloads.  Arguments as acm_gpu_grep_host's, checked by the caller. */
+ * device (blocks of `temps`, which also owns what this makes): tally_room and its one repeat, the
+ * downloads.  Arguments as acm_gpu_grep_host's, checked by the caller. */
 int
 grep_resident (ACMPlan *plan, DeviceTemps &temps, const void *d_text, uint64_t n_symbols, const uint64_t *d_off, uint64_t n_texts, uint32_t flags,
                uint64_t *hits, uint32_t *kept, uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets,
                uint64_t *out_symbols) {
-  /* the window and the record room as acm_gpu_tally_host picks them, ACM_GPU_TALLY_CAPACITY included */
-  uint64_t window = 1ull << 25, capacity = 1ull << 21;
-  if (const char *e = getenv ("ACM_GPU_TALLY_CAPACITY"))
-    if (atoll (e) > 0 && (uint64_t)atoll (e) < (1ull << 31))
-      capacity = (uint64_t)atoll (e);
-  if (n_symbols < (1ull << 31) / tally_max_outputs (plan) && n_symbols * tally_max_outputs (plan) < capacity)
-    capacity = n_symbols ? n_symbols * tally_max_outputs (plan) : 1;
+  RecordRoom room = tally_room (plan, n_symbols);
   const uint32_t sb = plan->text_sym_bytes;
   if (!out)
     out_capacity = 0;
@@ -4064,28 +4126,19 @@ grep_resident (ACMPlan *plan, DeviceTemps &temps, const void *d_text, uint64_t n
   if (out)
     HOST_TRY (temps.get (&d_out, (size_t)out_capacity * sb));
   uint64_t res[4] = { 0, 0, 0, 0 };
-  for (int attempt = 0; attempt < 2; attempt++) {
-    const size_t tmp_bytes = acm_gpu_grep_tmp_bytes (plan, window, capacity, n_symbols, n_texts);
+  for (;;) {
+    const size_t tmp_bytes = acm_gpu_grep_tmp_bytes (plan, room.window, room.capacity, n_symbols, n_texts);
     HOST_TRY (temps.get (&d_tmp, tmp_bytes));
-    int rc = acm_gpu_grep_device (plan, d_text, n_symbols, d_off, n_texts, flags, window, capacity, d_hits, d_kept, d_res, d_res + 1, d_res + 2, d_out,
-                                  out_capacity, d_out_off, out ? d_res + 3 : nullptr, d_tmp, tmp_bytes, nullptr);
-    if (!rc)
-      rc = acm_gpu_plan_status (plan); /* (waits for the device) */
-    if (rc) {
-      (void)hipDeviceSynchronize ();
+    if (const int rc = settle (plan, acm_gpu_grep_device (plan, d_text, n_symbols, d_off, n_texts, flags, room.window, room.capacity, d_hits, d_kept, d_res,
+                                                          d_res + 1, d_res + 2, d_out, out_capacity, d_out_off, out ? d_res + 3 : nullptr, d_tmp, tmp_bytes,
+                                                          nullptr), true))
       return rc;
-    }
     HOST_TRY (hipMemcpy (res, d_res, 32, hipMemcpyDeviceToHost));
     HOST_TRY (temps.release (d_tmp)); /* (the second attempt's is another size) */
-    if (res[2] <= capacity)
+    if (res[2] <= room.capacity)
       break;
-    if (attempt == 1) /* (W x M records cannot be exceeded: never expected) */
+    if (!tally_room_shrink (plan, &room))
       return ACM_GPU_E_INTERNAL;
-    /* a window of W symbols has at most W x M records: the second attempt cannot overflow */
-    const uint64_t m = tally_max_outputs (plan);
-    if (capacity / m < 16)
-      capacity = 16 * m;
-    window = capacity / m / 16 * 16;
   }
   if (res[0] > n_texts)
     return ACM_GPU_E_INTERNAL;
@@ -4115,21 +4168,15 @@ grep_resident (ACMPlan *plan, DeviceTemps &temps, const void *d_text, uint64_t n
 extern "C" int
 acm_gpu_grep_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t flags, uint64_t *hits, uint32_t *kept,
                    uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols) {
-  if (!plan || !n_kept || n_texts >= (1ull << 31) || flags > ACM_GREP_INVERT || !batch_offsets_ok (offsets, n_texts))
+  if (!plan || !n_kept || flags > ACM_GREP_INVERT || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
     return ACM_GPU_E_ARG;
   const uint64_t n_symbols = offsets[n_texts];
-  if (n_symbols && !text)
-    return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
   DeviceTemps temps;
   void *d_text = nullptr;
   uint64_t *d_off = nullptr;
-  HOST_TRY (temps.get (&d_text, tbytes));
-  HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
   return grep_resident (plan, temps, d_text, n_symbols, d_off, n_texts, flags, hits, kept, n_kept, total, out, out_capacity, out_offsets, out_symbols);
 }
 
@@ -4199,7 +4246,7 @@ acm_gpu_split_tmp_bytes (const ACMPlan *plan, uint64_t n_symbols) {
 extern "C" int
 acm_gpu_split_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const void *delims, uint32_t n_delims, uint32_t flags, uint64_t *d_offsets,
                       uint64_t capacity, uint64_t *d_n_texts, void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!plan || !d_n_texts || !delims || n_delims == 0 || n_delims > ACM_SPLIT_MAX_DELIMS || flags > ACM_SPLIT_RUNS || (n_symbols && !d_text) ||
+  if (!plan || !d_n_texts || !split_args_ok (delims, n_delims, flags) || (n_symbols && !d_text) ||
       (d_offsets && capacity >= (1ull << 31)) || !split_size_ok (plan, n_symbols))
     return ACM_GPU_E_ARG;
   const uint32_t sb = plan->text_sym_bytes;
@@ -4267,18 +4314,14 @@ split_count_resident (ACMPlan *plan, DeviceTemps &temps, const void *d_text, uin
 extern "C" int
 acm_gpu_split_host (ACMPlan *plan, const void *text, uint64_t n_symbols, const void *delims, uint32_t n_delims, uint32_t flags, uint64_t *offsets,
                     uint64_t capacity, uint64_t *n_texts) {
-  if (!plan || !n_texts || !delims || n_delims == 0 || n_delims > ACM_SPLIT_MAX_DELIMS || flags > ACM_SPLIT_RUNS || (n_symbols && !text) ||
-      !split_size_ok (plan, n_symbols))
+  if (!plan || !n_texts || !split_args_ok (delims, n_delims, flags) || (n_symbols && !text) || !split_size_ok (plan, n_symbols))
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
   DeviceTemps temps;
   void *d_text = nullptr, *d_tmp = nullptr;
   uint64_t *d_n = nullptr, *d_off = nullptr;
   size_t tmp_bytes = 0;
-  HOST_TRY (temps.get (&d_text, tbytes));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
   int rc = split_count_resident (plan, temps, d_text, n_symbols, delims, n_delims, flags, &d_tmp, &tmp_bytes, &d_n, n_texts);
   if (rc || !offsets)
     return rc;
@@ -4298,18 +4341,15 @@ extern "C" int
 acm_gpu_grep_lines_host (ACMPlan *plan, const void *text, uint64_t n_symbols, const void *delims, uint32_t n_delims, uint32_t split_flags,
                          uint32_t grep_flags, uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity,
                          uint64_t *out_symbols, uint64_t texts_capacity, uint64_t *offsets, uint64_t *hits, uint32_t *kept, uint64_t *out_offsets) {
-  if (!plan || !n_texts || !n_kept || !delims || n_delims == 0 || n_delims > ACM_SPLIT_MAX_DELIMS || split_flags > ACM_SPLIT_RUNS ||
-      grep_flags > ACM_GREP_INVERT || (n_symbols && !text) || !split_size_ok (plan, n_symbols))
+  if (!plan || !n_texts || !n_kept || !split_args_ok (delims, n_delims, split_flags) || grep_flags > ACM_GREP_INVERT || (n_symbols && !text) ||
+      !split_size_ok (plan, n_symbols))
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
   DeviceTemps temps;
   void *d_text = nullptr, *d_tmp = nullptr;
   uint64_t *d_n = nullptr, *d_off = nullptr;
   size_t tmp_bytes = 0;
-  HOST_TRY (temps.get (&d_text, tbytes));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
   int rc = split_count_resident (plan, temps, d_text, n_symbols, delims, n_delims, split_flags, &d_tmp, &tmp_bytes, &d_n, n_texts);
   if (rc)
     return rc;
@@ -4506,66 +4546,45 @@ acm_gpu_tally_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbol
 extern "C" int
 acm_gpu_tally_batch_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint64_t *row_ptr, uint32_t *col, uint64_t *val,
                           uint64_t nnz_capacity, uint64_t *nnz, uint64_t *total) {
-  if (!plan || !row_ptr || !nnz || n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts))
+  if (!plan || !row_ptr || !nnz || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
     return ACM_GPU_E_ARG;
   const uint64_t n_symbols = offsets[n_texts];
-  if (n_symbols && !text)
-    return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  /* the window and the record room as acm_gpu_tally_host picks them, ACM_GPU_TALLY_CAPACITY included;
-   * the pair room: as many as records of a window, no more than the buffer can have */
-  uint64_t window = 1ull << 25, capacity = 1ull << 21;
-  if (const char *e = getenv ("ACM_GPU_TALLY_CAPACITY"))
-    if (atoll (e) > 0 && (uint64_t)atoll (e) < (1ull << 31))
-      capacity = (uint64_t)atoll (e);
-  uint64_t pair_capacity = std::max<uint64_t> (capacity, 1ull << 16);
+  /* the pair room: as many as records of a window, 2^16 at the least, no more than the buffer can have (n x M, to which
+   * tally_room has clipped the record room already: the larger of the two before the clip is the larger behind it) */
+  RecordRoom room = tally_room (plan, n_symbols);
+  uint64_t pair_capacity = std::max<uint64_t> (room.capacity, 1ull << 16);
   const uint64_t most = n_symbols < (1ull << 31) / tally_max_outputs (plan) ? n_symbols * tally_max_outputs (plan) : 1ull << 31;
-  if (most < capacity)
-    capacity = most ? most : 1;
   if (most < pair_capacity)
     pair_capacity = most ? most : 1;
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes;
   DeviceTemps temps;
   void *d_text = nullptr, *d_tmp = nullptr;
   uint64_t *d_off = nullptr, *d_row_ptr = nullptr, *d_val = nullptr, *d_res = nullptr; /* d_res: nnz, total, need, need_pairs */
   uint32_t *d_col = nullptr;
-  HOST_TRY (temps.get (&d_text, tbytes));
-  HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
   HOST_TRY (temps.get (&d_row_ptr, (n_texts + 1) * 8));
   HOST_TRY (temps.get (&d_res, 32));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
   uint64_t res[4] = { 0, 0, 0, 0 };
-  bool again_records = false, again_pairs = false;
+  bool again_pairs = false;
   for (;;) {
-    const size_t tmp_bytes = acm_gpu_tally_batch_tmp_bytes (plan, window, capacity, pair_capacity, n_symbols, n_texts);
+    const size_t tmp_bytes = acm_gpu_tally_batch_tmp_bytes (plan, room.window, room.capacity, pair_capacity, n_symbols, n_texts);
     HOST_TRY (temps.get (&d_tmp, tmp_bytes));
     HOST_TRY (temps.get (&d_col, (size_t)pair_capacity * 4));
     HOST_TRY (temps.get (&d_val, (size_t)pair_capacity * 8));
-    int rc = acm_gpu_tally_batch_device (plan, d_text, n_symbols, d_off, n_texts, window, capacity, pair_capacity, d_row_ptr, d_col, d_val, d_res,
-                                         d_res + 1, d_res + 2, d_res + 3, d_tmp, tmp_bytes, nullptr);
-    if (!rc)
-      rc = acm_gpu_plan_status (plan); /* (waits for the device) */
-    if (rc) {
-      (void)hipDeviceSynchronize ();
+    if (const int rc = settle (plan, acm_gpu_tally_batch_device (plan, d_text, n_symbols, d_off, n_texts, room.window, room.capacity, pair_capacity,
+                                                                 d_row_ptr, d_col, d_val, d_res, d_res + 1, d_res + 2, d_res + 3, d_tmp, tmp_bytes, nullptr),
+                               true))
       return rc;
-    }
     HOST_TRY (hipMemcpy (res, d_res, 32, hipMemcpyDeviceToHost));
-    if (res[2] <= capacity && res[3] <= pair_capacity)
+    if (res[2] <= room.capacity && res[3] <= pair_capacity)
       break;
     HOST_TRY (temps.release (d_tmp)); /* (the next attempt's are other sizes) */
     HOST_TRY (temps.release (d_col));
     HOST_TRY (temps.release (d_val));
-    if (res[2] > capacity) {
-      if (again_records) /* (W x M records cannot be exceeded: never expected) */
+    if (res[2] > room.capacity) {
+      if (!tally_room_shrink (plan, &room))
         return ACM_GPU_E_INTERNAL;
-      again_records = true;
-      /* a window of W symbols has at most W x M records: the second attempt cannot overflow */
-      const uint64_t m = tally_max_outputs (plan);
-      if (capacity / m < 16)
-        capacity = 16 * m;
-      window = capacity / m / 16 * 16;
     } else {
       if (again_pairs) /* (the kept records cannot be exceeded: never expected) */
         return ACM_GPU_E_INTERNAL;
@@ -4766,17 +4785,15 @@ acm_gpu_scan_select_host (ACMPlan *plan, const void *text, uint64_t n_symbols, u
   if (!plan || !n_found || capacity >= (1ull << 31) || (n_symbols && !text) || (capacity && !records))
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, tmp_bytes = acm_gpu_scan_select_tmp_bytes (plan, capacity, n_symbols);
+  const size_t tmp_bytes = acm_gpu_scan_select_tmp_bytes (plan, capacity, n_symbols);
   DeviceTemps temps;
   void *d_text = nullptr, *d_tmp = nullptr;
   uint64_t *d_count = nullptr;
   ACMRecord *d_rec = nullptr;
-  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
   HOST_TRY (temps.get (&d_count, 8));
   HOST_TRY (temps.get (&d_rec, capacity * 16));
   HOST_TRY (temps.get (&d_tmp, tmp_bytes));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
   const int rc = acm_gpu_scan_select_device (plan, d_text, n_symbols, pos_base, d_rec, capacity, d_count, d_tmp, tmp_bytes, nullptr);
   return download_records (rc, d_count, d_rec, records, capacity, n_found);
 }
@@ -4950,26 +4967,18 @@ acm_gpu_scan_replace_host (ACMPlan *plan, const void *text, uint64_t n_symbols, 
       return ACM_GPU_E_ARG;
   }
   HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * sb, obytes = (size_t)out_capacity * sb;
+  const size_t obytes = (size_t)out_capacity * sb;
   const size_t rbytes = (size_t)(repl_off ? repl_off[n_keywords] : 1) * sb;
   DeviceTemps temps;
   void *d_text = nullptr, *d_tmp = nullptr, *d_repl = nullptr, *d_out = nullptr;
   uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the count, the output's symbols */
   ACMRecord *d_rec = nullptr;
-  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
   HOST_TRY (temps.get (&d_res, 16));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  /* the record room is the exact number of matches: the caller gives none and sees no record overflow */
   uint64_t matches = 0;
-  int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_res, nullptr);
-  if (rc) {
-    (void)hipDeviceSynchronize ();
+  int rc = count_first (plan, d_text, n_symbols, d_res, &matches);
+  if (rc)
     return rc;
-  }
-  HOST_TRY (hipMemcpy (&matches, d_res, 8, hipMemcpyDeviceToHost));
-  if (matches >= (1ull << 31)) /* (acm_gpu_scan_select_device's limit) */
-    return ACM_GPU_E_ARG;
   const size_t tmp_bytes = acm_gpu_scan_replace_tmp_bytes (plan, matches, n_symbols);
   HOST_TRY (temps.get (&d_rec, matches * 16));
   HOST_TRY (temps.get (&d_tmp, tmp_bytes));
@@ -4981,14 +4990,10 @@ acm_gpu_scan_replace_host (ACMPlan *plan, const void *text, uint64_t n_symbols, 
     HOST_TRY (temps.get (&d_off, (n_keywords + 1) * 8));
     HOST_TRY (hipMemcpy (d_off, repl_off, (n_keywords + 1) * 8, hipMemcpyHostToDevice));
   }
-  rc = acm_gpu_scan_replace_device (plan, d_text, n_symbols, 0, d_rec, matches, d_res, d_repl, d_off, n_keywords, d_out, out_capacity, d_res + 1,
-                                    nullptr, d_tmp, tmp_bytes, nullptr);
-  if (!rc)
-    rc = acm_gpu_plan_status (plan); /* (waits for the device) */
-  if (rc) {
-    (void)hipDeviceSynchronize ();
+  rc = settle (plan, acm_gpu_scan_replace_device (plan, d_text, n_symbols, 0, d_rec, matches, d_res, d_repl, d_off, n_keywords, d_out, out_capacity,
+                                                  d_res + 1, nullptr, d_tmp, tmp_bytes, nullptr), true);
+  if (rc)
     return rc;
-  }
   uint64_t res[2] = { 0, 0 };
   HOST_TRY (hipMemcpy (res, d_res, 16, hipMemcpyDeviceToHost));
   if (res[0] > matches) /* (the scan found more than the count said: never expected) */
@@ -5171,32 +5176,21 @@ acm_gpu_scan_tokens_host (ACMPlan *plan, const void *text, uint64_t n_symbols, c
                           uint64_t n_keywords, uint32_t gap_base, uint32_t mode, uint32_t *tok_id, uint64_t *tok_start, uint32_t *tok_len,
                           uint64_t token_capacity, uint64_t *n_tokens, uint64_t *tok_first, uint64_t *n_selected) {
   if (!plan || !n_tokens || (n_symbols && !text) || (!offsets && tok_first) || n_keywords >= (1ull << 32) ||
-      !tokens_mode_ok (plan->text_sym_bytes, gap_base, mode) || !tokens_table_covers (plan, tok_of, n_keywords))
+      !tokens_mode_ok (plan->text_sym_bytes, gap_base, mode) || !tokens_table_covers (plan, tok_of, n_keywords) ||
+      !optional_offsets_ok (offsets, n_texts, n_symbols))
     return ACM_GPU_E_ARG;
-  if (offsets && (n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts) || offsets[n_texts] != n_symbols))
-    return ACM_GPU_E_ARG;
-  const uint32_t sb = plan->text_sym_bytes;
   HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * sb;
   DeviceTemps temps;
   void *d_text = nullptr, *d_tmp = nullptr;
   uint64_t *d_res = nullptr, *d_off = nullptr, *d_first = nullptr, *d_start = nullptr; /* d_res: the count, the tokens */
   uint32_t *d_of = nullptr, *d_id = nullptr, *d_len = nullptr;
   ACMRecord *d_rec = nullptr;
-  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
   HOST_TRY (temps.get (&d_res, 16));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  /* the record room is the number of matches of the buffer: the caller gives none and sees no record overflow */
   uint64_t matches = 0;
-  int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_res, nullptr);
-  if (rc) {
-    (void)hipDeviceSynchronize ();
+  int rc = count_first (plan, d_text, n_symbols, d_res, &matches);
+  if (rc)
     return rc;
-  }
-  HOST_TRY (hipMemcpy (&matches, d_res, 8, hipMemcpyDeviceToHost));
-  if (matches >= (1ull << 31)) /* (acm_gpu_scan_select_device's limit) */
-    return ACM_GPU_E_ARG;
   if (offsets && matches == 0) /* (the batch scan is given room for a record) */
     matches = 1;
   const uint64_t room = tok_id ? token_capacity : 0;
@@ -5216,19 +5210,15 @@ acm_gpu_scan_tokens_host (ACMPlan *plan, const void *text, uint64_t n_symbols, c
       HOST_TRY (hipMemcpy (d_of, tok_of, n_keywords * 4, hipMemcpyHostToDevice));
   }
   if (offsets) {
-    HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
-    HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
+    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
     if (tok_first)
       HOST_TRY (temps.get (&d_first, (n_texts + 1) * 8));
   }
-  rc = acm_gpu_scan_tokens_device (plan, d_text, n_symbols, 0, d_off, n_texts, d_rec, matches, d_res, tok_of ? d_of : nullptr, n_keywords, gap_base, mode,
-                                   tok_id ? d_id : nullptr, d_start, d_len, room, d_res + 1, d_first, d_tmp, tmp_bytes, nullptr);
-  if (!rc)
-    rc = acm_gpu_plan_status (plan); /* (waits for the device) */
-  if (rc) {
-    (void)hipDeviceSynchronize ();
+  rc = settle (plan, acm_gpu_scan_tokens_device (plan, d_text, n_symbols, 0, d_off, n_texts, d_rec, matches, d_res, tok_of ? d_of : nullptr, n_keywords,
+                                                 gap_base, mode, tok_id ? d_id : nullptr, d_start, d_len, room, d_res + 1, d_first, d_tmp, tmp_bytes,
+                                                 nullptr), true);
+  if (rc)
     return rc;
-  }
   uint64_t res[2] = { 0, 0 };
   HOST_TRY (hipMemcpy (res, d_res, 16, hipMemcpyDeviceToHost));
   if (res[0] > matches) /* (the scan found more than the count said: never expected) */
@@ -5439,26 +5429,20 @@ extern "C" int
 acm_gpu_scan_words_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
                          const void *ranges, uint32_t n_ranges, uint32_t flags, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!plan || !n_found || capacity >= (1ull << 31) || (n_symbols && !text) || (capacity && !records) ||
-      !acm_internal_words_args_ok (plan->text_sym_bytes, ranges, n_ranges, flags))
-    return ACM_GPU_E_ARG;
-  if (offsets && (n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts) || offsets[n_texts] != n_symbols))
+      !acm_internal_words_args_ok (plan->text_sym_bytes, ranges, n_ranges, flags) || !optional_offsets_ok (offsets, n_texts, n_symbols))
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  const size_t tbytes = (size_t)n_symbols * plan->text_sym_bytes, tmp_bytes = acm_gpu_scan_words_tmp_bytes (plan, capacity, n_symbols, n_texts);
+  const size_t tmp_bytes = acm_gpu_scan_words_tmp_bytes (plan, capacity, n_symbols, n_texts);
   DeviceTemps temps;
   void *d_text = nullptr, *d_tmp = nullptr;
   uint64_t *d_count = nullptr, *d_off = nullptr;
   ACMRecord *d_rec = nullptr;
-  HOST_TRY (temps.get (&d_text, tbytes));
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
   HOST_TRY (temps.get (&d_count, 8));
   HOST_TRY (temps.get (&d_rec, capacity * 16));
   HOST_TRY (temps.get (&d_tmp, tmp_bytes));
-  if (tbytes)
-    HOST_TRY (hipMemcpy (d_text, text, tbytes, hipMemcpyHostToDevice));
-  if (offsets) {
-    HOST_TRY (temps.get (&d_off, (n_texts + 1) * 8));
-    HOST_TRY (hipMemcpy (d_off, offsets, (n_texts + 1) * 8, hipMemcpyHostToDevice));
-  }
+  if (offsets)
+    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
   const int rc = acm_gpu_scan_words_device (plan, d_text, n_symbols, pos_base, d_off, n_texts, ranges, n_ranges, flags, d_rec, capacity, d_count, d_tmp,
                                             tmp_bytes, nullptr);
   return download_records (rc, d_count, d_rec, records, capacity, n_found);
@@ -6162,8 +6146,7 @@ acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *r
 extern "C" int
 acm_scan_batch (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, ACMRecord *records, uint32_t *text_id,
                 uint64_t *first, uint64_t capacity, uint64_t *n_found) {
-  if (!machine || !n_found || n_texts >= (1ull << 32) || (capacity && !records) || !batch_offsets_ok (offsets, n_texts) ||
-      (offsets[n_texts] && !text))
+  if (!machine || !n_found || (capacity && !records) || !batch_args_ok (text, offsets, n_texts, 1ull << 32))
     return ACM_GPU_E_ARG;
   return routed_scan (
     machine, RecordPath::Always,
@@ -6188,12 +6171,7 @@ acm_select (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord 
     return ACM_GPU_E_ARG;
   return routed_scan (
     machine, RecordPath::OnSuccessOrOverflow,
-    [&] (uint32_t said) {
-      const int rc = acm_internal_cpu_scan (machine, text, n_symbols, said, records, capacity, n_found);
-      if (!rc)
-        *n_found = acm_select_records (records, *n_found);
-      return rc;
-    },
+    [&] (uint32_t said) { return acm_internal_cpu_select (machine, text, n_symbols, said, records, capacity, n_found); },
     [&] (ACMPlan *plan) { return acm_gpu_scan_select_host (plan, text, n_symbols, 0, records, capacity, n_found); });
 }
 
@@ -6218,33 +6196,7 @@ acm_replace (ACMachine *machine, const void *text, uint64_t n_symbols, const voi
   return routed_scan (
     machine, RecordPath::OnSuccessOrOverflow,
     [&] (uint32_t said) {
-      /* the caller loop into a record room the call grows itself, the selection, the sequential pass.
-       * The table covers every keyword of the machine, as on the GPU paths. */
-      if (repl_off && n_keywords < acm_nb_keywords (machine))
-        return (int)ACM_GPU_E_ARG;
-      uint64_t room = std::max<uint64_t> (1024, n_symbols / 64), found = 0;
-      ACMRecord *records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
-      if (!records)
-        return (int)ACM_GPU_E_NOMEM;
-      int rc = acm_internal_cpu_scan (machine, text, n_symbols, said, records, room, &found);
-      if (rc == ACM_GPU_E_OVERFLOW) {
-        free (records);
-        room = found;
-        records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
-        if (!records)
-          return (int)ACM_GPU_E_NOMEM;
-        rc = acm_internal_cpu_scan (machine, text, n_symbols, said, records, room, &found);
-        if (rc == ACM_GPU_E_OVERFLOW) /* (keywords inserted between the two scans) */
-          rc = ACM_GPU_E_INTERNAL;
-      }
-      if (!rc) {
-        found = acm_select_records (records, found);
-        if (n_replaced)
-          *n_replaced = found;
-        rc = acm_replace_records (text, n_symbols, said, 0, records, found, repl_data, repl_off, n_keywords, out, out_capacity, out_symbols);
-      }
-      free (records);
-      return rc;
+      return acm_internal_cpu_replace (machine, text, n_symbols, said, repl_data, repl_off, n_keywords, out, out_capacity, out_symbols, n_replaced);
     },
     [&] (ACMPlan *plan) { return acm_gpu_scan_replace_host (plan, text, n_symbols, repl_data, repl_off, n_keywords, out, out_capacity, out_symbols, n_replaced); });
 }
@@ -6254,45 +6206,16 @@ extern "C" int
 acm_tokenize (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const uint32_t *tok_of,
               uint64_t n_keywords, uint32_t gap_base, uint32_t mode, uint32_t *tok_id, uint64_t *tok_start, uint32_t *tok_len, uint64_t token_capacity,
               uint64_t *n_tokens, uint64_t *tok_first, uint64_t *n_selected) {
-  if (!machine || !n_tokens || (n_symbols && !text) || (!offsets && tok_first) || mode > ACM_TOKENS_GAP_DROP)
-    return ACM_GPU_E_ARG;
-  if (offsets && (n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts) || offsets[n_texts] != n_symbols))
+  if (!machine || !n_tokens || (n_symbols && !text) || (!offsets && tok_first) || mode > ACM_TOKENS_GAP_DROP ||
+      !optional_offsets_ok (offsets, n_texts, n_symbols))
     return ACM_GPU_E_ARG;
   if (tok_of && n_keywords < acm_nb_keywords (machine)) /* the table covers every keyword of the machine, on every path */
     return ACM_GPU_E_ARG;
   return routed_scan (
     machine, RecordPath::OnSuccessOrOverflow,
     [&] (uint32_t said) {
-      /* the caller loop from the root at every offset into a record room the call grows itself, the
-       * selection (a batch's records never cross a text: one selection serves all texts), the sequential pass */
-      auto scan = [&] (ACMRecord *records, uint64_t room, uint64_t *found) {
-        return offsets ? acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, said, records, nullptr, nullptr, room, found)
-                       : acm_internal_cpu_scan (machine, text, n_symbols, said, records, room, found);
-      };
-      uint64_t room = std::max<uint64_t> (1024, n_symbols / 64), found = 0;
-      ACMRecord *records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
-      if (!records)
-        return (int)ACM_GPU_E_NOMEM;
-      int rc = scan (records, room, &found);
-      if (rc == ACM_GPU_E_OVERFLOW) {
-        free (records);
-        room = found;
-        records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
-        if (!records)
-          return (int)ACM_GPU_E_NOMEM;
-        rc = scan (records, room, &found);
-        if (rc == ACM_GPU_E_OVERFLOW) /* (keywords inserted between the two scans) */
-          rc = ACM_GPU_E_INTERNAL;
-      }
-      if (!rc) {
-        found = acm_select_records (records, found);
-        if (n_selected)
-          *n_selected = found;
-        rc = acm_tokens_records (text, n_symbols, said, 0, records, found, offsets, n_texts, tok_of, n_keywords, gap_base, mode, tok_id, tok_start,
-                                 tok_len, token_capacity, n_tokens, tok_first);
-      }
-      free (records);
-      return rc;
+      return acm_internal_cpu_tokenize (machine, text, n_symbols, said, offsets, n_texts, tok_of, n_keywords, gap_base, mode, tok_id, tok_start, tok_len,
+                                        token_capacity, n_tokens, tok_first, n_selected);
     },
     [&] (ACMPlan *plan) {
       return acm_gpu_scan_tokens_host (plan, text, n_symbols, offsets, n_texts, tok_of, n_keywords, gap_base, mode, tok_id, tok_start, tok_len,
@@ -6304,28 +6227,12 @@ acm_tokenize (ACMachine *machine, const void *text, uint64_t n_symbols, const ui
 extern "C" int
 acm_grep (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t flags, uint64_t *hits, uint32_t *kept,
           uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets, uint64_t *out_symbols) {
-  if (!machine || !n_kept || n_texts >= (1ull << 31) || flags > ACM_GREP_INVERT || !batch_offsets_ok (offsets, n_texts) ||
-      (offsets[n_texts] && !text))
+  if (!machine || !n_kept || flags > ACM_GREP_INVERT || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
     return ACM_GPU_E_ARG;
   return routed_scan (
     machine, RecordPath::OnSuccessOrOverflow,
     [&] (uint32_t said) {
-      /* the caller loop from the root at every offset, counting; then the sequential gather */
-      std::vector<uint64_t> own;
-      uint64_t *h = hits;
-      if (!h) {
-        own.resize (n_texts + 1);
-        h = own.data ();
-      }
-      int rc = acm_internal_cpu_grep_hits (machine, text, offsets, n_texts, said, h);
-      if (rc)
-        return rc;
-      if (total) {
-        *total = 0;
-        for (uint64_t t = 0; t < n_texts; t++)
-          *total += h[t];
-      }
-      return acm_grep_gather (text, said, offsets, n_texts, h, flags, kept, n_kept, out, out ? out_capacity : 0, out_offsets, out_symbols);
+      return acm_internal_cpu_grep (machine, text, offsets, n_texts, said, flags, hits, kept, n_kept, total, out, out_capacity, out_offsets, out_symbols);
     },
     [&] (ACMPlan *plan) {
       return acm_gpu_grep_host (plan, text, offsets, n_texts, flags, hits, kept, n_kept, total, out, out_capacity, out_offsets, out_symbols);
@@ -6337,8 +6244,7 @@ extern "C" int
 acm_grep_lines (ACMachine *machine, const void *text, uint64_t n_symbols, const void *delims, uint32_t n_delims, uint32_t split_flags, uint32_t grep_flags,
                 uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t texts_capacity,
                 uint64_t *offsets, uint64_t *hits, uint32_t *kept, uint64_t *out_offsets) {
-  if (!machine || !n_texts || !n_kept || !delims || n_delims == 0 || n_delims > ACM_SPLIT_MAX_DELIMS || split_flags > ACM_SPLIT_RUNS ||
-      grep_flags > ACM_GREP_INVERT || (n_symbols && !text))
+  if (!machine || !n_texts || !n_kept || !split_args_ok (delims, n_delims, split_flags) || grep_flags > ACM_GREP_INVERT || (n_symbols && !text))
     return ACM_GPU_E_ARG;
   return routed_scan (
     machine, RecordPath::OnSuccessOrOverflow,
@@ -6356,37 +6262,11 @@ acm_grep_lines (ACMachine *machine, const void *text, uint64_t n_symbols, const 
 extern "C" int
 acm_tally_batch (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, uint64_t *row_ptr, uint32_t *col, uint64_t *val,
                  uint64_t nnz_capacity, uint64_t *nnz, uint64_t *total) {
-  if (!machine || !row_ptr || !nnz || n_texts >= (1ull << 31) || !batch_offsets_ok (offsets, n_texts) || (offsets[n_texts] && !text))
+  if (!machine || !row_ptr || !nnz || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
     return ACM_GPU_E_ARG;
   return routed_scan (
     machine, RecordPath::OnSuccessOrOverflow,
-    [&] (uint32_t said) {
-      /* the caller loop from the root at every offset into a record room the call grows itself, then the sequential pass */
-      const uint64_t n_symbols = offsets[n_texts];
-      uint64_t room = std::max<uint64_t> (1024, n_symbols / 64), found = 0;
-      std::vector<uint64_t> first (n_texts + 1);
-      ACMRecord *records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
-      if (!records)
-        return (int)ACM_GPU_E_NOMEM;
-      int rc = acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, said, records, nullptr, first.data (), room, &found);
-      if (rc == ACM_GPU_E_OVERFLOW) {
-        free (records);
-        room = found;
-        records = static_cast<ACMRecord *> (malloc (room * sizeof (ACMRecord)));
-        if (!records)
-          return (int)ACM_GPU_E_NOMEM;
-        rc = acm_internal_cpu_scan_batch (machine, text, offsets, n_texts, said, records, nullptr, first.data (), room, &found);
-        if (rc == ACM_GPU_E_OVERFLOW) /* (keywords inserted between the two scans) */
-          rc = ACM_GPU_E_INTERNAL;
-      }
-      if (!rc) {
-        if (total)
-          *total = found;
-        rc = acm_tally_batch_records (records, first.data (), n_texts, acm_nb_keywords (machine), row_ptr, col, val, nnz_capacity, nnz);
-      }
-      free (records);
-      return rc;
-    },
+    [&] (uint32_t said) { return acm_internal_cpu_tally_batch (machine, text, offsets, n_texts, said, row_ptr, col, val, nnz_capacity, nnz, total); },
     [&] (ACMPlan *plan) { return acm_gpu_tally_batch_host (plan, text, offsets, n_texts, row_ptr, col, val, nnz_capacity, nnz, total); });
 }
 

@@ -917,8 +917,8 @@ acm_split_offsets (const void *text, uint64_t n_symbols, uint32_t sym_bytes, con
   return ACM_GPU_OK;
 }
 
-/* acm_grep_lines on the host (include/acm_gpu.h): the split, the caller loop from the root on every
- * text, counting, then the sequential gather -- what ACM_SCAN_PATH_CPU_LOOP runs. */
+/* acm_grep_lines on the host (include/acm_gpu.h): the split, then acm_internal_cpu_grep over its
+ * texts -- what ACM_SCAN_PATH_CPU_LOOP runs. */
 int
 acm_internal_cpu_grep_lines (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *delims, uint32_t n_delims,
                              uint32_t split_flags, uint32_t grep_flags, uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out,
@@ -936,24 +936,13 @@ acm_internal_cpu_grep_lines (ACMachine *m, const void *text, uint64_t n_symbols,
   if (n >= (1ull << 31))
     return ACM_GPU_E_ARG;
   uint64_t *own_off = offsets ? NULL : malloc ((n + 1) * sizeof (uint64_t));
-  uint64_t *own_hits = hits ? NULL : malloc ((n + 1) * sizeof (uint64_t));
-  uint64_t *off = offsets ? offsets : own_off, *h = hits ? hits : own_hits;
-  if (!off || !h)
-    rc = ACM_GPU_E_NOMEM;
+  uint64_t *off = offsets ? offsets : own_off;
+  if (!off)
+    return ACM_GPU_E_NOMEM;
+  rc = acm_split_offsets (text, n_symbols, sym_bytes, delims, n_delims, split_flags, off, n, &n);
   if (!rc)
-    rc = acm_split_offsets (text, n_symbols, sym_bytes, delims, n_delims, split_flags, off, n, &n);
-  if (!rc)
-    rc = acm_internal_cpu_grep_hits (m, text, off, n, sym_bytes, h);
-  if (!rc) {
-    if (total) {
-      *total = 0;
-      for (uint64_t t = 0; t < n; t++)
-        *total += h[t];
-    }
-    rc = acm_grep_gather (text, sym_bytes, off, n, h, grep_flags, kept, n_kept, out, out ? out_capacity : 0, out_offsets, out_symbols);
-  }
+    rc = acm_internal_cpu_grep (m, text, off, n, sym_bytes, grep_flags, hits, kept, n_kept, total, out, out_capacity, out_offsets, out_symbols);
   free (own_off);
-  free (own_hits);
   return rc;
 }
 
@@ -1315,4 +1304,118 @@ acm_tokens_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, ui
     return ACM_GPU_E_OVERFLOW;
   (void)tokens_walk (t, n_symbols, sym_bytes, pos_base, records, n, offsets, n_texts, tok_of, gap_base, mode, 1, tok_id, tok_start, tok_len, NULL);
   return ACM_GPU_OK;
+}
+
+/* ---- what ACM_SCAN_PATH_CPU_LOOP runs for the other calls of include/acm_gpu.h; arguments as the public call's, behind its checks.
+ * The caller loop over one text (offsets NULL) or from the root at every offset of a batch (first[] as acm_internal_cpu_scan_batch's,
+ * may be NULL), into a record room the call grows itself: one record per 64 symbols, 1024 at the least, and once more with the
+ * number the first scan found.  *records is the caller's to free, whatever is returned. */
+static int
+cpu_scan_grown (ACMachine *m, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint64_t *first,
+                ACMRecord **records, uint64_t *n_found) {
+  uint64_t room = n_symbols / 64 > 1024 ? n_symbols / 64 : 1024;
+  *records = NULL;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    free (*records);
+    *records = malloc (room * sizeof (ACMRecord));
+    if (!*records)
+      return ACM_GPU_E_NOMEM;
+    const int rc = offsets ? acm_internal_cpu_scan_batch (m, text, offsets, n_texts, sym_bytes, *records, NULL, first, room, n_found)
+                           : acm_internal_cpu_scan (m, text, n_symbols, sym_bytes, *records, room, n_found);
+    if (rc != ACM_GPU_E_OVERFLOW)
+      return rc;
+    room = *n_found;
+  }
+  return ACM_GPU_E_INTERNAL; /* (keywords inserted between the two scans) */
+}
+
+int
+acm_internal_cpu_select (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records, uint64_t capacity,
+                         uint64_t *n_found) {
+  const int rc = acm_internal_cpu_scan (m, text, n_symbols, sym_bytes, records, capacity, n_found);
+  if (!rc)
+    *n_found = acm_select_records (records, *n_found);
+  return rc;
+}
+
+/* the loop, the selection, the sequential pass.  The table covers every keyword of the machine, as on the GPU paths. */
+int
+acm_internal_cpu_replace (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *repl_data, const uint64_t *repl_off,
+                          uint64_t n_keywords, void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_replaced) {
+  if (!m || (repl_off && n_keywords < acm_nb_keywords (m)))
+    return ACM_GPU_E_ARG;
+  ACMRecord *records;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, n_symbols, NULL, 0, sym_bytes, NULL, &records, &found);
+  if (!rc) {
+    found = acm_select_records (records, found);
+    if (n_replaced)
+      *n_replaced = found;
+    rc = acm_replace_records (text, n_symbols, sym_bytes, 0, records, found, repl_data, repl_off, n_keywords, out, out_capacity, out_symbols);
+  }
+  free (records);
+  return rc;
+}
+
+/* the same with the token pass (a batch's records never cross a text: one selection serves all texts) */
+int
+acm_internal_cpu_tokenize (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                           const uint32_t *tok_of, uint64_t n_keywords, uint32_t gap_base, uint32_t mode, uint32_t *tok_id, uint64_t *tok_start,
+                           uint32_t *tok_len, uint64_t token_capacity, uint64_t *n_tokens, uint64_t *tok_first, uint64_t *n_selected) {
+  ACMRecord *records;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, n_symbols, offsets, n_texts, sym_bytes, NULL, &records, &found);
+  if (!rc) {
+    found = acm_select_records (records, found);
+    if (n_selected)
+      *n_selected = found;
+    rc = acm_tokens_records (text, n_symbols, sym_bytes, 0, records, found, offsets, n_texts, tok_of, n_keywords, gap_base, mode, tok_id, tok_start,
+                             tok_len, token_capacity, n_tokens, tok_first);
+  }
+  free (records);
+  return rc;
+}
+
+/* the loop, counting per text (into the caller's hits[] or the call's own), then the sequential gather */
+int
+acm_internal_cpu_grep (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint32_t flags, uint64_t *hits,
+                       uint32_t *kept, uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets,
+                       uint64_t *out_symbols) {
+  uint64_t *own = hits ? NULL : malloc ((n_texts + 1) * sizeof (uint64_t));
+  uint64_t *h = hits ? hits : own;
+  if (!h)
+    return ACM_GPU_E_NOMEM;
+  int rc = acm_internal_cpu_grep_hits (m, text, offsets, n_texts, sym_bytes, h);
+  if (!rc) {
+    if (total) {
+      *total = 0;
+      for (uint64_t t = 0; t < n_texts; t++)
+        *total += h[t];
+    }
+    rc = acm_grep_gather (text, sym_bytes, offsets, n_texts, h, flags, kept, n_kept, out, out ? out_capacity : 0, out_offsets, out_symbols);
+  }
+  free (own);
+  return rc;
+}
+
+/* the loop with first[], then the sequential pass over the records */
+int
+acm_internal_cpu_tally_batch (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint64_t *row_ptr,
+                              uint32_t *col, uint64_t *val, uint64_t nnz_capacity, uint64_t *nnz, uint64_t *total) {
+  if (!m || !offsets)
+    return ACM_GPU_E_ARG;
+  uint64_t *first = malloc ((n_texts + 1) * sizeof (uint64_t));
+  if (!first)
+    return ACM_GPU_E_NOMEM;
+  ACMRecord *records;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, offsets[n_texts], offsets, n_texts, sym_bytes, first, &records, &found);
+  if (!rc) {
+    if (total)
+      *total = found;
+    rc = acm_tally_batch_records (records, first, n_texts, acm_nb_keywords (m), row_ptr, col, val, nnz_capacity, nnz);
+  }
+  free (records);
+  free (first);
+  return rc;
 }

@@ -68,7 +68,21 @@ int acm_internal_cpu_tally (ACMachine *m, const void *text, uint64_t n_symbols, 
 /* the same loop from the root on every text of a batch, counting per text instead of recording (acm_grep): hits[t] = the
  * number of matches of text t; offsets[] already checked */
 int acm_internal_cpu_grep_hits (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint64_t *hits);
-/* acm_grep_lines' host path: acm_split_offsets, the loop above, acm_grep_gather (arguments as acm_grep_lines') */
+/* The host paths of the calls that give their caller no record room: arguments as the public call's (include/acm_gpu.h)
+ * with the symbol size behind the text; the public call has checked them.  The record room is the call's own and grown once. */
+int acm_internal_cpu_select (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records, uint64_t capacity,
+                             uint64_t *n_found);
+int acm_internal_cpu_replace (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *repl_data, const uint64_t *repl_off,
+                              uint64_t n_keywords, void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_replaced);
+int acm_internal_cpu_tokenize (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                               const uint32_t *tok_of, uint64_t n_keywords, uint32_t gap_base, uint32_t mode, uint32_t *tok_id, uint64_t *tok_start,
+                               uint32_t *tok_len, uint64_t token_capacity, uint64_t *n_tokens, uint64_t *tok_first, uint64_t *n_selected);
+int acm_internal_cpu_grep (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint32_t flags, uint64_t *hits,
+                           uint32_t *kept, uint64_t *n_kept, uint64_t *total, void *out, uint64_t out_capacity, uint64_t *out_offsets,
+                           uint64_t *out_symbols);
+int acm_internal_cpu_tally_batch (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint64_t *row_ptr,
+                                  uint32_t *col, uint64_t *val, uint64_t nnz_capacity, uint64_t *nnz, uint64_t *total);
+/* acm_grep_lines' host path: acm_split_offsets, then acm_internal_cpu_grep (arguments as acm_grep_lines') */
 int acm_internal_cpu_grep_lines (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *delims, uint32_t n_delims,
                                  uint32_t split_flags, uint32_t grep_flags, uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out,
                                  uint64_t out_capacity, uint64_t *out_symbols, uint64_t texts_capacity, uint64_t *offsets, uint64_t *hits,

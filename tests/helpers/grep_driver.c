@@ -1,10 +1,10 @@
-/* Test-only driver: acm_grep_gather and the caller-loop acm_grep (acm_host.c, no HIP) under
+/* Test-only driver: acm_grep_gather and acm_grep's host path (acm_host.c, no HIP) under
  * AddressSanitizer and UBSan.  Every buffer is allocated at its exact size, so that a byte read or
  * written beside it is seen.  The machine's comparator is memcmp over 3-byte symbols, declared with
- * acm_set_symbol_bytes: what acm_grep would run for it is the caller loop on the host, and that loop
- * and the gather are called here as acm_grep calls them (acm_grep itself lives in the HIP translation
- * unit, which this program does not link).  Built and run by tests/test_grep_sanitized.py; exits 0
- * when every check held. */
+ * acm_set_symbol_bytes: what acm_grep runs for it is the caller loop on the host.  The loop and the
+ * gather are called on their own, and then acm_internal_cpu_grep, the very function acm_grep calls
+ * for such a machine (acm_grep itself lives in the HIP translation unit, which this program does not
+ * link).  Built and run by tests/test_grep_sanitized.py; exits 0 when every check held. */
 #include "aho_corasick.h"
 #include "acm_gpu.h"
 #include "acm_internal.h"
@@ -112,6 +112,21 @@ main (void) {
   uint64_t *zero = exact ((uint64_t[]){ 0 }, sizeof (uint64_t));
   CHECK (acm_grep_gather (NULL, 3, zero, 0, NULL, ACM_GREP_INVERT, NULL, &n_kept, NULL, 0, NULL, &out_symbols) == ACM_GPU_OK);
   CHECK (n_kept == 0 && out_symbols == 0);
+  /* what acm_grep runs on the host, with hit counters of its own: the loop, the total, the gather */
+  uint64_t total = 99;
+  n_kept = out_symbols = 99;
+  memset (out, 0, 3 * 24);
+  CHECK (acm_internal_cpu_grep (m, text, off, n_texts, 3, ACM_GREP_MATCHING, NULL, kept, &n_kept, &total, out, 24, out_off, &out_symbols) == ACM_GPU_OK);
+  CHECK (n_kept == 3 && kept[0] == 1 && kept[2] == 3 && total == 10 && out_symbols == 24 && out_off[3] == 24 && memcmp (out, text, 3 * 24) == 0);
+  /* one text of 3000 x "s": 3000 matches, counted into the caller's one counter */
+  unsigned char *big = malloc (3 * 3000);
+  uint64_t *big_off = exact ((uint64_t[]){ 0, 3000 }, 2 * sizeof (uint64_t)), *big_hits = malloc (sizeof *big_hits);
+  CHECK (big && big_hits);
+  for (int i = 0; i < 3000; i++)
+    sym3 (big + 3 * i, "s", 1);
+  CHECK (acm_internal_cpu_grep (m, big, big_off, 1, 3, ACM_GREP_MATCHING, big_hits, NULL, &n_kept, &total, NULL, 0, NULL, &out_symbols) == ACM_GPU_OK);
+  CHECK (n_kept == 1 && total == 3000 && big_hits[0] == 3000 && out_symbols == 3000);
+  free (big_hits), free (big_off), free (big);
   off[2] = 14;
   CHECK (acm_grep_gather (text, 3, off, n_texts, hits, ACM_GREP_MATCHING, kept, &n_kept, out, 24, out_off, &out_symbols) == ACM_GPU_E_ARG);
   free (zero), free (inv), free (small), free (out), free (out_off), free (kept), free (hits), free (off), free (text);

@@ -1,9 +1,11 @@
-/* Test-only driver: acm_replace_records (acm_host.c, no HIP) under AddressSanitizer and UBSan -- the
- * ushers case, a deletion of everything, an output with one symbol too little room.  Every buffer is
- * allocated at its exact size, so that a byte read or written beside it is seen.  Built and run by
- * tests/test_replace_sanitized.py; exits 0 when every check held. */
+/* Test-only driver: acm_replace_records and acm_replace's host path, acm_internal_cpu_replace (acm_host.c,
+ * no HIP), under AddressSanitizer and UBSan -- the ushers case, a deletion of everything, an output with
+ * one symbol too little room, a text with more records than the host path's record room starts with.
+ * Every buffer is allocated at its exact size, so that a byte read or written beside it is seen.  Built
+ * and run by tests/test_replace_sanitized.py; exits 0 when every check held. */
 #include "aho_corasick.h"
 #include "acm_gpu.h"
+#include "acm_internal.h"
 
 #include <stdint.h>
 #include <stdio.h>
@@ -100,6 +102,22 @@ main (void) {
   CHECK (acm_replace_records (t3, 4, 3, 1000, all, 4, r3, off0, 1, o3, 8, &need) == ACM_GPU_OK && need == 8);
   for (int i = 0; i < 4; i++)
     CHECK (memcmp (o3 + 6 * i, "XYZxyz", 6) == 0);
+  /* what acm_replace runs on the host for a machine no GPU path takes: the loop into a record room of
+   * its own, the selection, the pass above */
+  uint64_t replaced = 99;
+  need = 99;
+  CHECK (acm_internal_cpu_replace (m, text, 6, 1, data, off, 4, out, 6, &need, &replaced) == ACM_GPU_OK);
+  CHECK (need == 6 && replaced == 1 && memcmp (out, "u[X]rs", 6) == 0);
+  /* "he" x 1500: more records than the 1024 the room starts with, so it is grown; every match becomes "[H]" */
+  char *big = malloc (3000), *big_out = malloc (4500);
+  CHECK (big && big_out);
+  for (int i = 0; i < 3000; i++)
+    big[i] = "he"[i % 2];
+  CHECK (acm_internal_cpu_replace (m, big, 3000, 1, data, off, 4, big_out, 4500, &need, &replaced) == ACM_GPU_OK);
+  CHECK (need == 4500 && replaced == 1500);
+  for (int i = 0; i < 4500; i++)
+    CHECK (big_out[i] == "[H]"[i % 3]);
+  free (big_out), free (big);
   free (o3), free (r3), free (off0), free (all), free (t3), free (small), free (out), free (off), free (data), free (rec), free (text);
   acm_release (m);
   printf ("all checks held\n");

@@ -1,8 +1,9 @@
-/* Test-only driver: acm_tally_batch_records and the caller loop of acm_tally_batch (acm_host.c, no
- * HIP) under AddressSanitizer and UBSan.  Every buffer is allocated at its exact size, so that a
- * byte read or written beside it is seen.  The machine's comparator is memcmp over 3-byte symbols,
- * declared with acm_set_symbol_bytes: what acm_tally_batch would run for it is the caller loop on
- * the host, and that loop and the sequential pass are called here as acm_tally_batch calls them
+/* Test-only driver: acm_tally_batch_records and acm_tally_batch's host path (acm_host.c, no HIP)
+ * under AddressSanitizer and UBSan.  Every buffer is allocated at its exact size, so that a byte
+ * read or written beside it is seen.  The machine's comparator is memcmp over 3-byte symbols,
+ * declared with acm_set_symbol_bytes: what acm_tally_batch runs for it is the caller loop on the
+ * host.  The loop and the sequential pass are called on their own, and then
+ * acm_internal_cpu_tally_batch, the very function acm_tally_batch calls for such a machine
  * (acm_tally_batch itself lives in the HIP translation unit, which this program does not link).
  * Built and run by tests/test_tally_batch_sanitized.py; exits 0 when every check held. */
 #include "aho_corasick.h"
@@ -107,6 +108,31 @@ main (void) {
     CHECK (((unsigned char *)small_col)[i] == '.');
   for (size_t i = 0; i < 6 * sizeof *small_val; i++)
     CHECK (((unsigned char *)small_val)[i] == '.');
+  /* what acm_tally_batch runs on the host: the loop into a record room of its own, then the pass above */
+  uint64_t total = 99;
+  nnz = 99;
+  memset (row_ptr, 0xFF, (n_texts + 1) * sizeof *row_ptr);
+  memset (col, 0xFF, 7 * sizeof *col);
+  memset (val, 0xFF, 7 * sizeof *val);
+  CHECK (acm_internal_cpu_tally_batch (m, text, off, n_texts, 3, row_ptr, col, val, 7, &nnz, &total) == ACM_GPU_OK);
+  CHECK (nnz == 7 && total == 10 && memcmp (row_ptr, want_ptr, sizeof want_ptr) == 0);
+  CHECK (memcmp (col, want_col, sizeof want_col) == 0 && memcmp (val, want_val, sizeof want_val) == 0);
+  /* "he", 3000 x "s", "she": more records than the 1024 the room starts with, so it is grown */
+  unsigned char *big = malloc (3 * 3005);
+  CHECK (big);
+  sym3 (big, "he", 2);
+  for (int i = 0; i < 3000; i++)
+    sym3 (big + 3 * (2 + i), "s", 1);
+  sym3 (big + 3 * 3002, "she", 3);
+  uint64_t *big_off = exact ((uint64_t[]){ 0, 2, 3002, 3005 }, 4 * sizeof (uint64_t));
+  uint64_t *big_ptr = malloc (4 * sizeof *big_ptr), *big_val = malloc (5 * sizeof *big_val);
+  uint32_t *big_col = malloc (5 * sizeof *big_col);
+  CHECK (big_ptr && big_val && big_col);
+  CHECK (acm_internal_cpu_tally_batch (m, big, big_off, 3, 3, big_ptr, big_col, big_val, 5, &nnz, &total) == ACM_GPU_OK);
+  CHECK (nnz == 5 && total == 3004 && memcmp (big_ptr, (uint64_t[]){ 0, 1, 2, 5 }, 4 * sizeof (uint64_t)) == 0);
+  CHECK (memcmp (big_col, (uint32_t[]){ 0, 3, 0, 1, 3 }, 5 * sizeof (uint32_t)) == 0);
+  CHECK (memcmp (big_val, (uint64_t[]){ 1, 3000, 1, 1, 1 }, 5 * sizeof (uint64_t)) == 0);
+  free (big_col), free (big_val), free (big_ptr), free (big_off), free (big);
   /* counting only; no text at all; a first[] that decreases; a keyword id that is none */
   nnz = 99;
   CHECK (acm_tally_batch_records (records, first, n_texts, 4, row_ptr, NULL, NULL, 0, &nnz) == ACM_GPU_OK && nnz == 7);

@@ -1,10 +1,12 @@
-/* Test-only driver: acm_tokens_records (acm_host.c, no HIP) under AddressSanitizer and UBSan -- the
- * ushers case in the three modes, as one text and as the batch us | hers, a count-only call, a token
- * room one short, the argument errors.  Every buffer is allocated at its exact size, so that a byte
- * read or written beside it is seen.  Built and run by tests/test_tokens_sanitized.py; exits 0 when
- * every check held. */
+/* Test-only driver: acm_tokens_records and acm_tokenize's host path, acm_internal_cpu_tokenize
+ * (acm_host.c, no HIP), under AddressSanitizer and UBSan -- the ushers case in the three modes, as one
+ * text and as the batch us | hers, a count-only call, a token room one short, the argument errors, a
+ * text with more records than the host path's record room starts with.  Every buffer is allocated at its
+ * exact size, so that a byte read or written beside it is seen.  Built and run by
+ * tests/test_tokens_sanitized.py; exits 0 when every check held. */
 #include "aho_corasick.h"
 #include "acm_gpu.h"
+#include "acm_internal.h"
 
 #include <stdint.h>
 #include <stdio.h>
@@ -104,6 +106,28 @@ main (void) {
   CHECK (acm_tokens_records (NULL, 6, 1, 0, brec, bn, off, 2, NULL, 0, gb, ACM_TOKENS_GAP_RUN, id, start, len, 2, &need, first) == ACM_GPU_OK);
   CHECK (need == 2 && same32 (id, (uint32_t[]){ gb, 3 }, 2) && same64 (start, (uint64_t[]){ 0, 2 }, 2) && same32 (len, (uint32_t[]){ 2, 4 }, 2) &&
          same64 (first, (uint64_t[]){ 0, 1, 2 }, 3));
+  /* what acm_tokenize runs on the host for a machine no GPU path takes (the loop into a record room of its
+   * own, the selection, the pass above): the one text through the table, then the batch */
+  uint64_t selected = 99;
+  CHECK (acm_internal_cpu_tokenize (m, text, 6, 1, NULL, 0, tok_of, 4, gb, ACM_TOKENS_GAP_RUN, id, NULL, len, 3, &need, NULL, &selected) == ACM_GPU_OK);
+  CHECK (need == 3 && selected == 1 && same32 (id, (uint32_t[]){ gb, 51, gb }, 3) && same32 (len, (uint32_t[]){ 1, 3, 2 }, 3));
+  memset (first, 0xff, 3 * sizeof *first);
+  CHECK (acm_internal_cpu_tokenize (m, text, 6, 1, off, 2, NULL, 0, gb, ACM_TOKENS_GAP_RUN, id, start, len, 2, &need, first, &selected) == ACM_GPU_OK);
+  CHECK (need == 2 && selected == 1 && same32 (id, (uint32_t[]){ gb, 3 }, 2) && same64 (start, (uint64_t[]){ 0, 2 }, 2) &&
+         same32 (len, (uint32_t[]){ 2, 4 }, 2) && same64 (first, (uint64_t[]){ 0, 1, 2 }, 3));
+  /* "he" x 1500: more records than the 1024 the room starts with, so it is grown; 1500 tokens of `he` and no gap */
+  char *big = malloc (3000);
+  uint32_t *big_id = malloc (1500 * sizeof *big_id);
+  uint64_t *big_start = malloc (1500 * sizeof *big_start);
+  CHECK (big && big_id && big_start);
+  for (int i = 0; i < 3000; i++)
+    big[i] = "he"[i % 2];
+  CHECK (acm_internal_cpu_tokenize (m, big, 3000, 1, NULL, 0, tok_of, 4, gb, ACM_TOKENS_GAP_DROP, big_id, big_start, NULL, 1500, &need, NULL, &selected) ==
+         ACM_GPU_OK);
+  CHECK (need == 1500 && selected == 1500);
+  for (uint64_t i = 0; i < 1500; i++)
+    CHECK (big_id[i] == 50 && big_start[i] == 2 * i);
+  free (big_start), free (big_id), free (big);
   /* the token room too small: tok_first is written all the same */
   memset (first, 0xff, 3 * sizeof *first);
   CHECK (acm_tokens_records (text, 6, 1, 0, brec, bn, off, 2, NULL, 0, gb, ACM_TOKENS_GAP_SYMBOL, id, start, len, 2, &need, first) == ACM_GPU_E_OVERFLOW);

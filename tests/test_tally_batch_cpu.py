@@ -131,6 +131,29 @@ def test_tally_batch_on_the_host_loop():
     L.acm_release(h)
 
 
+def test_tally_batch_on_the_host_loop_regrows_its_record_room():
+    """one text of 3,000 x "s" between two short ones: more records than the 1,024 the loop starts with"""
+    o = byte_oracle(KEYWORDS)
+    texts = [b"ushers", b"s" * 3000, b"she"]
+    text = np.frombuffer(b"".join(texts), np.uint8)
+    off = offsets_of(texts)
+    want = expected(o, text, off)
+    assert int(want[2].sum()) > 1024 > text.size // 64
+    L = acm.lib()
+    h, keep = loop_machine(KEYWORDS)
+    raw = np.frombuffer(sym3(bytes(text)), np.uint8).copy()
+    n, k = off.size - 1, want[1].size
+    row_ptr = np.zeros(n + 1, np.uint64)
+    col, val = np.full(k + 2, GUARD32, np.uint32), np.full(k + 2, GUARD64, np.uint64)
+    nnz, total = C.c_uint64(99), C.c_uint64(99)
+    rc = L.acm_tally_batch(h, raw.ctypes.data, off.ctypes.data, n, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data, k, C.byref(nnz),
+                           C.byref(total))
+    assert rc == 0 and L.acm_scan_path(h) == PATH_LOOP
+    check(binding.TalliedBatch(row_ptr, col[:nnz.value], val[:nnz.value], int(nnz.value), int(total.value)), want, "acm_tally_batch, regrown")
+    assert np.all(col[k:] == GUARD32) and np.all(val[k:] == GUARD64)
+    L.acm_release(h)
+
+
 def test_plan_level_calls_refuse_before_they_touch_a_device():
     L = acm.lib()
     nnz = C.c_uint64(0)
