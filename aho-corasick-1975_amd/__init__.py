@@ -13,6 +13,7 @@ from .binding import (  # noqa: F401
     tokens_records, Tokens, TOKENS_GAP_SYMBOL, TOKENS_GAP_RUN, TOKENS_GAP_DROP,
     grep_gather, Grepped, split_offsets,
     tally_batch_records, TalliedBatch,
+    rule, present, absent, between, RuleSet, Rules, Fired, rules_matrix, ACM_RULE_NO_MAX,
     words_records, ASCII_WORD, ACM_WORDS_LEFT, ACM_WORDS_RIGHT, ACM_WORDS_BOTH,
 )
 from . import synth  # noqa: F401

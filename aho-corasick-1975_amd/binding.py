@@ -19,6 +19,7 @@ ACM_GPU_E_ARG = -5
 ACM_GREP_MATCHING, ACM_GREP_INVERT = 0, 1
 ACM_SPLIT_EVERY, ACM_SPLIT_RUNS = 0, 1
 ACM_WORDS_LEFT, ACM_WORDS_RIGHT, ACM_WORDS_BOTH = 1, 2, 3
+ACM_RULE_NO_MAX = 0xFFFFFFFF
 # the usual ASCII word set as inclusive (lo, hi) ranges: 0-9, A-Z, _, a-z (UTF-8 byte text adds (0x80, 0xFF))
 ASCII_WORD = ((0x30, 0x39), (0x41, 0x5A), (0x5F, 0x5F), (0x61, 0x7A))
 
@@ -70,6 +71,10 @@ class PlanInfo(C.Structure):
                                      ("records_direct", C.c_uint32), ("variant", C.c_uint32)]
 
 
+class RulesInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("rules", "terms", "always_rules", "postings", "fast_texts", "wide_texts")]
+
+
 _lib = None
 
 # every symbol include/acm.h and include/acm_gpu.h declare
@@ -103,6 +108,8 @@ EXPORTS = [
     "acm_tally_batch_records", "acm_gpu_tally_batch_tmp_bytes", "acm_gpu_tally_batch_device", "acm_gpu_tally_batch_host", "acm_tally_batch",
     "acm_words_records", "acm_gpu_words_tmp_bytes", "acm_gpu_words_records_device", "acm_gpu_scan_words_tmp_bytes", "acm_gpu_scan_words_device",
     "acm_gpu_scan_words_host", "acm_scan_words",
+    "acm_rules_check", "acm_rules_matrix", "acm_gpu_rules_create", "acm_gpu_rules_destroy", "acm_gpu_rules_info", "acm_gpu_rules_matrix_tmp_bytes",
+    "acm_gpu_rules_matrix_device", "acm_gpu_rules_tmp_bytes", "acm_gpu_rules_device", "acm_gpu_rules_host", "acm_rules",
 ]
 
 
@@ -334,6 +341,27 @@ def lib():
     L.acm_gpu_tally_batch_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.acm_tally_batch.restype = i32
     L.acm_tally_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_rules_check.restype = i32
+    L.acm_rules_check.argtypes = [vp, vp, vp, u64, u64]
+    L.acm_rules_matrix.restype = i32
+    L.acm_rules_matrix.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_rules_create.restype = i32
+    L.acm_gpu_rules_create.argtypes = [vp, vp, vp, vp, u64, C.POINTER(vp)]
+    L.acm_gpu_rules_destroy.restype = None
+    L.acm_gpu_rules_destroy.argtypes = [vp]
+    L.acm_gpu_rules_info.restype = i32
+    L.acm_gpu_rules_info.argtypes = [vp, C.POINTER(RulesInfo)]
+    L.acm_gpu_rules_matrix_tmp_bytes.restype = sz
+    L.acm_gpu_rules_matrix_tmp_bytes.argtypes = [vp, vp, u64]
+    L.acm_gpu_rules_matrix_device.restype = i32
+    L.acm_gpu_rules_matrix_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_rules_tmp_bytes.restype = sz
+    L.acm_gpu_rules_tmp_bytes.argtypes = [vp, vp, u64, u64, u64, u64, u64]
+    L.acm_gpu_rules_device.restype = i32
+    L.acm_gpu_rules_device.argtypes = [vp, vp, vp, u64, vp, u64, u64, u64, u64, vp, vp, u64, vp, vp, vp, vp, vp, sz, vp]
+    for fn in (L.acm_gpu_rules_host, L.acm_rules):
+        fn.restype = i32
+        fn.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.acm_split_offsets.restype = i32
     L.acm_split_offsets.argtypes = [vp, u64, u32, vp, u32, u32, vp, u64, C.POINTER(u64)]
     L.acm_gpu_split_tmp_bytes.restype = sz
@@ -678,6 +706,135 @@ def tally_batch_records(records, first, n_keywords):
     return TalliedBatch(row_ptr, col[:k], val[:k], k, int(val[:k].sum()))
 
 
+def present(k, at_least=1):
+    """the term `keyword k occurs at_least times or more`"""
+    return (int(k), int(at_least), ACM_RULE_NO_MAX)
+
+
+def absent(k):
+    """the term `keyword k does not occur`"""
+    return (int(k), 0, 0)
+
+
+def between(k, lo, hi):
+    """the term `keyword k occurs lo to hi times` (hi = ACM_RULE_NO_MAX: no upper bound)"""
+    return (int(k), int(lo), int(hi))
+
+
+def rule(terms, need=None):
+    """a rule: (terms, need) -- it fires when `need` of its terms (keyword_id, lo, hi) hold or more;
+    need None: all of them (AND), 1: any (OR)"""
+    terms = [tuple(int(x) for x in t) for t in terms]
+    return terms, len(terms) if need is None else int(need)
+
+
+class RuleSet:
+    """rules (what rule() returns, or (terms, need) pairs) packed to the three arrays the C calls
+    take: terms (uint32 [n_terms, 3]), rule_ptr (uint64, n_rules + 1) and need (uint32)."""
+
+    def __init__(self, rules):
+        rules = [r if isinstance(r[1], int) else rule(r) for r in rules]
+        self.n_rules = len(rules)
+        flat = [t for terms, _ in rules for t in terms]
+        self.terms = np.array(flat, dtype=np.uint32).reshape(-1, 3) if flat else np.zeros((0, 3), np.uint32)
+        self.rule_ptr = np.zeros(self.n_rules + 1, np.uint64)
+        if rules:
+            np.cumsum([len(terms) for terms, _ in rules], out=self.rule_ptr[1:])
+        self.need = np.array([need for _, need in rules], dtype=np.uint32)
+
+    def args(self):
+        """(terms, rule_ptr, need, n_rules) as the C calls take them"""
+        return (self.terms.ctypes.data if self.terms.size else None, self.rule_ptr.ctypes.data, self.need.ctypes.data if self.need.size else None,
+                self.n_rules)
+
+    def check(self, n_keywords):
+        """acm_rules_check(): raises ACMError (ACM_GPU_E_ARG) for a set the calls would refuse"""
+        _check(lib().acm_rules_check(*self.args(), int(n_keywords)), "acm_rules_check")
+
+
+def _ruleset(rules):
+    return rules if isinstance(rules, RuleSet) else RuleSet(rules)
+
+
+class Fired:
+    """What the rules calls return: the text x rule boolean matrix of a batch in CSR form.  fired_ptr
+    (n_texts + 1 entries) and fired (rule ids, ascending within a row): int64 / int32 device tensors
+    from Plan.rules() and Plan.rules_matrix() -- fired has room for fired_capacity entries, its first
+    n_fired count --, uint64 / uint32 numpy arrays cut to size from the host calls.  n_fired, total,
+    need and need_pairs are Python ints (the device calls synchronise to read them; total, need and
+    need_pairs are None where no text was scanned): n_fired > fired_capacity says that `fired` had no
+    room, need > capacity or need_pairs > pair_capacity that the tally in front overflowed --
+    n_fired = 0 then."""
+
+    def __init__(self, fired_ptr, fired, n_fired, total=None, need=None, need_pairs=None, fired_capacity=None):
+        self.fired_ptr, self.fired, self.n_fired, self.total, self.need, self.need_pairs = fired_ptr, fired, n_fired, total, need, need_pairs
+        self.fired_capacity = fired_capacity
+
+    def to_sparse_csr(self, n_rules):
+        """The matrix as a torch.sparse_csr_tensor of n_texts x n_rules ones (int8), built on the index
+        arrays where they are."""
+        import torch
+
+        def tensor(a, dtype):
+            return a.view(dtype) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).view(dtype)
+        col = tensor(self.fired, torch.int32)[:self.n_fired]
+        return torch.sparse_csr_tensor(tensor(self.fired_ptr, torch.int64), col, torch.ones(self.n_fired, dtype=torch.int8, device=col.device),
+                                       size=(self.fired_ptr.shape[0] - 1, int(n_rules)))
+
+    def rule_hits(self, n_rules):
+        """in how many texts every rule fired: a bincount of `fired`"""
+        import torch
+        if isinstance(self.fired, torch.Tensor):
+            return torch.bincount(self.fired[:self.n_fired].to(torch.int64), minlength=int(n_rules))
+        return np.bincount(np.asarray(self.fired[:self.n_fired]).astype(np.int64), minlength=int(n_rules))
+
+
+def _fired_host_call(call, what, n_texts, total=None):
+    """call(fired_ptr, fired, capacity, n_fired) -> rc, for acm_rules_matrix / acm_gpu_rules_host /
+    acm_rules: a Fired of numpy arrays out.  An output overflow is repeated once with the size the
+    call reports."""
+    fired_ptr = np.zeros(n_texts + 1, np.uint64)
+    cap = max(1024, n_texts)
+    for attempt in (0, 1):
+        fired = np.zeros(cap, np.uint32)
+        n = C.c_uint64(0)
+        rc = call(fired_ptr.ctypes.data, fired.ctypes.data, cap, C.byref(n))
+        if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
+            cap = int(n.value)
+            continue
+        _check(rc, what)
+        k = int(n.value)
+        return Fired(fired_ptr, fired[:k], k, int(total.value) if total is not None else None, fired_capacity=cap)
+
+
+def rules_matrix(tallied, ruleset, n_keywords):
+    """acm_rules_matrix(): which rules fire in which text, given the count matrix `tallied` (a
+    TalliedBatch of numpy arrays), by the sequential evaluation on the host.  Returns a Fired of numpy
+    arrays."""
+    rs = _ruleset(ruleset)
+    row_ptr = np.ascontiguousarray(tallied.row_ptr, dtype=np.uint64)
+    col = np.ascontiguousarray(tallied.col, dtype=np.uint32)
+    val = np.ascontiguousarray(tallied.val, dtype=np.uint64)
+    assert row_ptr.size >= 1, "row_ptr has n_texts + 1 entries"
+
+    def call(fired_ptr, fired, cap, n):
+        return lib().acm_rules_matrix(row_ptr.ctypes.data, col.ctypes.data if col.size else None, val.ctypes.data if val.size else None,
+                                      row_ptr.size - 1, int(n_keywords), *rs.args(), fired_ptr, fired, cap, n)
+    return _fired_host_call(call, "acm_rules_matrix", row_ptr.size - 1)
+
+
+def _rules_host_call(fn, what, handle, t, sym_size, off, ruleset):
+    """acm_gpu_rules_host / acm_rules: numpy in, a Fired of numpy arrays out"""
+    rs = _ruleset(ruleset)
+    n_texts = off.size - 1
+    assert t.size * t.itemsize == int(off[-1]) * sym_size, "the last offset is the number of symbols"
+    total = C.c_uint64(0)
+
+    def call(fired_ptr, fired, cap, n):
+        return fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, *rs.args(), fired_ptr, fired, cap, n, C.byref(total))
+    return _fired_host_call(call, what, n_texts, total)
+
+
 def _delims(delims, sym_size, raw=False):
     """delimiters as a contiguous array of whole symbols: bytes are one symbol per byte, widened to the
     symbol size (b"\\n" is the symbol 10), unless `raw` (symbols without a numpy type: the bytes as they are)"""
@@ -900,6 +1057,20 @@ class Machine:
         if isinstance(x, (bytes, bytearray)):
             x = np.frombuffer(bytes(x), dtype=np.uint8)
         return np.ascontiguousarray(x, dtype=_SYM_DTYPE[self.sym_size])
+
+    def _pack_texts(self, texts):
+        """a list of texts (bytes or arrays of symbols) side by side in one array, and their n + 1 offsets"""
+        def symbols(t):
+            if self.sym_size in _SYM_DTYPE:
+                return self._symbols(t)
+            return np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t)
+        parts = [symbols(t).reshape(-1) for t in texts]
+        offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
+        if parts:
+            np.cumsum([p.size * p.itemsize // self.sym_size for p in parts], out=offsets[1:])
+        dtype = _SYM_DTYPE.get(self.sym_size, np.uint8)
+        packed = np.concatenate([p.view(dtype) for p in parts]) if parts else np.zeros(0, dtype)
+        return packed, offsets
 
     def add_keyword(self, symbols, value=None):
         """acm_insert_letter_of_keyword per symbol then acm_insert_end_of_keyword.  Returns the
@@ -1180,16 +1351,7 @@ class Machine:
         the root on its own in ONE call.  Returns a Grepped of numpy arrays: hits per text, the ids of
         the texts with a match (invert: of those without one) and, with gather, those texts packed in
         `out` with their offsets."""
-        def symbols(t):
-            if self.sym_size in _SYM_DTYPE:
-                return self._symbols(t)
-            return np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t)
-        parts = [symbols(t).reshape(-1) for t in texts]
-        offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
-        if parts:
-            np.cumsum([p.size * p.itemsize // self.sym_size for p in parts], out=offsets[1:])
-        dtype = _SYM_DTYPE.get(self.sym_size, np.uint8)
-        packed = np.concatenate([p.view(dtype) for p in parts]) if parts else np.zeros(0, dtype)
+        packed, offsets = self._pack_texts(texts)
         return _grep_host_call(self.L.acm_grep, "acm_grep", self.handle, packed, self.sym_size, offsets, invert, gather, None)
 
     def grep_lines(self, buffer, delims=b"\n", runs=False, invert=False, gather=True):
@@ -1208,17 +1370,15 @@ class Machine:
         """acm_tally_batch(): which keywords occur how often in which text of a list of texts (bytes or
         arrays of symbols), each scanned from the root on its own in ONE call.  Returns a TalliedBatch
         of numpy arrays: the text x keyword count matrix in CSR form."""
-        def symbols(t):
-            if self.sym_size in _SYM_DTYPE:
-                return self._symbols(t)
-            return np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t)
-        parts = [symbols(t).reshape(-1) for t in texts]
-        offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
-        if parts:
-            np.cumsum([p.size * p.itemsize // self.sym_size for p in parts], out=offsets[1:])
-        dtype = _SYM_DTYPE.get(self.sym_size, np.uint8)
-        packed = np.concatenate([p.view(dtype) for p in parts]) if parts else np.zeros(0, dtype)
+        packed, offsets = self._pack_texts(texts)
         return _tally_batch_host_call(self.L.acm_tally_batch, "acm_tally_batch", self.handle, packed, self.sym_size, offsets)
+
+    def rules(self, texts, ruleset):
+        """acm_rules(): which rules of `ruleset` (a RuleSet, or a list of rule()s) fire in which text of
+        a list of texts, each scanned from the root on its own in ONE call.  Returns a Fired of numpy
+        arrays: the text x rule matrix in CSR form."""
+        packed, offsets = self._pack_texts(texts)
+        return _rules_host_call(self.L.acm_rules, "acm_rules", self.handle, packed, self.sym_size, offsets, ruleset)
 
 
 class Replaced:
@@ -1230,6 +1390,32 @@ class Replaced:
     def __init__(self, out, out_symbols, out_capacity, records, count, out_start):
         self.out, self.out_symbols, self.out_capacity = out, out_symbols, out_capacity
         self.records, self.count, self.out_start = records, count, out_start
+
+
+class Rules:
+    """A rule set on a plan's device (ACMRules): Plan.rules_create() makes one."""
+
+    def __init__(self, handle, n_rules):
+        self.h = handle
+        self.n_rules = n_rules
+
+    def info(self):
+        """acm_gpu_rules_info(): rules, terms, always_rules, postings and the texts the set's
+        evaluations sent through the fast and the wide form so far, as a dict; waits for the device."""
+        i = RulesInfo()
+        _check(lib().acm_gpu_rules_info(self.h, C.byref(i)), "acm_gpu_rules_info")
+        return {n: int(getattr(i, n)) for n, _ in RulesInfo._fields_}
+
+    def close(self):
+        if self.h:
+            lib().acm_gpu_rules_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Plan:
@@ -1616,6 +1802,102 @@ class Plan:
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         assert off.size >= 1, "offsets has n_texts + 1 entries"
         return _tally_batch_host_call(lib().acm_gpu_tally_batch_host, "acm_gpu_tally_batch_host", self.h, t, self.sym_size, off)
+
+    def rules_create(self, ruleset):
+        """acm_gpu_rules_create(): `ruleset` (a RuleSet, or a list of rule()s) compiled and uploaded to
+        this plan's device.  Returns a Rules; it stays valid across update()."""
+        rs = _ruleset(ruleset)
+        h = C.c_void_p()
+        _check(lib().acm_gpu_rules_create(self.h, *rs.args(), C.byref(h)), "acm_gpu_rules_create")
+        return Rules(h, rs.n_rules)
+
+    def _rules_handle(self, rules):
+        """(a Rules, whether this call made it) of a Rules, a RuleSet or a list of rule()s"""
+        return (rules, False) if isinstance(rules, Rules) else (self.rules_create(rules), True)
+
+    def _fired_outputs(self, dev, n_texts, fired_capacity):
+        import torch
+        fired_ptr = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
+        fired = torch.zeros(max(fired_capacity, 1), dtype=torch.int32, device=dev) if fired_capacity else None
+        return fired_ptr, fired
+
+    def rules(self, text, offsets, rules, window=None, capacity=None, pair_capacity=None, fired_capacity=None):
+        """acm_gpu_rules_device(): which rules fire in which text of a batch, on the device: the tally
+        of tally_batch() (same `text`, `offsets`, `window`, `capacity`, `pair_capacity`) and the
+        evaluation behind it in one call; neither a record nor the count matrix leaves the device.
+        `rules` is a Rules from rules_create() (or a RuleSet / a list of rule()s, compiled for this
+        call).  fired_capacity: the room of `fired` (0: count only; None: counted first, then sized by
+        the count).  Returns a Fired of device tensors; synchronises to read its four numbers."""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        window = int(window) if window is not None else 1 << 24
+        capacity = int(capacity) if capacity is not None else 1 << 20
+        pair_capacity = int(pair_capacity) if pair_capacity is not None else capacity
+        dev = text.device
+        R, own = self._rules_handle(rules)
+        res = torch.zeros(4, dtype=torch.int64, device=dev)                      # n_fired, total, need, need_pairs
+        tb = lib().acm_gpu_rules_tmp_bytes(self.h, R.h, window, capacity, pair_capacity, n_symbols, n_texts)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+
+        def call(cap):
+            fired_ptr, fired = self._fired_outputs(dev, n_texts, cap)
+            _check(lib().acm_gpu_rules_device(self.h, R.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity,
+                                              fired_ptr.data_ptr(), fired.data_ptr() if cap else None, cap, res.data_ptr(), res.data_ptr() + 8,
+                                              res.data_ptr() + 16, res.data_ptr() + 24, tmp.data_ptr(), tmp.numel(), self._stream()),
+                   "acm_gpu_rules_device")
+            n_fired, total, need, need_pairs = (int(x) for x in res.cpu())
+            return Fired(fired_ptr, fired, n_fired, total, need, need_pairs, cap)
+        try:
+            got = call(int(fired_capacity) if fired_capacity is not None else 0)
+            if fired_capacity is None and got.n_fired:
+                got = call(got.n_fired)
+            return got
+        finally:
+            if own:
+                R.close()
+
+    def rules_matrix(self, tallied, rules, fired_capacity=None):
+        """acm_gpu_rules_matrix_device(): the same for a count matrix that lies on the device: `tallied`
+        is a TalliedBatch of device tensors, tally_batch()'s or the caller's own (row_ptr int64 with
+        n_texts + 1 entries, col int32, val int64).  Returns a Fired of device tensors (total, need and
+        need_pairs None); synchronises to read n_fired."""
+        import torch
+        row_ptr, col, val = tallied.row_ptr, tallied.col, tallied.val
+        assert row_ptr.is_cuda and row_ptr.is_contiguous() and row_ptr.dtype == torch.int64
+        assert col.is_contiguous() and col.dtype == torch.int32 and val.is_contiguous() and val.dtype == torch.int64
+        n_texts = row_ptr.numel() - 1
+        assert n_texts >= 0
+        dev = row_ptr.device
+        R, own = self._rules_handle(rules)
+        res = torch.zeros(1, dtype=torch.int64, device=dev)
+        tb = lib().acm_gpu_rules_matrix_tmp_bytes(self.h, R.h, n_texts)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+
+        def call(cap):
+            fired_ptr, fired = self._fired_outputs(dev, n_texts, cap)
+            _check(lib().acm_gpu_rules_matrix_device(self.h, R.h, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), n_texts, fired_ptr.data_ptr(),
+                                                     fired.data_ptr() if cap else None, cap, res.data_ptr(), tmp.data_ptr(), tmp.numel(),
+                                                     self._stream()), "acm_gpu_rules_matrix_device")
+            return Fired(fired_ptr, fired, int(res.item()), fired_capacity=cap)
+        try:
+            got = call(int(fired_capacity) if fired_capacity is not None else 0)
+            if fired_capacity is None and got.n_fired:
+                got = call(got.n_fired)
+            return got
+        finally:
+            if own:
+                R.close()
+
+    def rules_host(self, text, offsets, ruleset):
+        """acm_gpu_rules_host(): the same as rules() from host arrays, through the C ABI only (no torch).
+        The call sizes its windows and its pair room itself.  Returns a Fired of numpy arrays."""
+        t = np.ascontiguousarray(text)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        return _rules_host_call(lib().acm_gpu_rules_host, "acm_gpu_rules_host", self.h, t, self.sym_size, off, ruleset)
 
     @property
     def select_form(self):

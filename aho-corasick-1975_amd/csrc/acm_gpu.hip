@@ -34,6 +34,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -4611,6 +4612,363 @@ acm_gpu_tally_batch_host (ACMPlan *plan, const void *text, const uint64_t *offse
   return ACM_GPU_OK;
 }
 
+/* ------------------------------------------------------------------ keyword rules per text (include/acm_gpu.h, dev_rules.h)
+ * A rule set compiled into an index inverted by keyword, and the passes that evaluate it on a count
+ * matrix on the device; acm_gpu_rules_device runs them behind acm_gpu_tally_batch_device. */
+struct ACMRules {
+  int device = 0;
+  uint64_t n_rules = 0, n_terms = 0;
+  uint32_t n_keywords = 0, n_always = 0, n_postings = 0;
+  void *blob = nullptr; /* one allocation: the arrays below, then the two form counters */
+  uint32_t *d_post_ptr = nullptr, *d_base = nullptr, *d_need = nullptr, *d_always = nullptr;
+  RulePost *d_post = nullptr;
+  unsigned long long *d_forms = nullptr;
+};
+
+namespace {
+struct RulesLayout {
+  uint32_t wide_p2 = 1;
+  size_t o_ctl = 0, o_cnt = 0, zero_bytes = 0, o_ptr = 0, o_wide = 0, o_cub = 0, cub_bytes = 0, o_wkey = 0, o_wd = 0, total = 0;
+};
+RulesLayout
+rules_layout (const ACMRules *rules, uint64_t n_texts) {
+  RulesLayout L;
+  while (L.wide_p2 < rules->n_postings)
+    L.wide_p2 <<= 1;
+  L.cub_bytes = exclusive_sum_bytes64 (n_texts + 1);
+  size_t cur = 0;
+  L.o_ctl = blob_reserve (cur, sizeof (RulesCtl));
+  L.o_cnt = blob_reserve (cur, (n_texts + 1) * 8);
+  L.zero_bytes = cur; /* control words and the rows' counts: cleared in front of every call */
+  L.o_ptr = blob_reserve (cur, (n_texts + 1) * 8);
+  L.o_wide = blob_reserve (cur, (n_texts + 1) * 4);
+  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
+  L.o_wkey = blob_reserve (cur, (size_t)RULES_WIDE_BLOCKS * L.wide_p2 * 4);
+  L.o_wd = blob_reserve (cur, (size_t)RULES_WIDE_BLOCKS * ((size_t)rules->n_postings + 1) * 4);
+  L.total = cur + 256;
+  return L;
+}
+
+/* ACM_GPU_RULES_ITEMS=<1 to 4,096>: the widest text, in items, of the fast form (tests, experiments;
+ * read at every call) */
+uint32_t
+rules_items (void) {
+  const int r = env_int ("ACM_GPU_RULES_ITEMS", (int)RULES_ITEMS_DEFAULT);
+  return r >= 1 && r <= (int)RULES_ITEMS_MAX ? (uint32_t)r : RULES_ITEMS_DEFAULT;
+}
+
+/* the matrix calls' own arguments: the set is this plan's device's, the outputs are there */
+bool
+rules_args_ok (const ACMPlan *plan, const ACMRules *rules, uint64_t n_texts, const uint64_t *d_fired_ptr, const uint32_t *d_fired, uint64_t fired_capacity,
+               const uint64_t *d_n_fired) {
+  return plan && rules && rules->device == plan->device && n_texts < (1ull << 31) && d_fired_ptr && d_n_fired && (d_fired || fired_capacity == 0);
+}
+
+/* the passes of dev_rules.h on a matrix on the device; `tb`: the control words of the tally_batch
+ * queued in front, whose stopping stops this call too (nullptr: a caller's matrix) */
+int
+rules_evaluate (ACMPlan *plan, const ACMRules *rules, const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_val, uint64_t n_texts,
+                uint64_t *d_fired_ptr, uint32_t *d_fired, uint64_t fired_capacity, uint64_t *d_n_fired, void *d_tmp, hipStream_t st, const TbCtl *tb,
+                uint64_t tb_capacity, uint64_t tb_pair_capacity) {
+  const RulesLayout L = rules_layout (rules, n_texts);
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  RulesK K{};
+  K.row_ptr = reinterpret_cast<const unsigned long long *> (d_row_ptr);
+  K.col = d_col;
+  K.val = reinterpret_cast<const unsigned long long *> (d_val);
+  K.n_texts = n_texts;
+  K.post_ptr = rules->d_post_ptr;
+  K.post = rules->d_post;
+  K.base = rules->d_base;
+  K.need = rules->d_need;
+  K.always = rules->d_always;
+  K.n_keywords = rules->n_keywords;
+  K.n_always = rules->n_always;
+  K.n_postings = rules->n_postings;
+  K.forms = rules->d_forms;
+  K.items = rules_items ();
+  K.items_p2 = 1;
+  while (K.items_p2 < K.items)
+    K.items_p2 <<= 1;
+  K.wide_p2 = L.wide_p2;
+  K.cnt = reinterpret_cast<unsigned long long *> (t + L.o_cnt);
+  K.ptr = reinterpret_cast<const unsigned long long *> (t + L.o_ptr);
+  K.wide = reinterpret_cast<uint32_t *> (t + L.o_wide);
+  K.wkey = reinterpret_cast<uint32_t *> (t + L.o_wkey);
+  K.wd = reinterpret_cast<int32_t *> (t + L.o_wd);
+  K.ctl = reinterpret_cast<RulesCtl *> (t + L.o_ctl);
+  K.tb = tb;
+  K.tb_capacity = tb_capacity;
+  K.tb_pair_capacity = tb_pair_capacity;
+  K.d_fired_ptr = reinterpret_cast<unsigned long long *> (d_fired_ptr);
+  K.d_n_fired = reinterpret_cast<unsigned long long *> (d_n_fired);
+  K.d_fired = d_fired;
+  K.fired_capacity = fired_capacity;
+  K.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (t, 0, L.zero_bytes, st));
+  const dim3 flat_grid = capped_grid (plan, (n_texts + 1 + 255) / 256);
+  const dim3 fast_grid = capped_grid (plan, n_texts, RULES_FAST_PER_CU);
+  const size_t fast_lds = (size_t)K.items_p2 * 4 + ((size_t)K.items + 1) * 4;
+  /* 1. */
+  hipLaunchKernelGGL (rules_check_kernel, flat_grid, dim3 (256), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  /* 2. */
+  hipLaunchKernelGGL (rules_fast_kernel<false>, fast_grid, dim3 (WAVE), fast_lds, st, K);
+  HIP_TRY (hipGetLastError ());
+  hipLaunchKernelGGL (rules_wide_kernel<false>, dim3 (RULES_WIDE_BLOCKS), dim3 (RULES_WIDE_THREADS), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  /* 3. */
+  size_t cub = L.cub_bytes;
+  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_cnt), reinterpret_cast<long long *> (t + L.o_ptr),
+                                             (int)(n_texts + 1), st));
+  hipLaunchKernelGGL (rules_finish_kernel, flat_grid, dim3 (256), 0, st, K);
+  HIP_TRY (hipGetLastError ());
+  /* 4. */
+  if (d_fired) {
+    hipLaunchKernelGGL (rules_fast_kernel<true>, fast_grid, dim3 (WAVE), fast_lds, st, K);
+    HIP_TRY (hipGetLastError ());
+    hipLaunchKernelGGL (rules_wide_kernel<true>, dim3 (RULES_WIDE_BLOCKS), dim3 (RULES_WIDE_THREADS), 0, st, K);
+    HIP_TRY (hipGetLastError ());
+  }
+  return ACM_GPU_OK;
+}
+
+/* where acm_gpu_rules_device keeps the count matrix and tally_batch's scratch inside its own */
+struct RulesCallLayout {
+  size_t o_row_ptr = 0, o_col = 0, o_val = 0, o_nnz = 0, o_tally = 0, tally_bytes = 0, total = 0;
+};
+RulesCallLayout
+rules_call_layout (const ACMPlan *plan, const ACMRules *rules, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts) {
+  RulesCallLayout L;
+  size_t cur = rules_layout (rules, n_texts).total;
+  L.o_row_ptr = blob_reserve (cur, (n_texts + 1) * 8);
+  L.o_col = blob_reserve (cur, (size_t)pair_capacity * 4);
+  L.o_val = blob_reserve (cur, (size_t)pair_capacity * 8);
+  L.o_nnz = blob_reserve (cur, 8);
+  L.tally_bytes = tally_batch_layout (plan, capacity, pair_capacity, n_symbols, n_texts).total;
+  L.o_tally = blob_reserve (cur, L.tally_bytes);
+  L.total = cur + 256;
+  return L;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_rules_create (ACMPlan *plan, const ACMRuleTerm *terms, const uint64_t *rule_ptr, const uint32_t *need, uint64_t n_rules, ACMRules **out) {
+  if (!plan || !out)
+    return ACM_GPU_E_ARG;
+  const uint64_t nk = plan->covered_keywords;
+  if (acm_rules_check (terms, rule_ptr, need, n_rules, nk) || rule_ptr[n_rules] >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_terms = rule_ptr[n_rules];
+  /* the index: a counting sort of the terms by keyword, rules ascending within a keyword */
+  std::vector<uint32_t> post_ptr (nk + 2, 0), base (n_rules ? n_rules : 1, 0), always;
+  auto posted = [] (const ACMRuleTerm &q) { return !(q.lo == 0 && q.hi == ACM_RULE_NO_MAX); }; /* (holds at every count: base alone) */
+  for (uint64_t i = 0; i < n_terms; i++)
+    if (posted (terms[i]))
+      post_ptr[terms[i].keyword_id + 2]++;
+  for (uint64_t k = 2; k < nk + 2; k++)
+    post_ptr[k] += post_ptr[k - 1];
+  const uint32_t n_postings = post_ptr[nk + 1];
+  std::vector<RulePost> post (n_postings ? n_postings : 1);
+  for (uint64_t r = 0; r < n_rules; r++) {
+    for (uint64_t i = rule_ptr[r]; i < rule_ptr[r + 1]; i++) {
+      const ACMRuleTerm &q = terms[i];
+      base[r] += q.lo == 0;
+      if (posted (q))
+        post[post_ptr[q.keyword_id + 1]++] = RulePost{ (uint32_t)r, q.lo, q.hi };
+    }
+    if (base[r] >= need[r])
+      always.push_back ((uint32_t)r);
+  } /* (post_ptr[k + 1] has moved on to the end of k's postings: post_ptr[0 .. nk] are the row pointers now) */
+  HIP_TRY (hipSetDevice (plan->device));
+  ACMRules *R = new (std::nothrow) ACMRules ();
+  if (!R)
+    return ACM_GPU_E_NOMEM;
+  R->device = plan->device;
+  R->n_rules = n_rules;
+  R->n_terms = n_terms;
+  R->n_keywords = (uint32_t)nk;
+  R->n_always = (uint32_t)always.size ();
+  R->n_postings = n_postings;
+  size_t cur = 0;
+  const size_t o_post_ptr = blob_reserve (cur, (nk + 1) * 4), o_post = blob_reserve (cur, post.size () * sizeof (RulePost)),
+               o_base = blob_reserve (cur, base.size () * 4), o_need = blob_reserve (cur, base.size () * 4),
+               o_always = blob_reserve (cur, (always.size () + 1) * 4), o_forms = blob_reserve (cur, 16);
+  bool ok = hipMalloc (&R->blob, cur) == hipSuccess;
+  unsigned char *b = static_cast<unsigned char *> (R->blob);
+  ok = ok && hipMemset (b, 0, cur) == hipSuccess && hipMemcpy (b + o_post_ptr, post_ptr.data (), (nk + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_post, post.data (), post.size () * sizeof (RulePost), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_base, base.data (), base.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
+       (!n_rules || hipMemcpy (b + o_need, need, n_rules * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+       (always.empty () || hipMemcpy (b + o_always, always.data (), always.size () * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+       hipDeviceSynchronize () == hipSuccess;
+  if (!ok) {
+    acm_gpu_rules_destroy (R);
+    return ACM_GPU_E_NOMEM;
+  }
+  R->d_post_ptr = reinterpret_cast<uint32_t *> (b + o_post_ptr);
+  R->d_post = reinterpret_cast<RulePost *> (b + o_post);
+  R->d_base = reinterpret_cast<uint32_t *> (b + o_base);
+  R->d_need = reinterpret_cast<uint32_t *> (b + o_need);
+  R->d_always = reinterpret_cast<uint32_t *> (b + o_always);
+  R->d_forms = reinterpret_cast<unsigned long long *> (b + o_forms);
+  *out = R;
+  return ACM_GPU_OK;
+}
+
+extern "C" void
+acm_gpu_rules_destroy (ACMRules *rules) {
+  if (!rules)
+    return;
+  (void)hipSetDevice (rules->device);
+  if (rules->blob)
+    (void)hipFree (rules->blob);
+  delete rules;
+}
+
+extern "C" int
+acm_gpu_rules_info (const ACMRules *rules, ACMRulesInfo *info) {
+  if (!rules || !info)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (rules->device));
+  HIP_TRY (hipDeviceSynchronize ());
+  unsigned long long forms[2] = { 0, 0 };
+  HIP_TRY (hipMemcpy (forms, rules->d_forms, sizeof forms, hipMemcpyDeviceToHost));
+  *info = ACMRulesInfo{ rules->n_rules, rules->n_terms, rules->n_always, rules->n_postings, forms[0], forms[1] };
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_rules_matrix_tmp_bytes (const ACMPlan *plan, const ACMRules *rules, uint64_t n_texts) {
+  if (!plan || !rules || n_texts >= (1ull << 31))
+    return 0;
+  return rules_layout (rules, n_texts).total;
+}
+
+extern "C" int
+acm_gpu_rules_matrix_device (ACMPlan *plan, const ACMRules *rules, const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_val,
+                             uint64_t n_texts, uint64_t *d_fired_ptr, uint32_t *d_fired, uint64_t fired_capacity, uint64_t *d_n_fired, void *d_tmp,
+                             size_t tmp_bytes, void *stream) {
+  if (!rules_args_ok (plan, rules, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0) { /* no text: an empty matrix */
+    HIP_TRY (hipMemsetAsync (d_fired_ptr, 0, 8, st));
+    HIP_TRY (hipMemsetAsync (d_n_fired, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  if (!d_row_ptr || !d_tmp || tmp_bytes < rules_layout (rules, n_texts).total)
+    return ACM_GPU_E_ARG;
+  return rules_evaluate (plan, rules, d_row_ptr, d_col, d_val, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired, d_tmp, st, nullptr, 0, 0);
+}
+
+extern "C" size_t
+acm_gpu_rules_tmp_bytes (const ACMPlan *plan, const ACMRules *rules, uint64_t window_symbols, uint64_t capacity, uint64_t pair_capacity,
+                         uint64_t n_symbols, uint64_t n_texts) {
+  if (!rules || !acm_gpu_tally_batch_tmp_bytes (plan, window_symbols, capacity, pair_capacity, n_symbols, n_texts))
+    return 0;
+  return rules_call_layout (plan, rules, capacity, pair_capacity, n_symbols, n_texts).total;
+}
+
+extern "C" int
+acm_gpu_rules_device (ACMPlan *plan, const ACMRules *rules, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts,
+                      uint64_t window_symbols, uint64_t capacity, uint64_t pair_capacity, uint64_t *d_fired_ptr, uint32_t *d_fired,
+                      uint64_t fired_capacity, uint64_t *d_n_fired, uint64_t *d_total, uint64_t *d_need, uint64_t *d_need_pairs, void *d_tmp,
+                      size_t tmp_bytes, void *stream) {
+  if (!rules_args_ok (plan, rules, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired) || !d_tmp || capacity == 0 || capacity >= (1ull << 31) ||
+      pair_capacity == 0 || pair_capacity >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  const RulesCallLayout L = rules_call_layout (plan, rules, capacity, pair_capacity, n_symbols, n_texts);
+  if (tmp_bytes < L.total)
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  uint64_t *d_row_ptr = reinterpret_cast<uint64_t *> (t + L.o_row_ptr), *d_val = reinterpret_cast<uint64_t *> (t + L.o_val),
+           *d_nnz = reinterpret_cast<uint64_t *> (t + L.o_nnz);
+  uint32_t *d_col = reinterpret_cast<uint32_t *> (t + L.o_col);
+  /* (the remaining arguments are tally_batch's to check) */
+  if (const int rc = acm_gpu_tally_batch_device (plan, d_text, n_symbols, d_offsets, n_texts, window_symbols, capacity, pair_capacity, d_row_ptr, d_col,
+                                                 d_val, d_nnz, d_total, d_need, d_need_pairs, t + L.o_tally, L.tally_bytes, stream))
+    return rc;
+  if (n_texts == 0) {
+    HIP_TRY (hipMemsetAsync (d_fired_ptr, 0, 8, st));
+    HIP_TRY (hipMemsetAsync (d_n_fired, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  /* tally_batch's control words lie at the head of its scratch */
+  const TbCtl *tb = reinterpret_cast<const TbCtl *> (t + L.o_tally + tally_batch_layout (plan, capacity, pair_capacity, n_symbols, n_texts).o_ctl);
+  return rules_evaluate (plan, rules, d_row_ptr, d_col, d_val, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired, d_tmp, st, tb, capacity,
+                         pair_capacity);
+}
+
+extern "C" int
+acm_gpu_rules_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, const ACMRuleTerm *terms, const uint64_t *rule_ptr,
+                    const uint32_t *need, uint64_t n_rules, uint64_t *fired_ptr, uint32_t *fired, uint64_t fired_capacity, uint64_t *n_fired,
+                    uint64_t *total) {
+  if (!plan || !fired_ptr || !n_fired || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
+    return ACM_GPU_E_ARG;
+  ACMRules *made = nullptr;
+  if (const int rc = acm_gpu_rules_create (plan, terms, rule_ptr, need, n_rules, &made))
+    return rc;
+  std::unique_ptr<ACMRules, void (*) (ACMRules *)> rules (made, acm_gpu_rules_destroy);
+  const uint64_t n_symbols = offsets[n_texts];
+  /* the rooms: acm_gpu_tally_batch_host's */
+  RecordRoom room = tally_room (plan, n_symbols);
+  uint64_t pair_capacity = std::max<uint64_t> (room.capacity, 1ull << 16);
+  const uint64_t most = n_symbols < (1ull << 31) / tally_max_outputs (plan) ? n_symbols * tally_max_outputs (plan) : 1ull << 31;
+  if (most < pair_capacity)
+    pair_capacity = most ? most : 1;
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_off = nullptr, *d_fired_ptr = nullptr, *d_res = nullptr; /* d_res: n_fired, total, need, need_pairs */
+  uint32_t *d_fired = nullptr;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  HOST_TRY (temps.get (&d_fired_ptr, (n_texts + 1) * 8));
+  HOST_TRY (temps.get (&d_res, 32));
+  if (fired && fired_capacity)
+    HOST_TRY (temps.get (&d_fired, (size_t)fired_capacity * 4));
+  const uint64_t d_capacity = d_fired ? fired_capacity : 0;
+  uint64_t res[4] = { 0, 0, 0, 0 };
+  bool again_pairs = false;
+  for (;;) {
+    const size_t tmp_bytes = acm_gpu_rules_tmp_bytes (plan, rules.get (), room.window, room.capacity, pair_capacity, n_symbols, n_texts);
+    HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+    if (const int rc = settle (plan, acm_gpu_rules_device (plan, rules.get (), d_text, n_symbols, d_off, n_texts, room.window, room.capacity, pair_capacity,
+                                                           d_fired_ptr, d_fired, d_capacity, d_res, d_res + 1, d_res + 2, d_res + 3, d_tmp, tmp_bytes,
+                                                           nullptr),
+                               true))
+      return rc;
+    HOST_TRY (hipMemcpy (res, d_res, 32, hipMemcpyDeviceToHost));
+    if (res[2] <= room.capacity && res[3] <= pair_capacity)
+      break;
+    HOST_TRY (temps.release (d_tmp)); /* (the next attempt's is another size) */
+    if (res[2] > room.capacity) {
+      if (!tally_room_shrink (plan, &room))
+        return ACM_GPU_E_INTERNAL;
+    } else {
+      if (again_pairs) /* (the kept records cannot be exceeded: never expected) */
+        return ACM_GPU_E_INTERNAL;
+      if (res[3] >= (1ull << 31)) /* more partial pairs than one call holds */
+        return ACM_GPU_E_NOMEM;
+      again_pairs = true;
+      pair_capacity = res[3];
+    }
+  }
+  HOST_TRY (hipMemcpy (fired_ptr, d_fired_ptr, (n_texts + 1) * 8, hipMemcpyDeviceToHost));
+  *n_fired = res[0];
+  if (total)
+    *total = res[1];
+  if (!fired) /* the call only counts */
+    return ACM_GPU_OK;
+  if (res[0] > fired_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (res[0])
+    HOST_TRY (hipMemcpy (fired, d_fired, res[0] * 4, hipMemcpyDeviceToHost));
+  return ACM_GPU_OK;
+}
+
 /* ------------------------------------------------------------------ leftmost-longest selection (include/acm_gpu.h, dev_select.h)
  * The passes over a record set in canonical order; acm_gpu_scan_select_device runs them behind the
  * ordered scan. */
@@ -6106,7 +6464,7 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally only a scan that
  * succeeded, acm_select, acm_scan_words and acm_scan_from also one that found more records than there was room for,
- * acm_replace, acm_tokenize, acm_grep, acm_grep_lines and acm_tally_batch also one whose output had no room. */
+ * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch and acm_rules also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -6132,7 +6490,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The eleven calls below run on the same route, the same cached plan, under the same lock. */
+/* The twelve calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -6268,6 +6626,23 @@ acm_tally_batch (ACMachine *machine, const void *text, const uint64_t *offsets, 
     machine, RecordPath::OnSuccessOrOverflow,
     [&] (uint32_t said) { return acm_internal_cpu_tally_batch (machine, text, offsets, n_texts, said, row_ptr, col, val, nnz_capacity, nnz, total); },
     [&] (ACMPlan *plan) { return acm_gpu_tally_batch_host (plan, text, offsets, n_texts, row_ptr, col, val, nnz_capacity, nnz, total); });
+}
+
+/* keyword rules per text of a batch (include/acm_gpu.h) */
+extern "C" int
+acm_rules (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, const ACMRuleTerm *terms, const uint64_t *rule_ptr,
+           const uint32_t *need, uint64_t n_rules, uint64_t *fired_ptr, uint32_t *fired, uint64_t fired_capacity, uint64_t *n_fired, uint64_t *total) {
+  if (!machine || !fired_ptr || !n_fired || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      return acm_internal_cpu_rules (machine, text, offsets, n_texts, said, terms, rule_ptr, need, n_rules, fired_ptr, fired, fired_capacity, n_fired,
+                                     total);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_rules_host (plan, text, offsets, n_texts, terms, rule_ptr, need, n_rules, fired_ptr, fired, fired_capacity, n_fired, total);
+    });
 }
 
 /* acm_scan continued from a cursor (include/acm_gpu.h): the reference's own `const ACState *`, in

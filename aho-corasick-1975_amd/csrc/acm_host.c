@@ -1014,6 +1014,86 @@ acm_tally_batch_records (const ACMRecord *records, const uint64_t *first, uint64
   return rc;
 }
 
+/* The argument checks of a rule set (include/acm_gpu.h) */
+int
+acm_rules_check (const ACMRuleTerm *terms, const uint64_t *rule_ptr, const uint32_t *need, uint64_t n_rules, uint64_t n_keywords) {
+  if (!rule_ptr || rule_ptr[0] != 0 || n_rules >= (1ull << 31) || (n_rules && (!terms || !need)))
+    return ACM_GPU_E_ARG;
+  for (uint64_t r = 0; r < n_rules; r++) {
+    if (rule_ptr[r] >= rule_ptr[r + 1]) /* decreasing, or a rule without terms */
+      return ACM_GPU_E_ARG;
+    if (need[r] == 0 || need[r] > rule_ptr[r + 1] - rule_ptr[r])
+      return ACM_GPU_E_ARG;
+  }
+  for (uint64_t i = 0; i < rule_ptr[n_rules]; i++)
+    if (terms[i].keyword_id >= n_keywords || terms[i].lo > terms[i].hi)
+      return ACM_GPU_E_ARG;
+  return ACM_GPU_OK;
+}
+
+/* whether a term holds at count c */
+static int
+rule_term_holds (const ACMRuleTerm *term, uint64_t c) {
+  return c >= term->lo && (term->hi == ACM_RULE_NO_MAX || c <= term->hi);
+}
+
+/* The text x rule matrix of a count matrix in CSR form (include/acm_gpu.h): the plain sequential
+ * evaluation.  A row is spread into count[] (and taken back out), every rule looks its terms up
+ * there; the first walk counts, so that nothing is written to `fired` when it has no room. */
+int
+acm_rules_matrix (const uint64_t *row_ptr, const uint32_t *col, const uint64_t *val, uint64_t n_texts, uint64_t n_keywords, const ACMRuleTerm *terms,
+                  const uint64_t *rule_ptr, const uint32_t *need, uint64_t n_rules, uint64_t *fired_ptr, uint32_t *fired, uint64_t fired_capacity,
+                  uint64_t *n_fired) {
+  if (!row_ptr || row_ptr[0] != 0 || !fired_ptr || !n_fired || n_texts >= (1ull << 31) || n_keywords >= (1ull << 32))
+    return ACM_GPU_E_ARG;
+  if (acm_rules_check (terms, rule_ptr, need, n_rules, n_keywords))
+    return ACM_GPU_E_ARG;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (row_ptr[t] > row_ptr[t + 1])
+      return ACM_GPU_E_ARG;
+  const uint64_t nnz = row_ptr[n_texts];
+  if (nnz && (!col || !val))
+    return ACM_GPU_E_ARG;
+  for (uint64_t e = 0; e < nnz; e++)
+    if (col[e] >= n_keywords)
+      return ACM_GPU_E_ARG;
+  uint64_t *count = calloc (n_keywords ? n_keywords : 1, sizeof (uint64_t));
+  if (!count)
+    return ACM_GPU_E_NOMEM;
+  int rc = ACM_GPU_OK;
+  for (int fill = 0; fill < 2 && !rc; fill++) {
+    uint64_t all = 0;
+    for (uint64_t t = 0; t < n_texts; t++) {
+      if (!fill)
+        fired_ptr[t] = all;
+      for (uint64_t e = row_ptr[t]; e < row_ptr[t + 1]; e++)
+        count[col[e]] += val[e];
+      for (uint64_t r = 0; r < n_rules; r++) {
+        uint64_t held = 0;
+        for (uint64_t i = rule_ptr[r]; i < rule_ptr[r + 1]; i++)
+          held += (uint64_t)rule_term_holds (&terms[i], count[terms[i].keyword_id]);
+        if (held >= need[r]) {
+          if (fill)
+            fired[all] = (uint32_t)r;
+          all++;
+        }
+      }
+      for (uint64_t e = row_ptr[t]; e < row_ptr[t + 1]; e++)
+        count[col[e]] = 0;
+    }
+    if (!fill) {
+      fired_ptr[n_texts] = all;
+      *n_fired = all;
+      if (!fired)
+        break; /* the call only counts */
+      if (all > fired_capacity)
+        rc = ACM_GPU_E_OVERFLOW;
+    }
+  }
+  free (count);
+  return rc;
+}
+
 /* SELECT of records in canonical order (include/acm_gpu.h), in place in the front of the array: the
  * plain sequential greedy pass.  The order is by end and the rule goes by start, so a round looks
  * at a window: from the first record that ends at or behind p up to the first that ends lmax or
@@ -1417,5 +1497,42 @@ acm_internal_cpu_tally_batch (ACMachine *m, const void *text, const uint64_t *of
   }
   free (records);
   free (first);
+  return rc;
+}
+
+/* the loop and the count matrix as above, into a room grown to what the matrix needs, then the sequential evaluation */
+int
+acm_internal_cpu_rules (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, const ACMRuleTerm *terms,
+                        const uint64_t *rule_ptr, const uint32_t *need, uint64_t n_rules, uint64_t *fired_ptr, uint32_t *fired, uint64_t fired_capacity,
+                        uint64_t *n_fired, uint64_t *total) {
+  if (!m || !offsets || !fired_ptr || !n_fired)
+    return ACM_GPU_E_ARG;
+  const uint64_t n_keywords = acm_nb_keywords (m);
+  if (acm_rules_check (terms, rule_ptr, need, n_rules, n_keywords))
+    return ACM_GPU_E_ARG;
+  uint64_t *row_ptr = malloc ((n_texts + 1) * sizeof (uint64_t));
+  uint32_t *col = NULL;
+  uint64_t *val = NULL, room = 1024, nnz = 0;
+  int rc = row_ptr ? ACM_GPU_OK : ACM_GPU_E_NOMEM;
+  for (int attempt = 0; !rc && attempt < 2; attempt++) {
+    col = malloc (room * sizeof (uint32_t));
+    val = malloc (room * sizeof (uint64_t));
+    rc = col && val ? acm_internal_cpu_tally_batch (m, text, offsets, n_texts, sym_bytes, row_ptr, col, val, room, &nnz, total) : ACM_GPU_E_NOMEM;
+    if (rc != ACM_GPU_E_OVERFLOW || attempt)
+      break;
+    free (col);
+    free (val);
+    col = NULL;
+    val = NULL;
+    room = nnz;
+    rc = ACM_GPU_OK;
+  }
+  if (rc == ACM_GPU_E_OVERFLOW) /* (the second room is what the first attempt asked for: never expected) */
+    rc = ACM_GPU_E_INTERNAL;
+  if (!rc)
+    rc = acm_rules_matrix (row_ptr, col, val, n_texts, n_keywords, terms, rule_ptr, need, n_rules, fired_ptr, fired, fired_capacity, n_fired);
+  free (val);
+  free (col);
+  free (row_ptr);
   return rc;
 }

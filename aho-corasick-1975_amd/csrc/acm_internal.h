@@ -82,6 +82,10 @@ int acm_internal_cpu_grep (ACMachine *m, const void *text, const uint64_t *offse
                            uint64_t *out_symbols);
 int acm_internal_cpu_tally_batch (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint64_t *row_ptr,
                                   uint32_t *col, uint64_t *val, uint64_t nnz_capacity, uint64_t *nnz, uint64_t *total);
+/* acm_rules' host path: acm_internal_cpu_tally_batch into a room of the call's own, then acm_rules_matrix (arguments as acm_rules') */
+int acm_internal_cpu_rules (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, const ACMRuleTerm *terms,
+                            const uint64_t *rule_ptr, const uint32_t *need, uint64_t n_rules, uint64_t *fired_ptr, uint32_t *fired,
+                            uint64_t fired_capacity, uint64_t *n_fired, uint64_t *total);
 /* acm_grep_lines' host path: acm_split_offsets, then acm_internal_cpu_grep (arguments as acm_grep_lines') */
 int acm_internal_cpu_grep_lines (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *delims, uint32_t n_delims,
                                  uint32_t split_flags, uint32_t grep_flags, uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out,

@@ -167,6 +167,7 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_tokens.h"
 #include "dev_grep.h"
 #include "dev_tally_batch.h"
+#include "dev_rules.h"
 #include "dev_split.h"
 #include "dev_words.h"
 

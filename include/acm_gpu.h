@@ -966,6 +966,134 @@ int acm_tally_batch (ACMachine *machine, const void *text, const uint64_t *offse
                      uint64_t *row_ptr, uint32_t *col, uint64_t *val, uint64_t nnz_capacity,
                      uint64_t *nnz, uint64_t *total);
 
+/* ------------------------------------------------------------------ keyword rules per text
+ * The count matrix above says which keywords a text holds.  A signature of an IDS, a YARA rule or a
+ * log classifier is a COMBINATION of keywords: "A and B", "A but not B", "any two of these five",
+ * "A at least three times".  These calls evaluate a set of such rules on every text of a batch, on
+ * the device, behind the tally: which rules fired in which text, so that the stage that decides
+ * which texts the next stage sees needs no copy of the matrix to the host.
+ *
+ * DEFINITION.  C[t][k] is acm_tally_batch's matrix; the batch contract, the offsets contract and
+ * empty texts are the same as there.
+ *   A TERM is (keyword_id, lo, hi), three uint32_t (ACMRuleTerm).  It HOLDS for text t iff
+ *     lo <= C[t][keyword_id] <= hi; hi = ACM_RULE_NO_MAX (0xFFFFFFFF) is no upper bound: a count
+ *     above 2^32 still holds such a term.  (k, 1, NO_MAX) is "k present", (k, 0, 0) "k absent",
+ *     (k, 3, NO_MAX) "k at least three times", (k, 2, 3) an interval; (k, 0, NO_MAX) always holds and
+ *     is allowed.  lo > hi is ACM_GPU_E_ARG.
+ *   A RULE r is the terms [rule_ptr[r], rule_ptr[r + 1]) of terms[] (rule_ptr: uint64_t, n_rules + 1
+ *     entries) and need[r] (uint32_t).  It FIRES for t iff at least need[r] of its terms hold:
+ *     need = the number of terms is AND, need = 1 is OR, anything between is "m of n".  One keyword
+ *     may occur in several terms of one rule (two disjoint intervals).  ACM_GPU_E_ARG: a rule without
+ *     terms, need[r] = 0, need[r] above the rule's number of terms, a rule_ptr that decreases or does
+ *     not begin with 0, a keyword_id >= n_keywords, n_rules >= 2^31.
+ *   The RESULT is the text x rule boolean matrix in CSR form: fired_ptr[0 .. n_texts] (uint64_t,
+ *     fired_ptr[0] = 0), row t is the rule ids fired[fired_ptr[t] .. fired_ptr[t + 1]) (uint32_t,
+ *     strictly ascending); n_fired = fired_ptr[n_texts].  Outputs are SET, not added to.
+ * A rule whose terms that hold at count 0 already reach `need` fires on a text with no keyword at
+ * all, an empty text among them: "absent he" fires on "".
+ * Keyword ids are first-insertion ranks, so a rule set stays valid when the dictionary grows
+ * (acm_gpu_plan_update); keywords added later occur in no rule.
+ *
+ * acm_rules_check: the argument checks above, no device; every other entry point runs it.
+ * acm_rules_matrix: the plain sequential evaluation of a given count matrix (row_ptr, col, val as
+ * acm_tally_batch gives them) on the host.  ACM_GPU_E_OVERFLOW with *n_fired = the entries needed
+ * when fired_capacity is too small: `fired` is untouched then, fired_ptr is written all the same.
+ * `fired` may be NULL: the call only counts and returns ACM_GPU_OK.  A row_ptr that decreases or
+ * does not begin with 0 and a col >= n_keywords are ACM_GPU_E_ARG (acm_tally_batch_records' rule).
+ *
+ * acm_gpu_rules_create: a rule set is compiled once, on the host, into an index inverted by keyword
+ * and uploaded to the plan's device: post_ptr[n_keywords + 1], the postings (rule, lo, hi) of every
+ * keyword (a term that holds at every count has none: it only counts into base), base[r] = the
+ * number of r's terms that hold at count 0, need[r], and the ascending list of the ALWAYS-RULES,
+ * those with base[r] >= need[r].  n_keywords is acm_gpu_tally_keywords (plan) at creation; the set
+ * belongs to the plan's device and serves that plan, also after acm_gpu_plan_update.  2^31 terms
+ * or more are ACM_GPU_E_ARG.  acm_gpu_rules_info waits for the device and reports the sizes
+ * and how many texts the set's evaluations have sent through the fast and through the wide form
+ * since creation (below).
+ *
+ * acm_gpu_rules_matrix_device: the evaluation of ANY count matrix that lies on the device,
+ * acm_gpu_tally_batch_device's or a caller's own (rows ascending by keyword id without repeats).
+ * One wave takes one text (dev_rules.h): every posting of every keyword of the row whose holding
+ * differs from holding at count 0 is an item (rule, +1 / -1); the items are sorted by rule in the
+ * wave's LDS and summed per rule; rule r fires iff base[r] + sum >= need[r]; the sorted touched
+ * rules are merged with the always-list.  A text with more items than the fast form has room for
+ * is taken by a block that sorts in scratch (the wide form: slower, always correct).  A count pass
+ * fills d_fired_ptr, a fill pass d_fired: work per text goes by the postings of the row's keywords
+ * and the always-list, no memory is sized n_texts x n_rules.  Outputs, all device memory, valid when
+ * `stream` has passed:
+ *     *d_n_fired <= fired_capacity:  every output is complete.
+ *     *d_n_fired > fired_capacity:  it is the capacity needed; d_fired_ptr is complete and valid,
+ *         d_fired unspecified; nothing is written outside d_fired[0 .. fired_capacity).
+ * d_fired may be NULL with fired_capacity = 0: the call only counts.  A d_row_ptr that breaks the
+ * contract is handled as tally_batch handles offsets: *d_n_fired = 0, nothing else is written,
+ * acm_gpu_plan_status reports ACM_GPU_E_INTERNAL, and no address is formed from a row pointer before
+ * the check has seen it.  A d_col entry >= the rule set's n_keywords is skipped, not flagged: after
+ * acm_gpu_plan_update the matrix may hold newer keywords.  n_texts >= 2^31 is ACM_GPU_E_ARG;
+ * n_texts = 0 gives fired_ptr[0] = 0 and n_fired = 0.  d_tmp must hold acm_gpu_rules_matrix_tmp_bytes
+ * (plan, rules, n_texts) bytes: 20 per text and 96 per posting of the set.  In the environment, read
+ * at every call (tests, experiments): ACM_GPU_RULES_ITEMS=<1 to 4,096> is the widest text, in items,
+ * that takes the fast form (1,024 when absent).  The call only queues launches on `stream`, with no
+ * host round trip.
+ * acm_gpu_rules_device: acm_gpu_tally_batch_device into a matrix inside d_tmp, then the evaluation,
+ * queued in one call (any plan kind, a pending delta included, not while a stream is open).
+ * Windows, `capacity`, pair_capacity, *d_total, *d_need and *d_need_pairs are exactly tally_batch's;
+ * when a window or the pairs overflowed, or d_offsets break the contract, *d_n_fired = 0 and
+ * d_fired_ptr and d_fired are not written.  d_tmp must hold acm_gpu_rules_tmp_bytes (plan, rules,
+ * window_symbols, capacity, pair_capacity, n_symbols, n_texts) bytes.
+ * acm_gpu_rules_host: the same from host memory, blocking, with the rule arrays: it creates and
+ * destroys the set itself and picks and repeats the rooms exactly as acm_gpu_tally_batch_host does.
+ * ACM_GPU_E_OVERFLOW means only "fired_capacity is too small, *n_fired suffices": fired_ptr, total
+ * and n_fired are valid then, `fired` untouched.  `fired` may be NULL: the call only counts.
+ * acm_rules: the call on the machine itself, total over machines exactly as acm_tally_batch is
+ * (same three paths, same cached plan, acm_scan_path recorded on success and on an output overflow):
+ * the GPU paths run acm_gpu_rules_host, ACM_SCAN_PATH_CPU_LOOP runs acm_tally_batch's host loop
+ * into a room the call grows itself, then acm_rules_matrix.  A missing device stays an error, never
+ * a fallback.
+ * Out of scope: positional rules (distance, order, offset), regular expressions, per-rule hit
+ * counts on the device (a bincount of fired[]), flows, several GPUs. */
+#define ACM_RULE_NO_MAX 0xFFFFFFFFu
+typedef struct {
+  uint32_t keyword_id, lo, hi;
+} ACMRuleTerm;
+typedef struct ACMRules ACMRules;
+typedef struct {
+  uint64_t rules, terms, always_rules, postings;
+  uint64_t fast_texts, wide_texts; /* texts evaluated by either form since creation (count passes) */
+} ACMRulesInfo;
+int acm_rules_check (const ACMRuleTerm *terms, const uint64_t *rule_ptr, const uint32_t *need,
+                     uint64_t n_rules, uint64_t n_keywords);
+int acm_rules_matrix (const uint64_t *row_ptr, const uint32_t *col, const uint64_t *val, uint64_t n_texts,
+                      uint64_t n_keywords, const ACMRuleTerm *terms, const uint64_t *rule_ptr,
+                      const uint32_t *need, uint64_t n_rules, uint64_t *fired_ptr /* n_texts + 1 */,
+                      uint32_t *fired, uint64_t fired_capacity, uint64_t *n_fired);
+int acm_gpu_rules_create (ACMPlan *plan, const ACMRuleTerm *terms, const uint64_t *rule_ptr,
+                          const uint32_t *need, uint64_t n_rules, ACMRules **out);
+void acm_gpu_rules_destroy (ACMRules *rules);
+int acm_gpu_rules_info (const ACMRules *rules, ACMRulesInfo *info);
+size_t acm_gpu_rules_matrix_tmp_bytes (const ACMPlan *plan, const ACMRules *rules, uint64_t n_texts);
+int acm_gpu_rules_matrix_device (ACMPlan *plan, const ACMRules *rules, const uint64_t *d_row_ptr,
+                                 const uint32_t *d_col, const uint64_t *d_val, uint64_t n_texts,
+                                 uint64_t *d_fired_ptr /* n_texts + 1 */, uint32_t *d_fired,
+                                 uint64_t fired_capacity, uint64_t *d_n_fired, void *d_tmp,
+                                 size_t tmp_bytes, void *stream);
+size_t acm_gpu_rules_tmp_bytes (const ACMPlan *plan, const ACMRules *rules, uint64_t window_symbols,
+                                uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols,
+                                uint64_t n_texts);
+int acm_gpu_rules_device (ACMPlan *plan, const ACMRules *rules, const void *d_text, uint64_t n_symbols,
+                          const uint64_t *d_offsets, uint64_t n_texts, uint64_t window_symbols,
+                          uint64_t capacity, uint64_t pair_capacity, uint64_t *d_fired_ptr /* n_texts + 1 */,
+                          uint32_t *d_fired, uint64_t fired_capacity, uint64_t *d_n_fired,
+                          uint64_t *d_total, uint64_t *d_need, uint64_t *d_need_pairs, void *d_tmp,
+                          size_t tmp_bytes, void *stream);
+int acm_gpu_rules_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts,
+                        const ACMRuleTerm *terms, const uint64_t *rule_ptr, const uint32_t *need,
+                        uint64_t n_rules, uint64_t *fired_ptr, uint32_t *fired, uint64_t fired_capacity,
+                        uint64_t *n_fired, uint64_t *total);   /* blocking */
+int acm_rules (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts,
+               const ACMRuleTerm *terms, const uint64_t *rule_ptr, const uint32_t *need, uint64_t n_rules,
+               uint64_t *fired_ptr, uint32_t *fired, uint64_t fired_capacity, uint64_t *n_fired,
+               uint64_t *total);
+
 /* ------------------------------------------------------------------ a buffer cut into texts: the batch calls' front end
  * Every batch call above takes offsets[] as given.  A caller with a file or a capture holds ONE
  * buffer with delimiters in it -- log lines, cells, the words that
