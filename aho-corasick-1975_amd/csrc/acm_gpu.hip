@@ -34,6 +34,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <unordered_map>
@@ -349,6 +350,73 @@ struct DeviceTemps {
     return hipFree (b);
   }
 };
+
+/* ---- what the device entry points share.
+ * The scratch of one call, taken buffer by buffer from `d_tmp` under blob_reserve's 256-byte rule.
+ * Without a base nothing is bound (take () gives nullptr) and only the size is kept: a family's
+ * *_carve function runs once without a base for *_tmp_bytes and once over d_tmp for the device
+ * call, so what is reported and what is bound are the same lines. */
+struct Carve {
+  uintptr_t base;
+  size_t used = 0;
+  explicit Carve (void *d_tmp = nullptr) : base (reinterpret_cast<uintptr_t> (d_tmp)) {}
+  template <typename T = unsigned char>
+  T *
+  take (size_t count) {
+    const size_t at = blob_reserve (used, count * sizeof (T));
+    return base ? reinterpret_cast<T *> (base + at) : nullptr;
+  }
+  size_t
+  boundary () { /* where the next buffer will begin */
+    return blob_reserve (used, 0);
+  }
+  size_t
+  total () const { /* what *_tmp_bytes reports */
+    return used + 256;
+  }
+};
+
+/* hipcub's scratch inside a carve: room for the exclusive sum over n32 32-bit counts and over n64
+ * 64-bit sums, whichever needs more */
+struct CubRoom {
+  void *at = nullptr;
+  size_t bytes = 0;
+};
+CubRoom
+cub_room (Carve &c, uint64_t n32, uint64_t n64) {
+  CubRoom r;
+  r.bytes = std::max (n32 ? exclusive_sum_bytes (n32) : 0, n64 ? exclusive_sum_bytes64 (n64) : 0);
+  r.at = c.take (r.bytes + 16);
+  return r;
+}
+
+/* out[i] = in[0] + ... + in[i - 1] over n items of either width, queued on st */
+template <typename In, typename Out>
+hipError_t
+exclusive_sum (const CubRoom &cub, In in, Out out, uint64_t n, hipStream_t st) {
+  size_t bytes = cub.bytes;
+  return hipcub::DeviceScan::ExclusiveSum (cub.at, bytes, in, out, (int)n, st);
+}
+
+/* a kernel launch and what it left: HIP_TRY (launch (...)) */
+template <typename... Params, typename... Args>
+hipError_t
+launch (void (*kernel) (Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args &...args) {
+  hipLaunchKernelGGL (kernel, grid, block, lds, st, args...);
+  return hipGetLastError ();
+}
+
+/* a test tunable, read from the environment at every call: `absent` unless the value lies in
+ * [lo, hi] and keeps the rule */
+enum class Tune { Any, Mult16, MultWave, Pow2 };
+uint32_t
+tunable (const char *name, uint32_t absent, uint32_t lo, uint32_t hi, Tune rule) {
+  const int v = env_int (name, (int)absent);
+  const bool fits = v >= (int)lo && v <= (int)hi &&
+                    (rule == Tune::Any || (rule == Tune::Mult16 && v % 16 == 0) || (rule == Tune::MultWave && v % (int)WAVE == 0) ||
+                     (rule == Tune::Pow2 && (v & (v - 1)) == 0));
+  return fits ? (uint32_t)v : absent;
+}
 
 /* ---- the kernel a plan launches, by the plan's own facts: set_lds_attributes and the launch
  * functions ask the same function, so the attribute is set on what is launched */
@@ -2125,8 +2193,7 @@ starts_flush (ACMPlan *p, hipStream_t st) {
   PatchTables T;
   for (int t = 0; t < 5; t++)
     T.t[t] = M.dev[t];
-  hipLaunchKernelGGL (patch_kernel, dim3 ((uint32_t)((np + 255) / 256)), dim3 (256), 0, st, T, M.d_patches, (uint32_t)np);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (patch_kernel, dim3 ((uint32_t)((np + 255) / 256)), dim3 (256), 0, st, T, M.d_patches, (uint32_t)np));
   M.patches.clear ();
   return ACM_GPU_OK;
 }
@@ -2389,10 +2456,9 @@ classify_text32 (ACMPlan *p, const void *d_text, uint64_t n, hipStream_t st) {
    * that never grows, far fewer with one that doubles */
   for (uint32_t round = 0; round < ACMPlan::CLS32_KNOWN_MAX / ACMPlan::CLS32_CAP_MIN + 64; round++) {
     HIP_TRY (hipMemsetAsync (p->d_unknown, 0, 4, st));
-    hipLaunchKernelGGL (classify32_kernel, dim3 (grid), dim3 (256), 0, st, static_cast<const uint32_t *> (d_text),
-                        static_cast<uint32_t *> (p->scratch.d_remap), n, p->d_cls32, p->cls32_slots - 1, p->d_unknown + 1, p->d_unknown,
-                        p->cls32_cap);
-    HIP_TRY (hipGetLastError ());
+    HIP_TRY (launch (classify32_kernel, dim3 (grid), dim3 (256), 0, st, static_cast<const uint32_t *> (d_text),
+                     static_cast<uint32_t *> (p->scratch.d_remap), n, p->d_cls32, p->cls32_slots - 1, p->d_unknown + 1, p->d_unknown,
+                     p->cls32_cap));
     uint32_t cnt = 0;
     HIP_TRY (hipMemcpyWithStream (&cnt, p->d_unknown, 4, hipMemcpyDeviceToHost, st));
     if (cnt == 0)
@@ -2440,9 +2506,8 @@ prepare_text (ACMPlan *p, const void **text, uint64_t n, hipStream_t st) {
       return rc;
     const uint64_t want_blocks = (n + 255) / 256;
     const uint32_t grid = (uint32_t)(want_blocks < (uint64_t)p->cu_count * 32 ? want_blocks : (uint64_t)p->cu_count * 32);
-    hipLaunchKernelGGL (intern_kernel, dim3 (grid), dim3 (256), 0, st, static_cast<const uint64_t *> (d_text),
-                        static_cast<uint32_t *> (p->scratch.d_remap), n, p->d_intern, p->intern_mask);
-    HIP_TRY (hipGetLastError ());
+    HIP_TRY (launch (intern_kernel, dim3 (grid), dim3 (256), 0, st, static_cast<const uint64_t *> (d_text),
+                     static_cast<uint32_t *> (p->scratch.d_remap), n, p->d_intern, p->intern_mask));
     *text = p->scratch.d_remap;
   } else if (p->cls32) {
     int rc = classify_text32 (p, d_text, n, st);
@@ -2669,8 +2734,7 @@ scan_plan (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
     rc = scan_impl<COUNT_ONLY> (p->delta, d_text, n, emit_from, pos_base, d_records, capacity, d_count, st, true, p->scratch.d_total);
   p->delta_scanned += n; /* what acm_gpu_plan_update weighs against the cost of one plan of everything */
   if (!accumulate) { /* (also after a failure: the total must not leak into the next scan) */
-    hipLaunchKernelGGL (finish_count_kernel, dim3 (1), dim3 (64), 0, st, p->scratch.d_total, reinterpret_cast<unsigned long long *> (d_count));
-    HIP_TRY (hipGetLastError ());
+    HIP_TRY (launch (finish_count_kernel, dim3 (1), dim3 (64), 0, st, p->scratch.d_total, reinterpret_cast<unsigned long long *> (d_count)));
   }
   return rc;
 }
@@ -2910,8 +2974,7 @@ radix_sort_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, void *d_tmp
   size_t cub_bytes = cub_sort_bytes (n);
   const uint32_t len_bits = len_bits_of (plan_lmax (plan));
   /* key = end_pos in the high bits, (max - length) below: 64 - len_bits bits remain for positions */
-  hipLaunchKernelGGL (make_keys_kernel, dim3 ((uint32_t)((n + 255) / 256)), dim3 (256), 0, st, d_records, n, len_bits, pos_lo, k0);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (make_keys_kernel, dim3 ((uint32_t)((n + 255) / 256)), dim3 (256), 0, st, d_records, n, len_bits, pos_lo, k0));
   hipcub::DoubleBuffer<uint64_t> keys (k0, k1);
   hipcub::DoubleBuffer<Rec16> vals (reinterpret_cast<Rec16 *> (d_records), v1);
   HIP_TRY (hipcub::DeviceRadixSort::SortPairs (cub_tmp, cub_bytes, keys, vals, (int)n, 0, key_bits, st));
@@ -2926,11 +2989,14 @@ namespace {
 struct OrderPlan {
   uint32_t wlog = 0, n_buckets = 0, len_bits = 1, key_bits = 64;
   bool sparse = false; /* fewer than 8 records per 4,096 positions: pass C goes by windows of buckets, not by bucket */
-  size_t o_hist = 0, o_cur = 0, o_rec = 0, o_cub = 0, cub_bytes = 0, total = 0;
+  uint32_t *hist = nullptr, *cur = nullptr; /* the scratch, bound when the carve has a base */
+  ACMRecord *bucketed = nullptr;
+  CubRoom cub;
+  size_t total = 0;
   bool ok = false;
 };
 OrderPlan
-order_layout (const ACMPlan *plan, uint64_t n, uint64_t span) {
+order_layout (const ACMPlan *plan, uint64_t n, uint64_t span, Carve c = Carve ()) {
   OrderPlan L;
   if (n == 0 || span == 0 || n >= (1ull << 31))
     return L;
@@ -2951,14 +3017,11 @@ order_layout (const ACMPlan *plan, uint64_t n, uint64_t span) {
     return L;
   L.wlog = wlog;
   L.n_buckets = (uint32_t)nb;
-  const size_t cub = exclusive_sum_bytes (nb + 1);
-  L.cub_bytes = cub;
-  size_t cur = 0;
-  L.o_hist = blob_reserve (cur, (nb + 1) * 4 + (nb + 2) * 4); /* counts, then (o_cur, right behind them) a zero word and the sums */
-  L.o_cur = L.o_hist + (nb + 1) * 4;
-  L.o_rec = blob_reserve (cur, n * sizeof (ACMRecord));
-  L.o_cub = blob_reserve (cur, cub + 16);
-  L.total = cur + 256;
+  L.hist = c.take<uint32_t> ((nb + 1) + (nb + 2)); /* counts, then (cur, right behind them) a zero word and the sums */
+  L.cur = L.hist ? L.hist + (nb + 1) : nullptr;
+  L.bucketed = c.take<ACMRecord> (n);
+  L.cub = cub_room (c, nb + 1, 0);
+  L.total = c.total ();
   L.ok = true;
   return L;
 }
@@ -2995,7 +3058,7 @@ order_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, const unsigned l
                size_t tmp_bytes, void *stream) {
   if (tmp_bytes < acm_gpu_order_tmp_bytes (plan, n, span))
     return ACM_GPU_E_ARG;
-  const OrderPlan L = order_layout (plan, n, span);
+  const OrderPlan L = order_layout (plan, n, span, Carve (d_tmp));
   if (!order_by_buckets (plan, L)) {
     if (n_dev)
       return ACM_GPU_E_ARG; /* (the caller asks order_by_buckets first) */
@@ -3003,9 +3066,8 @@ order_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, const unsigned l
   }
   HIP_TRY (hipSetDevice (plan->device));
   hipStream_t st = static_cast<hipStream_t> (stream);
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  uint32_t *hist = reinterpret_cast<uint32_t *> (t + L.o_hist), *cur = reinterpret_cast<uint32_t *> (t + L.o_cur);
-  ACMRecord *bucketed = reinterpret_cast<ACMRecord *> (t + L.o_rec);
+  uint32_t *hist = L.hist, *cur = L.cur;
+  ACMRecord *bucketed = L.bucketed;
   OrderK K{};
   K.in = d_records;
   K.n = n;
@@ -3024,12 +3086,9 @@ order_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, const unsigned l
   const uint64_t pieces = (n + ORDER_PIECE - 1) / ORDER_PIECE, pblocks = (pieces + ORDER_THREADS / WAVE - 1) / (ORDER_THREADS / WAVE);
   const dim3 grid = capped_grid (plan, pblocks);
   HIP_TRY (hipMemsetAsync (hist, 0, order_zero_bytes (L), st)); /* (the counts and cur[0], which lies right behind them) */
-  hipLaunchKernelGGL (order_bucket_kernel<false>, grid, dim3 (ORDER_THREADS), 0, st, K, hist, static_cast<ACMRecord *> (nullptr));
-  HIP_TRY (hipGetLastError ());
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, hist, cur + 1, (int)(L.n_buckets + 1), st));
-  hipLaunchKernelGGL (order_bucket_kernel<true>, grid, dim3 (ORDER_THREADS), 0, st, K, cur + 1, bucketed);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (order_bucket_kernel<false>, grid, dim3 (ORDER_THREADS), 0, st, K, hist, static_cast<ACMRecord *> (nullptr)));
+  HIP_TRY (exclusive_sum (L.cub, hist, cur + 1, L.n_buckets + 1, st));
+  HIP_TRY (launch (order_bucket_kernel<true>, grid, dim3 (ORDER_THREADS), 0, st, K, cur + 1, bucketed));
   /* pass C: buckets (dense record sets) or windows of buckets (sparse ones) of up to 256 records by
    * a wave each, crowded buckets by a block each (each role skips the others' buckets); a role
    * that does not run keeps a grid of zero */
@@ -3041,8 +3100,7 @@ order_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, const unsigned l
   if (n_dev || !L.sparse)
     sgrid = capped_grid (plan, (L.n_buckets + 3) / 4, 16).x;
   const uint32_t cgrid = capped_grid (plan, (L.n_buckets + ORDER_COUNT_THREADS - 1) / ORDER_COUNT_THREADS).x;
-  hipLaunchKernelGGL (order_finish_kernel, dim3 (wgrid + sgrid + cgrid), dim3 (256), 0, st, K, cur, bucketed, d_records, wgrid, sgrid);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (order_finish_kernel, dim3 (wgrid + sgrid + cgrid), dim3 (256), 0, st, K, cur, bucketed, d_records, wgrid, sgrid));
   return ACM_GPU_OK;
 }
 } // namespace
@@ -3064,7 +3122,12 @@ struct TiledPlan {
   uint32_t n_tiles = 0;
   uint64_t raw_slots = 0;
   uint32_t len_bits = 1, nsub = 2;
-  size_t o_raw = 0, o_prev = 0, o_dir = 0, o_size = 0, o_begin = 0, o_crowded = 0, o_over = 0, o_cub = 0, cub_bytes = 0, total = 0;
+  ACMRecord *raw = nullptr; /* the scratch, bound when the carve has a base */
+  uint32_t *prev = nullptr, *size = nullptr, *begin = nullptr, *crowded = nullptr;
+  TileEntry *dir = nullptr;
+  unsigned long long *over = nullptr;
+  CubRoom cub;
+  size_t total = 0;
 };
 
 /* the tiles of all the launches scan_impl makes for this text.
@@ -3074,7 +3137,7 @@ struct TiledPlan {
  * 64), so a later emit_from can LOWER R and give more tiles than emit_from = 0: 1 GiB on 256 CUs
  * is 16,384 tiles at emit_from = 0 and 20,480 when 81,919 groups are left.) */
 TiledPlan
-tiled_layout (const ACMPlan *p, uint64_t capacity, uint64_t n, uint64_t emit_from, bool bound = false) {
+tiled_layout (const ACMPlan *p, uint64_t capacity, uint64_t n, uint64_t emit_from, bool bound = false, Carve c = Carve ()) {
   TiledPlan L;
   const char *env = getenv ("ACM_GPU_ORDER"); /* radix / buckets: not this way (experiments, tests) */
   if (env && (strcmp (env, "radix") == 0 || strcmp (env, "buckets") == 0))
@@ -3102,61 +3165,52 @@ tiled_layout (const ACMPlan *p, uint64_t capacity, uint64_t n, uint64_t emit_fro
   /* whole chunks: the records and what every wave may leave unused of its last chunk */
   L.raw_slots = (capacity + REC_CHUNK - 1) / REC_CHUNK * REC_CHUNK + ((uint64_t)p->cu_count * (SPARSE_THREADS / WAVE) + 1) * REC_CHUNK;
   L.len_bits = len_bits_of (plan_lmax (p));
-  const size_t cub = exclusive_sum_bytes ((uint64_t)L.n_tiles + 1);
-  L.cub_bytes = cub;
-  size_t cur = 0;
-  L.o_raw = blob_reserve (cur, L.raw_slots * sizeof (ACMRecord));
-  L.o_prev = blob_reserve (cur, (L.raw_slots / REC_CHUNK) * 4);
-  L.o_dir = blob_reserve (cur, (size_t)L.n_tiles * sizeof (TileEntry));
-  L.o_size = blob_reserve (cur, ((size_t)L.n_tiles + 1) * 4);
-  L.o_begin = blob_reserve (cur, ((size_t)L.n_tiles + 1) * 4);
-  L.o_crowded = blob_reserve (cur, ((size_t)L.n_tiles + 1) * 4);
-  L.o_over = blob_reserve (cur, 8);
-  L.o_cub = blob_reserve (cur, cub + 16);
-  L.total = cur + 256;
+  L.raw = c.take<ACMRecord> (L.raw_slots);
+  L.prev = c.take<uint32_t> (L.raw_slots / REC_CHUNK);
+  L.dir = c.take<TileEntry> (L.n_tiles);
+  L.size = c.take<uint32_t> ((size_t)L.n_tiles + 1);
+  L.begin = c.take<uint32_t> ((size_t)L.n_tiles + 1);
+  L.crowded = c.take<uint32_t> ((size_t)L.n_tiles + 1);
+  L.over = c.take<unsigned long long> (1);
+  L.cub = cub_room (c, (uint64_t)L.n_tiles + 1, 0);
+  L.total = c.total ();
   L.ok = true;
   return L;
 }
 
 int
 scan_tiled (ACMPlan *plan, const TiledPlan &L, const void *d_text, uint64_t n_symbols, uint64_t emit_from, uint64_t pos_base, ACMRecord *d_records,
-            uint64_t capacity, uint64_t *d_count, void *d_tmp, hipStream_t st) {
+            uint64_t capacity, uint64_t *d_count, hipStream_t st) {
   HIP_TRY (hipSetDevice (plan->device));
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  TiledScan tiled = { reinterpret_cast<TileEntry *> (t + L.o_dir), reinterpret_cast<uint32_t *> (t + L.o_prev), 0 };
-  int rc = scan_impl<false> (plan, d_text, n_symbols, emit_from, pos_base, reinterpret_cast<ACMRecord *> (t + L.o_raw), L.raw_slots, d_count, st,
-                             false, nullptr, &tiled);
+  TiledScan tiled = { L.dir, L.prev, 0 };
+  int rc = scan_impl<false> (plan, d_text, n_symbols, emit_from, pos_base, L.raw, L.raw_slots, d_count, st, false, nullptr, &tiled);
   if (rc || tiled.base != L.n_tiles) { /* (the directory was sized by tiled_layout, filled by launch_gram) */
     (void)hipMemsetAsync (plan->scratch.d_total, 0, 8, st); /* (the scan's running total must not leak into the next one) */
     return rc ? rc : ACM_GPU_E_INTERNAL;
   }
   TileK K{};
-  K.raw = reinterpret_cast<const ACMRecord *> (t + L.o_raw);
-  K.chunk_prev = reinterpret_cast<const uint32_t *> (t + L.o_prev);
-  K.dir = reinterpret_cast<const TileEntry *> (t + L.o_dir);
+  K.raw = L.raw;
+  K.chunk_prev = L.prev;
+  K.dir = L.dir;
   K.n_tiles = L.n_tiles;
-  K.size = reinterpret_cast<uint32_t *> (t + L.o_size);
-  K.begin = reinterpret_cast<const uint32_t *> (t + L.o_begin);
+  K.size = L.size;
+  K.begin = L.begin;
   K.out = d_records;
   K.capacity = capacity;
   K.d_count = reinterpret_cast<unsigned long long *> (d_count);
   K.reserved = plan->scratch.d_total;
   K.len_bits = L.len_bits;
   K.nsub = L.nsub;
-  K.crowded = reinterpret_cast<uint32_t *> (t + L.o_crowded);
+  K.crowded = L.crowded;
   K.raw_slots = L.raw_slots;
-  K.over_total = reinterpret_cast<unsigned long long *> (t + L.o_over);
+  K.over_total = L.over;
   HIP_TRY (hipMemsetAsync (K.over_total, 0, 8, st));
   K.error = error_word (plan);
-  hipLaunchKernelGGL (tile_size_kernel, capped_grid (plan, (L.n_tiles + 1 + 3) / 4, 16), dim3 (256), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.size, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(L.n_tiles + 1), st));
-  hipLaunchKernelGGL (tile_gather_kernel, capped_grid (plan, L.n_tiles, 16), dim3 (TILE_THREADS), tile_lds_bytes (L.nsub), st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (tile_size_kernel, capped_grid (plan, (L.n_tiles + 1 + 3) / 4, 16), dim3 (256), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, K.size, L.begin, L.n_tiles + 1, st));
+  HIP_TRY (launch (tile_gather_kernel, capped_grid (plan, L.n_tiles, 16), dim3 (TILE_THREADS), tile_lds_bytes (L.nsub), st, K));
   /* the tiles it found crowded (dense matches; none on ordinary texts: the kernel returns at once) */
-  hipLaunchKernelGGL (tile_crowded_kernel, capped_grid (plan, L.n_tiles, 4), dim3 (TILE_THREADS), tile_lds_bytes (L.nsub), st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (tile_crowded_kernel, capped_grid (plan, L.n_tiles, 4), dim3 (TILE_THREADS), tile_lds_bytes (L.nsub), st, K));
   return ACM_GPU_OK;
 }
 } // namespace
@@ -3183,11 +3237,11 @@ acm_gpu_scan_ordered_device (ACMPlan *plan, const void *d_text, uint64_t n_symbo
     return ACM_GPU_E_ARG;
   if (capacity && tmp_bytes < acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols))
     return ACM_GPU_E_ARG;
-  const TiledPlan T = tiled_layout (plan, capacity, n_symbols, emit_from);
+  const TiledPlan T = tiled_layout (plan, capacity, n_symbols, emit_from, false, Carve (d_tmp));
   /* (the layout of THIS emit_from must fit what the caller gave -- the query is an upper bound, so
    * it does; a buffer sized some other way takes the general passes, never a write past its end) */
   if (T.ok && T.total <= tmp_bytes)
-    return scan_tiled (plan, T, d_text, n_symbols, emit_from, pos_base, d_records, capacity, d_count, d_tmp, static_cast<hipStream_t> (stream));
+    return scan_tiled (plan, T, d_text, n_symbols, emit_from, pos_base, d_records, capacity, d_count, static_cast<hipStream_t> (stream));
   const OrderPlan L = order_layout (plan, capacity, n_symbols);
   int rc = acm_gpu_scan_device (plan, d_text, n_symbols, emit_from, pos_base, d_records, capacity, d_count, stream);
   if (rc || capacity == 0 || n_symbols == 0)
@@ -3303,6 +3357,26 @@ batch_args_ok (const void *text, const uint64_t *offsets, uint64_t n_texts, uint
   return n_texts < limit && batch_offsets_ok (offsets, n_texts) && (!offsets[n_texts] || text);
 }
 
+/* the device calls' shared checks.  A buffer of n symbols of sb bytes on the device (a text, an
+ * output): on the symbols' grid, its bytes countable in 56 bits */
+bool
+symbols_ok (const void *d, uint64_t n, uint32_t sb) {
+  return reinterpret_cast<uintptr_t> (d) % sb == 0 && n < (1ull << 56) / sb;
+}
+
+/* an output of out_capacity symbols built from the text beside it: the two do not overlap */
+bool
+apart (const void *d_text, uint64_t n_symbols, const void *d_out, uint64_t out_capacity, uint32_t sb) {
+  const uintptr_t t0 = reinterpret_cast<uintptr_t> (d_text), o0 = reinterpret_cast<uintptr_t> (d_out);
+  return !(n_symbols && out_capacity && t0 < o0 + out_capacity * sb && o0 < t0 + n_symbols * sb);
+}
+
+/* the windowed calls (tally, grep, tally_batch): windows of whole 16-symbol groups, a record room below 2^31 */
+bool
+window_ok (uint64_t window_symbols, uint64_t capacity) {
+  return window_symbols != 0 && window_symbols % 16 == 0 && capacity != 0 && capacity < (1ull << 31);
+}
+
 /* where offsets[] may be NULL (one text) and the number of symbols is given beside it: fewer than 2^31 texts, which end there */
 bool
 optional_offsets_ok (const uint64_t *offsets, uint64_t n_texts, uint64_t n_symbols) {
@@ -3358,28 +3432,59 @@ acm_gpu_scan_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t
  * The ordered scan of the concatenation into the caller's scratch, then the pass over its records:
  * those that lie inside one text go to d_records, with their text beside them. */
 namespace {
-struct BatchLayout {
-  uint64_t n_blocks = 0, n_tiles = 0;
-  size_t o_ctl = 0, o_index = 0, o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, o_rec = 0, o_ord = 0, ord_bytes = 0, total = 0;
+/* what batch_carve derives beside K's pointers */
+struct BatchRoom {
+  uint32_t *tile_begin = nullptr; /* K.tile_begin, for the sum that writes it */
+  CubRoom cub;
+  ACMRecord *ordered = nullptr; /* the ordered scan's records and its scratch */
+  unsigned char *ord = nullptr;
+  size_t ord_bytes = 0;
 };
-BatchLayout
-batch_layout (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols) {
-  BatchLayout L;
-  L.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
-  L.n_tiles = (capacity + BATCH_TILE - 1) / BATCH_TILE;
-  const size_t cub = exclusive_sum_bytes (L.n_tiles + 1);
-  L.cub_bytes = cub;
-  L.ord_bytes = acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols);
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (BatchCtl));
-  L.o_index = blob_reserve (cur, L.n_blocks * 4);
-  L.o_count = blob_reserve (cur, (L.n_tiles + 1) * 4);
-  L.o_begin = blob_reserve (cur, (L.n_tiles + 1) * 4);
-  L.o_cub = blob_reserve (cur, cub + 16);
-  L.o_rec = blob_reserve (cur, (capacity ? capacity : 1) * sizeof (ACMRecord));
-  L.o_ord = blob_reserve (cur, L.ord_bytes);
-  L.total = cur + 256;
-  return L;
+BatchRoom
+batch_carve (Carve &c, const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, BatchK &K) {
+  BatchRoom R;
+  K.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
+  K.n_tiles = (capacity + BATCH_TILE - 1) / BATCH_TILE;
+  R.ord_bytes = acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols);
+  K.ctl = c.take<BatchCtl> (1);
+  K.index = c.take<uint32_t> (K.n_blocks);
+  K.tile_count = c.take<uint32_t> (K.n_tiles + 1);
+  K.tile_begin = R.tile_begin = c.take<uint32_t> (K.n_tiles + 1);
+  R.cub = cub_room (c, K.n_tiles + 1, 0);
+  K.in = R.ordered = c.take<ACMRecord> (capacity ? capacity : 1);
+  R.ord = c.take (R.ord_bytes);
+  return R;
+}
+
+/* grid-stride kernels: never more blocks than keep the chip busy.  The kernels that also walk
+ * offsets[] are sized by the positions; a batch of many texts over few symbols (mostly empty texts)
+ * gets the full capped grid instead -- one size, whatever the number of texts */
+dim3
+batch_grid (const ACMPlan *plan, uint64_t by_positions, uint64_t n_texts) {
+  const uint64_t many_texts = n_texts >= (1ull << 16) ? (uint64_t)plan->cu_count * 8 : 1;
+  return capped_grid (plan, std::max (by_positions, many_texts));
+}
+
+/* the first step of the batch and flow scans, of grep and of tally_batch: for every block of
+ * positions the text it begins in, into index[n_blocks], and the check of offsets[], whose verdict
+ * goes to ctl->bad and to the plan's error word.  pre_bad: a flow scan's own verdict (BatchK) */
+int
+batch_index (const ACMPlan *plan, const uint64_t *d_offsets, uint64_t n_texts, uint64_t n_symbols, uint32_t *index, uint64_t n_blocks, BatchCtl *ctl,
+             unsigned int *error, hipStream_t st, const unsigned int *pre_bad = nullptr) {
+  BatchK B{};
+  B.offsets = d_offsets;
+  B.n_texts = n_texts;
+  B.n_symbols = n_symbols;
+  B.index = index;
+  B.n_blocks = n_blocks;
+  B.ctl = ctl;
+  B.error = error;
+  B.pre_bad = pre_bad;
+  /* (the index goes by the positions, the check of offsets[] by a grid-stride loop of the same launch) */
+  const dim3 grid = batch_grid (plan, (n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, n_texts);
+  HIP_TRY (pre_bad ? launch (batch_index_kernel<true>, grid, dim3 (BATCH_THREADS), 0, st, B)
+                   : launch (batch_index_kernel<false>, grid, dim3 (BATCH_THREADS), 0, st, B));
+  return ACM_GPU_OK;
 }
 } // namespace
 
@@ -3388,7 +3493,10 @@ acm_gpu_scan_batch_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n
   (void)n_texts; /* (nothing here is sized by the number of texts: the index goes by blocks of positions) */
   if (!plan || capacity >= (1ull << 31))
     return 0;
-  return batch_layout (plan, capacity, n_symbols).total;
+  Carve c;
+  BatchK K{};
+  batch_carve (c, plan, capacity, n_symbols, K);
+  return c.total ();
 }
 
 namespace {
@@ -3400,15 +3508,16 @@ struct BatchHeads {
   const unsigned int *pre_bad; /* the caller's own checks have failed */
 };
 
-/* a batch of no texts: no symbol, no record */
+/* a batch of no texts: no symbol, and a zero in every output the caller gave (its counts, the first
+ * entry of its row pointers) */
 int
-empty_batch (ACMPlan *plan, uint64_t n_symbols, uint64_t *d_first, uint64_t *d_count, hipStream_t st) {
+empty_batch (ACMPlan *plan, uint64_t n_symbols, std::initializer_list<uint64_t *> outputs, hipStream_t st) {
   if (n_symbols)
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
-  if (d_first)
-    HIP_TRY (hipMemsetAsync (d_first, 0, 8, st));
+  for (uint64_t *d : outputs)
+    if (d)
+      HIP_TRY (hipMemsetAsync (d, 0, 8, st));
   return ACM_GPU_OK;
 }
 
@@ -3422,33 +3531,25 @@ batch_scan (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
   if (n_texts == 0)
-    return empty_batch (plan, n_symbols, d_first, d_count, st);
-  const BatchLayout L = batch_layout (plan, capacity, n_symbols);
-  if (!d_offsets || !d_tmp || tmp_bytes < L.total)
+    return empty_batch (plan, n_symbols, { d_count, d_first }, st);
+  Carve carve (d_tmp);
+  BatchK K{};
+  const BatchRoom L = batch_carve (carve, plan, capacity, n_symbols, K);
+  if (!d_offsets || !d_tmp || tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  ACMRecord *ordered = reinterpret_cast<ACMRecord *> (t + L.o_rec);
-  int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, 0, ordered, capacity, d_count, t + L.o_ord, L.ord_bytes, stream);
+  int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, 0, L.ordered, capacity, d_count, L.ord, L.ord_bytes, stream);
   if (rc)
     return rc;
-  BatchK K{};
-  K.in = ordered;
   K.capacity = capacity;
   K.n_dev = reinterpret_cast<const unsigned long long *> (d_count);
   K.offsets = d_offsets;
   K.n_texts = n_texts;
   K.n_symbols = n_symbols;
-  K.index = reinterpret_cast<uint32_t *> (t + L.o_index);
-  K.n_blocks = L.n_blocks;
-  K.tile_count = reinterpret_cast<uint32_t *> (t + L.o_count);
-  K.tile_begin = reinterpret_cast<const uint32_t *> (t + L.o_begin);
-  K.n_tiles = L.n_tiles;
   K.out = d_records;
   K.text_id = d_text_id;
   K.first = d_first;
   K.d_count = reinterpret_cast<unsigned long long *> (d_count);
-  K.ctl = reinterpret_cast<BatchCtl *> (t + L.o_ctl);
   K.error = error_word (plan);
   if (HEADS) {
     K.head = heads->head;
@@ -3456,22 +3557,13 @@ batch_scan (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_
     K.n_real = heads->n_real;
     K.pre_bad = heads->pre_bad;
   }
-  /* grid-stride kernels: never more blocks than keep the chip busy.  The two kernels that also walk
-   * offsets[] are sized by the positions; a batch of many texts over few symbols (mostly empty texts)
-   * gets the full capped grid instead -- one size, whatever the number of texts */
-  const uint64_t many_texts = n_texts >= (1ull << 16) ? (uint64_t)plan->cu_count * 8 : 1;
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (BatchCtl), st));
-  /* (the index goes by the positions, the check of offsets[] by a grid-stride loop of the same launch) */
-  hipLaunchKernelGGL (batch_index_kernel<HEADS>, capped_grid (plan, std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL ((batch_filter_kernel<false, HEADS>), capped_grid (plan, L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.tile_count, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(L.n_tiles + 1), st));
-  hipLaunchKernelGGL ((batch_filter_kernel<true, HEADS>), capped_grid (plan, L.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (batch_first_kernel<HEADS>, capped_grid (plan, std::max (L.n_blocks / 4 + 1, many_texts)), dim3 (BATCH_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  if (const int bad = batch_index (plan, d_offsets, n_texts, n_symbols, K.index, K.n_blocks, K.ctl, K.error, st, HEADS ? heads->pre_bad : nullptr))
+    return bad;
+  HIP_TRY (launch (batch_filter_kernel<false, HEADS>, capped_grid (plan, K.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, K.tile_count, L.tile_begin, K.n_tiles + 1, st));
+  HIP_TRY (launch (batch_filter_kernel<true, HEADS>, capped_grid (plan, K.n_tiles + 1), dim3 (BATCH_THREADS), 0, st, K));
+  HIP_TRY (launch (batch_first_kernel<HEADS>, batch_grid (plan, K.n_blocks / 4 + 1, n_texts), dim3 (BATCH_THREADS), 0, st, K));
   return ACM_GPU_OK;
 }
 } // namespace
@@ -3554,28 +3646,33 @@ struct HeadTo64 {
 };
 using HeadIterator = hipcub::TransformInputIterator<uint64_t, HeadTo64, const uint32_t *>;
 
-struct FlowsLayout {
-  uint64_t n_expanded = 0;
-  size_t o_ctl = 0, o_head = 0, o_sum = 0, o_xoff = 0, o_cub = 0, cub_bytes = 0, o_text = 0, o_batch = 0, batch_bytes = 0, total = 0;
+/* what flows_carve derives beside F's pointers */
+struct FlowsRoom {
+  uint64_t *head_sum = nullptr; /* F.head_sum, for the sum that writes it */
+  CubRoom cub;
+  unsigned char *batch = nullptr; /* the batch scan's scratch */
+  size_t batch_bytes = 0;
 };
-FlowsLayout
-flows_layout (const ACMPlan *plan, const ACMFlows *flows, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
-  FlowsLayout L;
-  L.n_expanded = n_symbols + n_texts * flows_keep (plan); /* every text behind a full carry: the worst case */
-  size_t cub = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, cub, HeadIterator (static_cast<const uint32_t *> (nullptr), HeadTo64 ()), static_cast<uint64_t *> (nullptr), (int)(n_texts + 1), nullptr);
-  L.cub_bytes = cub;
-  L.batch_bytes = batch_layout (plan, capacity, L.n_expanded).total;
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (FlowsCtl));
-  L.o_head = blob_reserve (cur, (n_texts + 1) * 4);
-  L.o_sum = blob_reserve (cur, (n_texts + 1) * 8);
-  L.o_xoff = blob_reserve (cur, (n_texts + 2) * 8);
-  L.o_cub = blob_reserve (cur, cub + 16);
-  L.o_text = blob_reserve (cur, L.n_expanded * flows->sb + 256);
-  L.o_batch = blob_reserve (cur, L.batch_bytes);
-  L.total = cur + 256;
-  return L;
+FlowsRoom
+flows_carve (Carve &c, const ACMPlan *plan, const ACMFlows *flows, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts, FlowsK &F) {
+  FlowsRoom R;
+  F.n_expanded = n_symbols + n_texts * flows_keep (plan); /* every text behind a full carry: the worst case */
+  (void)hipcub::DeviceScan::ExclusiveSum (nullptr, R.cub.bytes, HeadIterator (static_cast<const uint32_t *> (nullptr), HeadTo64 ()), static_cast<uint64_t *> (nullptr), (int)(n_texts + 1), nullptr);
+  Carve sized;
+  BatchK B{};
+  batch_carve (sized, plan, capacity, F.n_expanded, B);
+  R.batch_bytes = sized.total ();
+  F.ctl = c.take<FlowsCtl> (1);
+  F.head = c.take<uint32_t> (n_texts + 1);
+  F.head_sum = R.head_sum = c.take<uint64_t> (n_texts + 1);
+  F.xoff = c.take<uint64_t> (n_texts + 2);
+  R.cub.at = c.take (R.cub.bytes + 16);
+  F.expanded = c.take (F.n_expanded * flows->sb + 256);
+  R.batch = c.take (R.batch_bytes);
+  Carve inner (R.batch); /* (the batch scan's control block, where batch_scan will put it) */
+  batch_carve (inner, plan, capacity, F.n_expanded, B);
+  F.batch = B.ctl;
+  return R;
 }
 
 uint32_t
@@ -3636,9 +3733,8 @@ acm_gpu_flows_reset (ACMFlows *f, const uint32_t *d_flow_ids, uint64_t n, void *
     return ACM_GPU_OK;
   ACMPlan *plan = f->plan;
   HIP_TRY (hipSetDevice (plan->device));
-  hipLaunchKernelGGL (flows_reset_kernel, capped_grid (plan, (items + FLOWS_THREADS - 1) / FLOWS_THREADS), dim3 (FLOWS_THREADS), 0,
-                      static_cast<hipStream_t> (stream), f->d_len, f->n_flows, d_flow_ids, n, error_word (plan));
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (flows_reset_kernel, capped_grid (plan, (items + FLOWS_THREADS - 1) / FLOWS_THREADS), dim3 (FLOWS_THREADS), 0,
+                   static_cast<hipStream_t> (stream), f->d_len, f->n_flows, d_flow_ids, n, error_word (plan)));
   return ACM_GPU_OK;
 }
 
@@ -3646,7 +3742,10 @@ extern "C" size_t
 acm_gpu_scan_flows_tmp_bytes (const ACMPlan *plan, const ACMFlows *flows, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
   if (!plan || !flows || flows->plan != plan || capacity >= (1ull << 31) || n_texts >= (1ull << 31))
     return 0;
-  return flows_layout (plan, flows, capacity, n_symbols, n_texts).total;
+  Carve c;
+  FlowsK F{};
+  flows_carve (c, plan, flows, capacity, n_symbols, n_texts, F);
+  return c.total ();
 }
 
 extern "C" int
@@ -3663,17 +3762,17 @@ acm_gpu_scan_flows_device (ACMPlan *plan, ACMFlows *flows, const void *d_text, u
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
   if (n_texts == 0)
-    return empty_batch (plan, n_symbols, d_first, d_count, st);
-  const FlowsLayout L = flows_layout (plan, flows, capacity, n_symbols, n_texts);
-  if (!d_offsets || !d_tmp || tmp_bytes < L.total)
+    return empty_batch (plan, n_symbols, { d_count, d_first }, st);
+  Carve carve (d_tmp);
+  FlowsK F{};
+  const FlowsRoom L = flows_carve (carve, plan, flows, capacity, n_symbols, n_texts, F);
+  if (!d_offsets || !d_tmp || tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
   if (++flows->seq == 0) { /* the sequence numbers have gone round: no claim of an old call may look like a new one */
     HIP_TRY (hipMemsetAsync (flows->d_claim, 0, (size_t)flows->n_flows * 4, st));
     flows->seq = 1;
   }
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  FlowsK F{};
   F.text = static_cast<const unsigned char *> (d_text);
   F.offsets = d_offsets;
   F.flow = d_flow;
@@ -3687,39 +3786,25 @@ acm_gpu_scan_flows_device (ACMPlan *plan, ACMFlows *flows, const void *d_text, u
   F.carry_len = flows->d_len;
   F.claim = flows->d_claim;
   F.seq = flows->seq;
-  F.head = reinterpret_cast<uint32_t *> (t + L.o_head);
-  F.head_sum = reinterpret_cast<const uint64_t *> (t + L.o_sum);
-  F.xoff = reinterpret_cast<uint64_t *> (t + L.o_xoff);
-  F.expanded = t + L.o_text;
-  F.n_expanded = L.n_expanded;
-  F.ctl = reinterpret_cast<FlowsCtl *> (t + L.o_ctl);
-  F.batch = reinterpret_cast<const BatchCtl *> (t + L.o_batch + batch_layout (plan, capacity, L.n_expanded).o_ctl);
   F.error = error_word (plan);
   /* grid-stride kernels with capped grids: one launch size whatever the number of texts and flows */
   const uint64_t per_text = (n_texts + 2 + FLOWS_THREADS - 1) / FLOWS_THREADS;
   HIP_TRY (hipMemsetAsync (F.ctl, 0, sizeof (FlowsCtl), st));
-  hipLaunchKernelGGL (flows_check_kernel, capped_grid (plan, per_text), dim3 (FLOWS_THREADS), 0, st, F);
-  HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (flows_head_kernel, capped_grid (plan, per_text), dim3 (FLOWS_THREADS), 0, st, F);
-  HIP_TRY (hipGetLastError ());
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, HeadIterator (F.head, HeadTo64 ()), reinterpret_cast<uint64_t *> (t + L.o_sum),
-                                             (int)(n_texts + 1), st));
-  hipLaunchKernelGGL (flows_xoff_kernel, capped_grid (plan, per_text), dim3 (FLOWS_THREADS), 0, st, F);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (flows_check_kernel, capped_grid (plan, per_text), dim3 (FLOWS_THREADS), 0, st, F));
+  HIP_TRY (launch (flows_head_kernel, capped_grid (plan, per_text), dim3 (FLOWS_THREADS), 0, st, F));
+  HIP_TRY (exclusive_sum (L.cub, HeadIterator (F.head, HeadTo64 ()), L.head_sum, n_texts + 1, st));
+  HIP_TRY (launch (flows_xoff_kernel, capped_grid (plan, per_text), dim3 (FLOWS_THREADS), 0, st, F));
   /* the gather: lanes per text by the mean length of a text, 16 bytes a lane and step */
   F.group_log2 = log2_ceil_capped ((n_symbols * F.sb / n_texts + 15) / 16, 6);
   const uint64_t gather_blocks = std::max (((n_texts << F.group_log2) + FLOWS_THREADS - 1) / FLOWS_THREADS, n_texts * keep * F.sb / 16 / FLOWS_THREADS + 1);
-  hipLaunchKernelGGL (flows_gather_kernel, capped_grid (plan, gather_blocks), dim3 (FLOWS_THREADS), 0, st, F);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (flows_gather_kernel, capped_grid (plan, gather_blocks), dim3 (FLOWS_THREADS), 0, st, F));
   BatchHeads H{ F.head, d_offsets, n_texts, &F.ctl->bad };
-  const int rc = batch_scan<true> (plan, F.expanded, L.n_expanded, F.xoff, n_texts + 1, d_records, d_text_id, d_first, capacity, d_count, t + L.o_batch,
+  const int rc = batch_scan<true> (plan, F.expanded, F.n_expanded, F.xoff, n_texts + 1, d_records, d_text_id, d_first, capacity, d_count, L.batch,
                                    L.batch_bytes, stream, &H);
   if (rc)
     return rc;
   F.group_log2 = log2_ceil_capped (flows->slot_bytes / 16, 6);
-  hipLaunchKernelGGL (flows_carry_kernel, capped_grid (plan, ((n_texts << F.group_log2) + FLOWS_THREADS - 1) / FLOWS_THREADS), dim3 (FLOWS_THREADS), 0, st, F);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (flows_carry_kernel, capped_grid (plan, ((n_texts << F.group_log2) + FLOWS_THREADS - 1) / FLOWS_THREADS), dim3 (FLOWS_THREADS), 0, st, F));
   return ACM_GPU_OK;
 }
 
@@ -3745,19 +3830,21 @@ acm_gpu_scan_flows_host (ACMPlan *plan, ACMFlows *flows, const void *text, uint6
  * The record scan of the text, window by window into the caller's scratch, and a histogram pass
  * over every window's records; the caller's counters take the sums at the end, all or nothing. */
 namespace {
-struct TallyLayout {
-  size_t o_ctl = 0, o_hist = 0, o_count = 0, o_rec = 0, total = 0;
+/* what tally_carve derives beside K's pointers */
+struct TallyRoom {
+  size_t zero_bytes = 0; /* control words, histogram, count: the head of the scratch, cleared in front of every call */
+  uint64_t *d_count = nullptr;
+  ACMRecord *rec = nullptr;
 };
-TallyLayout
-tally_layout (const ACMPlan *plan, uint64_t capacity) {
-  TallyLayout L;
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (TallyCtl));
-  L.o_hist = blob_reserve (cur, ((size_t)plan->covered_keywords + 1) * 8);
-  L.o_count = blob_reserve (cur, 8);
-  L.o_rec = blob_reserve (cur, (size_t)capacity * sizeof (ACMRecord));
-  L.total = cur + 256;
-  return L;
+TallyRoom
+tally_carve (Carve &c, const ACMPlan *plan, uint64_t capacity, TallyK &K) {
+  TallyRoom R;
+  K.ctl = c.take<TallyCtl> (1);
+  K.hist = c.take<unsigned long long> ((size_t)plan->covered_keywords + 1);
+  R.d_count = c.take<uint64_t> (1);
+  R.zero_bytes = c.boundary (); /* (up to where the records begin) */
+  R.rec = c.take<ACMRecord> ((size_t)capacity);
+  return R;
 }
 
 /* ACM_GPU_TALLY=global: every plan takes the form of the big dictionaries (experiments, tests) */
@@ -3858,56 +3945,47 @@ acm_gpu_tally_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t 
   (void)window_symbols; /* (what a window's scan needs beside its records belongs to the plan) */
   if (!plan || capacity == 0 || capacity >= (1ull << 31))
     return 0;
-  return tally_layout (plan, capacity).total;
+  Carve c;
+  TallyK K{};
+  tally_carve (c, plan, capacity, K);
+  return c.total ();
 }
 
 extern "C" int
 acm_gpu_tally_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t emit_from, uint64_t *d_tally, uint64_t n_keywords,
                       uint64_t window_symbols, uint64_t capacity, uint64_t *d_total, uint64_t *d_need, void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!plan || !d_tally || !d_total || !d_need || !d_tmp || (n_symbols && !d_text) || window_symbols == 0 || window_symbols % 16 ||
-      capacity == 0 || capacity >= (1ull << 31) || n_keywords < plan->covered_keywords)
+  if (!plan || !d_tally || !d_total || !d_need || !d_tmp || (n_symbols && !d_text) || !window_ok (window_symbols, capacity) ||
+      n_keywords < plan->covered_keywords)
     return ACM_GPU_E_ARG;
-  const TallyLayout L = tally_layout (plan, capacity);
-  if (tmp_bytes < L.total)
+  Carve carve (d_tmp);
+  TallyK K{}; /* the finish pass'; the window passes add the records to a copy */
+  const TallyRoom L = tally_carve (carve, plan, capacity, K);
+  if (tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
   hipStream_t st = static_cast<hipStream_t> (stream);
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  uint64_t *d_count = reinterpret_cast<uint64_t *> (t + L.o_count);
-  ACMRecord *rec = reinterpret_cast<ACMRecord *> (t + L.o_rec);
-  HIP_TRY (hipMemsetAsync (t, 0, L.o_rec, st)); /* control words, histogram, count */
+  HIP_TRY (hipMemsetAsync (d_tmp, 0, L.zero_bytes, st));
   HIP_TRY (hipMemsetAsync (d_total, 0, 8, st));
+  K.capacity = capacity;
+  K.n_keywords = plan->covered_keywords;
 
-  const int rc = scan_windows (plan, d_text, n_symbols, emit_from, window_symbols, rec, capacity, d_count, st, [&] (uint64_t) -> int {
-    TallyK K{};
-    K.rec = rec;
-    K.capacity = capacity;
-    K.n_dev = reinterpret_cast<const unsigned long long *> (d_count);
-    K.hist = reinterpret_cast<unsigned long long *> (t + L.o_hist);
-    K.n_keywords = plan->covered_keywords;
-    K.ctl = reinterpret_cast<TallyCtl *> (t + L.o_ctl);
-    K.error = error_word (plan);
+  const int rc = scan_windows (plan, d_text, n_symbols, emit_from, window_symbols, L.rec, capacity, L.d_count, st, [&] (uint64_t) -> int {
+    TallyK W = K;
+    W.rec = L.rec;
+    W.n_dev = reinterpret_cast<const unsigned long long *> (L.d_count);
+    W.error = error_word (plan);
     /* grid-stride, two blocks per CU (what the LDS form's counters allow), whatever the scan found */
     const dim3 grid ((uint32_t)plan->cu_count * 2);
-    if (tally_lds_form (plan))
-      hipLaunchKernelGGL (tally_records_kernel<true>, grid, dim3 (TALLY_THREADS), (size_t)K.n_keywords * 4, st, K);
-    else
-      hipLaunchKernelGGL (tally_records_kernel<false>, grid, dim3 (TALLY_THREADS), 0, st, K);
-    HIP_TRY (hipGetLastError ());
+    HIP_TRY (tally_lds_form (plan) ? launch (tally_records_kernel<true>, grid, dim3 (TALLY_THREADS), (size_t)W.n_keywords * 4, st, W)
+                                   : launch (tally_records_kernel<false>, grid, dim3 (TALLY_THREADS), 0, st, W));
     return ACM_GPU_OK;
   });
   if (rc)
     return rc;
-  TallyK K{};
-  K.capacity = capacity;
-  K.hist = reinterpret_cast<unsigned long long *> (t + L.o_hist);
-  K.n_keywords = plan->covered_keywords;
-  K.ctl = reinterpret_cast<TallyCtl *> (t + L.o_ctl);
   K.d_tally = reinterpret_cast<unsigned long long *> (d_tally);
   K.d_total = reinterpret_cast<unsigned long long *> (d_total);
   K.d_need = reinterpret_cast<unsigned long long *> (d_need);
-  hipLaunchKernelGGL (tally_finish_kernel, capped_grid (plan, ((uint64_t)K.n_keywords + TALLY_THREADS - 1) / TALLY_THREADS), dim3 (TALLY_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (tally_finish_kernel, capped_grid (plan, ((uint64_t)K.n_keywords + TALLY_THREADS - 1) / TALLY_THREADS), dim3 (TALLY_THREADS), 0, st, K));
   return ACM_GPU_OK;
 }
 
@@ -3955,40 +4033,37 @@ acm_gpu_tally_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_
  * window's records that counts them per text, then the kept texts' ids, their offsets in the
  * output and the output itself. */
 namespace {
-struct GrepLayout {
-  uint64_t n_blocks = 0, n_tiles = 0;
-  size_t o_ctl = 0, o_count = 0, o_hits = 0, zero_bytes = 0, o_index = 0, o_tkept = 0, o_tkept_begin = 0, o_tsym = 0, o_tsym_begin = 0, o_cub = 0,
-         cub_bytes = 0, o_kept = 0, o_kept_off = 0, o_rec = 0, total = 0;
+/* what grep_carve derives beside K's pointers */
+struct GrepRoom {
+  uint64_t n_blocks = 0;
+  size_t zero_bytes = 0; /* control words, count, hit counters: the head of the scratch, cleared in front of every call */
+  uint64_t *d_count = nullptr;
+  ACMRecord *rec = nullptr; /* K's, for the passes that write them */
+  uint32_t *index = nullptr, *tile_kept_begin = nullptr;
+  long long *tile_sym = nullptr, *tile_sym_begin = nullptr;
+  CubRoom cub;
 };
-GrepLayout
-grep_layout (uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
-  GrepLayout L;
-  L.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
-  L.n_tiles = (n_texts + GREP_TILE - 1) / GREP_TILE;
-  L.cub_bytes = std::max (exclusive_sum_bytes (L.n_tiles + 1), exclusive_sum_bytes64 (L.n_tiles + 1));
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (GrepCtl));
-  L.o_count = blob_reserve (cur, 8);
-  L.o_hits = blob_reserve (cur, (n_texts + 1) * 8);
-  L.zero_bytes = cur; /* control words, count, hit counters: cleared in front of every call */
-  L.o_index = blob_reserve (cur, L.n_blocks * 4);
-  L.o_tkept = blob_reserve (cur, (L.n_tiles + 1) * 4);
-  L.o_tkept_begin = blob_reserve (cur, (L.n_tiles + 1) * 4);
-  L.o_tsym = blob_reserve (cur, (L.n_tiles + 1) * 8);
-  L.o_tsym_begin = blob_reserve (cur, (L.n_tiles + 1) * 8);
-  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
-  L.o_kept = blob_reserve (cur, (n_texts + 1) * 4);
-  L.o_kept_off = blob_reserve (cur, (n_texts + 2) * 8);
-  L.o_rec = blob_reserve (cur, (size_t)capacity * sizeof (ACMRecord));
-  L.total = cur + 256;
-  return L;
-}
-
-/* ACM_GPU_GREP_TILE=<bytes of output>: the gather's tile, a multiple of 16 (tests; read at every call) */
-uint32_t
-grep_out_tile (void) {
-  const int t = env_int ("ACM_GPU_GREP_TILE", (int)GREP_OUT_TILE_DEFAULT);
-  return t >= (int)GREP_OUT_TILE_MIN && t <= (int)GREP_OUT_TILE_MAX && t % 16 == 0 ? (uint32_t)t : GREP_OUT_TILE_DEFAULT;
+GrepRoom
+grep_carve (Carve &c, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts, GrepK &K) {
+  GrepRoom R;
+  R.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
+  K.n_tiles = (n_texts + GREP_TILE - 1) / GREP_TILE;
+  K.ctl = c.take<GrepCtl> (1);
+  R.d_count = c.take<uint64_t> (1);
+  K.hits = c.take<unsigned long long> (n_texts + 1);
+  R.zero_bytes = c.used;
+  K.index = R.index = c.take<uint32_t> (R.n_blocks);
+  K.tile_kept = c.take<uint32_t> (K.n_tiles + 1);
+  K.tile_kept_begin = R.tile_kept_begin = c.take<uint32_t> (K.n_tiles + 1);
+  R.tile_sym = c.take<long long> (K.n_tiles + 1);
+  R.tile_sym_begin = c.take<long long> (K.n_tiles + 1);
+  K.tile_sym = reinterpret_cast<unsigned long long *> (R.tile_sym);
+  K.tile_sym_begin = reinterpret_cast<const unsigned long long *> (R.tile_sym_begin);
+  R.cub = cub_room (c, K.n_tiles + 1, K.n_tiles + 1);
+  K.kept = c.take<uint32_t> (n_texts + 1);
+  K.kept_off = c.take<unsigned long long> (n_texts + 2);
+  K.rec = R.rec = c.take<ACMRecord> ((size_t)capacity);
+  return R;
 }
 } // namespace
 
@@ -3997,7 +4072,10 @@ acm_gpu_grep_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t c
   (void)window_symbols; /* (what a window's scan needs beside its records belongs to the plan) */
   if (!plan || capacity == 0 || capacity >= (1ull << 31) || n_texts >= (1ull << 31))
     return 0;
-  return grep_layout (capacity, n_symbols, n_texts).total;
+  Carve c;
+  GrepK K{};
+  grep_carve (c, capacity, n_symbols, n_texts, K);
+  return c.total ();
 }
 
 extern "C" int
@@ -4005,49 +4083,27 @@ acm_gpu_grep_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, cons
                      uint64_t window_symbols, uint64_t capacity, uint64_t *d_hits, uint32_t *d_kept, uint64_t *d_n_kept, uint64_t *d_total,
                      uint64_t *d_need, void *d_out, uint64_t out_capacity, uint64_t *d_out_offsets, uint64_t *d_out_symbols, void *d_tmp,
                      size_t tmp_bytes, void *stream) {
-  if (!plan || !d_n_kept || !d_total || !d_need || (n_symbols && !d_text) || window_symbols == 0 || window_symbols % 16 || capacity == 0 ||
-      capacity >= (1ull << 31) || n_texts >= (1ull << 31) || flags > ACM_GREP_INVERT || (d_out != nullptr) != (d_out_symbols != nullptr))
+  if (!plan || !d_n_kept || !d_total || !d_need || (n_symbols && !d_text) || !window_ok (window_symbols, capacity) || n_texts >= (1ull << 31) ||
+      flags > ACM_GREP_INVERT || (d_out != nullptr) != (d_out_symbols != nullptr))
     return ACM_GPU_E_ARG;
   const uint32_t sb = plan->text_sym_bytes;
-  const uintptr_t t0 = reinterpret_cast<uintptr_t> (d_text), o0 = reinterpret_cast<uintptr_t> (d_out);
-  if (t0 % sb || o0 % sb || n_symbols >= (1ull << 56) / sb || out_capacity >= (1ull << 56) / sb)
-    return ACM_GPU_E_ARG;
-  if (d_out && n_symbols && out_capacity && t0 < o0 + out_capacity * sb && o0 < t0 + n_symbols * sb) /* the output is built from the text beside it */
+  if (!symbols_ok (d_text, n_symbols, sb) || !symbols_ok (d_out, out_capacity, sb) || (d_out && !apart (d_text, n_symbols, d_out, out_capacity, sb)))
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
-  if (n_texts == 0) { /* a batch of no texts: no symbol, nothing kept */
-    if (n_symbols)
-      return ACM_GPU_E_ARG;
-    HIP_TRY (hipSetDevice (plan->device));
-    for (uint64_t *d : { d_n_kept, d_total, d_need, d_out_symbols, d_out_offsets })
-      if (d)
-        HIP_TRY (hipMemsetAsync (d, 0, 8, st));
-    return ACM_GPU_OK;
-  }
-  const GrepLayout L = grep_layout (capacity, n_symbols, n_texts);
-  if (!d_offsets || !d_tmp || tmp_bytes < L.total)
+  if (n_texts == 0) /* (nothing kept) */
+    return empty_batch (plan, n_symbols, { d_n_kept, d_total, d_need, d_out_symbols, d_out_offsets }, st);
+  Carve carve (d_tmp);
+  GrepK K{};
+  const GrepRoom L = grep_carve (carve, capacity, n_symbols, n_texts, K);
+  if (!d_offsets || !d_tmp || tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  uint64_t *d_count = reinterpret_cast<uint64_t *> (t + L.o_count);
-  ACMRecord *rec = reinterpret_cast<ACMRecord *> (t + L.o_rec);
-  GrepK K{};
-  K.rec = rec;
   K.capacity = capacity;
-  K.n_dev = reinterpret_cast<const unsigned long long *> (d_count);
+  K.n_dev = reinterpret_cast<const unsigned long long *> (L.d_count);
   K.offsets = d_offsets;
   K.n_texts = n_texts;
   K.n_symbols = n_symbols;
-  K.index = reinterpret_cast<const uint32_t *> (t + L.o_index);
-  K.hits = reinterpret_cast<unsigned long long *> (t + L.o_hits);
   K.flags = flags;
-  K.tile_kept = reinterpret_cast<uint32_t *> (t + L.o_tkept);
-  K.tile_kept_begin = reinterpret_cast<const uint32_t *> (t + L.o_tkept_begin);
-  K.tile_sym = reinterpret_cast<unsigned long long *> (t + L.o_tsym);
-  K.tile_sym_begin = reinterpret_cast<const unsigned long long *> (t + L.o_tsym_begin);
-  K.n_tiles = L.n_tiles;
-  K.kept = reinterpret_cast<uint32_t *> (t + L.o_kept);
-  K.kept_off = reinterpret_cast<unsigned long long *> (t + L.o_kept_off);
   K.d_hits = reinterpret_cast<unsigned long long *> (d_hits);
   K.d_kept = d_kept;
   K.d_out_offsets = reinterpret_cast<unsigned long long *> (d_out_offsets);
@@ -4059,48 +4115,32 @@ acm_gpu_grep_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, cons
   K.out = static_cast<unsigned char *> (d_out);
   K.out_capacity = out_capacity;
   K.sb = sb;
-  K.tile_words = grep_out_tile () / 16;
-  K.ctl = reinterpret_cast<GrepCtl *> (t + L.o_ctl);
+  /* ACM_GPU_GREP_TILE=<bytes of output>: the gather's tile, a multiple of 16 (tests) */
+  K.tile_words = tunable ("ACM_GPU_GREP_TILE", GREP_OUT_TILE_DEFAULT, GREP_OUT_TILE_MIN, GREP_OUT_TILE_MAX, Tune::Mult16) / 16;
   K.error = error_word (plan);
-  HIP_TRY (hipMemsetAsync (t, 0, L.zero_bytes, st));
-  /* 1. the index and the check of offsets[], by batch_index_kernel's own launch rule */
-  BatchK B{};
-  B.offsets = d_offsets;
-  B.n_texts = n_texts;
-  B.n_symbols = n_symbols;
-  B.index = reinterpret_cast<uint32_t *> (t + L.o_index);
-  B.n_blocks = L.n_blocks;
-  B.ctl = &K.ctl->batch;
-  B.error = K.error;
-  const uint64_t many_texts = n_texts >= (1ull << 16) ? (uint64_t)plan->cu_count * 8 : 1;
-  hipLaunchKernelGGL (batch_index_kernel<false>, capped_grid (plan, std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, B);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (hipMemsetAsync (d_tmp, 0, L.zero_bytes, st));
+  /* 1. the index and the check of offsets[] */
+  if (const int bad = batch_index (plan, d_offsets, n_texts, n_symbols, L.index, L.n_blocks, &K.ctl->batch, K.error, st))
+    return bad;
   /* 2. every window's records, counted per text: the grid by the room, whatever the scan found */
   const dim3 hits_grid = capped_grid (plan, (capacity + GREP_THREADS - 1) / GREP_THREADS);
-  const int rc = scan_windows (plan, d_text, n_symbols, 0, window_symbols, rec, capacity, d_count, st, [&] (uint64_t read_begin) -> int {
+  const int rc = scan_windows (plan, d_text, n_symbols, 0, window_symbols, L.rec, capacity, L.d_count, st, [&] (uint64_t read_begin) -> int {
     K.read_begin = read_begin;
-    hipLaunchKernelGGL (grep_hits_kernel, hits_grid, dim3 (GREP_THREADS), 0, st, K);
-    HIP_TRY (hipGetLastError ());
+    HIP_TRY (launch (grep_hits_kernel, hits_grid, dim3 (GREP_THREADS), 0, st, K));
     return ACM_GPU_OK;
   });
   if (rc)
     return rc;
   /* 3. */
-  const dim3 tiles_grid = capped_grid (plan, L.n_tiles + 1);
-  hipLaunchKernelGGL (grep_flag_kernel<false>, tiles_grid, dim3 (GREP_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.tile_kept, reinterpret_cast<uint32_t *> (t + L.o_tkept_begin), (int)(L.n_tiles + 1), st));
-  cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_tsym),
-                                             reinterpret_cast<long long *> (t + L.o_tsym_begin), (int)(L.n_tiles + 1), st));
-  hipLaunchKernelGGL (grep_flag_kernel<true>, tiles_grid, dim3 (GREP_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  const dim3 tiles_grid = capped_grid (plan, K.n_tiles + 1);
+  HIP_TRY (launch (grep_flag_kernel<false>, tiles_grid, dim3 (GREP_THREADS), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, K.tile_kept, L.tile_kept_begin, K.n_tiles + 1, st));
+  HIP_TRY (exclusive_sum (L.cub, L.tile_sym, L.tile_sym_begin, K.n_tiles + 1, st));
+  HIP_TRY (launch (grep_flag_kernel<true>, tiles_grid, dim3 (GREP_THREADS), 0, st, K));
   /* 4. the grid by the room of the output, not by what the passes found */
   if (d_out) {
     const uint64_t tiles = (out_capacity * sb + 15 + 16) / ((uint64_t)K.tile_words * 16) + 1;
-    hipLaunchKernelGGL (grep_gather_kernel, capped_grid (plan, tiles), dim3 (GREP_THREADS), 0, st, K);
-    HIP_TRY (hipGetLastError ());
+    HIP_TRY (launch (grep_gather_kernel, capped_grid (plan, tiles), dim3 (GREP_THREADS), 0, st, K));
   }
   return ACM_GPU_OK;
 }
@@ -4185,35 +4225,28 @@ acm_gpu_grep_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uin
  * Count per tile, prefix sum over the tiles, write.  The plan gives its device, its caller symbol
  * size and its grid cap, nothing else. */
 namespace {
-struct SplitLayout {
-  uint32_t tile_words = 0;
-  uint64_t n_words = 0, n_tiles = 0;
-  size_t o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, total = 0;
+/* what split_carve derives beside K's pointers: the tile counts and their sums as the sum takes them */
+struct SplitRoom {
+  long long *count = nullptr, *begin = nullptr;
+  CubRoom cub;
 };
-
-/* ACM_GPU_SPLIT_TILE=<bytes of text>: the passes' tile, a multiple of 16 (tests; read at every call) */
-uint32_t
-split_tile (void) {
-  const int t = env_int ("ACM_GPU_SPLIT_TILE", (int)SPLIT_TILE_DEFAULT);
-  return t >= (int)SPLIT_TILE_MIN && t <= (int)SPLIT_TILE_MAX && t % 16 == 0 ? (uint32_t)t : SPLIT_TILE_DEFAULT;
-}
 
 /* the scratch is laid out for the most words a text of this size can touch (15 bytes off the grid);
  * n_words and n_tiles are those of the text's own address mod 16, `mis` */
-SplitLayout
-split_layout (uint64_t n_symbols, uint32_t sb, uint32_t mis) {
-  SplitLayout L;
-  L.tile_words = split_tile () / 16;
-  L.n_words = (n_symbols * sb + mis + 15) / 16;
-  L.n_tiles = (L.n_words + L.tile_words - 1) / L.tile_words;
-  const uint64_t most_tiles = ((n_symbols * sb + 30) / 16 + L.tile_words - 1) / L.tile_words;
-  L.cub_bytes = exclusive_sum_bytes64 (most_tiles + 1);
-  size_t cur = 0;
-  L.o_count = blob_reserve (cur, (most_tiles + 1) * 8);
-  L.o_begin = blob_reserve (cur, (most_tiles + 1) * 8);
-  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
-  L.total = cur + 256;
-  return L;
+SplitRoom
+split_carve (Carve &c, uint64_t n_symbols, uint32_t sb, uint32_t mis, SplitK &K) {
+  SplitRoom R;
+  /* ACM_GPU_SPLIT_TILE=<bytes of text>: the passes' tile, a multiple of 16 (tests) */
+  K.tile_words = tunable ("ACM_GPU_SPLIT_TILE", SPLIT_TILE_DEFAULT, SPLIT_TILE_MIN, SPLIT_TILE_MAX, Tune::Mult16) / 16;
+  K.n_words = (n_symbols * sb + mis + 15) / 16;
+  K.n_tiles = (K.n_words + K.tile_words - 1) / K.tile_words;
+  const uint64_t most_tiles = ((n_symbols * sb + 30) / 16 + K.tile_words - 1) / K.tile_words;
+  R.count = c.take<long long> (most_tiles + 1);
+  R.begin = c.take<long long> (most_tiles + 1);
+  R.cub = cub_room (c, 0, most_tiles + 1);
+  K.tile_count = reinterpret_cast<unsigned long long *> (R.count);
+  K.tile_begin = reinterpret_cast<const unsigned long long *> (R.begin);
+  return R;
 }
 
 bool
@@ -4222,18 +4255,12 @@ split_size_ok (const ACMPlan *plan, uint64_t n_symbols) {
 }
 
 template <int SB>
-void
-split_launch (const ACMPlan *plan, const SplitLayout &L, const SplitK &K, unsigned char *t, hipStream_t st, hipError_t *err) {
-  hipLaunchKernelGGL (split_count_kernel<SB>, capped_grid (plan, L.n_tiles + 1), dim3 (SPLIT_THREADS), 0, st, K);
-  if ((*err = hipGetLastError ()) != hipSuccess)
-    return;
-  size_t cub = L.cub_bytes;
-  *err = hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_count), reinterpret_cast<long long *> (t + L.o_begin),
-                                           (int)(L.n_tiles + 1), st);
-  if (*err != hipSuccess)
-    return;
-  hipLaunchKernelGGL (split_write_kernel<SB>, K.offsets ? capped_grid (plan, L.n_tiles) : dim3 (1), dim3 (SPLIT_THREADS), 0, st, K);
-  *err = hipGetLastError ();
+int
+split_launch (const ACMPlan *plan, const SplitRoom &L, const SplitK &K, hipStream_t st) {
+  HIP_TRY (launch (split_count_kernel<SB>, capped_grid (plan, K.n_tiles + 1), dim3 (SPLIT_THREADS), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, L.count, L.begin, K.n_tiles + 1, st));
+  HIP_TRY (launch (split_write_kernel<SB>, K.offsets ? capped_grid (plan, K.n_tiles) : dim3 (1), dim3 (SPLIT_THREADS), 0, st, K));
+  return ACM_GPU_OK;
 }
 } // namespace
 
@@ -4241,7 +4268,10 @@ extern "C" size_t
 acm_gpu_split_tmp_bytes (const ACMPlan *plan, uint64_t n_symbols) {
   if (!plan || !split_size_ok (plan, n_symbols))
     return 0;
-  return split_layout (n_symbols, plan->text_sym_bytes, 15).total;
+  Carve c;
+  SplitK K{};
+  split_carve (c, n_symbols, plan->text_sym_bytes, 15, K);
+  return c.total ();
 }
 
 extern "C" int
@@ -4254,8 +4284,10 @@ acm_gpu_split_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, con
   const uintptr_t t0 = reinterpret_cast<uintptr_t> (d_text);
   if (t0 % sb)
     return ACM_GPU_E_ARG;
-  const SplitLayout L = split_layout (n_symbols, sb, (uint32_t)(t0 & 15));
-  if (n_symbols && (!d_tmp || tmp_bytes < L.total))
+  Carve carve (d_tmp);
+  SplitK K{};
+  const SplitRoom L = split_carve (carve, n_symbols, sb, (uint32_t)(t0 & 15), K);
+  if (n_symbols && (!d_tmp || tmp_bytes < carve.total ()))
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
   HIP_TRY (hipSetDevice (plan->device));
@@ -4265,8 +4297,6 @@ acm_gpu_split_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, con
       HIP_TRY (hipMemsetAsync (d_offsets, 0, 8, st));
     return ACM_GPU_OK;
   }
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  SplitK K{};
   K.text = static_cast<const unsigned char *> (d_text);
   K.n_symbols = n_symbols;
   for (uint32_t j = 0; j < n_delims; j++) { /* the caller's symbols, bit for bit; below 4 bytes repeated over 32 bits */
@@ -4276,24 +4306,16 @@ acm_gpu_split_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, con
   }
   K.n_delims = n_delims;
   K.runs = flags == ACM_SPLIT_RUNS;
-  K.tile_words = L.tile_words;
-  K.n_words = L.n_words;
-  K.n_tiles = L.n_tiles;
-  K.tile_count = reinterpret_cast<unsigned long long *> (t + L.o_count);
-  K.tile_begin = reinterpret_cast<const unsigned long long *> (t + L.o_begin);
   K.offsets = reinterpret_cast<unsigned long long *> (d_offsets);
   K.capacity = capacity;
   K.d_n_texts = reinterpret_cast<unsigned long long *> (d_n_texts);
-  hipError_t err = hipSuccess;
   switch (sb) {
-  case 1: split_launch<1> (plan, L, K, t, st, &err); break;
-  case 2: split_launch<2> (plan, L, K, t, st, &err); break;
-  case 4: split_launch<4> (plan, L, K, t, st, &err); break;
-  case 8: split_launch<8> (plan, L, K, t, st, &err); break;
+  case 1: return split_launch<1> (plan, L, K, st);
+  case 2: return split_launch<2> (plan, L, K, st);
+  case 4: return split_launch<4> (plan, L, K, st);
+  case 8: return split_launch<8> (plan, L, K, st);
   default: return ACM_GPU_E_ARG;
   }
-  HIP_TRY (err);
-  return ACM_GPU_OK;
 }
 
 namespace {
@@ -4373,51 +4395,40 @@ acm_gpu_grep_lines_host (ACMPlan *plan, const void *text, uint64_t n_symbols, co
  * grep's window walk, every window's records reduced to partial (text, keyword) pairs, then the
  * pairs bucketed by text, merged per row and compacted into the caller's CSR arrays. */
 namespace {
-struct TallyBatchLayout {
-  uint64_t n_blocks = 0, n_keywords = 0;
-  size_t o_ctl = 0, o_count = 0, o_hist = 0, o_row_nnz = 0, zero_bytes = 0, o_index = 0, o_begin = 0, o_row_ptr = 0, o_wide = 0, o_cub = 0, cub_bytes = 0,
-         o_pkey = 0, o_pcnt = 0, o_bkw = 0, o_btext = 0, o_bval = 0, o_whist = 0, o_rec = 0, total = 0;
+/* what tally_batch_carve derives beside K's pointers */
+struct TallyBatchRoom {
+  uint64_t n_blocks = 0;
+  size_t zero_bytes = 0; /* control words, count, pairs per text, row lengths: the head of the scratch, cleared in front of every call */
+  uint64_t *d_count = nullptr;
+  ACMRecord *rec = nullptr; /* K's, for the passes that write them */
+  uint32_t *index = nullptr, *begin = nullptr;
+  long long *row_nnz = nullptr, *row_ptr = nullptr;
+  CubRoom cub;
 };
-TallyBatchLayout
-tally_batch_layout (const ACMPlan *plan, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts) {
-  TallyBatchLayout L;
-  L.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
-  L.n_keywords = (uint64_t)plan->covered_keywords + 1;
-  L.cub_bytes = std::max (exclusive_sum_bytes (n_texts + 1), exclusive_sum_bytes64 (n_texts + 1));
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (TbCtl));
-  L.o_count = blob_reserve (cur, 8);
-  L.o_hist = blob_reserve (cur, (n_texts + 1) * 4);
-  L.o_row_nnz = blob_reserve (cur, (n_texts + 1) * 8);
-  L.zero_bytes = cur; /* control words, count, pairs per text, row lengths: cleared in front of every call */
-  L.o_index = blob_reserve (cur, L.n_blocks * 4);
-  L.o_begin = blob_reserve (cur, (n_texts + 1) * 4);
-  L.o_row_ptr = blob_reserve (cur, (n_texts + 1) * 8);
-  L.o_wide = blob_reserve (cur, (n_texts + 1) * 4);
-  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
-  L.o_pkey = blob_reserve (cur, (size_t)pair_capacity * 8);
-  L.o_pcnt = blob_reserve (cur, (size_t)pair_capacity * 4);
-  L.o_bkw = blob_reserve (cur, (size_t)pair_capacity * 4);
-  L.o_btext = blob_reserve (cur, (size_t)pair_capacity * 4);
-  L.o_bval = blob_reserve (cur, (size_t)pair_capacity * 8);
-  L.o_whist = blob_reserve (cur, (size_t)TB_WIDE_BLOCKS * L.n_keywords * 8);
-  L.o_rec = blob_reserve (cur, (size_t)capacity * sizeof (ACMRecord));
-  L.total = cur + 256;
-  return L;
-}
-
-/* ACM_GPU_TALLY_BATCH_SLOTS=<a power of two from 8 to 4,096>: the slots of a block's LDS table;
- * ACM_GPU_TALLY_BATCH_ROW=<1 to 2,048>: R, the entries of the widest row merged in LDS (tests,
- * experiments; read at every call) */
-uint32_t
-tally_batch_slots (void) {
-  const int s = env_int ("ACM_GPU_TALLY_BATCH_SLOTS", (int)TB_SLOTS_DEFAULT);
-  return s >= (int)TB_SLOTS_MIN && s <= (int)TB_SLOTS_MAX && (s & (s - 1)) == 0 ? (uint32_t)s : TB_SLOTS_DEFAULT;
-}
-uint32_t
-tally_batch_row (void) {
-  const int r = env_int ("ACM_GPU_TALLY_BATCH_ROW", (int)TB_ROW_DEFAULT);
-  return r >= 1 && r <= (int)TB_ROW_MAX ? (uint32_t)r : TB_ROW_DEFAULT;
+TallyBatchRoom
+tally_batch_carve (Carve &c, const ACMPlan *plan, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts, TbK &K) {
+  TallyBatchRoom R;
+  R.n_blocks = (n_symbols >> BATCH_BLOCK_LOG2) + 2;
+  K.ctl = c.take<TbCtl> (1);
+  R.d_count = c.take<uint64_t> (1);
+  K.hist = c.take<uint32_t> (n_texts + 1);
+  R.row_nnz = c.take<long long> (n_texts + 1);
+  R.zero_bytes = c.used;
+  K.index = R.index = c.take<uint32_t> (R.n_blocks);
+  K.begin = R.begin = c.take<uint32_t> (n_texts + 1);
+  R.row_ptr = c.take<long long> (n_texts + 1);
+  K.wide = c.take<uint32_t> (n_texts + 1);
+  R.cub = cub_room (c, n_texts + 1, n_texts + 1);
+  K.mval = K.pkey = c.take<unsigned long long> ((size_t)pair_capacity); /* (the partial pairs are dead behind the scatter: */
+  K.mcol = K.pcnt = c.take<uint32_t> ((size_t)pair_capacity);           /* the merged rows take their memory) */
+  K.bkw = c.take<uint32_t> ((size_t)pair_capacity);
+  K.btext = c.take<uint32_t> ((size_t)pair_capacity);
+  K.bval = c.take<unsigned long long> ((size_t)pair_capacity);
+  K.whist = c.take<unsigned long long> ((size_t)TB_WIDE_BLOCKS * ((uint64_t)plan->covered_keywords + 1));
+  K.rec = R.rec = c.take<ACMRecord> ((size_t)capacity);
+  K.row_nnz = reinterpret_cast<unsigned long long *> (R.row_nnz);
+  K.row_ptr = reinterpret_cast<const unsigned long long *> (R.row_ptr);
+  return R;
 }
 } // namespace
 
@@ -4427,67 +4438,46 @@ acm_gpu_tally_batch_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uin
   (void)window_symbols; /* (what a window's scan needs beside its records belongs to the plan) */
   if (!plan || capacity == 0 || capacity >= (1ull << 31) || pair_capacity == 0 || pair_capacity >= (1ull << 31) || n_texts >= (1ull << 31))
     return 0;
-  return tally_batch_layout (plan, capacity, pair_capacity, n_symbols, n_texts).total;
+  Carve c;
+  TbK K{};
+  tally_batch_carve (c, plan, capacity, pair_capacity, n_symbols, n_texts, K);
+  return c.total ();
 }
 
 extern "C" int
 acm_gpu_tally_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint64_t window_symbols,
                             uint64_t capacity, uint64_t pair_capacity, uint64_t *d_row_ptr, uint32_t *d_col, uint64_t *d_val, uint64_t *d_nnz,
                             uint64_t *d_total, uint64_t *d_need, uint64_t *d_need_pairs, void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!plan || !d_row_ptr || !d_col || !d_val || !d_nnz || !d_total || !d_need || !d_need_pairs || (n_symbols && !d_text) || window_symbols == 0 ||
-      window_symbols % 16 || capacity == 0 || capacity >= (1ull << 31) || pair_capacity == 0 || pair_capacity >= (1ull << 31) ||
-      n_texts >= (1ull << 31))
-    return ACM_GPU_E_ARG;
-  const uint32_t sb = plan->text_sym_bytes;
-  if (reinterpret_cast<uintptr_t> (d_text) % sb || n_symbols >= (1ull << 56) / sb)
+  if (!plan || !d_row_ptr || !d_col || !d_val || !d_nnz || !d_total || !d_need || !d_need_pairs || (n_symbols && !d_text) ||
+      !window_ok (window_symbols, capacity) || pair_capacity == 0 || pair_capacity >= (1ull << 31) || n_texts >= (1ull << 31) ||
+      !symbols_ok (d_text, n_symbols, plan->text_sym_bytes))
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
-  if (n_texts == 0) { /* a batch of no texts: no symbol, an empty matrix */
-    if (n_symbols)
-      return ACM_GPU_E_ARG;
-    HIP_TRY (hipSetDevice (plan->device));
-    for (uint64_t *d : { d_row_ptr, d_nnz, d_total, d_need, d_need_pairs })
-      HIP_TRY (hipMemsetAsync (d, 0, 8, st));
-    return ACM_GPU_OK;
-  }
-  const TallyBatchLayout L = tally_batch_layout (plan, capacity, pair_capacity, n_symbols, n_texts);
-  if (!d_offsets || !d_tmp || tmp_bytes < L.total)
+  if (n_texts == 0) /* (an empty matrix) */
+    return empty_batch (plan, n_symbols, { d_row_ptr, d_nnz, d_total, d_need, d_need_pairs }, st);
+  Carve carve (d_tmp);
+  TbK K{};
+  const TallyBatchRoom L = tally_batch_carve (carve, plan, capacity, pair_capacity, n_symbols, n_texts, K);
+  if (!d_offsets || !d_tmp || tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  uint64_t *d_count = reinterpret_cast<uint64_t *> (t + L.o_count);
-  ACMRecord *rec = reinterpret_cast<ACMRecord *> (t + L.o_rec);
-  TbK K{};
-  K.rec = rec;
   K.capacity = capacity;
-  K.n_dev = reinterpret_cast<const unsigned long long *> (d_count);
+  K.n_dev = reinterpret_cast<const unsigned long long *> (L.d_count);
   K.offsets = d_offsets;
   K.n_texts = n_texts;
   K.n_symbols = n_symbols;
-  K.index = reinterpret_cast<const uint32_t *> (t + L.o_index);
   K.n_keywords = plan->covered_keywords;
-  K.slots = tally_batch_slots ();
+  /* ACM_GPU_TALLY_BATCH_SLOTS=<a power of two from 8 to 4,096>: the slots of a block's LDS table;
+   * ACM_GPU_TALLY_BATCH_ROW=<1 to 2,048>: R, the entries of the widest row merged in LDS (tests, experiments) */
+  K.slots = tunable ("ACM_GPU_TALLY_BATCH_SLOTS", TB_SLOTS_DEFAULT, TB_SLOTS_MIN, TB_SLOTS_MAX, Tune::Pow2);
   K.shift = 64;
   for (uint32_t s = K.slots; s > 1; s >>= 1)
     K.shift--;
   K.pair_capacity = pair_capacity;
-  K.pkey = reinterpret_cast<unsigned long long *> (t + L.o_pkey);
-  K.pcnt = reinterpret_cast<uint32_t *> (t + L.o_pcnt);
-  K.hist = reinterpret_cast<uint32_t *> (t + L.o_hist);
-  K.begin = reinterpret_cast<const uint32_t *> (t + L.o_begin);
-  K.bkw = reinterpret_cast<uint32_t *> (t + L.o_bkw);
-  K.btext = reinterpret_cast<uint32_t *> (t + L.o_btext);
-  K.bval = reinterpret_cast<unsigned long long *> (t + L.o_bval);
-  K.row = tally_batch_row ();
+  K.row = tunable ("ACM_GPU_TALLY_BATCH_ROW", TB_ROW_DEFAULT, 1, TB_ROW_MAX, Tune::Any);
   K.row_p2 = 1;
   while (K.row_p2 < K.row)
     K.row_p2 <<= 1;
-  K.mcol = K.pcnt; /* (the partial pairs are dead behind the scatter) */
-  K.mval = K.pkey;
-  K.row_nnz = reinterpret_cast<unsigned long long *> (t + L.o_row_nnz);
-  K.wide = reinterpret_cast<uint32_t *> (t + L.o_wide);
-  K.whist = reinterpret_cast<unsigned long long *> (t + L.o_whist);
-  K.row_ptr = reinterpret_cast<const unsigned long long *> (t + L.o_row_ptr);
   K.d_row_ptr = reinterpret_cast<unsigned long long *> (d_row_ptr);
   K.d_col = d_col;
   K.d_val = reinterpret_cast<unsigned long long *> (d_val);
@@ -4495,52 +4485,33 @@ acm_gpu_tally_batch_device (ACMPlan *plan, const void *d_text, uint64_t n_symbol
   K.d_total = reinterpret_cast<unsigned long long *> (d_total);
   K.d_need = reinterpret_cast<unsigned long long *> (d_need);
   K.d_need_pairs = reinterpret_cast<unsigned long long *> (d_need_pairs);
-  K.ctl = reinterpret_cast<TbCtl *> (t + L.o_ctl);
   K.error = error_word (plan);
-  HIP_TRY (hipMemsetAsync (t, 0, L.zero_bytes, st));
-  /* 1. the index and the check of offsets[], as acm_gpu_grep_device launches it */
-  BatchK B{};
-  B.offsets = d_offsets;
-  B.n_texts = n_texts;
-  B.n_symbols = n_symbols;
-  B.index = reinterpret_cast<uint32_t *> (t + L.o_index);
-  B.n_blocks = L.n_blocks;
-  B.ctl = &K.ctl->batch;
-  B.error = K.error;
-  const uint64_t many_texts = n_texts >= (1ull << 16) ? (uint64_t)plan->cu_count * 8 : 1;
-  hipLaunchKernelGGL (batch_index_kernel<false>, capped_grid (plan, std::max ((L.n_blocks + BATCH_THREADS - 1) / BATCH_THREADS, many_texts)), dim3 (BATCH_THREADS), 0, st, B);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (hipMemsetAsync (d_tmp, 0, L.zero_bytes, st));
+  /* 1. the index and the check of offsets[] */
+  if (const int bad = batch_index (plan, d_offsets, n_texts, n_symbols, L.index, L.n_blocks, &K.ctl->batch, K.error, st))
+    return bad;
   /* 2. every window's records to partial pairs: the grid by the room, two blocks per CU at the most */
   const dim3 pairs_grid = capped_grid (plan, (capacity + TB_THREADS - 1) / TB_THREADS, 2);
   const size_t table_bytes = (size_t)K.slots * 12;
-  const int rc = scan_windows (plan, d_text, n_symbols, 0, window_symbols, rec, capacity, d_count, st, [&] (uint64_t read_begin) -> int {
+  const int rc = scan_windows (plan, d_text, n_symbols, 0, window_symbols, L.rec, capacity, L.d_count, st, [&] (uint64_t read_begin) -> int {
     K.read_begin = read_begin;
-    hipLaunchKernelGGL (tb_pairs_kernel, pairs_grid, dim3 (TB_THREADS), table_bytes, st, K);
-    HIP_TRY (hipGetLastError ());
+    HIP_TRY (launch (tb_pairs_kernel, pairs_grid, dim3 (TB_THREADS), table_bytes, st, K));
     return ACM_GPU_OK;
   });
   if (rc)
     return rc;
   /* 3. the grids by the room of the pairs */
   const dim3 pair_grid = capped_grid (plan, (pair_capacity + TB_THREADS - 1) / TB_THREADS);
-  hipLaunchKernelGGL (tb_hist_kernel, pair_grid, dim3 (TB_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.hist, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(n_texts + 1), st));
-  hipLaunchKernelGGL (tb_scatter_kernel, pair_grid, dim3 (TB_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (tb_hist_kernel, pair_grid, dim3 (TB_THREADS), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, K.hist, L.begin, n_texts + 1, st));
+  HIP_TRY (launch (tb_scatter_kernel, pair_grid, dim3 (TB_THREADS), 0, st, K));
   /* 4. */
-  hipLaunchKernelGGL (tb_merge_kernel, capped_grid (plan, (n_texts + TB_TILE - 1) / TB_TILE), dim3 (TB_THREADS), (size_t)K.row_p2 * 16 + ((size_t)K.row_p2 + 1) * 4,
-                      st, K);
-  HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (tb_wide_kernel, dim3 (TB_WIDE_BLOCKS), dim3 (TB_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (tb_merge_kernel, capped_grid (plan, (n_texts + TB_TILE - 1) / TB_TILE), dim3 (TB_THREADS), (size_t)K.row_p2 * 16 + ((size_t)K.row_p2 + 1) * 4,
+                   st, K));
+  HIP_TRY (launch (tb_wide_kernel, dim3 (TB_WIDE_BLOCKS), dim3 (TB_THREADS), 0, st, K));
   /* 5. */
-  cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_row_nnz),
-                                             reinterpret_cast<long long *> (t + L.o_row_ptr), (int)(n_texts + 1), st));
-  hipLaunchKernelGGL (tb_finish_kernel, capped_grid (plan, (std::max (pair_capacity, n_texts + 1) + TB_THREADS - 1) / TB_THREADS), dim3 (TB_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (exclusive_sum (L.cub, L.row_nnz, L.row_ptr, n_texts + 1, st));
+  HIP_TRY (launch (tb_finish_kernel, capped_grid (plan, (std::max (pair_capacity, n_texts + 1) + TB_THREADS - 1) / TB_THREADS), dim3 (TB_THREADS), 0, st, K));
   return ACM_GPU_OK;
 }
 
@@ -4626,35 +4597,38 @@ struct ACMRules {
 };
 
 namespace {
-struct RulesLayout {
-  uint32_t wide_p2 = 1;
-  size_t o_ctl = 0, o_cnt = 0, zero_bytes = 0, o_ptr = 0, o_wide = 0, o_cub = 0, cub_bytes = 0, o_wkey = 0, o_wd = 0, total = 0;
+/* what rules_carve derives beside K's pointers */
+struct RulesRoom {
+  size_t zero_bytes = 0; /* control words and the rows' counts: the head of the scratch, cleared in front of every call */
+  long long *cnt = nullptr, *ptr = nullptr; /* K's, as the sum takes them */
+  CubRoom cub;
 };
-RulesLayout
-rules_layout (const ACMRules *rules, uint64_t n_texts) {
-  RulesLayout L;
-  while (L.wide_p2 < rules->n_postings)
-    L.wide_p2 <<= 1;
-  L.cub_bytes = exclusive_sum_bytes64 (n_texts + 1);
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (RulesCtl));
-  L.o_cnt = blob_reserve (cur, (n_texts + 1) * 8);
-  L.zero_bytes = cur; /* control words and the rows' counts: cleared in front of every call */
-  L.o_ptr = blob_reserve (cur, (n_texts + 1) * 8);
-  L.o_wide = blob_reserve (cur, (n_texts + 1) * 4);
-  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
-  L.o_wkey = blob_reserve (cur, (size_t)RULES_WIDE_BLOCKS * L.wide_p2 * 4);
-  L.o_wd = blob_reserve (cur, (size_t)RULES_WIDE_BLOCKS * ((size_t)rules->n_postings + 1) * 4);
-  L.total = cur + 256;
-  return L;
+RulesRoom
+rules_carve (Carve &c, const ACMRules *rules, uint64_t n_texts, RulesK &K) {
+  RulesRoom R;
+  K.wide_p2 = 1;
+  while (K.wide_p2 < rules->n_postings)
+    K.wide_p2 <<= 1;
+  K.ctl = c.take<RulesCtl> (1);
+  R.cnt = c.take<long long> (n_texts + 1);
+  R.zero_bytes = c.used;
+  R.ptr = c.take<long long> (n_texts + 1);
+  K.wide = c.take<uint32_t> (n_texts + 1);
+  R.cub = cub_room (c, 0, n_texts + 1);
+  K.wkey = c.take<uint32_t> ((size_t)RULES_WIDE_BLOCKS * K.wide_p2);
+  K.wd = c.take<int32_t> ((size_t)RULES_WIDE_BLOCKS * ((size_t)rules->n_postings + 1));
+  K.cnt = reinterpret_cast<unsigned long long *> (R.cnt);
+  K.ptr = reinterpret_cast<const unsigned long long *> (R.ptr);
+  return R;
 }
 
-/* ACM_GPU_RULES_ITEMS=<1 to 4,096>: the widest text, in items, of the fast form (tests, experiments;
- * read at every call) */
-uint32_t
-rules_items (void) {
-  const int r = env_int ("ACM_GPU_RULES_ITEMS", (int)RULES_ITEMS_DEFAULT);
-  return r >= 1 && r <= (int)RULES_ITEMS_MAX ? (uint32_t)r : RULES_ITEMS_DEFAULT;
+/* acm_gpu_rules_matrix_tmp_bytes behind its checks */
+size_t
+rules_bytes (const ACMRules *rules, uint64_t n_texts) {
+  Carve c;
+  RulesK K{};
+  rules_carve (c, rules, n_texts, K);
+  return c.total ();
 }
 
 /* the matrix calls' own arguments: the set is this plan's device's, the outputs are there */
@@ -4670,9 +4644,9 @@ int
 rules_evaluate (ACMPlan *plan, const ACMRules *rules, const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_val, uint64_t n_texts,
                 uint64_t *d_fired_ptr, uint32_t *d_fired, uint64_t fired_capacity, uint64_t *d_n_fired, void *d_tmp, hipStream_t st, const TbCtl *tb,
                 uint64_t tb_capacity, uint64_t tb_pair_capacity) {
-  const RulesLayout L = rules_layout (rules, n_texts);
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
+  Carve carve (d_tmp);
   RulesK K{};
+  const RulesRoom L = rules_carve (carve, rules, n_texts, K);
   K.row_ptr = reinterpret_cast<const unsigned long long *> (d_row_ptr);
   K.col = d_col;
   K.val = reinterpret_cast<const unsigned long long *> (d_val);
@@ -4686,17 +4660,11 @@ rules_evaluate (ACMPlan *plan, const ACMRules *rules, const uint64_t *d_row_ptr,
   K.n_always = rules->n_always;
   K.n_postings = rules->n_postings;
   K.forms = rules->d_forms;
-  K.items = rules_items ();
+  /* ACM_GPU_RULES_ITEMS=<1 to 4,096>: the widest text, in items, of the fast form (tests, experiments) */
+  K.items = tunable ("ACM_GPU_RULES_ITEMS", RULES_ITEMS_DEFAULT, 1, RULES_ITEMS_MAX, Tune::Any);
   K.items_p2 = 1;
   while (K.items_p2 < K.items)
     K.items_p2 <<= 1;
-  K.wide_p2 = L.wide_p2;
-  K.cnt = reinterpret_cast<unsigned long long *> (t + L.o_cnt);
-  K.ptr = reinterpret_cast<const unsigned long long *> (t + L.o_ptr);
-  K.wide = reinterpret_cast<uint32_t *> (t + L.o_wide);
-  K.wkey = reinterpret_cast<uint32_t *> (t + L.o_wkey);
-  K.wd = reinterpret_cast<int32_t *> (t + L.o_wd);
-  K.ctl = reinterpret_cast<RulesCtl *> (t + L.o_ctl);
   K.tb = tb;
   K.tb_capacity = tb_capacity;
   K.tb_pair_capacity = tb_pair_capacity;
@@ -4705,50 +4673,51 @@ rules_evaluate (ACMPlan *plan, const ACMRules *rules, const uint64_t *d_row_ptr,
   K.d_fired = d_fired;
   K.fired_capacity = fired_capacity;
   K.error = error_word (plan);
-  HIP_TRY (hipMemsetAsync (t, 0, L.zero_bytes, st));
+  HIP_TRY (hipMemsetAsync (d_tmp, 0, L.zero_bytes, st));
   const dim3 flat_grid = capped_grid (plan, (n_texts + 1 + 255) / 256);
   const dim3 fast_grid = capped_grid (plan, n_texts, RULES_FAST_PER_CU);
   const size_t fast_lds = (size_t)K.items_p2 * 4 + ((size_t)K.items + 1) * 4;
   /* 1. */
-  hipLaunchKernelGGL (rules_check_kernel, flat_grid, dim3 (256), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (rules_check_kernel, flat_grid, dim3 (256), 0, st, K));
   /* 2. */
-  hipLaunchKernelGGL (rules_fast_kernel<false>, fast_grid, dim3 (WAVE), fast_lds, st, K);
-  HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (rules_wide_kernel<false>, dim3 (RULES_WIDE_BLOCKS), dim3 (RULES_WIDE_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (rules_fast_kernel<false>, fast_grid, dim3 (WAVE), fast_lds, st, K));
+  HIP_TRY (launch (rules_wide_kernel<false>, dim3 (RULES_WIDE_BLOCKS), dim3 (RULES_WIDE_THREADS), 0, st, K));
   /* 3. */
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_cnt), reinterpret_cast<long long *> (t + L.o_ptr),
-                                             (int)(n_texts + 1), st));
-  hipLaunchKernelGGL (rules_finish_kernel, flat_grid, dim3 (256), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (exclusive_sum (L.cub, L.cnt, L.ptr, n_texts + 1, st));
+  HIP_TRY (launch (rules_finish_kernel, flat_grid, dim3 (256), 0, st, K));
   /* 4. */
   if (d_fired) {
-    hipLaunchKernelGGL (rules_fast_kernel<true>, fast_grid, dim3 (WAVE), fast_lds, st, K);
-    HIP_TRY (hipGetLastError ());
-    hipLaunchKernelGGL (rules_wide_kernel<true>, dim3 (RULES_WIDE_BLOCKS), dim3 (RULES_WIDE_THREADS), 0, st, K);
-    HIP_TRY (hipGetLastError ());
+    HIP_TRY (launch (rules_fast_kernel<true>, fast_grid, dim3 (WAVE), fast_lds, st, K));
+    HIP_TRY (launch (rules_wide_kernel<true>, dim3 (RULES_WIDE_BLOCKS), dim3 (RULES_WIDE_THREADS), 0, st, K));
   }
   return ACM_GPU_OK;
 }
 
 /* where acm_gpu_rules_device keeps the count matrix and tally_batch's scratch inside its own */
-struct RulesCallLayout {
-  size_t o_row_ptr = 0, o_col = 0, o_val = 0, o_nnz = 0, o_tally = 0, tally_bytes = 0, total = 0;
+struct RulesCallRoom {
+  uint64_t *row_ptr = nullptr, *val = nullptr, *nnz = nullptr;
+  uint32_t *col = nullptr;
+  unsigned char *tally = nullptr;
+  size_t tally_bytes = 0;
+  const TbCtl *tb = nullptr; /* tally_batch's control words, where it will put them */
 };
-RulesCallLayout
-rules_call_layout (const ACMPlan *plan, const ACMRules *rules, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts) {
-  RulesCallLayout L;
-  size_t cur = rules_layout (rules, n_texts).total;
-  L.o_row_ptr = blob_reserve (cur, (n_texts + 1) * 8);
-  L.o_col = blob_reserve (cur, (size_t)pair_capacity * 4);
-  L.o_val = blob_reserve (cur, (size_t)pair_capacity * 8);
-  L.o_nnz = blob_reserve (cur, 8);
-  L.tally_bytes = tally_batch_layout (plan, capacity, pair_capacity, n_symbols, n_texts).total;
-  L.o_tally = blob_reserve (cur, L.tally_bytes);
-  L.total = cur + 256;
-  return L;
+RulesCallRoom
+rules_call_carve (Carve &c, const ACMPlan *plan, const ACMRules *rules, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts) {
+  RulesCallRoom R;
+  c.used = rules_bytes (rules, n_texts); /* (rules_evaluate's scratch lies in front, as the matrix call has it) */
+  R.row_ptr = c.take<uint64_t> (n_texts + 1);
+  R.col = c.take<uint32_t> ((size_t)pair_capacity);
+  R.val = c.take<uint64_t> ((size_t)pair_capacity);
+  R.nnz = c.take<uint64_t> (1);
+  Carve sized;
+  TbK T{};
+  tally_batch_carve (sized, plan, capacity, pair_capacity, n_symbols, n_texts, T);
+  R.tally_bytes = sized.total ();
+  R.tally = c.take (R.tally_bytes);
+  Carve inner (R.tally);
+  tally_batch_carve (inner, plan, capacity, pair_capacity, n_symbols, n_texts, T);
+  R.tb = T.ctl;
+  return R;
 }
 } // namespace
 
@@ -4842,7 +4811,7 @@ extern "C" size_t
 acm_gpu_rules_matrix_tmp_bytes (const ACMPlan *plan, const ACMRules *rules, uint64_t n_texts) {
   if (!plan || !rules || n_texts >= (1ull << 31))
     return 0;
-  return rules_layout (rules, n_texts).total;
+  return rules_bytes (rules, n_texts);
 }
 
 extern "C" int
@@ -4858,7 +4827,7 @@ acm_gpu_rules_matrix_device (ACMPlan *plan, const ACMRules *rules, const uint64_
     HIP_TRY (hipMemsetAsync (d_n_fired, 0, 8, st));
     return ACM_GPU_OK;
   }
-  if (!d_row_ptr || !d_tmp || tmp_bytes < rules_layout (rules, n_texts).total)
+  if (!d_row_ptr || !d_tmp || tmp_bytes < rules_bytes (rules, n_texts))
     return ACM_GPU_E_ARG;
   return rules_evaluate (plan, rules, d_row_ptr, d_col, d_val, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired, d_tmp, st, nullptr, 0, 0);
 }
@@ -4868,7 +4837,9 @@ acm_gpu_rules_tmp_bytes (const ACMPlan *plan, const ACMRules *rules, uint64_t wi
                          uint64_t n_symbols, uint64_t n_texts) {
   if (!rules || !acm_gpu_tally_batch_tmp_bytes (plan, window_symbols, capacity, pair_capacity, n_symbols, n_texts))
     return 0;
-  return rules_call_layout (plan, rules, capacity, pair_capacity, n_symbols, n_texts).total;
+  Carve c;
+  rules_call_carve (c, plan, rules, capacity, pair_capacity, n_symbols, n_texts);
+  return c.total ();
 }
 
 extern "C" int
@@ -4879,26 +4850,21 @@ acm_gpu_rules_device (ACMPlan *plan, const ACMRules *rules, const void *d_text, 
   if (!rules_args_ok (plan, rules, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired) || !d_tmp || capacity == 0 || capacity >= (1ull << 31) ||
       pair_capacity == 0 || pair_capacity >= (1ull << 31))
     return ACM_GPU_E_ARG;
-  const RulesCallLayout L = rules_call_layout (plan, rules, capacity, pair_capacity, n_symbols, n_texts);
-  if (tmp_bytes < L.total)
+  Carve carve (d_tmp);
+  const RulesCallRoom L = rules_call_carve (carve, plan, rules, capacity, pair_capacity, n_symbols, n_texts);
+  if (tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  uint64_t *d_row_ptr = reinterpret_cast<uint64_t *> (t + L.o_row_ptr), *d_val = reinterpret_cast<uint64_t *> (t + L.o_val),
-           *d_nnz = reinterpret_cast<uint64_t *> (t + L.o_nnz);
-  uint32_t *d_col = reinterpret_cast<uint32_t *> (t + L.o_col);
   /* (the remaining arguments are tally_batch's to check) */
-  if (const int rc = acm_gpu_tally_batch_device (plan, d_text, n_symbols, d_offsets, n_texts, window_symbols, capacity, pair_capacity, d_row_ptr, d_col,
-                                                 d_val, d_nnz, d_total, d_need, d_need_pairs, t + L.o_tally, L.tally_bytes, stream))
+  if (const int rc = acm_gpu_tally_batch_device (plan, d_text, n_symbols, d_offsets, n_texts, window_symbols, capacity, pair_capacity, L.row_ptr, L.col,
+                                                 L.val, L.nnz, d_total, d_need, d_need_pairs, L.tally, L.tally_bytes, stream))
     return rc;
   if (n_texts == 0) {
     HIP_TRY (hipMemsetAsync (d_fired_ptr, 0, 8, st));
     HIP_TRY (hipMemsetAsync (d_n_fired, 0, 8, st));
     return ACM_GPU_OK;
   }
-  /* tally_batch's control words lie at the head of its scratch */
-  const TbCtl *tb = reinterpret_cast<const TbCtl *> (t + L.o_tally + tally_batch_layout (plan, capacity, pair_capacity, n_symbols, n_texts).o_ctl);
-  return rules_evaluate (plan, rules, d_row_ptr, d_col, d_val, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired, d_tmp, st, tb, capacity,
+  return rules_evaluate (plan, rules, L.row_ptr, L.col, L.val, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired, d_tmp, st, L.tb, capacity,
                          pair_capacity);
 }
 
@@ -4973,46 +4939,53 @@ acm_gpu_rules_host (ACMPlan *plan, const void *text, const uint64_t *offsets, ui
  * The passes over a record set in canonical order; acm_gpu_scan_select_device runs them behind the
  * ordered scan. */
 namespace {
-struct SelectLayout {
-  uint64_t n_chunks = 0;
-  size_t o_ctl = 0, o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, o_map = 0, o_entry = 0, o_base = 0, o_keyed = 0, o_work = 0, work_bytes = 0,
-         total = 0;
+/* what select_carve derives beside K's pointers */
+struct SelectRoom {
+  uint32_t *chunk_begin = nullptr; /* K.chunk_begin, for the sum that writes it */
+  CubRoom cub;
+  size_t work_bytes = 0; /* of K.cand: the order pass's scratch; the candidates take its place when the order is made */
 };
 /* nothing here depends on the environment: the maps and the tiles' words are sized for every T */
-SelectLayout
-select_layout (const ACMPlan *plan, uint64_t capacity, uint64_t span) {
-  SelectLayout L;
-  L.n_chunks = (capacity + SELECT_CHUNK - 1) / SELECT_CHUNK;
-  const size_t cub = exclusive_sum_bytes (L.n_chunks + 1);
-  L.cub_bytes = cub;
-  /* the order pass's scratch; the candidates take its place when the order is made */
-  L.work_bytes = std::max (acm_gpu_order_tmp_bytes (plan, capacity, span), (size_t)capacity * sizeof (ACMRecord) + 256);
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (SelectCtl));
-  L.o_count = blob_reserve (cur, (L.n_chunks + 1) * 4);
-  L.o_begin = blob_reserve (cur, (L.n_chunks + 1) * 4);
-  L.o_cub = blob_reserve (cur, cub + 16);
-  L.o_map = blob_reserve (cur, ((size_t)capacity + SELECT_TILE_MAX) * 4); /* tiles x E <= capacity + T words */
-  L.o_entry = blob_reserve (cur, ((size_t)capacity / SELECT_TILE_MIN + 1) * 4);
-  L.o_base = blob_reserve (cur, ((size_t)capacity / SELECT_TILE_MIN + 1) * 4);
-  L.o_keyed = blob_reserve (cur, (size_t)(capacity ? capacity : 1) * sizeof (ACMRecord));
-  L.o_work = blob_reserve (cur, L.work_bytes);
-  L.total = cur + 256;
-  return L;
+SelectRoom
+select_carve (Carve &c, const ACMPlan *plan, uint64_t capacity, uint64_t span, SelectK &K) {
+  SelectRoom R;
+  K.n_chunks = (capacity + SELECT_CHUNK - 1) / SELECT_CHUNK;
+  R.work_bytes = std::max (acm_gpu_order_tmp_bytes (plan, capacity, span), (size_t)capacity * sizeof (ACMRecord) + 256);
+  K.ctl = c.take<SelectCtl> (1);
+  K.chunk_count = c.take<uint32_t> (K.n_chunks + 1);
+  K.chunk_begin = R.chunk_begin = c.take<uint32_t> (K.n_chunks + 1);
+  R.cub = cub_room (c, K.n_chunks + 1, 0);
+  K.map = c.take<uint32_t> ((size_t)capacity + SELECT_TILE_MAX); /* tiles x E <= capacity + T words */
+  K.tile_entry = c.take<uint32_t> ((size_t)capacity / SELECT_TILE_MIN + 1);
+  K.tile_base = c.take<uint32_t> ((size_t)capacity / SELECT_TILE_MIN + 1);
+  K.keyed = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
+  K.cand = reinterpret_cast<ACMRecord *> (c.take (R.work_bytes));
+  return R;
 }
 
-/* ACM_GPU_SELECT_TILE=<candidates>: T (tests; read at every call) */
+/* ACM_GPU_SELECT_TILE=<candidates>: T (tests) */
 uint32_t
 select_tile (void) {
-  const int t = env_int ("ACM_GPU_SELECT_TILE", (int)SELECT_TILE_DEFAULT);
-  return t >= (int)SELECT_TILE_MIN && t <= (int)SELECT_TILE_MAX ? (uint32_t)t : SELECT_TILE_DEFAULT;
+  return tunable ("ACM_GPU_SELECT_TILE", SELECT_TILE_DEFAULT, SELECT_TILE_MIN, SELECT_TILE_MAX, Tune::Any);
 }
 
 /* ACM_GPU_SELECT=walk: every plan takes the general form (experiments, tests) */
 bool
-select_tiled_form (const ACMPlan *plan) {
+select_tiled_form (const ACMPlan *plan, uint32_t tile) {
   const bool walk = getenv ("ACM_GPU_SELECT") && strcmp (getenv ("ACM_GPU_SELECT"), "walk") == 0;
-  return !walk && plan_lmax (plan) <= select_tile ();
+  return !walk && plan_lmax (plan) <= tile;
+}
+
+/* no record to pass on (select, words): a count that came in stays -- it says what room the records
+ * need --, else the count is 0 */
+int
+no_record (ACMPlan *plan, const uint64_t *d_n, uint64_t *d_count, hipStream_t st) {
+  HIP_TRY (hipSetDevice (plan->device));
+  if (!d_n)
+    HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
+  else if (d_n != d_count)
+    HIP_TRY (hipMemcpyAsync (d_count, d_n, 8, hipMemcpyDeviceToDevice, st));
+  return ACM_GPU_OK;
 }
 } // namespace
 
@@ -5020,14 +4993,17 @@ extern "C" int
 acm_gpu_select_form (const ACMPlan *plan) {
   if (!plan)
     return ACM_GPU_E_ARG;
-  return select_tiled_form (plan) ? ACM_GPU_SELECT_FORM_TILED : ACM_GPU_SELECT_FORM_WALK;
+  return select_tiled_form (plan, select_tile ()) ? ACM_GPU_SELECT_FORM_TILED : ACM_GPU_SELECT_FORM_WALK;
 }
 
 extern "C" size_t
 acm_gpu_select_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t span) {
   if (!plan || capacity >= (1ull << 31))
     return 0;
-  return select_layout (plan, capacity, span).total;
+  Carve c;
+  SelectK K{};
+  select_carve (c, plan, capacity, span, K);
+  return c.total ();
 }
 
 extern "C" int
@@ -5036,20 +5012,14 @@ acm_gpu_select_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64
   if (!plan || !d_count || n >= (1ull << 31) || (n && (!d_records || !d_out || !d_tmp || span == 0)))
     return ACM_GPU_E_ARG;
   hipStream_t st = static_cast<hipStream_t> (stream);
-  if (n == 0) { /* no room, no record: a count that came in stays (it says what room the records need) */
-    HIP_TRY (hipSetDevice (plan->device));
-    if (!d_n)
-      HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
-    else if (d_n != d_count)
-      HIP_TRY (hipMemcpyAsync (d_count, d_n, 8, hipMemcpyDeviceToDevice, st));
-    return ACM_GPU_OK;
-  }
-  const SelectLayout L = select_layout (plan, n, span);
-  if (tmp_bytes < L.total)
+  if (n == 0) /* (no room) */
+    return no_record (plan, d_n, d_count, st);
+  Carve carve (d_tmp);
+  SelectK K{};
+  const SelectRoom L = select_carve (carve, plan, n, span, K);
+  if (tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  SelectK K{};
   K.in = d_records;
   K.capacity = n;
   K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
@@ -5058,27 +5028,16 @@ acm_gpu_select_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64
   K.lmax = plan_lmax (plan);
   K.T = select_tile ();
   K.E = K.lmax < K.T ? K.lmax : K.T;
-  K.keyed = reinterpret_cast<ACMRecord *> (t + L.o_keyed);
-  K.chunk_count = reinterpret_cast<uint32_t *> (t + L.o_count);
-  K.chunk_begin = reinterpret_cast<const uint32_t *> (t + L.o_begin);
-  K.n_chunks = L.n_chunks;
-  K.cand = reinterpret_cast<ACMRecord *> (t + L.o_work);
-  K.map = reinterpret_cast<uint32_t *> (t + L.o_map);
-  K.tile_entry = reinterpret_cast<uint32_t *> (t + L.o_entry);
-  K.tile_base = reinterpret_cast<uint32_t *> (t + L.o_base);
   K.max_tiles = (n + K.T - 1) / K.T;
   K.out = d_out;
   K.d_count = reinterpret_cast<unsigned long long *> (d_count);
-  K.ctl = reinterpret_cast<SelectCtl *> (t + L.o_ctl);
   K.error = error_word (plan);
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (SelectCtl), st));
   /* a. keys, the records that break the contract out, the order by (start, length descending) */
-  hipLaunchKernelGGL (select_key_kernel, capped_grid (plan, (n + SELECT_THREADS - 1) / SELECT_THREADS), dim3 (SELECT_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (select_drop_kernel, dim3 (1), dim3 (SELECT_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (select_key_kernel, capped_grid (plan, (n + SELECT_THREADS - 1) / SELECT_THREADS), dim3 (SELECT_THREADS), 0, st, K));
+  HIP_TRY (launch (select_drop_kernel, dim3 (1), dim3 (SELECT_THREADS), 0, st, K));
   if (order_by_buckets (plan, order_layout (plan, n, span))) {
-    const int rc = order_records (plan, K.keyed, n, &K.ctl->n, pos_lo, span, t + L.o_work, L.work_bytes, stream);
+    const int rc = order_records (plan, K.keyed, n, &K.ctl->n, pos_lo, span, K.cand, L.work_bytes, stream);
     if (rc)
       return rc;
   } else {
@@ -5088,31 +5047,24 @@ acm_gpu_select_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64
     HIP_TRY (hipMemcpyAsync (&kept, &K.ctl->n, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY (hipStreamSynchronize (st));
     if (kept > 1) {
-      const int rc = order_records (plan, K.keyed, kept, nullptr, pos_lo, span, t + L.o_work, L.work_bytes, stream);
+      const int rc = order_records (plan, K.keyed, kept, nullptr, pos_lo, span, K.cand, L.work_bytes, stream);
       if (rc)
         return rc;
     }
   }
   /* b. the candidates */
-  hipLaunchKernelGGL (select_cand_kernel<false>, capped_grid (plan, L.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.chunk_count, reinterpret_cast<uint32_t *> (t + L.o_begin), (int)(L.n_chunks + 1), st));
-  hipLaunchKernelGGL (select_cand_kernel<true>, capped_grid (plan, L.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  if (!select_tiled_form (plan)) { /* f. */
-    hipLaunchKernelGGL (select_walk_kernel, dim3 (1), dim3 (WAVE), 0, st, K);
-    HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (select_cand_kernel<false>, capped_grid (plan, K.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, K.chunk_count, L.chunk_begin, K.n_chunks + 1, st));
+  HIP_TRY (launch (select_cand_kernel<true>, capped_grid (plan, K.n_chunks + 1), dim3 (SELECT_THREADS), 0, st, K));
+  if (!select_tiled_form (plan, K.T)) { /* f. */
+    HIP_TRY (launch (select_walk_kernel, dim3 (1), dim3 (WAVE), 0, st, K));
     return ACM_GPU_OK;
   }
   /* c. d. e. */
   const size_t lds = select_tile_lds (K.T);
-  hipLaunchKernelGGL (select_tile_kernel<false>, capped_grid (plan, K.max_tiles), dim3 (SELECT_THREADS), lds, st, K);
-  HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (select_resolve_kernel, dim3 (1), dim3 (SELECT_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  hipLaunchKernelGGL (select_tile_kernel<true>, capped_grid (plan, K.max_tiles), dim3 (SELECT_THREADS), lds, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (select_tile_kernel<false>, capped_grid (plan, K.max_tiles), dim3 (SELECT_THREADS), lds, st, K));
+  HIP_TRY (launch (select_resolve_kernel, dim3 (1), dim3 (SELECT_THREADS), 0, st, K));
+  HIP_TRY (launch (select_tile_kernel<true>, capped_grid (plan, K.max_tiles), dim3 (SELECT_THREADS), lds, st, K));
   return ACM_GPU_OK;
 }
 
@@ -5160,30 +5112,21 @@ acm_gpu_scan_select_host (ACMPlan *plan, const void *text, uint64_t n_symbols, u
  * The passes behind a selection: validate and measure, the prefix over the chunks and the records'
  * places in the output, the output itself. */
 namespace {
-struct ReplaceLayout {
-  uint64_t n_chunks = 0;
-  size_t o_ctl = 0, o_sum = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, o_start = 0, total = 0;
+/* what replace_carve derives beside K's pointers */
+struct ReplaceRoom {
+  long long *chunk_begin = nullptr; /* K.chunk_begin, for the sum that writes it */
+  CubRoom cub;
 };
-ReplaceLayout
-replace_layout (uint64_t capacity) {
-  ReplaceLayout L;
-  L.n_chunks = (capacity + REPLACE_CHUNK - 1) / REPLACE_CHUNK;
-  L.cub_bytes = exclusive_sum_bytes64 (L.n_chunks + 1);
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (ReplaceCtl));
-  L.o_sum = blob_reserve (cur, (L.n_chunks + 1) * 8);
-  L.o_begin = blob_reserve (cur, (L.n_chunks + 1) * 8);
-  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
-  L.o_start = blob_reserve (cur, (size_t)(capacity ? capacity : 1) * 8);
-  L.total = cur + 256;
-  return L;
-}
-
-/* ACM_GPU_REPLACE_TILE=<bytes of output>: pass c's tile, a multiple of 16 (tests; read at every call) */
-uint32_t
-replace_tile (void) {
-  const int t = env_int ("ACM_GPU_REPLACE_TILE", (int)REPLACE_TILE_DEFAULT);
-  return t >= (int)REPLACE_TILE_MIN && t <= (int)REPLACE_TILE_MAX && t % 16 == 0 ? (uint32_t)t : REPLACE_TILE_DEFAULT;
+ReplaceRoom
+replace_carve (Carve &c, uint64_t capacity, ReplaceK &K) {
+  ReplaceRoom R;
+  K.n_chunks = (capacity + REPLACE_CHUNK - 1) / REPLACE_CHUNK;
+  K.ctl = c.take<ReplaceCtl> (1);
+  K.chunk_sum = c.take<long long> (K.n_chunks + 1);
+  K.chunk_begin = R.chunk_begin = c.take<long long> (K.n_chunks + 1);
+  R.cub = cub_room (c, 0, K.n_chunks + 1);
+  K.out_start = c.take<long long> ((size_t)(capacity ? capacity : 1));
+  return R;
 }
 
 /* table mode: the table has an entry for every keyword the plan can report */
@@ -5198,30 +5141,32 @@ acm_gpu_replace_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t
   (void)n_symbols; /* (the passes keep nothing per symbol) */
   if (!plan || n_or_capacity >= (1ull << 31))
     return 0;
-  return replace_layout (n_or_capacity).total;
+  Carve c;
+  ReplaceK K{};
+  replace_carve (c, n_or_capacity, K);
+  return c.total ();
 }
 
 namespace {
-/* the passes, with the layout of their scratch (made once per call) */
+/* the passes over a selection of n records, or of *d_n in a room of n */
 int
-replace_records (ACMPlan *plan, const ReplaceLayout &L, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const ACMRecord *d_sel, uint64_t n,
+replace_records (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const ACMRecord *d_sel, uint64_t n,
                  const uint64_t *d_n, const void *d_repl_data, const uint64_t *d_repl_off, uint64_t n_keywords, void *d_out, uint64_t out_capacity,
                  uint64_t *d_out_symbols, int64_t *d_out_start, void *d_tmp, size_t tmp_bytes, void *stream) {
   if (!plan || !d_out_symbols || !d_tmp || n >= (1ull << 31) || (n_symbols && !d_text) || (out_capacity && !d_out) || (n && !d_sel) ||
       (!d_repl_off && !d_repl_data) || n_keywords >= (1ull << 32))
     return ACM_GPU_E_ARG;
   const uint32_t sb = plan->text_sym_bytes;
-  const uintptr_t t0 = reinterpret_cast<uintptr_t> (d_text), o0 = reinterpret_cast<uintptr_t> (d_out);
-  if (t0 % sb || o0 % sb || reinterpret_cast<uintptr_t> (d_repl_data) % sb || n_symbols >= (1ull << 56) / sb || out_capacity >= (1ull << 56) / sb)
+  if (!symbols_ok (d_text, n_symbols, sb) || !symbols_ok (d_out, out_capacity, sb) || reinterpret_cast<uintptr_t> (d_repl_data) % sb ||
+      !apart (d_text, n_symbols, d_out, out_capacity, sb))
     return ACM_GPU_E_ARG;
-  if (n_symbols && out_capacity && t0 < o0 + out_capacity * sb && o0 < t0 + n_symbols * sb) /* the output is built from the text beside it */
-    return ACM_GPU_E_ARG;
-  if (tmp_bytes < L.total)
+  Carve carve (d_tmp);
+  ReplaceK K{};
+  const ReplaceRoom L = replace_carve (carve, n, K);
+  if (tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
   hipStream_t st = static_cast<hipStream_t> (stream);
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  ReplaceK K{};
   K.sel = d_sel;
   K.capacity = n;
   K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
@@ -5229,44 +5174,29 @@ replace_records (ACMPlan *plan, const ReplaceLayout &L, const void *d_text, uint
   K.n_symbols = n_symbols;
   K.pos_base = pos_base;
   K.sb = sb;
-  K.tile_words = replace_tile () / 16;
+  /* ACM_GPU_REPLACE_TILE=<bytes of output>: pass c's tile, a multiple of 16 (tests) */
+  K.tile_words = tunable ("ACM_GPU_REPLACE_TILE", REPLACE_TILE_DEFAULT, REPLACE_TILE_MIN, REPLACE_TILE_MAX, Tune::Mult16) / 16;
   K.repl = static_cast<const unsigned char *> (d_repl_data);
   K.repl_off = reinterpret_cast<const unsigned long long *> (d_repl_off);
   K.n_keywords = n_keywords;
-  K.chunk_sum = reinterpret_cast<long long *> (t + L.o_sum);
-  K.chunk_begin = reinterpret_cast<const long long *> (t + L.o_begin);
-  K.n_chunks = L.n_chunks;
-  K.out_start = reinterpret_cast<long long *> (t + L.o_start);
   K.d_out_start = reinterpret_cast<long long *> (d_out_start);
   K.out = static_cast<unsigned char *> (d_out);
   K.out_capacity = out_capacity;
   K.d_out_symbols = reinterpret_cast<unsigned long long *> (d_out_symbols);
-  K.ctl = reinterpret_cast<ReplaceCtl *> (t + L.o_ctl);
   K.error = error_word (plan);
   const bool mask = d_repl_off == nullptr;
+  const dim3 block (REPLACE_THREADS);
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (ReplaceCtl), st));
   /* a. */
-  const dim3 chunks_grid = capped_grid (plan, std::max (L.n_chunks + 1, mask ? (uint64_t)0 : (n_keywords + REPLACE_THREADS - 1) / REPLACE_THREADS));
-  if (mask)
-    hipLaunchKernelGGL (replace_measure_kernel<true>, chunks_grid, dim3 (REPLACE_THREADS), 0, st, K);
-  else
-    hipLaunchKernelGGL (replace_measure_kernel<false>, chunks_grid, dim3 (REPLACE_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  const dim3 chunks_grid = capped_grid (plan, std::max (K.n_chunks + 1, mask ? (uint64_t)0 : (n_keywords + REPLACE_THREADS - 1) / REPLACE_THREADS));
+  HIP_TRY (mask ? launch (replace_measure_kernel<true>, chunks_grid, block, 0, st, K) : launch (replace_measure_kernel<false>, chunks_grid, block, 0, st, K));
   /* b. */
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.chunk_sum, reinterpret_cast<long long *> (t + L.o_begin), (int)(L.n_chunks + 1), st));
-  if (mask)
-    hipLaunchKernelGGL (replace_starts_kernel<true>, capped_grid (plan, L.n_chunks), dim3 (REPLACE_THREADS), 0, st, K);
-  else
-    hipLaunchKernelGGL (replace_starts_kernel<false>, capped_grid (plan, L.n_chunks), dim3 (REPLACE_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (exclusive_sum (L.cub, K.chunk_sum, L.chunk_begin, K.n_chunks + 1, st));
+  const dim3 starts_grid = capped_grid (plan, K.n_chunks);
+  HIP_TRY (mask ? launch (replace_starts_kernel<true>, starts_grid, block, 0, st, K) : launch (replace_starts_kernel<false>, starts_grid, block, 0, st, K));
   /* c. the grid by the room of the output, not by what the passes found */
-  const uint64_t tiles = (out_capacity * sb + 15 + 16) / ((uint64_t)K.tile_words * 16) + 1;
-  if (mask)
-    hipLaunchKernelGGL (replace_build_kernel<true>, capped_grid (plan, tiles), dim3 (REPLACE_THREADS), 0, st, K);
-  else
-    hipLaunchKernelGGL (replace_build_kernel<false>, capped_grid (plan, tiles), dim3 (REPLACE_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  const dim3 tiles_grid = capped_grid (plan, (out_capacity * sb + 15 + 16) / ((uint64_t)K.tile_words * 16) + 1);
+  HIP_TRY (mask ? launch (replace_build_kernel<true>, tiles_grid, block, 0, st, K) : launch (replace_build_kernel<false>, tiles_grid, block, 0, st, K));
   return ACM_GPU_OK;
 }
 
@@ -5279,7 +5209,7 @@ acm_gpu_replace_records_device (ACMPlan *plan, const void *d_text, uint64_t n_sy
                                 void *stream) {
   if (!plan || n >= (1ull << 31))
     return ACM_GPU_E_ARG;
-  return replace_records (plan, replace_layout (n), d_text, n_symbols, pos_base, d_sel, n, d_n, d_repl_data, d_repl_off, n_keywords, d_out,
+  return replace_records (plan, d_text, n_symbols, pos_base, d_sel, n, d_n, d_repl_data, d_repl_off, n_keywords, d_out,
                           out_capacity, d_out_symbols, d_out_start, d_tmp, tmp_bytes, stream);
 }
 
@@ -5298,13 +5228,12 @@ acm_gpu_scan_replace_device (ACMPlan *plan, const void *d_text, uint64_t n_symbo
   if (!plan || !d_count || !d_out_symbols || !d_tmp || capacity >= (1ull << 31) || (n_symbols && !d_text) || (capacity && !d_records) ||
       (out_capacity && !d_out) || (!d_repl_off && !d_repl_data) || !replace_table_covers (plan, d_repl_off, n_keywords))
     return ACM_GPU_E_ARG;
-  const ReplaceLayout L = replace_layout (capacity);
-  if (tmp_bytes < std::max (acm_gpu_scan_select_tmp_bytes (plan, capacity, n_symbols), L.total))
+  if (tmp_bytes < acm_gpu_scan_replace_tmp_bytes (plan, capacity, n_symbols))
     return ACM_GPU_E_ARG;
   const int rc = acm_gpu_scan_select_device (plan, d_text, n_symbols, pos_base, d_records, capacity, d_count, d_tmp, tmp_bytes, stream);
   if (rc)
     return rc;
-  return replace_records (plan, L, d_text, n_symbols, pos_base, d_records, capacity, d_count, d_repl_data, d_repl_off, n_keywords, d_out, out_capacity,
+  return replace_records (plan, d_text, n_symbols, pos_base, d_records, capacity, d_count, d_repl_data, d_repl_off, n_keywords, d_out, out_capacity,
                           d_out_symbols, d_out_start, d_tmp, tmp_bytes, stream);
 }
 
@@ -5370,33 +5299,26 @@ acm_gpu_scan_replace_host (ACMPlan *plan, const void *text, uint64_t n_symbols, 
  * The passes behind a selection: validate, count the token starts per tile of the text, the prefix
  * over the tiles, the tokens themselves. */
 namespace {
-/* ACM_GPU_TOKENS_TILE=<symbols>: the tile of the passes, a multiple of 64 (tests; read at every call) */
-uint32_t
-tokens_tile (void) {
-  const int t = env_int ("ACM_GPU_TOKENS_TILE", (int)TOKENS_TILE_DEFAULT);
-  return t >= (int)TOKENS_TILE_MIN && t <= (int)TOKENS_TILE_MAX && t % 64 == 0 ? (uint32_t)t : TOKENS_TILE_DEFAULT;
-}
-
-struct TokensLayout {
-  uint32_t tile = 0;
-  uint64_t n_tiles = 0;
-  size_t o_ctl = 0, o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, total = 0;
+/* what tokens_carve derives beside K's pointers */
+struct TokensRoom {
+  bool ok = false; /* false: a text of more tiles than the prefix sum can count (its entries are an int's), nothing carved */
+  long long *tile_begin = nullptr; /* K.tile_begin, for the sum that writes it */
+  CubRoom cub;
 };
-TokensLayout
-tokens_layout (uint64_t n_symbols) {
-  TokensLayout L;
-  L.tile = tokens_tile ();
-  L.n_tiles = (n_symbols + L.tile - 1) / L.tile;
-  if (L.n_tiles + 1 >= (1ull << 31)) /* (the prefix sum counts its entries in an int: no layout) */
-    return L;
-  L.cub_bytes = exclusive_sum_bytes64 (L.n_tiles + 1);
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (TokensCtl));
-  L.o_count = blob_reserve (cur, (L.n_tiles + 1) * 8);
-  L.o_begin = blob_reserve (cur, (L.n_tiles + 1) * 8);
-  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
-  L.total = cur + 256;
-  return L;
+TokensRoom
+tokens_carve (Carve &c, uint64_t n_symbols, TokensK &K) {
+  TokensRoom R;
+  /* ACM_GPU_TOKENS_TILE=<symbols>: the tile of the passes, a multiple of 64 (tests) */
+  K.tile = tunable ("ACM_GPU_TOKENS_TILE", TOKENS_TILE_DEFAULT, TOKENS_TILE_MIN, TOKENS_TILE_MAX, Tune::MultWave);
+  K.n_tiles = (n_symbols + K.tile - 1) / K.tile;
+  if (K.n_tiles + 1 >= (1ull << 31))
+    return R;
+  R.ok = true;
+  K.ctl = c.take<TokensCtl> (1);
+  K.tile_count = c.take<long long> (K.n_tiles + 1);
+  K.tile_begin = R.tile_begin = c.take<long long> (K.n_tiles + 1);
+  R.cub = cub_room (c, 0, K.n_tiles + 1);
+  return R;
 }
 
 /* a table keyword -> vocabulary id has an entry for every keyword the plan can report */
@@ -5413,9 +5335,9 @@ tokens_mode_ok (uint32_t sym_bytes, uint32_t gap_base, uint32_t mode) {
   return mode != ACM_TOKENS_GAP_SYMBOL || (sym_bytes <= 2 && (uint64_t)gap_base <= (1ull << 32) - (1ull << (8 * sym_bytes)));
 }
 
-/* the passes, with the layout of their scratch (made once per call) */
+/* the passes over a selection of n records, or of *d_n in a room of n */
 int
-tokens_records (ACMPlan *plan, const TokensLayout &L, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const ACMRecord *d_sel, uint64_t n,
+tokens_records (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const ACMRecord *d_sel, uint64_t n,
                 const uint64_t *d_n, const uint64_t *d_offsets, uint64_t n_texts, const uint32_t *d_tok_of, uint64_t n_keywords, uint32_t gap_base,
                 uint32_t mode, uint32_t *d_tok_id, uint64_t *d_tok_start, uint32_t *d_tok_len, uint64_t token_capacity, uint64_t *d_n_tokens,
                 uint64_t *d_tok_first, void *d_tmp, size_t tmp_bytes, void *stream) {
@@ -5427,12 +5349,13 @@ tokens_records (ACMPlan *plan, const TokensLayout &L, const void *d_text, uint64
     return ACM_GPU_E_ARG;
   if (mode == ACM_TOKENS_GAP_SYMBOL && ((n_symbols && !d_text) || reinterpret_cast<uintptr_t> (d_text) % sb))
     return ACM_GPU_E_ARG;
-  if (L.total == 0 || tmp_bytes < L.total)
+  Carve carve (d_tmp);
+  TokensK K{};
+  const TokensRoom L = tokens_carve (carve, n_symbols, K);
+  if (!L.ok || tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
   hipStream_t st = static_cast<hipStream_t> (stream);
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  TokensK K{};
   K.sel = d_sel;
   K.capacity = n;
   K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
@@ -5442,35 +5365,26 @@ tokens_records (ACMPlan *plan, const TokensLayout &L, const void *d_text, uint64
   K.sb = sb;
   K.mode = mode;
   K.gap_base = gap_base;
-  K.tile = L.tile;
   K.offsets = reinterpret_cast<const unsigned long long *> (d_offsets);
   K.n_texts = d_offsets ? n_texts : 0;
   K.tok_of = d_tok_of;
   K.n_keywords = n_keywords;
-  K.tile_count = reinterpret_cast<long long *> (t + L.o_count);
-  K.tile_begin = reinterpret_cast<const long long *> (t + L.o_begin);
-  K.n_tiles = L.n_tiles;
   K.tok_id = d_tok_id;
   K.tok_start = reinterpret_cast<unsigned long long *> (d_tok_start);
   K.tok_len = d_tok_len;
   K.token_capacity = d_tok_id ? token_capacity : 0;
   K.d_n_tokens = reinterpret_cast<unsigned long long *> (d_n_tokens);
   K.tok_first = reinterpret_cast<unsigned long long *> (d_tok_first);
-  K.ctl = reinterpret_cast<TokensCtl *> (t + L.o_ctl);
   K.error = error_word (plan);
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (TokensCtl), st));
   /* a. the grid by the rooms the caller names */
   const uint64_t check_blocks = std::max ((n + TOKENS_THREADS - 1) / TOKENS_THREADS, d_offsets ? (n_texts + TOKENS_THREADS) / TOKENS_THREADS : (uint64_t)0);
-  hipLaunchKernelGGL (tokens_check_kernel, capped_grid (plan, check_blocks), dim3 (TOKENS_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (tokens_check_kernel, capped_grid (plan, check_blocks), dim3 (TOKENS_THREADS), 0, st, K));
   /* b. c. d. the grid by the tiles of the text */
-  hipLaunchKernelGGL (tokens_tile_kernel<false>, capped_grid (plan, L.n_tiles + 1), dim3 (TOKENS_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
-  size_t cub = L.cub_bytes;
-  HIP_TRY (hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, K.tile_count, reinterpret_cast<long long *> (t + L.o_begin), (int)(L.n_tiles + 1), st));
-  hipLaunchKernelGGL (tokens_tile_kernel<true>, capped_grid (plan, std::max (L.n_tiles, d_offsets ? (n_texts + TOKENS_THREADS) / TOKENS_THREADS / 64 : (uint64_t)0)),
-                      dim3 (TOKENS_THREADS), 0, st, K);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (tokens_tile_kernel<false>, capped_grid (plan, K.n_tiles + 1), dim3 (TOKENS_THREADS), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, K.tile_count, L.tile_begin, K.n_tiles + 1, st));
+  HIP_TRY (launch (tokens_tile_kernel<true>, capped_grid (plan, std::max (K.n_tiles, d_offsets ? (n_texts + TOKENS_THREADS) / TOKENS_THREADS / 64 : (uint64_t)0)),
+                   dim3 (TOKENS_THREADS), 0, st, K));
   return ACM_GPU_OK;
 }
 } // namespace
@@ -5479,7 +5393,9 @@ extern "C" size_t
 acm_gpu_tokens_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_symbols) {
   if (!plan || n_or_capacity >= (1ull << 31))
     return 0;
-  return tokens_layout (n_symbols).total; /* (the passes keep nothing per record) */
+  Carve c; /* (the passes keep nothing per record) */
+  TokensK K{};
+  return tokens_carve (c, n_symbols, K).ok ? c.total () : 0;
 }
 
 extern "C" int
@@ -5489,7 +5405,7 @@ acm_gpu_tokens_records_device (ACMPlan *plan, const void *d_text, uint64_t n_sym
                                uint64_t token_capacity, uint64_t *d_n_tokens, uint64_t *d_tok_first, void *d_tmp, size_t tmp_bytes, void *stream) {
   if (!plan || n_symbols >= (1ull << 56))
     return ACM_GPU_E_ARG;
-  return tokens_records (plan, tokens_layout (n_symbols), d_text, n_symbols, pos_base, d_sel, n, d_n, d_offsets, n_texts, d_tok_of, n_keywords, gap_base,
+  return tokens_records (plan, d_text, n_symbols, pos_base, d_sel, n, d_n, d_offsets, n_texts, d_tok_of, n_keywords, gap_base,
                          mode, d_tok_id, d_tok_start, d_tok_len, token_capacity, d_n_tokens, d_tok_first, d_tmp, tmp_bytes, stream);
 }
 
@@ -5512,7 +5428,6 @@ acm_gpu_scan_tokens_device (ACMPlan *plan, const void *d_text, uint64_t n_symbol
       (capacity && !d_records) || (!d_offsets && d_tok_first) || (d_offsets && (pos_base || n_texts >= (1ull << 31))) ||
       !tokens_mode_ok (plan->text_sym_bytes, gap_base, mode) || !tokens_table_covers (plan, d_tok_of, n_keywords))
     return ACM_GPU_E_ARG;
-  const TokensLayout L = tokens_layout (n_symbols);
   if (tmp_bytes < acm_gpu_scan_tokens_tmp_bytes (plan, capacity, n_symbols, n_texts))
     return ACM_GPU_E_ARG;
   int rc;
@@ -5525,7 +5440,7 @@ acm_gpu_scan_tokens_device (ACMPlan *plan, const void *d_text, uint64_t n_symbol
   }
   if (rc)
     return rc;
-  return tokens_records (plan, L, d_text, n_symbols, pos_base, d_records, capacity, d_count, d_offsets, n_texts, d_tok_of, n_keywords, gap_base, mode,
+  return tokens_records (plan, d_text, n_symbols, pos_base, d_records, capacity, d_count, d_offsets, n_texts, d_tok_of, n_keywords, gap_base, mode,
                          d_tok_id, d_tok_start, d_tok_len, token_capacity, d_n_tokens, d_tok_first, d_tmp, tmp_bytes, stream);
 }
 
@@ -5604,33 +5519,25 @@ acm_gpu_scan_tokens_host (ACMPlan *plan, const void *text, uint64_t n_symbols, c
  * One stable compaction of a record set under the symbols next to each match: the check of
  * offsets[], the mark pass, the prefix over the tiles, the write pass. */
 namespace {
-struct WordsLayout {
-  uint32_t tile = 0;
-  uint64_t n_tiles = 0;
-  size_t o_ctl = 0, o_count = 0, o_begin = 0, o_cub = 0, cub_bytes = 0, o_mask = 0, total = 0;
+/* what words_carve derives beside K's pointers: the tile counts and their sums as the sum takes them */
+struct WordsRoom {
+  long long *count = nullptr, *begin = nullptr;
+  CubRoom cub;
 };
-
-/* ACM_GPU_WORDS_TILE=<records>: the passes' tile, a multiple of 64 (tests; read at every call) */
-uint32_t
-words_tile (void) {
-  const int t = env_int ("ACM_GPU_WORDS_TILE", (int)WORDS_TILE_DEFAULT);
-  return t >= (int)WORDS_TILE_MIN && t <= (int)WORDS_TILE_MAX && t % (int)WAVE == 0 ? (uint32_t)t : WORDS_TILE_DEFAULT;
-}
-
-WordsLayout
-words_layout (uint64_t capacity) {
-  WordsLayout L;
-  L.tile = words_tile ();
-  L.n_tiles = (capacity + L.tile - 1) / L.tile;
-  L.cub_bytes = exclusive_sum_bytes64 (L.n_tiles + 1);
-  size_t cur = 0;
-  L.o_ctl = blob_reserve (cur, sizeof (WordsCtl));
-  L.o_count = blob_reserve (cur, (L.n_tiles + 1) * 8);
-  L.o_begin = blob_reserve (cur, (L.n_tiles + 1) * 8);
-  L.o_cub = blob_reserve (cur, L.cub_bytes + 16);
-  L.o_mask = blob_reserve (cur, ((size_t)capacity + WAVE - 1) / WAVE * 8);
-  L.total = cur + 256;
-  return L;
+WordsRoom
+words_carve (Carve &c, uint64_t capacity, WordsK &K) {
+  WordsRoom R;
+  /* ACM_GPU_WORDS_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
+  K.tile = tunable ("ACM_GPU_WORDS_TILE", WORDS_TILE_DEFAULT, WORDS_TILE_MIN, WORDS_TILE_MAX, Tune::MultWave);
+  K.n_tiles = (capacity + K.tile - 1) / K.tile;
+  K.ctl = c.take<WordsCtl> (1);
+  R.count = c.take<long long> (K.n_tiles + 1);
+  R.begin = c.take<long long> (K.n_tiles + 1);
+  R.cub = cub_room (c, 0, K.n_tiles + 1);
+  K.mask = c.take<unsigned long long> (((size_t)capacity + WAVE - 1) / WAVE);
+  K.tile_count = reinterpret_cast<unsigned long long *> (R.count);
+  K.tile_begin = reinterpret_cast<const unsigned long long *> (R.begin);
+  return R;
 }
 
 /* the word set of a call into the kernels' arguments: the caller's symbols as unsigned integers */
@@ -5651,18 +5558,12 @@ words_ranges (WordsK &K, uint32_t sb, const void *ranges, uint32_t n_ranges, uin
 }
 
 template <int SB>
-void
-words_launch (const ACMPlan *plan, const WordsLayout &L, const WordsK &K, unsigned char *t, hipStream_t st, hipError_t *err) {
-  hipLaunchKernelGGL (words_mark_kernel<SB>, capped_grid (plan, L.n_tiles + 1), dim3 (WORDS_THREADS), 0, st, K);
-  if ((*err = hipGetLastError ()) != hipSuccess)
-    return;
-  size_t cub = L.cub_bytes;
-  *err = hipcub::DeviceScan::ExclusiveSum (t + L.o_cub, cub, reinterpret_cast<long long *> (t + L.o_count), reinterpret_cast<long long *> (t + L.o_begin),
-                                           (int)(L.n_tiles + 1), st);
-  if (*err != hipSuccess)
-    return;
-  hipLaunchKernelGGL (words_write_kernel, capped_grid (plan, L.n_tiles), dim3 (WORDS_THREADS), 0, st, K);
-  *err = hipGetLastError ();
+int
+words_launch (const ACMPlan *plan, const WordsRoom &L, const WordsK &K, hipStream_t st) {
+  HIP_TRY (launch (words_mark_kernel<SB>, capped_grid (plan, K.n_tiles + 1), dim3 (WORDS_THREADS), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, L.count, L.begin, K.n_tiles + 1, st));
+  HIP_TRY (launch (words_write_kernel, capped_grid (plan, K.n_tiles), dim3 (WORDS_THREADS), 0, st, K));
+  return ACM_GPU_OK;
 }
 } // namespace
 
@@ -5671,7 +5572,10 @@ acm_gpu_words_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n
   (void)n_texts; /* (nothing here is sized by the number of texts: a record's text is a bisection of offsets[]) */
   if (!plan || n_or_capacity >= (1ull << 31))
     return 0;
-  return words_layout (n_or_capacity).total;
+  Carve c;
+  WordsK K{};
+  words_carve (c, n_or_capacity, K);
+  return c.total ();
 }
 
 extern "C" int
@@ -5691,19 +5595,13 @@ acm_gpu_words_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symb
       return ACM_GPU_E_ARG;
   }
   hipStream_t st = static_cast<hipStream_t> (stream);
-  if (n == 0) { /* no room, no record: a count that came in stays (it says what room the records need) */
-    HIP_TRY (hipSetDevice (plan->device));
-    if (!d_n)
-      HIP_TRY (hipMemsetAsync (d_count, 0, 8, st));
-    else if (d_n != d_count)
-      HIP_TRY (hipMemcpyAsync (d_count, d_n, 8, hipMemcpyDeviceToDevice, st));
-    return ACM_GPU_OK;
-  }
-  const WordsLayout L = words_layout (n);
-  if (tmp_bytes < L.total)
+  if (n == 0) /* (no room) */
+    return no_record (plan, d_n, d_count, st);
+  Carve carve (d_tmp);
+  const WordsRoom L = words_carve (carve, n, K);
+  if (tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
   K.text = static_cast<const unsigned char *> (d_text);
   K.n_symbols = n_symbols;
   K.pos_base = pos_base;
@@ -5712,47 +5610,36 @@ acm_gpu_words_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symb
   K.in = d_records;
   K.capacity = n;
   K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
-  K.tile = L.tile;
-  K.n_tiles = L.n_tiles;
-  K.mask = reinterpret_cast<unsigned long long *> (t + L.o_mask);
-  K.tile_count = reinterpret_cast<unsigned long long *> (t + L.o_count);
-  K.tile_begin = reinterpret_cast<const unsigned long long *> (t + L.o_begin);
   K.out = d_out;
   K.d_count = reinterpret_cast<unsigned long long *> (d_count);
-  K.ctl = reinterpret_cast<WordsCtl *> (t + L.o_ctl);
   K.error = error_word (plan);
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (WordsCtl), st));
-  if (K.offsets) { /* one size, whatever the number of texts */
-    hipLaunchKernelGGL (words_check_kernel, capped_grid (plan, (n_texts + WORDS_THREADS - 1) / WORDS_THREADS), dim3 (WORDS_THREADS), 0, st, K);
-    HIP_TRY (hipGetLastError ());
-  }
-  hipError_t err = hipSuccess;
+  if (K.offsets) /* one size, whatever the number of texts */
+    HIP_TRY (launch (words_check_kernel, capped_grid (plan, (n_texts + WORDS_THREADS - 1) / WORDS_THREADS), dim3 (WORDS_THREADS), 0, st, K));
   switch (sb) {
-  case 1: words_launch<1> (plan, L, K, t, st, &err); break;
-  case 2: words_launch<2> (plan, L, K, t, st, &err); break;
-  case 4: words_launch<4> (plan, L, K, t, st, &err); break;
-  case 8: words_launch<8> (plan, L, K, t, st, &err); break;
+  case 1: return words_launch<1> (plan, L, K, st);
+  case 2: return words_launch<2> (plan, L, K, st);
+  case 4: return words_launch<4> (plan, L, K, st);
+  case 8: return words_launch<8> (plan, L, K, st);
   default: return ACM_GPU_E_ARG;
   }
-  HIP_TRY (err);
-  return ACM_GPU_OK;
 }
 
 namespace {
 /* the fused call's scratch: the ordered scan's records, then the room the scan and the filter share
  * (the scan has ended when the filter begins) */
-struct ScanWordsLayout {
-  size_t o_rec = 0, o_work = 0, work_bytes = 0, total = 0;
+struct ScanWordsRoom {
+  ACMRecord *found = nullptr;
+  unsigned char *work = nullptr;
+  size_t work_bytes = 0;
 };
-ScanWordsLayout
-scan_words_layout (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
-  ScanWordsLayout L;
-  L.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_words_tmp_bytes (plan, capacity, n_texts));
-  size_t cur = 0;
-  L.o_rec = blob_reserve (cur, (size_t)(capacity ? capacity : 1) * sizeof (ACMRecord));
-  L.o_work = blob_reserve (cur, L.work_bytes);
-  L.total = cur + 256;
-  return L;
+ScanWordsRoom
+scan_words_carve (Carve &c, const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  ScanWordsRoom R;
+  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_words_tmp_bytes (plan, capacity, n_texts));
+  R.found = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
+  R.work = c.take (R.work_bytes);
+  return R;
 }
 } // namespace
 
@@ -5760,7 +5647,9 @@ extern "C" size_t
 acm_gpu_scan_words_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
   if (!plan || capacity >= (1ull << 31))
     return 0;
-  return scan_words_layout (plan, capacity, n_symbols, n_texts).total;
+  Carve c;
+  scan_words_carve (c, plan, capacity, n_symbols, n_texts);
+  return c.total ();
 }
 
 extern "C" int
@@ -5770,17 +5659,15 @@ acm_gpu_scan_words_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols
   if (!plan || !d_count || capacity >= (1ull << 31) || (n_symbols && !d_text) || (capacity && (!d_records || !d_tmp)) ||
       !acm_internal_words_args_ok (plan->text_sym_bytes, ranges, n_ranges, flags))
     return ACM_GPU_E_ARG;
-  const ScanWordsLayout L = scan_words_layout (plan, capacity, n_symbols, n_texts);
-  if (capacity && tmp_bytes < L.total)
+  Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
+  const ScanWordsRoom L = scan_words_carve (carve, plan, capacity, n_symbols, n_texts);
+  if (capacity && tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
-  unsigned char *t = static_cast<unsigned char *> (d_tmp);
-  ACMRecord *found = capacity ? reinterpret_cast<ACMRecord *> (t + L.o_rec) : nullptr;
-  const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, found, capacity, d_count, capacity ? t + L.o_work : nullptr,
-                                              L.work_bytes, stream);
+  const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, L.found, capacity, d_count, L.work, L.work_bytes, stream);
   if (rc || capacity == 0) /* (no room: *d_count says what the records need) */
     return rc;
-  return acm_gpu_words_records_device (plan, d_text, n_symbols, pos_base, d_offsets, n_texts, ranges, n_ranges, flags, found, capacity, d_count,
-                                       d_records, d_count, t + L.o_work, L.work_bytes, stream);
+  return acm_gpu_words_records_device (plan, d_text, n_symbols, pos_base, d_offsets, n_texts, ranges, n_ranges, flags, L.found, capacity, d_count,
+                                       d_records, d_count, L.work, L.work_bytes, stream);
 }
 
 extern "C" int
@@ -5832,9 +5719,8 @@ acm_gpu_pack_records_device (const ACMRecord *d_records, uint64_t n, uint64_t po
   if (n == 0)
     return ACM_GPU_OK;
   const uint64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL (pack_records_kernel, dim3 ((uint32_t)(blocks < 16384 ? blocks : 16384)), dim3 (256), 0, static_cast<hipStream_t> (stream), d_records, n,
-                      pos_lo, pos_bits, len_bits, d_packed);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (pack_records_kernel, dim3 ((uint32_t)(blocks < 16384 ? blocks : 16384)), dim3 (256), 0, static_cast<hipStream_t> (stream), d_records, n,
+                   pos_lo, pos_bits, len_bits, d_packed));
   return ACM_GPU_OK;
 }
 
@@ -5846,9 +5732,8 @@ acm_gpu_unpack_records_device (const uint64_t *d_packed, uint64_t n, uint64_t po
   if (n == 0)
     return ACM_GPU_OK;
   const uint64_t blocks = (n + 255) / 256;
-  hipLaunchKernelGGL (unpack_records_kernel, dim3 ((uint32_t)(blocks < 16384 ? blocks : 16384)), dim3 (256), 0, static_cast<hipStream_t> (stream), d_packed, n,
-                      pos_lo, pos_bits, len_bits, d_records);
-  HIP_TRY (hipGetLastError ());
+  HIP_TRY (launch (unpack_records_kernel, dim3 ((uint32_t)(blocks < 16384 ? blocks : 16384)), dim3 (256), 0, static_cast<hipStream_t> (stream), d_packed, n,
+                   pos_lo, pos_bits, len_bits, d_records));
   return ACM_GPU_OK;
 }
 

@@ -1,0 +1,164 @@
+"""The scratch a device call reports is the scratch it uses (acm_gpu_grep_device,
+acm_gpu_tally_batch_device, acm_gpu_select_records_device, acm_gpu_words_records_device, called
+through binding.lib () directly).  With exactly *_tmp_bytes of room, every byte of it and of a
+256-byte guard on either side set to 0xFF, a call gives what the matching Plan method gives (other
+tests hold those against the oracle) and leaves both guards alone: nothing relies on scratch being
+zero beyond what the call clears itself, and nothing is written past the reported size.  With one
+byte less every call returns ACM_GPU_E_ARG and touches no output."""
+import numpy as np
+import pytest
+
+from aho_corasick_1975_amd import binding
+from tests.cases import build_pair
+
+pytestmark = pytest.mark.gpu
+
+E_ARG = binding.ACM_GPU_E_ARG
+KEYWORDS = [b"he", b"she", b"his", b"hers"]
+N_SYMBOLS, N_TEXTS = 4096, 37
+WINDOW, CAPACITY, PAIR_CAPACITY = 4096, 1024, 1024
+GUARD, SENTINEL = 256, 0x5A
+FAMILIES = ["grep", "tally_batch", "select", "words"]
+
+
+def _batch():
+    """4 KiB over a seven-letter alphabet, cut into 37 texts: an empty first one, one of 700 symbols
+    (more than a 256-symbol batch block), 34 random ones, an empty last one"""
+    rng = np.random.default_rng(75)
+    text = np.frombuffer(b"hesir .", np.uint8)[rng.integers(0, 7, size=N_SYMBOLS)].copy()
+    cuts = np.sort(rng.choice(np.arange(701, N_SYMBOLS), size=N_TEXTS - 4, replace=False))
+    off = np.concatenate(([0, 0, 700], cuts, [N_SYMBOLS, N_SYMBOLS])).astype(np.uint64)
+    assert off.size == N_TEXTS + 1 and off[1] == off[0] and off[-1] == off[-2] and np.all(off[1:] >= off[:-1])
+    return text, off
+
+
+class Case:
+    pass
+
+
+@pytest.fixture(scope="module")
+def case():
+    """the plan, the batch on the device, the records of its ordered scan and what the four Plan
+    methods give for them, made once"""
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU (run with -m gpu on the GPU box)"
+    torch.cuda.set_device(0)
+    c = Case()
+    c.torch = torch
+    m, o = build_pair(KEYWORDS, 1)
+    text, off = _batch()
+    # on the CPU, by the oracle: enough matches for more than one tile or wave, all within the 1,024-record room
+    whole = o.scan(text).size
+    inside = sum(o.scan(text[int(off[t]):int(off[t + 1])]).size for t in range(N_TEXTS))
+    assert 64 <= inside <= whole <= 1000, (inside, whole)
+    c.machine, c.plan = m, m.plan(0)
+    c.text = torch.from_numpy(text).cuda()
+    c.offsets = torch.from_numpy(off.view(np.int64).copy()).cuda()
+    c.ranges, c.n_ranges = binding._word_ranges(binding.ASCII_WORD, 1)
+    rec, cnt, _ = c.plan.scan_ordered(c.text, capacity=CAPACITY)
+    c.records, c.n = rec, int(cnt.item())
+    assert c.n == whole
+    g = c.plan.grep(c.text, c.offsets, window=WINDOW, capacity=CAPACITY)
+    assert g.need <= CAPACITY and 0 < g.n_kept < N_TEXTS and g.out_symbols > 0
+    tb = c.plan.tally_batch(c.text, c.offsets, window=WINDOW, capacity=CAPACITY, pair_capacity=PAIR_CAPACITY)
+    assert tb.need <= CAPACITY and 0 < tb.nnz <= PAIR_CAPACITY and tb.total == inside
+    sel, n_sel = c.plan.select_records(c.records, c.n, 0, N_SYMBOLS)
+    assert 0 < n_sel < c.n
+    wrd, n_wrd = c.plan.words_records(c.text, c.records, c.n, offsets=c.offsets)
+    n_wrd = int(n_wrd.item())
+    assert 0 < n_wrd < c.n
+    c.want = {
+        "grep": [g.hits[:N_TEXTS], g.kept[:g.n_kept], torch.tensor([g.n_kept, g.total, g.need, g.out_symbols]), g.out[:g.out_symbols],
+                 g.out_offsets[:g.n_kept + 1]],
+        "tally_batch": [tb.row_ptr, tb.col[:tb.nnz], tb.val[:tb.nnz], torch.tensor([tb.nnz, tb.total, tb.need, tb.need_pairs])],
+        "select": [sel[:n_sel], torch.tensor([n_sel])],
+        "words": [wrd[:n_wrd], torch.tensor([n_wrd])],
+    }
+    torch.cuda.synchronize()
+    return c
+
+
+def _tmp_bytes(c, family):
+    L, h = binding.lib(), c.plan.h
+    if family == "grep":
+        return L.acm_gpu_grep_tmp_bytes(h, WINDOW, CAPACITY, N_SYMBOLS, N_TEXTS)
+    if family == "tally_batch":
+        return L.acm_gpu_tally_batch_tmp_bytes(h, WINDOW, CAPACITY, PAIR_CAPACITY, N_SYMBOLS, N_TEXTS)
+    if family == "select":
+        return L.acm_gpu_select_tmp_bytes(h, c.n, N_SYMBOLS)
+    return L.acm_gpu_words_tmp_bytes(h, c.n, N_TEXTS)
+
+
+def _outputs(c, family):
+    """the call's output tensors, every byte SENTINEL"""
+    torch = c.torch
+
+    def full(n, dtype):
+        t = torch.empty(n, dtype=dtype, device=c.text.device)
+        t.view(torch.uint8).fill_(SENTINEL)
+        return t
+    if family == "grep":        # hits, kept, (n_kept, total, need, out_symbols), out, out_offsets
+        return [full(N_TEXTS, torch.int64), full(N_TEXTS, torch.int32), full(4, torch.int64), full(N_SYMBOLS, torch.uint8),
+                full(N_TEXTS + 1, torch.int64)]
+    if family == "tally_batch":  # row_ptr, col, val, (nnz, total, need, need_pairs)
+        return [full(N_TEXTS + 1, torch.int64), full(PAIR_CAPACITY, torch.int32), full(PAIR_CAPACITY, torch.int64), full(4, torch.int64)]
+    return [full(2 * c.n, torch.int64).view(c.n, 2), full(1, torch.int64)]   # out, count
+
+
+def _call(c, family, out, d_tmp, tmp_bytes):
+    L, h, st = binding.lib(), c.plan.h, c.plan._stream()
+    p = [t.data_ptr() for t in out]
+    if family == "grep":
+        return L.acm_gpu_grep_device(h, c.text.data_ptr(), N_SYMBOLS, c.offsets.data_ptr(), N_TEXTS, binding.ACM_GREP_MATCHING, WINDOW, CAPACITY,
+                                     p[0], p[1], p[2], p[2] + 8, p[2] + 16, p[3], N_SYMBOLS, p[4], p[2] + 24, d_tmp, tmp_bytes, st)
+    if family == "tally_batch":
+        return L.acm_gpu_tally_batch_device(h, c.text.data_ptr(), N_SYMBOLS, c.offsets.data_ptr(), N_TEXTS, WINDOW, CAPACITY, PAIR_CAPACITY,
+                                            p[0], p[1], p[2], p[3], p[3] + 8, p[3] + 16, p[3] + 24, d_tmp, tmp_bytes, st)
+    if family == "select":
+        return L.acm_gpu_select_records_device(h, c.records.data_ptr(), c.n, None, 0, N_SYMBOLS, p[0], p[1], d_tmp, tmp_bytes, st)
+    return L.acm_gpu_words_records_device(h, c.text.data_ptr(), N_SYMBOLS, 0, c.offsets.data_ptr(), N_TEXTS, c.ranges.ctypes.data, c.n_ranges,
+                                          binding.ACM_WORDS_BOTH, c.records.data_ptr(), c.n, None, p[0], p[1], d_tmp, tmp_bytes, st)
+
+
+def _cut(family, out):
+    """the part of every output that counts, as c.want lists it"""
+    if family == "grep":
+        n_kept, _, _, out_symbols = (int(x) for x in out[2].cpu())
+        return [out[0], out[1][:n_kept], out[2], out[3][:out_symbols], out[4][:n_kept + 1]]
+    if family == "tally_batch":
+        nnz = int(out[3][0].item())
+        return [out[0], out[1][:nnz], out[2][:nnz], out[3]]
+    return [out[0][:int(out[1].item())], out[1]]
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+def test_exact_room(case, family):
+    c, torch = case, case.torch
+    tb = _tmp_bytes(c, family)
+    assert tb > 0
+    room = torch.empty(GUARD + tb + GUARD, dtype=torch.uint8, device=c.text.device)
+    room.fill_(0xFF)
+    out = _outputs(c, family)
+    rc = _call(c, family, out, room.data_ptr() + GUARD, tb)
+    torch.cuda.synchronize()
+    assert rc == binding.ACM_GPU_OK, rc
+    c.plan.status()                                      # (raises when a kernel flagged an error)
+    got = _cut(family, out)
+    assert len(got) == len(c.want[family])
+    for i, (g, w) in enumerate(zip(got, c.want[family])):
+        assert g.shape == w.shape and torch.equal(g.cpu(), w.cpu()), (family, i, g[:8], w[:8])
+    assert bool((room[:GUARD] == 0xFF).all()), "written in front of d_tmp"
+    assert bool((room[GUARD + tb:] == 0xFF).all()), "written past the reported size"
+
+
+@pytest.mark.parametrize("family", FAMILIES)
+def test_room_one_byte_short(case, family):
+    c, torch = case, case.torch
+    tb = _tmp_bytes(c, family)
+    room = torch.empty(GUARD + tb + GUARD, dtype=torch.uint8, device=c.text.device)
+    out = _outputs(c, family)
+    rc = _call(c, family, out, room.data_ptr() + GUARD, tb - 1)
+    torch.cuda.synchronize()
+    assert rc == E_ARG, rc
+    for i, t in enumerate(out):
+        assert bool((t.view(torch.uint8) == SENTINEL).all()), (family, i)
