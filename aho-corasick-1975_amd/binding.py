@@ -20,6 +20,8 @@ ACM_GREP_MATCHING, ACM_GREP_INVERT = 0, 1
 ACM_SPLIT_EVERY, ACM_SPLIT_RUNS = 0, 1
 ACM_WORDS_LEFT, ACM_WORDS_RIGHT, ACM_WORDS_BOTH = 1, 2, 3
 ACM_RULE_NO_MAX = 0xFFFFFFFF
+ACM_ANCHORED_PREFIXES, ACM_ANCHORED_LONGEST, ACM_ANCHORED_WHOLE = 1, 2, 3
+ACM_LOOKUP_NONE = 0xFFFFFFFF
 # the usual ASCII word set as inclusive (lo, hi) ranges: 0-9, A-Z, _, a-z (UTF-8 byte text adds (0x80, 0xFF))
 ASCII_WORD = ((0x30, 0x39), (0x41, 0x5A), (0x5F, 0x5F), (0x61, 0x7A))
 
@@ -108,6 +110,8 @@ EXPORTS = [
     "acm_tally_batch_records", "acm_gpu_tally_batch_tmp_bytes", "acm_gpu_tally_batch_device", "acm_gpu_tally_batch_host", "acm_tally_batch",
     "acm_words_records", "acm_gpu_words_tmp_bytes", "acm_gpu_words_records_device", "acm_gpu_scan_words_tmp_bytes", "acm_gpu_scan_words_device",
     "acm_gpu_scan_words_host", "acm_scan_words",
+    "acm_anchored_records", "acm_gpu_scan_anchored_tmp_bytes", "acm_gpu_scan_anchored_device", "acm_gpu_lookup_tmp_bytes", "acm_gpu_lookup_device",
+    "acm_gpu_scan_anchored_host", "acm_gpu_lookup_host", "acm_scan_anchored", "acm_lookup",
     "acm_rules_check", "acm_rules_matrix", "acm_gpu_rules_create", "acm_gpu_rules_destroy", "acm_gpu_rules_info", "acm_gpu_rules_matrix_tmp_bytes",
     "acm_gpu_rules_matrix_device", "acm_gpu_rules_tmp_bytes", "acm_gpu_rules_device", "acm_gpu_rules_host", "acm_rules",
 ]
@@ -387,6 +391,24 @@ def lib():
     L.acm_gpu_scan_words_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, u32, u32, vp, u64, C.POINTER(u64)]
     L.acm_scan_words.restype = i32
     L.acm_scan_words.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, C.POINTER(u64)]
+    L.acm_anchored_records.restype = i32
+    L.acm_anchored_records.argtypes = [vp, u64, u32, vp, u64, vp, vp, C.POINTER(u64)]
+    L.acm_gpu_scan_anchored_tmp_bytes.restype = sz
+    L.acm_gpu_scan_anchored_tmp_bytes.argtypes = [vp, u64]
+    L.acm_gpu_scan_anchored_device.restype = i32
+    L.acm_gpu_scan_anchored_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_lookup_tmp_bytes.restype = sz
+    L.acm_gpu_lookup_tmp_bytes.argtypes = [vp, u64]
+    L.acm_gpu_lookup_device.restype = i32
+    L.acm_gpu_lookup_device.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_anchored_host.restype = i32
+    L.acm_gpu_scan_anchored_host.argtypes = [vp, vp, vp, u64, u32, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_lookup_host.restype = i32
+    L.acm_gpu_lookup_host.argtypes = [vp, vp, vp, u64, vp, vp, vp]
+    L.acm_scan_anchored.restype = i32
+    L.acm_scan_anchored.argtypes = [vp, vp, vp, u64, u32, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_lookup.restype = i32
+    L.acm_lookup.argtypes = [vp, vp, vp, u64, vp, vp, vp]
     L.acm_gpu_flows_create.restype = i32
     L.acm_gpu_flows_create.argtypes = [vp, u64, C.POINTER(vp)]
     L.acm_gpu_flows_destroy.restype = None
@@ -899,6 +921,56 @@ def words_records(text, records, offsets=None, ranges=ASCII_WORD, flags="both", 
     return a[:n.value]
 
 
+_ANCHORED_MODES = {"prefixes": ACM_ANCHORED_PREFIXES, "longest": ACM_ANCHORED_LONGEST, "whole": ACM_ANCHORED_WHOLE}
+
+
+def _anchored_mode(mode):
+    return _ANCHORED_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def anchored_records(records, offsets, mode="prefixes"):
+    """acm_anchored_records(): ANCHORED of a batch's records (RECORD_DTYPE, canonical order) under
+    `offsets` by the sequential pass on the host -- mode "prefixes" (the keywords every text begins
+    with), "longest" (the longest of them) or "whole" (the keyword that spells the whole text).
+    Returns new arrays (records, text_id, first); `records` is not changed."""
+    a = np.array(records, dtype=RECORD_DTYPE, copy=True).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64)
+    assert off.size >= 1, "offsets has n_texts + 1 entries"
+    tid = np.zeros(max(a.size, 1), dtype=np.uint32)
+    first = np.zeros(off.size, dtype=np.uint64)
+    n = C.c_uint64(0)
+    _check(lib().acm_anchored_records(off.ctypes.data, off.size - 1, _anchored_mode(mode), a.ctypes.data if a.size else None, a.size,
+                                      tid.ctypes.data, first.ctypes.data, C.byref(n)), "acm_anchored_records")
+    return a[:n.value], tid[:n.value], first
+
+
+def _anchored_host_call(fn, what, handle, t, off, mode, capacity):
+    """the host-memory anchored calls (plan or machine): (records, text_id, first); an overflow is
+    repeated once with the size the call reports unless `capacity` was given"""
+    n_texts = off.size - 1
+    cap = int(capacity) if capacity is not None else max(n_texts, 1)
+    for attempt in (0, 1):
+        out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
+        tid = np.zeros(max(cap, 1), dtype=np.uint32)
+        first = np.zeros(n_texts + 1, dtype=np.uint64)
+        n = C.c_uint64(0)
+        rc = fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, _anchored_mode(mode), out.ctypes.data, tid.ctypes.data,
+                first.ctypes.data, cap, C.byref(n))
+        if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
+            cap = int(n.value)
+            continue
+        _check(rc, what)
+        return out[:n.value], tid[:n.value], first
+
+
+def _lookup_host_call(fn, what, handle, t, off):
+    """the host-memory lookup calls (plan or machine): (whole_id, prefix_id, prefix_len), one entry per text"""
+    n_texts = off.size - 1
+    res = [np.zeros(max(n_texts, 1), dtype=np.uint32) for _ in range(3)]
+    _check(fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, *[r.ctypes.data for r in res]), what)
+    return tuple(r[:n_texts] for r in res)
+
+
 def _grep_lines_host_call(fn, what, handle, t, sym_size, d, nd, runs, invert, gather):
     """acm_gpu_grep_lines_host / acm_grep_lines: numpy in, a Grepped of numpy arrays out.  A first call
     with no room for a text learns n_texts (it ends behind the split's count), the second has room."""
@@ -1239,6 +1311,21 @@ class Machine:
                 r["end_pos"] -= offsets[t]
                 res.append(r)
             return res
+
+    def scan_anchored(self, texts, mode="prefixes", capacity=None):
+        """acm_scan_anchored(): the keywords every text of a list begins with (mode "prefixes"), the
+        longest of them ("longest") or the keyword that spells the whole text ("whole": `grep -x`).
+        Returns (records, text_id, first) as scan_batch's packed form: end_pos = the index in the
+        packed buffer, records [first[t], first[t + 1]) are those of text t."""
+        packed, offsets = self._pack_texts(texts)
+        return _anchored_host_call(self.L.acm_scan_anchored, "acm_scan_anchored", self.handle, packed, offsets, mode, capacity)
+
+    def lookup(self, texts):
+        """acm_lookup(): one answer per text of a list -- (whole_id, prefix_id, prefix_len): the id of
+        the keyword that spells the whole text, the id and the length of the longest keyword the text
+        begins with; ACM_LOOKUP_NONE / 0 where there is none.  whole_id is a column's dictionary code."""
+        packed, offsets = self._pack_texts(texts)
+        return _lookup_host_call(self.L.acm_lookup, "acm_lookup", self.handle, packed, offsets)
 
     def tally(self, text, tally=None):
         """acm_tally(): how often every keyword occurs in `text`.  Returns (np.uint64 array with one
@@ -1611,6 +1698,72 @@ class Plan:
                 continue
             _check(rc, "acm_gpu_scan_batch_host")
             return out[:n.value], tid[:n.value], first
+
+    def scan_anchored(self, text, offsets, mode="prefixes", capacity=None, records=None, text_id=None, first=None, count=None, tmp=None):
+        """acm_gpu_scan_anchored_device(): `text` and `offsets` as Plan.scan_batch takes them.  The
+        keywords every text begins with (mode "prefixes"), the longest of them ("longest") or the
+        keyword that spells the whole text ("whole"), found by a walk from the root with no scan.
+        Queued on the current stream; returns device tensors (records int64 [capacity, 2], text_id
+        int32, first int64 [n_texts + 1], count int64 [1], tmp).  capacity holds the anchored records
+        only: by default n_texts, which "longest" and "whole" cannot exceed; count > capacity says
+        what "prefixes" needs, and first is complete either way."""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        dev = text.device
+        if records is None:
+            records = torch.empty((max(int(capacity) if capacity is not None else n_texts, 1), 2), dtype=torch.int64, device=dev)
+        cap = records.shape[0] if capacity is None else int(capacity)
+        if text_id is None:
+            text_id = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        if first is None:
+            first = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
+        if count is None:
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+        tb = lib().acm_gpu_scan_anchored_tmp_bytes(self.h, n_texts)
+        if tmp is None or tmp.numel() < tb:
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        _check(lib().acm_gpu_scan_anchored_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, _anchored_mode(mode),
+                                                  records.data_ptr(), text_id.data_ptr(), first.data_ptr(), cap, count.data_ptr(), tmp.data_ptr(),
+                                                  tmp.numel(), self._stream()), "acm_gpu_scan_anchored_device")
+        return records, text_id, first, count, tmp
+
+    def lookup(self, text, offsets, whole_id=True, prefix_id=True, prefix_len=True, tmp=None):
+        """acm_gpu_lookup_device(): one answer per text of a batch on the device, queued on the current
+        stream -- int32 device tensors (whole_id, prefix_id, prefix_len) of n_texts entries: the id
+        of the keyword that spells the whole text (a column's dictionary code), the id and the
+        length of the longest keyword the text begins with; -1 (ACM_LOOKUP_NONE) / 0 where there is
+        none.  An output given as False is not computed (None comes back); a tensor is written in place."""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        outs = [torch.empty(max(n_texts, 1), dtype=torch.int32, device=text.device) if o is True else (None if o is False or o is None else o)
+                for o in (whole_id, prefix_id, prefix_len)]
+        tb = lib().acm_gpu_lookup_tmp_bytes(self.h, n_texts)
+        if tmp is None or tmp.numel() < tb:
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        _check(lib().acm_gpu_lookup_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts,
+                                           *[o.data_ptr() if o is not None else None for o in outs], tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_lookup_device")
+        return tuple(o[:n_texts] if o is not None else None for o in outs)
+
+    def scan_anchored_host(self, text, offsets, mode="prefixes", capacity=None):
+        """acm_gpu_scan_anchored_host(): the same from host arrays, through the C ABI only (no torch):
+        numpy arrays (records, text_id, first)."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        return _anchored_host_call(lib().acm_gpu_scan_anchored_host, "acm_gpu_scan_anchored_host", self.h, np.ascontiguousarray(text), off, mode,
+                                   capacity)
+
+    def lookup_host(self, text, offsets):
+        """acm_gpu_lookup_host(): numpy in, (whole_id, prefix_id, prefix_len) out, through the C ABI only."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        return _lookup_host_call(lib().acm_gpu_lookup_host, "acm_gpu_lookup_host", self.h, np.ascontiguousarray(text), off)
 
     @property
     def tally_form(self):

@@ -2712,21 +2712,29 @@ scan_impl (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint6
   return rc;
 }
 
+/* deltas replaced since the last call that used the plan's delta: whatever may still use them is on
+ * this stream, in front of this mark */
+int
+mark_retired (ACMPlan *p, hipStream_t st) {
+  if (p->retired.empty ())
+    return ACM_GPU_OK;
+  HIP_TRY (hipSetDevice (p->device));
+  for (auto &r : p->retired)
+    if (!r.done) {
+      HIP_TRY (hipEventCreateWithFlags (&r.done, hipEventDisableTiming));
+      HIP_TRY (hipEventRecord (r.done, st));
+    }
+  return ACM_GPU_OK;
+}
+
 /* a plan and, if it has one, its delta (acm_gpu_plan_update): both scans append to the same record
  * buffer through the plan's running total, handed to the caller's counter at the end */
 template <bool COUNT_ONLY>
 int
 scan_plan (ACMPlan *p, const void *d_text, uint64_t n, uint64_t emit_from, uint64_t pos_base, ACMRecord *d_records,
            uint64_t capacity, uint64_t *d_count, hipStream_t st, bool accumulate = false) {
-  if (!p->retired.empty ()) {
-    HIP_TRY (hipSetDevice (p->device));
-    /* deltas replaced since the last scan: whatever may still use them is on this stream, in front of this mark */
-    for (auto &r : p->retired)
-      if (!r.done) {
-        HIP_TRY (hipEventCreateWithFlags (&r.done, hipEventDisableTiming));
-        HIP_TRY (hipEventRecord (r.done, st));
-      }
-  }
+  if (const int rc = mark_retired (p, st))
+    return rc;
   if (!p->delta)
     return scan_impl<COUNT_ONLY> (p, d_text, n, emit_from, pos_base, d_records, capacity, d_count, st, accumulate);
   int rc = scan_impl<COUNT_ONLY> (p, d_text, n, emit_from, pos_base, d_records, capacity, d_count, st, true);
@@ -3265,6 +3273,7 @@ struct BatchDownload {
   uint64_t *first;
   const uint64_t *d_first;
   uint64_t n_texts;
+  bool first_on_overflow = false; /* the call leaves d_first complete when the records had no room (anchored): first[] comes down then too */
 };
 
 /* the end of a host convenience, behind its device call (which gave rc): the count, *n_found,
@@ -3279,8 +3288,11 @@ download_records (int rc, const uint64_t *d_count, const ACMRecord *d_rec, ACMRe
   if (!rc) {
     HOST_TRY (hipMemcpy (&found, d_count, 8, hipMemcpyDeviceToHost));
     *n_found = found;
-    if (found > capacity)
+    if (found > capacity) {
+      if (batch && batch->first_on_overflow && batch->first) /* (complete on the device whatever the room) */
+        HOST_TRY (hipMemcpy (batch->first, batch->d_first, (batch->n_texts + 1) * 8, hipMemcpyDeviceToHost));
       return ACM_GPU_E_OVERFLOW;
+    }
     rc = order (found);
   }
   if (rc) {
@@ -3350,6 +3362,9 @@ batch_offsets_ok (const uint64_t *offsets, uint64_t n_texts) {
       return false;
   return true;
 }
+
+/* the anchored records call takes fewer texts than this: hipCUB's sum counts its n_texts + 1 items in an int */
+constexpr uint64_t ANCHORED_MOST_TEXTS = (1ull << 31) - 1;
 
 /* a batch's arguments: fewer than `limit` texts, offsets[] as above, a text where there are symbols */
 bool
@@ -5693,6 +5708,238 @@ acm_gpu_scan_words_host (ACMPlan *plan, const void *text, uint64_t n_symbols, ui
   return download_records (rc, d_count, d_rec, records, capacity, n_found);
 }
 
+/* ------------------------------------------------------------------ anchored matches and dictionary lookup (include/acm_gpu.h, dev_anchored.h)
+ * No scan: the check of offsets[], one lane per text walking the goto function from the root, and for
+ * the records a prefix sum over the texts' counts and a second walk that writes them. */
+namespace {
+/* what anchored_carve derives beside K's pointers: the counts and their sums as the sum takes them */
+struct AnchoredRoom {
+  long long *count = nullptr, *first = nullptr;
+  CubRoom cub;
+};
+AnchoredRoom
+anchored_carve (Carve &c, uint64_t n_texts, bool records, AnchoredK &K) {
+  AnchoredRoom R;
+  K.ctl = c.take<AnchoredCtl> (1);
+  if (!records) /* the lookup call: the count pass writes the caller's arrays and nothing else */
+    return R;
+  R.count = c.take<long long> (n_texts + 1);
+  R.first = c.take<long long> (n_texts + 1);
+  R.cub = cub_room (c, 0, n_texts + 1);
+  K.count = reinterpret_cast<unsigned long long *> (R.count);
+  K.first = reinterpret_cast<const unsigned long long *> (R.first);
+  return R;
+}
+
+/* the plan's own trie is walked in the start-parallel tables: what acm_gpu_plan_update edits in place */
+bool
+anchored_in_starts (const ACMPlan *p) {
+  return p->kind == PlanKind::Starts && p->mir != nullptr;
+}
+
+/* a plan's trie as the walk reads it, behind starts_flush and prepare_text (which set what is bound here) */
+AnchoredTrie
+anchored_trie (const ACMPlan *p, bool starts, const void *walked_text) {
+  AnchoredTrie T{};
+  if (starts) {
+    T.starts.srec = p->TK.srec;
+    T.starts.sedge = p->TK.sedge;
+    T.starts.lut = p->TK.lut;
+    T.lut_size = p->TK.lut_size;
+  } else {
+    T.csr.row_ptr = p->csr.row_ptr;
+    T.csr.edge_sym = p->csr.edge_sym;
+    T.csr.edge_next = p->csr.edge_next;
+  }
+  T.live = p->finfo.n_edges != 0 ? 1u : 0u;
+  T.oinfo = p->d_oinfo;
+  T.text = static_cast<const unsigned char *> (walked_text);
+  return T;
+}
+
+/* pending updates of a start-parallel plan into its tables, then the text as the plan's kernels read it */
+int
+anchored_prepare (ACMPlan *p, const void **text, uint64_t n_symbols, hipStream_t st) {
+  if (p->mir && (p->mir->full_upload || !p->mir->patches.empty ()))
+    if (const int rc = starts_flush (p, st))
+      return rc;
+  /* the text as the plan compares it: interned ids, class ids (prepare_text; the host round of 4-byte class plans
+   * included).  The aligned copy prepare_text makes for the scan kernels of other plans is not needed: the walk
+   * takes one naturally aligned symbol at a time and would pay for the whole buffer to read lmax symbols a text */
+  const bool mapped = p->d_intern || p->cls32 || p->d_classlut;
+  return n_symbols && mapped ? prepare_text (p, text, n_symbols, st) : (int)ACM_GPU_OK;
+}
+
+template <int SB, bool STARTS>
+int
+anchored_passes (const ACMPlan *plan, const AnchoredRoom &L, const AnchoredK &K, hipStream_t st) {
+  /* ACM_GPU_ANCHORED_GRID=<blocks>: the most blocks of the two passes (tests) */
+  const uint32_t most = tunable ("ACM_GPU_ANCHORED_GRID", ANCHORED_GRID_MAX, 1, ANCHORED_GRID_MAX, Tune::Any);
+  dim3 grid = capped_grid (plan, (K.n_texts + 1 + ANCHORED_THREADS - 1) / ANCHORED_THREADS);
+  grid.x = std::min (grid.x, most);
+  HIP_TRY (launch (anchored_count_kernel<SB, STARTS>, grid, dim3 (ANCHORED_THREADS), 0, st, K));
+  if (!K.mode)
+    return ACM_GPU_OK;
+  HIP_TRY (exclusive_sum (L.cub, L.count, L.first, K.n_texts + 1, st));
+  HIP_TRY (launch (anchored_fill_kernel<SB, STARTS>, grid, dim3 (ANCHORED_THREADS), 0, st, K));
+  return ACM_GPU_OK;
+}
+
+template <int SB>
+int
+anchored_launch (const ACMPlan *plan, const AnchoredRoom &L, const AnchoredK &K, hipStream_t st) {
+  return anchored_in_starts (plan) ? anchored_passes<SB, true> (plan, L, K, st) : anchored_passes<SB, false> (plan, L, K, st);
+}
+
+/* both device calls behind their own argument checks; K: the outputs and the mode (0: lookup) */
+int
+anchored_call (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, AnchoredK &K, void *d_tmp,
+               size_t tmp_bytes, hipStream_t st) {
+  Carve carve (d_tmp);
+  const AnchoredRoom L = anchored_carve (carve, n_texts, K.mode != 0, K);
+  if (!d_offsets || !d_tmp || tmp_bytes < carve.total () || (n_symbols && !d_text) || !symbols_ok (d_text, n_symbols, plan->text_sym_bytes))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  if (const int rc = mark_retired (plan, st))
+    return rc;
+  const void *text = d_text, *delta_text = d_text;
+  if (const int rc = anchored_prepare (plan, &text, n_symbols, st))
+    return rc;
+  K.base = anchored_trie (plan, anchored_in_starts (plan), text);
+  K.lmax = plan_lmax (plan);
+  if (plan->delta) {
+    if (const int rc = anchored_prepare (plan->delta, &delta_text, n_symbols, st))
+      return rc;
+    K.delta = anchored_trie (plan->delta, false, delta_text); /* (never edited in place: its CSR rows) */
+  } else
+    K.delta.text = K.base.text; /* (never read: the delta is not live) */
+  K.offsets = reinterpret_cast<const unsigned long long *> (d_offsets);
+  K.n_texts = n_texts;
+  K.n_symbols = n_symbols;
+  K.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (AnchoredCtl), st));
+  HIP_TRY (launch (anchored_check_kernel, capped_grid (plan, (n_texts + ANCHORED_THREADS - 1) / ANCHORED_THREADS), dim3 (ANCHORED_THREADS), 0, st, K));
+  switch (plan->finfo.sym_bytes) { /* (what the kernels walk: an interned 8-byte plan walks 4-byte ids) */
+  case 1: return anchored_launch<1> (plan, L, K, st);
+  case 2: return anchored_launch<2> (plan, L, K, st);
+  case 4: return anchored_launch<4> (plan, L, K, st);
+  default: return ACM_GPU_E_ARG;
+  }
+}
+
+bool
+anchored_mode_ok (uint32_t mode) {
+  return mode >= ACM_ANCHORED_PREFIXES && mode <= ACM_ANCHORED_WHOLE;
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_scan_anchored_tmp_bytes (const ACMPlan *plan, uint64_t n_texts) {
+  if (!plan || n_texts >= ANCHORED_MOST_TEXTS)
+    return 0;
+  Carve c;
+  AnchoredK K{};
+  anchored_carve (c, n_texts, true, K);
+  return c.total ();
+}
+
+extern "C" size_t
+acm_gpu_lookup_tmp_bytes (const ACMPlan *plan, uint64_t n_texts) {
+  if (!plan || n_texts >= (1ull << 32))
+    return 0;
+  Carve c;
+  AnchoredK K{};
+  anchored_carve (c, n_texts, false, K);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_scan_anchored_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint32_t mode,
+                              ACMRecord *d_records, uint32_t *d_text_id, uint64_t *d_first, uint64_t capacity, uint64_t *d_count, void *d_tmp,
+                              size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || !anchored_mode_ok (mode) || n_texts >= ANCHORED_MOST_TEXTS || (capacity && !d_records))
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0)
+    return empty_batch (plan, n_symbols, { d_count, d_first }, st);
+  AnchoredK K{};
+  K.mode = mode;
+  K.records = d_records;
+  K.text_id = d_text_id;
+  K.d_first = reinterpret_cast<unsigned long long *> (d_first);
+  K.capacity = capacity;
+  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
+  return anchored_call (plan, d_text, n_symbols, d_offsets, n_texts, K, d_tmp, tmp_bytes, st);
+}
+
+extern "C" int
+acm_gpu_lookup_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint32_t *d_whole_id,
+                       uint32_t *d_prefix_id, uint32_t *d_prefix_len, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || (!d_whole_id && !d_prefix_id && !d_prefix_len) || n_texts >= (1ull << 32))
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0)
+    return empty_batch (plan, n_symbols, {}, st);
+  AnchoredK K{};
+  K.whole_id = d_whole_id;
+  K.prefix_id = d_prefix_id;
+  K.prefix_len = d_prefix_len;
+  return anchored_call (plan, d_text, n_symbols, d_offsets, n_texts, K, d_tmp, tmp_bytes, st);
+}
+
+extern "C" int
+acm_gpu_scan_anchored_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t mode, ACMRecord *records,
+                            uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found) {
+  if (!plan || !n_found || !anchored_mode_ok (mode) || (capacity && !records) || !batch_args_ok (text, offsets, n_texts, ANCHORED_MOST_TEXTS))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const uint64_t n_symbols = offsets[n_texts];
+  const size_t tmp_bytes = acm_gpu_scan_anchored_tmp_bytes (plan, n_texts);
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_off = nullptr, *d_count = nullptr, *d_first = nullptr;
+  uint32_t *d_tid = nullptr;
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  HOST_TRY (temps.get (&d_count, 8));
+  HOST_TRY (temps.get (&d_rec, capacity * 16));
+  HOST_TRY (temps.get (&d_tid, capacity * 4));
+  HOST_TRY (temps.get (&d_first, (n_texts + 1) * 8));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  const int rc = acm_gpu_scan_anchored_device (plan, d_text, n_symbols, d_off, n_texts, mode, d_rec, d_tid, d_first, capacity, d_count, d_tmp, tmp_bytes,
+                                               nullptr);
+  const BatchDownload down = { text_id, d_tid, first, d_first, n_texts, true };
+  return download_records (rc, d_count, d_rec, records, capacity, n_found, &down);
+}
+
+extern "C" int
+acm_gpu_lookup_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t *whole_id, uint32_t *prefix_id,
+                     uint32_t *prefix_len) {
+  if (!plan || (!whole_id && !prefix_id && !prefix_len) || !batch_args_ok (text, offsets, n_texts, 1ull << 32))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const uint64_t n_symbols = offsets[n_texts];
+  const size_t tmp_bytes = acm_gpu_lookup_tmp_bytes (plan, n_texts);
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_off = nullptr;
+  uint32_t *host[3] = { whole_id, prefix_id, prefix_len }, *dev[3] = { nullptr, nullptr, nullptr };
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  for (int a = 0; a < 3; a++)
+    if (host[a])
+      HOST_TRY (temps.get (&dev[a], n_texts * 4));
+  if (const int rc = settle (plan, acm_gpu_lookup_device (plan, d_text, n_symbols, d_off, n_texts, dev[0], dev[1], dev[2], d_tmp, tmp_bytes, nullptr), false))
+    return rc;
+  for (int a = 0; a < 3; a++)
+    if (host[a] && n_texts)
+      HOST_TRY (hipMemcpy (host[a], dev[a], n_texts * 4, hipMemcpyDeviceToHost));
+  HOST_TRY (hipDeviceSynchronize ());
+  return ACM_GPU_OK;
+}
+
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
 extern "C" int
 acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint32_t *len_bits, uint32_t *kw_bits) {
@@ -6347,8 +6594,8 @@ route_plan (ACMachine *machine, ScanRoute *R) {
 
 namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
- * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally only a scan that
- * succeeded, acm_select, acm_scan_words and acm_scan_from also one that found more records than there was room for,
+ * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally and acm_lookup only a scan that
+ * succeeded, acm_select, acm_scan_words, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
  * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch and acm_rules also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
@@ -6375,7 +6622,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The twelve calls below run on the same route, the same cached plan, under the same lock. */
+/* The fourteen calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -6428,6 +6675,31 @@ acm_scan_words (ACMachine *machine, const void *text, uint64_t n_symbols, const 
     machine, RecordPath::OnSuccessOrOverflow,
     [&] (uint32_t said) { return acm_internal_cpu_scan_words (machine, text, n_symbols, said, ranges, n_ranges, flags, records, capacity, n_found); },
     [&] (ACMPlan *plan) { return acm_gpu_scan_words_host (plan, text, n_symbols, 0, nullptr, 0, ranges, n_ranges, flags, records, capacity, n_found); });
+}
+
+/* anchored matches and the dictionary lookup of a batch (include/acm_gpu.h) */
+extern "C" int
+acm_scan_anchored (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t mode, ACMRecord *records,
+                   uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found) {
+  if (!machine || !n_found || !anchored_mode_ok (mode) || (capacity && !records) || !batch_args_ok (text, offsets, n_texts, ANCHORED_MOST_TEXTS))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      return acm_internal_cpu_scan_anchored (machine, text, offsets, n_texts, said, mode, records, text_id, first, capacity, n_found);
+    },
+    [&] (ACMPlan *plan) { return acm_gpu_scan_anchored_host (plan, text, offsets, n_texts, mode, records, text_id, first, capacity, n_found); });
+}
+
+extern "C" int
+acm_lookup (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t *whole_id, uint32_t *prefix_id,
+            uint32_t *prefix_len) {
+  if (!machine || (!whole_id && !prefix_id && !prefix_len) || !batch_args_ok (text, offsets, n_texts, 1ull << 32))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccess,
+    [&] (uint32_t said) { return acm_internal_cpu_lookup (machine, text, offsets, n_texts, said, whole_id, prefix_id, prefix_len); },
+    [&] (ACMPlan *plan) { return acm_gpu_lookup_host (plan, text, offsets, n_texts, whole_id, prefix_id, prefix_len); });
 }
 
 /* search-and-replace (include/acm_gpu.h) */

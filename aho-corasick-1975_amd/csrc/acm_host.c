@@ -1536,3 +1536,130 @@ acm_internal_cpu_rules (ACMachine *m, const void *text, const uint64_t *offsets,
   free (row_ptr);
   return rc;
 }
+
+/* ANCHORED of a batch's records (include/acm_gpu.h): the plain sequential pass, in place in the front
+ * of the array.  Everything is checked first, so that nothing is modified when the call fails. */
+static uint64_t
+anchored_text_of (const uint64_t *offsets, uint64_t n_texts, uint64_t s) {
+  uint64_t lo = 0, hi = n_texts - 1; /* the largest text with offsets[text] <= s */
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo + 1) / 2;
+    if (offsets[mid] <= s)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  return lo;
+}
+
+int
+acm_anchored_records (const uint64_t *offsets, uint64_t n_texts, uint32_t mode, ACMRecord *records, uint64_t n, uint32_t *text_id, uint64_t *first,
+                      uint64_t *n_kept) {
+  if (!offsets || !n_kept || (n && !records) || mode < ACM_ANCHORED_PREFIXES || mode > ACM_ANCHORED_WHOLE || n_texts >= (1ull << 32) ||
+      offsets[0] != 0)
+    return ACM_GPU_E_ARG;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (offsets[t] > offsets[t + 1])
+      return ACM_GPU_E_ARG;
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    if (r->end_pos >= offsets[n_texts] || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos)
+      return ACM_GPU_E_ARG;
+    if (r->end_pos >= offsets[anchored_text_of (offsets, n_texts, r->end_pos + 1 - r->length) + 1]) /* across a cut */
+      return ACM_GPU_E_ARG;
+  }
+  uint64_t kept = 0, next = 0, last = UINT64_MAX; /* next: the first text whose first[] is still to be set; last: the text of records[kept - 1] */
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord r = records[j];
+    const uint64_t s = r.end_pos + 1 - r.length, t = anchored_text_of (offsets, n_texts, s);
+    if (s != offsets[t] || (mode == ACM_ANCHORED_WHOLE && r.length != offsets[t + 1] - offsets[t]))
+      continue;
+    if (mode == ACM_ANCHORED_LONGEST && kept && last == t) { /* a longer prefix of the same text takes the place of the shorter */
+      records[kept - 1] = r;
+      continue;
+    }
+    for (; first && next <= t; next++)
+      first[next] = kept;
+    if (text_id)
+      text_id[kept] = (uint32_t)t;
+    records[kept++] = r;
+    last = t;
+  }
+  for (; first && next <= n_texts; next++)
+    first[next] = kept;
+  *n_kept = kept;
+  return ACM_GPU_OK;
+}
+
+/* acm_scan_anchored on the host (include/acm_gpu.h): the caller loop from the root at every offset into a room of the
+ * call's own, then the sequential pass over what it found -- what ACM_SCAN_PATH_CPU_LOOP runs.  offsets[] has been
+ * checked by the caller.  records and text_id are written only when the kept records fit; first[] always is. */
+int
+acm_internal_cpu_scan_anchored (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint32_t mode,
+                                ACMRecord *records, uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found) {
+  if (!m || !offsets || !n_found || (capacity && !records) || mode < ACM_ANCHORED_PREFIXES || mode > ACM_ANCHORED_WHOLE)
+    return ACM_GPU_E_ARG;
+  ACMRecord *found_rec;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, offsets[n_texts], offsets, n_texts, sym_bytes, NULL, &found_rec, &found);
+  uint32_t *tid = !rc && text_id ? malloc ((found + 1) * sizeof (uint32_t)) : NULL;
+  if (!rc && text_id && !tid)
+    rc = ACM_GPU_E_NOMEM;
+  if (!rc)
+    rc = acm_anchored_records (offsets, n_texts, mode, found_rec, found, tid, first, n_found);
+  if (!rc && *n_found > capacity)
+    rc = ACM_GPU_E_OVERFLOW;
+  if (!rc && *n_found) {
+    memcpy (records, found_rec, *n_found * sizeof (ACMRecord));
+    if (text_id)
+      memcpy (text_id, tid, *n_found * sizeof (uint32_t));
+  }
+  free (tid);
+  free (found_rec);
+  return rc;
+}
+
+/* acm_lookup on the host: the same loop, PREFIXES in place, then LONGEST of it and WHOLE of a copy of it */
+int
+acm_internal_cpu_lookup (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint32_t *whole_id,
+                         uint32_t *prefix_id, uint32_t *prefix_len) {
+  if (!m || !offsets || (!whole_id && !prefix_id && !prefix_len))
+    return ACM_GPU_E_ARG;
+  ACMRecord *rec, *copy = NULL;
+  uint32_t *tid = NULL;
+  uint64_t found = 0, n_longest = 0, n_whole = 0;
+  int rc = cpu_scan_grown (m, text, offsets[n_texts], offsets, n_texts, sym_bytes, NULL, &rec, &found);
+  if (!rc)
+    rc = acm_anchored_records (offsets, n_texts, ACM_ANCHORED_PREFIXES, rec, found, NULL, NULL, &found);
+  if (!rc) {
+    copy = malloc ((found + 1) * sizeof (ACMRecord));
+    tid = malloc ((found + 1) * sizeof (uint32_t));
+    rc = copy && tid ? ACM_GPU_OK : ACM_GPU_E_NOMEM;
+  }
+  if (!rc) {
+    memcpy (copy, rec, found * sizeof (ACMRecord));
+    for (uint64_t t = 0; t < n_texts; t++) {
+      if (whole_id)
+        whole_id[t] = ACM_LOOKUP_NONE;
+      if (prefix_id)
+        prefix_id[t] = ACM_LOOKUP_NONE;
+      if (prefix_len)
+        prefix_len[t] = 0;
+    }
+    rc = acm_anchored_records (offsets, n_texts, ACM_ANCHORED_LONGEST, rec, found, tid, NULL, &n_longest);
+  }
+  for (uint64_t j = 0; !rc && j < n_longest; j++) {
+    if (prefix_id)
+      prefix_id[tid[j]] = rec[j].keyword_id;
+    if (prefix_len)
+      prefix_len[tid[j]] = rec[j].length;
+  }
+  if (!rc)
+    rc = acm_anchored_records (offsets, n_texts, ACM_ANCHORED_WHOLE, copy, found, tid, NULL, &n_whole);
+  for (uint64_t j = 0; !rc && whole_id && j < n_whole; j++)
+    whole_id[tid[j]] = copy[j].keyword_id;
+  free (tid);
+  free (copy);
+  free (rec);
+  return rc;
+}

@@ -96,6 +96,12 @@ int acm_internal_words_args_ok (uint32_t sym_bytes, const void *ranges, uint32_t
 /* acm_scan_words' host path: the caller loop, then acm_words_records over its records (arguments as acm_scan_words') */
 int acm_internal_cpu_scan_words (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *ranges, uint32_t n_ranges,
                                  uint32_t flags, ACMRecord *records, uint64_t capacity, uint64_t *n_found);
+/* acm_scan_anchored's and acm_lookup's host paths: the caller loop from the root at every offset, then acm_anchored_records over its
+ * records (arguments as the public calls'; offsets[] already checked) */
+int acm_internal_cpu_scan_anchored (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint32_t mode,
+                                    ACMRecord *records, uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found);
+int acm_internal_cpu_lookup (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint32_t *whole_id,
+                             uint32_t *prefix_id, uint32_t *prefix_len);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

@@ -1291,6 +1291,116 @@ int acm_scan_words (ACMachine *machine, const void *text, uint64_t n_symbols,
                     const void *ranges, uint32_t n_ranges, uint32_t flags,
                     ACMRecord *records, uint64_t capacity, uint64_t *n_found);
 
+/* ------------------------------------------------------------------ anchored matches and dictionary lookup
+ * Every consumer above rests on the unanchored scan: every occurrence of every keyword anywhere in a
+ * text.  The first question asked of table cells, packets and log lines is an anchored one: is this
+ * cell a keyword (set membership, dictionary encoding of a column, `grep -x -F -f`), does this line
+ * begin with a keyword (a protocol verb, a log tag, a URL scheme), which is the longest keyword it
+ * begins with.  It needs no scan: text t is walked from the root along the goto function only -- no
+ * failure link -- for at most min (|text t|, lmax) symbols, stopping at the first missing edge.  The
+ * cost does not depend on how long the texts are, and the result is bounded by the texts, not by
+ * the matches of the buffer.
+ *
+ * DEFINITION.  Inputs: the batch contract -- text t is the symbols [offsets[t], offsets[t + 1]) of
+ * one packed buffer, offsets[0] = 0, offsets[n_texts] = n_symbols, never decreasing, empty texts
+ * allowed.  Let B be acm_scan_batch's record set of that batch (the caller loop from acm_initiate on
+ * every text alone, end_pos = offsets[t] + i); a record's start is end_pos + 1 - length.
+ * ANCHORED (B, offsets, mode).  For every text t, in order, let P_t be the records of text t whose
+ * start equals offsets[t] -- the keywords that are prefixes of text t -- by ascending length (the
+ * canonical order: they share a start).
+ *   ACM_ANCHORED_PREFIXES (1) keeps all of P_t;
+ *   ACM_ANCHORED_LONGEST (2) keeps the last record of P_t, if P_t has any;
+ *   ACM_ANCHORED_WHOLE (3) keeps the record of P_t whose length is offsets[t + 1] - offsets[t], if
+ *     there is one: `grep -x`.
+ * Any other mode is ACM_GPU_E_ARG.  An empty text has no record.  The output is the concatenation
+ * over t, in canonical order by construction; text_id[r] and first[0 .. n_texts] come beside the
+ * records and mean exactly what acm_scan_batch's mean.
+ * LOOKUP.  The same walk with one fixed-size answer per text and no records:
+ *   whole_id[t]    the keyword_id of WHOLE's record of text t, else ACM_LOOKUP_NONE (0xFFFFFFFF);
+ *   prefix_id[t]   the keyword_id of LONGEST's record of text t, else ACM_LOOKUP_NONE;
+ *   prefix_len[t]  the length of LONGEST's record of text t, else 0.
+ * Each of the three arrays may be NULL; all three NULL is ACM_GPU_E_ARG.  The outputs are SET, not
+ * added to.
+ * Symbols compare as the plan's scan compares them: a plan of comparator classes matches over
+ * classes, an interned 8-byte plan over its ids.  Keyword ids are first-insertion ranks; keywords of
+ * a pending delta count like any others.
+ *
+ * acm_anchored_records: the plain sequential ANCHORED of a batch's records (in canonical order) on
+ * the host, no device, in place in the front of the array; text_id and first (each may be NULL) are
+ * rewritten for the kept records.  Offsets that break the contract, a record outside
+ * [0, offsets[n_texts]), of length 0 or across a cut: ACM_GPU_E_ARG, nothing modified.
+ *
+ * acm_gpu_scan_anchored_device (dev_anchored.h): the check of d_offsets in a launch of its own, a
+ * count pass (one lane per text), a 64-bit prefix sum into first[], a fill pass that walks again.
+ * The call only queues launches on `stream`, with no host round trip -- but for the classification
+ * round of 4-byte comparator-class plans, which the scans have too: the text goes through the plan's
+ * own preparation where that changes what a symbol is (class ids, interned ids) and the walk
+ * compares what the scan kernels compare; the aligned copy some plans make of a text for their scan
+ * kernels is not made, since the walk reads at most lmax symbols of a text.  A start-parallel plan
+ * is walked in the tables acm_gpu_plan_update edits; a plan with a pending delta walks both tries in
+ * lockstep.  d_text: any multiple of the caller's symbol size.
+ * CAPACITY holds the ANCHORED records only, never the concatenation's matches:
+ * min (sum over t of min (len_t, lmax), n_texts x the deepest nesting of keyword prefixes) bounds
+ * PREFIXES; LONGEST and WHOLE keep at most one record per text, so capacity = n_texts cannot overflow.
+ * *d_count <= capacity: the count is exact, and d_records, d_text_id and d_first are complete.
+ * *d_count > capacity: it is the capacity needed, and d_first is complete and valid (as
+ * acm_gpu_rules_device's fired_ptr is); d_records and d_text_id are unspecified and nothing is
+ * written outside d_records[0 .. capacity).  d_offsets that break the contract: *d_count = 0, no
+ * other output, acm_gpu_plan_status reports ACM_GPU_E_INTERNAL; no address is formed from an offset
+ * before the check has seen it.  n_texts = 0 requires n_symbols = 0 and gives no record; n_texts >=
+ * 2^31 - 1 is ACM_GPU_E_ARG (the prefix sum counts its n_texts + 1 items in 31 bits;
+ * acm_gpu_lookup_device, which has none, takes up to 2^32 - 1 texts).  d_tmp must hold acm_gpu_scan_anchored_tmp_bytes (plan,
+ * n_texts) bytes (0 for a call that would be refused): about 16 bytes per text.  Any plan kind, not
+ * while a stream (acm_gpu_stream_*) is open on the plan, one call at a time per plan.
+ * ACM_GPU_ANCHORED_GRID=<blocks> in the environment (1 to 2^20, read at every call) caps the grids
+ * of the two passes (tests: a few blocks striding over thousands of texts).
+ * acm_gpu_lookup_device: the check and the count pass alone, writing the arrays the caller gave.
+ * Under d_offsets that break the contract no output array is written and the status is
+ * ACM_GPU_E_INTERNAL.  d_tmp must hold acm_gpu_lookup_tmp_bytes (plan, n_texts) bytes.
+ * acm_gpu_scan_anchored_host, acm_gpu_lookup_host: the same from host memory, blocking; offsets[]
+ * is checked on the host (ACM_GPU_E_ARG); on ACM_GPU_E_OVERFLOW *n_found holds the capacity needed and
+ * first[] (if given) is complete, on every path of acm_scan_anchored too; records and text_id are
+ * not written then.
+ * acm_scan_anchored, acm_lookup: the calls on the machine itself, total over machines exactly as
+ * acm_scan_batch is (same three paths, same cached plan, same acm_gpu_plan_update; acm_scan_path
+ * recorded on success and on overflow).  ACM_SCAN_PATH_CPU_LOOP runs the caller loop per text on the
+ * host and acm_anchored_records, and derives the lookup arrays from LONGEST and WHOLE.  A missing
+ * device stays an error, never a fallback.
+ *
+ * Out of scope: matches anchored at the END of a text (suffix matches: acm_scan_batch and a host
+ * filter); flows, streams and several GPUs; pos_base; anchoring inside acm_grep, acm_tally_batch or
+ * acm_rules (their signatures do not change); case folding other than through comparator classes. */
+#define ACM_ANCHORED_PREFIXES 1
+#define ACM_ANCHORED_LONGEST 2
+#define ACM_ANCHORED_WHOLE 3
+#define ACM_LOOKUP_NONE 0xFFFFFFFFu
+int acm_anchored_records (const uint64_t *offsets, uint64_t n_texts, uint32_t mode,
+                          ACMRecord *records, uint64_t n, uint32_t *text_id /* may be NULL */,
+                          uint64_t *first /* n_texts + 1, may be NULL */, uint64_t *n_kept);   /* in place, front of the array */
+size_t acm_gpu_scan_anchored_tmp_bytes (const ACMPlan *plan, uint64_t n_texts);
+int acm_gpu_scan_anchored_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols,
+                                  const uint64_t *d_offsets, uint64_t n_texts, uint32_t mode,
+                                  ACMRecord *d_records, uint32_t *d_text_id /* may be NULL */,
+                                  uint64_t *d_first /* n_texts + 1, may be NULL */,
+                                  uint64_t capacity, uint64_t *d_count,
+                                  void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_lookup_tmp_bytes (const ACMPlan *plan, uint64_t n_texts);
+int acm_gpu_lookup_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols,
+                           const uint64_t *d_offsets, uint64_t n_texts,
+                           uint32_t *d_whole_id /* may be NULL */, uint32_t *d_prefix_id /* may be NULL */,
+                           uint32_t *d_prefix_len /* may be NULL */,
+                           void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_anchored_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t mode,
+                                ACMRecord *records, uint32_t *text_id, uint64_t *first,
+                                uint64_t capacity, uint64_t *n_found);       /* blocking */
+int acm_gpu_lookup_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts,
+                         uint32_t *whole_id, uint32_t *prefix_id, uint32_t *prefix_len);   /* blocking */
+int acm_scan_anchored (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t mode,
+                       ACMRecord *records, uint32_t *text_id, uint64_t *first,
+                       uint64_t capacity, uint64_t *n_found);
+int acm_lookup (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts,
+                uint32_t *whole_id, uint32_t *prefix_id, uint32_t *prefix_len);
+
 /* ------------------------------------------------------------------ streaming scan
  * Text that arrives piece by piece from the host (the reference's callers read files symbol by
  * symbol, generic_test.c:191).  The result is the caller loop's output over the concatenation of
