@@ -77,6 +77,10 @@ class RulesInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rules", "terms", "always_rules", "postings", "fast_texts", "wide_texts")]
 
 
+class PatternsInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("patterns", "terms", "anchor_keywords", "longest", "max_anchor_postings")]
+
+
 _lib = None
 
 # every symbol include/acm.h and include/acm_gpu.h declare
@@ -114,6 +118,9 @@ EXPORTS = [
     "acm_gpu_scan_anchored_host", "acm_gpu_lookup_host", "acm_scan_anchored", "acm_lookup",
     "acm_rules_check", "acm_rules_matrix", "acm_gpu_rules_create", "acm_gpu_rules_destroy", "acm_gpu_rules_info", "acm_gpu_rules_matrix_tmp_bytes",
     "acm_gpu_rules_matrix_device", "acm_gpu_rules_tmp_bytes", "acm_gpu_rules_device", "acm_gpu_rules_host", "acm_rules",
+    "acm_patterns_check", "acm_patterns_records", "acm_gpu_patterns_create", "acm_gpu_patterns_destroy", "acm_gpu_patterns_info",
+    "acm_gpu_patterns_tmp_bytes", "acm_gpu_patterns_records_device", "acm_gpu_scan_patterns_tmp_bytes", "acm_gpu_scan_patterns_device",
+    "acm_gpu_scan_patterns_host", "acm_scan_patterns",
 ]
 
 
@@ -366,6 +373,28 @@ def lib():
     for fn in (L.acm_gpu_rules_host, L.acm_rules):
         fn.restype = i32
         fn.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_patterns_check.restype = i32
+    L.acm_patterns_check.argtypes = [vp, vp, u64, u64]
+    L.acm_patterns_records.restype = i32
+    L.acm_patterns_records.argtypes = [vp, u64, u64, u64, vp, u64, vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_patterns_create.restype = i32
+    L.acm_gpu_patterns_create.argtypes = [vp, vp, vp, u64, C.POINTER(vp)]
+    L.acm_gpu_patterns_destroy.restype = None
+    L.acm_gpu_patterns_destroy.argtypes = [vp]
+    L.acm_gpu_patterns_info.restype = i32
+    L.acm_gpu_patterns_info.argtypes = [vp, C.POINTER(PatternsInfo)]
+    L.acm_gpu_patterns_tmp_bytes.restype = sz
+    L.acm_gpu_patterns_tmp_bytes.argtypes = [vp, vp, u64, u64]
+    L.acm_gpu_patterns_records_device.restype = i32
+    L.acm_gpu_patterns_records_device.argtypes = [vp, vp, vp, u64, vp, u64, u64, vp, u64, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_patterns_tmp_bytes.restype = sz
+    L.acm_gpu_scan_patterns_tmp_bytes.argtypes = [vp, vp, u64, u64, u64]
+    L.acm_gpu_scan_patterns_device.restype = i32
+    L.acm_gpu_scan_patterns_device.argtypes = [vp, vp, vp, u64, u64, vp, u64, u64, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_patterns_host.restype = i32
+    L.acm_gpu_scan_patterns_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_scan_patterns.restype = i32
+    L.acm_scan_patterns.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_split_offsets.restype = i32
     L.acm_split_offsets.argtypes = [vp, u64, u32, vp, u32, u32, vp, u64, C.POINTER(u64)]
     L.acm_gpu_split_tmp_bytes.restype = sz
@@ -855,6 +884,104 @@ def _rules_host_call(fn, what, handle, t, sym_size, off, ruleset):
     def call(fired_ptr, fired, cap, n):
         return fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, *rs.args(), fired_ptr, fired, cap, n, C.byref(total))
     return _fired_host_call(call, what, n_texts, total)
+
+
+class PatternSet:
+    """Patterns with don't-care gaps packed to the two arrays the C calls take: terms (uint32 [n_terms, 3]:
+    keyword_id, offset, length) and pat_ptr (uint64, n_patterns + 1).  `patterns`: one list of (keyword_id,
+    offset, length) terms per pattern -- keyword keyword_id, `length` symbols long, begins `offset` symbols
+    behind the pattern's first symbol.  from_templates() makes one from templates with a wildcard symbol."""
+
+    def __init__(self, patterns):
+        patterns = [list(p) for p in patterns]
+        self.n_patterns = len(patterns)
+        flat = [tuple(int(x) for x in t) for p in patterns for t in p]
+        self.terms = np.array(flat, dtype=np.uint32).reshape(-1, 3)
+        self.pat_ptr = np.zeros(self.n_patterns + 1, np.uint64)
+        if patterns:
+            np.cumsum([len(p) for p in patterns], out=self.pat_ptr[1:])
+        self.n_keywords = int(self.terms[:, 0].max()) + 1 if self.terms.size else 0   # what the host pass is told when nothing else is known
+
+    @classmethod
+    def from_templates(cls, machine, templates, wildcard=None):
+        """A template is a sequence of symbols (bytes, or an array of symbol values) in which `wildcard` (a
+        symbol value; for bytes also a 1-byte string) marks a don't-care that matches any one symbol.  Every
+        template is cut into its maximal don't-care-free runs; the runs `machine` does not hold yet are
+        inserted, those it holds keep their ids.  ValueError for a template that ends in a don't-care or has
+        no symbol.  Returns the PatternSet (n_keywords = the machine's keywords afterwards)."""
+        if isinstance(wildcard, (bytes, bytearray)):
+            wildcard = wildcard[0]
+        known = None
+        patterns = []
+        for tpl in templates:
+            sym = [int(x) for x in (bytes(tpl) if isinstance(tpl, (bytes, bytearray)) else np.asarray(tpl).reshape(-1))]
+            if not sym or all(x == wildcard for x in sym):
+                raise ValueError("a template needs a symbol that is no don't-care")
+            if wildcard is not None and sym[-1] == wildcard:
+                raise ValueError("a template cannot end in a don't-care: it would test nothing but that the text goes on")
+            terms, i = [], 0
+            while i < len(sym):
+                if wildcard is not None and sym[i] == wildcard:
+                    i += 1
+                    continue
+                j = i
+                while j < len(sym) and (wildcard is None or sym[j] != wildcard):
+                    j += 1
+                run = np.array(sym[i:j], dtype=_SYM_DTYPE[machine.sym_size])
+                before = machine.nb_keywords
+                machine.add_keyword(run)
+                if machine.nb_keywords > before:
+                    kid = before
+                    if known is not None:
+                        known[machine.keyword(kid)[0]] = kid
+                else:                                              # held already: the dictionary's spelling of the run says which
+                    if known is None:
+                        known = {machine.keyword(k)[0]: k for k in range(machine.nb_keywords)}
+                    spelt = [w for e, length, w, _ in machine.match_loop(run) if e == run.size - 1 and length == run.size]
+                    kid = known[spelt[0]]
+                terms.append((kid, i, j - i))
+                i = j
+            patterns.append(terms)
+        ps = cls(patterns)
+        ps.n_keywords = machine.nb_keywords
+        return ps
+
+    def args(self):
+        """(terms, pat_ptr, n_patterns) as the C calls take them"""
+        return self.terms.ctypes.data if self.terms.size else None, self.pat_ptr.ctypes.data, self.n_patterns
+
+    def check(self, n_keywords):
+        """acm_patterns_check(): raises ACMError (ACM_GPU_E_ARG) for a set the calls would refuse"""
+        _check(lib().acm_patterns_check(*self.args(), int(n_keywords)), "acm_patterns_check")
+
+
+def _patternset(patterns):
+    return patterns if isinstance(patterns, PatternSet) else PatternSet(patterns)
+
+
+def patterns_records(records, patternset, n_symbols, offsets=None, pos_base=0, n_keywords=None, out_capacity=None):
+    """acm_patterns_records(): the matches of the patterns of `patternset` among `records` (RECORD_DTYPE, in
+    canonical order, positions pos_base + index into a buffer of n_symbols symbols), by the sequential pass
+    on the host: one record (end_pos of the match's last symbol, the pattern's length, the pattern's id) per
+    match, by end_pos ascending, length descending, pattern id ascending.  `offsets` (n_texts + 1 entries)
+    cuts the buffer into texts; a match lies inside one text.  out_capacity None: counted first, then sized
+    by the count; given and too small: ACMError (ACM_GPU_E_OVERFLOW)."""
+    ps = _patternset(patternset)
+    a = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
+    off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+    nk = int(n_keywords) if n_keywords is not None else ps.n_keywords
+    n = C.c_uint64(0)
+
+    def call(out, cap):
+        return lib().acm_patterns_records(a.ctypes.data if a.size else None, a.size, int(n_symbols), int(pos_base),
+                                          off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *ps.args(), nk,
+                                          out.ctypes.data if out is not None else None, cap, C.byref(n))
+    if out_capacity is None:                                       # (no output: the call only counts)
+        _check(call(None, 0), "acm_patterns_records")
+        out_capacity = int(n.value)
+    out = np.zeros(max(int(out_capacity), 1), dtype=RECORD_DTYPE)
+    _check(call(out, int(out_capacity)), "acm_patterns_records")
+    return out[:n.value]
 
 
 def _delims(delims, sym_size, raw=False):
@@ -1376,6 +1503,26 @@ class Machine:
             _check(rc, "acm_scan_words")
             return out[:n.value]
 
+    def scan_patterns(self, text, patternset, offsets=None, out_capacity=None):
+        """acm_scan_patterns(): the matches of the patterns of `patternset` (see patterns_records) in `text`,
+        or in every text of the buffer when `offsets` (n_texts + 1 entries) cuts it; by default an overflow is
+        repeated once with the size the call reports."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        ps = _patternset(patternset)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        cap = int(out_capacity) if out_capacity is not None else 1024
+        for attempt in (0, 1):
+            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            rc = self.L.acm_scan_patterns(self.handle, t.ctypes.data if t.size else None, t.size * t.itemsize // self.sym_size,
+                                          off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *ps.args(),
+                                          out.ctypes.data if cap else None, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_scan_patterns")
+            return out[:n.value]
+
     def replace(self, text, replacements=None, fill=None, out_capacity=None):
         """acm_replace(): `text` with its leftmost-longest non-overlapping matches (select()) replaced:
         by `replacements`, a list with one entry per keyword in keyword_id order (`bytes` or arrays
@@ -1496,6 +1643,32 @@ class Rules:
     def close(self):
         if self.h:
             lib().acm_gpu_rules_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Patterns:
+    """A pattern set on a plan's device (ACMPatterns): Plan.patterns_create() makes one."""
+
+    def __init__(self, handle, n_patterns):
+        self.h = handle
+        self.n_patterns = n_patterns
+
+    def info(self):
+        """acm_gpu_patterns_info(): patterns, terms, anchor_keywords, longest and max_anchor_postings as a
+        dict; n records give at most n * max_anchor_postings matches."""
+        i = PatternsInfo()
+        _check(lib().acm_gpu_patterns_info(self.h, C.byref(i)), "acm_gpu_patterns_info")
+        return {n: int(getattr(i, n)) for n, _ in PatternsInfo._fields_}
+
+    def close(self):
+        if self.h:
+            lib().acm_gpu_patterns_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -2051,6 +2224,108 @@ class Plan:
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         assert off.size >= 1, "offsets has n_texts + 1 entries"
         return _rules_host_call(lib().acm_gpu_rules_host, "acm_gpu_rules_host", self.h, t, self.sym_size, off, ruleset)
+
+    def patterns_create(self, patternset):
+        """acm_gpu_patterns_create(): `patternset` (a PatternSet, or lists of (keyword_id, offset, length)
+        terms) compiled and uploaded to this plan's device.  Returns a Patterns; it stays valid across update()."""
+        ps = _patternset(patternset)
+        h = C.c_void_p()
+        _check(lib().acm_gpu_patterns_create(self.h, *ps.args(), C.byref(h)), "acm_gpu_patterns_create")
+        return Patterns(h, ps.n_patterns)
+
+    def _patterns_handle(self, patterns):
+        """(a Patterns, whether this call made it) of a Patterns, a PatternSet or lists of terms"""
+        return (patterns, False) if isinstance(patterns, Patterns) else (self.patterns_create(patterns), True)
+
+    def patterns_records(self, records, n, patterns, n_symbols, offsets=None, pos_base=0, count=None, out=None, out_capacity=None, out_count=None):
+        """acm_gpu_patterns_records_device(): the matches of `patterns` (a Patterns from patterns_create(), or a
+        PatternSet compiled for this call) among records[:n] (an int64 [capacity, 2] device tensor in
+        canonical order), into `out` (None: a new tensor of out_capacity records, by default n times the
+        set's max_anchor_postings, which cannot overflow), queued on the current stream.  `count` (a device
+        int64 tensor) gives the number of records on the device: n is the room of `records` then.
+        `offsets` is a device int64 tensor of n_texts + 1 entries.  Returns (out, out_count): out_count (a
+        device tensor) holds the number of matches; above out_capacity it is the capacity needed.  Nothing
+        is synchronised."""
+        import torch
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
+        n = int(n)
+        P, own = self._patterns_handle(patterns)
+        try:
+            if out_capacity is None:
+                out_capacity = out.shape[0] if out is not None else n * P.info()["max_anchor_postings"]
+            out_capacity = int(out_capacity)
+            if out is None:
+                out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=records.device)
+            assert out.is_cuda and out.is_contiguous() and out.shape[0] >= out_capacity
+            if out_count is None:
+                out_count = torch.zeros(1, dtype=torch.int64, device=records.device)
+            n_texts = offsets.numel() - 1 if offsets is not None else 0
+            tb = lib().acm_gpu_patterns_tmp_bytes(self.h, P.h, n, n_texts)
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
+            _check(lib().acm_gpu_patterns_records_device(self.h, P.h, records.data_ptr(), n, count.data_ptr() if count is not None else None,
+                                                         int(n_symbols), int(pos_base), offsets.data_ptr() if offsets is not None else None, n_texts,
+                                                         out.data_ptr() if out_capacity else None, out_capacity, out_count.data_ptr(),
+                                                         tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_patterns_records_device")
+            if own:
+                torch.cuda.current_stream().synchronize()          # the set goes away with this call
+            return out, out_count
+        finally:
+            if own:
+                P.close()
+
+    def scan_patterns(self, text, patterns, offsets=None, n_symbols=None, pos_base=0, capacity=None, out=None, out_capacity=None, tmp=None):
+        """acm_gpu_scan_patterns_device(): the ordered scan of a device tensor into `capacity` records of the
+        call's own and the matches of `patterns` among them, queued on the current stream.  Returns (out,
+        count, found, tmp) with count and found device tensors: out[:count] are the matches when count <=
+        out_capacity; found is the scan's count -- above `capacity` there is no match (count 0) and found
+        is a capacity that suffices."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        capacity = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+        P, own = self._patterns_handle(patterns)
+        try:
+            if out_capacity is None:
+                out_capacity = out.shape[0] if out is not None else capacity * P.info()["max_anchor_postings"]
+            out_capacity = int(out_capacity)
+            if out is None:
+                out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=text.device)
+            res = torch.zeros(2, dtype=torch.int64, device=text.device)
+            n_texts = offsets.numel() - 1 if offsets is not None else 0
+            tb = lib().acm_gpu_scan_patterns_tmp_bytes(self.h, P.h, capacity, n_symbols, n_texts)
+            if tmp is None or tmp.numel() < tb:
+                tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+            _check(lib().acm_gpu_scan_patterns_device(self.h, P.h, text.data_ptr(), n_symbols, int(pos_base),
+                                                      offsets.data_ptr() if offsets is not None else None, n_texts, capacity,
+                                                      out.data_ptr() if out_capacity else None, out_capacity, res.data_ptr(), res.data_ptr() + 8,
+                                                      tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_scan_patterns_device")
+            if own:
+                torch.cuda.current_stream().synchronize()          # the set goes away with this call
+            return out, res[0:1], res[1:2], tmp
+        finally:
+            if own:
+                P.close()
+
+    def scan_patterns_host(self, text, patternset, offsets=None, pos_base=0, out_capacity=None):
+        """acm_gpu_scan_patterns_host(): numpy in, the pattern matches out, through the C ABI only (no torch); an
+        overflow is repeated once with the size the call reports."""
+        t = np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        ps = _patternset(patternset)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        cap = int(out_capacity) if out_capacity is not None else 1024
+        for attempt in (0, 1):
+            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            rc = lib().acm_gpu_scan_patterns_host(self.h, t.ctypes.data if t.size else None, n_sym, int(pos_base),
+                                                  off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *ps.args(),
+                                                  out.ctypes.data if cap else None, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_gpu_scan_patterns_host")
+            return out[:n.value]
 
     @property
     def select_form(self):

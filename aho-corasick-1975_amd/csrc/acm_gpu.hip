@@ -5940,6 +5940,289 @@ acm_gpu_lookup_host (ACMPlan *plan, const void *text, const uint64_t *offsets, u
   return ACM_GPU_OK;
 }
 
+/* ------------------------------------------------------------------ keyword patterns with don't-care gaps (include/acm_gpu.h, dev_patterns.h)
+ * A pattern set compiled into an index inverted by anchor keyword, and the passes that join a record
+ * set in canonical order under it: the check of offsets[], the count pass, the prefix over the
+ * records' counts, the fill pass, the order pass. */
+struct ACMPatterns {
+  int device = 0;
+  uint64_t n_patterns = 0, n_terms = 0, anchor_keywords = 0, longest = 0, max_anchor_postings = 0;
+  uint32_t n_keywords = 0;
+  void *blob = nullptr; /* one allocation: the arrays below */
+  uint32_t *d_anchor_ptr = nullptr, *d_other_ptr = nullptr;
+  uint4 *d_post = nullptr;
+  PatternOther *d_other = nullptr;
+};
+
+namespace {
+/* what patterns_carve derives beside K's pointers: the counts and their sums as the sum takes them */
+struct PatternsRoom {
+  long long *count = nullptr, *first = nullptr;
+  CubRoom cub;
+};
+PatternsRoom
+patterns_carve (Carve &c, uint64_t capacity, PatternsK &K) {
+  PatternsRoom R;
+  /* ACM_GPU_PATTERNS_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
+  K.tile = tunable ("ACM_GPU_PATTERNS_TILE", PATTERNS_TILE_DEFAULT, PATTERNS_TILE_MIN, PATTERNS_TILE_MAX, Tune::MultWave);
+  K.n_tiles = (capacity + K.tile - 1) / K.tile;
+  K.ctl = c.take<PatternsCtl> (1);
+  R.count = c.take<long long> ((size_t)capacity + 1);
+  R.first = c.take<long long> ((size_t)capacity + 1);
+  R.cub = cub_room (c, 0, capacity + 1);
+  K.count = reinterpret_cast<unsigned long long *> (R.count);
+  K.first = reinterpret_cast<const unsigned long long *> (R.first);
+  return R;
+}
+
+/* the fused call's scratch: the ordered scan's records, then the room the scan and the join share
+ * (the scan has ended when the join begins) */
+struct ScanPatternsRoom {
+  ACMRecord *found = nullptr;
+  unsigned char *work = nullptr;
+  size_t work_bytes = 0;
+};
+ScanPatternsRoom
+scan_patterns_carve (Carve &c, const ACMPlan *plan, const ACMPatterns *patterns, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  ScanPatternsRoom R;
+  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_patterns_tmp_bytes (plan, patterns, capacity, n_texts));
+  R.found = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
+  R.work = c.take (R.work_bytes);
+  return R;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_patterns_create (ACMPlan *plan, const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, ACMPatterns **out) {
+  if (!plan || !out)
+    return ACM_GPU_E_ARG;
+  const uint64_t nk = plan->covered_keywords;
+  if (acm_patterns_check (terms, pat_ptr, n_patterns, nk))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_terms = pat_ptr[n_patterns];
+  /* the index: every pattern under its anchor, the term with the greatest offset + length (the lowest
+   * index among equals); a keyword's postings by L descending, then pattern id ascending */
+  struct Post {
+    uint32_t keyword_id, pattern, L, alen;
+  };
+  std::vector<Post> post (n_patterns);
+  std::vector<uint32_t> anchor_ptr (nk + 1, 0), other_ptr (n_patterns + 1, 0);
+  std::vector<PatternOther> other (n_terms - n_patterns ? n_terms - n_patterns : 1);
+  uint64_t longest = 0;
+  for (uint64_t p = 0; p < n_patterns; p++) {
+    uint64_t anchor = pat_ptr[p];
+    for (uint64_t i = pat_ptr[p] + 1; i < pat_ptr[p + 1]; i++)
+      if (terms[i].offset + terms[i].length > terms[anchor].offset + terms[anchor].length)
+        anchor = i;
+    const uint32_t L = terms[anchor].offset + terms[anchor].length;
+    post[p] = Post{ terms[anchor].keyword_id, (uint32_t)p, L, terms[anchor].length };
+    longest = std::max<uint64_t> (longest, L);
+    uint32_t at = other_ptr[p];
+    for (uint64_t i = pat_ptr[p]; i < pat_ptr[p + 1]; i++)
+      if (i != anchor)
+        other[at++] = PatternOther{ L - (terms[i].offset + terms[i].length), terms[i].length, terms[i].keyword_id };
+    other_ptr[p + 1] = at;
+  }
+  std::sort (post.begin (), post.end (), [] (const Post &a, const Post &b) {
+    return a.keyword_id != b.keyword_id ? a.keyword_id < b.keyword_id : a.L != b.L ? a.L > b.L : a.pattern < b.pattern;
+  });
+  std::vector<uint4> post_dev (n_patterns ? n_patterns : 1);
+  for (uint64_t q = 0; q < n_patterns; q++) {
+    post_dev[q] = make_uint4 (post[q].pattern, post[q].L, post[q].alen, 0);
+    anchor_ptr[post[q].keyword_id + 1]++;
+  }
+  uint64_t anchor_keywords = 0, max_postings = 0;
+  for (uint64_t k = 0; k < nk; k++) {
+    anchor_keywords += anchor_ptr[k + 1] != 0;
+    max_postings = std::max<uint64_t> (max_postings, anchor_ptr[k + 1]);
+    anchor_ptr[k + 1] += anchor_ptr[k];
+  }
+  HIP_TRY (hipSetDevice (plan->device));
+  ACMPatterns *P = new (std::nothrow) ACMPatterns ();
+  if (!P)
+    return ACM_GPU_E_NOMEM;
+  P->device = plan->device;
+  P->n_patterns = n_patterns;
+  P->n_terms = n_terms;
+  P->anchor_keywords = anchor_keywords;
+  P->longest = longest;
+  P->max_anchor_postings = max_postings;
+  P->n_keywords = (uint32_t)nk;
+  size_t cur = 0;
+  const size_t o_anchor_ptr = blob_reserve (cur, anchor_ptr.size () * 4), o_post = blob_reserve (cur, post_dev.size () * sizeof (uint4)),
+               o_other_ptr = blob_reserve (cur, other_ptr.size () * 4), o_other = blob_reserve (cur, other.size () * sizeof (PatternOther));
+  bool ok = hipMalloc (&P->blob, cur) == hipSuccess;
+  unsigned char *b = static_cast<unsigned char *> (P->blob);
+  ok = ok && hipMemcpy (b + o_anchor_ptr, anchor_ptr.data (), anchor_ptr.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_post, post_dev.data (), post_dev.size () * sizeof (uint4), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_other_ptr, other_ptr.data (), other_ptr.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_other, other.data (), other.size () * sizeof (PatternOther), hipMemcpyHostToDevice) == hipSuccess &&
+       hipDeviceSynchronize () == hipSuccess;
+  if (!ok) {
+    acm_gpu_patterns_destroy (P);
+    return ACM_GPU_E_NOMEM;
+  }
+  P->d_anchor_ptr = reinterpret_cast<uint32_t *> (b + o_anchor_ptr);
+  P->d_post = reinterpret_cast<uint4 *> (b + o_post);
+  P->d_other_ptr = reinterpret_cast<uint32_t *> (b + o_other_ptr);
+  P->d_other = reinterpret_cast<PatternOther *> (b + o_other);
+  *out = P;
+  return ACM_GPU_OK;
+}
+
+extern "C" void
+acm_gpu_patterns_destroy (ACMPatterns *patterns) {
+  if (!patterns)
+    return;
+  (void)hipSetDevice (patterns->device);
+  if (patterns->blob)
+    (void)hipFree (patterns->blob);
+  delete patterns;
+}
+
+extern "C" int
+acm_gpu_patterns_info (const ACMPatterns *patterns, ACMPatternsInfo *info) {
+  if (!patterns || !info)
+    return ACM_GPU_E_ARG;
+  *info = ACMPatternsInfo{ patterns->n_patterns, patterns->n_terms, patterns->anchor_keywords, patterns->longest, patterns->max_anchor_postings };
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_patterns_tmp_bytes (const ACMPlan *plan, const ACMPatterns *patterns, uint64_t n_or_capacity, uint64_t n_texts) {
+  (void)n_texts; /* (nothing here is sized by the number of texts: the text of a match is a bisection of offsets[]) */
+  if (!plan || !patterns || n_or_capacity >= (1ull << 31))
+    return 0;
+  Carve c;
+  PatternsK K{};
+  patterns_carve (c, n_or_capacity, K);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_patterns_records_device (ACMPlan *plan, const ACMPatterns *patterns, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n,
+                                 uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out,
+                                 uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !patterns || patterns->device != plan->device || !d_count || n >= (1ull << 31) || out_capacity >= (1ull << 31) ||
+      n_symbols >= (1ull << 56) || (out_capacity && !d_out) || (n && (!d_records || !d_tmp)) ||
+      (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+    return ACM_GPU_E_ARG;
+  if (n && out_capacity) { /* (the output is written while the input is still read) */
+    const uintptr_t a = reinterpret_cast<uintptr_t> (d_records), b = reinterpret_cast<uintptr_t> (d_out);
+    if (a < b + out_capacity * sizeof (ACMRecord) && b < a + n * sizeof (ACMRecord))
+      return ACM_GPU_E_ARG;
+  }
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n == 0) /* (no record: no match, whatever *d_n says) */
+    return no_record (plan, nullptr, d_count, st);
+  Carve carve (d_tmp);
+  PatternsK K{};
+  const PatternsRoom L = patterns_carve (carve, n, K);
+  if (tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  K.anchor_ptr = patterns->d_anchor_ptr;
+  K.post = patterns->d_post;
+  K.other_ptr = patterns->d_other_ptr;
+  K.other = patterns->d_other;
+  K.n_keywords = patterns->n_keywords;
+  K.in = d_records;
+  K.capacity = n;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.n_symbols = n_symbols;
+  K.pos_base = pos_base;
+  K.offsets = n_texts ? d_offsets : nullptr; /* (no text: no symbol, every record breaks the contract) */
+  K.n_texts = n_texts;
+  K.out = d_out;
+  K.out_capacity = out_capacity;
+  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
+  K.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (PatternsCtl), st));
+  /* 1. */
+  if (K.offsets) /* one size, whatever the number of texts */
+    HIP_TRY (launch (patterns_check_kernel, capped_grid (plan, (n_texts + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, K));
+  /* 2. */
+  HIP_TRY (launch (patterns_count_kernel, capped_grid (plan, K.n_tiles), dim3 (PATTERNS_THREADS), 0, st, K));
+  /* 3. */
+  HIP_TRY (exclusive_sum (L.cub, L.count, L.first, n + 1, st));
+  /* 4. */
+  HIP_TRY (launch (patterns_fill_kernel, capped_grid (plan, K.n_tiles), dim3 (PATTERNS_THREADS), 0, st, K));
+  /* 5. */
+  if (out_capacity > 1)
+    HIP_TRY (launch (patterns_order_kernel, capped_grid (plan, (out_capacity + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, K));
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_scan_patterns_tmp_bytes (const ACMPlan *plan, const ACMPatterns *patterns, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!plan || !patterns || capacity >= (1ull << 31))
+    return 0;
+  Carve c;
+  scan_patterns_carve (c, plan, patterns, capacity, n_symbols, n_texts);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_scan_patterns_device (ACMPlan *plan, const ACMPatterns *patterns, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                              const uint64_t *d_offsets, uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint64_t out_capacity, uint64_t *d_count,
+                              uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !patterns || patterns->device != plan->device || !d_count || !d_found || capacity >= (1ull << 31) || out_capacity >= (1ull << 31) ||
+      (n_symbols && !d_text) || (out_capacity && !d_out) || (capacity && !d_tmp))
+    return ACM_GPU_E_ARG;
+  Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
+  const ScanPatternsRoom L = scan_patterns_carve (carve, plan, patterns, capacity, n_symbols, n_texts);
+  if (capacity && tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  if (capacity == 0) { /* no room: *d_found says what the records need, and nothing matches */
+    if (const int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_found, stream))
+      return rc;
+    return no_record (plan, nullptr, d_count, static_cast<hipStream_t> (stream));
+  }
+  if (const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, L.found, capacity, d_found, L.work, L.work_bytes, stream))
+    return rc;
+  return acm_gpu_patterns_records_device (plan, patterns, L.found, capacity, d_found, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count,
+                                          L.work, L.work_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_patterns_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                            const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, ACMRecord *out, uint64_t out_capacity,
+                            uint64_t *n_found) {
+  if (!plan || !n_found || out_capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
+      !optional_offsets_ok (offsets, n_texts, n_symbols) || (offsets && n_texts == 0 && n_symbols))
+    return ACM_GPU_E_ARG;
+  ACMPatterns *made = nullptr;
+  if (const int rc = acm_gpu_patterns_create (plan, terms, pat_ptr, n_patterns, &made))
+    return rc;
+  std::unique_ptr<ACMPatterns, void (*) (ACMPatterns *)> patterns (made, acm_gpu_patterns_destroy);
+  HIP_TRY (hipSetDevice (plan->device));
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the matches, the scan's records */
+  ACMRecord *d_out = nullptr;
+  uint64_t capacity = 0;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (temps.get (&d_res, 16));
+  if (const int rc = count_first (plan, d_text, n_symbols, d_res, &capacity)) /* the record room: the exact number of matches */
+    return rc;
+  const size_t tmp_bytes = acm_gpu_scan_patterns_tmp_bytes (plan, patterns.get (), capacity, n_symbols, n_texts);
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  HOST_TRY (temps.get (&d_out, out_capacity * 16));
+  if (offsets)
+    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  int rc = settle (plan,
+                   acm_gpu_scan_patterns_device (plan, patterns.get (), d_text, n_symbols, pos_base, d_off, n_texts, capacity, d_out, out_capacity, d_res,
+                                                 d_res + 1, d_tmp, tmp_bytes, nullptr),
+                   true);
+  uint64_t found = 0;
+  if (!rc) {
+    HOST_TRY (hipMemcpy (&found, d_res + 1, 8, hipMemcpyDeviceToHost));
+    if (found > capacity) /* (the room is what the count pass found: never expected) */
+      rc = ACM_GPU_E_INTERNAL;
+  }
+  return download_records (rc, d_res, d_out, out, out_capacity, n_found);
+}
+
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
 extern "C" int
 acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint32_t *len_bits, uint32_t *kw_bits) {
@@ -6596,7 +6879,7 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally and acm_lookup only a scan that
  * succeeded, acm_select, acm_scan_words, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
- * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch and acm_rules also one whose output had no room. */
+ * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules and acm_scan_patterns also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -6622,7 +6905,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The fourteen calls below run on the same route, the same cached plan, under the same lock. */
+/* The fifteen calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -6799,6 +7082,23 @@ acm_rules (ACMachine *machine, const void *text, const uint64_t *offsets, uint64
     },
     [&] (ACMPlan *plan) {
       return acm_gpu_rules_host (plan, text, offsets, n_texts, terms, rule_ptr, need, n_rules, fired_ptr, fired, fired_capacity, n_fired, total);
+    });
+}
+
+/* keyword patterns with don't-care gaps (include/acm_gpu.h) */
+extern "C" int
+acm_scan_patterns (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const ACMPatternTerm *terms,
+                   const uint64_t *pat_ptr, uint64_t n_patterns, ACMRecord *out, uint64_t out_capacity, uint64_t *n_found) {
+  if (!machine || !n_found || (n_symbols && !text) || (out_capacity && !out) || !optional_offsets_ok (offsets, n_texts, n_symbols) ||
+      acm_internal_patterns_machine_check (machine, terms, pat_ptr, n_patterns))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      return acm_internal_cpu_scan_patterns (machine, text, n_symbols, said, offsets, n_texts, terms, pat_ptr, n_patterns, out, out_capacity, n_found);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_scan_patterns_host (plan, text, n_symbols, 0, offsets, n_texts, terms, pat_ptr, n_patterns, out, out_capacity, n_found);
     });
 }
 

@@ -1663,3 +1663,197 @@ acm_internal_cpu_lookup (ACMachine *m, const void *text, const uint64_t *offsets
   free (rec);
   return rc;
 }
+
+/* ---- keyword patterns with don't-care gaps (include/acm_gpu.h): the argument checks, the plain sequential PATTERNS of a record
+ * set in canonical order, and acm_scan_patterns' host path. */
+int
+acm_patterns_check (const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, uint64_t n_keywords) {
+  if (!pat_ptr || pat_ptr[0] != 0 || n_patterns >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  for (uint64_t p = 0; p < n_patterns; p++)
+    if (pat_ptr[p] >= pat_ptr[p + 1]) /* decreasing, or a pattern without terms */
+      return ACM_GPU_E_ARG;
+  if (pat_ptr[n_patterns] >= (1ull << 31) || (n_patterns && !terms))
+    return ACM_GPU_E_ARG;
+  for (uint64_t i = 0; i < pat_ptr[n_patterns]; i++)
+    if (terms[i].length == 0 || (uint64_t)terms[i].offset + terms[i].length >= (1ull << 31) || terms[i].keyword_id >= n_keywords)
+      return ACM_GPU_E_ARG;
+  return ACM_GPU_OK;
+}
+
+/* a pattern under its anchor -- the term with the greatest offset + length, the lowest index among equals: its match ends where
+ * the pattern's does */
+struct pat_post {
+  uint32_t keyword_id, length; /* the anchor term's */
+  uint32_t L, pattern;
+};
+
+/* by anchor keyword, then L descending, then pattern id ascending: the order of a keyword's postings */
+static int
+pat_post_cmp (const void *a, const void *b) {
+  const struct pat_post *x = a, *y = b;
+  if (x->keyword_id != y->keyword_id)
+    return x->keyword_id < y->keyword_id ? -1 : 1;
+  if (x->L != y->L)
+    return x->L > y->L ? -1 : 1;
+  return x->pattern < y->pattern ? -1 : x->pattern > y->pattern;
+}
+
+/* the output order inside a group of equal end_pos: length descending, then pattern id ascending */
+static int
+pat_out_cmp (const void *a, const void *b) {
+  const ACMRecord *x = a, *y = b;
+  if (x->length != y->length)
+    return x->length > y->length ? -1 : 1;
+  return x->keyword_id < y->keyword_id ? -1 : x->keyword_id > y->keyword_id;
+}
+
+/* whether the record (end_pos, length, keyword_id) is in records[0 .. n), which are in canonical order (end_pos ascending, length
+ * descending: the pair is unique) */
+static int
+pat_has_record (const ACMRecord *records, uint64_t n, uint64_t end_pos, uint32_t length, uint32_t keyword_id) {
+  uint64_t lo = 0, hi = n; /* the first record at or behind the key */
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (records[mid].end_pos < end_pos || (records[mid].end_pos == end_pos && records[mid].length > length))
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo < n && records[lo].end_pos == end_pos && records[lo].length == length && records[lo].keyword_id == keyword_id;
+}
+
+/* whether the pattern of posting q matches with its anchor at record r (its keyword is the posting's) */
+static int
+pat_matches (const ACMRecord *records, uint64_t n, const ACMRecord *r, const struct pat_post *q, uint64_t n_symbols, uint64_t pos_base,
+             const uint64_t *offsets, uint64_t n_texts, const ACMPatternTerm *terms, const uint64_t *pat_ptr) {
+  const uint64_t e = r->end_pos - pos_base;
+  if (r->length != q->length || (uint64_t)q->L - 1 > e)
+    return 0;
+  const uint64_t S = e + 1 - q->L;
+  uint64_t t_hi = n_symbols; /* where the text of S ends */
+  if (offsets) {
+    uint64_t lo = 0, hi = n_texts - 1; /* the largest text with offsets[text] <= S (S < n_symbols: there are texts) */
+    while (lo < hi) {
+      const uint64_t mid = lo + (hi - lo + 1) / 2;
+      if (offsets[mid] <= S)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    t_hi = offsets[lo + 1];
+  }
+  if (e >= t_hi)
+    return 0;
+  for (uint64_t i = pat_ptr[q->pattern]; i < pat_ptr[q->pattern + 1]; i++) {
+    const ACMPatternTerm *term = &terms[i];
+    if (!pat_has_record (records, n, pos_base + S + term->offset + term->length - 1, term->length, term->keyword_id))
+      return 0;
+  }
+  return 1;
+}
+
+int
+acm_patterns_records (const ACMRecord *records, uint64_t n, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                      const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, uint64_t n_keywords, ACMRecord *out,
+                      uint64_t out_capacity, uint64_t *n_found) {
+  if (!n_found || (n && !records) || (out_capacity && !out) || acm_patterns_check (terms, pat_ptr, n_patterns, n_keywords))
+    return ACM_GPU_E_ARG;
+  if (offsets) {
+    if (offsets[0] != 0 || offsets[n_texts] != n_symbols)
+      return ACM_GPU_E_ARG;
+    for (uint64_t t = 0; t < n_texts; t++)
+      if (offsets[t] > offsets[t + 1])
+        return ACM_GPU_E_ARG;
+  }
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+      return ACM_GPU_E_ARG;
+  }
+  struct pat_post *post = malloc ((n_patterns ? n_patterns : 1) * sizeof *post);
+  if (!post)
+    return ACM_GPU_E_NOMEM;
+  for (uint64_t p = 0; p < n_patterns; p++) {
+    uint64_t anchor = pat_ptr[p];
+    for (uint64_t i = pat_ptr[p] + 1; i < pat_ptr[p + 1]; i++)
+      if (terms[i].offset + terms[i].length > terms[anchor].offset + terms[anchor].length)
+        anchor = i;
+    post[p] = (struct pat_post){ terms[anchor].keyword_id, terms[anchor].length, terms[anchor].offset + terms[anchor].length, (uint32_t)p };
+  }
+  qsort (post, n_patterns, sizeof *post, pat_post_cmp);
+  /* two passes over the records as anchors: the count, then -- when the matches fit -- the matches themselves */
+  uint64_t found = 0;
+  for (int fill = 0; fill < 2; fill++) {
+    found = 0;
+    for (uint64_t j = 0; j < n; j++) {
+      const ACMRecord *r = &records[j];
+      uint64_t lo = 0, hi = n_patterns; /* the keyword's first posting */
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (post[mid].keyword_id < r->keyword_id)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      for (uint64_t q = lo; q < n_patterns && post[q].keyword_id == r->keyword_id; q++)
+        if (pat_matches (records, n, r, &post[q], n_symbols, pos_base, offsets, n_texts, terms, pat_ptr)) {
+          if (fill)
+            out[found] = (ACMRecord){ r->end_pos, post[q].L, post[q].pattern };
+          found++;
+        }
+    }
+    if (!out || found > out_capacity) /* the call only counts, or the matches have no room */
+      break;
+  }
+  free (post);
+  *n_found = found;
+  if (!out)
+    return ACM_GPU_OK;
+  if (found > out_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  /* matches of one end can come from several anchor records and interleave in L then */
+  for (uint64_t b = 0; b < found;) {
+    uint64_t e = b + 1;
+    while (e < found && out[e].end_pos == out[b].end_pos)
+      e++;
+    if (e - b > 1)
+      qsort (out + b, e - b, sizeof *out, pat_out_cmp);
+    b = e;
+  }
+  return ACM_GPU_OK;
+}
+
+/* the checks acm_scan_patterns makes on every path: acm_patterns_check against the machine's keywords, and every term's
+ * length is its keyword's */
+int
+acm_internal_patterns_machine_check (ACMachine *m, const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns) {
+  if (!m)
+    return ACM_GPU_E_ARG;
+  int rc = ACM_GPU_OK;
+  acm_internal_lock (m);
+  rc = acm_patterns_check (terms, pat_ptr, n_patterns, m->nb_keywords);
+  for (uint64_t i = 0; !rc && i < pat_ptr[n_patterns]; i++)
+    if (m->keywords[terms[i].keyword_id]->depth != terms[i].length)
+      rc = ACM_GPU_E_ARG;
+  acm_internal_unlock (m);
+  return rc;
+}
+
+/* acm_scan_patterns on the host: the caller loop (from the root at every offset of a batch), then the sequential pass over
+ * what it found -- what ACM_SCAN_PATH_CPU_LOOP runs.  The public call has checked the arguments. */
+int
+acm_internal_cpu_scan_patterns (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                                const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, ACMRecord *out, uint64_t out_capacity,
+                                uint64_t *n_found) {
+  if (!m || !n_found)
+    return ACM_GPU_E_ARG;
+  ACMRecord *records;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, n_symbols, offsets, n_texts, sym_bytes, NULL, &records, &found);
+  if (!rc)
+    rc = acm_patterns_records (records, found, n_symbols, 0, offsets, n_texts, terms, pat_ptr, n_patterns, acm_nb_keywords (m), out, out_capacity,
+                               n_found);
+  free (records);
+  return rc;
+}

@@ -102,6 +102,13 @@ int acm_internal_cpu_scan_anchored (ACMachine *m, const void *text, const uint64
                                     ACMRecord *records, uint32_t *text_id, uint64_t *first, uint64_t capacity, uint64_t *n_found);
 int acm_internal_cpu_lookup (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint32_t *whole_id,
                              uint32_t *prefix_id, uint32_t *prefix_len);
+/* acm_scan_patterns' checks on every path: acm_patterns_check against the machine's keywords, and every term's length is its keyword's */
+int acm_internal_patterns_machine_check (ACMachine *m, const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns);
+/* acm_scan_patterns' host path: the caller loop (from the root at every offset when offsets is given), then acm_patterns_records over
+ * its records (arguments as acm_scan_patterns', the symbol size behind n_symbols; the public call has checked them) */
+int acm_internal_cpu_scan_patterns (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                                    const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, ACMRecord *out, uint64_t out_capacity,
+                                    uint64_t *n_found);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

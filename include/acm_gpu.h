@@ -1420,6 +1420,143 @@ int acm_gpu_stream_feed (ACMStream *stream, const void *text, uint64_t n_symbols
 int acm_gpu_stream_finish (ACMStream *stream, ACMRecord *records, uint64_t capacity, uint64_t *n_found);
 void acm_gpu_stream_close (ACMStream *stream);
 
+/* ------------------------------------------------------------------ keyword patterns with don't-care gaps
+ * Every consumer above acts on whole keywords; acm_rules combines them per text but knows no
+ * position.  A pattern with don't-care symbols -- a hex signature `E2 34 ?? C8 A1`, a motif with N, a
+ * fixed-column record template -- is the textbook second use of the automaton: the pattern is cut
+ * into its fragments, the fragments are the dictionary, and an occurrence of the pattern is a set of
+ * fragment occurrences at fixed distances from each other.  PATTERNS is that join.  It is a pure
+ * function of a record set in canonical order, as WORDS and SELECT are, so it runs behind every plan
+ * kind, symbol size, class plan and pending delta alike and has the record passes' calling shape.
+ *
+ * DEFINITION.  Terms and patterns: an ACMPatternTerm is (keyword_id, offset, length), three uint32_t.
+ * Pattern p is the terms [pat_ptr[p], pat_ptr[p + 1]) of terms[]; pat_ptr has n_patterns + 1 uint64_t
+ * entries.  A term says: keyword keyword_id, which is `length` symbols long, begins `offset` symbols
+ * behind the pattern's first symbol.  The pattern's length is L_p = max over its terms of (offset +
+ * length).  Symbols covered by no term are don't-cares.  Terms may come in any order and may
+ * overlap; leading don't-cares are allowed (the smallest offset may be above 0).
+ * ACM_GPU_E_ARG: a pattern without terms, length == 0, offset + length >= 2^31, keyword_id >=
+ * n_keywords, a pat_ptr that decreases or does not begin with 0, n_patterns >= 2^31, 2^31 terms or
+ * more.
+ * PATTERNS (R, offsets, P).  R is a record set in canonical order with positions pos_base + index.
+ * Text t is [offsets[t], offsets[t + 1]) under the batch contract (first 0, last n_symbols, never
+ * decreasing, empty texts allowed); offsets == NULL means that the buffer [0, n_symbols) is one
+ * text.  Pattern p MATCHES at buffer index S iff
+ *   there is a text t with offsets[t] <= S and S + L_p <= offsets[t + 1], and
+ *   for every term (k, o, l) of p the record (pos_base + S + o + l - 1, l, k) is in R.
+ * Each match gives one ACMRecord (end_pos = pos_base + S + L_p - 1, length = L_p, keyword_id = p).
+ * The output is in the total order end_pos ascending, then length descending, then pattern id
+ * ascending: deterministic, whichever term an implementation anchors on.  A term whose `length` is
+ * not its keyword's length never holds; the record passes cannot know the lengths, so this is no
+ * error in them.  Records that span a cut never take part, because every term lies inside
+ * [S, S + L_p): PATTERNS of the ordered scan of the packed buffer equals PATTERNS of
+ * acm_scan_batch's records.  When the terms of every pattern are the maximal don't-care-free runs of
+ * a template, this is exactly every occurrence, overlapping ones included, of the template with each
+ * don't-care matching any one symbol, inside one text; symbols compare as the plan's scan compares
+ * them.
+ *
+ * acm_patterns_check: the argument checks above, no device; every other entry point runs it.
+ * acm_patterns_records: the plain sequential PATTERNS on the host, no device.  ACM_GPU_E_OVERFLOW
+ * with *n_found = the entries needed when out_capacity is too small; `out` is untouched then.
+ * out == NULL with capacity 0 only counts.  ACM_GPU_E_ARG, with nothing written, for offsets that
+ * break the batch contract and for a record outside [pos_base, pos_base + n_symbols) (its end or
+ * its start) or of length 0.
+ *
+ * acm_gpu_patterns_create compiles a set once on the host and uploads it to the plan's device
+ * (ACMPatterns, opaque like ACMRules).  Each pattern's ANCHOR is the term with the greatest offset +
+ * length, the lowest index among equals: the anchor's match ends where the pattern's does.  The
+ * compiled set is an index inverted by anchor keyword, each keyword's postings sorted by (L
+ * descending, pattern id ascending), and per pattern its terms as (distance of the term's end in
+ * front of the pattern's end, length, keyword_id).  n_keywords is acm_gpu_tally_keywords (plan) at
+ * creation; the set stays valid after acm_gpu_plan_update, as a rule set does.
+ * acm_gpu_patterns_info: patterns, terms, the keywords that anchor a pattern, the longest L_p and the
+ * most postings of one keyword.  n x max_anchor_postings bounds the output of n records, so a caller
+ * can pick an out_capacity that cannot overflow.
+ *
+ * acm_gpu_patterns_records_device (dev_patterns.h): PATTERNS of d_records on the device,
+ * acm_gpu_words_records_device's shape: d_n NULL -- n_or_capacity is the number of records; d_n
+ * given -- *d_n is, and n_or_capacity the room of d_records.  n_or_capacity, out_capacity and
+ * n_texts are below 2^31; d_out must not overlap d_records (ACM_GPU_E_ARG).  The call only queues
+ * launches on `stream`, with no host round trip; the plan is used for its device, its grid cap and
+ * its error word only.  The check of d_offsets in a launch of its own (no address is formed from an
+ * offset before the check has seen it); a count pass, one lane per input record over tiles of 4,096
+ * records (ACM_GPU_PATTERNS_TILE=<records> in the environment sets another: a multiple of 64 from 64
+ * to 1 Mi, read at every call) -- the lane reads its keyword's postings and, per posting, tests the
+ * anchor term's length, finds the text of S by a bisection of offsets[], tests both bounds and looks
+ * every other term up in d_records by its key (end_pos, length), which is unique in canonical order;
+ * a 64-bit exclusive sum over the counts; a fill pass that verifies again and writes each match at
+ * its slot, one 16-byte store; an order pass that puts every group of equal end_pos into (L
+ * descending, pattern id ascending) -- matches of one end can come from several anchor records.  No
+ * atomics decide a slot, every output slot is written by one lane, and launch geometry never depends
+ * on what the records hold.  d_tmp must hold acm_gpu_patterns_tmp_bytes (plan, patterns,
+ * n_or_capacity, n_texts) bytes (0 for a call that would be refused).
+ *   *d_count <= out_capacity: the count is exact and d_out is complete and in order.
+ *   *d_count > out_capacity: it is the capacity needed, d_out is unspecified, and nothing is written
+ *     outside d_out[0 .. out_capacity).
+ *   *d_n > n_or_capacity (a scan that overflowed): *d_count = 0 and nothing is written.
+ *   d_offsets that break the contract: *d_count = 0, no other output, acm_gpu_plan_status reports
+ *     ACM_GPU_E_INTERNAL.
+ * A record that breaks the contract (a position outside [pos_base, pos_base + n_symbols), a start
+ * below pos_base, a length of 0) is skipped and acm_gpu_plan_status reports ACM_GPU_E_INTERNAL
+ * (select's rule).  Input that is not in canonical order gives an unspecified result; nothing is
+ * read or written out of bounds.
+ *
+ * acm_gpu_scan_patterns_device: acm_gpu_scan_ordered_device (emit_from 0) into `capacity` records
+ * inside d_tmp, then the passes above; d_tmp must hold acm_gpu_scan_patterns_tmp_bytes (plan,
+ * patterns, capacity, n_symbols, n_texts) bytes.  *d_found receives the scan's count: when it
+ * exceeds `capacity`, *d_count = 0 and *d_found is a capacity that suffices.
+ * acm_gpu_scan_patterns_host: the same from host memory, blocking; it creates and destroys the set
+ * itself and sizes the record room from acm_gpu_count_device.  ACM_GPU_E_OVERFLOW means only
+ * "out_capacity is too small, *n_found suffices".  Offsets that break the batch contract are
+ * ACM_GPU_E_ARG.
+ * acm_scan_patterns: the call on the machine itself, total over machines exactly as acm_rules is
+ * (same three paths, same cached plan, same acm_gpu_plan_update; acm_scan_path recorded on success
+ * and on overflow).  ACM_SCAN_PATH_CPU_LOOP runs the caller loop per text on the host, then
+ * acm_patterns_records.  This call knows the machine: a term whose `length` is not its keyword's
+ * length is ACM_GPU_E_ARG here.  A missing device stays an error, never a fallback.
+ *
+ * Out of scope: trailing don't-cares (not expressible: they would test nothing but that the text
+ * goes on); bounded variable gaps ({n-m}); symbol classes or alternatives inside a pattern; flows,
+ * streams and several GPUs; feeding pattern records to SELECT or REPLACE (their contract bounds
+ * lengths by the plan's lmax, and L_p is not bound by it). */
+typedef struct {
+  uint32_t keyword_id, offset, length;
+} ACMPatternTerm;
+typedef struct ACMPatterns ACMPatterns;
+typedef struct {
+  uint64_t patterns, terms, anchor_keywords, longest, max_anchor_postings;
+} ACMPatternsInfo;
+int acm_patterns_check (const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, uint64_t n_keywords);
+int acm_patterns_records (const ACMRecord *records, uint64_t n, uint64_t n_symbols, uint64_t pos_base,
+                          const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                          const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, uint64_t n_keywords,
+                          ACMRecord *out, uint64_t out_capacity, uint64_t *n_found);
+int acm_gpu_patterns_create (ACMPlan *plan, const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns,
+                             ACMPatterns **out);
+void acm_gpu_patterns_destroy (ACMPatterns *patterns);
+int acm_gpu_patterns_info (const ACMPatterns *patterns, ACMPatternsInfo *info);
+size_t acm_gpu_patterns_tmp_bytes (const ACMPlan *plan, const ACMPatterns *patterns, uint64_t n_or_capacity, uint64_t n_texts);
+int acm_gpu_patterns_records_device (ACMPlan *plan, const ACMPatterns *patterns, const ACMRecord *d_records,
+                                     uint64_t n_or_capacity, const uint64_t *d_n /* may be NULL */,
+                                     uint64_t n_symbols, uint64_t pos_base,
+                                     const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                     ACMRecord *d_out, uint64_t out_capacity, uint64_t *d_count,
+                                     void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_scan_patterns_tmp_bytes (const ACMPlan *plan, const ACMPatterns *patterns, uint64_t capacity,
+                                        uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_patterns_device (ACMPlan *plan, const ACMPatterns *patterns, const void *d_text, uint64_t n_symbols,
+                                  uint64_t pos_base, const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                  uint64_t capacity, ACMRecord *d_out, uint64_t out_capacity,
+                                  uint64_t *d_count, uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_patterns_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base,
+                                const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                                const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns,
+                                ACMRecord *out, uint64_t out_capacity, uint64_t *n_found);   /* blocking */
+int acm_scan_patterns (ACMachine *machine, const void *text, uint64_t n_symbols,
+                       const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                       const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns,
+                       ACMRecord *out, uint64_t out_capacity, uint64_t *n_found);
+
 /* ------------------------------------------------------------------ several GPUs of one node, one process
  * The reference's model for parallel work is one shared read-only machine and one cursor per worker
  * (/root/reference/README.md:364, aho_corasick.h:70: the caller owns the `const ACState *`).  The
