@@ -81,6 +81,10 @@ class PatternsInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("patterns", "terms", "anchor_keywords", "longest", "max_anchor_postings")]
 
 
+class ApproxInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("targets", "terms", "seed_keywords", "longest", "max_k", "max_postings")]
+
+
 _lib = None
 
 # every symbol include/acm.h and include/acm_gpu.h declare
@@ -121,6 +125,9 @@ EXPORTS = [
     "acm_patterns_check", "acm_patterns_records", "acm_gpu_patterns_create", "acm_gpu_patterns_destroy", "acm_gpu_patterns_info",
     "acm_gpu_patterns_tmp_bytes", "acm_gpu_patterns_records_device", "acm_gpu_scan_patterns_tmp_bytes", "acm_gpu_scan_patterns_device",
     "acm_gpu_scan_patterns_host", "acm_scan_patterns",
+    "acm_approx_check", "acm_approx_split", "acm_approx_records", "acm_gpu_approx_create", "acm_gpu_approx_destroy", "acm_gpu_approx_info",
+    "acm_gpu_approx_tmp_bytes", "acm_gpu_approx_records_device", "acm_gpu_scan_approx_tmp_bytes", "acm_gpu_scan_approx_device",
+    "acm_gpu_scan_approx_host", "acm_scan_approx",
 ]
 
 
@@ -395,6 +402,30 @@ def lib():
     L.acm_gpu_scan_patterns_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_scan_patterns.restype = i32
     L.acm_scan_patterns.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_approx_check.restype = i32
+    L.acm_approx_check.argtypes = [vp, vp, vp, vp, u64, u64]
+    L.acm_approx_split.restype = i32
+    L.acm_approx_split.argtypes = [u64, u32, u32, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_approx_records.restype = i32
+    L.acm_approx_records.argtypes = [vp, u64, vp, u32, u64, u64, vp, u64, vp, vp, vp, vp, vp, u64, u64, vp, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_approx_create.restype = i32
+    L.acm_gpu_approx_create.argtypes = [vp, vp, vp, vp, vp, vp, u64, C.POINTER(vp)]
+    L.acm_gpu_approx_destroy.restype = None
+    L.acm_gpu_approx_destroy.argtypes = [vp]
+    L.acm_gpu_approx_info.restype = i32
+    L.acm_gpu_approx_info.argtypes = [vp, C.POINTER(ApproxInfo)]
+    L.acm_gpu_approx_tmp_bytes.restype = sz
+    L.acm_gpu_approx_tmp_bytes.argtypes = [vp, vp, u64, u64, u64]
+    L.acm_gpu_approx_records_device.restype = i32
+    L.acm_gpu_approx_records_device.argtypes = [vp, vp, vp, u64, vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_approx_tmp_bytes.restype = sz
+    L.acm_gpu_scan_approx_tmp_bytes.argtypes = [vp, vp, u64, u64, u64, u64]
+    L.acm_gpu_scan_approx_device.restype = i32
+    L.acm_gpu_scan_approx_device.argtypes = [vp, vp, vp, u64, u64, vp, u64, u64, vp, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_approx_host.restype = i32
+    L.acm_gpu_scan_approx_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
+    L.acm_scan_approx.restype = i32
+    L.acm_scan_approx.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.acm_split_offsets.restype = i32
     L.acm_split_offsets.argtypes = [vp, u64, u32, vp, u32, u32, vp, u64, C.POINTER(u64)]
     L.acm_gpu_split_tmp_bytes.restype = sz
@@ -984,6 +1015,113 @@ def patterns_records(records, patternset, n_symbols, offsets=None, pos_base=0, n
     return out[:n.value]
 
 
+class ApproxSet:
+    """Targets with a mismatch budget packed to the arrays the C calls take: spell_data (the spellings side by
+    side, symbols of `sym_size` bytes), spell_off (uint64, n_targets + 1), k (uint32 per target), terms (uint32
+    [n_terms, 3]: keyword_id, offset, length) and tgt_ptr (uint64, n_targets + 1).  `targets`: one spelling per
+    target (bytes, or an array of symbols); `k`: a scalar or one budget per target; `terms`: one list of
+    (keyword_id, offset, length) per target -- keyword keyword_id, `length` symbols long, is the piece of the
+    spelling that begins at `offset`.  from_targets() makes one by the canonical cut."""
+
+    def __init__(self, targets, k, terms, sym_size=None):
+        targets = list(targets)
+        if sym_size is None:
+            sym_size = next((np.asarray(t).dtype.itemsize for t in targets if not isinstance(t, (bytes, bytearray))), 1)
+        self.sym_size = int(sym_size)
+        dt = _SYM_DTYPE[self.sym_size]
+        spelt = [np.frombuffer(bytes(t), np.uint8).astype(dt) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t, dtype=dt).reshape(-1)
+                 for t in targets]
+        self.n_targets = len(spelt)
+        self.spell_data = np.ascontiguousarray(np.concatenate(spelt)) if spelt else np.zeros(0, dt)
+        self.spell_off = np.zeros(self.n_targets + 1, np.uint64)
+        self.k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.uint32), (self.n_targets,)))
+        terms = [list(t) for t in terms]
+        assert len(terms) == self.n_targets, "one list of terms per target"
+        flat = [tuple(int(x) for x in t) for p in terms for t in p]
+        self.terms = np.array(flat, dtype=np.uint32).reshape(-1, 3)
+        self.tgt_ptr = np.zeros(self.n_targets + 1, np.uint64)
+        if spelt:
+            np.cumsum([t.size for t in spelt], out=self.spell_off[1:])
+            np.cumsum([len(p) for p in terms], out=self.tgt_ptr[1:])
+        self.n_keywords = int(self.terms[:, 0].max()) + 1 if self.terms.size else 0   # what the host pass is told when nothing else is known
+
+    @classmethod
+    def from_targets(cls, machine, targets, k):
+        """Every target is cut into k + 1 pieces by the canonical cut (acm_approx_split: piece j is [j * L // (k + 1),
+        (j + 1) * L // (k + 1))); the distinct pieces `machine` does not hold yet are inserted as keywords in order
+        of first appearance, those it holds keep their ids.  `k`: a scalar or one per target.  ValueError for a
+        target shorter than k + 1 symbols.  Returns the ApproxSet (n_keywords = the machine's keywords afterwards)."""
+        targets = list(targets)
+        ks = [int(x) for x in np.broadcast_to(np.asarray(k), (len(targets),))]
+        known = None
+        spelt, terms = [], []
+        for tgt, kk in zip(targets, ks):
+            sym = machine._symbols(tgt).reshape(-1)
+            if sym.size < kk + 1:
+                raise ValueError("a target of %d symbols cannot be cut into %d pieces" % (sym.size, kk + 1))
+            mine = []
+            for j in range(kk + 1):
+                b, e = C.c_uint64(0), C.c_uint64(0)
+                _check(lib().acm_approx_split(sym.size, kk, j, C.byref(b), C.byref(e)), "acm_approx_split")
+                run = np.array(sym[b.value:e.value], dtype=_SYM_DTYPE[machine.sym_size])
+                before = machine.nb_keywords
+                machine.add_keyword(run)
+                if machine.nb_keywords > before:
+                    kid = before
+                    if known is not None:
+                        known[machine.keyword(kid)[0]] = kid
+                else:                                              # held already: the dictionary's spelling of the piece says which
+                    if known is None:
+                        known = {machine.keyword(i)[0]: i for i in range(machine.nb_keywords)}
+                    spelling = [w for at, length, w, _ in machine.match_loop(run) if at == run.size - 1 and length == run.size]
+                    kid = known[spelling[0]]
+                mine.append((kid, int(b.value), int(e.value - b.value)))
+            spelt.append(sym)
+            terms.append(mine)
+        aset = cls(spelt, ks, terms, sym_size=machine.sym_size)
+        aset.n_keywords = machine.nb_keywords
+        return aset
+
+    def args(self):
+        """(spell_data, spell_off, k, terms, tgt_ptr, n_targets) as the C calls take them"""
+        return (self.spell_data.ctypes.data if self.spell_data.size else None, self.spell_off.ctypes.data, self.k.ctypes.data if self.k.size else None,
+                self.terms.ctypes.data if self.terms.size else None, self.tgt_ptr.ctypes.data, self.n_targets)
+
+    def check(self, n_keywords):
+        """acm_approx_check(): raises ACMError (ACM_GPU_E_ARG) for a set the calls would refuse"""
+        _check(lib().acm_approx_check(*self.args()[1:], int(n_keywords)), "acm_approx_check")
+
+
+def approx_records(records, approxset, text, offsets=None, pos_base=0, n_keywords=None, out_capacity=None):
+    """acm_approx_records(): the occurrences with at most k mismatches of the targets of `approxset` (an
+    ApproxSet) that the `records` seed (RECORD_DTYPE, in canonical order, positions pos_base + index into
+    `text`, an array of symbols of the set's size or bytes), by the sequential pass on the host.  Returns
+    (matches, dist): one record (end_pos of the last symbol, the target's length, the target's id) per match,
+    by end_pos ascending, length descending, target id ascending, and the mismatches of each.  `offsets`
+    (n_texts + 1 entries) cuts the buffer into texts; a match lies inside one text.  out_capacity None: counted
+    first, then sized by the count; given and too small: ACMError (ACM_GPU_E_OVERFLOW)."""
+    aset = approxset
+    a = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
+    t = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text)
+    n_symbols = t.size * t.itemsize // aset.sym_size
+    off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+    nk = int(n_keywords) if n_keywords is not None else aset.n_keywords
+    n = C.c_uint64(0)
+
+    def call(out, dist, cap):
+        return lib().acm_approx_records(a.ctypes.data if a.size else None, a.size, t.ctypes.data if t.size else None, aset.sym_size, n_symbols,
+                                        int(pos_base), off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0,
+                                        *aset.args(), nk, out.ctypes.data if out is not None else None,
+                                        dist.ctypes.data if dist is not None else None, cap, C.byref(n))
+    if out_capacity is None:                                       # (no output: the call only counts)
+        _check(call(None, None, 0), "acm_approx_records")
+        out_capacity = int(n.value)
+    out = np.zeros(max(int(out_capacity), 1), dtype=RECORD_DTYPE)
+    dist = np.zeros(max(int(out_capacity), 1), dtype=np.uint32)
+    _check(call(out, dist, int(out_capacity)), "acm_approx_records")
+    return out[:n.value], dist[:n.value]
+
+
 def _delims(delims, sym_size, raw=False):
     """delimiters as a contiguous array of whole symbols: bytes are one symbol per byte, widened to the
     symbol size (b"\\n" is the symbol 10), unless `raw` (symbols without a numpy type: the bytes as they are)"""
@@ -1523,6 +1661,26 @@ class Machine:
             _check(rc, "acm_scan_patterns")
             return out[:n.value]
 
+    def scan_approx(self, text, approxset, offsets=None, out_capacity=None):
+        """acm_scan_approx(): (matches, dist) of the targets of `approxset` (see approx_records) in `text`, or in
+        every text of the buffer when `offsets` (n_texts + 1 entries) cuts it; by default an overflow is repeated
+        once with the size the call reports."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        cap = int(out_capacity) if out_capacity is not None else 1024
+        for attempt in (0, 1):
+            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
+            dist = np.zeros(max(cap, 1), dtype=np.uint32)
+            n = C.c_uint64(0)
+            rc = self.L.acm_scan_approx(self.handle, t.ctypes.data if t.size else None, t.size * t.itemsize // self.sym_size,
+                                        off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *approxset.args(),
+                                        out.ctypes.data if cap else None, dist.ctypes.data, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_scan_approx")
+            return out[:n.value], dist[:n.value]
+
     def replace(self, text, replacements=None, fill=None, out_capacity=None):
         """acm_replace(): `text` with its leftmost-longest non-overlapping matches (select()) replaced:
         by `replacements`, a list with one entry per keyword in keyword_id order (`bytes` or arrays
@@ -1669,6 +1827,32 @@ class Patterns:
     def close(self):
         if self.h:
             lib().acm_gpu_patterns_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Approx:
+    """A target set with mismatch budgets on a plan's device (ACMApprox): Plan.approx_create() makes one."""
+
+    def __init__(self, handle, n_targets):
+        self.h = handle
+        self.n_targets = n_targets
+
+    def info(self):
+        """acm_gpu_approx_info(): targets, terms, seed_keywords, longest, max_k and max_postings as a dict; n
+        records give at most n * max_postings matches."""
+        i = ApproxInfo()
+        _check(lib().acm_gpu_approx_info(self.h, C.byref(i)), "acm_gpu_approx_info")
+        return {n: int(getattr(i, n)) for n, _ in ApproxInfo._fields_}
+
+    def close(self):
+        if self.h:
+            lib().acm_gpu_approx_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -2326,6 +2510,116 @@ class Plan:
                 continue
             _check(rc, "acm_gpu_scan_patterns_host")
             return out[:n.value]
+
+    def approx_create(self, approxset):
+        """acm_gpu_approx_create(): `approxset` (an ApproxSet) compiled and uploaded to this plan's device.
+        Returns an Approx; it stays valid across update().  A plan over comparator classes refuses
+        (ACM_GPU_E_INELIGIBLE)."""
+        h = C.c_void_p()
+        _check(lib().acm_gpu_approx_create(self.h, *approxset.args(), C.byref(h)), "acm_gpu_approx_create")
+        return Approx(h, approxset.n_targets)
+
+    def _approx_handle(self, approx):
+        """(an Approx, whether this call made it) of an Approx or an ApproxSet"""
+        return (approx, False) if isinstance(approx, Approx) else (self.approx_create(approx), True)
+
+    def approx_records(self, records, n, approx, text, n_symbols=None, offsets=None, pos_base=0, count=None, out=None, dist=None, out_capacity=None,
+                       out_count=None):
+        """acm_gpu_approx_records_device(): the occurrences with at most k mismatches of the targets of `approx`
+        (an Approx from approx_create(), or an ApproxSet compiled for this call) that records[:n] seed (an int64
+        [capacity, 2] device tensor in canonical order) in `text` (a device tensor of the caller's symbols), into
+        `out` and `dist` (None: new tensors of out_capacity entries, by default n times the set's max_postings,
+        which cannot overflow), queued on the current stream.  `count` (a device int64 tensor) gives the number of
+        records on the device: n is the room of `records` then.  `offsets` is a device int64 tensor of n_texts + 1
+        entries.  Returns (out, dist, out_count): out_count (a device tensor) holds the number of matches; above
+        out_capacity it is the capacity needed.  Nothing is synchronised."""
+        import torch
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
+        assert text.is_cuda and text.is_contiguous()
+        n = int(n)
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        A, own = self._approx_handle(approx)
+        try:
+            if out_capacity is None:
+                out_capacity = out.shape[0] if out is not None else n * A.info()["max_postings"]
+            out_capacity = int(out_capacity)
+            if out is None:
+                out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=records.device)
+            if dist is None:
+                dist = torch.empty(max(out_capacity, 1), dtype=torch.int32, device=records.device)
+            assert out.is_cuda and out.is_contiguous() and out.shape[0] >= out_capacity and dist.is_cuda and dist.numel() >= out_capacity
+            if out_count is None:
+                out_count = torch.zeros(1, dtype=torch.int64, device=records.device)
+            n_texts = offsets.numel() - 1 if offsets is not None else 0
+            tb = lib().acm_gpu_approx_tmp_bytes(self.h, A.h, n, out_capacity, n_texts)
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
+            _check(lib().acm_gpu_approx_records_device(self.h, A.h, records.data_ptr(), n, count.data_ptr() if count is not None else None,
+                                                       text.data_ptr(), int(n_symbols), int(pos_base), offsets.data_ptr() if offsets is not None else None,
+                                                       n_texts, out.data_ptr() if out_capacity else None, dist.data_ptr(), out_capacity,
+                                                       out_count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_approx_records_device")
+            if own:
+                torch.cuda.current_stream().synchronize()          # the set goes away with this call
+            return out, dist, out_count
+        finally:
+            if own:
+                A.close()
+
+    def scan_approx(self, text, approx, offsets=None, n_symbols=None, pos_base=0, capacity=None, out=None, dist=None, out_capacity=None, tmp=None):
+        """acm_gpu_scan_approx_device(): the ordered scan of a device tensor into `capacity` records of the call's
+        own and the targets of `approx` verified around them, queued on the current stream.  Returns (out, dist,
+        count, found, tmp) with count and found device tensors: out[:count] and dist[:count] are the matches when
+        count <= out_capacity; found is the scan's count -- above `capacity` there is no match (count 0) and found
+        is a capacity that suffices."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        capacity = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+        A, own = self._approx_handle(approx)
+        try:
+            if out_capacity is None:
+                out_capacity = out.shape[0] if out is not None else capacity * A.info()["max_postings"]
+            out_capacity = int(out_capacity)
+            if out is None:
+                out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=text.device)
+            if dist is None:
+                dist = torch.empty(max(out_capacity, 1), dtype=torch.int32, device=text.device)
+            res = torch.zeros(2, dtype=torch.int64, device=text.device)
+            n_texts = offsets.numel() - 1 if offsets is not None else 0
+            tb = lib().acm_gpu_scan_approx_tmp_bytes(self.h, A.h, capacity, out_capacity, n_symbols, n_texts)
+            if tmp is None or tmp.numel() < tb:
+                tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+            _check(lib().acm_gpu_scan_approx_device(self.h, A.h, text.data_ptr(), n_symbols, int(pos_base),
+                                                    offsets.data_ptr() if offsets is not None else None, n_texts, capacity,
+                                                    out.data_ptr() if out_capacity else None, dist.data_ptr(), out_capacity, res.data_ptr(),
+                                                    res.data_ptr() + 8, tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_scan_approx_device")
+            if own:
+                torch.cuda.current_stream().synchronize()          # the set goes away with this call
+            return out, dist, res[0:1], res[1:2], tmp
+        finally:
+            if own:
+                A.close()
+
+    def scan_approx_host(self, text, approxset, offsets=None, pos_base=0, out_capacity=None):
+        """acm_gpu_scan_approx_host(): numpy in, (matches, dist) out, through the C ABI only (no torch); an overflow
+        is repeated once with the size the call reports."""
+        t = np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        cap = int(out_capacity) if out_capacity is not None else 1024
+        for attempt in (0, 1):
+            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
+            dist = np.zeros(max(cap, 1), dtype=np.uint32)
+            n = C.c_uint64(0)
+            rc = lib().acm_gpu_scan_approx_host(self.h, t.ctypes.data if t.size else None, n_sym, int(pos_base),
+                                                off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *approxset.args(),
+                                                out.ctypes.data if cap else None, dist.ctypes.data, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_gpu_scan_approx_host")
+            return out[:n.value], dist[:n.value]
 
     @property
     def select_form(self):

@@ -6223,6 +6223,372 @@ acm_gpu_scan_patterns_host (ACMPlan *plan, const void *text, uint64_t n_symbols,
   return download_records (rc, d_res, d_out, out, out_capacity, n_found);
 }
 
+/* ------------------------------------------------------------------ keywords with up to k mismatches (include/acm_gpu.h, dev_approx.h)
+ * A target set compiled into an index inverted by term keyword, and the passes that verify a record set in
+ * canonical order under it: the check of offsets[], the count pass, the prefix over the records' counts, the
+ * fill pass, the two sorts of the order and the gather. */
+struct ACMApprox {
+  int device = 0;
+  uint64_t n_targets = 0, n_terms = 0, seed_keywords = 0, longest = 0, max_k = 0, max_postings = 0;
+  uint32_t n_keywords = 0, sym_bytes = 0;
+  void *blob = nullptr; /* one allocation: the arrays below */
+  uint32_t *d_post_ptr = nullptr;
+  uint4 *d_post = nullptr, *d_target = nullptr;
+  uint64_t *d_spell_off = nullptr;
+  ApproxTerm *d_terms = nullptr;
+  void *d_spell = nullptr;
+};
+
+namespace {
+/* bits that hold every value in [0, most] */
+uint32_t
+bits_of (uint64_t most) {
+  uint32_t bits = 1;
+  while (bits < 64 && (most >> bits))
+    bits++;
+  return bits;
+}
+
+size_t
+approx_sort_bytes (uint64_t n) {
+  size_t bytes = 0;
+  (void)hipcub::DeviceRadixSort::SortPairs (nullptr, bytes, static_cast<const uint64_t *> (nullptr), static_cast<uint64_t *> (nullptr),
+                                            static_cast<const uint32_t *> (nullptr), static_cast<uint32_t *> (nullptr), (int)n, 0, 64, nullptr);
+  return bytes;
+}
+
+/* what approx_carve derives beside K's pointers: the counts and their sums as the sum takes them, the order's two
+ * key and index buffers */
+struct ApproxRoom {
+  long long *count = nullptr, *first = nullptr;
+  CubRoom cub;
+  uint64_t *key_a = nullptr, *key_b = nullptr;
+  uint32_t *idx_a = nullptr, *idx_b = nullptr;
+  void *sort = nullptr;
+  size_t sort_bytes = 0;
+};
+ApproxRoom
+approx_carve (Carve &c, uint64_t capacity, uint64_t out_capacity, ApproxK &K) {
+  ApproxRoom R;
+  /* ACM_GPU_APPROX_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
+  K.tile = tunable ("ACM_GPU_APPROX_TILE", APPROX_TILE_DEFAULT, APPROX_TILE_MIN, APPROX_TILE_MAX, Tune::MultWave);
+  K.n_tiles = (capacity + K.tile - 1) / K.tile;
+  K.ctl = c.take<ApproxCtl> (1);
+  R.count = c.take<long long> ((size_t)capacity + 1);
+  R.first = c.take<long long> ((size_t)capacity + 1);
+  R.cub = cub_room (c, 0, capacity + 1);
+  K.count = reinterpret_cast<unsigned long long *> (R.count);
+  K.first = reinterpret_cast<const unsigned long long *> (R.first);
+  if (out_capacity) {
+    K.fill = c.take<ACMRecord> ((size_t)out_capacity);
+    K.fill_dist = c.take<uint32_t> ((size_t)out_capacity);
+    R.key_a = c.take<uint64_t> ((size_t)out_capacity);
+    R.key_b = c.take<uint64_t> ((size_t)out_capacity);
+    R.idx_a = c.take<uint32_t> ((size_t)out_capacity);
+    R.idx_b = c.take<uint32_t> ((size_t)out_capacity);
+    R.sort_bytes = approx_sort_bytes (out_capacity);
+    R.sort = c.take (R.sort_bytes + 16);
+  }
+  return R;
+}
+
+/* the fused call's scratch: the ordered scan's records, then the room the scan and the passes share (the scan
+ * has ended when the passes begin) */
+struct ScanApproxRoom {
+  ACMRecord *found = nullptr;
+  unsigned char *work = nullptr;
+  size_t work_bytes = 0;
+};
+ScanApproxRoom
+scan_approx_carve (Carve &c, const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity, uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts) {
+  ScanApproxRoom R;
+  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_approx_tmp_bytes (plan, approx, capacity, out_capacity, n_texts));
+  R.found = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
+  R.work = c.take (R.work_bytes);
+  return R;
+}
+
+template <typename T>
+int
+approx_passes (ACMPlan *plan, ApproxK &K, const ApproxRoom &L, uint64_t n, uint64_t n_texts, hipStream_t st) {
+  /* 1. */
+  if (K.offsets) /* one size, whatever the number of texts */
+    HIP_TRY (launch (approx_check_kernel, capped_grid (plan, (n_texts + APPROX_THREADS - 1) / APPROX_THREADS), dim3 (APPROX_THREADS), 0, st, K));
+  /* 2. */
+  HIP_TRY (launch (approx_count_kernel<T>, capped_grid (plan, K.n_tiles), dim3 (APPROX_THREADS), 0, st, K));
+  /* 3. */
+  HIP_TRY (exclusive_sum (L.cub, L.count, L.first, n + 1, st));
+  /* 4. */
+  HIP_TRY (launch (approx_fill_kernel<T>, capped_grid (plan, K.n_tiles), dim3 (APPROX_THREADS), 0, st, K));
+  return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_approx_create (ACMPlan *plan, const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
+                       const uint64_t *tgt_ptr, uint64_t n_targets, ACMApprox **out) {
+  if (!plan || !out || (n_targets && !spell_data))
+    return ACM_GPU_E_ARG;
+  const uint64_t nk = plan->covered_keywords;
+  if (acm_approx_check (spell_off, k, terms, tgt_ptr, n_targets, nk))
+    return ACM_GPU_E_ARG;
+  if (plan->class_sym_bytes) /* verification is bitwise on the caller's text */
+    return ACM_GPU_E_INELIGIBLE;
+  const uint64_t n_terms = tgt_ptr[n_targets], n_spell = spell_off[n_targets];
+  const uint32_t sb = plan->text_sym_bytes;
+  /* the index: every term under its keyword; a keyword's postings by target id, then term index */
+  struct Post {
+    uint32_t keyword_id, target, j, offset, length;
+  };
+  std::vector<Post> post (n_terms);
+  std::vector<uint32_t> post_ptr (nk + 1, 0);
+  std::vector<uint4> target (n_targets ? n_targets : 1);
+  std::vector<uint64_t> first_symbol (n_targets ? n_targets : 1);
+  std::vector<ApproxTerm> term_dev (n_terms ? n_terms : 1);
+  uint64_t longest = 0, max_k = 0;
+  for (uint64_t w = 0; w < n_targets; w++) {
+    const uint64_t L = spell_off[w + 1] - spell_off[w];
+    target[w] = make_uint4 ((uint32_t)L, k[w], (uint32_t)tgt_ptr[w], 0);
+    first_symbol[w] = spell_off[w];
+    longest = std::max (longest, L);
+    max_k = std::max<uint64_t> (max_k, k[w]);
+    for (uint64_t i = tgt_ptr[w]; i < tgt_ptr[w + 1]; i++) {
+      post[i] = Post{ terms[i].keyword_id, (uint32_t)w, (uint32_t)(i - tgt_ptr[w]), terms[i].offset, terms[i].length };
+      term_dev[i] = ApproxTerm{ terms[i].offset, terms[i].length, terms[i].keyword_id };
+    }
+  }
+  std::sort (post.begin (), post.end (), [] (const Post &a, const Post &b) {
+    return a.keyword_id != b.keyword_id ? a.keyword_id < b.keyword_id : a.target != b.target ? a.target < b.target : a.j < b.j;
+  });
+  std::vector<uint4> post_dev (n_terms ? n_terms : 1);
+  for (uint64_t q = 0; q < n_terms; q++) {
+    post_dev[q] = make_uint4 (post[q].target, post[q].j, post[q].offset, post[q].length);
+    post_ptr[post[q].keyword_id + 1]++;
+  }
+  uint64_t seed_keywords = 0, max_postings = 0;
+  for (uint64_t kw = 0; kw < nk; kw++) {
+    seed_keywords += post_ptr[kw + 1] != 0;
+    max_postings = std::max<uint64_t> (max_postings, post_ptr[kw + 1]);
+    post_ptr[kw + 1] += post_ptr[kw];
+  }
+  HIP_TRY (hipSetDevice (plan->device));
+  ACMApprox *A = new (std::nothrow) ACMApprox ();
+  if (!A)
+    return ACM_GPU_E_NOMEM;
+  A->device = plan->device;
+  A->n_targets = n_targets;
+  A->n_terms = n_terms;
+  A->seed_keywords = seed_keywords;
+  A->longest = longest;
+  A->max_k = max_k;
+  A->max_postings = max_postings;
+  A->n_keywords = (uint32_t)nk;
+  A->sym_bytes = sb;
+  size_t cur = 0;
+  const size_t spell_bytes = (size_t)n_spell * sb;
+  const size_t o_post_ptr = blob_reserve (cur, post_ptr.size () * 4), o_post = blob_reserve (cur, post_dev.size () * sizeof (uint4)),
+               o_target = blob_reserve (cur, target.size () * sizeof (uint4)), o_first = blob_reserve (cur, first_symbol.size () * 8),
+               o_terms = blob_reserve (cur, term_dev.size () * sizeof (ApproxTerm)), o_spell = blob_reserve (cur, spell_bytes + 16);
+  bool ok = hipMalloc (&A->blob, cur) == hipSuccess;
+  unsigned char *b = static_cast<unsigned char *> (A->blob);
+  ok = ok && hipMemcpy (b + o_post_ptr, post_ptr.data (), post_ptr.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_post, post_dev.data (), post_dev.size () * sizeof (uint4), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_target, target.data (), target.size () * sizeof (uint4), hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_first, first_symbol.data (), first_symbol.size () * 8, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_terms, term_dev.data (), term_dev.size () * sizeof (ApproxTerm), hipMemcpyHostToDevice) == hipSuccess &&
+       (!spell_bytes || hipMemcpy (b + o_spell, spell_data, spell_bytes, hipMemcpyHostToDevice) == hipSuccess) && hipDeviceSynchronize () == hipSuccess;
+  if (!ok) {
+    acm_gpu_approx_destroy (A);
+    return ACM_GPU_E_NOMEM;
+  }
+  A->d_post_ptr = reinterpret_cast<uint32_t *> (b + o_post_ptr);
+  A->d_post = reinterpret_cast<uint4 *> (b + o_post);
+  A->d_target = reinterpret_cast<uint4 *> (b + o_target);
+  A->d_spell_off = reinterpret_cast<uint64_t *> (b + o_first);
+  A->d_terms = reinterpret_cast<ApproxTerm *> (b + o_terms);
+  A->d_spell = b + o_spell;
+  *out = A;
+  return ACM_GPU_OK;
+}
+
+extern "C" void
+acm_gpu_approx_destroy (ACMApprox *approx) {
+  if (!approx)
+    return;
+  (void)hipSetDevice (approx->device);
+  if (approx->blob)
+    (void)hipFree (approx->blob);
+  delete approx;
+}
+
+extern "C" int
+acm_gpu_approx_info (const ACMApprox *approx, ACMApproxInfo *info) {
+  if (!approx || !info)
+    return ACM_GPU_E_ARG;
+  *info = ACMApproxInfo{ approx->n_targets, approx->n_terms, approx->seed_keywords, approx->longest, approx->max_k, approx->max_postings };
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_approx_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t n_or_capacity, uint64_t out_capacity, uint64_t n_texts) {
+  (void)n_texts; /* (nothing here is sized by the number of texts: the text of a match is a bisection of offsets[]) */
+  if (!plan || !approx || approx->device != plan->device || approx->sym_bytes != plan->text_sym_bytes || plan->class_sym_bytes ||
+      n_or_capacity >= (1ull << 31) || out_capacity >= (1ull << 31))
+    return 0;
+  Carve c;
+  ApproxK K{};
+  approx_carve (c, n_or_capacity, out_capacity, K);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, const void *d_text,
+                               uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint32_t *d_dist,
+                               uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !approx || approx->device != plan->device || approx->sym_bytes != plan->text_sym_bytes || plan->class_sym_bytes || !d_count ||
+      n >= (1ull << 31) || out_capacity >= (1ull << 31) || (out_capacity && !d_out) || (n && (!d_records || !d_tmp)) || (n_symbols && !d_text) ||
+      !symbols_ok (d_text, n_symbols, approx->sym_bytes) || (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+    return ACM_GPU_E_ARG;
+  if (n && out_capacity) { /* (the output is written while the input is still read) */
+    const uintptr_t a = reinterpret_cast<uintptr_t> (d_records), b = reinterpret_cast<uintptr_t> (d_out);
+    if (a < b + out_capacity * sizeof (ACMRecord) && b < a + n * sizeof (ACMRecord))
+      return ACM_GPU_E_ARG;
+  }
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n == 0) /* (no record: no match, whatever *d_n says) */
+    return no_record (plan, nullptr, d_count, st);
+  Carve carve (d_tmp);
+  ApproxK K{};
+  const ApproxRoom L = approx_carve (carve, n, out_capacity, K);
+  if (tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  K.post_ptr = approx->d_post_ptr;
+  K.post = approx->d_post;
+  K.target = approx->d_target;
+  K.spell_off = approx->d_spell_off;
+  K.terms = approx->d_terms;
+  K.spell = approx->d_spell;
+  K.n_keywords = approx->n_keywords;
+  K.longest = (uint32_t)approx->longest;
+  K.tgt_bits = bits_of (approx->n_targets ? approx->n_targets - 1 : 0);
+  K.in = d_records;
+  K.capacity = n;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.text = d_text;
+  K.n_symbols = n_symbols;
+  K.pos_base = pos_base;
+  K.offsets = n_texts ? d_offsets : nullptr; /* (no text: no symbol, every record breaks the contract) */
+  K.n_texts = n_texts;
+  K.out = d_out;
+  K.dist = d_dist;
+  K.out_capacity = out_capacity;
+  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
+  K.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (ApproxCtl), st));
+  int rc = ACM_GPU_E_INTERNAL;
+  switch (approx->sym_bytes) {
+  case 1: rc = approx_passes<uint8_t> (plan, K, L, n, n_texts, st); break;
+  case 2: rc = approx_passes<uint16_t> (plan, K, L, n, n_texts, st); break;
+  case 4: rc = approx_passes<uint32_t> (plan, K, L, n, n_texts, st); break;
+  case 8: rc = approx_passes<uint64_t> (plan, K, L, n, n_texts, st); break;
+  }
+  if (rc || !out_capacity)
+    return rc;
+  /* 5. the order (the kernels return at once when the total does not fit) */
+  const dim3 grid = capped_grid (plan, (out_capacity + APPROX_THREADS - 1) / APPROX_THREADS);
+  size_t sort_bytes = L.sort_bytes;
+  K.key = L.key_a;
+  K.idx = L.idx_a;
+  HIP_TRY (launch (approx_key1_kernel, grid, dim3 (APPROX_THREADS), 0, st, K));
+  HIP_TRY (hipcub::DeviceRadixSort::SortPairs (L.sort, sort_bytes, static_cast<const uint64_t *> (L.key_a), L.key_b, static_cast<const uint32_t *> (L.idx_a),
+                                               L.idx_b, (int)out_capacity, 0, (int)(K.tgt_bits + bits_of (approx->longest)), st));
+  K.idx_from = L.idx_b;
+  HIP_TRY (launch (approx_key2_kernel, grid, dim3 (APPROX_THREADS), 0, st, K));
+  sort_bytes = L.sort_bytes;
+  HIP_TRY (hipcub::DeviceRadixSort::SortPairs (L.sort, sort_bytes, static_cast<const uint64_t *> (L.key_a), L.key_b, static_cast<const uint32_t *> (L.idx_b),
+                                               L.idx_a, (int)out_capacity, 0, (int)bits_of (n_symbols), st));
+  K.idx_from = L.idx_a;
+  HIP_TRY (launch (approx_gather_kernel, grid, dim3 (APPROX_THREADS), 0, st, K));
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_scan_approx_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity, uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!plan || !approx || approx->device != plan->device || approx->sym_bytes != plan->text_sym_bytes || plan->class_sym_bytes ||
+      capacity >= (1ull << 31) || out_capacity >= (1ull << 31))
+    return 0;
+  Carve c;
+  scan_approx_carve (c, plan, approx, capacity, out_capacity, n_symbols, n_texts);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_scan_approx_device (ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
+                            uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count,
+                            uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !approx || approx->device != plan->device || approx->sym_bytes != plan->text_sym_bytes || plan->class_sym_bytes || !d_count || !d_found ||
+      capacity >= (1ull << 31) || out_capacity >= (1ull << 31) || (n_symbols && !d_text) || (out_capacity && !d_out) || (capacity && !d_tmp))
+    return ACM_GPU_E_ARG;
+  Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
+  const ScanApproxRoom L = scan_approx_carve (carve, plan, approx, capacity, out_capacity, n_symbols, n_texts);
+  if (capacity && tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  if (capacity == 0) { /* no room: *d_found says what the records need, and nothing matches */
+    if (const int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_found, stream))
+      return rc;
+    return no_record (plan, nullptr, d_count, static_cast<hipStream_t> (stream));
+  }
+  if (const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, L.found, capacity, d_found, L.work, L.work_bytes, stream))
+    return rc;
+  return acm_gpu_approx_records_device (plan, approx, L.found, capacity, d_found, d_text, n_symbols, pos_base, d_offsets, n_texts, d_out, d_dist,
+                                        out_capacity, d_count, L.work, L.work_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_approx_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                          const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
+                          uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  if (!plan || !n_found || out_capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
+      !optional_offsets_ok (offsets, n_texts, n_symbols) || (offsets && n_texts == 0 && n_symbols))
+    return ACM_GPU_E_ARG;
+  ACMApprox *made = nullptr;
+  if (const int rc = acm_gpu_approx_create (plan, spell_data, spell_off, k, terms, tgt_ptr, n_targets, &made))
+    return rc;
+  std::unique_ptr<ACMApprox, void (*) (ACMApprox *)> approx (made, acm_gpu_approx_destroy);
+  HIP_TRY (hipSetDevice (plan->device));
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the matches, the scan's records */
+  ACMRecord *d_out = nullptr;
+  uint32_t *d_dist = nullptr;
+  uint64_t capacity = 0;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (temps.get (&d_res, 16));
+  if (const int rc = count_first (plan, d_text, n_symbols, d_res, &capacity)) /* the record room: the exact number of matches */
+    return rc;
+  const size_t tmp_bytes = acm_gpu_scan_approx_tmp_bytes (plan, approx.get (), capacity, out_capacity, n_symbols, n_texts);
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  HOST_TRY (temps.get (&d_out, out_capacity * 16));
+  HOST_TRY (temps.get (&d_dist, out_capacity * 4));
+  if (offsets)
+    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  int rc = settle (plan,
+                   acm_gpu_scan_approx_device (plan, approx.get (), d_text, n_symbols, pos_base, d_off, n_texts, capacity, d_out, d_dist, out_capacity,
+                                               d_res, d_res + 1, d_tmp, tmp_bytes, nullptr),
+                   true);
+  uint64_t found = 0;
+  if (!rc) {
+    HOST_TRY (hipMemcpy (&found, d_res + 1, 8, hipMemcpyDeviceToHost));
+    if (found > capacity) /* (the room is what the count pass found: never expected) */
+      rc = ACM_GPU_E_INTERNAL;
+  }
+  rc = download_records (rc, d_res, d_out, out, out_capacity, n_found);
+  if (!rc && dist && *n_found)
+    HOST_TRY (hipMemcpy (dist, d_dist, *n_found * 4, hipMemcpyDeviceToHost));
+  return rc;
+}
+
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
 extern "C" int
 acm_gpu_wire_bits (const ACMPlan *plan, uint64_t span, uint32_t *pos_bits, uint32_t *len_bits, uint32_t *kw_bits) {
@@ -6879,7 +7245,7 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally and acm_lookup only a scan that
  * succeeded, acm_select, acm_scan_words, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
- * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules and acm_scan_patterns also one whose output had no room. */
+ * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_scan_patterns and acm_scan_approx also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -6905,7 +7271,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The fifteen calls below run on the same route, the same cached plan, under the same lock. */
+/* The sixteen calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -7100,6 +7466,40 @@ acm_scan_patterns (ACMachine *machine, const void *text, uint64_t n_symbols, con
     [&] (ACMPlan *plan) {
       return acm_gpu_scan_patterns_host (plan, text, n_symbols, 0, offsets, n_texts, terms, pat_ptr, n_patterns, out, out_capacity, n_found);
     });
+}
+
+/* keywords with up to k mismatches (include/acm_gpu.h).  Verification is bitwise on the device, so a machine with
+ * another comparator runs the caller loop and the host join under its comparator, whatever its symbol size. */
+extern "C" int
+acm_scan_approx (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const void *spell_data,
+                 const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out,
+                 uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  if (!machine || !n_found || (n_symbols && !text) || (out_capacity && !out) || !optional_offsets_ok (offsets, n_texts, n_symbols))
+    return ACM_GPU_E_ARG;
+  ScanRoute R;
+  if (const int rc = scan_route (machine, &R))
+    return rc;
+  uint32_t sb = R.said;
+  if (R.path == ACM_SCAN_PATH_GPU && acm_internal_symbol_bytes (machine, &sb))
+    return ACM_GPU_E_INTERNAL;
+  if (acm_internal_approx_machine_check (machine, sb, spell_data, spell_off, k, terms, tgt_ptr, n_targets))
+    return ACM_GPU_E_ARG;
+  const auto host_loop = [&] (uint32_t said) {
+    return acm_internal_cpu_scan_approx (machine, text, n_symbols, said, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist,
+                                         out_capacity, n_found);
+  };
+  if (R.path != ACM_SCAN_PATH_GPU) { /* (no class plan is made: the route is the loop itself) */
+    acm_internal_plan_lock (machine);
+    const int rc = host_loop (R.said);
+    if (!rc || rc == ACM_GPU_E_OVERFLOW)
+      acm_internal_set_scan_path (machine, ACM_SCAN_PATH_CPU_LOOP);
+    acm_internal_plan_unlock (machine);
+    return rc;
+  }
+  return routed_scan (machine, RecordPath::OnSuccessOrOverflow, host_loop, [&] (ACMPlan *plan) {
+    return acm_gpu_scan_approx_host (plan, text, n_symbols, 0, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist, out_capacity,
+                                     n_found);
+  });
 }
 
 /* acm_scan continued from a cursor (include/acm_gpu.h): the reference's own `const ACState *`, in

@@ -1857,3 +1857,253 @@ acm_internal_cpu_scan_patterns (ACMachine *m, const void *text, uint64_t n_symbo
   free (records);
   return rc;
 }
+
+/* ---- keywords with up to k mismatches (include/acm_gpu.h): the argument checks, the canonical cut, the plain sequential APPROX of a
+ * record set in canonical order, and acm_scan_approx's host path. */
+int
+acm_approx_check (const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets,
+                  uint64_t n_keywords) {
+  if (!spell_off || !tgt_ptr || spell_off[0] != 0 || tgt_ptr[0] != 0 || n_targets >= (1ull << 31) || (n_targets && (!k || !terms)))
+    return ACM_GPU_E_ARG;
+  for (uint64_t w = 0; w < n_targets; w++) {
+    if (tgt_ptr[w] >= tgt_ptr[w + 1]) /* decreasing, or a target without terms */
+      return ACM_GPU_E_ARG;
+    if (spell_off[w] >= spell_off[w + 1] || spell_off[w + 1] - spell_off[w] >= (1ull << 31) || k[w] > 255) /* decreasing, or L_w == 0 */
+      return ACM_GPU_E_ARG;
+  }
+  if (tgt_ptr[n_targets] >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  for (uint64_t w = 0; w < n_targets; w++) {
+    const uint64_t L = spell_off[w + 1] - spell_off[w];
+    for (uint64_t i = tgt_ptr[w]; i < tgt_ptr[w + 1]; i++)
+      if (terms[i].length == 0 || (uint64_t)terms[i].offset + terms[i].length > L || terms[i].keyword_id >= n_keywords)
+        return ACM_GPU_E_ARG;
+  }
+  return ACM_GPU_OK;
+}
+
+int
+acm_approx_split (uint64_t L, uint32_t k, uint32_t j, uint64_t *begin, uint64_t *end) {
+  if (!begin || !end || L >= (1ull << 31) || L < (uint64_t)k + 1 || j > k)
+    return ACM_GPU_E_ARG;
+  *begin = (uint64_t)j * L / ((uint64_t)k + 1);
+  *end = ((uint64_t)j + 1) * L / ((uint64_t)k + 1);
+  return ACM_GPU_OK;
+}
+
+/* a term under its keyword: (target id, the term's index inside its target) */
+struct apx_post {
+  uint32_t keyword_id, target, j;
+};
+
+/* by keyword, then target id, then term index: the order of a keyword's postings */
+static int
+apx_post_cmp (const void *a, const void *b) {
+  const struct apx_post *x = a, *y = b;
+  if (x->keyword_id != y->keyword_id)
+    return x->keyword_id < y->keyword_id ? -1 : 1;
+  if (x->target != y->target)
+    return x->target < y->target ? -1 : 1;
+  return x->j < y->j ? -1 : x->j > y->j;
+}
+
+/* a match and its distance, so that the two are ordered together */
+struct apx_hit {
+  ACMRecord r;
+  uint32_t d;
+};
+
+/* the output order: end_pos ascending, then length descending, then target id ascending */
+static int
+apx_hit_cmp (const void *a, const void *b) {
+  const struct apx_hit *x = a, *y = b;
+  if (x->r.end_pos != y->r.end_pos)
+    return x->r.end_pos < y->r.end_pos ? -1 : 1;
+  if (x->r.length != y->r.length)
+    return x->r.length > y->r.length ? -1 : 1;
+  return x->r.keyword_id < y->r.keyword_id ? -1 : x->r.keyword_id > y->r.keyword_id;
+}
+
+/* the tables of a call, as every entry point takes them */
+struct apx_set {
+  const unsigned char *spell;
+  const uint64_t *spell_off;
+  const uint32_t *k;
+  const ACMPatternTerm *terms;
+  const uint64_t *tgt_ptr;
+  uint32_t sym_bytes;
+  CMP_TYPE cmp; /* NULL: symbols compare bitwise */
+  void *cmp_arg;
+};
+
+/* whether target q->target matches with its term q->j seeded by record r (the term's keyword is the record's); *d = the mismatches */
+static int
+apx_matches (const ACMRecord *records, uint64_t n, const ACMRecord *r, const struct apx_post *q, const unsigned char *text, uint64_t n_symbols,
+             uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts, const struct apx_set *A, uint64_t *S_out, uint32_t *d) {
+  const uint64_t e = r->end_pos - pos_base, first = A->tgt_ptr[q->target], L = A->spell_off[q->target + 1] - A->spell_off[q->target];
+  const ACMPatternTerm *term = &A->terms[first + q->j];
+  if (r->length != term->length || (uint64_t)term->offset + term->length - 1 > e)
+    return 0;
+  const uint64_t S = e + 1 - term->length - term->offset;
+  uint64_t t_hi = n_symbols; /* where the text of S ends */
+  if (offsets) {
+    if (!n_texts)
+      return 0;
+    uint64_t lo = 0, hi = n_texts - 1; /* the largest text with offsets[text] <= S */
+    while (lo < hi) {
+      const uint64_t mid = lo + (hi - lo + 1) / 2;
+      if (offsets[mid] <= S)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    t_hi = offsets[lo + 1];
+  }
+  if (S + L > t_hi)
+    return 0;
+  for (uint32_t i = 0; i < q->j; i++) { /* a term of lower index that seeds the same match emits it */
+    const ACMPatternTerm *t = &A->terms[first + i];
+    if (pat_has_record (records, n, pos_base + S + t->offset + t->length - 1, t->length, t->keyword_id))
+      return 0;
+  }
+  const unsigned char *a = text + S * A->sym_bytes, *b = A->spell + A->spell_off[q->target] * A->sym_bytes;
+  uint32_t miss = 0;
+  for (uint64_t i = 0; i < L; i++) {
+    const int same = A->cmp ? A->cmp (a + i * A->sym_bytes, b + i * A->sym_bytes, A->cmp_arg) == 0
+                            : memcmp (a + i * A->sym_bytes, b + i * A->sym_bytes, A->sym_bytes) == 0;
+    if (!same && ++miss > A->k[q->target])
+      return 0;
+  }
+  *S_out = S;
+  *d = miss;
+  return 1;
+}
+
+static int
+approx_core (const ACMRecord *records, uint64_t n, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+             const struct apx_set *A, uint64_t n_targets, uint64_t n_keywords, ACMRecord *out, uint32_t *dist, uint64_t out_capacity,
+             uint64_t *n_found) {
+  if (!n_found || (n && !records) || (out_capacity && !out) || A->sym_bytes == 0 || (n_symbols && !text) || (n_targets && !A->spell) ||
+      acm_approx_check (A->spell_off, A->k, A->terms, A->tgt_ptr, n_targets, n_keywords))
+    return ACM_GPU_E_ARG;
+  if (offsets) {
+    if (offsets[0] != 0 || offsets[n_texts] != n_symbols)
+      return ACM_GPU_E_ARG;
+    for (uint64_t t = 0; t < n_texts; t++)
+      if (offsets[t] > offsets[t + 1])
+        return ACM_GPU_E_ARG;
+  }
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+      return ACM_GPU_E_ARG;
+  }
+  const uint64_t n_terms = A->tgt_ptr[n_targets];
+  struct apx_post *post = malloc ((n_terms ? n_terms : 1) * sizeof *post);
+  if (!post)
+    return ACM_GPU_E_NOMEM;
+  for (uint64_t w = 0; w < n_targets; w++)
+    for (uint64_t i = A->tgt_ptr[w]; i < A->tgt_ptr[w + 1]; i++)
+      post[i] = (struct apx_post){ A->terms[i].keyword_id, (uint32_t)w, (uint32_t)(i - A->tgt_ptr[w]) };
+  qsort (post, n_terms, sizeof *post, apx_post_cmp);
+  /* two passes over the records as seeds: the count, then -- when the matches fit -- the matches themselves */
+  struct apx_hit *hit = NULL;
+  uint64_t found = 0;
+  for (int fill = 0; fill < 2; fill++) {
+    found = 0;
+    for (uint64_t j = 0; j < n; j++) {
+      const ACMRecord *r = &records[j];
+      uint64_t lo = 0, hi = n_terms; /* the keyword's first posting */
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (post[mid].keyword_id < r->keyword_id)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      for (uint64_t q = lo; q < n_terms && post[q].keyword_id == r->keyword_id; q++) {
+        uint64_t S = 0;
+        uint32_t d = 0;
+        if (!apx_matches (records, n, r, &post[q], text, n_symbols, pos_base, offsets, n_texts, A, &S, &d))
+          continue;
+        if (fill) {
+          const uint64_t L = A->spell_off[post[q].target + 1] - A->spell_off[post[q].target];
+          hit[found] = (struct apx_hit){ { pos_base + S + L - 1, (uint32_t)L, post[q].target }, d };
+        }
+        found++;
+      }
+    }
+    if (!out || found > out_capacity || found == 0) /* the call only counts, or the matches have no room */
+      break;
+    if (!fill && !(hit = malloc (found * sizeof *hit))) {
+      free (post);
+      return ACM_GPU_E_NOMEM;
+    }
+  }
+  free (post);
+  *n_found = found;
+  if (out && found <= out_capacity && found) {
+    qsort (hit, found, sizeof *hit, apx_hit_cmp); /* the seeds lie anywhere inside their targets */
+    for (uint64_t i = 0; i < found; i++) {
+      out[i] = hit[i].r;
+      if (dist)
+        dist[i] = hit[i].d;
+    }
+  }
+  free (hit);
+  return out && found > out_capacity ? ACM_GPU_E_OVERFLOW : ACM_GPU_OK;
+}
+
+int
+acm_approx_records (const ACMRecord *records, uint64_t n, const void *text, uint32_t sym_bytes, uint64_t n_symbols, uint64_t pos_base,
+                    const uint64_t *offsets, uint64_t n_texts, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                    const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, uint64_t n_keywords, ACMRecord *out, uint32_t *dist,
+                    uint64_t out_capacity, uint64_t *n_found) {
+  const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, NULL, NULL };
+  return approx_core (records, n, text, n_symbols, pos_base, offsets, n_texts, &A, n_targets, n_keywords, out, dist, out_capacity, n_found);
+}
+
+/* the checks acm_scan_approx makes on every path: acm_approx_check against the machine's keywords, and every term's keyword is
+ * spelled as the term's piece of its target (by the machine's comparator over symbols of sym_bytes bytes) */
+int
+acm_internal_approx_machine_check (ACMachine *m, uint32_t sym_bytes, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                                   const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets) {
+  if (!m || !sym_bytes || (n_targets && !spell_data))
+    return ACM_GPU_E_ARG;
+  acm_internal_lock (m);
+  int rc = acm_approx_check (spell_off, k, terms, tgt_ptr, n_targets, m->nb_keywords);
+  for (uint64_t w = 0; !rc && w < n_targets; w++)
+    for (uint64_t i = tgt_ptr[w]; !rc && i < tgt_ptr[w + 1]; i++) {
+      const struct _ac_state *s = m->keywords[terms[i].keyword_id];
+      if (s->depth != terms[i].length) {
+        rc = ACM_GPU_E_ARG;
+        break;
+      }
+      const unsigned char *piece = (const unsigned char *)spell_data + (spell_off[w] + terms[i].offset) * sym_bytes;
+      for (uint32_t at = terms[i].length; !rc && at-- > 0; s = s->parent)
+        if (m->cmp (s->letter, piece + (size_t)at * sym_bytes, m->cmp_arg) != 0)
+          rc = ACM_GPU_E_ARG;
+    }
+  acm_internal_unlock (m);
+  return rc;
+}
+
+/* acm_scan_approx on the host: the caller loop (from the root at every offset of a batch), then the sequential pass over what it
+ * found, with symbols compared by the machine's comparator -- what ACM_SCAN_PATH_CPU_LOOP runs.  The public call has checked the
+ * arguments. */
+int
+acm_internal_cpu_scan_approx (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                              const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
+                              const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  if (!m || !n_found)
+    return ACM_GPU_E_ARG;
+  ACMRecord *records;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, n_symbols, offsets, n_texts, sym_bytes, NULL, &records, &found);
+  if (!rc) {
+    const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, m->cmp, m->cmp_arg };
+    rc = approx_core (records, found, text, n_symbols, 0, offsets, n_texts, &A, n_targets, acm_nb_keywords (m), out, dist, out_capacity, n_found);
+  }
+  free (records);
+  return rc;
+}

@@ -109,6 +109,17 @@ int acm_internal_patterns_machine_check (ACMachine *m, const ACMPatternTerm *ter
 int acm_internal_cpu_scan_patterns (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
                                     const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, ACMRecord *out, uint64_t out_capacity,
                                     uint64_t *n_found);
+/* acm_scan_approx's checks on every path: acm_approx_check against the machine's keywords, and every term's keyword is spelled as the
+ * term's piece of its target, by the machine's comparator over symbols of sym_bytes bytes */
+int acm_internal_approx_machine_check (ACMachine *m, uint32_t sym_bytes, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                                       const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets);
+/* acm_scan_approx's host path: the caller loop (from the root at every offset when offsets is given), then the sequential APPROX over
+ * its records with symbols compared by the machine's comparator (arguments as acm_scan_approx', the symbol size behind n_symbols; the
+ * public call has checked them) */
+int acm_internal_cpu_scan_approx (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                                  const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
+                                  const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity,
+                                  uint64_t *n_found);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

@@ -172,5 +172,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_words.h"
 #include "dev_anchored.h"
 #include "dev_patterns.h"
+#include "dev_approx.h"
 
 } // namespace

@@ -86,13 +86,13 @@ patterns_check_kernel (PatternsK K) {
 }
 
 /* whether the record (end_pos, length, keyword_id) is among in[0 .. n): a bisection for the first record
- * at or behind the key (end_pos ascending, length descending) */
+ * at or behind the key (end_pos ascending, length descending).  Shared with dev_approx.h. */
 __device__ __forceinline__ bool
-patterns_has_record (const PatternsK &K, uint64_t n, uint64_t end_pos, uint32_t length, uint32_t keyword_id) {
+records_have (const ACMRecord *in, uint64_t n, uint64_t end_pos, uint32_t length, uint32_t keyword_id) {
   uint64_t lo = 0, hi = n;
   while (lo < hi) {
     const uint64_t mid = lo + (hi - lo) / 2;
-    const uint4 r = *reinterpret_cast<const uint4 *> (&K.in[mid]);
+    const uint4 r = *reinterpret_cast<const uint4 *> (&in[mid]);
     const uint64_t pos = ((uint64_t)r.y << 32) | r.x;
     if (pos < end_pos || (pos == end_pos && r.z > length))
       lo = mid + 1;
@@ -101,7 +101,7 @@ patterns_has_record (const PatternsK &K, uint64_t n, uint64_t end_pos, uint32_t 
   }
   if (lo >= n)
     return false;
-  const uint4 r = *reinterpret_cast<const uint4 *> (&K.in[lo]);
+  const uint4 r = *reinterpret_cast<const uint4 *> (&in[lo]);
   return ((((uint64_t)r.y << 32) | r.x) == end_pos) && r.z == length && r.w == keyword_id;
 }
 
@@ -118,7 +118,7 @@ patterns_match (const PatternsK &K, uint64_t n, uint64_t e, uint32_t length, con
   }
   for (uint32_t j = K.other_ptr[q.x]; j < K.other_ptr[q.x + 1]; j++) {
     const PatternOther o = K.other[j]; /* (back <= L - length of the term: the term begins at or behind S) */
-    if (!patterns_has_record (K, n, K.pos_base + e - o.back, o.length, o.keyword_id))
+    if (!records_have (K.in, n, K.pos_base + e - o.back, o.length, o.keyword_id))
       return false;
   }
   return true;

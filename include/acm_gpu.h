@@ -1557,6 +1557,145 @@ int acm_scan_patterns (ACMachine *machine, const void *text, uint64_t n_symbols,
                        const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns,
                        ACMRecord *out, uint64_t out_capacity, uint64_t *n_found);
 
+/* ------------------------------------------------------------------ keywords with up to k mismatches
+ * Every consumer above acts on exact occurrences.  APPROX gives approximate ones: every place where a
+ * target occurs with at most k substituted symbols (Hamming distance) -- typo-tolerant term lists, primers
+ * and motifs with mismatches, signatures with a few variable bytes at unknown positions.  The textbook
+ * construction: a target of L symbols with budget k is cut into k + 1 disjoint pieces; wherever the target
+ * occurs with at most k mismatches, at least one piece occurs exactly.  So the pieces are the dictionary,
+ * every exact piece record is a SEED, and the seed's target is verified against the text around it.  The
+ * scan kernels stay untouched; APPROX is a function of a record set in canonical order, of the text and of
+ * offsets[], and has the record passes' calling shape.
+ *
+ * DEFINITION.  Targets: there are n_targets targets.  Target w has a spelling, the symbols
+ * [spell_off[w], spell_off[w + 1]) of spell_data in the caller's symbol size (spell_off has n_targets + 1
+ * uint64_t entries); its length is L_w.  It has a budget k[w] (uint32_t) and the terms
+ * [tgt_ptr[w], tgt_ptr[w + 1]) of terms[] (ACMPatternTerm reused: keyword_id, offset, length).  A term says:
+ * keyword keyword_id, `length` symbols long, is the piece of the spelling that begins at `offset`.
+ * ACM_GPU_E_ARG: a target without terms, L_w == 0 or L_w >= 2^31, k[w] > 255, a term with length == 0 or
+ * offset + length > L_w, keyword_id >= n_keywords, a spell_off or tgt_ptr that decreases or does not begin
+ * with 0, n_targets >= 2^31, 2^31 terms or more.
+ * APPROX (R, text, offsets, T).  R is a record set in canonical order with positions pos_base + index;
+ * text[0 .. n_symbols) is the buffer in the caller's symbols; offsets follows the batch contract (NULL:
+ * one text).  Target w MATCHES at buffer index S iff
+ *   1. some text t has offsets[t] <= S and S + L_w <= offsets[t + 1], and
+ *   2. (seed) some term (kid, o, l) of w has the record (pos_base + S + o + l - 1, l, kid) in R, and
+ *   3. d = the number of i < L_w with text[S + i] != spell_w[i] is <= k[w]; symbols compare bitwise over
+ *      sym_bytes bytes.
+ * Each (w, S) that matches gives exactly one ACMRecord (end_pos = pos_base + S + L_w - 1, length = L_w,
+ * keyword_id = w) and dist[r] = d, however many terms seed it.  The total order is end_pos ascending, then
+ * length descending, then target id ascending.
+ * COMPLETENESS.  When the terms of w are k[w] + 1 pairwise disjoint pieces, each keyword is spelled exactly
+ * as its piece and R is the full record set of the buffer, condition 2 follows from 1 and 3: APPROX is
+ * then every occurrence of every target within its budget, inside one text.  acm_approx_split (L, k, j)
+ * gives the canonical cut: piece j is [floor (j * L / (k + 1)), floor ((j + 1) * L / (k + 1))); it needs
+ * L >= k + 1 and j <= k (ACM_GPU_E_ARG otherwise).  With fewer terms, or terms that are not such pieces,
+ * the seed condition removes matches; that is defined, not an error.
+ *
+ * acm_approx_check: the argument checks above, no device; every other entry point runs it.
+ * acm_approx_records: the plain sequential APPROX on the host, no device.  ACM_GPU_E_OVERFLOW with
+ * *n_found = the entries needed, and nothing written, when out_capacity is too small; out == NULL with
+ * capacity 0 only counts; `dist` may be NULL.  ACM_GPU_E_ARG, with nothing written, for offsets that break
+ * the batch contract and for a record outside [pos_base, pos_base + n_symbols) (its end or its start) or
+ * of length 0.
+ *
+ * acm_gpu_approx_create compiles a set once on the host and uploads it to the plan's device (ACMApprox,
+ * opaque like ACMPatterns): an index inverted by term keyword with postings (target id, term index j,
+ * offset, term length) sorted by (target id, j), per target its terms, the spellings and the budgets.
+ * n_keywords is acm_gpu_tally_keywords (plan) at creation; the set stays valid after acm_gpu_plan_update.
+ * A plan over comparator classes is refused with ACM_GPU_E_INELIGIBLE, because verification is bitwise on
+ * the caller's text; plans that intern 8-byte symbols are taken, since interning is exact.
+ * acm_gpu_approx_info: targets, terms, the keywords that seed a target, the longest L_w, the largest k and
+ * the most postings of one keyword; n x max_postings bounds the output of n records.
+ *
+ * acm_gpu_approx_records_device (dev_approx.h): APPROX of d_records on the device, the shape of
+ * acm_gpu_patterns_records_device (d_n, n_or_capacity, overlap rule, 2^31 limits) plus d_text -- the
+ * caller's symbols at any address that is a multiple of the symbol size -- and d_dist (uint32_t per
+ * output entry, may be NULL).  It only queues launches, with no host round trip.  The check of d_offsets
+ * in a launch of its own; a count pass with one group of 16 consecutive lanes per input record over tiles
+ * of 1,024 records (ACM_GPU_APPROX_TILE=<records>: a multiple of 64 from 64 to 1 Mi, read at every call):
+ * the group reads the postings of the record's keyword and per posting tests the term's length, S >= 0,
+ * the text of S by a bisection of offsets[] and that S + L_w ends inside it, verifies cooperatively --
+ * lane j compares symbols j, j + 16, ... with naturally aligned loads of one symbol, the mismatches grow
+ * by the popcount of the group's 16 bits of the wave's ballot, and the group stops once they exceed k[w]
+ * -- and drops a candidate within its budget when a term of lower index of the same target also has its
+ * record in R (that term's group emits the match); a 64-bit exclusive sum; a fill pass in which the groups with a
+ * nonzero count verify again and store each match with one 16-byte store plus its distance; an order
+ * pass, run only when the total fits out_capacity -- two stable radix sorts (hipCUB) of an index
+ * permutation, by (length descending, target id) and then by end_pos - pos_base, and one gather of
+ * records and distances.  No atomics decide a slot and launch geometry never depends on what the records
+ * hold.  d_tmp must hold acm_gpu_approx_tmp_bytes (plan, approx, n_or_capacity, out_capacity, n_texts)
+ * bytes (0 for a call that would be refused).
+ *   *d_count <= out_capacity: the count is exact, d_out and d_dist are complete and in order.
+ *   *d_count > out_capacity: it is the capacity needed, and nothing is written to d_out or d_dist.
+ *   *d_n > n_or_capacity (a scan that overflowed): *d_count = 0 and nothing is written.
+ *   d_offsets that break the contract: *d_count = 0, no other output, acm_gpu_plan_status reports
+ *     ACM_GPU_E_INTERNAL.
+ * A record that breaks the contract (a position outside [pos_base, pos_base + n_symbols), a start below
+ * pos_base, a length of 0) is skipped and acm_gpu_plan_status reports ACM_GPU_E_INTERNAL (select's
+ * rule).  Input that is not in canonical order gives an unspecified result; nothing is read or written
+ * out of bounds.
+ *
+ * acm_gpu_scan_approx_device: acm_gpu_scan_ordered_device (emit_from 0) into `capacity` records inside
+ * d_tmp, then the passes above; d_tmp must hold acm_gpu_scan_approx_tmp_bytes (plan, approx, capacity,
+ * out_capacity, n_symbols, n_texts) bytes.  *d_found receives the scan's count: when it exceeds
+ * `capacity`, *d_count = 0 and *d_found is a capacity that suffices.
+ * acm_gpu_scan_approx_host: the same from host memory, blocking; it creates and destroys the set itself
+ * and sizes the record room from acm_gpu_count_device.  ACM_GPU_E_OVERFLOW means only "out_capacity is
+ * too small, *n_found suffices".  Offsets that break the batch contract are ACM_GPU_E_ARG.
+ * acm_scan_approx: the call on the machine itself.  This call knows the machine: a term whose length or
+ * spelling is not that of its keyword's piece is ACM_GPU_E_ARG.  Machines with ACM_CMP_DEFAULT run the
+ * GPU path; machines with another comparator run the caller loop on the host and the sequential join
+ * with symbols compared by the machine's comparator, report ACM_SCAN_PATH_CPU_LOOP and need
+ * acm_set_symbol_bytes (ACM_GPU_E_INELIGIBLE without it).  A missing device stays an error, never a
+ * fallback.
+ *
+ * Out of scope: insertions and deletions (edit distance); class plans on the device; flows, streams and
+ * several GPUs; feeding the output to SELECT or REPLACE (their contract bounds lengths by the plan's
+ * lmax, and L_w is not bound by it). */
+typedef struct ACMApprox ACMApprox;
+typedef struct {
+  uint64_t targets, terms, seed_keywords, longest, max_k, max_postings;
+} ACMApproxInfo;
+int acm_approx_check (const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
+                      uint64_t n_targets, uint64_t n_keywords);
+int acm_approx_split (uint64_t L, uint32_t k, uint32_t j, uint64_t *begin, uint64_t *end);
+int acm_approx_records (const ACMRecord *records, uint64_t n, const void *text, uint32_t sym_bytes, uint64_t n_symbols,
+                        uint64_t pos_base, const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                        const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                        const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, uint64_t n_keywords,
+                        ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity, uint64_t *n_found);
+int acm_gpu_approx_create (ACMPlan *plan, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                           const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, ACMApprox **out);
+void acm_gpu_approx_destroy (ACMApprox *approx);
+int acm_gpu_approx_info (const ACMApprox *approx, ACMApproxInfo *info);
+size_t acm_gpu_approx_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t n_or_capacity,
+                                 uint64_t out_capacity, uint64_t n_texts);
+int acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records,
+                                   uint64_t n_or_capacity, const uint64_t *d_n /* may be NULL */,
+                                   const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                   const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                   ACMRecord *d_out, uint32_t *d_dist /* may be NULL */, uint64_t out_capacity,
+                                   uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_scan_approx_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity,
+                                      uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_approx_device (ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols,
+                                uint64_t pos_base, const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist /* may be NULL */,
+                                uint64_t out_capacity, uint64_t *d_count, uint64_t *d_found,
+                                void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_approx_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base,
+                              const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                              const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                              const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets,
+                              ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity,
+                              uint64_t *n_found);   /* blocking */
+int acm_scan_approx (ACMachine *machine, const void *text, uint64_t n_symbols,
+                     const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                     const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                     const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets,
+                     ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity, uint64_t *n_found);
+
 /* ------------------------------------------------------------------ several GPUs of one node, one process
  * The reference's model for parallel work is one shared read-only machine and one cursor per worker
  * (/root/reference/README.md:364, aho_corasick.h:70: the caller owns the `const ACState *`).  The
