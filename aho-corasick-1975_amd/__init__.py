@@ -17,7 +17,7 @@ from .binding import (  # noqa: F401
     words_records, ASCII_WORD, ACM_WORDS_LEFT, ACM_WORDS_RIGHT, ACM_WORDS_BOTH,
     anchored_records, ACM_ANCHORED_PREFIXES, ACM_ANCHORED_LONGEST, ACM_ANCHORED_WHOLE, ACM_LOOKUP_NONE,
     PatternSet, Patterns, patterns_records,
-    ApproxSet, Approx, approx_records,
+    ApproxSet, Approx, approx_records, edit_records,
 )
 from . import synth  # noqa: F401
 from . import sharded  # noqa: F401

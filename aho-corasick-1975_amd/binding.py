@@ -128,6 +128,8 @@ EXPORTS = [
     "acm_approx_check", "acm_approx_split", "acm_approx_records", "acm_gpu_approx_create", "acm_gpu_approx_destroy", "acm_gpu_approx_info",
     "acm_gpu_approx_tmp_bytes", "acm_gpu_approx_records_device", "acm_gpu_scan_approx_tmp_bytes", "acm_gpu_scan_approx_device",
     "acm_gpu_scan_approx_host", "acm_scan_approx",
+    "acm_edit_check", "acm_edit_records", "acm_gpu_edit_tmp_bytes", "acm_gpu_edit_records_device", "acm_gpu_scan_edit_tmp_bytes",
+    "acm_gpu_scan_edit_device", "acm_gpu_scan_edit_host", "acm_scan_edit",
 ]
 
 
@@ -426,6 +428,10 @@ def lib():
     L.acm_gpu_scan_approx_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.acm_scan_approx.restype = i32
     L.acm_scan_approx.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
+    for call in ("acm_%s_check", "acm_%s_records", "acm_gpu_%s_tmp_bytes", "acm_gpu_%s_records_device", "acm_gpu_scan_%s_tmp_bytes",
+                 "acm_gpu_scan_%s_device", "acm_gpu_scan_%s_host", "acm_scan_%s"):   # the edit calls have the signatures of their APPROX counterparts
+        getattr(L, call % "edit").restype = getattr(L, call % "approx").restype
+        getattr(L, call % "edit").argtypes = getattr(L, call % "approx").argtypes
     L.acm_split_offsets.restype = i32
     L.acm_split_offsets.argtypes = [vp, u64, u32, vp, u32, u32, vp, u64, C.POINTER(u64)]
     L.acm_gpu_split_tmp_bytes.restype = sz
@@ -1091,6 +1097,11 @@ class ApproxSet:
         """acm_approx_check(): raises ACMError (ACM_GPU_E_ARG) for a set the calls would refuse"""
         _check(lib().acm_approx_check(*self.args()[1:], int(n_keywords)), "acm_approx_check")
 
+    def check_edit(self, n_keywords=None):
+        """acm_edit_check(): raises ACMError (ACM_GPU_E_ARG) for a set the edit calls would refuse -- acm_approx_check's
+        errors, a budget above 15, a budget that is not below its target's length"""
+        _check(lib().acm_edit_check(*self.args()[1:], int(n_keywords) if n_keywords is not None else self.n_keywords), "acm_edit_check")
+
 
 def approx_records(records, approxset, text, offsets=None, pos_base=0, n_keywords=None, out_capacity=None):
     """acm_approx_records(): the occurrences with at most k mismatches of the targets of `approxset` (an
@@ -1100,7 +1111,22 @@ def approx_records(records, approxset, text, offsets=None, pos_base=0, n_keyword
     by end_pos ascending, length descending, target id ascending, and the mismatches of each.  `offsets`
     (n_texts + 1 entries) cuts the buffer into texts; a match lies inside one text.  out_capacity None: counted
     first, then sized by the count; given and too small: ACMError (ACM_GPU_E_OVERFLOW)."""
-    aset = approxset
+    return _set_records("acm_approx_records", records, approxset, text, offsets, pos_base, n_keywords, out_capacity)
+
+
+def edit_records(records, approxset, text, offsets=None, pos_base=0, n_keywords=None, out_capacity=None):
+    """acm_edit_records(): the ends at which the targets of `approxset` (an ApproxSet; check_edit() says whether the
+    edit calls take it) occur within edit distance k among those the `records` seed, by the sequential pass on the
+    host; arguments and order as approx_records().  Returns (matches, dist): one record (end_pos of the last
+    symbol, the length of the shortest best match ending there, the target's id) per (target, end), and the edit
+    distance of each."""
+    return _set_records("acm_edit_records", records, approxset, text, offsets, pos_base, n_keywords, out_capacity)
+
+
+def _set_records(name, records, aset, text, offsets, pos_base, n_keywords, out_capacity):
+    """what approx_records() and edit_records() share: the C call `name` on numpy arrays, counted first when no
+    capacity is given"""
+    fn = getattr(lib(), name)
     a = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
     t = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text)
     n_symbols = t.size * t.itemsize // aset.sym_size
@@ -1109,16 +1135,15 @@ def approx_records(records, approxset, text, offsets=None, pos_base=0, n_keyword
     n = C.c_uint64(0)
 
     def call(out, dist, cap):
-        return lib().acm_approx_records(a.ctypes.data if a.size else None, a.size, t.ctypes.data if t.size else None, aset.sym_size, n_symbols,
-                                        int(pos_base), off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0,
-                                        *aset.args(), nk, out.ctypes.data if out is not None else None,
-                                        dist.ctypes.data if dist is not None else None, cap, C.byref(n))
+        return fn(a.ctypes.data if a.size else None, a.size, t.ctypes.data if t.size else None, aset.sym_size, n_symbols,
+                  int(pos_base), off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0,
+                  *aset.args(), nk, out.ctypes.data if out is not None else None, dist.ctypes.data if dist is not None else None, cap, C.byref(n))
     if out_capacity is None:                                       # (no output: the call only counts)
-        _check(call(None, None, 0), "acm_approx_records")
+        _check(call(None, None, 0), name)
         out_capacity = int(n.value)
     out = np.zeros(max(int(out_capacity), 1), dtype=RECORD_DTYPE)
     dist = np.zeros(max(int(out_capacity), 1), dtype=np.uint32)
-    _check(call(out, dist, int(out_capacity)), "acm_approx_records")
+    _check(call(out, dist, int(out_capacity)), name)
     return out[:n.value], dist[:n.value]
 
 
@@ -1665,6 +1690,15 @@ class Machine:
         """acm_scan_approx(): (matches, dist) of the targets of `approxset` (see approx_records) in `text`, or in
         every text of the buffer when `offsets` (n_texts + 1 entries) cuts it; by default an overflow is repeated
         once with the size the call reports."""
+        return self._scan_set("acm_scan_approx", text, approxset, offsets, out_capacity)
+
+    def scan_edit(self, text, approxset, offsets=None, out_capacity=None):
+        """acm_scan_edit(): (matches, dist) of the targets of `approxset` within edit distance k (see edit_records) in
+        `text`, or in every text of the buffer when `offsets` cuts it; arguments as scan_approx()."""
+        return self._scan_set("acm_scan_edit", text, approxset, offsets, out_capacity)
+
+    def _scan_set(self, name, text, approxset, offsets, out_capacity):
+        """what scan_approx() and scan_edit() share: the machine-level C call `name`"""
         t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
         off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
         cap = int(out_capacity) if out_capacity is not None else 1024
@@ -1672,13 +1706,13 @@ class Machine:
             out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
             dist = np.zeros(max(cap, 1), dtype=np.uint32)
             n = C.c_uint64(0)
-            rc = self.L.acm_scan_approx(self.handle, t.ctypes.data if t.size else None, t.size * t.itemsize // self.sym_size,
-                                        off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *approxset.args(),
-                                        out.ctypes.data if cap else None, dist.ctypes.data, cap, C.byref(n))
+            rc = getattr(self.L, name)(self.handle, t.ctypes.data if t.size else None, t.size * t.itemsize // self.sym_size,
+                                       off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *approxset.args(),
+                                       out.ctypes.data if cap else None, dist.ctypes.data, cap, C.byref(n))
             if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
                 cap = int(n.value)
                 continue
-            _check(rc, "acm_scan_approx")
+            _check(rc, name)
             return out[:n.value], dist[:n.value]
 
     def replace(self, text, replacements=None, fill=None, out_capacity=None):
@@ -1845,7 +1879,7 @@ class Approx:
 
     def info(self):
         """acm_gpu_approx_info(): targets, terms, seed_keywords, longest, max_k and max_postings as a dict; n
-        records give at most n * max_postings matches."""
+        records give at most n * max_postings matches (the edit calls: times 2 * max_k + 1)."""
         i = ApproxInfo()
         _check(lib().acm_gpu_approx_info(self.h, C.byref(i)), "acm_gpu_approx_info")
         return {n: int(getattr(i, n)) for n, _ in ApproxInfo._fields_}
@@ -2533,16 +2567,34 @@ class Plan:
         records on the device: n is the room of `records` then.  `offsets` is a device int64 tensor of n_texts + 1
         entries.  Returns (out, dist, out_count): out_count (a device tensor) holds the number of matches; above
         out_capacity it is the capacity needed.  Nothing is synchronised."""
+        return self._set_records("approx", records, n, approx, text, n_symbols, offsets, pos_base, count, out, dist, out_capacity, out_count)
+
+    def edit_records(self, records, n, approx, text, n_symbols=None, offsets=None, pos_base=0, count=None, out=None, dist=None, out_capacity=None,
+                     out_count=None):
+        """acm_gpu_edit_records_device(): the ends at which the targets of `approx` occur within edit distance k among
+        those records[:n] seed; arguments and return as approx_records().  out_capacity defaults to n times the
+        set's max_postings times 2 max_k + 1, which cannot overflow.  A set with a budget above 15, or not below
+        its target's length, is refused (ACM_GPU_E_ARG)."""
+        return self._set_records("edit", records, n, approx, text, n_symbols, offsets, pos_base, count, out, dist, out_capacity, out_count)
+
+    @staticmethod
+    def _most_per_record(metric, info):
+        """the matches one record can seed, from acm_gpu_approx_info()'s figures"""
+        return info["max_postings"] * (2 * info["max_k"] + 1 if metric == "edit" else 1)
+
+    def _set_records(self, metric, records, n, approx, text, n_symbols, offsets, pos_base, count, out, dist, out_capacity, out_count):
+        """what approx_records() and edit_records() share: acm_gpu_<metric>_tmp_bytes and acm_gpu_<metric>_records_device"""
         import torch
         assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
         assert text.is_cuda and text.is_contiguous()
         n = int(n)
+        call = "acm_gpu_%s_records_device" % metric
         if n_symbols is None:
             n_symbols = text.numel() * text.element_size() // self.sym_size
         A, own = self._approx_handle(approx)
         try:
             if out_capacity is None:
-                out_capacity = out.shape[0] if out is not None else n * A.info()["max_postings"]
+                out_capacity = out.shape[0] if out is not None else n * self._most_per_record(metric, A.info())
             out_capacity = int(out_capacity)
             if out is None:
                 out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=records.device)
@@ -2552,12 +2604,12 @@ class Plan:
             if out_count is None:
                 out_count = torch.zeros(1, dtype=torch.int64, device=records.device)
             n_texts = offsets.numel() - 1 if offsets is not None else 0
-            tb = lib().acm_gpu_approx_tmp_bytes(self.h, A.h, n, out_capacity, n_texts)
+            tb = getattr(lib(), "acm_gpu_%s_tmp_bytes" % metric)(self.h, A.h, n, out_capacity, n_texts)
             tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
-            _check(lib().acm_gpu_approx_records_device(self.h, A.h, records.data_ptr(), n, count.data_ptr() if count is not None else None,
-                                                       text.data_ptr(), int(n_symbols), int(pos_base), offsets.data_ptr() if offsets is not None else None,
-                                                       n_texts, out.data_ptr() if out_capacity else None, dist.data_ptr(), out_capacity,
-                                                       out_count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_approx_records_device")
+            _check(getattr(lib(), call)(self.h, A.h, records.data_ptr(), n, count.data_ptr() if count is not None else None,
+                                        text.data_ptr(), int(n_symbols), int(pos_base), offsets.data_ptr() if offsets is not None else None,
+                                        n_texts, out.data_ptr() if out_capacity else None, dist.data_ptr(), out_capacity,
+                                        out_count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), call)
             if own:
                 torch.cuda.current_stream().synchronize()          # the set goes away with this call
             return out, dist, out_count
@@ -2571,15 +2623,25 @@ class Plan:
         count, found, tmp) with count and found device tensors: out[:count] and dist[:count] are the matches when
         count <= out_capacity; found is the scan's count -- above `capacity` there is no match (count 0) and found
         is a capacity that suffices."""
+        return self._scan_set("approx", text, approx, offsets, n_symbols, pos_base, capacity, out, dist, out_capacity, tmp)
+
+    def scan_edit(self, text, approx, offsets=None, n_symbols=None, pos_base=0, capacity=None, out=None, dist=None, out_capacity=None, tmp=None):
+        """acm_gpu_scan_edit_device(): the ordered scan of a device tensor and the targets of `approx` verified within
+        edit distance k around its records; arguments and return as scan_approx()."""
+        return self._scan_set("edit", text, approx, offsets, n_symbols, pos_base, capacity, out, dist, out_capacity, tmp)
+
+    def _scan_set(self, metric, text, approx, offsets, n_symbols, pos_base, capacity, out, dist, out_capacity, tmp):
+        """what scan_approx() and scan_edit() share: acm_gpu_scan_<metric>_tmp_bytes and acm_gpu_scan_<metric>_device"""
         import torch
         assert text.is_cuda and text.is_contiguous()
+        call = "acm_gpu_scan_%s_device" % metric
         if n_symbols is None:
             n_symbols = text.numel() * text.element_size() // self.sym_size
         capacity = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
         A, own = self._approx_handle(approx)
         try:
             if out_capacity is None:
-                out_capacity = out.shape[0] if out is not None else capacity * A.info()["max_postings"]
+                out_capacity = out.shape[0] if out is not None else capacity * self._most_per_record(metric, A.info())
             out_capacity = int(out_capacity)
             if out is None:
                 out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=text.device)
@@ -2587,13 +2649,13 @@ class Plan:
                 dist = torch.empty(max(out_capacity, 1), dtype=torch.int32, device=text.device)
             res = torch.zeros(2, dtype=torch.int64, device=text.device)
             n_texts = offsets.numel() - 1 if offsets is not None else 0
-            tb = lib().acm_gpu_scan_approx_tmp_bytes(self.h, A.h, capacity, out_capacity, n_symbols, n_texts)
+            tb = getattr(lib(), "acm_gpu_scan_%s_tmp_bytes" % metric)(self.h, A.h, capacity, out_capacity, n_symbols, n_texts)
             if tmp is None or tmp.numel() < tb:
                 tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-            _check(lib().acm_gpu_scan_approx_device(self.h, A.h, text.data_ptr(), n_symbols, int(pos_base),
-                                                    offsets.data_ptr() if offsets is not None else None, n_texts, capacity,
-                                                    out.data_ptr() if out_capacity else None, dist.data_ptr(), out_capacity, res.data_ptr(),
-                                                    res.data_ptr() + 8, tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_scan_approx_device")
+            _check(getattr(lib(), call)(self.h, A.h, text.data_ptr(), n_symbols, int(pos_base),
+                                        offsets.data_ptr() if offsets is not None else None, n_texts, capacity,
+                                        out.data_ptr() if out_capacity else None, dist.data_ptr(), out_capacity, res.data_ptr(),
+                                        res.data_ptr() + 8, tmp.data_ptr(), tmp.numel(), self._stream()), call)
             if own:
                 torch.cuda.current_stream().synchronize()          # the set goes away with this call
             return out, dist, res[0:1], res[1:2], tmp
@@ -2604,6 +2666,14 @@ class Plan:
     def scan_approx_host(self, text, approxset, offsets=None, pos_base=0, out_capacity=None):
         """acm_gpu_scan_approx_host(): numpy in, (matches, dist) out, through the C ABI only (no torch); an overflow
         is repeated once with the size the call reports."""
+        return self._scan_set_host("acm_gpu_scan_approx_host", text, approxset, offsets, pos_base, out_capacity)
+
+    def scan_edit_host(self, text, approxset, offsets=None, pos_base=0, out_capacity=None):
+        """acm_gpu_scan_edit_host(): numpy in, (matches, dist) within edit distance k out; arguments as scan_approx_host()."""
+        return self._scan_set_host("acm_gpu_scan_edit_host", text, approxset, offsets, pos_base, out_capacity)
+
+    def _scan_set_host(self, name, text, approxset, offsets, pos_base, out_capacity):
+        """what scan_approx_host() and scan_edit_host() share: the blocking C call `name`"""
         t = np.ascontiguousarray(text)
         n_sym = t.size * t.itemsize // self.sym_size
         off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
@@ -2612,13 +2682,13 @@ class Plan:
             out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
             dist = np.zeros(max(cap, 1), dtype=np.uint32)
             n = C.c_uint64(0)
-            rc = lib().acm_gpu_scan_approx_host(self.h, t.ctypes.data if t.size else None, n_sym, int(pos_base),
-                                                off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *approxset.args(),
-                                                out.ctypes.data if cap else None, dist.ctypes.data, cap, C.byref(n))
+            rc = getattr(lib(), name)(self.h, t.ctypes.data if t.size else None, n_sym, int(pos_base),
+                                      off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *approxset.args(),
+                                      out.ctypes.data if cap else None, dist.ctypes.data, cap, C.byref(n))
             if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
                 cap = int(n.value)
                 continue
-            _check(rc, "acm_gpu_scan_approx_host")
+            _check(rc, name)
             return out[:n.value], dist[:n.value]
 
     @property

@@ -6231,7 +6231,8 @@ struct ACMApprox {
   int device = 0;
   uint64_t n_targets = 0, n_terms = 0, seed_keywords = 0, longest = 0, max_k = 0, max_postings = 0;
   uint32_t n_keywords = 0, sym_bytes = 0;
-  void *blob = nullptr; /* one allocation: the arrays below */
+  bool edit_fit = false; /* every k[w] <= 15 and < L_w: the edit calls take the set (acm_edit_check's two conditions) */
+  void *blob = nullptr;  /* one allocation: the arrays below */
   uint32_t *d_post_ptr = nullptr;
   uint4 *d_post = nullptr, *d_target = nullptr;
   uint64_t *d_spell_off = nullptr;
@@ -6300,9 +6301,9 @@ struct ScanApproxRoom {
   size_t work_bytes = 0;
 };
 ScanApproxRoom
-scan_approx_carve (Carve &c, const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity, uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts) {
+scan_approx_carve (Carve &c, const ACMPlan *plan, size_t passes_bytes, uint64_t capacity, uint64_t n_symbols) {
   ScanApproxRoom R;
-  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_approx_tmp_bytes (plan, approx, capacity, out_capacity, n_texts));
+  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), passes_bytes);
   R.found = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
   R.work = c.take (R.work_bytes);
   return R;
@@ -6321,6 +6322,64 @@ approx_passes (ACMPlan *plan, ApproxK &K, const ApproxRoom &L, uint64_t n, uint6
   /* 4. */
   HIP_TRY (launch (approx_fill_kernel<T>, capped_grid (plan, K.n_tiles), dim3 (APPROX_THREADS), 0, st, K));
   return ACM_GPU_OK;
+}
+
+/* ---- keywords within edit distance k (include/acm_gpu.h, dev_edit.h).  The set is ACMApprox and the passes are the ones above; the
+ * count and fill kernels are dev_edit.h's, with the group width fixed per call from the set's max_k.  The metric is a property of the
+ * call, so the entry points of both metrics are one body each (set_records_device, scan_set_device, scan_set_host). */
+enum class Metric { Mismatches, Edits };
+
+/* whether the calls of a metric take this plan and set */
+bool
+set_usable (Metric metric, const ACMPlan *plan, const ACMApprox *approx) {
+  return plan && approx && approx->device == plan->device && approx->sym_bytes == plan->text_sym_bytes && !plan->class_sym_bytes &&
+         (metric == Metric::Mismatches || approx->edit_fit);
+}
+
+/* approx_carve; the edit passes have a tile of their own */
+ApproxRoom
+set_carve (Metric metric, Carve &c, uint64_t capacity, uint64_t out_capacity, ApproxK &K) {
+  const ApproxRoom R = approx_carve (c, capacity, out_capacity, K);
+  if (metric == Metric::Edits) {
+    /* ACM_GPU_EDIT_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
+    K.tile = tunable ("ACM_GPU_EDIT_TILE", EDIT_TILE_DEFAULT, EDIT_TILE_MIN, EDIT_TILE_MAX, Tune::MultWave);
+    K.n_tiles = (capacity + K.tile - 1) / K.tile;
+  }
+  return R;
+}
+
+size_t
+set_tmp_bytes (Metric metric, const ACMPlan *plan, const ACMApprox *approx, uint64_t n_or_capacity, uint64_t out_capacity) {
+  if (!set_usable (metric, plan, approx) || n_or_capacity >= (1ull << 31) || out_capacity >= (1ull << 31))
+    return 0;
+  Carve c;
+  ApproxK K{};
+  set_carve (metric, c, n_or_capacity, out_capacity, K);
+  return c.total ();
+}
+
+template <typename T, uint32_t G>
+int
+edit_passes (ACMPlan *plan, ApproxK &K, const ApproxRoom &L, uint64_t n, uint64_t n_texts, hipStream_t st) {
+  if (K.offsets)
+    HIP_TRY (launch (approx_check_kernel, capped_grid (plan, (n_texts + APPROX_THREADS - 1) / APPROX_THREADS), dim3 (APPROX_THREADS), 0, st, K));
+  HIP_TRY (launch (edit_count_kernel<T, G>, capped_grid (plan, K.n_tiles), dim3 (EDIT_THREADS), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, L.count, L.first, n + 1, st));
+  HIP_TRY (launch (edit_fill_kernel<T, G>, capped_grid (plan, K.n_tiles), dim3 (EDIT_THREADS), 0, st, K));
+  return ACM_GPU_OK;
+}
+
+/* the passes of a call: APPROX's, or EDIT's at the group width of the set (a band is at most 4 k + 1 diagonals wide) */
+template <typename T>
+int
+set_passes (Metric metric, uint64_t max_k, ACMPlan *plan, ApproxK &K, const ApproxRoom &L, uint64_t n, uint64_t n_texts, hipStream_t st) {
+  if (metric == Metric::Mismatches)
+    return approx_passes<T> (plan, K, L, n, n_texts, st);
+  if (max_k <= 3)
+    return edit_passes<T, 16> (plan, K, L, n, n_texts, st);
+  if (max_k <= 7)
+    return edit_passes<T, 32> (plan, K, L, n, n_texts, st);
+  return edit_passes<T, 64> (plan, K, L, n, n_texts, st);
 }
 } // namespace
 
@@ -6346,8 +6405,10 @@ acm_gpu_approx_create (ACMPlan *plan, const void *spell_data, const uint64_t *sp
   std::vector<uint64_t> first_symbol (n_targets ? n_targets : 1);
   std::vector<ApproxTerm> term_dev (n_terms ? n_terms : 1);
   uint64_t longest = 0, max_k = 0;
+  bool edit_fit = true;
   for (uint64_t w = 0; w < n_targets; w++) {
     const uint64_t L = spell_off[w + 1] - spell_off[w];
+    edit_fit = edit_fit && k[w] <= EDIT_MAX_K && k[w] < L;
     target[w] = make_uint4 ((uint32_t)L, k[w], (uint32_t)tgt_ptr[w], 0);
     first_symbol[w] = spell_off[w];
     longest = std::max (longest, L);
@@ -6381,6 +6442,7 @@ acm_gpu_approx_create (ACMPlan *plan, const void *spell_data, const uint64_t *sp
   A->seed_keywords = seed_keywords;
   A->longest = longest;
   A->max_k = max_k;
+  A->edit_fit = edit_fit;
   A->max_postings = max_postings;
   A->n_keywords = (uint32_t)nk;
   A->sym_bytes = sb;
@@ -6432,22 +6494,23 @@ acm_gpu_approx_info (const ACMApprox *approx, ACMApproxInfo *info) {
 extern "C" size_t
 acm_gpu_approx_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t n_or_capacity, uint64_t out_capacity, uint64_t n_texts) {
   (void)n_texts; /* (nothing here is sized by the number of texts: the text of a match is a bisection of offsets[]) */
-  if (!plan || !approx || approx->device != plan->device || approx->sym_bytes != plan->text_sym_bytes || plan->class_sym_bytes ||
-      n_or_capacity >= (1ull << 31) || out_capacity >= (1ull << 31))
-    return 0;
-  Carve c;
-  ApproxK K{};
-  approx_carve (c, n_or_capacity, out_capacity, K);
-  return c.total ();
+  return set_tmp_bytes (Metric::Mismatches, plan, approx, n_or_capacity, out_capacity);
 }
 
-extern "C" int
-acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, const void *d_text,
-                               uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint32_t *d_dist,
-                               uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!plan || !approx || approx->device != plan->device || approx->sym_bytes != plan->text_sym_bytes || plan->class_sym_bytes || !d_count ||
-      n >= (1ull << 31) || out_capacity >= (1ull << 31) || (out_capacity && !d_out) || (n && (!d_records || !d_tmp)) || (n_symbols && !d_text) ||
-      !symbols_ok (d_text, n_symbols, approx->sym_bytes) || (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+extern "C" size_t
+acm_gpu_edit_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t n_or_capacity, uint64_t out_capacity, uint64_t n_texts) {
+  (void)n_texts;
+  return set_tmp_bytes (Metric::Edits, plan, approx, n_or_capacity, out_capacity);
+}
+
+namespace {
+int
+set_records_device (Metric metric, ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, const void *d_text,
+                    uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint32_t *d_dist,
+                    uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!set_usable (metric, plan, approx) || !d_count || n >= (1ull << 31) || out_capacity >= (1ull << 31) || (out_capacity && !d_out) ||
+      (n && (!d_records || !d_tmp)) || (n_symbols && !d_text) || !symbols_ok (d_text, n_symbols, approx->sym_bytes) ||
+      (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
     return ACM_GPU_E_ARG;
   if (n && out_capacity) { /* (the output is written while the input is still read) */
     const uintptr_t a = reinterpret_cast<uintptr_t> (d_records), b = reinterpret_cast<uintptr_t> (d_out);
@@ -6459,10 +6522,11 @@ acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACM
     return no_record (plan, nullptr, d_count, st);
   Carve carve (d_tmp);
   ApproxK K{};
-  const ApproxRoom L = approx_carve (carve, n, out_capacity, K);
+  const ApproxRoom L = set_carve (metric, carve, n, out_capacity, K);
   if (tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
+  const uint64_t longest = approx->longest + (metric == Metric::Edits ? approx->max_k : 0); /* (a match within k edits may be longer than its target) */
   K.post_ptr = approx->d_post_ptr;
   K.post = approx->d_post;
   K.target = approx->d_target;
@@ -6470,7 +6534,7 @@ acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACM
   K.terms = approx->d_terms;
   K.spell = approx->d_spell;
   K.n_keywords = approx->n_keywords;
-  K.longest = (uint32_t)approx->longest;
+  K.longest = (uint32_t)longest;
   K.tgt_bits = bits_of (approx->n_targets ? approx->n_targets - 1 : 0);
   K.in = d_records;
   K.capacity = n;
@@ -6488,10 +6552,10 @@ acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACM
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (ApproxCtl), st));
   int rc = ACM_GPU_E_INTERNAL;
   switch (approx->sym_bytes) {
-  case 1: rc = approx_passes<uint8_t> (plan, K, L, n, n_texts, st); break;
-  case 2: rc = approx_passes<uint16_t> (plan, K, L, n, n_texts, st); break;
-  case 4: rc = approx_passes<uint32_t> (plan, K, L, n, n_texts, st); break;
-  case 8: rc = approx_passes<uint64_t> (plan, K, L, n, n_texts, st); break;
+  case 1: rc = set_passes<uint8_t> (metric, approx->max_k, plan, K, L, n, n_texts, st); break;
+  case 2: rc = set_passes<uint16_t> (metric, approx->max_k, plan, K, L, n, n_texts, st); break;
+  case 4: rc = set_passes<uint32_t> (metric, approx->max_k, plan, K, L, n, n_texts, st); break;
+  case 8: rc = set_passes<uint64_t> (metric, approx->max_k, plan, K, L, n, n_texts, st); break;
   }
   if (rc || !out_capacity)
     return rc;
@@ -6502,7 +6566,7 @@ acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACM
   K.idx = L.idx_a;
   HIP_TRY (launch (approx_key1_kernel, grid, dim3 (APPROX_THREADS), 0, st, K));
   HIP_TRY (hipcub::DeviceRadixSort::SortPairs (L.sort, sort_bytes, static_cast<const uint64_t *> (L.key_a), L.key_b, static_cast<const uint32_t *> (L.idx_a),
-                                               L.idx_b, (int)out_capacity, 0, (int)(K.tgt_bits + bits_of (approx->longest)), st));
+                                               L.idx_b, (int)out_capacity, 0, (int)(K.tgt_bits + bits_of (longest)), st));
   K.idx_from = L.idx_b;
   HIP_TRY (launch (approx_key2_kernel, grid, dim3 (APPROX_THREADS), 0, st, K));
   sort_bytes = L.sort_bytes;
@@ -6513,25 +6577,24 @@ acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACM
   return ACM_GPU_OK;
 }
 
-extern "C" size_t
-acm_gpu_scan_approx_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity, uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts) {
-  if (!plan || !approx || approx->device != plan->device || approx->sym_bytes != plan->text_sym_bytes || plan->class_sym_bytes ||
-      capacity >= (1ull << 31) || out_capacity >= (1ull << 31))
+size_t
+scan_set_tmp_bytes (Metric metric, const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity, uint64_t out_capacity, uint64_t n_symbols) {
+  if (!set_usable (metric, plan, approx) || capacity >= (1ull << 31) || out_capacity >= (1ull << 31))
     return 0;
   Carve c;
-  scan_approx_carve (c, plan, approx, capacity, out_capacity, n_symbols, n_texts);
+  scan_approx_carve (c, plan, set_tmp_bytes (metric, plan, approx, capacity, out_capacity), capacity, n_symbols);
   return c.total ();
 }
 
-extern "C" int
-acm_gpu_scan_approx_device (ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
-                            uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count,
-                            uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!plan || !approx || approx->device != plan->device || approx->sym_bytes != plan->text_sym_bytes || plan->class_sym_bytes || !d_count || !d_found ||
-      capacity >= (1ull << 31) || out_capacity >= (1ull << 31) || (n_symbols && !d_text) || (out_capacity && !d_out) || (capacity && !d_tmp))
+int
+scan_set_device (Metric metric, ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
+                 uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count, uint64_t *d_found,
+                 void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!set_usable (metric, plan, approx) || !d_count || !d_found || capacity >= (1ull << 31) || out_capacity >= (1ull << 31) || (n_symbols && !d_text) ||
+      (out_capacity && !d_out) || (capacity && !d_tmp))
     return ACM_GPU_E_ARG;
   Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
-  const ScanApproxRoom L = scan_approx_carve (carve, plan, approx, capacity, out_capacity, n_symbols, n_texts);
+  const ScanApproxRoom L = scan_approx_carve (carve, plan, set_tmp_bytes (metric, plan, approx, capacity, out_capacity), capacity, n_symbols);
   if (capacity && tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   if (capacity == 0) { /* no room: *d_found says what the records need, and nothing matches */
@@ -6541,16 +6604,18 @@ acm_gpu_scan_approx_device (ACMPlan *plan, const ACMApprox *approx, const void *
   }
   if (const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, L.found, capacity, d_found, L.work, L.work_bytes, stream))
     return rc;
-  return acm_gpu_approx_records_device (plan, approx, L.found, capacity, d_found, d_text, n_symbols, pos_base, d_offsets, n_texts, d_out, d_dist,
-                                        out_capacity, d_count, L.work, L.work_bytes, stream);
+  return set_records_device (metric, plan, approx, L.found, capacity, d_found, d_text, n_symbols, pos_base, d_offsets, n_texts, d_out, d_dist, out_capacity,
+                             d_count, L.work, L.work_bytes, stream);
 }
 
-extern "C" int
-acm_gpu_scan_approx_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
-                          const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
-                          uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+int
+scan_set_host (Metric metric, ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+               const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
+               uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
   if (!plan || !n_found || out_capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
       !optional_offsets_ok (offsets, n_texts, n_symbols) || (offsets && n_texts == 0 && n_symbols))
+    return ACM_GPU_E_ARG;
+  if (metric == Metric::Edits && acm_edit_check (spell_off, k, terms, tgt_ptr, n_targets, plan->covered_keywords)) /* (the set would be made, and refused) */
     return ACM_GPU_E_ARG;
   ACMApprox *made = nullptr;
   if (const int rc = acm_gpu_approx_create (plan, spell_data, spell_off, k, terms, tgt_ptr, n_targets, &made))
@@ -6567,15 +6632,15 @@ acm_gpu_scan_approx_host (ACMPlan *plan, const void *text, uint64_t n_symbols, u
   HOST_TRY (temps.get (&d_res, 16));
   if (const int rc = count_first (plan, d_text, n_symbols, d_res, &capacity)) /* the record room: the exact number of matches */
     return rc;
-  const size_t tmp_bytes = acm_gpu_scan_approx_tmp_bytes (plan, approx.get (), capacity, out_capacity, n_symbols, n_texts);
+  const size_t tmp_bytes = scan_set_tmp_bytes (metric, plan, approx.get (), capacity, out_capacity, n_symbols);
   HOST_TRY (temps.get (&d_tmp, tmp_bytes));
   HOST_TRY (temps.get (&d_out, out_capacity * 16));
   HOST_TRY (temps.get (&d_dist, out_capacity * 4));
   if (offsets)
     HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
   int rc = settle (plan,
-                   acm_gpu_scan_approx_device (plan, approx.get (), d_text, n_symbols, pos_base, d_off, n_texts, capacity, d_out, d_dist, out_capacity,
-                                               d_res, d_res + 1, d_tmp, tmp_bytes, nullptr),
+                   scan_set_device (metric, plan, approx.get (), d_text, n_symbols, pos_base, d_off, n_texts, capacity, d_out, d_dist, out_capacity, d_res,
+                                    d_res + 1, d_tmp, tmp_bytes, nullptr),
                    true);
   uint64_t found = 0;
   if (!rc) {
@@ -6587,6 +6652,68 @@ acm_gpu_scan_approx_host (ACMPlan *plan, const void *text, uint64_t n_symbols, u
   if (!rc && dist && *n_found)
     HOST_TRY (hipMemcpy (dist, d_dist, *n_found * 4, hipMemcpyDeviceToHost));
   return rc;
+}
+} // namespace
+
+/* the entry points of the two metrics (include/acm_gpu.h) */
+extern "C" int
+acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, const void *d_text,
+                               uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint32_t *d_dist,
+                               uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  return set_records_device (Metric::Mismatches, plan, approx, d_records, n, d_n, d_text, n_symbols, pos_base, d_offsets, n_texts, d_out, d_dist,
+                             out_capacity, d_count, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_edit_records_device (ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, const void *d_text,
+                             uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint32_t *d_dist,
+                             uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  return set_records_device (Metric::Edits, plan, approx, d_records, n, d_n, d_text, n_symbols, pos_base, d_offsets, n_texts, d_out, d_dist, out_capacity,
+                             d_count, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" size_t
+acm_gpu_scan_approx_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity, uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts) {
+  (void)n_texts;
+  return scan_set_tmp_bytes (Metric::Mismatches, plan, approx, capacity, out_capacity, n_symbols);
+}
+
+extern "C" size_t
+acm_gpu_scan_edit_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity, uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts) {
+  (void)n_texts;
+  return scan_set_tmp_bytes (Metric::Edits, plan, approx, capacity, out_capacity, n_symbols);
+}
+
+extern "C" int
+acm_gpu_scan_approx_device (ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
+                            uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count,
+                            uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
+  return scan_set_device (Metric::Mismatches, plan, approx, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, d_dist, out_capacity, d_count,
+                          d_found, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_edit_device (ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
+                          uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count,
+                          uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
+  return scan_set_device (Metric::Edits, plan, approx, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, d_dist, out_capacity, d_count,
+                          d_found, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_approx_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                          const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
+                          uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  return scan_set_host (Metric::Mismatches, plan, text, n_symbols, pos_base, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist,
+                        out_capacity, n_found);
+}
+
+extern "C" int
+acm_gpu_scan_edit_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                        const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
+                        uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  return scan_set_host (Metric::Edits, plan, text, n_symbols, pos_base, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist,
+                        out_capacity, n_found);
 }
 
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
@@ -7245,7 +7372,8 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally and acm_lookup only a scan that
  * succeeded, acm_select, acm_scan_words, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
- * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_scan_patterns and acm_scan_approx also one whose output had no room. */
+ * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_scan_patterns, acm_scan_approx and acm_scan_edit also one whose
+ * output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -7271,7 +7399,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The sixteen calls below run on the same route, the same cached plan, under the same lock. */
+/* The seventeen calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -7468,25 +7596,27 @@ acm_scan_patterns (ACMachine *machine, const void *text, uint64_t n_symbols, con
     });
 }
 
-/* keywords with up to k mismatches (include/acm_gpu.h).  Verification is bitwise on the device, so a machine with
- * another comparator runs the caller loop and the host join under its comparator, whatever its symbol size. */
-extern "C" int
-acm_scan_approx (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const void *spell_data,
-                 const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out,
-                 uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+/* keywords with up to k mismatches, and within edit distance k (include/acm_gpu.h).  Verification is bitwise on the device, so a
+ * machine with another comparator runs the caller loop and the host pass under its comparator, whatever its symbol size. */
+namespace {
+int
+scan_set (Metric metric, ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const void *spell_data,
+          const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out,
+          uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
   if (!machine || !n_found || (n_symbols && !text) || (out_capacity && !out) || !optional_offsets_ok (offsets, n_texts, n_symbols))
     return ACM_GPU_E_ARG;
+  const bool edits = metric == Metric::Edits;
   ScanRoute R;
   if (const int rc = scan_route (machine, &R))
     return rc;
   uint32_t sb = R.said;
   if (R.path == ACM_SCAN_PATH_GPU && acm_internal_symbol_bytes (machine, &sb))
     return ACM_GPU_E_INTERNAL;
-  if (acm_internal_approx_machine_check (machine, sb, spell_data, spell_off, k, terms, tgt_ptr, n_targets))
+  if ((edits ? acm_internal_edit_machine_check : acm_internal_approx_machine_check) (machine, sb, spell_data, spell_off, k, terms, tgt_ptr, n_targets))
     return ACM_GPU_E_ARG;
   const auto host_loop = [&] (uint32_t said) {
-    return acm_internal_cpu_scan_approx (machine, text, n_symbols, said, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist,
-                                         out_capacity, n_found);
+    return (edits ? acm_internal_cpu_scan_edit : acm_internal_cpu_scan_approx) (machine, text, n_symbols, said, offsets, n_texts, spell_data, spell_off, k,
+                                                                                terms, tgt_ptr, n_targets, out, dist, out_capacity, n_found);
   };
   if (R.path != ACM_SCAN_PATH_GPU) { /* (no class plan is made: the route is the loop itself) */
     acm_internal_plan_lock (machine);
@@ -7497,9 +7627,26 @@ acm_scan_approx (ACMachine *machine, const void *text, uint64_t n_symbols, const
     return rc;
   }
   return routed_scan (machine, RecordPath::OnSuccessOrOverflow, host_loop, [&] (ACMPlan *plan) {
-    return acm_gpu_scan_approx_host (plan, text, n_symbols, 0, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist, out_capacity,
-                                     n_found);
+    return scan_set_host (metric, plan, text, n_symbols, 0, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist, out_capacity,
+                          n_found);
   });
+}
+} // namespace
+
+extern "C" int
+acm_scan_approx (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const void *spell_data,
+                 const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out,
+                 uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  return scan_set (Metric::Mismatches, machine, text, n_symbols, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist, out_capacity,
+                   n_found);
+}
+
+extern "C" int
+acm_scan_edit (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const void *spell_data,
+               const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out,
+               uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  return scan_set (Metric::Edits, machine, text, n_symbols, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist, out_capacity,
+                   n_found);
 }
 
 /* acm_scan continued from a cursor (include/acm_gpu.h): the reference's own `const ACState *`, in

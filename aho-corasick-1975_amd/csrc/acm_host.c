@@ -2107,3 +2107,225 @@ acm_internal_cpu_scan_approx (ACMachine *m, const void *text, uint64_t n_symbols
   free (records);
   return rc;
 }
+
+/* ---- keywords within edit distance k (include/acm_gpu.h): the two further conditions on the budgets, the plain sequential EDIT of a
+ * record set in canonical order, and acm_scan_edit's host path.  The set, the postings and the hits are APPROX's (apx_set, apx_post,
+ * apx_hit); what differs is the verification: a seed fixes a window of ends, not one start. */
+#define EDIT_MAX_K 15u
+#define EDIT_INF 0xFFFFFFFFu
+
+/* the conditions the edit calls add to acm_approx_check: k[w] <= 15 and k[w] < L_w */
+static int
+edit_budgets_check (const uint64_t *spell_off, const uint32_t *k, uint64_t n_targets) {
+  for (uint64_t w = 0; w < n_targets; w++)
+    if (k[w] > EDIT_MAX_K || k[w] >= spell_off[w + 1] - spell_off[w])
+      return ACM_GPU_E_ARG;
+  return ACM_GPU_OK;
+}
+
+int
+acm_edit_check (const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets,
+                uint64_t n_keywords) {
+  if (acm_approx_check (spell_off, k, terms, tgt_ptr, n_targets, n_keywords))
+    return ACM_GPU_E_ARG;
+  return edit_budgets_check (spell_off, k, n_targets);
+}
+
+/* the hits of a call, grown as the seeds are walked */
+struct edit_hits {
+  struct apx_hit *hit;
+  uint64_t n, room;
+};
+
+static int
+edit_hits_push (struct edit_hits *H, uint64_t end_pos, uint32_t length, uint32_t target, uint32_t d) {
+  if (H->n == H->room) {
+    const uint64_t room = H->room ? 2 * H->room : 64;
+    struct apx_hit *grown = realloc (H->hit, room * sizeof *grown);
+    if (!grown)
+      return ACM_GPU_E_NOMEM;
+    H->hit = grown;
+    H->room = room;
+  }
+  H->hit[H->n++] = (struct apx_hit){ { end_pos, length, target }, d };
+  return ACM_GPU_OK;
+}
+
+/* What one seed gives: record r is term q->j of target q->target (the term's keyword is the record's).  The ends it can seed are
+ * [e0, e1]; the banded dynamic programme over the diagonals [e0 + 1 - L - k, e1 + 1 - L + k] gives (D, s*) at every such end whose
+ * D is within the budget.  Cell (i, c): i symbols of the target matched, the text consumed up to c; diagonal index d = c - i - B.
+ * A cell is cost << 6 | (63 - d0) with d0 the diagonal index its path began on in row 0, so that one minimum takes the least cost
+ * and then the largest start; cells above k, left of lo and right of e1 + 1 do not exist (EDIT_INF). */
+static int
+edit_window (const ACMRecord *r, const struct apx_post *q, const unsigned char *text, uint64_t n_symbols, uint64_t pos_base,
+             const uint64_t *offsets, uint64_t n_texts, const struct apx_set *A, struct edit_hits *H) {
+  const uint64_t eq = r->end_pos - pos_base, L = A->spell_off[q->target + 1] - A->spell_off[q->target];
+  const ACMPatternTerm *term = &A->terms[A->tgt_ptr[q->target] + q->j];
+  const uint32_t k = A->k[q->target], sb = A->sym_bytes;
+  if (r->length != term->length)
+    return ACM_GPU_OK;
+  uint64_t t_lo = 0, t_hi = n_symbols; /* the text of the record's end */
+  if (offsets) {
+    if (!n_texts)
+      return ACM_GPU_OK;
+    uint64_t lo = 0, hi = n_texts - 1; /* the largest text with offsets[text] <= eq */
+    while (lo < hi) {
+      const uint64_t mid = lo + (hi - lo + 1) / 2;
+      if (offsets[mid] <= eq)
+        lo = mid;
+      else
+        hi = mid - 1;
+    }
+    t_lo = offsets[lo];
+    t_hi = offsets[lo + 1];
+  }
+  if (eq + 1 < t_lo + term->length) /* the piece begins in front of its text: a record that spans a cut */
+    return ACM_GPU_OK;
+  const uint64_t behind = L - term->offset - term->length; /* the symbols of the target behind the piece */
+  const uint64_t e0 = eq + (behind > k ? behind - k : 0), e1 = eq + behind + k < t_hi - 1 ? eq + behind + k : t_hi - 1;
+  if (e0 > e1)
+    return ACM_GPU_OK;
+  const int64_t B = (int64_t)e0 + 1 - (int64_t)L - (int64_t)k, c_lo = (int64_t)t_lo, c_hi = (int64_t)e1 + 1;
+  const uint32_t nd = (uint32_t)(e1 - e0) + 2 * k + 1; /* <= 4 k + 1 <= 61 */
+  const unsigned char *spell = A->spell + A->spell_off[q->target] * sb;
+  uint32_t row_a[64], row_b[64], *prev = row_a, *cur = row_b;
+  for (uint32_t d = 0; d < nd; d++)
+    prev[d] = B + d >= c_lo && B + d <= c_hi ? 63 - d : EDIT_INF;
+  for (uint64_t i = 1; i <= L; i++) {
+    int any = 0;
+    for (uint32_t d = 0; d < nd; d++) {
+      const int64_t c = B + (int64_t)d + (int64_t)i;
+      uint32_t v = EDIT_INF;
+      if (c >= c_lo && c <= c_hi) {
+        if (c > c_lo && prev[d] != EDIT_INF) {
+          const unsigned char *a = text + (uint64_t)(c - 1) * sb, *b = spell + (i - 1) * sb;
+          const int same = A->cmp ? A->cmp (a, b, A->cmp_arg) == 0 : memcmp (a, b, sb) == 0;
+          v = prev[d] + (same ? 0 : 64);
+        }
+        if (d + 1 < nd && prev[d + 1] != EDIT_INF && prev[d + 1] + 64 < v)
+          v = prev[d + 1] + 64;
+        if (d > 0 && cur[d - 1] != EDIT_INF && cur[d - 1] + 64 < v)
+          v = cur[d - 1] + 64;
+        if (v != EDIT_INF && (v >> 6) > k)
+          v = EDIT_INF;
+      }
+      cur[d] = v;
+      any |= v != EDIT_INF;
+    }
+    if (!any) /* Ukkonen's cut-off: no cell of this row is within the budget, so none behind it is */
+      return ACM_GPU_OK;
+    uint32_t *t = prev;
+    prev = cur;
+    cur = t;
+  }
+  for (uint32_t d = k; d <= k + (uint32_t)(e1 - e0); d++)
+    if (prev[d] != EDIT_INF) {
+      const uint32_t d0 = 63 - (prev[d] & 63);
+      if (edit_hits_push (H, pos_base + e0 - k + d, (uint32_t)(L + d - d0), q->target, prev[d] >> 6))
+        return ACM_GPU_E_NOMEM;
+    }
+  return ACM_GPU_OK;
+}
+
+/* approx_core's argument walk, then every seed's window; the hits are ordered, and what several seeds reached is kept once */
+static int
+edit_core (const ACMRecord *records, uint64_t n, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+           const struct apx_set *A, uint64_t n_targets, uint64_t n_keywords, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  if (!n_found || (n && !records) || (out_capacity && !out) || A->sym_bytes == 0 || (n_symbols && !text) || (n_targets && !A->spell) ||
+      acm_edit_check (A->spell_off, A->k, A->terms, A->tgt_ptr, n_targets, n_keywords))
+    return ACM_GPU_E_ARG;
+  if (offsets) {
+    if (offsets[0] != 0 || offsets[n_texts] != n_symbols)
+      return ACM_GPU_E_ARG;
+    for (uint64_t t = 0; t < n_texts; t++)
+      if (offsets[t] > offsets[t + 1])
+        return ACM_GPU_E_ARG;
+  }
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+      return ACM_GPU_E_ARG;
+  }
+  const uint64_t n_terms = A->tgt_ptr[n_targets];
+  struct apx_post *post = malloc ((n_terms ? n_terms : 1) * sizeof *post);
+  if (!post)
+    return ACM_GPU_E_NOMEM;
+  for (uint64_t w = 0; w < n_targets; w++)
+    for (uint64_t i = A->tgt_ptr[w]; i < A->tgt_ptr[w + 1]; i++)
+      post[i] = (struct apx_post){ A->terms[i].keyword_id, (uint32_t)w, (uint32_t)(i - A->tgt_ptr[w]) };
+  qsort (post, n_terms, sizeof *post, apx_post_cmp);
+  struct edit_hits H = { NULL, 0, 0 };
+  int rc = ACM_GPU_OK;
+  for (uint64_t j = 0; !rc && j < n; j++) {
+    const ACMRecord *r = &records[j];
+    uint64_t lo = 0, hi = n_terms; /* the keyword's first posting */
+    while (lo < hi) {
+      const uint64_t mid = lo + (hi - lo) / 2;
+      if (post[mid].keyword_id < r->keyword_id)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    for (uint64_t q = lo; !rc && q < n_terms && post[q].keyword_id == r->keyword_id; q++)
+      rc = edit_window (r, &post[q], text, n_symbols, pos_base, offsets, n_texts, A, &H);
+  }
+  free (post);
+  if (rc) {
+    free (H.hit);
+    return rc;
+  }
+  /* (w, e) reached from several seeds has one D and one s*, so its hits are equal and stand side by side in the order */
+  uint64_t found = 0;
+  if (H.n) {
+    qsort (H.hit, H.n, sizeof *H.hit, apx_hit_cmp);
+    for (uint64_t i = 0; i < H.n; i++)
+      if (!found || H.hit[i].r.end_pos != H.hit[found - 1].r.end_pos || H.hit[i].r.keyword_id != H.hit[found - 1].r.keyword_id ||
+          H.hit[i].r.length != H.hit[found - 1].r.length)
+        H.hit[found++] = H.hit[i];
+  }
+  *n_found = found;
+  if (out && found <= out_capacity)
+    for (uint64_t i = 0; i < found; i++) {
+      out[i] = H.hit[i].r;
+      if (dist)
+        dist[i] = H.hit[i].d;
+    }
+  free (H.hit);
+  return out && found > out_capacity ? ACM_GPU_E_OVERFLOW : ACM_GPU_OK;
+}
+
+int
+acm_edit_records (const ACMRecord *records, uint64_t n, const void *text, uint32_t sym_bytes, uint64_t n_symbols, uint64_t pos_base,
+                  const uint64_t *offsets, uint64_t n_texts, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                  const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, uint64_t n_keywords, ACMRecord *out, uint32_t *dist,
+                  uint64_t out_capacity, uint64_t *n_found) {
+  const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, NULL, NULL };
+  return edit_core (records, n, text, n_symbols, pos_base, offsets, n_texts, &A, n_targets, n_keywords, out, dist, out_capacity, n_found);
+}
+
+/* the checks acm_scan_edit makes on every path: acm_scan_approx's, plus the two conditions on the budgets */
+int
+acm_internal_edit_machine_check (ACMachine *m, uint32_t sym_bytes, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                                 const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets) {
+  if (acm_internal_approx_machine_check (m, sym_bytes, spell_data, spell_off, k, terms, tgt_ptr, n_targets))
+    return ACM_GPU_E_ARG;
+  return edit_budgets_check (spell_off, k, n_targets);
+}
+
+/* acm_scan_edit on the host: acm_internal_cpu_scan_approx with the sequential EDIT behind the caller loop */
+int
+acm_internal_cpu_scan_edit (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                            const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
+                            const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  if (!m || !n_found)
+    return ACM_GPU_E_ARG;
+  ACMRecord *records;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, n_symbols, offsets, n_texts, sym_bytes, NULL, &records, &found);
+  if (!rc) {
+    const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, m->cmp, m->cmp_arg };
+    rc = edit_core (records, found, text, n_symbols, 0, offsets, n_texts, &A, n_targets, acm_nb_keywords (m), out, dist, out_capacity, n_found);
+  }
+  free (records);
+  return rc;
+}

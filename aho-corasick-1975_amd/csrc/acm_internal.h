@@ -120,6 +120,14 @@ int acm_internal_cpu_scan_approx (ACMachine *m, const void *text, uint64_t n_sym
                                   const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
                                   const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity,
                                   uint64_t *n_found);
+/* acm_scan_edit's checks on every path: acm_internal_approx_machine_check plus the edit calls' two conditions (k[w] <= 15, k[w] < L_w) */
+int acm_internal_edit_machine_check (ACMachine *m, uint32_t sym_bytes, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                                     const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets);
+/* acm_scan_edit's host path: acm_internal_cpu_scan_approx with the sequential EDIT behind the caller loop */
+int acm_internal_cpu_scan_edit (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                                const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
+                                const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity,
+                                uint64_t *n_found);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

@@ -173,5 +173,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_anchored.h"
 #include "dev_patterns.h"
 #include "dev_approx.h"
+#include "dev_edit.h"
 
 } // namespace

@@ -1650,9 +1650,9 @@ int acm_scan_patterns (ACMachine *machine, const void *text, uint64_t n_symbols,
  * acm_set_symbol_bytes (ACM_GPU_E_INELIGIBLE without it).  A missing device stays an error, never a
  * fallback.
  *
- * Out of scope: insertions and deletions (edit distance); class plans on the device; flows, streams and
- * several GPUs; feeding the output to SELECT or REPLACE (their contract bounds lengths by the plan's
- * lmax, and L_w is not bound by it). */
+ * Out of scope: insertions and deletions (edit distance: EDIT, the next section); class plans on the
+ * device; flows, streams and several GPUs; feeding the output to SELECT or REPLACE (their contract bounds
+ * lengths by the plan's lmax, and L_w is not bound by it). */
 typedef struct ACMApprox ACMApprox;
 typedef struct {
   uint64_t targets, terms, seed_keywords, longest, max_k, max_postings;
@@ -1695,6 +1695,105 @@ int acm_scan_approx (ACMachine *machine, const void *text, uint64_t n_symbols,
                      const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
                      const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets,
                      ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity, uint64_t *n_found);
+
+/* ------------------------------------------------------------------ keywords within edit distance k
+ * APPROX survives substituted symbols only.  EDIT also survives a dropped and an added symbol: every end
+ * at which a target occurs within unit-cost Levenshtein distance k -- the typos of a term list (`Daloway`
+ * is at Hamming distance 6 of `Dalloway`, and at edit distance 1), indels in primers and motifs, a byte
+ * inserted into a signature.  The compiled set is APPROX's (ACMApprox, acm_gpu_approx_create / _destroy /
+ * _info): the metric is a property of the call.  The cut into k + 1 pieces is complete for edit distance
+ * too; what differs is the verification, because a seed no longer fixes one start: it fixes up to
+ * 2 k + 1 ends and a band of start diagonals.
+ *
+ * DEFINITION.  Targets, spellings, budgets and terms are exactly APPROX's: spell_data, spell_off, k,
+ * terms, tgt_ptr, n_targets.  The edit calls add two conditions (acm_edit_check; ACM_GPU_E_ARG
+ * otherwise): k[w] <= 15, and k[w] < L_w, so that no match is empty.
+ * EDIT (R, text, offsets, T).  R is a record set in canonical order with positions pos_base + index;
+ * text[0 .. n_symbols) is in the caller's symbols; offsets follows the batch contract (NULL: one text);
+ * symbols compare bitwise over sym_bytes bytes.  For a target w with spelling P (L symbols) and a text
+ * [lo, hi):
+ *   ed (P, X) is the unit-cost Levenshtein distance: substitution, insertion and deletion cost 1 each;
+ *   for a buffer index e in [lo, hi), D_w (e) = min over s in [lo, e + 1] of ed (P, text[s .. e]);
+ *   s*_w (e) is the LARGEST s that attains the minimum: the shortest best match.  With D <= k < L it has
+ *   e - s* + 1 >= L - k >= 1.
+ * Target w MATCHES with end e iff
+ *   1. D_w (e) <= k[w], and
+ *   2. (seed) some term (kid, o, l) of w, with r = L_w - o - l the symbols of the target behind the piece,
+ *      has a record (pos_base + q, l, kid) in R with lo <= q - l + 1 and q < hi (the piece lies inside
+ *      the text of e) and max (0, r - k[w]) <= e - q <= r + k[w].
+ * Each (w, e) that matches gives exactly one ACMRecord (end_pos = pos_base + e, length = e - s*_w (e) + 1,
+ * keyword_id = w) and dist[...] = D_w (e), however many terms and records seed it.  The total order is
+ * end_pos ascending, then length descending, then target id ascending.
+ * COMPLETENESS.  When the terms of w are k[w] + 1 pairwise disjoint pieces, each keyword is spelled as its
+ * piece and R is the full record set of the buffer, condition 2 follows from condition 1.  Proof: an
+ * alignment of P with text[s* .. e] of cost D <= k touches at most k of the k + 1 disjoint pieces, so one
+ * piece [o, o + l) is aligned symbol by symbol with equal text symbols text[q - l + 1 .. q], s* <= q - l + 1
+ * and q <= e; that is an exact occurrence of the keyword inside the text of e, so its record is in R.  The
+ * r symbols of P behind the piece are aligned with text(q .. e], whose e - q symbols differ from r by at
+ * most the insertions and deletions of the alignment: |e - q - r| <= k, and e - q >= 0.  EDIT is then
+ * every end, inside one text, at which the target occurs within its budget: the textbook (Sellers)
+ * semantics.  Neighbouring ends e - 1, e, e + 1 of one occurrence are all reported when all are within
+ * the budget; that is the definition.  With fewer terms, or terms that are not such pieces, condition 2
+ * removes matches; that is defined, not an error.
+ *
+ * acm_edit_check: acm_approx_check plus the two conditions.  acm_edit_records: the plain sequential EDIT
+ * on the host, no device, acm_approx_records' contract; its work follows the seeds: per seed the banded
+ * dynamic programme of its window, then the hits in order with each (w, e) kept once.
+ * acm_gpu_edit_records_device (dev_edit.h): acm_gpu_approx_records_device's contract, word for word,
+ * with these differences.  A set with max_k > 15 or a target of L_w <= k[w] is refused (ACM_GPU_E_ARG,
+ * and the tmp_bytes calls return 0); the set remembers at creation whether it is fit for EDIT.
+ * acm_gpu_approx_info's figures bound the output: n records give at most n x max_postings x
+ * (2 max_k + 1) matches.  One group of G consecutive lanes takes one input record, G = 16, 32 or 64 for
+ * max_k <= 3, 7 or 15, over tiles of 64 records (ACM_GPU_EDIT_TILE=<records>: a multiple of 64 from 64
+ * to 1 Mi, read at every call).  Per posting the group runs the cheap tests, then the banded dynamic
+ * programme with one lane per diagonal as an anti-diagonal wavefront with Ukkonen's cut-off, and a match
+ * (w, e) is emitted by its OWNER alone: the least (term index, record end) among the seeds that satisfy
+ * condition 2 for e, decided by lookups in R -- so *d_count is exact in every case, also above
+ * out_capacity, and no atomic decides a slot.  The passes are APPROX's: the check of d_offsets in a launch
+ * of its own, count, a 64-bit exclusive sum, fill (verifying again), and the order passes only when the
+ * total fits.  *d_n > n_or_capacity, bad offsets, records that break the contract and input not in
+ * canonical order: APPROX's rules.
+ * acm_gpu_scan_edit_device, acm_gpu_scan_edit_host, acm_scan_edit: as their APPROX counterparts.  Class
+ * plans are refused with ACM_GPU_E_INELIGIBLE; plans that intern 8-byte symbols are taken.  acm_scan_edit
+ * is total over machines as acm_scan_approx is: machines with another comparator run the caller loop and
+ * the sequential EDIT under that comparator, report ACM_SCAN_PATH_CPU_LOOP and need acm_set_symbol_bytes;
+ * its machine-knowing check is acm_scan_approx's plus the two conditions.
+ *
+ * Out of scope: thinning neighbouring ends of one occurrence to one match; transpositions at cost 1;
+ * weighted costs; k > 15; class plans on the device; flows, streams and several GPUs. */
+int acm_edit_check (const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
+                    uint64_t n_targets, uint64_t n_keywords);
+int acm_edit_records (const ACMRecord *records, uint64_t n, const void *text, uint32_t sym_bytes, uint64_t n_symbols,
+                      uint64_t pos_base, const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                      const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                      const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, uint64_t n_keywords,
+                      ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity, uint64_t *n_found);
+size_t acm_gpu_edit_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t n_or_capacity,
+                               uint64_t out_capacity, uint64_t n_texts);
+int acm_gpu_edit_records_device (ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records,
+                                 uint64_t n_or_capacity, const uint64_t *d_n /* may be NULL */,
+                                 const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                 const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                 ACMRecord *d_out, uint32_t *d_dist /* may be NULL */, uint64_t out_capacity,
+                                 uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_scan_edit_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity,
+                                    uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_edit_device (ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols,
+                              uint64_t pos_base, const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                              uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist /* may be NULL */,
+                              uint64_t out_capacity, uint64_t *d_count, uint64_t *d_found,
+                              void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_edit_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base,
+                            const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                            const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                            const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets,
+                            ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity,
+                            uint64_t *n_found);   /* blocking */
+int acm_scan_edit (ACMachine *machine, const void *text, uint64_t n_symbols,
+                   const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                   const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
+                   const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets,
+                   ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity, uint64_t *n_found);
 
 /* ------------------------------------------------------------------ several GPUs of one node, one process
  * The reference's model for parallel work is one shared read-only machine and one cursor per worker
