@@ -18,6 +18,7 @@ from .binding import (  # noqa: F401
     anchored_records, ACM_ANCHORED_PREFIXES, ACM_ANCHORED_LONGEST, ACM_ANCHORED_WHOLE, ACM_LOOKUP_NONE,
     PatternSet, Patterns, patterns_records,
     ApproxSet, Approx, approx_records, edit_records,
+    ChainSet, Chains, ChainsInfo, chains_records,
 )
 from . import synth  # noqa: F401
 from . import sharded  # noqa: F401

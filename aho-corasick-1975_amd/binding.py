@@ -81,6 +81,10 @@ class PatternsInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("patterns", "terms", "anchor_keywords", "longest", "max_anchor_postings")]
 
 
+class ChainsInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("chains", "terms", "max_terms", "max_gap", "max_postings", "max_last_postings")]
+
+
 class ApproxInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("targets", "terms", "seed_keywords", "longest", "max_k", "max_postings")]
 
@@ -130,6 +134,9 @@ EXPORTS = [
     "acm_gpu_scan_approx_host", "acm_scan_approx",
     "acm_edit_check", "acm_edit_records", "acm_gpu_edit_tmp_bytes", "acm_gpu_edit_records_device", "acm_gpu_scan_edit_tmp_bytes",
     "acm_gpu_scan_edit_device", "acm_gpu_scan_edit_host", "acm_scan_edit",
+    "acm_chains_check", "acm_chains_records", "acm_gpu_chains_create", "acm_gpu_chains_destroy", "acm_gpu_chains_info",
+    "acm_gpu_chains_tmp_bytes", "acm_gpu_chains_records_device", "acm_gpu_scan_chains_tmp_bytes", "acm_gpu_scan_chains_device",
+    "acm_gpu_scan_chains_host", "acm_scan_chains",
 ]
 
 
@@ -404,6 +411,28 @@ def lib():
     L.acm_gpu_scan_patterns_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_scan_patterns.restype = i32
     L.acm_scan_patterns.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_chains_check.restype = i32
+    L.acm_chains_check.argtypes = [vp, vp, u64, u64]
+    L.acm_chains_records.restype = i32
+    L.acm_chains_records.argtypes = [vp, u64, u64, u64, vp, u64, vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_chains_create.restype = i32
+    L.acm_gpu_chains_create.argtypes = [vp, vp, vp, u64, C.POINTER(vp)]
+    L.acm_gpu_chains_destroy.restype = None
+    L.acm_gpu_chains_destroy.argtypes = [vp]
+    L.acm_gpu_chains_info.restype = i32
+    L.acm_gpu_chains_info.argtypes = [vp, C.POINTER(ChainsInfo)]
+    L.acm_gpu_chains_tmp_bytes.restype = sz
+    L.acm_gpu_chains_tmp_bytes.argtypes = [vp, vp, u64, u64]
+    L.acm_gpu_chains_records_device.restype = i32
+    L.acm_gpu_chains_records_device.argtypes = [vp, vp, vp, u64, vp, u64, u64, vp, u64, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_chains_tmp_bytes.restype = sz
+    L.acm_gpu_scan_chains_tmp_bytes.argtypes = [vp, vp, u64, u64, u64]
+    L.acm_gpu_scan_chains_device.restype = i32
+    L.acm_gpu_scan_chains_device.argtypes = [vp, vp, vp, u64, u64, vp, u64, u64, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_chains_host.restype = i32
+    L.acm_gpu_scan_chains_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_scan_chains.restype = i32
+    L.acm_scan_chains.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_approx_check.restype = i32
     L.acm_approx_check.argtypes = [vp, vp, vp, vp, u64, u64]
     L.acm_approx_split.restype = i32
@@ -1018,6 +1047,100 @@ def patterns_records(records, patternset, n_symbols, offsets=None, pos_base=0, n
         out_capacity = int(n.value)
     out = np.zeros(max(int(out_capacity), 1), dtype=RECORD_DTYPE)
     _check(call(out, int(out_capacity)), "acm_patterns_records")
+    return out[:n.value]
+
+
+class ChainSet:
+    """Keyword chains with bounded gaps packed to the two arrays the C calls take: terms (uint32 [n_terms, 3]:
+    keyword_id, gap_min, gap_max) and chain_ptr (uint64, n_chains + 1).  `chains`: one list of (keyword_id,
+    gap_min, gap_max) terms per chain, in order -- the keyword begins gap_min to gap_max symbols behind the
+    last symbol of the term in front; a chain's first term has the gaps 0, 0.  from_specs() makes one from
+    keywords and gaps."""
+
+    def __init__(self, chains):
+        chains = [list(c) for c in chains]
+        self.n_chains = len(chains)
+        flat = [tuple(int(x) for x in t) for c in chains for t in c]
+        self.terms = np.array(flat, dtype=np.uint32).reshape(-1, 3)
+        self.chain_ptr = np.zeros(self.n_chains + 1, np.uint64)
+        if chains:
+            np.cumsum([len(c) for c in chains], out=self.chain_ptr[1:])
+        self.n_keywords = int(self.terms[:, 0].max()) + 1 if self.terms.size else 0   # what the host pass is told when nothing else is known
+
+    @classmethod
+    def from_specs(cls, machine, specs):
+        """A spec is [kw0, (min, max), kw1, (min, max), kw2, ...]: keywords (bytes, or arrays of symbol values)
+        with the bounds of the gap between each two.  The keywords `machine` does not hold yet are inserted,
+        those it holds keep their ids.  ValueError for a spec of another shape.  Returns the ChainSet
+        (n_keywords = the machine's keywords afterwards)."""
+        known = None
+        chains = []
+        for spec in specs:
+            spec = list(spec)
+            if len(spec) % 2 == 0:
+                raise ValueError("a chain is keyword, (min, max), keyword, ...: it begins and ends with a keyword")
+            terms = []
+            for j in range(0, len(spec), 2):
+                kw = spec[j]
+                run = np.frombuffer(bytes(kw), np.uint8) if isinstance(kw, (bytes, bytearray)) else np.asarray(kw).reshape(-1)
+                run = run.astype(_SYM_DTYPE[machine.sym_size])
+                if run.size == 0:
+                    raise ValueError("a keyword needs a symbol")
+                before = machine.nb_keywords
+                machine.add_keyword(run)
+                if machine.nb_keywords > before:
+                    kid = before
+                    if known is not None:
+                        known[machine.keyword(kid)[0]] = kid
+                else:                                              # held already: the dictionary's spelling of the run says which
+                    if known is None:
+                        known = {machine.keyword(k)[0]: k for k in range(machine.nb_keywords)}
+                    spelt = [w for e, length, w, _ in machine.match_loop(run) if e == run.size - 1 and length == run.size]
+                    kid = known[spelt[0]]
+                gap = (0, 0) if j == 0 else tuple(int(x) for x in spec[j - 1])
+                if len(gap) != 2:
+                    raise ValueError("a gap is (min, max)")
+                terms.append((kid, gap[0], gap[1]))
+            chains.append(terms)
+        cs = cls(chains)
+        cs.n_keywords = machine.nb_keywords
+        return cs
+
+    def args(self):
+        """(terms, chain_ptr, n_chains) as the C calls take them"""
+        return self.terms.ctypes.data if self.terms.size else None, self.chain_ptr.ctypes.data, self.n_chains
+
+    def check(self, n_keywords):
+        """acm_chains_check(): raises ACMError (ACM_GPU_E_ARG) for a set the calls would refuse"""
+        _check(lib().acm_chains_check(*self.args(), int(n_keywords)), "acm_chains_check")
+
+
+def _chainset(chains):
+    return chains if isinstance(chains, ChainSet) else ChainSet(chains)
+
+
+def chains_records(records, chainset, n_symbols, offsets=None, pos_base=0, n_keywords=None, out_capacity=None):
+    """acm_chains_records(): the matches of the chains of `chainset` among `records` (RECORD_DTYPE, in canonical
+    order, positions pos_base + index into a buffer of n_symbols symbols), by the sequential pass on the
+    host: per chain and end one record (end_pos of the match's last symbol, the length of the shortest match
+    that ends there, the chain's id), by end_pos ascending, length descending, chain id ascending.  `offsets`
+    (n_texts + 1 entries) cuts the buffer into texts; a match lies inside one text.  out_capacity None:
+    counted first, then sized by the count; given and too small: ACMError (ACM_GPU_E_OVERFLOW)."""
+    cs = _chainset(chainset)
+    a = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
+    off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+    nk = int(n_keywords) if n_keywords is not None else cs.n_keywords
+    n = C.c_uint64(0)
+
+    def call(out, cap):
+        return lib().acm_chains_records(a.ctypes.data if a.size else None, a.size, int(n_symbols), int(pos_base),
+                                        off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *cs.args(), nk,
+                                        out.ctypes.data if out is not None else None, cap, C.byref(n))
+    if out_capacity is None:                                       # (no output: the call only counts)
+        _check(call(None, 0), "acm_chains_records")
+        out_capacity = int(n.value)
+    out = np.zeros(max(int(out_capacity), 1), dtype=RECORD_DTYPE)
+    _check(call(out, int(out_capacity)), "acm_chains_records")
     return out[:n.value]
 
 
@@ -1686,6 +1809,26 @@ class Machine:
             _check(rc, "acm_scan_patterns")
             return out[:n.value]
 
+    def scan_chains(self, text, chainset, offsets=None, out_capacity=None):
+        """acm_scan_chains(): the matches of the chains of `chainset` (see chains_records) in `text`, or in
+        every text of the buffer when `offsets` (n_texts + 1 entries) cuts it; by default an overflow is
+        repeated once with the size the call reports."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        cs = _chainset(chainset)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        cap = int(out_capacity) if out_capacity is not None else 1024
+        for attempt in (0, 1):
+            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            rc = self.L.acm_scan_chains(self.handle, t.ctypes.data if t.size else None, t.size * t.itemsize // self.sym_size,
+                                        off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *cs.args(),
+                                        out.ctypes.data if cap else None, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_scan_chains")
+            return out[:n.value]
+
     def scan_approx(self, text, approxset, offsets=None, out_capacity=None):
         """acm_scan_approx(): (matches, dist) of the targets of `approxset` (see approx_records) in `text`, or in
         every text of the buffer when `offsets` (n_texts + 1 entries) cuts it; by default an overflow is repeated
@@ -1861,6 +2004,32 @@ class Patterns:
     def close(self):
         if self.h:
             lib().acm_gpu_patterns_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Chains:
+    """A chain set on a plan's device (ACMChains): Plan.chains_create() makes one."""
+
+    def __init__(self, handle, n_chains):
+        self.h = handle
+        self.n_chains = n_chains
+
+    def info(self):
+        """acm_gpu_chains_info(): chains, terms, max_terms, max_gap, max_postings and max_last_postings as a
+        dict; n records give at most n * max_last_postings matches."""
+        i = ChainsInfo()
+        _check(lib().acm_gpu_chains_info(self.h, C.byref(i)), "acm_gpu_chains_info")
+        return {n: int(getattr(i, n)) for n, _ in ChainsInfo._fields_}
+
+    def close(self):
+        if self.h:
+            lib().acm_gpu_chains_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -2543,6 +2712,108 @@ class Plan:
                 cap = int(n.value)
                 continue
             _check(rc, "acm_gpu_scan_patterns_host")
+            return out[:n.value]
+
+    def chains_create(self, chainset):
+        """acm_gpu_chains_create(): `chainset` (a ChainSet, or lists of (keyword_id, gap_min, gap_max) terms)
+        compiled and uploaded to this plan's device.  Returns a Chains; it stays valid across update()."""
+        cs = _chainset(chainset)
+        h = C.c_void_p()
+        _check(lib().acm_gpu_chains_create(self.h, *cs.args(), C.byref(h)), "acm_gpu_chains_create")
+        return Chains(h, cs.n_chains)
+
+    def _chains_handle(self, chains):
+        """(a Chains, whether this call made it) of a Chains, a ChainSet or lists of terms"""
+        return (chains, False) if isinstance(chains, Chains) else (self.chains_create(chains), True)
+
+    def chains_records(self, records, n, chains, n_symbols, offsets=None, pos_base=0, count=None, out=None, out_capacity=None, out_count=None):
+        """acm_gpu_chains_records_device(): the matches of `chains` (a Chains from chains_create(), or a
+        ChainSet compiled for this call) among records[:n] (an int64 [capacity, 2] device tensor in
+        canonical order), into `out` (None: a new tensor of out_capacity records, by default n times the
+        set's max_last_postings, which cannot overflow), queued on the current stream.  `count` (a device
+        int64 tensor) gives the number of records on the device: n is the room of `records` then.
+        `offsets` is a device int64 tensor of n_texts + 1 entries.  Returns (out, out_count): out_count (a
+        device tensor) holds the number of matches; above out_capacity it is the capacity needed.  Nothing
+        is synchronised."""
+        import torch
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
+        n = int(n)
+        S, own = self._chains_handle(chains)
+        try:
+            if out_capacity is None:
+                out_capacity = out.shape[0] if out is not None else n * S.info()["max_last_postings"]
+            out_capacity = int(out_capacity)
+            if out is None:
+                out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=records.device)
+            assert out.is_cuda and out.is_contiguous() and out.shape[0] >= out_capacity
+            if out_count is None:
+                out_count = torch.zeros(1, dtype=torch.int64, device=records.device)
+            n_texts = offsets.numel() - 1 if offsets is not None else 0
+            tb = lib().acm_gpu_chains_tmp_bytes(self.h, S.h, n, n_texts)
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
+            _check(lib().acm_gpu_chains_records_device(self.h, S.h, records.data_ptr(), n, count.data_ptr() if count is not None else None,
+                                                       int(n_symbols), int(pos_base), offsets.data_ptr() if offsets is not None else None, n_texts,
+                                                       out.data_ptr() if out_capacity else None, out_capacity, out_count.data_ptr(),
+                                                       tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_chains_records_device")
+            if own:
+                torch.cuda.current_stream().synchronize()          # the set goes away with this call
+            return out, out_count
+        finally:
+            if own:
+                S.close()
+
+    def scan_chains(self, text, chains, offsets=None, n_symbols=None, pos_base=0, capacity=None, out=None, out_capacity=None, tmp=None):
+        """acm_gpu_scan_chains_device(): the ordered scan of a device tensor into `capacity` records of the
+        call's own and the matches of `chains` among them, queued on the current stream.  Returns (out,
+        count, found, tmp) with count and found device tensors: out[:count] are the matches when count <=
+        out_capacity; found is the scan's count -- above `capacity` there is no match (count 0) and found
+        is a capacity that suffices."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        capacity = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+        S, own = self._chains_handle(chains)
+        try:
+            if out_capacity is None:
+                out_capacity = out.shape[0] if out is not None else capacity * S.info()["max_last_postings"]
+            out_capacity = int(out_capacity)
+            if out is None:
+                out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=text.device)
+            res = torch.zeros(2, dtype=torch.int64, device=text.device)
+            n_texts = offsets.numel() - 1 if offsets is not None else 0
+            tb = lib().acm_gpu_scan_chains_tmp_bytes(self.h, S.h, capacity, n_symbols, n_texts)
+            if tmp is None or tmp.numel() < tb:
+                tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+            _check(lib().acm_gpu_scan_chains_device(self.h, S.h, text.data_ptr(), n_symbols, int(pos_base),
+                                                    offsets.data_ptr() if offsets is not None else None, n_texts, capacity,
+                                                    out.data_ptr() if out_capacity else None, out_capacity, res.data_ptr(), res.data_ptr() + 8,
+                                                    tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_scan_chains_device")
+            if own:
+                torch.cuda.current_stream().synchronize()          # the set goes away with this call
+            return out, res[0:1], res[1:2], tmp
+        finally:
+            if own:
+                S.close()
+
+    def scan_chains_host(self, text, chainset, offsets=None, pos_base=0, out_capacity=None):
+        """acm_gpu_scan_chains_host(): numpy in, the chain matches out, through the C ABI only (no torch); an
+        overflow is repeated once with the size the call reports."""
+        t = np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        cs = _chainset(chainset)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        cap = int(out_capacity) if out_capacity is not None else 1024
+        for attempt in (0, 1):
+            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            rc = lib().acm_gpu_scan_chains_host(self.h, t.ctypes.data if t.size else None, n_sym, int(pos_base),
+                                                off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *cs.args(),
+                                                out.ctypes.data if cap else None, cap, C.byref(n))
+            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_gpu_scan_chains_host")
             return out[:n.value]
 
     def approx_create(self, approxset):

@@ -6223,6 +6223,303 @@ acm_gpu_scan_patterns_host (ACMPlan *plan, const void *text, uint64_t n_symbols,
   return download_records (rc, d_res, d_out, out, out_capacity, n_found);
 }
 
+/* ------------------------------------------------------------------ keyword chains with bounded gaps (include/acm_gpu.h, dev_chains.h)
+ * A chain set compiled into an index inverted by keyword, and the passes that join a record set in
+ * canonical order under it: the check of offsets[], one level pass per term level of the set, the
+ * count pass, the prefix over the records' counts, the fill pass, the patterns' order pass. */
+struct ACMChains {
+  int device = 0;
+  uint64_t n_chains = 0, n_terms = 0, max_terms = 0, max_gap = 0, max_postings = 0, max_last_postings = 0;
+  uint32_t n_keywords = 0;
+  void *blob = nullptr; /* one allocation: the arrays below */
+  uint32_t *d_post_ptr = nullptr;
+  ChainPost *d_post = nullptr;
+};
+
+namespace {
+constexpr uint64_t CHAINS_MOST_SLOTS = 1ull << 40; /* state slots of one call: records x the most postings of a keyword */
+
+struct ChainsRoom {
+  long long *count = nullptr, *first = nullptr;
+  CubRoom cub;
+};
+ChainsRoom
+chains_carve (Carve &c, const ACMChains *chains, uint64_t capacity, ChainsK &K) {
+  ChainsRoom R;
+  /* ACM_GPU_CHAINS_TILE=<records>: the passes' tile, a multiple of 64 (tests); ACM_GPU_CHAINS_COOP=<records>: windows of more
+   * records are walked by the whole wave (0: every window, a huge value: none) */
+  K.tile = tunable ("ACM_GPU_CHAINS_TILE", CHAINS_TILE_DEFAULT, CHAINS_TILE_MIN, CHAINS_TILE_MAX, Tune::MultWave);
+  K.coop = tunable ("ACM_GPU_CHAINS_COOP", CHAINS_COOP_DEFAULT, 0, 0x7FFFFFFFu, Tune::Any);
+  K.n_tiles = (capacity + K.tile - 1) / K.tile;
+  K.stride = (uint32_t)std::max<uint64_t> (chains->max_postings, 1);
+  K.ctl = c.take<PatternsCtl> (1);
+  K.state = c.take<unsigned long long> ((size_t)(capacity * K.stride));
+  R.count = c.take<long long> ((size_t)capacity + 1);
+  R.first = c.take<long long> ((size_t)capacity + 1);
+  R.cub = cub_room (c, 0, capacity + 1);
+  K.count = reinterpret_cast<unsigned long long *> (R.count);
+  K.first = reinterpret_cast<const unsigned long long *> (R.first);
+  return R;
+}
+
+bool
+chains_room_ok (const ACMChains *chains, uint64_t capacity) {
+  return capacity < (1ull << 31) && capacity * std::max<uint64_t> (chains->max_postings, 1) < CHAINS_MOST_SLOTS;
+}
+
+/* the fused call's scratch: the ordered scan's records, then the room the scan and the join share
+ * (the scan has ended when the join begins) */
+ScanPatternsRoom
+scan_chains_carve (Carve &c, const ACMPlan *plan, const ACMChains *chains, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  ScanPatternsRoom R;
+  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_chains_tmp_bytes (plan, chains, capacity, n_texts));
+  R.found = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
+  R.work = c.take (R.work_bytes);
+  return R;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_chains_create (ACMPlan *plan, const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains, ACMChains **out) {
+  if (!plan || !out)
+    return ACM_GPU_E_ARG;
+  const uint64_t nk = plan->covered_keywords;
+  if (acm_chains_check (terms, chain_ptr, n_chains, nk))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_terms = chain_ptr[n_chains];
+  /* the index: every term under its keyword, a keyword's postings by level, then chain */
+  struct Place {
+    uint32_t keyword_id, level, chain, term;
+  };
+  std::vector<Place> place (n_terms);
+  std::vector<uint32_t> post_ptr (nk + 1, 0), last_of (nk + 1, 0), at_of (n_terms ? n_terms : 1);
+  uint64_t max_terms = 0, max_gap = 0;
+  for (uint64_t c = 0; c < n_chains; c++) {
+    max_terms = std::max (max_terms, chain_ptr[c + 1] - chain_ptr[c]);
+    for (uint64_t i = chain_ptr[c]; i < chain_ptr[c + 1]; i++) {
+      place[i] = Place{ terms[i].keyword_id, (uint32_t)(i - chain_ptr[c]), (uint32_t)c, (uint32_t)i };
+      max_gap = std::max<uint64_t> (max_gap, terms[i].gap_max);
+      post_ptr[terms[i].keyword_id + 1]++;
+      last_of[terms[i].keyword_id] += i + 1 == chain_ptr[c + 1];
+    }
+  }
+  std::sort (place.begin (), place.end (), [] (const Place &a, const Place &b) {
+    return a.keyword_id != b.keyword_id ? a.keyword_id < b.keyword_id : a.level != b.level ? a.level < b.level : a.chain < b.chain;
+  });
+  uint64_t max_postings = 0, max_last = 0;
+  for (uint64_t k = 0; k < nk; k++) {
+    max_postings = std::max<uint64_t> (max_postings, post_ptr[k + 1]);
+    max_last = std::max<uint64_t> (max_last, last_of[k]);
+    post_ptr[k + 1] += post_ptr[k];
+  }
+  for (uint64_t q = 0; q < n_terms; q++) /* where a term stands among its keyword's postings */
+    at_of[place[q].term] = (uint32_t)(q - post_ptr[place[q].keyword_id]);
+  std::vector<ChainPost> post (n_terms ? n_terms : 1);
+  for (uint64_t q = 0; q < n_terms; q++) {
+    const Place &p = place[q];
+    const ACMChainTerm &t = terms[p.term];
+    const bool last = p.term + 1 == chain_ptr[p.chain + 1];
+    post[q] = ChainPost{ p.chain, p.level | (last ? CHAINS_LAST : 0), t.gap_min, t.gap_max, p.level ? terms[p.term - 1].keyword_id : 0,
+                         p.level ? at_of[p.term - 1] : 0, { 0, 0 } };
+  }
+  HIP_TRY (hipSetDevice (plan->device));
+  ACMChains *S = new (std::nothrow) ACMChains ();
+  if (!S)
+    return ACM_GPU_E_NOMEM;
+  S->device = plan->device;
+  S->n_chains = n_chains;
+  S->n_terms = n_terms;
+  S->max_terms = max_terms;
+  S->max_gap = max_gap;
+  S->max_postings = max_postings;
+  S->max_last_postings = max_last;
+  S->n_keywords = (uint32_t)nk;
+  size_t cur = 0;
+  const size_t o_post_ptr = blob_reserve (cur, post_ptr.size () * 4), o_post = blob_reserve (cur, post.size () * sizeof (ChainPost));
+  bool ok = hipMalloc (&S->blob, cur) == hipSuccess;
+  unsigned char *b = static_cast<unsigned char *> (S->blob);
+  ok = ok && hipMemcpy (b + o_post_ptr, post_ptr.data (), post_ptr.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_post, post.data (), post.size () * sizeof (ChainPost), hipMemcpyHostToDevice) == hipSuccess &&
+       hipDeviceSynchronize () == hipSuccess;
+  if (!ok) {
+    acm_gpu_chains_destroy (S);
+    return ACM_GPU_E_NOMEM;
+  }
+  S->d_post_ptr = reinterpret_cast<uint32_t *> (b + o_post_ptr);
+  S->d_post = reinterpret_cast<ChainPost *> (b + o_post);
+  *out = S;
+  return ACM_GPU_OK;
+}
+
+extern "C" void
+acm_gpu_chains_destroy (ACMChains *chains) {
+  if (!chains)
+    return;
+  (void)hipSetDevice (chains->device);
+  if (chains->blob)
+    (void)hipFree (chains->blob);
+  delete chains;
+}
+
+extern "C" int
+acm_gpu_chains_info (const ACMChains *chains, ACMChainsInfo *info) {
+  if (!chains || !info)
+    return ACM_GPU_E_ARG;
+  *info = ACMChainsInfo{ chains->n_chains, chains->n_terms, chains->max_terms, chains->max_gap, chains->max_postings, chains->max_last_postings };
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_chains_tmp_bytes (const ACMPlan *plan, const ACMChains *chains, uint64_t n_or_capacity, uint64_t n_texts) {
+  (void)n_texts; /* (nothing here is sized by the number of texts: the text of a match is a bisection of offsets[]) */
+  if (!plan || !chains || !chains_room_ok (chains, n_or_capacity))
+    return 0;
+  Carve c;
+  ChainsK K{};
+  chains_carve (c, chains, n_or_capacity, K);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_chains_records_device (ACMPlan *plan, const ACMChains *chains, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, uint64_t n_symbols,
+                               uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint64_t out_capacity,
+                               uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !chains || chains->device != plan->device || !d_count || !chains_room_ok (chains, n) || out_capacity >= (1ull << 31) ||
+      n_symbols >= (1ull << 56) || (out_capacity && !d_out) || (n && (!d_records || !d_tmp)) ||
+      (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+    return ACM_GPU_E_ARG;
+  if (n && out_capacity) { /* (the output is written while the input is still read) */
+    const uintptr_t a = reinterpret_cast<uintptr_t> (d_records), b = reinterpret_cast<uintptr_t> (d_out);
+    if (a < b + out_capacity * sizeof (ACMRecord) && b < a + n * sizeof (ACMRecord))
+      return ACM_GPU_E_ARG;
+  }
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n == 0) /* (no record: no match, whatever *d_n says) */
+    return no_record (plan, nullptr, d_count, st);
+  Carve carve (d_tmp);
+  ChainsK K{};
+  const ChainsRoom L = chains_carve (carve, chains, n, K);
+  if (tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  K.post_ptr = chains->d_post_ptr;
+  K.post = chains->d_post;
+  K.n_keywords = chains->n_keywords;
+  K.in = d_records;
+  K.capacity = n;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.n_symbols = n_symbols;
+  K.pos_base = pos_base;
+  K.offsets = n_texts ? d_offsets : nullptr; /* (no text: no symbol, every record breaks the contract) */
+  K.n_texts = n_texts;
+  K.out = d_out;
+  K.out_capacity = out_capacity;
+  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
+  K.error = error_word (plan);
+  /* what the two kernels of dev_patterns.h that run here as they are read of their argument */
+  PatternsK P{};
+  P.offsets = K.offsets;
+  P.n_texts = n_texts;
+  P.n_symbols = n_symbols;
+  P.ctl = K.ctl;
+  P.error = K.error;
+  P.capacity = n;
+  P.first = K.first;
+  P.out = d_out;
+  P.out_capacity = out_capacity;
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (PatternsCtl), st));
+  /* the check */
+  if (K.offsets) /* one size, whatever the number of texts */
+    HIP_TRY (launch (patterns_check_kernel, capped_grid (plan, (n_texts + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, P));
+  /* 1. (as many launches as the set's longest chain has terms) */
+  for (uint32_t level = 0; level < chains->max_terms; level++) {
+    K.level = level;
+    HIP_TRY (launch (chains_level_kernel, capped_grid (plan, K.n_tiles), dim3 (CHAINS_THREADS), 0, st, K));
+  }
+  /* 2. */
+  HIP_TRY (launch (chains_count_kernel, capped_grid (plan, K.n_tiles), dim3 (CHAINS_THREADS), 0, st, K));
+  /* 3. */
+  HIP_TRY (exclusive_sum (L.cub, L.count, L.first, n + 1, st));
+  /* 4. */
+  HIP_TRY (launch (chains_fill_kernel, capped_grid (plan, K.n_tiles), dim3 (CHAINS_THREADS), 0, st, K));
+  /* 5. */
+  if (out_capacity > 1)
+    HIP_TRY (launch (patterns_order_kernel, capped_grid (plan, (out_capacity + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, P));
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_scan_chains_tmp_bytes (const ACMPlan *plan, const ACMChains *chains, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!plan || !chains || !chains_room_ok (chains, capacity))
+    return 0;
+  Carve c;
+  scan_chains_carve (c, plan, chains, capacity, n_symbols, n_texts);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_scan_chains_device (ACMPlan *plan, const ACMChains *chains, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
+                            uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint64_t out_capacity, uint64_t *d_count, uint64_t *d_found,
+                            void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !chains || chains->device != plan->device || !d_count || !d_found || !chains_room_ok (chains, capacity) ||
+      out_capacity >= (1ull << 31) || (n_symbols && !d_text) || (out_capacity && !d_out) || (capacity && !d_tmp))
+    return ACM_GPU_E_ARG;
+  Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
+  const ScanPatternsRoom L = scan_chains_carve (carve, plan, chains, capacity, n_symbols, n_texts);
+  if (capacity && tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  if (capacity == 0) { /* no room: *d_found says what the records need, and nothing matches */
+    if (const int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_found, stream))
+      return rc;
+    return no_record (plan, nullptr, d_count, static_cast<hipStream_t> (stream));
+  }
+  if (const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, L.found, capacity, d_found, L.work, L.work_bytes, stream))
+    return rc;
+  return acm_gpu_chains_records_device (plan, chains, L.found, capacity, d_found, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count,
+                                        L.work, L.work_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_chains_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                          const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains, ACMRecord *out, uint64_t out_capacity,
+                          uint64_t *n_found) {
+  if (!plan || !n_found || out_capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
+      !optional_offsets_ok (offsets, n_texts, n_symbols) || (offsets && n_texts == 0 && n_symbols))
+    return ACM_GPU_E_ARG;
+  ACMChains *made = nullptr;
+  if (const int rc = acm_gpu_chains_create (plan, terms, chain_ptr, n_chains, &made))
+    return rc;
+  std::unique_ptr<ACMChains, void (*) (ACMChains *)> chains (made, acm_gpu_chains_destroy);
+  HIP_TRY (hipSetDevice (plan->device));
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the matches, the scan's records */
+  ACMRecord *d_out = nullptr;
+  uint64_t capacity = 0;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (temps.get (&d_res, 16));
+  if (const int rc = count_first (plan, d_text, n_symbols, d_res, &capacity)) /* the record room: the exact number of matches */
+    return rc;
+  if (!chains_room_ok (chains.get (), capacity))
+    return ACM_GPU_E_NOMEM;
+  const size_t tmp_bytes = acm_gpu_scan_chains_tmp_bytes (plan, chains.get (), capacity, n_symbols, n_texts);
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  HOST_TRY (temps.get (&d_out, out_capacity * 16));
+  if (offsets)
+    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  int rc = settle (plan,
+                   acm_gpu_scan_chains_device (plan, chains.get (), d_text, n_symbols, pos_base, d_off, n_texts, capacity, d_out, out_capacity, d_res,
+                                               d_res + 1, d_tmp, tmp_bytes, nullptr),
+                   true);
+  uint64_t found = 0;
+  if (!rc) {
+    HOST_TRY (hipMemcpy (&found, d_res + 1, 8, hipMemcpyDeviceToHost));
+    if (found > capacity) /* (the room is what the count pass found: never expected) */
+      rc = ACM_GPU_E_INTERNAL;
+  }
+  return download_records (rc, d_res, d_out, out, out_capacity, n_found);
+}
+
 /* ------------------------------------------------------------------ keywords with up to k mismatches (include/acm_gpu.h, dev_approx.h)
  * A target set compiled into an index inverted by term keyword, and the passes that verify a record set in
  * canonical order under it: the check of offsets[], the count pass, the prefix over the records' counts, the
@@ -7372,8 +7669,8 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally and acm_lookup only a scan that
  * succeeded, acm_select, acm_scan_words, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
- * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_scan_patterns, acm_scan_approx and acm_scan_edit also one whose
- * output had no room. */
+ * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_scan_patterns, acm_scan_chains, acm_scan_approx and
+ * acm_scan_edit also one whose output had no room. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -7399,7 +7696,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The seventeen calls below run on the same route, the same cached plan, under the same lock. */
+/* The eighteen calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -7593,6 +7890,23 @@ acm_scan_patterns (ACMachine *machine, const void *text, uint64_t n_symbols, con
     },
     [&] (ACMPlan *plan) {
       return acm_gpu_scan_patterns_host (plan, text, n_symbols, 0, offsets, n_texts, terms, pat_ptr, n_patterns, out, out_capacity, n_found);
+    });
+}
+
+/* keyword chains with bounded gaps (include/acm_gpu.h) */
+extern "C" int
+acm_scan_chains (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const ACMChainTerm *terms,
+                 const uint64_t *chain_ptr, uint64_t n_chains, ACMRecord *out, uint64_t out_capacity, uint64_t *n_found) {
+  if (!machine || !n_found || (n_symbols && !text) || (out_capacity && !out) || !optional_offsets_ok (offsets, n_texts, n_symbols) ||
+      acm_internal_chains_machine_check (machine, terms, chain_ptr, n_chains))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      return acm_internal_cpu_scan_chains (machine, text, n_symbols, said, offsets, n_texts, terms, chain_ptr, n_chains, out, out_capacity, n_found);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_scan_chains_host (plan, text, n_symbols, 0, offsets, n_texts, terms, chain_ptr, n_chains, out, out_capacity, n_found);
     });
 }
 

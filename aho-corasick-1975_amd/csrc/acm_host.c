@@ -1858,6 +1858,176 @@ acm_internal_cpu_scan_patterns (ACMachine *m, const void *text, uint64_t n_symbo
   return rc;
 }
 
+/* ---- keyword chains with bounded gaps (include/acm_gpu.h): the argument checks, the plain sequential CHAINS of a record set in
+ * canonical order, and acm_scan_chains' host path. */
+int
+acm_chains_check (const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains, uint64_t n_keywords) {
+  if (!chain_ptr || chain_ptr[0] != 0 || n_chains >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  for (uint64_t c = 0; c < n_chains; c++)
+    if (chain_ptr[c] >= chain_ptr[c + 1] || chain_ptr[c + 1] - chain_ptr[c] > ACM_CHAIN_TERMS_MAX) /* decreasing, no term, too many */
+      return ACM_GPU_E_ARG;
+  if (chain_ptr[n_chains] >= (1ull << 31) || (n_chains && !terms))
+    return ACM_GPU_E_ARG;
+  for (uint64_t c = 0; c < n_chains; c++)
+    for (uint64_t i = chain_ptr[c]; i < chain_ptr[c + 1]; i++) {
+      if (terms[i].gap_min > terms[i].gap_max || terms[i].gap_max > ACM_CHAIN_GAP_MAX || terms[i].keyword_id >= n_keywords)
+        return ACM_GPU_E_ARG;
+      if (i == chain_ptr[c] && terms[i].gap_max != 0) /* (gap_min <= gap_max: both are 0) */
+        return ACM_GPU_E_ARG;
+    }
+  return ACM_GPU_OK;
+}
+
+/* the total order of the output: end_pos ascending, length descending, chain id ascending */
+static int
+chain_out_cmp (const void *a, const void *b) {
+  const ACMRecord *x = a, *y = b;
+  if (x->end_pos != y->end_pos)
+    return x->end_pos < y->end_pos ? -1 : 1;
+  if (x->length != y->length)
+    return x->length > y->length ? -1 : 1;
+  return x->keyword_id < y->keyword_id ? -1 : x->keyword_id > y->keyword_id;
+}
+
+/* the first record of records[0 .. n) (canonical order) that ends at or behind end_pos */
+static uint64_t
+chain_first_at (const ACMRecord *records, uint64_t n, uint64_t end_pos) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (records[mid].end_pos < end_pos)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+#define CHAIN_NONE (~0ull)
+
+int
+acm_chains_records (const ACMRecord *records, uint64_t n, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                    const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains, uint64_t n_keywords, ACMRecord *out,
+                    uint64_t out_capacity, uint64_t *n_found) {
+  if (!n_found || (n && !records) || (out_capacity && !out) || acm_chains_check (terms, chain_ptr, n_chains, n_keywords))
+    return ACM_GPU_E_ARG;
+  if (offsets) {
+    if (offsets[0] != 0 || offsets[n_texts] != n_symbols)
+      return ACM_GPU_E_ARG;
+    for (uint64_t t = 0; t < n_texts; t++)
+      if (offsets[t] > offsets[t + 1])
+        return ACM_GPU_E_ARG;
+  }
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+      return ACM_GPU_E_ARG;
+  }
+  /* per chain the dynamic programme over its levels: best[i] = the greatest start of an embedding of the terms so far whose
+   * last record is record i (CHAIN_NONE: there is none); the matches gather in `hits`, which grows as they come */
+  uint64_t *best = malloc ((n ? n : 1) * sizeof *best), *prev = malloc ((n ? n : 1) * sizeof *prev);
+  ACMRecord *hits = NULL;
+  uint64_t found = 0, room = 0;
+  int rc = best && prev ? ACM_GPU_OK : ACM_GPU_E_NOMEM;
+  for (uint64_t c = 0; !rc && c < n_chains; c++) {
+    for (uint64_t i = chain_ptr[c]; i < chain_ptr[c + 1]; i++) {
+      const ACMChainTerm *term = &terms[i];
+      uint64_t *swap = prev;
+      prev = best;
+      best = swap;
+      for (uint64_t j = 0; j < n; j++) {
+        const ACMRecord *r = &records[j];
+        best[j] = CHAIN_NONE;
+        if (r->keyword_id != term->keyword_id)
+          continue;
+        const uint64_t s = r->end_pos - pos_base + 1 - r->length;
+        if (i == chain_ptr[c]) {
+          best[j] = s;
+          continue;
+        }
+        if (s < (uint64_t)term->gap_min + 1) /* the window [s - 1 - gap_max, s - 1 - gap_min] of ends is empty */
+          continue;
+        const uint64_t hi = s - 1 - term->gap_min, lo = s - 1 >= term->gap_max ? s - 1 - term->gap_max : 0;
+        for (uint64_t w = chain_first_at (records, n, pos_base + lo); w < n && records[w].end_pos - pos_base <= hi; w++)
+          if (records[w].keyword_id == terms[i - 1].keyword_id && prev[w] != CHAIN_NONE && (best[j] == CHAIN_NONE || prev[w] > best[j]))
+            best[j] = prev[w];
+      }
+    }
+    for (uint64_t j = 0; !rc && j < n; j++) {
+      if (best[j] == CHAIN_NONE)
+        continue;
+      const uint64_t e = records[j].end_pos - pos_base, S = best[j];
+      if (offsets) { /* one text holds S and e: the text of S, the largest with offsets[text] <= S, ends behind e */
+        uint64_t lo = 0, hi = n_texts - 1;
+        while (lo < hi) {
+          const uint64_t mid = lo + (hi - lo + 1) / 2;
+          if (offsets[mid] <= S)
+            lo = mid;
+          else
+            hi = mid - 1;
+        }
+        if (e >= offsets[lo + 1])
+          continue;
+      }
+      if (found == room) {
+        room = room ? 2 * room : 256;
+        ACMRecord *more = realloc (hits, room * sizeof *hits);
+        if (!more) {
+          rc = ACM_GPU_E_NOMEM;
+          break;
+        }
+        hits = more;
+      }
+      hits[found++] = (ACMRecord){ records[j].end_pos, (uint32_t)(e + 1 - S), (uint32_t)c };
+    }
+  }
+  free (best);
+  free (prev);
+  if (!rc) {
+    *n_found = found;
+    if (out && found > out_capacity)
+      rc = ACM_GPU_E_OVERFLOW;
+    else if (out) {
+      if (found > 1)
+        qsort (hits, found, sizeof *hits, chain_out_cmp);
+      if (found)
+        memcpy (out, hits, found * sizeof *hits);
+    }
+  }
+  free (hits);
+  return rc;
+}
+
+/* the check acm_scan_chains makes on every path: acm_chains_check against the machine's keywords */
+int
+acm_internal_chains_machine_check (ACMachine *m, const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains) {
+  if (!m)
+    return ACM_GPU_E_ARG;
+  acm_internal_lock (m);
+  const int rc = acm_chains_check (terms, chain_ptr, n_chains, m->nb_keywords);
+  acm_internal_unlock (m);
+  return rc;
+}
+
+/* acm_scan_chains on the host: the caller loop (from the root at every offset of a batch), then the sequential pass over what
+ * it found -- what ACM_SCAN_PATH_CPU_LOOP runs.  The public call has checked the arguments. */
+int
+acm_internal_cpu_scan_chains (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                              const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains, ACMRecord *out, uint64_t out_capacity,
+                              uint64_t *n_found) {
+  if (!m || !n_found)
+    return ACM_GPU_E_ARG;
+  ACMRecord *records;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, n_symbols, offsets, n_texts, sym_bytes, NULL, &records, &found);
+  if (!rc)
+    rc = acm_chains_records (records, found, n_symbols, 0, offsets, n_texts, terms, chain_ptr, n_chains, acm_nb_keywords (m), out, out_capacity,
+                             n_found);
+  free (records);
+  return rc;
+}
+
 /* ---- keywords with up to k mismatches (include/acm_gpu.h): the argument checks, the canonical cut, the plain sequential APPROX of a
  * record set in canonical order, and acm_scan_approx's host path. */
 int

@@ -174,5 +174,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_patterns.h"
 #include "dev_approx.h"
 #include "dev_edit.h"
+#include "dev_chains.h"
 
 } // namespace

@@ -1516,7 +1516,7 @@ void acm_gpu_stream_close (ACMStream *stream);
  * length is ACM_GPU_E_ARG here.  A missing device stays an error, never a fallback.
  *
  * Out of scope: trailing don't-cares (not expressible: they would test nothing but that the text
- * goes on); bounded variable gaps ({n-m}); symbol classes or alternatives inside a pattern; flows,
+ * goes on); bounded variable gaps ({n-m}: acm_scan_chains below joins those); symbol classes or alternatives inside a pattern; flows,
  * streams and several GPUs; feeding pattern records to SELECT or REPLACE (their contract bounds
  * lengths by the plan's lmax, and L_p is not bound by it). */
 typedef struct {
@@ -1794,6 +1794,141 @@ int acm_scan_edit (ACMachine *machine, const void *text, uint64_t n_symbols,
                    const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
                    const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets,
                    ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity, uint64_t *n_found);
+
+/* ------------------------------------------------------------------ keyword chains with bounded gaps
+ * PATTERNS joins keyword records at fixed distances.  Most multi-part signatures leave the distance
+ * open inside bounds: `content:"A"; content:"B"; distance:2; within:40;`, a motif `C-x(2,4)-C-x(3)-H`,
+ * "term A, then term B within n symbols in the same line".  CHAINS is that join.  It is a pure function
+ * of a record set in canonical order, as PATTERNS is, so it runs behind every plan kind, symbol size,
+ * class plan and pending delta alike and has the record passes' calling shape.
+ *
+ * DEFINITION.  Terms and chains: an ACMChainTerm is (keyword_id, gap_min, gap_max), three uint32_t.
+ * Chain c is the terms [chain_ptr[c], chain_ptr[c + 1]) of terms[], in order; chain_ptr has n_chains +
+ * 1 uint64_t entries.  Term j >= 1 says: an occurrence of its keyword begins at least gap_min and at
+ * most gap_max symbols behind the last symbol of the occurrence chosen for term j - 1; gap 0 means
+ * adjacent.  Terms of one chain never overlap.
+ * ACM_GPU_E_ARG: a chain without terms, more than ACM_CHAIN_TERMS_MAX (16) terms, gap_min > gap_max,
+ * gap_max > ACM_CHAIN_GAP_MAX (2^20), a first term whose gaps are not 0, 0, keyword_id >= n_keywords,
+ * a chain_ptr that decreases or does not begin with 0, n_chains >= 2^31, 2^31 terms or more.
+ * CHAINS (R, offsets, C).  R is a record set in canonical order with positions pos_base + index.
+ * Texts are as in PATTERNS: offsets == NULL means one text, empty texts are allowed.  An EMBEDDING of
+ * chain c with m terms is a list of records r_0 .. r_{m-1} of R such that
+ *   r_j has the keyword of term j,
+ *   with s_j = end_j + 1 - length_j: gap_min_j <= s_j - end_{j-1} - 1 <= gap_max_j for j >= 1, and
+ *   one text holds both s_0 and end_{m-1}.
+ * For every pair (c, e) such that an embedding of c with end_{m-1} = e exists the output holds exactly
+ * one ACMRecord (end_pos = pos_base + e, length = e + 1 - S, keyword_id = c), S the greatest s_0 among
+ * those embeddings: the shortest match that ends at e, the way acm_scan_edit reports.  The output is
+ * in the total order end_pos ascending, length descending, chain id ascending.  A chain of one term
+ * gives its keyword's records; a chain whose gaps all have gap_min == gap_max gives exactly PATTERNS of
+ * the equivalent fixed-offset pattern.  The definition permits a dynamic programme over the term
+ * levels -- B_0 (r) = s (r), B_j (r) = the greatest B_{j-1} (r') over the records r' of term j - 1's
+ * keyword that end inside r's window [s - 1 - gap_max_j, s - 1 - gap_min_j] -- with the text test made
+ * once at the end, on S: a smaller s_0 lies in no later text.
+ *
+ * acm_chains_check: the argument checks above, no device; every other entry point runs it.
+ * acm_chains_records: the plain sequential CHAINS on the host, no device, acm_patterns_records'
+ * calling shape: ACM_GPU_E_OVERFLOW with *n_found = the entries needed when out_capacity is too small
+ * (`out` is untouched then), out == NULL with capacity 0 only counts, ACM_GPU_E_ARG with nothing
+ * written for offsets that break the batch contract and for a record outside [pos_base, pos_base +
+ * n_symbols) (its end or its start) or of length 0.
+ *
+ * acm_gpu_chains_create compiles a set once on the host and uploads it to the plan's device
+ * (ACMChains, opaque like ACMPatterns): an index inverted by keyword.  A keyword's postings are
+ * (chain, level j, gap_min, gap_max, the keyword of term j - 1, the index of the posting (chain, j - 1)
+ * among that keyword's postings, a last-term flag), by level, then chain.  n_keywords is
+ * acm_gpu_tally_keywords (plan) at creation; the set stays valid after acm_gpu_plan_update, and a
+ * keyword added later chains nothing.
+ * acm_gpu_chains_info: chains, terms, the most terms of a chain, the widest gap_max, the most
+ * postings of one keyword and the most last-term postings of one keyword.  n x max_last_postings
+ * bounds the output of n records, so a caller can pick an out_capacity that cannot overflow.
+ *
+ * acm_gpu_chains_records_device (dev_chains.h): CHAINS of d_records on the device,
+ * acm_gpu_patterns_records_device's contract: d_n NULL -- n_or_capacity is the number of records; d_n
+ * given -- *d_n is, and n_or_capacity the room of d_records.  n_or_capacity, out_capacity and n_texts
+ * are below 2^31 (and n_or_capacity x max_postings below 2^40); d_out must not overlap d_records
+ * (ACM_GPU_E_ARG).  The call only queues launches on `stream`, with no host round trip; the plan is
+ * used for its device, its grid cap and its error word only.  The check of d_offsets in a launch of
+ * its own; then one LEVEL PASS per term level of the set (max_terms launches, at most 16): every
+ * record has one state slot per posting of its keyword (a fixed stride of max_postings slots), a slot
+ * holds the best start or "none", and pass j fills the slots of level-j postings from the level-(j - 1)
+ * slots the launch before wrote -- one bisection of d_records for the window's first record, then a
+ * walk forward.  A window of up to T records is walked by its own lane; a wider one by the whole wave,
+ * one such lane at a time, 64 records per 16-byte-per-lane load, the maximum reduced across the wave.
+ * T is 64 (ACM_GPU_CHAINS_COOP=<records> in the environment sets another, read at every call: 0
+ * makes every window cooperative, a huge value none; both forms give the same output).  Then a count
+ * pass over the last-term slots (with the text test on S), a 64-bit exclusive sum, a fill pass and
+ * PATTERNS' order pass over every group of equal end_pos.  Tiles of 4,096 records
+ * (ACM_GPU_CHAINS_TILE=<records>: a multiple of 64 from 64 to 1 Mi, read at every call).  No atomics
+ * decide a slot, every slot is written by one lane, and launch geometry and launch count depend on the
+ * set, never on what the records hold.  d_tmp must hold acm_gpu_chains_tmp_bytes (plan, chains,
+ * n_or_capacity, n_texts) bytes (0 for a call that would be refused).
+ *   *d_count <= out_capacity: the count is exact and d_out is complete and in order.
+ *   *d_count > out_capacity: it is the capacity needed, d_out is unspecified, and nothing is written
+ *     outside d_out[0 .. out_capacity).
+ *   *d_n > n_or_capacity (a scan that overflowed): *d_count = 0 and nothing is written.
+ *   d_offsets that break the contract: *d_count = 0, no other output, acm_gpu_plan_status reports
+ *     ACM_GPU_E_INTERNAL.
+ * A record that breaks the contract (a position outside [pos_base, pos_base + n_symbols), a start
+ * below pos_base, a length of 0) is skipped -- it ends no chain and takes part in none -- and
+ * acm_gpu_plan_status reports ACM_GPU_E_INTERNAL (select's rule).  Input that is not in canonical
+ * order gives an unspecified result; nothing is read or written out of bounds.
+ *
+ * acm_gpu_scan_chains_device: acm_gpu_scan_ordered_device (emit_from 0) into `capacity` records
+ * inside d_tmp, then the passes above; d_tmp must hold acm_gpu_scan_chains_tmp_bytes (plan, chains,
+ * capacity, n_symbols, n_texts) bytes.  *d_found receives the scan's count: when it exceeds
+ * `capacity`, *d_count = 0 and *d_found is a capacity that suffices.
+ * acm_gpu_scan_chains_host: the same from host memory, blocking; it creates and destroys the set
+ * itself and sizes the record room from acm_gpu_count_device.  ACM_GPU_E_OVERFLOW means only
+ * "out_capacity is too small, *n_found suffices".  Offsets that break the batch contract are
+ * ACM_GPU_E_ARG.
+ * acm_scan_chains: the call on the machine itself, total over machines exactly as acm_scan_patterns
+ * is (same three paths, same cached plan, same acm_gpu_plan_update; acm_scan_path recorded on success
+ * and on overflow).  ACM_SCAN_PATH_CPU_LOOP runs the caller loop per text on the host, then
+ * acm_chains_records.  A missing device stays an error, never a fallback.
+ *
+ * Out of scope: negative gaps and overlapping terms; unordered proximity (NEAR); symbol classes
+ * inside a gap; all embeddings rather than one record per end; flows, streams and several GPUs;
+ * feeding chain records to SELECT or REPLACE (their contract bounds lengths by the plan's lmax). */
+#define ACM_CHAIN_TERMS_MAX 16u
+#define ACM_CHAIN_GAP_MAX (1u << 20)
+typedef struct {
+  uint32_t keyword_id, gap_min, gap_max;
+} ACMChainTerm;
+typedef struct ACMChains ACMChains;
+typedef struct {
+  uint64_t chains, terms, max_terms, max_gap, max_postings, max_last_postings;
+} ACMChainsInfo;
+int acm_chains_check (const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains, uint64_t n_keywords);
+int acm_chains_records (const ACMRecord *records, uint64_t n, uint64_t n_symbols, uint64_t pos_base,
+                        const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                        const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains, uint64_t n_keywords,
+                        ACMRecord *out, uint64_t out_capacity, uint64_t *n_found);
+int acm_gpu_chains_create (ACMPlan *plan, const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains,
+                           ACMChains **out);
+void acm_gpu_chains_destroy (ACMChains *chains);
+int acm_gpu_chains_info (const ACMChains *chains, ACMChainsInfo *info);
+size_t acm_gpu_chains_tmp_bytes (const ACMPlan *plan, const ACMChains *chains, uint64_t n_or_capacity, uint64_t n_texts);
+int acm_gpu_chains_records_device (ACMPlan *plan, const ACMChains *chains, const ACMRecord *d_records,
+                                   uint64_t n_or_capacity, const uint64_t *d_n /* may be NULL */,
+                                   uint64_t n_symbols, uint64_t pos_base,
+                                   const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                   ACMRecord *d_out, uint64_t out_capacity, uint64_t *d_count,
+                                   void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_scan_chains_tmp_bytes (const ACMPlan *plan, const ACMChains *chains, uint64_t capacity,
+                                      uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_chains_device (ACMPlan *plan, const ACMChains *chains, const void *d_text, uint64_t n_symbols,
+                                uint64_t pos_base, const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                uint64_t capacity, ACMRecord *d_out, uint64_t out_capacity,
+                                uint64_t *d_count, uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_chains_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base,
+                              const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                              const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains,
+                              ACMRecord *out, uint64_t out_capacity, uint64_t *n_found);   /* blocking */
+int acm_scan_chains (ACMachine *machine, const void *text, uint64_t n_symbols,
+                     const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                     const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains,
+                     ACMRecord *out, uint64_t out_capacity, uint64_t *n_found);
 
 /* ------------------------------------------------------------------ several GPUs of one node, one process
  * The reference's model for parallel work is one shared read-only machine and one cursor per worker
