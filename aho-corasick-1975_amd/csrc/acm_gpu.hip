@@ -172,6 +172,9 @@ struct ACMPlan {
   const uint32_t *d_wrows = nullptr;
   const uint32_t *d_dstart = nullptr;
   uint32_t lds_image_bytes = 0;
+  /* dynamic LDS of a launch: info.lds_bytes (what the rows, hotfail, queues and tile counter
+   * occupy) in sticky mode, DENSE_HF_END in continuation mode (the unused gap included) */
+  uint32_t dense_lds_launch = 0;
   uint32_t entry_bytes = 0, streams = ACM_DENSE_S, chunk = 64;
   /* comparator-class plans: the text is mapped to class ids into scratch.d_remap before every scan */
   uint16_t *d_classlut = nullptr;
@@ -883,7 +886,8 @@ bind_common (ACMPlan *p, const PlanBuild &B, const CommonTables &T, unsigned cha
  * of every other state */
 struct DenseTables {
   bool on = false, cont = false; /* cont: continuation mode (2-byte entries), see scan_dense_kernel */
-  uint32_t entry_bytes = 0, rowbytes = 0, queue_bytes = 0, HD = 0, rows_lds = 0, image_bytes = 0;
+  uint32_t entry_bytes = 0, rowbytes = 0, queue_bytes = 0, HD = 0, rows_lds = 0, hf_bytes = 0, image_bytes = 0;
+  uint32_t lds_bytes = 0, lds_launch = 0; /* LDS in use; LDS a launch asks for (ACMPlan::dense_lds_launch) */
   std::vector<uint16_t> hotfail;
   size_t o_dense = 0, o_contdh = 0, o_wrows = 0, o_chain = 0, o_image = 0;
 };
@@ -930,8 +934,10 @@ build_dense (PlanBuild &B, DenseTables &D) {
   const uint32_t n = fi.n_states;
   /* failure-resolved rows for byte alphabets whenever the whole DFA fits comfortably in HBM */
   D.entry_bytes = n <= 32768 ? 2 : 4;
+  /* (the kernel's LDS layout is fixed at compile time for the 160 KiB of gfx950: DENSE_HF_END) */
   D.on = fi.sym_bytes == 1 && fi.n_edges > 0 && (uint64_t)n * fi.width < (1ull << 31) &&
-         (uint64_t)n * fi.width * D.entry_bytes <= (8ull << 30) && fi.lmax >= 1 && fi.lmax - 1 <= 16u * 255;
+         (uint64_t)n * fi.width * D.entry_bytes <= (8ull << 30) && fi.lmax >= 1 && fi.lmax - 1 <= 16u * 255 &&
+         B.lds_cap == DENSE_LDS_CAP;
   D.cont = D.on && D.entry_bytes == 2;
   D.rowbytes = fi.width * D.entry_bytes;
   /* (-DACM_DENSE_DIRECT_PARK: the dense kernel parks its items straight into HBM, no LDS queues) */
@@ -959,15 +965,24 @@ build_dense (PlanBuild &B, DenseTables &D) {
   D.o_contdh = B.reserve (D.cont ? (size_t)n * 2 : 0);
   D.o_wrows = B.reserve (D.cont ? (size_t)n * fi.width * 4 : 0);
   D.o_chain = B.reserve (D.cont ? (size_t)(n - D.HD) * 16 + 16 : 0);
+  /* LDS: [HD rows][16 queues][tile counter] from address 0 and, continuation mode with rowless
+   * states, their hotfail in descending order below DENSE_HF_END (dev_all.h); the image holds the
+   * two parts back to back, each a multiple of 16 bytes */
   D.rows_lds = D.on ? ((D.HD * D.rowbytes + 15) & ~15u) : 0;
-  D.image_bytes = D.on ? ((D.rows_lds + (D.cont ? (n - D.HD) * 2 : 0) + 15) & ~15u) : 0;
+  D.hf_bytes = D.cont ? (((n - D.HD) * 2 + 15) & ~15u) : 0;
+  D.image_bytes = D.rows_lds + D.hf_bytes;
+  D.lds_bytes = D.image_bytes + D.queue_bytes + 16 /* tile counter */;
+  /* (continuation mode always up to DENSE_HF_END: its slow step reads there in every lane) */
+  D.lds_launch = D.cont ? DENSE_HF_END : D.lds_bytes;
   D.o_image = B.reserve (D.image_bytes + 16);
   if (!D.on)
     return ACM_GPU_OK;
+  if (D.rows_lds + D.queue_bytes + 16 + D.hf_bytes > DENSE_HF_END) /* (the budget above rules it out) */
+    return ACM_GPU_E_INELIGIBLE;
   int rc = acm_flat_dense_rows (B.flat, n, D.entry_bytes, B.at<unsigned char> (D.o_dense));
   if (rc)
     return rc;
-  /* LDS image: the first HD rows, then hotfail of the states [HD, n) */
+  /* LDS image: the first HD rows, then hotfail of the states n - 1, n - 2, ..., HD */
   memcpy (B.at<unsigned char> (D.o_image), B.at<unsigned char> (D.o_dense), (size_t)D.HD * D.rowbytes);
   if (D.cont) {
     const uint16_t *r16 = B.at<uint16_t> (D.o_dense);
@@ -977,7 +992,10 @@ build_dense (PlanBuild &B, DenseTables &D) {
     uint16_t *cdh = B.at<uint16_t> (D.o_contdh);
     for (uint32_t s = 0; s < n; s++)
       cdh[s] = (uint16_t)fv.depth[D.hotfail[s]];
-    memcpy (B.at<unsigned char> (D.o_image + D.rows_lds), D.hotfail.data () + D.HD, (size_t)(n - D.HD) * 2);
+    uint16_t *hf = B.at<uint16_t> (D.o_image + D.rows_lds);
+    const uint32_t hf_slots = D.hf_bytes / 2;
+    for (uint32_t i = 0; i < hf_slots; i++) /* slot hf_slots - 1 is state HD; the slots of the rounding come first */
+      hf[i] = hf_slots - 1 - i < n - D.HD ? D.hotfail[D.HD + (hf_slots - 1 - i)] : 0;
     fill_chain_records (fv, n, D, B.at<uint32_t> (D.o_chain));
   }
   return ACM_GPU_OK;
@@ -996,14 +1014,15 @@ bind_dense (ACMPlan *p, const PlanBuild &B, const DenseTables &D, unsigned char 
   p->d_chain = D.cont ? reinterpret_cast<const uint4 *> (b + D.o_chain) : nullptr;
   p->d_wrows = D.cont ? reinterpret_cast<const uint32_t *> (b + D.o_wrows) : nullptr;
   p->lds_image_bytes = D.image_bytes;
+  p->dense_lds_launch = D.lds_launch;
   DenseK &K = p->K;
   K.W = fi.width;
   K.rowbytes = D.rowbytes;
   K.lo = fi.alpha_lo;
   K.span = fi.alpha_span;
   K.HD = D.HD;
-  K.aux_off = D.rows_lds;
-  K.queue_off = D.image_bytes;
+  K.rows_bytes = D.rows_lds;
+  K.queue_off = D.rows_lds;
   K.wub = fi.lmax > 1 ? (fi.lmax - 1 + 15) / 16 : 0;
   K.lmax = fi.lmax;
   K.stream_stride = WAVE * p->chunk;
@@ -1370,7 +1389,7 @@ fill_plan_info (ACMPlan *p, const DenseTables &D) {
   I.block_threads = SPARSE_THREADS;
   switch (p->kind) {
   case PlanKind::Dense:
-    I.lds_bytes = D.image_bytes + D.queue_bytes + 16 /* tile counter */;
+    I.lds_bytes = D.lds_bytes;
     I.block_threads = DENSE_THREADS;
     break;
   case PlanKind::Csr:
@@ -1433,7 +1452,7 @@ set_lds_attributes (const ACMPlan *p) {
     switch (p->kind) {
     case PlanKind::Dense:
       HIP_TRY (hipFuncSetAttribute (dense_kernel (p, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)p->info.lds_bytes));
+                                    (int)p->dense_lds_launch));
       break;
     case PlanKind::Starts:
       HIP_TRY (hipFuncSetAttribute (starts_kernel (p, co != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2105,7 +2124,7 @@ launch_dense (ACMPlan *p, const EmitCtx &E, Launch a, hipStream_t st, hipEvent_t
   ItemBuffer &I = p->items ();
   void *args[] = { &p->K, const_cast<EmitCtx *> (&E), &a, &p->d_dense, &p->d_lds_image, &p->lds_image_bytes, &a.text,
                    &I.items, &I.region_items, &I.fill, &p->d_dstart };
-  HIP_TRY (hipLaunchKernel (dense_kernel (p, COUNT_ONLY), dim3 (grid), dim3 (DENSE_THREADS), args, p->info.lds_bytes, st));
+  HIP_TRY (hipLaunchKernel (dense_kernel (p, COUNT_ONLY), dim3 (grid), dim3 (DENSE_THREADS), args, p->dense_lds_launch, st));
   if (stop)
     HIP_TRY (hipEventRecord (stop, st));
   ExpandTail tail;

@@ -42,6 +42,7 @@ constexpr int DENSE_THREADS = 1024; /* one workgroup per CU, 16 waves */
 #ifndef ACM_DENSE_S
 #define ACM_DENSE_S 2
 #endif
+constexpr int DENSE_C = 64; /* (the kernel's template argument C; the slow step takes the stream stride 64 * C from here) */
 /* a region must hold the items of two 16-step blocks beside a queue's worth: region_make_room */
 constexpr uint32_t DENSE_MIN_REGION_ITEMS = 2 * (16 * ACM_DENSE_S * WAVE + QCAP);
 /* continuation mode: straight-line run-over steps past a chunk before the lanes still inside a
@@ -130,11 +131,23 @@ struct Launch {
 };
 static constexpr uint32_t POOL_CLASSES = 16, POOL_CTR_STRIDE = 64; /* counters 256 B apart */
 
+/* Dense kernel, continuation mode: hotfail (s) of the rowless states s = HD, HD + 1, ... lies in
+ * LDS in DESCENDING order of address and ends at this compile-time address: hotfail (s) is the
+ * 2 bytes at DENSE_HF_END - 2 - 2 * (s - HD), which the slow step forms from HD (in a scalar
+ * register anyway: the fast side compares with it) and a literal, with no other kernel argument.
+ * The rows, the queues and the tile counter lie below, from address 0; the gap between the two
+ * parts is what the budget of build_dense leaves unused.  (The kernel runs on gfx950 only: 160 KiB
+ * per workgroup; 512 bytes less 48 of rounding stay free as before.) */
+constexpr uint32_t DENSE_LDS_CAP = 160 * 1024;
+constexpr uint32_t DENSE_HF_END = DENSE_LDS_CAP - 512 + 48;
+static_assert (DENSE_HF_END % 16 == 0 && DENSE_HF_END <= DENSE_LDS_CAP, "the hotfail part is staged in 16-byte pieces");
+
 /* small uniform constants of the dense kernel */
 struct DenseK {
   uint32_t W, rowbytes, lo, span;
   uint32_t HD; /* states [0, HD): failure-resolved row in LDS */
-  uint32_t aux_off, queue_off, wub, lmax;
+  uint32_t rows_bytes; /* the rows' part of the LDS image (a multiple of 16); the rest goes below DENSE_HF_END */
+  uint32_t queue_off, wub, lmax;
   uint32_t stream_stride; /* 64 * C: distance between the chunks of a lane's consecutive streams */
 };
 

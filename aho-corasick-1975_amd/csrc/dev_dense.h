@@ -47,15 +47,38 @@ struct StepAt {
   int phase;
 };
 
-/* one item per lane with `hit`: through the wave's LDS queue, or (-DACM_DENSE_DIRECT_PARK)
- * straight into the wave's HBM region */
+/* one item per stream q of every lane with hit[q]: through the wave's LDS queue -- one bookkeeping
+ * for all streams (queue_push_streams; -DACM_DENSE_PUSH_EACH: one per stream) --, or
+ * (-DACM_DENSE_DIRECT_PARK) straight into the wave's HBM region */
 template <bool CONT, bool COUNT_ONLY, int S>
 __device__ __forceinline__ void
-dense_park (const EmitCtx &E, uint2 *queue, Walk<S> &w, bool hit, uint32_t pos, uint32_t word, uint32_t lane) {
-  if (DENSE_LDS_QUEUE)
-    queue_push<CONT, COUNT_ONLY, true> (E, queue, w.qn, hit, pos, word, lane, &w.spill);
-  else
-    region_push (&w.spill, hit, pos, word);
+dense_park (const EmitCtx &E, uint2 *queue, Walk<S> &w, const bool (&hit)[S], const uint32_t (&pos)[S],
+            const uint32_t (&word)[S], uint32_t lane) {
+#ifdef ACM_DENSE_PUSH_EACH
+  constexpr bool EACH = true;
+#else
+  constexpr bool EACH = S * WAVE > QCAP; /* (-DACM_DENSE_S=3, 4: a step's items can exceed a queue) */
+#endif
+  if constexpr (DENSE_LDS_QUEUE && !EACH)
+    queue_push_streams<CONT, COUNT_ONLY, S> (E, queue, w.qn, hit, pos, word, lane, &w.spill);
+  else {
+#pragma unroll
+    for (int q = 0; q < S; q++) {
+      if (DENSE_LDS_QUEUE)
+        queue_push<CONT, COUNT_ONLY, true> (E, queue, w.qn, hit[q], pos[q], word[q], lane, &w.spill);
+      else
+        region_push (&w.spill, hit[q], pos[q], word[q]);
+    }
+  }
+}
+
+/* hotfail (ns) from its place below DENSE_HF_END (dev_all.h).  Every lane reads: one with
+ * ns < HD reads the entry of state HD and does not use it, so that no branch stands around the
+ * read and the reads of a lane's streams are issued back to back. */
+__device__ __forceinline__ uint32_t
+lds_hotfail (uint32_t ns, uint32_t HD) {
+  const uint32_t addr = DENSE_HF_END - 2u - 2u * (max (ns, HD) - HD);
+  return *reinterpret_cast<const __attribute__ ((address_space (3))) uint16_t *> (addr);
 }
 
 /* Slow side of one step: the whole wave comes here when some lane looked up an entry >= HD (next
@@ -79,29 +102,31 @@ dense_step_slow (const DenseK &K, const EmitCtx &E, uint32_t emit_from, uint32_t
 #pragma unroll
   for (int q = 0; q < S; q++) {
     ns[q] = e[q] & IDMASK;
-    hf[q] = 0;
-    if (CONT && ns[q] >= K.HD) /* the lane carries on from the nearest state that has a row */
-      hf[q] = *reinterpret_cast<const __attribute__ ((address_space (3))) uint16_t *> (K.aux_off + (ns[q] - K.HD) * 2u);
+    /* a lane with ns >= HD carries on from the nearest state that has a row */
+    hf[q] = CONT ? lds_hotfail (ns[q], K.HD) : 0u;
   }
+  bool hit[S];
+  uint32_t pos[S], word[S];
 #pragma unroll
   for (int q = 0; q < S; q++) {
-    const uint32_t pos = at.pos0 + (uint32_t)q * K.stream_stride;
-    const bool window = pos >= emit_from && pos < emit_end;
+    pos[q] = at.pos0 + (uint32_t)q * (WAVE * DENSE_C);
+    const bool window = pos[q] >= emit_from && pos[q] < emit_end;
     if (CONT) {
       /* run-over: a lane whose state is no deeper than k has nothing of its own left */
       const bool live = at.phase != PH_RUN || ns[q] >= at.live_from;
       const bool out = live && (e[q] & FLAG) && window;
-      const bool deep = live && ns[q] >= K.HD && pos < emit_end;
-      uint32_t word = ns[q] | (deep ? IT_CONT : 0u) | (out ? IT_OUT : 0u);
+      const bool deep = live && ns[q] >= K.HD && pos[q] < emit_end;
+      word[q] = ns[q] | (deep ? IT_CONT : 0u) | (out ? IT_OUT : 0u);
       if (at.phase == PH_RUN)
-        word |= IT_RUN | (at.k << IT_K_SHIFT);
-      dense_park<CONT, COUNT_ONLY, S> (E, queue, w, out | deep, pos, word, lane);
+        word[q] |= IT_RUN | (at.k << IT_K_SHIFT);
+      hit[q] = out | deep;
     } else {
-      const bool out = at.phase == PH_MAIN && (e[q] & FLAG) && window;
-      dense_park<CONT, COUNT_ONLY, S> (E, queue, w, out, pos, ns[q], lane);
+      hit[q] = at.phase == PH_MAIN && (e[q] & FLAG) && window;
+      word[q] = ns[q];
       rowless |= ns[q] >= K.HD;
     }
   }
+  dense_park<CONT, COUNT_ONLY, S> (E, queue, w, hit, pos, word, lane);
   /* the next states go into e[] itself, after its last use above: the caller takes them from
    * there on both sides of its branch, so the looked-up entry and the state can share a register */
 #pragma unroll
@@ -191,13 +216,31 @@ dense_run_steps (const DenseK &K, const EmitCtx &E, uint32_t emit_from, uint32_t
                  uint2 *queue, Walk<S> &w, const uint4 (&post)[S], uint32_t ce0, const uint32_t *__restrict__ dstart, uint32_t lane) {
   if constexpr (k <= DENSE_RUNOVER) {
     if (k < K.lmax) {
-      uint32_t b_[S];
+      /* the last step is skipped when no lane-stream of the wave is still inside a match before
+       * it (state deeper than k - 1): such a stream reports nothing in step k and is no deeper
+       * than k after it, so it parks no walk item either -- the test behind the run-over compares
+       * with depth_start[k + 1], which the stale states fail as well.  One wave-uniform test per
+       * tile; -DACM_DENSE_RUN_ALL builds the kernel without it. */
+      bool go = true;
+#ifndef ACM_DENSE_RUN_ALL
+      if constexpr (k == DENSE_RUNOVER) {
+        const uint32_t live_before = dstart[k];
+        bool live = false;
 #pragma unroll
-      for (int q = 0; q < S; q++)
-        b_[q] = block_byte (post[q], k - 1);
-      const StepAt at = { ce0 + k - 1, k, dstart[k + 1], PH_RUN };
-      dense_step<ENTRY, S, COUNT_ONLY> (K, E, emit_from, emit_end, gdense, queue, w, b_, at, lane);
-      DIAG (w.d_run_steps++;)
+        for (int q = 0; q < S; q++)
+          live |= w.s[q] >= live_before;
+        go = __ballot (live) != 0;
+      }
+#endif
+      if (go) {
+        uint32_t b_[S];
+#pragma unroll
+        for (int q = 0; q < S; q++)
+          b_[q] = block_byte (post[q], k - 1);
+        const StepAt at = { ce0 + k - 1, k, dstart[k + 1], PH_RUN };
+        dense_step<ENTRY, S, COUNT_ONLY> (K, E, emit_from, emit_end, gdense, queue, w, b_, at, lane);
+        DIAG (w.d_run_steps++;)
+      }
       dense_run_steps<ENTRY, S, COUNT_ONLY, k + 1> (K, E, emit_from, emit_end, gdense, queue, w, post, ce0, dstart, lane);
     }
   }
@@ -207,8 +250,9 @@ dense_run_steps (const DenseK &K, const EmitCtx &E, uint32_t emit_from, uint32_t
  * ragged.  16-byte loads are clamped to the last block that holds a valid byte (an aligned
  * 16-byte block never straddles a page, so it cannot fault); what a lane walks beyond the end of
  * the segment is never reported (emit window [emit_from, n)).
- * LDS image: [HD rows][continuation mode: hotfail of every other state, 2 B each][16 queues]
- * [tile counter] (-DACM_DENSE_DIRECT_PARK: no queues). */
+ * LDS: [HD rows][16 queues][tile counter] (-DACM_DENSE_DIRECT_PARK: no queues) from address 0;
+ * continuation mode: hotfail of every other state, 2 B each, in descending order below
+ * DENSE_HF_END (dev_all.h). */
 template <typename ENTRY, int C, int S, bool COUNT_ONLY>
 __global__ __launch_bounds__ (DENSE_THREADS) void
 scan_dense_kernel (DenseK K, EmitCtx E, Launch A, const ENTRY *__restrict__ gdense, const uint4 *__restrict__ lds_image,
@@ -218,12 +262,15 @@ scan_dense_kernel (DenseK K, EmitCtx E, Launch A, const ENTRY *__restrict__ gden
   constexpr uint32_t TILE = WAVE * S * C;
   constexpr int NB = C / 16;
   constexpr bool CONT = EntryTraits<ENTRY>::CONT;
+  static_assert (C == DENSE_C, "the slow step places a lane's streams WAVE * DENSE_C bytes apart");
 
-  /* stage rows (+ hotfail): a straight 16-byte-per-lane copy of the prebuilt image */
+  /* stage rows (+ hotfail): a 16-byte-per-lane copy of the prebuilt image, its rows to address 0
+   * and what follows them to the addresses that end at DENSE_HF_END */
   {
     uint4 *dst = reinterpret_cast<uint4 *> (smem);
+    const uint32_t rows16 = K.rows_bytes / 16, gap16 = (DENSE_HF_END - lds_image_bytes) / 16;
     for (uint32_t i = threadIdx.x; i < lds_image_bytes / 16; i += blockDim.x)
-      dst[i] = lds_image[i];
+      dst[i < rows16 ? i : i + gap16] = lds_image[i];
   }
   /* tiles are handed out dynamically inside the workgroup (its waves do not run at the same
    * pace: a static split left the slowest wave of a block 11% behind the block's mean) */
@@ -380,20 +427,22 @@ scan_dense_kernel (DenseK K, EmitCtx E, Launch A, const ENTRY *__restrict__ gden
       dense_run_steps<ENTRY, S, COUNT_ONLY, 1> (K, E, emit_from, emit_end, gdense, queue, w, post, pos0 + C, dstart, lane);
       if (K.lmax > DENSE_RUNOVER + 1) {
         const uint32_t live_from = dstart[DENSE_RUNOVER + 1];
+        bool walk[S];
+        uint32_t pos[S], word[S];
 #pragma unroll
         for (int q = 0; q < S; q++) {
-          const uint32_t pos = pos0 + q * K.stream_stride + C + DENSE_RUNOVER - 1;
-          const bool walk = w.s[q] >= live_from && pos + 1 < emit_end;
-          dense_park<CONT, COUNT_ONLY, S> (E, queue, w, walk, pos,
-                                           w.s[q] | IT_CONT | IT_RUN | IT_WALK | (DENSE_RUNOVER << IT_K_SHIFT), lane);
+          pos[q] = pos0 + q * (WAVE * C) + C + DENSE_RUNOVER - 1;
+          walk[q] = w.s[q] >= live_from && pos[q] + 1 < emit_end;
+          word[q] = w.s[q] | IT_CONT | IT_RUN | IT_WALK | (DENSE_RUNOVER << IT_K_SHIFT);
         }
+        dense_park<CONT, COUNT_ONLY, S> (E, queue, w, walk, pos, word, lane);
       }
 #pragma unroll
       for (int q = 0; q < S; q++)
         post[q] = load_block (npos0, NB, q);
     }
   }
-  if (DENSE_LDS_QUEUE && w.qn) /* (at most 64 items: the last block's room covers them) */
+  if (DENSE_LDS_QUEUE && w.qn) /* (at most a queue's worth: the last block's room covers them) */
     queue_drain<CONT, COUNT_ONLY, true> (E, queue, w.qn, &w.spill, lane);
   if (lane == 0 && fill)
     fill[wave] = w.spill.fill;

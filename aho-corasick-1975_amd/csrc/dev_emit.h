@@ -264,6 +264,42 @@ queue_push (const EmitCtx &E, uint2 *queue, uint32_t &qn, bool hit, uint32_t pos
   }
 }
 
+/* Dense kernel: the items of all S streams of a step with ONE bookkeeping -- S ballots, one fill,
+ * one test and one drain site (the per-stream form has S of each at every one of the kernel's
+ * unrolled slow steps).  The queue is drained BEFORE the step's items when they would not fit
+ * (up to S * 64 of them: qn stays <= QCAP, where queue_push keeps it <= QCAP - 64), so a kernel
+ * uses this form or queue_push on a queue, not both. */
+template <bool CONT, bool COUNT_ONLY, int S>
+__device__ __forceinline__ void
+queue_push_streams (const EmitCtx &E, uint2 *queue, uint32_t &qn, const bool (&hit)[S], const uint32_t (&pos)[S],
+                    const uint32_t (&word)[S], uint32_t lane, Spill *sp) {
+  static_assert (S * WAVE <= QCAP, "one step's items must fit an empty queue");
+  uint64_t m[S], any = 0;
+#pragma unroll
+  for (int q = 0; q < S; q++) {
+    m[q] = __ballot (hit[q]);
+    any |= m[q];
+  }
+  if (any) {
+    uint32_t add = 0;
+#pragma unroll
+    for (int q = 0; q < S; q++)
+      add += (uint32_t)__popcll (m[q]);
+    if (qn + add > QCAP) {
+      queue_drain<CONT, COUNT_ONLY, true> (E, queue, qn, sp, lane);
+      qn = 0;
+    }
+    uint32_t at = qn;
+#pragma unroll
+    for (int q = 0; q < S; q++) {
+      if (hit[q])
+        queue[at + rank_below (m[q])] = make_uint2 (pos[q], word[q]);
+      at += (uint32_t)__popcll (m[q]);
+    }
+    qn = uniform (at);
+  }
+}
+
 /* Dense kernel: append one item per lane with `hit` straight to the wave's region, one plain
  * 8-byte vector store per hitting lane at fill + its rank in the ballot; the fill stays
  * wave-uniform (scalar registers).  region_make_room has made room for the whole block. */
