@@ -18,6 +18,8 @@ from .binding import (  # noqa: F401
     anchored_records, ACM_ANCHORED_PREFIXES, ACM_ANCHORED_LONGEST, ACM_ANCHORED_WHOLE, ACM_LOOKUP_NONE,
     PatternSet, Patterns, patterns_records,
     ApproxSet, Approx, approx_records, edit_records,
+    TemplateSet, Templates, SymbolClass, ANY, IUPAC, template, hex_template, templates_records,
+    ACM_TEMPLATE_LITERAL, ACM_TEMPLATE_ANY, ACM_TEMPLATE_NEGATED, ACM_TEMPLATE_MAX_RANGES,
     ChainSet, Chains, ChainsInfo, chains_records,
 )
 from . import synth  # noqa: F401

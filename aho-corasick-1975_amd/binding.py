@@ -89,6 +89,17 @@ class ApproxInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("targets", "terms", "seed_keywords", "longest", "max_k", "max_postings")]
 
 
+class TemplatesInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("templates", "terms", "classes", "seed_keywords", "longest", "max_k", "max_postings")]
+
+
+class TemplateSpec(C.Structure):
+    """ACMTemplateSpec: the arrays of a template set, host pointers"""
+    _fields_ = [("spell_data", C.c_void_p), ("spell_off", C.c_void_p), ("cells", C.c_void_p), ("k", C.c_void_p), ("terms", C.c_void_p),
+                ("tgt_ptr", C.c_void_p), ("n_templates", C.c_uint64), ("ranges", C.c_void_p), ("cls_ptr", C.c_void_p), ("cls_flags", C.c_void_p),
+                ("n_classes", C.c_uint64)]
+
+
 _lib = None
 
 # every symbol include/acm.h and include/acm_gpu.h declare
@@ -132,6 +143,9 @@ EXPORTS = [
     "acm_approx_check", "acm_approx_split", "acm_approx_records", "acm_gpu_approx_create", "acm_gpu_approx_destroy", "acm_gpu_approx_info",
     "acm_gpu_approx_tmp_bytes", "acm_gpu_approx_records_device", "acm_gpu_scan_approx_tmp_bytes", "acm_gpu_scan_approx_device",
     "acm_gpu_scan_approx_host", "acm_scan_approx",
+    "acm_templates_check", "acm_templates_split", "acm_templates_records", "acm_gpu_templates_create", "acm_gpu_templates_destroy",
+    "acm_gpu_templates_info", "acm_gpu_templates_tmp_bytes", "acm_gpu_templates_records_device", "acm_gpu_scan_templates_tmp_bytes",
+    "acm_gpu_scan_templates_device", "acm_gpu_scan_templates_host", "acm_scan_templates",
     "acm_edit_check", "acm_edit_records", "acm_gpu_edit_tmp_bytes", "acm_gpu_edit_records_device", "acm_gpu_scan_edit_tmp_bytes",
     "acm_gpu_scan_edit_device", "acm_gpu_scan_edit_host", "acm_scan_edit",
     "acm_chains_check", "acm_chains_records", "acm_gpu_chains_create", "acm_gpu_chains_destroy", "acm_gpu_chains_info",
@@ -457,6 +471,25 @@ def lib():
     L.acm_gpu_scan_approx_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.acm_scan_approx.restype = i32
     L.acm_scan_approx.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
+    L.acm_templates_check.restype = i32
+    L.acm_templates_check.argtypes = [vp, u32, u64]
+    L.acm_templates_split.restype = i32
+    L.acm_templates_split.argtypes = [vp, u64, u32, u32, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_templates_records.restype = i32
+    L.acm_templates_records.argtypes = [vp, u64, vp, u32, u64, u64, vp, u64, vp, u64, vp, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_templates_create.restype = i32
+    L.acm_gpu_templates_create.argtypes = [vp, vp, C.POINTER(vp)]
+    L.acm_gpu_templates_destroy.restype = None
+    L.acm_gpu_templates_destroy.argtypes = [vp]
+    L.acm_gpu_templates_info.restype = i32
+    L.acm_gpu_templates_info.argtypes = [vp, C.POINTER(TemplatesInfo)]
+    for call in ("acm_gpu_%s_tmp_bytes", "acm_gpu_%s_records_device", "acm_gpu_scan_%s_tmp_bytes", "acm_gpu_scan_%s_device"):   # APPROX's signatures
+        getattr(L, call % "templates").restype = getattr(L, call % "approx").restype
+        getattr(L, call % "templates").argtypes = getattr(L, call % "approx").argtypes
+    L.acm_gpu_scan_templates_host.restype = i32
+    L.acm_gpu_scan_templates_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_scan_templates.restype = i32
+    L.acm_scan_templates.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
     for call in ("acm_%s_check", "acm_%s_records", "acm_gpu_%s_tmp_bytes", "acm_gpu_%s_records_device", "acm_gpu_scan_%s_tmp_bytes",
                  "acm_gpu_scan_%s_device", "acm_gpu_scan_%s_host", "acm_scan_%s"):   # the edit calls have the signatures of their APPROX counterparts
         getattr(L, call % "edit").restype = getattr(L, call % "approx").restype
@@ -1144,6 +1177,29 @@ def chains_records(records, chainset, n_symbols, offsets=None, pos_base=0, n_key
     return out[:n.value]
 
 
+class _PieceKeywords:
+    """the pieces of targets as keywords of `machine`: add() inserts a piece the machine does not hold yet (in order of
+    first appearance) and returns the id of the keyword that is the piece"""
+
+    def __init__(self, machine):
+        self.machine = machine
+        self.known = None
+
+    def add(self, piece):
+        machine = self.machine
+        run = np.array(piece, dtype=_SYM_DTYPE[machine.sym_size])
+        before = machine.nb_keywords
+        machine.add_keyword(run)
+        if machine.nb_keywords > before:
+            if self.known is not None:
+                self.known[machine.keyword(before)[0]] = before
+            return before
+        if self.known is None:                                     # held already: the dictionary's spelling of the piece says which
+            self.known = {machine.keyword(i)[0]: i for i in range(machine.nb_keywords)}
+        spelling = [w for at, length, w, _ in machine.match_loop(run) if at == run.size - 1 and length == run.size]
+        return self.known[spelling[0]]
+
+
 class ApproxSet:
     """Targets with a mismatch budget packed to the arrays the C calls take: spell_data (the spellings side by
     side, symbols of `sym_size` bytes), spell_off (uint64, n_targets + 1), k (uint32 per target), terms (uint32
@@ -1182,7 +1238,7 @@ class ApproxSet:
         target shorter than k + 1 symbols.  Returns the ApproxSet (n_keywords = the machine's keywords afterwards)."""
         targets = list(targets)
         ks = [int(x) for x in np.broadcast_to(np.asarray(k), (len(targets),))]
-        known = None
+        pieces = _PieceKeywords(machine)
         spelt, terms = [], []
         for tgt, kk in zip(targets, ks):
             sym = machine._symbols(tgt).reshape(-1)
@@ -1192,19 +1248,7 @@ class ApproxSet:
             for j in range(kk + 1):
                 b, e = C.c_uint64(0), C.c_uint64(0)
                 _check(lib().acm_approx_split(sym.size, kk, j, C.byref(b), C.byref(e)), "acm_approx_split")
-                run = np.array(sym[b.value:e.value], dtype=_SYM_DTYPE[machine.sym_size])
-                before = machine.nb_keywords
-                machine.add_keyword(run)
-                if machine.nb_keywords > before:
-                    kid = before
-                    if known is not None:
-                        known[machine.keyword(kid)[0]] = kid
-                else:                                              # held already: the dictionary's spelling of the piece says which
-                    if known is None:
-                        known = {machine.keyword(i)[0]: i for i in range(machine.nb_keywords)}
-                    spelling = [w for at, length, w, _ in machine.match_loop(run) if at == run.size - 1 and length == run.size]
-                    kid = known[spelling[0]]
-                mine.append((kid, int(b.value), int(e.value - b.value)))
+                mine.append((pieces.add(sym[b.value:e.value]), int(b.value), int(e.value - b.value)))
             spelt.append(sym)
             terms.append(mine)
         aset = cls(spelt, ks, terms, sym_size=machine.sym_size)
@@ -1268,6 +1312,254 @@ def _set_records(name, records, aset, text, offsets, pos_base, n_keywords, out_c
     dist = np.zeros(max(int(out_capacity), 1), dtype=np.uint32)
     _check(call(out, dist, int(out_capacity)), name)
     return out[:n.value], dist[:n.value]
+
+
+ACM_TEMPLATE_LITERAL = 0xFFFFFFFF
+ACM_TEMPLATE_ANY = 0xFFFFFFFE
+ACM_TEMPLATE_NEGATED = 1
+ACM_TEMPLATE_MAX_RANGES = 16
+
+
+class _Any:
+    """the cell that accepts every symbol"""
+
+    def __repr__(self):
+        return "ANY"
+
+
+ANY = _Any()
+
+
+class SymbolClass:
+    """A cell that accepts a set of symbols: `ranges` holds symbols and inclusive (lo, hi) pairs, at most 16 in all;
+    with `negate` the cell accepts every symbol outside them.  Equal classes compare equal and share an id in a
+    TemplateSet."""
+
+    def __init__(self, ranges, negate=False):
+        self.ranges = tuple((int(r), int(r)) if np.isscalar(r) else (int(r[0]), int(r[1])) for r in ranges)
+        self.negate = bool(negate)
+
+    def _key(self):
+        return (self.ranges, self.negate)
+
+    def __eq__(self, other):
+        return isinstance(other, SymbolClass) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "SymbolClass(%r%s)" % (list(self.ranges), ", negate=True" if self.negate else "")
+
+
+class TemplateSet:
+    """Keyword templates packed to the arrays of an ACMTemplateSpec.  `templates`: one sequence of cells per template
+    (or bytes: literals only); a cell is an int (a literal symbol), ANY, or a SymbolClass.  `k`: a scalar or one
+    budget per template; `terms`: one list of (keyword_id, offset, length) per template -- keyword keyword_id,
+    `length` symbols long, is the piece at `offset`, on literal cells.  Symbols have `sym_size` bytes (default 1).
+    from_templates() makes one by the canonical cut."""
+
+    def __init__(self, templates, k, terms, sym_size=None):
+        self.sym_size = int(sym_size) if sym_size is not None else 1
+        dt = _SYM_DTYPE[self.sym_size]
+        self.templates = [list(t) for t in templates]
+        self.n_templates = self.n_targets = len(self.templates)
+        ids, spell, cells = {}, [], []
+        for t in self.templates:
+            for c in t:
+                if c is ANY:
+                    spell.append(0)
+                    cells.append(ACM_TEMPLATE_ANY)
+                elif isinstance(c, SymbolClass):
+                    spell.append(0)
+                    cells.append(ids.setdefault(c, len(ids)))
+                else:
+                    spell.append(int(c))
+                    cells.append(ACM_TEMPLATE_LITERAL)
+        self.classes = list(ids)                                   # (a dict keeps the order of insertion: the ids)
+        self.spell_data = np.array(spell, dtype=dt)
+        self.cells = np.array(cells, dtype=np.uint32)
+        self.spell_off = np.zeros(self.n_templates + 1, np.uint64)
+        self.k = np.ascontiguousarray(np.broadcast_to(np.asarray(k, dtype=np.uint32), (self.n_templates,)))
+        terms = [list(t) for t in terms]
+        assert len(terms) == self.n_templates, "one list of terms per template"
+        self.terms = np.array([tuple(int(x) for x in t) for p in terms for t in p], dtype=np.uint32).reshape(-1, 3)
+        self.tgt_ptr = np.zeros(self.n_templates + 1, np.uint64)
+        if self.templates:
+            np.cumsum([len(t) for t in self.templates], out=self.spell_off[1:])
+            np.cumsum([len(p) for p in terms], out=self.tgt_ptr[1:])
+        self.ranges = np.array([x for c in self.classes for r in c.ranges for x in r], dtype=dt)
+        self.cls_ptr = np.zeros(len(self.classes) + 1, np.uint64)
+        if self.classes:
+            np.cumsum([len(c.ranges) for c in self.classes], out=self.cls_ptr[1:])
+        self.cls_flags = np.array([ACM_TEMPLATE_NEGATED if c.negate else 0 for c in self.classes], dtype=np.uint32)
+        self.n_keywords = int(self.terms[:, 0].max()) + 1 if self.terms.size else 0
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self.spec = TemplateSpec(ptr(self.spell_data), self.spell_off.ctypes.data, ptr(self.cells), ptr(self.k), ptr(self.terms), self.tgt_ptr.ctypes.data,
+                                 self.n_templates, ptr(self.ranges), self.cls_ptr.ctypes.data, ptr(self.cls_flags), len(self.classes))
+
+    @staticmethod
+    def split(cells, k):
+        """acm_templates_split(): the canonical cut of one template, [(offset, length)] of its k + 1 pieces; ValueError
+        when the template has fewer than k + 1 literal cells"""
+        words = np.array([ACM_TEMPLATE_ANY if c is ANY else 0 if isinstance(c, SymbolClass) else ACM_TEMPLATE_LITERAL for c in cells], dtype=np.uint32)
+        pieces = []
+        for j in range(int(k) + 1):
+            o, n = C.c_uint64(0), C.c_uint64(0)
+            if lib().acm_templates_split(words.ctypes.data if words.size else None, words.size, int(k), j, C.byref(o), C.byref(n)):
+                raise ValueError("a template with %d literal cells cannot be cut into %d pieces"
+                                 % (int((words == ACM_TEMPLATE_LITERAL).sum()), int(k) + 1))
+            pieces.append((int(o.value), int(n.value)))
+        return pieces
+
+    @classmethod
+    def from_templates(cls, machine, templates, k=0):
+        """Every template is cut by the canonical cut (acm_templates_split: k + 1 pieces of one length on its literal
+        runs); the distinct pieces `machine` does not hold yet are inserted as keywords in order of first appearance,
+        those it holds keep their ids.  `k`: a scalar or one per template.  ValueError for a template with fewer than
+        k + 1 literal cells.  Returns the TemplateSet (n_keywords = the machine's keywords afterwards)."""
+        templates = [list(t) for t in templates]
+        ks = [int(x) for x in np.broadcast_to(np.asarray(k), (len(templates),))]
+        cuts = [cls.split(t, kk) for t, kk in zip(templates, ks)]   # (every template is cut before the machine grows)
+        pieces = _PieceKeywords(machine)
+        terms = [[(pieces.add(t[o:o + n]), o, n) for o, n in cut] for t, cut in zip(templates, cuts)]
+        tset = cls(templates, ks, terms, sym_size=machine.sym_size)
+        tset.n_keywords = machine.nb_keywords
+        return tset
+
+    def args(self):
+        """(the ACMTemplateSpec by reference,) as the C calls take it"""
+        return (C.byref(self.spec),)
+
+    def check(self, n_keywords):
+        """acm_templates_check(): raises ACMError (ACM_GPU_E_ARG) for a set the calls would refuse"""
+        _check(lib().acm_templates_check(*self.args(), self.sym_size, int(n_keywords)), "acm_templates_check")
+
+
+def templates_records(records, templateset, text, offsets=None, pos_base=0, n_keywords=None, out_capacity=None):
+    """acm_templates_records(): the places where the templates of `templateset` (a TemplateSet) accept the text with
+    at most k failing cells, among those the `records` seed, by the sequential pass on the host; arguments, order
+    and return as approx_records(): (matches, dist) with the template's id as keyword_id."""
+    return _set_records("acm_templates_records", records, templateset, text, offsets, pos_base, n_keywords, out_capacity)
+
+
+_TEMPLATE_ESCAPES = {"n": 10, "t": 9, "r": 13, "f": 12, "v": 11, "0": 0}
+_TEMPLATE_CLASSES = {"d": ((48, 57),), "w": ((48, 57), (65, 90), (95, 95), (97, 122)), "s": ((9, 13), (32, 32))}
+
+
+def template(string):
+    """The cells of a byte template written in a fixed-length subset of regular-expression syntax: literals, `.` (any
+    byte), sets `[a-z0-9_]` and `[^...]`, `\\d` `\\w` `\\s` (ASCII; upper case negates, outside a set), `\\xHH`,
+    `\\n \\t \\r \\f \\v \\0`, escaped punctuation, and `{n}` behind a cell.  Everything of variable length or
+    without a width (`* + ? | ( ) {n,m} ^ $`) raises ValueError.  `string` is a str of code points below 256, or bytes."""
+    s = string.decode("latin-1") if isinstance(string, (bytes, bytearray)) else str(string)
+    if any(ord(c) > 255 for c in s):
+        raise ValueError("a byte template holds code points below 256 only")
+
+    def escape(i, in_set):
+        """the cell (an int, or a tuple of ranges) of the escape whose letter is s[i], and the index behind it"""
+        if i >= len(s):
+            raise ValueError("a template ends inside an escape")
+        c = s[i]
+        if c == "x":
+            if i + 3 > len(s) or any(h not in "0123456789abcdefABCDEF" for h in s[i + 1:i + 3]):
+                raise ValueError("\\x takes two hex digits")
+            return int(s[i + 1:i + 3], 16), i + 3
+        if c in _TEMPLATE_CLASSES:
+            return _TEMPLATE_CLASSES[c], i + 1
+        if c.lower() in _TEMPLATE_CLASSES and not in_set:
+            return SymbolClass(_TEMPLATE_CLASSES[c.lower()], negate=True), i + 1
+        if c in _TEMPLATE_ESCAPES:
+            return _TEMPLATE_ESCAPES[c], i + 1
+        if c.isalnum() or c == "_":
+            raise ValueError("the escape \\%s is not part of the template syntax" % c)
+        return ord(c), i + 1
+
+    cells, i = [], 0
+    while i < len(s):
+        c = s[i]
+        if c in "*+?|()^$":
+            raise ValueError("%r at %d: a template has one cell per symbol" % (c, i))
+        if c == "{":
+            j = s.find("}", i)
+            if j < 0 or not s[i + 1:j].isdigit() or not cells:
+                raise ValueError("a repeat at %d must be {n} behind a cell" % i)
+            n = int(s[i + 1:j])
+            if n == 0:
+                cells.pop()
+            else:
+                cells.extend([cells[-1]] * (n - 1))
+            i = j + 1
+            continue
+        if c == "}" or c == "]":
+            raise ValueError("%r at %d stands alone" % (c, i))
+        if c == ".":
+            cells.append(ANY)
+            i += 1
+        elif c == "\\":
+            cell, i = escape(i + 1, False)
+            cells.append(SymbolClass(cell) if isinstance(cell, tuple) else cell)
+        elif c == "[":
+            i += 1
+            negate = i < len(s) and s[i] == "^"
+            i += negate
+            ranges = []
+            while i < len(s) and s[i] != "]":
+                if s[i] == "[":
+                    raise ValueError("a set inside a set at %d" % i)
+                lo, i = escape(i + 1, True) if s[i] == "\\" else (ord(s[i]), i + 1)
+                if isinstance(lo, tuple):
+                    ranges.extend(lo)
+                    continue
+                hi = lo
+                if i + 1 < len(s) and s[i] == "-" and s[i + 1] != "]":
+                    hi, i = escape(i + 2, True) if s[i + 1] == "\\" else (ord(s[i + 1]), i + 2)
+                    if isinstance(hi, tuple) or hi < lo:
+                        raise ValueError("a range in a set ends below its begin, or on a class")
+                ranges.append((lo, hi))
+            if i >= len(s) or not ranges:
+                raise ValueError("a set without an end, or an empty one")
+            if len(ranges) > ACM_TEMPLATE_MAX_RANGES:
+                raise ValueError("a set of more than %d ranges" % ACM_TEMPLATE_MAX_RANGES)
+            cells.append(SymbolClass(ranges, negate))
+            i += 1
+        else:
+            cells.append(ord(c))
+            i += 1
+    return cells
+
+
+def hex_template(string):
+    """The cells of a hex signature: tokens between blanks; `E2` is a literal byte, `??` ANY, `3?` the 16 bytes 0x30 to
+    0x3F, `?3` the 16 bytes whose low nibble is 3, `[C0-CF]` a byte range.  ValueError for anything else."""
+    hexd = "0123456789abcdefABCDEF"
+    cells = []
+    for tok in str(string).split():
+        if len(tok) == 2 and tok[0] in hexd and tok[1] in hexd:
+            cells.append(int(tok, 16))
+        elif tok == "??":
+            cells.append(ANY)
+        elif len(tok) == 2 and tok[0] in hexd and tok[1] == "?":
+            cells.append(SymbolClass([(int(tok[0], 16) << 4, (int(tok[0], 16) << 4) | 15)]))
+        elif len(tok) == 2 and tok[0] == "?" and tok[1] in hexd:
+            cells.append(SymbolClass([(hi << 4) | int(tok[1], 16) for hi in range(16)]))
+        elif len(tok) == 7 and tok[0] == "[" and tok[3] == "-" and tok[6] == "]" and all(h in hexd for h in tok[1:3] + tok[4:6]) \
+                and int(tok[1:3], 16) <= int(tok[4:6], 16):
+            cells.append(SymbolClass([(int(tok[1:3], 16), int(tok[4:6], 16))]))
+        else:
+            raise ValueError("%r is no token of a hex signature" % tok)
+    return cells
+
+
+def _iupac():
+    codes = {"A": "A", "C": "C", "G": "G", "T": "T", "R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC",
+             "B": "CGT", "D": "AGT", "H": "ACT", "V": "ACG"}
+    cells = {c: ord(m) if len(m) == 1 else SymbolClass([ord(x) for x in m]) for c, m in codes.items()}
+    cells["N"] = ANY
+    return cells
+
+
+IUPAC = _iupac()   # the 15 IUPAC nucleotide codes as cells over upper-case ASCII: [IUPAC[c] for c in "GGNRYCC"] is a template
 
 
 def _delims(delims, sym_size, raw=False):
@@ -1840,8 +2132,13 @@ class Machine:
         `text`, or in every text of the buffer when `offsets` cuts it; arguments as scan_approx()."""
         return self._scan_set("acm_scan_edit", text, approxset, offsets, out_capacity)
 
+    def scan_templates(self, text, templateset, offsets=None, out_capacity=None):
+        """acm_scan_templates(): (matches, dist) of the templates of `templateset` (a TemplateSet, see
+        templates_records) in `text`, or in every text of the buffer when `offsets` cuts it; arguments as scan_approx()."""
+        return self._scan_set("acm_scan_templates", text, templateset, offsets, out_capacity)
+
     def _scan_set(self, name, text, approxset, offsets, out_capacity):
-        """what scan_approx() and scan_edit() share: the machine-level C call `name`"""
+        """what scan_approx(), scan_edit() and scan_templates() share: the machine-level C call `name`"""
         t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
         off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
         cap = int(out_capacity) if out_capacity is not None else 1024
@@ -2063,6 +2360,22 @@ class Approx:
             self.close()
         except Exception:
             pass
+
+
+class Templates(Approx):
+    """A template set on a plan's device (ACMTemplates): Plan.templates_create() makes one."""
+
+    def info(self):
+        """acm_gpu_templates_info(): templates, terms, classes, seed_keywords, longest, max_k and max_postings as a
+        dict; n records give at most n * max_postings matches."""
+        i = TemplatesInfo()
+        _check(lib().acm_gpu_templates_info(self.h, C.byref(i)), "acm_gpu_templates_info")
+        return {n: int(getattr(i, n)) for n, _ in TemplatesInfo._fields_}
+
+    def close(self):
+        if self.h:
+            lib().acm_gpu_templates_destroy(self.h)
+            self.h = None
 
 
 class Plan:
@@ -2824,9 +3137,35 @@ class Plan:
         _check(lib().acm_gpu_approx_create(self.h, *approxset.args(), C.byref(h)), "acm_gpu_approx_create")
         return Approx(h, approxset.n_targets)
 
+    def templates_create(self, templateset):
+        """acm_gpu_templates_create(): `templateset` (a TemplateSet) compiled and uploaded to this plan's device.
+        Returns a Templates; it stays valid across update().  A plan over comparator classes refuses
+        (ACM_GPU_E_INELIGIBLE)."""
+        h = C.c_void_p()
+        _check(lib().acm_gpu_templates_create(self.h, *templateset.args(), C.byref(h)), "acm_gpu_templates_create")
+        return Templates(h, templateset.n_templates)
+
     def _approx_handle(self, approx):
-        """(an Approx, whether this call made it) of an Approx or an ApproxSet"""
-        return (approx, False) if isinstance(approx, Approx) else (self.approx_create(approx), True)
+        """(an Approx or a Templates, whether this call made it) of one of the two, of an ApproxSet or of a TemplateSet"""
+        if isinstance(approx, Approx):
+            return approx, False
+        return (self.templates_create(approx) if isinstance(approx, TemplateSet) else self.approx_create(approx)), True
+
+    def templates_records(self, records, n, templates, text, n_symbols=None, offsets=None, pos_base=0, count=None, out=None, dist=None,
+                          out_capacity=None, out_count=None):
+        """acm_gpu_templates_records_device(): the matches of the templates of `templates` (a Templates from
+        templates_create(), or a TemplateSet compiled for this call) that records[:n] seed; arguments and return as
+        approx_records()."""
+        return self._set_records("templates", records, n, templates, text, n_symbols, offsets, pos_base, count, out, dist, out_capacity, out_count)
+
+    def scan_templates(self, text, templates, offsets=None, n_symbols=None, pos_base=0, capacity=None, out=None, dist=None, out_capacity=None, tmp=None):
+        """acm_gpu_scan_templates_device(): the ordered scan of a device tensor and the templates of `templates` verified
+        around its records; arguments and return as scan_approx()."""
+        return self._scan_set("templates", text, templates, offsets, n_symbols, pos_base, capacity, out, dist, out_capacity, tmp)
+
+    def scan_templates_host(self, text, templateset, offsets=None, pos_base=0, out_capacity=None):
+        """acm_gpu_scan_templates_host(): numpy in, (matches, dist) out; arguments as scan_approx_host()."""
+        return self._scan_set_host("acm_gpu_scan_templates_host", text, templateset, offsets, pos_base, out_capacity)
 
     def approx_records(self, records, n, approx, text, n_symbols=None, offsets=None, pos_base=0, count=None, out=None, dist=None, out_capacity=None,
                        out_count=None):

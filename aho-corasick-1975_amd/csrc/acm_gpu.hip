@@ -6554,6 +6554,16 @@ struct ACMApprox {
   uint64_t *d_spell_off = nullptr;
   ApproxTerm *d_terms = nullptr;
   void *d_spell = nullptr;
+  /* a template set (dev_templates.h): the cells and the compiled classes; d_cells stays NULL in a target set */
+  uint64_t n_classes = 0;
+  uint32_t *d_cells = nullptr, *d_cls_bitmap = nullptr, *d_cls_flags = nullptr;
+  uint64_t *d_cls_ptr = nullptr;
+  void *d_cls_ranges = nullptr;
+};
+
+/* a template set is a target set whose positions are cells */
+struct ACMTemplates {
+  ACMApprox *set = nullptr;
 };
 
 namespace {
@@ -6625,31 +6635,31 @@ scan_approx_carve (Carve &c, const ACMPlan *plan, size_t passes_bytes, uint64_t 
   return R;
 }
 
-template <typename T>
+template <typename T, bool CELLS>
 int
 approx_passes (ACMPlan *plan, ApproxK &K, const ApproxRoom &L, uint64_t n, uint64_t n_texts, hipStream_t st) {
   /* 1. */
   if (K.offsets) /* one size, whatever the number of texts */
     HIP_TRY (launch (approx_check_kernel, capped_grid (plan, (n_texts + APPROX_THREADS - 1) / APPROX_THREADS), dim3 (APPROX_THREADS), 0, st, K));
   /* 2. */
-  HIP_TRY (launch (approx_count_kernel<T>, capped_grid (plan, K.n_tiles), dim3 (APPROX_THREADS), 0, st, K));
+  HIP_TRY (launch (approx_count_kernel<T, CELLS>, capped_grid (plan, K.n_tiles), dim3 (APPROX_THREADS), 0, st, K));
   /* 3. */
   HIP_TRY (exclusive_sum (L.cub, L.count, L.first, n + 1, st));
   /* 4. */
-  HIP_TRY (launch (approx_fill_kernel<T>, capped_grid (plan, K.n_tiles), dim3 (APPROX_THREADS), 0, st, K));
+  HIP_TRY (launch (approx_fill_kernel<T, CELLS>, capped_grid (plan, K.n_tiles), dim3 (APPROX_THREADS), 0, st, K));
   return ACM_GPU_OK;
 }
 
 /* ---- keywords within edit distance k (include/acm_gpu.h, dev_edit.h).  The set is ACMApprox and the passes are the ones above; the
  * count and fill kernels are dev_edit.h's, with the group width fixed per call from the set's max_k.  The metric is a property of the
  * call, so the entry points of both metrics are one body each (set_records_device, scan_set_device, scan_set_host). */
-enum class Metric { Mismatches, Edits };
+enum class Metric { Mismatches, Edits, Templates }; /* Templates: mismatches of cells, over a template set (dev_templates.h) */
 
 /* whether the calls of a metric take this plan and set */
 bool
 set_usable (Metric metric, const ACMPlan *plan, const ACMApprox *approx) {
   return plan && approx && approx->device == plan->device && approx->sym_bytes == plan->text_sym_bytes && !plan->class_sym_bytes &&
-         (metric == Metric::Mismatches || approx->edit_fit);
+         (metric == Metric::Templates) == (approx->d_cells != nullptr) && (metric != Metric::Edits || approx->edit_fit);
 }
 
 /* approx_carve; the edit passes have a tile of their own */
@@ -6659,6 +6669,11 @@ set_carve (Metric metric, Carve &c, uint64_t capacity, uint64_t out_capacity, Ap
   if (metric == Metric::Edits) {
     /* ACM_GPU_EDIT_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
     K.tile = tunable ("ACM_GPU_EDIT_TILE", EDIT_TILE_DEFAULT, EDIT_TILE_MIN, EDIT_TILE_MAX, Tune::MultWave);
+    K.n_tiles = (capacity + K.tile - 1) / K.tile;
+  }
+  if (metric == Metric::Templates) {
+    /* ACM_GPU_TEMPLATES_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
+    K.tile = tunable ("ACM_GPU_TEMPLATES_TILE", APPROX_TILE_DEFAULT, APPROX_TILE_MIN, APPROX_TILE_MAX, Tune::MultWave);
     K.n_tiles = (capacity + K.tile - 1) / K.tile;
   }
   return R;
@@ -6690,7 +6705,9 @@ template <typename T>
 int
 set_passes (Metric metric, uint64_t max_k, ACMPlan *plan, ApproxK &K, const ApproxRoom &L, uint64_t n, uint64_t n_texts, hipStream_t st) {
   if (metric == Metric::Mismatches)
-    return approx_passes<T> (plan, K, L, n, n_texts, st);
+    return approx_passes<T, false> (plan, K, L, n, n_texts, st);
+  if (metric == Metric::Templates)
+    return approx_passes<T, true> (plan, K, L, n, n_texts, st);
   if (max_k <= 3)
     return edit_passes<T, 16> (plan, K, L, n, n_texts, st);
   if (max_k <= 7)
@@ -6699,9 +6716,41 @@ set_passes (Metric metric, uint64_t max_k, ACMPlan *plan, ApproxK &K, const Appr
 }
 } // namespace
 
-extern "C" int
-acm_gpu_approx_create (ACMPlan *plan, const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
-                       const uint64_t *tgt_ptr, uint64_t n_targets, ACMApprox **out) {
+namespace {
+/* the classes of a template set as the device reads them (dev_templates.h): bitmaps for 1-byte symbols, else pointers, ranges, flags */
+struct ClassTables {
+  std::vector<uint32_t> bitmap, flags;
+  std::vector<uint64_t> ptr;
+};
+ClassTables
+compile_classes (const ACMTemplateSpec *T, uint32_t sb) {
+  ClassTables C;
+  if (sb == 1) {
+    const unsigned char *ranges = static_cast<const unsigned char *> (T->ranges);
+    C.bitmap.assign ((size_t)T->n_classes * 8, 0);
+    for (uint64_t c = 0; c < T->n_classes; c++) {
+      uint32_t *words = &C.bitmap[(size_t)c * 8];
+      for (uint64_t r = T->cls_ptr[c]; r < T->cls_ptr[c + 1]; r++)
+        for (uint32_t x = ranges[2 * r]; x <= ranges[2 * r + 1]; x++)
+          words[x >> 5] |= 1u << (x & 31);
+      if (T->cls_flags[c] & ACM_TEMPLATE_NEGATED)
+        for (uint32_t i = 0; i < 8; i++)
+          words[i] = ~words[i];
+    }
+  } else {
+    C.ptr.assign (1, 0);
+    if (T->n_classes) {
+      C.ptr.assign (T->cls_ptr, T->cls_ptr + T->n_classes + 1);
+      C.flags.assign (T->cls_flags, T->cls_flags + T->n_classes);
+    }
+  }
+  return C;
+}
+
+/* acm_gpu_approx_create; with `tpl`, whose arrays the other arguments are, a template set (the caller has run acm_templates_check) */
+int
+set_create (ACMPlan *plan, const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
+            uint64_t n_targets, const ACMTemplateSpec *tpl, ACMApprox **out) {
   if (!plan || !out || (n_targets && !spell_data))
     return ACM_GPU_E_ARG;
   const uint64_t nk = plan->covered_keywords;
@@ -6767,8 +6816,32 @@ acm_gpu_approx_create (ACMPlan *plan, const void *spell_data, const uint64_t *sp
   const size_t o_post_ptr = blob_reserve (cur, post_ptr.size () * 4), o_post = blob_reserve (cur, post_dev.size () * sizeof (uint4)),
                o_target = blob_reserve (cur, target.size () * sizeof (uint4)), o_first = blob_reserve (cur, first_symbol.size () * 8),
                o_terms = blob_reserve (cur, term_dev.size () * sizeof (ApproxTerm)), o_spell = blob_reserve (cur, spell_bytes + 16);
+  /* a template set: the cells, and the classes in the form the symbol size reads (every array with room, so that none is NULL) */
+  ClassTables classes;
+  size_t o_cells = 0, o_bitmap = 0, o_cls_ptr = 0, o_ranges = 0, o_flags = 0, range_bytes = 0;
+  if (tpl) {
+    classes = compile_classes (tpl, sb);
+    range_bytes = sb == 1 ? 0 : (size_t)classes.ptr.back () * 2 * sb;
+    o_cells = blob_reserve (cur, (size_t)n_spell * 4 + 16);
+    o_bitmap = blob_reserve (cur, classes.bitmap.size () * 4 + 16);
+    o_cls_ptr = blob_reserve (cur, classes.ptr.size () * 8 + 16);
+    o_ranges = blob_reserve (cur, range_bytes + 16);
+    o_flags = blob_reserve (cur, classes.flags.size () * 4 + 16);
+  }
   bool ok = hipMalloc (&A->blob, cur) == hipSuccess;
   unsigned char *b = static_cast<unsigned char *> (A->blob);
+  if (ok && tpl) {
+    const auto up = [&] (size_t at, const void *from, size_t bytes) { return !bytes || hipMemcpy (b + at, from, bytes, hipMemcpyHostToDevice) == hipSuccess; };
+    ok = up (o_cells, tpl->cells, (size_t)n_spell * 4) && up (o_bitmap, classes.bitmap.data (), classes.bitmap.size () * 4) &&
+         up (o_cls_ptr, classes.ptr.data (), classes.ptr.size () * 8) && up (o_ranges, tpl->ranges, range_bytes) &&
+         up (o_flags, classes.flags.data (), classes.flags.size () * 4);
+    A->n_classes = tpl->n_classes;
+    A->d_cells = reinterpret_cast<uint32_t *> (b + o_cells);
+    A->d_cls_bitmap = reinterpret_cast<uint32_t *> (b + o_bitmap);
+    A->d_cls_ptr = reinterpret_cast<uint64_t *> (b + o_cls_ptr);
+    A->d_cls_ranges = b + o_ranges;
+    A->d_cls_flags = reinterpret_cast<uint32_t *> (b + o_flags);
+  }
   ok = ok && hipMemcpy (b + o_post_ptr, post_ptr.data (), post_ptr.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy (b + o_post, post_dev.data (), post_dev.size () * sizeof (uint4), hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy (b + o_target, target.data (), target.size () * sizeof (uint4), hipMemcpyHostToDevice) == hipSuccess &&
@@ -6786,6 +6859,45 @@ acm_gpu_approx_create (ACMPlan *plan, const void *spell_data, const uint64_t *sp
   A->d_terms = reinterpret_cast<ApproxTerm *> (b + o_terms);
   A->d_spell = b + o_spell;
   *out = A;
+  return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_approx_create (ACMPlan *plan, const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
+                       const uint64_t *tgt_ptr, uint64_t n_targets, ACMApprox **out) {
+  return set_create (plan, spell_data, spell_off, k, terms, tgt_ptr, n_targets, nullptr, out);
+}
+
+extern "C" int
+acm_gpu_templates_create (ACMPlan *plan, const ACMTemplateSpec *spec, ACMTemplates **out) {
+  if (!plan || !out || acm_templates_check (spec, plan->class_sym_bytes ? plan->class_sym_bytes : plan->text_sym_bytes, plan->covered_keywords))
+    return ACM_GPU_E_ARG;
+  ACMTemplates *made = new (std::nothrow) ACMTemplates ();
+  if (!made)
+    return ACM_GPU_E_NOMEM;
+  if (const int rc = set_create (plan, spec->spell_data, spec->spell_off, spec->k, spec->terms, spec->tgt_ptr, spec->n_templates, spec, &made->set)) {
+    delete made;
+    return rc;
+  }
+  *out = made;
+  return ACM_GPU_OK;
+}
+
+extern "C" void
+acm_gpu_templates_destroy (ACMTemplates *templates) {
+  if (!templates)
+    return;
+  acm_gpu_approx_destroy (templates->set);
+  delete templates;
+}
+
+extern "C" int
+acm_gpu_templates_info (const ACMTemplates *templates, ACMTemplatesInfo *info) {
+  if (!templates || !info)
+    return ACM_GPU_E_ARG;
+  const ACMApprox *set = templates->set;
+  *info = ACMTemplatesInfo{ set->n_targets, set->n_terms, set->n_classes, set->seed_keywords, set->longest, set->max_k, set->max_postings };
   return ACM_GPU_OK;
 }
 
@@ -6849,6 +6961,11 @@ set_records_device (Metric metric, ACMPlan *plan, const ACMApprox *approx, const
   K.spell_off = approx->d_spell_off;
   K.terms = approx->d_terms;
   K.spell = approx->d_spell;
+  K.cells = approx->d_cells;
+  K.cls_bitmap = approx->d_cls_bitmap;
+  K.cls_ptr = approx->d_cls_ptr;
+  K.cls_ranges = approx->d_cls_ranges;
+  K.cls_flags = approx->d_cls_flags;
   K.n_keywords = approx->n_keywords;
   K.longest = (uint32_t)longest;
   K.tgt_bits = bits_of (approx->n_targets ? approx->n_targets - 1 : 0);
@@ -6927,14 +7044,16 @@ scan_set_device (Metric metric, ACMPlan *plan, const ACMApprox *approx, const vo
 int
 scan_set_host (Metric metric, ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
                const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
-               uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+               uint64_t n_targets, const ACMTemplateSpec *tpl, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
   if (!plan || !n_found || out_capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
       !optional_offsets_ok (offsets, n_texts, n_symbols) || (offsets && n_texts == 0 && n_symbols))
     return ACM_GPU_E_ARG;
   if (metric == Metric::Edits && acm_edit_check (spell_off, k, terms, tgt_ptr, n_targets, plan->covered_keywords)) /* (the set would be made, and refused) */
     return ACM_GPU_E_ARG;
+  if (tpl && acm_templates_check (tpl, plan->class_sym_bytes ? plan->class_sym_bytes : plan->text_sym_bytes, plan->covered_keywords))
+    return ACM_GPU_E_ARG;
   ACMApprox *made = nullptr;
-  if (const int rc = acm_gpu_approx_create (plan, spell_data, spell_off, k, terms, tgt_ptr, n_targets, &made))
+  if (const int rc = set_create (plan, spell_data, spell_off, k, terms, tgt_ptr, n_targets, tpl, &made))
     return rc;
   std::unique_ptr<ACMApprox, void (*) (ACMApprox *)> approx (made, acm_gpu_approx_destroy);
   HIP_TRY (hipSetDevice (plan->device));
@@ -6988,6 +7107,45 @@ acm_gpu_edit_records_device (ACMPlan *plan, const ACMApprox *approx, const ACMRe
                              d_count, d_tmp, tmp_bytes, stream);
 }
 
+/* TEMPLATES: the entry points of APPROX over a template set */
+extern "C" size_t
+acm_gpu_templates_tmp_bytes (const ACMPlan *plan, const ACMTemplates *templates, uint64_t n_or_capacity, uint64_t out_capacity, uint64_t n_texts) {
+  (void)n_texts;
+  return templates ? set_tmp_bytes (Metric::Templates, plan, templates->set, n_or_capacity, out_capacity) : 0;
+}
+
+extern "C" int
+acm_gpu_templates_records_device (ACMPlan *plan, const ACMTemplates *templates, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n,
+                                  const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out,
+                                  uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  return set_records_device (Metric::Templates, plan, templates ? templates->set : nullptr, d_records, n, d_n, d_text, n_symbols, pos_base, d_offsets, n_texts,
+                             d_out, d_dist, out_capacity, d_count, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" size_t
+acm_gpu_scan_templates_tmp_bytes (const ACMPlan *plan, const ACMTemplates *templates, uint64_t capacity, uint64_t out_capacity, uint64_t n_symbols,
+                                  uint64_t n_texts) {
+  (void)n_texts;
+  return templates ? scan_set_tmp_bytes (Metric::Templates, plan, templates->set, capacity, out_capacity, n_symbols) : 0;
+}
+
+extern "C" int
+acm_gpu_scan_templates_device (ACMPlan *plan, const ACMTemplates *templates, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                               const uint64_t *d_offsets, uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity,
+                               uint64_t *d_count, uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
+  return scan_set_device (Metric::Templates, plan, templates ? templates->set : nullptr, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out,
+                          d_dist, out_capacity, d_count, d_found, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_templates_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                             const ACMTemplateSpec *spec, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  if (!spec)
+    return ACM_GPU_E_ARG;
+  return scan_set_host (Metric::Templates, plan, text, n_symbols, pos_base, offsets, n_texts, spec->spell_data, spec->spell_off, spec->k, spec->terms,
+                        spec->tgt_ptr, spec->n_templates, spec, out, dist, out_capacity, n_found);
+}
+
 extern "C" size_t
 acm_gpu_scan_approx_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t capacity, uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts) {
   (void)n_texts;
@@ -7020,7 +7178,7 @@ extern "C" int
 acm_gpu_scan_approx_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
                           const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
                           uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
-  return scan_set_host (Metric::Mismatches, plan, text, n_symbols, pos_base, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist,
+  return scan_set_host (Metric::Mismatches, plan, text, n_symbols, pos_base, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, nullptr, out, dist,
                         out_capacity, n_found);
 }
 
@@ -7028,7 +7186,7 @@ extern "C" int
 acm_gpu_scan_edit_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
                         const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
                         uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
-  return scan_set_host (Metric::Edits, plan, text, n_symbols, pos_base, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist,
+  return scan_set_host (Metric::Edits, plan, text, n_symbols, pos_base, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, nullptr, out, dist,
                         out_capacity, n_found);
 }
 
@@ -7934,8 +8092,8 @@ acm_scan_chains (ACMachine *machine, const void *text, uint64_t n_symbols, const
 namespace {
 int
 scan_set (Metric metric, ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const void *spell_data,
-          const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out,
-          uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+          const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets,
+          const ACMTemplateSpec *tpl, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
   if (!machine || !n_found || (n_symbols && !text) || (out_capacity && !out) || !optional_offsets_ok (offsets, n_texts, n_symbols))
     return ACM_GPU_E_ARG;
   const bool edits = metric == Metric::Edits;
@@ -7945,9 +8103,12 @@ scan_set (Metric metric, ACMachine *machine, const void *text, uint64_t n_symbol
   uint32_t sb = R.said;
   if (R.path == ACM_SCAN_PATH_GPU && acm_internal_symbol_bytes (machine, &sb))
     return ACM_GPU_E_INTERNAL;
-  if ((edits ? acm_internal_edit_machine_check : acm_internal_approx_machine_check) (machine, sb, spell_data, spell_off, k, terms, tgt_ptr, n_targets))
+  if (tpl ? acm_internal_templates_machine_check (machine, sb, tpl)
+          : (edits ? acm_internal_edit_machine_check : acm_internal_approx_machine_check) (machine, sb, spell_data, spell_off, k, terms, tgt_ptr, n_targets))
     return ACM_GPU_E_ARG;
   const auto host_loop = [&] (uint32_t said) {
+    if (tpl)
+      return acm_internal_cpu_scan_templates (machine, text, n_symbols, said, offsets, n_texts, tpl, out, dist, out_capacity, n_found);
     return (edits ? acm_internal_cpu_scan_edit : acm_internal_cpu_scan_approx) (machine, text, n_symbols, said, offsets, n_texts, spell_data, spell_off, k,
                                                                                 terms, tgt_ptr, n_targets, out, dist, out_capacity, n_found);
   };
@@ -7960,8 +8121,8 @@ scan_set (Metric metric, ACMachine *machine, const void *text, uint64_t n_symbol
     return rc;
   }
   return routed_scan (machine, RecordPath::OnSuccessOrOverflow, host_loop, [&] (ACMPlan *plan) {
-    return scan_set_host (metric, plan, text, n_symbols, 0, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist, out_capacity,
-                          n_found);
+    return scan_set_host (metric, plan, text, n_symbols, 0, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, tpl, out, dist,
+                          out_capacity, n_found);
   });
 }
 } // namespace
@@ -7970,16 +8131,25 @@ extern "C" int
 acm_scan_approx (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const void *spell_data,
                  const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out,
                  uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
-  return scan_set (Metric::Mismatches, machine, text, n_symbols, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist, out_capacity,
-                   n_found);
+  return scan_set (Metric::Mismatches, machine, text, n_symbols, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, nullptr, out, dist,
+                   out_capacity, n_found);
 }
 
 extern "C" int
 acm_scan_edit (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const void *spell_data,
                const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out,
                uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
-  return scan_set (Metric::Edits, machine, text, n_symbols, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, out, dist, out_capacity,
-                   n_found);
+  return scan_set (Metric::Edits, machine, text, n_symbols, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, nullptr, out, dist,
+                   out_capacity, n_found);
+}
+
+extern "C" int
+acm_scan_templates (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const ACMTemplateSpec *spec,
+                    ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  if (!spec)
+    return ACM_GPU_E_ARG;
+  return scan_set (Metric::Templates, machine, text, n_symbols, offsets, n_texts, spec->spell_data, spec->spell_off, spec->k, spec->terms, spec->tgt_ptr,
+                   spec->n_templates, spec, out, dist, out_capacity, n_found);
 }
 
 /* acm_scan continued from a cursor (include/acm_gpu.h): the reference's own `const ACState *`, in

@@ -2104,7 +2104,17 @@ struct apx_set {
   uint32_t sym_bytes;
   CMP_TYPE cmp; /* NULL: symbols compare bitwise */
   void *cmp_arg;
+  const ACMTemplateSpec *tpl; /* TEMPLATES: the cells and the classes; NULL: every position is its spelling's symbol */
 };
+
+/* whether class c of a template set holds symbol x */
+static int
+tpl_class_has (const ACMTemplateSpec *T, uint32_t c, uint64_t x, uint32_t sb) {
+  int in = 0;
+  for (uint64_t r = T->cls_ptr[c]; !in && r < T->cls_ptr[c + 1]; r++)
+    in = x >= words_symbol (T->ranges, 2 * r, sb) && x <= words_symbol (T->ranges, 2 * r + 1, sb);
+  return (T->cls_flags[c] & ACM_TEMPLATE_NEGATED) ? !in : in;
+}
 
 /* whether target q->target matches with its term q->j seeded by record r (the term's keyword is the record's); *d = the mismatches */
 static int
@@ -2138,9 +2148,16 @@ apx_matches (const ACMRecord *records, uint64_t n, const ACMRecord *r, const str
   }
   const unsigned char *a = text + S * A->sym_bytes, *b = A->spell + A->spell_off[q->target] * A->sym_bytes;
   uint32_t miss = 0;
+  const uint32_t *cells = A->tpl ? A->tpl->cells + A->spell_off[q->target] : NULL;
   for (uint64_t i = 0; i < L; i++) {
-    const int same = A->cmp ? A->cmp (a + i * A->sym_bytes, b + i * A->sym_bytes, A->cmp_arg) == 0
-                            : memcmp (a + i * A->sym_bytes, b + i * A->sym_bytes, A->sym_bytes) == 0;
+    int same;
+    if (cells && cells[i] == ACM_TEMPLATE_ANY)
+      same = 1;
+    else if (cells && cells[i] != ACM_TEMPLATE_LITERAL) /* (a class cell: by value, whatever the comparator) */
+      same = tpl_class_has (A->tpl, cells[i], words_symbol (a, i, A->sym_bytes), A->sym_bytes);
+    else
+      same = A->cmp ? A->cmp (a + i * A->sym_bytes, b + i * A->sym_bytes, A->cmp_arg) == 0
+                    : memcmp (a + i * A->sym_bytes, b + i * A->sym_bytes, A->sym_bytes) == 0;
     if (!same && ++miss > A->k[q->target])
       return 0;
   }
@@ -2229,7 +2246,7 @@ acm_approx_records (const ACMRecord *records, uint64_t n, const void *text, uint
                     const uint64_t *offsets, uint64_t n_texts, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
                     const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, uint64_t n_keywords, ACMRecord *out, uint32_t *dist,
                     uint64_t out_capacity, uint64_t *n_found) {
-  const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, NULL, NULL };
+  const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, NULL, NULL, NULL };
   return approx_core (records, n, text, n_symbols, pos_base, offsets, n_texts, &A, n_targets, n_keywords, out, dist, out_capacity, n_found);
 }
 
@@ -2271,8 +2288,107 @@ acm_internal_cpu_scan_approx (ACMachine *m, const void *text, uint64_t n_symbols
   uint64_t found = 0;
   int rc = cpu_scan_grown (m, text, n_symbols, offsets, n_texts, sym_bytes, NULL, &records, &found);
   if (!rc) {
-    const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, m->cmp, m->cmp_arg };
+    const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, m->cmp, m->cmp_arg, NULL };
     rc = approx_core (records, found, text, n_symbols, 0, offsets, n_texts, &A, n_targets, acm_nb_keywords (m), out, dist, out_capacity, n_found);
+  }
+  free (records);
+  return rc;
+}
+
+/* ---- keyword templates with symbol classes (include/acm_gpu.h): the argument checks, the canonical cut, the plain sequential TEMPLATES
+ * and acm_scan_templates' host path.  The set, the postings, the hits and the pass are APPROX's; apx_matches takes the cells. */
+int
+acm_templates_check (const ACMTemplateSpec *T, uint32_t sym_bytes, uint64_t n_keywords) {
+  if (!T || (sym_bytes != 1 && sym_bytes != 2 && sym_bytes != 4 && sym_bytes != 8) || T->n_classes >= ACM_TEMPLATE_ANY ||
+      (T->n_classes && (!T->cls_ptr || !T->cls_flags)) || (T->cls_ptr && T->cls_ptr[0] != 0))
+    return ACM_GPU_E_ARG;
+  for (uint64_t c = 0; c < T->n_classes; c++) {
+    if (T->cls_ptr[c] > T->cls_ptr[c + 1] || T->cls_ptr[c + 1] - T->cls_ptr[c] > ACM_TEMPLATE_MAX_RANGES || (T->cls_ptr[c + 1] && !T->ranges))
+      return ACM_GPU_E_ARG;
+    for (uint64_t r = T->cls_ptr[c]; r < T->cls_ptr[c + 1]; r++)
+      if (words_symbol (T->ranges, 2 * r, sym_bytes) > words_symbol (T->ranges, 2 * r + 1, sym_bytes))
+        return ACM_GPU_E_ARG;
+  }
+  if (acm_approx_check (T->spell_off, T->k, T->terms, T->tgt_ptr, T->n_templates, n_keywords) || (T->n_templates && !T->cells))
+    return ACM_GPU_E_ARG;
+  for (uint64_t i = 0; i < T->spell_off[T->n_templates]; i++)
+    if (T->cells[i] < ACM_TEMPLATE_ANY && T->cells[i] >= T->n_classes)
+      return ACM_GPU_E_ARG;
+  for (uint64_t w = 0; w < T->n_templates; w++)
+    for (uint64_t i = T->tgt_ptr[w]; i < T->tgt_ptr[w + 1]; i++) /* a piece is an exact keyword: literal cells only */
+      for (uint32_t at = 0; at < T->terms[i].length; at++)
+        if (T->cells[T->spell_off[w] + T->terms[i].offset + at] != ACM_TEMPLATE_LITERAL)
+          return ACM_GPU_E_ARG;
+  return ACM_GPU_OK;
+}
+
+/* the pieces of q cells that the literal runs of a template give: sum over runs of floor (run / q); with `j`, where piece j begins */
+static uint64_t
+tpl_pieces (const uint32_t *cells, uint64_t L, uint64_t q, const uint32_t *j, uint64_t *offset) {
+  uint64_t pieces = 0;
+  for (uint64_t i = 0; i < L;) {
+    if (cells[i] != ACM_TEMPLATE_LITERAL) {
+      i++;
+      continue;
+    }
+    uint64_t run = i;
+    while (run < L && cells[run] == ACM_TEMPLATE_LITERAL)
+      run++;
+    const uint64_t here = (run - i) / q;
+    if (j && *j >= pieces && *j < pieces + here)
+      *offset = i + (*j - pieces) * q;
+    pieces += here;
+    i = run;
+  }
+  return pieces;
+}
+
+int
+acm_templates_split (const uint32_t *cells, uint64_t L, uint32_t k, uint32_t j, uint64_t *offset, uint64_t *length) {
+  if (!cells || !offset || !length || L == 0 || L >= (1ull << 31) || j > k || tpl_pieces (cells, L, 1, NULL, NULL) < (uint64_t)k + 1)
+    return ACM_GPU_E_ARG;
+  uint64_t q = 1; /* the largest length that still gives k + 1 pieces (the number of pieces does not grow with q) */
+  while (q < L && tpl_pieces (cells, L, q + 1, NULL, NULL) >= (uint64_t)k + 1)
+    q++;
+  (void)tpl_pieces (cells, L, q, &j, offset);
+  *length = q;
+  return ACM_GPU_OK;
+}
+
+int
+acm_templates_records (const ACMRecord *records, uint64_t n, const void *text, uint32_t sym_bytes, uint64_t n_symbols, uint64_t pos_base,
+                       const uint64_t *offsets, uint64_t n_texts, const ACMTemplateSpec *T, uint64_t n_keywords, ACMRecord *out, uint32_t *dist,
+                       uint64_t out_capacity, uint64_t *n_found) {
+  if (acm_templates_check (T, sym_bytes, n_keywords))
+    return ACM_GPU_E_ARG;
+  const struct apx_set A = { T->spell_data, T->spell_off, T->k, T->terms, T->tgt_ptr, sym_bytes, NULL, NULL, T };
+  return approx_core (records, n, text, n_symbols, pos_base, offsets, n_texts, &A, T->n_templates, n_keywords, out, dist, out_capacity, n_found);
+}
+
+/* the checks acm_scan_templates makes on every path: acm_templates_check against the machine's keywords, and acm_scan_approx's on the
+ * terms (they stand on literal cells, so their pieces are spelled in spell_data) */
+int
+acm_internal_templates_machine_check (ACMachine *m, uint32_t sym_bytes, const ACMTemplateSpec *T) {
+  if (!m || !T)
+    return ACM_GPU_E_ARG;
+  acm_internal_lock (m);
+  const int rc = acm_templates_check (T, sym_bytes, m->nb_keywords);
+  acm_internal_unlock (m);
+  return rc ? rc : acm_internal_approx_machine_check (m, sym_bytes, T->spell_data, T->spell_off, T->k, T->terms, T->tgt_ptr, T->n_templates);
+}
+
+/* acm_scan_templates on the host: acm_internal_cpu_scan_approx with the cells; literal cells by the comparator, class cells by value */
+int
+acm_internal_cpu_scan_templates (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                                 const ACMTemplateSpec *T, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
+  if (!m || !n_found || !T)
+    return ACM_GPU_E_ARG;
+  ACMRecord *records;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, n_symbols, offsets, n_texts, sym_bytes, NULL, &records, &found);
+  if (!rc) {
+    const struct apx_set A = { T->spell_data, T->spell_off, T->k, T->terms, T->tgt_ptr, sym_bytes, m->cmp, m->cmp_arg, T };
+    rc = approx_core (records, found, text, n_symbols, 0, offsets, n_texts, &A, T->n_templates, acm_nb_keywords (m), out, dist, out_capacity, n_found);
   }
   free (records);
   return rc;
@@ -2469,7 +2585,7 @@ acm_edit_records (const ACMRecord *records, uint64_t n, const void *text, uint32
                   const uint64_t *offsets, uint64_t n_texts, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,
                   const ACMPatternTerm *terms, const uint64_t *tgt_ptr, uint64_t n_targets, uint64_t n_keywords, ACMRecord *out, uint32_t *dist,
                   uint64_t out_capacity, uint64_t *n_found) {
-  const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, NULL, NULL };
+  const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, NULL, NULL, NULL };
   return edit_core (records, n, text, n_symbols, pos_base, offsets, n_texts, &A, n_targets, n_keywords, out, dist, out_capacity, n_found);
 }
 
@@ -2493,7 +2609,7 @@ acm_internal_cpu_scan_edit (ACMachine *m, const void *text, uint64_t n_symbols, 
   uint64_t found = 0;
   int rc = cpu_scan_grown (m, text, n_symbols, offsets, n_texts, sym_bytes, NULL, &records, &found);
   if (!rc) {
-    const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, m->cmp, m->cmp_arg };
+    const struct apx_set A = { spell_data, spell_off, k, terms, tgt_ptr, sym_bytes, m->cmp, m->cmp_arg, NULL };
     rc = edit_core (records, found, text, n_symbols, 0, offsets, n_texts, &A, n_targets, acm_nb_keywords (m), out, dist, out_capacity, n_found);
   }
   free (records);

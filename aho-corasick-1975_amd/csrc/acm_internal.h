@@ -135,6 +135,11 @@ int acm_internal_cpu_scan_edit (ACMachine *m, const void *text, uint64_t n_symbo
                                 const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
                                 const uint64_t *tgt_ptr, uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity,
                                 uint64_t *n_found);
+/* acm_scan_templates' checks on every path: acm_templates_check against the machine's keywords plus acm_scan_approx's on the terms */
+int acm_internal_templates_machine_check (ACMachine *m, uint32_t sym_bytes, const ACMTemplateSpec *spec);
+/* acm_scan_templates' host path: acm_internal_cpu_scan_approx with the cells (literal cells by the comparator, class cells by value) */
+int acm_internal_cpu_scan_templates (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                                     const ACMTemplateSpec *spec, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found);
 void acm_internal_set_scan_path (ACMachine *m, int path);
 /* ACM_NMEYER_85 builds: brings failure links and output counts up to date (no-op otherwise);
  * takes the machine lock itself */

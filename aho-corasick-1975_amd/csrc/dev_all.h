@@ -186,6 +186,7 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_anchored.h"
 #include "dev_patterns.h"
 #include "dev_approx.h"
+#include "dev_templates.h"
 #include "dev_edit.h"
 #include "dev_chains.h"
 

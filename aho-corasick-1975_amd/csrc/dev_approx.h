@@ -80,6 +80,12 @@ struct ApproxK {
   unsigned long long *d_count;
   ApproxCtl *ctl;
   unsigned int *error; /* the plan's device-side flag (acm_gpu_plan_status) */
+  /* TEMPLATES only (dev_templates.h): the cells beside the spellings and the compiled classes */
+  const uint32_t *cells;      /* [the spellings' symbols] ACM_TEMPLATE_LITERAL, ACM_TEMPLATE_ANY or a class id */
+  const uint32_t *cls_bitmap; /* 1-byte symbols: [n_classes][8] the accepted symbols, the negate flag applied */
+  const uint64_t *cls_ptr;    /* wider symbols: [n_classes + 1] the ranges of a class in cls_ranges ... */
+  const void *cls_ranges;     /* ... pairs lo, hi of the caller's size ... */
+  const uint32_t *cls_flags;  /* ... and ACM_TEMPLATE_NEGATED */
 };
 
 /* the batch contract on offsets[]: batch_index_kernel's check */
@@ -115,8 +121,12 @@ approx_postings (const ApproxK &K, const uint4 r, uint32_t &begin, uint32_t &end
 
 /* What a wave does with its four records: every group walks the postings [q, q_end) of its record r (none: q ==
  * q_end) and returns the number of matches it seeds; with FILL it stores them from slot `at` on.  All 64 lanes
- * call this together; q, q_end, r and `at` are the same in the 16 lanes of a group. */
-template <typename T, bool FILL>
+ * call this together; q, q_end, r and `at` are the same in the 16 lanes of a group.  With CELLS the targets are templates: a position
+ * is accepted by its cell (templates_cell_fails of dev_templates.h), not by its spelling alone. */
+template <typename T>
+__device__ __forceinline__ bool templates_cell_fails (const ApproxK &K, uint32_t cell, const T *__restrict__ text_at, const T *__restrict__ spell_at);
+
+template <typename T, bool FILL, bool CELLS>
 __device__ __forceinline__ uint32_t
 approx_group (const ApproxK &K, uint64_t n, const uint4 r, uint32_t q, uint32_t q_end, unsigned long long at) {
   const uint32_t lane = threadIdx.x & (WAVE - 1), sub = lane & (APPROX_GROUP - 1), shift = lane & ~(APPROX_GROUP - 1);
@@ -128,6 +138,7 @@ approx_group (const ApproxK &K, uint64_t n, const uint4 r, uint32_t q, uint32_t 
     uint32_t L = 0, k = 0, w = 0, lower = 0, lower_end = 0; /* [lower, lower_end): the target's terms of lower index */
     uint64_t S = 0;
     const T *__restrict__ spell = nullptr;
+    const uint32_t *__restrict__ cells = nullptr;
     if (q < q_end) {
       const uint4 p = K.post[q++];
       if (r.z == p.w && (uint64_t)p.z + p.w - 1 <= e) { /* the piece's length, and the target begins inside the buffer */
@@ -143,6 +154,8 @@ approx_group (const ApproxK &K, uint64_t n, const uint4 r, uint32_t q, uint32_t 
         lower = tg.z;
         lower_end = tg.z + p.y;
         spell = static_cast<const T *> (K.spell) + K.spell_off[w];
+        if (CELLS)
+          cells = K.cells + K.spell_off[w];
       }
     }
     uint32_t miss = 0;
@@ -153,7 +166,7 @@ approx_group (const ApproxK &K, uint64_t n, const uint4 r, uint32_t q, uint32_t 
       const uint32_t i = i0 + sub;
       bool differ = false;
       if (active && i < L)
-        differ = text[S + i] != spell[i];
+        differ = CELLS ? templates_cell_fails<T> (K, cells[i], text + S + i, spell + i) : text[S + i] != spell[i];
       miss += __popcll ((__ballot (differ) >> shift) & 0xFFFFull);
     }
     bool match = cand && miss <= k;
@@ -177,7 +190,7 @@ approx_group (const ApproxK &K, uint64_t n, const uint4 r, uint32_t q, uint32_t 
 }
 
 /* pass 1 */
-template <typename T>
+template <typename T, bool CELLS = false>
 __global__ __launch_bounds__ (APPROX_THREADS) void
 approx_count_kernel (ApproxK K) {
   const uint32_t lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, group = lane / APPROX_GROUP;
@@ -199,7 +212,7 @@ approx_count_kernel (ApproxK K) {
         r = *reinterpret_cast<const uint4 *> (&K.in[i]);
         approx_postings (K, r, q, q_end, bad);
       }
-      const uint32_t found = approx_group<T, false> (K, n, r, q, q_end, 0);
+      const uint32_t found = approx_group<T, false, CELLS> (K, n, r, q, q_end, 0);
       if (i < end && (lane & (APPROX_GROUP - 1)) == 0)
         K.count[i] = found;
     }
@@ -209,7 +222,7 @@ approx_count_kernel (ApproxK K) {
 }
 
 /* pass 2 */
-template <typename T>
+template <typename T, bool CELLS = false>
 __global__ __launch_bounds__ (APPROX_THREADS) void
 approx_fill_kernel (ApproxK K) {
   const uint32_t lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE, group = lane / APPROX_GROUP;
@@ -234,7 +247,7 @@ approx_fill_kernel (ApproxK K) {
           approx_postings (K, r, q, q_end, bad);
         }
       }
-      (void)approx_group<T, true> (K, n, r, q, q_end, at);
+      (void)approx_group<T, true, CELLS> (K, n, r, q, q_end, at);
     }
   }
 }

@@ -1516,7 +1516,8 @@ void acm_gpu_stream_close (ACMStream *stream);
  * length is ACM_GPU_E_ARG here.  A missing device stays an error, never a fallback.
  *
  * Out of scope: trailing don't-cares (not expressible: they would test nothing but that the text
- * goes on); bounded variable gaps ({n-m}: acm_scan_chains below joins those); symbol classes or alternatives inside a pattern; flows,
+ * goes on); bounded variable gaps ({n-m}: acm_scan_chains below joins those); symbol classes inside a pattern (TEMPLATES, the section
+ * behind acm_scan_chains, has them) and alternatives (AA|BB); flows,
  * streams and several GPUs; feeding pattern records to SELECT or REPLACE (their contract bounds
  * lengths by the plan's lmax, and L_p is not bound by it). */
 typedef struct {
@@ -1650,7 +1651,8 @@ int acm_scan_patterns (ACMachine *machine, const void *text, uint64_t n_symbols,
  * acm_set_symbol_bytes (ACM_GPU_E_INELIGIBLE without it).  A missing device stays an error, never a
  * fallback.
  *
- * Out of scope: insertions and deletions (edit distance: EDIT, the next section); class plans on the
+ * Out of scope: insertions and deletions (edit distance: EDIT, the next section); positions that take one
+ * of several symbols (TEMPLATES, the section behind acm_scan_chains); class plans on the
  * device; flows, streams and several GPUs; feeding the output to SELECT or REPLACE (their contract bounds
  * lengths by the plan's lmax, and L_w is not bound by it). */
 typedef struct ACMApprox ACMApprox;
@@ -1929,6 +1931,130 @@ int acm_scan_chains (ACMachine *machine, const void *text, uint64_t n_symbols,
                      const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
                      const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains,
                      ACMRecord *out, uint64_t out_capacity, uint64_t *n_found);
+
+/* ------------------------------------------------------------------ keyword templates with symbol classes
+ * In PATTERNS and APPROX a position is one exact symbol or anything at all.  TEMPLATES adds "one of these
+ * symbols": hex signatures with nibble wildcards and byte ranges (E2 3? ?? [C0-CF] A1), primers in IUPAC
+ * codes under a mismatch budget, fixed-column templates such as \d{3}-\d{2}-\d{4}.  It is APPROX with an
+ * acceptance test per position that is a set membership: the literal stretches of a template give the
+ * pieces, every exact piece record is a seed, and the template is verified against the text around it.
+ * The scan kernels stay untouched.
+ *
+ * DEFINITION.  Classes: there are n_classes classes.  Class c is the set of symbols in the inclusive
+ * ranges [cls_ptr[c], cls_ptr[c + 1]) of ranges[] (cls_ptr has n_classes + 1 uint64_t entries); a range is
+ * two symbols lo, hi of the caller's symbol size, compared as unsigned integers (acm_words_records'
+ * convention).  With cls_flags[c] & ACM_TEMPLATE_NEGATED the class is the complement of that set.  A class
+ * has at most ACM_TEMPLATE_MAX_RANGES (16) ranges; an empty class is allowed and accepts nothing, negated
+ * it accepts everything.  ACM_GPU_E_ARG: a range with lo > hi, more than 16 ranges, a cls_ptr that
+ * decreases or does not begin with 0, n_classes >= 0xFFFFFFFE.
+ * Templates: template w has L_w cells, cells[spell_off[w] .. spell_off[w + 1]), one uint32_t each:
+ *   ACM_TEMPLATE_LITERAL (0xFFFFFFFF): the cell accepts exactly spell_data[spell_off[w] + i];
+ *   ACM_TEMPLATE_ANY (0xFFFFFFFE): the cell accepts every symbol;
+ *   a class id < n_classes: the cell accepts the symbols of that class.
+ * spell_data has an entry for every cell; it is ignored where the cell is not literal.  Template w has a
+ * budget k[w] (at most 255) and the terms [tgt_ptr[w], tgt_ptr[w + 1]), ACMPatternTerm reused as in
+ * APPROX: keyword keyword_id, `length` symbols long, is the piece at `offset`.  ACM_GPU_E_ARG: everything
+ * acm_approx_check refuses, a cell value that is neither of the two constants nor a class id, and a term
+ * that covers a cell that is not literal (a piece is an exact keyword: it stands on literal cells only).
+ * The arrays travel in one plain struct of host pointers, ACMTemplateSpec.
+ * TEMPLATES (R, text, offsets, T).  Template w MATCHES at buffer index S iff
+ *   1. some text t has offsets[t] <= S and S + L_w <= offsets[t + 1], and
+ *   2. (seed) some term (kid, o, l) of w has the record (pos_base + S + o + l - 1, l, kid) in R, and
+ *   3. d = the number of cells i that do not accept text[S + i] is <= k[w]; symbols are taken bitwise in
+ *      the caller's size.
+ * Each (w, S) that matches gives exactly one ACMRecord (end_pos = pos_base + S + L_w - 1, length = L_w,
+ * keyword_id = w) and dist[r] = d, however many terms seed it.  The total order is end_pos ascending, then
+ * length descending, then template id ascending.
+ * COMPLETENESS.  When the terms of w are k[w] + 1 pairwise disjoint pieces on literal cells, each keyword
+ * is spelled as its piece and R is the full record set, condition 2 follows from 1 and 3: at most k cells
+ * fail, so at least one piece is intact.  A template with fewer than k + 1 literal cells cannot be seeded
+ * completely; the seed condition then removes matches, which is defined and no error in the record passes.
+ * THE CANONICAL CUT.  acm_templates_split (cells, L, k, j, &offset, &length): the literal runs of the
+ * template are its maximal stretches of literal cells; q is the largest length with sum over runs of
+ * floor (run / q) >= k + 1; each run gives floor (run / q) pieces of q cells from its left end on; piece j
+ * is the j-th of these, left to right, for j <= k.  ACM_GPU_E_ARG when the template has fewer than k + 1
+ * literal cells.  For k = 0 this is the first of the longest literal runs, whole.
+ *
+ * acm_templates_check (spec, sym_bytes, n_keywords): the argument checks above, no device; every other
+ * entry point runs it.  acm_templates_records: the plain sequential TEMPLATES on the host, no device, with
+ * acm_approx_records' rules for overflow, for counting only, for dist == NULL and for ACM_GPU_E_ARG.
+ * acm_gpu_templates_create compiles a set once and uploads it to the plan's device (ACMTemplates, opaque):
+ * APPROX's index over the terms, the cell words, and the classes -- for 1-byte symbols a bitmap of 256
+ * bits per class with the negate flag applied, for wider symbols the ranges and the flags.  A plan over
+ * comparator classes is refused with ACM_GPU_E_INELIGIBLE; plans that intern 8-byte symbols are taken;
+ * the set stays valid after acm_gpu_plan_update.  acm_gpu_templates_info: templates, terms, classes, the
+ * keywords that seed a template, the longest L_w, the largest k and the most postings of one keyword.
+ * acm_gpu_templates_records_device (dev_templates.h): acm_gpu_approx_records_device's contract, word for
+ * word -- arguments, the four outcomes for count and overflow, the rule for records and offsets that break
+ * the contract, launches only -- and its passes: the check of d_offsets in a launch of its own, a count
+ * pass with one group of 16 lanes per record over tiles (ACM_GPU_TEMPLATES_TILE=<records>: a multiple of
+ * 64 from 64 to 1 Mi, default 1,024), a 64-bit exclusive sum, a fill pass that verifies again, and the
+ * order pass when the total fits.  Inside the group lane j takes cells j, j + 16, ...: a literal cell
+ * compares with the spelling, an ANY cell accepts without loading the text, a class cell of 1-byte symbols
+ * tests one bit of the class's bitmap (one 32-bit load of word sym >> 5, from global memory), a class cell
+ * of wider symbols walks the class's ranges.  d_tmp must hold acm_gpu_templates_tmp_bytes bytes.
+ * acm_gpu_scan_templates_device / _host, acm_scan_templates: as their APPROX counterparts.  On the machine
+ * a term whose keyword is not spelled as its piece is ACM_GPU_E_ARG; a machine with another comparator
+ * runs the caller loop and the sequential pass -- literal cells compared by the comparator, class cells by
+ * value -- and reports ACM_SCAN_PATH_CPU_LOOP.  A missing device stays an error.
+ *
+ * Out of scope: templates without a literal cell (a class-only scan kernel); variable-length cells;
+ * alternatives (AA|BB); classes inside CHAINS' gaps; edits; flows, streams and several GPUs; class plans
+ * on the device. */
+#define ACM_TEMPLATE_LITERAL 0xFFFFFFFFu
+#define ACM_TEMPLATE_ANY 0xFFFFFFFEu
+#define ACM_TEMPLATE_NEGATED 1u
+#define ACM_TEMPLATE_MAX_RANGES 16u
+typedef struct {
+  const void *spell_data;
+  const uint64_t *spell_off;
+  const uint32_t *cells;
+  const uint32_t *k;
+  const ACMPatternTerm *terms;
+  const uint64_t *tgt_ptr;
+  uint64_t n_templates;
+  const void *ranges;
+  const uint64_t *cls_ptr;
+  const uint32_t *cls_flags;
+  uint64_t n_classes;
+} ACMTemplateSpec;
+typedef struct ACMTemplates ACMTemplates;
+typedef struct {
+  uint64_t templates, terms, classes, seed_keywords, longest, max_k, max_postings;
+} ACMTemplatesInfo;
+int acm_templates_check (const ACMTemplateSpec *spec, uint32_t sym_bytes, uint64_t n_keywords);
+int acm_templates_split (const uint32_t *cells, uint64_t L, uint32_t k, uint32_t j, uint64_t *offset, uint64_t *length);
+int acm_templates_records (const ACMRecord *records, uint64_t n, const void *text, uint32_t sym_bytes, uint64_t n_symbols,
+                           uint64_t pos_base, const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                           const ACMTemplateSpec *spec, uint64_t n_keywords,
+                           ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity, uint64_t *n_found);
+int acm_gpu_templates_create (ACMPlan *plan, const ACMTemplateSpec *spec, ACMTemplates **out);
+void acm_gpu_templates_destroy (ACMTemplates *templates);
+int acm_gpu_templates_info (const ACMTemplates *templates, ACMTemplatesInfo *info);
+size_t acm_gpu_templates_tmp_bytes (const ACMPlan *plan, const ACMTemplates *templates, uint64_t n_or_capacity,
+                                    uint64_t out_capacity, uint64_t n_texts);
+int acm_gpu_templates_records_device (ACMPlan *plan, const ACMTemplates *templates, const ACMRecord *d_records,
+                                      uint64_t n_or_capacity, const uint64_t *d_n /* may be NULL */,
+                                      const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                      const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                      ACMRecord *d_out, uint32_t *d_dist /* may be NULL */, uint64_t out_capacity,
+                                      uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_scan_templates_tmp_bytes (const ACMPlan *plan, const ACMTemplates *templates, uint64_t capacity,
+                                         uint64_t out_capacity, uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_templates_device (ACMPlan *plan, const ACMTemplates *templates, const void *d_text, uint64_t n_symbols,
+                                   uint64_t pos_base, const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                   uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist /* may be NULL */,
+                                   uint64_t out_capacity, uint64_t *d_count, uint64_t *d_found,
+                                   void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_templates_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base,
+                                 const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                                 const ACMTemplateSpec *spec,
+                                 ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity,
+                                 uint64_t *n_found);   /* blocking */
+int acm_scan_templates (ACMachine *machine, const void *text, uint64_t n_symbols,
+                        const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                        const ACMTemplateSpec *spec,
+                        ACMRecord *out, uint32_t *dist /* may be NULL */, uint64_t out_capacity, uint64_t *n_found);
 
 /* ------------------------------------------------------------------ several GPUs of one node, one process
  * The reference's model for parallel work is one shared read-only machine and one cursor per worker
