@@ -19,6 +19,8 @@ ACM_GPU_E_ARG = -5
 ACM_GREP_MATCHING, ACM_GREP_INVERT = 0, 1
 ACM_SPLIT_EVERY, ACM_SPLIT_RUNS = 0, 1
 ACM_WORDS_LEFT, ACM_WORDS_RIGHT, ACM_WORDS_BOTH = 1, 2, 3
+ACM_CONTEXT_SYMBOLS, ACM_CONTEXT_TEXTS, ACM_CONTEXT_EACH, ACM_CONTEXT_MERGE = 0, 1, 0, 2
+ACM_CONTEXT_NONE = 0xFFFFFFFF
 ACM_RULE_NO_MAX = 0xFFFFFFFF
 ACM_ANCHORED_PREFIXES, ACM_ANCHORED_LONGEST, ACM_ANCHORED_WHOLE = 1, 2, 3
 ACM_LOOKUP_NONE = 0xFFFFFFFF
@@ -133,6 +135,8 @@ EXPORTS = [
     "acm_tally_batch_records", "acm_gpu_tally_batch_tmp_bytes", "acm_gpu_tally_batch_device", "acm_gpu_tally_batch_host", "acm_tally_batch",
     "acm_words_records", "acm_gpu_words_tmp_bytes", "acm_gpu_words_records_device", "acm_gpu_scan_words_tmp_bytes", "acm_gpu_scan_words_device",
     "acm_gpu_scan_words_host", "acm_scan_words",
+    "acm_context_records", "acm_gpu_context_tmp_bytes", "acm_gpu_context_records_device", "acm_gpu_scan_context_tmp_bytes",
+    "acm_gpu_scan_context_device", "acm_gpu_scan_context_host", "acm_context",
     "acm_anchored_records", "acm_gpu_scan_anchored_tmp_bytes", "acm_gpu_scan_anchored_device", "acm_gpu_lookup_tmp_bytes", "acm_gpu_lookup_device",
     "acm_gpu_scan_anchored_host", "acm_gpu_lookup_host", "acm_scan_anchored", "acm_lookup",
     "acm_rules_check", "acm_rules_matrix", "acm_gpu_rules_create", "acm_gpu_rules_destroy", "acm_gpu_rules_info", "acm_gpu_rules_matrix_tmp_bytes",
@@ -519,6 +523,21 @@ def lib():
     L.acm_gpu_scan_words_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, u32, u32, vp, u64, C.POINTER(u64)]
     L.acm_scan_words.restype = i32
     L.acm_scan_words.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, C.POINTER(u64)]
+    ctx_out = [vp, u64, C.POINTER(u64), C.POINTER(u64), vp, vp, vp, vp, vp]   # out, out_capacity, out_symbols, n_snippets, the five arrays
+    L.acm_context_records.restype = i32
+    L.acm_context_records.argtypes = [vp, u64, u32, u64, vp, u64, vp, u64, u32, u32, u32] + ctx_out
+    L.acm_gpu_context_tmp_bytes.restype = sz
+    L.acm_gpu_context_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_context_records_device.restype = i32
+    L.acm_gpu_context_records_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, u64, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_context_tmp_bytes.restype = sz
+    L.acm_gpu_scan_context_tmp_bytes.argtypes = [vp, u64, u64, u64]
+    L.acm_gpu_scan_context_device.restype = i32
+    L.acm_gpu_scan_context_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, u64, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_context_host.restype = i32
+    L.acm_gpu_scan_context_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, u64, C.POINTER(u64), u32, u32, u32] + ctx_out
+    L.acm_context.restype = i32
+    L.acm_context.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), u32, u32, u32] + ctx_out
     L.acm_anchored_records.restype = i32
     L.acm_anchored_records.argtypes = [vp, u64, u32, vp, u64, vp, vp, C.POINTER(u64)]
     L.acm_gpu_scan_anchored_tmp_bytes.restype = sz
@@ -1626,6 +1645,100 @@ def words_records(text, records, offsets=None, ranges=ASCII_WORD, flags="both", 
     return a[:n.value]
 
 
+class Snippets:
+    """What the context calls return: the text around the matches, packed.  out (the snippets side by
+    side, in the text's own symbols), out_offsets (n_snippets + 1 offsets into `out`), snip_lo (the
+    buffer index of every snippet's first symbol), snip_text (the text that holds it), rec_snip (the
+    snippet every record lies in, ACM_CONTEXT_NONE for a record that spans a cut) and rec_at (where
+    the match begins in `out`, -1 for such a record): numpy arrays cut to size from the host calls;
+    device tensors with room for every record from the Plan calls -- their first n_snippets (+ 1) or
+    `count` entries and out_symbols symbols count.  `records` are the records the windows were made
+    round.  n_snippets, out_symbols and count are Python ints (the Plan calls synchronise to read
+    them): count > capacity says that the scan overflowed (n_snippets = out_symbols = 0 then),
+    out_symbols > out_capacity is the room the output needs.  snippets[j] is snippet j, len() their number."""
+
+    def __init__(self, out, out_offsets, snip_lo, snip_text, rec_snip, rec_at, n_snippets, out_symbols, out_capacity=None, records=None, count=None,
+                 sym_size=None):
+        self.out, self.out_offsets, self.snip_lo, self.snip_text, self.rec_snip, self.rec_at = out, out_offsets, snip_lo, snip_text, rec_snip, rec_at
+        self.n_snippets, self.out_symbols, self.out_capacity, self.records, self.count = n_snippets, out_symbols, out_capacity, records, count
+        self.sym_size = sym_size            # bytes per symbol; None: one element of `out` per symbol
+        self.offsets = None                 # Plan.grep_context_lines: the n_texts + 1 offsets the buffer was cut at
+
+    def __len__(self):
+        return self.n_snippets
+
+    def __getitem__(self, j):
+        if self.out is None or not -self.n_snippets <= j < self.n_snippets:
+            raise IndexError(j)
+        j %= self.n_snippets
+        per = 1 if self.sym_size is None else self.sym_size // (self.out.element_size() if hasattr(self.out, "element_size") else self.out.itemsize)
+        return self.out[int(self.out_offsets[j]) * per:int(self.out_offsets[j + 1]) * per]
+
+
+_CONTEXT_UNITS = {"symbols": ACM_CONTEXT_SYMBOLS, "texts": ACM_CONTEXT_TEXTS}
+
+
+def _context_flags(unit, merge):
+    return (_CONTEXT_UNITS[unit] if isinstance(unit, str) else int(unit)) | (ACM_CONTEXT_MERGE if merge else ACM_CONTEXT_EACH)
+
+
+def _context_host_call(call, what, t, sym_size, room, grow, gather, out_capacity):
+    """the host context calls: numpy in, a Snippets of numpy arrays out.  `call` takes the record room and (out,
+    out_capacity, out_symbols, n_snippets, snip_lo, out_offsets, snip_text, rec_snip, rec_at) and returns (rc, the
+    records, their number).  Each of the two overflows is repeated once with the size the call reports: the records'
+    when `grow`, the output's when out_capacity is None."""
+    cap = int(out_capacity) if out_capacity is not None else 0
+    for attempt in (0, 1, 2):
+        snip_lo, out_off = np.zeros(max(room, 1), np.uint64), np.zeros(room + 1, np.uint64)
+        snip_text, rec_snip, rec_at = np.zeros(max(room, 1), np.uint32), np.zeros(max(room, 1), np.uint32), np.zeros(max(room, 1), np.int64)
+        out = np.zeros(max(cap * sym_size // t.itemsize, 1), dtype=t.dtype) if gather else None
+        sym, ns = C.c_uint64(0), C.c_uint64(0)
+        rc, records, m = call(room, out.ctypes.data if gather else None, cap if gather else 0, C.byref(sym), C.byref(ns), snip_lo.ctypes.data,
+                              out_off.ctypes.data, snip_text.ctypes.data, rec_snip.ctypes.data, rec_at.ctypes.data)
+        if rc == ACM_GPU_E_OVERFLOW and m > room and grow and attempt < 2:
+            room, grow = m, False
+            continue
+        if rc == ACM_GPU_E_OVERFLOW and m <= room and out_capacity is None and int(sym.value) > cap and attempt < 2:
+            cap = int(sym.value)
+            continue
+        _check(rc, what)
+        k, n = int(ns.value), int(sym.value)
+        return Snippets(out[:n * sym_size // t.itemsize] if gather else None, out_off[:k + 1], snip_lo[:k], snip_text[:k], rec_snip[:m], rec_at[:m],
+                        k, n, cap, records, m, sym_size)
+
+
+def context_records(text, records, offsets=None, before=0, after=0, unit="symbols", merge=True, pos_base=0, sym_size=None, gather=True,
+                    out_capacity=None):
+    """acm_context_records(): the text round the matches `records` (RECORD_DTYPE) of `text` (an array of
+    symbols; with sym_size, raw bytes of symbols of that size), by the sequential pass on the host: every
+    match with `before` symbols in front of it and `after` behind it, clipped to its text -- with unit
+    "texts", its whole text with that many texts in front and behind (grep -B / -A).  merge: windows that
+    overlap or touch become one snippet (grep -C; the records' end_pos must not decrease); else one
+    snippet per record, in the order of the input.  `offsets` (n_texts + 1 entries) cuts the buffer into
+    texts.  Returns a Snippets of numpy arrays."""
+    t = np.ascontiguousarray(text)
+    sb = int(sym_size) if sym_size is not None else t.itemsize
+    a = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
+    off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+    flags = _context_flags(unit, merge)
+
+    def call(room, *outputs):
+        return lib().acm_context_records(t.ctypes.data if t.size else None, t.size * t.itemsize // sb, sb, int(pos_base),
+                                         off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0,
+                                         a.ctypes.data if a.size else None, a.size, int(before), int(after), flags, *outputs), a, a.size
+    return _context_host_call(call, "acm_context_records", t, sb, a.size, False, gather, out_capacity)
+
+
+def _context_scan_call(fn, head, t, n_sym, off, before, after, flags):
+    """acm_context / acm_gpu_scan_context_host as _context_host_call's `call`: a record room of the call's own"""
+    def call(room, *outputs):
+        rec = np.zeros(max(room, 1), dtype=RECORD_DTYPE)
+        n = C.c_uint64(0)
+        rc = fn(*head, t.ctypes.data if t.size else None, n_sym, *off, rec.ctypes.data, room, C.byref(n), int(before), int(after), flags, *outputs)
+        return rc, rec[:min(int(n.value), room)], int(n.value)
+    return call
+
+
 _ANCHORED_MODES = {"prefixes": ACM_ANCHORED_PREFIXES, "longest": ACM_ANCHORED_LONGEST, "whole": ACM_ANCHORED_WHOLE}
 
 
@@ -2080,6 +2193,17 @@ class Machine:
                 continue
             _check(rc, "acm_scan_words")
             return out[:n.value]
+
+    def context(self, text, before=0, after=0, merge=True, capacity=None, gather=True, out_capacity=None):
+        """acm_context(): the matches of `text` with `before` symbols in front of and `after` behind each
+        (see context_records), as a Snippets of numpy arrays whose `records` are the matches in canonical
+        order.  `capacity` must hold ALL matches; by default each overflow is repeated once with the size
+        the call reports."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        call = _context_scan_call(self.L.acm_context, (self.handle,), t, n_sym, (), before, after, _context_flags("symbols", merge))
+        return _context_host_call(call, "acm_context", t, self.sym_size, int(capacity) if capacity is not None else max(1024, t.size // 64),
+                                  capacity is None, gather, out_capacity)
 
     def scan_patterns(self, text, patternset, offsets=None, out_capacity=None):
         """acm_scan_patterns(): the matches of the patterns of `patternset` (see patterns_records) in `text`,
@@ -3437,6 +3561,105 @@ class Plan:
                 continue
             _check(rc, "acm_gpu_scan_words_host")
             return out[:n.value]
+
+    def _context_outputs(self, text, room, n_symbols, gather, out, out_capacity):
+        """the device outputs of the context calls: (snip_lo, out_offsets, snip_text, rec_snip, rec_at, res, out, out_capacity);
+        res = the record count, n_snippets, out_symbols"""
+        import torch
+        dev = text.device
+        i64 = lambda n: torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        i32 = lambda n: torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        if gather:
+            if out_capacity is None:
+                out_capacity = out.numel() * out.element_size() // self.sym_size if out is not None else n_symbols
+            if out is None:
+                out = torch.empty(max(int(out_capacity) * self.sym_size, 16), dtype=torch.uint8, device=dev)
+            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= int(out_capacity) * self.sym_size
+        else:
+            out, out_capacity = None, 0
+        return i64(room), i64(room + 1), i32(room), i32(room), i64(room), i64(3), out, int(out_capacity)
+
+    def context_records(self, text, records, n, offsets=None, before=0, after=0, unit="symbols", merge=True, pos_base=0, n_symbols=None, count=None,
+                        gather=True, out=None, out_capacity=None):
+        """acm_gpu_context_records_device(): the text round the matches records[:n] (an int64
+        [capacity, 2] device tensor; see context_records) of `text` (a device tensor), queued on the
+        current stream.  `count` (a device int64 tensor) gives the number of records on the device: n
+        is the room of `records` then.  `offsets` is a device int64 tensor of n_texts + 1 entries.
+        With gather the snippets are packed into `out` (None: a new uint8 tensor with room for
+        out_capacity symbols, by default for the whole buffer; it must not overlap `text`).  Returns a
+        Snippets of device tensors; synchronises to read its numbers."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
+        n = int(n)
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        snip_lo, out_off, snip_text, rec_snip, rec_at, res, out, out_capacity = self._context_outputs(text, n, n_symbols, gather, out, out_capacity)
+        n_texts = offsets.numel() - 1 if offsets is not None else 0
+        tb = lib().acm_gpu_context_tmp_bytes(self.h, n, n_texts)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        _check(lib().acm_gpu_context_records_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
+                                                    n_texts, records.data_ptr(), n, count.data_ptr() if count is not None else None, int(before),
+                                                    int(after), _context_flags(unit, merge), out.data_ptr() if gather else None, out_capacity,
+                                                    res.data_ptr() + 16, res.data_ptr() + 8, snip_lo.data_ptr(), out_off.data_ptr(),
+                                                    snip_text.data_ptr(), rec_snip.data_ptr(), rec_at.data_ptr(), tmp.data_ptr(), tmp.numel(),
+                                                    self._stream()), "acm_gpu_context_records_device")
+        _, n_snippets, out_symbols = (int(x) for x in res.cpu())
+        return Snippets(out, out_off, snip_lo, snip_text, rec_snip, rec_at, n_snippets, out_symbols, out_capacity, records,
+                        int(count.item()) if count is not None else n, self.sym_size)
+
+    def scan_context(self, text, offsets=None, before=0, after=0, unit="symbols", merge=True, n_symbols=None, pos_base=0, capacity=None, records=None,
+                     gather=True, out=None, out_capacity=None):
+        """acm_gpu_scan_context_device(): the ordered scan of a device tensor and the text round its
+        matches (see context_records), queued on the current stream.  `capacity` must hold ALL
+        matches.  Returns a Snippets of device tensors whose `records` are the matches in canonical
+        order: count > capacity is the number of ALL matches (n_snippets = out_symbols = 0 then);
+        out_symbols > out_capacity is the room the output needs.  Synchronises to read the three."""
+        import torch
+        assert text.is_cuda and text.is_contiguous()
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        if records is None:
+            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+            records = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=text.device)
+        else:
+            cap = records.shape[0] if capacity is None else int(capacity)
+        snip_lo, out_off, snip_text, rec_snip, rec_at, res, out, out_capacity = self._context_outputs(text, cap, n_symbols, gather, out, out_capacity)
+        n_texts = offsets.numel() - 1 if offsets is not None else 0
+        tb = lib().acm_gpu_scan_context_tmp_bytes(self.h, cap, n_symbols, n_texts)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        _check(lib().acm_gpu_scan_context_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
+                                                 n_texts, records.data_ptr(), cap, res.data_ptr(), int(before), int(after),
+                                                 _context_flags(unit, merge), out.data_ptr() if gather else None, out_capacity, res.data_ptr() + 16,
+                                                 res.data_ptr() + 8, snip_lo.data_ptr(), out_off.data_ptr(), snip_text.data_ptr(),
+                                                 rec_snip.data_ptr(), rec_at.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_scan_context_device")
+        count, n_snippets, out_symbols = (int(x) for x in res.cpu())
+        return Snippets(out, out_off, snip_lo, snip_text, rec_snip, rec_at, n_snippets, out_symbols, out_capacity, records, count, self.sym_size)
+
+    def scan_context_host(self, text, offsets=None, before=0, after=0, unit="symbols", merge=True, pos_base=0, capacity=None, gather=True,
+                          out_capacity=None):
+        """acm_gpu_scan_context_host(): numpy in, a Snippets of numpy arrays out, through the C ABI only
+        (no torch); each overflow is repeated once with the size the call reports."""
+        t = np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        call = _context_scan_call(lib().acm_gpu_scan_context_host, (self.h,), t, n_sym,
+                                  (int(pos_base), off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0), before, after,
+                                  _context_flags(unit, merge))
+        return _context_host_call(call, "acm_gpu_scan_context_host", t, self.sym_size, int(capacity) if capacity is not None else max(1024, n_sym // 64),
+                                  capacity is None, gather, out_capacity)
+
+    def grep_context_lines(self, buffer, delims=b"\n", before=0, after=0, runs=False, capacity=None, out=None, out_capacity=None):
+        """`grep -F -f keywords -C n file` on a device buffer: split() into lines, then scan_context()
+        with unit "texts" and merge -- every line with a match with `before` lines in front of it and
+        `after` behind it, overlapping and adjacent groups joined as grep joins them -- all on the
+        device.  Returns scan_context()'s Snippets with `offsets`, the lines' offsets, beside: snippet
+        j is one group, snip_text[j] the number of its first line."""
+        offsets = self.split(buffer, delims, runs)
+        s = self.scan_context(buffer, offsets, before, after, "texts", True, capacity=capacity, out=out, out_capacity=out_capacity)
+        s.offsets = offsets
+        return s
 
     def _replace_inputs(self, text, n_symbols, replacements, fill, out, out_capacity, most_records):
         import torch

@@ -5727,6 +5727,218 @@ acm_gpu_scan_words_host (ACMPlan *plan, const void *text, uint64_t n_symbols, ui
   return download_records (rc, d_count, d_rec, records, capacity, n_found);
 }
 
+/* ------------------------------------------------------------------ match contexts (include/acm_gpu.h, dev_context.h)
+ * Records into windows, windows into snippets, snippets into one packed output: the check of
+ * offsets[], the window pass, under MERGE the carries over the tiles and the flag pass, the prefix
+ * sums over the tiles, the index pass and the gather. */
+namespace {
+/* what context_carve derives beside K's pointers: hipCUB's room */
+struct ContextRoom {
+  long long *cnt_begin = nullptr, *sum_begin = nullptr;
+  CubRoom cub;
+};
+ContextRoom
+context_carve (Carve &c, uint64_t capacity, ContextK &K) {
+  ContextRoom R;
+  /* ACM_GPU_CONTEXT_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
+  K.tile = tunable ("ACM_GPU_CONTEXT_TILE", CONTEXT_TILE_DEFAULT, CONTEXT_TILE_MIN, CONTEXT_TILE_MAX, Tune::MultWave);
+  K.n_tiles = (capacity + K.tile - 1) / K.tile;
+  K.ctl = c.take<ContextCtl> (1);
+  K.tile_lo = c.take<unsigned long long> (K.n_tiles + 1);
+  K.tile_hi = c.take<unsigned long long> (K.n_tiles + 1);
+  K.tile_cnt = c.take<long long> (K.n_tiles + 1);
+  K.tile_sum = c.take<long long> (K.n_tiles + 1);
+  K.tile_cnt_begin = R.cnt_begin = c.take<long long> (K.n_tiles + 1);
+  K.tile_sum_begin = R.sum_begin = c.take<long long> (K.n_tiles + 1);
+  R.cub = cub_room (c, 0, K.n_tiles + 1);
+  K.lo = c.take<unsigned long long> ((size_t)capacity);
+  K.hi = c.take<unsigned long long> ((size_t)capacity);
+  K.tx = c.take<uint32_t> ((size_t)capacity);
+  return R;
+}
+
+/* CONTEXT's flags on the device: the two bits, TEXTS only over offsets[] */
+bool
+context_flags_ok (uint32_t flags, const uint64_t *offsets) {
+  return flags <= (ACM_CONTEXT_TEXTS | ACM_CONTEXT_MERGE) && (!(flags & ACM_CONTEXT_TEXTS) || offsets);
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_context_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_texts) {
+  (void)n_texts; /* (nothing here is sized by the number of texts: a record's text is a bisection of offsets[]) */
+  if (!plan || n_or_capacity >= (1ull << 31))
+    return 0;
+  Carve c;
+  ContextK K{};
+  context_carve (c, n_or_capacity, K);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_context_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts,
+                                const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, uint32_t before, uint32_t after, uint32_t flags,
+                                void *d_out, uint64_t out_capacity, uint64_t *d_out_symbols, uint64_t *d_n_snippets, uint64_t *d_snip_lo,
+                                uint64_t *d_out_offsets, uint32_t *d_snip_text, uint32_t *d_rec_snip, int64_t *d_rec_at, void *d_tmp, size_t tmp_bytes,
+                                void *stream) {
+  if (!plan || !d_out_symbols || !d_n_snippets || !d_out_offsets || n >= (1ull << 31) || (n_symbols && !d_text) ||
+      (n && (!d_records || !d_snip_lo || !d_tmp)) || !context_flags_ok (flags, d_offsets) ||
+      (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+    return ACM_GPU_E_ARG;
+  const uint32_t sb = plan->text_sym_bytes;
+  if (!symbols_ok (d_text, n_symbols, sb) || (d_out && (!symbols_ok (d_out, out_capacity, sb) || !apart (d_text, n_symbols, d_out, out_capacity, sb))))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n == 0) { /* (no room: no snippet; a count that came in above 0 is an overflow, which reports the same) */
+    HIP_TRY (hipMemsetAsync (d_n_snippets, 0, 8, st));
+    HIP_TRY (hipMemsetAsync (d_out_symbols, 0, 8, st));
+    HIP_TRY (hipMemsetAsync (d_out_offsets, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  Carve carve (d_tmp);
+  ContextK K{};
+  const ContextRoom L = context_carve (carve, n, K);
+  if (tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  K.text = static_cast<const unsigned char *> (d_text);
+  K.n_symbols = n_symbols;
+  K.pos_base = pos_base;
+  K.offsets = n_texts ? d_offsets : nullptr; /* (no text: no symbol, every record breaks the contract) */
+  K.n_texts = n_texts;
+  K.in = d_records;
+  K.capacity = n;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.before = before;
+  K.after = after;
+  K.flags = flags;
+  K.d_n_snippets = reinterpret_cast<unsigned long long *> (d_n_snippets);
+  K.d_out_symbols = reinterpret_cast<unsigned long long *> (d_out_symbols);
+  K.d_snip_lo = reinterpret_cast<unsigned long long *> (d_snip_lo);
+  K.d_out_offsets = reinterpret_cast<long long *> (d_out_offsets);
+  K.d_snip_text = d_snip_text;
+  K.d_rec_snip = d_rec_snip;
+  K.d_rec_at = reinterpret_cast<long long *> (d_rec_at);
+  K.out = static_cast<unsigned char *> (d_out);
+  K.out_capacity = out_capacity;
+  K.sb = sb;
+  /* ACM_GPU_CONTEXT_OUT_TILE=<bytes of output>: the gather's tile, a multiple of 16 (tests) */
+  K.tile_words = tunable ("ACM_GPU_CONTEXT_OUT_TILE", CONTEXT_OUT_TILE_DEFAULT, CONTEXT_OUT_TILE_MIN, CONTEXT_OUT_TILE_MAX, Tune::Mult16) / 16;
+  K.error = error_word (plan);
+  const bool merge = (flags & ACM_CONTEXT_MERGE) != 0;
+  const dim3 block (CONTEXT_THREADS), tiles_grid = capped_grid (plan, K.n_tiles + 1);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (ContextCtl), st));
+  if (K.offsets) /* one size, whatever the number of texts */
+    HIP_TRY (launch (context_check_kernel, capped_grid (plan, (n_texts + CONTEXT_THREADS - 1) / CONTEXT_THREADS), block, 0, st, K));
+  /* 1. */
+  HIP_TRY (merge ? launch (context_window_kernel<true>, tiles_grid, block, 0, st, K) : launch (context_window_kernel<false>, tiles_grid, block, 0, st, K));
+  if (merge) { /* 2., 3. */
+    HIP_TRY (launch (context_carry_kernel, dim3 (1), block, 0, st, K));
+    HIP_TRY (launch (context_flag_kernel, tiles_grid, block, 0, st, K));
+    HIP_TRY (exclusive_sum (L.cub, K.tile_cnt, L.cnt_begin, K.n_tiles + 1, st));
+  }
+  /* 4. */
+  HIP_TRY (exclusive_sum (L.cub, K.tile_sum, L.sum_begin, K.n_tiles + 1, st));
+  HIP_TRY (merge ? launch (context_index_kernel<true>, tiles_grid, block, 0, st, K) : launch (context_index_kernel<false>, tiles_grid, block, 0, st, K));
+  /* 5. the grid by the room of the output, not by what the passes found */
+  if (d_out && out_capacity)
+    HIP_TRY (launch (context_gather_kernel, capped_grid (plan, (out_capacity * sb + 15 + 16) / ((uint64_t)K.tile_words * 16) + 1), block, 0, st, K));
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_scan_context_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!plan || capacity >= (1ull << 31))
+    return 0;
+  /* (the scan has ended when the context passes begin: they read d_records) */
+  return std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_context_tmp_bytes (plan, capacity, n_texts));
+}
+
+extern "C" int
+acm_gpu_scan_context_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts,
+                             ACMRecord *d_records, uint64_t capacity, uint64_t *d_count, uint32_t before, uint32_t after, uint32_t flags, void *d_out,
+                             uint64_t out_capacity, uint64_t *d_out_symbols, uint64_t *d_n_snippets, uint64_t *d_snip_lo, uint64_t *d_out_offsets,
+                             uint32_t *d_snip_text, uint32_t *d_rec_snip, int64_t *d_rec_at, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || !d_out_symbols || !d_n_snippets || !d_out_offsets || capacity >= (1ull << 31) || (n_symbols && !d_text) ||
+      (capacity && (!d_records || !d_snip_lo || !d_tmp)) || !context_flags_ok (flags, d_offsets) ||
+      (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+    return ACM_GPU_E_ARG;
+  if (d_out && (!symbols_ok (d_out, out_capacity, plan->text_sym_bytes) || !apart (d_text, n_symbols, d_out, out_capacity, plan->text_sym_bytes)))
+    return ACM_GPU_E_ARG; /* (refused before the scan runs, not behind it) */
+  if (capacity && tmp_bytes < acm_gpu_scan_context_tmp_bytes (plan, capacity, n_symbols, n_texts))
+    return ACM_GPU_E_ARG;
+  const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, d_records, capacity, d_count, d_tmp, tmp_bytes, stream);
+  if (rc)
+    return rc;
+  return acm_gpu_context_records_device (plan, d_text, n_symbols, pos_base, d_offsets, n_texts, d_records, capacity, d_count, before, after, flags, d_out,
+                                         out_capacity, d_out_symbols, d_n_snippets, d_snip_lo, d_out_offsets, d_snip_text, d_rec_snip, d_rec_at, d_tmp,
+                                         tmp_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_context_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                           ACMRecord *records, uint64_t capacity, uint64_t *n_found, uint32_t before, uint32_t after, uint32_t flags, void *out,
+                           uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_snippets, uint64_t *snip_lo, uint64_t *out_offsets,
+                           uint32_t *snip_text, uint32_t *rec_snip, int64_t *rec_at) {
+  if (!plan || !n_found || !out_symbols || !n_snippets || capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
+      !context_flags_ok (flags, offsets) || !optional_offsets_ok (offsets, n_texts, n_symbols))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const uint32_t sb = plan->text_sym_bytes;
+  const size_t tmp_bytes = acm_gpu_scan_context_tmp_bytes (plan, capacity, n_symbols, n_texts);
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr, *d_out = nullptr;
+  uint64_t *d_res = nullptr, *d_off = nullptr, *d_lo = nullptr, *d_oo = nullptr; /* d_res: the count, the snippets, the output's symbols */
+  uint32_t *d_st = nullptr, *d_rs = nullptr;
+  int64_t *d_ra = nullptr;
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (temps.get (&d_res, 24));
+  HOST_TRY (temps.get (&d_rec, capacity * 16));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  HOST_TRY (temps.get (&d_lo, capacity * 8));
+  HOST_TRY (temps.get (&d_oo, (capacity + 1) * 8));
+  if (snip_text)
+    HOST_TRY (temps.get (&d_st, capacity * 4));
+  if (rec_snip)
+    HOST_TRY (temps.get (&d_rs, capacity * 4));
+  if (rec_at)
+    HOST_TRY (temps.get (&d_ra, capacity * 8));
+  if (out)
+    HOST_TRY (temps.get (&d_out, (size_t)out_capacity * sb));
+  if (offsets)
+    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  const int rc = settle (plan, acm_gpu_scan_context_device (plan, d_text, n_symbols, pos_base, d_off, n_texts, d_rec, capacity, d_res, before, after, flags,
+                                                            d_out, out_capacity, d_res + 2, d_res + 1, d_lo, d_oo, d_st, d_rs, d_ra, d_tmp, tmp_bytes, nullptr),
+                         true);
+  if (rc)
+    return rc;
+  uint64_t res[3] = { 0, 0, 0 };
+  HOST_TRY (hipMemcpy (res, d_res, 24, hipMemcpyDeviceToHost));
+  *n_found = res[0];
+  if (res[0] > capacity) /* the first meaning: only *n_found is valid */
+    return ACM_GPU_E_OVERFLOW;
+  *n_snippets = res[1];
+  *out_symbols = res[2];
+  if (records && res[0])
+    HOST_TRY (hipMemcpy (records, d_rec, res[0] * 16, hipMemcpyDeviceToHost));
+  if (snip_lo && res[1])
+    HOST_TRY (hipMemcpy (snip_lo, d_lo, res[1] * 8, hipMemcpyDeviceToHost));
+  if (out_offsets)
+    HOST_TRY (hipMemcpy (out_offsets, d_oo, (res[1] + 1) * 8, hipMemcpyDeviceToHost));
+  if (snip_text && res[1])
+    HOST_TRY (hipMemcpy (snip_text, d_st, res[1] * 4, hipMemcpyDeviceToHost));
+  if (rec_snip && res[0])
+    HOST_TRY (hipMemcpy (rec_snip, d_rs, res[0] * 4, hipMemcpyDeviceToHost));
+  if (rec_at && res[0])
+    HOST_TRY (hipMemcpy (rec_at, d_ra, res[0] * 8, hipMemcpyDeviceToHost));
+  if (out && res[2] > out_capacity) /* the second: everything but `out` is valid */
+    return ACM_GPU_E_OVERFLOW;
+  if (out && res[2])
+    HOST_TRY (hipMemcpy (out, d_out, (size_t)res[2] * sb, hipMemcpyDeviceToHost));
+  return ACM_GPU_OK;
+}
+
 /* ------------------------------------------------------------------ anchored matches and dictionary lookup (include/acm_gpu.h, dev_anchored.h)
  * No scan: the check of offsets[], one lane per text walking the goto function from the root, and for
  * the records a prefix sum over the texts' counts and a second walk that writes them. */
@@ -7847,7 +8059,7 @@ namespace {
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally and acm_lookup only a scan that
  * succeeded, acm_select, acm_scan_words, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
  * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_scan_patterns, acm_scan_chains, acm_scan_approx and
- * acm_scan_edit also one whose output had no room. */
+ * acm_scan_edit also one whose output had no room, acm_context either of the two. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
 /* what every machine-level call does around its scan: the route, the machine's plan lock, the
@@ -7873,7 +8085,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The eighteen calls below run on the same route, the same cached plan, under the same lock. */
+/* The nineteen calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -7926,6 +8138,26 @@ acm_scan_words (ACMachine *machine, const void *text, uint64_t n_symbols, const 
     machine, RecordPath::OnSuccessOrOverflow,
     [&] (uint32_t said) { return acm_internal_cpu_scan_words (machine, text, n_symbols, said, ranges, n_ranges, flags, records, capacity, n_found); },
     [&] (ACMPlan *plan) { return acm_gpu_scan_words_host (plan, text, n_symbols, 0, nullptr, 0, ranges, n_ranges, flags, records, capacity, n_found); });
+}
+
+/* the matches of one text with the text around them (include/acm_gpu.h) */
+extern "C" int
+acm_context (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found, uint32_t before,
+             uint32_t after, uint32_t flags, void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_snippets, uint64_t *snip_lo,
+             uint64_t *out_offsets, uint32_t *snip_text, uint32_t *rec_snip, int64_t *rec_at) {
+  if (!machine || !n_found || !out_symbols || !n_snippets || capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
+      !context_flags_ok (flags, nullptr))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      return acm_internal_cpu_context (machine, text, n_symbols, said, records, capacity, n_found, before, after, flags, out, out_capacity, out_symbols,
+                                       n_snippets, snip_lo, out_offsets, snip_text, rec_snip, rec_at);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_scan_context_host (plan, text, n_symbols, 0, nullptr, 0, records, capacity, n_found, before, after, flags, out, out_capacity,
+                                        out_symbols, n_snippets, snip_lo, out_offsets, snip_text, rec_snip, rec_at);
+    });
 }
 
 /* anchored matches and the dictionary lookup of a batch (include/acm_gpu.h) */

@@ -1228,6 +1228,180 @@ acm_internal_cpu_scan_words (ACMachine *m, const void *text, uint64_t n_symbols,
   return acm_words_records (text, n_symbols, sym_bytes, 0, NULL, 0, ranges, n_ranges, flags, records, *n_found, n_found);
 }
 
+/* CONTEXT of a record set (include/acm_gpu.h): the plain sequential pass.  Everything is checked
+ * and every window made first.  MERGE walks the records BACKWARDS: over the windowed records hi
+ * never decreases, so a record joins the run behind it iff its hi reaches the smallest lo of that
+ * run (and, under SYMBOLS, it lies in the same text); a second walk forwards numbers the runs and
+ * measures them.  The output is gathered last, when it is known to have room. */
+#define CONTEXT_WINDOWLESS 0x80000000u /* in tx[]: the record spans a cut (a text is below 2^31) */
+
+/* the largest text with offsets[text] <= pos, pos in [0, offsets[n_texts]), n_texts > 0 */
+static uint64_t
+context_text_of (const uint64_t *offsets, uint64_t n_texts, uint64_t pos) {
+  uint64_t lo = 0, hi = n_texts - 1;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo + 1) / 2;
+    if (offsets[mid] <= pos)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  return lo;
+}
+
+int
+acm_context_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                     const ACMRecord *records, uint64_t n, uint32_t before, uint32_t after, uint32_t flags, void *out, uint64_t out_capacity,
+                     uint64_t *out_symbols, uint64_t *n_snippets, uint64_t *snip_lo, uint64_t *out_offsets, uint32_t *snip_text, uint32_t *rec_snip,
+                     int64_t *rec_at) {
+  if (!out_symbols || !n_snippets || (n_symbols && !text) || (n && !records) || n >= (1ull << 31) ||
+      (sym_bytes != 1 && sym_bytes != 2 && sym_bytes != 4 && sym_bytes != 8) || flags > (ACM_CONTEXT_TEXTS | ACM_CONTEXT_MERGE) ||
+      ((flags & ACM_CONTEXT_TEXTS) && !offsets))
+    return ACM_GPU_E_ARG;
+  if (offsets) {
+    if (n_texts >= (1ull << 31) || offsets[0] != 0 || offsets[n_texts] != n_symbols)
+      return ACM_GPU_E_ARG;
+    for (uint64_t t = 0; t < n_texts; t++)
+      if (offsets[t] > offsets[t + 1])
+        return ACM_GPU_E_ARG;
+  }
+  const int merge = (flags & ACM_CONTEXT_MERGE) != 0, texts = (flags & ACM_CONTEXT_TEXTS) != 0;
+  for (uint64_t j = 0; j < n; j++) {
+    const ACMRecord *r = &records[j];
+    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+      return ACM_GPU_E_ARG;
+    if (merge && j > 0 && records[j - 1].end_pos > r->end_pos)
+      return ACM_GPU_E_ARG;
+  }
+  /* the windows; MERGE: begin[j] says that a snippet begins at record j, lo[j] is then its first symbol */
+  uint64_t *lo = malloc ((n ? n : 1) * (2 * sizeof (uint64_t) + sizeof (uint32_t) + 1));
+  if (!lo)
+    return ACM_GPU_E_NOMEM;
+  uint64_t *hi = lo + (n ? n : 1);
+  uint32_t *tx = (uint32_t *)(hi + (n ? n : 1));
+  unsigned char *begin = (unsigned char *)(tx + (n ? n : 1));
+  for (uint64_t j = 0; j < n; j++) {
+    const uint64_t e = records[j].end_pos - pos_base, s = e + 1 - records[j].length;
+    uint64_t t = 0, t_lo = 0, t_hi = n_symbols; /* the record's text: [t_lo, t_hi) */
+    begin[j] = 0;
+    if (offsets) { /* (n_texts > 0: a record lies in [0, n_symbols) = [0, offsets[n_texts])) */
+      t = context_text_of (offsets, n_texts, s);
+      t_lo = offsets[t];
+      t_hi = offsets[t + 1];
+    }
+    tx[j] = (uint32_t)t;
+    if (e >= t_hi) { /* the match spans a cut: no match of any text */
+      tx[j] |= CONTEXT_WINDOWLESS;
+      lo[j] = hi[j] = s;
+    } else if (texts) {
+      lo[j] = offsets[t > before ? t - before : 0];
+      hi[j] = offsets[n_texts - (t + 1) > after ? t + 1 + after : n_texts];
+    } else {
+      lo[j] = s - t_lo > before ? s - before : t_lo;
+      hi[j] = t_hi - (e + 1) > after ? e + 1 + after : t_hi;
+    }
+  }
+  if (merge) {
+    uint64_t run_lo = 0, run_first = n; /* the run behind the walk: its smallest lo, its first record (n: none yet) */
+    for (uint64_t j = n; j-- > 0;) {
+      if (tx[j] & CONTEXT_WINDOWLESS)
+        continue;
+      if (run_first < n && hi[j] >= run_lo && (texts || tx[j] == tx[run_first])) {
+        run_lo = lo[j] < run_lo ? lo[j] : run_lo;
+      } else {
+        if (run_first < n) {
+          begin[run_first] = 1;
+          lo[run_first] = run_lo;
+        }
+        run_lo = lo[j];
+      }
+      run_first = j;
+    }
+    if (run_first < n) {
+      begin[run_first] = 1;
+      lo[run_first] = run_lo;
+    }
+  }
+  /* the snippets: number, place and length; q = the snippet under way (MERGE) */
+  uint64_t count = 0, all = 0, q_lo = 0, q_at = 0;
+  for (uint64_t j = 0; j < n; j++) {
+    const int windowed = !(tx[j] & CONTEXT_WINDOWLESS);
+    if (merge ? windowed && begin[j] : 1) {
+      q_lo = lo[j];
+      q_at = all;
+      if (snip_lo)
+        snip_lo[count] = q_lo;
+      if (out_offsets)
+        out_offsets[count] = q_at;
+      if (snip_text)
+        snip_text[count] = offsets ? (uint32_t)context_text_of (offsets, n_texts, q_lo) : 0;
+      count++;
+    }
+    if (windowed && hi[j] - q_lo > all - q_at) /* (the snippet reaches as far as its records' windows do) */
+      all = q_at + (hi[j] - q_lo);
+    if (rec_snip)
+      rec_snip[j] = windowed ? (uint32_t)(count - 1) : 0xFFFFFFFFu;
+    if (rec_at)
+      rec_at[j] = windowed ? (int64_t)(q_at + (records[j].end_pos - pos_base + 1 - records[j].length - q_lo)) : -1;
+    if (merge && windowed) /* (the snippet's end so far, for the gather) */
+      hi[j] = q_lo + (all - q_at);
+  }
+  if (out_offsets)
+    out_offsets[count] = all;
+  *n_snippets = count;
+  *out_symbols = all;
+  int rc = ACM_GPU_OK;
+  if (out && all > out_capacity)
+    rc = ACM_GPU_E_OVERFLOW;
+  else if (out) {
+    unsigned char *o = out;
+    for (uint64_t j = 0; j < n; j++) {
+      const int windowed = !(tx[j] & CONTEXT_WINDOWLESS);
+      if (!windowed)
+        continue;
+      if (!merge) {
+        memcpy (o, (const unsigned char *)text + lo[j] * sym_bytes, (hi[j] - lo[j]) * sym_bytes);
+        o += (hi[j] - lo[j]) * sym_bytes;
+        continue;
+      }
+      /* the last record of a run holds the run's end: copy when the next windowed record begins one, or there is none */
+      uint64_t k = j + 1;
+      while (k < n && (tx[k] & CONTEXT_WINDOWLESS))
+        k++;
+      if (begin[j])
+        q_lo = lo[j];
+      if (k == n || begin[k]) {
+        memcpy (o, (const unsigned char *)text + q_lo * sym_bytes, (hi[j] - q_lo) * sym_bytes);
+        o += (hi[j] - q_lo) * sym_bytes;
+      }
+    }
+  }
+  free (lo);
+  return rc;
+}
+
+/* acm_context on the host (include/acm_gpu.h): the caller loop, then the sequential pass over what it
+ * found -- what ACM_SCAN_PATH_CPU_LOOP runs.  Without a record array of the caller's the room is the call's own. */
+int
+acm_internal_cpu_context (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records, uint64_t capacity,
+                          uint64_t *n_found, uint32_t before, uint32_t after, uint32_t flags, void *out, uint64_t out_capacity, uint64_t *out_symbols,
+                          uint64_t *n_snippets, uint64_t *snip_lo, uint64_t *out_offsets, uint32_t *snip_text, uint32_t *rec_snip, int64_t *rec_at) {
+  if (!m || !n_found)
+    return ACM_GPU_E_ARG;
+  ACMRecord *own = NULL;
+  if (!records && capacity) {
+    records = own = malloc (capacity * sizeof (ACMRecord));
+    if (!own)
+      return ACM_GPU_E_NOMEM;
+  }
+  int rc = acm_internal_cpu_scan (m, text, n_symbols, sym_bytes, records, capacity, n_found);
+  if (!rc)
+    rc = acm_context_records (text, n_symbols, sym_bytes, 0, NULL, 0, records, *n_found, before, after, flags, out, out_capacity, out_symbols,
+                              n_snippets, snip_lo, out_offsets, snip_text, rec_snip, rec_at);
+  free (own);
+  return rc;
+}
+
 /* REPLACE of a text under a selection (include/acm_gpu.h): the plain sequential pass.  The records
  * are checked and the output measured first, so that nothing is written when it has no room. */
 int

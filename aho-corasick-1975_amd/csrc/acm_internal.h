@@ -96,6 +96,12 @@ int acm_internal_words_args_ok (uint32_t sym_bytes, const void *ranges, uint32_t
 /* acm_scan_words' host path: the caller loop, then acm_words_records over its records (arguments as acm_scan_words') */
 int acm_internal_cpu_scan_words (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *ranges, uint32_t n_ranges,
                                  uint32_t flags, ACMRecord *records, uint64_t capacity, uint64_t *n_found);
+/* acm_context's host path: the caller loop, then acm_context_records over its records (arguments as acm_context's, the symbol size
+ * behind n_symbols; records NULL: a room of the call's own) */
+int acm_internal_cpu_context (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records, uint64_t capacity,
+                              uint64_t *n_found, uint32_t before, uint32_t after, uint32_t flags, void *out, uint64_t out_capacity,
+                              uint64_t *out_symbols, uint64_t *n_snippets, uint64_t *snip_lo, uint64_t *out_offsets, uint32_t *snip_text,
+                              uint32_t *rec_snip, int64_t *rec_at);
 /* acm_scan_anchored's and acm_lookup's host paths: the caller loop from the root at every offset, then acm_anchored_records over its
  * records (arguments as the public calls'; offsets[] already checked) */
 int acm_internal_cpu_scan_anchored (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint32_t mode,

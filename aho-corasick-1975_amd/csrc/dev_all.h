@@ -183,6 +183,7 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_rules.h"
 #include "dev_split.h"
 #include "dev_words.h"
+#include "dev_context.h"
 #include "dev_anchored.h"
 #include "dev_patterns.h"
 #include "dev_approx.h"

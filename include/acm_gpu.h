@@ -1291,6 +1291,144 @@ int acm_scan_words (ACMachine *machine, const void *text, uint64_t n_symbols,
                     const void *ranges, uint32_t n_ranges, uint32_t flags,
                     ACMRecord *records, uint64_t capacity, uint64_t *n_found);
 
+/* ------------------------------------------------------------------ match contexts: the text around the matches
+ * Every consumer above answers with numbers.  What people do with a match list is look at the text
+ * around it: `grep -C 2` prints the hit lines with their neighbours, a concordance wants 40 symbols
+ * on both sides of every hit, a log triage tool the matching packet with the two in front of it, a
+ * reviewer of acm_scan_approx's, acm_scan_chains' or acm_scan_templates' hits the stretch each one
+ * lies in.  CONTEXT turns records into windows, merges them, and copies them out into one packed
+ * buffer with the index a highlighter needs -- on the device, so that the text need not come back
+ * for it.  It takes ANY record array of the ACMRecord layout: the record sets of acm_scan_words,
+ * acm_select, acm_scan_patterns, acm_scan_approx, acm_scan_chains and acm_scan_templates go through
+ * it unchanged.
+ *
+ * DEFINITION.  Inputs: text[0 .. n_symbols) in the caller's symbols, sym_bytes 1, 2, 4 or 8, copied
+ * bit for bit -- never the class-mapped or interned copy a plan keeps for its scan (acm_replace's
+ * rule); offsets[0 .. n_texts] under the batch contract, or NULL: one text; records r_0 .. r_{m-1}
+ * with pos_base, as in WORDS; `before` and `after`; flags = the unit in bit 0, ACM_CONTEXT_SYMBOLS
+ * (0) or ACM_CONTEXT_TEXTS (1), and the mode in bit 1, ACM_CONTEXT_EACH (0) or ACM_CONTEXT_MERGE
+ * (2).  Flags above 3, and TEXTS with offsets NULL, are ACM_GPU_E_ARG.
+ * For a record r let s = end_pos + 1 - length - pos_base, e = end_pos - pos_base and t the text with
+ * offsets[t] <= s < offsets[t + 1].  A record with e >= offsets[t + 1] spans a cut and is
+ * WINDOWLESS (WORDS' rule: the ordered scan of a packed buffer can be fed in as it is).  The window
+ * W (r) = [lo, hi), all arithmetic saturating (before = 2^32 - 1 is legal):
+ *   SYMBOLS: lo = max (offsets[t], s - before), hi = min (offsets[t + 1], e + 1 + after); with
+ *            offsets NULL offsets[t] is 0 and offsets[t + 1] is n_symbols;
+ *   TEXTS:   lo = offsets[max (0, t - before)], hi = offsets[min (n_texts, t + 1 + after)]: the
+ *            match's text with `before` texts in front and `after` behind, `grep -B` and `grep -A`.
+ * EACH: snippet j is W (r_j), j = 0 .. m - 1, in the order of the input (any order), n_snippets = m;
+ * a windowless record gives an empty snippet, at its own start s.
+ * MERGE: let C be the union of all windows.  The snippets are the maximal runs of consecutive
+ * positions in C, ascending.  Under SYMBOLS a run is also cut at every text boundary inside it: two
+ * windows that touch across offsets[t] stay two snippets, two that touch inside a text are one.
+ * Under TEXTS runs are not cut, a snippet is a run of whole texts: how `grep -C` joins overlapping
+ * and adjacent context groups.  MERGE requires end_pos never to decrease over the records;
+ * canonical order satisfies it.
+ * Outputs: n_snippets; snip_lo[j], the buffer index of the snippet's first symbol, without
+ * pos_base; out_offsets[0 .. n_snippets], out_offsets[0] = 0; out = the concatenation of
+ * text[snip_lo[j] .. snip_lo[j] + len_j); out_symbols = out_offsets[n_snippets]; optional
+ * snip_text[j] (uint32_t), the text that holds the symbol snip_lo[j] (0 without offsets; behind an
+ * empty text under TEXTS it is the first text of the run that has a symbol); optional rec_snip[i]
+ * (uint32_t), the snippet record i lies in, 0xFFFFFFFF (ACM_CONTEXT_NONE) when windowless; optional
+ * rec_at[i] (int64_t), the index in `out` of the match's first symbol, out_offsets[rec_snip[i]] +
+ * s_i - snip_lo[rec_snip[i]], -1 when windowless: the offset map a highlighter uses, the
+ * counterpart of replace's out_start.  n_snippets <= m: the per-snippet arrays are sized by the
+ * record room (out_offsets one more).
+ *
+ * acm_context_records: the plain sequential pass on the host, no device.  n_snippets and out_symbols
+ * are required, every array may be NULL.  `out` NULL: nothing is gathered, *out_symbols still says
+ * what it takes.  ACM_GPU_E_OVERFLOW when out_capacity (symbols) is too small: *out_symbols is the
+ * length needed, nothing is written to `out`, every index array is valid (acm_grep_gather's rule).
+ * ACM_GPU_E_ARG: offsets that break the batch contract, a record outside [pos_base, pos_base +
+ * n_symbols) (its end or its start) or of length 0, MERGE over records whose end_pos decreases, m
+ * or n_texts of 2^31 or more; nothing is written then.
+ *
+ * acm_gpu_context_records_device: the same on the device (dev_context.h).  The text, offsets,
+ * records, d_n and n_or_capacity arguments are acm_gpu_words_records_device's (d_n NULL:
+ * n_or_capacity is the number of records; else *d_n is, and n_or_capacity the room, below 2^31), the
+ * output arguments acm_gpu_replace_records_device's.  d_n_snippets, d_out_symbols (8 bytes each),
+ * d_snip_lo (n_or_capacity entries) and d_out_offsets (n_or_capacity + 1) are required; d_snip_text,
+ * d_rec_snip and d_rec_at (n_or_capacity each) may be NULL.  The call only queues launches on
+ * `stream`, with no host round trip; the plan is used for its device, its caller symbol size and
+ * its grid cap only.  d_out NULL: no gather, *d_out_symbols is still written.  *d_out_symbols >
+ * out_capacity afterwards: it is the capacity needed, d_out is unspecified, nothing was written
+ * outside d_out[0 .. out_capacity) and all index arrays are valid.  *d_n > n_or_capacity (a scan
+ * that overflowed): *d_n_snippets = *d_out_symbols = 0 and nothing else is written.  A contract
+ * violation -- bad offsets, a record out of range, end_pos decreasing under MERGE -- is handled as
+ * replace handles one: a validation pass sees every offset and every record before an address is
+ * formed from it, the two counts are 0, d_out and the arrays are untouched, acm_gpu_plan_status
+ * reports ACM_GPU_E_INTERNAL and nothing is read or written out of bounds.  d_out must not overlap
+ * d_text (ACM_GPU_E_ARG); both may have ANY alignment that is a multiple of the symbol size
+ * (replace's 16-byte-word rule: up to 15 bytes in front of and behind a snippet's source are read,
+ * never beyond the aligned word that holds a byte of it).  The passes work on tiles of 4,096
+ * records (ACM_GPU_CONTEXT_TILE=<records>: a multiple of 64 from 64 to 1 Mi) and the gather on
+ * tiles of 16,384 bytes of the output (ACM_GPU_CONTEXT_OUT_TILE=<bytes>: a multiple of 16 from 256
+ * to 1 Mi), both read from the environment at every call.  d_tmp must hold
+ * acm_gpu_context_tmp_bytes (plan, n_or_capacity, n_texts) bytes: about 20 per record, nothing per
+ * symbol or per text (0 for a call that would be refused).
+ *
+ * acm_gpu_scan_context_device: acm_gpu_scan_ordered_device with emit_from = 0, and the passes above
+ * behind it on `stream`; the records stay in d_records[0 .. *d_count).  The capacity rule is
+ * select's: `capacity` must hold ALL matches.  *d_count > capacity afterwards: it is the scan's
+ * count, *d_n_snippets = *d_out_symbols = 0.  d_tmp must hold acm_gpu_scan_context_tmp_bytes (plan,
+ * capacity, n_symbols, n_texts) bytes: the scan's scratch is reused, it has ended when the context
+ * passes begin.
+ * acm_gpu_scan_context_host: the same from host memory, blocking.  n_found, n_snippets and
+ * out_symbols are required; records and every array may be NULL.  ACM_GPU_E_OVERFLOW has
+ * acm_gpu_grep_lines_host's two meanings, told apart the same way: *n_found > capacity -- only
+ * *n_found is valid --; otherwise *out_symbols > out_capacity -- everything but `out` is valid.
+ * Offsets that break the batch contract are ACM_GPU_E_ARG.
+ * acm_context: the call on the machine itself, for one text (so TEXTS is ACM_GPU_E_ARG), total over
+ * machines exactly as acm_scan_words is (same three paths, same cached plan, acm_scan_path recorded
+ * on success and on either overflow): ACM_SCAN_PATH_CPU_LOOP runs the caller loop and then
+ * acm_context_records.  A missing device stays an error.
+ *
+ * Out of scope: context flags inside acm_grep and acm_grep_lines (their signatures do not change);
+ * several GPUs, streams and flows; highlight markers written into the output (rec_at gives their
+ * places); line numbers (snip_text is the line number under a split). */
+#define ACM_CONTEXT_SYMBOLS 0
+#define ACM_CONTEXT_TEXTS 1
+#define ACM_CONTEXT_EACH 0
+#define ACM_CONTEXT_MERGE 2
+#define ACM_CONTEXT_NONE 0xFFFFFFFFu
+int acm_context_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint64_t pos_base,
+                         const uint64_t *offsets /* may be NULL */, uint64_t n_texts,
+                         const ACMRecord *records, uint64_t n, uint32_t before, uint32_t after, uint32_t flags,
+                         void *out /* may be NULL */, uint64_t out_capacity, uint64_t *out_symbols,
+                         uint64_t *n_snippets, uint64_t *snip_lo, uint64_t *out_offsets,
+                         uint32_t *snip_text, uint32_t *rec_snip, int64_t *rec_at);
+size_t acm_gpu_context_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_texts);
+int acm_gpu_context_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                    const uint64_t *d_offsets /* may be NULL */, uint64_t n_texts,
+                                    const ACMRecord *d_records, uint64_t n_or_capacity, const uint64_t *d_n /* may be NULL */,
+                                    uint32_t before, uint32_t after, uint32_t flags,
+                                    void *d_out /* may be NULL */, uint64_t out_capacity, uint64_t *d_out_symbols,
+                                    uint64_t *d_n_snippets, uint64_t *d_snip_lo, uint64_t *d_out_offsets,
+                                    uint32_t *d_snip_text, uint32_t *d_rec_snip, int64_t *d_rec_at /* the three may be NULL */,
+                                    void *d_tmp, size_t tmp_bytes, void *stream);
+size_t acm_gpu_scan_context_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts);
+int acm_gpu_scan_context_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
+                                 const uint64_t *d_offsets, uint64_t n_texts,
+                                 ACMRecord *d_records, uint64_t capacity, uint64_t *d_count,
+                                 uint32_t before, uint32_t after, uint32_t flags,
+                                 void *d_out, uint64_t out_capacity, uint64_t *d_out_symbols,
+                                 uint64_t *d_n_snippets, uint64_t *d_snip_lo, uint64_t *d_out_offsets,
+                                 uint32_t *d_snip_text, uint32_t *d_rec_snip, int64_t *d_rec_at,
+                                 void *d_tmp, size_t tmp_bytes, void *stream);
+int acm_gpu_scan_context_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base,
+                               const uint64_t *offsets, uint64_t n_texts,
+                               ACMRecord *records /* may be NULL */, uint64_t capacity, uint64_t *n_found,
+                               uint32_t before, uint32_t after, uint32_t flags,
+                               void *out, uint64_t out_capacity, uint64_t *out_symbols,
+                               uint64_t *n_snippets, uint64_t *snip_lo, uint64_t *out_offsets,
+                               uint32_t *snip_text, uint32_t *rec_snip, int64_t *rec_at);   /* blocking */
+int acm_context (ACMachine *machine, const void *text, uint64_t n_symbols,
+                 ACMRecord *records /* may be NULL */, uint64_t capacity, uint64_t *n_found,
+                 uint32_t before, uint32_t after, uint32_t flags,
+                 void *out, uint64_t out_capacity, uint64_t *out_symbols,
+                 uint64_t *n_snippets, uint64_t *snip_lo, uint64_t *out_offsets,
+                 uint32_t *snip_text, uint32_t *rec_snip, int64_t *rec_at);
+
 /* ------------------------------------------------------------------ anchored matches and dictionary lookup
  * Every consumer above rests on the unanchored scan: every occurrence of every keyword anywhere in a
  * text.  The first question asked of table cells, packets and log lines is an anchored one: is this
