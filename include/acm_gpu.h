@@ -199,7 +199,13 @@ int acm_gpu_plan_create_classes (ACMachine *machine, uint32_t sym_bytes, int dev
  * rebuilding its tables and without waiting for the device:
  *   - plans of the start-parallel kernel (2- and 4-byte symbols) are edited in place: only the
  *     words of the new keywords' own states change, and they are written on the stream of the next
- *     scan, in front of it;
+ *     scan, in front of it.  That next scan (any entry point that scans or walks the plan) is the
+ *     one call of such a plan that is NOT only queued: the changed words come from pageable host
+ *     memory, in a copy that returns when `stream` has reached it (hipMemcpyWithStream), and the
+ *     first update of a plan -- its tables still lie in the blob of its creation -- as well as one
+ *     that outgrows the headroom of the tables waits for the whole device
+ *     (hipDeviceSynchronize), allocates and sends the tables again.  Every later scan is
+ *     asynchronous as its entry point says;
  *   - every other plan keeps its tables; the keywords added since it was made are flattened into a
  *     small delta plan of their own (cost independent of the size of the dictionary), scanned
  *     right after the plan into the same record buffer -- the match set of a dictionary is the
