@@ -104,7 +104,7 @@ class TemplateSpec(C.Structure):
 
 _lib = None
 
-# every symbol include/acm.h and include/acm_gpu.h declare
+# every symbol include/acm.h and include/acm_gpu.h (with include/acm_segment.h) declare
 EXPORTS = [
     "ACM_CMP_DEFAULT", "ACM_INCREMENTAL_STRING_MATCHING", "acm_create", "acm_initiate",
     "acm_insert_letter_of_keyword", "acm_insert_end_of_keyword", "acm_match", "acm_matcher_init", "acm_get_match",
@@ -155,6 +155,8 @@ EXPORTS = [
     "acm_chains_check", "acm_chains_records", "acm_gpu_chains_create", "acm_gpu_chains_destroy", "acm_gpu_chains_info",
     "acm_gpu_chains_tmp_bytes", "acm_gpu_chains_records_device", "acm_gpu_scan_chains_tmp_bytes", "acm_gpu_scan_chains_device",
     "acm_gpu_scan_chains_host", "acm_scan_chains",
+    "acm_segment_records", "acm_gpu_segment_tmp_bytes", "acm_gpu_segment_records_device", "acm_gpu_scan_segment_tmp_bytes",
+    "acm_gpu_scan_segment_device", "acm_gpu_scan_segment_host", "acm_segment",
 ]
 
 
@@ -338,6 +340,20 @@ def lib():
     L.acm_gpu_scan_select_host.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
     L.acm_select.restype = i32
     L.acm_select.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_segment_records.restype = i32
+    L.acm_segment_records.argtypes = [vp, u64, vp, u64, u32, C.POINTER(u64), vp]
+    L.acm_gpu_segment_tmp_bytes.restype = sz
+    L.acm_gpu_segment_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_segment_records_device.restype = i32
+    L.acm_gpu_segment_records_device.argtypes = [vp, vp, u64, vp, u64, u64, vp, u64, u32, vp, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_segment_tmp_bytes.restype = sz
+    L.acm_gpu_scan_segment_tmp_bytes.argtypes = [vp, u64, u64, u64]
+    L.acm_gpu_scan_segment_device.restype = i32
+    L.acm_gpu_scan_segment_device.argtypes = [vp, vp, u64, u64, vp, u64, vp, u64, u32, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_segment_host.restype = i32
+    L.acm_gpu_scan_segment_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, u64, u32, vp, u64, C.POINTER(u64), vp]
+    L.acm_segment.restype = i32
+    L.acm_segment.argtypes = [vp, vp, u64, vp, u64, u32, vp, u64, C.POINTER(u64), vp]
     L.acm_replace_records.restype = i32
     L.acm_replace_records.argtypes = [vp, u64, u32, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_gpu_replace_tmp_bytes.restype = sz
@@ -590,6 +606,26 @@ def select_records(array):
     a = np.array(array, dtype=RECORD_DTYPE, copy=True).reshape(-1)
     n = lib().acm_select_records(a.ctypes.data if a.size else None, a.size)
     return a[:n]
+
+
+def _costs(cost):
+    """a cost table as the segment calls take it: uint32, contiguous"""
+    c = np.ascontiguousarray(cost, dtype=np.uint32).reshape(-1)
+    return c, (c.ctypes.data if c.size else None)
+
+
+def segment_records(array, cost, gap_cost):
+    """acm_segment_records(): the minimum-cost tiling of `array` (RECORD_DTYPE, in canonical order) under
+    cost[keyword_id] per record and gap_cost per uncovered symbol (include/acm_segment.h), by the
+    sequential pass on the host.  Returns (records, sums): a new array, `array` is not changed; sums =
+    (the cost of the records, their lengths)."""
+    a = np.array(array, dtype=RECORD_DTYPE, copy=True).reshape(-1)
+    c, cp = _costs(cost)
+    n = C.c_uint64(0)
+    sums = np.zeros(2, np.uint64)
+    _check(lib().acm_segment_records(a.ctypes.data if a.size else None, a.size, cp, c.size, int(gap_cost), C.byref(n), sums.ctypes.data),
+           "acm_segment_records")
+    return a[:n.value], (int(sums[0]), int(sums[1]))
 
 
 def replacement_table(replacements, sym_size, fill=None):
@@ -2176,6 +2212,26 @@ class Machine:
             return out[:n.value]
 
 
+    def segment(self, text, cost, gap_cost, capacity=None):
+        """acm_segment(): the minimum-cost tiling of `text` by the keywords in canonical order, under
+        cost[keyword_id] per match taken and gap_cost per uncovered symbol (include/acm_segment.h).
+        `capacity` must hold ALL matches (they are found first); by default an overflow is repeated
+        once with the size the call reports.  Returns (records, sums)."""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        c, cp = _costs(cost)
+        cap = int(capacity) if capacity is not None else max(1024, t.size // 64)
+        for attempt in (0, 1):
+            out = np.zeros(cap, dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            sums = np.zeros(2, np.uint64)
+            rc = self.L.acm_segment(self.handle, t.ctypes.data, t.size * t.itemsize // self.sym_size, cp, c.size, int(gap_cost),
+                                    out.ctypes.data, cap, C.byref(n), sums.ctypes.data)
+            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_segment")
+            return out[:n.value], (int(sums[0]), int(sums[1]))
+
     def scan_words(self, text, ranges=ASCII_WORD, flags="both", capacity=None):
         """acm_scan_words(): the whole-word matches of `text` in canonical order (see words_records).
         `capacity` must hold ALL matches (they are found first); by default an overflow is repeated
@@ -3470,6 +3526,82 @@ class Plan:
                                                 count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
                "acm_gpu_scan_select_device")
         return records, count, tmp
+
+    def segment_records(self, records, n, pos_lo, span, cost, gap_cost, out=None, count=None, sums=None):
+        """acm_gpu_segment_records_device(): SEGMENT of records[:n] (an int64 [capacity, 2] device tensor
+        in canonical order, every start and end in [pos_lo, pos_lo + span)) under `cost` (a device
+        tensor of int32 / uint32 words, one per keyword) and gap_cost, into `out` (None: a new tensor;
+        may be `records` itself).  `count` (a device tensor of one int64, None: n is the count) holds
+        the number of records on the way in and of selected records on the way out.  Returns (out,
+        count, sums): Python ints read after a synchronise, sums = (cost, lengths)."""
+        import torch
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64
+        assert cost.is_cuda and cost.is_contiguous() and cost.element_size() == 4
+        room = int(records.shape[0]) if count is not None else int(n)
+        if out is None:
+            out = torch.empty((max(room, 1), 2), dtype=torch.int64, device=records.device)
+        assert out.is_cuda and out.is_contiguous() and out.shape[0] >= room and records.shape[0] >= room
+        d_count = count if count is not None else torch.zeros(1, dtype=torch.int64, device=records.device)
+        if sums is None:
+            sums = torch.zeros(2, dtype=torch.int64, device=records.device)
+        tb = lib().acm_gpu_segment_tmp_bytes(self.h, room, span)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
+        _check(lib().acm_gpu_segment_records_device(self.h, records.data_ptr(), room, count.data_ptr() if count is not None else None, pos_lo, span,
+                                                    cost.data_ptr(), cost.numel(), int(gap_cost), out.data_ptr(), d_count.data_ptr(),
+                                                    sums.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_segment_records_device")
+        return out, int(d_count.item()), (int(sums[0].item()), int(sums[1].item()))
+
+    def scan_segment(self, text, cost, gap_cost, offsets=None, n_symbols=None, pos_base=0, capacity=None, records=None, count=None, sums=None,
+                     tmp=None):
+        """acm_gpu_scan_segment_device(): the ordered scan of a device tensor (offsets, a device tensor of
+        int64 [n_texts + 1]: the batch scan) and the minimum-cost tiling of its records, queued on the
+        current stream.  Returns (records, count, sums, tmp): records[:count] is the tiling when count
+        <= capacity; a greater count is the number of ALL matches, the capacity the call needs."""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and cost.is_cuda and cost.is_contiguous() and cost.element_size() == 4
+        if n_symbols is None:
+            n_symbols = text.numel() * text.element_size() // self.sym_size
+        if records is None:
+            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+            records = torch.empty((cap, 2), dtype=torch.int64, device=text.device)
+        if count is None:
+            count = torch.zeros(1, dtype=torch.int64, device=text.device)
+        if sums is None:
+            sums = torch.zeros(2, dtype=torch.int64, device=text.device)
+        n_texts = 0
+        if offsets is not None:
+            assert offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+            n_texts = offsets.numel() - 1
+        tb = lib().acm_gpu_scan_segment_tmp_bytes(self.h, records.shape[0], n_symbols, n_texts)
+        if tmp is None or tmp.numel() < tb:
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        _check(lib().acm_gpu_scan_segment_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
+                                                 n_texts, cost.data_ptr(), cost.numel(), int(gap_cost), records.data_ptr(), records.shape[0],
+                                                 count.data_ptr(), sums.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_scan_segment_device")
+        return records, count, sums, tmp
+
+    def scan_segment_host(self, text, cost, gap_cost, offsets=None, pos_base=0, capacity=None):
+        """acm_gpu_scan_segment_host(): numpy in, (records, sums) out, through the C ABI only (no torch);
+        an overflow is repeated once with the size the call reports."""
+        t = np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        c, cp = _costs(cost)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
+        for attempt in (0, 1):
+            out = np.zeros(cap, dtype=RECORD_DTYPE)
+            n = C.c_uint64(0)
+            sums = np.zeros(2, np.uint64)
+            rc = lib().acm_gpu_scan_segment_host(self.h, t.ctypes.data, n_sym, pos_base, off.ctypes.data if off is not None else None,
+                                                 off.size - 1 if off is not None else 0, cp, c.size, int(gap_cost), out.ctypes.data, cap,
+                                                 C.byref(n), sums.ctypes.data)
+            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
+                cap = int(n.value)
+                continue
+            _check(rc, "acm_gpu_scan_segment_host")
+            return out[:n.value], (int(sums[0]), int(sums[1]))
 
     def scan_select_host(self, text, pos_base=0, capacity=None):
         """acm_gpu_scan_select_host(): numpy in, the selected records out, through the C ABI only (no

@@ -5142,6 +5142,195 @@ acm_gpu_scan_select_host (ACMPlan *plan, const void *text, uint64_t n_symbols, u
   return download_records (rc, d_count, d_rec, records, capacity, n_found);
 }
 
+/* ------------------------------------------------------------------ minimum-cost tiling (include/acm_segment.h, dev_segment.h)
+ * The passes over a record set in canonical order; acm_gpu_scan_segment_device runs them behind the
+ * ordered scan or the batch scan. */
+namespace {
+/* what segment_carve derives beside K's pointers */
+struct SegmentRoom {
+  uint32_t *tile_begin = nullptr; /* K.tile_begin, for the sums that write it */
+  CubRoom cub;
+};
+/* ACM_GPU_SEGMENT_TILE=<records>: the tile of the group and compaction passes, a multiple of 64 (tests) */
+uint32_t
+segment_tile (void) {
+  return tunable ("ACM_GPU_SEGMENT_TILE", SEGMENT_TILE_DEFAULT, SEGMENT_TILE_MIN, SEGMENT_TILE_MAX, Tune::MultWave);
+}
+
+/* ACM_GPU_SEGMENT_LONG=<records>: the groups of so many records take the wave form (tests) */
+uint32_t
+segment_long (void) {
+  return tunable ("ACM_GPU_SEGMENT_LONG", SEGMENT_LONG_DEFAULT, SEGMENT_LONG_MIN, SEGMENT_LONG_MAX, Tune::Any);
+}
+
+SegmentRoom
+segment_carve (Carve &c, uint64_t capacity, SegmentK &K) {
+  SegmentRoom R;
+  const size_t room = (size_t)(capacity ? capacity : 1);
+  K.tile = segment_tile ();
+  K.n_tiles = (capacity + K.tile - 1) / K.tile;
+  K.S.ctl = c.take<SelectCtl> (1);
+  K.ctl = c.take<SegmentCtl> (1);
+  K.tile_min = c.take<unsigned long long> (K.n_tiles + 1);
+  K.tile_count = c.take<uint32_t> (K.n_tiles + 1);
+  K.tile_begin = R.tile_begin = c.take<uint32_t> (K.n_tiles + 1);
+  R.cub = cub_room (c, K.n_tiles + 1, 0);
+  K.S.keyed = c.take<ACMRecord> (room);
+  K.V = c.take<unsigned long long> (room);
+  K.mark = c.take<uint32_t> (room);
+  K.group_first = c.take<uint32_t> (room);
+  K.prev = c.take<uint32_t> (room);
+  K.choice = c.take<uint32_t> (room);
+  K.cfirst = c.take<uint32_t> (room);
+  K.long_list = c.take<uint32_t> (room);
+  return R;
+}
+
+/* what every entry checks of the cost table's shape (the values are the device's to check, or the host entry's) */
+bool
+segment_args_ok (const uint32_t *cost, uint64_t n_keywords, uint32_t gap_cost) {
+  return gap_cost < SEGMENT_COST_LIMIT && n_keywords < (1ull << 32) && (cost || n_keywords == 0);
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_segment_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t span) {
+  (void)span; /* (no order pass: the scratch goes by the records alone) */
+  if (!plan || capacity >= (1ull << 31))
+    return 0;
+  Carve c;
+  SegmentK K{};
+  segment_carve (c, capacity, K);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_segment_records_device (ACMPlan *plan, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, uint64_t pos_lo, uint64_t span,
+                                const uint32_t *d_cost, uint64_t n_keywords, uint32_t gap_cost, ACMRecord *d_out, uint64_t *d_count,
+                                uint64_t *d_sums, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || n >= (1ull << 31) || (n && (!d_records || !d_out || !d_tmp || span == 0)) || !segment_args_ok (d_cost, n_keywords, gap_cost))
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n == 0) { /* (no room) */
+    if (const int rc = no_record (plan, d_n, d_count, st))
+      return rc;
+    if (d_sums)
+      HIP_TRY (hipMemsetAsync (d_sums, 0, 16, st));
+    return ACM_GPU_OK;
+  }
+  Carve carve (d_tmp);
+  SegmentK K{};
+  const SegmentRoom L = segment_carve (carve, n, K);
+  if (tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  K.S.in = d_records;
+  K.S.capacity = n;
+  K.S.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.S.pos_lo = pos_lo;
+  K.S.span = span;
+  K.S.lmax = plan_lmax (plan);
+  K.S.error = error_word (plan);
+  K.cost = d_cost;
+  K.n_keywords = n_keywords;
+  K.gap = gap_cost;
+  K.long_min = segment_long ();
+  K.out = d_out;
+  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
+  K.d_sums = reinterpret_cast<unsigned long long *> (d_sums);
+  HIP_TRY (hipMemsetAsync (K.S.ctl, 0, sizeof (SelectCtl), st));
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (SegmentCtl), st));
+  const dim3 threads (SEGMENT_THREADS), per_record = capped_grid (plan, (n + SEGMENT_THREADS - 1) / SEGMENT_THREADS),
+                                        per_tile = capped_grid (plan, K.n_tiles + 1);
+  /* a. SELECT's keys and contract, then the keyword ids and the costs */
+  HIP_TRY (launch (select_key_kernel, per_record, threads, 0, st, K.S));
+  HIP_TRY (launch (select_drop_kernel, dim3 (1), threads, 0, st, K.S));
+  HIP_TRY (launch (segment_check_kernel, capped_grid (plan, (std::max (n, n_keywords) + SEGMENT_THREADS - 1) / SEGMENT_THREADS), threads, 0, st, K));
+  /* b. the groups */
+  HIP_TRY (launch (segment_min_kernel, per_tile, threads, 0, st, K));
+  HIP_TRY (launch (segment_carry_kernel, dim3 (1), threads, 0, st, K));
+  HIP_TRY (launch (segment_flag_kernel, per_tile, threads, 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, K.tile_count, L.tile_begin, K.n_tiles + 1, st));
+  HIP_TRY (launch (segment_place_kernel<false>, per_tile, threads, 0, st, K));
+  /* c. d. e. */
+  HIP_TRY (launch (segment_link_kernel, per_record, threads, 0, st, K));
+  HIP_TRY (launch (segment_lane_kernel, per_record, threads, 0, st, K));
+  HIP_TRY (launch (segment_wave_kernel, capped_grid (plan, (n + K.long_min - 1) / K.long_min), dim3 (WAVE), 0, st, K));
+  /* f. */
+  HIP_TRY (launch (segment_count_kernel, per_tile, threads, 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, K.tile_count, L.tile_begin, K.n_tiles + 1, st));
+  HIP_TRY (launch (segment_place_kernel<true>, per_tile, threads, 0, st, K));
+  HIP_TRY (launch (segment_finish_kernel, dim3 (1), dim3 (WAVE), 0, st, K));
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_scan_segment_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!plan || capacity >= (1ull << 31))
+    return 0;
+  /* (one room for both forms of the call: the scan's scratch is free again when the passes begin, they read d_records) */
+  const size_t scans = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_scan_batch_tmp_bytes (plan, capacity, n_symbols, n_texts));
+  return std::max (scans, acm_gpu_segment_tmp_bytes (plan, capacity, n_symbols));
+}
+
+extern "C" int
+acm_gpu_scan_segment_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts,
+                             const uint32_t *d_cost, uint64_t n_keywords, uint32_t gap_cost, ACMRecord *d_records, uint64_t capacity,
+                             uint64_t *d_count, uint64_t *d_sums, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_count || capacity >= (1ull << 31) || (n_symbols && !d_text) || (capacity && (!d_records || !d_tmp)) ||
+      (d_offsets && (pos_base || n_texts >= (1ull << 31))) || !segment_args_ok (d_cost, n_keywords, gap_cost) || n_keywords < plan->covered_keywords)
+    return ACM_GPU_E_ARG;
+  if (capacity && tmp_bytes < acm_gpu_scan_segment_tmp_bytes (plan, capacity, n_symbols, n_texts))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  if (d_sums) /* (what stays when the passes do not run: no room, no text) */
+    HIP_TRY (hipMemsetAsync (d_sums, 0, 16, static_cast<hipStream_t> (stream)));
+  int rc;
+  if (!d_offsets)
+    rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, d_records, capacity, d_count, d_tmp, tmp_bytes, stream);
+  else
+    rc = acm_gpu_scan_batch_device (plan, d_text, n_symbols, d_offsets, n_texts, d_records, nullptr, nullptr, capacity, d_count, d_tmp, tmp_bytes, stream);
+  if (rc || capacity == 0 || n_symbols == 0) /* (no room: *d_count says what the records need; no text: 0) */
+    return rc;
+  return acm_gpu_segment_records_device (plan, d_records, capacity, d_count, pos_base, n_symbols, d_cost, n_keywords, gap_cost, d_records, d_count,
+                                         d_sums, d_tmp, tmp_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_segment_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                           const uint32_t *cost, uint64_t n_keywords, uint32_t gap_cost, ACMRecord *records, uint64_t capacity, uint64_t *n_found,
+                           uint64_t sums[2]) {
+  if (!plan || !n_found || capacity >= (1ull << 31) || (n_symbols && !text) || (capacity && !records) || (offsets && pos_base) ||
+      !segment_args_ok (cost, n_keywords, gap_cost) || n_keywords < plan->covered_keywords || !optional_offsets_ok (offsets, n_texts, n_symbols))
+    return ACM_GPU_E_ARG;
+  for (uint64_t k = 0; k < n_keywords; k++)
+    if (cost[k] >= SEGMENT_COST_LIMIT)
+      return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tmp_bytes = acm_gpu_scan_segment_tmp_bytes (plan, capacity, n_symbols, n_texts);
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the count, the sums */
+  uint32_t *d_cost = nullptr;
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (temps.get (&d_res, 24));
+  HOST_TRY (temps.get (&d_rec, capacity * 16));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  HOST_TRY (temps.get (&d_cost, n_keywords * 4));
+  if (n_keywords)
+    HOST_TRY (hipMemcpy (d_cost, cost, n_keywords * 4, hipMemcpyHostToDevice));
+  if (offsets)
+    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  const int rc = acm_gpu_scan_segment_device (plan, d_text, n_symbols, pos_base, d_off, n_texts, d_cost, n_keywords, gap_cost, d_rec, capacity, d_res,
+                                              d_res + 1, d_tmp, tmp_bytes, nullptr);
+  return download_records (rc, d_res, d_rec, records, capacity, n_found, nullptr, [&] (uint64_t) -> int {
+    if (sums)
+      HOST_TRY (hipMemcpy (sums, d_res + 1, 16, hipMemcpyDeviceToHost));
+    return (int)ACM_GPU_OK;
+  });
+}
+
 /* ------------------------------------------------------------------ search-and-replace (include/acm_gpu.h, dev_replace.h)
  * The passes behind a selection: validate and measure, the prefix over the chunks and the records'
  * places in the output, the output itself. */
@@ -8126,6 +8315,20 @@ acm_select (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord 
     machine, RecordPath::OnSuccessOrOverflow,
     [&] (uint32_t said) { return acm_internal_cpu_select (machine, text, n_symbols, said, records, capacity, n_found); },
     [&] (ACMPlan *plan) { return acm_gpu_scan_select_host (plan, text, n_symbols, 0, records, capacity, n_found); });
+}
+
+/* the minimum-cost tiling (include/acm_segment.h) */
+extern "C" int
+acm_segment (ACMachine *machine, const void *text, uint64_t n_symbols, const uint32_t *cost, uint64_t n_keywords, uint32_t gap_cost,
+             ACMRecord *records, uint64_t capacity, uint64_t *n_found, uint64_t sums[2]) {
+  if (!machine || !n_found || (n_symbols && !text) || (capacity && !records) || !segment_args_ok (cost, n_keywords, gap_cost))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) { return acm_internal_cpu_segment (machine, text, n_symbols, said, cost, n_keywords, gap_cost, records, capacity, n_found, sums); },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_scan_segment_host (plan, text, n_symbols, 0, nullptr, 0, cost, n_keywords, gap_cost, records, capacity, n_found, sums);
+    });
 }
 
 /* whole-word matches of one text (include/acm_gpu.h) */

@@ -1138,6 +1138,104 @@ acm_select_records (ACMRecord *records, uint64_t n) {
   return out;
 }
 
+/* SEGMENT of records in canonical order (include/acm_segment.h), in place in the front of the array:
+ * the definition run sequentially, over the records and not over the positions -- V[i] is best[] behind
+ * record i among the records up to i, so V of the last record of an end class is best[end + 1], and
+ * best[] at a start is V of the last record that ends in front of it plus the uncovered symbols
+ * between.  Everything is checked first, so that nothing is modified when the call fails.  Starts are
+ * signed.  The output never overwrites a record that is still to be read: it goes forward and holds
+ * fewer records than were read. */
+int
+acm_segment_records (ACMRecord *records, uint64_t n, const uint32_t *cost, uint64_t n_keywords, uint32_t gap_cost, uint64_t *n_selected,
+                     uint64_t sums[2]) {
+  const uint32_t limit = 1u << 24;
+  if (!n_selected || (n && !records) || (n_keywords && !cost) || gap_cost >= limit || n >= (1ull << 32) - 1)
+    return ACM_GPU_E_ARG;
+  for (uint64_t k = 0; k < n_keywords; k++)
+    if (cost[k] >= limit)
+      return ACM_GPU_E_ARG;
+  int64_t base = INT64_MAX;
+  for (uint64_t i = 0; i < n; i++) {
+    const ACMRecord *r = &records[i];
+    if (r->keyword_id >= n_keywords || r->length == 0 || r->end_pos > (uint64_t)INT64_MAX - 1 || (i && r->end_pos < records[i - 1].end_pos))
+      return ACM_GPU_E_ARG;
+    const int64_t start = (int64_t)r->end_pos + 1 - (int64_t)r->length;
+    if (start < base)
+      base = start;
+  }
+  if (n && (uint64_t)((int64_t)records[n - 1].end_pos - base) >= (1ull << 40))
+    return ACM_GPU_E_ARG;
+  *n_selected = 0;
+  if (sums)
+    sums[0] = sums[1] = 0;
+  if (n == 0)
+    return ACM_GPU_OK;
+  const uint32_t none = 0xFFFFFFFFu;
+  uint64_t *V = malloc (n * sizeof *V);
+  uint32_t *prev = malloc (n * sizeof *prev), *choice = malloc (n * sizeof *choice), *cfirst = malloc (n * sizeof *cfirst);
+  unsigned char *taken = calloc (n, 1);
+  int rc = ACM_GPU_E_NOMEM;
+  if (V && prev && choice && cfirst && taken) {
+    const uint64_t gap = gap_cost;
+    uint64_t gap_path = 0, best_w = 0;
+    uint32_t best_i = none, cls = 0;
+    for (uint64_t i = 0; i < n; i++) {
+      const ACMRecord *r = &records[i];
+      const int64_t end = (int64_t)r->end_pos, start = end + 1 - (int64_t)r->length;
+      uint64_t lo = 0, hi = i; /* the records in front of lo end in front of start, those from hi on do not */
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if ((int64_t)records[mid].end_pos < start)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      prev[i] = lo ? (uint32_t)(lo - 1) : none;
+      if (i == 0 || records[i - 1].end_pos != r->end_pos) { /* a new end class */
+        gap_path = i ? V[i - 1] + gap * (uint64_t)(end - (int64_t)records[i - 1].end_pos) : gap * (uint64_t)(end + 1 - base);
+        best_i = none;
+        cls = (uint32_t)i;
+      }
+      const uint64_t w = (lo ? V[lo - 1] + gap * (uint64_t)(start - (int64_t)records[lo - 1].end_pos - 1) : gap * (uint64_t)(start - base)) + cost[r->keyword_id];
+      const ACMRecord *b = best_i != none ? &records[best_i] : NULL;
+      if (!b || w < best_w || (w == best_w && (r->length > b->length || (r->length == b->length && r->keyword_id < b->keyword_id)))) {
+        best_w = w;
+        best_i = (uint32_t)i;
+      }
+      const int covered = best_w <= gap_path; /* a keyword wins a tie against uncovered symbols */
+      V[i] = covered ? best_w : gap_path;
+      choice[i] = covered ? best_i : none;
+      cfirst[i] = cls;
+    }
+    for (uint32_t at = (uint32_t)(n - 1);;) { /* backwards from the last class */
+      uint32_t next;
+      if (choice[at] != none) {
+        taken[choice[at]] = 1;
+        next = prev[choice[at]];
+      } else
+        next = cfirst[at] ? cfirst[at] - 1 : none;
+      if (next == none)
+        break;
+      at = next;
+    }
+    uint64_t out = 0, sum_cost = 0, sum_len = 0;
+    for (uint64_t i = 0; i < n; i++)
+      if (taken[i]) {
+        sum_cost += cost[records[i].keyword_id];
+        sum_len += records[i].length;
+        records[out++] = records[i];
+      }
+    *n_selected = out;
+    if (sums) {
+      sums[0] = sum_cost;
+      sums[1] = sum_len;
+    }
+    rc = ACM_GPU_OK;
+  }
+  free (taken), free (cfirst), free (choice), free (prev), free (V);
+  return rc;
+}
+
 /* WORDS of a record set (include/acm_gpu.h): the plain sequential pass, in place in the front of the
  * array.  Symbols are unsigned little-endian integers of sym_bytes bytes.  Everything is checked
  * first, so that nothing is modified when the call fails. */
@@ -1589,6 +1687,21 @@ acm_internal_cpu_select (ACMachine *m, const void *text, uint64_t n_symbols, uin
   const int rc = acm_internal_cpu_scan (m, text, n_symbols, sym_bytes, records, capacity, n_found);
   if (!rc)
     *n_found = acm_select_records (records, *n_found);
+  return rc;
+}
+
+/* the loop, then SEGMENT.  The table covers every keyword of the machine, as on the GPU paths. */
+int
+acm_internal_cpu_segment (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint32_t *cost, uint64_t n_keywords,
+                          uint32_t gap_cost, ACMRecord *records, uint64_t capacity, uint64_t *n_found, uint64_t sums[2]) {
+  if (!m || n_keywords < acm_nb_keywords (m))
+    return ACM_GPU_E_ARG;
+  for (uint64_t k = 0; k < n_keywords; k++)
+    if (cost[k] >= (1u << 24))
+      return ACM_GPU_E_ARG;
+  int rc = acm_internal_cpu_scan (m, text, n_symbols, sym_bytes, records, capacity, n_found);
+  if (!rc)
+    rc = acm_segment_records (records, *n_found, cost, n_keywords, gap_cost, n_found, sums);
   return rc;
 }
 

@@ -72,6 +72,8 @@ int acm_internal_cpu_grep_hits (ACMachine *m, const void *text, const uint64_t *
  * with the symbol size behind the text; the public call has checked them.  The record room is the call's own and grown once. */
 int acm_internal_cpu_select (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records, uint64_t capacity,
                              uint64_t *n_found);
+int acm_internal_cpu_segment (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint32_t *cost, uint64_t n_keywords,
+                              uint32_t gap_cost, ACMRecord *records, uint64_t capacity, uint64_t *n_found, uint64_t sums[2]);
 int acm_internal_cpu_replace (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *repl_data, const uint64_t *repl_off,
                               uint64_t n_keywords, void *out, uint64_t out_capacity, uint64_t *out_symbols, uint64_t *n_replaced);
 int acm_internal_cpu_tokenize (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,

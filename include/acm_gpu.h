@@ -2299,3 +2299,4 @@ int acm_gpu_synth_text (int device, void *d_text, uint64_t n, uint64_t global_be
 }
 #endif
 #endif
+#include "acm_segment.h"
