@@ -22,6 +22,9 @@ ACM_WORDS_LEFT, ACM_WORDS_RIGHT, ACM_WORDS_BOTH = 1, 2, 3
 ACM_CONTEXT_SYMBOLS, ACM_CONTEXT_TEXTS, ACM_CONTEXT_EACH, ACM_CONTEXT_MERGE = 0, 1, 0, 2
 ACM_CONTEXT_NONE = 0xFFFFFFFF
 ACM_RULE_NO_MAX = 0xFFFFFFFF
+ACM_SCORE_NO_CAP = 0xFFFFFFFF
+ACM_SCORE_NONE = 0xFFFFFFFF
+ACM_SCORE_TOP_MAX = 256
 ACM_ANCHORED_PREFIXES, ACM_ANCHORED_LONGEST, ACM_ANCHORED_WHOLE = 1, 2, 3
 ACM_LOOKUP_NONE = 0xFFFFFFFF
 # the usual ASCII word set as inclusive (lo, hi) ranges: 0-9, A-Z, _, a-z (UTF-8 byte text adds (0x80, 0xFF))
@@ -79,6 +82,10 @@ class RulesInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rules", "terms", "always_rules", "postings", "fast_texts", "wide_texts")]
 
 
+class ScoreInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("classes", "terms", "postings", "always_classes", "fast_texts", "wide_texts")]
+
+
 class PatternsInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("patterns", "terms", "anchor_keywords", "longest", "max_anchor_postings")]
 
@@ -104,7 +111,7 @@ class TemplateSpec(C.Structure):
 
 _lib = None
 
-# every symbol include/acm.h and include/acm_gpu.h (with include/acm_segment.h) declare
+# every symbol include/acm.h and include/acm_gpu.h (with include/acm_segment.h and include/acm_score.h) declare
 EXPORTS = [
     "ACM_CMP_DEFAULT", "ACM_INCREMENTAL_STRING_MATCHING", "acm_create", "acm_initiate",
     "acm_insert_letter_of_keyword", "acm_insert_end_of_keyword", "acm_match", "acm_matcher_init", "acm_get_match",
@@ -157,6 +164,9 @@ EXPORTS = [
     "acm_gpu_scan_chains_host", "acm_scan_chains",
     "acm_segment_records", "acm_gpu_segment_tmp_bytes", "acm_gpu_segment_records_device", "acm_gpu_scan_segment_tmp_bytes",
     "acm_gpu_scan_segment_device", "acm_gpu_scan_segment_host", "acm_segment",
+    "acm_score_check", "acm_score_matrix", "acm_score_top", "acm_gpu_score_create", "acm_gpu_score_destroy", "acm_gpu_score_info",
+    "acm_gpu_score_matrix_tmp_bytes", "acm_gpu_score_matrix_device", "acm_gpu_score_top_tmp_bytes", "acm_gpu_score_top_device",
+    "acm_gpu_score_tmp_bytes", "acm_gpu_score_device", "acm_gpu_score_host", "acm_score",
 ]
 
 
@@ -340,6 +350,33 @@ def lib():
     L.acm_gpu_scan_select_host.argtypes = [vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
     L.acm_select.restype = i32
     L.acm_select.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_score_check.restype = i32
+    L.acm_score_check.argtypes = [vp, vp, vp, vp, u64, u64]
+    L.acm_score_matrix.restype = i32
+    L.acm_score_matrix.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), vp]
+    L.acm_score_top.restype = i32
+    L.acm_score_top.argtypes = [vp, vp, vp, u64, u64, u32, vp, vp, vp, vp]
+    L.acm_gpu_score_create.restype = i32
+    L.acm_gpu_score_create.argtypes = [vp, vp, vp, vp, vp, u64, C.POINTER(vp)]
+    L.acm_gpu_score_destroy.restype = None
+    L.acm_gpu_score_destroy.argtypes = [vp]
+    L.acm_gpu_score_info.restype = i32
+    L.acm_gpu_score_info.argtypes = [vp, C.POINTER(ScoreInfo)]
+    L.acm_gpu_score_matrix_tmp_bytes.restype = sz
+    L.acm_gpu_score_matrix_tmp_bytes.argtypes = [vp, vp, u64]
+    L.acm_gpu_score_matrix_device.restype = i32
+    L.acm_gpu_score_matrix_device.argtypes = [vp, vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_score_top_tmp_bytes.restype = sz
+    L.acm_gpu_score_top_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_score_top_device.restype = i32
+    L.acm_gpu_score_top_device.argtypes = [vp, vp, vp, vp, u64, u64, u64, u32, vp, vp, vp, vp, vp, sz, vp]
+    L.acm_gpu_score_tmp_bytes.restype = sz
+    L.acm_gpu_score_tmp_bytes.argtypes = [vp, vp, u64, u64, u64, u64, u64, u64, u32]
+    L.acm_gpu_score_device.restype = i32
+    L.acm_gpu_score_device.argtypes = [vp, vp, vp, u64, vp, u64, u64, u64, u64, vp, vp, vp, u64, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    for fn in (L.acm_gpu_score_host, L.acm_score):
+        fn.restype = i32
+        fn.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), vp, u32, vp, vp, vp, vp, C.POINTER(u64)]
     L.acm_segment_records.restype = i32
     L.acm_segment_records.argtypes = [vp, u64, vp, u64, u32, C.POINTER(u64), vp]
     L.acm_gpu_segment_tmp_bytes.restype = sz
@@ -1038,6 +1075,148 @@ def _rules_host_call(fn, what, handle, t, sym_size, off, ruleset):
     def call(fired_ptr, fired, cap, n):
         return fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, *rs.args(), fired_ptr, fired, cap, n, C.byref(total))
     return _fired_host_call(call, what, n_texts, total)
+
+
+def weight(k, w, cap=None):
+    """the term `w times the count of keyword k`, the count taken as at most `cap` (None: no cap; 1: presence)"""
+    return (int(k), int(w), ACM_SCORE_NO_CAP if cap is None else int(cap))
+
+
+def score_class(terms, bias=0, threshold=1):
+    """a class: (terms, bias, threshold) -- its score is bias + the sum of its weight() terms, kept where it reaches threshold"""
+    return [tuple(int(x) for x in t) for t in terms], int(bias), int(threshold)
+
+
+SCORE_TERM_DTYPE = np.dtype([("keyword_id", "<u4"), ("weight", "<i4"), ("cap", "<u4")])
+
+
+class ScoreModel:
+    """classes (what score_class() returns) packed to the four arrays the C calls take: terms
+    (SCORE_TERM_DTYPE), class_ptr (uint64, n_classes + 1), bias and threshold (int64)."""
+
+    def __init__(self, classes):
+        classes = [c if len(c) == 3 and isinstance(c[1], int) else score_class(c) for c in classes]
+        self.n_classes = len(classes)
+        flat = [t for terms, _, _ in classes for t in terms]
+        self.terms = np.array(flat, dtype=SCORE_TERM_DTYPE) if flat else np.zeros(0, SCORE_TERM_DTYPE)
+        self.class_ptr = np.zeros(self.n_classes + 1, np.uint64)
+        if classes:
+            np.cumsum([len(terms) for terms, _, _ in classes], out=self.class_ptr[1:])
+        self.bias = np.array([b for _, b, _ in classes], dtype=np.int64)
+        self.threshold = np.array([t for _, _, t in classes], dtype=np.int64)
+
+    def args(self):
+        """(terms, class_ptr, bias, threshold, n_classes) as the C calls take them"""
+        return (self.terms.ctypes.data if self.terms.size else None, self.class_ptr.ctypes.data, self.bias.ctypes.data if self.n_classes else None,
+                self.threshold.ctypes.data if self.n_classes else None, self.n_classes)
+
+    def check(self, n_keywords):
+        """acm_score_check(): raises ACMError (ACM_GPU_E_ARG) for a model the calls would refuse"""
+        _check(lib().acm_score_check(*self.args(), int(n_keywords)), "acm_score_check")
+
+
+def _scoremodel(model):
+    return model if isinstance(model, ScoreModel) else ScoreModel(model)
+
+
+class Scored:
+    """What the score calls return: the kept part of the text x class score matrix of a batch in CSR
+    form -- kept_ptr (n_texts + 1 entries), kept_class (ascending within a row) and kept_score --, best
+    (the class of every text's largest kept score, ACM_SCORE_NONE for an empty row; None where the call
+    did not make it) and, from a call with k > 0, class_hits (kept texts per class), top_n, top_text and
+    top_score ([n_classes, k]; ACM_SCORE_NONE and 0 beyond top_n).  int64 / int32 device tensors from
+    Plan.score(), Plan.score_matrix() and Plan.score_top() -- the kept arrays have room for kept_capacity
+    entries, their first n_kept count --, numpy arrays cut to size from the host calls.  n_kept, total,
+    need and need_pairs are Python ints as Fired has them: n_kept > kept_capacity says that the kept
+    arrays had no room (best is unspecified, the top arrays are zero then), need > capacity or
+    need_pairs > pair_capacity that the tally in front overflowed -- n_kept = 0 then."""
+
+    def __init__(self, kept_ptr, kept_class, kept_score, n_kept, best=None, class_hits=None, top_n=None, top_text=None, top_score=None, total=None,
+                 need=None, need_pairs=None, kept_capacity=None):
+        self.kept_ptr, self.kept_class, self.kept_score, self.n_kept, self.best = kept_ptr, kept_class, kept_score, n_kept, best
+        self.class_hits, self.top_n, self.top_text, self.top_score = class_hits, top_n, top_text, top_score
+        self.total, self.need, self.need_pairs, self.kept_capacity = total, need, need_pairs, kept_capacity
+
+    def to_sparse_csr(self, n_classes):
+        """The kept scores as a torch.sparse_csr_tensor of n_texts x n_classes (int64), built on the
+        arrays where they are."""
+        import torch
+
+        def tensor(a, dtype):
+            return a.view(dtype) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).view(dtype)
+        return torch.sparse_csr_tensor(tensor(self.kept_ptr, torch.int64), tensor(self.kept_class, torch.int32)[:self.n_kept],
+                                       tensor(self.kept_score, torch.int64)[:self.n_kept], size=(self.kept_ptr.shape[0] - 1, int(n_classes)))
+
+
+def _top_host_arrays(n_classes, k):
+    return (np.zeros(n_classes, np.uint64), np.zeros(n_classes, np.uint32), np.zeros((n_classes, k), np.uint32), np.zeros((n_classes, k), np.int64))
+
+
+def _ptr(a):
+    return a.ctypes.data if a.size else None
+
+
+def _scored_host_call(call, what, n_texts, n_classes, k, total=None):
+    """call(kept_ptr, kept_class, kept_score, capacity, n_kept, best, top arrays...) -> rc, for acm_score_matrix /
+    acm_gpu_score_host / acm_score: a Scored of numpy arrays out.  An output overflow is repeated once with the size
+    the call reports."""
+    kept_ptr, best = np.zeros(n_texts + 1, np.uint64), np.full(n_texts, ACM_SCORE_NONE, np.uint32)
+    hits, top_n, top_text, top_score = _top_host_arrays(n_classes, k)
+    cap = max(1024, n_texts)
+    for attempt in (0, 1):
+        kept_class, kept_score = np.zeros(cap, np.uint32), np.zeros(cap, np.int64)
+        n = C.c_uint64(0)
+        rc = call(kept_ptr.ctypes.data, kept_class.ctypes.data, kept_score.ctypes.data, cap, C.byref(n), _ptr(best), _ptr(hits), _ptr(top_n),
+                  _ptr(top_text), _ptr(top_score))
+        if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
+            cap = int(n.value)
+            continue
+        _check(rc, what)
+        m = int(n.value)
+        top = (hits, top_n, top_text, top_score) if k else (None, None, None, None)
+        return Scored(kept_ptr, kept_class[:m], kept_score[:m], m, best, *top, total=int(total.value) if total is not None else None, kept_capacity=cap)
+
+
+def score_matrix(tallied, model, n_keywords):
+    """acm_score_matrix(): the kept scores of every text, given the count matrix `tallied` (a
+    TalliedBatch of numpy arrays), by the sequential evaluation on the host.  Returns a Scored of numpy
+    arrays (no top arrays: score_top())."""
+    sm = _scoremodel(model)
+    row_ptr = np.ascontiguousarray(tallied.row_ptr, dtype=np.uint64)
+    col = np.ascontiguousarray(tallied.col, dtype=np.uint32)
+    val = np.ascontiguousarray(tallied.val, dtype=np.uint64)
+    assert row_ptr.size >= 1, "row_ptr has n_texts + 1 entries"
+
+    def call(kept_ptr, kept_class, kept_score, cap, n, best, *top):
+        return lib().acm_score_matrix(row_ptr.ctypes.data, _ptr(col), _ptr(val), row_ptr.size - 1, int(n_keywords), *sm.args(), kept_ptr, kept_class,
+                                      kept_score, cap, n, best)
+    return _scored_host_call(call, "acm_score_matrix", row_ptr.size - 1, sm.n_classes, 0)
+
+
+def score_top(scored, n_classes, k):
+    """acm_score_top(): TOP of a Scored of numpy arrays on the host; returns it with class_hits, top_n, top_text and
+    top_score ([n_classes, k]) filled in."""
+    kept_ptr = np.ascontiguousarray(scored.kept_ptr, dtype=np.uint64)
+    kept_class = np.ascontiguousarray(scored.kept_class, dtype=np.uint32)
+    kept_score = np.ascontiguousarray(scored.kept_score, dtype=np.int64)
+    hits, top_n, top_text, top_score = _top_host_arrays(int(n_classes), int(k))
+    _check(lib().acm_score_top(kept_ptr.ctypes.data, _ptr(kept_class), _ptr(kept_score), kept_ptr.size - 1, int(n_classes), int(k), _ptr(hits),
+                               _ptr(top_n), _ptr(top_text), _ptr(top_score)), "acm_score_top")
+    scored.class_hits, scored.top_n, scored.top_text, scored.top_score = hits, top_n, top_text, top_score
+    return scored
+
+
+def _score_host_call(fn, what, handle, t, sym_size, off, model, k):
+    """acm_gpu_score_host / acm_score: numpy in, a Scored of numpy arrays out"""
+    sm = _scoremodel(model)
+    n_texts = off.size - 1
+    assert t.size * t.itemsize == int(off[-1]) * sym_size, "the last offset is the number of symbols"
+    total = C.c_uint64(0)
+
+    def call(kept_ptr, kept_class, kept_score, cap, n, best, hits, top_n, top_text, top_score):
+        return fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, *sm.args(), kept_ptr, kept_class, kept_score, cap, n, best,
+                  int(k), hits, top_n, top_text, top_score, C.byref(total))
+    return _scored_host_call(call, what, n_texts, sm.n_classes, int(k), total)
 
 
 class PatternSet:
@@ -2426,6 +2605,39 @@ class Machine:
         packed, offsets = self._pack_texts(texts)
         return _rules_host_call(self.L.acm_rules, "acm_rules", self.handle, packed, self.sym_size, offsets, ruleset)
 
+    def score(self, texts, model, k=0):
+        """acm_score(): the kept scores of `model` (a ScoreModel, or a list of score_class()es) for every
+        text of a list of texts, each scanned from the root on its own in ONE call, every text's best
+        class and, with k > 0, every class's best k texts.  Returns a Scored of numpy arrays."""
+        packed, offsets = self._pack_texts(texts)
+        return _score_host_call(self.L.acm_score, "acm_score", self.handle, packed, self.sym_size, offsets, model, k)
+
+
+class Score:
+    """A score model on a plan's device (ACMScore): Plan.score_create() makes one."""
+
+    def __init__(self, handle, n_classes):
+        self.h = handle
+        self.n_classes = n_classes
+
+    def info(self):
+        """acm_gpu_score_info(): classes, terms, postings, always_classes and the texts the model's
+        evaluations sent through the fast and the wide form so far, as a dict; waits for the device."""
+        i = ScoreInfo()
+        _check(lib().acm_gpu_score_info(self.h, C.byref(i)), "acm_gpu_score_info")
+        return {n: int(getattr(i, n)) for n, _ in ScoreInfo._fields_}
+
+    def close(self):
+        if self.h:
+            lib().acm_gpu_score_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class Replaced:
     """What Plan.replace_records() and Plan.scan_replace() leave on the device: `out` (a uint8 tensor,
@@ -3104,6 +3316,139 @@ class Plan:
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         assert off.size >= 1, "offsets has n_texts + 1 entries"
         return _rules_host_call(lib().acm_gpu_rules_host, "acm_gpu_rules_host", self.h, t, self.sym_size, off, ruleset)
+
+    def score_create(self, model):
+        """acm_gpu_score_create(): `model` (a ScoreModel, or a list of score_class()es) compiled and
+        uploaded to this plan's device.  Returns a Score; it stays valid across update()."""
+        sm = _scoremodel(model)
+        h = C.c_void_p()
+        _check(lib().acm_gpu_score_create(self.h, *sm.args(), C.byref(h)), "acm_gpu_score_create")
+        return Score(h, sm.n_classes)
+
+    def _score_handle(self, model):
+        """(a Score, whether this call made it) of a Score, a ScoreModel or a list of score_class()es"""
+        return (model, False) if isinstance(model, Score) else (self.score_create(model), True)
+
+    def _kept_outputs(self, dev, n_texts, kept_capacity):
+        import torch
+        kept_ptr = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
+        kept_class = torch.zeros(kept_capacity, dtype=torch.int32, device=dev) if kept_capacity else None
+        kept_score = torch.zeros(kept_capacity, dtype=torch.int64, device=dev) if kept_capacity else None
+        best = torch.full((max(n_texts, 1),), -1, dtype=torch.int32, device=dev)[:n_texts] if kept_capacity else None
+        return kept_ptr, kept_class, kept_score, best
+
+    def _top_outputs(self, dev, n_classes, k):
+        import torch
+        return (torch.zeros(max(n_classes, 1), dtype=torch.int64, device=dev)[:n_classes],
+                torch.zeros(max(n_classes, 1), dtype=torch.int32, device=dev)[:n_classes],
+                torch.zeros((max(n_classes, 1), max(k, 1)), dtype=torch.int32, device=dev)[:n_classes, :k],
+                torch.zeros((max(n_classes, 1), max(k, 1)), dtype=torch.int64, device=dev)[:n_classes, :k])
+
+    def score(self, text, offsets, model, k=0, window=None, capacity=None, pair_capacity=None, kept_capacity=None):
+        """acm_gpu_score_device(): the kept scores of every text of a batch, every text's best class and,
+        with k > 0, every class's best k texts, on the device: the tally of tally_batch() (same `text`,
+        `offsets`, `window`, `capacity`, `pair_capacity`), the evaluation and the ranking in one call.
+        `model` is a Score from score_create() (or a ScoreModel / a list of score_class()es, compiled for
+        this call).  kept_capacity: the room of the kept arrays (0: count only; None: counted first, then
+        sized by the count).  Returns a Scored of device tensors; synchronises to read its four numbers."""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        window = int(window) if window is not None else 1 << 24
+        capacity = int(capacity) if capacity is not None else 1 << 20
+        pair_capacity = int(pair_capacity) if pair_capacity is not None else capacity
+        k = int(k)
+        dev = text.device
+        S, own = self._score_handle(model)
+        res = torch.zeros(4, dtype=torch.int64, device=dev)                      # n_kept, total, need, need_pairs
+
+        def call(cap):
+            tb = lib().acm_gpu_score_tmp_bytes(self.h, S.h, window, capacity, pair_capacity, n_symbols, n_texts, cap, k)
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+            kept_ptr, kept_class, kept_score, best = self._kept_outputs(dev, n_texts, cap)
+            hits, top_n, top_text, top_score = self._top_outputs(dev, S.n_classes, k) if k and cap else (None, None, None, None)
+
+            def p(x):
+                return x.data_ptr() if x is not None and x.numel() else None
+            _check(lib().acm_gpu_score_device(self.h, S.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity,
+                                              kept_ptr.data_ptr(), p(kept_class), p(kept_score), cap, res.data_ptr(), p(best), k if hits is not None else 0,
+                                              p(hits), p(top_n), p(top_text), p(top_score), res.data_ptr() + 8, res.data_ptr() + 16, res.data_ptr() + 24,
+                                              tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_score_device")
+            n_kept, total, need, need_pairs = (int(x) for x in res.cpu())
+            return Scored(kept_ptr, kept_class, kept_score, n_kept, best, hits, top_n, top_text, top_score, total, need, need_pairs, cap)
+        try:
+            got = call(int(kept_capacity) if kept_capacity is not None else 0)
+            if kept_capacity is None and got.n_kept:
+                got = call(got.n_kept)
+            return got
+        finally:
+            if own:
+                S.close()
+
+    def score_matrix(self, tallied, model, kept_capacity=None):
+        """acm_gpu_score_matrix_device(): the evaluation for a count matrix that lies on the device:
+        `tallied` is a TalliedBatch of device tensors, tally_batch()'s or the caller's own (row_ptr int64
+        with n_texts + 1 entries, col int32, val int64).  Returns a Scored of device tensors (no top
+        arrays: score_top(); total, need and need_pairs None); synchronises to read n_kept."""
+        import torch
+        row_ptr, col, val = tallied.row_ptr, tallied.col, tallied.val
+        assert row_ptr.is_cuda and row_ptr.is_contiguous() and row_ptr.dtype == torch.int64
+        assert col.is_contiguous() and col.dtype == torch.int32 and val.is_contiguous() and val.dtype == torch.int64
+        n_texts = row_ptr.numel() - 1
+        assert n_texts >= 0
+        dev = row_ptr.device
+        S, own = self._score_handle(model)
+        res = torch.zeros(1, dtype=torch.int64, device=dev)
+        tb = lib().acm_gpu_score_matrix_tmp_bytes(self.h, S.h, n_texts)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+
+        def call(cap):
+            kept_ptr, kept_class, kept_score, best = self._kept_outputs(dev, n_texts, cap)
+            _check(lib().acm_gpu_score_matrix_device(self.h, S.h, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), n_texts, kept_ptr.data_ptr(),
+                                                     kept_class.data_ptr() if cap else None, kept_score.data_ptr() if cap else None, cap, res.data_ptr(),
+                                                     best.data_ptr() if cap and n_texts else None, tmp.data_ptr(), tmp.numel(), self._stream()),
+                   "acm_gpu_score_matrix_device")
+            return Scored(kept_ptr, kept_class, kept_score, int(res.item()), best, kept_capacity=cap)
+        try:
+            got = call(int(kept_capacity) if kept_capacity is not None else 0)
+            if kept_capacity is None and got.n_kept:
+                got = call(got.n_kept)
+            return got
+        finally:
+            if own:
+                S.close()
+
+    def score_top(self, scored, n_classes, k):
+        """acm_gpu_score_top_device(): TOP of a Scored of device tensors; returns it with class_hits, top_n, top_text and
+        top_score ([n_classes, k]) filled in.  Queues only."""
+        import torch
+        n_classes, k = int(n_classes), int(k)
+        kept_ptr = scored.kept_ptr
+        assert kept_ptr.is_cuda and kept_ptr.is_contiguous() and kept_ptr.dtype == torch.int64
+        dev = kept_ptr.device
+        cap = int(scored.kept_class.numel()) if scored.kept_class is not None else 0
+        hits, top_n, top_text, top_score = self._top_outputs(dev, n_classes, k)
+        tb = lib().acm_gpu_score_top_tmp_bytes(self.h, cap, n_classes)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+
+        def p(x):
+            return x.data_ptr() if x is not None and x.numel() else None
+        _check(lib().acm_gpu_score_top_device(self.h, kept_ptr.data_ptr(), p(scored.kept_class), p(scored.kept_score), cap, kept_ptr.numel() - 1, n_classes,
+                                              k, p(hits), p(top_n), p(top_text), p(top_score), tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_score_top_device")
+        scored.class_hits, scored.top_n, scored.top_text, scored.top_score = hits, top_n, top_text, top_score
+        scored._top_tmp = tmp                                                    # (the launches may still be queued)
+        return scored
+
+    def score_host(self, text, offsets, model, k=0):
+        """acm_gpu_score_host(): the same as score() from host arrays, through the C ABI only (no torch).
+        The call sizes its windows and its pair room itself.  Returns a Scored of numpy arrays."""
+        t = np.ascontiguousarray(text)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        return _score_host_call(lib().acm_gpu_score_host, "acm_gpu_score_host", self.h, t, self.sym_size, off, model, k)
 
     def patterns_create(self, patternset):
         """acm_gpu_patterns_create(): `patternset` (a PatternSet, or lists of (keyword_id, offset, length)

@@ -4637,11 +4637,12 @@ struct RulesRoom {
   long long *cnt = nullptr, *ptr = nullptr; /* K's, as the sum takes them */
   CubRoom cub;
 };
+/* the part that goes by the texts, and K.wide_p2: what the score passes (below) carve too, in front of their own wide rooms */
 RulesRoom
-rules_carve (Carve &c, const ACMRules *rules, uint64_t n_texts, RulesK &K) {
+rules_rows_carve (Carve &c, uint32_t n_postings, uint64_t n_texts, RulesK &K) {
   RulesRoom R;
   K.wide_p2 = 1;
-  while (K.wide_p2 < rules->n_postings)
+  while (K.wide_p2 < n_postings)
     K.wide_p2 <<= 1;
   K.ctl = c.take<RulesCtl> (1);
   R.cnt = c.take<long long> (n_texts + 1);
@@ -4649,10 +4650,15 @@ rules_carve (Carve &c, const ACMRules *rules, uint64_t n_texts, RulesK &K) {
   R.ptr = c.take<long long> (n_texts + 1);
   K.wide = c.take<uint32_t> (n_texts + 1);
   R.cub = cub_room (c, 0, n_texts + 1);
-  K.wkey = c.take<uint32_t> ((size_t)RULES_WIDE_BLOCKS * K.wide_p2);
-  K.wd = c.take<int32_t> ((size_t)RULES_WIDE_BLOCKS * ((size_t)rules->n_postings + 1));
   K.cnt = reinterpret_cast<unsigned long long *> (R.cnt);
   K.ptr = reinterpret_cast<const unsigned long long *> (R.ptr);
+  return R;
+}
+RulesRoom
+rules_carve (Carve &c, const ACMRules *rules, uint64_t n_texts, RulesK &K) {
+  const RulesRoom R = rules_rows_carve (c, rules->n_postings, n_texts, K);
+  K.wkey = c.take<uint32_t> ((size_t)RULES_WIDE_BLOCKS * K.wide_p2);
+  K.wd = c.take<int32_t> ((size_t)RULES_WIDE_BLOCKS * ((size_t)rules->n_postings + 1));
   return R;
 }
 
@@ -4727,7 +4733,7 @@ rules_evaluate (ACMPlan *plan, const ACMRules *rules, const uint64_t *d_row_ptr,
   return ACM_GPU_OK;
 }
 
-/* where acm_gpu_rules_device keeps the count matrix and tally_batch's scratch inside its own */
+/* where acm_gpu_rules_device and acm_gpu_score_device keep the count matrix and tally_batch's scratch inside their own */
 struct RulesCallRoom {
   uint64_t *row_ptr = nullptr, *val = nullptr, *nnz = nullptr;
   uint32_t *col = nullptr;
@@ -4736,9 +4742,9 @@ struct RulesCallRoom {
   const TbCtl *tb = nullptr; /* tally_batch's control words, where it will put them */
 };
 RulesCallRoom
-rules_call_carve (Carve &c, const ACMPlan *plan, const ACMRules *rules, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts) {
+rules_call_carve (Carve &c, const ACMPlan *plan, size_t evaluate_bytes, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts) {
   RulesCallRoom R;
-  c.used = rules_bytes (rules, n_texts); /* (rules_evaluate's scratch lies in front, as the matrix call has it) */
+  c.used = evaluate_bytes; /* (the evaluation's scratch lies in front, as the matrix call has it) */
   R.row_ptr = c.take<uint64_t> (n_texts + 1);
   R.col = c.take<uint32_t> ((size_t)pair_capacity);
   R.val = c.take<uint64_t> ((size_t)pair_capacity);
@@ -4752,6 +4758,62 @@ rules_call_carve (Carve &c, const ACMPlan *plan, const ACMRules *rules, uint64_t
   tally_batch_carve (inner, plan, capacity, pair_capacity, n_symbols, n_texts, T);
   R.tb = T.ctl;
   return R;
+}
+
+/* acm_gpu_tally_batch_device into the matrix of L, then evaluate (), which queues the passes over it; without a text the
+ * empty result.  (The arguments that are not checked here are tally_batch's to check.) */
+template <typename Evaluate>
+int
+tally_then_evaluate (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint64_t window_symbols,
+                     uint64_t capacity, uint64_t pair_capacity, const RulesCallRoom &L, uint64_t *d_out_ptr, uint64_t *d_n_out, uint64_t *d_total,
+                     uint64_t *d_need, uint64_t *d_need_pairs, void *stream, Evaluate evaluate) {
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (const int rc = acm_gpu_tally_batch_device (plan, d_text, n_symbols, d_offsets, n_texts, window_symbols, capacity, pair_capacity, L.row_ptr, L.col,
+                                                 L.val, L.nnz, d_total, d_need, d_need_pairs, L.tally, L.tally_bytes, stream))
+    return rc;
+  if (n_texts == 0) {
+    HIP_TRY (hipMemsetAsync (d_out_ptr, 0, 8, st));
+    HIP_TRY (hipMemsetAsync (d_n_out, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  return evaluate ();
+}
+
+/* The rooms of a blocking call that runs tally_batch inside: acm_gpu_tally_batch_host's, repeated with what the device
+ * reported.  tmp_bytes (window, capacity, pair_capacity) sizes the scratch, call (window, capacity, pair_capacity, d_tmp,
+ * tmp_bytes) queues the device call, whose four numbers -- its output count, total, need, need_pairs -- lie at d_res and
+ * come back in res[]. */
+template <typename TmpBytes, typename Call>
+int
+with_tally_rooms (ACMPlan *plan, DeviceTemps &temps, uint64_t n_symbols, const uint64_t *d_res, uint64_t res[4], TmpBytes tmp_bytes_of, Call call) {
+  RecordRoom room = tally_room (plan, n_symbols);
+  uint64_t pair_capacity = std::max<uint64_t> (room.capacity, 1ull << 16);
+  const uint64_t most = n_symbols < (1ull << 31) / tally_max_outputs (plan) ? n_symbols * tally_max_outputs (plan) : 1ull << 31;
+  if (most < pair_capacity)
+    pair_capacity = most ? most : 1;
+  void *d_tmp = nullptr;
+  bool again_pairs = false;
+  for (;;) {
+    const size_t tmp_bytes = tmp_bytes_of (room.window, room.capacity, pair_capacity);
+    HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+    if (const int rc = settle (plan, call (room.window, room.capacity, pair_capacity, d_tmp, tmp_bytes), true))
+      return rc;
+    HOST_TRY (hipMemcpy (res, d_res, 32, hipMemcpyDeviceToHost));
+    if (res[2] <= room.capacity && res[3] <= pair_capacity)
+      return ACM_GPU_OK;
+    HOST_TRY (temps.release (d_tmp)); /* (the next attempt's is another size) */
+    if (res[2] > room.capacity) {
+      if (!tally_room_shrink (plan, &room))
+        return ACM_GPU_E_INTERNAL;
+    } else {
+      if (again_pairs) /* (the kept records cannot be exceeded: never expected) */
+        return ACM_GPU_E_INTERNAL;
+      if (res[3] >= (1ull << 31)) /* more partial pairs than one call holds */
+        return ACM_GPU_E_NOMEM;
+      again_pairs = true;
+      pair_capacity = res[3];
+    }
+  }
 }
 } // namespace
 
@@ -4872,7 +4934,7 @@ acm_gpu_rules_tmp_bytes (const ACMPlan *plan, const ACMRules *rules, uint64_t wi
   if (!rules || !acm_gpu_tally_batch_tmp_bytes (plan, window_symbols, capacity, pair_capacity, n_symbols, n_texts))
     return 0;
   Carve c;
-  rules_call_carve (c, plan, rules, capacity, pair_capacity, n_symbols, n_texts);
+  rules_call_carve (c, plan, rules_bytes (rules, n_texts), capacity, pair_capacity, n_symbols, n_texts);
   return c.total ();
 }
 
@@ -4885,21 +4947,14 @@ acm_gpu_rules_device (ACMPlan *plan, const ACMRules *rules, const void *d_text, 
       pair_capacity == 0 || pair_capacity >= (1ull << 31))
     return ACM_GPU_E_ARG;
   Carve carve (d_tmp);
-  const RulesCallRoom L = rules_call_carve (carve, plan, rules, capacity, pair_capacity, n_symbols, n_texts);
+  const RulesCallRoom L = rules_call_carve (carve, plan, rules_bytes (rules, n_texts), capacity, pair_capacity, n_symbols, n_texts);
   if (tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
-  hipStream_t st = static_cast<hipStream_t> (stream);
-  /* (the remaining arguments are tally_batch's to check) */
-  if (const int rc = acm_gpu_tally_batch_device (plan, d_text, n_symbols, d_offsets, n_texts, window_symbols, capacity, pair_capacity, L.row_ptr, L.col,
-                                                 L.val, L.nnz, d_total, d_need, d_need_pairs, L.tally, L.tally_bytes, stream))
-    return rc;
-  if (n_texts == 0) {
-    HIP_TRY (hipMemsetAsync (d_fired_ptr, 0, 8, st));
-    HIP_TRY (hipMemsetAsync (d_n_fired, 0, 8, st));
-    return ACM_GPU_OK;
-  }
-  return rules_evaluate (plan, rules, L.row_ptr, L.col, L.val, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired, d_tmp, st, L.tb, capacity,
-                         pair_capacity);
+  return tally_then_evaluate (plan, d_text, n_symbols, d_offsets, n_texts, window_symbols, capacity, pair_capacity, L, d_fired_ptr, d_n_fired, d_total,
+                              d_need, d_need_pairs, stream, [&] {
+                                return rules_evaluate (plan, rules, L.row_ptr, L.col, L.val, n_texts, d_fired_ptr, d_fired, fired_capacity, d_n_fired, d_tmp,
+                                                       static_cast<hipStream_t> (stream), L.tb, capacity, pair_capacity);
+                              });
 }
 
 extern "C" int
@@ -4913,14 +4968,8 @@ acm_gpu_rules_host (ACMPlan *plan, const void *text, const uint64_t *offsets, ui
     return rc;
   std::unique_ptr<ACMRules, void (*) (ACMRules *)> rules (made, acm_gpu_rules_destroy);
   const uint64_t n_symbols = offsets[n_texts];
-  /* the rooms: acm_gpu_tally_batch_host's */
-  RecordRoom room = tally_room (plan, n_symbols);
-  uint64_t pair_capacity = std::max<uint64_t> (room.capacity, 1ull << 16);
-  const uint64_t most = n_symbols < (1ull << 31) / tally_max_outputs (plan) ? n_symbols * tally_max_outputs (plan) : 1ull << 31;
-  if (most < pair_capacity)
-    pair_capacity = most ? most : 1;
   DeviceTemps temps;
-  void *d_text = nullptr, *d_tmp = nullptr;
+  void *d_text = nullptr;
   uint64_t *d_off = nullptr, *d_fired_ptr = nullptr, *d_res = nullptr; /* d_res: n_fired, total, need, need_pairs */
   uint32_t *d_fired = nullptr;
   HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
@@ -4931,31 +4980,16 @@ acm_gpu_rules_host (ACMPlan *plan, const void *text, const uint64_t *offsets, ui
     HOST_TRY (temps.get (&d_fired, (size_t)fired_capacity * 4));
   const uint64_t d_capacity = d_fired ? fired_capacity : 0;
   uint64_t res[4] = { 0, 0, 0, 0 };
-  bool again_pairs = false;
-  for (;;) {
-    const size_t tmp_bytes = acm_gpu_rules_tmp_bytes (plan, rules.get (), room.window, room.capacity, pair_capacity, n_symbols, n_texts);
-    HOST_TRY (temps.get (&d_tmp, tmp_bytes));
-    if (const int rc = settle (plan, acm_gpu_rules_device (plan, rules.get (), d_text, n_symbols, d_off, n_texts, room.window, room.capacity, pair_capacity,
-                                                           d_fired_ptr, d_fired, d_capacity, d_res, d_res + 1, d_res + 2, d_res + 3, d_tmp, tmp_bytes,
-                                                           nullptr),
-                               true))
-      return rc;
-    HOST_TRY (hipMemcpy (res, d_res, 32, hipMemcpyDeviceToHost));
-    if (res[2] <= room.capacity && res[3] <= pair_capacity)
-      break;
-    HOST_TRY (temps.release (d_tmp)); /* (the next attempt's is another size) */
-    if (res[2] > room.capacity) {
-      if (!tally_room_shrink (plan, &room))
-        return ACM_GPU_E_INTERNAL;
-    } else {
-      if (again_pairs) /* (the kept records cannot be exceeded: never expected) */
-        return ACM_GPU_E_INTERNAL;
-      if (res[3] >= (1ull << 31)) /* more partial pairs than one call holds */
-        return ACM_GPU_E_NOMEM;
-      again_pairs = true;
-      pair_capacity = res[3];
-    }
-  }
+  if (const int rc = with_tally_rooms (
+        plan, temps, n_symbols, d_res, res,
+        [&] (uint64_t window, uint64_t capacity, uint64_t pairs) {
+          return acm_gpu_rules_tmp_bytes (plan, rules.get (), window, capacity, pairs, n_symbols, n_texts);
+        },
+        [&] (uint64_t window, uint64_t capacity, uint64_t pairs, void *d_tmp, size_t tmp_bytes) {
+          return acm_gpu_rules_device (plan, rules.get (), d_text, n_symbols, d_off, n_texts, window, capacity, pairs, d_fired_ptr, d_fired, d_capacity,
+                                       d_res, d_res + 1, d_res + 2, d_res + 3, d_tmp, tmp_bytes, nullptr);
+        }))
+    return rc;
   HOST_TRY (hipMemcpy (fired_ptr, d_fired_ptr, (n_texts + 1) * 8, hipMemcpyDeviceToHost));
   *n_fired = res[0];
   if (total)
@@ -4966,6 +5000,456 @@ acm_gpu_rules_host (ACMPlan *plan, const void *text, const uint64_t *offsets, ui
     return ACM_GPU_E_OVERFLOW;
   if (res[0])
     HOST_TRY (hipMemcpy (fired, d_fired, res[0] * 4, hipMemcpyDeviceToHost));
+  return ACM_GPU_OK;
+}
+
+/* ------------------------------------------------------------------ weighted scores per text (include/acm_score.h, dev_score.h)
+ * A model compiled into an index inverted by keyword, the passes that evaluate it on a count matrix on
+ * the device and the passes that rank a kept matrix by class; acm_gpu_score_device runs both behind
+ * acm_gpu_tally_batch_device. */
+struct ACMScore {
+  int device = 0;
+  uint64_t n_classes = 0, n_terms = 0;
+  uint32_t n_keywords = 0, n_always = 0, n_postings = 0;
+  void *blob = nullptr; /* one allocation: the arrays below, then the two form counters */
+  uint32_t *d_post_ptr = nullptr, *d_always = nullptr;
+  ScorePost *d_post = nullptr;
+  long long *d_bias = nullptr, *d_threshold = nullptr;
+  unsigned long long *d_forms = nullptr;
+};
+
+namespace {
+RulesRoom
+score_carve (Carve &c, const ACMScore *score, uint64_t n_texts, ScoreK &K) {
+  const RulesRoom R = rules_rows_carve (c, score->n_postings, n_texts, K.R);
+  K.wkey = c.take<unsigned long long> ((size_t)SCORE_WIDE_BLOCKS * K.R.wide_p2);
+  K.wval = c.take<unsigned long long> ((size_t)SCORE_WIDE_BLOCKS * ((size_t)score->n_postings + 1));
+  return R;
+}
+
+/* acm_gpu_score_matrix_tmp_bytes behind its checks */
+size_t
+score_bytes (const ACMScore *score, uint64_t n_texts) {
+  Carve c;
+  ScoreK K{};
+  score_carve (c, score, n_texts, K);
+  return c.total ();
+}
+
+/* the matrix calls' own arguments: the model is this plan's device's, the outputs are there */
+bool
+score_args_ok (const ACMPlan *plan, const ACMScore *score, uint64_t n_texts, const uint64_t *d_kept_ptr, const uint32_t *d_kept_class,
+               const int64_t *d_kept_score, uint64_t kept_capacity, const uint64_t *d_n_kept) {
+  return plan && score && score->device == plan->device && n_texts < (1ull << 31) && d_kept_ptr && d_n_kept &&
+         ((d_kept_class && d_kept_score) || kept_capacity == 0);
+}
+
+/* the evaluation passes of dev_score.h on a matrix on the device; `tb` as rules_evaluate has it.  *gate receives the RulesK
+ * whose stop tests a top pass behind this call asks. */
+int
+score_evaluate (ACMPlan *plan, const ACMScore *score, const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_val, uint64_t n_texts,
+                uint64_t *d_kept_ptr, uint32_t *d_kept_class, int64_t *d_kept_score, uint64_t kept_capacity, uint64_t *d_n_kept, uint32_t *d_best,
+                void *d_tmp, hipStream_t st, const TbCtl *tb, uint64_t tb_capacity, uint64_t tb_pair_capacity, RulesK *gate) {
+  Carve carve (d_tmp);
+  ScoreK K{};
+  const RulesRoom L = score_carve (carve, score, n_texts, K);
+  RulesK &R = K.R;
+  R.row_ptr = reinterpret_cast<const unsigned long long *> (d_row_ptr);
+  R.col = d_col;
+  R.val = reinterpret_cast<const unsigned long long *> (d_val);
+  R.n_texts = n_texts;
+  R.post_ptr = score->d_post_ptr;
+  R.always = score->d_always;
+  R.n_keywords = score->n_keywords;
+  R.n_always = score->n_always;
+  R.n_postings = score->n_postings;
+  R.forms = score->d_forms;
+  /* ACM_GPU_SCORE_ITEMS=<1 to 4,096>: the widest text, in items, of the fast form (tests, experiments) */
+  R.items = tunable ("ACM_GPU_SCORE_ITEMS", SCORE_ITEMS_DEFAULT, 1, SCORE_ITEMS_MAX, Tune::Any);
+  R.items_p2 = 1;
+  while (R.items_p2 < R.items)
+    R.items_p2 <<= 1;
+  R.tb = tb;
+  R.tb_capacity = tb_capacity;
+  R.tb_pair_capacity = tb_pair_capacity;
+  R.d_fired_ptr = reinterpret_cast<unsigned long long *> (d_kept_ptr);
+  R.d_n_fired = reinterpret_cast<unsigned long long *> (d_n_kept);
+  R.d_fired = d_kept_class;
+  R.fired_capacity = kept_capacity;
+  R.error = error_word (plan);
+  K.post = score->d_post;
+  K.bias = score->d_bias;
+  K.threshold = score->d_threshold;
+  K.d_kept_score = reinterpret_cast<long long *> (d_kept_score);
+  K.d_best = d_best;
+  if (gate)
+    *gate = R;
+  HIP_TRY (hipMemsetAsync (d_tmp, 0, L.zero_bytes, st));
+  const dim3 flat_grid = capped_grid (plan, (n_texts + 1 + 255) / 256);
+  const size_t fast_lds = ((size_t)R.items_p2 + R.items) * 8;
+  /* one-wave blocks a CU: eight at the default room, more at a smaller one and fewer at a larger one by the LDS they take,
+   * sixteen (dev_rules.h's number) at the most: 128 KiB of a CU's 160 at every room */
+  const uint32_t fast_per_cu =
+    (uint32_t)std::min<size_t> (RULES_FAST_PER_CU, std::max<size_t> (1, (size_t)SCORE_FAST_PER_CU * SCORE_ITEMS_DEFAULT * SCORE_ITEM_BYTES / fast_lds));
+  const dim3 fast_grid = capped_grid (plan, n_texts, fast_per_cu);
+  if (fast_lds + 64 > 64 * 1024) { /* (a room near the largest only: beyond what a kernel may take unasked) */
+    HIP_TRY (hipFuncSetAttribute (reinterpret_cast<const void *> (&score_fast_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast_lds));
+    HIP_TRY (hipFuncSetAttribute (reinterpret_cast<const void *> (&score_fast_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast_lds));
+  }
+  /* 1. */
+  HIP_TRY (launch (rules_check_kernel, flat_grid, dim3 (256), 0, st, R));
+  /* 2. */
+  HIP_TRY (launch (score_fast_kernel<false>, fast_grid, dim3 (WAVE), fast_lds, st, K));
+  HIP_TRY (launch (score_wide_kernel<false>, dim3 (SCORE_WIDE_BLOCKS), dim3 (SCORE_WIDE_THREADS), 0, st, K));
+  /* 3. */
+  HIP_TRY (exclusive_sum (L.cub, L.cnt, L.ptr, n_texts + 1, st));
+  HIP_TRY (launch (rules_finish_kernel, flat_grid, dim3 (256), 0, st, R));
+  /* 4. */
+  if (d_kept_class) {
+    HIP_TRY (launch (score_fast_kernel<true>, fast_grid, dim3 (WAVE), fast_lds, st, K));
+    HIP_TRY (launch (score_wide_kernel<true>, dim3 (SCORE_WIDE_BLOCKS), dim3 (SCORE_WIDE_THREADS), 0, st, K));
+  }
+  return ACM_GPU_OK;
+}
+
+/* what score_top_carve derives beside T's pointers */
+struct ScoreTopRoom {
+  size_t zero_bytes = 0; /* the gate's control words, the histogram and the cursors: the head of the scratch, cleared in front of every call */
+  RulesCtl *ctl = nullptr;
+  long long *hist = nullptr, *col_ptr = nullptr; /* T's, as the sum takes them */
+  CubRoom cub;
+};
+ScoreTopRoom
+score_top_carve (Carve &c, uint64_t kept_capacity, uint64_t n_classes, ScoreTopK &T) {
+  ScoreTopRoom R;
+  R.ctl = c.take<RulesCtl> (1);
+  R.hist = c.take<long long> (n_classes + 1);
+  T.cursor = c.take<unsigned long long> (n_classes + 1);
+  R.zero_bytes = c.used;
+  R.col_ptr = c.take<long long> (n_classes + 1);
+  R.cub = cub_room (c, 0, n_classes + 1);
+  T.keys = c.take<ulonglong2> ((size_t)kept_capacity + 1);
+  T.hist = reinterpret_cast<unsigned long long *> (R.hist);
+  T.col_ptr = reinterpret_cast<const unsigned long long *> (R.col_ptr);
+  return R;
+}
+
+size_t
+score_top_bytes (uint64_t kept_capacity, uint64_t n_classes) {
+  Carve c;
+  ScoreTopK T{};
+  score_top_carve (c, kept_capacity, n_classes, T);
+  return c.total ();
+}
+
+bool
+score_top_args_ok (const ACMPlan *plan, uint64_t kept_capacity, uint64_t n_texts, uint64_t n_classes, uint32_t k) {
+  return plan && kept_capacity < (1ull << 31) && n_texts < (1ull << 31) && n_classes < (1ull << 31) && k <= SCORE_TOP_MAX;
+}
+
+/* the top passes of dev_score.h over a kept matrix on the device, scratch at d_tmp.  gate: the RulesK of the evaluation
+ * queued in front, whose stopping stops these passes too (nullptr: a caller's matrix, whose d_kept_ptr is checked first) */
+int
+score_top_passes (ACMPlan *plan, const uint64_t *d_kept_ptr, const uint32_t *d_kept_class, const int64_t *d_kept_score, uint64_t kept_capacity,
+                  uint64_t n_texts, uint64_t n_classes, uint32_t k, uint64_t *d_class_hits, uint32_t *d_top_n, uint32_t *d_top_text,
+                  int64_t *d_top_score, void *d_tmp, hipStream_t st, const RulesK *gate) {
+  Carve carve (d_tmp);
+  ScoreTopK T{};
+  const ScoreTopRoom L = score_top_carve (carve, kept_capacity, n_classes, T);
+  T.kept_ptr = reinterpret_cast<const unsigned long long *> (d_kept_ptr);
+  T.kept_class = d_kept_class;
+  T.kept_score = reinterpret_cast<const long long *> (d_kept_score);
+  T.n_texts = n_texts;
+  T.kept_capacity = kept_capacity;
+  T.n_classes = (uint32_t)n_classes;
+  T.k = k;
+  T.d_class_hits = reinterpret_cast<unsigned long long *> (d_class_hits);
+  T.d_top_n = d_top_n;
+  T.d_top_text = d_top_text;
+  T.d_top_score = reinterpret_cast<long long *> (d_top_score);
+  T.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (d_tmp, 0, L.zero_bytes, st));
+  if (gate)
+    T.G = *gate;
+  else {
+    T.G.row_ptr = T.kept_ptr;
+    T.G.n_texts = n_texts;
+    T.G.ctl = L.ctl;
+    T.G.error = T.error;
+    HIP_TRY (launch (rules_check_kernel, capped_grid (plan, (n_texts + 1 + 255) / 256), dim3 (256), 0, st, T.G));
+  }
+  const dim3 entry_grid = capped_grid (plan, (kept_capacity + 255) / 256);
+  /* 1. */
+  HIP_TRY (launch (score_top_hist_kernel, entry_grid, dim3 (256), 0, st, T));
+  /* 2. */
+  HIP_TRY (exclusive_sum (L.cub, L.hist, L.col_ptr, n_classes + 1, st));
+  /* 3. */
+  HIP_TRY (launch (score_top_scatter_kernel, entry_grid, dim3 (256), 0, st, T));
+  /* 4. */
+  /* ACM_GPU_SCORE_TOP_BLOCKS=<1 to 65,536>: the most blocks of the select pass, so that tests make it stride over few classes */
+  const uint32_t most_blocks = tunable ("ACM_GPU_SCORE_TOP_BLOCKS", 65536, 1, 65536, Tune::Any);
+  HIP_TRY (launch (score_top_select_kernel, capped_grid (plan, std::min<uint64_t> (n_classes, most_blocks), 4), dim3 (SCORE_TOP_THREADS), 0, st, T));
+  return ACM_GPU_OK;
+}
+
+/* whether a call that evaluates is to rank as well */
+bool
+score_wants_top (uint32_t k, const uint64_t *class_hits, const uint32_t *top_n, const uint32_t *top_text, const int64_t *top_score) {
+  return k > 0 && class_hits && top_n && top_text && top_score;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_score_create (ACMPlan *plan, const ACMScoreTerm *terms, const uint64_t *class_ptr, const int64_t *bias, const int64_t *threshold,
+                      uint64_t n_classes, ACMScore **out) {
+  if (!plan || !out)
+    return ACM_GPU_E_ARG;
+  const uint64_t nk = plan->covered_keywords;
+  if (acm_score_check (terms, class_ptr, bias, threshold, n_classes, nk))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_terms = class_ptr[n_classes];
+  /* the index: a counting sort of the terms by keyword, classes ascending within a keyword */
+  std::vector<uint32_t> post_ptr (nk + 2, 0), always;
+  for (uint64_t i = 0; i < n_terms; i++)
+    if (terms[i].weight != 0) /* (a weight of 0 adds nothing at any count) */
+      post_ptr[terms[i].keyword_id + 2]++;
+  for (uint64_t k = 2; k < nk + 2; k++)
+    post_ptr[k] += post_ptr[k - 1];
+  const uint32_t n_postings = post_ptr[nk + 1];
+  std::vector<ScorePost> post (n_postings ? n_postings : 1);
+  for (uint64_t c = 0; c < n_classes; c++) {
+    for (uint64_t i = class_ptr[c]; i < class_ptr[c + 1]; i++) {
+      const ACMScoreTerm &q = terms[i];
+      if (q.weight != 0)
+        post[post_ptr[q.keyword_id + 1]++] = ScorePost{ (uint32_t)c, q.weight, q.cap };
+    }
+    if (bias[c] >= threshold[c])
+      always.push_back ((uint32_t)c);
+  } /* (post_ptr[k + 1] has moved on to the end of k's postings: post_ptr[0 .. nk] are the row pointers now) */
+  HIP_TRY (hipSetDevice (plan->device));
+  ACMScore *S = new (std::nothrow) ACMScore ();
+  if (!S)
+    return ACM_GPU_E_NOMEM;
+  S->device = plan->device;
+  S->n_classes = n_classes;
+  S->n_terms = n_terms;
+  S->n_keywords = (uint32_t)nk;
+  S->n_always = (uint32_t)always.size ();
+  S->n_postings = n_postings;
+  const size_t classes_bytes = (n_classes ? n_classes : 1) * 8;
+  size_t cur = 0;
+  const size_t o_post_ptr = blob_reserve (cur, (nk + 1) * 4), o_post = blob_reserve (cur, post.size () * sizeof (ScorePost)),
+               o_bias = blob_reserve (cur, classes_bytes), o_threshold = blob_reserve (cur, classes_bytes),
+               o_always = blob_reserve (cur, (always.size () + 1) * 4), o_forms = blob_reserve (cur, 16);
+  bool ok = hipMalloc (&S->blob, cur) == hipSuccess;
+  unsigned char *b = static_cast<unsigned char *> (S->blob);
+  ok = ok && hipMemset (b, 0, cur) == hipSuccess && hipMemcpy (b + o_post_ptr, post_ptr.data (), (nk + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
+       hipMemcpy (b + o_post, post.data (), post.size () * sizeof (ScorePost), hipMemcpyHostToDevice) == hipSuccess &&
+       (!n_classes || (hipMemcpy (b + o_bias, bias, n_classes * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                       hipMemcpy (b + o_threshold, threshold, n_classes * 8, hipMemcpyHostToDevice) == hipSuccess)) &&
+       (always.empty () || hipMemcpy (b + o_always, always.data (), always.size () * 4, hipMemcpyHostToDevice) == hipSuccess) &&
+       hipDeviceSynchronize () == hipSuccess;
+  if (!ok) {
+    acm_gpu_score_destroy (S);
+    return ACM_GPU_E_NOMEM;
+  }
+  S->d_post_ptr = reinterpret_cast<uint32_t *> (b + o_post_ptr);
+  S->d_post = reinterpret_cast<ScorePost *> (b + o_post);
+  S->d_bias = reinterpret_cast<long long *> (b + o_bias);
+  S->d_threshold = reinterpret_cast<long long *> (b + o_threshold);
+  S->d_always = reinterpret_cast<uint32_t *> (b + o_always);
+  S->d_forms = reinterpret_cast<unsigned long long *> (b + o_forms);
+  *out = S;
+  return ACM_GPU_OK;
+}
+
+extern "C" void
+acm_gpu_score_destroy (ACMScore *score) {
+  if (!score)
+    return;
+  (void)hipSetDevice (score->device);
+  if (score->blob)
+    (void)hipFree (score->blob);
+  delete score;
+}
+
+extern "C" int
+acm_gpu_score_info (const ACMScore *score, ACMScoreInfo *info) {
+  if (!score || !info)
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (score->device));
+  HIP_TRY (hipDeviceSynchronize ());
+  unsigned long long forms[2] = { 0, 0 };
+  HIP_TRY (hipMemcpy (forms, score->d_forms, sizeof forms, hipMemcpyDeviceToHost));
+  *info = ACMScoreInfo{ score->n_classes, score->n_terms, score->n_postings, score->n_always, forms[0], forms[1] };
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_score_matrix_tmp_bytes (const ACMPlan *plan, const ACMScore *score, uint64_t n_texts) {
+  if (!plan || !score || n_texts >= (1ull << 31))
+    return 0;
+  return score_bytes (score, n_texts);
+}
+
+extern "C" int
+acm_gpu_score_matrix_device (ACMPlan *plan, const ACMScore *score, const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_val,
+                             uint64_t n_texts, uint64_t *d_kept_ptr, uint32_t *d_kept_class, int64_t *d_kept_score, uint64_t kept_capacity,
+                             uint64_t *d_n_kept, uint32_t *d_best, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!score_args_ok (plan, score, n_texts, d_kept_ptr, d_kept_class, d_kept_score, kept_capacity, d_n_kept))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0) { /* no text: an empty matrix */
+    HIP_TRY (hipMemsetAsync (d_kept_ptr, 0, 8, st));
+    HIP_TRY (hipMemsetAsync (d_n_kept, 0, 8, st));
+    return ACM_GPU_OK;
+  }
+  if (!d_row_ptr || !d_tmp || tmp_bytes < score_bytes (score, n_texts))
+    return ACM_GPU_E_ARG;
+  return score_evaluate (plan, score, d_row_ptr, d_col, d_val, n_texts, d_kept_ptr, d_kept_class, d_kept_score, kept_capacity, d_n_kept, d_best, d_tmp,
+                         st, nullptr, 0, 0, nullptr);
+}
+
+extern "C" size_t
+acm_gpu_score_top_tmp_bytes (const ACMPlan *plan, uint64_t kept_capacity, uint64_t n_classes) {
+  if (!score_top_args_ok (plan, kept_capacity, 0, n_classes, 0))
+    return 0;
+  return score_top_bytes (kept_capacity, n_classes);
+}
+
+extern "C" int
+acm_gpu_score_top_device (ACMPlan *plan, const uint64_t *d_kept_ptr, const uint32_t *d_kept_class, const int64_t *d_kept_score, uint64_t kept_capacity,
+                          uint64_t n_texts, uint64_t n_classes, uint32_t k, uint64_t *d_class_hits, uint32_t *d_top_n, uint32_t *d_top_text,
+                          int64_t *d_top_score, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!score_top_args_ok (plan, kept_capacity, n_texts, n_classes, k) || !d_kept_ptr || (kept_capacity && (!d_kept_class || !d_kept_score)) ||
+      (n_classes && (!d_class_hits || !d_top_n || (k && (!d_top_text || !d_top_score)))) || !d_tmp ||
+      tmp_bytes < score_top_bytes (kept_capacity, n_classes))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  return score_top_passes (plan, d_kept_ptr, d_kept_class, d_kept_score, kept_capacity, n_texts, n_classes, k, d_class_hits, d_top_n, d_top_text,
+                           d_top_score, d_tmp, static_cast<hipStream_t> (stream), nullptr);
+}
+
+extern "C" size_t
+acm_gpu_score_tmp_bytes (const ACMPlan *plan, const ACMScore *score, uint64_t window_symbols, uint64_t capacity, uint64_t pair_capacity,
+                         uint64_t n_symbols, uint64_t n_texts, uint64_t kept_capacity, uint32_t k) {
+  if (!score || !score_top_args_ok (plan, kept_capacity, n_texts, score->n_classes, k) ||
+      !acm_gpu_tally_batch_tmp_bytes (plan, window_symbols, capacity, pair_capacity, n_symbols, n_texts))
+    return 0;
+  Carve c;
+  rules_call_carve (c, plan, score_bytes (score, n_texts), capacity, pair_capacity, n_symbols, n_texts);
+  if (k)
+    c.take (score_top_bytes (kept_capacity, score->n_classes));
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_score_device (ACMPlan *plan, const ACMScore *score, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts,
+                      uint64_t window_symbols, uint64_t capacity, uint64_t pair_capacity, uint64_t *d_kept_ptr, uint32_t *d_kept_class,
+                      int64_t *d_kept_score, uint64_t kept_capacity, uint64_t *d_n_kept, uint32_t *d_best, uint32_t k, uint64_t *d_class_hits,
+                      uint32_t *d_top_n, uint32_t *d_top_text, int64_t *d_top_score, uint64_t *d_total, uint64_t *d_need, uint64_t *d_need_pairs,
+                      void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!score_args_ok (plan, score, n_texts, d_kept_ptr, d_kept_class, d_kept_score, kept_capacity, d_n_kept) ||
+      !score_top_args_ok (plan, kept_capacity, n_texts, score->n_classes, k) || !d_tmp || capacity == 0 || capacity >= (1ull << 31) ||
+      pair_capacity == 0 || pair_capacity >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  Carve carve (d_tmp);
+  const RulesCallRoom L = rules_call_carve (carve, plan, score_bytes (score, n_texts), capacity, pair_capacity, n_symbols, n_texts);
+  void *d_top_tmp = k ? carve.take (score_top_bytes (kept_capacity, score->n_classes)) : nullptr;
+  if (tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  const bool top = score_wants_top (k, d_class_hits, d_top_n, d_top_text, d_top_score) && d_kept_class;
+  return tally_then_evaluate (
+    plan, d_text, n_symbols, d_offsets, n_texts, window_symbols, capacity, pair_capacity, L, d_kept_ptr, d_n_kept, d_total, d_need, d_need_pairs, stream, [&] {
+      hipStream_t st = static_cast<hipStream_t> (stream);
+      RulesK gate{};
+      if (const int rc = score_evaluate (plan, score, L.row_ptr, L.col, L.val, n_texts, d_kept_ptr, d_kept_class, d_kept_score, kept_capacity, d_n_kept,
+                                         d_best, d_tmp, st, L.tb, capacity, pair_capacity, &gate))
+        return rc;
+      return top ? score_top_passes (plan, d_kept_ptr, d_kept_class, d_kept_score, kept_capacity, n_texts, score->n_classes, k, d_class_hits, d_top_n,
+                                     d_top_text, d_top_score, d_top_tmp, st, &gate)
+                 : (int)ACM_GPU_OK;
+    });
+}
+
+extern "C" int
+acm_gpu_score_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, const ACMScoreTerm *terms, const uint64_t *class_ptr,
+                    const int64_t *bias, const int64_t *threshold, uint64_t n_classes, uint64_t *kept_ptr, uint32_t *kept_class, int64_t *kept_score,
+                    uint64_t kept_capacity, uint64_t *n_kept, uint32_t *best, uint32_t k, uint64_t *class_hits, uint32_t *top_n, uint32_t *top_text,
+                    int64_t *top_score, uint64_t *total) {
+  if (!plan || !kept_ptr || !n_kept || k > SCORE_TOP_MAX || kept_capacity >= (1ull << 31) || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
+    return ACM_GPU_E_ARG;
+  ACMScore *made = nullptr;
+  if (const int rc = acm_gpu_score_create (plan, terms, class_ptr, bias, threshold, n_classes, &made))
+    return rc;
+  std::unique_ptr<ACMScore, void (*) (ACMScore *)> score (made, acm_gpu_score_destroy);
+  const uint64_t n_symbols = offsets[n_texts];
+  const bool fills = kept_class && kept_score && kept_capacity;
+  const bool top = fills && n_classes && score_wants_top (k, class_hits, top_n, top_text, top_score);
+  const uint32_t d_k = top ? k : 0;
+  DeviceTemps temps;
+  void *d_text = nullptr;
+  uint64_t *d_off = nullptr, *d_kept_ptr = nullptr, *d_res = nullptr, *d_hits = nullptr; /* d_res: n_kept, total, need, need_pairs */
+  uint32_t *d_kept_class = nullptr, *d_best = nullptr, *d_top_n = nullptr, *d_top_text = nullptr;
+  int64_t *d_kept_score = nullptr, *d_top_score = nullptr;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  HOST_TRY (temps.get (&d_kept_ptr, (n_texts + 1) * 8));
+  HOST_TRY (temps.get (&d_res, 32));
+  if (fills) {
+    HOST_TRY (temps.get (&d_kept_class, (size_t)kept_capacity * 4));
+    HOST_TRY (temps.get (&d_kept_score, (size_t)kept_capacity * 8));
+    if (best && n_texts)
+      HOST_TRY (temps.get (&d_best, (size_t)n_texts * 4));
+  }
+  if (top) {
+    HOST_TRY (temps.get (&d_hits, (size_t)n_classes * 8));
+    HOST_TRY (temps.get (&d_top_n, (size_t)n_classes * 4));
+    HOST_TRY (temps.get (&d_top_text, (size_t)n_classes * k * 4));
+    HOST_TRY (temps.get (&d_top_score, (size_t)n_classes * k * 8));
+  }
+  const uint64_t d_capacity = fills ? kept_capacity : 0;
+  uint64_t res[4] = { 0, 0, 0, 0 };
+  if (const int rc = with_tally_rooms (
+        plan, temps, n_symbols, d_res, res,
+        [&] (uint64_t window, uint64_t capacity, uint64_t pairs) {
+          return acm_gpu_score_tmp_bytes (plan, score.get (), window, capacity, pairs, n_symbols, n_texts, d_capacity, d_k);
+        },
+        [&] (uint64_t window, uint64_t capacity, uint64_t pairs, void *d_tmp, size_t tmp_bytes) {
+          return acm_gpu_score_device (plan, score.get (), d_text, n_symbols, d_off, n_texts, window, capacity, pairs, d_kept_ptr, d_kept_class,
+                                       d_kept_score, d_capacity, d_res, d_best, d_k, d_hits, d_top_n, d_top_text, d_top_score, d_res + 1, d_res + 2,
+                                       d_res + 3, d_tmp, tmp_bytes, nullptr);
+        }))
+    return rc;
+  HOST_TRY (hipMemcpy (kept_ptr, d_kept_ptr, (n_texts + 1) * 8, hipMemcpyDeviceToHost));
+  *n_kept = res[0];
+  if (total)
+    *total = res[1];
+  if (!kept_class || !kept_score) /* the call only counts */
+    return ACM_GPU_OK;
+  if (res[0] > kept_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (res[0]) {
+    HOST_TRY (hipMemcpy (kept_class, d_kept_class, res[0] * 4, hipMemcpyDeviceToHost));
+    HOST_TRY (hipMemcpy (kept_score, d_kept_score, res[0] * 8, hipMemcpyDeviceToHost));
+  }
+  if (best && n_texts) {
+    if (d_best)
+      HOST_TRY (hipMemcpy (best, d_best, n_texts * 4, hipMemcpyDeviceToHost));
+    else /* (no room and nothing kept: every row is empty) */
+      std::fill (best, best + n_texts, ACM_SCORE_NONE);
+  }
+  if (top) {
+    if (n_texts) {
+      HOST_TRY (hipMemcpy (class_hits, d_hits, n_classes * 8, hipMemcpyDeviceToHost));
+      HOST_TRY (hipMemcpy (top_n, d_top_n, n_classes * 4, hipMemcpyDeviceToHost));
+      HOST_TRY (hipMemcpy (top_text, d_top_text, n_classes * k * 4, hipMemcpyDeviceToHost));
+      HOST_TRY (hipMemcpy (top_score, d_top_score, n_classes * k * 8, hipMemcpyDeviceToHost));
+    } else /* (no text: the device call ends behind the tally) */
+      return acm_score_top (kept_ptr, kept_class, kept_score, 0, n_classes, k, class_hits, top_n, top_text, top_score);
+  } else if (n_classes && score_wants_top (k, class_hits, top_n, top_text, top_score)) /* (nothing kept and no room: every column is empty) */
+    return acm_score_top (kept_ptr, kept_class, kept_score, n_texts, n_classes, k, class_hits, top_n, top_text, top_score);
   return ACM_GPU_OK;
 }
 
@@ -8247,7 +8731,7 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally and acm_lookup only a scan that
  * succeeded, acm_select, acm_scan_words, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
- * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_scan_patterns, acm_scan_chains, acm_scan_approx and
+ * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_score, acm_scan_patterns, acm_scan_chains, acm_scan_approx and
  * acm_scan_edit also one whose output had no room, acm_context either of the two. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
@@ -8274,7 +8758,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The nineteen calls below run on the same route, the same cached plan, under the same lock. */
+/* The twenty calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -8485,6 +8969,26 @@ acm_rules (ACMachine *machine, const void *text, const uint64_t *offsets, uint64
     },
     [&] (ACMPlan *plan) {
       return acm_gpu_rules_host (plan, text, offsets, n_texts, terms, rule_ptr, need, n_rules, fired_ptr, fired, fired_capacity, n_fired, total);
+    });
+}
+
+/* weighted scores per text of a batch (include/acm_score.h) */
+extern "C" int
+acm_score (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, const ACMScoreTerm *terms, const uint64_t *class_ptr,
+           const int64_t *bias, const int64_t *threshold, uint64_t n_classes, uint64_t *kept_ptr, uint32_t *kept_class, int64_t *kept_score,
+           uint64_t kept_capacity, uint64_t *n_kept, uint32_t *best, uint32_t k, uint64_t *class_hits, uint32_t *top_n, uint32_t *top_text,
+           int64_t *top_score, uint64_t *total) {
+  if (!machine || !kept_ptr || !n_kept || k > ACM_SCORE_TOP_MAX || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      return acm_internal_cpu_score (machine, text, offsets, n_texts, said, terms, class_ptr, bias, threshold, n_classes, kept_ptr, kept_class, kept_score,
+                                     kept_capacity, n_kept, best, k, class_hits, top_n, top_text, top_score, total);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_score_host (plan, text, offsets, n_texts, terms, class_ptr, bias, threshold, n_classes, kept_ptr, kept_class, kept_score,
+                                 kept_capacity, n_kept, best, k, class_hits, top_n, top_text, top_score, total);
     });
 }
 

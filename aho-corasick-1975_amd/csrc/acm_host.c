@@ -1094,6 +1094,165 @@ acm_rules_matrix (const uint64_t *row_ptr, const uint32_t *col, const uint64_t *
   return rc;
 }
 
+/* The argument checks of a score model (include/acm_score.h) */
+int
+acm_score_check (const ACMScoreTerm *terms, const uint64_t *class_ptr, const int64_t *bias, const int64_t *threshold, uint64_t n_classes,
+                 uint64_t n_keywords) {
+  if (!class_ptr || class_ptr[0] != 0 || n_classes >= (1ull << 31) || (n_classes && (!bias || !threshold)))
+    return ACM_GPU_E_ARG;
+  for (uint64_t c = 0; c < n_classes; c++)
+    if (class_ptr[c] > class_ptr[c + 1])
+      return ACM_GPU_E_ARG;
+  const uint64_t n_terms = class_ptr[n_classes];
+  if (n_terms >= (1ull << 31) || (n_terms && !terms))
+    return ACM_GPU_E_ARG;
+  for (uint64_t i = 0; i < n_terms; i++)
+    if (terms[i].keyword_id >= n_keywords || terms[i].cap == 0)
+      return ACM_GPU_E_ARG;
+  return ACM_GPU_OK;
+}
+
+/* a term's value at count c, modulo 2^64 */
+static uint64_t
+score_term_value (const ACMScoreTerm *term, uint64_t c) {
+  const uint64_t capped = term->cap != ACM_SCORE_NO_CAP && c > term->cap ? term->cap : c;
+  return (uint64_t)(int64_t)term->weight * capped;
+}
+
+/* The kept part of the text x class score matrix of a count matrix in CSR form (include/acm_score.h):
+ * the plain sequential evaluation, acm_rules_matrix's walk with sums in place of held terms.  Sums are
+ * unsigned, so that nothing overflows as a signed number; the first walk counts, so that nothing is
+ * written to the kept entries or to best[] when they have no room. */
+int
+acm_score_matrix (const uint64_t *row_ptr, const uint32_t *col, const uint64_t *val, uint64_t n_texts, uint64_t n_keywords, const ACMScoreTerm *terms,
+                  const uint64_t *class_ptr, const int64_t *bias, const int64_t *threshold, uint64_t n_classes, uint64_t *kept_ptr, uint32_t *kept_class,
+                  int64_t *kept_score, uint64_t kept_capacity, uint64_t *n_kept, uint32_t *best) {
+  if (!row_ptr || row_ptr[0] != 0 || !kept_ptr || !n_kept || n_texts >= (1ull << 31) || n_keywords >= (1ull << 32))
+    return ACM_GPU_E_ARG;
+  if (acm_score_check (terms, class_ptr, bias, threshold, n_classes, n_keywords))
+    return ACM_GPU_E_ARG;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (row_ptr[t] > row_ptr[t + 1])
+      return ACM_GPU_E_ARG;
+  const uint64_t nnz = row_ptr[n_texts];
+  if (nnz && (!col || !val))
+    return ACM_GPU_E_ARG;
+  for (uint64_t e = 0; e < nnz; e++)
+    if (col[e] >= n_keywords)
+      return ACM_GPU_E_ARG;
+  uint64_t *count = calloc (n_keywords ? n_keywords : 1, sizeof (uint64_t));
+  if (!count)
+    return ACM_GPU_E_NOMEM;
+  const int counts_only = !kept_class || !kept_score;
+  int rc = ACM_GPU_OK;
+  for (int fill = 0; fill < 2 && !rc; fill++) {
+    uint64_t all = 0;
+    for (uint64_t t = 0; t < n_texts; t++) {
+      if (!fill)
+        kept_ptr[t] = all;
+      for (uint64_t e = row_ptr[t]; e < row_ptr[t + 1]; e++)
+        count[col[e]] += val[e];
+      uint32_t best_class = ACM_SCORE_NONE;
+      int64_t best_score = 0;
+      for (uint64_t c = 0; c < n_classes; c++) {
+        uint64_t sum = (uint64_t)bias[c];
+        for (uint64_t i = class_ptr[c]; i < class_ptr[c + 1]; i++)
+          sum += score_term_value (&terms[i], count[terms[i].keyword_id]);
+        const int64_t score = (int64_t)sum;
+        if (score >= threshold[c]) {
+          if (fill) {
+            kept_class[all] = (uint32_t)c;
+            kept_score[all] = score;
+            if (best_class == ACM_SCORE_NONE || score > best_score) {
+              best_class = (uint32_t)c;
+              best_score = score;
+            }
+          }
+          all++;
+        }
+      }
+      if (fill && best)
+        best[t] = best_class;
+      for (uint64_t e = row_ptr[t]; e < row_ptr[t + 1]; e++)
+        count[col[e]] = 0;
+    }
+    if (!fill) {
+      kept_ptr[n_texts] = all;
+      *n_kept = all;
+      if (counts_only)
+        break; /* the call only counts */
+      if (all > kept_capacity)
+        rc = ACM_GPU_E_OVERFLOW;
+    }
+  }
+  free (count);
+  return rc;
+}
+
+/* a kept pair of one column: the order of TOP is score descending, text ascending */
+typedef struct {
+  int64_t score;
+  uint32_t text;
+} ScoreTopItem;
+
+static int
+cmp_score_top (const void *a, const void *b) {
+  const ScoreTopItem *x = a, *y = b;
+  if (x->score != y->score)
+    return x->score > y->score ? -1 : 1;
+  return x->text < y->text ? -1 : x->text > y->text;
+}
+
+/* TOP of a kept matrix (include/acm_score.h): the kept pairs are put together by class (a counting sort,
+ * texts ascending within a class), every column is sorted and its first k entries are taken. */
+int
+acm_score_top (const uint64_t *kept_ptr, const uint32_t *kept_class, const int64_t *kept_score, uint64_t n_texts, uint64_t n_classes, uint32_t k,
+               uint64_t *class_hits, uint32_t *top_n, uint32_t *top_text, int64_t *top_score) {
+  if (!kept_ptr || kept_ptr[0] != 0 || n_texts >= (1ull << 31) || n_classes >= (1ull << 31) || k > ACM_SCORE_TOP_MAX ||
+      (n_classes && (!class_hits || !top_n || (k && (!top_text || !top_score)))))
+    return ACM_GPU_E_ARG;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (kept_ptr[t] > kept_ptr[t + 1])
+      return ACM_GPU_E_ARG;
+  const uint64_t n = kept_ptr[n_texts];
+  if (n && (!kept_class || !kept_score))
+    return ACM_GPU_E_ARG;
+  for (uint64_t e = 0; e < n; e++)
+    if (kept_class[e] >= n_classes)
+      return ACM_GPU_E_ARG;
+  uint64_t *begin = calloc (n_classes + 1, sizeof (uint64_t));
+  ScoreTopItem *item = malloc ((n ? n : 1) * sizeof *item);
+  if (!begin || !item) {
+    free (begin);
+    free (item);
+    return ACM_GPU_E_NOMEM;
+  }
+  for (uint64_t e = 0; e < n; e++)
+    begin[kept_class[e] + 1]++;
+  for (uint64_t c = 0; c < n_classes; c++) {
+    class_hits[c] = begin[c + 1];
+    begin[c + 1] += begin[c];
+  }
+  for (uint64_t t = 0; t < n_texts; t++)
+    for (uint64_t e = kept_ptr[t]; e < kept_ptr[t + 1]; e++)
+      item[begin[kept_class[e]]++] = (ScoreTopItem){ kept_score[e], (uint32_t)t };
+  /* (begin[c] has moved on to the end of column c) */
+  for (uint64_t c = 0; c < n_classes; c++) {
+    const uint64_t hits = class_hits[c];
+    ScoreTopItem *column = item + (begin[c] - hits);
+    if (k)
+      qsort (column, hits, sizeof *column, cmp_score_top);
+    top_n[c] = (uint32_t)(hits < k ? hits : k);
+    for (uint32_t j = 0; j < k; j++) {
+      top_text[c * k + j] = j < top_n[c] ? column[j].text : ACM_SCORE_NONE;
+      top_score[c * k + j] = j < top_n[c] ? column[j].score : 0;
+    }
+  }
+  free (item);
+  free (begin);
+  return ACM_GPU_OK;
+}
+
 /* SELECT of records in canonical order (include/acm_gpu.h), in place in the front of the array: the
  * plain sequential greedy pass.  The order is by end and the rule goes by start, so a round looks
  * at a window: from the first record that ends at or behind p up to the first that ends lmax or
@@ -1787,16 +1946,11 @@ acm_internal_cpu_tally_batch (ACMachine *m, const void *text, const uint64_t *of
   return rc;
 }
 
-/* the loop and the count matrix as above, into a room grown to what the matrix needs, then the sequential evaluation */
-int
-acm_internal_cpu_rules (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, const ACMRuleTerm *terms,
-                        const uint64_t *rule_ptr, const uint32_t *need, uint64_t n_rules, uint64_t *fired_ptr, uint32_t *fired, uint64_t fired_capacity,
-                        uint64_t *n_fired, uint64_t *total) {
-  if (!m || !offsets || !fired_ptr || !n_fired)
-    return ACM_GPU_E_ARG;
-  const uint64_t n_keywords = acm_nb_keywords (m);
-  if (acm_rules_check (terms, rule_ptr, need, n_rules, n_keywords))
-    return ACM_GPU_E_ARG;
+/* the loop and the count matrix as above, into a room of the call's own that is grown to what the matrix needs;
+ * the caller frees the three arrays, whatever comes back */
+static int
+cpu_tally_batch_grown (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, uint64_t **row_ptr_out,
+                       uint32_t **col_out, uint64_t **val_out, uint64_t *total) {
   uint64_t *row_ptr = malloc ((n_texts + 1) * sizeof (uint64_t));
   uint32_t *col = NULL;
   uint64_t *val = NULL, room = 1024, nnz = 0;
@@ -1816,8 +1970,52 @@ acm_internal_cpu_rules (ACMachine *m, const void *text, const uint64_t *offsets,
   }
   if (rc == ACM_GPU_E_OVERFLOW) /* (the second room is what the first attempt asked for: never expected) */
     rc = ACM_GPU_E_INTERNAL;
+  *row_ptr_out = row_ptr;
+  *col_out = col;
+  *val_out = val;
+  return rc;
+}
+
+/* that count matrix, then the sequential evaluation */
+int
+acm_internal_cpu_rules (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, const ACMRuleTerm *terms,
+                        const uint64_t *rule_ptr, const uint32_t *need, uint64_t n_rules, uint64_t *fired_ptr, uint32_t *fired, uint64_t fired_capacity,
+                        uint64_t *n_fired, uint64_t *total) {
+  if (!m || !offsets || !fired_ptr || !n_fired)
+    return ACM_GPU_E_ARG;
+  const uint64_t n_keywords = acm_nb_keywords (m);
+  if (acm_rules_check (terms, rule_ptr, need, n_rules, n_keywords))
+    return ACM_GPU_E_ARG;
+  uint64_t *row_ptr, *val;
+  uint32_t *col;
+  int rc = cpu_tally_batch_grown (m, text, offsets, n_texts, sym_bytes, &row_ptr, &col, &val, total);
   if (!rc)
     rc = acm_rules_matrix (row_ptr, col, val, n_texts, n_keywords, terms, rule_ptr, need, n_rules, fired_ptr, fired, fired_capacity, n_fired);
+  free (val);
+  free (col);
+  free (row_ptr);
+  return rc;
+}
+
+/* the same in front of the scores and, when the kept entries were written and k > 0, their TOP */
+int
+acm_internal_cpu_score (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, const ACMScoreTerm *terms,
+                        const uint64_t *class_ptr, const int64_t *bias, const int64_t *threshold, uint64_t n_classes, uint64_t *kept_ptr,
+                        uint32_t *kept_class, int64_t *kept_score, uint64_t kept_capacity, uint64_t *n_kept, uint32_t *best, uint32_t k,
+                        uint64_t *class_hits, uint32_t *top_n, uint32_t *top_text, int64_t *top_score, uint64_t *total) {
+  if (!m || !offsets || !kept_ptr || !n_kept || k > ACM_SCORE_TOP_MAX)
+    return ACM_GPU_E_ARG;
+  const uint64_t n_keywords = acm_nb_keywords (m);
+  if (acm_score_check (terms, class_ptr, bias, threshold, n_classes, n_keywords))
+    return ACM_GPU_E_ARG;
+  uint64_t *row_ptr, *val;
+  uint32_t *col;
+  int rc = cpu_tally_batch_grown (m, text, offsets, n_texts, sym_bytes, &row_ptr, &col, &val, total);
+  if (!rc)
+    rc = acm_score_matrix (row_ptr, col, val, n_texts, n_keywords, terms, class_ptr, bias, threshold, n_classes, kept_ptr, kept_class, kept_score,
+                           kept_capacity, n_kept, best);
+  if (!rc && k && kept_class && kept_score && class_hits && top_n && top_text && top_score)
+    rc = acm_score_top (kept_ptr, kept_class, kept_score, n_texts, n_classes, k, class_hits, top_n, top_text, top_score);
   free (val);
   free (col);
   free (row_ptr);

@@ -88,6 +88,12 @@ int acm_internal_cpu_tally_batch (ACMachine *m, const void *text, const uint64_t
 int acm_internal_cpu_rules (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, const ACMRuleTerm *terms,
                             const uint64_t *rule_ptr, const uint32_t *need, uint64_t n_rules, uint64_t *fired_ptr, uint32_t *fired,
                             uint64_t fired_capacity, uint64_t *n_fired, uint64_t *total);
+/* acm_score's host path: the same count matrix, then acm_score_matrix and, when the kept entries had room and k > 0, acm_score_top
+ * (arguments as acm_score's) */
+int acm_internal_cpu_score (ACMachine *m, const void *text, const uint64_t *offsets, uint64_t n_texts, uint32_t sym_bytes, const ACMScoreTerm *terms,
+                            const uint64_t *class_ptr, const int64_t *bias, const int64_t *threshold, uint64_t n_classes, uint64_t *kept_ptr,
+                            uint32_t *kept_class, int64_t *kept_score, uint64_t kept_capacity, uint64_t *n_kept, uint32_t *best, uint32_t k,
+                            uint64_t *class_hits, uint32_t *top_n, uint32_t *top_text, int64_t *top_score, uint64_t *total);
 /* acm_grep_lines' host path: acm_split_offsets, then acm_internal_cpu_grep (arguments as acm_grep_lines') */
 int acm_internal_cpu_grep_lines (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *delims, uint32_t n_delims,
                                  uint32_t split_flags, uint32_t grep_flags, uint64_t *n_texts, uint64_t *n_kept, uint64_t *total, void *out,

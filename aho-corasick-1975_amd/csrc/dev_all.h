@@ -191,5 +191,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_edit.h"
 #include "dev_chains.h"
 #include "dev_segment.h"
+#include "dev_score.h"
 
 } // namespace

@@ -1056,7 +1056,8 @@ int acm_tally_batch (ACMachine *machine, const void *text, const uint64_t *offse
  * into a room the call grows itself, then acm_rules_matrix.  A missing device stays an error, never
  * a fallback.
  * Out of scope: positional rules (distance, order, offset), regular expressions, per-rule hit
- * counts on the device (a bincount of fired[]), flows, several GPUs. */
+ * counts on the device (a bincount of fired[]), flows, several GPUs.  Weighted sums of the counts,
+ * thresholds on them, the best class of a text and the best texts of a class are acm_score.h's. */
 #define ACM_RULE_NO_MAX 0xFFFFFFFFu
 typedef struct {
   uint32_t keyword_id, lo, hi;
@@ -2299,4 +2300,5 @@ int acm_gpu_synth_text (int device, void *d_text, uint64_t n, uint64_t global_be
 }
 #endif
 #endif
+#include "acm_score.h"
 #include "acm_segment.h"
