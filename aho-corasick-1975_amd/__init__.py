@@ -15,6 +15,7 @@ from .binding import (  # noqa: F401
     tally_batch_records, TalliedBatch,
     rule, present, absent, between, RuleSet, Rules, Fired, rules_matrix, ACM_RULE_NO_MAX,
     weight, score_class, ScoreModel, Score, Scored, ScoreInfo, score_matrix, score_top, ACM_SCORE_NO_CAP, ACM_SCORE_NONE, ACM_SCORE_TOP_MAX,
+    Indexed, index_matrix, index_concat,
     words_records, ASCII_WORD, ACM_WORDS_LEFT, ACM_WORDS_RIGHT, ACM_WORDS_BOTH,
     context_records, Snippets, ACM_CONTEXT_SYMBOLS, ACM_CONTEXT_TEXTS, ACM_CONTEXT_EACH, ACM_CONTEXT_MERGE, ACM_CONTEXT_NONE,
     anchored_records, ACM_ANCHORED_PREFIXES, ACM_ANCHORED_LONGEST, ACM_ANCHORED_WHOLE, ACM_LOOKUP_NONE,

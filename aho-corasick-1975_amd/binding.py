@@ -111,7 +111,7 @@ class TemplateSpec(C.Structure):
 
 _lib = None
 
-# every symbol include/acm.h and include/acm_gpu.h (with include/acm_segment.h and include/acm_score.h) declare
+# every symbol include/acm.h and include/acm_gpu.h (with include/acm_segment.h, include/acm_score.h and include/acm_index.h) declare
 EXPORTS = [
     "ACM_CMP_DEFAULT", "ACM_INCREMENTAL_STRING_MATCHING", "acm_create", "acm_initiate",
     "acm_insert_letter_of_keyword", "acm_insert_end_of_keyword", "acm_match", "acm_matcher_init", "acm_get_match",
@@ -167,6 +167,8 @@ EXPORTS = [
     "acm_score_check", "acm_score_matrix", "acm_score_top", "acm_gpu_score_create", "acm_gpu_score_destroy", "acm_gpu_score_info",
     "acm_gpu_score_matrix_tmp_bytes", "acm_gpu_score_matrix_device", "acm_gpu_score_top_tmp_bytes", "acm_gpu_score_top_device",
     "acm_gpu_score_tmp_bytes", "acm_gpu_score_device", "acm_gpu_score_host", "acm_score",
+    "acm_index_matrix", "acm_index_concat", "acm_gpu_index_matrix_tmp_bytes", "acm_gpu_index_matrix_device", "acm_gpu_index_concat_tmp_bytes",
+    "acm_gpu_index_concat_device", "acm_gpu_index_tmp_bytes", "acm_gpu_index_device", "acm_gpu_index_host", "acm_index",
 ]
 
 
@@ -377,6 +379,25 @@ def lib():
     for fn in (L.acm_gpu_score_host, L.acm_score):
         fn.restype = i32
         fn.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64), vp, u32, vp, vp, vp, vp, C.POINTER(u64)]
+    L.acm_index_matrix.restype = i32
+    L.acm_index_matrix.argtypes = [vp, vp, vp, u64, u64, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_index_concat.restype = i32
+    L.acm_index_concat.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_index_matrix_tmp_bytes.restype = sz
+    L.acm_gpu_index_matrix_tmp_bytes.argtypes = [vp, u64, u64, u64]
+    L.acm_gpu_index_matrix_device.restype = i32
+    L.acm_gpu_index_matrix_device.argtypes = [vp, vp, vp, vp, u64, u64, u64, vp, vp, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_index_concat_tmp_bytes.restype = sz
+    L.acm_gpu_index_concat_tmp_bytes.argtypes = [vp, u64]
+    L.acm_gpu_index_concat_device.restype = i32
+    L.acm_gpu_index_concat_device.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_index_tmp_bytes.restype = sz
+    L.acm_gpu_index_tmp_bytes.argtypes = [vp, u64, u64, u64, u64, u64, u64, u64]
+    L.acm_gpu_index_device.restype = i32
+    L.acm_gpu_index_device.argtypes = [vp, vp, u64, vp, u64, u64, u64, u64, u64, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, sz, vp]
+    for fn in (L.acm_gpu_index_host, L.acm_index):
+        fn.restype = i32
+        fn.argtypes = [vp, vp, vp, u64, u64, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.acm_segment_records.restype = i32
     L.acm_segment_records.argtypes = [vp, u64, vp, u64, u32, C.POINTER(u64), vp]
     L.acm_gpu_segment_tmp_bytes.restype = sz
@@ -1075,6 +1096,112 @@ def _rules_host_call(fn, what, handle, t, sym_size, off, ruleset):
     def call(fired_ptr, fired, cap, n):
         return fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, *rs.args(), fired_ptr, fired, cap, n, C.byref(total))
     return _fired_host_call(call, what, n_texts, total)
+
+
+class Indexed:
+    """What the index calls return: the inverted index of a batch, the count matrix transposed, in CSR
+    form over keywords -- post_ptr (n_keywords + 1 entries), post_text (text_base + t, strictly
+    ascending within a keyword) and post_count.  int64 / int32 / int64 device tensors from Plan.index(),
+    Plan.index_matrix() and Plan.index_concat() -- post_text and post_count have room for post_capacity
+    entries, their first nnz count --, uint64 / uint32 / uint64 numpy arrays cut to size from the host
+    calls.  nnz, total, need and need_pairs are Python ints as a TalliedBatch has them (total None where
+    no text was scanned); forms is (lists put in order by the fast form, by the wide form) from the
+    device calls, None elsewhere."""
+
+    def __init__(self, post_ptr, post_text, post_count, nnz, total=None, text_base=0, need=None, need_pairs=None, post_capacity=None, forms=None):
+        self.post_ptr, self.post_text, self.post_count, self.nnz, self.total, self.text_base = post_ptr, post_text, post_count, nnz, total, text_base
+        self.need, self.need_pairs, self.post_capacity, self.forms = need, need_pairs, post_capacity, forms
+
+    @property
+    def n_keywords(self):
+        return int(self.post_ptr.shape[0]) - 1
+
+    def df(self):
+        """the document frequency of every keyword, df[k] = post_ptr[k + 1] - post_ptr[k], where the index lies"""
+        return self.post_ptr[1:] - self.post_ptr[:-1]
+
+    def postings(self, k):
+        """(post_text, post_count) of keyword k: views of its list"""
+        a, b = int(self.post_ptr[int(k)]), int(self.post_ptr[int(k) + 1])
+        return self.post_text[a:b], self.post_count[a:b]
+
+    def to_sparse_csr(self, n_texts):
+        """The index as a torch.sparse_csr_tensor of n_keywords x n_texts int64 counts (column t is text
+        text_base + t), built on the arrays where they are; only the text ids are rebased when
+        text_base is not 0."""
+        import torch
+
+        def tensor(a, dtype):
+            return a.view(dtype) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).view(dtype)
+        col = tensor(self.post_text, torch.int32)[:self.nnz]
+        if self.text_base:
+            col = (col.to(torch.int64) & 0xFFFFFFFF).sub_(int(self.text_base)).to(torch.int32)
+        return torch.sparse_csr_tensor(tensor(self.post_ptr, torch.int64), col, tensor(self.post_count, torch.int64)[:self.nnz],
+                                       size=(self.n_keywords, int(n_texts)))
+
+
+def _indexed_host_call(call, what, n_keywords, text_base=0, total=None):
+    """call(post_ptr, post_text, post_count, capacity, nnz) -> rc, for the host calls: an Indexed of numpy arrays
+    out.  An output overflow is repeated once with the size the call reports."""
+    post_ptr = np.zeros(int(n_keywords) + 1, np.uint64)
+    cap = 1024
+    for attempt in (0, 1):
+        post_text, post_count = np.zeros(cap, np.uint32), np.zeros(cap, np.uint64)
+        n = C.c_uint64(0)
+        rc = call(post_ptr.ctypes.data, post_text.ctypes.data, post_count.ctypes.data, cap, C.byref(n))
+        if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
+            cap = int(n.value)
+            continue
+        _check(rc, what)
+        m = int(n.value)
+        return Indexed(post_ptr, post_text[:m], post_count[:m], m, int(total.value) if total is not None else None, int(text_base), post_capacity=cap)
+
+
+def index_matrix(tallied, n_keywords, text_base=0):
+    """acm_index_matrix(): the inverted index of the count matrix `tallied` (a TalliedBatch of numpy
+    arrays) over n_keywords keywords, by the sequential transposition on the host.  Returns an Indexed
+    of numpy arrays (total: the sum of the counts)."""
+    row_ptr = np.ascontiguousarray(tallied.row_ptr, dtype=np.uint64)
+    col = np.ascontiguousarray(tallied.col, dtype=np.uint32)
+    val = np.ascontiguousarray(tallied.val, dtype=np.uint64)
+    assert row_ptr.size >= 1, "row_ptr has n_texts + 1 entries"
+
+    def call(post_ptr, post_text, post_count, cap, n):
+        return lib().acm_index_matrix(row_ptr.ctypes.data, _ptr(col), _ptr(val), row_ptr.size - 1, int(n_keywords), int(text_base), post_ptr, post_text,
+                                      post_count, cap, n)
+    got = _indexed_host_call(call, "acm_index_matrix", n_keywords, text_base)
+    got.total = int(got.post_count.sum())
+    return got
+
+
+def index_concat(a, b):
+    """acm_index_concat(): per keyword a's list, then b's (two Indexed of numpy arrays; a has no more
+    keywords than b, and b's text ids lie above a's in every list).  Returns an Indexed of numpy arrays."""
+    arrays = []
+    for x in (a, b):
+        arrays.append((np.ascontiguousarray(x.post_ptr, dtype=np.uint64), np.ascontiguousarray(x.post_text, dtype=np.uint32),
+                       np.ascontiguousarray(x.post_count, dtype=np.uint64)))
+    (ap, at, ac), (bp, bt, bc) = arrays
+    assert ap.size >= 1 and bp.size >= 1, "post_ptr has n_keywords + 1 entries"
+
+    def call(out_ptr, out_text, out_count, cap, n):
+        return lib().acm_index_concat(ap.ctypes.data, _ptr(at), _ptr(ac), ap.size - 1, bp.ctypes.data, _ptr(bt), _ptr(bc), bp.size - 1, out_ptr, out_text,
+                                      out_count, cap, n)
+    got = _indexed_host_call(call, "acm_index_concat", bp.size - 1, a.text_base)
+    got.total = a.total + b.total if a.total is not None and b.total is not None else None
+    return got
+
+
+def _index_host_call(fn, what, handle, t, sym_size, off, n_keywords, text_base):
+    """acm_gpu_index_host / acm_index: numpy in, an Indexed of numpy arrays out"""
+    n_texts = off.size - 1
+    assert t.size * t.itemsize == int(off[-1]) * sym_size, "the last offset is the number of symbols"
+    total = C.c_uint64(0)
+
+    def call(post_ptr, post_text, post_count, cap, n):
+        return fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, int(text_base), post_ptr, int(n_keywords), post_text, post_count,
+                  cap, n, C.byref(total))
+    return _indexed_host_call(call, what, n_keywords, text_base, total)
 
 
 def weight(k, w, cap=None):
@@ -2612,6 +2739,15 @@ class Machine:
         packed, offsets = self._pack_texts(texts)
         return _score_host_call(self.L.acm_score, "acm_score", self.handle, packed, self.sym_size, offsets, model, k)
 
+    def index(self, texts, n_keywords=None, text_base=0):
+        """acm_index(): the inverted index of a list of texts (bytes or arrays of symbols), each scanned
+        from the root on its own in ONE call: which texts hold keyword k, and how often.  n_keywords
+        (None: the machine's) may be larger for a dictionary that will grow; text ids start at
+        text_base.  Returns an Indexed of numpy arrays."""
+        packed, offsets = self._pack_texts(texts)
+        nk = self.nb_keywords if n_keywords is None else int(n_keywords)
+        return _index_host_call(self.L.acm_index, "acm_index", self.handle, packed, self.sym_size, offsets, nk, text_base)
+
 
 class Score:
     """A score model on a plan's device (ACMScore): Plan.score_create() makes one."""
@@ -3449,6 +3585,110 @@ class Plan:
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         assert off.size >= 1, "offsets has n_texts + 1 entries"
         return _score_host_call(lib().acm_gpu_score_host, "acm_gpu_score_host", self.h, t, self.sym_size, off, model, k)
+
+    def _index_keywords(self, n_keywords):
+        return int(lib().acm_gpu_tally_keywords(self.h)) if n_keywords is None else int(n_keywords)
+
+    def _post_outputs(self, dev, n_keywords, post_capacity):
+        import torch
+        post_ptr = torch.zeros(n_keywords + 1, dtype=torch.int64, device=dev)
+        post_text = torch.zeros(post_capacity, dtype=torch.int32, device=dev) if post_capacity else None
+        post_count = torch.zeros(post_capacity, dtype=torch.int64, device=dev) if post_capacity else None
+        return post_ptr, post_text, post_count
+
+    def index(self, text, offsets, n_keywords=None, text_base=0, window=None, capacity=None, pair_capacity=None, post_capacity=None):
+        """acm_gpu_index_device(): the inverted index of a batch on the device: the tally of tally_batch()
+        (same `text`, `offsets`, `window`, `capacity`, `pair_capacity`) and the transposition behind it
+        in one call; neither a record nor the count matrix leaves the device.  n_keywords (None: the
+        plan's) may be larger; text ids start at text_base.  post_capacity: the room of post_text and
+        post_count (0: count only, which gives post_ptr and so df; None: counted first, then sized by
+        the count).  Returns an Indexed of device tensors; synchronises to read its four numbers."""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        window = int(window) if window is not None else 1 << 24
+        capacity = int(capacity) if capacity is not None else 1 << 20
+        pair_capacity = int(pair_capacity) if pair_capacity is not None else capacity
+        nk = self._index_keywords(n_keywords)
+        dev = text.device
+        res = torch.zeros(6, dtype=torch.int64, device=dev)                      # nnz, total, need, need_pairs, forms[2]
+
+        def call(cap):
+            tb = lib().acm_gpu_index_tmp_bytes(self.h, window, capacity, pair_capacity, n_symbols, n_texts, nk, cap)
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+            post_ptr, post_text, post_count = self._post_outputs(dev, nk, cap)
+            p = (lambda x: x.data_ptr() if x is not None else None)
+            _check(lib().acm_gpu_index_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity, nk,
+                                              int(text_base), post_ptr.data_ptr(), p(post_text), p(post_count), cap, res.data_ptr(), res.data_ptr() + 32,
+                                              res.data_ptr() + 8, res.data_ptr() + 16, res.data_ptr() + 24, tmp.data_ptr(), tmp.numel(), self._stream()),
+                   "acm_gpu_index_device")
+            nnz, total, need, need_pairs, fast, wide = (int(x) for x in res.cpu())
+            return Indexed(post_ptr, post_text, post_count, nnz, total, int(text_base), need, need_pairs, cap, (fast, wide))
+        got = call(int(post_capacity) if post_capacity is not None else 0)
+        if post_capacity is None and got.nnz:
+            got = call(got.nnz)
+        return got
+
+    def index_matrix(self, tallied, n_keywords=None, text_base=0, post_capacity=None):
+        """acm_gpu_index_matrix_device(): the transposition of a count matrix that lies on the device:
+        `tallied` is a TalliedBatch of device tensors, tally_batch()'s or the caller's own (row_ptr int64
+        with n_texts + 1 entries, col int32, val int64).  Returns an Indexed of device tensors (total,
+        need and need_pairs None); synchronises to read nnz."""
+        import torch
+        row_ptr, col, val = tallied.row_ptr, tallied.col, tallied.val
+        assert row_ptr.is_cuda and row_ptr.is_contiguous() and row_ptr.dtype == torch.int64
+        assert col.is_contiguous() and col.dtype == torch.int32 and val.is_contiguous() and val.dtype == torch.int64
+        n_texts = row_ptr.numel() - 1
+        assert n_texts >= 0
+        nk = self._index_keywords(n_keywords)
+        dev = row_ptr.device
+        res = torch.zeros(3, dtype=torch.int64, device=dev)                      # nnz, forms[2]
+
+        def call(cap):
+            tb = lib().acm_gpu_index_matrix_tmp_bytes(self.h, n_texts, nk, cap)
+            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+            post_ptr, post_text, post_count = self._post_outputs(dev, nk, cap)
+            p = (lambda x: x.data_ptr() if x is not None else None)
+            _check(lib().acm_gpu_index_matrix_device(self.h, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), n_texts, nk, int(text_base),
+                                                     post_ptr.data_ptr(), p(post_text), p(post_count), cap, res.data_ptr(), res.data_ptr() + 8,
+                                                     tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_index_matrix_device")
+            nnz, fast, wide = (int(x) for x in res.cpu())
+            return Indexed(post_ptr, post_text, post_count, nnz, None, int(text_base), post_capacity=cap, forms=(fast, wide))
+        got = call(int(post_capacity) if post_capacity is not None else 0)
+        if post_capacity is None and got.nnz:
+            got = call(got.nnz)
+        return got
+
+    def index_concat(self, a, b, out_capacity=None):
+        """acm_gpu_index_concat_device(): per keyword a's list, then b's, for two Indexed of device
+        tensors (a has no more keywords than b, and b's text ids lie above a's in every list).
+        out_capacity None: a.nnz + b.nnz.  Returns an Indexed of device tensors; synchronises to read nnz."""
+        import torch
+        dev = a.post_ptr.device
+        for x in (a, b):
+            assert x.post_ptr.is_cuda and x.post_ptr.is_contiguous() and x.post_ptr.dtype == torch.int64
+        nka, nkb = a.n_keywords, b.n_keywords
+        cap = int(out_capacity) if out_capacity is not None else int(a.nnz) + int(b.nnz)
+        res = torch.zeros(1, dtype=torch.int64, device=dev)
+        tb = lib().acm_gpu_index_concat_tmp_bytes(self.h, nkb)
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        out_ptr, out_text, out_count = self._post_outputs(dev, nkb, cap)
+        p = (lambda x: x.data_ptr() if x is not None else None)
+        _check(lib().acm_gpu_index_concat_device(self.h, a.post_ptr.data_ptr(), p(a.post_text), p(a.post_count), nka, b.post_ptr.data_ptr(),
+                                                 p(b.post_text), p(b.post_count), nkb, out_ptr.data_ptr(), p(out_text), p(out_count), cap,
+                                                 res.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_index_concat_device")
+        total = a.total + b.total if a.total is not None and b.total is not None else None
+        return Indexed(out_ptr, out_text, out_count, int(res.item()), total, a.text_base, post_capacity=cap)
+
+    def index_host(self, text, offsets, n_keywords=None, text_base=0):
+        """acm_gpu_index_host(): the same as index() from host arrays, through the C ABI only (no torch).
+        The call sizes its windows and its pair room itself.  Returns an Indexed of numpy arrays."""
+        t = np.ascontiguousarray(text)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        return _index_host_call(lib().acm_gpu_index_host, "acm_gpu_index_host", self.h, t, self.sym_size, off, self._index_keywords(n_keywords), text_base)
 
     def patterns_create(self, patternset):
         """acm_gpu_patterns_create(): `patternset` (a PatternSet, or lists of (keyword_id, offset, length)

@@ -5453,6 +5453,340 @@ acm_gpu_score_host (ACMPlan *plan, const void *text, const uint64_t *offsets, ui
   return ACM_GPU_OK;
 }
 
+/* ------------------------------------------------------------------ the inverted index of a batch (include/acm_index.h, dev_index.h)
+ * The passes that transpose a count matrix on the device into the postings of every keyword, and the
+ * concatenation of two indexes; acm_gpu_index_device runs the former behind acm_gpu_tally_batch_device. */
+namespace {
+size_t
+index_sort_bytes (uint64_t n) {
+  size_t tmp = 0;
+  hipcub::DoubleBuffer<unsigned long long> k (nullptr, nullptr), v (nullptr, nullptr);
+  (void)hipcub::DeviceRadixSort::SortPairs (nullptr, tmp, k, v, (int)n, 0, 64, nullptr);
+  return tmp;
+}
+
+/* ACM_GPU_INDEX_LIST=<1 to 4,096>: the longest list of the fast form (tests, experiments) */
+uint32_t
+index_list () {
+  return tunable ("ACM_GPU_INDEX_LIST", INDEX_LIST_DEFAULT, 1, INDEX_LIST_MAX, Tune::Any);
+}
+
+/* LDS of index_sort_kernel for lists of up to `longest` entries: the keys, padded to a power of two, and the counts */
+size_t
+index_sort_lds (uint32_t longest) {
+  uint32_t p2 = 1;
+  while (p2 < longest)
+    p2 <<= 1;
+  return ((size_t)p2 + longest) * 8;
+}
+
+/* what index_carve derives beside K's pointers */
+struct IndexRoom {
+  size_t zero_bytes = 0; /* control words and the keywords' counts: the head of the scratch, cleared in front of every call */
+  long long *cnt = nullptr, *ptr = nullptr, *wcnt = nullptr, *wbase = nullptr; /* K's, as the sums take them */
+  unsigned long long *key[2] = { nullptr, nullptr }, *val[2] = { nullptr, nullptr }; /* the sort room and its second half */
+  CubRoom cub;
+  void *sort_tmp = nullptr;
+  size_t sort_bytes = 0;
+};
+/* wide: the call has a wide form (n_texts above the fast form's longest list, and a room to fill) */
+IndexRoom
+index_carve (Carve &c, uint64_t n_keywords, uint64_t post_capacity, bool wide, IndexK &K) {
+  IndexRoom R;
+  K.G.ctl = c.take<RulesCtl> (1);
+  K.ictl = c.take<IndexCtl> (1);
+  R.cnt = c.take<long long> (n_keywords + 1);
+  R.zero_bytes = c.used;
+  R.ptr = c.take<long long> (n_keywords + 1);
+  R.cub = cub_room (c, 0, n_keywords + 1);
+  K.tier = c.take<uint32_t> (n_keywords);
+  if (wide) {
+    R.wcnt = c.take<long long> (n_keywords + 1);
+    R.wbase = c.take<long long> (n_keywords + 1);
+    for (int h = 0; h < 2; h++) {
+      R.key[h] = c.take<unsigned long long> ((size_t)post_capacity);
+      R.val[h] = c.take<unsigned long long> ((size_t)post_capacity);
+    }
+    R.sort_bytes = index_sort_bytes (post_capacity);
+    R.sort_tmp = c.take (R.sort_bytes + 16);
+  }
+  K.cnt = reinterpret_cast<unsigned long long *> (R.cnt);
+  K.ptr = reinterpret_cast<const unsigned long long *> (R.ptr);
+  K.wcnt = reinterpret_cast<unsigned long long *> (R.wcnt);
+  K.wbase = reinterpret_cast<const unsigned long long *> (R.wbase);
+  K.wkey = R.key[0];
+  K.wval = R.val[0];
+  return R;
+}
+
+bool
+index_wide (uint64_t n_texts, uint64_t post_capacity) {
+  return post_capacity > 0 && n_texts > index_list ();
+}
+
+/* acm_gpu_index_matrix_tmp_bytes behind its checks */
+size_t
+index_bytes (uint64_t n_texts, uint64_t n_keywords, uint64_t post_capacity) {
+  Carve c;
+  IndexK K{};
+  index_carve (c, n_keywords, post_capacity, index_wide (n_texts, post_capacity), K);
+  return c.total ();
+}
+
+/* the matrix calls' own arguments */
+bool
+index_args_ok (const ACMPlan *plan, uint64_t n_texts, uint64_t n_keywords, uint64_t text_base, const uint64_t *d_post_ptr, const uint32_t *d_post_text,
+               const uint64_t *d_post_count, uint64_t post_capacity, const uint64_t *d_nnz) {
+  return plan && n_texts < (1ull << 31) && n_keywords >= plan->covered_keywords && n_keywords < (1ull << 32) && text_base <= (1ull << 32) &&
+         text_base + n_texts <= (1ull << 32) && post_capacity < (1ull << 31) && d_post_ptr && d_nnz &&
+         ((d_post_text && d_post_count) || (post_capacity == 0 && !d_post_text && !d_post_count));
+}
+
+/* without a text: every list is empty */
+int
+index_empty (uint64_t n_keywords, uint64_t *d_post_ptr, uint64_t *d_nnz, uint64_t *d_forms, hipStream_t st) {
+  HIP_TRY (hipMemsetAsync (d_post_ptr, 0, (n_keywords + 1) * 8, st));
+  HIP_TRY (hipMemsetAsync (d_nnz, 0, 8, st));
+  if (d_forms)
+    HIP_TRY (hipMemsetAsync (d_forms, 0, 16, st));
+  return ACM_GPU_OK;
+}
+
+/* the passes of dev_index.h on a matrix on the device; `tb` as rules_evaluate has it */
+int
+index_transpose (ACMPlan *plan, const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_val, uint64_t n_texts, uint64_t n_keywords,
+                 uint64_t text_base, uint64_t *d_post_ptr, uint32_t *d_post_text, uint64_t *d_post_count, uint64_t post_capacity, uint64_t *d_nnz,
+                 uint64_t *d_forms, void *d_tmp, hipStream_t st, const TbCtl *tb, uint64_t tb_capacity, uint64_t tb_pair_capacity) {
+  Carve carve (d_tmp);
+  IndexK K{};
+  const bool wide = index_wide (n_texts, post_capacity);
+  const IndexRoom L = index_carve (carve, n_keywords, post_capacity, wide, K);
+  K.G.row_ptr = reinterpret_cast<const unsigned long long *> (d_row_ptr);
+  K.G.n_texts = n_texts;
+  K.G.tb = tb;
+  K.G.tb_capacity = tb_capacity;
+  K.G.tb_pair_capacity = tb_pair_capacity;
+  K.G.error = error_word (plan);
+  K.col = d_col;
+  K.val = reinterpret_cast<const unsigned long long *> (d_val);
+  K.n_keywords = n_keywords;
+  K.text_base = text_base;
+  K.post_capacity = post_capacity;
+  K.list = index_list ();
+  K.d_post_ptr = reinterpret_cast<unsigned long long *> (d_post_ptr);
+  K.d_post_text = d_post_text;
+  K.d_post_count = reinterpret_cast<unsigned long long *> (d_post_count);
+  K.d_nnz = reinterpret_cast<unsigned long long *> (d_nnz);
+  K.d_forms = reinterpret_cast<unsigned long long *> (d_forms);
+  HIP_TRY (hipMemsetAsync (d_tmp, 0, L.zero_bytes, st));
+  /* the grids of the passes over the matrix's entries: the device alone knows how many there are.  Two blocks a CU count:
+   * every block ends with an atomic per LDS counter it used */
+  const dim3 entry_grid = capped_grid (plan, ~0ull), hist_grid = capped_grid (plan, ~0ull, 2),
+             keyword_grid = capped_grid (plan, (n_keywords + 1 + 255) / 256);
+  /* 1. */
+  HIP_TRY (launch (rules_check_kernel, capped_grid (plan, (n_texts + 1 + 255) / 256), dim3 (256), 0, st, K.G));
+  /* 2. */
+  HIP_TRY (launch (index_hist_kernel, hist_grid, dim3 (256), 0, st, K));
+  /* 3. */
+  HIP_TRY (exclusive_sum (L.cub, L.cnt, L.ptr, n_keywords + 1, st));
+  HIP_TRY (launch (index_finish_kernel, keyword_grid, dim3 (256), 0, st, K));
+  if (d_post_text) {
+    if (wide) {
+      HIP_TRY (exclusive_sum (L.cub, L.wcnt, L.wbase, n_keywords + 1, st));
+      HIP_TRY (hipMemsetAsync (L.key[0], 0xFF, (size_t)post_capacity * 8, st)); /* the sentinels */
+    }
+    /* 4. */
+    HIP_TRY (launch (index_scatter_kernel, entry_grid, dim3 (256), 0, st, K));
+    /* 5. (a block per list of the tier: the host knows no more than that there are at most n_keywords) */
+    const uint32_t wave_list = std::min (K.list, INDEX_WAVE_LIST);
+    if (wave_list >= 2)
+      HIP_TRY (launch (index_sort_kernel<WAVE, 0>, capped_grid (plan, n_keywords, 16), dim3 (WAVE), index_sort_lds (wave_list), st, K, wave_list));
+    if (K.list > INDEX_WAVE_LIST) {
+      const size_t lds = index_sort_lds (K.list);
+      if (lds + 64 > 64 * 1024) /* (the longest list only: beyond what a kernel may take unasked) */
+        HIP_TRY (hipFuncSetAttribute (reinterpret_cast<const void *> (&index_sort_kernel<INDEX_SORT_THREADS, 1>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      const uint32_t per_cu = (uint32_t)std::max<size_t> (1, std::min<size_t> (8, (128 * 1024) / lds));
+      HIP_TRY (launch (index_sort_kernel<INDEX_SORT_THREADS, 1>, capped_grid (plan, n_keywords, per_cu), dim3 (INDEX_SORT_THREADS), lds, st, K, K.list));
+    }
+    /* 6. */
+    if (wide) {
+      int key_bits = INDEX_TEXT_BITS + 1;
+      while (key_bits < 63 && (n_keywords >> (key_bits - INDEX_TEXT_BITS)) != 0)
+        key_bits++;
+      hipcub::DoubleBuffer<unsigned long long> keys (L.key[0], L.key[1]), vals (L.val[0], L.val[1]);
+      size_t sort_bytes = L.sort_bytes;
+      HIP_TRY (hipcub::DeviceRadixSort::SortPairs (L.sort_tmp, sort_bytes, keys, vals, (int)post_capacity, 0, key_bits, st));
+      K.skey = keys.Current ();
+      K.sval = vals.Current ();
+      HIP_TRY (launch (index_wide_put_kernel, capped_grid (plan, (post_capacity + 255) / 256), dim3 (256), 0, st, K));
+    }
+  }
+  if (d_forms)
+    HIP_TRY (launch (index_forms_kernel, dim3 (1), dim3 (WAVE), 0, st, K));
+  return ACM_GPU_OK;
+}
+
+bool
+index_concat_args_ok (const ACMPlan *plan, const uint64_t *d_a_ptr, uint64_t n_keywords_a, const uint64_t *d_b_ptr, uint64_t n_keywords_b,
+                      const uint64_t *d_out_ptr, const uint32_t *d_out_text, const uint64_t *d_out_count, uint64_t out_capacity,
+                      const uint64_t *d_out_nnz) {
+  return plan && d_a_ptr && d_b_ptr && n_keywords_a <= n_keywords_b && n_keywords_b < (1ull << 32) && out_capacity < (1ull << 31) && d_out_ptr &&
+         d_out_nnz && ((d_out_text && d_out_count) || (out_capacity == 0 && !d_out_text && !d_out_count));
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_index_matrix_tmp_bytes (const ACMPlan *plan, uint64_t n_texts, uint64_t n_keywords, uint64_t post_capacity) {
+  if (!plan || n_texts >= (1ull << 31) || n_keywords >= (1ull << 32) || post_capacity >= (1ull << 31))
+    return 0;
+  return index_bytes (n_texts, n_keywords, post_capacity);
+}
+
+extern "C" int
+acm_gpu_index_matrix_device (ACMPlan *plan, const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_val, uint64_t n_texts, uint64_t n_keywords,
+                             uint64_t text_base, uint64_t *d_post_ptr, uint32_t *d_post_text, uint64_t *d_post_count, uint64_t post_capacity,
+                             uint64_t *d_nnz, uint64_t *d_forms, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!index_args_ok (plan, n_texts, n_keywords, text_base, d_post_ptr, d_post_text, d_post_count, post_capacity, d_nnz))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0)
+    return index_empty (n_keywords, d_post_ptr, d_nnz, d_forms, st);
+  if (!d_row_ptr || !d_tmp || tmp_bytes < index_bytes (n_texts, n_keywords, post_capacity))
+    return ACM_GPU_E_ARG;
+  return index_transpose (plan, d_row_ptr, d_col, d_val, n_texts, n_keywords, text_base, d_post_ptr, d_post_text, d_post_count, post_capacity, d_nnz, d_forms,
+                          d_tmp, st, nullptr, 0, 0);
+}
+
+extern "C" size_t
+acm_gpu_index_concat_tmp_bytes (const ACMPlan *plan, uint64_t n_keywords_b) {
+  if (!plan || n_keywords_b >= (1ull << 32))
+    return 0;
+  Carve c;
+  c.take<RulesCtl> (1);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_index_concat_device (ACMPlan *plan, const uint64_t *d_a_ptr, const uint32_t *d_a_text, const uint64_t *d_a_count, uint64_t n_keywords_a,
+                             const uint64_t *d_b_ptr, const uint32_t *d_b_text, const uint64_t *d_b_count, uint64_t n_keywords_b, uint64_t *d_out_ptr,
+                             uint32_t *d_out_text, uint64_t *d_out_count, uint64_t out_capacity, uint64_t *d_out_nnz, void *d_tmp, size_t tmp_bytes,
+                             void *stream) {
+  if (!index_concat_args_ok (plan, d_a_ptr, n_keywords_a, d_b_ptr, n_keywords_b, d_out_ptr, d_out_text, d_out_count, out_capacity, d_out_nnz) || !d_tmp ||
+      tmp_bytes < acm_gpu_index_concat_tmp_bytes (plan, n_keywords_b))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  Carve carve (d_tmp);
+  IndexCatK C{};
+  C.ctl = carve.take<RulesCtl> (1);
+  C.a_ptr = reinterpret_cast<const unsigned long long *> (d_a_ptr);
+  C.b_ptr = reinterpret_cast<const unsigned long long *> (d_b_ptr);
+  C.a_count = reinterpret_cast<const unsigned long long *> (d_a_count);
+  C.b_count = reinterpret_cast<const unsigned long long *> (d_b_count);
+  C.a_text = d_a_text;
+  C.b_text = d_b_text;
+  C.n_a = n_keywords_a;
+  C.n_b = n_keywords_b;
+  C.out_capacity = out_capacity;
+  C.d_out_ptr = reinterpret_cast<unsigned long long *> (d_out_ptr);
+  C.d_out_nnz = reinterpret_cast<unsigned long long *> (d_out_nnz);
+  C.d_out_count = reinterpret_cast<unsigned long long *> (d_out_count);
+  C.d_out_text = d_out_text;
+  C.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (C.ctl, 0, sizeof (RulesCtl), st));
+  const dim3 keyword_grid = capped_grid (plan, (n_keywords_b + 1 + 255) / 256);
+  /* the count pass: the pointer arrays, then (an address is formed from them only now) the boundaries, then out_ptr */
+  HIP_TRY (launch (index_concat_check_kernel<false>, keyword_grid, dim3 (256), 0, st, C));
+  HIP_TRY (launch (index_concat_check_kernel<true>, keyword_grid, dim3 (256), 0, st, C));
+  HIP_TRY (launch (index_concat_finish_kernel, keyword_grid, dim3 (256), 0, st, C));
+  /* the fill pass, by the room */
+  if (d_out_text)
+    HIP_TRY (launch (index_concat_fill_kernel, capped_grid (plan, (out_capacity + 255) / 256), dim3 (256), 0, st, C));
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_index_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts,
+                         uint64_t n_keywords, uint64_t post_capacity) {
+  if (n_keywords >= (1ull << 32) || post_capacity >= (1ull << 31) ||
+      !acm_gpu_tally_batch_tmp_bytes (plan, window_symbols, capacity, pair_capacity, n_symbols, n_texts))
+    return 0;
+  Carve c;
+  rules_call_carve (c, plan, index_bytes (n_texts, n_keywords, post_capacity), capacity, pair_capacity, n_symbols, n_texts);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_index_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint64_t window_symbols,
+                      uint64_t capacity, uint64_t pair_capacity, uint64_t n_keywords, uint64_t text_base, uint64_t *d_post_ptr, uint32_t *d_post_text,
+                      uint64_t *d_post_count, uint64_t post_capacity, uint64_t *d_nnz, uint64_t *d_forms, uint64_t *d_total, uint64_t *d_need,
+                      uint64_t *d_need_pairs, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!index_args_ok (plan, n_texts, n_keywords, text_base, d_post_ptr, d_post_text, d_post_count, post_capacity, d_nnz) || !d_tmp || capacity == 0 ||
+      capacity >= (1ull << 31) || pair_capacity == 0 || pair_capacity >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  Carve carve (d_tmp);
+  const RulesCallRoom L = rules_call_carve (carve, plan, index_bytes (n_texts, n_keywords, post_capacity), capacity, pair_capacity, n_symbols, n_texts);
+  if (tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (const int rc = tally_then_evaluate (plan, d_text, n_symbols, d_offsets, n_texts, window_symbols, capacity, pair_capacity, L, d_post_ptr, d_nnz, d_total,
+                                          d_need, d_need_pairs, stream, [&] {
+                                            return index_transpose (plan, L.row_ptr, L.col, L.val, n_texts, n_keywords, text_base, d_post_ptr, d_post_text,
+                                                                    d_post_count, post_capacity, d_nnz, d_forms, d_tmp, st, L.tb, capacity, pair_capacity);
+                                          }))
+    return rc;
+  return n_texts == 0 ? index_empty (n_keywords, d_post_ptr, d_nnz, d_forms, st) : ACM_GPU_OK;
+}
+
+extern "C" int
+acm_gpu_index_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint64_t text_base, uint64_t *post_ptr, uint64_t n_keywords,
+                    uint32_t *post_text, uint64_t *post_count, uint64_t post_capacity, uint64_t *nnz, uint64_t *total) {
+  if (!plan || !post_ptr || !nnz || n_keywords < plan->covered_keywords || n_keywords >= (1ull << 32) || text_base > (1ull << 32) ||
+      text_base + n_texts > (1ull << 32) || post_capacity >= (1ull << 31) || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_symbols = offsets[n_texts];
+  const bool fills = post_text && post_count && post_capacity;
+  DeviceTemps temps;
+  void *d_text = nullptr;
+  uint64_t *d_off = nullptr, *d_post_ptr = nullptr, *d_post_count = nullptr, *d_res = nullptr; /* d_res: nnz, total, need, need_pairs */
+  uint32_t *d_post_text = nullptr;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  HOST_TRY (temps.get (&d_post_ptr, (n_keywords + 1) * 8));
+  HOST_TRY (temps.get (&d_res, 32));
+  if (fills) {
+    HOST_TRY (temps.get (&d_post_text, (size_t)post_capacity * 4));
+    HOST_TRY (temps.get (&d_post_count, (size_t)post_capacity * 8));
+  }
+  const uint64_t d_capacity = fills ? post_capacity : 0;
+  uint64_t res[4] = { 0, 0, 0, 0 };
+  if (const int rc = with_tally_rooms (
+        plan, temps, n_symbols, d_res, res,
+        [&] (uint64_t window, uint64_t capacity, uint64_t pairs) {
+          return acm_gpu_index_tmp_bytes (plan, window, capacity, pairs, n_symbols, n_texts, n_keywords, d_capacity);
+        },
+        [&] (uint64_t window, uint64_t capacity, uint64_t pairs, void *d_tmp, size_t tmp_bytes) {
+          return acm_gpu_index_device (plan, d_text, n_symbols, d_off, n_texts, window, capacity, pairs, n_keywords, text_base, d_post_ptr, d_post_text,
+                                       d_post_count, d_capacity, d_res, nullptr, d_res + 1, d_res + 2, d_res + 3, d_tmp, tmp_bytes, nullptr);
+        }))
+    return rc;
+  HOST_TRY (hipMemcpy (post_ptr, d_post_ptr, (n_keywords + 1) * 8, hipMemcpyDeviceToHost));
+  *nnz = res[0];
+  if (total)
+    *total = res[1];
+  if (!post_text || !post_count) /* the call only counts */
+    return ACM_GPU_OK;
+  if (res[0] > post_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (res[0]) {
+    HOST_TRY (hipMemcpy (post_text, d_post_text, res[0] * 4, hipMemcpyDeviceToHost));
+    HOST_TRY (hipMemcpy (post_count, d_post_count, res[0] * 8, hipMemcpyDeviceToHost));
+  }
+  return ACM_GPU_OK;
+}
+
 /* ------------------------------------------------------------------ leftmost-longest selection (include/acm_gpu.h, dev_select.h)
  * The passes over a record set in canonical order; acm_gpu_scan_select_device runs them behind the
  * ordered scan. */
@@ -8731,7 +9065,7 @@ namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally and acm_lookup only a scan that
  * succeeded, acm_select, acm_scan_words, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
- * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_score, acm_scan_patterns, acm_scan_chains, acm_scan_approx and
+ * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_score, acm_index, acm_scan_patterns, acm_scan_chains, acm_scan_approx and
  * acm_scan_edit also one whose output had no room, acm_context either of the two. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
 
@@ -8758,7 +9092,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The twenty calls below run on the same route, the same cached plan, under the same lock. */
+/* The twenty-one calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -8989,6 +9323,42 @@ acm_score (ACMachine *machine, const void *text, const uint64_t *offsets, uint64
     [&] (ACMPlan *plan) {
       return acm_gpu_score_host (plan, text, offsets, n_texts, terms, class_ptr, bias, threshold, n_classes, kept_ptr, kept_class, kept_score,
                                  kept_capacity, n_kept, best, k, class_hits, top_n, top_text, top_score, total);
+    });
+}
+
+/* the inverted index of a batch (include/acm_index.h) */
+extern "C" int
+acm_index (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, uint64_t text_base, uint64_t *post_ptr, uint64_t n_keywords,
+           uint32_t *post_text, uint64_t *post_count, uint64_t post_capacity, uint64_t *nnz, uint64_t *total) {
+  if (!machine || !post_ptr || !nnz || n_keywords >= (1ull << 32) || text_base > (1ull << 32) || text_base + n_texts > (1ull << 32) ||
+      post_capacity >= (1ull << 31) || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      if (n_keywords < acm_nb_keywords (machine))
+        return (int)ACM_GPU_E_ARG;
+      /* tally_batch's host loop into a room of the call's own, grown once to what the matrix needs */
+      std::vector<uint64_t> row_ptr (n_texts + 1), val;
+      std::vector<uint32_t> col;
+      uint64_t room = 1024, found = 0;
+      int rc = ACM_GPU_OK;
+      for (int attempt = 0; attempt < 2; attempt++) {
+        col.resize (room);
+        val.resize (room);
+        rc = acm_internal_cpu_tally_batch (machine, text, offsets, n_texts, said, row_ptr.data (), col.data (), val.data (), room, &found, total);
+        if (rc != ACM_GPU_E_OVERFLOW)
+          break;
+        room = found;
+      }
+      if (rc == ACM_GPU_E_OVERFLOW) /* (the second room is what the first attempt asked for: never expected) */
+        rc = ACM_GPU_E_INTERNAL;
+      return rc ? rc
+                : acm_index_matrix (row_ptr.data (), col.data (), val.data (), n_texts, n_keywords, text_base, post_ptr, post_text, post_count,
+                                    post_capacity, nnz);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_index_host (plan, text, offsets, n_texts, text_base, post_ptr, n_keywords, post_text, post_count, post_capacity, nnz, total);
     });
 }
 

@@ -1253,6 +1253,89 @@ acm_score_top (const uint64_t *kept_ptr, const uint32_t *kept_class, const int64
   return ACM_GPU_OK;
 }
 
+/* The inverted index of a count matrix in CSR form (include/acm_index.h): the plain sequential
+ * transposition.  The lists' lengths are counted into post_ptr[] and summed; the fill walks the rows
+ * in order, so every list ascends by text id, with post_ptr[k] as list k's cursor, and moves the
+ * pointers back by one place behind it. */
+int
+acm_index_matrix (const uint64_t *row_ptr, const uint32_t *col, const uint64_t *val, uint64_t n_texts, uint64_t n_keywords, uint64_t text_base,
+                  uint64_t *post_ptr, uint32_t *post_text, uint64_t *post_count, uint64_t post_capacity, uint64_t *nnz) {
+  if (!row_ptr || row_ptr[0] != 0 || !post_ptr || !nnz || n_texts >= (1ull << 31) || n_keywords >= (1ull << 32) || text_base > (1ull << 32) ||
+      text_base + n_texts > (1ull << 32) || post_capacity >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (row_ptr[t] > row_ptr[t + 1])
+      return ACM_GPU_E_ARG;
+  const uint64_t all = row_ptr[n_texts];
+  if (all && (!col || !val))
+    return ACM_GPU_E_ARG;
+  for (uint64_t e = 0; e < all; e++)
+    if (col[e] >= n_keywords)
+      return ACM_GPU_E_ARG;
+  for (uint64_t k = 0; k <= n_keywords; k++)
+    post_ptr[k] = 0;
+  for (uint64_t e = 0; e < all; e++)
+    post_ptr[col[e] + 1]++;
+  for (uint64_t k = 0; k < n_keywords; k++)
+    post_ptr[k + 1] += post_ptr[k];
+  *nnz = all;
+  if (!post_text || !post_count) /* the call only counts */
+    return ACM_GPU_OK;
+  if (all > post_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  for (uint64_t t = 0; t < n_texts; t++)
+    for (uint64_t e = row_ptr[t]; e < row_ptr[t + 1]; e++) {
+      const uint64_t at = post_ptr[col[e]]++;
+      post_text[at] = (uint32_t)(text_base + t);
+      post_count[at] = val[e];
+    }
+  for (uint64_t k = n_keywords; k > 0; k--) /* (post_ptr[k] has moved on to the end of k's list) */
+    post_ptr[k] = post_ptr[k - 1];
+  post_ptr[0] = 0;
+  return ACM_GPU_OK;
+}
+
+/* CONCAT of two indexes (include/acm_index.h): per keyword A's list, then B's */
+int
+acm_index_concat (const uint64_t *a_ptr, const uint32_t *a_text, const uint64_t *a_count, uint64_t n_keywords_a, const uint64_t *b_ptr,
+                  const uint32_t *b_text, const uint64_t *b_count, uint64_t n_keywords_b, uint64_t *out_ptr, uint32_t *out_text, uint64_t *out_count,
+                  uint64_t out_capacity, uint64_t *out_nnz) {
+  if (!a_ptr || a_ptr[0] != 0 || !b_ptr || b_ptr[0] != 0 || !out_ptr || !out_nnz || n_keywords_a > n_keywords_b || n_keywords_b >= (1ull << 32) ||
+      out_capacity >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  for (uint64_t k = 0; k < n_keywords_a; k++)
+    if (a_ptr[k] > a_ptr[k + 1])
+      return ACM_GPU_E_ARG;
+  for (uint64_t k = 0; k < n_keywords_b; k++)
+    if (b_ptr[k] > b_ptr[k + 1])
+      return ACM_GPU_E_ARG;
+  if ((a_ptr[n_keywords_a] && (!a_text || !a_count)) || (b_ptr[n_keywords_b] && (!b_text || !b_count)))
+    return ACM_GPU_E_ARG;
+  for (uint64_t k = 0; k < n_keywords_a; k++)
+    if (a_ptr[k] < a_ptr[k + 1] && b_ptr[k] < b_ptr[k + 1] && b_text[b_ptr[k]] <= a_text[a_ptr[k + 1] - 1])
+      return ACM_GPU_E_ARG;
+  for (uint64_t k = 0; k <= n_keywords_b; k++)
+    out_ptr[k] = a_ptr[k < n_keywords_a ? k : n_keywords_a] + b_ptr[k];
+  const uint64_t all = out_ptr[n_keywords_b];
+  *out_nnz = all;
+  if (!out_text || !out_count) /* the call only counts */
+    return ACM_GPU_OK;
+  if (all > out_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  for (uint64_t k = 0; k < n_keywords_b; k++) {
+    uint64_t at = out_ptr[k];
+    for (uint64_t e = k < n_keywords_a ? a_ptr[k] : 0, end = k < n_keywords_a ? a_ptr[k + 1] : 0; e < end; e++, at++) {
+      out_text[at] = a_text[e];
+      out_count[at] = a_count[e];
+    }
+    for (uint64_t e = b_ptr[k]; e < b_ptr[k + 1]; e++, at++) {
+      out_text[at] = b_text[e];
+      out_count[at] = b_count[e];
+    }
+  }
+  return ACM_GPU_OK;
+}
+
 /* SELECT of records in canonical order (include/acm_gpu.h), in place in the front of the array: the
  * plain sequential greedy pass.  The order is by end and the rule goes by start, so a round looks
  * at a window: from the first record that ends at or behind p up to the first that ends lmax or

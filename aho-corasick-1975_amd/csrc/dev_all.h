@@ -192,5 +192,6 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_chains.h"
 #include "dev_segment.h"
 #include "dev_score.h"
+#include "dev_index.h"
 
 } // namespace

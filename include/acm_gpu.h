@@ -2301,4 +2301,5 @@ int acm_gpu_synth_text (int device, void *d_text, uint64_t n, uint64_t global_be
 #endif
 #endif
 #include "acm_score.h"
+#include "acm_index.h"
 #include "acm_segment.h"
