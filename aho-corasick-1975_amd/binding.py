@@ -1,4 +1,5 @@
 """ctypes bindings of libac75_amd.so (include/acm.h + include/acm_gpu.h)."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -210,6 +211,7 @@ def lib():
     L.acm_gpu_strerror.restype = C.c_char_p
     L.acm_gpu_strerror.argtypes = [i32]
     L.acm_gpu_device_count.restype = i32
+    L.acm_gpu_device_count.argtypes = []
     L.acm_get_keyword.restype = i32
     L.acm_get_keyword.argtypes = [vp, u32, C.POINTER(MatchHolder)]
     L.acm_flatten.restype = i32
@@ -658,6 +660,115 @@ def _check(rc, what):
 _SYM_DTYPE = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
 
 
+def _ptr(a):
+    """the address of a numpy array, None for an empty one"""
+    return a.ctypes.data if a.size else None
+
+
+def _opt(x):
+    """the address of an optional numpy array or device tensor: None stays None"""
+    if x is None:
+        return None
+    return x.data_ptr() if hasattr(x, "data_ptr") else x.ctypes.data
+
+
+def _opt_full(x):
+    """the address of an optional device tensor that holds something: None for None and for an empty one"""
+    return x.data_ptr() if x is not None and x.numel() else None
+
+
+def _cut(offsets):
+    """(address, n_texts) of the optional offsets of a batch -- a numpy array or a device tensor of n_texts + 1
+    entries --, (None, 0) for a buffer that is one text"""
+    return (_opt(offsets), offsets.shape[0] - 1) if offsets is not None else (None, 0)
+
+
+def _room_call(call, what, cap, fixed=False, repeats=1):
+    """The room loop of the host calls: call(cap) -> (rc, need, out) runs the C call with room for `cap`
+    entries; on ACM_GPU_E_OVERFLOW it is repeated with `need`, the size the call reported -- `repeats` times
+    at the most (None: until it fits), and never when the caller `fixed` the capacity.  Returns (out, need,
+    cap) of the call that had room; any other outcome raises ACMError(rc, what)."""
+    attempt = 0
+    while True:
+        rc, need, out = call(cap)
+        if rc == ACM_GPU_E_OVERFLOW and not fixed and (repeats is None or attempt < repeats):
+            cap, attempt = int(need), attempt + 1
+            continue
+        _check(rc, what)
+        return out, int(need), cap
+
+
+def _records_host_call(fn, what, before, cap, fixed, repeats=1):
+    """fn(*before, out, cap, n) in the room loop, for the host calls that fill `cap` records and nothing else:
+    the records"""
+    def call(cap):
+        out = np.zeros(cap, dtype=RECORD_DTYPE)
+        n = C.c_uint64(0)
+        return fn(*before, out.ctypes.data, cap, C.byref(n)), n.value, out
+    out, n, _ = _room_call(call, what, cap, fixed, repeats)
+    return out[:n]
+
+
+def _matches_host_call(fn, what, before, out_capacity, extra=()):
+    """fn(*before, out, one array per dtype of `extra`, cap, n) in the room loop, for the host calls of the
+    pattern, chain, approx, edit and template families: room for 1024 matches unless out_capacity says
+    otherwise, no address for no room.  Returns (matches, the extra arrays...), cut to size."""
+    def call(cap):
+        out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
+        more = [np.zeros(max(cap, 1), dtype=d) for d in extra]
+        n = C.c_uint64(0)
+        rc = fn(*before, out.ctypes.data if cap else None, *[m.ctypes.data for m in more], cap, C.byref(n))
+        return rc, n.value, (out, *more)
+    arrays, n, _ = _room_call(call, what, int(out_capacity) if out_capacity is not None else 1024, out_capacity is not None)
+    return tuple(a[:n] for a in arrays)
+
+
+def _counted(call, capacity, count):
+    """call(capacity) when a capacity is given; None: call(0), which only counts, then call again sized by the
+    count -- the attribute `count` of what call returns"""
+    got = call(int(capacity) if capacity is not None else 0)
+    if capacity is None and getattr(got, count):
+        got = call(getattr(got, count))
+    return got
+
+
+def _device_room_call(run, what, cap):
+    """run(cap) -> (count, out) for a device call whose count is read back: repeated once, sized by the count,
+    when that is above cap.  Returns (count, out); ACMError (ACM_GPU_E_OVERFLOW) when it still has no room."""
+    n, out = run(cap)
+    if n > cap:
+        cap = n
+        n, out = run(cap)
+        if n > cap:
+            raise ACMError(ACM_GPU_E_OVERFLOW, "%s: %d records" % (what, n))
+    return n, out
+
+
+def _scratch(tb, dev, tmp=None):
+    """a uint8 scratch tensor of tb bytes or more on `dev` (16 at the least: the calls want an address): the
+    caller's `tmp` when that is large enough"""
+    import torch
+    if tmp is None or tmp.numel() < tb:
+        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+    return tmp
+
+
+def _i64(n, dev):
+    """a zeroed int64 tensor of n entries on `dev`: the numbers a device call leaves for the host"""
+    import torch
+    return torch.zeros(n, dtype=torch.int64, device=dev)
+
+
+class _Owner:
+    """An object over a native handle: whatever its close() releases goes with the object."""
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def select_records(array):
     """acm_select_records(): the leftmost-longest non-overlapping records of `array` (RECORD_DTYPE, in
     canonical order), by the sequential pass on the host.  Returns a new array; `array` is not changed."""
@@ -726,9 +837,8 @@ def replace_records(text, records, replacements=None, fill=None, pos_base=0, sym
     need = C.c_uint64(0)
 
     def call(out, cap):
-        return lib().acm_replace_records(t.ctypes.data if t.size else None, n_sym, sb, pos_base, rec.ctypes.data if rec.size else None, rec.size,
-                                         data.ctypes.data, off.ctypes.data if off is not None else None, nk,
-                                         out.ctypes.data if out is not None else None, cap, C.byref(need))
+        return lib().acm_replace_records(_ptr(t), n_sym, sb, pos_base, _ptr(rec), rec.size, data.ctypes.data, _opt(off), nk, _opt(out), cap,
+                                         C.byref(need))
     if out_capacity is None:
         rc = call(None, 0)
         if rc not in (ACM_GPU_OK, ACM_GPU_E_OVERFLOW):
@@ -825,11 +935,8 @@ def tokens_records(text, records, offsets=None, mode="run", gap_base=0, tok_of=N
 
     def call(ids, start, length, cap, need, first, m):
         m.value = rec.size
-        return lib().acm_tokens_records(t.ctypes.data if t.size else None, n_sym, sb, pos_base, rec.ctypes.data if rec.size else None, rec.size,
-                                        off.ctypes.data if off is not None else None, n_texts, table.ctypes.data if table is not None else None, nk,
-                                        int(gap_base), md, ids.ctypes.data if ids is not None else None,
-                                        start.ctypes.data if start is not None else None, length.ctypes.data if length is not None else None, cap,
-                                        C.byref(need), first.ctypes.data if first is not None else None)
+        return lib().acm_tokens_records(_ptr(t), n_sym, sb, pos_base, _ptr(rec), rec.size, _opt(off), n_texts, _opt(table), nk, int(gap_base), md,
+                                        _opt(ids), _opt(start), _opt(length), cap, C.byref(need), _opt(first))
     return _tokens_host_call(call, "acm_tokens_records", n_texts, off is not None, token_capacity)
 
 
@@ -857,19 +964,16 @@ def _grep_host_call(fn, what, handle, t, sym_size, off, invert, gather, out_capa
     hits = np.zeros(n_texts, np.uint64)
     kept = np.zeros(n_texts, np.uint32)
     out_off = np.zeros(n_texts + 1, np.uint64)
-    cap = int(out_capacity) if out_capacity is not None else n_sym
-    for attempt in (0, 1):
+    def call(cap):
         out = np.zeros(max(cap * sym_size // t.itemsize, 1), dtype=t.dtype) if gather else None
         nk, total, need = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        rc = fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, ACM_GREP_INVERT if invert else ACM_GREP_MATCHING,
-                hits.ctypes.data, kept.ctypes.data, C.byref(nk), C.byref(total), out.ctypes.data if gather else None, cap if gather else 0,
+        rc = fn(handle, _ptr(t), off.ctypes.data, n_texts, ACM_GREP_INVERT if invert else ACM_GREP_MATCHING,
+                hits.ctypes.data, kept.ctypes.data, C.byref(nk), C.byref(total), _opt(out), cap if gather else 0,
                 out_off.ctypes.data, C.byref(need))
-        if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
-            cap = int(need.value)
-            continue
-        _check(rc, what)
-        k, sym = int(nk.value), int(need.value)
-        return Grepped(hits, kept[:k], k, int(total.value), None, out[:sym * sym_size // t.itemsize] if gather else None, out_off[:k + 1], sym, cap)
+        return rc, need.value, (out, nk, total)
+    (out, nk, total), sym, cap = _room_call(call, what, int(out_capacity) if out_capacity is not None else n_sym, out_capacity is not None)
+    k = int(nk.value)
+    return Grepped(hits, kept[:k], k, int(total.value), None, out[:sym * sym_size // t.itemsize] if gather else None, out_off[:k + 1], sym, cap)
 
 
 def grep_gather(text, offsets, hits, invert=False, sym_size=None, gather=True, out_capacity=None):
@@ -890,9 +994,8 @@ def grep_gather(text, offsets, hits, invert=False, sym_size=None, gather=True, o
     flags = ACM_GREP_INVERT if invert else ACM_GREP_MATCHING
 
     def call(out, cap):
-        return lib().acm_grep_gather(t.ctypes.data if t.size else None, sb, off.ctypes.data, n_texts, h.ctypes.data if h.size else None, flags,
-                                     kept.ctypes.data, C.byref(nk), out.ctypes.data if out is not None else None, cap, out_off.ctypes.data,
-                                     C.byref(sym))
+        return lib().acm_grep_gather(_ptr(t), sb, off.ctypes.data, n_texts, _ptr(h), flags, kept.ctypes.data, C.byref(nk), _opt(out), cap,
+                                     out_off.ctypes.data, C.byref(sym))
     out = None
     if gather:
         if out_capacity is None:
@@ -935,18 +1038,13 @@ def _tally_batch_host_call(fn, what, handle, t, sym_size, off):
     n_sym = int(off[-1])
     assert t.size * t.itemsize == n_sym * sym_size, "the last offset is the number of symbols"
     row_ptr = np.zeros(n_texts + 1, np.uint64)
-    cap = max(1024, n_sym // 16)
-    for attempt in (0, 1):
+    def call(cap):
         col, val = np.zeros(cap, np.uint32), np.zeros(cap, np.uint64)
         nnz, total = C.c_uint64(0), C.c_uint64(0)
-        rc = fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data, cap,
-                C.byref(nnz), C.byref(total))
-        if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
-            cap = int(nnz.value)
-            continue
-        _check(rc, what)
-        k = int(nnz.value)
-        return TalliedBatch(row_ptr, col[:k], val[:k], k, int(total.value))
+        rc = fn(handle, _ptr(t), off.ctypes.data, n_texts, row_ptr.ctypes.data, col.ctypes.data, val.ctypes.data, cap, C.byref(nnz), C.byref(total))
+        return rc, nnz.value, (col, val, total)
+    (col, val, total), k, _ = _room_call(call, what, max(1024, n_sym // 16))
+    return TalliedBatch(row_ptr, col[:k], val[:k], k, int(total.value))
 
 
 def tally_batch_records(records, first, n_keywords):
@@ -1057,17 +1155,12 @@ def _fired_host_call(call, what, n_texts, total=None):
     acm_rules: a Fired of numpy arrays out.  An output overflow is repeated once with the size the
     call reports."""
     fired_ptr = np.zeros(n_texts + 1, np.uint64)
-    cap = max(1024, n_texts)
-    for attempt in (0, 1):
+    def room(cap):
         fired = np.zeros(cap, np.uint32)
         n = C.c_uint64(0)
-        rc = call(fired_ptr.ctypes.data, fired.ctypes.data, cap, C.byref(n))
-        if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
-            cap = int(n.value)
-            continue
-        _check(rc, what)
-        k = int(n.value)
-        return Fired(fired_ptr, fired[:k], k, int(total.value) if total is not None else None, fired_capacity=cap)
+        return call(fired_ptr.ctypes.data, fired.ctypes.data, cap, C.byref(n)), n.value, fired
+    fired, k, cap = _room_call(room, what, max(1024, n_texts))
+    return Fired(fired_ptr, fired[:k], k, int(total.value) if total is not None else None, fired_capacity=cap)
 
 
 def rules_matrix(tallied, ruleset, n_keywords):
@@ -1144,17 +1237,12 @@ def _indexed_host_call(call, what, n_keywords, text_base=0, total=None):
     """call(post_ptr, post_text, post_count, capacity, nnz) -> rc, for the host calls: an Indexed of numpy arrays
     out.  An output overflow is repeated once with the size the call reports."""
     post_ptr = np.zeros(int(n_keywords) + 1, np.uint64)
-    cap = 1024
-    for attempt in (0, 1):
+    def room(cap):
         post_text, post_count = np.zeros(cap, np.uint32), np.zeros(cap, np.uint64)
         n = C.c_uint64(0)
-        rc = call(post_ptr.ctypes.data, post_text.ctypes.data, post_count.ctypes.data, cap, C.byref(n))
-        if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
-            cap = int(n.value)
-            continue
-        _check(rc, what)
-        m = int(n.value)
-        return Indexed(post_ptr, post_text[:m], post_count[:m], m, int(total.value) if total is not None else None, int(text_base), post_capacity=cap)
+        return call(post_ptr.ctypes.data, post_text.ctypes.data, post_count.ctypes.data, cap, C.byref(n)), n.value, (post_text, post_count)
+    (post_text, post_count), m, cap = _room_call(room, what, 1024)
+    return Indexed(post_ptr, post_text[:m], post_count[:m], m, int(total.value) if total is not None else None, int(text_base), post_capacity=cap)
 
 
 def index_matrix(tallied, n_keywords, text_base=0):
@@ -1279,29 +1367,21 @@ def _top_host_arrays(n_classes, k):
     return (np.zeros(n_classes, np.uint64), np.zeros(n_classes, np.uint32), np.zeros((n_classes, k), np.uint32), np.zeros((n_classes, k), np.int64))
 
 
-def _ptr(a):
-    return a.ctypes.data if a.size else None
-
-
 def _scored_host_call(call, what, n_texts, n_classes, k, total=None):
     """call(kept_ptr, kept_class, kept_score, capacity, n_kept, best, top arrays...) -> rc, for acm_score_matrix /
     acm_gpu_score_host / acm_score: a Scored of numpy arrays out.  An output overflow is repeated once with the size
     the call reports."""
     kept_ptr, best = np.zeros(n_texts + 1, np.uint64), np.full(n_texts, ACM_SCORE_NONE, np.uint32)
     hits, top_n, top_text, top_score = _top_host_arrays(n_classes, k)
-    cap = max(1024, n_texts)
-    for attempt in (0, 1):
+    def room(cap):
         kept_class, kept_score = np.zeros(cap, np.uint32), np.zeros(cap, np.int64)
         n = C.c_uint64(0)
         rc = call(kept_ptr.ctypes.data, kept_class.ctypes.data, kept_score.ctypes.data, cap, C.byref(n), _ptr(best), _ptr(hits), _ptr(top_n),
                   _ptr(top_text), _ptr(top_score))
-        if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
-            cap = int(n.value)
-            continue
-        _check(rc, what)
-        m = int(n.value)
-        top = (hits, top_n, top_text, top_score) if k else (None, None, None, None)
-        return Scored(kept_ptr, kept_class[:m], kept_score[:m], m, best, *top, total=int(total.value) if total is not None else None, kept_capacity=cap)
+        return rc, n.value, (kept_class, kept_score)
+    (kept_class, kept_score), m, cap = _room_call(room, what, max(1024, n_texts))
+    top = (hits, top_n, top_text, top_score) if k else (None, None, None, None)
+    return Scored(kept_ptr, kept_class[:m], kept_score[:m], m, best, *top, total=int(total.value) if total is not None else None, kept_capacity=cap)
 
 
 def score_matrix(tallied, model, n_keywords):
@@ -1426,21 +1506,25 @@ def patterns_records(records, patternset, n_symbols, offsets=None, pos_base=0, n
     match, by end_pos ascending, length descending, pattern id ascending.  `offsets` (n_texts + 1 entries)
     cuts the buffer into texts; a match lies inside one text.  out_capacity None: counted first, then sized
     by the count; given and too small: ACMError (ACM_GPU_E_OVERFLOW)."""
-    ps = _patternset(patternset)
+    return _terms_records("acm_patterns_records", records, _patternset(patternset), n_symbols, offsets, pos_base, n_keywords, out_capacity)
+
+
+def _terms_records(name, records, tset, n_symbols, offsets, pos_base, n_keywords, out_capacity):
+    """what patterns_records() and chains_records() share: the C call `name` on numpy arrays, counted first when
+    no capacity is given"""
+    fn = getattr(lib(), name)
     a = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
     off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-    nk = int(n_keywords) if n_keywords is not None else ps.n_keywords
+    nk = int(n_keywords) if n_keywords is not None else tset.n_keywords
     n = C.c_uint64(0)
 
     def call(out, cap):
-        return lib().acm_patterns_records(a.ctypes.data if a.size else None, a.size, int(n_symbols), int(pos_base),
-                                          off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *ps.args(), nk,
-                                          out.ctypes.data if out is not None else None, cap, C.byref(n))
+        return fn(_ptr(a), a.size, int(n_symbols), int(pos_base), *_cut(off), *tset.args(), nk, _opt(out), cap, C.byref(n))
     if out_capacity is None:                                       # (no output: the call only counts)
-        _check(call(None, 0), "acm_patterns_records")
+        _check(call(None, 0), name)
         out_capacity = int(n.value)
     out = np.zeros(max(int(out_capacity), 1), dtype=RECORD_DTYPE)
-    _check(call(out, int(out_capacity)), "acm_patterns_records")
+    _check(call(out, int(out_capacity)), name)
     return out[:n.value]
 
 
@@ -1520,22 +1604,7 @@ def chains_records(records, chainset, n_symbols, offsets=None, pos_base=0, n_key
     that ends there, the chain's id), by end_pos ascending, length descending, chain id ascending.  `offsets`
     (n_texts + 1 entries) cuts the buffer into texts; a match lies inside one text.  out_capacity None:
     counted first, then sized by the count; given and too small: ACMError (ACM_GPU_E_OVERFLOW)."""
-    cs = _chainset(chainset)
-    a = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
-    off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-    nk = int(n_keywords) if n_keywords is not None else cs.n_keywords
-    n = C.c_uint64(0)
-
-    def call(out, cap):
-        return lib().acm_chains_records(a.ctypes.data if a.size else None, a.size, int(n_symbols), int(pos_base),
-                                        off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *cs.args(), nk,
-                                        out.ctypes.data if out is not None else None, cap, C.byref(n))
-    if out_capacity is None:                                       # (no output: the call only counts)
-        _check(call(None, 0), "acm_chains_records")
-        out_capacity = int(n.value)
-    out = np.zeros(max(int(out_capacity), 1), dtype=RECORD_DTYPE)
-    _check(call(out, int(out_capacity)), "acm_chains_records")
-    return out[:n.value]
+    return _terms_records("acm_chains_records", records, _chainset(chainset), n_symbols, offsets, pos_base, n_keywords, out_capacity)
 
 
 class _PieceKeywords:
@@ -1663,9 +1732,7 @@ def _set_records(name, records, aset, text, offsets, pos_base, n_keywords, out_c
     n = C.c_uint64(0)
 
     def call(out, dist, cap):
-        return fn(a.ctypes.data if a.size else None, a.size, t.ctypes.data if t.size else None, aset.sym_size, n_symbols,
-                  int(pos_base), off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0,
-                  *aset.args(), nk, out.ctypes.data if out is not None else None, dist.ctypes.data if dist is not None else None, cap, C.byref(n))
+        return fn(_ptr(a), a.size, _ptr(t), aset.sym_size, n_symbols, int(pos_base), *_cut(off), *aset.args(), nk, _opt(out), _opt(dist), cap, C.byref(n))
     if out_capacity is None:                                       # (no output: the call only counts)
         _check(call(None, None, 0), name)
         out_capacity = int(n.value)
@@ -1981,9 +2048,8 @@ def words_records(text, records, offsets=None, ranges=ASCII_WORD, flags="both", 
     a = np.array(records, dtype=RECORD_DTYPE, copy=True).reshape(-1)
     off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
     n = C.c_uint64(0)
-    _check(lib().acm_words_records(t.ctypes.data if t.size else None, t.size * t.itemsize // sb, sb, int(pos_base),
-                                   off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, r.ctypes.data, nr,
-                                   _word_flags(flags), a.ctypes.data if a.size else None, a.size, C.byref(n)), "acm_words_records")
+    _check(lib().acm_words_records(_ptr(t), t.size * t.itemsize // sb, sb, int(pos_base), *_cut(off), r.ctypes.data, nr, _word_flags(flags), _ptr(a),
+                                   a.size, C.byref(n)), "acm_words_records")
     return a[:n.value]
 
 
@@ -2065,9 +2131,8 @@ def context_records(text, records, offsets=None, before=0, after=0, unit="symbol
     flags = _context_flags(unit, merge)
 
     def call(room, *outputs):
-        return lib().acm_context_records(t.ctypes.data if t.size else None, t.size * t.itemsize // sb, sb, int(pos_base),
-                                         off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0,
-                                         a.ctypes.data if a.size else None, a.size, int(before), int(after), flags, *outputs), a, a.size
+        return lib().acm_context_records(_ptr(t), t.size * t.itemsize // sb, sb, int(pos_base), *_cut(off), _ptr(a), a.size, int(before), int(after),
+                                         flags, *outputs), a, a.size
     return _context_host_call(call, "acm_context_records", t, sb, a.size, False, gather, out_capacity)
 
 
@@ -2108,19 +2173,63 @@ def _anchored_host_call(fn, what, handle, t, off, mode, capacity):
     """the host-memory anchored calls (plan or machine): (records, text_id, first); an overflow is
     repeated once with the size the call reports unless `capacity` was given"""
     n_texts = off.size - 1
-    cap = int(capacity) if capacity is not None else max(n_texts, 1)
-    for attempt in (0, 1):
+    return _batch_records_host_call(fn, what, (handle, _ptr(t), off.ctypes.data, n_texts, _anchored_mode(mode)), n_texts,
+                                    int(capacity) if capacity is not None else max(n_texts, 1), capacity is not None)
+
+
+def _batch_records_host_call(fn, what, before, n_texts, cap, fixed=False):
+    """fn(*before, out, text_id, first, cap, n) in the room loop, for the host calls that give the records of a
+    batch: (records, text_id, first)"""
+    def call(cap):
         out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
         tid = np.zeros(max(cap, 1), dtype=np.uint32)
         first = np.zeros(n_texts + 1, dtype=np.uint64)
         n = C.c_uint64(0)
-        rc = fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, _anchored_mode(mode), out.ctypes.data, tid.ctypes.data,
-                first.ctypes.data, cap, C.byref(n))
-        if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
-            cap = int(n.value)
-            continue
-        _check(rc, what)
-        return out[:n.value], tid[:n.value], first
+        return fn(*before, out.ctypes.data, tid.ctypes.data, first.ctypes.data, cap, C.byref(n)), n.value, (out, tid, first)
+    (out, tid, first), n, _ = _room_call(call, what, cap, fixed)
+    return out[:n], tid[:n], first
+
+
+def _segment_host_call(fn, what, before, cost, gap_cost, cap, fixed):
+    """acm_segment / acm_gpu_scan_segment_host: fn(*before, the cost table, gap_cost, out, cap, n, sums) in the room
+    loop; (records, sums)"""
+    c, cp = _costs(cost)
+
+    def call(cap):
+        out = np.zeros(cap, dtype=RECORD_DTYPE)
+        n = C.c_uint64(0)
+        sums = np.zeros(2, np.uint64)
+        return fn(*before, cp, c.size, int(gap_cost), out.ctypes.data, cap, C.byref(n), sums.ctypes.data), n.value, (out, sums)
+    (out, sums), n, _ = _room_call(call, what, cap, fixed)
+    return out[:n], (int(sums[0]), int(sums[1]))
+
+
+def _replace_host_call(fn, what, handle, t, sym_size, replacements, fill, out_capacity):
+    """acm_replace / acm_gpu_scan_replace_host: numpy in, (the new text, the number of matches replaced) out.  An
+    output overflow is repeated once with the size the call reports when out_capacity is None."""
+    n_sym = t.size * t.itemsize // sym_size
+    data, off, nk = replacement_table(replacements, sym_size, fill)
+
+    def call(cap):
+        out = np.zeros(max(cap * sym_size // t.itemsize, 1), dtype=t.dtype)
+        need, m = C.c_uint64(0), C.c_uint64(0)
+        rc = fn(handle, _ptr(t), n_sym, data.ctypes.data, _opt(off), nk, out.ctypes.data, cap, C.byref(need), C.byref(m))
+        return rc, need.value, (out, m)
+    (out, m), need, _ = _room_call(call, what, int(out_capacity) if out_capacity is not None else n_sym + 1024, out_capacity is not None)
+    return out[:need * sym_size // t.itemsize], int(m.value)
+
+
+def _tokenize_host_call(fn, what, handle, t, sym_size, off, mode, gap_base, tok_of, token_capacity):
+    """acm_tokenize / acm_gpu_scan_tokens_host: numpy in, a Tokens of numpy arrays out; `off` None: one text"""
+    n_sym = t.size * t.itemsize // sym_size
+    table, nk = _tok_of(tok_of)
+    md = _token_mode(mode)
+    off_ptr, n_texts = _cut(off)
+
+    def call(ids, start, length, cap, need, first, m):
+        return fn(handle, _ptr(t), n_sym, off_ptr, n_texts, _opt(table), nk, int(gap_base), md, _opt(ids), _opt(start), _opt(length), cap,
+                  C.byref(need), _opt(first), C.byref(m))
+    return _tokens_host_call(call, what, n_texts, off is not None, token_capacity)
 
 
 def _lookup_host_call(fn, what, handle, t, off):
@@ -2155,7 +2264,7 @@ def _grep_lines_host_call(fn, what, handle, t, sym_size, d, nd, runs, invert, ga
                    offsets=off, n_texts=n)
 
 
-class FlatTables:
+class FlatTables(_Owner):
     """Host snapshot of the machine's flattened goto/failure/output tables (acm_flatten)."""
 
     def __init__(self, handle):
@@ -2247,14 +2356,8 @@ class FlatTables:
             lib().acm_flat_release(self._h)
             self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
-
-class Machine:
+class Machine(_Owner):
     """An ACMachine over fixed-size symbols compared with ACM_CMP_DEFAULT (reference
     aho_corasick.h:35,45), i.e. what `acm_create (ACM_CMP_DEFAULT, &(size_t){ sym_size }, 0)` returns.
     With `cmp` (a C function pointer of type CMP_TYPE, e.g. ctypes.cast(lib.sym, c_void_p)) the
@@ -2279,16 +2382,15 @@ class Machine:
             self.L.acm_release(self.handle)
             self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _symbols(self, x):
         if isinstance(x, (bytes, bytearray)):
             x = np.frombuffer(bytes(x), dtype=np.uint8)
         return np.ascontiguousarray(x, dtype=_SYM_DTYPE[self.sym_size])
+
+    def _text(self, text):
+        """(the text as a contiguous array, its number of symbols) as the one-text calls take it"""
+        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        return t, t.size * t.itemsize // self.sym_size
 
     def _pack_texts(self, texts):
         """a list of texts (bytes or arrays of symbols) side by side in one array, and their n + 1 offsets"""
@@ -2405,17 +2507,9 @@ class Machine:
     def scan_host(self, text, capacity=None):
         """acm_scan(): host buffers in, canonical records out (GPU inside; the host loop for machines
         the GPU cannot take by their nature: scan_path says which)."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
-        cap = int(capacity) if capacity is not None else max(1024, t.size // 64)
-        while True:
-            out = np.zeros(cap, dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = self.L.acm_scan(self.handle, t.ctypes.data, t.size * t.itemsize // self.sym_size, out.ctypes.data, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_scan")
-            return out[:n.value]
+        t, n_sym = self._text(text)
+        return _records_host_call(self.L.acm_scan, "acm_scan", (self.handle, t.ctypes.data, n_sym),
+                                  int(capacity) if capacity is not None else max(1024, t.size // 64), capacity is not None, repeats=None)
 
     def root(self):
         """The cursor of a scan that has seen nothing yet (acm_initiate): what scan_from() and the
@@ -2426,51 +2520,39 @@ class Machine:
         """acm_scan_from(): scan_host() continued from `cursor` (root(), or what an earlier scan_from
         or acm_match left).  Returns (records, cursor afterwards): end_pos is the index in `text`, a
         keyword cut by the boundary between two texts is found.  `cursor` itself is not changed."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
-        cap = int(capacity) if capacity is not None else max(1024, t.size // 64)
-        while True:
+        t, n_sym = self._text(text)
+
+        def call(cap):
             out = np.zeros(cap, dtype=RECORD_DTYPE)
             n = C.c_uint64(0)
             cur = C.c_void_p(cursor.value)
-            rc = self.L.acm_scan_from(self.handle, C.byref(cur), t.ctypes.data, t.size * t.itemsize // self.sym_size, out.ctypes.data, cap,
-                                      C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_scan_from")
-            return out[:n.value], cur
+            return self.L.acm_scan_from(self.handle, C.byref(cur), t.ctypes.data, n_sym, out.ctypes.data, cap, C.byref(n)), n.value, (out, cur)
+        (out, cur), n, _ = _room_call(call, "acm_scan_from", int(capacity) if capacity is not None else max(1024, t.size // 64),
+                                      capacity is not None, repeats=None)
+        return out[:n], cur
 
     def scan_batch(self, texts, capacity=None):
         """acm_scan_batch(): a list of texts (bytes or arrays of symbols), each scanned from the root
         on its own in ONE call.  Returns a list with one record array per text, end_pos relative to
         the text's own first symbol -- what scan_host() gives for each of them alone."""
-        def symbols(t):
-            if self.sym_size in _SYM_DTYPE:
-                return self._symbols(t)
-            return np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t)
-        parts = [symbols(t) for t in texts]
-        offsets = np.zeros(len(parts) + 1, dtype=np.uint64)
-        if parts:
-            np.cumsum([p.size * p.itemsize // self.sym_size for p in parts], out=offsets[1:])
-        packed = (np.concatenate([p.reshape(-1).view(np.uint8) for p in parts]) if parts else np.zeros(0, np.uint8))
-        n_sym = int(offsets[-1])
-        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
-        while True:
+        packed, offsets = self._pack_texts(texts)
+        n_texts = offsets.size - 1
+
+        def call(cap):
             out = np.zeros(cap, dtype=RECORD_DTYPE)
-            first = np.zeros(len(parts) + 1, dtype=np.uint64)
+            first = np.zeros(n_texts + 1, dtype=np.uint64)
             n = C.c_uint64(0)
-            rc = self.L.acm_scan_batch(self.handle, packed.ctypes.data, offsets.ctypes.data, len(parts), out.ctypes.data, None,
-                                       first.ctypes.data, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_scan_batch")
-            res = []
-            for t in range(len(parts)):
-                r = out[int(first[t]):int(first[t + 1])].copy()
-                r["end_pos"] -= offsets[t]
-                res.append(r)
-            return res
+            rc = self.L.acm_scan_batch(self.handle, packed.ctypes.data, offsets.ctypes.data, n_texts, out.ctypes.data, None, first.ctypes.data, cap,
+                                       C.byref(n))
+            return rc, n.value, (out, first)
+        (out, first), _, _ = _room_call(call, "acm_scan_batch", int(capacity) if capacity is not None else max(1024, int(offsets[-1]) // 64),
+                                        capacity is not None, repeats=None)
+        res = []
+        for t in range(n_texts):
+            r = out[int(first[t]):int(first[t + 1])].copy()
+            r["end_pos"] -= offsets[t]
+            res.append(r)
+        return res
 
     def scan_anchored(self, texts, mode="prefixes", capacity=None):
         """acm_scan_anchored(): the keywords every text of a list begins with (mode "prefixes"), the
@@ -2491,13 +2573,12 @@ class Machine:
         """acm_tally(): how often every keyword occurs in `text`.  Returns (np.uint64 array with one
         counter per keyword, number of matches).  `tally` (an earlier call's array, at least
         nb_keywords entries) is ADDED TO in place; keyword(k) gives the spelling of counter k."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        t, n_sym = self._text(text)
         if tally is None:
             tally = np.zeros(self.nb_keywords, dtype=np.uint64)
         assert tally.dtype == np.uint64 and tally.flags.c_contiguous
         total = C.c_uint64(0)
-        _check(self.L.acm_tally(self.handle, t.ctypes.data, t.size * t.itemsize // self.sym_size, tally.ctypes.data, tally.size,
-                                C.byref(total)), "acm_tally")
+        _check(self.L.acm_tally(self.handle, t.ctypes.data, n_sym, tally.ctypes.data, tally.size, C.byref(total)), "acm_tally")
         return tally, int(total.value)
 
     def select(self, text, capacity=None):
@@ -2505,64 +2586,34 @@ class Machine:
         the one tiling a replacer, a redactor or a tokeniser acts on.  `capacity` must hold ALL
         matches (they are found first); by default an overflow is repeated once with the size the
         call reports."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
-        cap = int(capacity) if capacity is not None else max(1024, t.size // 64)
-        for attempt in (0, 1):
-            out = np.zeros(cap, dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = self.L.acm_select(self.handle, t.ctypes.data, t.size * t.itemsize // self.sym_size, out.ctypes.data, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_select")
-            return out[:n.value]
-
+        t, n_sym = self._text(text)
+        return _records_host_call(self.L.acm_select, "acm_select", (self.handle, t.ctypes.data, n_sym),
+                                  int(capacity) if capacity is not None else max(1024, t.size // 64), capacity is not None)
 
     def segment(self, text, cost, gap_cost, capacity=None):
         """acm_segment(): the minimum-cost tiling of `text` by the keywords in canonical order, under
         cost[keyword_id] per match taken and gap_cost per uncovered symbol (include/acm_segment.h).
         `capacity` must hold ALL matches (they are found first); by default an overflow is repeated
         once with the size the call reports.  Returns (records, sums)."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
-        c, cp = _costs(cost)
-        cap = int(capacity) if capacity is not None else max(1024, t.size // 64)
-        for attempt in (0, 1):
-            out = np.zeros(cap, dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            sums = np.zeros(2, np.uint64)
-            rc = self.L.acm_segment(self.handle, t.ctypes.data, t.size * t.itemsize // self.sym_size, cp, c.size, int(gap_cost),
-                                    out.ctypes.data, cap, C.byref(n), sums.ctypes.data)
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_segment")
-            return out[:n.value], (int(sums[0]), int(sums[1]))
+        t, n_sym = self._text(text)
+        return _segment_host_call(self.L.acm_segment, "acm_segment", (self.handle, t.ctypes.data, n_sym), cost, gap_cost,
+                                  int(capacity) if capacity is not None else max(1024, t.size // 64), capacity is not None)
 
     def scan_words(self, text, ranges=ASCII_WORD, flags="both", capacity=None):
         """acm_scan_words(): the whole-word matches of `text` in canonical order (see words_records).
         `capacity` must hold ALL matches (they are found first); by default an overflow is repeated
         once with the size the call reports."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+        t, n_sym = self._text(text)
         r, nr = _word_ranges(ranges, self.sym_size)
-        cap = int(capacity) if capacity is not None else max(1024, t.size // 64)
-        for attempt in (0, 1):
-            out = np.zeros(cap, dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = self.L.acm_scan_words(self.handle, t.ctypes.data, t.size * t.itemsize // self.sym_size, r.ctypes.data, nr, _word_flags(flags),
-                                       out.ctypes.data, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_scan_words")
-            return out[:n.value]
+        return _records_host_call(self.L.acm_scan_words, "acm_scan_words", (self.handle, t.ctypes.data, n_sym, r.ctypes.data, nr, _word_flags(flags)),
+                                  int(capacity) if capacity is not None else max(1024, t.size // 64), capacity is not None)
 
     def context(self, text, before=0, after=0, merge=True, capacity=None, gather=True, out_capacity=None):
         """acm_context(): the matches of `text` with `before` symbols in front of and `after` behind each
         (see context_records), as a Snippets of numpy arrays whose `records` are the matches in canonical
         order.  `capacity` must hold ALL matches; by default each overflow is repeated once with the size
         the call reports."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
-        n_sym = t.size * t.itemsize // self.sym_size
+        t, n_sym = self._text(text)
         call = _context_scan_call(self.L.acm_context, (self.handle,), t, n_sym, (), before, after, _context_flags("symbols", merge))
         return _context_host_call(call, "acm_context", t, self.sym_size, int(capacity) if capacity is not None else max(1024, t.size // 64),
                                   capacity is None, gather, out_capacity)
@@ -2571,41 +2622,13 @@ class Machine:
         """acm_scan_patterns(): the matches of the patterns of `patternset` (see patterns_records) in `text`,
         or in every text of the buffer when `offsets` (n_texts + 1 entries) cuts it; by default an overflow is
         repeated once with the size the call reports."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
-        ps = _patternset(patternset)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        cap = int(out_capacity) if out_capacity is not None else 1024
-        for attempt in (0, 1):
-            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = self.L.acm_scan_patterns(self.handle, t.ctypes.data if t.size else None, t.size * t.itemsize // self.sym_size,
-                                          off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *ps.args(),
-                                          out.ctypes.data if cap else None, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_scan_patterns")
-            return out[:n.value]
+        return self._scan_set("acm_scan_patterns", text, _patternset(patternset), offsets, out_capacity, extra=())[0]
 
     def scan_chains(self, text, chainset, offsets=None, out_capacity=None):
         """acm_scan_chains(): the matches of the chains of `chainset` (see chains_records) in `text`, or in
         every text of the buffer when `offsets` (n_texts + 1 entries) cuts it; by default an overflow is
         repeated once with the size the call reports."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
-        cs = _chainset(chainset)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        cap = int(out_capacity) if out_capacity is not None else 1024
-        for attempt in (0, 1):
-            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = self.L.acm_scan_chains(self.handle, t.ctypes.data if t.size else None, t.size * t.itemsize // self.sym_size,
-                                        off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *cs.args(),
-                                        out.ctypes.data if cap else None, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_scan_chains")
-            return out[:n.value]
+        return self._scan_set("acm_scan_chains", text, _chainset(chainset), offsets, out_capacity, extra=())[0]
 
     def scan_approx(self, text, approxset, offsets=None, out_capacity=None):
         """acm_scan_approx(): (matches, dist) of the targets of `approxset` (see approx_records) in `text`, or in
@@ -2623,23 +2646,12 @@ class Machine:
         templates_records) in `text`, or in every text of the buffer when `offsets` cuts it; arguments as scan_approx()."""
         return self._scan_set("acm_scan_templates", text, templateset, offsets, out_capacity)
 
-    def _scan_set(self, name, text, approxset, offsets, out_capacity):
-        """what scan_approx(), scan_edit() and scan_templates() share: the machine-level C call `name`"""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
+    def _scan_set(self, name, text, tset, offsets, out_capacity, extra=(np.uint32,)):
+        """what the scans for the sets of a family share -- patterns and chains, and with a distance per match
+        (`extra`) approx, edit and templates --: the machine-level C call `name`"""
+        t, n_sym = self._text(text)
         off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        cap = int(out_capacity) if out_capacity is not None else 1024
-        for attempt in (0, 1):
-            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
-            dist = np.zeros(max(cap, 1), dtype=np.uint32)
-            n = C.c_uint64(0)
-            rc = getattr(self.L, name)(self.handle, t.ctypes.data if t.size else None, t.size * t.itemsize // self.sym_size,
-                                       off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *approxset.args(),
-                                       out.ctypes.data if cap else None, dist.ctypes.data, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, name)
-            return out[:n.value], dist[:n.value]
+        return _matches_host_call(getattr(self.L, name), name, (self.handle, _ptr(t), n_sym, *_cut(off), *tset.args()), out_capacity, extra)
 
     def replace(self, text, replacements=None, fill=None, out_capacity=None):
         """acm_replace(): `text` with its leftmost-longest non-overlapping matches (select()) replaced:
@@ -2648,21 +2660,7 @@ class Machine:
         `fill`.  Returns (the new text as an array of the machine's symbols, the number of matches
         replaced).  out_capacity (symbols): by default an output overflow is repeated once with the
         size the call reports."""
-        t = np.ascontiguousarray(text) if self.sym_size not in _SYM_DTYPE else self._symbols(text)
-        n_sym = t.size * t.itemsize // self.sym_size
-        data, off, nk = replacement_table(replacements, self.sym_size, fill)
-        cap = int(out_capacity) if out_capacity is not None else n_sym + 1024
-        for attempt in (0, 1):
-            out = np.zeros(max(cap * self.sym_size // t.itemsize, 1), dtype=t.dtype)
-            need, m = C.c_uint64(0), C.c_uint64(0)
-            rc = self.L.acm_replace(self.handle, t.ctypes.data if t.size else None, n_sym, data.ctypes.data,
-                                    off.ctypes.data if off is not None else None, nk, out.ctypes.data, cap, C.byref(need), C.byref(m))
-            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
-                cap = int(need.value)
-                continue
-            _check(rc, "acm_replace")
-            return out[:int(need.value) * self.sym_size // t.itemsize], int(m.value)
-
+        return _replace_host_call(self.L.acm_replace, "acm_replace", self.handle, self._text(text)[0], self.sym_size, replacements, fill, out_capacity)
 
     def tokenize(self, texts_or_text, mode="run", gap_base=0, tok_of=None, token_capacity=None):
         """acm_tokenize(): the MaxMatch (greedy longest-match) tokens of one text (bytes or an array of
@@ -2671,32 +2669,11 @@ class Machine:
         covers by `mode` one token each ("symbol": gap_base + the symbol's value, 1- and 2-byte
         symbols), one token per run ("run": gap_base) or none ("drop").  Returns a Tokens of numpy
         arrays; `first` holds the row pointers of a list.  The call counts first and then fills."""
-        def symbols(t):
-            if self.sym_size in _SYM_DTYPE:
-                return self._symbols(t)
-            return np.frombuffer(bytes(t), dtype=np.uint8) if isinstance(t, (bytes, bytearray)) else np.ascontiguousarray(t)
-        dtype = _SYM_DTYPE.get(self.sym_size, np.uint8)
-        off = None
         if isinstance(texts_or_text, (list, tuple)):
-            parts = [symbols(t).reshape(-1) for t in texts_or_text]
-            off = np.zeros(len(parts) + 1, dtype=np.uint64)
-            if parts:
-                np.cumsum([p.size * p.itemsize // self.sym_size for p in parts], out=off[1:])
-            packed = np.concatenate([p.view(dtype) for p in parts]) if parts else np.zeros(0, dtype)
+            packed, off = self._pack_texts(texts_or_text)
         else:
-            packed = symbols(texts_or_text).reshape(-1)
-        n_sym = packed.size * packed.itemsize // self.sym_size
-        n_texts = off.size - 1 if off is not None else 0
-        table, nk = _tok_of(tok_of)
-        md = _token_mode(mode)
-
-        def call(ids, start, length, cap, need, first, m):
-            return self.L.acm_tokenize(self.handle, packed.ctypes.data if packed.size else None, n_sym, off.ctypes.data if off is not None else None,
-                                       n_texts, table.ctypes.data if table is not None else None, nk, int(gap_base), md,
-                                       ids.ctypes.data if ids is not None else None, start.ctypes.data if start is not None else None,
-                                       length.ctypes.data if length is not None else None, cap, C.byref(need),
-                                       first.ctypes.data if first is not None else None, C.byref(m))
-        return _tokens_host_call(call, "acm_tokenize", n_texts, off is not None, token_capacity)
+            packed, off = self._pack_texts([texts_or_text])[0], None
+        return _tokenize_host_call(self.L.acm_tokenize, "acm_tokenize", self.handle, packed, self.sym_size, off, mode, gap_base, tok_of, token_capacity)
 
     def grep(self, texts, invert=False, gather=True):
         """acm_grep(): `grep -F -f` over a list of texts (bytes or arrays of symbols), each scanned from
@@ -2749,32 +2726,6 @@ class Machine:
         return _index_host_call(self.L.acm_index, "acm_index", self.handle, packed, self.sym_size, offsets, nk, text_base)
 
 
-class Score:
-    """A score model on a plan's device (ACMScore): Plan.score_create() makes one."""
-
-    def __init__(self, handle, n_classes):
-        self.h = handle
-        self.n_classes = n_classes
-
-    def info(self):
-        """acm_gpu_score_info(): classes, terms, postings, always_classes and the texts the model's
-        evaluations sent through the fast and the wide form so far, as a dict; waits for the device."""
-        i = ScoreInfo()
-        _check(lib().acm_gpu_score_info(self.h, C.byref(i)), "acm_gpu_score_info")
-        return {n: int(getattr(i, n)) for n, _ in ScoreInfo._fields_}
-
-    def close(self):
-        if self.h:
-            lib().acm_gpu_score_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 class Replaced:
     """What Plan.replace_records() and Plan.scan_replace() leave on the device: `out` (a uint8 tensor,
     the first out_symbols symbols are the new text when out_symbols <= out_capacity), out_symbols and
@@ -2786,127 +2737,100 @@ class Replaced:
         self.records, self.count, self.out_start = records, count, out_start
 
 
-class Rules:
-    """A rule set on a plan's device (ACMRules): Plan.rules_create() makes one."""
+class _DeviceSet(_Owner):
+    """A set of a family compiled for a plan's device.  A subclass declares STEM (its C calls are
+    acm_gpu_<STEM>_create, _info and _destroy), INFO (the struct _info fills), SIZE (the attribute that holds the
+    number of its members, here and in its host description) and _host (what makes a host description of the
+    caller's argument)."""
+    _host = staticmethod(lambda description: description)
 
-    def __init__(self, handle, n_rules):
+    def __init__(self, handle, size):
         self.h = handle
-        self.n_rules = n_rules
+        setattr(self, self.SIZE, size)
+
+    @classmethod
+    def create(cls, plan, description):
+        """acm_gpu_<STEM>_create(): the host description compiled and uploaded to the plan's device"""
+        d = cls._host(description)
+        name = "acm_gpu_%s_create" % cls.STEM
+        h = C.c_void_p()
+        _check(getattr(lib(), name)(plan.h, *d.args(), C.byref(h)), name)
+        return cls(h, getattr(d, cls.SIZE))
+
+    @classmethod
+    @contextlib.contextmanager
+    def for_call(cls, plan, given, sync=False):
+        """The device set of one call: `given` itself when it is one, else its host description compiled for
+        this call and closed behind it.  sync: the current stream is synchronised before such a set goes away,
+        for the callers that queue work and return without reading a result."""
+        if isinstance(given, cls):
+            yield given
+            return
+        made = cls.create(plan, given)
+        try:
+            yield made
+            if sync:
+                import torch
+                torch.cuda.current_stream().synchronize()
+        finally:
+            made.close()
 
     def info(self):
-        """acm_gpu_rules_info(): rules, terms, always_rules, postings and the texts the set's
-        evaluations sent through the fast and the wide form so far, as a dict; waits for the device."""
-        i = RulesInfo()
-        _check(lib().acm_gpu_rules_info(self.h, C.byref(i)), "acm_gpu_rules_info")
-        return {n: int(getattr(i, n)) for n, _ in RulesInfo._fields_}
+        """acm_gpu_<STEM>_info(): the figures of the set as a dict (the class says which)"""
+        i = self.INFO()
+        name = "acm_gpu_%s_info" % self.STEM
+        _check(getattr(lib(), name)(self.h, C.byref(i)), name)
+        return {n: int(getattr(i, n)) for n, _ in self.INFO._fields_}
 
     def close(self):
         if self.h:
-            lib().acm_gpu_rules_destroy(self.h)
+            getattr(lib(), "acm_gpu_%s_destroy" % self.STEM)(self.h)
             self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+
+class Rules(_DeviceSet):
+    """A rule set on a plan's device (ACMRules): Plan.rules_create() makes one.  info(): rules, terms,
+    always_rules, postings and the texts the set's evaluations sent through the fast and the wide form so far;
+    waits for the device."""
+    STEM, INFO, SIZE, _host = "rules", RulesInfo, "n_rules", staticmethod(_ruleset)
 
 
-class Patterns:
-    """A pattern set on a plan's device (ACMPatterns): Plan.patterns_create() makes one."""
-
-    def __init__(self, handle, n_patterns):
-        self.h = handle
-        self.n_patterns = n_patterns
-
-    def info(self):
-        """acm_gpu_patterns_info(): patterns, terms, anchor_keywords, longest and max_anchor_postings as a
-        dict; n records give at most n * max_anchor_postings matches."""
-        i = PatternsInfo()
-        _check(lib().acm_gpu_patterns_info(self.h, C.byref(i)), "acm_gpu_patterns_info")
-        return {n: int(getattr(i, n)) for n, _ in PatternsInfo._fields_}
-
-    def close(self):
-        if self.h:
-            lib().acm_gpu_patterns_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class Score(_DeviceSet):
+    """A score model on a plan's device (ACMScore): Plan.score_create() makes one.  info(): classes, terms,
+    postings, always_classes and the texts the model's evaluations sent through the fast and the wide form so
+    far; waits for the device."""
+    STEM, INFO, SIZE, _host = "score", ScoreInfo, "n_classes", staticmethod(_scoremodel)
 
 
-class Chains:
-    """A chain set on a plan's device (ACMChains): Plan.chains_create() makes one."""
-
-    def __init__(self, handle, n_chains):
-        self.h = handle
-        self.n_chains = n_chains
-
-    def info(self):
-        """acm_gpu_chains_info(): chains, terms, max_terms, max_gap, max_postings and max_last_postings as a
-        dict; n records give at most n * max_last_postings matches."""
-        i = ChainsInfo()
-        _check(lib().acm_gpu_chains_info(self.h, C.byref(i)), "acm_gpu_chains_info")
-        return {n: int(getattr(i, n)) for n, _ in ChainsInfo._fields_}
-
-    def close(self):
-        if self.h:
-            lib().acm_gpu_chains_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class Patterns(_DeviceSet):
+    """A pattern set on a plan's device (ACMPatterns): Plan.patterns_create() makes one.  info(): patterns,
+    terms, anchor_keywords, longest and max_anchor_postings; n records give at most n * max_anchor_postings
+    matches (MOST)."""
+    STEM, INFO, SIZE, _host, MOST = "patterns", PatternsInfo, "n_patterns", staticmethod(_patternset), "max_anchor_postings"
 
 
-class Approx:
-    """A target set with mismatch budgets on a plan's device (ACMApprox): Plan.approx_create() makes one."""
+class Chains(_DeviceSet):
+    """A chain set on a plan's device (ACMChains): Plan.chains_create() makes one.  info(): chains, terms,
+    max_terms, max_gap, max_postings and max_last_postings; n records give at most n * max_last_postings
+    matches (MOST)."""
+    STEM, INFO, SIZE, _host, MOST = "chains", ChainsInfo, "n_chains", staticmethod(_chainset), "max_last_postings"
 
-    def __init__(self, handle, n_targets):
-        self.h = handle
-        self.n_targets = n_targets
 
-    def info(self):
-        """acm_gpu_approx_info(): targets, terms, seed_keywords, longest, max_k and max_postings as a dict; n
-        records give at most n * max_postings matches (the edit calls: times 2 * max_k + 1)."""
-        i = ApproxInfo()
-        _check(lib().acm_gpu_approx_info(self.h, C.byref(i)), "acm_gpu_approx_info")
-        return {n: int(getattr(i, n)) for n, _ in ApproxInfo._fields_}
-
-    def close(self):
-        if self.h:
-            lib().acm_gpu_approx_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class Approx(_DeviceSet):
+    """A target set with mismatch budgets on a plan's device (ACMApprox): Plan.approx_create() makes one.
+    info(): targets, terms, seed_keywords, longest, max_k and max_postings; n records give at most n *
+    max_postings matches (the edit calls: times 2 * max_k + 1)."""
+    STEM, INFO, SIZE = "approx", ApproxInfo, "n_targets"
 
 
 class Templates(Approx):
-    """A template set on a plan's device (ACMTemplates): Plan.templates_create() makes one."""
-
-    def info(self):
-        """acm_gpu_templates_info(): templates, terms, classes, seed_keywords, longest, max_k and max_postings as a
-        dict; n records give at most n * max_postings matches."""
-        i = TemplatesInfo()
-        _check(lib().acm_gpu_templates_info(self.h, C.byref(i)), "acm_gpu_templates_info")
-        return {n: int(getattr(i, n)) for n, _ in TemplatesInfo._fields_}
-
-    def close(self):
-        if self.h:
-            lib().acm_gpu_templates_destroy(self.h)
-            self.h = None
+    """A template set on a plan's device (ACMTemplates): Plan.templates_create() makes one.  info(): templates,
+    terms, classes, seed_keywords, longest, max_k and max_postings; n records give at most n * max_postings
+    matches."""
+    STEM, INFO = "templates", TemplatesInfo
 
 
-class Plan:
+class Plan(_Owner):
     """Device-resident flattened automaton (ACMPlan).  Scans take torch CUDA tensors (device
     memory and streams are torch's; the kernels are this library's)."""
 
@@ -2922,12 +2846,6 @@ class Plan:
             lib().acm_gpu_plan_destroy(self.h)
             self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def update(self, machine):
         """acm_gpu_plan_update(): take over the keywords added to `machine` since this plan was made."""
         _check(lib().acm_gpu_plan_update(self.h, machine.handle), "acm_gpu_plan_update")
@@ -2941,6 +2859,48 @@ class Plan:
     def _stream():
         import torch
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def _text_args(self, text, n_symbols=None):
+        """the checks of a device call on `text`; returns n_symbols, by default what the tensor holds"""
+        assert text.is_cuda and text.is_contiguous()
+        return text.numel() * text.element_size() // self.sym_size if n_symbols is None else n_symbols
+
+    def _batch_args(self, text, offsets):
+        """the checks of a device call on a batch -- `text` and its int64 `offsets`, n_texts + 1 of them --;
+        returns (n_symbols, n_texts)"""
+        import torch
+        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
+        n_texts = offsets.numel() - 1
+        assert n_texts >= 0
+        return text.numel() * text.element_size() // self.sym_size, n_texts
+
+    @staticmethod
+    def _windows(window, capacity, pair_capacity=None):
+        """(window, capacity, pair_capacity) of the tally in front of a call, by default 16 Mi symbols a window,
+        1 Mi records a window and as many pairs as records"""
+        window = int(window) if window is not None else 1 << 24
+        capacity = int(capacity) if capacity is not None else 1 << 20
+        return window, capacity, int(pair_capacity) if pair_capacity is not None else capacity
+
+    @staticmethod
+    def _records_out(records, count, capacity, n_symbols, dev):
+        """(records, count) of a scan that leaves both on the device: the caller's tensors, or new ones -- `capacity`
+        records, by default one for every 256 symbols and 4096 at the least, and a zeroed count"""
+        import torch
+        if records is None:
+            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+            records = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+        return records, count if count is not None else _i64(1, dev)
+
+    @staticmethod
+    def _records_room(records, capacity, n_symbols, dev):
+        """(records, capacity) of a scan into records of the call's own: the caller's tensor, or a new one of
+        `capacity` records, by default one for every 256 symbols and 4096 at the least"""
+        import torch
+        if records is not None:
+            return records, records.shape[0] if capacity is None else int(capacity)
+        cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
+        return torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev), cap
 
     def scan(self, text, n_symbols=None, emit_from=0, pos_base=0, capacity=None, records=None, count=None):
         """Unsorted scan of a device tensor (uint8 storage of n_symbols * sym_size bytes, or a
@@ -3034,17 +2994,8 @@ class Plan:
         """acm_gpu_scan_host(): numpy in, numpy out, through the C ABI only (no torch)."""
         t = np.ascontiguousarray(text)
         n_sym = t.size * t.itemsize // self.sym_size
-        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
-        while True:
-            out = np.zeros(cap, dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = lib().acm_gpu_scan_host(self.h, t.ctypes.data, n_sym, emit_from, pos_base, out.ctypes.data, cap,
-                                         C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_gpu_scan_host")
-            return out[:n.value]
+        return _records_host_call(lib().acm_gpu_scan_host, "acm_gpu_scan_host", (self.h, t.ctypes.data, n_sym, emit_from, pos_base),
+                                  int(capacity) if capacity is not None else max(1024, n_sym // 64), capacity is not None, repeats=None)
 
     def scan_batch(self, text, offsets, capacity=None):
         """acm_gpu_scan_batch_device(): `text` is a device tensor holding the texts of a batch side
@@ -3054,28 +3005,29 @@ class Plan:
         index in `text`, the text of each, and first[t] .. first[t + 1] = the records of text t.
         capacity must hold the matches of the whole buffer: by default Plan.count() says how many
         there are, and an overflow is repeated once with the size the call reports."""
-        import torch
-        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-        n_symbols = text.numel() * text.element_size() // self.sym_size
-        n_texts = offsets.numel() - 1
-        assert n_texts >= 0
-        cap = int(capacity) if capacity is not None else max(int(self.count(text).item()), 1)
-        for attempt in (0, 1):
-            records = torch.empty((cap, 2), dtype=torch.int64, device=text.device)
-            text_id = torch.empty(cap, dtype=torch.int32, device=text.device)
-            first = torch.zeros(n_texts + 1, dtype=torch.int64, device=text.device)
-            count = torch.zeros(1, dtype=torch.int64, device=text.device)
-            tb = lib().acm_gpu_scan_batch_tmp_bytes(self.h, cap, n_symbols, n_texts)
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        n_symbols, n_texts = self._batch_args(text, offsets)
+
+        def launch(records, text_id, first, cap, count):
+            tmp = _scratch(lib().acm_gpu_scan_batch_tmp_bytes(self.h, cap, n_symbols, n_texts), text.device)
             _check(lib().acm_gpu_scan_batch_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, records.data_ptr(),
                                                    text_id.data_ptr(), first.data_ptr(), cap, count.data_ptr(), tmp.data_ptr(), tmp.numel(),
                                                    self._stream()), "acm_gpu_scan_batch_device")
-            n = int(count.item())
-            if n <= cap:
-                break
-            if attempt == 1:
-                raise ACMError(ACM_GPU_E_OVERFLOW, "acm_gpu_scan_batch_device: %d records" % n)
-            cap = n
+        return self._batch_records_device(launch, "acm_gpu_scan_batch_device", text.device, n_texts,
+                                          int(capacity) if capacity is not None else max(int(self.count(text).item()), 1))
+
+    def _batch_records_device(self, launch, what, dev, n_texts, cap):
+        """what scan_batch() and Flows.scan() share: launch(records, text_id, first, cap, count) into tensors of
+        the call's own, repeated once with the count when that is above cap, then the plan's status and the
+        three as numpy arrays (records, text_id, first)"""
+        import torch
+
+        def run(cap):
+            records = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=dev)
+            text_id = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+            first, count = _i64(n_texts + 1, dev), _i64(1, dev)
+            launch(records, text_id, first, cap, count)
+            return int(count.item()), (records, text_id, first)
+        n, (records, text_id, first) = _device_room_call(run, what, cap)
         self.status()
         return (np.frombuffer(records[:n].cpu().numpy().tobytes(), dtype=RECORD_DTYPE).copy(),
                 text_id[:n].cpu().numpy().view(np.uint32).copy(), first.cpu().numpy().view(np.uint64).copy())
@@ -3085,20 +3037,8 @@ class Plan:
         t = np.ascontiguousarray(text)
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         assert off.size >= 1, "offsets has n_texts + 1 entries"
-        n_texts = off.size - 1
-        cap = int(capacity) if capacity is not None else max(1024, t.size * t.itemsize // self.sym_size // 64)
-        for attempt in (0, 1):
-            out = np.zeros(cap, dtype=RECORD_DTYPE)
-            tid = np.zeros(cap, dtype=np.uint32)
-            first = np.zeros(n_texts + 1, dtype=np.uint64)
-            n = C.c_uint64(0)
-            rc = lib().acm_gpu_scan_batch_host(self.h, t.ctypes.data, off.ctypes.data, n_texts, out.ctypes.data, tid.ctypes.data,
-                                               first.ctypes.data, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_gpu_scan_batch_host")
-            return out[:n.value], tid[:n.value], first
+        return _batch_records_host_call(lib().acm_gpu_scan_batch_host, "acm_gpu_scan_batch_host", (self.h, t.ctypes.data, off.ctypes.data, off.size - 1),
+                                        off.size - 1, int(capacity) if capacity is not None else max(1024, t.size * t.itemsize // self.sym_size // 64))
 
     def scan_anchored(self, text, offsets, mode="prefixes", capacity=None, records=None, text_id=None, first=None, count=None, tmp=None):
         """acm_gpu_scan_anchored_device(): `text` and `offsets` as Plan.scan_batch takes them.  The
@@ -3109,10 +3049,7 @@ class Plan:
         only: by default n_texts, which "longest" and "whole" cannot exceed; count > capacity says
         what "prefixes" needs, and first is complete either way."""
         import torch
-        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-        n_symbols = text.numel() * text.element_size() // self.sym_size
-        n_texts = offsets.numel() - 1
-        assert n_texts >= 0
+        n_symbols, n_texts = self._batch_args(text, offsets)
         dev = text.device
         if records is None:
             records = torch.empty((max(int(capacity) if capacity is not None else n_texts, 1), 2), dtype=torch.int64, device=dev)
@@ -3120,12 +3057,10 @@ class Plan:
         if text_id is None:
             text_id = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
         if first is None:
-            first = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
+            first = _i64(n_texts + 1, dev)
         if count is None:
-            count = torch.zeros(1, dtype=torch.int64, device=dev)
-        tb = lib().acm_gpu_scan_anchored_tmp_bytes(self.h, n_texts)
-        if tmp is None or tmp.numel() < tb:
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+            count = _i64(1, dev)
+        tmp = _scratch(lib().acm_gpu_scan_anchored_tmp_bytes(self.h, n_texts), dev, tmp)
         _check(lib().acm_gpu_scan_anchored_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, _anchored_mode(mode),
                                                   records.data_ptr(), text_id.data_ptr(), first.data_ptr(), cap, count.data_ptr(), tmp.data_ptr(),
                                                   tmp.numel(), self._stream()), "acm_gpu_scan_anchored_device")
@@ -3138,18 +3073,12 @@ class Plan:
         length of the longest keyword the text begins with; -1 (ACM_LOOKUP_NONE) / 0 where there is
         none.  An output given as False is not computed (None comes back); a tensor is written in place."""
         import torch
-        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-        n_symbols = text.numel() * text.element_size() // self.sym_size
-        n_texts = offsets.numel() - 1
-        assert n_texts >= 0
+        n_symbols, n_texts = self._batch_args(text, offsets)
         outs = [torch.empty(max(n_texts, 1), dtype=torch.int32, device=text.device) if o is True else (None if o is False or o is None else o)
                 for o in (whole_id, prefix_id, prefix_len)]
-        tb = lib().acm_gpu_lookup_tmp_bytes(self.h, n_texts)
-        if tmp is None or tmp.numel() < tb:
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-        _check(lib().acm_gpu_lookup_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts,
-                                           *[o.data_ptr() if o is not None else None for o in outs], tmp.data_ptr(), tmp.numel(), self._stream()),
-               "acm_gpu_lookup_device")
+        tmp = _scratch(lib().acm_gpu_lookup_tmp_bytes(self.h, n_texts), text.device, tmp)
+        _check(lib().acm_gpu_lookup_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, *[_opt(o) for o in outs], tmp.data_ptr(),
+                                           tmp.numel(), self._stream()), "acm_gpu_lookup_device")
         return tuple(o[:n_texts] if o is not None else None for o in outs)
 
     def scan_anchored_host(self, text, offsets, mode="prefixes", capacity=None):
@@ -3184,17 +3113,13 @@ class Plan:
         that a window overflowed -- tally is untouched and total is 0 then, and a capacity of `need`
         suffices for the same window.  Synchronises to read total and need."""
         import torch
-        assert text.is_cuda and text.is_contiguous()
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
-        window = int(window) if window is not None else 1 << 24
-        capacity = int(capacity) if capacity is not None else 1 << 20
+        n_symbols = self._text_args(text, n_symbols)
+        window, capacity, _ = self._windows(window, capacity)
         if tally is None:
-            tally = torch.zeros(max(self.tally_keywords, 1), dtype=torch.int64, device=text.device)
+            tally = _i64(max(self.tally_keywords, 1), text.device)
         assert tally.is_cuda and tally.is_contiguous() and tally.dtype == torch.int64
-        out = torch.zeros(2, dtype=torch.int64, device=text.device)
-        tb = lib().acm_gpu_tally_tmp_bytes(self.h, window, capacity)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        out = _i64(2, text.device)
+        tmp = _scratch(lib().acm_gpu_tally_tmp_bytes(self.h, window, capacity), text.device)
         _check(lib().acm_gpu_tally_device(self.h, text.data_ptr(), n_symbols, emit_from, tally.data_ptr(), tally.numel(), window, capacity,
                                           out.data_ptr(), out.data_ptr() + 8, tmp.data_ptr(), tmp.numel(), self._stream()),
                "acm_gpu_tally_device")
@@ -3220,36 +3145,36 @@ class Plan:
         buffer; it must not overlap `text`).  Returns a Grepped of device tensors; synchronises to
         read its four numbers."""
         import torch
-        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-        n_symbols = text.numel() * text.element_size() // self.sym_size
-        n_texts = offsets.numel() - 1
-        assert n_texts >= 0
-        window = int(window) if window is not None else 1 << 24
-        capacity = int(capacity) if capacity is not None else 1 << 20
+        n_symbols, n_texts = self._batch_args(text, offsets)
+        window, capacity, _ = self._windows(window, capacity)
         dev = text.device
-        hits = torch.zeros(max(n_texts, 1), dtype=torch.int64, device=dev)
+        hits = _i64(max(n_texts, 1), dev)
         kept = torch.zeros(max(n_texts, 1), dtype=torch.int32, device=dev)
-        out_off = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
-        res = torch.zeros(4, dtype=torch.int64, device=dev)                      # n_kept, total, need, out_symbols
-        if gather:
-            if out_capacity is None:
-                out_capacity = out.numel() * out.element_size() // self.sym_size if out is not None else n_symbols
-            if out is None:
-                out = torch.empty(max(int(out_capacity) * self.sym_size, 16), dtype=torch.uint8, device=dev)
-            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= int(out_capacity) * self.sym_size
-        else:
-            out, out_capacity = None, 0
-        tb = lib().acm_gpu_grep_tmp_bytes(self.h, window, capacity, n_symbols, n_texts)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        out_off = _i64(n_texts + 1, dev)
+        res = _i64(4, dev)                                                       # n_kept, total, need, out_symbols
+        out, out_capacity = self._gather_room(dev, gather, out, out_capacity, n_symbols)
+        tmp = _scratch(lib().acm_gpu_grep_tmp_bytes(self.h, window, capacity, n_symbols, n_texts), dev)
         _check(lib().acm_gpu_grep_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts,
                                          ACM_GREP_INVERT if invert else ACM_GREP_MATCHING, window, capacity, hits.data_ptr(), kept.data_ptr(),
-                                         res.data_ptr(), res.data_ptr() + 8, res.data_ptr() + 16, out.data_ptr() if gather else None,
-                                         int(out_capacity), out_off.data_ptr(), res.data_ptr() + 24 if gather else None, tmp.data_ptr(),
-                                         tmp.numel(), self._stream()), "acm_gpu_grep_device")
+                                         res.data_ptr(), res.data_ptr() + 8, res.data_ptr() + 16, _opt(out), out_capacity, out_off.data_ptr(),
+                                         res.data_ptr() + 24 if gather else None, tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_grep_device")
         n_kept, total, need, out_symbols = (int(x) for x in res.cpu())
         if not gather:
             out_symbols = int(out_off[n_kept].item()) if need <= capacity else 0
-        return Grepped(hits[:n_texts], kept, n_kept, total, need, out, out_off, out_symbols, int(out_capacity))
+        return Grepped(hits[:n_texts], kept, n_kept, total, need, out, out_off, out_symbols, out_capacity)
+
+    def _gather_room(self, dev, gather, out, out_capacity, n_symbols):
+        """(out, out_capacity) of a call that packs symbols into `out` when `gather`: the caller's tensor, or a new
+        uint8 one with room for out_capacity symbols, by default for the whole buffer; (None, 0) without"""
+        import torch
+        if not gather:
+            return None, 0
+        if out_capacity is None:
+            out_capacity = out.numel() * out.element_size() // self.sym_size if out is not None else n_symbols
+        if out is None:
+            out = torch.empty(max(int(out_capacity) * self.sym_size, 16), dtype=torch.uint8, device=dev)
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= int(out_capacity) * self.sym_size
+        return out, int(out_capacity)
 
     def grep_host(self, text, offsets, invert=False, gather=True, out_capacity=None):
         """acm_gpu_grep_host(): the same from host arrays, through the C ABI only (no torch).  The call
@@ -3267,22 +3192,20 @@ class Plan:
         Plan.grep, Plan.scan_batch, Plan.tally_batch and Flows take as it is.  Without `capacity` the
         texts are counted first (one synchronise) and the tensor is sized by the count; with it the
         call raises ACM_GPU_E_OVERFLOW, the count needed in its `need`, when there are more texts."""
-        import torch
-        assert text.is_cuda and text.is_contiguous()
-        n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_symbols = self._text_args(text)
         d, nd = _delims(delims, self.sym_size)
         flags = ACM_SPLIT_RUNS if runs else ACM_SPLIT_EVERY
         dev = text.device
-        tmp = torch.empty(max(lib().acm_gpu_split_tmp_bytes(self.h, n_symbols), 16), dtype=torch.uint8, device=dev)
-        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        tmp = _scratch(lib().acm_gpu_split_tmp_bytes(self.h, n_symbols), dev)
+        count = _i64(1, dev)
 
         def call(off, cap):
-            _check(lib().acm_gpu_split_device(self.h, text.data_ptr(), n_symbols, d.ctypes.data, nd, flags, off.data_ptr() if off is not None else None,
-                                              cap, count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_split_device")
+            _check(lib().acm_gpu_split_device(self.h, text.data_ptr(), n_symbols, d.ctypes.data, nd, flags, _opt(off), cap, count.data_ptr(),
+                                              tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_split_device")
         if capacity is None:
             call(None, 0)
             capacity = int(count.item())
-        off = torch.zeros(int(capacity) + 1, dtype=torch.int64, device=dev)
+        off = _i64(int(capacity) + 1, dev)
         call(off, int(capacity))
         n = int(count.item())
         if n > int(capacity):
@@ -3328,20 +3251,14 @@ class Plan:
         `pair_capacity` (the room of col and val) to `capacity`.  Returns a TalliedBatch of device
         tensors; synchronises to read its four numbers."""
         import torch
-        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-        n_symbols = text.numel() * text.element_size() // self.sym_size
-        n_texts = offsets.numel() - 1
-        assert n_texts >= 0
-        window = int(window) if window is not None else 1 << 24
-        capacity = int(capacity) if capacity is not None else 1 << 20
-        pair_capacity = int(pair_capacity) if pair_capacity is not None else capacity
+        n_symbols, n_texts = self._batch_args(text, offsets)
+        window, capacity, pair_capacity = self._windows(window, capacity, pair_capacity)
         dev = text.device
-        row_ptr = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
+        row_ptr = _i64(n_texts + 1, dev)
         col = torch.zeros(max(pair_capacity, 1), dtype=torch.int32, device=dev)
-        val = torch.zeros(max(pair_capacity, 1), dtype=torch.int64, device=dev)
-        res = torch.zeros(4, dtype=torch.int64, device=dev)                      # nnz, total, need, need_pairs
-        tb = lib().acm_gpu_tally_batch_tmp_bytes(self.h, window, capacity, pair_capacity, n_symbols, n_texts)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        val = _i64(max(pair_capacity, 1), dev)
+        res = _i64(4, dev)                                                       # nnz, total, need, need_pairs
+        tmp = _scratch(lib().acm_gpu_tally_batch_tmp_bytes(self.h, window, capacity, pair_capacity, n_symbols, n_texts), dev)
         _check(lib().acm_gpu_tally_batch_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity,
                                                 row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), res.data_ptr(), res.data_ptr() + 8,
                                                 res.data_ptr() + 16, res.data_ptr() + 24, tmp.data_ptr(), tmp.numel(), self._stream()),
@@ -3360,20 +3277,24 @@ class Plan:
     def rules_create(self, ruleset):
         """acm_gpu_rules_create(): `ruleset` (a RuleSet, or a list of rule()s) compiled and uploaded to
         this plan's device.  Returns a Rules; it stays valid across update()."""
-        rs = _ruleset(ruleset)
-        h = C.c_void_p()
-        _check(lib().acm_gpu_rules_create(self.h, *rs.args(), C.byref(h)), "acm_gpu_rules_create")
-        return Rules(h, rs.n_rules)
-
-    def _rules_handle(self, rules):
-        """(a Rules, whether this call made it) of a Rules, a RuleSet or a list of rule()s"""
-        return (rules, False) if isinstance(rules, Rules) else (self.rules_create(rules), True)
+        return Rules.create(self, ruleset)
 
     def _fired_outputs(self, dev, n_texts, fired_capacity):
         import torch
-        fired_ptr = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
         fired = torch.zeros(max(fired_capacity, 1), dtype=torch.int32, device=dev) if fired_capacity else None
-        return fired_ptr, fired
+        return _i64(n_texts + 1, dev), fired
+
+    @staticmethod
+    def _matrix_args(tallied):
+        """the checks of a device call on a count matrix (a TalliedBatch of device tensors); returns (row_ptr, col,
+        val, n_texts)"""
+        import torch
+        row_ptr, col, val = tallied.row_ptr, tallied.col, tallied.val
+        assert row_ptr.is_cuda and row_ptr.is_contiguous() and row_ptr.dtype == torch.int64
+        assert col.is_contiguous() and col.dtype == torch.int32 and val.is_contiguous() and val.dtype == torch.int64
+        n_texts = row_ptr.numel() - 1
+        assert n_texts >= 0
+        return row_ptr, col, val, n_texts
 
     def rules(self, text, offsets, rules, window=None, capacity=None, pair_capacity=None, fired_capacity=None):
         """acm_gpu_rules_device(): which rules fire in which text of a batch, on the device: the tally
@@ -3382,68 +3303,41 @@ class Plan:
         `rules` is a Rules from rules_create() (or a RuleSet / a list of rule()s, compiled for this
         call).  fired_capacity: the room of `fired` (0: count only; None: counted first, then sized by
         the count).  Returns a Fired of device tensors; synchronises to read its four numbers."""
-        import torch
-        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-        n_symbols = text.numel() * text.element_size() // self.sym_size
-        n_texts = offsets.numel() - 1
-        assert n_texts >= 0
-        window = int(window) if window is not None else 1 << 24
-        capacity = int(capacity) if capacity is not None else 1 << 20
-        pair_capacity = int(pair_capacity) if pair_capacity is not None else capacity
+        n_symbols, n_texts = self._batch_args(text, offsets)
+        window, capacity, pair_capacity = self._windows(window, capacity, pair_capacity)
         dev = text.device
-        R, own = self._rules_handle(rules)
-        res = torch.zeros(4, dtype=torch.int64, device=dev)                      # n_fired, total, need, need_pairs
-        tb = lib().acm_gpu_rules_tmp_bytes(self.h, R.h, window, capacity, pair_capacity, n_symbols, n_texts)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        with Rules.for_call(self, rules) as R:
+            res = _i64(4, dev)                                                   # n_fired, total, need, need_pairs
+            tmp = _scratch(lib().acm_gpu_rules_tmp_bytes(self.h, R.h, window, capacity, pair_capacity, n_symbols, n_texts), dev)
 
-        def call(cap):
-            fired_ptr, fired = self._fired_outputs(dev, n_texts, cap)
-            _check(lib().acm_gpu_rules_device(self.h, R.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity,
-                                              fired_ptr.data_ptr(), fired.data_ptr() if cap else None, cap, res.data_ptr(), res.data_ptr() + 8,
-                                              res.data_ptr() + 16, res.data_ptr() + 24, tmp.data_ptr(), tmp.numel(), self._stream()),
-                   "acm_gpu_rules_device")
-            n_fired, total, need, need_pairs = (int(x) for x in res.cpu())
-            return Fired(fired_ptr, fired, n_fired, total, need, need_pairs, cap)
-        try:
-            got = call(int(fired_capacity) if fired_capacity is not None else 0)
-            if fired_capacity is None and got.n_fired:
-                got = call(got.n_fired)
-            return got
-        finally:
-            if own:
-                R.close()
+            def call(cap):
+                fired_ptr, fired = self._fired_outputs(dev, n_texts, cap)
+                _check(lib().acm_gpu_rules_device(self.h, R.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity,
+                                                  fired_ptr.data_ptr(), _opt(fired), cap, res.data_ptr(), res.data_ptr() + 8,
+                                                  res.data_ptr() + 16, res.data_ptr() + 24, tmp.data_ptr(), tmp.numel(), self._stream()),
+                       "acm_gpu_rules_device")
+                n_fired, total, need, need_pairs = (int(x) for x in res.cpu())
+                return Fired(fired_ptr, fired, n_fired, total, need, need_pairs, cap)
+            return _counted(call, fired_capacity, "n_fired")
 
     def rules_matrix(self, tallied, rules, fired_capacity=None):
         """acm_gpu_rules_matrix_device(): the same for a count matrix that lies on the device: `tallied`
         is a TalliedBatch of device tensors, tally_batch()'s or the caller's own (row_ptr int64 with
         n_texts + 1 entries, col int32, val int64).  Returns a Fired of device tensors (total, need and
         need_pairs None); synchronises to read n_fired."""
-        import torch
-        row_ptr, col, val = tallied.row_ptr, tallied.col, tallied.val
-        assert row_ptr.is_cuda and row_ptr.is_contiguous() and row_ptr.dtype == torch.int64
-        assert col.is_contiguous() and col.dtype == torch.int32 and val.is_contiguous() and val.dtype == torch.int64
-        n_texts = row_ptr.numel() - 1
-        assert n_texts >= 0
+        row_ptr, col, val, n_texts = self._matrix_args(tallied)
         dev = row_ptr.device
-        R, own = self._rules_handle(rules)
-        res = torch.zeros(1, dtype=torch.int64, device=dev)
-        tb = lib().acm_gpu_rules_matrix_tmp_bytes(self.h, R.h, n_texts)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        with Rules.for_call(self, rules) as R:
+            res = _i64(1, dev)
+            tmp = _scratch(lib().acm_gpu_rules_matrix_tmp_bytes(self.h, R.h, n_texts), dev)
 
-        def call(cap):
-            fired_ptr, fired = self._fired_outputs(dev, n_texts, cap)
-            _check(lib().acm_gpu_rules_matrix_device(self.h, R.h, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), n_texts, fired_ptr.data_ptr(),
-                                                     fired.data_ptr() if cap else None, cap, res.data_ptr(), tmp.data_ptr(), tmp.numel(),
-                                                     self._stream()), "acm_gpu_rules_matrix_device")
-            return Fired(fired_ptr, fired, int(res.item()), fired_capacity=cap)
-        try:
-            got = call(int(fired_capacity) if fired_capacity is not None else 0)
-            if fired_capacity is None and got.n_fired:
-                got = call(got.n_fired)
-            return got
-        finally:
-            if own:
-                R.close()
+            def call(cap):
+                fired_ptr, fired = self._fired_outputs(dev, n_texts, cap)
+                _check(lib().acm_gpu_rules_matrix_device(self.h, R.h, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), n_texts, fired_ptr.data_ptr(),
+                                                         _opt(fired), cap, res.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
+                       "acm_gpu_rules_matrix_device")
+                return Fired(fired_ptr, fired, int(res.item()), fired_capacity=cap)
+            return _counted(call, fired_capacity, "n_fired")
 
     def rules_host(self, text, offsets, ruleset):
         """acm_gpu_rules_host(): the same as rules() from host arrays, through the C ABI only (no torch).
@@ -3456,20 +3350,13 @@ class Plan:
     def score_create(self, model):
         """acm_gpu_score_create(): `model` (a ScoreModel, or a list of score_class()es) compiled and
         uploaded to this plan's device.  Returns a Score; it stays valid across update()."""
-        sm = _scoremodel(model)
-        h = C.c_void_p()
-        _check(lib().acm_gpu_score_create(self.h, *sm.args(), C.byref(h)), "acm_gpu_score_create")
-        return Score(h, sm.n_classes)
-
-    def _score_handle(self, model):
-        """(a Score, whether this call made it) of a Score, a ScoreModel or a list of score_class()es"""
-        return (model, False) if isinstance(model, Score) else (self.score_create(model), True)
+        return Score.create(self, model)
 
     def _kept_outputs(self, dev, n_texts, kept_capacity):
         import torch
-        kept_ptr = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev)
+        kept_ptr = _i64(n_texts + 1, dev)
         kept_class = torch.zeros(kept_capacity, dtype=torch.int32, device=dev) if kept_capacity else None
-        kept_score = torch.zeros(kept_capacity, dtype=torch.int64, device=dev) if kept_capacity else None
+        kept_score = _i64(kept_capacity, dev) if kept_capacity else None
         best = torch.full((max(n_texts, 1),), -1, dtype=torch.int32, device=dev)[:n_texts] if kept_capacity else None
         return kept_ptr, kept_class, kept_score, best
 
@@ -3487,74 +3374,45 @@ class Plan:
         `model` is a Score from score_create() (or a ScoreModel / a list of score_class()es, compiled for
         this call).  kept_capacity: the room of the kept arrays (0: count only; None: counted first, then
         sized by the count).  Returns a Scored of device tensors; synchronises to read its four numbers."""
-        import torch
-        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-        n_symbols = text.numel() * text.element_size() // self.sym_size
-        n_texts = offsets.numel() - 1
-        assert n_texts >= 0
-        window = int(window) if window is not None else 1 << 24
-        capacity = int(capacity) if capacity is not None else 1 << 20
-        pair_capacity = int(pair_capacity) if pair_capacity is not None else capacity
+        n_symbols, n_texts = self._batch_args(text, offsets)
+        window, capacity, pair_capacity = self._windows(window, capacity, pair_capacity)
         k = int(k)
         dev = text.device
-        S, own = self._score_handle(model)
-        res = torch.zeros(4, dtype=torch.int64, device=dev)                      # n_kept, total, need, need_pairs
+        with Score.for_call(self, model) as S:
+            res = _i64(4, dev)                                                   # n_kept, total, need, need_pairs
 
-        def call(cap):
-            tb = lib().acm_gpu_score_tmp_bytes(self.h, S.h, window, capacity, pair_capacity, n_symbols, n_texts, cap, k)
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
-            kept_ptr, kept_class, kept_score, best = self._kept_outputs(dev, n_texts, cap)
-            hits, top_n, top_text, top_score = self._top_outputs(dev, S.n_classes, k) if k and cap else (None, None, None, None)
-
-            def p(x):
-                return x.data_ptr() if x is not None and x.numel() else None
-            _check(lib().acm_gpu_score_device(self.h, S.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity,
-                                              kept_ptr.data_ptr(), p(kept_class), p(kept_score), cap, res.data_ptr(), p(best), k if hits is not None else 0,
-                                              p(hits), p(top_n), p(top_text), p(top_score), res.data_ptr() + 8, res.data_ptr() + 16, res.data_ptr() + 24,
-                                              tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_score_device")
-            n_kept, total, need, need_pairs = (int(x) for x in res.cpu())
-            return Scored(kept_ptr, kept_class, kept_score, n_kept, best, hits, top_n, top_text, top_score, total, need, need_pairs, cap)
-        try:
-            got = call(int(kept_capacity) if kept_capacity is not None else 0)
-            if kept_capacity is None and got.n_kept:
-                got = call(got.n_kept)
-            return got
-        finally:
-            if own:
-                S.close()
+            def call(cap):
+                tmp = _scratch(lib().acm_gpu_score_tmp_bytes(self.h, S.h, window, capacity, pair_capacity, n_symbols, n_texts, cap, k), dev)
+                kept_ptr, kept_class, kept_score, best = self._kept_outputs(dev, n_texts, cap)
+                hits, top_n, top_text, top_score = self._top_outputs(dev, S.n_classes, k) if k and cap else (None, None, None, None)
+                p = _opt_full
+                _check(lib().acm_gpu_score_device(self.h, S.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity,
+                                                  kept_ptr.data_ptr(), p(kept_class), p(kept_score), cap, res.data_ptr(), p(best),
+                                                  k if hits is not None else 0, p(hits), p(top_n), p(top_text), p(top_score), res.data_ptr() + 8,
+                                                  res.data_ptr() + 16, res.data_ptr() + 24, tmp.data_ptr(), tmp.numel(), self._stream()),
+                       "acm_gpu_score_device")
+                n_kept, total, need, need_pairs = (int(x) for x in res.cpu())
+                return Scored(kept_ptr, kept_class, kept_score, n_kept, best, hits, top_n, top_text, top_score, total, need, need_pairs, cap)
+            return _counted(call, kept_capacity, "n_kept")
 
     def score_matrix(self, tallied, model, kept_capacity=None):
         """acm_gpu_score_matrix_device(): the evaluation for a count matrix that lies on the device:
         `tallied` is a TalliedBatch of device tensors, tally_batch()'s or the caller's own (row_ptr int64
         with n_texts + 1 entries, col int32, val int64).  Returns a Scored of device tensors (no top
         arrays: score_top(); total, need and need_pairs None); synchronises to read n_kept."""
-        import torch
-        row_ptr, col, val = tallied.row_ptr, tallied.col, tallied.val
-        assert row_ptr.is_cuda and row_ptr.is_contiguous() and row_ptr.dtype == torch.int64
-        assert col.is_contiguous() and col.dtype == torch.int32 and val.is_contiguous() and val.dtype == torch.int64
-        n_texts = row_ptr.numel() - 1
-        assert n_texts >= 0
+        row_ptr, col, val, n_texts = self._matrix_args(tallied)
         dev = row_ptr.device
-        S, own = self._score_handle(model)
-        res = torch.zeros(1, dtype=torch.int64, device=dev)
-        tb = lib().acm_gpu_score_matrix_tmp_bytes(self.h, S.h, n_texts)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        with Score.for_call(self, model) as S:
+            res = _i64(1, dev)
+            tmp = _scratch(lib().acm_gpu_score_matrix_tmp_bytes(self.h, S.h, n_texts), dev)
 
-        def call(cap):
-            kept_ptr, kept_class, kept_score, best = self._kept_outputs(dev, n_texts, cap)
-            _check(lib().acm_gpu_score_matrix_device(self.h, S.h, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), n_texts, kept_ptr.data_ptr(),
-                                                     kept_class.data_ptr() if cap else None, kept_score.data_ptr() if cap else None, cap, res.data_ptr(),
-                                                     best.data_ptr() if cap and n_texts else None, tmp.data_ptr(), tmp.numel(), self._stream()),
-                   "acm_gpu_score_matrix_device")
-            return Scored(kept_ptr, kept_class, kept_score, int(res.item()), best, kept_capacity=cap)
-        try:
-            got = call(int(kept_capacity) if kept_capacity is not None else 0)
-            if kept_capacity is None and got.n_kept:
-                got = call(got.n_kept)
-            return got
-        finally:
-            if own:
-                S.close()
+            def call(cap):
+                kept_ptr, kept_class, kept_score, best = self._kept_outputs(dev, n_texts, cap)
+                _check(lib().acm_gpu_score_matrix_device(self.h, S.h, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), n_texts, kept_ptr.data_ptr(),
+                                                         _opt(kept_class), _opt(kept_score), cap, res.data_ptr(), _opt_full(best), tmp.data_ptr(),
+                                                         tmp.numel(), self._stream()), "acm_gpu_score_matrix_device")
+                return Scored(kept_ptr, kept_class, kept_score, int(res.item()), best, kept_capacity=cap)
+            return _counted(call, kept_capacity, "n_kept")
 
     def score_top(self, scored, n_classes, k):
         """acm_gpu_score_top_device(): TOP of a Scored of device tensors; returns it with class_hits, top_n, top_text and
@@ -3566,11 +3424,8 @@ class Plan:
         dev = kept_ptr.device
         cap = int(scored.kept_class.numel()) if scored.kept_class is not None else 0
         hits, top_n, top_text, top_score = self._top_outputs(dev, n_classes, k)
-        tb = lib().acm_gpu_score_top_tmp_bytes(self.h, cap, n_classes)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
-
-        def p(x):
-            return x.data_ptr() if x is not None and x.numel() else None
+        tmp = _scratch(lib().acm_gpu_score_top_tmp_bytes(self.h, cap, n_classes), dev)
+        p = _opt_full
         _check(lib().acm_gpu_score_top_device(self.h, kept_ptr.data_ptr(), p(scored.kept_class), p(scored.kept_score), cap, kept_ptr.numel() - 1, n_classes,
                                               k, p(hits), p(top_n), p(top_text), p(top_score), tmp.data_ptr(), tmp.numel(), self._stream()),
                "acm_gpu_score_top_device")
@@ -3591,10 +3446,8 @@ class Plan:
 
     def _post_outputs(self, dev, n_keywords, post_capacity):
         import torch
-        post_ptr = torch.zeros(n_keywords + 1, dtype=torch.int64, device=dev)
         post_text = torch.zeros(post_capacity, dtype=torch.int32, device=dev) if post_capacity else None
-        post_count = torch.zeros(post_capacity, dtype=torch.int64, device=dev) if post_capacity else None
-        return post_ptr, post_text, post_count
+        return _i64(n_keywords + 1, dev), post_text, _i64(post_capacity, dev) if post_capacity else None
 
     def index(self, text, offsets, n_keywords=None, text_base=0, window=None, capacity=None, pair_capacity=None, post_capacity=None):
         """acm_gpu_index_device(): the inverted index of a batch on the device: the tally of tally_batch()
@@ -3603,63 +3456,42 @@ class Plan:
         plan's) may be larger; text ids start at text_base.  post_capacity: the room of post_text and
         post_count (0: count only, which gives post_ptr and so df; None: counted first, then sized by
         the count).  Returns an Indexed of device tensors; synchronises to read its four numbers."""
-        import torch
-        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-        n_symbols = text.numel() * text.element_size() // self.sym_size
-        n_texts = offsets.numel() - 1
-        assert n_texts >= 0
-        window = int(window) if window is not None else 1 << 24
-        capacity = int(capacity) if capacity is not None else 1 << 20
-        pair_capacity = int(pair_capacity) if pair_capacity is not None else capacity
+        n_symbols, n_texts = self._batch_args(text, offsets)
+        window, capacity, pair_capacity = self._windows(window, capacity, pair_capacity)
         nk = self._index_keywords(n_keywords)
         dev = text.device
-        res = torch.zeros(6, dtype=torch.int64, device=dev)                      # nnz, total, need, need_pairs, forms[2]
+        res = _i64(6, dev)                                                       # nnz, total, need, need_pairs, forms[2]
 
         def call(cap):
-            tb = lib().acm_gpu_index_tmp_bytes(self.h, window, capacity, pair_capacity, n_symbols, n_texts, nk, cap)
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+            tmp = _scratch(lib().acm_gpu_index_tmp_bytes(self.h, window, capacity, pair_capacity, n_symbols, n_texts, nk, cap), dev)
             post_ptr, post_text, post_count = self._post_outputs(dev, nk, cap)
-            p = (lambda x: x.data_ptr() if x is not None else None)
             _check(lib().acm_gpu_index_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity, nk,
-                                              int(text_base), post_ptr.data_ptr(), p(post_text), p(post_count), cap, res.data_ptr(), res.data_ptr() + 32,
-                                              res.data_ptr() + 8, res.data_ptr() + 16, res.data_ptr() + 24, tmp.data_ptr(), tmp.numel(), self._stream()),
-                   "acm_gpu_index_device")
+                                              int(text_base), post_ptr.data_ptr(), _opt(post_text), _opt(post_count), cap, res.data_ptr(),
+                                              res.data_ptr() + 32, res.data_ptr() + 8, res.data_ptr() + 16, res.data_ptr() + 24, tmp.data_ptr(),
+                                              tmp.numel(), self._stream()), "acm_gpu_index_device")
             nnz, total, need, need_pairs, fast, wide = (int(x) for x in res.cpu())
             return Indexed(post_ptr, post_text, post_count, nnz, total, int(text_base), need, need_pairs, cap, (fast, wide))
-        got = call(int(post_capacity) if post_capacity is not None else 0)
-        if post_capacity is None and got.nnz:
-            got = call(got.nnz)
-        return got
+        return _counted(call, post_capacity, "nnz")
 
     def index_matrix(self, tallied, n_keywords=None, text_base=0, post_capacity=None):
         """acm_gpu_index_matrix_device(): the transposition of a count matrix that lies on the device:
         `tallied` is a TalliedBatch of device tensors, tally_batch()'s or the caller's own (row_ptr int64
         with n_texts + 1 entries, col int32, val int64).  Returns an Indexed of device tensors (total,
         need and need_pairs None); synchronises to read nnz."""
-        import torch
-        row_ptr, col, val = tallied.row_ptr, tallied.col, tallied.val
-        assert row_ptr.is_cuda and row_ptr.is_contiguous() and row_ptr.dtype == torch.int64
-        assert col.is_contiguous() and col.dtype == torch.int32 and val.is_contiguous() and val.dtype == torch.int64
-        n_texts = row_ptr.numel() - 1
-        assert n_texts >= 0
+        row_ptr, col, val, n_texts = self._matrix_args(tallied)
         nk = self._index_keywords(n_keywords)
         dev = row_ptr.device
-        res = torch.zeros(3, dtype=torch.int64, device=dev)                      # nnz, forms[2]
+        res = _i64(3, dev)                                                       # nnz, forms[2]
 
         def call(cap):
-            tb = lib().acm_gpu_index_matrix_tmp_bytes(self.h, n_texts, nk, cap)
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+            tmp = _scratch(lib().acm_gpu_index_matrix_tmp_bytes(self.h, n_texts, nk, cap), dev)
             post_ptr, post_text, post_count = self._post_outputs(dev, nk, cap)
-            p = (lambda x: x.data_ptr() if x is not None else None)
             _check(lib().acm_gpu_index_matrix_device(self.h, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), n_texts, nk, int(text_base),
-                                                     post_ptr.data_ptr(), p(post_text), p(post_count), cap, res.data_ptr(), res.data_ptr() + 8,
+                                                     post_ptr.data_ptr(), _opt(post_text), _opt(post_count), cap, res.data_ptr(), res.data_ptr() + 8,
                                                      tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_index_matrix_device")
             nnz, fast, wide = (int(x) for x in res.cpu())
             return Indexed(post_ptr, post_text, post_count, nnz, None, int(text_base), post_capacity=cap, forms=(fast, wide))
-        got = call(int(post_capacity) if post_capacity is not None else 0)
-        if post_capacity is None and got.nnz:
-            got = call(got.nnz)
-        return got
+        return _counted(call, post_capacity, "nnz")
 
     def index_concat(self, a, b, out_capacity=None):
         """acm_gpu_index_concat_device(): per keyword a's list, then b's, for two Indexed of device
@@ -3671,11 +3503,10 @@ class Plan:
             assert x.post_ptr.is_cuda and x.post_ptr.is_contiguous() and x.post_ptr.dtype == torch.int64
         nka, nkb = a.n_keywords, b.n_keywords
         cap = int(out_capacity) if out_capacity is not None else int(a.nnz) + int(b.nnz)
-        res = torch.zeros(1, dtype=torch.int64, device=dev)
-        tb = lib().acm_gpu_index_concat_tmp_bytes(self.h, nkb)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
+        res = _i64(1, dev)
+        tmp = _scratch(lib().acm_gpu_index_concat_tmp_bytes(self.h, nkb), dev)
         out_ptr, out_text, out_count = self._post_outputs(dev, nkb, cap)
-        p = (lambda x: x.data_ptr() if x is not None else None)
+        p = _opt
         _check(lib().acm_gpu_index_concat_device(self.h, a.post_ptr.data_ptr(), p(a.post_text), p(a.post_count), nka, b.post_ptr.data_ptr(),
                                                  p(b.post_text), p(b.post_count), nkb, out_ptr.data_ptr(), p(out_text), p(out_count), cap,
                                                  res.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_index_concat_device")
@@ -3693,14 +3524,7 @@ class Plan:
     def patterns_create(self, patternset):
         """acm_gpu_patterns_create(): `patternset` (a PatternSet, or lists of (keyword_id, offset, length)
         terms) compiled and uploaded to this plan's device.  Returns a Patterns; it stays valid across update()."""
-        ps = _patternset(patternset)
-        h = C.c_void_p()
-        _check(lib().acm_gpu_patterns_create(self.h, *ps.args(), C.byref(h)), "acm_gpu_patterns_create")
-        return Patterns(h, ps.n_patterns)
-
-    def _patterns_handle(self, patterns):
-        """(a Patterns, whether this call made it) of a Patterns, a PatternSet or lists of terms"""
-        return (patterns, False) if isinstance(patterns, Patterns) else (self.patterns_create(patterns), True)
+        return Patterns.create(self, patternset)
 
     def patterns_records(self, records, n, patterns, n_symbols, offsets=None, pos_base=0, count=None, out=None, out_capacity=None, out_count=None):
         """acm_gpu_patterns_records_device(): the matches of `patterns` (a Patterns from patterns_create(), or a
@@ -3711,32 +3535,30 @@ class Plan:
         `offsets` is a device int64 tensor of n_texts + 1 entries.  Returns (out, out_count): out_count (a
         device tensor) holds the number of matches; above out_capacity it is the capacity needed.  Nothing
         is synchronised."""
+        return self._terms_records(Patterns, records, n, patterns, n_symbols, offsets, pos_base, count, out, out_capacity, out_count)
+
+    def _terms_records(self, family, records, n, given, n_symbols, offsets, pos_base, count, out, out_capacity, out_count):
+        """what patterns_records() and chains_records() share, `family` being Patterns or Chains: acm_gpu_<family>_tmp_bytes
+        and acm_gpu_<family>_records_device"""
         import torch
         assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
         n = int(n)
-        P, own = self._patterns_handle(patterns)
-        try:
+        call = "acm_gpu_%s_records_device" % family.STEM
+        with family.for_call(self, given, sync=True) as S:
             if out_capacity is None:
-                out_capacity = out.shape[0] if out is not None else n * P.info()["max_anchor_postings"]
+                out_capacity = out.shape[0] if out is not None else n * S.info()[family.MOST]
             out_capacity = int(out_capacity)
             if out is None:
                 out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=records.device)
             assert out.is_cuda and out.is_contiguous() and out.shape[0] >= out_capacity
             if out_count is None:
-                out_count = torch.zeros(1, dtype=torch.int64, device=records.device)
-            n_texts = offsets.numel() - 1 if offsets is not None else 0
-            tb = lib().acm_gpu_patterns_tmp_bytes(self.h, P.h, n, n_texts)
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
-            _check(lib().acm_gpu_patterns_records_device(self.h, P.h, records.data_ptr(), n, count.data_ptr() if count is not None else None,
-                                                         int(n_symbols), int(pos_base), offsets.data_ptr() if offsets is not None else None, n_texts,
-                                                         out.data_ptr() if out_capacity else None, out_capacity, out_count.data_ptr(),
-                                                         tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_patterns_records_device")
-            if own:
-                torch.cuda.current_stream().synchronize()          # the set goes away with this call
+                out_count = _i64(1, records.device)
+            off_ptr, n_texts = _cut(offsets)
+            tmp = _scratch(getattr(lib(), "acm_gpu_%s_tmp_bytes" % family.STEM)(self.h, S.h, n, n_texts), records.device)
+            _check(getattr(lib(), call)(self.h, S.h, records.data_ptr(), n, _opt(count), int(n_symbols), int(pos_base), off_ptr, n_texts,
+                                        out.data_ptr() if out_capacity else None, out_capacity, out_count.data_ptr(), tmp.data_ptr(), tmp.numel(),
+                                        self._stream()), call)
             return out, out_count
-        finally:
-            if own:
-                P.close()
 
     def scan_patterns(self, text, patterns, offsets=None, n_symbols=None, pos_base=0, capacity=None, out=None, out_capacity=None, tmp=None):
         """acm_gpu_scan_patterns_device(): the ordered scan of a device tensor into `capacity` records of the
@@ -3744,65 +3566,38 @@ class Plan:
         count, found, tmp) with count and found device tensors: out[:count] are the matches when count <=
         out_capacity; found is the scan's count -- above `capacity` there is no match (count 0) and found
         is a capacity that suffices."""
+        return self._scan_terms(Patterns, text, patterns, offsets, n_symbols, pos_base, capacity, out, out_capacity, tmp)
+
+    def _scan_terms(self, family, text, given, offsets, n_symbols, pos_base, capacity, out, out_capacity, tmp):
+        """what scan_patterns() and scan_chains() share, `family` being Patterns or Chains: acm_gpu_scan_<family>_tmp_bytes
+        and acm_gpu_scan_<family>_device"""
         import torch
-        assert text.is_cuda and text.is_contiguous()
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_symbols = self._text_args(text, n_symbols)
+        call = "acm_gpu_scan_%s_device" % family.STEM
         capacity = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
-        P, own = self._patterns_handle(patterns)
-        try:
+        with family.for_call(self, given, sync=True) as S:
             if out_capacity is None:
-                out_capacity = out.shape[0] if out is not None else capacity * P.info()["max_anchor_postings"]
+                out_capacity = out.shape[0] if out is not None else capacity * S.info()[family.MOST]
             out_capacity = int(out_capacity)
             if out is None:
                 out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=text.device)
-            res = torch.zeros(2, dtype=torch.int64, device=text.device)
-            n_texts = offsets.numel() - 1 if offsets is not None else 0
-            tb = lib().acm_gpu_scan_patterns_tmp_bytes(self.h, P.h, capacity, n_symbols, n_texts)
-            if tmp is None or tmp.numel() < tb:
-                tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-            _check(lib().acm_gpu_scan_patterns_device(self.h, P.h, text.data_ptr(), n_symbols, int(pos_base),
-                                                      offsets.data_ptr() if offsets is not None else None, n_texts, capacity,
-                                                      out.data_ptr() if out_capacity else None, out_capacity, res.data_ptr(), res.data_ptr() + 8,
-                                                      tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_scan_patterns_device")
-            if own:
-                torch.cuda.current_stream().synchronize()          # the set goes away with this call
+            res = _i64(2, text.device)
+            off_ptr, n_texts = _cut(offsets)
+            tmp = _scratch(getattr(lib(), "acm_gpu_scan_%s_tmp_bytes" % family.STEM)(self.h, S.h, capacity, n_symbols, n_texts), text.device, tmp)
+            _check(getattr(lib(), call)(self.h, S.h, text.data_ptr(), n_symbols, int(pos_base), off_ptr, n_texts, capacity,
+                                        out.data_ptr() if out_capacity else None, out_capacity, res.data_ptr(), res.data_ptr() + 8,
+                                        tmp.data_ptr(), tmp.numel(), self._stream()), call)
             return out, res[0:1], res[1:2], tmp
-        finally:
-            if own:
-                P.close()
 
     def scan_patterns_host(self, text, patternset, offsets=None, pos_base=0, out_capacity=None):
         """acm_gpu_scan_patterns_host(): numpy in, the pattern matches out, through the C ABI only (no torch); an
         overflow is repeated once with the size the call reports."""
-        t = np.ascontiguousarray(text)
-        n_sym = t.size * t.itemsize // self.sym_size
-        ps = _patternset(patternset)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        cap = int(out_capacity) if out_capacity is not None else 1024
-        for attempt in (0, 1):
-            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = lib().acm_gpu_scan_patterns_host(self.h, t.ctypes.data if t.size else None, n_sym, int(pos_base),
-                                                  off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *ps.args(),
-                                                  out.ctypes.data if cap else None, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_gpu_scan_patterns_host")
-            return out[:n.value]
+        return self._scan_set_host("acm_gpu_scan_patterns_host", text, _patternset(patternset), offsets, pos_base, out_capacity, extra=())[0]
 
     def chains_create(self, chainset):
         """acm_gpu_chains_create(): `chainset` (a ChainSet, or lists of (keyword_id, gap_min, gap_max) terms)
         compiled and uploaded to this plan's device.  Returns a Chains; it stays valid across update()."""
-        cs = _chainset(chainset)
-        h = C.c_void_p()
-        _check(lib().acm_gpu_chains_create(self.h, *cs.args(), C.byref(h)), "acm_gpu_chains_create")
-        return Chains(h, cs.n_chains)
-
-    def _chains_handle(self, chains):
-        """(a Chains, whether this call made it) of a Chains, a ChainSet or lists of terms"""
-        return (chains, False) if isinstance(chains, Chains) else (self.chains_create(chains), True)
+        return Chains.create(self, chainset)
 
     def chains_records(self, records, n, chains, n_symbols, offsets=None, pos_base=0, count=None, out=None, out_capacity=None, out_count=None):
         """acm_gpu_chains_records_device(): the matches of `chains` (a Chains from chains_create(), or a
@@ -3813,32 +3608,7 @@ class Plan:
         `offsets` is a device int64 tensor of n_texts + 1 entries.  Returns (out, out_count): out_count (a
         device tensor) holds the number of matches; above out_capacity it is the capacity needed.  Nothing
         is synchronised."""
-        import torch
-        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
-        n = int(n)
-        S, own = self._chains_handle(chains)
-        try:
-            if out_capacity is None:
-                out_capacity = out.shape[0] if out is not None else n * S.info()["max_last_postings"]
-            out_capacity = int(out_capacity)
-            if out is None:
-                out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=records.device)
-            assert out.is_cuda and out.is_contiguous() and out.shape[0] >= out_capacity
-            if out_count is None:
-                out_count = torch.zeros(1, dtype=torch.int64, device=records.device)
-            n_texts = offsets.numel() - 1 if offsets is not None else 0
-            tb = lib().acm_gpu_chains_tmp_bytes(self.h, S.h, n, n_texts)
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
-            _check(lib().acm_gpu_chains_records_device(self.h, S.h, records.data_ptr(), n, count.data_ptr() if count is not None else None,
-                                                       int(n_symbols), int(pos_base), offsets.data_ptr() if offsets is not None else None, n_texts,
-                                                       out.data_ptr() if out_capacity else None, out_capacity, out_count.data_ptr(),
-                                                       tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_chains_records_device")
-            if own:
-                torch.cuda.current_stream().synchronize()          # the set goes away with this call
-            return out, out_count
-        finally:
-            if own:
-                S.close()
+        return self._terms_records(Chains, records, n, chains, n_symbols, offsets, pos_base, count, out, out_capacity, out_count)
 
     def scan_chains(self, text, chains, offsets=None, n_symbols=None, pos_base=0, capacity=None, out=None, out_capacity=None, tmp=None):
         """acm_gpu_scan_chains_device(): the ordered scan of a device tensor into `capacity` records of the
@@ -3846,75 +3616,29 @@ class Plan:
         count, found, tmp) with count and found device tensors: out[:count] are the matches when count <=
         out_capacity; found is the scan's count -- above `capacity` there is no match (count 0) and found
         is a capacity that suffices."""
-        import torch
-        assert text.is_cuda and text.is_contiguous()
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
-        capacity = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
-        S, own = self._chains_handle(chains)
-        try:
-            if out_capacity is None:
-                out_capacity = out.shape[0] if out is not None else capacity * S.info()["max_last_postings"]
-            out_capacity = int(out_capacity)
-            if out is None:
-                out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=text.device)
-            res = torch.zeros(2, dtype=torch.int64, device=text.device)
-            n_texts = offsets.numel() - 1 if offsets is not None else 0
-            tb = lib().acm_gpu_scan_chains_tmp_bytes(self.h, S.h, capacity, n_symbols, n_texts)
-            if tmp is None or tmp.numel() < tb:
-                tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-            _check(lib().acm_gpu_scan_chains_device(self.h, S.h, text.data_ptr(), n_symbols, int(pos_base),
-                                                    offsets.data_ptr() if offsets is not None else None, n_texts, capacity,
-                                                    out.data_ptr() if out_capacity else None, out_capacity, res.data_ptr(), res.data_ptr() + 8,
-                                                    tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_scan_chains_device")
-            if own:
-                torch.cuda.current_stream().synchronize()          # the set goes away with this call
-            return out, res[0:1], res[1:2], tmp
-        finally:
-            if own:
-                S.close()
+        return self._scan_terms(Chains, text, chains, offsets, n_symbols, pos_base, capacity, out, out_capacity, tmp)
 
     def scan_chains_host(self, text, chainset, offsets=None, pos_base=0, out_capacity=None):
         """acm_gpu_scan_chains_host(): numpy in, the chain matches out, through the C ABI only (no torch); an
         overflow is repeated once with the size the call reports."""
-        t = np.ascontiguousarray(text)
-        n_sym = t.size * t.itemsize // self.sym_size
-        cs = _chainset(chainset)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        cap = int(out_capacity) if out_capacity is not None else 1024
-        for attempt in (0, 1):
-            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = lib().acm_gpu_scan_chains_host(self.h, t.ctypes.data if t.size else None, n_sym, int(pos_base),
-                                                off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *cs.args(),
-                                                out.ctypes.data if cap else None, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_gpu_scan_chains_host")
-            return out[:n.value]
+        return self._scan_set_host("acm_gpu_scan_chains_host", text, _chainset(chainset), offsets, pos_base, out_capacity, extra=())[0]
 
     def approx_create(self, approxset):
         """acm_gpu_approx_create(): `approxset` (an ApproxSet) compiled and uploaded to this plan's device.
         Returns an Approx; it stays valid across update().  A plan over comparator classes refuses
         (ACM_GPU_E_INELIGIBLE)."""
-        h = C.c_void_p()
-        _check(lib().acm_gpu_approx_create(self.h, *approxset.args(), C.byref(h)), "acm_gpu_approx_create")
-        return Approx(h, approxset.n_targets)
+        return Approx.create(self, approxset)
 
     def templates_create(self, templateset):
         """acm_gpu_templates_create(): `templateset` (a TemplateSet) compiled and uploaded to this plan's device.
         Returns a Templates; it stays valid across update().  A plan over comparator classes refuses
         (ACM_GPU_E_INELIGIBLE)."""
-        h = C.c_void_p()
-        _check(lib().acm_gpu_templates_create(self.h, *templateset.args(), C.byref(h)), "acm_gpu_templates_create")
-        return Templates(h, templateset.n_templates)
+        return Templates.create(self, templateset)
 
-    def _approx_handle(self, approx):
-        """(an Approx or a Templates, whether this call made it) of one of the two, of an ApproxSet or of a TemplateSet"""
-        if isinstance(approx, Approx):
-            return approx, False
-        return (self.templates_create(approx) if isinstance(approx, TemplateSet) else self.approx_create(approx)), True
+    def _approx_for_call(self, approx):
+        """the Approx or Templates of one call: `approx` itself, or an ApproxSet or a TemplateSet compiled for it (an
+        Approx is what the calls take; a Templates is one)"""
+        return (Templates if isinstance(approx, TemplateSet) else Approx).for_call(self, approx, sync=True)
 
     def templates_records(self, records, n, templates, text, n_symbols=None, offsets=None, pos_base=0, count=None, out=None, dist=None,
                           out_capacity=None, out_count=None):
@@ -3961,13 +3685,10 @@ class Plan:
         """what approx_records() and edit_records() share: acm_gpu_<metric>_tmp_bytes and acm_gpu_<metric>_records_device"""
         import torch
         assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
-        assert text.is_cuda and text.is_contiguous()
         n = int(n)
         call = "acm_gpu_%s_records_device" % metric
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
-        A, own = self._approx_handle(approx)
-        try:
+        n_symbols = self._text_args(text, n_symbols)
+        with self._approx_for_call(approx) as A:
             if out_capacity is None:
                 out_capacity = out.shape[0] if out is not None else n * self._most_per_record(metric, A.info())
             out_capacity = int(out_capacity)
@@ -3977,20 +3698,13 @@ class Plan:
                 dist = torch.empty(max(out_capacity, 1), dtype=torch.int32, device=records.device)
             assert out.is_cuda and out.is_contiguous() and out.shape[0] >= out_capacity and dist.is_cuda and dist.numel() >= out_capacity
             if out_count is None:
-                out_count = torch.zeros(1, dtype=torch.int64, device=records.device)
-            n_texts = offsets.numel() - 1 if offsets is not None else 0
-            tb = getattr(lib(), "acm_gpu_%s_tmp_bytes" % metric)(self.h, A.h, n, out_capacity, n_texts)
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
-            _check(getattr(lib(), call)(self.h, A.h, records.data_ptr(), n, count.data_ptr() if count is not None else None,
-                                        text.data_ptr(), int(n_symbols), int(pos_base), offsets.data_ptr() if offsets is not None else None,
+                out_count = _i64(1, records.device)
+            off_ptr, n_texts = _cut(offsets)
+            tmp = _scratch(getattr(lib(), "acm_gpu_%s_tmp_bytes" % metric)(self.h, A.h, n, out_capacity, n_texts), records.device)
+            _check(getattr(lib(), call)(self.h, A.h, records.data_ptr(), n, _opt(count), text.data_ptr(), int(n_symbols), int(pos_base), off_ptr,
                                         n_texts, out.data_ptr() if out_capacity else None, dist.data_ptr(), out_capacity,
                                         out_count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), call)
-            if own:
-                torch.cuda.current_stream().synchronize()          # the set goes away with this call
             return out, dist, out_count
-        finally:
-            if own:
-                A.close()
 
     def scan_approx(self, text, approx, offsets=None, n_symbols=None, pos_base=0, capacity=None, out=None, dist=None, out_capacity=None, tmp=None):
         """acm_gpu_scan_approx_device(): the ordered scan of a device tensor into `capacity` records of the call's
@@ -4008,13 +3722,10 @@ class Plan:
     def _scan_set(self, metric, text, approx, offsets, n_symbols, pos_base, capacity, out, dist, out_capacity, tmp):
         """what scan_approx() and scan_edit() share: acm_gpu_scan_<metric>_tmp_bytes and acm_gpu_scan_<metric>_device"""
         import torch
-        assert text.is_cuda and text.is_contiguous()
         call = "acm_gpu_scan_%s_device" % metric
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_symbols = self._text_args(text, n_symbols)
         capacity = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
-        A, own = self._approx_handle(approx)
-        try:
+        with self._approx_for_call(approx) as A:
             if out_capacity is None:
                 out_capacity = out.shape[0] if out is not None else capacity * self._most_per_record(metric, A.info())
             out_capacity = int(out_capacity)
@@ -4022,21 +3733,13 @@ class Plan:
                 out = torch.empty((max(out_capacity, 1), 2), dtype=torch.int64, device=text.device)
             if dist is None:
                 dist = torch.empty(max(out_capacity, 1), dtype=torch.int32, device=text.device)
-            res = torch.zeros(2, dtype=torch.int64, device=text.device)
-            n_texts = offsets.numel() - 1 if offsets is not None else 0
-            tb = getattr(lib(), "acm_gpu_scan_%s_tmp_bytes" % metric)(self.h, A.h, capacity, out_capacity, n_symbols, n_texts)
-            if tmp is None or tmp.numel() < tb:
-                tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-            _check(getattr(lib(), call)(self.h, A.h, text.data_ptr(), n_symbols, int(pos_base),
-                                        offsets.data_ptr() if offsets is not None else None, n_texts, capacity,
+            res = _i64(2, text.device)
+            off_ptr, n_texts = _cut(offsets)
+            tmp = _scratch(getattr(lib(), "acm_gpu_scan_%s_tmp_bytes" % metric)(self.h, A.h, capacity, out_capacity, n_symbols, n_texts), text.device, tmp)
+            _check(getattr(lib(), call)(self.h, A.h, text.data_ptr(), n_symbols, int(pos_base), off_ptr, n_texts, capacity,
                                         out.data_ptr() if out_capacity else None, dist.data_ptr(), out_capacity, res.data_ptr(),
                                         res.data_ptr() + 8, tmp.data_ptr(), tmp.numel(), self._stream()), call)
-            if own:
-                torch.cuda.current_stream().synchronize()          # the set goes away with this call
             return out, dist, res[0:1], res[1:2], tmp
-        finally:
-            if own:
-                A.close()
 
     def scan_approx_host(self, text, approxset, offsets=None, pos_base=0, out_capacity=None):
         """acm_gpu_scan_approx_host(): numpy in, (matches, dist) out, through the C ABI only (no torch); an overflow
@@ -4047,24 +3750,13 @@ class Plan:
         """acm_gpu_scan_edit_host(): numpy in, (matches, dist) within edit distance k out; arguments as scan_approx_host()."""
         return self._scan_set_host("acm_gpu_scan_edit_host", text, approxset, offsets, pos_base, out_capacity)
 
-    def _scan_set_host(self, name, text, approxset, offsets, pos_base, out_capacity):
-        """what scan_approx_host() and scan_edit_host() share: the blocking C call `name`"""
+    def _scan_set_host(self, name, text, tset, offsets, pos_base, out_capacity, extra=(np.uint32,)):
+        """what the host scans for the sets of a family share -- patterns and chains, and with a distance per match
+        (`extra`) approx, edit and templates --: the blocking C call `name`"""
         t = np.ascontiguousarray(text)
         n_sym = t.size * t.itemsize // self.sym_size
         off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        cap = int(out_capacity) if out_capacity is not None else 1024
-        for attempt in (0, 1):
-            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
-            dist = np.zeros(max(cap, 1), dtype=np.uint32)
-            n = C.c_uint64(0)
-            rc = getattr(lib(), name)(self.h, t.ctypes.data if t.size else None, n_sym, int(pos_base),
-                                      off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0, *approxset.args(),
-                                      out.ctypes.data if cap else None, dist.ctypes.data, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, name)
-            return out[:n.value], dist[:n.value]
+        return _matches_host_call(getattr(lib(), name), name, (self.h, _ptr(t), n_sym, int(pos_base), *_cut(off), *tset.args()), out_capacity, extra)
 
     @property
     def select_form(self):
@@ -4083,9 +3775,8 @@ class Plan:
         if out is None:
             out = torch.empty((max(n, 1), 2), dtype=torch.int64, device=records.device)
         assert out.is_cuda and out.is_contiguous() and out.shape[0] >= n and records.shape[0] >= n
-        count = torch.zeros(1, dtype=torch.int64, device=records.device)
-        tb = lib().acm_gpu_select_tmp_bytes(self.h, n, span)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
+        count = _i64(1, records.device)
+        tmp = _scratch(lib().acm_gpu_select_tmp_bytes(self.h, n, span), records.device)
         _check(lib().acm_gpu_select_records_device(self.h, records.data_ptr(), n, None, pos_lo, span, out.data_ptr(), count.data_ptr(),
                                                    tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_select_records_device")
         return out, int(count.item())
@@ -4095,18 +3786,9 @@ class Plan:
         selection of its records, queued on the current stream.  Returns (records, count, tmp):
         records[:count] is the selection when count <= capacity; a greater count is the number of ALL
         matches, the capacity the call needs."""
-        import torch
-        assert text.is_cuda and text.is_contiguous()
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
-        if records is None:
-            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
-            records = torch.empty((cap, 2), dtype=torch.int64, device=text.device)
-        if count is None:
-            count = torch.zeros(1, dtype=torch.int64, device=text.device)
-        tb = lib().acm_gpu_scan_select_tmp_bytes(self.h, records.shape[0], n_symbols)
-        if tmp is None or tmp.numel() < tb:
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        n_symbols = self._text_args(text, n_symbols)
+        records, count = self._records_out(records, count, capacity, n_symbols, text.device)
+        tmp = _scratch(lib().acm_gpu_scan_select_tmp_bytes(self.h, records.shape[0], n_symbols), text.device, tmp)
         _check(lib().acm_gpu_scan_select_device(self.h, text.data_ptr(), n_symbols, pos_base, records.data_ptr(), records.shape[0],
                                                 count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
                "acm_gpu_scan_select_device")
@@ -4126,12 +3808,11 @@ class Plan:
         if out is None:
             out = torch.empty((max(room, 1), 2), dtype=torch.int64, device=records.device)
         assert out.is_cuda and out.is_contiguous() and out.shape[0] >= room and records.shape[0] >= room
-        d_count = count if count is not None else torch.zeros(1, dtype=torch.int64, device=records.device)
+        d_count = count if count is not None else _i64(1, records.device)
         if sums is None:
-            sums = torch.zeros(2, dtype=torch.int64, device=records.device)
-        tb = lib().acm_gpu_segment_tmp_bytes(self.h, room, span)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
-        _check(lib().acm_gpu_segment_records_device(self.h, records.data_ptr(), room, count.data_ptr() if count is not None else None, pos_lo, span,
+            sums = _i64(2, records.device)
+        tmp = _scratch(lib().acm_gpu_segment_tmp_bytes(self.h, room, span), records.device)
+        _check(lib().acm_gpu_segment_records_device(self.h, records.data_ptr(), room, _opt(count), pos_lo, span,
                                                     cost.data_ptr(), cost.numel(), int(gap_cost), out.data_ptr(), d_count.data_ptr(),
                                                     sums.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
                "acm_gpu_segment_records_device")
@@ -4145,23 +3826,14 @@ class Plan:
         <= capacity; a greater count is the number of ALL matches, the capacity the call needs."""
         import torch
         assert text.is_cuda and text.is_contiguous() and cost.is_cuda and cost.is_contiguous() and cost.element_size() == 4
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
-        if records is None:
-            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
-            records = torch.empty((cap, 2), dtype=torch.int64, device=text.device)
-        if count is None:
-            count = torch.zeros(1, dtype=torch.int64, device=text.device)
+        n_symbols = self._text_args(text, n_symbols)
+        records, count = self._records_out(records, count, capacity, n_symbols, text.device)
         if sums is None:
-            sums = torch.zeros(2, dtype=torch.int64, device=text.device)
-        n_texts = 0
-        if offsets is not None:
-            assert offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-            n_texts = offsets.numel() - 1
-        tb = lib().acm_gpu_scan_segment_tmp_bytes(self.h, records.shape[0], n_symbols, n_texts)
-        if tmp is None or tmp.numel() < tb:
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-        _check(lib().acm_gpu_scan_segment_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
+            sums = _i64(2, text.device)
+        assert offsets is None or (offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64)
+        off_ptr, n_texts = _cut(offsets)
+        tmp = _scratch(lib().acm_gpu_scan_segment_tmp_bytes(self.h, records.shape[0], n_symbols, n_texts), text.device, tmp)
+        _check(lib().acm_gpu_scan_segment_device(self.h, text.data_ptr(), n_symbols, pos_base, off_ptr,
                                                  n_texts, cost.data_ptr(), cost.numel(), int(gap_cost), records.data_ptr(), records.shape[0],
                                                  count.data_ptr(), sums.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
                "acm_gpu_scan_segment_device")
@@ -4172,37 +3844,17 @@ class Plan:
         an overflow is repeated once with the size the call reports."""
         t = np.ascontiguousarray(text)
         n_sym = t.size * t.itemsize // self.sym_size
-        c, cp = _costs(cost)
         off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
-        for attempt in (0, 1):
-            out = np.zeros(cap, dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            sums = np.zeros(2, np.uint64)
-            rc = lib().acm_gpu_scan_segment_host(self.h, t.ctypes.data, n_sym, pos_base, off.ctypes.data if off is not None else None,
-                                                 off.size - 1 if off is not None else 0, cp, c.size, int(gap_cost), out.ctypes.data, cap,
-                                                 C.byref(n), sums.ctypes.data)
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_gpu_scan_segment_host")
-            return out[:n.value], (int(sums[0]), int(sums[1]))
+        return _segment_host_call(lib().acm_gpu_scan_segment_host, "acm_gpu_scan_segment_host", (self.h, t.ctypes.data, n_sym, pos_base, *_cut(off)),
+                                  cost, gap_cost, int(capacity) if capacity is not None else max(1024, n_sym // 64), capacity is not None)
 
     def scan_select_host(self, text, pos_base=0, capacity=None):
         """acm_gpu_scan_select_host(): numpy in, the selected records out, through the C ABI only (no
         torch); an overflow is repeated once with the size the call reports."""
         t = np.ascontiguousarray(text)
         n_sym = t.size * t.itemsize // self.sym_size
-        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
-        for attempt in (0, 1):
-            out = np.zeros(cap, dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = lib().acm_gpu_scan_select_host(self.h, t.ctypes.data, n_sym, pos_base, out.ctypes.data, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_gpu_scan_select_host")
-            return out[:n.value]
+        return _records_host_call(lib().acm_gpu_scan_select_host, "acm_gpu_scan_select_host", (self.h, t.ctypes.data, n_sym, pos_base),
+                                  int(capacity) if capacity is not None else max(1024, n_sym // 64), capacity is not None)
 
     def words_records(self, text, records, n, offsets=None, ranges=ASCII_WORD, flags="both", pos_base=0, n_symbols=None, out=None, count=None,
                       out_count=None):
@@ -4214,24 +3866,20 @@ class Plan:
         out_count (None: a new device tensor; may be `count`) holds the number of kept records, or
         `count`'s value when that exceeds n.  Nothing is synchronised."""
         import torch
-        assert text.is_cuda and text.is_contiguous()
+        n_symbols = self._text_args(text, n_symbols)
         assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
         n = int(n)
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
         if out is None:
             out = torch.empty((max(n, 1), 2), dtype=torch.int64, device=records.device)
         assert out.is_cuda and out.is_contiguous() and out.shape[0] >= n
         if out_count is None:
-            out_count = torch.zeros(1, dtype=torch.int64, device=records.device)
+            out_count = _i64(1, records.device)
         r, nr = _word_ranges(ranges, self.sym_size)
-        n_texts = offsets.numel() - 1 if offsets is not None else 0
-        tb = lib().acm_gpu_words_tmp_bytes(self.h, n, n_texts)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=records.device)
-        _check(lib().acm_gpu_words_records_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
-                                                  n_texts, r.ctypes.data, nr, _word_flags(flags), records.data_ptr(), n,
-                                                  count.data_ptr() if count is not None else None, out.data_ptr(), out_count.data_ptr(),
-                                                  tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_words_records_device")
+        off_ptr, n_texts = _cut(offsets)
+        tmp = _scratch(lib().acm_gpu_words_tmp_bytes(self.h, n, n_texts), records.device)
+        _check(lib().acm_gpu_words_records_device(self.h, text.data_ptr(), n_symbols, pos_base, off_ptr, n_texts, r.ctypes.data, nr, _word_flags(flags),
+                                                  records.data_ptr(), n, _opt(count), out.data_ptr(), out_count.data_ptr(), tmp.data_ptr(),
+                                                  tmp.numel(), self._stream()), "acm_gpu_words_records_device")
         return out, out_count
 
     def scan_words(self, text, offsets=None, ranges=ASCII_WORD, flags="both", n_symbols=None, pos_base=0, capacity=None, records=None, count=None,
@@ -4240,21 +3888,12 @@ class Plan:
         its records, queued on the current stream.  Returns (records, count, tmp): records[:count] are
         the whole-word matches in canonical order when count <= capacity; a greater count is the
         number of ALL matches, the capacity the call needs."""
-        import torch
-        assert text.is_cuda and text.is_contiguous()
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
-        if records is None:
-            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
-            records = torch.empty((cap, 2), dtype=torch.int64, device=text.device)
-        if count is None:
-            count = torch.zeros(1, dtype=torch.int64, device=text.device)
+        n_symbols = self._text_args(text, n_symbols)
+        records, count = self._records_out(records, count, capacity, n_symbols, text.device)
         r, nr = _word_ranges(ranges, self.sym_size)
-        n_texts = offsets.numel() - 1 if offsets is not None else 0
-        tb = lib().acm_gpu_scan_words_tmp_bytes(self.h, records.shape[0], n_symbols, n_texts)
-        if tmp is None or tmp.numel() < tb:
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-        _check(lib().acm_gpu_scan_words_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
+        off_ptr, n_texts = _cut(offsets)
+        tmp = _scratch(lib().acm_gpu_scan_words_tmp_bytes(self.h, records.shape[0], n_symbols, n_texts), text.device, tmp)
+        _check(lib().acm_gpu_scan_words_device(self.h, text.data_ptr(), n_symbols, pos_base, off_ptr,
                                                n_texts, r.ctypes.data, nr, _word_flags(flags), records.data_ptr(), records.shape[0],
                                                count.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_scan_words_device")
         return records, count, tmp
@@ -4266,18 +3905,9 @@ class Plan:
         n_sym = t.size * t.itemsize // self.sym_size
         r, nr = _word_ranges(ranges, self.sym_size)
         off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
-        for attempt in (0, 1):
-            out = np.zeros(cap, dtype=RECORD_DTYPE)
-            n = C.c_uint64(0)
-            rc = lib().acm_gpu_scan_words_host(self.h, t.ctypes.data if t.size else None, n_sym, pos_base, off.ctypes.data if off is not None else None,
-                                               off.size - 1 if off is not None else 0, r.ctypes.data, nr, _word_flags(flags), out.ctypes.data, cap,
-                                               C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and capacity is None and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_gpu_scan_words_host")
-            return out[:n.value]
+        return _records_host_call(lib().acm_gpu_scan_words_host, "acm_gpu_scan_words_host",
+                                  (self.h, _ptr(t), n_sym, pos_base, *_cut(off), r.ctypes.data, nr, _word_flags(flags)),
+                                  int(capacity) if capacity is not None else max(1024, n_sym // 64), capacity is not None)
 
     def _context_outputs(self, text, room, n_symbols, gather, out, out_capacity):
         """the device outputs of the context calls: (snip_lo, out_offsets, snip_text, rec_snip, rec_at, res, out, out_capacity);
@@ -4286,15 +3916,7 @@ class Plan:
         dev = text.device
         i64 = lambda n: torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
         i32 = lambda n: torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
-        if gather:
-            if out_capacity is None:
-                out_capacity = out.numel() * out.element_size() // self.sym_size if out is not None else n_symbols
-            if out is None:
-                out = torch.empty(max(int(out_capacity) * self.sym_size, 16), dtype=torch.uint8, device=dev)
-            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= int(out_capacity) * self.sym_size
-        else:
-            out, out_capacity = None, 0
-        return i64(room), i64(room + 1), i32(room), i32(room), i64(room), i64(3), out, int(out_capacity)
+        return (i64(room), i64(room + 1), i32(room), i32(room), i64(room), i64(3), *self._gather_room(dev, gather, out, out_capacity, n_symbols))
 
     def context_records(self, text, records, n, offsets=None, before=0, after=0, unit="symbols", merge=True, pos_base=0, n_symbols=None, count=None,
                         gather=True, out=None, out_capacity=None):
@@ -4306,18 +3928,15 @@ class Plan:
         out_capacity symbols, by default for the whole buffer; it must not overlap `text`).  Returns a
         Snippets of device tensors; synchronises to read its numbers."""
         import torch
-        assert text.is_cuda and text.is_contiguous()
+        n_symbols = self._text_args(text, n_symbols)
         assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
         n = int(n)
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
         snip_lo, out_off, snip_text, rec_snip, rec_at, res, out, out_capacity = self._context_outputs(text, n, n_symbols, gather, out, out_capacity)
-        n_texts = offsets.numel() - 1 if offsets is not None else 0
-        tb = lib().acm_gpu_context_tmp_bytes(self.h, n, n_texts)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-        _check(lib().acm_gpu_context_records_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
-                                                    n_texts, records.data_ptr(), n, count.data_ptr() if count is not None else None, int(before),
-                                                    int(after), _context_flags(unit, merge), out.data_ptr() if gather else None, out_capacity,
+        off_ptr, n_texts = _cut(offsets)
+        tmp = _scratch(lib().acm_gpu_context_tmp_bytes(self.h, n, n_texts), text.device)
+        _check(lib().acm_gpu_context_records_device(self.h, text.data_ptr(), n_symbols, pos_base, off_ptr,
+                                                    n_texts, records.data_ptr(), n, _opt(count), int(before),
+                                                    int(after), _context_flags(unit, merge), _opt(out), out_capacity,
                                                     res.data_ptr() + 16, res.data_ptr() + 8, snip_lo.data_ptr(), out_off.data_ptr(),
                                                     snip_text.data_ptr(), rec_snip.data_ptr(), rec_at.data_ptr(), tmp.data_ptr(), tmp.numel(),
                                                     self._stream()), "acm_gpu_context_records_device")
@@ -4332,22 +3951,14 @@ class Plan:
         matches.  Returns a Snippets of device tensors whose `records` are the matches in canonical
         order: count > capacity is the number of ALL matches (n_snippets = out_symbols = 0 then);
         out_symbols > out_capacity is the room the output needs.  Synchronises to read the three."""
-        import torch
-        assert text.is_cuda and text.is_contiguous()
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
-        if records is None:
-            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
-            records = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=text.device)
-        else:
-            cap = records.shape[0] if capacity is None else int(capacity)
+        n_symbols = self._text_args(text, n_symbols)
+        records, cap = self._records_room(records, capacity, n_symbols, text.device)
         snip_lo, out_off, snip_text, rec_snip, rec_at, res, out, out_capacity = self._context_outputs(text, cap, n_symbols, gather, out, out_capacity)
-        n_texts = offsets.numel() - 1 if offsets is not None else 0
-        tb = lib().acm_gpu_scan_context_tmp_bytes(self.h, cap, n_symbols, n_texts)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-        _check(lib().acm_gpu_scan_context_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
+        off_ptr, n_texts = _cut(offsets)
+        tmp = _scratch(lib().acm_gpu_scan_context_tmp_bytes(self.h, cap, n_symbols, n_texts), text.device)
+        _check(lib().acm_gpu_scan_context_device(self.h, text.data_ptr(), n_symbols, pos_base, off_ptr,
                                                  n_texts, records.data_ptr(), cap, res.data_ptr(), int(before), int(after),
-                                                 _context_flags(unit, merge), out.data_ptr() if gather else None, out_capacity, res.data_ptr() + 16,
+                                                 _context_flags(unit, merge), _opt(out), out_capacity, res.data_ptr() + 16,
                                                  res.data_ptr() + 8, snip_lo.data_ptr(), out_off.data_ptr(), snip_text.data_ptr(),
                                                  rec_snip.data_ptr(), rec_at.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
                "acm_gpu_scan_context_device")
@@ -4361,8 +3972,7 @@ class Plan:
         t = np.ascontiguousarray(text)
         n_sym = t.size * t.itemsize // self.sym_size
         off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        call = _context_scan_call(lib().acm_gpu_scan_context_host, (self.h,), t, n_sym,
-                                  (int(pos_base), off.ctypes.data if off is not None else None, off.size - 1 if off is not None else 0), before, after,
+        call = _context_scan_call(lib().acm_gpu_scan_context_host, (self.h,), t, n_sym, (int(pos_base), *_cut(off)), before, after,
                                   _context_flags(unit, merge))
         return _context_host_call(call, "acm_gpu_scan_context_host", t, self.sym_size, int(capacity) if capacity is not None else max(1024, n_sym // 64),
                                   capacity is None, gather, out_capacity)
@@ -4380,9 +3990,7 @@ class Plan:
 
     def _replace_inputs(self, text, n_symbols, replacements, fill, out, out_capacity, most_records):
         import torch
-        assert text.is_cuda and text.is_contiguous()
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
+        n_symbols = self._text_args(text, n_symbols)
         data, off, nk = replacement_table(replacements, self.sym_size, fill)
         d_data = torch.from_numpy(data.view(np.uint8).copy()).to(text.device)
         d_off = torch.from_numpy(off.view(np.int64).copy()).to(text.device) if off is not None else None
@@ -4409,15 +4017,12 @@ class Plan:
         assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
         n = int(n)
         n_symbols, d_data, d_off, nk, out, out_capacity = self._replace_inputs(text, n_symbols, replacements, fill, out, out_capacity, n)
-        res = torch.zeros(1, dtype=torch.int64, device=text.device)
-        starts = torch.zeros(max(n, 1), dtype=torch.int64, device=text.device) if out_start else None
-        tb = lib().acm_gpu_replace_tmp_bytes(self.h, n, n_symbols)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-        _check(lib().acm_gpu_replace_records_device(self.h, text.data_ptr(), n_symbols, pos_base, records.data_ptr(), n,
-                                                    count.data_ptr() if count is not None else None, d_data.data_ptr(),
-                                                    d_off.data_ptr() if d_off is not None else None, nk, out.data_ptr(), out_capacity,
-                                                    res.data_ptr(), starts.data_ptr() if out_start else None, tmp.data_ptr(), tmp.numel(),
-                                                    self._stream()), "acm_gpu_replace_records_device")
+        res = _i64(1, text.device)
+        starts = _i64(max(n, 1), text.device) if out_start else None
+        tmp = _scratch(lib().acm_gpu_replace_tmp_bytes(self.h, n, n_symbols), text.device)
+        _check(lib().acm_gpu_replace_records_device(self.h, text.data_ptr(), n_symbols, pos_base, records.data_ptr(), n, _opt(count), d_data.data_ptr(),
+                                                    _opt(d_off), nk, out.data_ptr(), out_capacity, res.data_ptr(), _opt(starts), tmp.data_ptr(),
+                                                    tmp.numel(), self._stream()), "acm_gpu_replace_records_device")
         return Replaced(out, int(res.item()), out_capacity, records, int(count.item()) if count is not None else n, starts)
 
     def scan_replace(self, text, replacements=None, fill=None, n_symbols=None, pos_base=0, capacity=None, records=None, out=None,
@@ -4427,23 +4032,16 @@ class Plan:
         hold ALL matches.  Returns a Replaced: count > capacity is the number of ALL matches (nothing
         was replaced, out_symbols is 0); out_symbols > out_capacity is the room the output needs.
         Synchronises to read the two."""
-        import torch
         if n_symbols is None:
             n_symbols = text.numel() * text.element_size() // self.sym_size
-        if records is None:
-            cap = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
-            records = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=text.device)
-        else:
-            cap = records.shape[0] if capacity is None else int(capacity)
+        records, cap = self._records_room(records, capacity, n_symbols, text.device)
         n_symbols, d_data, d_off, nk, out, out_capacity = self._replace_inputs(text, n_symbols, replacements, fill, out, out_capacity, cap)
-        res = torch.zeros(2, dtype=torch.int64, device=text.device)
-        starts = torch.zeros(max(cap, 1), dtype=torch.int64, device=text.device) if out_start else None
-        tb = lib().acm_gpu_scan_replace_tmp_bytes(self.h, cap, n_symbols)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
+        res = _i64(2, text.device)
+        starts = _i64(max(cap, 1), text.device) if out_start else None
+        tmp = _scratch(lib().acm_gpu_scan_replace_tmp_bytes(self.h, cap, n_symbols), text.device)
         _check(lib().acm_gpu_scan_replace_device(self.h, text.data_ptr(), n_symbols, pos_base, records.data_ptr(), cap, res.data_ptr(),
-                                                 d_data.data_ptr(), d_off.data_ptr() if d_off is not None else None, nk, out.data_ptr(),
-                                                 out_capacity, res.data_ptr() + 8, starts.data_ptr() if out_start else None, tmp.data_ptr(),
-                                                 tmp.numel(), self._stream()), "acm_gpu_scan_replace_device")
+                                                 d_data.data_ptr(), _opt(d_off), nk, out.data_ptr(), out_capacity, res.data_ptr() + 8, _opt(starts),
+                                                 tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_scan_replace_device")
         count, out_symbols = (int(x) for x in res.cpu())
         return Replaced(out, out_symbols, out_capacity, records, count, starts)
 
@@ -4451,20 +4049,8 @@ class Plan:
         """acm_gpu_scan_replace_host(): numpy in, (the new text, the number of matches replaced) out,
         through the C ABI only (no torch).  No record capacity: the call counts the matches first.  An
         output overflow is repeated once with the size the call reports when out_capacity is None."""
-        t = np.ascontiguousarray(text)
-        n_sym = t.size * t.itemsize // self.sym_size
-        data, off, nk = replacement_table(replacements, self.sym_size, fill)
-        cap = int(out_capacity) if out_capacity is not None else n_sym + 1024
-        for attempt in (0, 1):
-            out = np.zeros(max(cap * self.sym_size // t.itemsize, 1), dtype=t.dtype)
-            need, m = C.c_uint64(0), C.c_uint64(0)
-            rc = lib().acm_gpu_scan_replace_host(self.h, t.ctypes.data if t.size else None, n_sym, data.ctypes.data,
-                                                 off.ctypes.data if off is not None else None, nk, out.ctypes.data, cap, C.byref(need), C.byref(m))
-            if rc == ACM_GPU_E_OVERFLOW and out_capacity is None and attempt == 0:
-                cap = int(need.value)
-                continue
-            _check(rc, "acm_gpu_scan_replace_host")
-            return out[:int(need.value) * self.sym_size // t.itemsize], int(m.value)
+        return _replace_host_call(lib().acm_gpu_scan_replace_host, "acm_gpu_scan_replace_host", self.h, np.ascontiguousarray(text), self.sym_size,
+                                  replacements, fill, out_capacity)
 
     def _token_outputs(self, dev, token_capacity, n_texts, count_only):
         import torch
@@ -4473,10 +4059,21 @@ class Plan:
             ids = start = length = None
         else:
             ids = torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
-            start = torch.zeros(max(cap, 1), dtype=torch.int64, device=dev)
+            start = _i64(max(cap, 1), dev)
             length = torch.zeros(max(cap, 1), dtype=torch.int32, device=dev)
-        first = torch.zeros(n_texts + 1, dtype=torch.int64, device=dev) if n_texts is not None else None
+        first = _i64(n_texts + 1, dev) if n_texts is not None else None
         return cap, ids, start, length, first
+
+    @staticmethod
+    def _token_inputs(offsets, tok_of, dev):
+        """what the two token calls make of `offsets` (an int64 device tensor of n_texts + 1 entries, or None: one
+        text) and tok_of: (the offsets' address, n_texts or None, tok_of on the device or None, its entries)"""
+        import torch
+        assert offsets is None or (offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64)
+        off_ptr, n_texts = _cut(offsets)
+        table, nk = _tok_of(tok_of)
+        d_of = torch.from_numpy(table.view(np.int32).copy()).to(dev) if table is not None else None
+        return off_ptr, n_texts if offsets is not None else None, d_of, nk
 
     def tokens_records(self, text, records, n, offsets=None, mode="run", gap_base=0, tok_of=None, pos_base=0, n_symbols=None, token_capacity=None,
                        count=None, count_only=False):
@@ -4493,23 +4090,13 @@ class Plan:
         dev = records.device
         if n_symbols is None:
             n_symbols = text.numel() * text.element_size() // self.sym_size
-        n_texts = None
-        if offsets is not None:
-            assert offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-            n_texts = offsets.numel() - 1
-        table, nk = _tok_of(tok_of)
-        d_of = torch.from_numpy(table.view(np.int32).copy()).to(dev) if table is not None else None
+        off_ptr, n_texts, d_of, nk = self._token_inputs(offsets, tok_of, dev)
         cap, ids, start, length, first = self._token_outputs(dev, n_symbols if token_capacity is None else token_capacity, n_texts, count_only)
-        res = torch.zeros(1, dtype=torch.int64, device=dev)
-        tb = lib().acm_gpu_tokens_tmp_bytes(self.h, n, n_symbols)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
-        _check(lib().acm_gpu_tokens_records_device(self.h, text.data_ptr() if text is not None else None, n_symbols, pos_base, records.data_ptr(), n,
-                                                   count.data_ptr() if count is not None else None,
-                                                   offsets.data_ptr() if offsets is not None else None, n_texts or 0,
-                                                   d_of.data_ptr() if d_of is not None else None, nk, int(gap_base), _token_mode(mode),
-                                                   ids.data_ptr() if ids is not None else None, start.data_ptr() if start is not None else None,
-                                                   length.data_ptr() if length is not None else None, cap, res.data_ptr(),
-                                                   first.data_ptr() if first is not None else None, tmp.data_ptr(), tmp.numel(), self._stream()),
+        res = _i64(1, dev)
+        tmp = _scratch(lib().acm_gpu_tokens_tmp_bytes(self.h, n, n_symbols), dev)
+        _check(lib().acm_gpu_tokens_records_device(self.h, _opt(text), n_symbols, pos_base, records.data_ptr(), n, _opt(count), off_ptr, n_texts or 0,
+                                                   _opt(d_of), nk, int(gap_base), _token_mode(mode), _opt(ids), _opt(start), _opt(length), cap,
+                                                   res.data_ptr(), _opt(first), tmp.data_ptr(), tmp.numel(), self._stream()),
                "acm_gpu_tokens_records_device")
         return Tokens(ids, start, length, first, int(res.item()), records, int(count.item()) if count is not None else n, cap)
 
@@ -4522,32 +4109,16 @@ class Plan:
         always suffices.  Returns a Tokens of device tensors: count > capacity is a record room that
         suffices (n_tokens is 0 then); n_tokens > token_capacity is the room the tokens need.
         Synchronises to read the two."""
-        import torch
-        assert text.is_cuda and text.is_contiguous()
+        n_symbols = self._text_args(text, n_symbols)
         dev = text.device
-        if n_symbols is None:
-            n_symbols = text.numel() * text.element_size() // self.sym_size
-        if records is None:
-            cap_r = int(capacity) if capacity is not None else max(4096, n_symbols // 256)
-            records = torch.empty((max(cap_r, 1), 2), dtype=torch.int64, device=dev)
-        else:
-            cap_r = records.shape[0] if capacity is None else int(capacity)
-        n_texts = None
-        if offsets is not None:
-            assert offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-            n_texts = offsets.numel() - 1
-        table, nk = _tok_of(tok_of)
-        d_of = torch.from_numpy(table.view(np.int32).copy()).to(dev) if table is not None else None
+        records, cap_r = self._records_room(records, capacity, n_symbols, dev)
+        off_ptr, n_texts, d_of, nk = self._token_inputs(offsets, tok_of, dev)
         cap, ids, start, length, first = self._token_outputs(dev, n_symbols if token_capacity is None else token_capacity, n_texts, count_only)
-        res = torch.zeros(2, dtype=torch.int64, device=dev)
-        tb = lib().acm_gpu_scan_tokens_tmp_bytes(self.h, cap_r, n_symbols, n_texts or 0)
-        tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=dev)
-        _check(lib().acm_gpu_scan_tokens_device(self.h, text.data_ptr(), n_symbols, pos_base, offsets.data_ptr() if offsets is not None else None,
-                                                n_texts or 0, records.data_ptr(), cap_r, res.data_ptr(),
-                                                d_of.data_ptr() if d_of is not None else None, nk, int(gap_base), _token_mode(mode),
-                                                ids.data_ptr() if ids is not None else None, start.data_ptr() if start is not None else None,
-                                                length.data_ptr() if length is not None else None, cap, res.data_ptr() + 8,
-                                                first.data_ptr() if first is not None else None, tmp.data_ptr(), tmp.numel(), self._stream()),
+        res = _i64(2, dev)
+        tmp = _scratch(lib().acm_gpu_scan_tokens_tmp_bytes(self.h, cap_r, n_symbols, n_texts or 0), dev)
+        _check(lib().acm_gpu_scan_tokens_device(self.h, text.data_ptr(), n_symbols, pos_base, off_ptr, n_texts or 0, records.data_ptr(), cap_r,
+                                                res.data_ptr(), _opt(d_of), nk, int(gap_base), _token_mode(mode), _opt(ids), _opt(start), _opt(length),
+                                                cap, res.data_ptr() + 8, _opt(first), tmp.data_ptr(), tmp.numel(), self._stream()),
                "acm_gpu_scan_tokens_device")
         count, n_tokens = (int(x) for x in res.cpu())
         return Tokens(ids, start, length, first, n_tokens, records, count, cap)
@@ -4556,20 +4127,9 @@ class Plan:
         """acm_gpu_scan_tokens_host(): numpy in, a Tokens of numpy arrays out, through the C ABI only (no
         torch).  No record capacity: the call counts the matches first.  token_capacity None: the call
         is made twice, count and then fill."""
-        t = np.ascontiguousarray(text)
-        n_sym = t.size * t.itemsize // self.sym_size
         off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
-        n_texts = off.size - 1 if off is not None else 0
-        table, nk = _tok_of(tok_of)
-        md = _token_mode(mode)
-
-        def call(ids, start, length, cap, need, first, m):
-            return lib().acm_gpu_scan_tokens_host(self.h, t.ctypes.data if t.size else None, n_sym, off.ctypes.data if off is not None else None,
-                                                  n_texts, table.ctypes.data if table is not None else None, nk, int(gap_base), md,
-                                                  ids.ctypes.data if ids is not None else None, start.ctypes.data if start is not None else None,
-                                                  length.ctypes.data if length is not None else None, cap, C.byref(need),
-                                                  first.ctypes.data if first is not None else None, C.byref(m))
-        return _tokens_host_call(call, "acm_gpu_scan_tokens_host", n_texts, off is not None, token_capacity)
+        return _tokenize_host_call(lib().acm_gpu_scan_tokens_host, "acm_gpu_scan_tokens_host", self.h, np.ascontiguousarray(text), self.sym_size, off,
+                                   mode, gap_base, tok_of, token_capacity)
 
     def stream(self, max_piece_symbols, record_capacity):
         return Stream(self, max_piece_symbols, record_capacity)
@@ -4631,7 +4191,7 @@ def unpack_records(packed, wire, out):
     return out
 
 
-class MultiScan:
+class MultiScan(_Owner):
     """acm_gpu_multi_*: one process, shard r of a text on devices[r] (a device may repeat), the
     ordered records gathered on devices[0] by peer copies -- the C caller's way to use the GPUs of
     a node (include/acm_gpu.h); torch.distributed jobs use sharded.py instead."""
@@ -4647,12 +4207,6 @@ class MultiScan:
         if self.h:
             lib().acm_gpu_multi_destroy(self.h)
             self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def shard_bounds(self, n_symbols, shard):
         rb, b, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
@@ -4684,7 +4238,7 @@ class MultiScan:
         return int(found.value)
 
 
-class Comm:
+class Comm(_Owner):
     """acm_gpu_comm_*: one process (or, in the tests, one thread) per rank; the ranks' ordered
     records gathered on a root over RCCL through the C ABI (include/acm_gpu.h).  `unique_id()` on
     one rank, its 128 bytes handed to the others, then Comm(id, rank, world) on every rank with its
@@ -4727,14 +4281,8 @@ class Comm:
             lib().acm_gpu_comm_free(self.nccl)
             self.nccl = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
-
-class Flows:
+class Flows(_Owner):
     """acm_gpu_flows_* / acm_gpu_scan_flows_*: a batch scan whose text t continues flow flow[t] -- a
     keyword cut by the boundary between two pieces of a flow is found, with end_pos in the piece it
     ends in.  Results as Plan.scan_batch gives them: numpy arrays (records, text_id, first)."""
@@ -4752,32 +4300,16 @@ class Flows:
         once with the size the call reports (the flows have not moved)."""
         import torch
         p = self.plan
-        assert text.is_cuda and text.is_contiguous() and offsets.is_cuda and offsets.is_contiguous() and offsets.dtype == torch.int64
-        assert flow is None or (flow.is_cuda and flow.is_contiguous() and flow.dtype == torch.int32 and flow.numel() == offsets.numel() - 1)
-        n_symbols = text.numel() * text.element_size() // p.sym_size
-        n_texts = offsets.numel() - 1
-        assert n_texts >= 0
-        cap = int(capacity) if capacity is not None else max(1024, n_symbols // 64)
-        for attempt in (0, 1):
-            records = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=text.device)
-            text_id = torch.empty(max(cap, 1), dtype=torch.int32, device=text.device)
-            first = torch.zeros(n_texts + 1, dtype=torch.int64, device=text.device)
-            count = torch.zeros(1, dtype=torch.int64, device=text.device)
-            tb = lib().acm_gpu_scan_flows_tmp_bytes(p.h, self.h, cap, n_symbols, n_texts)
-            tmp = torch.empty(max(tb, 16), dtype=torch.uint8, device=text.device)
-            _check(lib().acm_gpu_scan_flows_device(p.h, self.h, text.data_ptr(), n_symbols, offsets.data_ptr(),
-                                                   flow.data_ptr() if flow is not None else None, n_texts, records.data_ptr(), text_id.data_ptr(),
-                                                   first.data_ptr(), cap, count.data_ptr(), tmp.data_ptr(), tmp.numel(), p._stream()),
-                   "acm_gpu_scan_flows_device")
-            n = int(count.item())
-            if n <= cap:
-                break
-            if attempt == 1:
-                raise ACMError(ACM_GPU_E_OVERFLOW, "acm_gpu_scan_flows_device: %d records" % n)
-            cap = n
-        p.status()
-        return (np.frombuffer(records[:n].cpu().numpy().tobytes(), dtype=RECORD_DTYPE).copy(),
-                text_id[:n].cpu().numpy().view(np.uint32).copy(), first.cpu().numpy().view(np.uint64).copy())
+        n_symbols, n_texts = p._batch_args(text, offsets)
+        assert flow is None or (flow.is_cuda and flow.is_contiguous() and flow.dtype == torch.int32 and flow.numel() == n_texts)
+
+        def launch(records, text_id, first, cap, count):
+            tmp = _scratch(lib().acm_gpu_scan_flows_tmp_bytes(p.h, self.h, cap, n_symbols, n_texts), text.device)
+            _check(lib().acm_gpu_scan_flows_device(p.h, self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), _opt(flow), n_texts,
+                                                   records.data_ptr(), text_id.data_ptr(), first.data_ptr(), cap, count.data_ptr(), tmp.data_ptr(),
+                                                   tmp.numel(), p._stream()), "acm_gpu_scan_flows_device")
+        return p._batch_records_device(launch, "acm_gpu_scan_flows_device", text.device, n_texts,
+                                       int(capacity) if capacity is not None else max(1024, n_symbols // 64))
 
     def scan_host(self, text, offsets, flow=None, capacity=None):
         """acm_gpu_scan_flows_host(): the same from host arrays, through the C ABI only (no torch)."""
@@ -4789,26 +4321,16 @@ class Flows:
         fl = None if flow is None else np.ascontiguousarray(flow, dtype=np.uint32)
         assert fl is None or fl.size == n_texts
         n_sym = t.size * t.itemsize // p.sym_size
-        cap = int(capacity) if capacity is not None else max(1024, n_sym // 64)
-        for attempt in (0, 1):
-            out = np.zeros(max(cap, 1), dtype=RECORD_DTYPE)
-            tid = np.zeros(max(cap, 1), dtype=np.uint32)
-            first = np.zeros(n_texts + 1, dtype=np.uint64)
-            n = C.c_uint64(0)
-            rc = lib().acm_gpu_scan_flows_host(p.h, self.h, t.ctypes.data, n_sym, off.ctypes.data, fl.ctypes.data if fl is not None else None,
-                                               n_texts, out.ctypes.data, tid.ctypes.data, first.ctypes.data, cap, C.byref(n))
-            if rc == ACM_GPU_E_OVERFLOW and attempt == 0:
-                cap = int(n.value)
-                continue
-            _check(rc, "acm_gpu_scan_flows_host")
-            return out[:n.value], tid[:n.value], first
+        return _batch_records_host_call(lib().acm_gpu_scan_flows_host, "acm_gpu_scan_flows_host",
+                                        (p.h, self.h, t.ctypes.data, n_sym, off.ctypes.data, _opt(fl), n_texts), n_texts,
+                                        int(capacity) if capacity is not None else max(1024, n_sym // 64))
 
     def reset(self, ids=None):
         """acm_gpu_flows_reset(): the flows `ids` (an int32 device tensor; None: all) back to the root."""
         if ids is not None:
             import torch
             assert ids.is_cuda and ids.is_contiguous() and ids.dtype == torch.int32
-        _check(lib().acm_gpu_flows_reset(self.h, ids.data_ptr() if ids is not None else None, ids.numel() if ids is not None else 0,
+        _check(lib().acm_gpu_flows_reset(self.h, _opt(ids), ids.numel() if ids is not None else 0,
                                          self.plan._stream() if ids is not None else None), "acm_gpu_flows_reset")
 
     def close(self):
@@ -4816,14 +4338,8 @@ class Flows:
             lib().acm_gpu_flows_destroy(self.h)
             self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
-
-class Stream:
+class Stream(_Owner):
     """acm_gpu_stream_*: feed host buffers piece by piece, get the records of the whole stream."""
 
     def __init__(self, plan, max_piece_symbols, record_capacity):
@@ -4854,9 +4370,3 @@ class Stream:
         if self.h:
             lib().acm_gpu_stream_close(self.h)
             self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
