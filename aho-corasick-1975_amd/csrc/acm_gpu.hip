@@ -2972,7 +2972,7 @@ acm_gpu_sort_tmp_bytes (uint64_t n) {
 }
 
 namespace {
-int radix_sort_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, void *d_tmp, size_t tmp_bytes, void *stream, uint64_t pos_lo, int key_bits);
+int radix_sort_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, void *d_tmp, size_t tmp_bytes, void *stream, uint64_t pos_lo, int pos_bits);
 }
 
 extern "C" int
@@ -2981,10 +2981,14 @@ acm_gpu_sort_records_device (ACMPlan *plan, ACMRecord *d_records, uint64_t n, vo
 }
 
 namespace {
-/* key = (end_pos - pos_lo) << len_bits | (max - length); only the low key_bits bits are sorted on
- * (a caller that knows the range of the positions saves the radix passes over bits that are zero) */
+/* Two stable radix sorts: by ~length (all 32 bits), then by end_pos - pos_lo (its low pos_bits bits:
+ * a caller that knows the range of the positions saves the radix passes over bits that are zero).
+ * The second keeps the first's order among equal positions, so the result is the canonical order
+ * for ANY 64-bit end_pos and ANY 32-bit length -- one key of (position << len_bits | max - length)
+ * loses the top len_bits bits of the position and every length above the plan's lmax.  Both sorts
+ * use the same key and value buffers, so the scratch is that of one. */
 int
-radix_sort_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, void *d_tmp, size_t tmp_bytes, void *stream, uint64_t pos_lo, int key_bits) {
+radix_sort_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, void *d_tmp, size_t tmp_bytes, void *stream, uint64_t pos_lo, int pos_bits) {
   if (!plan || (n && (!d_records || !d_tmp)))
     return ACM_GPU_E_ARG;
   if (n <= 1)
@@ -2996,17 +3000,22 @@ radix_sort_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, void *d_tmp
   unsigned char *t = static_cast<unsigned char *> (d_tmp);
   uint64_t *k0 = reinterpret_cast<uint64_t *> (t);
   uint64_t *k1 = reinterpret_cast<uint64_t *> (t + align256 (n * 8));
+  Rec16 *v0 = reinterpret_cast<Rec16 *> (d_records);
   Rec16 *v1 = reinterpret_cast<Rec16 *> (t + 2 * align256 (n * 8));
   void *cub_tmp = t + 2 * align256 (n * 8) + align256 (n * 16);
   size_t cub_bytes = cub_sort_bytes (n);
-  const uint32_t len_bits = len_bits_of (plan_lmax (plan));
-  /* key = end_pos in the high bits, (max - length) below: 64 - len_bits bits remain for positions */
-  HIP_TRY (launch (make_keys_kernel, dim3 ((uint32_t)((n + 255) / 256)), dim3 (256), 0, st, d_records, n, len_bits, pos_lo, k0));
-  hipcub::DoubleBuffer<uint64_t> keys (k0, k1);
-  hipcub::DoubleBuffer<Rec16> vals (reinterpret_cast<Rec16 *> (d_records), v1);
-  HIP_TRY (hipcub::DeviceRadixSort::SortPairs (cub_tmp, cub_bytes, keys, vals, (int)n, 0, key_bits, st));
-  if (vals.Current () != reinterpret_cast<Rec16 *> (d_records))
-    HIP_TRY (hipMemcpyAsync (d_records, vals.Current (), n * 16, hipMemcpyDeviceToDevice, st));
+  const dim3 kgrid ((uint32_t)((n + 255) / 256));
+  HIP_TRY (launch (make_keys_kernel<false>, kgrid, dim3 (256), 0, st, d_records, n, (uint64_t)0, k0));
+  hipcub::DoubleBuffer<uint64_t> lkeys (k0, k1);
+  hipcub::DoubleBuffer<Rec16> lvals (v0, v1);
+  HIP_TRY (hipcub::DeviceRadixSort::SortPairs (cub_tmp, cub_bytes, lkeys, lvals, (int)n, 0, 32, st));
+  Rec16 *by_len = lvals.Current (), *other = by_len == v0 ? v1 : v0;
+  HIP_TRY (launch (make_keys_kernel<true>, kgrid, dim3 (256), 0, st, reinterpret_cast<const ACMRecord *> (by_len), n, pos_lo, k0));
+  hipcub::DoubleBuffer<uint64_t> pkeys (k0, k1);
+  hipcub::DoubleBuffer<Rec16> pvals (by_len, other);
+  HIP_TRY (hipcub::DeviceRadixSort::SortPairs (cub_tmp, cub_bytes, pkeys, pvals, (int)n, 0, pos_bits, st));
+  if (pvals.Current () != v0)
+    HIP_TRY (hipMemcpyAsync (d_records, pvals.Current (), n * 16, hipMemcpyDeviceToDevice, st));
   return ACM_GPU_OK;
 }
 } // namespace
@@ -3014,7 +3023,7 @@ radix_sort_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, void *d_tmp
 /* ---- canonical order of records whose positions lie in [pos_lo, pos_lo + span): dev_order.h */
 namespace {
 struct OrderPlan {
-  uint32_t wlog = 0, n_buckets = 0, len_bits = 1, key_bits = 64;
+  uint32_t wlog = 0, n_buckets = 0, len_bits = 1, pos_bits = 64; /* pos_bits: the smallest b with 2^b >= span */
   bool sparse = false; /* fewer than 8 records per 4,096 positions: pass C goes by windows of buckets, not by bucket */
   uint32_t *hist = nullptr, *cur = nullptr; /* the scratch, bound when the carve has a base */
   ACMRecord *bucketed = nullptr;
@@ -3032,7 +3041,7 @@ order_layout (const ACMPlan *plan, uint64_t n, uint64_t span, Carve c = Carve ()
     span_bits++;
   const uint32_t len_bits = len_bits_of (plan_lmax (plan));
   L.len_bits = len_bits;
-  L.key_bits = span_bits + len_bits < 64 ? (int)(span_bits + len_bits) : 64;
+  L.pos_bits = (1ull << span_bits) < span ? 64 : span_bits;
   /* buckets of ORDER_POSITIONS positions (fewer when the whole range is shorter): whatever a
    * bucket holds, order_count_role has a counter per position for it */
   uint32_t wlog = 0;
@@ -3089,7 +3098,7 @@ order_records (ACMPlan *plan, ACMRecord *d_records, uint64_t n, const unsigned l
   if (!order_by_buckets (plan, L)) {
     if (n_dev)
       return ACM_GPU_E_ARG; /* (the caller asks order_by_buckets first) */
-    return radix_sort_records (plan, d_records, n, d_tmp, tmp_bytes, stream, pos_lo, L.key_bits);
+    return radix_sort_records (plan, d_records, n, d_tmp, tmp_bytes, stream, pos_lo, (int)L.pos_bits);
   }
   HIP_TRY (hipSetDevice (plan->device));
   hipStream_t st = static_cast<hipStream_t> (stream);

@@ -1396,16 +1396,20 @@ acm_segment_records (ACMRecord *records, uint64_t n, const uint32_t *cost, uint6
   for (uint64_t k = 0; k < n_keywords; k++)
     if (cost[k] >= limit)
       return ACM_GPU_E_ARG;
+  /* every position is taken relative to the first record's end, the smallest: any 64-bit end_pos is
+   * taken, bit 63 included, and only the differences have to fit a signed number */
+  const uint64_t ref = n ? records[0].end_pos : 0;
+#define REL_END(i) ((int64_t)(records[i].end_pos - ref))
   int64_t base = INT64_MAX;
   for (uint64_t i = 0; i < n; i++) {
     const ACMRecord *r = &records[i];
-    if (r->keyword_id >= n_keywords || r->length == 0 || r->end_pos > (uint64_t)INT64_MAX - 1 || (i && r->end_pos < records[i - 1].end_pos))
+    if (r->keyword_id >= n_keywords || r->length == 0 || (i && r->end_pos < records[i - 1].end_pos) || r->end_pos - ref >= (1ull << 40))
       return ACM_GPU_E_ARG;
-    const int64_t start = (int64_t)r->end_pos + 1 - (int64_t)r->length;
+    const int64_t start = REL_END (i) + 1 - (int64_t)r->length;
     if (start < base)
       base = start;
   }
-  if (n && (uint64_t)((int64_t)records[n - 1].end_pos - base) >= (1ull << 40))
+  if (n && (uint64_t)(REL_END (n - 1) - base) >= (1ull << 40))
     return ACM_GPU_E_ARG;
   *n_selected = 0;
   if (sums)
@@ -1423,22 +1427,22 @@ acm_segment_records (ACMRecord *records, uint64_t n, const uint32_t *cost, uint6
     uint32_t best_i = none, cls = 0;
     for (uint64_t i = 0; i < n; i++) {
       const ACMRecord *r = &records[i];
-      const int64_t end = (int64_t)r->end_pos, start = end + 1 - (int64_t)r->length;
+      const int64_t end = REL_END (i), start = end + 1 - (int64_t)r->length;
       uint64_t lo = 0, hi = i; /* the records in front of lo end in front of start, those from hi on do not */
       while (lo < hi) {
         const uint64_t mid = lo + (hi - lo) / 2;
-        if ((int64_t)records[mid].end_pos < start)
+        if (REL_END (mid) < start)
           lo = mid + 1;
         else
           hi = mid;
       }
       prev[i] = lo ? (uint32_t)(lo - 1) : none;
       if (i == 0 || records[i - 1].end_pos != r->end_pos) { /* a new end class */
-        gap_path = i ? V[i - 1] + gap * (uint64_t)(end - (int64_t)records[i - 1].end_pos) : gap * (uint64_t)(end + 1 - base);
+        gap_path = i ? V[i - 1] + gap * (uint64_t)(end - REL_END (i - 1)) : gap * (uint64_t)(end + 1 - base);
         best_i = none;
         cls = (uint32_t)i;
       }
-      const uint64_t w = (lo ? V[lo - 1] + gap * (uint64_t)(start - (int64_t)records[lo - 1].end_pos - 1) : gap * (uint64_t)(start - base)) + cost[r->keyword_id];
+      const uint64_t w = (lo ? V[lo - 1] + gap * (uint64_t)(start - REL_END (lo - 1) - 1) : gap * (uint64_t)(start - base)) + cost[r->keyword_id];
       const ACMRecord *b = best_i != none ? &records[best_i] : NULL;
       if (!b || w < best_w || (w == best_w && (r->length > b->length || (r->length == b->length && r->keyword_id < b->keyword_id)))) {
         best_w = w;
@@ -1477,6 +1481,7 @@ acm_segment_records (ACMRecord *records, uint64_t n, const uint32_t *cost, uint6
   free (taken), free (cfirst), free (choice), free (prev), free (V);
   return rc;
 }
+#undef REL_END
 
 /* WORDS of a record set (include/acm_gpu.h): the plain sequential pass, in place in the front of the
  * array.  Symbols are unsigned little-endian integers of sym_bytes bytes.  Everything is checked

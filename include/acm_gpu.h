@@ -234,7 +234,10 @@ int acm_gpu_scan_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, 
 int acm_gpu_count_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t emit_from,
                           uint64_t *d_count, void *stream);
 
-/* Puts n records into canonical order (end_pos ascending, length descending) in place.
+/* Puts n records into canonical order (end_pos ascending, length descending) in place, for ANY
+ * 64-bit end_pos and ANY 32-bit length: the records need not come from this plan (lengths above
+ * its longest keyword, positions with any of the 64 bits set).  Records equal in both fields keep
+ * the order they came in.  n must be below 2^31 (ACM_GPU_E_ARG).
  * d_tmp must hold acm_gpu_sort_tmp_bytes(n) bytes.  Asynchronous on `stream`. */
 size_t acm_gpu_sort_tmp_bytes (uint64_t n);
 int acm_gpu_sort_records_device (ACMPlan *plan, ACMRecord *d_records, uint64_t n, void *d_tmp,
@@ -243,7 +246,9 @@ int acm_gpu_sort_records_device (ACMPlan *plan, ACMRecord *d_records, uint64_t n
 /* The same order for records whose end_pos all lie in [pos_lo, pos_lo + span) -- what a scan of
  * `span` symbols with pos_base = pos_lo (and any emit_from) leaves: three passes over the records
  * (position buckets, then sorts of a few thousand records in LDS) instead of the radix sort's
- * eight.  A record outside the range makes acm_gpu_plan_status report ACM_GPU_E_INTERNAL.
+ * twelve.  A range the buckets cannot take (2^40 positions or more) goes to that radix sort, keyed
+ * by end_pos - pos_lo: any pos_lo, any span up to 2^64 - 1, any 32-bit length.
+ * A record outside the range makes acm_gpu_plan_status report ACM_GPU_E_INTERNAL.
  * d_tmp must hold acm_gpu_order_tmp_bytes(plan, n, span) bytes.  Asynchronous on `stream`. */
 size_t acm_gpu_order_tmp_bytes (const ACMPlan *plan, uint64_t n, uint64_t span);
 int acm_gpu_order_records_device (ACMPlan *plan, ACMRecord *d_records, uint64_t n, uint64_t pos_lo, uint64_t span,

@@ -43,8 +43,9 @@
  * (n_symbols - sums[1]).
  *
  * acm_segment_records: SEGMENT of records[0 .. n) in place in the front of the array, as
- * acm_select_records works; the plain sequential pass on the host, no device.  Starts are taken as
- * signed numbers.  ACM_GPU_E_ARG, with nothing modified: a NULL argument that is needed, a cost or
+ * acm_select_records works; the plain sequential pass on the host, no device.  Positions are taken
+ * relative to the first record's end, so any 64-bit end_pos is taken (bit 63 included) and a start
+ * may lie in front of position 0.  ACM_GPU_E_ARG, with nothing modified: a NULL argument that is needed, a cost or
  * gap_cost of 2^24 or more, a keyword_id >= n_keywords, a length of 0, an end_pos that decreases, a
  * span of 2^40 positions or more.
  *
