@@ -274,6 +274,73 @@ blob_reserve (size_t &cursor, size_t bytes) {
   return at;
 }
 
+/* ---- the compiled sets (rules, score, patterns, chains, approx): one allocation on the plan's device.
+ * What every set begins with ... */
+struct DeviceSet {
+  int device = 0;
+  void *blob = nullptr; /* one allocation: the set's arrays */
+  uint32_t n_keywords = 0;
+};
+
+/* ... how its blob is made: the parts are added as (what to copy or NULL, bytes to copy, bytes to reserve) under
+ * blob_reserve's 256-byte rule, upload () allocates once, clears the whole blob (the form counters of rules and
+ * score begin at 0) and copies part by part, and at<T> () is a part's place -- never NULL, also for no bytes ... */
+struct BlobBuilder {
+  struct Part {
+    const void *from;
+    size_t copy, at;
+  };
+  std::vector<Part> parts;
+  size_t bytes = 0;
+  unsigned char *base = nullptr;
+  size_t
+  add (const void *from, size_t copy, size_t reserve) {
+    parts.push_back (Part{ from, copy, blob_reserve (bytes, reserve) });
+    return parts.size () - 1;
+  }
+  size_t
+  add (const void *from, size_t copy) {
+    return add (from, copy, copy);
+  }
+  bool
+  upload (void **blob) {
+    if (hipMalloc (blob, bytes) != hipSuccess || hipMemset (*blob, 0, bytes) != hipSuccess)
+      return false;
+    base = static_cast<unsigned char *> (*blob);
+    for (const Part &p : parts)
+      if (p.copy && hipMemcpy (base + p.at, p.from, p.copy, hipMemcpyHostToDevice) != hipSuccess)
+        return false;
+    return hipDeviceSynchronize () == hipSuccess;
+  }
+  template <typename T = void>
+  T *
+  at (size_t part) const {
+    return reinterpret_cast<T *> (base + parts[part].at);
+  }
+};
+
+/* ... and how it goes away (the body of the five acm_gpu_*_destroy) */
+template <typename Set>
+void
+set_destroy (Set *set) {
+  if (!set)
+    return;
+  (void)hipSetDevice (set->device);
+  if (set->blob)
+    (void)hipFree (set->blob);
+  delete set;
+}
+
+/* the blob of a new set on the device, or ACM_GPU_E_NOMEM and the half-made set destroyed */
+template <typename Set>
+int
+set_upload (Set *set, BlobBuilder &b) {
+  if (b.upload (&set->blob))
+    return ACM_GPU_OK;
+  set_destroy (set);
+  return ACM_GPU_E_NOMEM;
+}
+
 int
 env_int (const char *name, int absent) {
   const char *e = getenv (name);
@@ -4629,11 +4696,9 @@ acm_gpu_tally_batch_host (ACMPlan *plan, const void *text, const uint64_t *offse
 /* ------------------------------------------------------------------ keyword rules per text (include/acm_gpu.h, dev_rules.h)
  * A rule set compiled into an index inverted by keyword, and the passes that evaluate it on a count
  * matrix on the device; acm_gpu_rules_device runs them behind acm_gpu_tally_batch_device. */
-struct ACMRules {
-  int device = 0;
+struct ACMRules : DeviceSet { /* (the blob: the arrays below, then the two form counters) */
   uint64_t n_rules = 0, n_terms = 0;
-  uint32_t n_keywords = 0, n_always = 0, n_postings = 0;
-  void *blob = nullptr; /* one allocation: the arrays below, then the two form counters */
+  uint32_t n_always = 0, n_postings = 0;
   uint32_t *d_post_ptr = nullptr, *d_base = nullptr, *d_need = nullptr, *d_always = nullptr;
   RulePost *d_post = nullptr;
   unsigned long long *d_forms = nullptr;
@@ -4864,40 +4929,25 @@ acm_gpu_rules_create (ACMPlan *plan, const ACMRuleTerm *terms, const uint64_t *r
   R->n_keywords = (uint32_t)nk;
   R->n_always = (uint32_t)always.size ();
   R->n_postings = n_postings;
-  size_t cur = 0;
-  const size_t o_post_ptr = blob_reserve (cur, (nk + 1) * 4), o_post = blob_reserve (cur, post.size () * sizeof (RulePost)),
-               o_base = blob_reserve (cur, base.size () * 4), o_need = blob_reserve (cur, base.size () * 4),
-               o_always = blob_reserve (cur, (always.size () + 1) * 4), o_forms = blob_reserve (cur, 16);
-  bool ok = hipMalloc (&R->blob, cur) == hipSuccess;
-  unsigned char *b = static_cast<unsigned char *> (R->blob);
-  ok = ok && hipMemset (b, 0, cur) == hipSuccess && hipMemcpy (b + o_post_ptr, post_ptr.data (), (nk + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_post, post.data (), post.size () * sizeof (RulePost), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_base, base.data (), base.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       (!n_rules || hipMemcpy (b + o_need, need, n_rules * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-       (always.empty () || hipMemcpy (b + o_always, always.data (), always.size () * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-       hipDeviceSynchronize () == hipSuccess;
-  if (!ok) {
-    acm_gpu_rules_destroy (R);
-    return ACM_GPU_E_NOMEM;
-  }
-  R->d_post_ptr = reinterpret_cast<uint32_t *> (b + o_post_ptr);
-  R->d_post = reinterpret_cast<RulePost *> (b + o_post);
-  R->d_base = reinterpret_cast<uint32_t *> (b + o_base);
-  R->d_need = reinterpret_cast<uint32_t *> (b + o_need);
-  R->d_always = reinterpret_cast<uint32_t *> (b + o_always);
-  R->d_forms = reinterpret_cast<unsigned long long *> (b + o_forms);
+  BlobBuilder b;
+  const size_t post_ptr_at = b.add (post_ptr.data (), (nk + 1) * 4), post_at = b.add (post.data (), post.size () * sizeof (RulePost)),
+               base_at = b.add (base.data (), base.size () * 4), need_at = b.add (need, n_rules * 4, base.size () * 4),
+               always_at = b.add (always.data (), always.size () * 4, (always.size () + 1) * 4), forms_at = b.add (nullptr, 0, 16);
+  if (const int rc = set_upload (R, b))
+    return rc;
+  R->d_post_ptr = b.at<uint32_t> (post_ptr_at);
+  R->d_post = b.at<RulePost> (post_at);
+  R->d_base = b.at<uint32_t> (base_at);
+  R->d_need = b.at<uint32_t> (need_at);
+  R->d_always = b.at<uint32_t> (always_at);
+  R->d_forms = b.at<unsigned long long> (forms_at);
   *out = R;
   return ACM_GPU_OK;
 }
 
 extern "C" void
 acm_gpu_rules_destroy (ACMRules *rules) {
-  if (!rules)
-    return;
-  (void)hipSetDevice (rules->device);
-  if (rules->blob)
-    (void)hipFree (rules->blob);
-  delete rules;
+  set_destroy (rules);
 }
 
 extern "C" int
@@ -5016,11 +5066,9 @@ acm_gpu_rules_host (ACMPlan *plan, const void *text, const uint64_t *offsets, ui
  * A model compiled into an index inverted by keyword, the passes that evaluate it on a count matrix on
  * the device and the passes that rank a kept matrix by class; acm_gpu_score_device runs both behind
  * acm_gpu_tally_batch_device. */
-struct ACMScore {
-  int device = 0;
+struct ACMScore : DeviceSet { /* (the blob: the arrays below, then the two form counters) */
   uint64_t n_classes = 0, n_terms = 0;
-  uint32_t n_keywords = 0, n_always = 0, n_postings = 0;
-  void *blob = nullptr; /* one allocation: the arrays below, then the two form counters */
+  uint32_t n_always = 0, n_postings = 0;
   uint32_t *d_post_ptr = nullptr, *d_always = nullptr;
   ScorePost *d_post = nullptr;
   long long *d_bias = nullptr, *d_threshold = nullptr;
@@ -5246,40 +5294,25 @@ acm_gpu_score_create (ACMPlan *plan, const ACMScoreTerm *terms, const uint64_t *
   S->n_always = (uint32_t)always.size ();
   S->n_postings = n_postings;
   const size_t classes_bytes = (n_classes ? n_classes : 1) * 8;
-  size_t cur = 0;
-  const size_t o_post_ptr = blob_reserve (cur, (nk + 1) * 4), o_post = blob_reserve (cur, post.size () * sizeof (ScorePost)),
-               o_bias = blob_reserve (cur, classes_bytes), o_threshold = blob_reserve (cur, classes_bytes),
-               o_always = blob_reserve (cur, (always.size () + 1) * 4), o_forms = blob_reserve (cur, 16);
-  bool ok = hipMalloc (&S->blob, cur) == hipSuccess;
-  unsigned char *b = static_cast<unsigned char *> (S->blob);
-  ok = ok && hipMemset (b, 0, cur) == hipSuccess && hipMemcpy (b + o_post_ptr, post_ptr.data (), (nk + 1) * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_post, post.data (), post.size () * sizeof (ScorePost), hipMemcpyHostToDevice) == hipSuccess &&
-       (!n_classes || (hipMemcpy (b + o_bias, bias, n_classes * 8, hipMemcpyHostToDevice) == hipSuccess &&
-                       hipMemcpy (b + o_threshold, threshold, n_classes * 8, hipMemcpyHostToDevice) == hipSuccess)) &&
-       (always.empty () || hipMemcpy (b + o_always, always.data (), always.size () * 4, hipMemcpyHostToDevice) == hipSuccess) &&
-       hipDeviceSynchronize () == hipSuccess;
-  if (!ok) {
-    acm_gpu_score_destroy (S);
-    return ACM_GPU_E_NOMEM;
-  }
-  S->d_post_ptr = reinterpret_cast<uint32_t *> (b + o_post_ptr);
-  S->d_post = reinterpret_cast<ScorePost *> (b + o_post);
-  S->d_bias = reinterpret_cast<long long *> (b + o_bias);
-  S->d_threshold = reinterpret_cast<long long *> (b + o_threshold);
-  S->d_always = reinterpret_cast<uint32_t *> (b + o_always);
-  S->d_forms = reinterpret_cast<unsigned long long *> (b + o_forms);
+  BlobBuilder b;
+  const size_t post_ptr_at = b.add (post_ptr.data (), (nk + 1) * 4), post_at = b.add (post.data (), post.size () * sizeof (ScorePost)),
+               bias_at = b.add (bias, n_classes * 8, classes_bytes), threshold_at = b.add (threshold, n_classes * 8, classes_bytes),
+               always_at = b.add (always.data (), always.size () * 4, (always.size () + 1) * 4), forms_at = b.add (nullptr, 0, 16);
+  if (const int rc = set_upload (S, b))
+    return rc;
+  S->d_post_ptr = b.at<uint32_t> (post_ptr_at);
+  S->d_post = b.at<ScorePost> (post_at);
+  S->d_bias = b.at<long long> (bias_at);
+  S->d_threshold = b.at<long long> (threshold_at);
+  S->d_always = b.at<uint32_t> (always_at);
+  S->d_forms = b.at<unsigned long long> (forms_at);
   *out = S;
   return ACM_GPU_OK;
 }
 
 extern "C" void
 acm_gpu_score_destroy (ACMScore *score) {
-  if (!score)
-    return;
-  (void)hipSetDevice (score->device);
-  if (score->blob)
-    (void)hipFree (score->blob);
-  delete score;
+  set_destroy (score);
 }
 
 extern "C" int
@@ -6665,7 +6698,8 @@ acm_gpu_words_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symb
   K.error = error_word (plan);
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (WordsCtl), st));
   if (K.offsets) /* one size, whatever the number of texts */
-    HIP_TRY (launch (words_check_kernel, capped_grid (plan, (n_texts + WORDS_THREADS - 1) / WORDS_THREADS), dim3 (WORDS_THREADS), 0, st, K));
+    HIP_TRY (launch (offsets_check_kernel, capped_grid (plan, (n_texts + WORDS_THREADS - 1) / WORDS_THREADS), dim3 (WORDS_THREADS), 0, st, K.offsets, K.n_texts,
+                     K.n_symbols, &K.ctl->bad, K.error));
   switch (sb) {
   case 1: return words_launch<1> (plan, L, K, st);
   case 2: return words_launch<2> (plan, L, K, st);
@@ -6676,17 +6710,18 @@ acm_gpu_words_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symb
 }
 
 namespace {
-/* the fused call's scratch: the ordered scan's records, then the room the scan and the filter share
- * (the scan has ended when the filter begins) */
-struct ScanWordsRoom {
+/* the scratch of a fused call (scan_words, scan_patterns, scan_chains, scan_approx, ...): the ordered scan's records, then
+ * the room the scan and the passes behind it share -- `passes_bytes` is what those report -- (the scan has ended when they
+ * begin) */
+struct ScanRoom {
   ACMRecord *found = nullptr;
   unsigned char *work = nullptr;
   size_t work_bytes = 0;
 };
-ScanWordsRoom
-scan_words_carve (Carve &c, const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
-  ScanWordsRoom R;
-  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_words_tmp_bytes (plan, capacity, n_texts));
+ScanRoom
+scan_room_carve (Carve &c, const ACMPlan *plan, size_t passes_bytes, uint64_t capacity, uint64_t n_symbols) {
+  ScanRoom R;
+  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), passes_bytes);
   R.found = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
   R.work = c.take (R.work_bytes);
   return R;
@@ -6698,7 +6733,7 @@ acm_gpu_scan_words_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n
   if (!plan || capacity >= (1ull << 31))
     return 0;
   Carve c;
-  scan_words_carve (c, plan, capacity, n_symbols, n_texts);
+  scan_room_carve (c, plan, acm_gpu_words_tmp_bytes (plan, capacity, n_texts), capacity, n_symbols);
   return c.total ();
 }
 
@@ -6710,7 +6745,7 @@ acm_gpu_scan_words_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols
       !acm_internal_words_args_ok (plan->text_sym_bytes, ranges, n_ranges, flags))
     return ACM_GPU_E_ARG;
   Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
-  const ScanWordsRoom L = scan_words_carve (carve, plan, capacity, n_symbols, n_texts);
+  const ScanRoom L = scan_room_carve (carve, plan, acm_gpu_words_tmp_bytes (plan, capacity, n_texts), capacity, n_symbols);
   if (capacity && tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, L.found, capacity, d_count, L.work, L.work_bytes, stream);
@@ -6845,7 +6880,8 @@ acm_gpu_context_records_device (ACMPlan *plan, const void *d_text, uint64_t n_sy
   const dim3 block (CONTEXT_THREADS), tiles_grid = capped_grid (plan, K.n_tiles + 1);
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (ContextCtl), st));
   if (K.offsets) /* one size, whatever the number of texts */
-    HIP_TRY (launch (context_check_kernel, capped_grid (plan, (n_texts + CONTEXT_THREADS - 1) / CONTEXT_THREADS), block, 0, st, K));
+    HIP_TRY (launch (offsets_check_kernel, capped_grid (plan, (n_texts + CONTEXT_THREADS - 1) / CONTEXT_THREADS), block, 0, st, K.offsets, K.n_texts, K.n_symbols,
+                     &K.ctl->bad, K.error));
   /* 1. */
   HIP_TRY (merge ? launch (context_window_kernel<true>, tiles_grid, block, 0, st, K) : launch (context_window_kernel<false>, tiles_grid, block, 0, st, K));
   if (merge) { /* 2., 3. */
@@ -7065,7 +7101,8 @@ anchored_call (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint
   K.n_symbols = n_symbols;
   K.error = error_word (plan);
   HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (AnchoredCtl), st));
-  HIP_TRY (launch (anchored_check_kernel, capped_grid (plan, (n_texts + ANCHORED_THREADS - 1) / ANCHORED_THREADS), dim3 (ANCHORED_THREADS), 0, st, K));
+  HIP_TRY (launch (offsets_check_kernel, capped_grid (plan, (n_texts + ANCHORED_THREADS - 1) / ANCHORED_THREADS), dim3 (ANCHORED_THREADS), 0, st,
+                   reinterpret_cast<const uint64_t *> (K.offsets), K.n_texts, K.n_symbols, &K.ctl->bad, K.error));
   switch (plan->finfo.sym_bytes) { /* (what the kernels walk: an interned 8-byte plan walks 4-byte ids) */
   case 1: return anchored_launch<1> (plan, L, K, st);
   case 2: return anchored_launch<2> (plan, L, K, st);
@@ -7187,33 +7224,52 @@ acm_gpu_lookup_host (ACMPlan *plan, const void *text, const uint64_t *offsets, u
   return ACM_GPU_OK;
 }
 
-/* ------------------------------------------------------------------ keyword patterns with don't-care gaps (include/acm_gpu.h, dev_patterns.h)
- * A pattern set compiled into an index inverted by anchor keyword, and the passes that join a record
- * set in canonical order under it: the check of offsets[], the count pass, the prefix over the
- * records' counts, the fill pass, the order pass. */
-struct ACMPatterns {
-  int device = 0;
-  uint64_t n_patterns = 0, n_terms = 0, anchor_keywords = 0, longest = 0, max_anchor_postings = 0;
-  uint32_t n_keywords = 0;
-  void *blob = nullptr; /* one allocation: the arrays below */
-  uint32_t *d_anchor_ptr = nullptr, *d_other_ptr = nullptr;
-  uint4 *d_post = nullptr;
-  PatternOther *d_other = nullptr;
+/* ------------------------------------------------------------------ the joins of a record set under a compiled set
+ * PATTERNS, CHAINS and APPROX / EDIT / TEMPLATES (the sections below) are one frame around different passes: a
+ * *_records_device call over JoinK (dev_all.h), a fused call that scans first, and a host form of the fused call.
+ * What the three share, one copy of each. */
+namespace {
+/* the arguments every *_records_device of a join has, under their names in include/acm_gpu.h */
+struct JoinCall {
+  ACMPlan *plan;
+  const ACMRecord *d_records;
+  uint64_t n;
+  const uint64_t *d_n;
+  uint64_t n_symbols, pos_base;
+  const uint64_t *d_offsets;
+  uint64_t n_texts;
+  ACMRecord *d_out;
+  uint64_t out_capacity;
+  uint64_t *d_count;
+  void *d_tmp;
+  size_t tmp_bytes;
+  void *stream;
 };
 
-namespace {
-/* what patterns_carve derives beside K's pointers: the counts and their sums as the sum takes them */
-struct PatternsRoom {
+/* whether a join takes them with this set; the output is written while the input is still read, so the two lie apart */
+bool
+join_args_ok (const JoinCall &C, const DeviceSet *set) {
+  return C.plan && set && set->device == C.plan->device && C.d_count && C.n < (1ull << 31) && C.out_capacity < (1ull << 31) &&
+         C.n_symbols < (1ull << 56) && (!C.out_capacity || C.d_out) && (!C.n || (C.d_records && C.d_tmp)) &&
+         (!C.d_offsets || (C.n_texts < (1ull << 31) && (C.n_texts || !C.n_symbols))) &&
+         apart (C.d_records, C.n, C.d_out, C.out_capacity, sizeof (ACMRecord));
+}
+
+/* the head of a join's scratch and what the sum takes of it: tile geometry and control words first (a family may
+ * take room of its own behind them), then the counts, their sums and hipCUB's room */
+struct JoinRoom {
   long long *count = nullptr, *first = nullptr;
   CubRoom cub;
 };
-PatternsRoom
-patterns_carve (Carve &c, uint64_t capacity, PatternsK &K) {
-  PatternsRoom R;
-  /* ACM_GPU_PATTERNS_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
-  K.tile = tunable ("ACM_GPU_PATTERNS_TILE", PATTERNS_TILE_DEFAULT, PATTERNS_TILE_MIN, PATTERNS_TILE_MAX, Tune::MultWave);
-  K.n_tiles = (capacity + K.tile - 1) / K.tile;
-  K.ctl = c.take<PatternsCtl> (1);
+void
+join_carve_ctl (Carve &c, uint64_t capacity, uint32_t tile, JoinK &K) {
+  K.tile = tile;
+  K.n_tiles = (capacity + tile - 1) / tile;
+  K.ctl = c.take<JoinCtl> (1);
+}
+JoinRoom
+join_carve_counts (Carve &c, uint64_t capacity, JoinK &K) {
+  JoinRoom R;
   R.count = c.take<long long> ((size_t)capacity + 1);
   R.first = c.take<long long> ((size_t)capacity + 1);
   R.cub = cub_room (c, 0, capacity + 1);
@@ -7222,20 +7278,144 @@ patterns_carve (Carve &c, uint64_t capacity, PatternsK &K) {
   return R;
 }
 
-/* the fused call's scratch: the ordered scan's records, then the room the scan and the join share
- * (the scan has ended when the join begins) */
-struct ScanPatternsRoom {
-  ACMRecord *found = nullptr;
-  unsigned char *work = nullptr;
-  size_t work_bytes = 0;
+/* the head of a join's kernel arguments from the call's */
+void
+bind_join (JoinK &K, const JoinCall &C) {
+  K.in = C.d_records;
+  K.capacity = C.n;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (C.d_n);
+  K.n_symbols = C.n_symbols;
+  K.pos_base = C.pos_base;
+  K.offsets = C.n_texts ? C.d_offsets : nullptr; /* (no text: no symbol, every record breaks the contract) */
+  K.n_texts = C.n_texts;
+  K.out = C.d_out;
+  K.out_capacity = C.out_capacity;
+  K.d_count = reinterpret_cast<unsigned long long *> (C.d_count);
+  K.error = error_word (C.plan);
+}
+
+/* the arguments every acm_gpu_scan_<join>_device has */
+struct ScanJoinCall {
+  ACMPlan *plan;
+  const void *d_text;
+  uint64_t n_symbols, pos_base;
+  const uint64_t *d_offsets;
+  uint64_t n_texts, capacity;
+  ACMRecord *d_out;
+  uint64_t out_capacity;
+  uint64_t *d_count, *d_found;
+  void *d_tmp;
+  size_t tmp_bytes;
+  void *stream;
 };
-ScanPatternsRoom
-scan_patterns_carve (Carve &c, const ACMPlan *plan, const ACMPatterns *patterns, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
-  ScanPatternsRoom R;
-  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_patterns_tmp_bytes (plan, patterns, capacity, n_texts));
-  R.found = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
-  R.work = c.take (R.work_bytes);
-  return R;
+
+/* A fused call: the ordered scan into `capacity` records of the call's own, then the family's join of them -- join
+ * (JoinCall) -- in the room the two share.  usable: the family takes this plan, set and capacity; passes_bytes: what its
+ * join reports for `capacity` records. */
+template <typename Join>
+int
+scan_then_join (const ScanJoinCall &C, bool usable, size_t passes_bytes, Join join) {
+  if (!usable || !C.d_count || !C.d_found || C.capacity >= (1ull << 31) || C.out_capacity >= (1ull << 31) || (C.n_symbols && !C.d_text) ||
+      (C.out_capacity && !C.d_out) || (C.capacity && !C.d_tmp))
+    return ACM_GPU_E_ARG;
+  Carve carve (C.capacity ? C.d_tmp : nullptr); /* (no room: nothing is bound) */
+  const ScanRoom L = scan_room_carve (carve, C.plan, passes_bytes, C.capacity, C.n_symbols);
+  if (C.capacity && C.tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  if (C.capacity == 0) { /* no room: *d_found says what the records need, and nothing matches */
+    if (const int rc = acm_gpu_count_device (C.plan, C.d_text, C.n_symbols, 0, C.d_found, C.stream))
+      return rc;
+    return no_record (C.plan, nullptr, C.d_count, static_cast<hipStream_t> (C.stream));
+  }
+  if (const int rc = acm_gpu_scan_ordered_device (C.plan, C.d_text, C.n_symbols, 0, C.pos_base, L.found, C.capacity, C.d_found, L.work, L.work_bytes, C.stream))
+    return rc;
+  return join (JoinCall{ C.plan, L.found, C.capacity, C.d_found, C.n_symbols, C.pos_base, C.d_offsets, C.n_texts, C.d_out, C.out_capacity, C.d_count, L.work,
+                         L.work_bytes, C.stream });
+}
+
+/* the arguments every acm_gpu_scan_<join>_host has beside its set; dist: the families with a distance per match, may be NULL */
+struct ScanJoinHost {
+  ACMPlan *plan;
+  const void *text;
+  uint64_t n_symbols, pos_base;
+  const uint64_t *offsets;
+  uint64_t n_texts;
+  ACMRecord *out;
+  uint32_t *dist;
+  uint64_t out_capacity;
+  uint64_t *n_found;
+};
+
+/* The host form of a fused call.  make (&set) compiles the call's set (which goes away with the call), the text goes up,
+ * the record room is the exact number of matches, counted first -- room_ok (set, capacity) or ACM_GPU_E_NOMEM --, then
+ * the scratch of tmp_bytes (set, capacity), the output, the offsets, the device call scan (set, ScanJoinCall, d_dist)
+ * and the matches (with_dist: and their distances) come down. */
+template <typename Set, typename Make, typename RoomOk, typename TmpBytes, typename Scan>
+int
+scan_join_host (const ScanJoinHost &H, bool with_dist, Make make, RoomOk room_ok, TmpBytes tmp_bytes_of, Scan scan) {
+  if (!H.plan || !H.n_found || H.out_capacity >= (1ull << 31) || (H.n_symbols && !H.text) || (H.out_capacity && !H.out) ||
+      !optional_offsets_ok (H.offsets, H.n_texts, H.n_symbols) || (H.offsets && H.n_texts == 0 && H.n_symbols))
+    return ACM_GPU_E_ARG;
+  Set *made = nullptr;
+  if (const int rc = make (&made))
+    return rc;
+  std::unique_ptr<Set, void (*) (Set *)> set (made, set_destroy<Set>);
+  HIP_TRY (hipSetDevice (H.plan->device));
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the matches, the scan's records */
+  ACMRecord *d_out = nullptr;
+  uint32_t *d_dist = nullptr;
+  uint64_t capacity = 0;
+  HOST_TRY (upload_text (temps, H.plan, H.text, H.n_symbols, &d_text));
+  HOST_TRY (temps.get (&d_res, 16));
+  if (const int rc = count_first (H.plan, d_text, H.n_symbols, d_res, &capacity)) /* the record room: the exact number of matches */
+    return rc;
+  if (!room_ok (set.get (), capacity))
+    return ACM_GPU_E_NOMEM;
+  const size_t tmp_bytes = tmp_bytes_of (set.get (), capacity);
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  HOST_TRY (temps.get (&d_out, H.out_capacity * 16));
+  if (with_dist)
+    HOST_TRY (temps.get (&d_dist, H.out_capacity * 4));
+  if (H.offsets)
+    HOST_TRY (upload_offsets (temps, H.offsets, H.n_texts, &d_off));
+  int rc = settle (H.plan,
+                   scan (set.get (),
+                         ScanJoinCall{ H.plan, d_text, H.n_symbols, H.pos_base, d_off, H.n_texts, capacity, d_out, H.out_capacity, d_res, d_res + 1, d_tmp,
+                                       tmp_bytes, nullptr },
+                         d_dist),
+                   true);
+  uint64_t found = 0;
+  if (!rc) {
+    HOST_TRY (hipMemcpy (&found, d_res + 1, 8, hipMemcpyDeviceToHost));
+    if (found > capacity) /* (the room is what the count pass found: never expected) */
+      rc = ACM_GPU_E_INTERNAL;
+  }
+  rc = download_records (rc, d_res, d_out, H.out, H.out_capacity, H.n_found);
+  if (!rc && with_dist && H.dist && *H.n_found)
+    HOST_TRY (hipMemcpy (H.dist, d_dist, *H.n_found * 4, hipMemcpyDeviceToHost));
+  return rc;
+}
+} // namespace
+
+/* ------------------------------------------------------------------ keyword patterns with don't-care gaps (include/acm_gpu.h, dev_patterns.h)
+ * A pattern set compiled into an index inverted by anchor keyword, and the passes that join a record
+ * set in canonical order under it: the check of offsets[], the count pass, the prefix over the
+ * records' counts, the fill pass, the order pass. */
+struct ACMPatterns : DeviceSet {
+  uint64_t n_patterns = 0, n_terms = 0, anchor_keywords = 0, longest = 0, max_anchor_postings = 0;
+  uint32_t *d_anchor_ptr = nullptr, *d_other_ptr = nullptr;
+  uint4 *d_post = nullptr;
+  PatternOther *d_other = nullptr;
+};
+
+namespace {
+JoinRoom
+patterns_carve (Carve &c, uint64_t capacity, PatternsK &K) {
+  /* ACM_GPU_PATTERNS_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
+  join_carve_ctl (c, capacity, tunable ("ACM_GPU_PATTERNS_TILE", PATTERNS_TILE_DEFAULT, PATTERNS_TILE_MIN, PATTERNS_TILE_MAX, Tune::MultWave), K);
+  return join_carve_counts (c, capacity, K);
 }
 } // namespace
 
@@ -7295,36 +7475,22 @@ acm_gpu_patterns_create (ACMPlan *plan, const ACMPatternTerm *terms, const uint6
   P->longest = longest;
   P->max_anchor_postings = max_postings;
   P->n_keywords = (uint32_t)nk;
-  size_t cur = 0;
-  const size_t o_anchor_ptr = blob_reserve (cur, anchor_ptr.size () * 4), o_post = blob_reserve (cur, post_dev.size () * sizeof (uint4)),
-               o_other_ptr = blob_reserve (cur, other_ptr.size () * 4), o_other = blob_reserve (cur, other.size () * sizeof (PatternOther));
-  bool ok = hipMalloc (&P->blob, cur) == hipSuccess;
-  unsigned char *b = static_cast<unsigned char *> (P->blob);
-  ok = ok && hipMemcpy (b + o_anchor_ptr, anchor_ptr.data (), anchor_ptr.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_post, post_dev.data (), post_dev.size () * sizeof (uint4), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_other_ptr, other_ptr.data (), other_ptr.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_other, other.data (), other.size () * sizeof (PatternOther), hipMemcpyHostToDevice) == hipSuccess &&
-       hipDeviceSynchronize () == hipSuccess;
-  if (!ok) {
-    acm_gpu_patterns_destroy (P);
-    return ACM_GPU_E_NOMEM;
-  }
-  P->d_anchor_ptr = reinterpret_cast<uint32_t *> (b + o_anchor_ptr);
-  P->d_post = reinterpret_cast<uint4 *> (b + o_post);
-  P->d_other_ptr = reinterpret_cast<uint32_t *> (b + o_other_ptr);
-  P->d_other = reinterpret_cast<PatternOther *> (b + o_other);
+  BlobBuilder b;
+  const size_t anchor_ptr_at = b.add (anchor_ptr.data (), anchor_ptr.size () * 4), post_at = b.add (post_dev.data (), post_dev.size () * sizeof (uint4)),
+               other_ptr_at = b.add (other_ptr.data (), other_ptr.size () * 4), other_at = b.add (other.data (), other.size () * sizeof (PatternOther));
+  if (const int rc = set_upload (P, b))
+    return rc;
+  P->d_anchor_ptr = b.at<uint32_t> (anchor_ptr_at);
+  P->d_post = b.at<uint4> (post_at);
+  P->d_other_ptr = b.at<uint32_t> (other_ptr_at);
+  P->d_other = b.at<PatternOther> (other_at);
   *out = P;
   return ACM_GPU_OK;
 }
 
 extern "C" void
 acm_gpu_patterns_destroy (ACMPatterns *patterns) {
-  if (!patterns)
-    return;
-  (void)hipSetDevice (patterns->device);
-  if (patterns->blob)
-    (void)hipFree (patterns->blob);
-  delete patterns;
+  set_destroy (patterns);
 }
 
 extern "C" int
@@ -7346,26 +7512,21 @@ acm_gpu_patterns_tmp_bytes (const ACMPlan *plan, const ACMPatterns *patterns, ui
   return c.total ();
 }
 
-extern "C" int
-acm_gpu_patterns_records_device (ACMPlan *plan, const ACMPatterns *patterns, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n,
-                                 uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out,
-                                 uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!plan || !patterns || patterns->device != plan->device || !d_count || n >= (1ull << 31) || out_capacity >= (1ull << 31) ||
-      n_symbols >= (1ull << 56) || (out_capacity && !d_out) || (n && (!d_records || !d_tmp)) ||
-      (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+namespace {
+/* acm_gpu_patterns_records_device */
+int
+patterns_join (const JoinCall &C, const ACMPatterns *patterns) {
+  if (!join_args_ok (C, patterns))
     return ACM_GPU_E_ARG;
-  if (n && out_capacity) { /* (the output is written while the input is still read) */
-    const uintptr_t a = reinterpret_cast<uintptr_t> (d_records), b = reinterpret_cast<uintptr_t> (d_out);
-    if (a < b + out_capacity * sizeof (ACMRecord) && b < a + n * sizeof (ACMRecord))
-      return ACM_GPU_E_ARG;
-  }
-  hipStream_t st = static_cast<hipStream_t> (stream);
+  ACMPlan *plan = C.plan;
+  const uint64_t n = C.n, n_texts = C.n_texts, out_capacity = C.out_capacity;
+  hipStream_t st = static_cast<hipStream_t> (C.stream);
   if (n == 0) /* (no record: no match, whatever *d_n says) */
-    return no_record (plan, nullptr, d_count, st);
-  Carve carve (d_tmp);
+    return no_record (plan, nullptr, C.d_count, st);
+  Carve carve (C.d_tmp);
   PatternsK K{};
-  const PatternsRoom L = patterns_carve (carve, n, K);
-  if (tmp_bytes < carve.total ())
+  const JoinRoom L = patterns_carve (carve, n, K);
+  if (C.tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
   K.anchor_ptr = patterns->d_anchor_ptr;
@@ -7373,21 +7534,12 @@ acm_gpu_patterns_records_device (ACMPlan *plan, const ACMPatterns *patterns, con
   K.other_ptr = patterns->d_other_ptr;
   K.other = patterns->d_other;
   K.n_keywords = patterns->n_keywords;
-  K.in = d_records;
-  K.capacity = n;
-  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
-  K.n_symbols = n_symbols;
-  K.pos_base = pos_base;
-  K.offsets = n_texts ? d_offsets : nullptr; /* (no text: no symbol, every record breaks the contract) */
-  K.n_texts = n_texts;
-  K.out = d_out;
-  K.out_capacity = out_capacity;
-  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
-  K.error = error_word (plan);
-  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (PatternsCtl), st));
+  bind_join (K, C);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (JoinCtl), st));
   /* 1. */
   if (K.offsets) /* one size, whatever the number of texts */
-    HIP_TRY (launch (patterns_check_kernel, capped_grid (plan, (n_texts + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, K));
+    HIP_TRY (launch (offsets_check_kernel, capped_grid (plan, (n_texts + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, K.offsets,
+                     K.n_texts, K.n_symbols, &K.ctl->bad, K.error));
   /* 2. */
   HIP_TRY (launch (patterns_count_kernel, capped_grid (plan, K.n_tiles), dim3 (PATTERNS_THREADS), 0, st, K));
   /* 3. */
@@ -7396,8 +7548,17 @@ acm_gpu_patterns_records_device (ACMPlan *plan, const ACMPatterns *patterns, con
   HIP_TRY (launch (patterns_fill_kernel, capped_grid (plan, K.n_tiles), dim3 (PATTERNS_THREADS), 0, st, K));
   /* 5. */
   if (out_capacity > 1)
-    HIP_TRY (launch (patterns_order_kernel, capped_grid (plan, (out_capacity + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, K));
+    HIP_TRY (launch (patterns_order_kernel, capped_grid (plan, (out_capacity + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st,
+                     static_cast<const JoinK &> (K)));
   return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_patterns_records_device (ACMPlan *plan, const ACMPatterns *patterns, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n,
+                                 uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out,
+                                 uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  return patterns_join (JoinCall{ plan, d_records, n, d_n, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count, d_tmp, tmp_bytes, stream }, patterns);
 }
 
 extern "C" size_t
@@ -7405,7 +7566,7 @@ acm_gpu_scan_patterns_tmp_bytes (const ACMPlan *plan, const ACMPatterns *pattern
   if (!plan || !patterns || capacity >= (1ull << 31))
     return 0;
   Carve c;
-  scan_patterns_carve (c, plan, patterns, capacity, n_symbols, n_texts);
+  scan_room_carve (c, plan, acm_gpu_patterns_tmp_bytes (plan, patterns, capacity, n_texts), capacity, n_symbols);
   return c.total ();
 }
 
@@ -7413,72 +7574,32 @@ extern "C" int
 acm_gpu_scan_patterns_device (ACMPlan *plan, const ACMPatterns *patterns, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
                               const uint64_t *d_offsets, uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint64_t out_capacity, uint64_t *d_count,
                               uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!plan || !patterns || patterns->device != plan->device || !d_count || !d_found || capacity >= (1ull << 31) || out_capacity >= (1ull << 31) ||
-      (n_symbols && !d_text) || (out_capacity && !d_out) || (capacity && !d_tmp))
-    return ACM_GPU_E_ARG;
-  Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
-  const ScanPatternsRoom L = scan_patterns_carve (carve, plan, patterns, capacity, n_symbols, n_texts);
-  if (capacity && tmp_bytes < carve.total ())
-    return ACM_GPU_E_ARG;
-  if (capacity == 0) { /* no room: *d_found says what the records need, and nothing matches */
-    if (const int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_found, stream))
-      return rc;
-    return no_record (plan, nullptr, d_count, static_cast<hipStream_t> (stream));
-  }
-  if (const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, L.found, capacity, d_found, L.work, L.work_bytes, stream))
-    return rc;
-  return acm_gpu_patterns_records_device (plan, patterns, L.found, capacity, d_found, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count,
-                                          L.work, L.work_bytes, stream);
+  const ScanJoinCall C{ plan, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, out_capacity, d_count, d_found, d_tmp, tmp_bytes, stream };
+  return scan_then_join (C, plan && patterns && patterns->device == plan->device, acm_gpu_patterns_tmp_bytes (plan, patterns, capacity, n_texts),
+                         [&] (const JoinCall &J) { return patterns_join (J, patterns); });
 }
 
 extern "C" int
 acm_gpu_scan_patterns_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
                             const ACMPatternTerm *terms, const uint64_t *pat_ptr, uint64_t n_patterns, ACMRecord *out, uint64_t out_capacity,
                             uint64_t *n_found) {
-  if (!plan || !n_found || out_capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
-      !optional_offsets_ok (offsets, n_texts, n_symbols) || (offsets && n_texts == 0 && n_symbols))
-    return ACM_GPU_E_ARG;
-  ACMPatterns *made = nullptr;
-  if (const int rc = acm_gpu_patterns_create (plan, terms, pat_ptr, n_patterns, &made))
-    return rc;
-  std::unique_ptr<ACMPatterns, void (*) (ACMPatterns *)> patterns (made, acm_gpu_patterns_destroy);
-  HIP_TRY (hipSetDevice (plan->device));
-  DeviceTemps temps;
-  void *d_text = nullptr, *d_tmp = nullptr;
-  uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the matches, the scan's records */
-  ACMRecord *d_out = nullptr;
-  uint64_t capacity = 0;
-  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
-  HOST_TRY (temps.get (&d_res, 16));
-  if (const int rc = count_first (plan, d_text, n_symbols, d_res, &capacity)) /* the record room: the exact number of matches */
-    return rc;
-  const size_t tmp_bytes = acm_gpu_scan_patterns_tmp_bytes (plan, patterns.get (), capacity, n_symbols, n_texts);
-  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
-  HOST_TRY (temps.get (&d_out, out_capacity * 16));
-  if (offsets)
-    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
-  int rc = settle (plan,
-                   acm_gpu_scan_patterns_device (plan, patterns.get (), d_text, n_symbols, pos_base, d_off, n_texts, capacity, d_out, out_capacity, d_res,
-                                                 d_res + 1, d_tmp, tmp_bytes, nullptr),
-                   true);
-  uint64_t found = 0;
-  if (!rc) {
-    HOST_TRY (hipMemcpy (&found, d_res + 1, 8, hipMemcpyDeviceToHost));
-    if (found > capacity) /* (the room is what the count pass found: never expected) */
-      rc = ACM_GPU_E_INTERNAL;
-  }
-  return download_records (rc, d_res, d_out, out, out_capacity, n_found);
+  const ScanJoinHost H{ plan, text, n_symbols, pos_base, offsets, n_texts, out, nullptr, out_capacity, n_found };
+  return scan_join_host<ACMPatterns> (
+    H, false, [&] (ACMPatterns **made) { return acm_gpu_patterns_create (plan, terms, pat_ptr, n_patterns, made); },
+    [] (const ACMPatterns *, uint64_t) { return true; },
+    [&] (const ACMPatterns *set, uint64_t capacity) { return acm_gpu_scan_patterns_tmp_bytes (plan, set, capacity, n_symbols, n_texts); },
+    [] (const ACMPatterns *set, const ScanJoinCall &C, uint32_t *) {
+      return acm_gpu_scan_patterns_device (C.plan, set, C.d_text, C.n_symbols, C.pos_base, C.d_offsets, C.n_texts, C.capacity, C.d_out, C.out_capacity, C.d_count,
+                                           C.d_found, C.d_tmp, C.tmp_bytes, C.stream);
+    });
 }
 
 /* ------------------------------------------------------------------ keyword chains with bounded gaps (include/acm_gpu.h, dev_chains.h)
  * A chain set compiled into an index inverted by keyword, and the passes that join a record set in
  * canonical order under it: the check of offsets[], one level pass per term level of the set, the
  * count pass, the prefix over the records' counts, the fill pass, the patterns' order pass. */
-struct ACMChains {
-  int device = 0;
+struct ACMChains : DeviceSet {
   uint64_t n_chains = 0, n_terms = 0, max_terms = 0, max_gap = 0, max_postings = 0, max_last_postings = 0;
-  uint32_t n_keywords = 0;
-  void *blob = nullptr; /* one allocation: the arrays below */
   uint32_t *d_post_ptr = nullptr;
   ChainPost *d_post = nullptr;
 };
@@ -7486,43 +7607,20 @@ struct ACMChains {
 namespace {
 constexpr uint64_t CHAINS_MOST_SLOTS = 1ull << 40; /* state slots of one call: records x the most postings of a keyword */
 
-struct ChainsRoom {
-  long long *count = nullptr, *first = nullptr;
-  CubRoom cub;
-};
-ChainsRoom
+JoinRoom
 chains_carve (Carve &c, const ACMChains *chains, uint64_t capacity, ChainsK &K) {
-  ChainsRoom R;
   /* ACM_GPU_CHAINS_TILE=<records>: the passes' tile, a multiple of 64 (tests); ACM_GPU_CHAINS_COOP=<records>: windows of more
    * records are walked by the whole wave (0: every window, a huge value: none) */
-  K.tile = tunable ("ACM_GPU_CHAINS_TILE", CHAINS_TILE_DEFAULT, CHAINS_TILE_MIN, CHAINS_TILE_MAX, Tune::MultWave);
+  join_carve_ctl (c, capacity, tunable ("ACM_GPU_CHAINS_TILE", CHAINS_TILE_DEFAULT, CHAINS_TILE_MIN, CHAINS_TILE_MAX, Tune::MultWave), K);
   K.coop = tunable ("ACM_GPU_CHAINS_COOP", CHAINS_COOP_DEFAULT, 0, 0x7FFFFFFFu, Tune::Any);
-  K.n_tiles = (capacity + K.tile - 1) / K.tile;
   K.stride = (uint32_t)std::max<uint64_t> (chains->max_postings, 1);
-  K.ctl = c.take<PatternsCtl> (1);
   K.state = c.take<unsigned long long> ((size_t)(capacity * K.stride));
-  R.count = c.take<long long> ((size_t)capacity + 1);
-  R.first = c.take<long long> ((size_t)capacity + 1);
-  R.cub = cub_room (c, 0, capacity + 1);
-  K.count = reinterpret_cast<unsigned long long *> (R.count);
-  K.first = reinterpret_cast<const unsigned long long *> (R.first);
-  return R;
+  return join_carve_counts (c, capacity, K);
 }
 
 bool
 chains_room_ok (const ACMChains *chains, uint64_t capacity) {
   return capacity < (1ull << 31) && capacity * std::max<uint64_t> (chains->max_postings, 1) < CHAINS_MOST_SLOTS;
-}
-
-/* the fused call's scratch: the ordered scan's records, then the room the scan and the join share
- * (the scan has ended when the join begins) */
-ScanPatternsRoom
-scan_chains_carve (Carve &c, const ACMPlan *plan, const ACMChains *chains, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
-  ScanPatternsRoom R;
-  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), acm_gpu_chains_tmp_bytes (plan, chains, capacity, n_texts));
-  R.found = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
-  R.work = c.take (R.work_bytes);
-  return R;
 }
 } // namespace
 
@@ -7581,31 +7679,19 @@ acm_gpu_chains_create (ACMPlan *plan, const ACMChainTerm *terms, const uint64_t 
   S->max_postings = max_postings;
   S->max_last_postings = max_last;
   S->n_keywords = (uint32_t)nk;
-  size_t cur = 0;
-  const size_t o_post_ptr = blob_reserve (cur, post_ptr.size () * 4), o_post = blob_reserve (cur, post.size () * sizeof (ChainPost));
-  bool ok = hipMalloc (&S->blob, cur) == hipSuccess;
-  unsigned char *b = static_cast<unsigned char *> (S->blob);
-  ok = ok && hipMemcpy (b + o_post_ptr, post_ptr.data (), post_ptr.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_post, post.data (), post.size () * sizeof (ChainPost), hipMemcpyHostToDevice) == hipSuccess &&
-       hipDeviceSynchronize () == hipSuccess;
-  if (!ok) {
-    acm_gpu_chains_destroy (S);
-    return ACM_GPU_E_NOMEM;
-  }
-  S->d_post_ptr = reinterpret_cast<uint32_t *> (b + o_post_ptr);
-  S->d_post = reinterpret_cast<ChainPost *> (b + o_post);
+  BlobBuilder b;
+  const size_t post_ptr_at = b.add (post_ptr.data (), post_ptr.size () * 4), post_at = b.add (post.data (), post.size () * sizeof (ChainPost));
+  if (const int rc = set_upload (S, b))
+    return rc;
+  S->d_post_ptr = b.at<uint32_t> (post_ptr_at);
+  S->d_post = b.at<ChainPost> (post_at);
   *out = S;
   return ACM_GPU_OK;
 }
 
 extern "C" void
 acm_gpu_chains_destroy (ACMChains *chains) {
-  if (!chains)
-    return;
-  (void)hipSetDevice (chains->device);
-  if (chains->blob)
-    (void)hipFree (chains->blob);
-  delete chains;
+  set_destroy (chains);
 }
 
 extern "C" int
@@ -7627,57 +7713,32 @@ acm_gpu_chains_tmp_bytes (const ACMPlan *plan, const ACMChains *chains, uint64_t
   return c.total ();
 }
 
-extern "C" int
-acm_gpu_chains_records_device (ACMPlan *plan, const ACMChains *chains, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, uint64_t n_symbols,
-                               uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint64_t out_capacity,
-                               uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!plan || !chains || chains->device != plan->device || !d_count || !chains_room_ok (chains, n) || out_capacity >= (1ull << 31) ||
-      n_symbols >= (1ull << 56) || (out_capacity && !d_out) || (n && (!d_records || !d_tmp)) ||
-      (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+namespace {
+/* acm_gpu_chains_records_device */
+int
+chains_join (const JoinCall &C, const ACMChains *chains) {
+  if (!join_args_ok (C, chains) || !chains_room_ok (chains, C.n))
     return ACM_GPU_E_ARG;
-  if (n && out_capacity) { /* (the output is written while the input is still read) */
-    const uintptr_t a = reinterpret_cast<uintptr_t> (d_records), b = reinterpret_cast<uintptr_t> (d_out);
-    if (a < b + out_capacity * sizeof (ACMRecord) && b < a + n * sizeof (ACMRecord))
-      return ACM_GPU_E_ARG;
-  }
-  hipStream_t st = static_cast<hipStream_t> (stream);
+  ACMPlan *plan = C.plan;
+  const uint64_t n = C.n, n_texts = C.n_texts, out_capacity = C.out_capacity;
+  hipStream_t st = static_cast<hipStream_t> (C.stream);
   if (n == 0) /* (no record: no match, whatever *d_n says) */
-    return no_record (plan, nullptr, d_count, st);
-  Carve carve (d_tmp);
+    return no_record (plan, nullptr, C.d_count, st);
+  Carve carve (C.d_tmp);
   ChainsK K{};
-  const ChainsRoom L = chains_carve (carve, chains, n, K);
-  if (tmp_bytes < carve.total ())
+  const JoinRoom L = chains_carve (carve, chains, n, K);
+  if (C.tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
   K.post_ptr = chains->d_post_ptr;
   K.post = chains->d_post;
   K.n_keywords = chains->n_keywords;
-  K.in = d_records;
-  K.capacity = n;
-  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
-  K.n_symbols = n_symbols;
-  K.pos_base = pos_base;
-  K.offsets = n_texts ? d_offsets : nullptr; /* (no text: no symbol, every record breaks the contract) */
-  K.n_texts = n_texts;
-  K.out = d_out;
-  K.out_capacity = out_capacity;
-  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
-  K.error = error_word (plan);
-  /* what the two kernels of dev_patterns.h that run here as they are read of their argument */
-  PatternsK P{};
-  P.offsets = K.offsets;
-  P.n_texts = n_texts;
-  P.n_symbols = n_symbols;
-  P.ctl = K.ctl;
-  P.error = K.error;
-  P.capacity = n;
-  P.first = K.first;
-  P.out = d_out;
-  P.out_capacity = out_capacity;
-  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (PatternsCtl), st));
+  bind_join (K, C);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (JoinCtl), st));
   /* the check */
   if (K.offsets) /* one size, whatever the number of texts */
-    HIP_TRY (launch (patterns_check_kernel, capped_grid (plan, (n_texts + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, P));
+    HIP_TRY (launch (offsets_check_kernel, capped_grid (plan, (n_texts + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, K.offsets,
+                     K.n_texts, K.n_symbols, &K.ctl->bad, K.error));
   /* 1. (as many launches as the set's longest chain has terms) */
   for (uint32_t level = 0; level < chains->max_terms; level++) {
     K.level = level;
@@ -7689,10 +7750,19 @@ acm_gpu_chains_records_device (ACMPlan *plan, const ACMChains *chains, const ACM
   HIP_TRY (exclusive_sum (L.cub, L.count, L.first, n + 1, st));
   /* 4. */
   HIP_TRY (launch (chains_fill_kernel, capped_grid (plan, K.n_tiles), dim3 (CHAINS_THREADS), 0, st, K));
-  /* 5. */
+  /* 5. (dev_patterns.h's, which reads the head of K alone) */
   if (out_capacity > 1)
-    HIP_TRY (launch (patterns_order_kernel, capped_grid (plan, (out_capacity + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, P));
+    HIP_TRY (launch (patterns_order_kernel, capped_grid (plan, (out_capacity + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st,
+                     static_cast<const JoinK &> (K)));
   return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_chains_records_device (ACMPlan *plan, const ACMChains *chains, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, uint64_t n_symbols,
+                               uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint64_t out_capacity,
+                               uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  return chains_join (JoinCall{ plan, d_records, n, d_n, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count, d_tmp, tmp_bytes, stream }, chains);
 }
 
 extern "C" size_t
@@ -7700,7 +7770,7 @@ acm_gpu_scan_chains_tmp_bytes (const ACMPlan *plan, const ACMChains *chains, uin
   if (!plan || !chains || !chains_room_ok (chains, capacity))
     return 0;
   Carve c;
-  scan_chains_carve (c, plan, chains, capacity, n_symbols, n_texts);
+  scan_room_carve (c, plan, acm_gpu_chains_tmp_bytes (plan, chains, capacity, n_texts), capacity, n_symbols);
   return c.total ();
 }
 
@@ -7708,75 +7778,33 @@ extern "C" int
 acm_gpu_scan_chains_device (ACMPlan *plan, const ACMChains *chains, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
                             uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint64_t out_capacity, uint64_t *d_count, uint64_t *d_found,
                             void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!plan || !chains || chains->device != plan->device || !d_count || !d_found || !chains_room_ok (chains, capacity) ||
-      out_capacity >= (1ull << 31) || (n_symbols && !d_text) || (out_capacity && !d_out) || (capacity && !d_tmp))
-    return ACM_GPU_E_ARG;
-  Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
-  const ScanPatternsRoom L = scan_chains_carve (carve, plan, chains, capacity, n_symbols, n_texts);
-  if (capacity && tmp_bytes < carve.total ())
-    return ACM_GPU_E_ARG;
-  if (capacity == 0) { /* no room: *d_found says what the records need, and nothing matches */
-    if (const int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_found, stream))
-      return rc;
-    return no_record (plan, nullptr, d_count, static_cast<hipStream_t> (stream));
-  }
-  if (const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, L.found, capacity, d_found, L.work, L.work_bytes, stream))
-    return rc;
-  return acm_gpu_chains_records_device (plan, chains, L.found, capacity, d_found, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count,
-                                        L.work, L.work_bytes, stream);
+  const ScanJoinCall C{ plan, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, out_capacity, d_count, d_found, d_tmp, tmp_bytes, stream };
+  return scan_then_join (C, plan && chains && chains->device == plan->device && chains_room_ok (chains, capacity),
+                         acm_gpu_chains_tmp_bytes (plan, chains, capacity, n_texts), [&] (const JoinCall &J) { return chains_join (J, chains); });
 }
 
 extern "C" int
 acm_gpu_scan_chains_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
                           const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains, ACMRecord *out, uint64_t out_capacity,
                           uint64_t *n_found) {
-  if (!plan || !n_found || out_capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
-      !optional_offsets_ok (offsets, n_texts, n_symbols) || (offsets && n_texts == 0 && n_symbols))
-    return ACM_GPU_E_ARG;
-  ACMChains *made = nullptr;
-  if (const int rc = acm_gpu_chains_create (plan, terms, chain_ptr, n_chains, &made))
-    return rc;
-  std::unique_ptr<ACMChains, void (*) (ACMChains *)> chains (made, acm_gpu_chains_destroy);
-  HIP_TRY (hipSetDevice (plan->device));
-  DeviceTemps temps;
-  void *d_text = nullptr, *d_tmp = nullptr;
-  uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the matches, the scan's records */
-  ACMRecord *d_out = nullptr;
-  uint64_t capacity = 0;
-  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
-  HOST_TRY (temps.get (&d_res, 16));
-  if (const int rc = count_first (plan, d_text, n_symbols, d_res, &capacity)) /* the record room: the exact number of matches */
-    return rc;
-  if (!chains_room_ok (chains.get (), capacity))
-    return ACM_GPU_E_NOMEM;
-  const size_t tmp_bytes = acm_gpu_scan_chains_tmp_bytes (plan, chains.get (), capacity, n_symbols, n_texts);
-  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
-  HOST_TRY (temps.get (&d_out, out_capacity * 16));
-  if (offsets)
-    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
-  int rc = settle (plan,
-                   acm_gpu_scan_chains_device (plan, chains.get (), d_text, n_symbols, pos_base, d_off, n_texts, capacity, d_out, out_capacity, d_res,
-                                               d_res + 1, d_tmp, tmp_bytes, nullptr),
-                   true);
-  uint64_t found = 0;
-  if (!rc) {
-    HOST_TRY (hipMemcpy (&found, d_res + 1, 8, hipMemcpyDeviceToHost));
-    if (found > capacity) /* (the room is what the count pass found: never expected) */
-      rc = ACM_GPU_E_INTERNAL;
-  }
-  return download_records (rc, d_res, d_out, out, out_capacity, n_found);
+  const ScanJoinHost H{ plan, text, n_symbols, pos_base, offsets, n_texts, out, nullptr, out_capacity, n_found };
+  return scan_join_host<ACMChains> (
+    H, false, [&] (ACMChains **made) { return acm_gpu_chains_create (plan, terms, chain_ptr, n_chains, made); }, chains_room_ok,
+    [&] (const ACMChains *set, uint64_t capacity) { return acm_gpu_scan_chains_tmp_bytes (plan, set, capacity, n_symbols, n_texts); },
+    [] (const ACMChains *set, const ScanJoinCall &C, uint32_t *) {
+      return acm_gpu_scan_chains_device (C.plan, set, C.d_text, C.n_symbols, C.pos_base, C.d_offsets, C.n_texts, C.capacity, C.d_out, C.out_capacity, C.d_count,
+                                         C.d_found, C.d_tmp, C.tmp_bytes, C.stream);
+    });
 }
 
 /* ------------------------------------------------------------------ keywords with up to k mismatches (include/acm_gpu.h, dev_approx.h)
  * A target set compiled into an index inverted by term keyword, and the passes that verify a record set in
  * canonical order under it: the check of offsets[], the count pass, the prefix over the records' counts, the
  * fill pass, the two sorts of the order and the gather. */
-struct ACMApprox {
-  int device = 0;
+struct ACMApprox : DeviceSet {
   uint64_t n_targets = 0, n_terms = 0, seed_keywords = 0, longest = 0, max_k = 0, max_postings = 0;
-  uint32_t n_keywords = 0, sym_bytes = 0;
+  uint32_t sym_bytes = 0;
   bool edit_fit = false; /* every k[w] <= 15 and < L_w: the edit calls take the set (acm_edit_check's two conditions) */
-  void *blob = nullptr;  /* one allocation: the arrays below */
   uint32_t *d_post_ptr = nullptr;
   uint4 *d_post = nullptr, *d_target = nullptr;
   uint64_t *d_spell_off = nullptr;
@@ -7812,11 +7840,8 @@ approx_sort_bytes (uint64_t n) {
   return bytes;
 }
 
-/* what approx_carve derives beside K's pointers: the counts and their sums as the sum takes them, the order's two
- * key and index buffers */
-struct ApproxRoom {
-  long long *count = nullptr, *first = nullptr;
-  CubRoom cub;
+/* what approx_carve derives beside K's pointers: the join's counts and sums, the order's two key and index buffers */
+struct ApproxRoom : JoinRoom {
   uint64_t *key_a = nullptr, *key_b = nullptr;
   uint32_t *idx_a = nullptr, *idx_b = nullptr;
   void *sort = nullptr;
@@ -7826,14 +7851,8 @@ ApproxRoom
 approx_carve (Carve &c, uint64_t capacity, uint64_t out_capacity, ApproxK &K) {
   ApproxRoom R;
   /* ACM_GPU_APPROX_TILE=<records>: the passes' tile, a multiple of 64 (tests) */
-  K.tile = tunable ("ACM_GPU_APPROX_TILE", APPROX_TILE_DEFAULT, APPROX_TILE_MIN, APPROX_TILE_MAX, Tune::MultWave);
-  K.n_tiles = (capacity + K.tile - 1) / K.tile;
-  K.ctl = c.take<ApproxCtl> (1);
-  R.count = c.take<long long> ((size_t)capacity + 1);
-  R.first = c.take<long long> ((size_t)capacity + 1);
-  R.cub = cub_room (c, 0, capacity + 1);
-  K.count = reinterpret_cast<unsigned long long *> (R.count);
-  K.first = reinterpret_cast<const unsigned long long *> (R.first);
+  join_carve_ctl (c, capacity, tunable ("ACM_GPU_APPROX_TILE", APPROX_TILE_DEFAULT, APPROX_TILE_MIN, APPROX_TILE_MAX, Tune::MultWave), K);
+  static_cast<JoinRoom &> (R) = join_carve_counts (c, capacity, K);
   if (out_capacity) {
     K.fill = c.take<ACMRecord> ((size_t)out_capacity);
     K.fill_dist = c.take<uint32_t> ((size_t)out_capacity);
@@ -7847,28 +7866,13 @@ approx_carve (Carve &c, uint64_t capacity, uint64_t out_capacity, ApproxK &K) {
   return R;
 }
 
-/* the fused call's scratch: the ordered scan's records, then the room the scan and the passes share (the scan
- * has ended when the passes begin) */
-struct ScanApproxRoom {
-  ACMRecord *found = nullptr;
-  unsigned char *work = nullptr;
-  size_t work_bytes = 0;
-};
-ScanApproxRoom
-scan_approx_carve (Carve &c, const ACMPlan *plan, size_t passes_bytes, uint64_t capacity, uint64_t n_symbols) {
-  ScanApproxRoom R;
-  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols), passes_bytes);
-  R.found = c.take<ACMRecord> ((size_t)(capacity ? capacity : 1));
-  R.work = c.take (R.work_bytes);
-  return R;
-}
-
 template <typename T, bool CELLS>
 int
 approx_passes (ACMPlan *plan, ApproxK &K, const ApproxRoom &L, uint64_t n, uint64_t n_texts, hipStream_t st) {
   /* 1. */
   if (K.offsets) /* one size, whatever the number of texts */
-    HIP_TRY (launch (approx_check_kernel, capped_grid (plan, (n_texts + APPROX_THREADS - 1) / APPROX_THREADS), dim3 (APPROX_THREADS), 0, st, K));
+    HIP_TRY (launch (offsets_check_kernel, capped_grid (plan, (n_texts + APPROX_THREADS - 1) / APPROX_THREADS), dim3 (APPROX_THREADS), 0, st, K.offsets,
+                     K.n_texts, K.n_symbols, &K.ctl->bad, K.error));
   /* 2. */
   HIP_TRY (launch (approx_count_kernel<T, CELLS>, capped_grid (plan, K.n_tiles), dim3 (APPROX_THREADS), 0, st, K));
   /* 3. */
@@ -7921,7 +7925,8 @@ template <typename T, uint32_t G>
 int
 edit_passes (ACMPlan *plan, ApproxK &K, const ApproxRoom &L, uint64_t n, uint64_t n_texts, hipStream_t st) {
   if (K.offsets)
-    HIP_TRY (launch (approx_check_kernel, capped_grid (plan, (n_texts + APPROX_THREADS - 1) / APPROX_THREADS), dim3 (APPROX_THREADS), 0, st, K));
+    HIP_TRY (launch (offsets_check_kernel, capped_grid (plan, (n_texts + APPROX_THREADS - 1) / APPROX_THREADS), dim3 (APPROX_THREADS), 0, st, K.offsets,
+                     K.n_texts, K.n_symbols, &K.ctl->bad, K.error));
   HIP_TRY (launch (edit_count_kernel<T, G>, capped_grid (plan, K.n_tiles), dim3 (EDIT_THREADS), 0, st, K));
   HIP_TRY (exclusive_sum (L.cub, L.count, L.first, n + 1, st));
   HIP_TRY (launch (edit_fill_kernel<T, G>, capped_grid (plan, K.n_tiles), dim3 (EDIT_THREADS), 0, st, K));
@@ -8039,53 +8044,39 @@ set_create (ACMPlan *plan, const void *spell_data, const uint64_t *spell_off, co
   A->max_postings = max_postings;
   A->n_keywords = (uint32_t)nk;
   A->sym_bytes = sb;
-  size_t cur = 0;
+  BlobBuilder b;
   const size_t spell_bytes = (size_t)n_spell * sb;
-  const size_t o_post_ptr = blob_reserve (cur, post_ptr.size () * 4), o_post = blob_reserve (cur, post_dev.size () * sizeof (uint4)),
-               o_target = blob_reserve (cur, target.size () * sizeof (uint4)), o_first = blob_reserve (cur, first_symbol.size () * 8),
-               o_terms = blob_reserve (cur, term_dev.size () * sizeof (ApproxTerm)), o_spell = blob_reserve (cur, spell_bytes + 16);
+  const size_t post_ptr_at = b.add (post_ptr.data (), post_ptr.size () * 4), post_at = b.add (post_dev.data (), post_dev.size () * sizeof (uint4)),
+               target_at = b.add (target.data (), target.size () * sizeof (uint4)), first_at = b.add (first_symbol.data (), first_symbol.size () * 8),
+               terms_at = b.add (term_dev.data (), term_dev.size () * sizeof (ApproxTerm)), spell_at = b.add (spell_data, spell_bytes, spell_bytes + 16);
   /* a template set: the cells, and the classes in the form the symbol size reads (every array with room, so that none is NULL) */
   ClassTables classes;
-  size_t o_cells = 0, o_bitmap = 0, o_cls_ptr = 0, o_ranges = 0, o_flags = 0, range_bytes = 0;
+  size_t cells_at = 0, bitmap_at = 0, cls_ptr_at = 0, ranges_at = 0, flags_at = 0;
   if (tpl) {
     classes = compile_classes (tpl, sb);
-    range_bytes = sb == 1 ? 0 : (size_t)classes.ptr.back () * 2 * sb;
-    o_cells = blob_reserve (cur, (size_t)n_spell * 4 + 16);
-    o_bitmap = blob_reserve (cur, classes.bitmap.size () * 4 + 16);
-    o_cls_ptr = blob_reserve (cur, classes.ptr.size () * 8 + 16);
-    o_ranges = blob_reserve (cur, range_bytes + 16);
-    o_flags = blob_reserve (cur, classes.flags.size () * 4 + 16);
+    const size_t range_bytes = sb == 1 ? 0 : (size_t)classes.ptr.back () * 2 * sb;
+    cells_at = b.add (tpl->cells, (size_t)n_spell * 4, (size_t)n_spell * 4 + 16);
+    bitmap_at = b.add (classes.bitmap.data (), classes.bitmap.size () * 4, classes.bitmap.size () * 4 + 16);
+    cls_ptr_at = b.add (classes.ptr.data (), classes.ptr.size () * 8, classes.ptr.size () * 8 + 16);
+    ranges_at = b.add (tpl->ranges, range_bytes, range_bytes + 16);
+    flags_at = b.add (classes.flags.data (), classes.flags.size () * 4, classes.flags.size () * 4 + 16);
   }
-  bool ok = hipMalloc (&A->blob, cur) == hipSuccess;
-  unsigned char *b = static_cast<unsigned char *> (A->blob);
-  if (ok && tpl) {
-    const auto up = [&] (size_t at, const void *from, size_t bytes) { return !bytes || hipMemcpy (b + at, from, bytes, hipMemcpyHostToDevice) == hipSuccess; };
-    ok = up (o_cells, tpl->cells, (size_t)n_spell * 4) && up (o_bitmap, classes.bitmap.data (), classes.bitmap.size () * 4) &&
-         up (o_cls_ptr, classes.ptr.data (), classes.ptr.size () * 8) && up (o_ranges, tpl->ranges, range_bytes) &&
-         up (o_flags, classes.flags.data (), classes.flags.size () * 4);
+  if (const int rc = set_upload (A, b))
+    return rc;
+  if (tpl) {
     A->n_classes = tpl->n_classes;
-    A->d_cells = reinterpret_cast<uint32_t *> (b + o_cells);
-    A->d_cls_bitmap = reinterpret_cast<uint32_t *> (b + o_bitmap);
-    A->d_cls_ptr = reinterpret_cast<uint64_t *> (b + o_cls_ptr);
-    A->d_cls_ranges = b + o_ranges;
-    A->d_cls_flags = reinterpret_cast<uint32_t *> (b + o_flags);
+    A->d_cells = b.at<uint32_t> (cells_at);
+    A->d_cls_bitmap = b.at<uint32_t> (bitmap_at);
+    A->d_cls_ptr = b.at<uint64_t> (cls_ptr_at);
+    A->d_cls_ranges = b.at<> (ranges_at);
+    A->d_cls_flags = b.at<uint32_t> (flags_at);
   }
-  ok = ok && hipMemcpy (b + o_post_ptr, post_ptr.data (), post_ptr.size () * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_post, post_dev.data (), post_dev.size () * sizeof (uint4), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_target, target.data (), target.size () * sizeof (uint4), hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_first, first_symbol.data (), first_symbol.size () * 8, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy (b + o_terms, term_dev.data (), term_dev.size () * sizeof (ApproxTerm), hipMemcpyHostToDevice) == hipSuccess &&
-       (!spell_bytes || hipMemcpy (b + o_spell, spell_data, spell_bytes, hipMemcpyHostToDevice) == hipSuccess) && hipDeviceSynchronize () == hipSuccess;
-  if (!ok) {
-    acm_gpu_approx_destroy (A);
-    return ACM_GPU_E_NOMEM;
-  }
-  A->d_post_ptr = reinterpret_cast<uint32_t *> (b + o_post_ptr);
-  A->d_post = reinterpret_cast<uint4 *> (b + o_post);
-  A->d_target = reinterpret_cast<uint4 *> (b + o_target);
-  A->d_spell_off = reinterpret_cast<uint64_t *> (b + o_first);
-  A->d_terms = reinterpret_cast<ApproxTerm *> (b + o_terms);
-  A->d_spell = b + o_spell;
+  A->d_post_ptr = b.at<uint32_t> (post_ptr_at);
+  A->d_post = b.at<uint4> (post_at);
+  A->d_target = b.at<uint4> (target_at);
+  A->d_spell_off = b.at<uint64_t> (first_at);
+  A->d_terms = b.at<ApproxTerm> (terms_at);
+  A->d_spell = b.at<> (spell_at);
   *out = A;
   return ACM_GPU_OK;
 }
@@ -8131,12 +8122,7 @@ acm_gpu_templates_info (const ACMTemplates *templates, ACMTemplatesInfo *info) {
 
 extern "C" void
 acm_gpu_approx_destroy (ACMApprox *approx) {
-  if (!approx)
-    return;
-  (void)hipSetDevice (approx->device);
-  if (approx->blob)
-    (void)hipFree (approx->blob);
-  delete approx;
+  set_destroy (approx);
 }
 
 extern "C" int
@@ -8160,26 +8146,20 @@ acm_gpu_edit_tmp_bytes (const ACMPlan *plan, const ACMApprox *approx, uint64_t n
 }
 
 namespace {
+/* (d_text and d_dist: what these joins take beside a JoinCall) */
 int
-set_records_device (Metric metric, ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, const void *d_text,
-                    uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint32_t *d_dist,
-                    uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!set_usable (metric, plan, approx) || !d_count || n >= (1ull << 31) || out_capacity >= (1ull << 31) || (out_capacity && !d_out) ||
-      (n && (!d_records || !d_tmp)) || (n_symbols && !d_text) || !symbols_ok (d_text, n_symbols, approx->sym_bytes) ||
-      (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+set_records_device (Metric metric, const JoinCall &C, const ACMApprox *approx, const void *d_text, uint32_t *d_dist) {
+  ACMPlan *plan = C.plan;
+  const uint64_t n = C.n, n_symbols = C.n_symbols, n_texts = C.n_texts, out_capacity = C.out_capacity;
+  if (!set_usable (metric, plan, approx) || !join_args_ok (C, approx) || (n_symbols && !d_text) || !symbols_ok (d_text, n_symbols, approx->sym_bytes))
     return ACM_GPU_E_ARG;
-  if (n && out_capacity) { /* (the output is written while the input is still read) */
-    const uintptr_t a = reinterpret_cast<uintptr_t> (d_records), b = reinterpret_cast<uintptr_t> (d_out);
-    if (a < b + out_capacity * sizeof (ACMRecord) && b < a + n * sizeof (ACMRecord))
-      return ACM_GPU_E_ARG;
-  }
-  hipStream_t st = static_cast<hipStream_t> (stream);
+  hipStream_t st = static_cast<hipStream_t> (C.stream);
   if (n == 0) /* (no record: no match, whatever *d_n says) */
-    return no_record (plan, nullptr, d_count, st);
-  Carve carve (d_tmp);
+    return no_record (plan, nullptr, C.d_count, st);
+  Carve carve (C.d_tmp);
   ApproxK K{};
   const ApproxRoom L = set_carve (metric, carve, n, out_capacity, K);
-  if (tmp_bytes < carve.total ())
+  if (C.tmp_bytes < carve.total ())
     return ACM_GPU_E_ARG;
   HIP_TRY (hipSetDevice (plan->device));
   const uint64_t longest = approx->longest + (metric == Metric::Edits ? approx->max_k : 0); /* (a match within k edits may be longer than its target) */
@@ -8197,20 +8177,10 @@ set_records_device (Metric metric, ACMPlan *plan, const ACMApprox *approx, const
   K.n_keywords = approx->n_keywords;
   K.longest = (uint32_t)longest;
   K.tgt_bits = bits_of (approx->n_targets ? approx->n_targets - 1 : 0);
-  K.in = d_records;
-  K.capacity = n;
-  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
   K.text = d_text;
-  K.n_symbols = n_symbols;
-  K.pos_base = pos_base;
-  K.offsets = n_texts ? d_offsets : nullptr; /* (no text: no symbol, every record breaks the contract) */
-  K.n_texts = n_texts;
-  K.out = d_out;
   K.dist = d_dist;
-  K.out_capacity = out_capacity;
-  K.d_count = reinterpret_cast<unsigned long long *> (d_count);
-  K.error = error_word (plan);
-  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (ApproxCtl), st));
+  bind_join (K, C);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (JoinCtl), st));
   int rc = ACM_GPU_E_INTERNAL;
   switch (approx->sym_bytes) {
   case 1: rc = set_passes<uint8_t> (metric, approx->max_k, plan, K, L, n, n_texts, st); break;
@@ -8243,78 +8213,32 @@ scan_set_tmp_bytes (Metric metric, const ACMPlan *plan, const ACMApprox *approx,
   if (!set_usable (metric, plan, approx) || capacity >= (1ull << 31) || out_capacity >= (1ull << 31))
     return 0;
   Carve c;
-  scan_approx_carve (c, plan, set_tmp_bytes (metric, plan, approx, capacity, out_capacity), capacity, n_symbols);
+  scan_room_carve (c, plan, set_tmp_bytes (metric, plan, approx, capacity, out_capacity), capacity, n_symbols);
   return c.total ();
 }
 
 int
-scan_set_device (Metric metric, ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
-                 uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count, uint64_t *d_found,
-                 void *d_tmp, size_t tmp_bytes, void *stream) {
-  if (!set_usable (metric, plan, approx) || !d_count || !d_found || capacity >= (1ull << 31) || out_capacity >= (1ull << 31) || (n_symbols && !d_text) ||
-      (out_capacity && !d_out) || (capacity && !d_tmp))
-    return ACM_GPU_E_ARG;
-  Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
-  const ScanApproxRoom L = scan_approx_carve (carve, plan, set_tmp_bytes (metric, plan, approx, capacity, out_capacity), capacity, n_symbols);
-  if (capacity && tmp_bytes < carve.total ())
-    return ACM_GPU_E_ARG;
-  if (capacity == 0) { /* no room: *d_found says what the records need, and nothing matches */
-    if (const int rc = acm_gpu_count_device (plan, d_text, n_symbols, 0, d_found, stream))
-      return rc;
-    return no_record (plan, nullptr, d_count, static_cast<hipStream_t> (stream));
-  }
-  if (const int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, L.found, capacity, d_found, L.work, L.work_bytes, stream))
-    return rc;
-  return set_records_device (metric, plan, approx, L.found, capacity, d_found, d_text, n_symbols, pos_base, d_offsets, n_texts, d_out, d_dist, out_capacity,
-                             d_count, L.work, L.work_bytes, stream);
+scan_set_device (Metric metric, const ScanJoinCall &C, const ACMApprox *approx, uint32_t *d_dist) {
+  return scan_then_join (C, set_usable (metric, C.plan, approx), set_tmp_bytes (metric, C.plan, approx, C.capacity, C.out_capacity),
+                         [&] (const JoinCall &J) { return set_records_device (metric, J, approx, C.d_text, d_dist); });
 }
 
 int
-scan_set_host (Metric metric, ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
-               const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
-               uint64_t n_targets, const ACMTemplateSpec *tpl, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
-  if (!plan || !n_found || out_capacity >= (1ull << 31) || (n_symbols && !text) || (out_capacity && !out) ||
-      !optional_offsets_ok (offsets, n_texts, n_symbols) || (offsets && n_texts == 0 && n_symbols))
-    return ACM_GPU_E_ARG;
-  if (metric == Metric::Edits && acm_edit_check (spell_off, k, terms, tgt_ptr, n_targets, plan->covered_keywords)) /* (the set would be made, and refused) */
-    return ACM_GPU_E_ARG;
-  if (tpl && acm_templates_check (tpl, plan->class_sym_bytes ? plan->class_sym_bytes : plan->text_sym_bytes, plan->covered_keywords))
-    return ACM_GPU_E_ARG;
-  ACMApprox *made = nullptr;
-  if (const int rc = set_create (plan, spell_data, spell_off, k, terms, tgt_ptr, n_targets, tpl, &made))
-    return rc;
-  std::unique_ptr<ACMApprox, void (*) (ACMApprox *)> approx (made, acm_gpu_approx_destroy);
-  HIP_TRY (hipSetDevice (plan->device));
-  DeviceTemps temps;
-  void *d_text = nullptr, *d_tmp = nullptr;
-  uint64_t *d_res = nullptr, *d_off = nullptr; /* d_res: the matches, the scan's records */
-  ACMRecord *d_out = nullptr;
-  uint32_t *d_dist = nullptr;
-  uint64_t capacity = 0;
-  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
-  HOST_TRY (temps.get (&d_res, 16));
-  if (const int rc = count_first (plan, d_text, n_symbols, d_res, &capacity)) /* the record room: the exact number of matches */
-    return rc;
-  const size_t tmp_bytes = scan_set_tmp_bytes (metric, plan, approx.get (), capacity, out_capacity, n_symbols);
-  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
-  HOST_TRY (temps.get (&d_out, out_capacity * 16));
-  HOST_TRY (temps.get (&d_dist, out_capacity * 4));
-  if (offsets)
-    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
-  int rc = settle (plan,
-                   scan_set_device (metric, plan, approx.get (), d_text, n_symbols, pos_base, d_off, n_texts, capacity, d_out, d_dist, out_capacity, d_res,
-                                    d_res + 1, d_tmp, tmp_bytes, nullptr),
-                   true);
-  uint64_t found = 0;
-  if (!rc) {
-    HOST_TRY (hipMemcpy (&found, d_res + 1, 8, hipMemcpyDeviceToHost));
-    if (found > capacity) /* (the room is what the count pass found: never expected) */
-      rc = ACM_GPU_E_INTERNAL;
-  }
-  rc = download_records (rc, d_res, d_out, out, out_capacity, n_found);
-  if (!rc && dist && *n_found)
-    HOST_TRY (hipMemcpy (dist, d_dist, *n_found * 4, hipMemcpyDeviceToHost));
-  return rc;
+scan_set_host (Metric metric, const ScanJoinHost &H, const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms,
+               const uint64_t *tgt_ptr, uint64_t n_targets, const ACMTemplateSpec *tpl) {
+  ACMPlan *plan = H.plan;
+  return scan_join_host<ACMApprox> (
+    H, true,
+    [&] (ACMApprox **made) {
+      if (metric == Metric::Edits && acm_edit_check (spell_off, k, terms, tgt_ptr, n_targets, plan->covered_keywords)) /* (the set would be made, and refused) */
+        return (int)ACM_GPU_E_ARG;
+      if (tpl && acm_templates_check (tpl, plan->class_sym_bytes ? plan->class_sym_bytes : plan->text_sym_bytes, plan->covered_keywords))
+        return (int)ACM_GPU_E_ARG;
+      return set_create (plan, spell_data, spell_off, k, terms, tgt_ptr, n_targets, tpl, made);
+    },
+    [] (const ACMApprox *, uint64_t) { return true; },
+    [&] (const ACMApprox *set, uint64_t capacity) { return scan_set_tmp_bytes (metric, plan, set, capacity, H.out_capacity, H.n_symbols); },
+    [&] (const ACMApprox *set, const ScanJoinCall &C, uint32_t *d_dist) { return scan_set_device (metric, C, set, d_dist); });
 }
 } // namespace
 
@@ -8323,16 +8247,17 @@ extern "C" int
 acm_gpu_approx_records_device (ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, const void *d_text,
                                uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint32_t *d_dist,
                                uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
-  return set_records_device (Metric::Mismatches, plan, approx, d_records, n, d_n, d_text, n_symbols, pos_base, d_offsets, n_texts, d_out, d_dist,
-                             out_capacity, d_count, d_tmp, tmp_bytes, stream);
+  return set_records_device (Metric::Mismatches,
+                             JoinCall{ plan, d_records, n, d_n, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count, d_tmp, tmp_bytes, stream }, approx,
+                             d_text, d_dist);
 }
 
 extern "C" int
 acm_gpu_edit_records_device (ACMPlan *plan, const ACMApprox *approx, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, const void *d_text,
                              uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint32_t *d_dist,
                              uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
-  return set_records_device (Metric::Edits, plan, approx, d_records, n, d_n, d_text, n_symbols, pos_base, d_offsets, n_texts, d_out, d_dist, out_capacity,
-                             d_count, d_tmp, tmp_bytes, stream);
+  return set_records_device (Metric::Edits, JoinCall{ plan, d_records, n, d_n, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count, d_tmp, tmp_bytes, stream },
+                             approx, d_text, d_dist);
 }
 
 /* TEMPLATES: the entry points of APPROX over a template set */
@@ -8346,8 +8271,9 @@ extern "C" int
 acm_gpu_templates_records_device (ACMPlan *plan, const ACMTemplates *templates, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n,
                                   const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out,
                                   uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
-  return set_records_device (Metric::Templates, plan, templates ? templates->set : nullptr, d_records, n, d_n, d_text, n_symbols, pos_base, d_offsets, n_texts,
-                             d_out, d_dist, out_capacity, d_count, d_tmp, tmp_bytes, stream);
+  return set_records_device (Metric::Templates,
+                             JoinCall{ plan, d_records, n, d_n, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count, d_tmp, tmp_bytes, stream },
+                             templates ? templates->set : nullptr, d_text, d_dist);
 }
 
 extern "C" size_t
@@ -8361,8 +8287,9 @@ extern "C" int
 acm_gpu_scan_templates_device (ACMPlan *plan, const ACMTemplates *templates, const void *d_text, uint64_t n_symbols, uint64_t pos_base,
                                const uint64_t *d_offsets, uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity,
                                uint64_t *d_count, uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
-  return scan_set_device (Metric::Templates, plan, templates ? templates->set : nullptr, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out,
-                          d_dist, out_capacity, d_count, d_found, d_tmp, tmp_bytes, stream);
+  return scan_set_device (Metric::Templates,
+                          ScanJoinCall{ plan, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, out_capacity, d_count, d_found, d_tmp, tmp_bytes, stream },
+                          templates ? templates->set : nullptr, d_dist);
 }
 
 extern "C" int
@@ -8370,8 +8297,8 @@ acm_gpu_scan_templates_host (ACMPlan *plan, const void *text, uint64_t n_symbols
                              const ACMTemplateSpec *spec, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
   if (!spec)
     return ACM_GPU_E_ARG;
-  return scan_set_host (Metric::Templates, plan, text, n_symbols, pos_base, offsets, n_texts, spec->spell_data, spec->spell_off, spec->k, spec->terms,
-                        spec->tgt_ptr, spec->n_templates, spec, out, dist, out_capacity, n_found);
+  return scan_set_host (Metric::Templates, ScanJoinHost{ plan, text, n_symbols, pos_base, offsets, n_texts, out, dist, out_capacity, n_found }, spec->spell_data, spec->spell_off,
+                        spec->k, spec->terms, spec->tgt_ptr, spec->n_templates, spec);
 }
 
 extern "C" size_t
@@ -8390,32 +8317,33 @@ extern "C" int
 acm_gpu_scan_approx_device (ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
                             uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count,
                             uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
-  return scan_set_device (Metric::Mismatches, plan, approx, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, d_dist, out_capacity, d_count,
-                          d_found, d_tmp, tmp_bytes, stream);
+  return scan_set_device (Metric::Mismatches,
+                          ScanJoinCall{ plan, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, out_capacity, d_count, d_found, d_tmp, tmp_bytes, stream }, approx,
+                          d_dist);
 }
 
 extern "C" int
 acm_gpu_scan_edit_device (ACMPlan *plan, const ACMApprox *approx, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
                           uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint32_t *d_dist, uint64_t out_capacity, uint64_t *d_count,
                           uint64_t *d_found, void *d_tmp, size_t tmp_bytes, void *stream) {
-  return scan_set_device (Metric::Edits, plan, approx, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, d_dist, out_capacity, d_count,
-                          d_found, d_tmp, tmp_bytes, stream);
+  return scan_set_device (Metric::Edits, ScanJoinCall{ plan, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, out_capacity, d_count, d_found, d_tmp, tmp_bytes, stream },
+                          approx, d_dist);
 }
 
 extern "C" int
 acm_gpu_scan_approx_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
                           const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
                           uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
-  return scan_set_host (Metric::Mismatches, plan, text, n_symbols, pos_base, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, nullptr, out, dist,
-                        out_capacity, n_found);
+  return scan_set_host (Metric::Mismatches, ScanJoinHost{ plan, text, n_symbols, pos_base, offsets, n_texts, out, dist, out_capacity, n_found }, spell_data, spell_off, k, terms,
+                        tgt_ptr, n_targets, nullptr);
 }
 
 extern "C" int
 acm_gpu_scan_edit_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
                         const void *spell_data, const uint64_t *spell_off, const uint32_t *k, const ACMPatternTerm *terms, const uint64_t *tgt_ptr,
                         uint64_t n_targets, ACMRecord *out, uint32_t *dist, uint64_t out_capacity, uint64_t *n_found) {
-  return scan_set_host (Metric::Edits, plan, text, n_symbols, pos_base, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, nullptr, out, dist,
-                        out_capacity, n_found);
+  return scan_set_host (Metric::Edits, ScanJoinHost{ plan, text, n_symbols, pos_base, offsets, n_texts, out, dist, out_capacity, n_found }, spell_data, spell_off, k, terms, tgt_ptr,
+                        n_targets, nullptr);
 }
 
 /* ------------------------------------------------------------------ records on the wire (include/acm_gpu.h) */
@@ -9439,8 +9367,8 @@ scan_set (Metric metric, ACMachine *machine, const void *text, uint64_t n_symbol
     return rc;
   }
   return routed_scan (machine, RecordPath::OnSuccessOrOverflow, host_loop, [&] (ACMPlan *plan) {
-    return scan_set_host (metric, plan, text, n_symbols, 0, offsets, n_texts, spell_data, spell_off, k, terms, tgt_ptr, n_targets, tpl, out, dist,
-                          out_capacity, n_found);
+    return scan_set_host (metric, ScanJoinHost{ plan, text, n_symbols, 0, offsets, n_texts, out, dist, out_capacity, n_found }, spell_data, spell_off, k, terms,
+                          tgt_ptr, n_targets, tpl);
   });
 }
 } // namespace

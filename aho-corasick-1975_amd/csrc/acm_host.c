@@ -1483,6 +1483,13 @@ acm_segment_records (ACMRecord *records, uint64_t n, const uint32_t *cost, uint6
 }
 #undef REL_END
 
+/* Whether a record breaks the contract of the passes that take a record set (below): its end lies outside
+ * [pos_base, pos_base + n_symbols), its length is 0, or it begins in front of pos_base. */
+static inline int
+record_breaks_contract (const ACMRecord *r, uint64_t pos_base, uint64_t n_symbols) {
+  return r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base;
+}
+
 /* WORDS of a record set (include/acm_gpu.h): the plain sequential pass, in place in the front of the
  * array.  Symbols are unsigned little-endian integers of sym_bytes bytes.  Everything is checked
  * first, so that nothing is modified when the call fails. */
@@ -1527,7 +1534,7 @@ acm_words_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, uin
   }
   for (uint64_t j = 0; j < n; j++) {
     const ACMRecord *r = &records[j];
-    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+    if (record_breaks_contract (r, pos_base, n_symbols))
       return ACM_GPU_E_ARG;
   }
   const unsigned char *t = text;
@@ -1613,7 +1620,7 @@ acm_context_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, u
   const int merge = (flags & ACM_CONTEXT_MERGE) != 0, texts = (flags & ACM_CONTEXT_TEXTS) != 0;
   for (uint64_t j = 0; j < n; j++) {
     const ACMRecord *r = &records[j];
-    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+    if (record_breaks_contract (r, pos_base, n_symbols))
       return ACM_GPU_E_ARG;
     if (merge && j > 0 && records[j - 1].end_pos > r->end_pos)
       return ACM_GPU_E_ARG;
@@ -1758,7 +1765,7 @@ acm_replace_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, u
   uint64_t next = 0, need = n_symbols; /* the first symbol no record has taken yet (relative to the text) */
   for (uint64_t j = 0; j < n; j++) {
     const ACMRecord *r = &records[j];
-    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+    if (record_breaks_contract (r, pos_base, n_symbols))
       return ACM_GPU_E_ARG;
     const uint64_t start = r->end_pos - pos_base + 1 - r->length;
     if (start < next)
@@ -1880,7 +1887,7 @@ acm_tokens_records (const void *text, uint64_t n_symbols, uint32_t sym_bytes, ui
   uint64_t next = 0, u = 0; /* the first symbol no record has taken yet; the first offset behind the record's start */
   for (uint64_t j = 0; j < n; j++) {
     const ACMRecord *r = &records[j];
-    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+    if (record_breaks_contract (r, pos_base, n_symbols))
       return ACM_GPU_E_ARG;
     const uint64_t start = r->end_pos - pos_base + 1 - r->length;
     if (start < next)
@@ -2136,7 +2143,7 @@ acm_anchored_records (const uint64_t *offsets, uint64_t n_texts, uint32_t mode, 
       return ACM_GPU_E_ARG;
   for (uint64_t j = 0; j < n; j++) {
     const ACMRecord *r = &records[j];
-    if (r->end_pos >= offsets[n_texts] || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos)
+    if (record_breaks_contract (r, 0, offsets[n_texts])) /* (positions from 0; the last offset is the number of symbols) */
       return ACM_GPU_E_ARG;
     if (r->end_pos >= offsets[anchored_text_of (offsets, n_texts, r->end_pos + 1 - r->length) + 1]) /* across a cut */
       return ACM_GPU_E_ARG;
@@ -2341,7 +2348,7 @@ acm_patterns_records (const ACMRecord *records, uint64_t n, uint64_t n_symbols, 
   }
   for (uint64_t j = 0; j < n; j++) {
     const ACMRecord *r = &records[j];
-    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+    if (record_breaks_contract (r, pos_base, n_symbols))
       return ACM_GPU_E_ARG;
   }
   struct pat_post *post = malloc ((n_patterns ? n_patterns : 1) * sizeof *post);
@@ -2494,7 +2501,7 @@ acm_chains_records (const ACMRecord *records, uint64_t n, uint64_t n_symbols, ui
   }
   for (uint64_t j = 0; j < n; j++) {
     const ACMRecord *r = &records[j];
-    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+    if (record_breaks_contract (r, pos_base, n_symbols))
       return ACM_GPU_E_ARG;
   }
   /* per chain the dynamic programme over its levels: best[i] = the greatest start of an embedding of the terms so far whose
@@ -2755,7 +2762,7 @@ approx_core (const ACMRecord *records, uint64_t n, const void *text, uint64_t n_
   }
   for (uint64_t j = 0; j < n; j++) {
     const ACMRecord *r = &records[j];
-    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+    if (record_breaks_contract (r, pos_base, n_symbols))
       return ACM_GPU_E_ARG;
   }
   const uint64_t n_terms = A->tgt_ptr[n_targets];
@@ -3102,7 +3109,7 @@ edit_core (const ACMRecord *records, uint64_t n, const void *text, uint64_t n_sy
   }
   for (uint64_t j = 0; j < n; j++) {
     const ACMRecord *r = &records[j];
-    if (r->end_pos < pos_base || r->end_pos - pos_base >= n_symbols || r->length == 0 || (uint64_t)r->length - 1 > r->end_pos - pos_base)
+    if (record_breaks_contract (r, pos_base, n_symbols))
       return ACM_GPU_E_ARG;
   }
   const uint64_t n_terms = A->tgt_ptr[n_targets];

@@ -161,6 +161,59 @@ constexpr uint32_t IT_OUT = 1u << 29;   /* report the outputs of the state itsel
  * walk on from it with no hotfail bound (walk_continuation) */
 constexpr uint32_t IT_WALK = 1u << 30;
 
+/* Whether a record breaks the contract of the calls that take a record set: its end lies outside [pos_base,
+ * pos_base + n_symbols), its length is 0, or it begins in front of pos_base.  Such a record is skipped and the
+ * plan's error flag raised (select's rule). */
+__device__ __forceinline__ bool
+record_breaks_contract (uint64_t pos, uint32_t length, uint64_t pos_base, uint64_t n_symbols) {
+  return pos < pos_base || pos - pos_base >= n_symbols || length == 0 || (uint64_t)length - 1 > pos - pos_base;
+}
+
+/* The joins of a record set under a compiled set (PATTERNS, CHAINS, APPROX and what runs APPROX's passes): control
+ * words at the head of the passes' scratch, cleared in front of every call ... */
+struct JoinCtl {
+  unsigned long long n; /* records the passes work on (0 after an overflow and under bad offsets) */
+  unsigned int bad;     /* offsets[] break the batch contract (offsets_check_kernel): nothing matches */
+  unsigned int pad;
+};
+
+/* ... and the head of their kernel arguments: PatternsK, ChainsK and ApproxK derive from it and add the compiled set
+ * and what their passes alone need */
+struct JoinK {
+  const ACMRecord *in;             /* canonical order */
+  uint64_t capacity;               /* of `in`; the count itself when n_dev is NULL */
+  const unsigned long long *n_dev; /* the record count (device), or NULL */
+  uint64_t n_symbols, pos_base;
+  const uint64_t *offsets;         /* [n_texts + 1], NULL: one text */
+  uint64_t n_texts;
+  uint32_t tile;                   /* records per tile, a multiple of WAVE */
+  uint64_t n_tiles;                /* tiles of `capacity` records */
+  unsigned long long *count;       /* [capacity + 1] matches per record (the last entry stays 0) */
+  const unsigned long long *first; /* [capacity + 1] their exclusive prefix sum: [capacity] = all matches */
+  ACMRecord *out;
+  uint64_t out_capacity;
+  unsigned long long *d_count;
+  JoinCtl *ctl;
+  unsigned int *error; /* the plan's device-side flag (acm_gpu_plan_status) */
+};
+
+/* The postings [begin, end) of record r's keyword in a set's index post_ptr[n_keywords + 1]; a record that breaks
+ * the contract sets `bad` (which is never cleared here: callers gather it over their records) and has no posting,
+ * and neither has a keyword the plan got after the set was made.  (CHAINS, whose bad records keep their postings,
+ * has a form of its own: chains_postings.) */
+__device__ __forceinline__ void
+join_postings (const JoinK &K, const uint32_t *post_ptr, uint32_t n_keywords, const uint4 r, uint32_t &begin, uint32_t &end, bool &bad) {
+  begin = end = 0;
+  if (record_breaks_contract (((uint64_t)r.y << 32) | r.x, r.z, K.pos_base, K.n_symbols)) {
+    bad = true;
+    return;
+  }
+  if (r.w < n_keywords) {
+    begin = post_ptr[r.w];
+    end = post_ptr[r.w + 1];
+  }
+}
+
 #include "dev_emit.h"
 #include "dev_dense.h"
 #include "dev_csr.h"
@@ -193,5 +246,9 @@ constexpr uint32_t IT_WALK = 1u << 30;
 #include "dev_segment.h"
 #include "dev_score.h"
 #include "dev_index.h"
+
+static_assert (WORDS_THREADS == OFFSETS_CHECK_THREADS && CONTEXT_THREADS == OFFSETS_CHECK_THREADS && ANCHORED_THREADS == OFFSETS_CHECK_THREADS &&
+                 PATTERNS_THREADS == OFFSETS_CHECK_THREADS && APPROX_THREADS == OFFSETS_CHECK_THREADS,
+               "offsets_check_kernel is launched with the block of the family it checks for");
 
 } // namespace

@@ -13,7 +13,7 @@
  * depth and the records of a text come out by ascending length with no merge.  A state s reached
  * after d symbols is a keyword's end iff oinfo[s] has outputs and its first output's length is d
  * (the first output of a state is its longest: the state's own keyword when it is terminal).
- * Behind anchored_check_kernel (the batch contract on offsets[]: first 0, last n_symbols,
+ * Behind offsets_check_kernel (dev_batch.h; the batch contract on offsets[]: first 0, last n_symbols,
  * non-decreasing, checked in a launch of its own so that no address is formed from an offset the
  * check has not seen), two passes with a prefix sum between them (hipCUB, 64-bit, over n_texts + 1
  * entries):
@@ -73,22 +73,6 @@ struct AnchoredK {
   AnchoredCtl *ctl;
   unsigned int *error; /* the plan's device-side flag (acm_gpu_plan_status) */
 };
-
-/* the batch contract on offsets[]: batch_index_kernel's check */
-__global__ __launch_bounds__ (ANCHORED_THREADS) void
-anchored_check_kernel (AnchoredK K) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, me = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool bad = false;
-  if (me == 0)
-    bad = K.offsets[0] != 0 || K.offsets[K.n_texts] != K.n_symbols;
-  for (uint64_t t = me; t < K.n_texts; t += stride)
-    bad = bad || K.offsets[t] > K.offsets[t + 1];
-  if (bad) {
-    K.ctl->bad = 1;
-    if (K.error)
-      *K.error = 1;
-  }
-}
 
 /* symbol i of a walked text: one naturally aligned load */
 template <int SB>

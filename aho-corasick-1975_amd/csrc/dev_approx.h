@@ -7,9 +7,9 @@
  * inverted by term keyword -- a keyword's postings (target id, term index j, offset, term length) sorted by
  * (target id, j) --, per target (L, k, its first term), the terms, and the spellings in the caller's symbols.
  * One GROUP of 16 consecutive lanes takes one input record, so a wave takes four records at a time; tiles of
- * K.tile records (a multiple of 64), blocks stride over the tiles.  Behind approx_check_kernel (offsets[]
- * given: the batch contract, checked in a launch of its own so that no address is formed from an offset the
- * check has not seen):
+ * K.tile records (a multiple of 64), blocks stride over the tiles.  Behind offsets_check_kernel (dev_batch.h;
+ * offsets[] given: the batch contract, checked in a launch of its own so that no address is formed from an offset
+ * the check has not seen):
  *   1. approx_count_kernel: count[i] = the matches seeded by record i.  Per posting the group runs the cheap
  *      tests (all 16 lanes the same: the term's length is the record's, S >= 0, the text of S by a bisection
  *      of offsets[], S + L ends inside that text).  Then the group verifies: lane j compares symbols j,
@@ -37,19 +37,12 @@
 constexpr uint32_t APPROX_THREADS = 256, APPROX_GROUP = 16, APPROX_PER_WAVE = WAVE / APPROX_GROUP, APPROX_PER_BLOCK = APPROX_THREADS / APPROX_GROUP;
 constexpr uint32_t APPROX_TILE_DEFAULT = 1024, APPROX_TILE_MIN = 64, APPROX_TILE_MAX = 1u << 20; /* records */
 
-/* control words at the head of the pass's scratch, cleared in front of every call */
-struct ApproxCtl {
-  unsigned long long n; /* records the passes work on (0 after an overflow and under bad offsets) */
-  unsigned int bad;     /* offsets[] break the batch contract: nothing matches */
-  unsigned int pad;
-};
-
 /* a term of a target: the piece of `length` symbols at `offset` is keyword keyword_id */
 struct ApproxTerm {
   uint32_t offset, length, keyword_id;
 };
 
-struct ApproxK {
+struct ApproxK : JoinK { /* (count[i]: the matches seeded by record i) */
   /* the compiled set (ACMApprox) */
   const uint32_t *post_ptr;  /* [n_keywords + 1] the postings of a keyword */
   const uint4 *post;         /* { target id, term index j inside the target, the term's offset, the term's length } */
@@ -58,28 +51,13 @@ struct ApproxK {
   const ApproxTerm *terms;
   const void *spell; /* the spellings, symbols of the caller's size */
   uint32_t n_keywords;
-  uint32_t longest, tgt_bits;      /* the longest L; bits of a target id (sort key 1) */
-  const ACMRecord *in;             /* canonical order */
-  uint64_t capacity;               /* of `in`; the count itself when n_dev is NULL */
-  const unsigned long long *n_dev; /* the record count (device), or NULL */
-  const void *text;                /* the caller's symbols */
-  uint64_t n_symbols, pos_base;
-  const uint64_t *offsets; /* [n_texts + 1], NULL: one text */
-  uint64_t n_texts;
-  uint32_t tile;                   /* records per tile, a multiple of WAVE */
-  uint64_t n_tiles;                /* tiles of `capacity` records */
-  unsigned long long *count;       /* [capacity + 1] matches per seed record (the last entry stays 0) */
-  const unsigned long long *first; /* [capacity + 1] their exclusive prefix sum: [capacity] = all matches */
-  ACMRecord *fill;                 /* [out_capacity] the matches in fill order (scratch) */
-  uint32_t *fill_dist;             /* [out_capacity] their distances */
-  uint64_t *key;                   /* [out_capacity] the sort key a key kernel writes */
-  uint32_t *idx, *idx_from;        /* [out_capacity] the permutation a kernel writes / reads */
-  ACMRecord *out;
-  uint32_t *dist; /* may be NULL */
-  uint64_t out_capacity;
-  unsigned long long *d_count;
-  ApproxCtl *ctl;
-  unsigned int *error; /* the plan's device-side flag (acm_gpu_plan_status) */
+  uint32_t longest, tgt_bits; /* the longest L; bits of a target id (sort key 1) */
+  const void *text;           /* the caller's symbols */
+  ACMRecord *fill;            /* [out_capacity] the matches in fill order (scratch) */
+  uint32_t *fill_dist;        /* [out_capacity] their distances */
+  uint64_t *key;              /* [out_capacity] the sort key a key kernel writes */
+  uint32_t *idx, *idx_from;   /* [out_capacity] the permutation a kernel writes / reads */
+  uint32_t *dist;             /* beside JoinK::out; may be NULL */
   /* TEMPLATES only (dev_templates.h): the cells beside the spellings and the compiled classes */
   const uint32_t *cells;      /* [the spellings' symbols] ACM_TEMPLATE_LITERAL, ACM_TEMPLATE_ANY or a class id */
   const uint32_t *cls_bitmap; /* 1-byte symbols: [n_classes][8] the accepted symbols, the negate flag applied */
@@ -87,37 +65,6 @@ struct ApproxK {
   const void *cls_ranges;     /* ... pairs lo, hi of the caller's size ... */
   const uint32_t *cls_flags;  /* ... and ACM_TEMPLATE_NEGATED */
 };
-
-/* the batch contract on offsets[]: batch_index_kernel's check */
-__global__ __launch_bounds__ (APPROX_THREADS) void
-approx_check_kernel (ApproxK K) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, me = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool bad = false;
-  if (me == 0)
-    bad = K.offsets[0] != 0 || K.offsets[K.n_texts] != K.n_symbols;
-  for (uint64_t t = me; t < K.n_texts; t += stride)
-    bad = bad || K.offsets[t] > K.offsets[t + 1];
-  if (bad) {
-    K.ctl->bad = 1;
-    if (K.error)
-      *K.error = 1;
-  }
-}
-
-/* the postings [begin, end) of record r's keyword; `bad` says that the record breaks the contract (no posting then) */
-__device__ __forceinline__ void
-approx_postings (const ApproxK &K, const uint4 r, uint32_t &begin, uint32_t &end, bool &bad) {
-  const uint64_t pos = ((uint64_t)r.y << 32) | r.x;
-  begin = end = 0;
-  if (pos < K.pos_base || pos - K.pos_base >= K.n_symbols || r.z == 0 || (uint64_t)r.z - 1 > pos - K.pos_base) {
-    bad = true;
-    return;
-  }
-  if (r.w < K.n_keywords) { /* (a keyword the plan got after the set was made seeds nothing) */
-    begin = K.post_ptr[r.w];
-    end = K.post_ptr[r.w + 1];
-  }
-}
 
 /* What a wave does with its four records: every group walks the postings [q, q_end) of its record r (none: q ==
  * q_end) and returns the number of matches it seeds; with FILL it stores them from slot `at` on.  All 64 lanes
@@ -210,7 +157,7 @@ approx_count_kernel (ApproxK K) {
       uint32_t q = 0, q_end = 0;
       if (i < n) {
         r = *reinterpret_cast<const uint4 *> (&K.in[i]);
-        approx_postings (K, r, q, q_end, bad);
+        join_postings (K, K.post_ptr, K.n_keywords, r, q, q_end, bad);
       }
       const uint32_t found = approx_group<T, false, CELLS> (K, n, r, q, q_end, 0);
       if (i < end && (lane & (APPROX_GROUP - 1)) == 0)
@@ -244,7 +191,7 @@ approx_fill_kernel (ApproxK K) {
         if (at != K.first[i + 1]) { /* (else: pass 1 found no match here) */
           bool bad = false;
           r = *reinterpret_cast<const uint4 *> (&K.in[i]);
-          approx_postings (K, r, q, q_end, bad);
+          join_postings (K, K.post_ptr, K.n_keywords, r, q, q_end, bad);
         }
       }
       (void)approx_group<T, true, CELLS> (K, n, r, q, q_end, at);

@@ -79,6 +79,26 @@ batch_text_of (const uint64_t *__restrict__ offsets, uint64_t lo, uint64_t hi, u
   return lo;
 }
 
+/* The batch contract on offsets[] (first 0, last n_symbols, non-decreasing) for every family that bisects
+ * offsets[] per record -- WORDS, CONTEXT, ANCHORED and the joins (JoinK) --, in a launch of its own so that no
+ * address is formed from an offset the check has not seen.  `bad` is the family's control word (cleared by the
+ * caller), `error` the plan's flag.  batch_index_kernel's check, without its index. */
+constexpr uint32_t OFFSETS_CHECK_THREADS = 256;
+__global__ __launch_bounds__ (OFFSETS_CHECK_THREADS) void
+offsets_check_kernel (const uint64_t *offsets, uint64_t n_texts, uint64_t n_symbols, unsigned int *bad_word, unsigned int *error) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, me = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool bad = false;
+  if (me == 0)
+    bad = offsets[0] != 0 || offsets[n_texts] != n_symbols;
+  for (uint64_t t = me; t < n_texts; t += stride)
+    bad = bad || offsets[t] > offsets[t + 1];
+  if (bad) {
+    *bad_word = 1;
+    if (error)
+      *error = 1;
+  }
+}
+
 template <bool HEADS>
 __global__ __launch_bounds__ (BATCH_THREADS) void
 batch_index_kernel (BatchK K) {

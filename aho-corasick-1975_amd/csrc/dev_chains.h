@@ -9,8 +9,8 @@
  * postings of a keyword, so the room is a function of the arguments alone); a slot holds S + 1 for the
  * greatest start S of an embedding of the chain's terms 0 .. j that ends in this record, 0 for "none",
  * so that the best of a window is a plain maximum.  Tiles of K.tile records (a multiple of 64), blocks
- * stride over the tiles, a wave takes 64 consecutive records at a time.  Behind patterns_check_kernel
- * (dev_patterns.h: the batch contract on offsets[] in a launch of its own):
+ * stride over the tiles, a wave takes 64 consecutive records at a time.  Behind offsets_check_kernel
+ * (dev_batch.h: the batch contract on offsets[] in a launch of its own):
  *   1. chains_level_kernel, once per level j of the set (max_terms launches): the lanes whose keyword
  *      has a posting of level j fill its slot.  Level 0 writes the record's own start.  Level j >= 1:
  *      the window of a record that begins at s is the records that end in [s - 1 - gap_max,
@@ -50,30 +50,15 @@ struct ChainPost {
 };
 static_assert (sizeof (ChainPost) == 32, "two uint4");
 
-struct ChainsK {
+struct ChainsK : JoinK {
   /* the compiled set (ACMChains) */
   const uint32_t *post_ptr; /* [n_keywords + 1] the postings of a keyword, by level then chain */
   const ChainPost *post;
   uint32_t n_keywords;
-  uint32_t stride;                 /* state slots per record: the most postings of a keyword (at least 1) */
-  uint32_t level;                  /* the level this launch fills */
-  uint32_t coop;                   /* windows of more records are walked by the wave */
-  const ACMRecord *in;             /* canonical order */
-  uint64_t capacity;               /* of `in`; the count itself when n_dev is NULL */
-  const unsigned long long *n_dev; /* the record count (device), or NULL */
-  uint64_t n_symbols, pos_base;
-  const uint64_t *offsets; /* [n_texts + 1], NULL: one text */
-  uint64_t n_texts;
-  uint32_t tile;                   /* records per tile, a multiple of WAVE */
-  uint64_t n_tiles;                /* tiles of `capacity` records */
-  unsigned long long *state;       /* [capacity * stride] S + 1, or 0 */
-  unsigned long long *count;       /* [capacity + 1] matches per record (the last entry stays 0) */
-  const unsigned long long *first; /* [capacity + 1] their exclusive prefix sum: [capacity] = all matches */
-  ACMRecord *out;
-  uint64_t out_capacity;
-  unsigned long long *d_count;
-  PatternsCtl *ctl;    /* patterns_check_kernel's words */
-  unsigned int *error; /* the plan's device-side flag (acm_gpu_plan_status) */
+  uint32_t stride;           /* state slots per record: the most postings of a keyword (at least 1) */
+  uint32_t level;            /* the level this launch fills */
+  uint32_t coop;             /* windows of more records are walked by the wave */
+  unsigned long long *state; /* [capacity * stride] S + 1, or 0 */
 };
 
 /* the records the passes work on: none after an overflowing scan and under bad offsets */
@@ -83,13 +68,12 @@ chains_n (const ChainsK &K) {
   return n_raw > K.capacity || K.ctl->bad ? 0 : n_raw;
 }
 
-/* the postings [begin, end) of record r's keyword (none for a keyword the plan got after the set was made); `bad` says that the
- * record breaks the contract */
+/* the postings [begin, end) of record r's keyword (none for a keyword the plan got after the set was made); `bad` says whether
+ * the record breaks the contract -- it has its postings all the same (join_postings gives it none), and the passes test `bad` */
 __device__ __forceinline__ void
 chains_postings (const ChainsK &K, const uint4 r, uint32_t &begin, uint32_t &end, bool &bad) {
-  const uint64_t pos = ((uint64_t)r.y << 32) | r.x;
   begin = end = 0;
-  bad = pos < K.pos_base || pos - K.pos_base >= K.n_symbols || r.z == 0 || (uint64_t)r.z - 1 > pos - K.pos_base;
+  bad = record_breaks_contract (((uint64_t)r.y << 32) | r.x, r.z, K.pos_base, K.n_symbols);
   if (r.w < K.n_keywords) {
     begin = K.post_ptr[r.w];
     end = K.post_ptr[r.w + 1];

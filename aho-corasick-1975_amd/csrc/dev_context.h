@@ -6,7 +6,7 @@
  * gather, and no pass is proportional to the text -- a record's text is a bisection of offsets[]
  * (WORDS' way: no index over the buffer, so the scratch is sized by the records alone).  Tiles of
  * K.tile records (a multiple of 64), blocks stride over the tiles, a block takes CONTEXT_THREADS
- * records of its tile at a time.  Behind context_check_kernel (offsets[] given: the batch contract,
+ * records of its tile at a time.  Behind offsets_check_kernel (dev_batch.h; offsets[] given: the batch contract,
  * in a launch of its own so that no address is formed from an offset the check has not seen):
  *   1. context_window_kernel: a lane takes CONTEXT_PER records 256 apart, validates them (WORDS' test;
  *      under MERGE also that end_pos does not decrease from the record in front), finds their texts --
@@ -51,7 +51,7 @@ static_assert (CONTEXT_THREADS == REPLACE_THREADS, "replace_wave_count_le and re
 /* control words at the head of the passes' scratch, cleared in front of every call */
 struct ContextCtl {
   unsigned long long n; /* records the passes work on (0 after an overflow and under bad offsets) */
-  unsigned int bad;     /* offsets[] break the batch contract (context_check_kernel) */
+  unsigned int bad;     /* offsets[] break the batch contract (offsets_check_kernel) */
   unsigned int n_bad;   /* records that break the contract, or the order under MERGE (pass 1) */
   unsigned int over;    /* *d_n > capacity: a scan that overflowed */
   unsigned int pad;
@@ -90,22 +90,6 @@ struct ContextK {
 __device__ __forceinline__ bool
 context_stopped (const ContextK &K) {
   return K.ctl->bad != 0 || K.ctl->n_bad != 0 || K.ctl->over != 0;
-}
-
-/* the batch contract on offsets[]: batch_index_kernel's check */
-__global__ __launch_bounds__ (CONTEXT_THREADS) void
-context_check_kernel (ContextK K) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, me = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool bad = false;
-  if (me == 0)
-    bad = K.offsets[0] != 0 || K.offsets[K.n_texts] != K.n_symbols;
-  for (uint64_t t = me; t < K.n_texts; t += stride)
-    bad = bad || K.offsets[t] > K.offsets[t + 1];
-  if (bad) {
-    K.ctl->bad = 1;
-    if (K.error)
-      *K.error = 1;
-  }
 }
 
 enum { CONTEXT_MIN, CONTEXT_MAX, CONTEXT_ADD };
@@ -179,7 +163,7 @@ __device__ __forceinline__ bool
 context_record (const ContextK &K, const uint4 r, uint64_t &s, uint64_t &e) {
   const uint64_t pos = ((uint64_t)r.y << 32) | r.x;
   s = e = 0;
-  if (pos < K.pos_base || pos - K.pos_base >= K.n_symbols || r.z == 0 || (uint64_t)r.z - 1 > pos - K.pos_base)
+  if (record_breaks_contract (pos, r.z, K.pos_base, K.n_symbols))
     return false;
   e = pos - K.pos_base;
   s = e + 1 - r.z;

@@ -190,7 +190,7 @@ edit_count_kernel (ApproxK K) {
       uint32_t q = 0, q_end = 0;
       if (i < n) {
         r = *reinterpret_cast<const uint4 *> (&K.in[i]);
-        approx_postings (K, r, q, q_end, bad);
+        join_postings (K, K.post_ptr, K.n_keywords, r, q, q_end, bad);
       }
       const uint32_t found = edit_group<T, G, false> (K, n, r, q, q_end, 0);
       if (i < end && (lane & (G - 1)) == 0)
@@ -225,7 +225,7 @@ edit_fill_kernel (ApproxK K) {
         if (at != K.first[i + 1]) { /* (else: pass 1 found no match here) */
           bool bad = false;
           r = *reinterpret_cast<const uint4 *> (&K.in[i]);
-          approx_postings (K, r, q, q_end, bad);
+          join_postings (K, K.post_ptr, K.n_keywords, r, q, q_end, bad);
         }
       }
       (void)edit_group<T, G, true> (K, n, r, q, q_end, at);

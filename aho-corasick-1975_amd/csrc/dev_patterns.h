@@ -11,9 +11,9 @@
  * inside that text, and looks every other term up in the records by its key (end_pos, length) -- unique
  * in canonical order -- with a bisection over the whole input; the keyword id decides.
  * Tiles of K.tile records (a multiple of 64), blocks stride over the tiles, a wave takes 64 consecutive
- * records at a time.  Behind patterns_check_kernel (offsets[] given: the batch contract, first 0, last
- * n_symbols, non-decreasing, checked in a launch of its own so that no address is formed from an offset
- * the check has not seen):
+ * records at a time.  Behind offsets_check_kernel (dev_batch.h; offsets[] given: the batch contract, first
+ * 0, last n_symbols, non-decreasing, checked in a launch of its own so that no address is formed from an
+ * offset the check has not seen):
  *   1. patterns_count_kernel: count[i] = the matches anchored at record i.  A record that breaks the
  *      contract (a position outside [pos_base, pos_base + n_symbols), a start below pos_base, a length
  *      of 0) is skipped and the plan's error flag raised (select's rule).  A wave in which no lane's
@@ -33,57 +33,19 @@
 constexpr uint32_t PATTERNS_THREADS = 256;
 constexpr uint32_t PATTERNS_TILE_DEFAULT = 4096, PATTERNS_TILE_MIN = 64, PATTERNS_TILE_MAX = 1u << 20; /* records */
 
-/* control words at the head of the pass's scratch, cleared in front of every call */
-struct PatternsCtl {
-  unsigned long long n; /* records the passes work on (0 after an overflow and under bad offsets) */
-  unsigned int bad;     /* offsets[] break the batch contract: nothing matches */
-  unsigned int pad;
-};
-
 /* a term of a pattern other than its anchor: where it ends in front of the pattern's end */
 struct PatternOther {
   uint32_t back, length, keyword_id;
 };
 
-struct PatternsK {
+struct PatternsK : JoinK { /* (count[i]: the matches anchored at record i) */
   /* the compiled set (ACMPatterns) */
   const uint32_t *anchor_ptr; /* [n_keywords + 1] the postings of a keyword */
   const uint4 *post;          /* { pattern id, L, the anchor term's length, unused } */
   const uint32_t *other_ptr;  /* [n_patterns + 1] a pattern's other terms */
   const PatternOther *other;
   uint32_t n_keywords;
-  const ACMRecord *in;             /* canonical order */
-  uint64_t capacity;               /* of `in`; the count itself when n_dev is NULL */
-  const unsigned long long *n_dev; /* the record count (device), or NULL */
-  uint64_t n_symbols, pos_base;
-  const uint64_t *offsets;           /* [n_texts + 1], NULL: one text */
-  uint64_t n_texts;
-  uint32_t tile;                   /* records per tile, a multiple of WAVE */
-  uint64_t n_tiles;                /* tiles of `capacity` records */
-  unsigned long long *count;       /* [capacity + 1] matches per anchor record (the last entry stays 0) */
-  const unsigned long long *first; /* [capacity + 1] their exclusive prefix sum: [capacity] = all matches */
-  ACMRecord *out;
-  uint64_t out_capacity;
-  unsigned long long *d_count;
-  PatternsCtl *ctl;
-  unsigned int *error; /* the plan's device-side flag (acm_gpu_plan_status) */
 };
-
-/* the batch contract on offsets[]: batch_index_kernel's check */
-__global__ __launch_bounds__ (PATTERNS_THREADS) void
-patterns_check_kernel (PatternsK K) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, me = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool bad = false;
-  if (me == 0)
-    bad = K.offsets[0] != 0 || K.offsets[K.n_texts] != K.n_symbols;
-  for (uint64_t t = me; t < K.n_texts; t += stride)
-    bad = bad || K.offsets[t] > K.offsets[t + 1];
-  if (bad) {
-    K.ctl->bad = 1;
-    if (K.error)
-      *K.error = 1;
-  }
-}
 
 /* whether the record (end_pos, length, keyword_id) is among in[0 .. n): a bisection for the first record
  * at or behind the key (end_pos ascending, length descending).  Shared with dev_approx.h. */
@@ -124,21 +86,6 @@ patterns_match (const PatternsK &K, uint64_t n, uint64_t e, uint32_t length, con
   return true;
 }
 
-/* the postings [begin, end) of record r's keyword; `bad` says that the record breaks the contract (no posting then) */
-__device__ __forceinline__ void
-patterns_postings (const PatternsK &K, const uint4 r, uint32_t &begin, uint32_t &end, bool &bad) {
-  const uint64_t pos = ((uint64_t)r.y << 32) | r.x;
-  begin = end = 0;
-  if (pos < K.pos_base || pos - K.pos_base >= K.n_symbols || r.z == 0 || (uint64_t)r.z - 1 > pos - K.pos_base) {
-    bad = true;
-    return;
-  }
-  if (r.w < K.n_keywords) { /* (a keyword the plan got after the set was made anchors nothing) */
-    begin = K.anchor_ptr[r.w];
-    end = K.anchor_ptr[r.w + 1];
-  }
-}
-
 /* pass 1 */
 __global__ __launch_bounds__ (PATTERNS_THREADS) void
 patterns_count_kernel (PatternsK K) {
@@ -159,7 +106,7 @@ patterns_count_kernel (PatternsK K) {
       uint32_t q = 0, q_end = 0;
       if (i < n) {
         r = *reinterpret_cast<const uint4 *> (&K.in[i]);
-        patterns_postings (K, r, q, q_end, bad);
+        join_postings (K, K.anchor_ptr, K.n_keywords, r, q, q_end, bad);
       }
       uint32_t found = 0;
       if (__ballot (q < q_end)) { /* (else: no lane of the wave anchors anything) */
@@ -198,7 +145,7 @@ patterns_fill_kernel (PatternsK K) {
       const uint4 r = *reinterpret_cast<const uint4 *> (&K.in[i]);
       uint32_t q = 0, q_end = 0;
       bool bad = false;
-      patterns_postings (K, r, q, q_end, bad);
+      join_postings (K, K.anchor_ptr, K.n_keywords, r, q, q_end, bad);
       const uint64_t e = (((uint64_t)r.y << 32) | r.x) - K.pos_base;
       for (; q < q_end && at < at_end; q++) { /* (at < at_end always: pass 1 counted the same matches) */
         const uint4 p = K.post[q];
@@ -218,9 +165,9 @@ patterns_before (const uint4 a, const uint4 b) {
   return a.z > b.z || (a.z == b.z && a.w < b.w);
 }
 
-/* pass 3 */
+/* pass 3 (CHAINS runs it too: it reads the head alone) */
 __global__ __launch_bounds__ (PATTERNS_THREADS) void
-patterns_order_kernel (PatternsK K) {
+patterns_order_kernel (JoinK K) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, me = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const unsigned long long total = K.first[K.capacity];
   if (total > K.out_capacity) /* the output is unspecified */

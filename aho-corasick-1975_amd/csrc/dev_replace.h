@@ -87,7 +87,7 @@ replace_fact (const ReplaceK &K, uint64_t i, uint64_t &start, uint64_t &after, u
   const uint64_t pos = ((uint64_t)r.y << 32) | r.x;
   len = r.z;
   if (CHECK) {
-    if (pos < K.pos_base || pos - K.pos_base >= K.n_symbols || len == 0 || (uint64_t)len - 1 > pos - K.pos_base)
+    if (record_breaks_contract (pos, len, K.pos_base, K.n_symbols))
       return false;
     if (i > 0) { /* behind the record in front of it (which answers for its own range) */
       const uint64_t prev = K.sel[i - 1].end_pos;

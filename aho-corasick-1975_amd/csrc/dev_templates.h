@@ -4,7 +4,7 @@
  * A template is a target of dev_approx.h whose positions are CELLS: a literal cell accepts its spelling's
  * symbol, an ANY cell every symbol, a class cell the symbols of a class.  The pieces stand on literal cells,
  * so seeds, postings, the cheap tests, the passes and the order are APPROX's, and they are APPROX's code: the
- * kernels are approx_count_kernel<T, true> and approx_fill_kernel<T, true> behind approx_check_kernel, and the
+ * kernels are approx_count_kernel<T, true> and approx_fill_kernel<T, true> behind offsets_check_kernel, and the
  * three order kernels behind them.  What is new is the acceptance test that a lane of the group runs on its
  * cell, below.  The compiled set (ACMTemplates) adds to APPROX's tables the cell words, one uint32_t beside
  * every symbol of the spellings, and the classes:

@@ -116,7 +116,7 @@ tokens_check_kernel (TokensK K) {
   for (uint64_t i = me; i < n; i += stride) {
     const ACMRecord r = K.sel[i];
     const uint64_t pos = r.end_pos;
-    if (pos < K.pos_base || pos - K.pos_base >= K.n_symbols || r.length == 0 || (uint64_t)r.length - 1 > pos - K.pos_base) {
+    if (record_breaks_contract (pos, r.length, K.pos_base, K.n_symbols)) {
       bad++;
       continue;
     }

@@ -7,7 +7,7 @@
  * lies outside the record's text.  The word set is up to 16 inclusive ranges of the caller's
  * symbols, which arrive as kernel arguments; the symbols are the caller's own, bit for bit.
  * Tiles of K.tile records (a multiple of 64), blocks stride over the tiles, a wave takes 64
- * consecutive records at a time.  Behind words_check_kernel (offsets[] given: the batch contract,
+ * consecutive records at a time.  Behind offsets_check_kernel (dev_batch.h; offsets[] given: the batch contract,
  * first 0, last n_symbols, non-decreasing, checked in a launch of its own so that no address is
  * formed from an offset the check has not seen), two passes with a prefix sum between them
  * (hipCUB, 64-bit, over n_tiles + 1 entries):
@@ -57,22 +57,6 @@ struct WordsK {
   unsigned int *error;                 /* the plan's device-side flag (acm_gpu_plan_status) */
 };
 
-/* the batch contract on offsets[]: batch_index_kernel's check */
-__global__ __launch_bounds__ (WORDS_THREADS) void
-words_check_kernel (WordsK K) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x, me = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool bad = false;
-  if (me == 0)
-    bad = K.offsets[0] != 0 || K.offsets[K.n_texts] != K.n_symbols;
-  for (uint64_t t = me; t < K.n_texts; t += stride)
-    bad = bad || K.offsets[t] > K.offsets[t + 1];
-  if (bad) {
-    K.ctl->bad = 1;
-    if (K.error)
-      *K.error = 1;
-  }
-}
-
 /* symbol i of the text, i in [0, n_symbols): one naturally aligned load */
 template <int SB>
 __device__ __forceinline__ unsigned long long
@@ -100,7 +84,7 @@ template <int SB>
 __device__ __forceinline__ bool
 words_keep (const WordsK &K, const uint4 r, bool &bad) {
   const uint64_t pos = ((uint64_t)r.y << 32) | r.x;
-  if (pos < K.pos_base || pos - K.pos_base >= K.n_symbols || r.z == 0 || (uint64_t)r.z - 1 > pos - K.pos_base) {
+  if (record_breaks_contract (pos, r.z, K.pos_base, K.n_symbols)) {
     bad = true;
     return false;
   }

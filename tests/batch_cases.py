@@ -37,6 +37,21 @@ def oracle_batch_cut(o, text, offsets):
     return oracle_batch(o, [text[off[t]:off[t + 1]] for t in range(len(off) - 1)])
 
 
+def broken_last_pair(n):
+    """(what, offsets) of n symbols cut into 1, 2 and 257 texts, each with exactly one break of the
+    contract, in the LAST pair: one text -- its only pair begins with 0, so the last offset is n - 1
+    (the test of the two ends, thread 0 alone); more texts -- offsets[n_texts - 1] = n + 1 lies behind
+    offsets[n_texts] = n, which only the thread of pair n_texts - 1 sees: with 257 texts that is the
+    first thread of a second block of 256, or the second round of a block's stride"""
+    cases = [("1 text, the last not n", [0, n - 1])]
+    for n_texts in (2, 257):
+        off = np.linspace(0, n, n_texts + 1).astype(np.int64)
+        off[-2] = n + 1
+        assert off[0] == 0 and off[-1] == n and np.all(off[1:-1] >= off[:-2]) and off[-2] > off[-1]
+        cases.append(("%d texts, the last pair decreasing" % n_texts, off.tolist()))
+    return cases
+
+
 def random_cuts(n, mean, seed=7):
     """offsets of a buffer of n symbols cut at n // mean random points; some cut points are doubled
     and tripled so that empty texts occur, also at the very front and the very end"""

@@ -12,6 +12,7 @@ import aho_corasick_1975_amd as acm
 from aho_corasick_1975_amd import binding
 from oracle import pyoracle as po
 from tests import anchored_cases as ac
+from tests.batch_cases import broken_last_pair
 from tests.cases import build_pair
 from tests.tally_cases import KINDS, PATH_CLASSES, PATH_GPU, byte_oracle, kind
 
@@ -300,6 +301,7 @@ def test_offsets_that_break_the_contract_write_nothing(torch_cuda):
     cases["last"][-1] -= 1
     cases["decrease"][6], cases["decrease"][7] = off[7] + 3, off[6]
     assert cases["decrease"][6] > cases["decrease"][7]
+    cases.update((what, np.array(bad, off.dtype)) for what, bad in broken_last_pair(len(packed)))
     for what, bad in cases.items():
         d_bad = _dev(torch, bad.astype(np.int64))
         plan = m.plan(0)
@@ -314,7 +316,7 @@ def test_offsets_that_break_the_contract_write_nothing(torch_cuda):
         with pytest.raises(binding.ACMError) as e:
             plan.status()
         assert e.value.code == E_INTERNAL, what
-        if what != "last":   # (the host calls have no n_symbols argument: there the last offset IS the number of symbols)
+        if what in ("first", "decrease"):   # (the host calls have no n_symbols argument: there the last offset IS the number of symbols)
             nf = C.c_uint64(0)
             L = binding.lib()
             assert L.acm_gpu_scan_anchored_host(plan.h, packed, bad.ctypes.data, bad.size - 1, 1, None, None, None, 0, C.byref(nf)) == E_ARG

@@ -14,6 +14,7 @@ import aho_corasick_1975_amd as acm
 from aho_corasick_1975_amd import binding
 from oracle import pyoracle as po
 from tests.approx_cases import approx, brute, compile_targets, hamming_scan, oracle_records, same, seeds_of
+from tests.batch_cases import broken_last_pair
 from tests.tally_cases import PATH_GPU, kind
 
 pytestmark = pytest.mark.gpu
@@ -397,6 +398,57 @@ def test_out_capacity_counts_on_the_device_and_overflow(torch_cuda):
     plan.status()
 
 
+def test_approx_device_arguments(torch_cuda):
+    torch = torch_cuda
+    targets, ks, text, cut, rec, want = _main(1)
+    m, aset = _machine(1, targets, ks, cut)
+    plan = m.plan(0)
+    A = plan.approx_create(aset)
+    L = acm.lib()
+    dev = _dev(torch, text)
+    total = want[0].size
+    d_rec = _rec_dev(torch, rec, 2 * rec.size + total)
+    sentinel = np.zeros(total, po.RECORD_DTYPE)
+    sentinel["end_pos"], sentinel["length"], sentinel["keyword_id"] = SENTINEL, 7, 7
+    d_out = _rec_dev(torch, sentinel)
+    d_dist = torch.full((total,), 0x5A5A, dtype=torch.int32, device="cuda")
+    count = torch.full((1,), 0x5A5A, dtype=torch.int64, device="cuda")
+    tb = L.acm_gpu_approx_tmp_bytes(plan.h, A.h, rec.size, total, 0)
+    tmp = torch.empty(tb, dtype=torch.uint8, device="cuda")
+
+    def call(plan_h=plan.h, approx_h=A.h, records=d_rec.data_ptr(), n=rec.size, out=d_out.data_ptr(), cap=total, cnt=count.data_ptr(),
+             scratch=tmp.data_ptr(), tmp_bytes=tb, offsets=None, n_texts=0):
+        return L.acm_gpu_approx_records_device(plan_h, approx_h, records, n, None, dev.data_ptr(), text.size, 0, offsets, n_texts, out, d_dist.data_ptr(), cap,
+                                               cnt, scratch, tmp_bytes, None)
+    assert tb > 0 and total > 0
+    assert call(plan_h=None) == E_ARG and call(approx_h=None) == E_ARG and call(records=None) == E_ARG and call(out=None) == E_ARG
+    assert call(cnt=None) == E_ARG and call(scratch=None) == E_ARG and call(tmp_bytes=tb - 1) == E_ARG and call(n=1 << 31) == E_ARG
+    assert call(cap=1 << 31) == E_ARG
+    assert call(out=d_rec.data_ptr()) == E_ARG and call(out=d_rec.data_ptr() + 16 * (rec.size - 1)) == E_ARG     # d_out overlapping d_records
+    assert call(out=d_rec.data_ptr() - 16 * (total - 1)) == E_ARG
+    assert call(offsets=d_rec.data_ptr(), n_texts=0) == E_ARG                     # no text, but symbols
+    if torch.cuda.device_count() > 1:                                             # a set of another device
+        elsewhere = m.plan(1)
+        B = elsewhere.approx_create(aset)
+        assert call(approx_h=B.h) == E_ARG
+        B.close()
+        elsewhere.close()
+        torch.cuda.set_device(0)
+    torch.cuda.synchronize()
+    assert np.array_equal(_rec_host(d_out, total), sentinel) and np.all(_dist_host(d_dist, total) == 0x5A5A) and int(count.item()) == 0x5A5A   # nothing was touched
+    assert call(out=d_rec.data_ptr() + 16 * rec.size) == 0                        # right behind the records: no overlap
+    torch.cuda.synchronize()
+    same((_rec_host(d_rec[rec.size:], int(count.item())), _dist_host(d_dist, total)), want)
+    assert call() == 0
+    torch.cuda.synchronize()
+    same((_rec_host(d_out, int(count.item())), _dist_host(d_dist, total)), want)
+    assert call(n=0, records=None, scratch=None, tmp_bytes=0) == 0                # no record: no match
+    torch.cuda.synchronize()
+    assert int(count.item()) == 0
+    A.close()
+    plan.status()
+
+
 def test_offsets_that_break_the_contract_match_nothing(torch_cuda):
     torch = torch_cuda
     targets, ks, text, cut, rec, want = _main(1)
@@ -405,7 +457,7 @@ def test_offsets_that_break_the_contract_match_nothing(torch_cuda):
     sentinel = np.zeros(want[0].size, po.RECORD_DTYPE)
     sentinel["end_pos"] = SENTINEL
     dev = _dev(torch, text)
-    for what, off in (("decreasing", [0, 40, 30, n]), ("first not 0", [1, 40, n]), ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n])):
+    for what, off in (("decreasing", [0, 40, 30, n]), ("first not 0", [1, 40, n]), ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n]), *broken_last_pair(n)):
         plan = m.plan(0)
         plan.status()
         d_out = _rec_dev(torch, sentinel)

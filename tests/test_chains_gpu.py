@@ -12,7 +12,7 @@ import pytest
 import aho_corasick_1975_amd as acm
 from aho_corasick_1975_amd import binding
 from oracle import pyoracle as po
-from tests.batch_cases import offsets_of
+from tests.batch_cases import broken_last_pair, offsets_of
 from tests.chain_cases import (CASE_CHAINS, CASE_CUT, CASE_KEYWORDS, CASE_TEXT, as_records, case_facts, chain_terms, chains, chains_by_re,
                                fixed_offset_patterns, oracle_records, random_case)
 from tests.tally_cases import PATH_CLASSES, PATH_GPU
@@ -376,13 +376,62 @@ def test_counts_on_the_device_and_a_scan_that_overflowed(torch_cuda, fixed):
     plan.status()
 
 
+def test_chains_device_arguments(torch_cuda, fixed):
+    torch = torch_cuda
+    rec, want = fixed
+    n_symbols = len(CASE_TEXT)
+    plan = _machine(CASE_KEYWORDS).plan(0)
+    S = plan.chains_create(CASE_CHAINS)
+    L = acm.lib()
+    d_rec = _rec_dev(torch, rec, 2 * rec.size + want.size)
+    sentinel = as_records([(SENTINEL, 7, 7)] * want.size)
+    d_out = _rec_dev(torch, sentinel)
+    count = torch.full((1,), 0x5A5A, dtype=torch.int64, device="cuda")
+    tb = L.acm_gpu_chains_tmp_bytes(plan.h, S.h, rec.size, 0)
+    tmp = torch.empty(tb, dtype=torch.uint8, device="cuda")
+
+    def call(plan_h=plan.h, chains_h=S.h, records=d_rec.data_ptr(), n=rec.size, out=d_out.data_ptr(), cap=want.size, cnt=count.data_ptr(),
+             scratch=tmp.data_ptr(), tmp_bytes=tb, offsets=None, n_texts=0):
+        return L.acm_gpu_chains_records_device(plan_h, chains_h, records, n, None, n_symbols, 0, offsets, n_texts, out, cap, cnt, scratch, tmp_bytes, None)
+    assert tb > 0 and want.size > 0
+    assert call(plan_h=None) == E_ARG and call(chains_h=None) == E_ARG and call(records=None) == E_ARG and call(out=None) == E_ARG
+    assert call(cnt=None) == E_ARG and call(scratch=None) == E_ARG and call(tmp_bytes=tb - 1) == E_ARG and call(n=1 << 31) == E_ARG
+    assert call(cap=1 << 31) == E_ARG
+    assert call(out=d_rec.data_ptr()) == E_ARG and call(out=d_rec.data_ptr() + 16 * (rec.size - 1)) == E_ARG     # d_out overlapping d_records
+    assert call(out=d_rec.data_ptr() - 16 * (want.size - 1)) == E_ARG
+    assert call(offsets=d_rec.data_ptr(), n_texts=0) == E_ARG                          # no text, but symbols
+    # a room beyond CHAINS_MOST_SLOTS = 2^40 state slots (records x the most postings of a keyword), with fewer than 2^31 records
+    crowd = plan.chains_create([[(0, 0, 0)]] * 600)
+    most = int(crowd.info()["max_postings"])
+    assert most == 600
+    n_beyond = -(-(1 << 40) // most)
+    assert n_beyond < 1 << 31 and (n_beyond - 1) * most < 1 << 40 <= n_beyond * most
+    assert L.acm_gpu_chains_tmp_bytes(plan.h, crowd.h, n_beyond - 1, 0) > 0 and L.acm_gpu_chains_tmp_bytes(plan.h, crowd.h, n_beyond, 0) == 0
+    assert L.acm_gpu_scan_chains_tmp_bytes(plan.h, crowd.h, n_beyond, 64, 0) == 0
+    assert call(chains_h=crowd.h, n=n_beyond) == E_ARG
+    crowd.close()
+    torch.cuda.synchronize()
+    assert np.array_equal(_rec_host(d_out, want.size), sentinel) and int(count.item()) == 0x5A5A                  # nothing was touched
+    assert call(out=d_rec.data_ptr() + 16 * rec.size) == 0                             # right behind the records: no overlap
+    torch.cuda.synchronize()
+    _same(_rec_host(d_rec[rec.size:], int(count.item())), want)
+    assert call() == 0
+    torch.cuda.synchronize()
+    _same(_rec_host(d_out, int(count.item())), want)
+    assert call(n=0, records=None, scratch=None, tmp_bytes=0) == 0                      # no record: no match
+    torch.cuda.synchronize()
+    assert int(count.item()) == 0
+    S.close()
+    plan.status()
+
+
 def test_offsets_that_break_the_contract_match_nothing(torch_cuda, fixed):
     torch = torch_cuda
     rec, want = fixed
     n = len(CASE_TEXT)
     m = _machine(CASE_KEYWORDS)
     sentinel = as_records([(SENTINEL, 7, 7)] * want.size)
-    for what, off in (("decreasing", [0, 40, 30, n]), ("first not 0", [1, 40, n]), ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n])):
+    for what, off in (("decreasing", [0, 40, 30, n]), ("first not 0", [1, 40, n]), ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n]), *broken_last_pair(n)):
         plan = m.plan(0)
         plan.status()
         d_out = _rec_dev(torch, sentinel)

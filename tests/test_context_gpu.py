@@ -11,6 +11,7 @@ import pytest
 import aho_corasick_1975_amd as acm
 from aho_corasick_1975_amd import binding
 from oracle import pyoracle as po
+from tests.batch_cases import broken_last_pair
 from tests.cases import build_pair
 from tests.context_cases import BATCH_TEXTS, KEYWORDS, MOST, NONE, Expected, batch_case, expected, line_offsets, not_vacuous, novel_page, oracle_records
 from tests.tally_cases import PATH_CLASSES, PATH_GPU, kind
@@ -331,7 +332,7 @@ def test_contract_violations_report_and_write_nothing(torch_cuda):
     cases = [("decreasing end_pos", swapped, off, True), ("beyond the buffer", beyond, off, True), ("beyond, EACH", beyond, off, False),
              ("a start below 0", long, None, True)]
     cases += [(what, rec, np.array(bad, np.uint64), merged) for what, bad in (("decreasing", [0, 40, 30, n]), ("first not 0", [1, 40, n]),
-                                                                              ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n]))
+                                                                              ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n]), *broken_last_pair(n))
               for merged in (True, False)]
     for what, records, offsets, merged in cases:
         plan = m.plan(0)

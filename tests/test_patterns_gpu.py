@@ -12,7 +12,7 @@ import pytest
 import aho_corasick_1975_amd as acm
 from aho_corasick_1975_amd import binding
 from oracle import pyoracle as po
-from tests.batch_cases import offsets_of, oracle_batch
+from tests.batch_cases import broken_last_pair, offsets_of, oracle_batch
 from tests.pattern_cases import as_records, byte_oracle, compile_templates, oracle_records, patterns, patterns_by_re
 from tests.tally_cases import PATH_CLASSES, PATH_GPU, kind
 
@@ -387,7 +387,7 @@ def test_offsets_that_break_the_contract_match_nothing(torch_cuda):
     m, ps, rec, want = _byte_case()
     n = len(TEXT)
     sentinel = as_records([(SENTINEL, 7, 7)] * want.size)
-    for what, off in (("decreasing", [0, 40, 30, n]), ("first not 0", [1, 40, n]), ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n])):
+    for what, off in (("decreasing", [0, 40, 30, n]), ("first not 0", [1, 40, n]), ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n]), *broken_last_pair(n)):
         plan = m.plan(0)
         plan.status()
         d_out = _rec_dev(torch, sentinel)

@@ -11,7 +11,7 @@ import pytest
 import aho_corasick_1975_amd as acm
 from aho_corasick_1975_amd import binding
 from oracle import pyoracle as po
-from tests.batch_cases import offsets_of, oracle_batch
+from tests.batch_cases import broken_last_pair, offsets_of, oracle_batch
 from tests.cases import build_pair
 from tests.replace_cases import replace_by_definition
 from tests.select_cases import greedy
@@ -422,7 +422,7 @@ def test_offsets_that_break_the_contract_keep_nothing(torch_cuda):
     dev = _dev(torch, TEXT)
     n = len(TEXT)
     prefilled = _hand_made(np.full(rec.size, PATTERN, np.uint64), 7, 7)
-    for what, off in (("decreasing", [0, 40, 30, n]), ("first not 0", [1, 40, n]), ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n])):
+    for what, off in (("decreasing", [0, 40, 30, n]), ("first not 0", [1, 40, n]), ("last not n", [0, 40, n - 1]), ("far out", [0, 1 << 60, n]), *broken_last_pair(n)):
         plan = m.plan(0)
         plan.status()
         d_out = _rec_dev(torch, prefilled)
