@@ -24,6 +24,7 @@ from .binding import (  # noqa: F401
     TemplateSet, Templates, SymbolClass, ANY, IUPAC, template, hex_template, templates_records,
     ACM_TEMPLATE_LITERAL, ACM_TEMPLATE_ANY, ACM_TEMPLATE_NEGATED, ACM_TEMPLATE_MAX_RANGES,
     ChainSet, Chains, ChainsInfo, chains_records,
+    NearSet, Near, NearInfo, near_records, NEAR_EXPORTS,
 )
 from . import synth  # noqa: F401
 from . import sharded  # noqa: F401

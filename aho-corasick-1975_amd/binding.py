@@ -99,6 +99,10 @@ class ApproxInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("targets", "terms", "seed_keywords", "longest", "max_k", "max_postings")]
 
 
+class NearInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("groups", "terms", "max_terms", "max_width", "max_postings")]
+
+
 class TemplatesInfo(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("templates", "terms", "classes", "seed_keywords", "longest", "max_k", "max_postings")]
 
@@ -170,6 +174,12 @@ EXPORTS = [
     "acm_gpu_score_tmp_bytes", "acm_gpu_score_device", "acm_gpu_score_host", "acm_score",
     "acm_index_matrix", "acm_index_concat", "acm_gpu_index_matrix_tmp_bytes", "acm_gpu_index_matrix_device", "acm_gpu_index_concat_tmp_bytes",
     "acm_gpu_index_concat_device", "acm_gpu_index_tmp_bytes", "acm_gpu_index_device", "acm_gpu_index_host", "acm_index",
+]
+
+# every function include/acm_near.h declares (a list of its own: EXPORTS is the five headers above)
+NEAR_EXPORTS = [
+    "acm_near_check", "acm_near_records", "acm_gpu_near_create", "acm_gpu_near_destroy", "acm_gpu_near_info", "acm_gpu_near_tmp_bytes",
+    "acm_gpu_near_records_device", "acm_gpu_scan_near_tmp_bytes", "acm_gpu_scan_near_device", "acm_gpu_scan_near_host", "acm_scan_near",
 ]
 
 
@@ -527,6 +537,28 @@ def lib():
     L.acm_gpu_scan_chains_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_scan_chains.restype = i32
     L.acm_scan_chains.argtypes = [vp, vp, u64, vp, u64, vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_near_check.restype = i32
+    L.acm_near_check.argtypes = [vp, vp, vp, u64, u64]
+    L.acm_near_records.restype = i32
+    L.acm_near_records.argtypes = [vp, u64, u64, u64, vp, u64, vp, vp, vp, u64, u64, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_near_create.restype = i32
+    L.acm_gpu_near_create.argtypes = [vp, vp, vp, vp, u64, C.POINTER(vp)]
+    L.acm_gpu_near_destroy.restype = None
+    L.acm_gpu_near_destroy.argtypes = [vp]
+    L.acm_gpu_near_info.restype = i32
+    L.acm_gpu_near_info.argtypes = [vp, C.POINTER(NearInfo)]
+    L.acm_gpu_near_tmp_bytes.restype = sz
+    L.acm_gpu_near_tmp_bytes.argtypes = [vp, vp, u64, u64]
+    L.acm_gpu_near_records_device.restype = i32
+    L.acm_gpu_near_records_device.argtypes = [vp, vp, vp, u64, vp, u64, u64, vp, u64, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_near_tmp_bytes.restype = sz
+    L.acm_gpu_scan_near_tmp_bytes.argtypes = [vp, vp, u64, u64, u64]
+    L.acm_gpu_scan_near_device.restype = i32
+    L.acm_gpu_scan_near_device.argtypes = [vp, vp, vp, u64, u64, vp, u64, u64, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_scan_near_host.restype = i32
+    L.acm_gpu_scan_near_host.argtypes = [vp, vp, u64, u64, vp, u64, vp, vp, vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_scan_near.restype = i32
+    L.acm_scan_near.argtypes = [vp, vp, u64, vp, u64, vp, vp, vp, u64, vp, u64, C.POINTER(u64)]
     L.acm_approx_check.restype = i32
     L.acm_approx_check.argtypes = [vp, vp, vp, vp, u64, u64]
     L.acm_approx_split.restype = i32
@@ -1510,7 +1542,7 @@ def patterns_records(records, patternset, n_symbols, offsets=None, pos_base=0, n
 
 
 def _terms_records(name, records, tset, n_symbols, offsets, pos_base, n_keywords, out_capacity):
-    """what patterns_records() and chains_records() share: the C call `name` on numpy arrays, counted first when
+    """what patterns_records(), chains_records() and near_records() share: the C call `name` on numpy arrays, counted first when
     no capacity is given"""
     fn = getattr(lib(), name)
     a = np.ascontiguousarray(np.asarray(records, dtype=RECORD_DTYPE).reshape(-1))
@@ -1605,6 +1637,55 @@ def chains_records(records, chainset, n_symbols, offsets=None, pos_base=0, n_key
     (n_texts + 1 entries) cuts the buffer into texts; a match lies inside one text.  out_capacity None:
     counted first, then sized by the count; given and too small: ACMError (ACM_GPU_E_OVERFLOW)."""
     return _terms_records("acm_chains_records", records, _chainset(chainset), n_symbols, offsets, pos_base, n_keywords, out_capacity)
+
+
+class NearSet:
+    """NEAR/n groups packed to the three arrays the C calls take: terms (uint32, the keyword ids of all groups),
+    group_ptr (uint64, n_groups + 1) and groups (uint32 [n_groups, 2]: width, need).  `groups`: one entry per
+    group, a list of keyword ids -- it takes the `width=` and `need=` given here -- or (ids, width) or (ids,
+    width, need).  A group matches where at least `need` of its keywords (0: all of them) occur, in any order
+    and overlapping or not, inside `width` symbols of one text."""
+
+    def __init__(self, groups, width=None, need=0):
+        packed = []
+        for g in groups:
+            if isinstance(g, tuple) and len(g) in (2, 3) and not np.isscalar(g[0]):
+                ids, w, k = (g + (need,))[:3]
+            else:
+                ids, w, k = g, width, need
+            if w is None:
+                raise ValueError("a group needs a width")
+            packed.append(([int(x) for x in ids], int(w), int(k)))
+        self.n_groups = len(packed)
+        self.terms = np.array([x for ids, _, _ in packed for x in ids], dtype=np.uint32)
+        self.group_ptr = np.zeros(self.n_groups + 1, np.uint64)
+        if packed:
+            np.cumsum([len(ids) for ids, _, _ in packed], out=self.group_ptr[1:])
+        self.groups = np.array([(w, k) for _, w, k in packed], dtype=np.uint32).reshape(-1, 2)
+        self.n_keywords = int(self.terms.max()) + 1 if self.terms.size else 0   # what the host pass is told when nothing else is known
+
+    def args(self):
+        """(terms, group_ptr, groups, n_groups) as the C calls take them"""
+        return (self.terms.ctypes.data if self.terms.size else None, self.group_ptr.ctypes.data,
+                self.groups.ctypes.data if self.groups.size else None, self.n_groups)
+
+    def check(self, n_keywords):
+        """acm_near_check(): raises ACMError (ACM_GPU_E_ARG) for a set the calls would refuse"""
+        _check(lib().acm_near_check(*self.args(), int(n_keywords)), "acm_near_check")
+
+
+def _nearset(groups):
+    return groups if isinstance(groups, NearSet) else NearSet(groups)
+
+
+def near_records(records, nearset, n_symbols, offsets=None, pos_base=0, n_keywords=None, out_capacity=None):
+    """acm_near_records(): the matches of the groups of `nearset` among `records` (RECORD_DTYPE, in canonical
+    order, positions pos_base + index into a buffer of n_symbols symbols), by the sequential pass on the
+    host: per group and end one record (end_pos of the window's last symbol, the length of the shortest
+    window that ends there, the group's id), by end_pos ascending, length descending, group id ascending.
+    `offsets` (n_texts + 1 entries) cuts the buffer into texts; a window lies inside one text.  out_capacity
+    None: counted first, then sized by the count; given and too small: ACMError (ACM_GPU_E_OVERFLOW)."""
+    return _terms_records("acm_near_records", records, _nearset(nearset), n_symbols, offsets, pos_base, n_keywords, out_capacity)
 
 
 class _PieceKeywords:
@@ -2630,6 +2711,12 @@ class Machine(_Owner):
         repeated once with the size the call reports."""
         return self._scan_set("acm_scan_chains", text, _chainset(chainset), offsets, out_capacity, extra=())[0]
 
+    def scan_near(self, text, nearset, offsets=None, out_capacity=None):
+        """acm_scan_near(): the matches of the groups of `nearset` (see near_records) in `text`, or in every
+        text of the buffer when `offsets` (n_texts + 1 entries) cuts it; by default an overflow is repeated
+        once with the size the call reports."""
+        return self._scan_set("acm_scan_near", text, _nearset(nearset), offsets, out_capacity, extra=())[0]
+
     def scan_approx(self, text, approxset, offsets=None, out_capacity=None):
         """acm_scan_approx(): (matches, dist) of the targets of `approxset` (see approx_records) in `text`, or in
         every text of the buffer when `offsets` (n_texts + 1 entries) cuts it; by default an overflow is repeated
@@ -2814,6 +2901,12 @@ class Chains(_DeviceSet):
     max_terms, max_gap, max_postings and max_last_postings; n records give at most n * max_last_postings
     matches (MOST)."""
     STEM, INFO, SIZE, _host, MOST = "chains", ChainsInfo, "n_chains", staticmethod(_chainset), "max_last_postings"
+
+
+class Near(_DeviceSet):
+    """A NEAR group set on a plan's device (ACMNear): Plan.near() makes one.  info(): groups, terms, max_terms,
+    max_width and max_postings; n records give at most n * max_postings matches (MOST)."""
+    STEM, INFO, SIZE, _host, MOST = "near", NearInfo, "n_groups", staticmethod(_nearset), "max_postings"
 
 
 class Approx(_DeviceSet):
@@ -3538,7 +3631,7 @@ class Plan(_Owner):
         return self._terms_records(Patterns, records, n, patterns, n_symbols, offsets, pos_base, count, out, out_capacity, out_count)
 
     def _terms_records(self, family, records, n, given, n_symbols, offsets, pos_base, count, out, out_capacity, out_count):
-        """what patterns_records() and chains_records() share, `family` being Patterns or Chains: acm_gpu_<family>_tmp_bytes
+        """what patterns_records(), chains_records() and near_records() share, `family` being Patterns, Chains or Near: acm_gpu_<family>_tmp_bytes
         and acm_gpu_<family>_records_device"""
         import torch
         assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
@@ -3569,7 +3662,7 @@ class Plan(_Owner):
         return self._scan_terms(Patterns, text, patterns, offsets, n_symbols, pos_base, capacity, out, out_capacity, tmp)
 
     def _scan_terms(self, family, text, given, offsets, n_symbols, pos_base, capacity, out, out_capacity, tmp):
-        """what scan_patterns() and scan_chains() share, `family` being Patterns or Chains: acm_gpu_scan_<family>_tmp_bytes
+        """what scan_patterns(), scan_chains() and scan_near() share, `family` being Patterns, Chains or Near: acm_gpu_scan_<family>_tmp_bytes
         and acm_gpu_scan_<family>_device"""
         import torch
         n_symbols = self._text_args(text, n_symbols)
@@ -3622,6 +3715,28 @@ class Plan(_Owner):
         """acm_gpu_scan_chains_host(): numpy in, the chain matches out, through the C ABI only (no torch); an
         overflow is repeated once with the size the call reports."""
         return self._scan_set_host("acm_gpu_scan_chains_host", text, _chainset(chainset), offsets, pos_base, out_capacity, extra=())[0]
+
+    def near(self, nearset):
+        """acm_gpu_near_create(): `nearset` (a NearSet, or what makes one) compiled and uploaded to this plan's
+        device.  Returns a Near; it stays valid across update()."""
+        return Near.create(self, nearset)
+
+    def near_records(self, records, n, near, n_symbols, offsets=None, pos_base=0, count=None, out=None, out_capacity=None, out_count=None):
+        """acm_gpu_near_records_device(): the matches of `near` (a Near from near(), or a NearSet compiled for
+        this call) among records[:n]; arguments and results as chains_records(), the default out_capacity
+        being n times the set's max_postings, which cannot overflow.  Nothing is synchronised."""
+        return self._terms_records(Near, records, n, near, n_symbols, offsets, pos_base, count, out, out_capacity, out_count)
+
+    def scan_near(self, text, near, offsets=None, n_symbols=None, pos_base=0, capacity=None, out=None, out_capacity=None, tmp=None):
+        """acm_gpu_scan_near_device(): the ordered scan of a device tensor into `capacity` records of the call's
+        own and the matches of `near` among them, queued on the current stream; arguments and results as
+        scan_chains()."""
+        return self._scan_terms(Near, text, near, offsets, n_symbols, pos_base, capacity, out, out_capacity, tmp)
+
+    def scan_near_host(self, text, nearset, offsets=None, pos_base=0, out_capacity=None):
+        """acm_gpu_scan_near_host(): numpy in, the NEAR matches out, through the C ABI only (no torch); an
+        overflow is repeated once with the size the call reports."""
+        return self._scan_set_host("acm_gpu_scan_near_host", text, _nearset(nearset), offsets, pos_base, out_capacity, extra=())[0]
 
     def approx_create(self, approxset):
         """acm_gpu_approx_create(): `approxset` (an ApproxSet) compiled and uploaded to this plan's device.

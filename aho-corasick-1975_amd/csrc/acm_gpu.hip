@@ -7797,6 +7797,189 @@ acm_gpu_scan_chains_host (ACMPlan *plan, const void *text, uint64_t n_symbols, u
     });
 }
 
+/* ------------------------------------------------------------------ unordered keyword proximity (include/acm_near.h, dev_near.h)
+ * A group set compiled into an index inverted by keyword, and the passes that join a record set in
+ * canonical order under it: the check of offsets[], the walk pass, the count pass, the prefix over
+ * the records' counts, the fill pass, the patterns' order pass. */
+struct ACMNear : DeviceSet {
+  uint64_t n_groups = 0, n_terms = 0, max_terms = 0, max_width = 0, max_postings = 0;
+  uint32_t *d_post_ptr = nullptr;
+  NearPost *d_post = nullptr;
+};
+
+namespace {
+constexpr uint64_t NEAR_MOST_SLOTS = 1ull << 40; /* slots of one call: records x the most postings of a keyword */
+
+JoinRoom
+near_carve (Carve &c, const ACMNear *near, uint64_t capacity, NearK &K) {
+  /* ACM_GPU_NEAR_TILE=<records>: the passes' tile, a multiple of 64 (tests); ACM_GPU_NEAR_COOP=<records>: walks of more records are
+   * finished by the whole wave (0: every walk, a huge value: none).  COOP's default is CHAINS' own; the tile's is the best of the four
+   * that tools/exp_near.py measured (dev_near.h). */
+  join_carve_ctl (c, capacity, tunable ("ACM_GPU_NEAR_TILE", NEAR_TILE_DEFAULT, NEAR_TILE_MIN, NEAR_TILE_MAX, Tune::MultWave), K);
+  K.coop = tunable ("ACM_GPU_NEAR_COOP", NEAR_COOP_DEFAULT, 0, 0x7FFFFFFFu, Tune::Any);
+  K.stride = (uint32_t)std::max<uint64_t> (near->max_postings, 1);
+  K.state = c.take<unsigned long long> ((size_t)(capacity * K.stride));
+  return join_carve_counts (c, capacity, K);
+}
+
+bool
+near_room_ok (const ACMNear *near, uint64_t capacity) {
+  return capacity < (1ull << 31) && capacity * std::max<uint64_t> (near->max_postings, 1) < NEAR_MOST_SLOTS;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_near_create (ACMPlan *plan, const uint32_t *terms, const uint64_t *group_ptr, const ACMNearGroup *groups, uint64_t n_groups, ACMNear **out) {
+  if (!plan || !out)
+    return ACM_GPU_E_ARG;
+  const uint64_t nk = plan->covered_keywords;
+  if (acm_near_check (terms, group_ptr, groups, n_groups, nk))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_terms = group_ptr[n_groups];
+  /* the index: every term under its keyword, a keyword's postings by group (a counting sort over the groups in order) */
+  std::vector<uint32_t> post_ptr (nk + 1, 0), at (nk, 0);
+  uint64_t max_terms = 0, max_width = 0, max_postings = 0;
+  for (uint64_t i = 0; i < n_terms; i++)
+    post_ptr[terms[i] + 1]++;
+  for (uint64_t k = 0; k < nk; k++) {
+    max_postings = std::max<uint64_t> (max_postings, post_ptr[k + 1]);
+    post_ptr[k + 1] += post_ptr[k];
+    at[k] = post_ptr[k];
+  }
+  std::vector<NearPost> post (n_terms ? n_terms : 1);
+  for (uint64_t g = 0; g < n_groups; g++) {
+    const uint64_t m = group_ptr[g + 1] - group_ptr[g], need = groups[g].need ? groups[g].need : m;
+    max_terms = std::max (max_terms, m);
+    max_width = std::max<uint64_t> (max_width, groups[g].width);
+    for (uint64_t j = 0; j < m; j++)
+      post[at[terms[group_ptr[g] + j]]++] = NearPost{ (uint32_t)g, groups[g].width, (uint32_t)(j | m << 8 | need << 16), 0 };
+  }
+  HIP_TRY (hipSetDevice (plan->device));
+  ACMNear *S = new (std::nothrow) ACMNear ();
+  if (!S)
+    return ACM_GPU_E_NOMEM;
+  S->device = plan->device;
+  S->n_groups = n_groups;
+  S->n_terms = n_terms;
+  S->max_terms = max_terms;
+  S->max_width = max_width;
+  S->max_postings = max_postings;
+  S->n_keywords = (uint32_t)nk;
+  BlobBuilder b;
+  const size_t post_ptr_at = b.add (post_ptr.data (), post_ptr.size () * 4), post_at = b.add (post.data (), post.size () * sizeof (NearPost));
+  if (const int rc = set_upload (S, b))
+    return rc;
+  S->d_post_ptr = b.at<uint32_t> (post_ptr_at);
+  S->d_post = b.at<NearPost> (post_at);
+  *out = S;
+  return ACM_GPU_OK;
+}
+
+extern "C" void
+acm_gpu_near_destroy (ACMNear *near) {
+  set_destroy (near);
+}
+
+extern "C" int
+acm_gpu_near_info (const ACMNear *near, ACMNearInfo *info) {
+  if (!near || !info)
+    return ACM_GPU_E_ARG;
+  *info = ACMNearInfo{ near->n_groups, near->n_terms, near->max_terms, near->max_width, near->max_postings };
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_near_tmp_bytes (const ACMPlan *plan, const ACMNear *near, uint64_t n_or_capacity, uint64_t n_texts) {
+  (void)n_texts; /* (nothing here is sized by the number of texts: the text of an end is a bisection of offsets[]) */
+  if (!plan || !near || !near_room_ok (near, n_or_capacity))
+    return 0;
+  Carve c;
+  NearK K{};
+  near_carve (c, near, n_or_capacity, K);
+  return c.total ();
+}
+
+namespace {
+/* acm_gpu_near_records_device */
+int
+near_join (const JoinCall &C, const ACMNear *near) {
+  if (!join_args_ok (C, near) || !near_room_ok (near, C.n))
+    return ACM_GPU_E_ARG;
+  ACMPlan *plan = C.plan;
+  const uint64_t n = C.n, n_texts = C.n_texts, out_capacity = C.out_capacity;
+  hipStream_t st = static_cast<hipStream_t> (C.stream);
+  if (n == 0) /* (no record: no match, whatever *d_n says) */
+    return no_record (plan, nullptr, C.d_count, st);
+  Carve carve (C.d_tmp);
+  NearK K{};
+  const JoinRoom L = near_carve (carve, near, n, K);
+  if (C.tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  K.post_ptr = near->d_post_ptr;
+  K.post = near->d_post;
+  K.n_keywords = near->n_keywords;
+  bind_join (K, C);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (JoinCtl), st));
+  /* the check */
+  if (K.offsets) /* one size, whatever the number of texts */
+    HIP_TRY (launch (offsets_check_kernel, capped_grid (plan, (n_texts + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st, K.offsets,
+                     K.n_texts, K.n_symbols, &K.ctl->bad, K.error));
+  /* 1. (one launch, whatever the groups hold) */
+  HIP_TRY (launch (near_walk_kernel, capped_grid (plan, K.n_tiles), dim3 (NEAR_THREADS), 0, st, K));
+  /* 2. */
+  HIP_TRY (launch (near_count_kernel, capped_grid (plan, K.n_tiles), dim3 (NEAR_THREADS), 0, st, K));
+  /* 3. */
+  HIP_TRY (exclusive_sum (L.cub, L.count, L.first, n + 1, st));
+  /* 4. */
+  HIP_TRY (launch (near_fill_kernel, capped_grid (plan, K.n_tiles), dim3 (NEAR_THREADS), 0, st, K));
+  /* 5. (dev_patterns.h's, which reads the head of K alone) */
+  if (out_capacity > 1)
+    HIP_TRY (launch (patterns_order_kernel, capped_grid (plan, (out_capacity + PATTERNS_THREADS - 1) / PATTERNS_THREADS), dim3 (PATTERNS_THREADS), 0, st,
+                     static_cast<const JoinK &> (K)));
+  return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" int
+acm_gpu_near_records_device (ACMPlan *plan, const ACMNear *near, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, uint64_t n_symbols,
+                             uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts, ACMRecord *d_out, uint64_t out_capacity, uint64_t *d_count,
+                             void *d_tmp, size_t tmp_bytes, void *stream) {
+  return near_join (JoinCall{ plan, d_records, n, d_n, n_symbols, pos_base, d_offsets, n_texts, d_out, out_capacity, d_count, d_tmp, tmp_bytes, stream }, near);
+}
+
+extern "C" size_t
+acm_gpu_scan_near_tmp_bytes (const ACMPlan *plan, const ACMNear *near, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!plan || !near || !near_room_ok (near, capacity))
+    return 0;
+  Carve c;
+  scan_room_carve (c, plan, acm_gpu_near_tmp_bytes (plan, near, capacity, n_texts), capacity, n_symbols);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_scan_near_device (ACMPlan *plan, const ACMNear *near, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets,
+                          uint64_t n_texts, uint64_t capacity, ACMRecord *d_out, uint64_t out_capacity, uint64_t *d_count, uint64_t *d_found, void *d_tmp,
+                          size_t tmp_bytes, void *stream) {
+  const ScanJoinCall C{ plan, d_text, n_symbols, pos_base, d_offsets, n_texts, capacity, d_out, out_capacity, d_count, d_found, d_tmp, tmp_bytes, stream };
+  return scan_then_join (C, plan && near && near->device == plan->device && near_room_ok (near, capacity),
+                         acm_gpu_near_tmp_bytes (plan, near, capacity, n_texts), [&] (const JoinCall &J) { return near_join (J, near); });
+}
+
+extern "C" int
+acm_gpu_scan_near_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                        const uint32_t *terms, const uint64_t *group_ptr, const ACMNearGroup *groups, uint64_t n_groups, ACMRecord *out,
+                        uint64_t out_capacity, uint64_t *n_found) {
+  const ScanJoinHost H{ plan, text, n_symbols, pos_base, offsets, n_texts, out, nullptr, out_capacity, n_found };
+  return scan_join_host<ACMNear> (
+    H, false, [&] (ACMNear **made) { return acm_gpu_near_create (plan, terms, group_ptr, groups, n_groups, made); }, near_room_ok,
+    [&] (const ACMNear *set, uint64_t capacity) { return acm_gpu_scan_near_tmp_bytes (plan, set, capacity, n_symbols, n_texts); },
+    [] (const ACMNear *set, const ScanJoinCall &C, uint32_t *) {
+      return acm_gpu_scan_near_device (C.plan, set, C.d_text, C.n_symbols, C.pos_base, C.d_offsets, C.n_texts, C.capacity, C.d_out, C.out_capacity, C.d_count,
+                                       C.d_found, C.d_tmp, C.tmp_bytes, C.stream);
+    });
+}
+
 /* ------------------------------------------------------------------ keywords with up to k mismatches (include/acm_gpu.h, dev_approx.h)
  * A target set compiled into an index inverted by term keyword, and the passes that verify a record set in
  * canonical order under it: the check of offsets[], the count pass, the prefix over the records' counts, the
@@ -9330,6 +9513,23 @@ acm_scan_chains (ACMachine *machine, const void *text, uint64_t n_symbols, const
     },
     [&] (ACMPlan *plan) {
       return acm_gpu_scan_chains_host (plan, text, n_symbols, 0, offsets, n_texts, terms, chain_ptr, n_chains, out, out_capacity, n_found);
+    });
+}
+
+/* unordered keyword proximity (include/acm_near.h) */
+extern "C" int
+acm_scan_near (ACMachine *machine, const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, const uint32_t *terms,
+               const uint64_t *group_ptr, const ACMNearGroup *groups, uint64_t n_groups, ACMRecord *out, uint64_t out_capacity, uint64_t *n_found) {
+  if (!machine || !n_found || (n_symbols && !text) || (out_capacity && !out) || !optional_offsets_ok (offsets, n_texts, n_symbols) ||
+      acm_internal_near_machine_check (machine, terms, group_ptr, groups, n_groups))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      return acm_internal_cpu_scan_near (machine, text, n_symbols, said, offsets, n_texts, terms, group_ptr, groups, n_groups, out, out_capacity, n_found);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_scan_near_host (plan, text, n_symbols, 0, offsets, n_texts, terms, group_ptr, groups, n_groups, out, out_capacity, n_found);
     });
 }
 

@@ -2608,6 +2608,198 @@ acm_internal_cpu_scan_chains (ACMachine *m, const void *text, uint64_t n_symbols
   return rc;
 }
 
+/* ---- unordered keyword proximity (include/acm_near.h): the argument checks, the plain sequential NEAR of a record set in
+ * canonical order, and acm_scan_near's host path. */
+int
+acm_near_check (const uint32_t *terms, const uint64_t *group_ptr, const ACMNearGroup *groups, uint64_t n_groups, uint64_t n_keywords) {
+  if (!group_ptr || group_ptr[0] != 0 || n_groups >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  for (uint64_t g = 0; g < n_groups; g++)
+    if (group_ptr[g] >= group_ptr[g + 1] || group_ptr[g + 1] - group_ptr[g] > ACM_NEAR_TERMS_MAX) /* decreasing, no term, too many */
+      return ACM_GPU_E_ARG;
+  if (group_ptr[n_groups] >= (1ull << 31) || (n_groups && (!terms || !groups)))
+    return ACM_GPU_E_ARG;
+  for (uint64_t g = 0; g < n_groups; g++) {
+    const uint64_t m = group_ptr[g + 1] - group_ptr[g];
+    if (groups[g].width == 0 || groups[g].width > ACM_NEAR_WIDTH_MAX || groups[g].need > m)
+      return ACM_GPU_E_ARG;
+    for (uint64_t i = group_ptr[g]; i < group_ptr[g + 1]; i++) {
+      if (terms[i] >= n_keywords)
+        return ACM_GPU_E_ARG;
+      for (uint64_t j = group_ptr[g]; j < i; j++)
+        if (terms[j] == terms[i])
+          return ACM_GPU_E_ARG;
+    }
+  }
+  return ACM_GPU_OK;
+}
+
+/* S* + 1 of the group whose terms are best[0 .. m) / at_end[0 .. m) (a start + 1, 0: none; at_end: of the record that ends at the
+ * end in hand), by the closed form: the greatest over the anchors a of min (a_start, the (need - 1)-th greatest best_u, u != a) */
+static uint64_t
+near_best_window (const uint64_t *best, const uint64_t *at_end, uint64_t m, uint64_t need) {
+  uint64_t top = 0;
+  for (uint64_t a = 0; a < m; a++) {
+    if (!at_end[a])
+      continue;
+    uint64_t S = at_end[a];
+    if (need > 1) {
+      uint64_t kth = 0; /* the (need - 1)-th greatest among the others: the one with need - 2 in front of it */
+      for (uint64_t u = 0; u < m && !kth; u++) {
+        if (u == a || !best[u])
+          continue;
+        uint64_t before = 0;
+        for (uint64_t v = 0; v < m; v++)
+          before += v != a && v != u && best[v] && (best[v] > best[u] || (best[v] == best[u] && v < u));
+        if (before == need - 2)
+          kth = best[u];
+      }
+      S = kth < S ? kth : S; /* (none: 0) */
+    }
+    top = S > top ? S : top;
+  }
+  return top;
+}
+
+int
+acm_near_records (const ACMRecord *records, uint64_t n, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts,
+                  const uint32_t *terms, const uint64_t *group_ptr, const ACMNearGroup *groups, uint64_t n_groups, uint64_t n_keywords,
+                  ACMRecord *out, uint64_t out_capacity, uint64_t *n_found) {
+  if (!n_found || (n && !records) || (out_capacity && !out) || acm_near_check (terms, group_ptr, groups, n_groups, n_keywords))
+    return ACM_GPU_E_ARG;
+  if (offsets) {
+    if (offsets[0] != 0 || offsets[n_texts] != n_symbols)
+      return ACM_GPU_E_ARG;
+    for (uint64_t t = 0; t < n_texts; t++)
+      if (offsets[t] > offsets[t + 1])
+        return ACM_GPU_E_ARG;
+  }
+  for (uint64_t j = 0; j < n; j++)
+    if (record_breaks_contract (&records[j], pos_base, n_symbols))
+      return ACM_GPU_E_ARG;
+  /* the terms under their keywords (kw_ptr, kw_term: positions in terms[]), the group of a term, and one pass over the runs of
+   * records of equal end: best[i] = the greatest start + 1 so far of term i's records, at_end[i] = that of the record of this
+   * run (seen[i] = the run's number + 1 says whether it is this run's), hot[] the groups this run touched */
+  const uint64_t n_terms = group_ptr[n_groups];
+  uint64_t *kw_ptr = calloc (n_keywords + 2, sizeof *kw_ptr), *kw_term = malloc ((n_terms ? n_terms : 1) * sizeof *kw_term);
+  uint64_t *group_of = malloc ((n_terms ? n_terms : 1) * sizeof *group_of), *best = calloc (n_terms ? n_terms : 1, sizeof *best);
+  uint64_t *at_end = calloc (n_terms ? n_terms : 1, sizeof *at_end), *seen = calloc (n_terms ? n_terms : 1, sizeof *seen);
+  uint64_t *hot = malloc ((n_groups ? n_groups : 1) * sizeof *hot), *hot_run = calloc (n_groups ? n_groups : 1, sizeof *hot_run);
+  ACMRecord *hits = NULL;
+  uint64_t found = 0, room = 0;
+  int rc = kw_ptr && kw_term && group_of && best && at_end && seen && hot && hot_run ? ACM_GPU_OK : ACM_GPU_E_NOMEM;
+  if (!rc) {
+    for (uint64_t i = 0; i < n_terms; i++)
+      kw_ptr[terms[i] + 2]++;
+    for (uint64_t k = 0; k < n_keywords; k++)
+      kw_ptr[k + 2] += kw_ptr[k + 1];
+    for (uint64_t g = 0; g < n_groups; g++)
+      for (uint64_t i = group_ptr[g]; i < group_ptr[g + 1]; i++) {
+        kw_term[kw_ptr[terms[i] + 1]++] = i; /* (kw_ptr[k + 1] runs up to where kw_ptr[k + 2] began: kw_ptr[k .. k + 1] bound k's terms afterwards) */
+        group_of[i] = g;
+      }
+  }
+  uint64_t text = 0; /* the text of the run's end: ends ascend, so it only moves forward */
+  for (uint64_t b = 0, run = 1; !rc && b < n; run++) {
+    uint64_t c = b + 1, n_hot = 0;
+    while (c < n && records[c].end_pos == records[b].end_pos)
+      c++;
+    const uint64_t e = records[b].end_pos - pos_base;
+    for (uint64_t j = b; j < c; j++) {
+      const ACMRecord *r = &records[j];
+      if (r->keyword_id >= n_keywords)
+        continue;
+      const uint64_t s1 = e + 2 - r->length;
+      for (uint64_t q = kw_ptr[r->keyword_id]; q < kw_ptr[r->keyword_id + 1]; q++) {
+        const uint64_t i = kw_term[q], g = group_of[i];
+        best[i] = s1 > best[i] ? s1 : best[i];
+        at_end[i] = seen[i] == run && at_end[i] > s1 ? at_end[i] : s1;
+        seen[i] = run;
+        if (hot_run[g] != run) {
+          hot_run[g] = run;
+          hot[n_hot++] = g;
+        }
+      }
+    }
+    uint64_t begin = 0;
+    if (offsets) {
+      while (text + 1 < n_texts && offsets[text + 1] <= e)
+        text++;
+      begin = offsets[text];
+    }
+    for (uint64_t h = 0; !rc && h < n_hot; h++) {
+      const uint64_t g = hot[h], t0 = group_ptr[g], m = group_ptr[g + 1] - t0;
+      uint64_t anchors[ACM_NEAR_TERMS_MAX];
+      for (uint64_t u = 0; u < m; u++)
+        anchors[u] = seen[t0 + u] == run ? at_end[t0 + u] : 0;
+      const uint64_t S1 = near_best_window (best + t0, anchors, m, groups[g].need ? groups[g].need : m);
+      if (!S1 || S1 - 1 < begin || e + 1 - (S1 - 1) > groups[g].width)
+        continue;
+      if (found == room) {
+        room = room ? 2 * room : 256;
+        ACMRecord *more = realloc (hits, room * sizeof *hits);
+        if (!more) {
+          rc = ACM_GPU_E_NOMEM;
+          break;
+        }
+        hits = more;
+      }
+      hits[found++] = (ACMRecord){ records[b].end_pos, (uint32_t)(e + 1 - (S1 - 1)), (uint32_t)g };
+    }
+    b = c;
+  }
+  free (kw_ptr);
+  free (kw_term);
+  free (group_of);
+  free (best);
+  free (at_end);
+  free (seen);
+  free (hot);
+  free (hot_run);
+  if (!rc) {
+    *n_found = found;
+    if (out && found > out_capacity)
+      rc = ACM_GPU_E_OVERFLOW;
+    else if (out) {
+      if (found > 1)
+        qsort (hits, found, sizeof *hits, chain_out_cmp);
+      if (found)
+        memcpy (out, hits, found * sizeof *hits);
+    }
+  }
+  free (hits);
+  return rc;
+}
+
+/* the check acm_scan_near makes on every path: acm_near_check against the machine's keywords */
+int
+acm_internal_near_machine_check (ACMachine *m, const uint32_t *terms, const uint64_t *group_ptr, const ACMNearGroup *groups, uint64_t n_groups) {
+  if (!m)
+    return ACM_GPU_E_ARG;
+  acm_internal_lock (m);
+  const int rc = acm_near_check (terms, group_ptr, groups, n_groups, m->nb_keywords);
+  acm_internal_unlock (m);
+  return rc;
+}
+
+/* acm_scan_near on the host: the caller loop (from the root at every offset of a batch), then the sequential pass over what it
+ * found -- what ACM_SCAN_PATH_CPU_LOOP runs.  The public call has checked the arguments. */
+int
+acm_internal_cpu_scan_near (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                            const uint32_t *terms, const uint64_t *group_ptr, const ACMNearGroup *groups, uint64_t n_groups, ACMRecord *out,
+                            uint64_t out_capacity, uint64_t *n_found) {
+  if (!m || !n_found)
+    return ACM_GPU_E_ARG;
+  ACMRecord *records;
+  uint64_t found = 0;
+  int rc = cpu_scan_grown (m, text, n_symbols, offsets, n_texts, sym_bytes, NULL, &records, &found);
+  if (!rc)
+    rc = acm_near_records (records, found, n_symbols, 0, offsets, n_texts, terms, group_ptr, groups, n_groups, acm_nb_keywords (m), out, out_capacity,
+                           n_found);
+  free (records);
+  return rc;
+}
+
 /* ---- keywords with up to k mismatches (include/acm_gpu.h): the argument checks, the canonical cut, the plain sequential APPROX of a
  * record set in canonical order, and acm_scan_approx's host path. */
 int

@@ -130,6 +130,13 @@ int acm_internal_chains_machine_check (ACMachine *m, const ACMChainTerm *terms, 
 int acm_internal_cpu_scan_chains (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
                                   const ACMChainTerm *terms, const uint64_t *chain_ptr, uint64_t n_chains, ACMRecord *out, uint64_t out_capacity,
                                   uint64_t *n_found);
+/* acm_scan_near's check on every path: acm_near_check against the machine's keywords */
+int acm_internal_near_machine_check (ACMachine *m, const uint32_t *terms, const uint64_t *group_ptr, const ACMNearGroup *groups, uint64_t n_groups);
+/* acm_scan_near's host path: the caller loop (from the root at every offset when offsets is given), then acm_near_records over its
+ * records (arguments as acm_scan_near's, the symbol size behind n_symbols; the public call has checked them) */
+int acm_internal_cpu_scan_near (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const uint64_t *offsets, uint64_t n_texts,
+                                const uint32_t *terms, const uint64_t *group_ptr, const ACMNearGroup *groups, uint64_t n_groups, ACMRecord *out,
+                                uint64_t out_capacity, uint64_t *n_found);
 /* acm_scan_approx's checks on every path: acm_approx_check against the machine's keywords, and every term's keyword is spelled as the
  * term's piece of its target, by the machine's comparator over symbols of sym_bytes bytes */
 int acm_internal_approx_machine_check (ACMachine *m, uint32_t sym_bytes, const void *spell_data, const uint64_t *spell_off, const uint32_t *k,

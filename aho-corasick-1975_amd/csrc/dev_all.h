@@ -243,6 +243,7 @@ join_postings (const JoinK &K, const uint32_t *post_ptr, uint32_t n_keywords, co
 #include "dev_templates.h"
 #include "dev_edit.h"
 #include "dev_chains.h"
+#include "dev_near.h"
 #include "dev_segment.h"
 #include "dev_score.h"
 #include "dev_index.h"

@@ -2039,8 +2039,8 @@ int acm_scan_edit (ACMachine *machine, const void *text, uint64_t n_symbols,
  * and on overflow).  ACM_SCAN_PATH_CPU_LOOP runs the caller loop per text on the host, then
  * acm_chains_records.  A missing device stays an error, never a fallback.
  *
- * Out of scope: negative gaps and overlapping terms; unordered proximity (NEAR); symbol classes
- * inside a gap; all embeddings rather than one record per end; flows, streams and several GPUs;
+ * Out of scope: negative gaps and overlapping terms; symbol classes inside a gap (unordered
+ * proximity, NEAR, is acm_near.h's); all embeddings rather than one record per end; flows, streams and several GPUs;
  * feeding chain records to SELECT or REPLACE (their contract bounds lengths by the plan's lmax). */
 #define ACM_CHAIN_TERMS_MAX 16u
 #define ACM_CHAIN_GAP_MAX (1u << 20)
@@ -2307,4 +2307,5 @@ int acm_gpu_synth_text (int device, void *d_text, uint64_t n, uint64_t global_be
 #endif
 #include "acm_score.h"
 #include "acm_index.h"
+#include "acm_near.h"
 #include "acm_segment.h"
