@@ -9093,16 +9093,28 @@ acm_gpu_plan_update (ACMPlan *plan, ACMachine *machine) {
   if (rc)
     return rc;
   HIP_TRY (hipDeviceSynchronize ()); /* scans in flight still read the old tables */
-  const bool timing = plan->timing;
+  /* timing goes on across the rebuild: the launches sampled so far into the totals (the device is idle), then the
+   * switch, the period, the place in it, the totals and the events themselves move to the new tables */
+  rc = acm_gpu_plan_timing_read_all (plan, nullptr, nullptr, nullptr);
+  if (rc) {
+    acm_gpu_plan_destroy (fresh);
+    return rc;
+  }
   const uint64_t segment = plan->segment;
   const uint32_t merges = plan->merges + 1;
   std::swap (*plan, *fresh);
+  plan->timing = fresh->timing;
+  plan->timing_every = fresh->timing_every;
+  plan->timing_seq = fresh->timing_seq;
+  plan->timing_ms = fresh->timing_ms;
+  plan->timing_all_ms = fresh->timing_all_ms;
+  plan->timing_launches = fresh->timing_launches;
+  std::swap (plan->events, fresh->events);
+  plan->events_used = 0;
   acm_gpu_plan_destroy (fresh); /* the old tables, their delta and what was retired */
   plan->segment = segment;
   plan->merges = merges;
   plan->generation = gen;
-  if (timing)
-    (void)acm_gpu_plan_timing (plan, 1);
   return ACM_GPU_OK;
 }
 

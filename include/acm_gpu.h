@@ -2283,7 +2283,10 @@ int acm_gpu_plan_status (ACMPlan *plan);
  * Reading synchronises on the recorded events.  enable = 1: every launch; enable = N > 1: every
  * N-th launch -- the three events of a launch cost about 10 us on the stream (a step of 1 GiB
  * against 1,000 keywords takes 282 us without them and 292 with: tools/exp_timing_overhead.py), so
- * a caller that measures throughput and kernel time in the same run samples. */
+ * a caller that measures throughput and kernel time in the same run samples.  An
+ * acm_gpu_plan_update that rebuilds the plan keeps all of it: the switch, the period N, the place
+ * in the period and the totals read so far.  It reads the launches sampled so far into the totals
+ * first; a HIP error there is the update's return value, and the plan is left as it was. */
 int acm_gpu_plan_timing (ACMPlan *plan, int enable);
 int acm_gpu_plan_timing_read (ACMPlan *plan, double *total_ms, uint64_t *launches);
 /* the same, and beside the scan kernels' time (scan_ms) the time from the start of each scan kernel

@@ -60,3 +60,14 @@ def random_cuts(n, mean, seed=7):
     dup = cuts[:: max(cuts.size // 50, 1)]
     off = np.sort(np.concatenate([[0, 0, 0], cuts, dup, dup[::3], [n, n]])).astype(np.uint64)
     return off
+
+
+def packed_batch(n_symbols=4096, n_texts=37):
+    """4 KiB over a seven-letter alphabet, cut into 37 texts: an empty first one, one of 700 symbols
+    (more than a 256-symbol batch block), 34 random ones, an empty last one -- (text, offsets)"""
+    rng = np.random.default_rng(75)
+    text = np.frombuffer(b"hesir .", np.uint8)[rng.integers(0, 7, size=n_symbols)].copy()
+    cuts = np.sort(rng.choice(np.arange(701, n_symbols), size=n_texts - 4, replace=False))
+    off = np.concatenate(([0, 0, 700], cuts, [n_symbols, n_symbols])).astype(np.uint64)
+    assert off.size == n_texts + 1 and off[1] == off[0] and off[-1] == off[-2] and np.all(off[1:] >= off[:-1])
+    return text, off

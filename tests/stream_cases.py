@@ -4,7 +4,8 @@ as a raw call through binding.lib () with caller-owned buffers, and the machiner
 A Case names the inputs that decide the answer (`gated`: name -> (real, decoy), same shape and type), the outputs, the
 scratch of exactly *_tmp_bytes and the part of every output that counts (`cut`).  A Run holds them on the device and
 runs the call
-    plain    on the null stream, synchronised: the expected value (the feature tests hold these against the oracle);
+    plain    on the null stream, synchronised: the expected value, held against Case.want -- the oracle's records and the
+             definitions of tests/*_cases.py, output by output (None: an output without a definition);
     early    the buffers hold the decoy, scratch and outputs are zero; on a non-blocking side stream a gate
              (torch.cuda._sleep), the copy of the real inputs and the call, the null stream idle: whatever the call
              launches on stream 0 runs during the gate, on the decoy and on empty scratch;
@@ -23,6 +24,9 @@ import numpy as np
 
 from aho_corasick_1975_amd import binding
 from oracle import pyoracle as po
+from tests import approx_cases, chain_cases, context_cases, edit_cases, flow_cases, grep_cases, pattern_cases, replace_cases, rules_cases
+from tests import split_cases, template_cases, token_cases, words_cases
+from tests.select_cases import greedy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "acm_gpu.h")
@@ -284,6 +288,20 @@ def padded(rec, room):
     return a
 
 
+def terms_of(terms, ptr):
+    """a set's flat terms[] as one list of (keyword_id, x, y) per member, by its ptr[] array"""
+    return [[tuple(int(x) for x in terms[i]) for i in range(int(ptr[c]), int(ptr[c + 1]))] for c in range(len(ptr) - 1)]
+
+
+def i32(a):
+    """values below 2^32 as the int32 a device buffer of uint32_t comes back as"""
+    return np.asarray(a).astype(np.uint32).view(np.int32)
+
+
+def i64(a):
+    return np.asarray(a).astype(np.uint64).view(np.int64)
+
+
 def batch_records(o, text, off):
     """the oracle's records of every text scanned on its own, end_pos = the index in the buffer"""
     parts = []
@@ -294,6 +312,26 @@ def batch_records(o, text, off):
             r["end_pos"] += lo
             parts.append(r)
     return np.concatenate(parts) if parts else np.zeros(0, REC)
+
+
+PLAIN_BY_PLAN = {
+    "acm_gpu_pack_records_device": "the packed word goes by acm_gpu_wire_bits (plan, ...): no expected value without a plan",
+    "acm_gpu_unpack_records_device": "its input is packed by acm_gpu_wire_bits (plan, ...): no expected value without a plan",
+}
+
+
+def plain_expected(o, real, decoy, which="real"):
+    """{entry point: expected outputs} of the plain entry points whose answer the oracle alone gives (not PLAIN_BY_PLAN's),
+    for the `real` or the `decoy` text: the scans give the oracle's records, the two sorts the first m of them, m = the
+    smaller number of records of the two texts"""
+    both = {"real": o.scan(real), "decoy": o.scan(decoy)}
+    m = min(both["real"].size, both["decoy"].size)
+    w = both[which]
+    return {"acm_gpu_scan_device": [sorted_rows(rec_rows(w)), np.array([w.size])],
+            "acm_gpu_count_device": [np.array([w.size])],
+            "acm_gpu_scan_ordered_device": [rec_rows(w), np.array([w.size])],
+            "acm_gpu_order_records_device": [rec_rows(w[:m])],
+            "acm_gpu_sort_records_device": [rec_rows(w[:m])]}
 
 
 def plain_cases(torch, plan, o, real, decoy, misalign=False):
@@ -307,6 +345,7 @@ def plain_cases(torch, plan, o, real, decoy, misalign=False):
     m = min(want.size, other.size)
     # on the CPU, by the oracle: non-empty, different, inside the capacity
     assert m >= 64 and not np.array_equal(want[:m], other[:m]) and want.size != other.size, (want.size, other.size)
+    by_oracle = plain_expected(o, real, decoy)
     text = {"text": (real.view(np.uint8) if misalign else real, decoy.view(np.uint8) if misalign else decoy)}
     mis = ("text",) if misalign else ()
     cases = []
@@ -314,16 +353,16 @@ def plain_cases(torch, plan, o, real, decoy, misalign=False):
                       lambda p, st: L.acm_gpu_scan_device(h, p["text"], n, 0, 0, p["rec"], cap, p["count"], st),
                       text, {"rec": (2 * cap, T.int64), "count": (1, T.int64)}, misalign=mis,
                       cut=lambda x: [sorted_rows(rows(x, "rec", min(x["count"][0], cap))), x["count"]],      # (in no particular order)
-                      want=[sorted_rows(rec_rows(want)), np.array([want.size])]))
+                      want=by_oracle["acm_gpu_scan_device"]))
     cases.append(Case("acm_gpu_count_device", plan,
                       lambda p, st: L.acm_gpu_count_device(h, p["text"], n, 0, p["count"], st),
-                      text, {"count": (1, T.int64)}, misalign=mis, want=[np.array([want.size])]))
+                      text, {"count": (1, T.int64)}, misalign=mis, want=by_oracle["acm_gpu_count_device"]))
     cases.append(Case("acm_gpu_scan_ordered_device", plan,
                       lambda p, st: L.acm_gpu_scan_ordered_device(h, p["text"], n, 0, 0, p["rec"], cap, p["count"], p["tmp"], tb_ordered, st),
                       text, {"rec": (2 * cap, T.int64), "count": (1, T.int64)}, misalign=mis,
                       tmp_bytes=L.acm_gpu_scan_ordered_tmp_bytes(h, cap, n),
                       cut=lambda x: [rows(x, "rec", min(x["count"][0], cap)), x["count"]],
-                      want=[rec_rows(want), np.array([want.size])]))
+                      want=by_oracle["acm_gpu_scan_ordered_device"]))
     tb_ordered = cases[-1].tmp_bytes
     # the records of both texts cut to one number and shuffled: a prefix of a canonical record set is one
     perm = np.random.default_rng(5).permutation(m)
@@ -331,10 +370,10 @@ def plain_cases(torch, plan, o, real, decoy, misalign=False):
     tb_order, tb_sort = L.acm_gpu_order_tmp_bytes(h, m, n), L.acm_gpu_sort_tmp_bytes(m)
     cases.append(Case("acm_gpu_order_records_device", plan,
                       lambda p, st: L.acm_gpu_order_records_device(h, p["rec"], m, 0, n, p["tmp"], tb_order, st),
-                      shuffled, {}, tmp_bytes=tb_order, cut=lambda x: [rows(x, "rec")], want=[rec_rows(want[:m])]))
+                      shuffled, {}, tmp_bytes=tb_order, cut=lambda x: [rows(x, "rec")], want=by_oracle["acm_gpu_order_records_device"]))
     cases.append(Case("acm_gpu_sort_records_device", plan,
                       lambda p, st: L.acm_gpu_sort_records_device(h, p["rec"], m, p["tmp"], tb_sort, st),
-                      shuffled, {}, tmp_bytes=tb_sort, cut=lambda x: [rows(x, "rec")], want=[rec_rows(want[:m])]))
+                      shuffled, {}, tmp_bytes=tb_sort, cut=lambda x: [rows(x, "rec")], want=by_oracle["acm_gpu_sort_records_device"]))
     bits = [C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)]
     assert L.acm_gpu_wire_bits(h, n, *[C.byref(x) for x in bits]) == 0
     pb, lb = bits[0].value, bits[1].value
@@ -359,9 +398,14 @@ WINDOW = 1024                                            # symbols per window of
 
 class Features:
     """One plan, one batch (text and decoy text of N symbols under one offsets[] of T texts), the sets of the
-    set families built from the two keywords the real text holds most often, and a Case per entry point."""
+    set families built from the two keywords of two symbols or more that the real text holds most often, a Case per
+    entry point and, without a device, what each of them must give: expected (name, "real" or "decoy"), from the oracle's
+    records and the families' definitions in plain Python.  torch None: no plan and no device buffers, expected () alone."""
 
-    def __init__(self, torch, m, o, make_plan, real, decoy, off, word_ranges=binding.ASCII_WORD):
+    def __init__(self, torch, m, o, make_plan, real, decoy, off, word_ranges=binding.ASCII_WORD, trailing=None, last_step=None):
+        """trailing: a keyword no set refers to, added to machine and oracle behind the sets' pieces.  last_step (features):
+        called once self.plan is there, in front of the first case -- a plan maker that has one step of growth left compiles
+        the sets on the plan as it is and then grows it (tests/growth_cases.py)."""
         self.torch, self.m, self.o = torch, m, o
         self.real, self.decoy, self.off = np.ascontiguousarray(real), np.ascontiguousarray(decoy), np.ascontiguousarray(off, dtype=np.uint64)
         self.N, self.T = self.real.size, self.off.size - 1
@@ -369,8 +413,8 @@ class Features:
         # the two keywords the real batch holds most often (by the oracle), and the sets made of them
         rec = batch_records(o, self.real, self.off)
         ids, counts = np.unique(rec["keyword_id"], return_counts=True)
-        order = np.argsort(-counts, kind="stable")
-        a, b = int(ids[order[0]]), int(ids[order[1]])
+        order = [int(ids[i]) for i in np.argsort(-counts, kind="stable") if len(m.keyword(int(ids[i]))[0]) >= 2]    # (of two symbols or more)
+        a, b = order[0], order[1]
         sa, sb = [int(x) for x in m.keyword(a)[0]], [int(x) for x in m.keyword(b)[0]]
         la, lb = len(sa), len(sb)
         assert la >= 2 and lb >= 2
@@ -379,16 +423,26 @@ class Features:
         self.ruleset = binding.RuleSet([binding.rule([binding.present(a)]), binding.rule([binding.present(b), binding.absent(a)]),
                                         binding.rule([binding.present(a, 2), binding.present(b, 2)], need=1)])
         before = m.nb_keywords
-        self.approxset = binding.ApproxSet.from_targets(m, [bytes(sa + sb), bytes(sb + [sa[0]])], 1)
+        self.targets, self.target_k = [bytes(sa + sb), bytes(sb + [sa[0]])], [1, 1]
+        self.approxset = binding.ApproxSet.from_targets(m, self.targets, 1)
         cells = list(sa)
         cells[1] = binding.SymbolClass([(sa[1] - 1, sa[1] + 1)])
-        self.templateset = binding.TemplateSet.from_templates(m, [cells, sb + [binding.ANY] + sa], k=[0, 1])
-        for k in range(before, m.nb_keywords):           # the pieces the two sets added, into the oracle as well
+        self.templates, self.template_k = [cells, sb + [binding.ANY] + sa], [0, 1]
+        self.templateset = binding.TemplateSet.from_templates(m, self.templates, k=self.template_k)
+        if trailing is not None:
+            m.add_keyword(trailing)
+        for k in range(before, m.nb_keywords):           # the pieces the two sets added (and the trailing keyword), into the oracle as well
             o.add_keyword(bytes(m.keyword(k)[0]))
         assert o.nb_keywords == m.nb_keywords
         self.K = m.nb_keywords
-        self.plan = make_plan(0)
-        assert self.plan.tally_keywords == self.K
+        self.word_ranges = tuple(word_ranges)
+        self.handles = {}
+        self.plan = None
+        if torch is not None:
+            self.plan = make_plan(0)
+            if last_step is not None:
+                last_step(self)
+            assert self.plan.tally_keywords == self.K
         # on the CPU, by the oracle: the records of both batches are there, differ and fit the room
         self.rec, self.rec_decoy = batch_records(o, self.real, self.off), batch_records(o, self.decoy, self.off)
         whole, whole_decoy = o.scan(self.real).size, o.scan(self.decoy).size
@@ -397,14 +451,18 @@ class Features:
         self.sel, self.sel_decoy = binding.select_records(self.rec), binding.select_records(self.rec_decoy)
         self.ns = min(self.sel.size, self.sel_decoy.size)
         assert 32 <= self.ns < self.n and not np.array_equal(self.sel[:self.ns], self.sel_decoy[:self.ns])
-        self.d_off = dev(torch, self.off)
+        self.whole = {"real": o.scan(self.real), "decoy": o.scan(self.decoy)}
         self.ranges, self.n_ranges = binding._word_ranges(word_ranges, 1)
-        self.delims, self.n_delims = binding._delims(bytes([int(np.bincount(self.real).argmax())]), 1)
+        self.delim = int(np.bincount(self.real).argmax())
+        self.delims, self.n_delims = binding._delims(bytes([self.delim]), 1)
+        self.pre_text = np.roll(self.decoy, 977)         # what every flow is fed in front of a flow case's call
         repl = [b"<%d>" % k if k % 2 else b"" for k in range(self.K)]
         data, roff = binding.replacement_table(repl, 1)[:2]
-        self.d_repl, self.d_repl_off = dev(torch, data), dev(torch, roff)
-        self.handles = {}
+        self.repl = repl
         self.keep = []
+        self.wants = {}
+        if torch is not None:
+            self.d_off, self.d_repl, self.d_repl_off = dev(torch, self.off), dev(torch, data), dev(torch, roff)
 
     def handle(self, family):
         if family not in self.handles:
@@ -428,6 +486,181 @@ class Features:
     def case(self, name):
         return getattr(self, "_" + name[len("acm_gpu_"):])(name)
 
+    # -- what every entry point must give, without the library's scans, joins and host passes
+    def expected(self, name, which="real"):
+        """the expected value of every output of case (name) that has a definition (None: one that has none), for the real
+        or the decoy inputs: the oracle's records and the definitions of tests/*_cases.py"""
+        if (name, which) not in self.wants:
+            self.wants[(name, which)] = [None if w is None else np.asarray(w) for w in getattr(self, "_want_" + name[len("acm_gpu_"):])(which)]
+        return self.wants[(name, which)]
+
+    def _side(self, which):
+        """(text, the batch's records, the selection of them, the records of the buffer as one text)"""
+        assert which in ("real", "decoy")
+        real = which == "real"
+        return (self.real if real else self.decoy, self.rec if real else self.rec_decoy, self.sel if real else self.sel_decoy, self.whole[which])
+
+    def _texts(self, text):
+        return [text[int(self.off[t]):int(self.off[t + 1])] for t in range(self.T)]
+
+    def _want_scan_batch_device(self, which):
+        _, rec, _, _ = self._side(which)
+        return [rec_rows(rec), self._text_ids(rec), self._first(rec), [rec.size]]
+
+    def _want_flow(self, steps):
+        rec, tid, first = flow_cases.expected(self.o, steps)[-1]
+        return [rec_rows(rec), i32(tid), i64(first), [rec.size]]
+
+    def _want_scan_flows_device(self, which):
+        flows = range(self.T)
+        return self._want_flow([flow_cases.Call(self._texts(self.pre_text), flows), flow_cases.Call(self._texts(self._side(which)[0]), flows)])
+
+    def _want_flows_reset(self, which):
+        flows = range(self.T)
+        ids = range(0 if which == "real" else 1, 2 * (self.T // 2), 2)
+        return self._want_flow([flow_cases.Call(self._texts(self.pre_text), flows), flow_cases.Reset(ids), flow_cases.Call(self._texts(self.real), flows)])
+
+    def _want_tally_device(self, which):
+        whole = self._side(which)[3]
+        return [np.bincount(whole["keyword_id"], minlength=self.K).astype(np.int64), [whole.size]]
+
+    def _want_grep_device(self, which):
+        text, rec, _, _ = self._side(which)
+        hits = np.diff(self._first(rec)).astype(np.uint64)
+        kept, out_off, out = grep_cases.expected(text, self.off, hits, False)
+        return [i64(hits), i32(kept), None, out, i64(out_off), [kept.size, int(hits.sum()), out.size]]
+
+    def _want_tally_batch_device(self, which):
+        rec = self._side(which)[1]
+        matrix = self._matrix(rec)
+        return matrix + [None, [matrix[1].size, rec.size]]
+
+    def _counts(self, rec):
+        rp, c, v = self._matrix(rec)
+        return rp.astype(np.uint64), c.astype(np.uint32), v.astype(np.uint64)
+
+    def _want_rules_matrix_device(self, which):
+        fired_ptr, fired, _ = rules_cases.expected_fired(self._counts(self._side(which)[1]), self.K, self.ruleset)
+        return [i64(fired_ptr), i32(fired), [fired.size]]
+
+    def _want_rules_device(self, which):
+        rec = self._side(which)[1]
+        fired_ptr, fired, _ = rules_cases.expected_fired(self._counts(rec), self.K, self.ruleset)
+        return [i64(fired_ptr), i32(fired), None, [fired.size, rec.size]]
+
+    def _want_split_device(self, which):
+        off = split_cases.expected_offsets(self._side(which)[0], self.delim, runs=False)
+        return [i64(off), [off.size - 1]]
+
+    def _want_select_records_device(self, which):
+        sel = greedy(self._side(which)[1][:self.n])
+        return [rec_rows(sel), [sel.size]]
+
+    def _want_scan_select_device(self, which):
+        sel = greedy(self._side(which)[3])
+        return [rec_rows(sel), [sel.size]]
+
+    def _want_replace_records_device(self, which):
+        text, _, sel, _ = self._side(which)
+        out, starts = replace_cases.replace_by_definition(text, sel[:self.ns], self.repl)
+        return [out, [out.size], starts]
+
+    def _want_scan_replace_device(self, which):
+        text, _, _, whole = self._side(which)
+        sel = greedy(whole)
+        out, starts = replace_cases.replace_by_definition(text, sel, self.repl)
+        return [rec_rows(sel), [sel.size], out, [out.size], starts]
+
+    def _want_tokens(self, text, sel):
+        ids, starts, lens, first = token_cases.tokens_by_definition(text, sel, token_cases.RUN, gap_base=1000, offsets=self.off)
+        return [i32(ids), i64(starts), i32(lens), [ids.size], i64(first)]
+
+    def _want_tokens_records_device(self, which):
+        text, _, sel, _ = self._side(which)
+        return self._want_tokens(text, sel[:self.ns])
+
+    def _want_scan_tokens_device(self, which):
+        text, rec, _, _ = self._side(which)
+        sel = greedy(rec)                                # (a batch's records never cross a text: one selection serves all texts)
+        return [rec_rows(sel), [sel.size]] + self._want_tokens(text, sel)
+
+    def _want_words(self, text, rec):
+        w = words_cases.words(rec, text, self.off, self.word_ranges, words_cases.BOTH)
+        return [rec_rows(w), [w.size]]
+
+    def _want_words_records_device(self, which):
+        text, rec, _, _ = self._side(which)
+        return self._want_words(text, rec[:self.n])
+
+    def _want_scan_words_device(self, which):
+        text, _, _, whole = self._side(which)
+        return self._want_words(text, whole)
+
+    def _want_context(self, text, rec):
+        e = context_cases.expected(rec, self.N, self.off, before=3, after=2, texts=False, merged=True)
+        return [e.out(text), [e.out_symbols], [e.n_snippets], i64(e.snip_lo), i64(e.out_offsets), i32(e.snip_text), i32(e.rec_snip), e.rec_at]
+
+    def _want_context_records_device(self, which):
+        text, rec, _, _ = self._side(which)
+        return self._want_context(text, rec[:self.n])
+
+    def _want_scan_context_device(self, which):
+        text, _, _, whole = self._side(which)
+        return [rec_rows(whole), [whole.size]] + self._want_context(text, whole)
+
+    def _want_join(self, which, fused, definition):
+        """a join of the batch's first n records, or (fused) of the records of the buffer as one text; definition
+        (records, text) gives the matches, or (matches, distances)"""
+        text, rec, _, whole = self._side(which)
+        got = definition(whole if fused else rec[:self.n], text)
+        got = list(got) if isinstance(got, tuple) else [got]
+        return [rec_rows(got[0])] + [i32(d) for d in got[1:]] + [[got[0].size, whole.size] if fused else [got[0].size]]
+
+    def _patterns_by_definition(self, rec, text):
+        return pattern_cases.patterns(rec, terms_of(self.patternset.terms, self.patternset.pat_ptr), self.N, self.off)
+
+    def _chains_by_definition(self, rec, text):
+        return chain_cases.chains(rec, chain_cases.chain_terms(self.chainset), self.N, self.off)
+
+    def _approx_by_definition(self, rec, text):
+        return approx_cases.approx(rec, text, self.targets, self.target_k, terms_of(self.approxset.terms, self.approxset.tgt_ptr), self.off)
+
+    def _edit_by_definition(self, rec, text):
+        return edit_cases.edits(rec, text, self.targets, self.target_k, terms_of(self.approxset.terms, self.approxset.tgt_ptr), self.off)
+
+    def _templates_by_definition(self, rec, text):
+        return template_cases.templates(rec, text, self.templates, self.template_k, terms_of(self.templateset.terms, self.templateset.tgt_ptr), self.off)
+
+    def _want_patterns_records_device(self, which):
+        return self._want_join(which, False, self._patterns_by_definition)
+
+    def _want_scan_patterns_device(self, which):
+        return self._want_join(which, True, self._patterns_by_definition)
+
+    def _want_chains_records_device(self, which):
+        return self._want_join(which, False, self._chains_by_definition)
+
+    def _want_scan_chains_device(self, which):
+        return self._want_join(which, True, self._chains_by_definition)
+
+    def _want_approx_records_device(self, which):
+        return self._want_join(which, False, self._approx_by_definition)
+
+    def _want_scan_approx_device(self, which):
+        return self._want_join(which, True, self._approx_by_definition)
+
+    def _want_edit_records_device(self, which):
+        return self._want_join(which, False, self._edit_by_definition)
+
+    def _want_scan_edit_device(self, which):
+        return self._want_join(which, True, self._edit_by_definition)
+
+    def _want_templates_records_device(self, which):
+        return self._want_join(which, False, self._templates_by_definition)
+
+    def _want_scan_templates_device(self, which):
+        return self._want_join(which, True, self._templates_by_definition)
+
     # -- batch and flows
     def _scan_batch_device(self, name):
         import torch as T
@@ -437,7 +670,7 @@ class Features:
                     lambda p, st: L.acm_gpu_scan_batch_device(h, p["text"], N, off, Tn, p["rec"], p["tid"], p["first"], CAP, p["count"], p["tmp"], tb, st),
                     self._text(), {"rec": (2 * CAP, T.int64), "tid": (CAP, T.int32), "first": (Tn + 1, T.int64), "count": (1, T.int64)}, tb,
                     cut=lambda x: [rows(x, "rec", x["count"][0]), x["tid"][:x["count"][0]], x["first"], x["count"]],
-                    want=[rec_rows(self.rec), self._text_ids(self.rec), self._first(self.rec), np.array([self.rec.size])])
+                    want=self.expected(name))
 
     def _text_ids(self, rec):
         """(the last text that begins at or before end_pos: the one that is not empty)"""
@@ -454,7 +687,7 @@ class Features:
             import torch as T
             L, h, fh = binding.lib(), self.plan.h, self.handle("flows").h
             tb = L.acm_gpu_scan_flows_tmp_bytes(h, fh, CAP, self.N, self.T)
-            self.pre = dict(text=dev(torch, np.roll(self.decoy, 977)), rec=T.zeros(2 * CAP, dtype=T.int64, device="cuda"),
+            self.pre = dict(text=dev(torch, self.pre_text), rec=T.zeros(2 * CAP, dtype=T.int64, device="cuda"),
                             count=T.zeros(1, dtype=T.int64, device="cuda"), tmp=T.zeros(max(tb, 16), dtype=T.uint8, device="cuda"), tb=tb)
         return self.pre
 
@@ -475,7 +708,8 @@ class Features:
                     lambda p, st: L.acm_gpu_scan_flows_device(h, fh, p["text"], N, off, None, Tn, p["rec"], p["tid"], p["first"], CAP, p["count"], p["tmp"],
                                                               tb, st),
                     self._text(), {"rec": (2 * CAP, T.int64), "tid": (CAP, T.int32), "first": (Tn + 1, T.int64), "count": (1, T.int64)}, tb,
-                    cut=lambda x: [rows(x, "rec", x["count"][0]), x["tid"][:x["count"][0]], x["first"], x["count"]], prepare=self._feed_pre)
+                    cut=lambda x: [rows(x, "rec", x["count"][0]), x["tid"][:x["count"][0]], x["first"], x["count"]], prepare=self._feed_pre,
+                    want=self.expected(name))
 
     def _flows_reset(self, name):
         """flows reset on the stream, seen by a flow scan of the real text behind it: the real ids are the even flows,
@@ -493,19 +727,18 @@ class Features:
                                                st) == OK
         return Case(name, self.plan, lambda p, st: L.acm_gpu_flows_reset(fh, p["ids"], k, st), ids,
                     {"rec": (2 * CAP, T.int64), "tid": (CAP, T.int32), "first": (Tn + 1, T.int64), "count": (1, T.int64)}, tb,
-                    cut=lambda x: [rows(x, "rec", x["count"][0]), x["tid"][:x["count"][0]], x["first"], x["count"]], prepare=self._feed_pre, post=post)
+                    cut=lambda x: [rows(x, "rec", x["count"][0]), x["tid"][:x["count"][0]], x["first"], x["count"]], prepare=self._feed_pre, post=post,
+                    want=self.expected(name))
 
     # -- tallies, grep, rules, split
     def _tally_device(self, name):
         import torch as T
         L, h, N, K = binding.lib(), self.plan.h, self.N, self.K
         tb = L.acm_gpu_tally_tmp_bytes(h, WINDOW, CAP)
-        want = self.o.scan(self.real)
         return Case(name, self.plan,
                     lambda p, st: L.acm_gpu_tally_device(h, p["text"], N, 0, p["tally"], K, WINDOW, CAP, p["res"], p["res"] + 8, p["tmp"], tb, st),
                     self._text(), {"tally": (K, T.int64), "res": (2, T.int64)}, tb, accumulate=("tally",),
-                    cut=lambda x: [x["tally"], x["res"][:1]],
-                    want=[np.bincount(want["keyword_id"], minlength=K).astype(np.int64), np.array([want.size])])
+                    cut=lambda x: [x["tally"], x["res"][:1]], want=self.expected(name))
 
     def _grep_device(self, name):
         import torch as T
@@ -514,12 +747,12 @@ class Features:
 
         def cut(x):
             n_kept, _, _, out_symbols = (int(v) for v in x["res"])
-            return [x["hits"], x["kept"][:n_kept], x["res"], x["out"][:out_symbols], x["out_off"][:n_kept + 1]]
+            return [x["hits"], x["kept"][:n_kept], x["res"], x["out"][:out_symbols], x["out_off"][:n_kept + 1], x["res"][[0, 1, 3]]]
         return Case(name, self.plan,
                     lambda p, st: L.acm_gpu_grep_device(h, p["text"], N, off, Tn, binding.ACM_GREP_MATCHING, WINDOW, CAP, p["hits"], p["kept"], p["res"],
                                                         p["res"] + 8, p["res"] + 16, p["out"], N, p["out_off"], p["res"] + 24, p["tmp"], tb, st),
                     self._text(), {"hits": (Tn, T.int64), "kept": (Tn, T.int32), "res": (4, T.int64), "out": (N, T.uint8), "out_off": (Tn + 1, T.int64)},
-                    tb, cut=cut)
+                    tb, cut=cut, want=self.expected(name))
 
     def _tally_batch_device(self, name):
         import torch as T
@@ -529,7 +762,7 @@ class Features:
                     lambda p, st: L.acm_gpu_tally_batch_device(h, p["text"], N, off, Tn, WINDOW, CAP, CAP, p["row_ptr"], p["col"], p["val"], p["res"],
                                                                p["res"] + 8, p["res"] + 16, p["res"] + 24, p["tmp"], tb, st),
                     self._text(), {"row_ptr": (Tn + 1, T.int64), "col": (CAP, T.int32), "val": (CAP, T.int64), "res": (4, T.int64)}, tb,
-                    cut=lambda x: [x["row_ptr"], x["col"][:x["res"][0]], x["val"][:x["res"][0]], x["res"]], want=self._matrix(self.rec) + [None])
+                    cut=lambda x: [x["row_ptr"], x["col"][:x["res"][0]], x["val"][:x["res"][0]], x["res"], x["res"][:2]], want=self.expected(name))
 
     def _matrix(self, rec):
         """the text x keyword count matrix of batch records in CSR form, columns ascending: [row_ptr, col, val]"""
@@ -557,7 +790,7 @@ class Features:
                                                                 p["tmp"], tb, st),
                     {"row_ptr": (rp, rp2), "col": (pad(c), pad(c2)), "val": (pad(v), pad(v2))},
                     {"fired_ptr": (Tn + 1, T.int64), "fired": (FC, T.int32), "n_fired": (1, T.int64)}, tb,
-                    cut=lambda x: [x["fired_ptr"], x["fired"][:x["n_fired"][0]], x["n_fired"]])
+                    cut=lambda x: [x["fired_ptr"], x["fired"][:x["n_fired"][0]], x["n_fired"]], want=self.expected(name))
 
     def _rules_device(self, name):
         import torch as T
@@ -568,7 +801,7 @@ class Features:
                     lambda p, st: L.acm_gpu_rules_device(h, R, p["text"], N, off, Tn, WINDOW, CAP, CAP, p["fired_ptr"], p["fired"], FC, p["res"], p["res"] + 8,
                                                          p["res"] + 16, p["res"] + 24, p["tmp"], tb, st),
                     self._text(), {"fired_ptr": (Tn + 1, T.int64), "fired": (FC, T.int32), "res": (4, T.int64)}, tb,
-                    cut=lambda x: [x["fired_ptr"], x["fired"][:x["res"][0]], x["res"]])
+                    cut=lambda x: [x["fired_ptr"], x["fired"][:x["res"][0]], x["res"], x["res"][:2]], want=self.expected(name))
 
     def _split_device(self, name):
         import torch as T
@@ -578,19 +811,19 @@ class Features:
         return Case(name, self.plan,
                     lambda p, st: L.acm_gpu_split_device(h, p["text"], N, d.ctypes.data, nd, binding.ACM_SPLIT_EVERY, p["off"], N, p["count"], p["tmp"], tb, st),
                     self._text(), {"off": (N + 1, T.int64), "count": (1, T.int64)}, tb,
-                    cut=lambda x: [x["off"][:x["count"][0] + 1], x["count"]])
+                    cut=lambda x: [x["off"][:x["count"][0] + 1], x["count"]], want=self.expected(name))
 
     # -- select, replace, tokens, words, context
     def _select_records_device(self, name):
         import torch as T
         L, h, N = binding.lib(), self.plan.h, self.N
         tb = L.acm_gpu_select_tmp_bytes(h, CAP, N)
-        gated, n = self._records()
+        gated, _ = self._records()
         del gated["text"]
         return Case(name, self.plan,
                     lambda p, st: L.acm_gpu_select_records_device(h, p["rec"], CAP, p["n"], 0, N, p["out"], p["count"], p["tmp"], tb, st),
                     gated, {"out": (2 * CAP, T.int64), "count": (1, T.int64)}, tb,
-                    cut=lambda x: [rows(x, "out", x["count"][0]), x["count"]], want=[rec_rows(binding.select_records(self.rec[:n])), None])
+                    cut=lambda x: [rows(x, "out", x["count"][0]), x["count"]], want=self.expected(name))
 
     def _scan_select_device(self, name):
         import torch as T
@@ -599,7 +832,7 @@ class Features:
         return Case(name, self.plan,
                     lambda p, st: L.acm_gpu_scan_select_device(h, p["text"], N, 0, p["rec"], CAP, p["count"], p["tmp"], tb, st),
                     self._text(), {"rec": (2 * CAP, T.int64), "count": (1, T.int64)}, tb,
-                    cut=lambda x: [rows(x, "rec", x["count"][0]), x["count"]], want=[rec_rows(binding.select_records(self.o.scan(self.real))), None])
+                    cut=lambda x: [rows(x, "rec", x["count"][0]), x["count"]], want=self.expected(name))
 
     def _replace_outs(self):
         import torch as T
@@ -614,7 +847,7 @@ class Features:
                     lambda p, st: L.acm_gpu_replace_records_device(h, p["text"], N, 0, p["rec"], CAP, p["n"], rd, ro, K, p["out"], 4 * N, p["out_symbols"],
                                                                    p["out_start"], p["tmp"], tb, st),
                     gated, self._replace_outs(), tb,
-                    cut=lambda x: [x["out"][:self._inside(x["out_symbols"][0], 4 * N)], x["out_symbols"], x["out_start"][:n]])
+                    cut=lambda x: [x["out"][:self._inside(x["out_symbols"][0], 4 * N)], x["out_symbols"], x["out_start"][:n]], want=self.expected(name))
 
     def _scan_replace_device(self, name):
         import torch as T
@@ -627,7 +860,7 @@ class Features:
                                                                 p["out_start"], p["tmp"], tb, st),
                     self._text(), outs, tb,
                     cut=lambda x: [rows(x, "rec", x["count"][0]), x["count"], x["out"][:self._inside(x["out_symbols"][0], 4 * N)],
-                                   x["out_symbols"], x["out_start"][:x["count"][0]]])
+                                   x["out_symbols"], x["out_start"][:x["count"][0]]], want=self.expected(name))
 
     def _token_outs(self):
         import torch as T
@@ -646,7 +879,7 @@ class Features:
         return Case(name, self.plan,
                     lambda p, st: L.acm_gpu_tokens_records_device(h, p["text"], N, 0, p["rec"], CAP, p["n"], off, Tn, None, K, 1000, binding.TOKENS_GAP_RUN,
                                                                   p["tok_id"], p["tok_start"], p["tok_len"], N, p["n_tokens"], p["tok_first"], p["tmp"], tb, st),
-                    gated, self._token_outs(), tb, cut=self._token_cut)
+                    gated, self._token_outs(), tb, cut=self._token_cut, want=self.expected(name))
 
     def _scan_tokens_device(self, name):
         import torch as T
@@ -656,7 +889,7 @@ class Features:
         return Case(name, self.plan,
                     lambda p, st: L.acm_gpu_scan_tokens_device(h, p["text"], N, 0, off, Tn, p["rec"], CAP, p["count"], None, K, 1000, binding.TOKENS_GAP_RUN,
                                                                p["tok_id"], p["tok_start"], p["tok_len"], N, p["n_tokens"], p["tok_first"], p["tmp"], tb, st),
-                    self._text(), outs, tb, cut=lambda x: [rows(x, "rec", x["count"][0]), x["count"]] + self._token_cut(x))
+                    self._text(), outs, tb, cut=lambda x: [rows(x, "rec", x["count"][0]), x["count"]] + self._token_cut(x), want=self.expected(name))
 
     def _words_records_device(self, name):
         import torch as T
@@ -667,7 +900,8 @@ class Features:
         return Case(name, self.plan,
                     lambda p, st: L.acm_gpu_words_records_device(h, p["text"], N, 0, off, Tn, r.ctypes.data, nr, binding.ACM_WORDS_BOTH, p["rec"], CAP, p["n"],
                                                                  p["out"], p["count"], p["tmp"], tb, st),
-                    gated, {"out": (2 * CAP, T.int64), "count": (1, T.int64)}, tb, cut=lambda x: [rows(x, "out", x["count"][0]), x["count"]])
+                    gated, {"out": (2 * CAP, T.int64), "count": (1, T.int64)}, tb, cut=lambda x: [rows(x, "out", x["count"][0]), x["count"]],
+                    want=self.expected(name))
 
     def _scan_words_device(self, name):
         import torch as T
@@ -677,7 +911,8 @@ class Features:
         return Case(name, self.plan,
                     lambda p, st: L.acm_gpu_scan_words_device(h, p["text"], N, 0, off, Tn, r.ctypes.data, nr, binding.ACM_WORDS_BOTH, p["rec"], CAP,
                                                               p["count"], p["tmp"], tb, st),
-                    self._text(), {"rec": (2 * CAP, T.int64), "count": (1, T.int64)}, tb, cut=lambda x: [rows(x, "rec", x["count"][0]), x["count"]])
+                    self._text(), {"rec": (2 * CAP, T.int64), "count": (1, T.int64)}, tb, cut=lambda x: [rows(x, "rec", x["count"][0]), x["count"]],
+                    want=self.expected(name))
 
     def _context_outs(self):
         import torch as T
@@ -703,7 +938,7 @@ class Features:
                     lambda p, st: L.acm_gpu_context_records_device(h, p["text"], N, 0, off, Tn, p["rec"], CAP, p["n"], 3, 2, flags, p["out"], 8 * N,
                                                                    p["out_symbols"], p["n_snippets"], p["snip_lo"], p["out_off"], p["snip_text"],
                                                                    p["rec_snip"], p["rec_at"], p["tmp"], tb, st),
-                    gated, self._context_outs(), tb, cut=lambda x: self._context_cut(x, n))
+                    gated, self._context_outs(), tb, cut=lambda x: self._context_cut(x, n), want=self.expected(name))
 
     def _scan_context_device(self, name):
         import torch as T
@@ -715,7 +950,8 @@ class Features:
                     lambda p, st: L.acm_gpu_scan_context_device(h, p["text"], N, 0, off, Tn, p["rec"], CAP, p["count"], 3, 2, flags, p["out"], 8 * N,
                                                                 p["out_symbols"], p["n_snippets"], p["snip_lo"], p["out_off"], p["snip_text"],
                                                                 p["rec_snip"], p["rec_at"], p["tmp"], tb, st),
-                    self._text(), outs, tb, cut=lambda x: [rows(x, "rec", x["count"][0]), x["count"]] + self._context_cut(x, int(x["count"][0])))
+                    self._text(), outs, tb, cut=lambda x: [rows(x, "rec", x["count"][0]), x["count"]] + self._context_cut(x, int(x["count"][0])),
+                    want=self.expected(name))
 
     # -- the set families: patterns and chains (records in, records out), approx, edit and templates (with distances)
     def _join_records(self, name, family, most):
@@ -727,7 +963,8 @@ class Features:
         del gated["text"]
         return Case(name, self.plan,
                     lambda p, st: getattr(L, name)(h, S, p["rec"], CAP, p["n"], N, 0, off, Tn, p["out"], OC, p["count"], p["tmp"], tb, st),
-                    gated, {"out": (2 * OC, T.int64), "count": (1, T.int64)}, tb, cut=lambda x: [rows(x, "out", x["count"][0]), x["count"]])
+                    gated, {"out": (2 * OC, T.int64), "count": (1, T.int64)}, tb, cut=lambda x: [rows(x, "out", x["count"][0]), x["count"]],
+                    want=self.expected(name) if hasattr(self, "_want_" + name[len("acm_gpu_"):]) else None)
 
     def _join_scan(self, name, family, most):
         import torch as T
@@ -736,7 +973,8 @@ class Features:
         tb = getattr(L, "acm_gpu_scan_%s_tmp_bytes" % family)(h, S, CAP, N, Tn)
         return Case(name, self.plan,
                     lambda p, st: getattr(L, name)(h, S, p["text"], N, 0, off, Tn, CAP, p["out"], OC, p["res"], p["res"] + 8, p["tmp"], tb, st),
-                    self._text(), {"out": (2 * OC, T.int64), "res": (2, T.int64)}, tb, cut=lambda x: [rows(x, "out", x["res"][0]), x["res"]])
+                    self._text(), {"out": (2 * OC, T.int64), "res": (2, T.int64)}, tb, cut=lambda x: [rows(x, "out", x["res"][0]), x["res"]],
+                    want=self.expected(name) if hasattr(self, "_want_" + name[len("acm_gpu_"):]) else None)
 
     def _patterns_records_device(self, name):
         return self._join_records(name, "patterns", int(self.handle("patterns").info()["max_anchor_postings"]))
@@ -763,7 +1001,7 @@ class Features:
                     lambda p, st: getattr(L, name)(h, S, p["rec"], CAP, p["n"], p["text"], N, 0, off, Tn, p["out"], p["dist"], OC, p["count"], p["tmp"], tb,
                                                    st),
                     gated, {"out": (2 * OC, T.int64), "dist": (OC, T.int32), "count": (1, T.int64)}, tb,
-                    cut=lambda x: [rows(x, "out", x["count"][0]), x["dist"][:x["count"][0]], x["count"]])
+                    cut=lambda x: [rows(x, "out", x["count"][0]), x["dist"][:x["count"][0]], x["count"]], want=self.expected(name))
 
     def _verify_scan(self, name, family):
         import torch as T
@@ -773,7 +1011,7 @@ class Features:
         return Case(name, self.plan,
                     lambda p, st: getattr(L, name)(h, S, p["text"], N, 0, off, Tn, CAP, p["out"], p["dist"], OC, p["res"], p["res"] + 8, p["tmp"], tb, st),
                     self._text(), {"out": (2 * OC, T.int64), "dist": (OC, T.int32), "res": (2, T.int64)}, tb,
-                    cut=lambda x: [rows(x, "out", x["res"][0]), x["dist"][:x["res"][0]], x["res"]])
+                    cut=lambda x: [rows(x, "out", x["res"][0]), x["dist"][:x["res"][0]], x["res"]], want=self.expected(name))
 
     def _approx_records_device(self, name):
         return self._verify_records(name, "approx")

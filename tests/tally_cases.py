@@ -103,6 +103,20 @@ def kind(name, monkeypatch, kat):
 KINDS = ["dense", "gram", "csr", "starts", "walk", "u64", "classes", "delta"]
 
 
+def planted(text, seed):
+    """`text` with 500 copies of six keywords of the 4-gram kind's dictionary (4 symbols or more each) written over it at
+    random: its own text holds a planted keyword per 4,096 symbols, too few for a selection or a pattern to tell"""
+    kd, ko = acm.synth.keywords(20000)
+    six = [k for k in range(ko.size - 1) if ko[k + 1] - ko[k] >= 4][:6]
+    rng = np.random.default_rng(seed)
+    t = text.copy()
+    for k in rng.choice(six, size=500):
+        w = kd[ko[k]:ko[k + 1]]
+        at = int(rng.integers(0, t.size - w.size))
+        t[at:at + w.size] = w
+    return t
+
+
 # ---- the machine without a GPU path: a comparator of its own over 3-byte symbols
 def sym3(word):
     """bytes -> the same word in 3-byte symbols (as bytes): the letter c is (c, c ^ 0x5A, 7) for the

@@ -40,8 +40,13 @@ def test_native_library_is_loaded_and_sees_the_gpu(torch_cuda):
 def test_small_cases_bit_exact(torch_cuda, name):
     kws, text, sym = CASES[name]
     m, o = build_pair(kws, sym)
+    bit_exact_on_plan(torch_cuda, m.plan(0), o, text)
+
+
+def bit_exact_on_plan(torch_cuda, plan, o, text):
+    """the plain scans of `text` on a plan of the oracle's dictionary, however it came to hold it (tests/test_growth_gpu.py
+    calls this with grown plans), against the oracle"""
     want = o.scan(text)
-    plan = m.plan(0)
     got = plan.scan_sorted(_dev(torch_cuda, text))
     assert got.size == want.size
     assert np.array_equal(got, want)
@@ -50,6 +55,11 @@ def test_small_cases_bit_exact(torch_cuda, name):
     assert int(cnt.item()) == o.count(text) == want.size
     # host-buffer C ABI path (no torch involved)
     assert np.array_equal(plan.scan_host(np.frombuffer(bytes(text), np.uint8) if isinstance(text, bytes) else text), want)
+    # the ordered scan writes the canonical order itself
+    rec, n, _ = plan.scan_ordered(_dev(torch_cuda, text), capacity=want.size + 8)
+    assert int(n.item()) == want.size
+    assert np.array_equal(np.frombuffer(rec[:want.size].cpu().numpy().tobytes(), dtype=acm.RECORD_DTYPE), want)
+    plan.status()
 
 
 @pytest.mark.parametrize("name", sorted(k for k in CASES if CASES[k][2] > 1))
@@ -1541,6 +1551,57 @@ def test_plan_timing_samples_every_nth_launch(torch_cuda):
         plan.timing(False)
         assert launches == sampled, (every, scans, launches)
         assert 0 < scan_ms <= all_ms and int(cnt.item()) == want
+    plan.timing(False)
+    plan.scan(dev, capacity=want + 8)
+    assert plan.timing_read_all()[2] == 0
+
+
+def test_plan_timing_goes_on_across_a_merge(torch_cuda, monkeypatch):
+    """acm_gpu_plan_timing (plan, 3), then acm_gpu_plan_update rebuilds everything behind the handle (a delta first, then
+    the merge): the period survives the new tables -- seven scans afterwards are launches 0, 3 and 6 -- and what was
+    sampled before the merge stays in the totals."""
+    torch = torch_cuda
+    rng = np.random.default_rng(12)
+    kws = [bytes(rng.integers(97, 123, size=int(rng.integers(2, 9)), dtype=np.uint8)) for _ in range(300)]
+    text = rng.integers(97, 123, size=1 << 20, dtype=np.uint8)
+    m, o = build_pair(kws[:200], 1)
+    plan = m.plan(0)
+    dev = _dev(torch, text)
+    plan.timing(3)
+    for w in kws[200:250]:
+        m.add_keyword(w)
+        o.add_keyword(w)
+    plan.update(m)
+    assert plan.info.delta_keywords > 0 and plan.info.merges == 0
+    for w in kws[250:]:
+        m.add_keyword(w)
+        o.add_keyword(w)
+    monkeypatch.setenv("ACM_GPU_DELTA", "0")
+    plan.update(m)
+    monkeypatch.delenv("ACM_GPU_DELTA")
+    assert plan.info.delta_keywords == 0 and plan.info.merges == 1
+    want = o.count(text)
+    for _ in range(7):
+        rec, cnt = plan.scan(dev, capacity=want + 8)
+    torch.cuda.synchronize()
+    scan_ms, all_ms, launches = plan.timing_read_all()
+    assert launches == 3, launches
+    assert 0 < scan_ms <= all_ms and int(cnt.item()) == want
+    # sampled before the merge, read after it: two scans at N = 2 in front, three behind -- launches 0, 2 and 4
+    plan.timing(2)
+    plan.scan(dev, capacity=want + 8)
+    plan.scan(dev, capacity=want + 8)
+    m.add_keyword(b"zzzzzzzzzz")
+    o.add_keyword(b"zzzzzzzzzz")
+    monkeypatch.setenv("ACM_GPU_DELTA", "0")
+    plan.update(m)
+    monkeypatch.delenv("ACM_GPU_DELTA")
+    assert plan.info.merges == 2
+    for _ in range(3):
+        rec, cnt = plan.scan(dev, capacity=want + 8)
+    torch.cuda.synchronize()
+    scan_ms, all_ms, launches = plan.timing_read_all()
+    assert launches == 3 and 0 < scan_ms <= all_ms and int(cnt.item()) == o.count(text)
     plan.timing(False)
     plan.scan(dev, capacity=want + 8)
     assert plan.timing_read_all()[2] == 0

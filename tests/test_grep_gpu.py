@@ -208,20 +208,24 @@ def test_contention_and_overflow(torch_cuda, monkeypatch):
     plan.status()
 
 
-def _alignment_case(sb, monkeypatch, kat):
+def small_dictionary(sb):
+    """(keywords, alphabet) of a symbol size: four keywords over seven symbols with every byte set"""
+    dtype = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[sb]
+    alphabet = (np.array([97, 98, 99, 100, 101, 102, 103], np.uint64) * np.uint64(int.from_bytes(b"\x01" * sb, "little"))).astype(dtype)
+    return [alphabet[[0, 1, 2]], alphabet[[3, 3]], alphabet[[6, 5, 4, 3]], alphabet[[2, 0]]], alphabet
+
+
+def _alignment_case(sb, monkeypatch, kat, small=False):
     """(oracle, plan maker, symbols, offsets) for a symbol size: the u64 kind, small dictionaries of our own
-    otherwise; one match of the buffer is copied across a text boundary"""
+    otherwise (small: for 8-byte symbols too); one match of the buffer is copied across a text boundary"""
     rng = np.random.default_rng(40 + sb)
     lens = [0, 1, 15, 16, 17, 33] * 8 + [5000] + [33, 17, 16, 15, 1, 0] * 8
     n = sum(lens)
-    if sb == 8:
+    if sb == 8 and not small:
         m, o, text, make_plan, plan_ok, form = kind("u64", monkeypatch, kat)
         base = text[1000:1000 + n].copy()
     else:
-        dtype = {1: np.uint8, 2: np.uint16, 4: np.uint32}[sb]
-        alphabet = np.array([97, 98, 99, 100, 101, 102, 103], np.uint64) * (1 if sb == 1 else 0x0101 if sb == 2 else 0x01010101)
-        alphabet = alphabet.astype(dtype)
-        kws = [alphabet[[0, 1, 2]], alphabet[[3, 3]], alphabet[[6, 5, 4, 3]], alphabet[[2, 0]]]
+        kws, alphabet = small_dictionary(sb)
         m, o = build_pair(kws, sb)
         make_plan = m.plan
         base = alphabet[rng.integers(0, alphabet.size, size=n)]
@@ -243,7 +247,12 @@ def test_gather_alignment(torch_cuda, monkeypatch, kat, sb, tile):
     if tile:
         monkeypatch.setenv("ACM_GPU_GREP_TILE", str(tile))
     o, make_plan, base, off = _alignment_case(sb, monkeypatch, kat)
-    plan = make_plan(0)
+    gather_alignment_on_plan(torch_cuda, make_plan(0), o, base, off, sb)
+
+
+def gather_alignment_on_plan(torch_cuda, plan, o, base, off, sb):
+    """test_gather_alignment's case through Plan.grep on a plan of the case's dictionary, however it came to hold it
+    (tests/test_growth_gpu.py calls this with grown plans)"""
     hits = oracle_hits(o, base, off)
     nontrivial(o, base, off, hits)
     d_off = _dev(torch_cuda, off)

@@ -120,14 +120,11 @@ def test_the_case_is_not_trivial():
     assert per[5] == 0 and min(per[:5] + per[6:]) >= 2 and ties >= 2 and two >= 1 and far >= 1 and lost >= 1
 
 
-@pytest.mark.parametrize("sb", [1, 2, 4, 8])
-def test_the_fixed_case_on_every_symbol_size(torch_cuda, fixed, sb):
-    torch = torch_cuda
-    rec, want = fixed
+def fixed_case_on_plan(torch, plan, sb, rec, want):
+    """the fixed case through every call that takes a plan (of CASE_KEYWORDS as symbols of sb bytes, however it came to
+    hold them: tests/test_growth_gpu.py calls this with grown plans); returns (symbols, set, offsets, NEAR under the cut)"""
     n = len(CASE_TEXT)
-    m = _machine(CASE_KEYWORDS, sb)
     ns = binding.NearSet(CASE_GROUPS)
-    plan = m.plan(0)
     sym = _sym(CASE_TEXT, sb)
     dev = _dev(torch, sym)
     S = plan.near(ns)
@@ -149,43 +146,67 @@ def test_the_fixed_case_on_every_symbol_size(torch_cuda, fixed, sb):
     for base in BASES:
         _same(_scan(plan, dev, S, rec.size, pos_base=base)[0], _shift(want, base), (sb, base))
         _same(_join(plan, _shift(rec, base), S, n, pos_base=base, offsets=d_off)[0], _shift(cut, base), (sb, base))
-    # host memory in, blocking; the machine's own call on a GPU path
+    # host memory in, blocking
     _same(plan.scan_near_host(sym, ns), want, sb)
     _same(plan.scan_near_host(sym, ns, pos_base=BASES[0], offsets=off), _shift(cut, BASES[0]), sb)
     with pytest.raises(acm.ACMError) as e:
         plan.scan_near_host(sym, ns, out_capacity=want.size - 1)
     assert e.value.code == E_OVERFLOW
-    _same(m.scan_near(sym, ns), want, sb)
-    assert m.scan_path == PATH_GPU
-    _same(m.scan_near(sym, ns, offsets=off), cut, sb)
-    with pytest.raises(acm.ACMError) as e:
-        m.scan_near(sym, ns, out_capacity=want.size - 1)
-    assert e.value.code == E_OVERFLOW and m.scan_path == PATH_GPU
     # an empty text, a text without a record
     assert plan.scan_near_host(np.zeros(0, DTYPE[sb]), ns).size == 0
     got, cnt, found = _scan(plan, _dev(torch, _sym(b"q" * 3000, sb)), S, 16)
     assert (cnt, found) == (0, 0)
     S.close()
     plan.status()
+    return sym, ns, off, cut
 
 
-def test_a_class_plan_nears_over_classes(torch_cuda, kat):
+@pytest.mark.parametrize("sb", [1, 2, 4, 8])
+def test_the_fixed_case_on_every_symbol_size(torch_cuda, fixed, sb):
+    rec, want = fixed
+    m = _machine(CASE_KEYWORDS, sb)
+    plan = m.plan(0)
+    sym, ns, off, cut = fixed_case_on_plan(torch_cuda, plan, sb, rec, want)
+    # the machine's own call on a GPU path
+    _same(m.scan_near(sym, ns), want, sb)
+    assert m.scan_path == PATH_GPU
+    _same(m.scan_near(sym, ns, offsets=off), cut, sb)
+    with pytest.raises(acm.ACMError) as e:
+        m.scan_near(sym, ns, out_capacity=want.size - 1)
+    assert e.value.code == E_OVERFLOW and m.scan_path == PATH_GPU
+    plan.status()
+
+
+def class_case(kat):
+    """(comparator, text, the oracle's records under the comparator, NEAR of them): the fixed case in mixed case"""
     cmp = C.cast(kat.kat_casecmp8, C.c_void_p)
-    m, o = _machine(CASE_KEYWORDS, cmp=cmp), po.Oracle(1, po.MEYER85, cmp=cmp)
+    o = po.Oracle(1, po.MEYER85, cmp=cmp)
     for w in CASE_KEYWORDS:
         o.add_keyword(w)
-    m.set_symbol_bytes(1)
     text = CASE_TEXT.replace(b"disk sda", b"DISK Sda").replace(b"she hers", b"SHE hers").replace(b"timeout error", b"TimeOut ERROR")
     assert text != CASE_TEXT and text.lower() == CASE_TEXT.lower()
     rec = o.scan(text)
     want = near(rec, CASE_GROUPS, len(text))
     _same(want, near_by_text(CASE_KEYWORDS, CASE_GROUPS, text.lower()), "the two derivations")
     assert near_by_text(CASE_KEYWORDS, CASE_GROUPS, text).size < want.size             # (the exact-case reading finds fewer)
-    plan = m.plan_classes(0)
-    got, cnt, found = _scan(plan, _dev(torch_cuda, text), CASE_GROUPS, rec.size)
+    return cmp, text, rec, want
+
+
+def class_case_on_plan(torch, plan, text, rec, want):
+    """the mixed-case text through the calls that take a class plan of CASE_KEYWORDS"""
+    got, cnt, found = _scan(plan, _dev(torch, text), CASE_GROUPS, rec.size)
     assert found == rec.size
     _same(got, want)
     _same(plan.scan_near_host(np.frombuffer(text, np.uint8), CASE_GROUPS), want)
+    plan.status()
+
+
+def test_a_class_plan_nears_over_classes(torch_cuda, kat):
+    cmp, text, rec, want = class_case(kat)
+    m = _machine(CASE_KEYWORDS, cmp=cmp)
+    m.set_symbol_bytes(1)
+    plan = m.plan_classes(0)
+    class_case_on_plan(torch_cuda, plan, text, rec, want)
     _same(m.scan_near(text, CASE_GROUPS), want)
     assert m.scan_path == PATH_CLASSES
     plan.status()

@@ -12,6 +12,7 @@ import pytest
 
 from aho_corasick_1975_amd import binding
 from aho_corasick_1975_amd.binding import ANY, SymbolClass
+from tests.batch_cases import packed_batch
 from tests.cases import build_pair
 
 pytestmark = pytest.mark.gpu
@@ -51,14 +52,8 @@ def _host_matches(family, rec, sets, text, off):
 
 
 def _batch():
-    """4 KiB over a seven-letter alphabet, cut into 37 texts: an empty first one, one of 700 symbols
-    (more than a 256-symbol batch block), 34 random ones, an empty last one"""
-    rng = np.random.default_rng(75)
-    text = np.frombuffer(b"hesir .", np.uint8)[rng.integers(0, 7, size=N_SYMBOLS)].copy()
-    cuts = np.sort(rng.choice(np.arange(701, N_SYMBOLS), size=N_TEXTS - 4, replace=False))
-    off = np.concatenate(([0, 0, 700], cuts, [N_SYMBOLS, N_SYMBOLS])).astype(np.uint64)
-    assert off.size == N_TEXTS + 1 and off[1] == off[0] and off[-1] == off[-2] and np.all(off[1:] >= off[:-1])
-    return text, off
+    """tests/batch_cases.py::packed_batch: 4 KiB over a seven-letter alphabet, cut into 37 texts"""
+    return packed_batch(N_SYMBOLS, N_TEXTS)
 
 
 class Case:

@@ -9,9 +9,9 @@ inputs and the call on the side stream over zeroed scratch: what runs on stream 
 LATE -- the gate on the null stream, scratch as a decoy call left it: what runs on stream 0 sits behind the gate and the
 stages behind it read what the decoy left; both also assert that the call came back while the gate was still running.
 CONTROL -- EARLY with the call on the null stream must give the decoy's answer: the gate is long enough, the streams are
-independent.  The expected value is the plain call's on the null stream; the feature tests hold those against the
-oracle and the definitions, and for the plain scans (and where a host pass of the definition is at hand) the case
-compares with the oracle directly as well.
+independent.  The expected value is the plain call's on the null stream, and that call is held against the case's own
+expected value first (Case.want): the oracle's records and the families' definitions in plain Python
+(stream_cases.Features.expected), for every output that has a definition -- never the library's own scan, join or host pass.
 
 The gate is 100 ms, or 50 times the plain call's wall time where that is more (never seen: on an MI355X the longest
 plain call of this module, synchronise included, took 0.56 ms, and _sleep ran at 2.40 million cycles per millisecond)."""
@@ -22,7 +22,7 @@ import aho_corasick_1975_amd as acm
 from tests import anchored_cases as ac
 from tests import stream_cases as sc
 from tests.cases import build_pair
-from tests.tally_cases import KINDS, kind
+from tests.tally_cases import KINDS, kind, planted
 from tests.test_scratch_bounds_gpu import KEYWORDS, _batch
 
 N_PLAIN = 1 << 16                                        # symbols of the plain scans: the text of a plan kind cut to its first 64 Ki
@@ -76,27 +76,13 @@ def dense_features(torch_cuda):
     return f
 
 
-def _planted(text, seed):
-    """`text` with 500 copies of six keywords of the 4-gram kind's dictionary (4 symbols or more each) written over it at
-    random: its own text holds a planted keyword per 4,096 symbols, too few for a selection or a pattern to tell"""
-    kd, ko = acm.synth.keywords(20000)
-    six = [k for k in range(ko.size - 1) if ko[k + 1] - ko[k] >= 4][:6]
-    rng = np.random.default_rng(seed)
-    t = text.copy()
-    for k in rng.choice(six, size=500):
-        w = kd[ko[k]:ko[k + 1]]
-        at = int(rng.integers(0, t.size - w.size))
-        t[at:at + w.size] = w
-    return t
-
-
 @pytest.fixture(scope="module")
 def gram_features(torch_cuda):
     """the 4-gram kind of tests/tally_cases.py over _batch ()'s offsets: two stretches of its text with keywords planted,
     words cut at n to z"""
     _, off = _batch()
     m, o, text, make_plan, plan_ok, _ = kind("gram", None, None)
-    f = sc.Features(torch_cuda, m, o, make_plan, _planted(text[:4096], 77), _planted(text[8192:12288], 78), off, word_ranges=((0x61, 0x6D),))
+    f = sc.Features(torch_cuda, m, o, make_plan, planted(text[:4096], 77), planted(text[8192:12288], 78), off, word_ranges=((0x61, 0x6D),))
     assert plan_ok(f.plan), f.plan.describe()
     return f
 
@@ -208,14 +194,19 @@ def test_anchored_entry_points(torch_cuda, gates, entry):
     real = np.frombuffer(b"".join(ac.TEXTS), np.uint8).copy()
     off = np.concatenate([[0], np.cumsum([len(t) for t in ac.TEXTS])]).astype(np.uint64)
     decoy = real[::-1].copy()
-    want = []
-    for text in (real, decoy):                           # on the CPU, by the oracle and the definition
+    want, look = [], []
+    for text in (real, decoy):                           # on the CPU, by the oracle and the definitions
         rec, text_of = ac.batch_records(o, text, off)
-        want.append(ac.anchored(rec, off, ac.PREFIXES, text_of)[0])
-    assert want[0].size == ac.N_PREFIXES and 0 < want[1].size != want[0].size
+        want.append(ac.anchored(rec, off, ac.PREFIXES, text_of))
+        look.append(ac.lookup(rec, off, text_of))
+    assert want[0][0].size == ac.N_PREFIXES and 0 < want[1][0].size != want[0][0].size
+    assert not all(np.array_equal(a, b) for a, b in zip(look[0], look[1]))
     case = {c.name: c for c in sc.anchored_cases(torch_cuda, m.plan(0), real, decoy, off)}[entry]
     if entry == "acm_gpu_scan_anchored_device":
-        case.want = [sc.rec_rows(want[0]), None, None, np.array([want[0].size])]
+        r, tid, first = want[0]
+        case.want = [sc.rec_rows(r), sc.i32(tid), sc.i64(first), np.array([r.size])]
+    else:
+        case.want = [sc.i32(a) for a in look[0]]
     _pass(sc.exercise(torch_cuda, gates, case, control=entry in sc.CONTROLS))
 
 

@@ -333,6 +333,53 @@ def test_a_class_plan_tests_the_callers_own_symbols(torch_cuda, monkeypatch, kat
     plan.status()
 
 
+def fused_calls_on_plan(torch_cuda, plan, sb, text, rec, want):
+    """the fused calls and the filter behind both scans, through every call that takes a plan (of novel_case ()'s keywords
+    as symbols of sb bytes, however it came to hold them: tests/test_growth_gpu.py calls this with grown plans); returns
+    (symbols, ranges)"""
+    sym = _sym(text, sb)
+    dev = _dev(torch_cuda, sym)
+    ranges = _ranges(ASCII_WORD, sb)
+    # scan_words is the filter of scan_ordered
+    all_rec, all_cnt, _ = plan.scan_ordered(dev, capacity=rec.size)
+    assert int(all_cnt.item()) == rec.size
+    assert np.array_equal(_rec_host(all_rec, rec.size), rec)
+    for flags, name in ((LEFT, "left"), (RIGHT, "right"), (BOTH, "both")):
+        r, c, _ = plan.scan_words(dev, ranges=ranges, flags=name, capacity=rec.size)
+        _same(_rec_host(r, int(c.item())), words(rec, text, flags=flags), (sb, name))
+        out, cnt = plan.words_records(dev, all_rec, rec.size, ranges=ranges, flags=name, count=all_cnt)
+        _same(_rec_host(out, int(cnt.item())), words(rec, text, flags=flags), (sb, name))
+    # the filter of the UNORDERED scan keeps the same set
+    raw, raw_cnt = plan.scan(dev, capacity=rec.size)
+    out, cnt = plan.words_records(dev, raw, rec.size, ranges=ranges, count=raw_cnt)
+    assert as_set(_rec_host(out, int(cnt.item()))) == as_set(want) and int(cnt.item()) == want.size
+    # capacity too small for ALL matches: the scan's count
+    r, c, _ = plan.scan_words(dev, ranges=ranges, capacity=rec.size - 1)
+    assert int(c.item()) == rec.size
+    r, c, _ = plan.scan_words(dev, ranges=ranges, capacity=want.size)
+    assert int(c.item()) == rec.size
+    # host memory in, blocking: an overflow reports a capacity that suffices
+    with pytest.raises(acm.ACMError) as e:
+        plan.scan_words_host(sym, ranges=ranges, capacity=rec.size - 1)
+    assert e.value.code == E_OVERFLOW
+    n = C.c_uint64(0)
+    small = np.zeros(rec.size - 1, po.RECORD_DTYPE)
+    rr = np.asarray(ranges, np.uint64).astype(DTYPE[sb]).reshape(-1)
+    assert acm.lib().acm_gpu_scan_words_host(plan.h, sym.ctypes.data, sym.size, 0, None, 0, rr.ctypes.data, 4, 3, small.ctypes.data, small.size,
+                                             C.byref(n)) == E_OVERFLOW and n.value == rec.size
+    _same(plan.scan_words_host(sym, ranges=ranges, capacity=int(n.value)), want)
+    _same(plan.scan_words_host(sym, ranges=ranges), want)
+    # an empty text and a text without a match
+    empty = _dev(torch_cuda, np.zeros(16, DTYPE[sb]))[:0]
+    r, c, _ = plan.scan_words(empty, ranges=ranges, capacity=16)
+    assert int(c.item()) == 0
+    r, c, _ = plan.scan_words(_dev(torch_cuda, _sym(b"q" * 3000, sb)), ranges=ranges, capacity=16)
+    assert int(c.item()) == 0
+    assert plan.scan_words_host(np.zeros(0, DTYPE[sb]), ranges=ranges).size == 0
+    plan.status()
+    return sym, ranges
+
+
 def test_fused_calls_on_every_symbol_size_and_a_pending_delta(torch_cuda, novel_bytes):
     keywords, text, rec, want = novel_case(novel_bytes)
     for sb in (1, 2, 4, 8):
@@ -346,50 +393,12 @@ def test_fused_calls_on_every_symbol_size_and_a_pending_delta(torch_cuda, novel_
                 m.add_keyword(_sym(kw, sb))
             plan.update(m)
             assert plan.info.delta_keywords == len(keywords) - first and plan.info.merges == 0, plan.describe()
-        sym = _sym(text, sb)
-        dev = _dev(torch_cuda, sym)
-        ranges = _ranges(ASCII_WORD, sb)
-        # scan_words is the filter of scan_ordered
-        all_rec, all_cnt, _ = plan.scan_ordered(dev, capacity=rec.size)
-        assert int(all_cnt.item()) == rec.size
-        assert np.array_equal(_rec_host(all_rec, rec.size), rec)
-        for flags, name in ((LEFT, "left"), (RIGHT, "right"), (BOTH, "both")):
-            r, c, _ = plan.scan_words(dev, ranges=ranges, flags=name, capacity=rec.size)
-            _same(_rec_host(r, int(c.item())), words(rec, text, flags=flags), (sb, name))
-            out, cnt = plan.words_records(dev, all_rec, rec.size, ranges=ranges, flags=name, count=all_cnt)
-            _same(_rec_host(out, int(cnt.item())), words(rec, text, flags=flags), (sb, name))
-        # the filter of the UNORDERED scan keeps the same set
-        raw, raw_cnt = plan.scan(dev, capacity=rec.size)
-        out, cnt = plan.words_records(dev, raw, rec.size, ranges=ranges, count=raw_cnt)
-        assert as_set(_rec_host(out, int(cnt.item()))) == as_set(want) and int(cnt.item()) == want.size
-        # capacity too small for ALL matches: the scan's count
-        r, c, _ = plan.scan_words(dev, ranges=ranges, capacity=rec.size - 1)
-        assert int(c.item()) == rec.size
-        r, c, _ = plan.scan_words(dev, ranges=ranges, capacity=want.size)
-        assert int(c.item()) == rec.size
-        # host memory in, blocking: an overflow reports a capacity that suffices
-        with pytest.raises(acm.ACMError) as e:
-            plan.scan_words_host(sym, ranges=ranges, capacity=rec.size - 1)
-        assert e.value.code == E_OVERFLOW
-        n = C.c_uint64(0)
-        small = np.zeros(rec.size - 1, po.RECORD_DTYPE)
-        rr = np.asarray(ranges, np.uint64).astype(DTYPE[sb]).reshape(-1)
-        assert acm.lib().acm_gpu_scan_words_host(plan.h, sym.ctypes.data, sym.size, 0, None, 0, rr.ctypes.data, 4, 3, small.ctypes.data, small.size,
-                                                 C.byref(n)) == E_OVERFLOW and n.value == rec.size
-        _same(plan.scan_words_host(sym, ranges=ranges, capacity=int(n.value)), want)
-        _same(plan.scan_words_host(sym, ranges=ranges), want)
+        sym, ranges = fused_calls_on_plan(torch_cuda, plan, sb, text, rec, want)
         # the machine's own call, on a GPU path
         _same(m.scan_words(sym, ranges=ranges), want)
         assert m.scan_path == PATH_GPU
         with pytest.raises(acm.ACMError):
             m.scan_words(sym, ranges=ranges, capacity=want.size)                        # room for the kept records alone is not enough
-        # an empty text and a text without a match
-        empty = _dev(torch_cuda, np.zeros(16, DTYPE[sb]))[:0]
-        r, c, _ = plan.scan_words(empty, ranges=ranges, capacity=16)
-        assert int(c.item()) == 0
-        r, c, _ = plan.scan_words(_dev(torch_cuda, _sym(b"q" * 3000, sb)), ranges=ranges, capacity=16)
-        assert int(c.item()) == 0
-        assert plan.scan_words_host(np.zeros(0, DTYPE[sb]), ranges=ranges).size == 0
         plan.status()
 
 
