@@ -25,6 +25,7 @@ from .binding import (  # noqa: F401
     ACM_TEMPLATE_LITERAL, ACM_TEMPLATE_ANY, ACM_TEMPLATE_NEGATED, ACM_TEMPLATE_MAX_RANGES,
     ChainSet, Chains, ChainsInfo, chains_records,
     NearSet, Near, NearInfo, near_records, NEAR_EXPORTS,
+    Cooccurred, cooccur_matrix, cooccur_add, COOCCUR_EXPORTS, ACM_COOCCUR_PRODUCT, ACM_COOCCUR_DIAGONAL,
 )
 from . import synth  # noqa: F401
 from . import sharded  # noqa: F401

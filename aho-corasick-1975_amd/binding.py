@@ -182,6 +182,13 @@ NEAR_EXPORTS = [
     "acm_gpu_near_records_device", "acm_gpu_scan_near_tmp_bytes", "acm_gpu_scan_near_device", "acm_gpu_scan_near_host", "acm_scan_near",
 ]
 
+# every function include/acm_cooccur.h declares (a list of its own, as NEAR_EXPORTS is)
+COOCCUR_EXPORTS = [
+    "acm_cooccur_matrix", "acm_cooccur_add", "acm_gpu_cooccur_matrix_tmp_bytes", "acm_gpu_cooccur_matrix_device", "acm_gpu_cooccur_add_tmp_bytes",
+    "acm_gpu_cooccur_add_device", "acm_gpu_cooccur_tmp_bytes", "acm_gpu_cooccur_device", "acm_gpu_cooccur_host", "acm_cooccur",
+]
+ACM_COOCCUR_PRODUCT, ACM_COOCCUR_DIAGONAL = 1, 2
+
 
 def lib():
     """Loads the native library; raises (never falls back) when it has not been built."""
@@ -410,6 +417,25 @@ def lib():
     for fn in (L.acm_gpu_index_host, L.acm_index):
         fn.restype = i32
         fn.argtypes = [vp, vp, vp, u64, u64, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.acm_cooccur_matrix.restype = i32
+    L.acm_cooccur_matrix.argtypes = [vp, vp, vp, u64, u64, u32, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.acm_cooccur_add.restype = i32
+    L.acm_cooccur_add.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_gpu_cooccur_matrix_tmp_bytes.restype = sz
+    L.acm_gpu_cooccur_matrix_tmp_bytes.argtypes = [vp, u64, u64, u64]
+    L.acm_gpu_cooccur_matrix_device.restype = i32
+    L.acm_gpu_cooccur_matrix_device.argtypes = [vp, vp, vp, vp, u64, u64, u32, u64, u64, vp, vp, vp, u64, vp, vp, vp, vp, sz, vp]
+    L.acm_gpu_cooccur_add_tmp_bytes.restype = sz
+    L.acm_gpu_cooccur_add_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_cooccur_add_device.restype = i32
+    L.acm_gpu_cooccur_add_device.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp, vp, sz, vp]
+    L.acm_gpu_cooccur_tmp_bytes.restype = sz
+    L.acm_gpu_cooccur_tmp_bytes.argtypes = [vp, u64, u64, u64, u64, u64, u64, u64]
+    L.acm_gpu_cooccur_device.restype = i32
+    L.acm_gpu_cooccur_device.argtypes = [vp, vp, u64, vp, u64, u64, u64, u64, u64, u32, u64, u64, vp, vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    for fn in (L.acm_gpu_cooccur_host, L.acm_cooccur):
+        fn.restype = i32
+        fn.argtypes = [vp, vp, vp, u64, u64, u32, u64, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.acm_segment_records.restype = i32
     L.acm_segment_records.argtypes = [vp, u64, vp, u64, u32, C.POINTER(u64), vp]
     L.acm_gpu_segment_tmp_bytes.restype = sz
@@ -1322,6 +1348,123 @@ def _index_host_call(fn, what, handle, t, sym_size, off, n_keywords, text_base):
         return fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, int(text_base), post_ptr, int(n_keywords), post_text, post_count,
                   cap, n, C.byref(total))
     return _indexed_host_call(call, what, n_keywords, text_base, total)
+
+
+class Cooccurred:
+    """What the cooccur calls return: the keyword co-occurrence matrix of a batch, the upper triangle of
+    X in CSR form over keywords -- co_ptr (n_keywords + 1 entries), co_col (the ids b, strictly ascending
+    within a row, b > a, or b >= a with ACM_COOCCUR_DIAGONAL) and co_val (X[a][b]).  int64 / int32 /
+    int64 device tensors from Plan.cooccur(), Plan.cooccur_matrix() and Plan.cooccur_add() -- co_col and
+    co_val have room for out_capacity entries, their first nnz count --, uint64 / uint32 / uint64 numpy
+    arrays cut to size from the host calls.  nnz, cross (the pair instances), skipped (the texts above
+    row_limit), flags, row_limit and total (the sum of the tally's counts; None where no text was
+    scanned) are Python ints; need and need_pairs as a TalliedBatch has them."""
+
+    def __init__(self, co_ptr, co_col, co_val, nnz, cross=None, skipped=None, flags=0, total=None, row_limit=0, need=None, need_pairs=None,
+                 out_capacity=None):
+        self.co_ptr, self.co_col, self.co_val, self.nnz, self.cross, self.skipped = co_ptr, co_col, co_val, nnz, cross, skipped
+        self.flags, self.total, self.row_limit, self.need, self.need_pairs, self.out_capacity = flags, total, row_limit, need, need_pairs, out_capacity
+
+    @property
+    def n_keywords(self):
+        return int(self.co_ptr.shape[0]) - 1
+
+    def row(self, a):
+        """(ids, values) of row a: views of its entries, the keywords b that occur with a and X[a][b]"""
+        lo, hi = int(self.co_ptr[int(a)]), int(self.co_ptr[int(a) + 1])
+        return self.co_col[lo:hi], self.co_val[lo:hi]
+
+    def value(self, a, b):
+        """X[a][b] as a Python int, the ids in either order; 0 where the matrix has no entry"""
+        a, b = min(int(a), int(b)), max(int(a), int(b))
+        ids, values = self.row(a)
+        hit = (ids == b).nonzero()
+        hit = hit[0] if isinstance(hit, tuple) else hit.reshape(-1)
+        return int(values[int(hit[0])]) & 0xFFFFFFFFFFFFFFFF if len(hit) else 0
+
+    def to_sparse_csr(self, n_keywords=None):
+        """The upper triangle as a torch.sparse_csr_tensor of n_keywords x n_keywords int64 values, built
+        on the arrays where they are: nothing is copied when they are device tensors."""
+        import torch
+
+        def tensor(a, dtype):
+            return a.view(dtype) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).view(dtype)
+        nk = self.n_keywords if n_keywords is None else int(n_keywords)
+        assert nk == self.n_keywords, "co_ptr has n_keywords + 1 entries"
+        return torch.sparse_csr_tensor(tensor(self.co_ptr, torch.int64), tensor(self.co_col, torch.int32)[:self.nnz],
+                                       tensor(self.co_val, torch.int64)[:self.nnz], size=(nk, nk))
+
+
+def _cooccur_flags(flags):
+    flags = int(flags)
+    if flags & ~(ACM_COOCCUR_PRODUCT | ACM_COOCCUR_DIAGONAL):
+        raise ACMError(ACM_GPU_E_ARG, "cooccur: flags is a bit set of ACM_COOCCUR_PRODUCT and ACM_COOCCUR_DIAGONAL")
+    return flags
+
+
+def _cooccurred_host_call(call, what, n_keywords, flags=0, row_limit=0, total=None):
+    """call(co_ptr, co_col, co_val, capacity, nnz, cross, skipped) -> rc, for the host calls: a Cooccurred of numpy
+    arrays out.  An output overflow is repeated once with the size the call reports."""
+    co_ptr = np.zeros(int(n_keywords) + 1, np.uint64)
+    cross, skipped = C.c_uint64(0), C.c_uint64(0)
+    def room(cap):
+        co_col, co_val = np.zeros(cap, np.uint32), np.zeros(cap, np.uint64)
+        n = C.c_uint64(0)
+        return call(co_ptr.ctypes.data, co_col.ctypes.data, co_val.ctypes.data, cap, C.byref(n), C.byref(cross), C.byref(skipped)), n.value, (co_col, co_val)
+    (co_col, co_val), m, cap = _room_call(room, what, 1024)
+    return Cooccurred(co_ptr, co_col[:m], co_val[:m], m, int(cross.value), int(skipped.value), int(flags),
+                      int(total.value) if total is not None else None, int(row_limit), out_capacity=cap)
+
+
+def cooccur_matrix(tallied, flags=0, row_limit=0, n_keywords=None):
+    """acm_cooccur_matrix(): the co-occurrence matrix of the count matrix `tallied` (a TalliedBatch of
+    numpy arrays) over n_keywords keywords (None: one more than the greatest id it holds), by the
+    sequential definition on the host.  Returns a Cooccurred of numpy arrays."""
+    row_ptr = np.ascontiguousarray(tallied.row_ptr, dtype=np.uint64)
+    col = np.ascontiguousarray(tallied.col, dtype=np.uint32)
+    val = np.ascontiguousarray(tallied.val, dtype=np.uint64)
+    assert row_ptr.size >= 1, "row_ptr has n_texts + 1 entries"
+    nk = int(n_keywords) if n_keywords is not None else (int(col.max()) + 1 if col.size else 0)
+
+    def call(co_ptr, co_col, co_val, cap, n, cross, skipped):
+        return lib().acm_cooccur_matrix(row_ptr.ctypes.data, _ptr(col), _ptr(val), row_ptr.size - 1, nk, int(flags), int(row_limit), co_ptr, co_col,
+                                        co_val, cap, n, cross, skipped)
+    return _cooccurred_host_call(call, "acm_cooccur_matrix", nk, flags, row_limit)
+
+
+def _sum_or_none(x, y):
+    return x + y if x is not None and y is not None else None
+
+
+def cooccur_add(a, b):
+    """acm_cooccur_add(): the entrywise sum of two Cooccurred of numpy arrays (a has no more keywords than
+    b; both under the same flags and row_limit).  Returns a Cooccurred of numpy arrays; cross, skipped and
+    total are the sums."""
+    arrays = []
+    for x in (a, b):
+        arrays.append((np.ascontiguousarray(x.co_ptr, dtype=np.uint64), np.ascontiguousarray(x.co_col, dtype=np.uint32),
+                       np.ascontiguousarray(x.co_val, dtype=np.uint64)))
+    (ap, ac, av), (bp, bc, bv) = arrays
+    assert ap.size >= 1 and bp.size >= 1, "co_ptr has n_keywords + 1 entries"
+
+    def call(out_ptr, out_col, out_val, cap, n, cross, skipped):
+        return lib().acm_cooccur_add(ap.ctypes.data, _ptr(ac), _ptr(av), ap.size - 1, bp.ctypes.data, _ptr(bc), _ptr(bv), bp.size - 1, out_ptr, out_col,
+                                     out_val, cap, n)
+    got = _cooccurred_host_call(call, "acm_cooccur_add", bp.size - 1, b.flags, b.row_limit)
+    got.cross, got.skipped, got.total = _sum_or_none(a.cross, b.cross), _sum_or_none(a.skipped, b.skipped), _sum_or_none(a.total, b.total)
+    return got
+
+
+def _cooccur_host_call(fn, what, handle, t, sym_size, off, n_keywords, flags, row_limit):
+    """acm_gpu_cooccur_host / acm_cooccur: numpy in, a Cooccurred of numpy arrays out"""
+    n_texts = off.size - 1
+    assert t.size * t.itemsize == int(off[-1]) * sym_size, "the last offset is the number of symbols"
+    total = C.c_uint64(0)
+
+    def call(co_ptr, co_col, co_val, cap, n, cross, skipped):
+        return fn(handle, t.ctypes.data if t.size else None, off.ctypes.data, n_texts, int(n_keywords), int(flags), int(row_limit), co_ptr, co_col,
+                  co_val, cap, n, cross, skipped, C.byref(total))
+    return _cooccurred_host_call(call, what, n_keywords, flags, row_limit, total)
 
 
 def weight(k, w, cap=None):
@@ -2812,6 +2955,16 @@ class Machine(_Owner):
         nk = self.nb_keywords if n_keywords is None else int(n_keywords)
         return _index_host_call(self.L.acm_index, "acm_index", self.handle, packed, self.sym_size, offsets, nk, text_base)
 
+    def cooccur(self, texts, flags=0, row_limit=0, n_keywords=None):
+        """acm_cooccur(): the keyword co-occurrence matrix of a list of texts (bytes or arrays of symbols),
+        each scanned from the root on its own in ONE call: which keywords occur together, and in how many
+        texts (flags: ACM_COOCCUR_PRODUCT sums the products of the counts, ACM_COOCCUR_DIAGONAL keeps
+        a == b; row_limit > 0 leaves out the texts with more keywords than that).  n_keywords (None: the
+        machine's) may be larger for a dictionary that will grow.  Returns a Cooccurred of numpy arrays."""
+        packed, offsets = self._pack_texts(texts)
+        nk = self.nb_keywords if n_keywords is None else int(n_keywords)
+        return _cooccur_host_call(self.L.acm_cooccur, "acm_cooccur", self.handle, packed, self.sym_size, offsets, nk, _cooccur_flags(flags), row_limit)
+
 
 class Replaced:
     """What Plan.replace_records() and Plan.scan_replace() leave on the device: `out` (a uint8 tensor,
@@ -3613,6 +3766,120 @@ class Plan(_Owner):
         off = np.ascontiguousarray(offsets, dtype=np.uint64)
         assert off.size >= 1, "offsets has n_texts + 1 entries"
         return _index_host_call(lib().acm_gpu_index_host, "acm_gpu_index_host", self.h, t, self.sym_size, off, self._index_keywords(n_keywords), text_base)
+
+    def _cooccur_outputs(self, dev, n_keywords, out_capacity):
+        import torch
+        co_col = torch.zeros(out_capacity, dtype=torch.int32, device=dev) if out_capacity else None
+        return _i64(n_keywords + 1, dev), co_col, _i64(out_capacity, dev) if out_capacity else None
+
+    @staticmethod
+    def _cooccur_rooms(run, what, cross_capacity, out_capacity):
+        """run(cross_capacity, out_capacity) -> a Cooccurred, for the device calls whose counts are read back: repeated
+        with the cross room the device reported when that was too small and none was given, then -- out_capacity
+        None -- counted first and sized by nnz"""
+        room = [int(cross_capacity) if cross_capacity is not None else 1 << 16]
+
+        def call(cap):
+            got = run(room[0], cap)
+            if got.cross > room[0] and cross_capacity is None:
+                room[0] = got.cross
+                got = run(room[0], cap)
+            if got.cross > room[0]:
+                e = ACMError(ACM_GPU_E_OVERFLOW, "%s: %d pair instances, room for %d" % (what, got.cross, room[0]))
+                e.need = got.cross
+                raise e
+            return got
+        return _counted(call, out_capacity, "nnz")
+
+    def cooccur(self, text, offsets, flags=0, row_limit=0, n_keywords=None, window=None, capacity=None, pair_capacity=None, cross_capacity=None,
+                out_capacity=None):
+        """acm_gpu_cooccur_device(): the keyword co-occurrence matrix of a batch on the device: the tally of
+        tally_batch() (same `text`, `offsets`, `window`, `capacity`, `pair_capacity`) and the pair passes
+        behind it in one call, queued on the current stream; neither a record nor the count matrix leaves
+        the device.  n_keywords (None: the plan's) may be larger.  cross_capacity: the room of the pair
+        instances (None: 64 Ki, repeated once with what the device reports).  out_capacity: the room of
+        co_col and co_val (0: count only, which gives co_ptr; None: counted first, then sized by the
+        count).  Returns a Cooccurred of device tensors; synchronises to read its numbers.  Every repeat runs
+        the whole call again, the tally included, with scratch of its own: with both rooms None that is up to
+        three runs (the cross room reported, the count, the sized run).  A caller who knows the rooms of a
+        batch, or takes them from the previous one (`cross`, `nnz`), passes both and pays for one."""
+        n_symbols, n_texts = self._batch_args(text, offsets)
+        window, capacity, pair_capacity = self._windows(window, capacity, pair_capacity)
+        nk = self._index_keywords(n_keywords)
+        flags = _cooccur_flags(flags)
+        dev = text.device
+        res = _i64(6, dev)                                                       # nnz, total, need, need_pairs, cross, skipped
+
+        def run(cross_cap, cap):
+            tmp = _scratch(lib().acm_gpu_cooccur_tmp_bytes(self.h, window, capacity, pair_capacity, n_symbols, n_texts, nk, cross_cap), dev)
+            co_ptr, co_col, co_val = self._cooccur_outputs(dev, nk, cap)
+            _check(lib().acm_gpu_cooccur_device(self.h, text.data_ptr(), n_symbols, offsets.data_ptr(), n_texts, window, capacity, pair_capacity, nk,
+                                                flags, int(row_limit), cross_cap, co_ptr.data_ptr(), _opt(co_col), _opt(co_val), cap, res.data_ptr(),
+                                                res.data_ptr() + 32, res.data_ptr() + 40, res.data_ptr() + 8, res.data_ptr() + 16,
+                                                res.data_ptr() + 24, tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_cooccur_device")
+            nnz, total, need, need_pairs, cross, skipped = (int(x) for x in res.cpu())
+            return Cooccurred(co_ptr, co_col, co_val, nnz, cross, skipped, flags, total, int(row_limit), need, need_pairs, cap)
+        return self._cooccur_rooms(run, "acm_gpu_cooccur_device", cross_capacity, out_capacity)
+
+    def cooccur_matrix(self, tallied, flags=0, row_limit=0, n_keywords=None, cross_capacity=None, out_capacity=None):
+        """acm_gpu_cooccur_matrix_device(): the co-occurrence matrix of a count matrix that lies on the
+        device: `tallied` is a TalliedBatch of device tensors, tally_batch()'s or the caller's own (row_ptr
+        int64 with n_texts + 1 entries, col int32 ascending within a row, val int64).  The rooms as in
+        cooccur().  Returns a Cooccurred of device tensors (total, need and need_pairs None); synchronises
+        to read its numbers."""
+        row_ptr, col, val, n_texts = self._matrix_args(tallied)
+        nk = self._index_keywords(n_keywords)
+        flags = _cooccur_flags(flags)
+        dev = row_ptr.device
+        res = _i64(3, dev)                                                       # nnz, cross, skipped
+
+        def run(cross_cap, cap):
+            tmp = _scratch(lib().acm_gpu_cooccur_matrix_tmp_bytes(self.h, n_texts, nk, cross_cap), dev)
+            co_ptr, co_col, co_val = self._cooccur_outputs(dev, nk, cap)
+            _check(lib().acm_gpu_cooccur_matrix_device(self.h, row_ptr.data_ptr(), col.data_ptr(), val.data_ptr(), n_texts, nk, flags, int(row_limit),
+                                                       cross_cap, co_ptr.data_ptr(), _opt(co_col), _opt(co_val), cap, res.data_ptr(),
+                                                       res.data_ptr() + 8, res.data_ptr() + 16, tmp.data_ptr(), tmp.numel(), self._stream()),
+                   "acm_gpu_cooccur_matrix_device")
+            nnz, cross, skipped = (int(x) for x in res.cpu())
+            return Cooccurred(co_ptr, co_col, co_val, nnz, cross, skipped, flags, None, int(row_limit), out_capacity=cap)
+        return self._cooccur_rooms(run, "acm_gpu_cooccur_matrix_device", cross_capacity, out_capacity)
+
+    def cooccur_add(self, a, b, cross_capacity=None, out_capacity=None):
+        """acm_gpu_cooccur_add_device(): the entrywise sum of two Cooccurred of device tensors (a has no
+        more keywords than b; both under the same flags and row_limit).  cross_capacity None: a.nnz +
+        b.nnz, which always suffices; out_capacity None: the same, which cannot overflow.  Returns a
+        Cooccurred of device tensors whose cross, skipped and total are the sums; synchronises to read nnz."""
+        import torch
+        dev = a.co_ptr.device
+        for x in (a, b):
+            assert x.co_ptr.is_cuda and x.co_ptr.is_contiguous() and x.co_ptr.dtype == torch.int64
+        nka, nkb = a.n_keywords, b.n_keywords
+        both = int(a.nnz) + int(b.nnz)
+        cross_cap = int(cross_capacity) if cross_capacity is not None else both
+        cap = int(out_capacity) if out_capacity is not None else both
+        res = _i64(2, dev)                                                       # nnz, the cross room needed
+        tmp = _scratch(lib().acm_gpu_cooccur_add_tmp_bytes(self.h, nkb, cross_cap), dev)
+        out_ptr, out_col, out_val = self._cooccur_outputs(dev, nkb, cap)
+        p = _opt
+        _check(lib().acm_gpu_cooccur_add_device(self.h, a.co_ptr.data_ptr(), p(a.co_col), p(a.co_val), nka, b.co_ptr.data_ptr(), p(b.co_col),
+                                                p(b.co_val), nkb, cross_cap, out_ptr.data_ptr(), p(out_col), p(out_val), cap, res.data_ptr(),
+                                                res.data_ptr() + 8, tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_cooccur_add_device")
+        nnz, need = (int(x) for x in res.cpu())
+        if need > cross_cap:
+            e = ACMError(ACM_GPU_E_OVERFLOW, "acm_gpu_cooccur_add_device: %d entries, room for %d" % (need, cross_cap))
+            e.need = need
+            raise e
+        return Cooccurred(out_ptr, out_col, out_val, nnz, _sum_or_none(a.cross, b.cross), _sum_or_none(a.skipped, b.skipped), b.flags,
+                          _sum_or_none(a.total, b.total), b.row_limit, out_capacity=cap)
+
+    def cooccur_host(self, text, offsets, flags=0, row_limit=0, n_keywords=None):
+        """acm_gpu_cooccur_host(): the same as cooccur() from host arrays, through the C ABI only (no torch).
+        The call sizes its windows, its pair room and its cross room itself.  Returns a Cooccurred of numpy arrays."""
+        t = np.ascontiguousarray(text)
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        assert off.size >= 1, "offsets has n_texts + 1 entries"
+        return _cooccur_host_call(lib().acm_gpu_cooccur_host, "acm_gpu_cooccur_host", self.h, t, self.sym_size, off, self._index_keywords(n_keywords),
+                                  _cooccur_flags(flags), row_limit)
 
     def patterns_create(self, patternset):
         """acm_gpu_patterns_create(): `patternset` (a PatternSet, or lists of (keyword_id, offset, length)

@@ -5829,6 +5829,349 @@ acm_gpu_index_host (ACMPlan *plan, const void *text, const uint64_t *offsets, ui
   return ACM_GPU_OK;
 }
 
+/* ------------------------------------------------------------------ the co-occurrence matrix of a batch (include/acm_cooccur.h, dev_cooccur.h)
+ * The passes that expand a count matrix on the device into its keyword pairs and reduce equal pairs, and
+ * the sum of two such matrices; acm_gpu_cooccur_device runs the former behind acm_gpu_tally_batch_device. */
+namespace {
+/* what cooccur_carve derives beside K's pointers */
+struct CooccurRoom {
+  size_t zero_bytes = 0; /* control words and the texts' pair counts: the head of the scratch, cleared in front of every call */
+  long long *p = nullptr, *pbase = nullptr; /* K's, as the sum takes them */
+  unsigned long long *key[2] = { nullptr, nullptr }, *w[2] = { nullptr, nullptr }; /* the sort room and its second half */
+  uint32_t *rank = nullptr;
+  CubRoom cub;  /* the exclusive sums: n_texts + 1 pair counts, room + 1 marks */
+  void *scan_tmp = nullptr, *sort_tmp = nullptr; /* the weights' inclusive sum, the radix sort */
+  size_t scan_bytes = 0, sort_bytes = 0;
+};
+
+size_t
+cooccur_scan_bytes (uint64_t n) {
+  size_t bytes = 0;
+  (void)hipcub::DeviceScan::InclusiveSum (nullptr, bytes, static_cast<unsigned long long *> (nullptr), static_cast<unsigned long long *> (nullptr), (int)n,
+                                          nullptr);
+  return bytes;
+}
+
+/* scratch of the radix sort over n slots, keys alone or pairs, whichever needs more */
+size_t
+cooccur_sort_bytes (uint64_t n) {
+  size_t keys_only = 0;
+  hipcub::DoubleBuffer<unsigned long long> k (nullptr, nullptr);
+  (void)hipcub::DeviceRadixSort::SortKeys (nullptr, keys_only, k, (int)n, 0, 64, nullptr);
+  return std::max (keys_only, index_sort_bytes (n));
+}
+
+/* n_texts = 0: ADD, which has no rows to count */
+CooccurRoom
+cooccur_carve (Carve &c, uint64_t n_texts, uint64_t cross_capacity, CoK &K) {
+  CooccurRoom R;
+  K.room = cross_capacity ? cross_capacity : 1;
+  K.G.ctl = c.take<RulesCtl> (1);
+  K.cctl = c.take<CoCtl> (1);
+  R.p = c.take<long long> (n_texts + 1);
+  R.zero_bytes = c.used;
+  R.pbase = c.take<long long> (n_texts + 1);
+  for (int h = 0; h < 2; h++) {
+    R.key[h] = c.take<unsigned long long> ((size_t)K.room);
+    R.w[h] = c.take<unsigned long long> ((size_t)K.room);
+  }
+  K.mark = c.take<uint32_t> ((size_t)K.room + 1);
+  R.rank = c.take<uint32_t> ((size_t)K.room + 1);
+  R.cub = cub_room (c, K.room + 1, n_texts + 1);
+  R.scan_bytes = cooccur_scan_bytes (K.room);
+  R.scan_tmp = c.take (R.scan_bytes + 16);
+  R.sort_bytes = cooccur_sort_bytes (K.room);
+  R.sort_tmp = c.take (R.sort_bytes + 16);
+  K.p = reinterpret_cast<unsigned long long *> (R.p);
+  K.pbase = reinterpret_cast<const unsigned long long *> (R.pbase);
+  K.key = R.key[0];
+  K.w = R.w[0];
+  K.rank = R.rank;
+  return R;
+}
+
+/* acm_gpu_cooccur_matrix_tmp_bytes behind its checks */
+size_t
+cooccur_bytes (uint64_t n_texts, uint64_t cross_capacity) {
+  Carve c;
+  CoK K{};
+  cooccur_carve (c, n_texts, cross_capacity, K);
+  return c.total ();
+}
+
+/* the matrix calls' own arguments */
+bool
+cooccur_args_ok (const ACMPlan *plan, uint64_t n_texts, uint64_t n_keywords, uint32_t flags, uint64_t cross_capacity, const uint64_t *d_co_ptr,
+                 const uint32_t *d_co_col, const uint64_t *d_co_val, uint64_t out_capacity, const uint64_t *d_nnz, const uint64_t *d_cross,
+                 const uint64_t *d_skipped) {
+  return plan && n_texts < (1ull << 31) && n_keywords >= plan->covered_keywords && n_keywords < (1ull << 32) &&
+         !(flags & ~(ACM_COOCCUR_PRODUCT | ACM_COOCCUR_DIAGONAL)) && cross_capacity < (1ull << 31) && out_capacity < (1ull << 31) && d_co_ptr && d_nnz &&
+         d_cross && d_skipped && ((d_co_col && d_co_val) || (out_capacity == 0 && !d_co_col && !d_co_val));
+}
+
+/* without a text: every row is empty */
+int
+cooccur_empty (uint64_t n_keywords, uint64_t *d_co_ptr, uint64_t *d_nnz, uint64_t *d_cross, uint64_t *d_skipped, hipStream_t st) {
+  HIP_TRY (hipMemsetAsync (d_co_ptr, 0, (n_keywords + 1) * 8, st));
+  HIP_TRY (hipMemsetAsync (d_nnz, 0, 8, st));
+  HIP_TRY (hipMemsetAsync (d_cross, 0, 8, st));
+  HIP_TRY (hipMemsetAsync (d_skipped, 0, 8, st));
+  return ACM_GPU_OK;
+}
+
+/* bits of a key's b-field: the fewest with 2^kb - 1 >= n_keywords, so that an all-ones field is no keyword */
+uint32_t
+cooccur_key_bits (uint64_t n_keywords) {
+  uint32_t kb = 1;
+  while (((1ull << kb) - 1) < n_keywords)
+    kb++;
+  return kb;
+}
+
+/* passes 4 to 7 of dev_cooccur.h over the room as pass 3 (or ADD's feed) filled it; weights: sort pairs and sum them */
+int
+cooccur_reduce (ACMPlan *plan, CoK &K, const CooccurRoom &L, bool weights, hipStream_t st) {
+  const dim3 room_grid = capped_grid (plan, (K.room + 1 + 255) / 256);
+  /* 4. */
+  hipcub::DoubleBuffer<unsigned long long> keys (L.key[0], L.key[1]), vals (L.w[0], L.w[1]);
+  size_t sort_bytes = L.sort_bytes;
+  if (weights)
+    HIP_TRY (hipcub::DeviceRadixSort::SortPairs (L.sort_tmp, sort_bytes, keys, vals, (int)K.room, 0, (int)(2 * K.kb), st));
+  else
+    HIP_TRY (hipcub::DeviceRadixSort::SortKeys (L.sort_tmp, sort_bytes, keys, (int)K.room, 0, (int)(2 * K.kb), st));
+  K.skey = keys.Current ();
+  K.start = reinterpret_cast<uint32_t *> (keys.Alternate ());
+  HIP_TRY (launch (cooccur_heads_kernel, room_grid, dim3 (256), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, K.mark, L.rank, K.room + 1, st));
+  /* 5. */
+  if (weights) {
+    size_t scan_bytes = L.scan_bytes;
+    HIP_TRY (hipcub::DeviceScan::InclusiveSum (L.scan_tmp, scan_bytes, vals.Current (), vals.Alternate (), (int)K.room, st));
+    K.wsum = vals.Alternate ();
+  }
+  /* 6. */
+  HIP_TRY (launch (cooccur_ptr_kernel, capped_grid (plan, (K.n_keywords + 1 + 255) / 256), dim3 (256), 0, st, K));
+  /* 7. (by the room: the host knows no more of nnz than that it is at most min (room, out_capacity)) */
+  if (K.d_co_col) {
+    HIP_TRY (launch (cooccur_starts_kernel, room_grid, dim3 (256), 0, st, K));
+    HIP_TRY (launch (cooccur_fill_kernel, capped_grid (plan, (std::min (K.room, K.out_capacity) + 255) / 256), dim3 (256), 0, st, K));
+  }
+  return ACM_GPU_OK;
+}
+
+/* the passes of dev_cooccur.h on a matrix on the device; `tb` as rules_evaluate has it */
+int
+cooccur_build (ACMPlan *plan, const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_val, uint64_t n_texts, uint64_t n_keywords, uint32_t flags,
+               uint64_t row_limit, uint64_t cross_capacity, uint64_t *d_co_ptr, uint32_t *d_co_col, uint64_t *d_co_val, uint64_t out_capacity,
+               uint64_t *d_nnz, uint64_t *d_cross, uint64_t *d_skipped, void *d_tmp, hipStream_t st, const TbCtl *tb, uint64_t tb_capacity,
+               uint64_t tb_pair_capacity) {
+  Carve carve (d_tmp);
+  CoK K{};
+  const CooccurRoom L = cooccur_carve (carve, n_texts, cross_capacity, K);
+  K.G.row_ptr = reinterpret_cast<const unsigned long long *> (d_row_ptr);
+  K.G.n_texts = n_texts;
+  K.G.tb = tb;
+  K.G.tb_capacity = tb_capacity;
+  K.G.tb_pair_capacity = tb_pair_capacity;
+  K.G.error = error_word (plan);
+  K.col = d_col;
+  K.val = reinterpret_cast<const unsigned long long *> (d_val);
+  K.n_keywords = n_keywords;
+  K.row_limit = row_limit;
+  K.cross_capacity = cross_capacity;
+  K.out_capacity = out_capacity;
+  K.flags = flags;
+  K.kb = cooccur_key_bits (n_keywords);
+  K.d_co_ptr = reinterpret_cast<unsigned long long *> (d_co_ptr);
+  K.d_co_col = d_co_col;
+  K.d_co_val = reinterpret_cast<unsigned long long *> (d_co_val);
+  K.d_nnz = reinterpret_cast<unsigned long long *> (d_nnz);
+  K.d_cross = reinterpret_cast<unsigned long long *> (d_cross);
+  K.d_skipped = reinterpret_cast<unsigned long long *> (d_skipped);
+  HIP_TRY (hipMemsetAsync (d_tmp, 0, L.zero_bytes, st));
+  const dim3 text_grid = capped_grid (plan, (n_texts + 1 + 255) / 256);
+  /* 1. */
+  HIP_TRY (launch (rules_check_kernel, text_grid, dim3 (256), 0, st, K.G));
+  /* 2. */
+  HIP_TRY (launch (cooccur_count_kernel, text_grid, dim3 (256), 0, st, K));
+  HIP_TRY (exclusive_sum (L.cub, L.p, L.pbase, n_texts + 1, st));
+  HIP_TRY (launch (cooccur_finish_kernel, dim3 (1), dim3 (WAVE), 0, st, K));
+  /* 3. */
+  HIP_TRY (launch (cooccur_expand_kernel, capped_grid (plan, (K.room + 255) / 256), dim3 (256), 0, st, K));
+  return cooccur_reduce (plan, K, L, (flags & ACM_COOCCUR_PRODUCT) != 0, st);
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_cooccur_matrix_tmp_bytes (const ACMPlan *plan, uint64_t n_texts, uint64_t n_keywords, uint64_t cross_capacity) {
+  if (!plan || n_texts >= (1ull << 31) || n_keywords < plan->covered_keywords || n_keywords >= (1ull << 32) || cross_capacity >= (1ull << 31))
+    return 0;
+  return cooccur_bytes (n_texts, cross_capacity);
+}
+
+extern "C" int
+acm_gpu_cooccur_matrix_device (ACMPlan *plan, const uint64_t *d_row_ptr, const uint32_t *d_col, const uint64_t *d_val, uint64_t n_texts, uint64_t n_keywords,
+                               uint32_t flags, uint64_t row_limit, uint64_t cross_capacity, uint64_t *d_co_ptr, uint32_t *d_co_col, uint64_t *d_co_val,
+                               uint64_t out_capacity, uint64_t *d_nnz, uint64_t *d_cross, uint64_t *d_skipped, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!cooccur_args_ok (plan, n_texts, n_keywords, flags, cross_capacity, d_co_ptr, d_co_col, d_co_val, out_capacity, d_nnz, d_cross, d_skipped))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (n_texts == 0)
+    return cooccur_empty (n_keywords, d_co_ptr, d_nnz, d_cross, d_skipped, st);
+  if (!d_row_ptr || !d_tmp || tmp_bytes < cooccur_bytes (n_texts, cross_capacity))
+    return ACM_GPU_E_ARG;
+  return cooccur_build (plan, d_row_ptr, d_col, d_val, n_texts, n_keywords, flags, row_limit, cross_capacity, d_co_ptr, d_co_col, d_co_val, out_capacity,
+                        d_nnz, d_cross, d_skipped, d_tmp, st, nullptr, 0, 0);
+}
+
+extern "C" size_t
+acm_gpu_cooccur_add_tmp_bytes (const ACMPlan *plan, uint64_t n_keywords_b, uint64_t cross_capacity) {
+  if (!plan || n_keywords_b >= (1ull << 32) || cross_capacity >= (1ull << 31))
+    return 0;
+  return cooccur_bytes (0, cross_capacity);
+}
+
+extern "C" int
+acm_gpu_cooccur_add_device (ACMPlan *plan, const uint64_t *d_a_ptr, const uint32_t *d_a_col, const uint64_t *d_a_val, uint64_t n_keywords_a,
+                            const uint64_t *d_b_ptr, const uint32_t *d_b_col, const uint64_t *d_b_val, uint64_t n_keywords_b, uint64_t cross_capacity,
+                            uint64_t *d_out_ptr, uint32_t *d_out_col, uint64_t *d_out_val, uint64_t out_capacity, uint64_t *d_out_nnz, uint64_t *d_cross,
+                            void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!plan || !d_a_ptr || !d_b_ptr || n_keywords_a > n_keywords_b || n_keywords_b >= (1ull << 32) || cross_capacity >= (1ull << 31) ||
+      out_capacity >= (1ull << 31) || !d_out_ptr || !d_out_nnz || !d_cross ||
+      !((d_out_col && d_out_val) || (out_capacity == 0 && !d_out_col && !d_out_val)) || !d_tmp || tmp_bytes < cooccur_bytes (0, cross_capacity))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  Carve carve (d_tmp);
+  CoK K{};
+  const CooccurRoom L = cooccur_carve (carve, 0, cross_capacity, K);
+  K.G.error = error_word (plan);
+  K.a_ptr = reinterpret_cast<const unsigned long long *> (d_a_ptr);
+  K.b_ptr = reinterpret_cast<const unsigned long long *> (d_b_ptr);
+  K.a_val = reinterpret_cast<const unsigned long long *> (d_a_val);
+  K.b_val = reinterpret_cast<const unsigned long long *> (d_b_val);
+  K.a_col = d_a_col;
+  K.b_col = d_b_col;
+  K.n_a = n_keywords_a;
+  K.n_keywords = n_keywords_b;
+  K.cross_capacity = cross_capacity;
+  K.out_capacity = out_capacity;
+  K.flags = ACM_COOCCUR_PRODUCT; /* (the later passes sum weights) */
+  K.kb = cooccur_key_bits (n_keywords_b);
+  K.d_co_ptr = reinterpret_cast<unsigned long long *> (d_out_ptr);
+  K.d_co_col = d_out_col;
+  K.d_co_val = reinterpret_cast<unsigned long long *> (d_out_val);
+  K.d_nnz = reinterpret_cast<unsigned long long *> (d_out_nnz);
+  K.d_cross = reinterpret_cast<unsigned long long *> (d_cross);
+  HIP_TRY (hipMemsetAsync (d_tmp, 0, L.zero_bytes, st));
+  /* the check of the pointer arrays (an address is formed from them only behind it), the room needed, the feed */
+  HIP_TRY (launch (cooccur_add_check_kernel, capped_grid (plan, (n_keywords_b + 1 + 255) / 256), dim3 (256), 0, st, K));
+  HIP_TRY (launch (cooccur_add_finish_kernel, dim3 (1), dim3 (WAVE), 0, st, K));
+  HIP_TRY (launch (cooccur_add_feed_kernel, capped_grid (plan, (K.room + 255) / 256), dim3 (256), 0, st, K));
+  return cooccur_reduce (plan, K, L, true, st);
+}
+
+extern "C" size_t
+acm_gpu_cooccur_tmp_bytes (const ACMPlan *plan, uint64_t window_symbols, uint64_t capacity, uint64_t pair_capacity, uint64_t n_symbols, uint64_t n_texts,
+                           uint64_t n_keywords, uint64_t cross_capacity) {
+  if (n_keywords >= (1ull << 32) || cross_capacity >= (1ull << 31) ||
+      !acm_gpu_tally_batch_tmp_bytes (plan, window_symbols, capacity, pair_capacity, n_symbols, n_texts) || n_keywords < plan->covered_keywords)
+    return 0;
+  Carve c;
+  rules_call_carve (c, plan, cooccur_bytes (n_texts, cross_capacity), capacity, pair_capacity, n_symbols, n_texts);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_cooccur_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint64_t window_symbols,
+                        uint64_t capacity, uint64_t pair_capacity, uint64_t n_keywords, uint32_t flags, uint64_t row_limit, uint64_t cross_capacity,
+                        uint64_t *d_co_ptr, uint32_t *d_co_col, uint64_t *d_co_val, uint64_t out_capacity, uint64_t *d_nnz, uint64_t *d_cross,
+                        uint64_t *d_skipped, uint64_t *d_total, uint64_t *d_need, uint64_t *d_need_pairs, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!cooccur_args_ok (plan, n_texts, n_keywords, flags, cross_capacity, d_co_ptr, d_co_col, d_co_val, out_capacity, d_nnz, d_cross, d_skipped) || !d_tmp ||
+      capacity == 0 || capacity >= (1ull << 31) || pair_capacity == 0 || pair_capacity >= (1ull << 31))
+    return ACM_GPU_E_ARG;
+  Carve carve (d_tmp);
+  const RulesCallRoom L = rules_call_carve (carve, plan, cooccur_bytes (n_texts, cross_capacity), capacity, pair_capacity, n_symbols, n_texts);
+  if (tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  if (const int rc = tally_then_evaluate (plan, d_text, n_symbols, d_offsets, n_texts, window_symbols, capacity, pair_capacity, L, d_co_ptr, d_nnz, d_total,
+                                          d_need, d_need_pairs, stream, [&] {
+                                            return cooccur_build (plan, L.row_ptr, L.col, L.val, n_texts, n_keywords, flags, row_limit, cross_capacity,
+                                                                  d_co_ptr, d_co_col, d_co_val, out_capacity, d_nnz, d_cross, d_skipped, d_tmp, st, L.tb,
+                                                                  capacity, pair_capacity);
+                                          }))
+    return rc;
+  return n_texts == 0 ? cooccur_empty (n_keywords, d_co_ptr, d_nnz, d_cross, d_skipped, st) : ACM_GPU_OK;
+}
+
+extern "C" int
+acm_gpu_cooccur_host (ACMPlan *plan, const void *text, const uint64_t *offsets, uint64_t n_texts, uint64_t n_keywords, uint32_t flags, uint64_t row_limit,
+                      uint64_t *co_ptr, uint32_t *co_col, uint64_t *co_val, uint64_t out_capacity, uint64_t *nnz, uint64_t *cross, uint64_t *skipped,
+                      uint64_t *total) {
+  if (!plan || !co_ptr || !nnz || n_keywords < plan->covered_keywords || n_keywords >= (1ull << 32) ||
+      (flags & ~(ACM_COOCCUR_PRODUCT | ACM_COOCCUR_DIAGONAL)) || out_capacity >= (1ull << 31) || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
+    return ACM_GPU_E_ARG;
+  const uint64_t n_symbols = offsets[n_texts];
+  const bool fills = co_col && co_val && out_capacity;
+  DeviceTemps temps;
+  void *d_text = nullptr;
+  uint64_t *d_off = nullptr, *d_co_ptr = nullptr, *d_co_val = nullptr, *d_res = nullptr; /* d_res: nnz, total, need, need_pairs, cross, skipped */
+  uint32_t *d_co_col = nullptr;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  HOST_TRY (temps.get (&d_co_ptr, (n_keywords + 1) * 8));
+  HOST_TRY (temps.get (&d_res, 48));
+  HOST_TRY (hipMemset (d_res, 0, 48));
+  if (fills) {
+    HOST_TRY (temps.get (&d_co_col, (size_t)out_capacity * 4));
+    HOST_TRY (temps.get (&d_co_val, (size_t)out_capacity * 8));
+  }
+  const uint64_t d_capacity = fills ? out_capacity : 0;
+  /* the cross room: a guess, then what the device reported, which is exact */
+  uint64_t cross_capacity = std::min<uint64_t> (std::max<uint64_t> (1ull << 16, 4 * n_texts), (1ull << 31) - 1);
+  uint64_t res[4] = { 0, 0, 0, 0 }, more[2] = { 0, 0 };
+  for (int attempt = 0;; attempt++) {
+    if (const int rc = with_tally_rooms (
+          plan, temps, n_symbols, d_res, res,
+          [&] (uint64_t window, uint64_t capacity, uint64_t pairs) {
+            return acm_gpu_cooccur_tmp_bytes (plan, window, capacity, pairs, n_symbols, n_texts, n_keywords, cross_capacity);
+          },
+          [&] (uint64_t window, uint64_t capacity, uint64_t pairs, void *d_tmp, size_t tmp_bytes) {
+            return acm_gpu_cooccur_device (plan, d_text, n_symbols, d_off, n_texts, window, capacity, pairs, n_keywords, flags, row_limit, cross_capacity,
+                                           d_co_ptr, d_co_col, d_co_val, d_capacity, d_res, d_res + 4, d_res + 5, d_res + 1, d_res + 2, d_res + 3, d_tmp,
+                                           tmp_bytes, nullptr);
+          }))
+      return rc;
+    HOST_TRY (hipMemcpy (more, d_res + 4, 16, hipMemcpyDeviceToHost));
+    if (more[0] <= cross_capacity)
+      break;
+    if (more[0] >= (1ull << 31)) /* more pair instances than one call holds */
+      return ACM_GPU_E_NOMEM;
+    if (attempt) /* (the second room is what the first attempt asked for: never expected) */
+      return ACM_GPU_E_INTERNAL;
+    cross_capacity = more[0];
+  }
+  HOST_TRY (hipMemcpy (co_ptr, d_co_ptr, (n_keywords + 1) * 8, hipMemcpyDeviceToHost));
+  *nnz = res[0];
+  if (cross)
+    *cross = more[0];
+  if (skipped)
+    *skipped = more[1];
+  if (total)
+    *total = res[1];
+  if (!co_col || !co_val) /* the call only counts */
+    return ACM_GPU_OK;
+  if (res[0] > out_capacity)
+    return ACM_GPU_E_OVERFLOW;
+  if (res[0]) {
+    HOST_TRY (hipMemcpy (co_col, d_co_col, res[0] * 4, hipMemcpyDeviceToHost));
+    HOST_TRY (hipMemcpy (co_val, d_co_val, res[0] * 8, hipMemcpyDeviceToHost));
+  }
+  return ACM_GPU_OK;
+}
+
 /* ------------------------------------------------------------------ leftmost-longest selection (include/acm_gpu.h, dev_select.h)
  * The passes over a record set in canonical order; acm_gpu_scan_select_device runs them behind the
  * ordered scan. */
@@ -9491,6 +9834,44 @@ acm_index (ACMachine *machine, const void *text, const uint64_t *offsets, uint64
     },
     [&] (ACMPlan *plan) {
       return acm_gpu_index_host (plan, text, offsets, n_texts, text_base, post_ptr, n_keywords, post_text, post_count, post_capacity, nnz, total);
+    });
+}
+
+/* the co-occurrence matrix of a batch (include/acm_cooccur.h) */
+extern "C" int
+acm_cooccur (ACMachine *machine, const void *text, const uint64_t *offsets, uint64_t n_texts, uint64_t n_keywords, uint32_t flags, uint64_t row_limit,
+             uint64_t *co_ptr, uint32_t *co_col, uint64_t *co_val, uint64_t out_capacity, uint64_t *nnz, uint64_t *cross, uint64_t *skipped,
+             uint64_t *total) {
+  if (!machine || !co_ptr || !nnz || n_keywords >= (1ull << 32) || (flags & ~(ACM_COOCCUR_PRODUCT | ACM_COOCCUR_DIAGONAL)) ||
+      out_capacity >= (1ull << 31) || !batch_args_ok (text, offsets, n_texts, 1ull << 31))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) {
+      if (n_keywords < acm_nb_keywords (machine))
+        return (int)ACM_GPU_E_ARG;
+      /* tally_batch's host loop into a room of the call's own, grown once to what the matrix needs */
+      std::vector<uint64_t> row_ptr (n_texts + 1), val;
+      std::vector<uint32_t> col;
+      uint64_t room = 1024, found = 0;
+      int rc = ACM_GPU_OK;
+      for (int attempt = 0; attempt < 2; attempt++) {
+        col.resize (room);
+        val.resize (room);
+        rc = acm_internal_cpu_tally_batch (machine, text, offsets, n_texts, said, row_ptr.data (), col.data (), val.data (), room, &found, total);
+        if (rc != ACM_GPU_E_OVERFLOW)
+          break;
+        room = found;
+      }
+      if (rc == ACM_GPU_E_OVERFLOW) /* (the second room is what the first attempt asked for: never expected) */
+        rc = ACM_GPU_E_INTERNAL;
+      return rc ? rc
+                : acm_cooccur_matrix (row_ptr.data (), col.data (), val.data (), n_texts, n_keywords, flags, row_limit, co_ptr, co_col, co_val,
+                                      out_capacity, nnz, cross, skipped);
+    },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_cooccur_host (plan, text, offsets, n_texts, n_keywords, flags, row_limit, co_ptr, co_col, co_val, out_capacity, nnz, cross, skipped,
+                                   total);
     });
 }
 

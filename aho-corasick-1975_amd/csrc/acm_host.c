@@ -1336,6 +1336,146 @@ acm_index_concat (const uint64_t *a_ptr, const uint32_t *a_text, const uint64_t 
   return ACM_GPU_OK;
 }
 
+/* The co-occurrence matrix of a count matrix in CSR form (include/acm_cooccur.h): the plain sequential
+ * definition.  Every contributing row is expanded into its pair instances (a << 32 | b, weight), the
+ * instances are sorted by key, and every run of equal keys is one entry: its length, or the sum of its
+ * weights modulo 2^64.  Memory: 16 bytes per pair instance. */
+typedef struct {
+  uint64_t key, w;
+} CooccurPair;
+
+static int
+cooccur_pair_cmp (const void *x, const void *y) {
+  const uint64_t a = ((const CooccurPair *)x)->key, b = ((const CooccurPair *)y)->key;
+  return a < b ? -1 : a > b;
+}
+
+/* a pointer array of n + 1 entries begins with 0 and never decreases; its rows ascend strictly by col, every col below `cols` */
+static int
+cooccur_csr_ok (const uint64_t *ptr, const uint32_t *col, uint64_t n, uint64_t cols) {
+  if (!ptr || ptr[0] != 0)
+    return 0;
+  for (uint64_t t = 0; t < n; t++)
+    if (ptr[t] > ptr[t + 1])
+      return 0;
+  if (ptr[n] && !col)
+    return 0;
+  for (uint64_t t = 0; t < n; t++)
+    for (uint64_t e = ptr[t]; e < ptr[t + 1]; e++)
+      if (col[e] >= cols || (e > ptr[t] && col[e] <= col[e - 1]))
+        return 0;
+  return 1;
+}
+
+int
+acm_cooccur_matrix (const uint64_t *row_ptr, const uint32_t *col, const uint64_t *val, uint64_t n_texts, uint64_t n_keywords, uint32_t flags,
+                    uint64_t row_limit, uint64_t *co_ptr, uint32_t *co_col, uint64_t *co_val, uint64_t out_capacity, uint64_t *nnz, uint64_t *cross,
+                    uint64_t *skipped) {
+  if (!co_ptr || !nnz || (flags & ~(ACM_COOCCUR_PRODUCT | ACM_COOCCUR_DIAGONAL)) || n_texts >= (1ull << 31) || n_keywords >= (1ull << 32) ||
+      out_capacity >= (1ull << 31) || !cooccur_csr_ok (row_ptr, col, n_texts, n_keywords) || (row_ptr[n_texts] && !val))
+    return ACM_GPU_E_ARG;
+  const int product = (flags & ACM_COOCCUR_PRODUCT) != 0, diagonal = (flags & ACM_COOCCUR_DIAGONAL) != 0;
+  uint64_t n_cross = 0, n_skipped = 0;
+  for (uint64_t t = 0; t < n_texts; t++) {
+    const uint64_t r = row_ptr[t + 1] - row_ptr[t]; /* (at most n_keywords: the row ascends strictly) */
+    if (row_limit && r > row_limit) {
+      n_skipped++;
+      continue;
+    }
+    const uint64_t p = r * (r - 1 + 2 * (uint64_t)diagonal) / 2;
+    if (n_cross + p < n_cross)
+      return ACM_GPU_E_NOMEM;
+    n_cross += p;
+  }
+  if (n_cross > SIZE_MAX / sizeof (CooccurPair))
+    return ACM_GPU_E_NOMEM;
+  CooccurPair *pair = malloc (n_cross ? n_cross * sizeof *pair : 1);
+  if (!pair)
+    return ACM_GPU_E_NOMEM;
+  uint64_t at = 0;
+  for (uint64_t t = 0; t < n_texts; t++) {
+    const uint64_t begin = row_ptr[t], end = row_ptr[t + 1];
+    if (row_limit && end - begin > row_limit)
+      continue;
+    for (uint64_t i = begin; i < end; i++)
+      for (uint64_t j = diagonal ? i : i + 1; j < end; j++) {
+        pair[at].key = ((uint64_t)col[i] << 32) | col[j];
+        pair[at++].w = product ? val[i] * val[j] : 1;
+      }
+  }
+  qsort (pair, n_cross, sizeof *pair, cooccur_pair_cmp);
+  for (uint64_t k = 0; k <= n_keywords; k++)
+    co_ptr[k] = 0;
+  uint64_t all = 0;
+  for (uint64_t q = 0; q < n_cross; q++)
+    if (q == 0 || pair[q].key != pair[q - 1].key) {
+      co_ptr[(pair[q].key >> 32) + 1]++;
+      all++;
+    }
+  for (uint64_t k = 0; k < n_keywords; k++)
+    co_ptr[k + 1] += co_ptr[k];
+  *nnz = all;
+  if (cross)
+    *cross = n_cross;
+  if (skipped)
+    *skipped = n_skipped;
+  int rc = ACM_GPU_OK;
+  if (co_col && co_val) { /* (else the call only counts) */
+    if (all > out_capacity)
+      rc = ACM_GPU_E_OVERFLOW;
+    else
+      for (uint64_t q = 0, e = 0; q < n_cross; e++) {
+        uint64_t sum = 0;
+        const uint64_t key = pair[q].key;
+        for (; q < n_cross && pair[q].key == key; q++)
+          sum += pair[q].w;
+        co_col[e] = (uint32_t)key;
+        co_val[e] = sum;
+      }
+  }
+  free (pair);
+  return rc;
+}
+
+/* ADD of two co-occurrence matrices (include/acm_cooccur.h): a two-pointer merge per row, run twice: to count, then to fill */
+int
+acm_cooccur_add (const uint64_t *a_ptr, const uint32_t *a_col, const uint64_t *a_val, uint64_t n_keywords_a, const uint64_t *b_ptr, const uint32_t *b_col,
+                 const uint64_t *b_val, uint64_t n_keywords_b, uint64_t *out_ptr, uint32_t *out_col, uint64_t *out_val, uint64_t out_capacity,
+                 uint64_t *out_nnz) {
+  if (!out_ptr || !out_nnz || n_keywords_a > n_keywords_b || n_keywords_b >= (1ull << 32) || out_capacity >= (1ull << 31) ||
+      !cooccur_csr_ok (a_ptr, a_col, n_keywords_a, n_keywords_b) || !cooccur_csr_ok (b_ptr, b_col, n_keywords_b, n_keywords_b) ||
+      (a_ptr[n_keywords_a] && !a_val) || (b_ptr[n_keywords_b] && !b_val))
+    return ACM_GPU_E_ARG;
+  for (int fill = 0; fill < 2; fill++) {
+    uint64_t at = 0;
+    for (uint64_t k = 0; k < n_keywords_b; k++) {
+      uint64_t i = k < n_keywords_a ? a_ptr[k] : 0, j = b_ptr[k];
+      const uint64_t i_end = k < n_keywords_a ? a_ptr[k + 1] : 0, j_end = b_ptr[k + 1];
+      if (!fill)
+        out_ptr[k] = at;
+      while (i < i_end || j < j_end) {
+        const int from_a = i < i_end && (j >= j_end || a_col[i] <= b_col[j]), from_b = j < j_end && (i >= i_end || b_col[j] <= a_col[i]);
+        if (fill) {
+          out_col[at] = from_a ? a_col[i] : b_col[j];
+          out_val[at] = (from_a ? a_val[i] : 0) + (from_b ? b_val[j] : 0);
+        }
+        i += from_a;
+        j += from_b;
+        at++;
+      }
+    }
+    if (!fill) {
+      out_ptr[n_keywords_b] = at;
+      *out_nnz = at;
+      if (!out_col || !out_val) /* the call only counts */
+        return ACM_GPU_OK;
+      if (at > out_capacity)
+        return ACM_GPU_E_OVERFLOW;
+    }
+  }
+  return ACM_GPU_OK;
+}
+
 /* SELECT of records in canonical order (include/acm_gpu.h), in place in the front of the array: the
  * plain sequential greedy pass.  The order is by end and the rule goes by start, so a round looks
  * at a window: from the first record that ends at or behind p up to the first that ends lmax or

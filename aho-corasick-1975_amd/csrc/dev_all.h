@@ -247,6 +247,7 @@ join_postings (const JoinK &K, const uint32_t *post_ptr, uint32_t n_keywords, co
 #include "dev_segment.h"
 #include "dev_score.h"
 #include "dev_index.h"
+#include "dev_cooccur.h"
 
 static_assert (WORDS_THREADS == OFFSETS_CHECK_THREADS && CONTEXT_THREADS == OFFSETS_CHECK_THREADS && ANCHORED_THREADS == OFFSETS_CHECK_THREADS &&
                  PATTERNS_THREADS == OFFSETS_CHECK_THREADS && APPROX_THREADS == OFFSETS_CHECK_THREADS,
