@@ -26,6 +26,8 @@ from .binding import (  # noqa: F401
     ChainSet, Chains, ChainsInfo, chains_records,
     NearSet, Near, NearInfo, near_records, NEAR_EXPORTS,
     Cooccurred, cooccur_matrix, cooccur_add, COOCCUR_EXPORTS, ACM_COOCCUR_PRODUCT, ACM_COOCCUR_DIAGONAL,
+    chars_records, chars_positions, CHARS_EXPORTS, STR_MATCH_DTYPE, ACM_CHARS_CODEPOINTS, ACM_CHARS_UTF16,
+    ACM_CHARS_EDGE_START, ACM_CHARS_EDGE_END, ACM_CHARS_EDGE_BAD,
 )
 from . import synth  # noqa: F401
 from . import sharded  # noqa: F401

@@ -189,6 +189,17 @@ COOCCUR_EXPORTS = [
 ]
 ACM_COOCCUR_PRODUCT, ACM_COOCCUR_DIAGONAL = 1, 2
 
+# every function include/acm_chars.h declares (a list of its own, as NEAR_EXPORTS is)
+CHARS_EXPORTS = [
+    "acm_chars_positions", "acm_chars_records", "acm_gpu_chars_ruler_bytes", "acm_gpu_chars_ruler_tmp_bytes", "acm_gpu_chars_ruler_device",
+    "acm_gpu_chars_tmp_bytes", "acm_gpu_chars_records_device", "acm_gpu_chars_positions_device", "acm_gpu_scan_chars_tmp_bytes",
+    "acm_gpu_scan_chars_device", "acm_gpu_scan_chars_host", "acm_scan_chars",
+]
+ACM_CHARS_CODEPOINTS, ACM_CHARS_UTF16 = 1, 2
+ACM_CHARS_EDGE_START, ACM_CHARS_EDGE_END, ACM_CHARS_EDGE_BAD = 1, 2, 4
+# what Machine.scan_str returns: a match in the indices of the str itself
+STR_MATCH_DTYPE = np.dtype([("start", "<u8"), ("stop", "<u8"), ("keyword_id", "<u4"), ("edge", "u1")])
+
 
 def lib():
     """Loads the native library; raises (never falls back) when it has not been built."""
@@ -704,6 +715,30 @@ def lib():
     L.acm_gpu_scan_flows_host.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]
     L.acm_scan_from.restype = i32
     L.acm_scan_from.argtypes = [vp, C.POINTER(vp), vp, u64, vp, u64, C.POINTER(u64)]
+    L.acm_chars_positions.restype = i32
+    L.acm_chars_positions.argtypes = [vp, u64, vp, u64, u32, vp, u64, vp]
+    L.acm_chars_records.restype = i32
+    L.acm_chars_records.argtypes = [vp, u64, u64, vp, u64, u32, vp, u64, vp, vp, vp]
+    L.acm_gpu_chars_ruler_bytes.restype = sz
+    L.acm_gpu_chars_ruler_bytes.argtypes = [vp, u64]
+    L.acm_gpu_chars_ruler_tmp_bytes.restype = sz
+    L.acm_gpu_chars_ruler_tmp_bytes.argtypes = [vp, u64]
+    L.acm_gpu_chars_ruler_device.restype = i32
+    L.acm_gpu_chars_ruler_device.argtypes = [vp, vp, u64, vp, sz, vp, sz, vp]
+    L.acm_gpu_chars_tmp_bytes.restype = sz
+    L.acm_gpu_chars_tmp_bytes.argtypes = [vp, u64, u64]
+    L.acm_gpu_chars_records_device.restype = i32
+    L.acm_gpu_chars_records_device.argtypes = [vp, vp, u64, u64, vp, u64, u32, vp, vp, u64, vp, vp, vp, vp, vp, sz, vp]
+    L.acm_gpu_chars_positions_device.restype = i32
+    L.acm_gpu_chars_positions_device.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_chars_tmp_bytes.restype = sz
+    L.acm_gpu_scan_chars_tmp_bytes.argtypes = [vp, u64, u64, u64]
+    L.acm_gpu_scan_chars_device.restype = i32
+    L.acm_gpu_scan_chars_device.argtypes = [vp, vp, u64, u64, vp, u64, u32, vp, vp, vp, vp, u64, vp, vp, sz, vp]
+    L.acm_gpu_scan_chars_host.restype = i32
+    L.acm_gpu_scan_chars_host.argtypes = [vp, vp, u64, u64, vp, u64, u32, vp, vp, vp, vp, u64, C.POINTER(u64)]
+    L.acm_scan_chars.restype = i32
+    L.acm_scan_chars.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp, u64, C.POINTER(u64)]
     L.acm_gpu_synth_text.restype = i32
     L.acm_gpu_synth_text.argtypes = [i32, vp, u64, u64, u32, u32, vp, vp, u32, vp]
     _lib = L
@@ -2277,6 +2312,50 @@ def words_records(text, records, offsets=None, ranges=ASCII_WORD, flags="both", 
     return a[:n.value]
 
 
+_CHARS_UNITS = {"codepoints": ACM_CHARS_CODEPOINTS, "utf16": ACM_CHARS_UTF16, "utf-16": ACM_CHARS_UTF16}
+
+
+def _chars_unit(unit):
+    return _CHARS_UNITS[unit] if isinstance(unit, str) else int(unit)
+
+
+def chars_positions(text, positions, offsets=None, unit="codepoints"):
+    """acm_chars_positions(): the byte positions `positions` (0 .. len(text)) of the UTF-8 bytes `text` (bytes or a
+    uint8 array) in code points ("codepoints") or UTF-16 code units ("utf16"), counted from the beginning of the
+    text that holds each -- `offsets` (n_texts + 1 entries) cuts the buffer into texts --, by the sequential
+    definition on the host.  Returns a np.uint64 array."""
+    t = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    p = np.ascontiguousarray(positions, dtype=np.uint64).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+    out = np.zeros(p.size, np.uint64)
+    _check(lib().acm_chars_positions(_ptr(t), t.size, *_cut(off), _chars_unit(unit), _ptr(p), p.size, _ptr(out)), "acm_chars_positions")
+    return out
+
+
+def chars_records(text, records, offsets=None, unit="codepoints", pos_base=0):
+    """acm_chars_records(): where every record of `records` (RECORD_DTYPE, any order) over the UTF-8 bytes `text`
+    lies in code points or UTF-16 code units (see chars_positions), by the sequential definition on the host.
+    Returns (char_start, char_len, edge): np.uint64, np.uint32 and np.uint8 arrays, one entry per record;
+    edge 0 says that the record begins and ends between characters (include/acm_chars.h)."""
+    t = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, dtype=np.uint8)
+    a = np.ascontiguousarray(records, dtype=RECORD_DTYPE).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+    start, length, edge = np.zeros(a.size, np.uint64), np.zeros(a.size, np.uint32), np.zeros(a.size, np.uint8)
+    _check(lib().acm_chars_records(_ptr(t), t.size, int(pos_base), *_cut(off), _chars_unit(unit), _ptr(a), a.size, start.ctypes.data,
+                                   length.ctypes.data, edge.ctypes.data), "acm_chars_records")
+    return start, length, edge
+
+
+def _chars_host_call(fn, what, before, cap, fixed):
+    """fn(*before, records, char_start, char_len, edge, cap, n) in the room loop: (records, char_start, char_len, edge)"""
+    def call(cap):
+        out = (np.zeros(cap, dtype=RECORD_DTYPE), np.zeros(cap, np.uint64), np.zeros(cap, np.uint32), np.zeros(cap, np.uint8))
+        n = C.c_uint64(0)
+        return fn(*before, *[a.ctypes.data for a in out], cap, C.byref(n)), n.value, out
+    out, n, _ = _room_call(call, what, cap, fixed)
+    return tuple(a[:n] for a in out)
+
+
 class Snippets:
     """What the context calls return: the text around the matches, packed.  out (the snippets side by
     side, in the text's own symbols), out_offsets (n_snippets + 1 offsets into `out`), snip_lo (the
@@ -2831,6 +2910,27 @@ class Machine(_Owner):
         r, nr = _word_ranges(ranges, self.sym_size)
         return _records_host_call(self.L.acm_scan_words, "acm_scan_words", (self.handle, t.ctypes.data, n_sym, r.ctypes.data, nr, _word_flags(flags)),
                                   int(capacity) if capacity is not None else max(1024, t.size // 64), capacity is not None)
+
+    def scan_chars(self, text, unit="codepoints", capacity=None):
+        """acm_scan_chars(): the matches of the UTF-8 bytes `text` in canonical order and where each lies in code
+        points ("codepoints") or UTF-16 code units ("utf16"): (records, char_start, char_len, edge), see
+        chars_records.  `capacity` must hold ALL matches; by default an overflow is repeated once with the size the
+        call reports."""
+        t, n_sym = self._text(text)
+        return _chars_host_call(self.L.acm_scan_chars, "acm_scan_chars", (self.handle, t.ctypes.data, n_sym, _chars_unit(unit)),
+                                int(capacity) if capacity is not None else max(1024, t.size // 64), capacity is not None)
+
+    def scan_str(self, s, unit="codepoints"):
+        """The matches of the keywords (UTF-8 bytes) in the str `s`, in the indices of `s` itself: a structured array
+        (start, stop, keyword_id, edge) in canonical order, s[start:stop] the match when edge is 0 -- "codepoints"
+        for a Python str, "utf16" for the strings of Java, JavaScript and the Language Server Protocol.  edge != 0
+        marks a match of bytes that begins or ends inside a character (include/acm_chars.h)."""
+        if self.sym_size != 1:
+            raise ValueError("scan_str needs a machine over bytes (sym_size 1), not %r" % (self.sym_size,))
+        rec, start, length, edge = self.scan_chars(s.encode("utf-8"), unit)
+        out = np.zeros(rec.size, STR_MATCH_DTYPE)
+        out["start"], out["stop"], out["keyword_id"], out["edge"] = start, start + length, rec["keyword_id"], edge
+        return out
 
     def context(self, text, before=0, after=0, merge=True, capacity=None, gather=True, out_capacity=None):
         """acm_context(): the matches of `text` with `before` symbols in front of and `after` behind each
@@ -4290,6 +4390,89 @@ class Plan(_Owner):
         return _records_host_call(lib().acm_gpu_scan_words_host, "acm_gpu_scan_words_host",
                                   (self.h, _ptr(t), n_sym, pos_base, *_cut(off), r.ctypes.data, nr, _word_flags(flags)),
                                   int(capacity) if capacity is not None else max(1024, n_sym // 64), capacity is not None)
+
+    def chars_ruler(self, text, n_symbols=None, ruler=None, tmp=None):
+        """acm_gpu_chars_ruler_device(): the rank structure of the UTF-8 bytes `text` (a device tensor) that
+        chars_records and chars_positions read, queued on the current stream.  It belongs to `text` as it lies: hand
+        the same tensor to those calls.  Returns the ruler (a uint8 device tensor; `ruler`: an earlier one to build in)."""
+        import torch
+        n_symbols = self._text_args(text, n_symbols)
+        rb = lib().acm_gpu_chars_ruler_bytes(self.h, n_symbols)
+        if not rb:
+            raise ACMError(ACM_GPU_E_ARG, "acm_gpu_chars_ruler_bytes")
+        if ruler is None or ruler.numel() < rb:
+            ruler = torch.empty(rb, dtype=torch.uint8, device=text.device)
+        tmp = _scratch(lib().acm_gpu_chars_ruler_tmp_bytes(self.h, n_symbols), text.device, tmp)
+        _check(lib().acm_gpu_chars_ruler_device(self.h, _opt_full(text), n_symbols, ruler.data_ptr(), ruler.numel(), tmp.data_ptr(), tmp.numel(),
+                                                self._stream()), "acm_gpu_chars_ruler_device")
+        return ruler
+
+    def chars_records(self, text, ruler, records, n, offsets=None, unit="codepoints", pos_base=0, n_symbols=None, count=None, char_start=None,
+                      char_len=None, edge=None):
+        """acm_gpu_chars_records_device(): where records[:n] (an int64 [capacity, 2] device tensor, any order) over
+        `text` lie in code points or UTF-16 code units (see chars_records), by `ruler` (chars_ruler(text)), queued on the
+        current stream.  `count` (a device int64 tensor) gives the number of records on the device: n is the room
+        then.  Returns (char_start int64, char_len int32, edge uint8) device tensors, one entry per record.  Nothing is
+        synchronised."""
+        import torch
+        n_symbols = self._text_args(text, n_symbols)
+        assert records.is_cuda and records.is_contiguous() and records.dtype == torch.int64 and records.shape[0] >= int(n)
+        n, dev = int(n), records.device
+        char_start = char_start if char_start is not None else torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        char_len = char_len if char_len is not None else torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        edge = edge if edge is not None else torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        off_ptr, n_texts = _cut(offsets)
+        tmp = _scratch(lib().acm_gpu_chars_tmp_bytes(self.h, n, n_texts), dev)
+        _check(lib().acm_gpu_chars_records_device(self.h, _opt_full(text), n_symbols, pos_base, off_ptr, n_texts, _chars_unit(unit), ruler.data_ptr(),
+                                                  records.data_ptr(), n, _opt(count), char_start.data_ptr(), char_len.data_ptr(), edge.data_ptr(),
+                                                  tmp.data_ptr(), tmp.numel(), self._stream()), "acm_gpu_chars_records_device")
+        return char_start, char_len, edge
+
+    def chars_positions(self, text, ruler, positions, offsets=None, unit="codepoints", n_symbols=None, out=None):
+        """acm_gpu_chars_positions_device(): the byte positions `positions` (a device int64 tensor, 0 .. n_symbols) in
+        code points or UTF-16 code units from the beginning of their text, by `ruler`, queued on the current stream:
+        the way the outputs of the other families (a selection's records, token places, snippet bounds) reach the
+        caller's units through one ruler.  Returns `out`, a device int64 tensor."""
+        import torch
+        n_symbols = self._text_args(text, n_symbols)
+        assert positions.is_cuda and positions.is_contiguous() and positions.dtype == torch.int64
+        n = positions.numel()
+        if out is None:
+            out = torch.empty(max(n, 1), dtype=torch.int64, device=positions.device)
+        off_ptr, n_texts = _cut(offsets)
+        tmp = _scratch(lib().acm_gpu_chars_tmp_bytes(self.h, n, n_texts), positions.device)
+        _check(lib().acm_gpu_chars_positions_device(self.h, _opt_full(text), n_symbols, off_ptr, n_texts, _chars_unit(unit), ruler.data_ptr(),
+                                                    _opt_full(positions), n, out.data_ptr(), tmp.data_ptr(), tmp.numel(), self._stream()),
+               "acm_gpu_chars_positions_device")
+        return out
+
+    def scan_chars(self, text, offsets=None, unit="codepoints", n_symbols=None, pos_base=0, capacity=None, records=None, count=None, tmp=None):
+        """acm_gpu_scan_chars_device(): the ordered scan of a device tensor of UTF-8 bytes, its ruler and the map of
+        its records, queued on the current stream.  Returns (records, char_start, char_len, edge, count, tmp):
+        their first `count` entries count when count <= capacity; a greater count is the number of ALL matches, the
+        capacity the call needs."""
+        import torch
+        n_symbols = self._text_args(text, n_symbols)
+        records, count = self._records_out(records, count, capacity, n_symbols, text.device)
+        cap, dev = records.shape[0], text.device
+        char_start = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        char_len = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        edge = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        off_ptr, n_texts = _cut(offsets)
+        tmp = _scratch(lib().acm_gpu_scan_chars_tmp_bytes(self.h, cap, n_symbols, n_texts), dev, tmp)
+        _check(lib().acm_gpu_scan_chars_device(self.h, _opt_full(text), n_symbols, pos_base, off_ptr, n_texts, _chars_unit(unit), records.data_ptr(),
+                                               char_start.data_ptr(), char_len.data_ptr(), edge.data_ptr(), cap, count.data_ptr(), tmp.data_ptr(),
+                                               tmp.numel(), self._stream()), "acm_gpu_scan_chars_device")
+        return records, char_start, char_len, edge, count, tmp
+
+    def scan_chars_host(self, text, offsets=None, unit="codepoints", pos_base=0, capacity=None):
+        """acm_gpu_scan_chars_host(): numpy in, (records, char_start, char_len, edge) out, through the C ABI only (no
+        torch); an overflow is repeated once with the size the call reports."""
+        t = np.frombuffer(bytes(text), np.uint8) if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text)
+        n_sym = t.size * t.itemsize // self.sym_size
+        off = np.ascontiguousarray(offsets, dtype=np.uint64) if offsets is not None else None
+        return _chars_host_call(lib().acm_gpu_scan_chars_host, "acm_gpu_scan_chars_host", (self.h, _ptr(t), n_sym, pos_base, *_cut(off), _chars_unit(unit)),
+                                int(capacity) if capacity is not None else max(1024, n_sym // 64), capacity is not None)
 
     def _context_outputs(self, text, room, n_symbols, gather, out, out_capacity):
         """the device outputs of the context calls: (snip_lo, out_offsets, snip_text, rec_snip, rec_at, res, out, out_capacity);

@@ -7121,6 +7121,277 @@ acm_gpu_scan_words_host (ACMPlan *plan, const void *text, uint64_t n_symbols, ui
   return download_records (rc, d_count, d_rec, records, capacity, n_found);
 }
 
+/* ------------------------------------------------------------------ positions in code points and UTF-16 units (include/acm_chars.h, dev_chars.h)
+ * The ruler: one pass over the text, two prefix sums over the tiles.  The maps: the check of offsets[], a lane per
+ * record or position.  The plan gives its device, its caller symbol size (1) and its grid cap, nothing else. */
+namespace {
+/* where a ruler's arrays lie, for the most words a text of this size can touch (15 bytes off the grid); n_tiles is
+ * that of the text's own address mod 16, `mis` */
+struct CharsLayout {
+  CharsHead H;
+  uint64_t n_words = 0, most_tiles = 0;
+  size_t bytes = 0;
+};
+CharsLayout
+chars_layout (uint64_t n_symbols, uint32_t mis) {
+  CharsLayout L;
+  /* ACM_GPU_CHARS_TILE=<bytes of text>: the ruler pass's tile, a multiple of 256; ACM_GPU_CHARS_CHUNK=64, 128 or 256 (experiments) */
+  uint32_t tile = tunable ("ACM_GPU_CHARS_TILE", CHARS_TILE_DEFAULT, CHARS_TILE_MIN, CHARS_TILE_MAX, Tune::Mult16);
+  if (tile % 256)
+    tile = CHARS_TILE_DEFAULT;
+  const uint32_t chunk = tunable ("ACM_GPU_CHARS_CHUNK", CHARS_CHUNK_DEFAULT, CHARS_CHUNK_MIN, CHARS_CHUNK_MAX, Tune::Pow2);
+  const uint64_t most_words = (n_symbols + 30) / 16;
+  L.n_words = (n_symbols + mis + 15) / 16;
+  L.most_tiles = (most_words * 16 + tile - 1) / tile;
+  L.H = CharsHead{};
+  L.H.magic = CHARS_MAGIC;
+  L.H.chunk_log2 = chunk == 64 ? 6 : chunk == 128 ? 7 : 8;
+  L.H.mis = mis;
+  L.H.tile_words = tile / 16;
+  L.H.n_symbols = n_symbols;
+  L.H.n_tiles = (L.n_words * 16 + tile - 1) / tile;
+  Carve c;
+  c.take<CharsHead> (1);
+  L.H.starts_at = c.boundary ();
+  c.take<long long> (L.most_tiles + 1);
+  L.H.wides_at = c.boundary ();
+  c.take<long long> (L.most_tiles + 1);
+  L.H.entry_at = c.boundary ();
+  c.take<uint2> ((most_words * 16 + chunk - 1) / chunk + 1);
+  L.bytes = c.total ();
+  return L;
+}
+
+/* what the ruler pass derives beside the ruler: the tiles' totals as the sums take them, hipCUB's room */
+struct CharsRulerRoom {
+  long long *starts = nullptr, *wides = nullptr;
+  CubRoom cub;
+};
+CharsRulerRoom
+chars_ruler_carve (Carve &c, const CharsLayout &L) {
+  CharsRulerRoom R;
+  R.starts = c.take<long long> (L.most_tiles + 1);
+  R.wides = c.take<long long> (L.most_tiles + 1);
+  R.cub = cub_room (c, 0, L.most_tiles + 1);
+  return R;
+}
+
+/* a byte plan and a text whose tiles the sums can count */
+bool
+chars_size_ok (const ACMPlan *plan, uint64_t n_symbols) {
+  return plan && plan->text_sym_bytes == 1 && n_symbols < (1ull << 38);
+}
+
+bool
+chars_unit_ok (uint32_t unit) {
+  return unit == ACM_CHARS_CODEPOINTS || unit == ACM_CHARS_UTF16;
+}
+
+/* what the two maps share: the checks, the scratch, the check of offsets[] */
+int
+chars_map_begin (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint32_t unit, const void *d_ruler,
+                 uint64_t n, void *d_tmp, size_t tmp_bytes, hipStream_t st, CharsMapK &K) {
+  if (!chars_size_ok (plan, n_symbols) || !chars_unit_ok (unit) || n >= (1ull << 31) || (n_symbols && !d_text) || !d_ruler ||
+      reinterpret_cast<uintptr_t> (d_ruler) % 16 || (n && !d_tmp) || (d_offsets && (n_texts >= (1ull << 31) || (n_texts == 0 && n_symbols))))
+    return ACM_GPU_E_ARG;
+  if (n == 0) /* (no room: nothing to write) */
+    return ACM_GPU_OK;
+  Carve carve (d_tmp);
+  K.ctl = carve.take<CharsCtl> (1);
+  if (tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  K.text = static_cast<const unsigned char *> (d_text);
+  K.n_symbols = n_symbols;
+  K.mis = (uint32_t)(reinterpret_cast<uintptr_t> (d_text) & 15);
+  K.utf16 = unit == ACM_CHARS_UTF16;
+  K.offsets = n_texts ? d_offsets : nullptr; /* (no text: no symbol, one empty text) */
+  K.n_texts = n_texts;
+  K.ruler = static_cast<const unsigned char *> (d_ruler);
+  K.capacity = n;
+  K.error = error_word (plan);
+  HIP_TRY (hipMemsetAsync (K.ctl, 0, sizeof (CharsCtl), st));
+  if (K.offsets) /* one size, whatever the number of texts */
+    HIP_TRY (launch (offsets_check_kernel, capped_grid (plan, (n_texts + CHARS_THREADS - 1) / CHARS_THREADS), dim3 (CHARS_THREADS), 0, st, K.offsets, K.n_texts,
+                     K.n_symbols, &K.ctl->bad, K.error));
+  return ACM_GPU_OK;
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_chars_ruler_bytes (const ACMPlan *plan, uint64_t n_symbols) {
+  return chars_size_ok (plan, n_symbols) ? chars_layout (n_symbols, 15).bytes : 0;
+}
+
+extern "C" size_t
+acm_gpu_chars_ruler_tmp_bytes (const ACMPlan *plan, uint64_t n_symbols) {
+  if (!chars_size_ok (plan, n_symbols))
+    return 0;
+  Carve c;
+  chars_ruler_carve (c, chars_layout (n_symbols, 15));
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_chars_ruler_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, void *d_ruler, size_t ruler_bytes, void *d_tmp, size_t tmp_bytes,
+                            void *stream) {
+  if (!chars_size_ok (plan, n_symbols) || (n_symbols && !d_text) || !d_ruler || reinterpret_cast<uintptr_t> (d_ruler) % 16 || !d_tmp)
+    return ACM_GPU_E_ARG;
+  const CharsLayout L = chars_layout (n_symbols, (uint32_t)(reinterpret_cast<uintptr_t> (d_text) & 15));
+  Carve carve (d_tmp);
+  const CharsRulerRoom R = chars_ruler_carve (carve, L);
+  if (ruler_bytes < L.bytes || tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  HIP_TRY (hipSetDevice (plan->device));
+  unsigned char *ruler = static_cast<unsigned char *> (d_ruler);
+  CharsRulerK K{};
+  K.text = static_cast<const unsigned char *> (d_text);
+  K.H = L.H;
+  K.n_words = L.n_words;
+  K.tile_starts = reinterpret_cast<unsigned long long *> (R.starts);
+  K.tile_wides = reinterpret_cast<unsigned long long *> (R.wides);
+  K.entry = reinterpret_cast<uint2 *> (ruler + L.H.entry_at);
+  K.head = reinterpret_cast<CharsHead *> (ruler);
+  HIP_TRY (launch (chars_ruler_kernel, capped_grid (plan, L.H.n_tiles + 1), dim3 (CHARS_THREADS), 0, st, K));
+  HIP_TRY (exclusive_sum (R.cub, R.starts, reinterpret_cast<long long *> (ruler + L.H.starts_at), L.H.n_tiles + 1, st));
+  HIP_TRY (exclusive_sum (R.cub, R.wides, reinterpret_cast<long long *> (ruler + L.H.wides_at), L.H.n_tiles + 1, st));
+  return ACM_GPU_OK;
+}
+
+extern "C" size_t
+acm_gpu_chars_tmp_bytes (const ACMPlan *plan, uint64_t n_or_capacity, uint64_t n_texts) {
+  (void)n_texts; /* (nothing here is sized by the number of texts: a record's text is a bisection of offsets[]) */
+  if (!plan || plan->text_sym_bytes != 1 || n_or_capacity >= (1ull << 31))
+    return 0;
+  Carve c;
+  c.take<CharsCtl> (1);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_chars_records_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts,
+                              uint32_t unit, const void *d_ruler, const ACMRecord *d_records, uint64_t n, const uint64_t *d_n, uint64_t *d_char_start,
+                              uint32_t *d_char_len, uint8_t *d_edge, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if ((!d_char_start && !d_char_len && !d_edge) || (n && !d_records))
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  CharsMapK K{};
+  const int rc = chars_map_begin (plan, d_text, n_symbols, d_offsets, n_texts, unit, d_ruler, n, d_tmp, tmp_bytes, st, K);
+  if (rc || n == 0) /* (no room: nothing to write) */
+    return rc;
+  K.pos_base = pos_base;
+  K.in = d_records;
+  K.n_dev = reinterpret_cast<const unsigned long long *> (d_n);
+  K.char_start = reinterpret_cast<unsigned long long *> (d_char_start);
+  K.char_len = d_char_len;
+  K.edge = d_edge;
+  HIP_TRY (launch (chars_records_kernel, capped_grid (plan, (n + CHARS_THREADS - 1) / CHARS_THREADS), dim3 (CHARS_THREADS), 0, st, K));
+  return ACM_GPU_OK;
+}
+
+extern "C" int
+acm_gpu_chars_positions_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, const uint64_t *d_offsets, uint64_t n_texts, uint32_t unit,
+                                const void *d_ruler, const uint64_t *d_pos, uint64_t n, uint64_t *d_out, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (n && (!d_pos || !d_out))
+    return ACM_GPU_E_ARG;
+  hipStream_t st = static_cast<hipStream_t> (stream);
+  CharsMapK K{};
+  const int rc = chars_map_begin (plan, d_text, n_symbols, d_offsets, n_texts, unit, d_ruler, n, d_tmp, tmp_bytes, st, K);
+  if (rc || n == 0)
+    return rc;
+  K.pos = reinterpret_cast<const unsigned long long *> (d_pos);
+  K.out = reinterpret_cast<unsigned long long *> (d_out);
+  HIP_TRY (launch (chars_positions_kernel, capped_grid (plan, (n + CHARS_THREADS - 1) / CHARS_THREADS), dim3 (CHARS_THREADS), 0, st, K));
+  return ACM_GPU_OK;
+}
+
+namespace {
+/* the scratch of acm_gpu_scan_chars_device: the ruler, then the room the scan, the ruler pass and the map share (each
+ * has ended when the next begins) */
+struct ScanCharsRoom {
+  unsigned char *ruler = nullptr, *work = nullptr;
+  size_t ruler_bytes = 0, work_bytes = 0;
+};
+ScanCharsRoom
+scan_chars_carve (Carve &c, const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  ScanCharsRoom R;
+  R.ruler_bytes = acm_gpu_chars_ruler_bytes (plan, n_symbols);
+  R.work_bytes = std::max (acm_gpu_scan_ordered_tmp_bytes (plan, capacity, n_symbols),
+                           std::max (acm_gpu_chars_ruler_tmp_bytes (plan, n_symbols), acm_gpu_chars_tmp_bytes (plan, capacity, n_texts)));
+  R.ruler = c.take (R.ruler_bytes);
+  R.work = c.take (R.work_bytes);
+  return R;
+}
+} // namespace
+
+extern "C" size_t
+acm_gpu_scan_chars_tmp_bytes (const ACMPlan *plan, uint64_t capacity, uint64_t n_symbols, uint64_t n_texts) {
+  if (!chars_size_ok (plan, n_symbols) || capacity >= (1ull << 31))
+    return 0;
+  Carve c;
+  scan_chars_carve (c, plan, capacity, n_symbols, n_texts);
+  return c.total ();
+}
+
+extern "C" int
+acm_gpu_scan_chars_device (ACMPlan *plan, const void *d_text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *d_offsets, uint64_t n_texts,
+                           uint32_t unit, ACMRecord *d_records, uint64_t *d_char_start, uint32_t *d_char_len, uint8_t *d_edge, uint64_t capacity,
+                           uint64_t *d_count, void *d_tmp, size_t tmp_bytes, void *stream) {
+  if (!chars_size_ok (plan, n_symbols) || !chars_unit_ok (unit) || !d_count || capacity >= (1ull << 31) || (n_symbols && !d_text) ||
+      (capacity && (!d_records || !d_tmp)) || (!d_char_start && !d_char_len && !d_edge))
+    return ACM_GPU_E_ARG;
+  Carve carve (capacity ? d_tmp : nullptr); /* (no room: nothing is bound) */
+  const ScanCharsRoom L = scan_chars_carve (carve, plan, capacity, n_symbols, n_texts);
+  if (capacity && tmp_bytes < carve.total ())
+    return ACM_GPU_E_ARG;
+  int rc = acm_gpu_scan_ordered_device (plan, d_text, n_symbols, 0, pos_base, d_records, capacity, d_count, L.work, L.work_bytes, stream);
+  if (rc || capacity == 0) /* (no room: *d_count says what the records need) */
+    return rc;
+  rc = acm_gpu_chars_ruler_device (plan, d_text, n_symbols, L.ruler, L.ruler_bytes, L.work, L.work_bytes, stream);
+  if (rc)
+    return rc;
+  return acm_gpu_chars_records_device (plan, d_text, n_symbols, pos_base, d_offsets, n_texts, unit, L.ruler, d_records, capacity, d_count, d_char_start,
+                                       d_char_len, d_edge, L.work, L.work_bytes, stream);
+}
+
+extern "C" int
+acm_gpu_scan_chars_host (ACMPlan *plan, const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts, uint32_t unit,
+                         ACMRecord *records, uint64_t *char_start, uint32_t *char_len, uint8_t *edge, uint64_t capacity, uint64_t *n_found) {
+  if (!chars_size_ok (plan, n_symbols) || !chars_unit_ok (unit) || !n_found || capacity >= (1ull << 31) || (n_symbols && !text) ||
+      (capacity && !records) || (!char_start && !char_len && !edge) || !optional_offsets_ok (offsets, n_texts, n_symbols))
+    return ACM_GPU_E_ARG;
+  HIP_TRY (hipSetDevice (plan->device));
+  const size_t tmp_bytes = acm_gpu_scan_chars_tmp_bytes (plan, capacity, n_symbols, n_texts);
+  DeviceTemps temps;
+  void *d_text = nullptr, *d_tmp = nullptr;
+  uint64_t *d_count = nullptr, *d_off = nullptr, *d_start = nullptr;
+  uint32_t *d_len = nullptr;
+  uint8_t *d_edge = nullptr;
+  ACMRecord *d_rec = nullptr;
+  HOST_TRY (upload_text (temps, plan, text, n_symbols, &d_text));
+  HOST_TRY (temps.get (&d_count, 8));
+  HOST_TRY (temps.get (&d_rec, capacity * 16));
+  HOST_TRY (temps.get (&d_start, capacity * 8));
+  HOST_TRY (temps.get (&d_len, capacity * 4));
+  HOST_TRY (temps.get (&d_edge, capacity));
+  HOST_TRY (temps.get (&d_tmp, tmp_bytes));
+  if (offsets)
+    HOST_TRY (upload_offsets (temps, offsets, n_texts, &d_off));
+  int rc = acm_gpu_scan_chars_device (plan, d_text, n_symbols, pos_base, d_off, n_texts, unit, d_rec, d_start, d_len, d_edge, capacity, d_count, d_tmp,
+                                      tmp_bytes, nullptr);
+  rc = download_records (rc, d_count, d_rec, records, capacity, n_found);
+  if (rc || *n_found == 0)
+    return rc;
+  if (char_start)
+    HOST_TRY (hipMemcpy (char_start, d_start, *n_found * 8, hipMemcpyDeviceToHost));
+  if (char_len)
+    HOST_TRY (hipMemcpy (char_len, d_len, *n_found * 4, hipMemcpyDeviceToHost));
+  if (edge)
+    HOST_TRY (hipMemcpy (edge, d_edge, *n_found, hipMemcpyDeviceToHost));
+  return ACM_GPU_OK;
+}
+
 /* ------------------------------------------------------------------ match contexts (include/acm_gpu.h, dev_context.h)
  * Records into windows, windows into snippets, snippets into one packed output: the check of
  * offsets[], the window pass, under MERGE the carries over the tiles and the flag pass, the prefix
@@ -9539,7 +9810,7 @@ route_plan (ACMachine *machine, ScanRoute *R) {
 namespace {
 /* when a call leaves its route in acm_scan_path.  The calls differ, and each keeps its own rule
  * here: acm_scan and acm_scan_batch record whatever their scan returned, acm_tally and acm_lookup only a scan that
- * succeeded, acm_select, acm_scan_words, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
+ * succeeded, acm_select, acm_scan_words, acm_scan_chars, acm_scan_anchored and acm_scan_from also one that found more records than there was room for,
  * acm_replace, acm_tokenize, acm_grep, acm_grep_lines, acm_tally_batch, acm_rules, acm_score, acm_index, acm_scan_patterns, acm_scan_chains, acm_scan_approx and
  * acm_scan_edit also one whose output had no room, acm_context either of the two. */
 enum class RecordPath { Always, OnSuccess, OnSuccessOrOverflow };
@@ -9567,7 +9838,7 @@ routed_scan (ACMachine *machine, RecordPath record, HostLoop host_loop, OnGpu on
 }
 } // namespace
 
-/* The twenty-one calls below run on the same route, the same cached plan, under the same lock. */
+/* The twenty-two calls below run on the same route, the same cached plan, under the same lock. */
 extern "C" int
 acm_scan (ACMachine *machine, const void *text, uint64_t n_symbols, ACMRecord *records, uint64_t capacity, uint64_t *n_found) {
   if (!machine || !n_found)
@@ -9634,6 +9905,20 @@ acm_scan_words (ACMachine *machine, const void *text, uint64_t n_symbols, const 
     machine, RecordPath::OnSuccessOrOverflow,
     [&] (uint32_t said) { return acm_internal_cpu_scan_words (machine, text, n_symbols, said, ranges, n_ranges, flags, records, capacity, n_found); },
     [&] (ACMPlan *plan) { return acm_gpu_scan_words_host (plan, text, n_symbols, 0, nullptr, 0, ranges, n_ranges, flags, records, capacity, n_found); });
+}
+
+/* the matches of one byte text with their places in code points or UTF-16 units (include/acm_chars.h) */
+extern "C" int
+acm_scan_chars (ACMachine *machine, const void *text, uint64_t n_symbols, uint32_t unit, ACMRecord *records, uint64_t *char_start, uint32_t *char_len,
+                uint8_t *edge, uint64_t capacity, uint64_t *n_found) {
+  if (!machine || !n_found || (n_symbols && !text) || (capacity && !records) || !chars_unit_ok (unit) || (!char_start && !char_len && !edge))
+    return ACM_GPU_E_ARG;
+  return routed_scan (
+    machine, RecordPath::OnSuccessOrOverflow,
+    [&] (uint32_t said) { return acm_internal_cpu_scan_chars (machine, text, n_symbols, said, unit, records, char_start, char_len, edge, capacity, n_found); },
+    [&] (ACMPlan *plan) {
+      return acm_gpu_scan_chars_host (plan, text, n_symbols, 0, nullptr, 0, unit, records, char_start, char_len, edge, capacity, n_found);
+    });
 }
 
 /* the matches of one text with the text around them (include/acm_gpu.h) */

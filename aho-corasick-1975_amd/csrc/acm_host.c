@@ -1720,6 +1720,133 @@ acm_internal_cpu_scan_words (ACMachine *m, const void *text, uint64_t n_symbols,
   return acm_words_records (text, n_symbols, sym_bytes, 0, NULL, 0, ranges, n_ranges, flags, records, *n_found, n_found);
 }
 
+/* CHARS (include/acm_chars.h): byte positions and records in code points or UTF-16 units, the plain sequential
+ * definition.  Two prefix counts over the text -- non-continuation bytes and, under UTF16, wide leads -- and every
+ * answer is a difference of two of their entries.  Everything is checked first, so that nothing is written when the
+ * call fails. */
+struct chars_rank {
+  uint64_t *starts, *wides; /* [n_symbols + 1]; wides NULL under CODEPOINTS */
+};
+
+static int
+chars_offsets_ok (const uint64_t *offsets, uint64_t n_texts, uint64_t n_symbols) {
+  if (!offsets)
+    return 1;
+  if (offsets[0] != 0 || offsets[n_texts] != n_symbols)
+    return 0;
+  for (uint64_t t = 0; t < n_texts; t++)
+    if (offsets[t] > offsets[t + 1])
+      return 0;
+  return 1;
+}
+
+static int
+chars_rank_make (struct chars_rank *R, const unsigned char *text, uint64_t n_symbols, uint32_t unit) {
+  R->starts = malloc ((n_symbols + 1) * sizeof (uint64_t));
+  R->wides = unit == ACM_CHARS_UTF16 ? malloc ((n_symbols + 1) * sizeof (uint64_t)) : NULL;
+  if (!R->starts || (unit == ACM_CHARS_UTF16 && !R->wides)) {
+    free (R->starts), free (R->wides);
+    return ACM_GPU_E_NOMEM;
+  }
+  R->starts[0] = 0;
+  if (R->wides)
+    R->wides[0] = 0;
+  for (uint64_t i = 0; i < n_symbols; i++) {
+    R->starts[i + 1] = R->starts[i] + ((text[i] & 0xC0) != 0x80);
+    if (R->wides)
+      R->wides[i + 1] = R->wides[i] + (text[i] >= 0xF0);
+  }
+  return ACM_GPU_OK;
+}
+
+/* count (a, b), a <= b <= n_symbols */
+static uint64_t
+chars_count (const struct chars_rank *R, uint64_t a, uint64_t b) {
+  return R->starts[b] - R->starts[a] + (R->wides ? R->wides[b] - R->wides[a] : 0);
+}
+
+/* the largest text t with offsets[t] <= p (n_texts > 0) */
+static uint64_t
+chars_text_of (const uint64_t *offsets, uint64_t n_texts, uint64_t p) {
+  uint64_t lo = 0, hi = n_texts - 1;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo + 1) / 2;
+    if (offsets[mid] <= p)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  return lo;
+}
+
+int
+acm_chars_positions (const void *text, uint64_t n_symbols, const uint64_t *offsets, uint64_t n_texts, uint32_t unit, const uint64_t *pos, uint64_t n,
+                     uint64_t *out) {
+  if ((unit != ACM_CHARS_CODEPOINTS && unit != ACM_CHARS_UTF16) || (n_symbols && !text) || (n && (!pos || !out)) ||
+      !chars_offsets_ok (offsets, n_texts, n_symbols))
+    return ACM_GPU_E_ARG;
+  for (uint64_t i = 0; i < n; i++)
+    if (pos[i] > n_symbols)
+      return ACM_GPU_E_ARG;
+  struct chars_rank R;
+  const int rc = chars_rank_make (&R, text, n_symbols, unit);
+  if (rc)
+    return rc;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t lo = offsets && n_texts ? offsets[chars_text_of (offsets, n_texts, pos[i])] : 0;
+    out[i] = chars_count (&R, lo, pos[i]);
+  }
+  free (R.starts), free (R.wides);
+  return ACM_GPU_OK;
+}
+
+int
+acm_chars_records (const void *text, uint64_t n_symbols, uint64_t pos_base, const uint64_t *offsets, uint64_t n_texts, uint32_t unit,
+                   const ACMRecord *records, uint64_t n, uint64_t *char_start, uint32_t *char_len, uint8_t *edge) {
+  if ((unit != ACM_CHARS_CODEPOINTS && unit != ACM_CHARS_UTF16) || (n_symbols && !text) || (n && !records) || (!char_start && !char_len && !edge) ||
+      !chars_offsets_ok (offsets, n_texts, n_symbols))
+    return ACM_GPU_E_ARG;
+  for (uint64_t j = 0; j < n; j++)
+    if (record_breaks_contract (&records[j], pos_base, n_symbols))
+      return ACM_GPU_E_ARG;
+  struct chars_rank R;
+  const int rc = chars_rank_make (&R, text, n_symbols, unit);
+  if (rc)
+    return rc;
+  const unsigned char *t = text;
+  for (uint64_t j = 0; j < n; j++) {
+    const uint64_t e = records[j].end_pos - pos_base, s = e + 1 - records[j].length;
+    uint64_t lo = 0, hi = n_symbols; /* the text of s: [lo, hi) */
+    if (offsets && n_texts) {
+      const uint64_t tx = chars_text_of (offsets, n_texts, s);
+      lo = offsets[tx];
+      hi = offsets[tx + 1];
+    }
+    if (char_start)
+      char_start[j] = chars_count (&R, lo, s);
+    if (char_len)
+      char_len[j] = (uint32_t)chars_count (&R, s, e + 1);
+    if (edge) /* a boundary: lo, hi, the end of the buffer, or a byte that is no continuation */
+      edge[j] = (uint8_t)((s != lo && (t[s] & 0xC0) == 0x80 ? ACM_CHARS_EDGE_START : 0u) |
+                          (e + 1 != hi && e + 1 < n_symbols && (t[e + 1] & 0xC0) == 0x80 ? ACM_CHARS_EDGE_END : 0u));
+  }
+  free (R.starts), free (R.wides);
+  return ACM_GPU_OK;
+}
+
+/* acm_scan_chars on the host (include/acm_chars.h): the caller loop, then the sequential map of what it found -- what
+ * ACM_SCAN_PATH_CPU_LOOP runs.  The text is bytes. */
+int
+acm_internal_cpu_scan_chars (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint32_t unit, ACMRecord *records,
+                             uint64_t *char_start, uint32_t *char_len, uint8_t *edge, uint64_t capacity, uint64_t *n_found) {
+  if (!m || !n_found || sym_bytes != 1 || (unit != ACM_CHARS_CODEPOINTS && unit != ACM_CHARS_UTF16) || (!char_start && !char_len && !edge))
+    return ACM_GPU_E_ARG;
+  const int rc = acm_internal_cpu_scan (m, text, n_symbols, sym_bytes, records, capacity, n_found);
+  if (rc)
+    return rc;
+  return acm_chars_records (text, n_symbols, 0, NULL, 0, unit, records, *n_found, char_start, char_len, edge);
+}
+
 /* CONTEXT of a record set (include/acm_gpu.h): the plain sequential pass.  Everything is checked
  * and every window made first.  MERGE walks the records BACKWARDS: over the windowed records hi
  * never decreases, so a record joins the run behind it iff its hi reaches the smallest lo of that

@@ -104,6 +104,10 @@ int acm_internal_words_args_ok (uint32_t sym_bytes, const void *ranges, uint32_t
 /* acm_scan_words' host path: the caller loop, then acm_words_records over its records (arguments as acm_scan_words') */
 int acm_internal_cpu_scan_words (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, const void *ranges, uint32_t n_ranges,
                                  uint32_t flags, ACMRecord *records, uint64_t capacity, uint64_t *n_found);
+/* acm_scan_chars' host path: the caller loop, then acm_chars_records over its records (arguments as acm_scan_chars', the symbol size
+ * behind n_symbols: anything but 1 is ACM_GPU_E_ARG) */
+int acm_internal_cpu_scan_chars (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, uint32_t unit, ACMRecord *records,
+                                 uint64_t *char_start, uint32_t *char_len, uint8_t *edge, uint64_t capacity, uint64_t *n_found);
 /* acm_context's host path: the caller loop, then acm_context_records over its records (arguments as acm_context's, the symbol size
  * behind n_symbols; records NULL: a room of the call's own) */
 int acm_internal_cpu_context (ACMachine *m, const void *text, uint64_t n_symbols, uint32_t sym_bytes, ACMRecord *records, uint64_t capacity,

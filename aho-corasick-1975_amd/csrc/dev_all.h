@@ -248,9 +248,10 @@ join_postings (const JoinK &K, const uint32_t *post_ptr, uint32_t n_keywords, co
 #include "dev_score.h"
 #include "dev_index.h"
 #include "dev_cooccur.h"
+#include "dev_chars.h"
 
 static_assert (WORDS_THREADS == OFFSETS_CHECK_THREADS && CONTEXT_THREADS == OFFSETS_CHECK_THREADS && ANCHORED_THREADS == OFFSETS_CHECK_THREADS &&
-                 PATTERNS_THREADS == OFFSETS_CHECK_THREADS && APPROX_THREADS == OFFSETS_CHECK_THREADS,
+                 PATTERNS_THREADS == OFFSETS_CHECK_THREADS && APPROX_THREADS == OFFSETS_CHECK_THREADS && CHARS_THREADS == OFFSETS_CHECK_THREADS,
                "offsets_check_kernel is launched with the block of the family it checks for");
 
 } // namespace

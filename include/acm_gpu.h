@@ -2312,4 +2312,5 @@ int acm_gpu_synth_text (int device, void *d_text, uint64_t n, uint64_t global_be
 #include "acm_index.h"
 #include "acm_near.h"
 #include "acm_cooccur.h"
+#include "acm_chars.h"
 #include "acm_segment.h"
